@@ -10,11 +10,20 @@ barrier and the max-over-ranks time.  Default: weak scaling, `--batch` problems 
 splits T problems over the ranks (BASELINE config 4: `--strong --total 256 --nvar 1000 --ncon 10`).
 Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up, times `--steps` steps and prints the headline line (`value`, `ms_per_step`, ...).  Everything
+else — the roofline and kernel timings, the CPU baseline and the parity guard against the oracle, the other batches, layouts
+and configurations — runs with `--full`, which prints the long line and then a compact final line.  `--dump-outputs DIR` writes
+what the last timed step computed (rank 0's shard: a fixed sample of the solutions, every problem's rho / rho_old / nfact /
+success) as DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
+
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus 8 --steps 20 --warmup 3
 """
 import argparse
+import collections
+import concurrent.futures as cf
 import json
 import os
 import sys
@@ -74,6 +83,50 @@ def band_batch(s, B, seed):
     vals[:, off[4]:off[5]] = -1.0
     rhs = rng.normal(size=(B, s.N))
     return vals, rhs
+
+
+def band_chunks(s, g0, nloc, chunk=512):
+    """band_batch over problems [g0, g0 + nloc) of the job in chunks of `chunk` (seed 3000 + the chunk's first global problem),
+    generated on host threads (numpy releases the GIL in the RNG and the array passes) and yielded in order as (b0, vals, rhs);
+    at most a few chunks per thread are held at once"""
+    starts = iter(range(0, nloc, chunk))
+    nthr = max(1, min(16, len(os.sched_getaffinity(0)), -(-nloc // chunk)))
+    with cf.ThreadPoolExecutor(nthr) as ex:
+        pending = collections.deque()
+
+        def submit():
+            b0 = next(starts, None)
+            if b0 is not None:
+                pending.append((b0, ex.submit(band_batch, s, min(chunk, nloc - b0), 3000 + g0 + b0)))
+        for _ in range(nthr + 2):
+            submit()
+        while pending:
+            b0, fut = pending.popleft()
+            vh, rh = fut.result()
+            submit()
+            yield b0, vh, rh
+
+
+def dump_outputs(path, prob, nsample=128, seed=0):
+    """what the last timed step left for the caller of cnl_newton_system_dev, as float64 .npy files: d of a fixed, seeded sample of
+    the shard's problems and the rho slots of their `vals` (the step writes them when the problem climbs the ladder), and rho,
+    rho_old, nfact, success of every problem"""
+    torch, hipldl, s, B = prob.torch, prob.hipldl, prob.s, prob.B
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    pick = np.sort(np.random.default_rng(seed).choice(B, size=min(B, nsample), replace=False))
+    sel = torch.from_numpy(pick).to(prob.d.device)
+    slots = np.arange(s.nnzNS - s.nvar, s.nnzNS)
+    if prob.L.config.get("batch_layout"):
+        idx = hipldl.il_index(pick[:, None], slots[None, :], s.nnzNS)
+        rho_slots = prob.vin[torch.from_numpy(idx).to(prob.d.device)]
+    else:
+        rho_slots = prob.vin[sel][:, s.nnzNS - s.nvar:]
+    arrays = {"sample_problems": pick.astype(np.float64), "d": prob.d[sel].cpu().numpy(), "vals_rho_slots": rho_slots.cpu().numpy(),
+              "rho": prob.rho.cpu().numpy(), "rho_old": prob.rho_old.cpu().numpy(),
+              "nfact": prob.nfact.cpu().numpy().astype(np.float64), "success": prob.succ.cpu().numpy().astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def backward_error(s, rows, cols, vals, rhs, d):
@@ -219,8 +272,11 @@ def main():
     ap.add_argument("--total", type=int, default=256, help="total problems with --strong")
     ap.add_argument("--nvar", "--n", dest="n", type=int, default=10000, help="variables = residuals per problem (spelled --nvar under torch.distributed.run, whose own options make --n ambiguous)")
     ap.add_argument("--ncon", type=int, default=50)
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="problems timed on the CPU oracle (-1 auto, 0 off)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the small-batch, PCIe-inclusive, cfg2 and f1 blocks")
+    ap.add_argument("--full", action="store_true", help="beside the headline: roofline and kernel timings, CPU baseline and parity guard against "
+                                                        "the oracle, the other batches, layouts and configurations (long line + compact final line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (rank 0's shard) as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="with --full: problems timed on the CPU oracle (-1 auto, 0 off)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the small-batch, PCIe-inclusive, cfg2 and f1 blocks")
     ap.add_argument("--layout", choices=("interleaved", "problem-major"), default="interleaved",
                     help="layout of the device-resident `vals` of the headline handle: interleaved = cnl_options.batch_layout 1 (what row f2 writes on "
                          "such a handle; falls back to problem-major where the band kernels do not serve the handle), problem-major = the reference's "
@@ -230,6 +286,8 @@ def main():
                                                          "(the second front end of DESIGN section 6) instead of one process per GPU")
     args = ap.parse_args()
     if args.multi:
+        if args.dump_outputs:
+            ap.error("--dump-outputs: the one-process-per-GPU path only (not --multi)")
         return main_multi(args)
 
     import torch
@@ -264,10 +322,8 @@ def main():
         nloc = g1 - g0
         vals = torch.empty((nloc, s.nnzNS), dtype=torch.float64, device=dev)
         rhs = torch.empty((nloc, s.N), dtype=torch.float64, device=dev)
-        CH = 512
-        for b0 in range(0, nloc, CH):
-            nb = min(CH, nloc - b0)
-            vh, rh = band_batch(s, nb, seed=3000 + (g0 + b0))
+        for b0, vh, rh in band_chunks(s, g0, nloc):
+            nb = len(vh)
             vals[b0:b0 + nb].copy_(torch.from_numpy(vh))
             rhs[b0:b0 + nb].copy_(torch.from_numpy(rh))
             if b0 == 0:
@@ -295,6 +351,10 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, prob)
+    if not args.full:
+        return headline_only(args, prob, counts, elapsed, total, world, B, dist)
 
     LDLT = prob.L
     step_ms = prob.timed(min(10, max(2, args.steps)), 1)  # HIP events on the launch stream: the whole step of this rank
@@ -340,8 +400,6 @@ def main():
     d_h = prob.d[:nchk].cpu().numpy()
     berr = max(backward_error(s, rows, cols, vals_h[b], rhs_h[b], d_h[b]) for b in range(nchk))
 
-    systems = counts[0] * args.steps
-    value = systems / elapsed
     info = LDLT.info
     headline = (args.n, args.ncon) == (10000, 50)
     # B_alg = 12 nnzNS + 24 N + 32 nnz(L*), nnz(L*) = min(fill of the build's own ordering WITHOUT the
@@ -359,19 +417,9 @@ def main():
     # backward sweep) — per pivot 15 doubles read + 6 written forward, 13 read + 2 written backward; B_alg above is the CONTRACT figure
     #  and no bound on this kernel's traffic, so the fraction on the kernel's own bytes is printed beside it
     kernel_bytes = band_kernel_bytes(LDLT, s) if band else None
-    out = {
-        "metric": "Newton systems/sec (fp64), batched n=1e4 NLS; achieved HBM GB/s vs peak",
-        "value": value, "unit": "systems/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / max(args.steps, 1) * 1e3, "higher_is_better": True, "scaling": "strong" if args.strong else "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"cfg3 band constrained NLS n={args.n} nequ={args.n} ncon={args.ncon}, "
-                               + (f"{total} independent problems split over {world} GPU(s)" if args.strong else f"{B} independent problems per GPU")
-                               + ", one newton_system! per problem per step",
-                   "vals_layout": ("interleaved over groups of 32 problems (cnl_options.batch_layout = 1: what cnl_prepare_newton_system_dev writes on "
-                                   "such a handle; rhs, d problem-major)" if LDLT.config.get("batch_layout") else "problem-major (the reference's vector per problem)"),
-                   "batch_per_gpu": B, "total_problems": counts[0], "sharding": f"independent problems, {world} contiguous shard(s), no collective",
-                   "ordering": info["order"], "nnzL_stored": info["nnzL"], "nnzL_exact": info["nnzL_exact"], "fronts": info["nsuper"],
-                   "kernel": LDLT.config, "all_success": ok, "backward_error": berr},
+    out = headline_fields(args, LDLT, counts, elapsed, total, world, B)
+    out["config"]["backward_error"] = berr
+    out.update({
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
                      "frac_of_measured_copy_rate": achieved / HBM_MEASURED_GBPS, "peak_measured_copy": HBM_MEASURED_GBPS,
                      "traffic": traffic, "traffic_source": traffic_src,
@@ -392,7 +440,7 @@ def main():
                              "rounds 1-2 (and round 3 before that change) priced a kernel that left 1.2 ms of the step to a second kernel on the same algorithmic bytes "
                              "(their step_frac is the comparable figure)",
                      "step_ms": step_ms, "step_frac": b_alg * B / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS},
-    }
+    })
     extras = (not args.no_extras) and world == 1 and not args.strong
     if extras:
         extra_blocks(out, torch, hipldl, syn, s, rows, cols, vals, rhs, vals_h, rhs_h, prob, B, dev, local_rank, stream, args)
@@ -416,6 +464,39 @@ def main():
         dist.destroy_process_group()
     if not guard["ok"]:
         print(f"bench.py: parity guard FAILED: {guard}", file=sys.stderr)
+        sys.exit(3)
+
+
+def headline_fields(args, LDLT, counts, elapsed, total, world, B):
+    """the mandated keys and the workload / handle description: what a plain run prints, and the head of the --full line"""
+    info = LDLT.info
+    return {
+        "metric": "Newton systems/sec (fp64), batched n=1e4 NLS; achieved HBM GB/s vs peak",
+        "value": counts[0] * args.steps / elapsed, "unit": "systems/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / max(args.steps, 1) * 1e3, "higher_is_better": True, "scaling": "strong" if args.strong else "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"cfg3 band constrained NLS n={args.n} nequ={args.n} ncon={args.ncon}, "
+                               + (f"{total} independent problems split over {world} GPU(s)" if args.strong else f"{B} independent problems per GPU")
+                               + ", one newton_system! per problem per step",
+                   "vals_layout": ("interleaved over groups of 32 problems (cnl_options.batch_layout = 1: what cnl_prepare_newton_system_dev writes on "
+                                   "such a handle; rhs, d problem-major)" if LDLT.config.get("batch_layout") else "problem-major (the reference's vector per problem)"),
+                   "batch_per_gpu": B, "total_problems": counts[0], "sharding": f"independent problems, {world} contiguous shard(s), no collective",
+                   "ordering": info["order"], "nnzL_stored": info["nnzL"], "nnzL_exact": info["nnzL_exact"], "fronts": info["nsuper"],
+                   "kernel": LDLT.config, "all_success": counts[1] == counts[0]},
+    }
+
+
+def headline_only(args, prob, counts, elapsed, total, world, B, dist):
+    """a plain run: the headline line alone; fails (exit 3) when a problem of the timed batch did not succeed"""
+    out = headline_fields(args, prob.L, counts, elapsed, total, world, B)
+    out["value_batch_per_gpu"] = B
+    out["value_vals_layout"] = "interleaved" if prob.L.config.get("batch_layout") else "problem-major"
+    print(json.dumps(out))
+    prob.close()
+    if dist is not None:
+        dist.destroy_process_group()
+    if not out["config"]["all_success"]:
+        print(f"bench.py: {counts[0] - counts[1]} of {counts[0]} problems did not succeed", file=sys.stderr)
         sys.exit(3)
 
 

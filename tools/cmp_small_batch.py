@@ -6,7 +6,7 @@ import ablate
 for v in sys.argv[1:]:
     for B in (1, 256, 2048, 8192):
         e = dict(os.environ, CANNOLES_HIP_LIB=ablate.libpath(v))
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(B), "--steps", "20", "--cpu-sample", "0", "--no-extras"], env=e, capture_output=True, text=True)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", str(B), "--steps", "20", "--cpu-sample", "0", "--no-extras"], env=e, capture_output=True, text=True)
         try:
             j = json.loads(out.stdout.strip().splitlines()[-1])
             print(v, "B", B, "systems/s %.0f" % j["value"], "ms/step %.4f" % j["ms_per_step"], j["config"]["kernel"]["kernel"], flush=True)

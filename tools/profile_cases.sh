@@ -13,7 +13,7 @@ run() {  # name, program, args...
   name=$1; shift
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_${name}_stats -o p -- python3 "$@" > $out/${tag}_${name}_stats.log 2>&1
 }
-B="$root/bench.py --steps 20 --warmup 3 --cpu-sample 0 --no-extras"
+B="$root/bench.py --full --steps 20 --warmup 3 --cpu-sample 0 --no-extras"
 run staged_B256 $B --batch 256
 run staged_B1 $B --batch 1
 run split_B5120 $B --batch 5120

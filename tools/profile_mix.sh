@@ -10,7 +10,7 @@ for pass in "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE
             "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT SQ_INST_CYCLES_SALU" \
             "SQ_INSTS_LDS_ATOMIC SQ_INSTS_LDS_LOAD SQ_INSTS_LDS_STORE SQ_THREAD_CYCLES_VALU SQ_BUSY_CYCLES SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_VMEM_WR SQ_IFETCH"; do
   i=$((i+1))
-  timeout 400 rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $OUT/mix$i -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-extras --cpu-sample 0 > $OUT/mix$i.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $OUT/mix$i -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-extras --cpu-sample 0 > $OUT/mix$i.log 2>&1
 done
 cd $ROOT
 python3 - <<'PY'

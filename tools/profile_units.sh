@@ -15,7 +15,7 @@ for pass in "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE
             "SQ_VMEM_TA_ADDR_FIFO_FULL SQ_VMEM_TA_CMD_FIFO_FULL SQ_VMEM_WR_TA_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL SQ_LDS_DATA_FIFO_FULL SQ_IFETCH SQ_INST_LEVEL_VMEM SQ_INST_LEVEL_LDS" \
             "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT SQ_INSTS_LDS_ATOMIC"; do
   i=$((i+1))
-  timeout 240 rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $out/${tag}_units_$i -o p -- python3 $root/bench.py $args > $out/${tag}_units_$i.log 2>&1
+  timeout 240 rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $out/${tag}_units_$i -o p -- python3 $root/bench.py --full $args > $out/${tag}_units_$i.log 2>&1
   tail -1 $out/${tag}_units_$i.log | cut -c1-160
 done
 python3 - <<PY

@@ -14,7 +14,7 @@ for pass in "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_INSTS_SALU SQ_IN
   name=$(echo $pass | tr ' ' '_' | cut -c1-40)
   # (a pass whose counters the profiler rejects can hang until the box limit: every pass under its own timeout.  The TA_FLAT_*
   #  counters abort rocprofv3 on this image and are left out)
-  timeout 240 rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $out/${tag}_vmem_$name -o p -- python3 $root/bench.py $args > $out/${tag}_vmem_$name.log 2>&1
+  timeout 240 rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $out/${tag}_vmem_$name -o p -- python3 $root/bench.py --full $args > $out/${tag}_vmem_$name.log 2>&1
   tail -2 $out/${tag}_vmem_$name.log
 done
 python3 - <<PY

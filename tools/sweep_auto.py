@@ -5,7 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT = (64, 128, 256, 512, 768, 1024, 1536, 2048, 2560, 3072, 4096, 4352, 4608, 5120, 6144, 7168, 8192, 8448, 10240, 12288, 16384)
 points = []
 for B in ([int(x) for x in sys.argv[1].split(',')] if len(sys.argv) > 1 else DEFAULT):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(B), "--steps", "10", "--cpu-sample", "0", "--no-extras"], capture_output=True, text=True)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", str(B), "--steps", "10", "--cpu-sample", "0", "--no-extras"], capture_output=True, text=True)
     try:
         j = json.loads(out.stdout.strip().splitlines()[-1])
         c = j["config"]

@@ -1,7 +1,7 @@
 import os, sys, json, subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def run(B, opt):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(B), "--steps", "20", "--cpu-sample", "0", "--no-extras", "--opt", opt], capture_output=True, text=True)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", str(B), "--steps", "20", "--cpu-sample", "0", "--no-extras", "--opt", opt], capture_output=True, text=True)
     try:
         j = json.loads(out.stdout.strip().splitlines()[-1])
         return j["value"], j["ms_per_step"], j["config"]["ordering"], j["config"]["fronts"], j["config"]["kernel"]["kernel"]
