@@ -19,34 +19,6 @@
 #include "band.h"
 #include "kernels.h"
 
-// timing probes (results wrong or missing): 1 no backward sweep, 2 no arithmetic in the forward steps, 4 none in the backward steps,
-// 8 no operand loads after the first epoch, 16 no factor / solution stores
-#ifndef BAND_DBG
-#define BAND_DBG 0
-#endif
-// probe: every operand piece / factor flush moved down to a multiple of eight doubles (WRONG results; what perfectly aligned streams
-// would be worth — build with -DBAND_DBG=1 so that garbage triggers no ladder)
-// probe: only every other operand load instruction is issued (WRONG results: what half the vector-memory LOAD instructions would be worth)
-#ifndef BAND_PROBE_HALF_LOADS
-#define BAND_PROBE_HALF_LOADS 0
-#endif
-#ifdef BAND_PROBE_ALIGNED
-constexpr int BAND_ALIGN_MASK = ~7;
-#else
-constexpr int BAND_ALIGN_MASK = ~0;
-#endif
-#if (BAND_DBG || defined(BAND_STAMPS) || defined(BAND_PROBE_ALIGNED) || BAND_PROBE_HALF_LOADS) && !defined(CNL_EXPERIMENT)
-#error "BAND_DBG needs -DCNL_EXPERIMENT=1"
-#endif
-
-#ifdef BAND_STAMPS   // diagnostic: time per phase of an epoch (s_memtime ticks, summed), written over d[0 .. 15] of the workgroup's first problem
-#define BSTAMP_DECL unsigned long long bst_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, bst_t = __builtin_amdgcn_s_memtime();
-#define BSTAMP(K) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); bst_[K] += t_ - bst_t; bst_t = t_; __builtin_amdgcn_sched_barrier(0); }
-#else
-#define BSTAMP_DECL
-#define BSTAMP(K)
-#endif
-
 namespace cnl {
 
 namespace {
@@ -394,7 +366,6 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   bool done = !valid, success = false, ovr = false;
 
   static_assert(NI <= 4, "at most four problem groups per mover lane");
-  constexpr bool BAND_ISSUE_ALWAYS = false;
   double stg[NPC][NI];   // operand pieces in flight
   int4 rstg0;            // step blocks in flight (one 16-byte word per lane: 256 ints)
   int pcs[NPC];          // piece descriptors of the epoch being loaded
@@ -405,22 +376,13 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   // piece's array are selected with scalar instructions, the lane's offset is problem * stride + element.  (Three guarded loads
   // made the compiler form all three 64-bit addresses of every piece up front — 96 NI VGPRs; selecting among per-array offset
   // arrays made it index them in scratch memory; lambdas instead of macros put every captured variable into scratch.)
-#if BAND_PROBE_HALF_LOADS == 2   /* one 16-byte load per lane instead of two 8-byte ones: the same lines, half the instructions (interleaved vals only) */
-#define BAND_ISSUE1(K, I)                                                                                                     \
-  if constexpr (I < NI && (I & 1) == 0) {                                                                                     \
-    const double2 v2_ = *reinterpret_cast<const double2*>(pb + ((movp[I] * strd + tl + (unsigned)lane) << 3));                \
-    stg[K][I] = v2_.x;                                                                                                        \
-    if constexpr (I + 1 < NI) stg[K][I + 1] = v2_.y;                                                                          \
-  }
-#else
-#define BAND_ISSUE1(K, I) if constexpr (I < NI && (!BAND_PROBE_HALF_LOADS || (I & 1) == 0)) stg[K][I] = *reinterpret_cast<const double*>(pb + ((movp[I] * strd + tl) << 3));
-#endif
+#define BAND_ISSUE1(K, I) if constexpr (I < NI) stg[K][I] = *reinterpret_cast<const double*>(pb + ((movp[I] * strd + tl) << 3));
 #define BAND_COMMIT1(K, I) if constexpr (I < NI) *reinterpret_cast<double*>(wblk + ldsb[I] + (BAND_IN_OFF + 8 * K) * 8) = stg[K][I];
 #define BAND_ISSUE(K)                                                                                                         \
-  if (BAND_ISSUE_ALWAYS || pcs[K] >= 0) {   /* (wave-uniform: an unused piece costs the memory pipeline what a used one does) */ \
-    const int pc = pcs[K] >= 0 ? pcs[K] : 0;   /* (ALWAYS: an unused piece loads element 0 of vals — a static number of loads per epoch) */ \
+  if (pcs[K] >= 0) {   /* (wave-uniform) */                                                                                   \
+    const int pc = pcs[K];                                                                                                    \
     const int arr = pc >> 28;                                                                                                 \
-    const int el_ = ((pc & ((1 << 28) - 1)) + (arr == 2 ? loff8 : 0)) & BAND_ALIGN_MASK;   /* (probe builds: -DBAND_PROBE_ALIGNED) */ \
+    const int el_ = (pc & ((1 << 28) - 1)) + (arr == 2 ? loff8 : 0);                                                          \
     /* lane offset (doubles) = problem * strd + tl, tl = t + (t >> 3) * gap with t = m + element of the lane: the caller's arrays    \
        are problem-major (m = 0, t < 8: gap = 0), the factor is interleaved in blocks of eight (see lbase_g) */                \
     const bool il_ = arr == 0 ? vil : arr == 1 ? ril : LINT;   /* (wave-uniform) */                                           \
@@ -455,7 +417,6 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   }
   static_assert(NPC == 15, "fifteen operand pieces");
 
-  BSTAMP_DECL
   Win W;
   int npos = 0, nzer = 0;
   double lj[6], zj[4];   // junction factor (first wavefront)
@@ -472,18 +433,15 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
     BAND_ISSUE_ALL(epochs, BE_FP, fops_g, 0)
     for (int e = 0; e < nepochs; e++) {
       cptr E = epochs + e * BAND_EW;
-      BSTAMP(0)
       BAND_COMMIT_ALL()
-      BSTAMP(1)
       // the next epoch's loads are issued in four groups behind the first four steps (a burst of 34 loads stalled the wavefront on
       // the CU's memory pipeline for ~2 500 cycles per epoch, in-kernel stamps), still four steps ahead of their use
-      const bool more_ = e + 1 < nepochs && !(BAND_DBG & 8);
+      const bool more_ = e + 1 < nepochs;
       if (more_) BAND_ISSUE_DESC(epochs + (e + 1) * BAND_EW, BE_FP)
       // The steps of the epoch: step t works on the slots of phase t (every epoch but the last has BAND_EPOCH steps), so the eight
       // instantiations follow each other in straight-line code and the window keeps its registers from step to step.
       const int nst = E[BE_NSTEP];
       int o = 0;
-      BSTAMP(2)
       // the blocks of step t + 1 (step block + first row block) are read from the record buffer while step t computes; the step
       // reads all its operands at its top (one LDS round trip).  (A third stage — operands a step ahead — was measured: no gain,
       // 170 more registers.)
@@ -496,7 +454,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
         const int fl = __builtin_amdgcn_readfirstlane(stC.v[BS_FLAGS]);                                                     \
         const int onext = o + BAND_SW + BAND_RW * ((fl >> 8) & 255);                                                        \
         if (PHV + 1 < nst) { load_rec(stN, recb, onext); load_row(rwN, recb, onext + BAND_SW); }                            \
-        if (clane && !(BAND_DBG & 2)) {                                                                                     \
+        if (clane) {                                                                                                        \
           FOps op_;                                                                                                         \
           fload(op_, stC, rwC, fl, myb);                                                                                    \
           fstep<PHV>(W, op_, stC, fl, recb, o, myb, gvals, grhs, borders, pv, pr, has_rhs, rho, ovr, tol, npos, nzer, vstride, rstride); \
@@ -509,7 +467,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
 #define BAND_LFLUSH(LB, LC)                                                                                                 \
       if (mode != MODE_FACTOR) {                                                                                            \
         const int lc_ = (LC);                                                                                               \
-        const int lb_ = ((LB) + loff8) & BAND_ALIGN_MASK;                                                                   \
+        const int lb_ = (LB) + loff8;                                                                                       \
         char* lout = reinterpret_cast<char*>(lbase_g) + ((LINT ? (long long)(lb_ >> 3) * (NL * 8) : (long long)lb_) << 3);  \
         const unsigned t_ = (LINT ? (unsigned)(lb_ & 7) : 0u) + (unsigned)le;                                               \
         const unsigned tl = t_ + (LINT ? (t_ >> 3) * (unsigned)(NL * 8 - 8) : 0u);                                          \
@@ -520,7 +478,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
           _Pragma("unroll") for (int i = 0; i < NI; i++) lx_[cpc][i] = *reinterpret_cast<const double*>(wblk + ldsb[i] + (BAND_LOUT_OFF + 8 * cpc) * 8); \
         _Pragma("unroll") for (int cpc = 0; cpc < BAND_LOUT_MAX / 8; cpc++)                                                 \
           _Pragma("unroll") for (int i = 0; i < NI; i++)                                                                    \
-            if (movok[i] && cpc * 8 + le < lc_ && !(BAND_DBG & 16))                                                         \
+            if (movok[i] && cpc * 8 + le < lc_)                                                                             \
               *reinterpret_cast<double*>(lout + (((movp[i] * lstr_ + tl) << 3) + lcp_ * cpc)) = lx_[cpc][i];                 \
       }
       BAND_FSTEP(0)
@@ -533,7 +491,6 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
       if (more_) { BAND_ISSUE(12) BAND_ISSUE(13) BAND_ISSUE(14) BAND_ISSUE_REC(fops_g, epochs[(e + 1) * BAND_EW + BE_FOFF]) }
       BAND_LFLUSH(E[BE_LBASE], E[BE_LCNT])
       BAND_FSTEP(4) BAND_FSTEP(5) BAND_FSTEP(6) BAND_FSTEP(7)
-      BSTAMP(3)
       static_assert(BAND_EPOCH == 8, "eight step instantiations per epoch");
       if (nst == BAND_EPOCH) {
         // behind a full epoch the slots 0 .. 3 are dead (pivoted in phases 4 .. 7): give them a constant, so that only the ten
@@ -549,7 +506,6 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
       }
       BAND_LFLUSH(E[BE_LBASE2], E[BE_LCNT2])
     }
-    BSTAMP(4)
     // ================= junction + inertia rule + rho ladder (src/solver_types.jl:90-97, src/CaNNOLeS.jl:1023-1047) ==========
     int tpos = npos, tzer = nzer;
     if (P.nparts == 2) {
@@ -602,7 +558,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
     }
     bool alldone = true;
     if (part == 0) {
-      const bool ok = (BAND_DBG != 0) || (tpos == P.nvar && tzer == 0);   // (timing probes compute garbage: no ladder behind them)
+      const bool ok = tpos == P.nvar && tzer == 0;
       if (mode == MODE_FACTOR) {
         if (valid) {
           as_global(Ain.success)[cprob] = ok ? 1 : 0;
@@ -638,7 +594,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
     }
     if (alldone) break;
   }
-  if (mode == MODE_FACTOR || (BAND_DBG & 1)) {
+  if (mode == MODE_FACTOR) {
     if (mode == MODE_NEWTON && part == 0 && valid) as_global(Ain.success)[cprob] = 1;
     return;
   }
@@ -685,14 +641,11 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
     BAND_ISSUE_ALL(epochs + (nepochs - 1) * BAND_EW, BE_BP, bops_g, 0)
     for (int e = nepochs - 1; e >= 0; e--) {
       cptr E = epochs + e * BAND_EW;
-      BSTAMP(5)
       BAND_COMMIT_ALL()
-      BSTAMP(6)
-      const bool more_ = e > 0 && !(BAND_DBG & 8);
+      const bool more_ = e > 0;
       if (more_) BAND_ISSUE_DESC(epochs + (e - 1) * BAND_EW, BE_BP)
       const int nst = E[BE_NSTEP];
       int o = 0;
-      BSTAMP(7)
       Rec stC, stN;
       RowRec rwC, rwN;
       load_rec(stC, recb, 0);
@@ -702,7 +655,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
         const int fl = __builtin_amdgcn_readfirstlane(stC.v[BS_FLAGS]);                                                     \
         const int onext = o + BAND_SW + BAND_RW * ((fl >> 8) & 255);                                                        \
         if (PHV > 0) { load_rec(stN, recb, onext); load_row(rwN, recb, onext + BAND_SW); }                                  \
-        if (clane && !(BAND_DBG & 4)) {                                                                                     \
+        if (clane) {                                                                                                        \
           BOps op_;                                                                                                         \
           bload(op_, stC, rwC, fl, myb);                                                                                    \
           bstep<PHV>(xs, op_, stC, rwC, fl, recb, o, myb, borders, gd, pd, okme);                                           \
@@ -718,7 +671,6 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
       BAND_BSTEP(4)
       if (more_) { BAND_ISSUE(12) BAND_ISSUE(13) BAND_ISSUE(14) BAND_ISSUE_REC(bops_g, epochs[(e - 1) * BAND_EW + BE_BOFF]) }
       BAND_BSTEP(3) BAND_BSTEP(2) BAND_BSTEP(1) BAND_BSTEP(0)
-      BSTAMP(8)
       // solution components of the epoch
       const int xlo = E[BE_DXLO], xc = E[BE_DXCNT], rlo = E[BE_DRLO], rc = E[BE_DRCNT];
       char* dxo = reinterpret_cast<char*>(dbase) + ((long long)xlo << 3);
@@ -733,19 +685,15 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
           for (int i = 0; i < NI; i++) dr_[cpc][i] = *reinterpret_cast<const double*>(wblk + ldsb[i] + (BAND_DR_OFF + 8 * cpc) * 8);
 #pragma unroll
         for (int i = 0; i < NI; i++)
-          if (movst[i] && le < xc && !(BAND_DBG & 16)) *reinterpret_cast<double*>(dxo + ((movp[i] * (unsigned)N + (unsigned)le) << 3)) = dx_[i];
+          if (movst[i] && le < xc) *reinterpret_cast<double*>(dxo + ((movp[i] * (unsigned)N + (unsigned)le) << 3)) = dx_[i];
 #pragma unroll
         for (int cpc = 0; cpc < BAND_DR_MAX / 8; cpc++)
 #pragma unroll
           for (int i = 0; i < NI; i++)
-            if (movst[i] && cpc * 8 + le < rc && !(BAND_DBG & 16)) *reinterpret_cast<double*>(dro + (((movp[i] * (unsigned)N + (unsigned)le) << 3) + 64 * cpc)) = dr_[cpc][i];
+            if (movst[i] && cpc * 8 + le < rc) *reinterpret_cast<double*>(dro + (((movp[i] * (unsigned)N + (unsigned)le) << 3) + 64 * cpc)) = dr_[cpc][i];
       }
     }
   }
-#ifdef BAND_STAMPS
-  BSTAMP(9)
-  if (blockIdx.x == 0 && lane == 0) for (int k = 0; k < 12; k++) gd[(long long)prob0 * N + part * 12 + k] = (double)bst_[k];
-#endif
   // ================= outputs of newton_system! =================
   if (part == 0 && mode == MODE_NEWTON) {
     if (nfact > 1 && rho <= rhomax) rho_old = rho;
@@ -773,480 +721,6 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   }
 }
 
-#if defined(BAND_MW) && !defined(CNL_EXPERIMENT)
-#error "BAND_MW needs -DCNL_EXPERIMENT=1"
-#endif
-#ifdef BAND_MW
-// ======================================================================================================================================
-// EXPERIMENT (round 6; not in the product build: -DCNL_EXPERIMENT=1 -DBAND_MW, tuning key band_movers=1..3): the same program with LOADER
-// wavefronts.  A workgroup of EIGHT wavefronts serves two groups of NL problems; per (group, part) one wavefront computes AND streams
-// its own factor records / solution components out (as in band_newton_kernel), and one wavefront only LOADS into staging registers and
-// commits them to LDS around the workgroup barriers of an epoch.  Only a wavefront without stores can wait for a set of loads alone: on
-// gfx950 loads and stores share one counter (vmcnt) and return out of order with respect to each other (profiles/r06_band_movers.jsonl:
-// the first two look-ahead experiments waited with vmcnt(0) for loads issued a few steps earlier).  Roles: waves 0,1 compute / 2,3 load
-// for group 0, waves 4,5 load / 6,7 compute for group 1 — wavefronts w and w + 4 share a SIMD (tools/simd_map.hip), so every SIMD holds
-// one of each.  Measured (same file): +6 ... 10 % at 8 192 problems, nothing at 16 384 — the look-ahead question is closed.
-#define MW_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-// v5: every (problem, part) owns TWO standard lane blocks (pieces | half ring | zero cell): the loader commits the operands of epoch
-// e + 1 into block (e + 1) % 2 WHILE epoch e computes out of block e % 2 — the compute wavefronts never wait for a commit.  One staging
-// set in registers: the loads of epoch e + 2 are issued behind the commit of e + 1 (a single generation in flight: the waits at the
-// next commit are counted, nothing younger to wait for).  The step blocks have ONE buffer, written between the two barriers of an epoch
-// boundary.  307 doubles per lane (odd): 4 x 16 lanes of a workgroup = 157 KB of the 160 KB of a CU.
-// v6 (DB = false): ONE block per lane and the staging registers as the second buffer — the loads of epoch e + 1 are issued behind
-// barrier X of epoch e and committed behind its barrier Y; 32 problems per group (4 x 32 lanes = the LDS of a CU, as band_newton_kernel<32>
-// at 16 384 problems).
-constexpr int MW_BLK = BAND_LANE_DOUBLES * 8;   // byte offset of the second block
-constexpr int mw_lane_d(bool db) { return db ? 2 * BAND_LANE_DOUBLES + 1 : BAND_LANE_DOUBLES; }
-
-template <int NL, bool DB>
-__global__ void __launch_bounds__(512, 2) band_newton_mw_kernel(const BandDev P, const LaunchArgs Ain) {
-  constexpr int NI = NL / 8;
-  constexpr int LANE_D = mw_lane_d(DB);
-  constexpr bool LINT = true;   // factor records interleaved over the group's problems (the address arithmetic is the mover's, off the chain)
-  extern __shared__ double lds[];
-  const int mode = Ain.mode, batch = Ain.batch;
-  double* const gvals = as_global(Ain.vals);
-  const double* const grhs = as_global(Ain.rhs);
-  double* const gd = as_global(Ain.d);
-  double* const gL = as_global(Ain.L);
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int grp = wv >> 2, part = wv & 1;
-  const bool computes = ((wv >> 1) & 1) == grp;
-  const int lq = lane >> 3, le = lane & 7;
-  const int prob0 = (blockIdx.x * 2 + grp) * NL;
-  const bool has_rhs = mode != MODE_FACTOR && grhs != nullptr;
-  char* wblk = reinterpret_cast<char*>(lds + (size_t)(grp * 2 + part) * NL * LANE_D);
-  char* recb = reinterpret_cast<char*>(lds + (size_t)4 * NL * LANE_D) + (size_t)(grp * 2 + part) * BAND_REC_MAX * 4;
-  double* ctrl = reinterpret_cast<double*>(reinterpret_cast<char*>(lds + (size_t)4 * NL * LANE_D) + (size_t)4 * BAND_REC_MAX * 4) + (size_t)grp * (2 * NL + 8);
-  cptr epochs = as_const(P.epochs[part]);
-  const int nepochs = P.nepochs[part];
-  const int nepmax = P.nepochs[0] > P.nepochs[1] ? P.nepochs[0] : P.nepochs[1];
-  const int nnz = P.nnz, N = P.N;
-  const bool live = prob0 < batch;   // (the last workgroup's second group may be empty: it only joins the barriers)
-  constexpr int G8 = BAND_IL_GROUP * 8;
-  const bool vil = (Ain.layout & 1) != 0, ril = (Ain.layout & 2) != 0;   // interleaved vals / rhs (band_newton_kernel)
-  const int vstride = vil ? G8 : 0, rstride = ril ? G8 : 0;
-  const long long ilg = prob0 / BAND_IL_GROUP;
-  const int ilp = (prob0 % BAND_IL_GROUP) * 8;
-  const double tol = Ain.params[0];
-
-  if (!computes) {
-    // ================================================ loader ================================================
-    const int* fops_g = as_global(P.fops[part]);
-    const int* bops_g = as_global(P.bops[part]);
-    const long long lsize = P.lsize;
-    const double* vbase = gvals + (vil ? ilg * band_il_blocks(nnz) * G8 + ilp : (long long)prob0 * nnz);
-    const double* rbase = !has_rhs ? gvals : grhs + (ril ? ilg * band_il_blocks(N) * G8 + ilp : (long long)prob0 * N);
-    double* lbase_g = gL + (long long)prob0 * lsize;
-    const int loff8 = (int)P.loff[part];
-    unsigned movp[NI], ldsb0[NI];
-    bool movok[NI];
-#pragma unroll
-    for (int i = 0; i < NI; i++) {
-      int pl = i * 8 + lq;
-      movok[i] = prob0 + pl < batch;
-      if (!movok[i]) pl = live ? batch - 1 - prob0 : 0;
-      movp[i] = (unsigned)pl;
-      ldsb0[i] = ((unsigned)(i * 8 + lq) * (unsigned)LANE_D + (unsigned)le) << 3;
-    }
-    double stg[NPC][NI];   // ONE staging set
-    int4 rstg0, rkeep;     // step blocks: in flight / waiting for their epoch boundary
-    int pcs[NPC];
-    constexpr bool BAND_ISSUE_ALWAYS = true;   // (a static number of loads per generation: counted waits)
-    // pieces of the staged epoch into block PAR of every lane; the step blocks are kept for the epoch boundary
-#define MW_COMMIT_PIECES(PAR)                                                                                                 \
-    {                                                                                                                         \
-      unsigned ldsb[NI];                                                                                                      \
-      _Pragma("unroll") for (int i_ = 0; i_ < NI; i_++) ldsb[i_] = ldsb0[i_] + (unsigned)(DB ? (PAR) * MW_BLK : 0);                     \
-      BAND_COMMIT(0) BAND_COMMIT(1) BAND_COMMIT(2) BAND_COMMIT(3) BAND_COMMIT(4) BAND_COMMIT(5) BAND_COMMIT(6) BAND_COMMIT(7) \
-      BAND_COMMIT(8) BAND_COMMIT(9) BAND_COMMIT(10) BAND_COMMIT(11) BAND_COMMIT(12) BAND_COMMIT(13) BAND_COMMIT(14)           \
-      rkeep = rstg0;                                                                                                          \
-    }
-#define MW_COMMIT_REC() { reinterpret_cast<int4*>(recb)[lane] = rkeep; }
-#define MW_ISSUE_ALL(EP, OFS, OPS, OPOFF)                                                                                     \
-    {                                                                                                                         \
-      BAND_ISSUE_DESC(EP, OFS)                                                                                                \
-      BAND_ISSUE_REC(OPS, OPOFF)                                                                                              \
-      BAND_ISSUE(0) BAND_ISSUE(1) BAND_ISSUE(2) BAND_ISSUE(3) BAND_ISSUE(4) BAND_ISSUE(5) BAND_ISSUE(6) BAND_ISSUE(7)         \
-      BAND_ISSUE(8) BAND_ISSUE(9) BAND_ISSUE(10) BAND_ISSUE(11) BAND_ISSUE(12) BAND_ISSUE(13) BAND_ISSUE(14)                  \
-    }
-    while (true) {
-      // ---- forward: epoch e computes out of block e % 2 ----
-      if (live && nepochs > 0) {
-        MW_ISSUE_ALL(epochs, BE_FP, fops_g, 0)
-        MW_COMMIT_PIECES(0)
-        MW_COMMIT_REC()
-        if (DB && nepochs > 1) MW_ISSUE_ALL(epochs + BAND_EW, BE_FP, fops_g, epochs[BAND_EW + BE_FOFF])
-      }
-      for (int e = 0; e < nepmax; e++) {
-        MW_BARRIER();   // X: pieces and step blocks of epoch e are in LDS
-        if (live) {
-          if constexpr (DB) {
-            if (e + 1 < nepochs) MW_COMMIT_PIECES((e + 1) & 1)   // (its block is free: the compute wavefront is past epoch e - 1)
-            if (e + 2 < nepochs) MW_ISSUE_ALL(epochs + (e + 2) * BAND_EW, BE_FP, fops_g, epochs[(e + 2) * BAND_EW + BE_FOFF])
-          } else {
-            if (e + 1 < nepochs) MW_ISSUE_ALL(epochs + (e + 1) * BAND_EW, BE_FP, fops_g, epochs[(e + 1) * BAND_EW + BE_FOFF])
-          }
-        }
-        MW_BARRIER();   // Y: the compute wavefront is through epoch e
-        if (live && e + 1 < nepochs) {
-          if constexpr (!DB) MW_COMMIT_PIECES(0)
-          MW_COMMIT_REC()
-        }
-      }
-      MW_BARRIER();   // J1
-      MW_BARRIER();   // J2: the decision is in the control block
-      const bool alldone = ctrl[2 * NL] != 0.0;
-      MW_BARRIER();   // J3
-      if (alldone) break;
-    }
-    if (mode == MODE_FACTOR) return;
-    // ---- backward: trip t handles epoch e = nepmax - 1 - t out of block t % 2 ----
-    MW_BARRIER();   // K1
-    MW_BARRIER();   // K2 (behind it the junction exchange in block 0 is read)
-    {
-      // the first trip with an epoch of this part, and the one behind it
-      const int t0 = nepmax - nepochs;   // trips 0 .. t0 - 1 have no epoch here
-      if (live && nepochs > 0) {
-        MW_ISSUE_ALL(epochs + (nepochs - 1) * BAND_EW, BE_BP, bops_g, epochs[(nepochs - 1) * BAND_EW + BE_BOFF])
-        MW_COMMIT_PIECES(t0 & 1)
-        MW_COMMIT_REC()
-        if (DB && nepochs > 1) MW_ISSUE_ALL(epochs + (nepochs - 2) * BAND_EW, BE_BP, bops_g, epochs[(nepochs - 2) * BAND_EW + BE_BOFF])
-      }
-      for (int t = 0; t < nepmax; t++) {
-        const int e = nepmax - 1 - t;   // epoch of this trip (>= nepochs: none)
-        MW_BARRIER();   // X
-        if (live && e < nepochs) {
-          if constexpr (DB) {
-            if (e - 1 >= 0) MW_COMMIT_PIECES((t + 1) & 1)
-            if (e - 2 >= 0) MW_ISSUE_ALL(epochs + (e - 2) * BAND_EW, BE_BP, bops_g, epochs[(e - 2) * BAND_EW + BE_BOFF])
-          } else {
-            if (e - 1 >= 0) MW_ISSUE_ALL(epochs + (e - 1) * BAND_EW, BE_BP, bops_g, epochs[(e - 1) * BAND_EW + BE_BOFF])
-          }
-        }
-        MW_BARRIER();   // Y
-        if (live && e < nepochs && e - 1 >= 0) {
-          if constexpr (!DB) MW_COMMIT_PIECES(0)
-          MW_COMMIT_REC()
-        }
-      }
-    }
-    return;
-  }
-
-  // ================================================ compute ================================================
-  cptr borders = as_const(P.borders[part]);
-  const bool clane = lane < NL;
-  const int cprob = prob0 + (clane ? lane : 0);
-  const bool valid = clane && cprob < batch;
-  const int cpl = valid ? cprob - prob0 : (live ? batch - 1 - prob0 : 0);
-  char* myb = wblk + (size_t)(clane ? lane : 0) * LANE_D * 8;
-  const long long pv = !live ? 0 : vil ? ilg * band_il_blocks(nnz) * G8 + ilp + cpl * 8 : (long long)(prob0 + cpl) * nnz;
-  const long long pr = !live ? 0 : ril ? ilg * band_il_blocks(N) * G8 + ilp + cpl * 8 : (long long)(prob0 + cpl) * N;
-  // the wavefront streams its own factor records / solution components out (all 64 lanes: lane (lq, le) = element le of problems lq, lq + 8)
-  const long long lsize = P.lsize;
-  double* lbase_g = gL + (long long)prob0 * lsize;
-  const int loff8 = (int)P.loff[part];
-  double* dbase = gd ? gd + (long long)prob0 * N : nullptr;
-  unsigned movp[NI], ldsb[NI];
-  bool movok[NI];
-#pragma unroll
-  for (int i = 0; i < NI; i++) {
-    int pl = i * 8 + lq;
-    movok[i] = prob0 + pl < batch;
-    if (!movok[i]) pl = live ? batch - 1 - prob0 : 0;
-    movp[i] = (unsigned)pl;
-    ldsb[i] = ((unsigned)(i * 8 + lq) * (unsigned)LANE_D + (unsigned)le) << 3;
-  }
-  for (int t = lane; t < NL; t += 64) {   // the zero cells
-    *reinterpret_cast<double*>(wblk + ((size_t)t * LANE_D + BAND_ZERO_OFF) * 8) = 0.0;
-    if constexpr (DB) *reinterpret_cast<double*>(wblk + ((size_t)t * LANE_D + BAND_ZERO_OFF) * 8 + MW_BLK) = 0.0;
-  }
-  char* const wblk0 = wblk;
-  char* const myb0 = myb;
-  const double kdec = Ain.params[2], kinc = Ain.params[3], klarge = Ain.params[4], rho0 = Ain.params[5], rhomax = Ain.params[6], rhomin = Ain.params[7];
-  double rho = 0.0, wrote = 0.0;
-  double rho_old = (mode == MODE_NEWTON && valid) ? as_global(Ain.rho_old)[cprob] : 0.0;
-  int nfact = 0;
-  bool done = !valid, success = false, ovr = false;
-  Win W;
-  int npos = 0, nzer = 0;
-  double lj[6], zj[4];
-  for (int q = 0; q < 6; q++) lj[q] = 0.0;
-  for (int q = 0; q < 4; q++) zj[q] = 0.0;
-  while (true) {
-#pragma unroll
-    for (int q = 0; q < NS * (NS + 1) / 2; q++) W.S[q] = 0.0;
-#pragma unroll
-    for (int q = 0; q < NS; q++) { W.X[q] = 0.0; W.c[q] = 0.0; }
-    W.S55 = 0.0; W.c5 = 0.0;
-    npos = 0; nzer = 0;
-    for (int e = 0; e < nepmax; e++) {
-      MW_BARRIER();   // X
-      if (live && e < nepochs) {
-        cptr E = epochs + e * BAND_EW;
-        const int nst = E[BE_NSTEP];
-        char* const wblk = wblk0 + (DB ? (e & 1) * MW_BLK : 0);   // the block of the epoch: operands, out ring, zero cell
-        char* const myb = myb0 + (DB ? (e & 1) * MW_BLK : 0);
-        int o = 0;
-        Rec stC, stN;
-        RowRec rwC, rwN;
-        load_rec(stC, recb, 0);
-        load_row(rwC, recb, BAND_SW);
-#define BAND_FSTEP_MW(PHV)                                                                                                  \
-        if (PHV < nst) {                                                                                                    \
-          const int fl = __builtin_amdgcn_readfirstlane(stC.v[BS_FLAGS]);                                                   \
-          const int onext = o + BAND_SW + BAND_RW * ((fl >> 8) & 255);                                                      \
-          if (PHV + 1 < nst) { load_rec(stN, recb, onext); load_row(rwN, recb, onext + BAND_SW); }                          \
-          if (clane) {                                                                                                      \
-            FOps op_;                                                                                                       \
-            fload(op_, stC, rwC, fl, myb);                                                                                  \
-            fstep<PHV>(W, op_, stC, fl, recb, o, myb, gvals, grhs, borders, pv, pr, has_rhs, rho, ovr, tol, npos, nzer, vstride, rstride); \
-          }                                                                                                                 \
-          o = onext; stC = stN; rwC = rwN;                                                                                  \
-        }
-        BAND_FSTEP_MW(0) BAND_FSTEP_MW(1) BAND_FSTEP_MW(2) BAND_FSTEP_MW(3)
-        BAND_LFLUSH(E[BE_LBASE], E[BE_LCNT])
-        BAND_FSTEP_MW(4) BAND_FSTEP_MW(5) BAND_FSTEP_MW(6) BAND_FSTEP_MW(7)
-        if (nst == BAND_EPOCH) {
-#pragma unroll
-          for (int a = 0; a < NS; a++)
-#pragma unroll
-            for (int b = 0; b <= a; b++)
-              if (b < 4) W.S[sidx(a, b)] = 0.0;
-#pragma unroll
-          for (int a = 0; a < 4; a++) { W.X[a] = 0.0; W.c[a] = 0.0; }
-        }
-        BAND_LFLUSH(E[BE_LBASE2], E[BE_LCNT2])
-      }
-      MW_BARRIER();   // Y
-    }
-    // ---- junction + inertia rule + rho ladder: as in band_newton_kernel (two parts) ----
-    int tpos = npos, tzer = nzer;
-    if (clane) {
-      double* ex = reinterpret_cast<double*>(myb + EXCH_OFF * 8);
-#pragma unroll
-      for (int q = 0; q < NS * (NS + 1) / 2; q++) ex[q] = W.S[q];
-#pragma unroll
-      for (int q = 0; q < NS; q++) ex[36 + q] = W.c[q];
-      ex[44] = (double)npos; ex[45] = (double)nzer;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the factor records are in L2 before the loader wavefront reads them back
-    MW_BARRIER();   // J1
-    if (part == 0 && clane) {
-      const double* exL = reinterpret_cast<const double*>(myb + EXCH_OFF * 8);
-      const double* exR = reinterpret_cast<const double*>(myb + (size_t)NL * LANE_D * 8 + EXCH_OFF * 8);
-      const int tL = P.m0 % NS, tR = (P.n - 1 - P.m0) % NS;
-      double SJ[10], cJ[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const int aL = (tL + i) % NS, aR = (tR - i + NS) % NS;
-#pragma unroll
-        for (int j = 0; j <= i; j++) {
-          const int bL = (tL + j) % NS, bR = (tR - j + NS) % NS;
-          const int iL = aL >= bL ? aL * (aL + 1) / 2 + bL : bL * (bL + 1) / 2 + aL;
-          const int iR = aR >= bR ? aR * (aR + 1) / 2 + bR : bR * (bR + 1) / 2 + aR;
-          SJ[i * (i + 1) / 2 + j] = exL[iL] + exR[iR];
-        }
-        cJ[i] = exL[36 + aL] + exR[36 + aR];
-      }
-      tpos += (int)exR[44]; tzer += (int)exR[45];
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const double d = SJ[sidx(i, i)];
-        tpos += d > tol;
-        tzer += fabs(d) <= tol;
-        const double r = rrcp(d);
-        zj[i] = rdiv(cJ[i], d, r);
-        double w[4];
-#pragma unroll
-        for (int a = i + 1; a < 4; a++) { w[a] = SJ[sidx(a, i)]; lj[sidx(a - 1, i)] = rdiv(w[a], d, r); }
-#pragma unroll
-        for (int a = i + 1; a < 4; a++) {
-#pragma unroll
-          for (int b = i + 1; b <= a; b++) SJ[sidx(a, b)] = fma(w[a], -lj[sidx(b - 1, i)], SJ[sidx(a, b)]);
-          cJ[a] = fma(w[a], -zj[i], cJ[a]);
-        }
-      }
-    }
-    bool alldone = true;
-    if (part == 0) {
-      const bool ok = tpos == P.nvar && tzer == 0;
-      if (mode == MODE_FACTOR) {
-        if (valid) {
-          as_global(Ain.success)[cprob] = ok ? 1 : 0;
-          if (Ain.npos) as_global(Ain.npos)[cprob] = tpos;
-          if (Ain.nzero) as_global(Ain.nzero)[cprob] = tzer;
-        }
-        done = true;
-      } else if (mode == MODE_SOLVE) {
-        success = ok;
-        done = true;
-      } else if (!done) {
-        nfact++;
-        if (ok) { done = true; success = true; }
-        else if (nfact == 1) {
-          rho = rho_old == 0.0 ? rho0 : fmax(rhomin, kdec * rho_old);
-          ovr = true; wrote = rho;
-        } else if (rho <= rhomax) {
-          rho = rho_old == 0.0 ? klarge * rho : kinc * rho;
-          if (rho <= rhomax) wrote = rho; else done = true;
-        } else done = true;
-      }
-      alldone = __all(done || !clane);
-      if (clane) { ctrl[lane] = rho; ctrl[NL + lane] = (ovr ? 1.0 : 0.0) + (success ? 2.0 : 0.0); }
-      if (lane == 0) ctrl[2 * NL] = alldone ? 1.0 : 0.0;
-    }
-    MW_BARRIER();   // J2
-    if (part == 1) {
-      if (clane) { rho = ctrl[lane]; const int f = (int)ctrl[NL + lane]; ovr = f & 1; success = f & 2; }
-      alldone = ctrl[2 * NL] != 0.0;
-    }
-    MW_BARRIER();   // J3
-    if (alldone) break;
-  }
-  if (mode == MODE_FACTOR) return;
-  // ---- backward ----
-  {
-    double xs[NS + 1];
-#pragma unroll
-    for (int q = 0; q < NS + 1; q++) xs[q] = 0.0;
-    if (part == 0 && clane) {
-      double xj[4];
-      xj[3] = zj[3];
-      xj[2] = fma(-lj[sidx(2, 2)], xj[3], zj[2]);
-      xj[1] = fma(-lj[sidx(2, 1)], xj[3], fma(-lj[sidx(1, 1)], xj[2], zj[1]));
-      xj[0] = fma(-lj[sidx(2, 0)], xj[3], fma(-lj[sidx(1, 0)], xj[2], fma(-lj[sidx(0, 0)], xj[1], zj[0])));
-      double* ex = reinterpret_cast<double*>(myb + EXCH_OFF * 8);
-      double* exR = reinterpret_cast<double*>(myb + (size_t)NL * LANE_D * 8 + EXCH_OFF * 8);
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        ex[i] = xj[i]; exR[i] = xj[i];
-        if (valid && success) gd[(long long)cprob * N + P.m0 + i] = -xj[i];
-      }
-    }
-    MW_BARRIER();   // K1
-    if (clane) {
-      const double* ex = reinterpret_cast<const double*>(myb + EXCH_OFF * 8);
-      const int t0 = part == 0 ? P.m0 % NS : (P.n - 1 - P.m0) % NS;
-#pragma unroll
-      for (int s = 0; s < NS; s++) {
-        const int i = part == 0 ? (s - t0 + NS) % NS : (t0 - s + NS) % NS;
-        xs[s] = i < 4 ? ex[i] : 0.0;
-      }
-    }
-    if (part == 0 && clane) ctrl[NL + lane] = (valid && success) ? 2.0 : 0.0;
-    MW_BARRIER();   // K2
-    const bool okme = valid && ctrl[NL + lane % NL] != 0.0 && clane;
-    bool movst[NI];
-#pragma unroll
-    for (int i = 0; i < NI; i++) movst[i] = movok[i] && ctrl[NL + i * 8 + lq] != 0.0;
-    const long long pd = live ? (long long)(prob0 + cpl) * N : 0;
-    for (int e = nepmax - 1; e >= 0; e--) {
-      MW_BARRIER();   // X
-      if (live && e < nepochs) {
-        cptr E = epochs + e * BAND_EW;
-        const int nst = E[BE_NSTEP];
-        char* const wblk = wblk0 + (DB ? ((nepmax - 1 - e) & 1) * MW_BLK : 0);   // the block of the trip
-        char* const myb = myb0 + (DB ? ((nepmax - 1 - e) & 1) * MW_BLK : 0);
-        int o = 0;
-        Rec stC, stN;
-        RowRec rwC, rwN;
-        load_rec(stC, recb, 0);
-        load_row(rwC, recb, BAND_SW);
-#define BAND_BSTEP_MW(PHV)                                                                                                  \
-        if (PHV < nst) {                                                                                                    \
-          const int fl = __builtin_amdgcn_readfirstlane(stC.v[BS_FLAGS]);                                                   \
-          const int onext = o + BAND_SW + BAND_RW * ((fl >> 8) & 255);                                                      \
-          if (PHV > 0) { load_rec(stN, recb, onext); load_row(rwN, recb, onext + BAND_SW); }                                \
-          if (clane) {                                                                                                      \
-            BOps op_;                                                                                                       \
-            bload(op_, stC, rwC, fl, myb);                                                                                  \
-            bstep<PHV>(xs, op_, stC, rwC, fl, recb, o, myb, borders, gd, pd, okme);                                         \
-          }                                                                                                                 \
-          o = onext; stC = stN; rwC = rwN;                                                                                  \
-        }
-        BAND_BSTEP_MW(7) BAND_BSTEP_MW(6) BAND_BSTEP_MW(5) BAND_BSTEP_MW(4) BAND_BSTEP_MW(3) BAND_BSTEP_MW(2) BAND_BSTEP_MW(1) BAND_BSTEP_MW(0)
-        {   // solution components of the epoch
-          const int xlo = E[BE_DXLO], xc = E[BE_DXCNT], rlo = E[BE_DRLO], rc = E[BE_DRCNT];
-          char* dxo = reinterpret_cast<char*>(dbase) + ((long long)xlo << 3);
-          char* dro = reinterpret_cast<char*>(dbase) + ((long long)rlo << 3);
-          double dx_[NI], dr_[BAND_DR_MAX / 8][NI];
-#pragma unroll
-          for (int i = 0; i < NI; i++) dx_[i] = *reinterpret_cast<const double*>(wblk + ldsb[i] + BAND_DX_OFF * 8);
-#pragma unroll
-          for (int cpc = 0; cpc < BAND_DR_MAX / 8; cpc++)
-#pragma unroll
-            for (int i = 0; i < NI; i++) dr_[cpc][i] = *reinterpret_cast<const double*>(wblk + ldsb[i] + (BAND_DR_OFF + 8 * cpc) * 8);
-#pragma unroll
-          for (int i = 0; i < NI; i++)
-            if (movst[i] && le < xc) *reinterpret_cast<double*>(dxo + ((movp[i] * (unsigned)N + (unsigned)le) << 3)) = dx_[i];
-#pragma unroll
-          for (int cpc = 0; cpc < BAND_DR_MAX / 8; cpc++)
-#pragma unroll
-            for (int i = 0; i < NI; i++)
-              if (movst[i] && cpc * 8 + le < rc) *reinterpret_cast<double*>(dro + (((movp[i] * (unsigned)N + (unsigned)le) << 3) + 64 * cpc)) = dr_[cpc][i];
-        }
-      }
-      MW_BARRIER();   // Y
-    }
-  }
-  // ---- outputs of newton_system! ----
-  if (part == 0 && mode == MODE_NEWTON) {
-    if (nfact > 1 && rho <= rhomax) rho_old = rho;
-    if (valid) {
-      as_global(Ain.rho)[cprob] = rho;
-      as_global(Ain.rho_old)[cprob] = rho_old;
-      as_global(Ain.nfact)[cprob] = nfact;
-      as_global(Ain.success)[cprob] = success ? 1 : 0;
-    }
-    for (int q = 0; q < NL; q++) {
-      const int nf = __builtin_amdgcn_readlane(nfact, q);
-      const int vq = __builtin_amdgcn_readlane((int)valid, q);
-      if (nf > 1 && vq) {
-        const double wq = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(wrote), q), __builtin_amdgcn_readlane(__double2loint(wrote), q));
-        if (vil) {
-          double* vg = gvals + ilg * band_il_blocks(nnz) * G8 + ilp + q * 8;
-          for (int i = lane; i < P.nvar; i += 64) vg[band_il_offset(nnz - P.nvar + i, vstride)] = wq;
-        } else {
-          double* vt = gvals + (long long)(prob0 + q) * nnz + (nnz - P.nvar);
-          for (int i = lane; i < P.nvar; i += 64) vt[i] = wq;
-        }
-      }
-    }
-  }
-}
-
-// variants (tuning key band_movers): 1 = 16 problems per group, two blocks per lane (v5); 2 = 32 per group, one block (v6); 3 = 16, one block
-static int mw_nl(int variant) { return variant == 2 ? 32 : 16; }
-int band_mw_group(int variant) { return variant >= 1 && variant <= 3 ? mw_nl(variant) : 0; }
-size_t band_mw_lds_bytes(int variant) {
-  const int nl = mw_nl(variant);
-  return ((size_t)4 * nl * mw_lane_d(variant == 1) + 2 * (2 * nl + 8)) * sizeof(double) + (size_t)4 * BAND_REC_MAX * 4;
-}
-
-hipError_t launch_band_mw(const BandDev& P, int variant, const LaunchArgs& a, hipStream_t stream) {
-  if (P.nparts != 2 || variant < 1 || variant > 3) return hipErrorInvalidConfiguration;
-  const size_t ldsb = band_mw_lds_bytes(variant);
-  const int nl = mw_nl(variant);
-  const int grid = (a.batch + 2 * nl - 1) / (2 * nl);
-  auto go = [&](auto kern) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)ldsb));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), ldsb, stream, P, a);
-    return hipGetLastError();
-  };
-  if (variant == 1) return go(band_newton_mw_kernel<16, true>);
-  if (variant == 2) return go(band_newton_mw_kernel<32, false>);
-  return go(band_newton_mw_kernel<16, false>);
-}
-
-#else
-int band_mw_group(int) { return 0; }
-size_t band_mw_lds_bytes(int) { return (size_t)-1; }   // (not compiled in: see the experiment above)
-hipError_t launch_band_mw(const BandDev&, int, const LaunchArgs&, hipStream_t) { return hipErrorNotSupported; }
-#endif
 size_t band_lds_bytes(int nparts, int nl) { return ((size_t)nparts * nl * LANE_D + 2 * nl + 8) * sizeof(double) + (size_t)nparts * BAND_REC_MAX * 4; }
 
 hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream) {

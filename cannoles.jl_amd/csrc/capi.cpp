@@ -44,9 +44,6 @@ struct cnl_plan {
   std::vector<int32_t> band_info, band_pinfo[2];
 };
 
-#ifndef CNL_PIPE_UPLOADERS
-#define CNL_PIPE_UPLOADERS 2
-#endif
 struct cnl_handle {
   cnl_plan* plan = nullptr;
   int device = 0;
@@ -106,7 +103,7 @@ struct cnl_handle {
   bool tail_fresh = false;    // the factors of the remainder live in the tail handle (false: in this handle's storage — chunked host calls)
   hipStream_t aux_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  static constexpr int kPipeUp = CNL_PIPE_UPLOADERS;  // host threads that upload chunks of a host-pointer call (each on its own stream)
+  static constexpr int kPipeUp = 2;  // host threads that upload chunks of a host-pointer call (each on its own stream)
   hipStream_t pipe_stream[kPipeUp + 1] = {};  // chunked host-pointer calls: the uploaders' compute streams, one more for the results
   std::vector<hipEvent_t> pipe_ev;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -129,7 +126,6 @@ struct cnl_handle {
   bool jac_segments = false;   // the J_F and the J_c entries are one run of slots each: [jf_lo, jf_lo + jf_n), [jc_lo, jc_lo + jc_n)
   int64_t jf_lo = 0, jf_n = 0, jc_lo = 0, jc_n = 0;
   int layout = 0;              // band handles: bit 0 = vals (cnl_options.batch_layout), bit 1 = rhs interleaved over groups of 32 problems (band.h)
-  int band_mw = 0;             // EXPERIMENT builds: the kernel with loader wavefronts serves the handle (band.hip, band_newton_mw_kernel)
   double* d_Lband = nullptr;   // [batch][bd.lsize] factor records of the band kernels
 };
 
@@ -375,7 +371,7 @@ int launch(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
     cnl::LaunchArgs b = a;
     b.L = h->d_Lband;
     b.layout = h->layout;
-    e = h->band_mw ? cnl::launch_band_mw(h->bd, h->band_mw, b, stream) : cnl::launch_band(h->bd, h->band_nl, b, stream);
+    e = cnl::launch_band(h->bd, h->band_nl, b, stream);
     g_launches[0]++;
   } else if (h->layout) {
     return fail(CNL_ERR_STATE, "this call is not served by the band kernels: a handle with batch_layout = CNL_LAYOUT_INTERLEAVED has no other");
@@ -768,7 +764,7 @@ int ensure_staging(cnl_handle* h) {
   h->d_rho_old = h->d_rho + B;
   h->d_nfact = reinterpret_cast<int32_t*>(h->d_rho_old + B);
   h->d_success = h->d_nfact + B;
-  if ((rc = dalloc(h, &h->d_npos, B * 2 + 64))) return rc;   // (+ 64: the phase stamps of diagnostic builds land here)
+  if ((rc = dalloc(h, &h->d_npos, B * 2))) return rc;
   h->d_nzero = h->d_npos + B;
   return CNL_OK;
 }
@@ -843,13 +839,8 @@ extern "C" {
 static int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device);
 
 const char* cnl_last_error(void) { return g_err.c_str(); }
-// 0.2.0 (round 4: in-kernel device ladder, cnl_options grew).  An EXPERIMENT build (timing probes, diagnostic stamps: results may be
-// wrong, see kernels2.hip) reports a NEGATIVE version; hipldl.py and the Julia glue refuse to load one unless asked to.
-#ifdef CNL_EXPERIMENT
-int32_t cnl_version(void) { return -200; }
-#else
+// 0.2.0 (round 4: in-kernel device ladder, cnl_options grew)
 int32_t cnl_version(void) { return 200; }
-#endif
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62
@@ -1299,12 +1290,6 @@ static int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* ro
     // 32 per workgroup (the LDS of a CU holds two such workgroups: 16384 problems resident) — tools/time_band.py
     h->band_nl = plan->opt.band_problems_per_group > 0 ? plan->opt.band_problems_per_group : (batch > 8192 ? 32 : 16);
     if (h->band_nl != 8 && h->band_nl != 16 && h->band_nl != 32) return bail(fail(CNL_ERR_ARG, "band_problems_per_group must be 8, 16 or 32"));
-    if (plan->opt.band_movers > 0 && cnl::band_mw_group(plan->opt.band_movers) == 0)
-      return bail(fail(CNL_ERR_ARG, "tuning key band_movers (1 .. 3) needs a library built with -DCNL_EXPERIMENT=1 -DBAND_MW (csrc/band.hip)"));
-    if (plan->opt.band_movers > 0 && bd.nparts == 2 && cnl::band_mw_lds_bytes(plan->opt.band_movers) <= std::min<size_t>(cnl::max_lds_bytes(), 160 * 1024)) {
-      h->band_mw = plan->opt.band_movers;
-      h->band_nl = cnl::band_mw_group(h->band_mw);
-    }
     // 32-bit byte offsets inside a workgroup's problems
     const uint64_t span = 8ull * (uint64_t)h->band_nl * (uint64_t)std::max<int64_t>({(int64_t)nnz, N, bd.lsize});
     if (span < (1ull << 32) && cnl::band_lds_bytes(bd.nparts, h->band_nl) <= std::min<size_t>(cnl::max_lds_bytes(), 160 * 1024)) {
@@ -1699,20 +1684,12 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   cfg[5] = (h->dense || h->gdense) ? 3 : (h->use_v2 ? (h->staged ? 4 : 2) : 1);
   if (h->lean && !h->dense && !h->gdense) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->tail) cfg[5] |= 32;                             // the remainder of the batch runs on a handle of its own (split_tail)
-  if (h->band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | (h->band_mw ? (int64_t)1 << 24 : 0) | ((int64_t)h->layout << 25);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts
+  if (h->band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->layout << 25);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts
   if (h->djt.rv_ntiles > 0) cfg[5] |= 128;               // row f1 runs on column tiles (kernels.h: DevJt::rv_*)
   cfg[6] = h->wpb2;
   cfg[7] = (int64_t)h->lds2;
   return CNL_OK;
 }
-
-#ifdef CNL_STAMPS
-int cnl_debug_stamps(cnl_handle* h, int64_t* out, int64_t n) {
-  if (!h || !h->d_npos) return fail(CNL_ERR_ARG, "no stamps");
-  HIPCHK(hipMemcpy(out, h->d_npos, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
-  return CNL_OK;
-}
-#endif
 
 // ---- device-pointer entry points -------------------------------------------------
 int cnl_factorize_dev(cnl_handle* h, const double* d_vals, double eig_tol, int32_t* d_success, void* stream) {
@@ -2097,9 +2074,6 @@ int cnl_newton_system(cnl_handle* h, double* vals, const double* rhs, double* d,
   a.mode = cnl::MODE_NEWTON;
   a.rho_old = h->d_rho_old; a.rho = h->d_rho;
   a.nfact = h->d_nfact; a.success = h->d_success;
-#ifdef CNL_STAMPS
-  a.npos = h->d_npos;  // diagnostic build: per-wave phase stamps land here (cnl_debug_stamps)
-#endif
   std::memcpy(a.params, params, 9 * sizeof(double));
   // Small batches on a staged handle: the rho ladder is driven from the HOST, like the reference's own newton_system!
   // (src/CaNNOLeS.jl:1023-1047) — every rung is a staged try_to_factorize (all tasks of the elimination tree in parallel, ~0.1 ms)

@@ -441,17 +441,11 @@ __device__ __forceinline__ void row_tile_ptrs(const DnDev& D, int b, int k, int 
 __global__ void __launch_bounds__(256) dn_panel(DnDev D, int k, double eig_tol, int b0) {
   __shared__ PanelLds P;
   const int b = b0 + blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#ifdef DN_STAMPS
-  const long long st0 = __builtin_amdgcn_s_memtime();
-#endif
   if (threadIdx.x == 0) P.pub[0] = 0;
   __syncthreads();
   if (wave == 0) {
     int np, nz;
     panel_diag(P, D.S + (size_t)b * D.T * D.T * TT + tile_off(D.T, k, k), min(64, D.ns - 64 * k), eig_tol, np, nz);
-#ifdef DN_STAMPS
-    if (lane == 0 && blockIdx.x == 0) { long long* sp = reinterpret_cast<long long*>(D.jxp); sp[k * 4 + 0] = __builtin_amdgcn_s_memtime() - st0; }
-#endif
     if (blockIdx.x == 0) {
       lds_fence();
       D.dv[(size_t)b * D.nsp + 64 * k + lane] = P.W[lane * 64 + lane];
@@ -466,9 +460,6 @@ __global__ void __launch_bounds__(256) dn_panel(DnDev D, int k, double eig_tol, 
       const double* in; double* out; double* wout; bool ident;
       row_tile_ptrs(D, b, k, rt, in, out, wout, ident);
       panel_rows(P, in, out, wout, ident);
-#ifdef DN_STAMPS
-      if (lane == 0 && blockIdx.x == 0) { long long* sp = reinterpret_cast<long long*>(D.jxp); sp[k * 4 + wave] = __builtin_amdgcn_s_memtime() - st0; }
-#endif
     }
   }
 }
@@ -483,12 +474,6 @@ __global__ void __launch_bounds__(256) dn_panel(DnDev D, int k, double eig_tol, 
 // operands of a plain v_fmac_f64), only the blocks to the right read the published column back.
 // Workgroup = row tile rt of the tile column: waves 0 .. 3 the diagonal tile's blocks (recomputed by every workgroup, as
 // before), waves 4 .. 7 the row tile's.  Multipliers of the row tile go from block to block through LDS (Lr).
-#ifndef DN_P2_SINGLES   // pivots of the block to the left that are applied one at a time (finer hand-over): measured 0.428 ms per system
-#define DN_P2_SINGLES 0  // with 0, 0.431 with 4, 0.435 with 8 — the coarser wait keeps more loads in flight
-#endif
-#ifndef DN_P2_ABL   // timing experiments (results wrong): 1 no row tiles, 2 no earlier-block updates in the diagonal tile, 4 no in-block
-#define DN_P2_ABL 0 // bulk in the diagonal tile, 8 no earlier-block updates in the row tiles
-#endif
 struct Panel2Lds {
   double W[TS * TS];   // [J][r]: column J of the diagonal tile at the moment pivot J is taken (undivided)
   double Lr[TS * TS];  // [J][r]: multiplier of pivot J for row r of the row tile
@@ -560,8 +545,8 @@ __device__ __forceinline__ void diag_own(Panel2Lds& P, double (&a)[16], int q, i
   // operand register of THIS pivot's remaining updates (columns >= JJ + 3): read back now, used a pivot later, behind the next
   // chain's first instructions — its LDS round trip never stalls the in-order issue
   double w = 0.0;
-  if constexpr (JJ + 3 < 16 && !(DN_P2_ABL & 4)) w = P.W[J * 64 + 16 * q + li];
-  if constexpr (JJ >= 1 && JJ + 2 < 16 && !(DN_P2_ABL & 4)) blk_update<JJ + 2>(a, wprev, nlprev);
+  if constexpr (JJ + 3 < 16) w = P.W[J * 64 + 16 * q + li];
+  if constexpr (JJ >= 1 && JJ + 2 < 16) blk_update<JJ + 2>(a, wprev, nlprev);
   if constexpr (JJ + 1 < 16) diag_own<JJ + 1>(P, a, q, lane, li, nreal, eig_tol, np, nz, rrn, w, nl);
 }
 
@@ -571,21 +556,15 @@ __device__ __forceinline__ void panel2_diag_block(Panel2Lds& P, const double* __
 #pragma unroll
   for (int c = 0; c < 16; c++) a[c] = tile[lane + 64 * (16 * q + c)];
   const int li = lane & 15;
-  const int nbulk = (DN_P2_ABL & 2) ? 0 : 16 * q - DN_P2_SINGLES;
-  for (int J0 = 0; J0 < nbulk; J0 += 4) {  // four pivots per wait: their operands are in flight together
+  // four pivots per wait: their operands are in flight together (taking the left block's last 4 or 8 pivots one at a time, a finer
+  // hand-over, measured 0.431 / 0.435 against 0.428 ms per system: the coarser wait keeps more loads in flight)
+  for (int J0 = 0; J0 < 16 * q; J0 += 4) {
     lds_wait_ge(&P.pub[0], J0 + 4);
     double l[4], w[4];
 #pragma unroll
     for (int u = 0; u < 4; u++) { l[u] = P.W[(J0 + u) * 64 + lane] * P.inv[J0 + u]; w[u] = P.W[(J0 + u) * 64 + 16 * q + li]; }
 #pragma unroll
     for (int u = 0; u < 4; u++) blk_update<0>(a, w[u], -l[u]);
-  }
-  // the last pivots of the block to the left one at a time: this wavefront's own chain starts right behind its last pivot
-  for (int J = nbulk < 0 ? 0 : nbulk; J < 16 * q && !(DN_P2_ABL & 2); J++) {
-    lds_wait_ge(&P.pub[0], J + 1);
-    const double l = P.W[J * 64 + lane] * P.inv[J];
-    const double w = P.W[J * 64 + 16 * q + li];
-    blk_update<0>(a, w, -l);
   }
   np = 0; nz = 0;
   diag_own<0>(P, a, q, lane, li, nreal, eig_tol, np, nz, __builtin_amdgcn_rcp(readlane_f64(a[0], 16 * q)), 0.0, 0.0);
@@ -625,7 +604,7 @@ __device__ __forceinline__ void panel2_rows_block(Panel2Lds& P, const double* __
 #pragma unroll
   for (int c = 0; c < 16; c++) x[c] = ident ? ((16 * q + c) == lane ? 1.0 : 0.0) : in[lane + 64 * (16 * q + c)];
   const int li = lane & 15;
-  for (int J0 = 0; J0 < 16 * q && !(DN_P2_ABL & 8); J0 += 4) {
+  for (int J0 = 0; J0 < 16 * q; J0 += 4) {
     lds_wait_ge(&P.pub[1], J0 + 4);
     double l[4], w[4];
 #pragma unroll
@@ -643,16 +622,10 @@ __global__ void __launch_bounds__(512) dn_panel2(DnDev D, int k, double eig_tol)
   Panel2Lds& P = *reinterpret_cast<Panel2Lds*>(dn_p2_lds);
   const int b = blockIdx.y, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (threadIdx.x == 0) { P.pub[0] = 0; P.pub[1] = 0; }
-#ifdef DN_STAMPS
-  const long long st0 = __builtin_amdgcn_s_memtime();
-#endif
   __syncthreads();
   if (wave < 4) {
     int np, nz;
     panel2_diag_block(P, D.S + (size_t)b * D.T * D.T * TT + tile_off(D.T, k, k), wave, lane, min(64, D.ns - 64 * k), eig_tol, np, nz);
-#ifdef DN_STAMPS
-    if (lane == 0 && blockIdx.x == 0) { long long* sp = reinterpret_cast<long long*>(D.jxp); sp[D.T * 4 + k * 8 + wave] = __builtin_amdgcn_s_memtime() - st0; }
-#endif
     if (blockIdx.x == 0) {
       if (lane >= 16 * wave && lane < 16 * wave + 16) D.dv[(size_t)b * D.nsp + 64 * k + lane] = P.W[lane * 64 + lane];  // own column: written by this wave
       if (lane == 0) {
@@ -660,14 +633,11 @@ __global__ void __launch_bounds__(512) dn_panel2(DnDev D, int k, double eig_tol)
         if (nz) atomicAdd(&D.cnt[b * 4 + 1], nz);
       }
     }
-  } else if (!(DN_P2_ABL & 1)) {
+  } else {
     const int rt = blockIdx.x;
     const double* in; double* out; double* wout; bool ident;
     row_tile_ptrs(D, b, k, rt, in, out, wout, ident);
     panel2_rows_block(P, in, out, wout, ident, wave - 4, lane);
-#ifdef DN_STAMPS
-    if (lane == 0 && blockIdx.x == 0) { long long* sp = reinterpret_cast<long long*>(D.jxp); sp[D.T * 4 + k * 8 + wave] = __builtin_amdgcn_s_memtime() - st0; }
-#endif
   }
 }
 
@@ -1171,9 +1141,6 @@ int upload_(DenseState* st, const T** p, const std::vector<T>& v, std::string& e
 // sizes, tile lists and buffers common to both forms
 int setup_common(DenseState* st, int ns, int nv, int64_t batch, std::string& err) {
   DnDev& d = st->d;
-#ifdef DN_STAMPS
-  st->use_graph = false;
-#endif
   d.ns = ns; d.nv = nv; d.T = (ns + TS - 1) / TS; d.nsp = d.T * TS;
   d.nlt = d.T * (d.T + 1) / 2;
   // The column-block panel kernel shortens the latency of a step at the price of T workgroups per problem that each refactorise
@@ -1464,17 +1431,6 @@ int dense_enqueue(DenseState* st, int mode, double* vals, const double* rhs, dou
     else
       hipLaunchKernelGGL(dn_decide, dim3(blocks(B)), dim3(256), 0, stream, d, B, mode, nullptr, success, npos, nzero);
     DCHK(hipGetLastError());
-#ifdef DN_STAMPS
-    if (mode == 1) {
-      (void)hipStreamSynchronize(stream);
-      std::vector<long long> hs(d.T * 4);
-      (void)hipMemcpy(hs.data(), d.jxp, hs.size() * sizeof(long long), hipMemcpyDeviceToHost);
-      for (int k2 = 0; k2 < d.T; k2++) fprintf(stderr, "[dn stamps] k=%d diag %lld rows %lld %lld %lld\n", k2, hs[k2 * 4], hs[k2 * 4 + 1], hs[k2 * 4 + 2], hs[k2 * 4 + 3]);
-      std::vector<long long> h2(d.T * 8);
-      (void)hipMemcpy(h2.data(), reinterpret_cast<long long*>(d.jxp) + d.T * 4, h2.size() * sizeof(long long), hipMemcpyDeviceToHost);
-      for (int k2 = 0; k2 < d.T; k2++) fprintf(stderr, "[dn stamps2] k=%d diag blocks %lld %lld %lld %lld rows %lld %lld %lld %lld\n", k2, h2[k2 * 8], h2[k2 * 8 + 1], h2[k2 * 8 + 2], h2[k2 * 8 + 3], h2[k2 * 8 + 4], h2[k2 * 8 + 5], h2[k2 * 8 + 6], h2[k2 * 8 + 7]);
-    }
-#endif
     if (mode == 1) return 0;
   }
   const int gate = mode == 0 ? 1 : 0;

@@ -31,33 +31,13 @@
 
 #include "kernels.h"
 
-// timing experiments only (tests/support/ablate.py): -DCNL_ABL=<bits> removes pieces of the hot path; results are wrong
-#ifndef CNL_ABL
-#define CNL_ABL 0
-#endif
-// Every switch that makes this file compute something else than the product (timing probes with wrong or unguaranteed results,
-// diagnostic stamps, the shortened division) compiles only in an EXPERIMENT build: -DCNL_EXPERIMENT=1, which also turns
-// cnl_version() negative (capi.cpp) so that such a library cannot pass for the product.
-#if (CNL_ABL != 0) || defined(CNL_DBG_NOCONF) || defined(CNL_DBG_VSTRIDE0) || defined(CNL_DBG_LSTRIDE0) || defined(CNL_DF_NOFENCE) || \
-    defined(CNL_STAMPS) || (defined(CNL_QUICK_DIV) && CNL_QUICK_DIV) || defined(CNL_DBG_COALJ)
-#ifndef CNL_EXPERIMENT
-#error "timing probes / diagnostic builds need -DCNL_EXPERIMENT=1 (cnl_version() then reports an experimental library)"
-#endif
-#endif
-
 namespace cnl {
 
 namespace {
 
 constexpr int RN = 3;    // record prefetch: RN x dwordx4 per lane = RN*256 words
-#ifndef CNL_PVR
-#define CNL_PVR 6
-#endif
-#ifndef CNL_PVN
-#define CNL_PVN 8
-#endif
-constexpr int PVR = CNL_PVR;   // raw-value prefetch of the on-the-fly condensation: PVR*16 matrix values per problem (+ 2 x 16 rhs values)
-constexpr int PVN = CNL_PVN;   // value prefetch: PVN doubles per lane = PVN*16 entries per problem
+constexpr int PVR = 6;   // raw-value prefetch of the on-the-fly condensation: PVR*16 matrix values per problem (+ 2 x 16 rhs values)
+constexpr int PVN = 8;   // value prefetch: PVN doubles per lane = PVN*16 entries per problem
 constexpr int KB = 10;   // panel rows prefetched per front in the solve sweeps (chain-like orders: up to 10 pivots per front)
 
 __device__ __forceinline__ int tri2(int i) { return (i * (i + 1)) >> 1; }
@@ -103,29 +83,21 @@ __device__ __forceinline__ double bcast(double v, int a, int grp4) {
 // fix-up steps; a zero or non-finite pivot still yields inf/NaN, which fails the inertia test anyway)
 // v_rcp_f64 is good to ~2^-25 (measured on gfx950); one Newton step brings the reciprocal to ~10 ulp, and the
 // residual correction of the quotient squares that error away: q' = q + (w - d q) r = (w/d)(1 - eps^2).
-#ifndef CNL_QUICK_DIV
-#define CNL_QUICK_DIV 0
-#endif
 __device__ __forceinline__ double fast_div(double w, double d) {
   double r = __builtin_amdgcn_rcp(d);
-#if !CNL_QUICK_DIV
   const double e = fma(-d, r, 1.0);
   r = fma(r, e, r);
-#endif
   const double q = w * r;
   const double res = fma(-d, q, w);
   return fma(res, r, q);
 }
 
-#ifndef CNL_DPP_BC
-#define CNL_DPP_BC true
-#endif
 template <int CTRL>
 __device__ __forceinline__ double dpp_mov(double v) {
   // bound_ctrl: every lane of a row rotation reads a valid lane, so the destination needs no initial value (the compiler
   // emitted a v_mov 0 in front of every DPP move otherwise: 8 of the 24 instructions of a 16-lane sum)
-  int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, CNL_DPP_BC);
-  int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, CNL_DPP_BC);
+  int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
+  int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
   return __hiloint2double(hi, lo);
 }
 
@@ -140,25 +112,6 @@ __device__ __forceinline__ double gsum(double v) {
   if (TE >= 64) v += __shfl_xor(v, 32, 64);
   return v;
 }
-
-// optional in-kernel stamps (diagnostic build only: -DCNL_STAMPS); sums of s_memtime deltas per phase
-#ifdef CNL_STAMPS
-#define STAMP_DECL unsigned long long st_t0 = 0, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define STAMP_BEGIN { __builtin_amdgcn_sched_barrier(0); st_t0 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
-#if CNL_STAMPS == 2   // the backward sweep in detail (BSTAMP 0..5); everything else in slot 7
-#define STAMP(k) { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[7] += t_ - st_t0; st_t0 = t_; __builtin_amdgcn_sched_barrier(0); }
-#define BSTAMP(k) { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_t0; st_t0 = t_; __builtin_amdgcn_sched_barrier(0); }
-#else
-#define STAMP(k) { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_t0; st_t0 = t_; __builtin_amdgcn_sched_barrier(0); }
-#endif
-#else
-#define STAMP_DECL
-#define STAMP_BEGIN
-#define STAMP(k)
-#endif
-#ifndef BSTAMP
-#define BSTAMP(k)
-#endif
 
 struct Ctx2 {
   const double* vals;   // batch base
@@ -202,20 +155,12 @@ struct Ctx2 {
 // fast fronts (order <= 16, LDS staging): the image is the packed triangle (plan.h, FAST_IMG_*), row a at a(a+1)/2, so the
 // 16 row loads are one base address plus immediate offsets; lanes past the diagonal read entries of later rows (never used)
 #define CNL_LOADS(k) r##k = Fss[((15 - k) * (16 - k)) / 2];
-#ifdef CNL_STAMPS
-#define ESTAMP0 unsigned long long et0_ = 0; if (st_) { __builtin_amdgcn_sched_barrier(0); et0_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
-#define ESTAMP(k) if (st_) { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_[k] += t_ - et0_; et0_ = t_; __builtin_amdgcn_sched_barrier(0); }
-#else
-#define ESTAMP0
-#define ESTAMP(k)
-#endif
 #define CNL_DEFINE_ELIM(NAME, INL, TEV, GFS, ALL, REV, STEPS, LOADM)                                                   \
   __device__ INL void NAME(int P_prob_doubles, int P_u2_peak, long long P_gs_doubles, long long P_lsize, double* cL_,   \
                            double* cgs_, int cbatch, int lane, int prob0, int pass,                                   \
                            int f, int nupd, long long lptr, int uoff, int fsoff, bool uglob, double* pbase0,          \
-                           int* cnt, double eig_tol, unsigned long long* st_ = nullptr) {                              \
+                           int* cnt, double eig_tol) {                                                                 \
     Ctx2 c;                                                                                                            \
-    ESTAMP0                                                                                                            \
     c.L = as_global(cL_); c.gs = as_global(cgs_); c.batch = cbatch;                                                    \
     constexpr int TE_ = TEV;                                                                                           \
     constexpr int PPW = 64 / TE_;                                                                                      \
@@ -239,7 +184,6 @@ struct Ctx2 {
     (void)Fss;                                                                                                         \
     ALL(CNL_DECL)                                                                                                      \
     ALL(LOADM)                                                                                                         \
-    ESTAMP(7)                                                                                                          \
     int npos = 0, nzer = 0;                                                                                            \
     (void)grp4;                                                                                                        \
     for (int i = top; i > nupd; i--) {                                                                                 \
@@ -253,19 +197,18 @@ struct Ctx2 {
       const double lv = fast_div(w, dpiv);                                                                             \
       npos += dpiv > eig_tol;                                                                                          \
       nzer += fabs(dpiv) <= eig_tol;                                                                                   \
-      if (valid && b <= i && !(CNL_ABL & 64)) Lp[tri2(i) - tu + b] = (b == i) ? dpiv : lv;                                                \
-      if (1 >= i || (CNL_ABL & 32)) goto rows_done;                                                                    \
+      if (valid && b <= i) Lp[tri2(i) - tu + b] = (b == i) ? dpiv : lv;                                               \
+      if (1 >= i) goto rows_done;                                                                                      \
       STEPS(CNL_STEPP, CNL_CHK, CNL_STEPA)                                                                             \
     rows_done:;                                                                                                        \
     }                                                                                                                  \
-    ESTAMP(5)                                                                                                          \
     if (b == 0) { cnt[gp * 2] += npos; cnt[gp * 2 + 1] += nzer; }                                                      \
     if (uglob) {                                                                                                       \
       if (valid) {                                                                                                     \
         double* Ug = c.gs + pclamp * P_gs_doubles + uoff;                                                              \
         REV(CNL_USTG)                                                                                                  \
       }                                                                                                                \
-    } else if (!(CNL_ABL & 128)) {                                                                                     \
+    } else {                                                                                                           \
       double* Ul = pb + uoff;                                                                                          \
       REV(CNL_USTL)                                                                                                    \
     }                                                                                                                  \
@@ -284,22 +227,7 @@ struct Ctx2 {
 // a backward sweep fed by global_load_lds_dwordx4 with headers through the scalar cache, a four-operation division chain — are
 // recorded in profiles/HISTORY.md section 4; their code lives in the git history, not here.)
 #define CNL_DPP_DIV fast_div
-#ifndef CNL_PIV_BITMASK
-#define CNL_PIV_BITMASK 1
-#endif
-#if CNL_PIV_BITMASK
 #define CNL_PIV_GUARD(i) (pm_ & (1u << (i)))
-#else
-#define CNL_PIV_GUARD(i) ((i) <= top && (i) > nupd)
-#endif
-#ifndef CNL_LANE_OPAQUE
-#define CNL_LANE_OPAQUE 1
-#endif
-#if CNL_LANE_OPAQUE
-#define CNL_LANE_FENCE asm volatile("" : "+v"(bm_));
-#else
-#define CNL_LANE_FENCE
-#endif
 #include "elim_dpp.inc"
 // L rows one front late.  Stores and loads return out of order with respect to each other, so a wait for ANY load is a
 // vmcnt(0) while stores are in flight: with the ten row stores of a front issued during its elimination, the first use of the
@@ -321,7 +249,7 @@ struct LPend {
 };
 #define CNL_LROW_OUT(i)                                                                                                              \
   if constexpr (LATE) LP.v##i = (bm_ == i) ? dpiv : lv;                                                                              \
-  else if (bm_ <= i && !(CNL_ABL & 64)) *reinterpret_cast<double*>(L_wb + (lofs + ((unsigned)tri2(i) << 3))) = (bm_ == i) ? dpiv : lv;
+  else if (bm_ <= i) *reinterpret_cast<double*>(L_wb + (lofs + ((unsigned)tri2(i) << 3))) = (bm_ == i) ? dpiv : lv;
 __device__ __forceinline__ void flush_lrows(LPend& LP, char* L_wb0, int bm_) {
   if (LP.pm == 0) return;
   char* L_wb = L_wb0 + (LP.lptr << 3);
@@ -329,7 +257,7 @@ __device__ __forceinline__ void flush_lrows(LPend& LP, char* L_wb0, int bm_) {
 #define CNL_LP_FLUSH(i)                                                                                                   \
   if (LP.pm & (1u << i)) {                                                                                                \
     asm volatile("" : "+v"(bm_));                                                                                         \
-    if (bm_ <= i && !(CNL_ABL & 64)) *reinterpret_cast<double*>(L_wb + (lofs + ((unsigned)tri2(i) << 3))) = LP.v##i;      \
+    if (bm_ <= i) *reinterpret_cast<double*>(L_wb + (lofs + ((unsigned)tri2(i) << 3))) = LP.v##i;                         \
   }
   CNL_LPEND_LIST(CNL_LP_FLUSH)
 #undef CNL_LP_FLUSH
@@ -347,9 +275,9 @@ __device__ __forceinline__ void flush_lrows(LPend& LP, char* L_wb0, int bm_) {
   nzer += fabs(dpiv) <= eig_tol;                                                                          \
   /* the lane number is made opaque per pivot: the sixteen (b <= i) and sixteen (b == i) lane masks would otherwise be hoisted  */ \
   /* out of the fronts loop into 64 SGPRs, spilled to VGPR lanes and fetched back with two v_readlane each (round 2 ISA)       */ \
-  CNL_LANE_FENCE                                                                                          \
+  asm volatile("" : "+v"(bm_));                                                                           \
   CNL_LROW_OUT(i)                                                                                         \
-  const double nl_ = (CNL_ABL & 32) ? 0.0 : -lv;
+  const double nl_ = -lv;
 #define CNL_DPP_POST(i)
 #define CNL_DPP_USTG(a) if (a <= nupd) Ug[tri2(a) + b] = R##a;
 #define CNL_DPP_USTL(a) if (a <= nupd) Ul[tri2(a) + b] = R##a;
@@ -399,7 +327,7 @@ __device__ __forceinline__ void eliminate16_dpp(int P_prob_doubles, int P_u2_pea
       double* Ug = gsg + pclamp * P_gs_doubles + uoff;
       CNL_DPP_ROWS(CNL_DPP_USTG)
     }
-  } else if (!(CNL_ABL & 128)) {
+  } else {
     double* Ul = pb + uoff;
     CNL_DPP_ROWS(CNL_DPP_USTL)
   }
@@ -628,15 +556,12 @@ __device__ __attribute__((noinline)) void slow_front(const int* prec_,
 // rows past the last pivot read finite data that is never used (the factor storage is zero-padded).
 // Same addressing as the forward gathers (wave-uniform base + 32-bit byte offset); rows past the last pivot are
 // not loaded.
-#ifndef CNL_DBG_LSTRIDE0   // timing probe: every problem reads problem 0's factor in the solve sweeps (cache hits; wrong results)
-#define CNL_DBG_LSTRIDE0 0
-#endif
 #define PREFETCH_ROWS(DST, LPTR, NUPD, NPIV)                                           \
   {                                                                                    \
-    const char* rb_ = CNL_DBG_LSTRIDE0 ? reinterpret_cast<const char*>(A.L) + ((long long)(LPTR) << 3) : L_wb + ((long long)(LPTR) << 3); \
-    unsigned ro_ = CNL_DBG_LSTRIDE0 ? (unsigned)l * 8u : gofs_l;                       \
+    const char* rb_ = L_wb + ((long long)(LPTR) << 3);                                 \
+    unsigned ro_ = gofs_l;                                                             \
     _Pragma("unroll") for (int k = 0; k < KB; k++) {                                   \
-      if (k < (NPIV) && !(CNL_ABL & 16384)) DST[k] = *reinterpret_cast<const double*>(rb_ + ro_); else DST[k] = 0.0; \
+      if (k < (NPIV)) DST[k] = *reinterpret_cast<const double*>(rb_ + ro_); else DST[k] = 0.0; \
       ro_ += (unsigned)((NUPD) + 2 + k) << 3;                                          \
     }                                                                                  \
   }
@@ -685,17 +610,10 @@ __device__ __attribute__((noinline)) void slow_front(const int* prec_,
     if (nv_ + 16 < nr_) prr[1] = GATHER_R(src_[PVR + 1]); else prr[1] = 0.0;           \
   }
 
-// timing probe (results wrong): the Jacobian operands of the row form read 16 CONSECUTIVE doubles per problem and instruction (from
-// row 0's first operand on: the same 5 x 16 doubles a front of 16 band rows owns) instead of one operand of each row (lane stride
-// = row length) — what do the vector-memory pipeline's extra line look-ups of the strided form cost?  1: forward, 2: backward, 3: both
-// (round 4: nothing — 7.97 against 8.06 ms — although a strided gather costs a CU 58 cycles against 17, tools/vmem_bench.hip)
-#ifdef CNL_DBG_COALJ
-#define ROWJ_SRC(BIT, RECP, ROFF, J, SRCJ) ((CNL_DBG_COALJ & (BIT)) ? (((RECP) + (ROFF))[16] + 16 * (J) + l) : (SRCJ))
-#else
-#define ROWJ_SRC(BIT, RECP, ROFF, J, SRCJ) (SRCJ)
-#endif
 // Row form of the condensation products (plan.h, RF_ROWS): lane l takes residual row l of the front.  Seven gathers without a
 // guard: the row's pivot (kept in pvr[ROWS_KM]), its ROWS_KM Jacobian operands (pvr[0 ..]) and its right-hand-side entry.
+// (Reading the Jacobian operands as 16 consecutive doubles instead of strided was measured in round 4: nothing, 7.97 against
+// 8.06 ms, although a strided gather costs a CU 58 cycles against 17, tools/vmem_bench.hip.)
 static_assert(PVR == ROWS_KM + 1, "the raw-value prefetch registers double as the row operands");
 #define PREFETCH_ROWFORM(RECP, ROFF)                                                   \
   {                                                                                    \
@@ -703,7 +621,7 @@ static_assert(PVR == ROWS_KM + 1, "the raw-value prefetch registers double as th
     int src_[ROWS_KM + 2];                                                             \
     _Pragma("unroll") for (int j = 0; j < ROWS_KM + 2; j++) src_[j] = sp_[j * 16];     \
     pvr[ROWS_KM] = GATHER_V(src_[0]);                                                  \
-    _Pragma("unroll") for (int j = 0; j < ROWS_KM; j++) pvr[j] = GATHER_V(ROWJ_SRC(1, RECP, ROFF, j, src_[1 + j])); \
+    _Pragma("unroll") for (int j = 0; j < ROWS_KM; j++) pvr[j] = GATHER_V(src_[1 + j]);                    \
     prr[0] = GATHER_R(src_[ROWS_KM + 1]);                                              \
     prr[1] = 0.0;                                                                      \
   }
@@ -718,17 +636,13 @@ static_assert(PVR == ROWS_KM + 1, "the raw-value prefetch registers double as th
     _Pragma("unroll") for (int j = 0; j < ROWS_KM + 3; j++) src_[j] = (ON) ? sp_[j * 16] : 0; \
     if (!(ON)) { src_[ROWS_KM + 1] = P.nnz; src_[ROWS_KM + 2] = 0x11111; }             \
     DST[0] = GATHER_V(src_[0]);                                                        \
-    _Pragma("unroll") for (int j = 1; j < ROWS_KM + 1; j++) DST[j] = GATHER_V(ROWJ_SRC(2, RECP, ROFF, j - 1, src_[j])); \
+    _Pragma("unroll") for (int j = 1; j < ROWS_KM + 1; j++) DST[j] = GATHER_V(src_[j]);                    \
     DST[ROWS_KM + 1] = GATHER_R(src_[ROWS_KM + 1]);                                    \
     IXW = src_[ROWS_KM + 2];                                                           \
     RSRC = src_[ROWS_KM + 1] - P.nnz;                                                  \
   }
 // image position of pair K (compile-time) out of the lane's position words
-#ifdef CNL_DBG_NOCONF   // timing probe (results wrong): the row products' atomics land on sixteen consecutive doubles per problem — what do their bank conflicts cost?
-#define ROW_POS(PW, K) ((unsigned)(l + 16 * ((K) & 7)))
-#else
 #define ROW_POS(PW, K) (((unsigned)(PW)[(K) >> 2] >> (8 * ((K) & 3))) & 255u)
-#endif
 
 // ==========================================================================================
 // dataflow execution of a staged plan: wait until *p >= target, then make the producer's global stores visible; signal = all
@@ -736,13 +650,6 @@ static_assert(PVR == ROWS_KM + 1, "the raw-value prefetch registers double as th
 // index order, a time-sliced device — must not hang the device): a wait that gives up is COUNTED in status_total / status_call,
 // and the classic launch that follows every staged attempt then redoes the whole batch sequentially, so a timeout costs time,
 // never a wrong result.  Once one wait of the call has given up the others stop waiting at once.
-#ifdef CNL_DBG_TRACE   // experiment builds: records of four ints in a device buffer, printed by the launcher behind the ladder launch
-__device__ int cnl_trace_buf[1 << 16];
-__device__ int cnl_trace_n;
-#define CNL_TRACE(TAG, A_, B_, C_) do { if ((threadIdx.x & 63) == 0) { const int i_ = atomicAdd(&cnl_trace_n, 4); if (i_ < (1 << 16) - 4) { cnl_trace_buf[i_] = (TAG) | ((int)blockIdx.x << 8); cnl_trace_buf[i_ + 1] = (A_); cnl_trace_buf[i_ + 2] = (B_); cnl_trace_buf[i_ + 3] = (C_); } } } while (0)
-#else
-#define CNL_TRACE(TAG, A_, B_, C_) do { } while (0)
-#endif
 // Every branch of the wait is WAVE-UNIFORM by construction (the polled values go through readfirstlane, the give-up bookkeeping is
 // done by all lanes, 63 of which add zero).  Round 5, the root of the staged-execution fault of round 4 on plans with out-of-line
 // front classes: with the natural form — `if (!ok && lane == 0) { atomics }` — the region is lane-divergent for the compiler, and
@@ -750,24 +657,19 @@ __device__ int cnl_trace_n;
 // into the tail of that region, i.e. on a path the regular case never takes: the reloads behind the call then returned whatever
 // earlier kernels had left in scratch memory (pointers among them).  Garbage-filled scratch made it deterministic, zeroed scratch
 // hid it; ending the wavefront in the give-up branch (a tracing build) made it disappear.  (profiles/HISTORY.md 4c.)
-__device__ __forceinline__ void spin_until(const int* p, int target, int limit, int* status_total, int* status_call, [[maybe_unused]] int site = 0) {
+__device__ __forceinline__ void spin_until(const int* p, int target, int limit, int* status_total, int* status_call) {
   int ok = 0;
   for (int it = 0; it < limit; it++) {
     if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >= target) { ok = 1; break; }
     if ((it & 255) == 255 && __builtin_amdgcn_readfirstlane(__hip_atomic_load(status_call, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0) break;
     __builtin_amdgcn_s_sleep(4);
   }
-#ifdef CNL_DBG_TRACE
-  if (!ok) { CNL_TRACE(9, target, __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), site); __builtin_amdgcn_endpgm(); }
-#endif
   if (!ok) {   // scalar branch
     const int one = (threadIdx.x & 63) == 0 ? 1 : 0;
     __hip_atomic_fetch_add(status_total, one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_fetch_add(status_call, one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-#ifndef CNL_DF_NOFENCE   // (timing probe: -DCNL_DF_NOFENCE drops both fences; results are then not guaranteed)
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
 }
 // Commit of the in-kernel ladder for problem g of a group (see the only_if_status prologue of the kernel): out of line, so that
 // the hot instantiations pay nothing for it.
@@ -779,11 +681,7 @@ __device__ __noinline__ void ladder_commit(const int* lq, int g, int l, double* 
 }
 __device__ __forceinline__ void task_done(int* counter, int lane, bool release = true) {
   if (!counter) return;
-#ifndef CNL_DF_NOFENCE
   if (release) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#else
-  if (release) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
   __builtin_amdgcn_wave_barrier();
   if (lane == 0) __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -792,9 +690,7 @@ __device__ __forceinline__ void task_done(int* counter, int lane, bool release =
 // 68 % of that time; two share a SIMD at 16.3 k cycles per front.  A 168-register variant with THREE per SIMD (the triangle
 // image makes twelve wavefronts fit the LDS of a CU) was built and measured: 12 288 problems in 11.6 ms against 8 192 in
 // 7.24 ms — 6 % less throughput; the CU-wide units (LDS, scalar/branch issue) are what the third wavefront queues for.
-#ifndef CNL_WAVES_PER_SIMD
-#define CNL_WAVES_PER_SIMD 2
-#endif
+constexpr int WAVES_PER_SIMD = 2;
 // LEAN (round 3): plans whose fronts are all of the fast class with row-form (or no) condensation products — what the chain-like
 // orders of band problems give — run an instantiation WITHOUT the cold paths: the forward substitution of MODE_SOLVE, the
 // out-of-line front classes, raw-value staging and product lists.  Those paths are never executed for such plans, but they sit
@@ -808,7 +704,7 @@ __device__ __forceinline__ void task_done(int* counter, int lane, bool release =
 // (only_if_status): it commits the ladder's rho_old / rho slots, or redoes the call when a wait gave up — the commit is compiled
 // into this instantiation only (in the hot lean kernel the call cost four more spilled SGPRs).
 template <bool STAGED, bool LATE, bool LEAN, bool SOLVE = false, bool FUSED = false>
-__global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(const DevPlan2 Pin, const LaunchArgs Ain) {
+__global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const DevPlan2 Pin, const LaunchArgs Ain) {
   DevPlan2 P = Pin;
   P.rec = as_global(Pin.rec); P.brec = as_global(Pin.brec);
   LaunchArgs A = Ain;
@@ -932,18 +828,10 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
   const int xpos = A.extra_pos ? A.extra_pos[pclamp] : 0, xzer = A.extra_zer ? A.extra_zer[pclamp] : 0;
   // gathers: wave-uniform bases of the first problem of the wave + 32-bit byte offsets (4 problems span < 4 GB)
   const int prob0u = __builtin_amdgcn_readfirstlane(prob0);
-#ifdef CNL_DBG_VSTRIDE0   // timing probe (results wrong): every problem gathers problem 0's values — what do the gathers cost when they hit in cache?
-  const char* vals_wb = reinterpret_cast<const char*>(A.vals);
-#else
   const char* vals_wb = reinterpret_cast<const char*>(A.vals + (long long)prob0u * P.vstride);
-#endif
   const char* rhs_wb = has_rhs ? reinterpret_cast<const char*>(A.rhs + (long long)prob0u * P.rstride) : vals_wb;
   const unsigned gsel = inb ? (unsigned)g : 0u;
-#ifdef CNL_DBG_VSTRIDE0
-  const unsigned gofs_v = 0u;
-#else
   const unsigned gofs_v = gsel * (unsigned)P.vstride * 8u;
-#endif
   const unsigned gofs_r = (gsel * (unsigned)(has_rhs ? P.rstride : P.vstride) - (unsigned)P.nnz) * 8u;  // rhs sources are nnz + index
   const char* L_wb = reinterpret_cast<const char*>(A.L + (long long)prob0u * P.lsize);
   const unsigned gofs_l = (gsel * (unsigned)P.lsize + (unsigned)l) * 8u;
@@ -1145,10 +1033,8 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
     if constexpr (STAGED) { task_done(dep_signal, lane, A.df_live != 0); return; }  // the backward sweep of the tasks comes in a launch of its own
   }
 
-  STAMP_DECL
   const bool do_fwd = !SOLVE && (STAGED ? ((A.phase == 0 || (FUSED && A.phase == 2)) && A.mode != MODE_SOLVE) : A.mode != MODE_SOLVE);
   while (do_fwd) {
-    STAMP_BEGIN
     // ---------------- forward pass over the record stream ----------------
     if (l == 0) { cnt[g * 2] = STAGED ? 0 : xpos; cnt[g * 2 + 1] = STAGED ? 0 : xzer; }
     int rpos = 0, rzer = 0;  // per-lane tallies of the condensed residual pivots staged by this lane
@@ -1187,8 +1073,8 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
         const bool fast0 = (fw0 >> 8) == 16 && !(fw0 & RF_FS_GLOBAL);
         if (!CNL_LEAN && !fast0) {
           // rare: large or globally staged front, handled out of line
-          if constexpr (STAGED) if (DEP_WAITING) { spin_until(dep_wait, dep_target, A.spin_limit, as_global(A.status_total), as_global(A.status_call), 1); dep_wait = nullptr; }
-          if (!(CNL_ABL & 2048)) slow_front(P.rec, A.vals, has_rhs ? A.rhs : nullptr, A.L, A.scratch, A.batch, lane, prob0, recw, roff, pbase0, cnt, eig_tol, rho, ovr, P.count_d != 0);
+          if constexpr (STAGED) if (DEP_WAITING) { spin_until(dep_wait, dep_target, A.spin_limit, as_global(A.status_total), as_global(A.status_call)); dep_wait = nullptr; }
+          slow_front(P.rec, A.vals, has_rhs ? A.rhs : nullptr, A.L, A.scratch, A.batch, lane, prob0, recw, roff, pbase0, cnt, eig_tol, rho, ovr, P.count_d != 0);
           gsync();
           roff = nxt_off;
           s++;
@@ -1205,7 +1091,7 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
       bool more = true;
       bool img_clean = false;  // the staging image is known to be all zeros
       while (more) {
-      if constexpr (STAGED) if (DEP_WAITING) { spin_until(dep_wait, dep_target, A.spin_limit, as_global(A.status_total), as_global(A.status_call), 2); dep_wait = nullptr; }  // children's update matrices are read below
+      if constexpr (STAGED) if (DEP_WAITING) { spin_until(dep_wait, dep_target, A.spin_limit, as_global(A.status_total), as_global(A.status_call)); dep_wait = nullptr; }  // children's update matrices are read below
       const int* rec = recw;
       const int hv = rec[lane & 15];
       const int npiv = HDRW(hv, R_NPIV), nupd = HDRW(hv, R_NUPD), nasm = HDRW(hv, R_NASM);
@@ -1226,12 +1112,12 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
         if (l < FAST_IMG_DOUBLES / 2 - 64) z2[64] = make_double2(0.0, 0.0);
         wsync();
       }
-      img_clean = !(CNL_ABL & 1024);
+      img_clean = true;
       // (2) extend-add the children's update matrices: needs nothing from global memory, so the stores of the
       //     previous front (L rows) retire behind it before the prefetched values are waited for
       {
         int co = coff;
-        for (int ci = 0; ci < ((CNL_ABL & 16) ? 0 : nchild); ci++) {
+        for (int ci = 0; ci < nchild; ci++) {
           const int cv = rec[co + (lane & 3)];
           const int cu = HDRW(cv, C_UOFF), tuc = HDRW(cv, C_TUC), cfl = HDRW(cv, C_FLAGS);
           const int* dest = rec + co + C_HDR;
@@ -1259,7 +1145,7 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
       // (3) assemble the prefetched values (then any overflow)
       const int raw_off = aoff + 2 * nasm;
       const bool rowform = flags & RF_ROWS;
-      if (!CNL_LEAN && nraw > 0 && !rowform && !(CNL_ABL & 4)) {
+      if (!CNL_LEAN && nraw > 0 && !rowform) {
         // on-the-fly condensation: raw values to LDS, matrix values first (the first nrd are the residual pivots
         // d_r: keep -1/d_r), then the right-hand-side operands (a missing right-hand side reads as zero)
 #pragma unroll
@@ -1298,7 +1184,7 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
         if (!needs_fix) {
 #pragma unroll
           for (int j = 0; j < PVN; j++)
-            if (j * 16 < nasmv && !(CNL_ABL & 2)) __hip_atomic_fetch_add(&myFs[pos[j]], pv[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            if (j * 16 < nasmv) __hip_atomic_fetch_add(&myFs[pos[j]], pv[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         } else {
 #pragma unroll
           for (int j = 0; j < PVN; j++)
@@ -1319,7 +1205,7 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
         const int src = rec[aoff + e], pos = rec[aoff + nasm + e];
         __hip_atomic_fetch_add(&myFs[pos], myrhs ? myrhs[src - P.nnz] : 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
       }
-      if (rowform && !(CNL_ABL & 1)) {
+      if (rowform) {
         // row form: lane l = residual row l.  w = -1/d_r once, then (J_p w) J_q to the position byte of pair (p, q); lanes
         // without a row multiply dummy operands into the padding slots.  The pivots this front owns are counted here
         // (src/solver_types.jl:90-95).
@@ -1345,14 +1231,11 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
         for (int q = 0; q < ROWS_KM; q++)
           __hip_atomic_fetch_add(&myFs[ROW_POS(pw_, ROWS_KM * (ROWS_KM + 1) / 2 + q)], tr * pvr[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
       }
-      if (!CNL_LEAN && nprod > 0 && !(CNL_ABL & 1)) {
+      if (!CNL_LEAN && nprod > 0) {
         // products -J_ra J_rb / d_r of the condensed residual rows: one packed word each, pos | ia<<8 | ib<<15 | id<<22
         // (PB rounds in flight: the LDS round trips of a round are dependent, those of different rounds are not)
         wsync();
-#ifndef CNL_PB
-#define CNL_PB 8
-#endif
-        constexpr int PB = CNL_PB;
+        constexpr int PB = 8;
         const int* pw = rec + raw_off + nraw + l;
         for (int e = 0; e < nprod; e += 16 * PB) {
           int w[PB];
@@ -1366,9 +1249,7 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
             if (e + 16 * q < nprod) __hip_atomic_fetch_add(&myFs[w[q] & 255], v[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         }
       }
-      STAMP(0)
       wsync();
-      STAMP(2)
       // (4) next record over the current one (nothing below reads the lists); prefetch the one after and the next front's values
       int nroff = nxt_off;
       more = false;
@@ -1398,28 +1279,21 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
         R1 = rstream[(nn_off >> 2) + lane + 64];
         R2 = rstream[(nn_off >> 2) + lane + 128];
         const bool nfast = (nflags1 >> 8) == 16 && !(nflags1 & RF_FS_GLOBAL);
-        if (!(CNL_ABL & 8)) {
         PREFETCH_VALUES(nrec, aoff1, nfast ? nasmv1 : 0, nfast ? nasm1 : 0)
         if (nfast && (nflags1 & RF_ROWS)) PREFETCH_ROWFORM(nrec, aoff1 + 2 * nasm1)
         else PREFETCH_RAW(nrec, aoff1 + 2 * nasm1, nfast ? nrawv1 : 0, nfast ? nraw1 : 0)
-        }
         nxt_off = nn_off;
         more = nfast;  // a large front ends the stretch: the outer loop takes over
       }
       else flush_lrows(LP, const_cast<char*>(L_wb), lp_bm);
-      STAMP(1)
       // (5) eliminate in registers, store L rows and the update matrix
-      if (!(CNL_ABL & 1024)) {
-        const int bandw = HDRW(hv, R_FSOFF);   // fast fronts: the band form (0: none), see eliminate16_dpp
-        if (bandw == (2 | (CNL_BAND_HW << 8))) eliminate16_dpp<LATE, 2>(P.prob_doubles, P.u2_peak, P.gs_doubles, P.lsize, c.L, c.gs, c.batch, lane, prob0, f, nupd, lptr, uoff, uglob, pbase0, cnt, eig_tol, LP);
-        else if (bandw == (3 | (CNL_BAND_HW << 8))) eliminate16_dpp<LATE, 3>(P.prob_doubles, P.u2_peak, P.gs_doubles, P.lsize, c.L, c.gs, c.batch, lane, prob0, f, nupd, lptr, uoff, uglob, pbase0, cnt, eig_tol, LP);
-        else eliminate16_dpp<LATE, 0>(P.prob_doubles, P.u2_peak, P.gs_doubles, P.lsize, c.L, c.gs, c.batch, lane, prob0, f, nupd, lptr, uoff, uglob, pbase0, cnt, eig_tol, LP);
-      }
-      STAMP(3)
+      const int bandw = HDRW(hv, R_FSOFF);   // fast fronts: the band form (0: none), see eliminate16_dpp
+      if (bandw == (2 | (CNL_BAND_HW << 8))) eliminate16_dpp<LATE, 2>(P.prob_doubles, P.u2_peak, P.gs_doubles, P.lsize, c.L, c.gs, c.batch, lane, prob0, f, nupd, lptr, uoff, uglob, pbase0, cnt, eig_tol, LP);
+      else if (bandw == (3 | (CNL_BAND_HW << 8))) eliminate16_dpp<LATE, 3>(P.prob_doubles, P.u2_peak, P.gs_doubles, P.lsize, c.L, c.gs, c.batch, lane, prob0, f, nupd, lptr, uoff, uglob, pbase0, cnt, eig_tol, LP);
+      else eliminate16_dpp<LATE, 0>(P.prob_doubles, P.u2_peak, P.gs_doubles, P.lsize, c.L, c.gs, c.batch, lane, prob0, f, nupd, lptr, uoff, uglob, pbase0, cnt, eig_tol, LP);
       if (uglob) gsync(); else wsync();
       roff = nroff;
       s++;
-      STAMP(4)
       }
       flush_lrows(LP, const_cast<char*>(L_wb), lp_bm);  // end of a stretch of fast fronts: nothing stays pending
     }
@@ -1498,7 +1372,7 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
         __builtin_amdgcn_wave_barrier();
         if (lane == 0) __hip_atomic_store(lad + 1, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       } else {
-        spin_until(lad + 1, 2 * rung, A.spin_limit, as_global(A.status_total), as_global(A.status_call), 3);
+        spin_until(lad + 1, 2 * rung, A.spin_limit, as_global(A.status_total), as_global(A.status_call));
         epoch = rfl(__hip_atomic_load(lad + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
       }
       // a wait that gave up anywhere: the sequential launch behind this one redoes the call; leave
@@ -1515,7 +1389,7 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
       continue;
       }
     }
-    const bool ok = (CNL_ABL != 0) || (tpos == P.nvar && tzer == 0);
+    const bool ok = tpos == P.nvar && tzer == 0;
     if (A.mode == MODE_FACTOR) {
       if (valid && l == 0) {
         A.success[prob] = ok ? 1 : 0;
@@ -1560,10 +1434,9 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
   }
   if (l == 0) cnt[8 + g] = (success && valid) ? 1 : 0;
   gsync();
-  STAMP(5)
   // ---------------- backward pass (d = -K^-1 rhs), only where the factorisation succeeded -----------
   // (problems that failed still walk the stream with the wave; their output is not stored)
-  if (__any(success) && !(CNL_ABL & 256)) {
+  if (__any(success)) {
     const int4* bstream = reinterpret_cast<const int4*>(P.brec);
     const int* okflag = cnt + 8;
     const bool okme = valid && okflag[g] != 0;
@@ -1580,7 +1453,7 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
     int ipend = -1;
     double dpend = 0.0;
     // (lean) operands of the residual rows the CURRENT front owns, prefetched one front ahead; their store is deferred too
-    const bool brows = CNL_LEAN && A.back_rows != 0 && !(CNL_ABL & 32768);
+    const bool brows = CNL_LEAN && A.back_rows != 0;
     double bpv[ROWS_KM + 2];
     int bix = 0, brs = 0, ipend2 = -1;
     double dpend2 = 0.0;
@@ -1600,7 +1473,7 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
         PREFETCH_ROWS(lr, lp0, nupd0, npiv0)
         primed = true;
       }
-      if constexpr (STAGED) if (DEP_WAITING) { spin_until(dep_wait, dep_target, A.spin_limit, as_global(A.status_total), as_global(A.status_call), 4); dep_wait = nullptr; }  // the parent's x is read below
+      if constexpr (STAGED) if (DEP_WAITING) { spin_until(dep_wait, dep_target, A.spin_limit, as_global(A.status_total), as_global(A.status_call)); dep_wait = nullptr; }  // the parent's x is read below
       const int* rec = recw;
       const int hb = rec[lane & 7];
       const int npiv = HDRW(hb, B_NPIV), nupd = HDRW(hb, B_NUPD), xoff = HDRW(hb, B_XOFF), pxoff = HDRW(hb, B_PXOFF);
@@ -1610,8 +1483,7 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
       if (!CNL_LEAN && cls != 16) {
         // rare large front: out of line, then restart the pipeline
         if (ipend >= 0) { mydout[ipend] = dpend; ipend = -1; }
-        if (CNL_ABL & 4096) {
-        } else if (cls == 32) {
+        if (cls == 32) {
           for (int pass = 0; pass < 2; pass++) {
             if (prob0 + pass * 2 >= A.batch) break;
             back_front_call<32>(P.prob_doubles, P.lsize, P.dstride, A.L, A.d, A.batch, lane, prob0, pass, rec, f, nupd, npiv, lptr, xoff, pxoff, pbase0, okflag);
@@ -1671,7 +1543,7 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
       wsync();
 #pragma unroll
       for (int k = 0; k < KB; k++) {
-        if (k < npiv && !(CNL_ABL & 8192)) {
+        if (k < npiv) {
           const double sum = gsum<16>(-lr[k] * xb);
           if (l == nupd + 1 + k) xb = sum;
         }
@@ -1684,7 +1556,7 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
       }
       // d = -x of the pivots: one scattered store per front (rec holds the original index of every pivot)
       if (ipend >= 0) mydout[ipend] = dpend;   // (only behind the last prefetch: the front before this one had no successor to carry it)
-      ipend = (okme && l > nupd && l < f && !(CNL_ABL & 65536)) ? rec[B_HDR + l] : -1;
+      ipend = (okme && l > nupd && l < f) ? rec[B_HDR + l] : -1;
       dpend = -xb;
       if (l >= 1 && l < f) xs[xoff + l] = xb;
       wsync();
@@ -1714,10 +1586,6 @@ __global__ void __launch_bounds__(256, CNL_WAVES_PER_SIMD) newton2_kernel_t(cons
     if (ipend >= 0) mydout[ipend] = dpend;
     if constexpr (CNL_LEAN) if (ipend2 >= 0) mydout[ipend2] = dpend2;
   }
-#ifdef CNL_STAMPS
-  STAMP(6)
-  if (lane == 0 && A.npos) for (int k = 0; k < 8; k++) A.npos[(blockIdx.x * WPB + wave) * 8 + k] = (long long)st_acc[k];
-#endif
   if constexpr (STAGED) {
     if (FUSED && A.phase == 2) { task_done(dep_signal, lane, true); return; }  // (outputs: written by the deciding wavefront; rho_old and the slots: committed behind)
     if (A.phase == 1) task_done(dep_signal, lane, A.df_live != 0);  // the children of this task may read its solution components now
@@ -1847,26 +1715,6 @@ hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, L
     for (int q = s_df - 1; q >= 0; q--) launch_range(1, stage_ptr[q], stage_ptr[q + 1]);
   }
   if (ladder) launch_ladder(0);  // the problems that failed the attempt climb the rho ladder here (the other groups' wavefronts exit at once)
-#ifdef CNL_DBG_TRACE
-  if (ladder) {
-    (void)hipStreamSynchronize(stream);
-    static int hb[1 << 16];
-    int n = 0;
-    (void)hipMemcpyFromSymbol(&n, HIP_SYMBOL(cnl_trace_n), sizeof(int));
-    (void)hipMemcpyFromSymbol(hb, HIP_SYMBOL(cnl_trace_buf), sizeof(hb));
-    fprintf(stderr, "[trace] ladder launch: ntasks_all %d nquads %d batch %d, %d records\n", ntasks_all, a.nquads, a.batch, n / 4);
-    for (int i = 0; i + 3 < n && i < (1 << 16) - 4; i += 4) {
-      const int tag = hb[i] & 255, wg = hb[i] >> 8;
-      if (tag == 1) fprintf(stderr, "[trace] wg %d START task %d widx %d nchild %d nfr %d parent %d\n", wg, hb[i + 1] & 0xffff, hb[i + 1] >> 16, hb[i + 2] & 0xffff, hb[i + 2] >> 16, hb[i + 3]);
-      else if (tag == 2) fprintf(stderr, "[trace] wg %d task %d END OF RUNG %d tpos %d tzer %d\n", wg, hb[i + 1] & 0xffff, hb[i + 1] >> 16, hb[i + 2], hb[i + 3]);
-      else if (tag == 3) fprintf(stderr, "[trace] wg %d task %d rung %d fin %d epoch %d\n", wg, hb[i + 1] & 0xffff, hb[i + 1] >> 16, hb[i + 2], hb[i + 3]);
-      else if (tag == 9) fprintf(stderr, "[trace] wg %d GIVE UP at site %d: wants %d has %d\n", wg, hb[i + 3], hb[i + 1], hb[i + 2]);
-      else fprintf(stderr, "[trace] wg %d tag %d: %d %d %d\n", wg, tag, hb[i + 1], hb[i + 2], hb[i + 3]);
-    }
-    n = 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(cnl_trace_n), &n, sizeof(int));
-  }
-#endif
   if (a.mode == MODE_FACTOR)
     hipLaunchKernelGGL(staged_decide_kernel, dim3((a.batch + 255) / 256), dim3(256), 0, stream, a.gcnt, P.nvar, a.batch, a.success, a.npos, a.nzero);
   return hipGetLastError();

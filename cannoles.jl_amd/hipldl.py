@@ -229,9 +229,8 @@ def lib():
             getattr(L, fn).argtypes = [vp, vp]
         L.cnl_outer_newton_done_dev.argtypes = [vp, C.c_int, vp]
         L.cnl_outer_ls_test_dev.argtypes = [vp, C.c_int, vp]
-        if L.cnl_version() < 0 and not os.environ.get("CANNOLES_HIP_ALLOW_EXPERIMENT"):
-            raise RuntimeError(f"{LIB_PATH} is an EXPERIMENT build (cnl_version() = {L.cnl_version()}: timing probes / diagnostic "
-                               "stamps compiled in, results may be wrong); set CANNOLES_HIP_ALLOW_EXPERIMENT=1 to load it on purpose")
+        if L.cnl_version() < 200:
+            raise RuntimeError(f"{LIB_PATH}: cnl_version() = {L.cnl_version()}, ABI version 0.2.0 or later required")
         _lib = L
     return _lib
 
@@ -344,7 +343,7 @@ class HIPLDLStruct:
         self.config = {"tpp": int(cfg[0]), "ppb": int(cfg[1]), "lds_bytes": int(cfg[2]), "lds_work": int(cfg[3]), "grid": int(cfg[4]),
                        "kernel": {2: "v2", 3: "dense", 4: "v2-staged"}.get(int(cfg[5]) & 15, "v1"), "wpb": int(cfg[6]), "lds2_bytes": int(cfg[7]),
                        "lean": bool(int(cfg[5]) & 16), "tail": bool(int(cfg[5]) & 32), "band": bool(int(cfg[5]) & 64), "f1_tiles": bool(int(cfg[5]) & 128),
-                       "band_nl": (int(cfg[5]) >> 8) & 255, "band_parts": (int(cfg[5]) >> 16) & 255, "band_movers": bool((int(cfg[5]) >> 24) & 1),
+                       "band_nl": (int(cfg[5]) >> 8) & 255, "band_parts": (int(cfg[5]) >> 16) & 255,
                        "batch_layout": (int(cfg[5]) >> 25) & 1, "rhs_interleaved": bool((int(cfg[5]) >> 26) & 1)}
 
     def plan_array(self, name):

@@ -55,8 +55,7 @@ end
 reference's 7-segment order (/root/reference/src/CaNNOLeS.jl:256-315).
 """
 function HIPFactor(N::Integer, rows::Vector{Int64}, cols::Vector{Int64}, nvar::Integer, nequ::Integer, ncon::Integer; device::Integer = 0)
-  # an EXPERIMENT build of the library (timing probes / diagnostic stamps compiled in) reports a negative version
-  ccall((:cnl_version, libcnl), Int32, ()) >= 200 || error("libcannoles_hip: ABI version 0.2.0 or later required (experiment builds are refused)")
+  ccall((:cnl_version, libcnl), Int32, ()) >= 200 || error("libcannoles_hip: ABI version 0.2.0 or later required")
   h = Ref{Ptr{Cvoid}}(C_NULL)
   check(ccall((:cnl_create, libcnl), Cint,
     (Ref{Ptr{Cvoid}}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Int64, Int64, Int64, Cint),

@@ -2,7 +2,7 @@
 """A/B of whole-library builds on ONE box (boxes of the pool differ by +-4 %, so only same-box pairs mean anything).
   build (CPU):  python tools/ab_lib.py build <name> <git-ref>|WORK [extra compiler flags]   -> build_abl/ab_<name>/libcannoles_hip.so
   run (GPU):    python tools/ab_lib.py run <B> <name> [<name> ...]    interleaved rounds, kernel ms of the headline step (cfg3 pattern)
-WORK = the working tree as it is.  Product builds only (no -D probes): the libraries are loaded through CANNOLES_HIP_LIB."""
+WORK = the working tree as it is.  The libraries are loaded through CANNOLES_HIP_LIB."""
 import os
 import shutil
 import subprocess
@@ -75,7 +75,7 @@ def run(B, names, n=10000, p=50, rounds=3):
     for r in range(rounds):
         for k in names:
             lib = os.path.join(OUTD, "ab_" + k, "libcannoles_hip.so")
-            env = dict(os.environ, CANNOLES_HIP_LIB=lib, CANNOLES_HIP_ALLOW_EXPERIMENT="1")
+            env = dict(os.environ, CANNOLES_HIP_LIB=lib)
             out = subprocess.run([sys.executable, "-c", RUN % {"root": ROOT, "B": B, "n": n, "p": p, "reps": reps}], env=env, capture_output=True, text=True)
             line = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT")]
             if not line:
