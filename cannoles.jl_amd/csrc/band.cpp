@@ -57,10 +57,11 @@ struct Packer {
     }
     return (int)pieces.size() <= BAND_NPIECE;
   }
+  int32_t esz = 8;   // bytes per element
   // LDS byte offset of element e of array a
   int32_t off(int a, int32_t e) const {
     for (const Piece& pc : pieces)
-      if (pc.arr == a && e >= pc.base && e < pc.base + 8) return (int32_t)((BAND_IN_OFF + 8 * pc.slot + (e - pc.base)) * 8);
+      if (pc.arr == a && e >= pc.base && e < pc.base + 8) return (int32_t)((BAND_IN_OFF + 8 * pc.slot + (e - pc.base)) * esz);
     return -1;
   }
 };
@@ -68,8 +69,9 @@ struct Packer {
 }  // namespace
 
 void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ,
-                     int64_t ncon, int nparts_wanted) {
+                     int64_t ncon, int nparts_wanted, int esz) {
   B = BandPlan();
+  if (esz != 8 && esz != 4) { B.ok = false; B.why = "element size must be 8 or 4 bytes"; return; }
   auto no = [&](const std::string& w) { B.ok = false; B.why = w; };
   const int64_t n = nvar, m = nequ, p = ncon;
   if (N != n + m + p) return no("N != nvar + nequ + ncon");
@@ -281,8 +283,9 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
     std::vector<std::vector<int32_t>> fblocks(nsteps), bblocks(nsteps);
     Packer pk;
     pk.len[0] = (int32_t)nnz; pk.len[1] = (int32_t)N; pk.len[2] = (int32_t)(lpart + 16);
+    pk.esz = esz;
     if (lpart + 16 >= (1 << 27)) return no("factor too long");
-    const int32_t ZB = BAND_ZERO_OFF * 8;
+    const int32_t ZB = BAND_ZERO_OFF * esz;
     // An epoch is a run of BAND_EPOCH steps whose operands must fit the pieces and whose outputs the rings.
     std::string why_not;
     auto try_epoch = [&](const int32_t u0, const int32_t u1, int32_t* E) -> bool {
@@ -365,8 +368,8 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
           blk[BS_RX] = dir == 0 ? off(st.rx) : ZB;
           if (dir == 0) {
             const int32_t lbh = u < uh ? lbase1 : lbase2;
-            blk[BS_LB] = st.lev_b >= 0 ? (BAND_LOUT_OFF + st.lev_b * BAND_LREC - lbh) * 8 : ZB;
-            blk[BS_LX] = st.lev_x >= 0 ? (BAND_LOUT_OFF + st.lev_x * BAND_LREC - lbh) * 8 : ZB;
+            blk[BS_LB] = st.lev_b >= 0 ? (BAND_LOUT_OFF + st.lev_b * BAND_LREC - lbh) * esz : ZB;
+            blk[BS_LX] = st.lev_x >= 0 ? (BAND_LOUT_OFF + st.lev_x * BAND_LREC - lbh) * esz : ZB;
             blk[BS_DX] = ZB;
           } else {
             blk[BS_LB] = st.lev_b >= 0 ? pk.off(2, st.lev_b * BAND_LREC) : ZB;
@@ -376,15 +379,15 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
             for (int32_t ev : {st.lev_b, st.lev_x})
               if (ev >= 0)
                 for (int i = 0; i < BAND_LREC; i++)
-                  if (pk.off(2, ev * BAND_LREC + i) != pk.off(2, ev * BAND_LREC) + 8 * i) return no("internal: factor record not contiguous in LDS");
-            blk[BS_DX] = (st.flags & BF_PIVOT_X) ? (BAND_DX_OFF + st.xpiv - x_lo) * 8 : ZB;
+                  if (pk.off(2, ev * BAND_LREC + i) != pk.off(2, ev * BAND_LREC) + esz * i) return no("internal: factor record not contiguous in LDS");
+            blk[BS_DX] = (st.flags & BF_PIVOT_X) ? (BAND_DX_OFF + st.xpiv - x_lo) * esz : ZB;
           }
           for (size_t i = 0; i < st.rows.size(); i++) {
             const RowOp& ro = st.rows[i];
             int32_t* rb = blk.data() + BAND_SW + BAND_RW * i;
             rb[BR_DI] = off(ro.di); rb[BR_RR] = off(ro.rr);
             for (int s = 0; s < BAND_NB; s++) rb[BR_J0 + s] = off(ro.j[s]);
-            rb[BR_DR] = (BAND_DR_OFF + ro.r - r_lo) * 8;
+            rb[BR_DR] = (BAND_DR_OFF + ro.r - r_lo) * esz;
             if (rb[BR_DI] < 0 || rb[BR_RR] < 0) return no("internal: operand without a piece");
             for (int s = 0; s < BAND_NB; s++) if (rb[BR_J0 + s] < 0) return no("internal: operand without a piece");
           }

@@ -33,7 +33,7 @@ constexpr int BAND_NPIECE = 15;     // 64-byte operand pieces per epoch and lane
 constexpr int BAND_REC_MAX = 256;    // ints of step + row blocks per epoch (LDS record buffer of a wavefront)
 constexpr int BAND_LREC = 6;        // factor doubles per pivot: band multipliers, border multiplier, z  (see band.hip)
 
-// LDS block of one lane, in doubles: [operand pieces | out ring | zero cell].  The out ring holds the factor records of HALF an
+// LDS block of one lane, in elements (doubles; floats on Float32 handles): [operand pieces | out ring | zero cell].  The out ring holds the factor records of HALF an
 // epoch in the forward sweep (flushed behind steps 3 and 7) and the solution components of an epoch in the backward sweep.
 // 153 doubles = 1224 bytes per lane: 128 lanes (two workgroups of 32 problems) fit the 160 KB of a CU.
 constexpr int BAND_IN_OFF = 0;
@@ -57,7 +57,8 @@ constexpr long long band_il_index(long long p, long long e, long long len) {
   return ((p / BAND_IL_GROUP * band_il_blocks(len) + e / 8) * BAND_IL_GROUP + p % BAND_IL_GROUP) * 8 + e % 8;
 }
 
-// step block (BAND_SW ints); LDS offsets are BYTES inside the lane block
+// step block (BAND_SW ints); LDS offsets are BYTES inside the lane block, written for the element size the program was built for
+// (build_band_plan: esz = 8 for double, 4 for float — the same program with every LDS offset scaled)
 enum {
   BS_FLAGS = 0,        // BF_* | rows << 8
   BS_DG0, BS_DG1, BS_DG2,   // plain diagonal entries of the entering variable, in COO order
@@ -110,8 +111,9 @@ struct BandPlan {
   BandPart part[2];
 };
 
-// rows1/cols1: the reference's 1-based COO pattern (src/CaNNOLeS.jl:256-315).  Fills B (B.ok, B.why); nparts_wanted: 1 or 2.
+// rows1/cols1: the reference's 1-based COO pattern (src/CaNNOLeS.jl:256-315).  Fills B (B.ok, B.why); nparts_wanted: 1 or 2;
+// esz: bytes per element of the kernel that runs the program (8: double, 4: float), the scale of its LDS byte offsets.
 void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ,
-                     int64_t ncon, int nparts_wanted);
+                     int64_t ncon, int nparts_wanted, int esz = 8);
 
 }  // namespace cnl

@@ -14,6 +14,11 @@
 // Summation order (documented deviation, within the fp64 bar of DESIGN section 5): entering position = plain entries in COO
 // order (src/solver_types.jl:53-59: duplicates summed in COO order), then the condensed rows' products in row order, then the
 // pivots' updates as they happen.
+// Element type T (LDLFactorization{T}): double, or float for Float32 handles (cnl_create_f32).  The program is the same — steps,
+// epochs, pieces of EIGHT elements, the lane block of BAND_LANE_DOUBLES elements — with its LDS byte offsets written for
+// sizeof(T) (build_band_plan's element size), so a float operand is one ds_read_b32 at an offset the generator fixed.  All
+// arithmetic is in T (fmaf, float compares, v_rcp_f32); only the control block of the two wavefronts stays double (a float
+// widens to double exactly).
 #include <hip/hip_runtime.h>
 
 #include "band.h"
@@ -40,32 +45,39 @@ __device__ __forceinline__ constexpr int sidx(int a, int b) { return a >= b ? a 
 
 // refined reciprocal (v_rcp_f64 is good to 2^-25 on gfx950: one Newton step) and a quotient with a residual correction: the same
 // division the register-front kernel uses (kernels2.hip, fast_div), the reciprocal shared by the multipliers of one pivot
-__device__ __forceinline__ double rrcp(double d) {
-  double r = __builtin_amdgcn_rcp(d);
-  const double e = fma(-d, r, 1.0);
+// (float: v_rcp_f32 is good to 1 ulp; the same Newton step and residual correction in float)
+template <class T>
+__device__ __forceinline__ T rrcp(T d) {
+  T r;
+  if constexpr (sizeof(T) == 8) r = __builtin_amdgcn_rcp(d);
+  else r = __builtin_amdgcn_rcpf(d);
+  const T e = fma(-d, r, T(1));
   return fma(r, e, r);
 }
-__device__ __forceinline__ double rdiv(double w, double d, double r) {
-  const double q = w * r;
-  const double res = fma(-d, q, w);
+template <class T>
+__device__ __forceinline__ T rdiv(T w, T d, T r) {
+  const T q = w * r;
+  const T res = fma(-d, q, w);
   return fma(res, r, q);
 }
+
 
 // The window: BAND_NS slots, of which the five that hold the variables entered last are live (the allocator sees that: every
 // index below is a compile-time constant, so the dead slots' registers are free).
 constexpr int NS = BAND_NS;
+template <class T>
 struct Win {
-  double S[NS * (NS + 1) / 2];   // band slots, packed lower triangle
-  double X[NS];                  // border row
-  double S55;
-  double c[NS];                  // right-hand side
-  double c5;
+  T S[NS * (NS + 1) / 2];   // band slots, packed lower triangle
+  T X[NS];                  // border row
+  T S55;
+  T c[NS];                  // right-hand side
+  T c5;
 };
 // live slot k of step phase PH: 0 = the step's pivot .. BAND_HW = the entering variable
 __device__ __forceinline__ constexpr int lslot(int PH, int k) { return (PH - BAND_HW + k + NS) % NS; }
 
-#define LDSD(off) (*reinterpret_cast<const double*>(myb + (off)))
-#define LDSW(off) (*reinterpret_cast<double*>(myb + (off)))
+#define LDSD(off) (*reinterpret_cast<const T*>(myb + (off)))
+#define LDSW(off) (*reinterpret_cast<T*>(myb + (off)))
 
 // Step and row blocks of the current epoch sit in the wavefront's LDS record buffer (copied there by the mover with the operand
 // pieces): every compute lane reads the same address (one broadcast read), the operand offsets stay in VGPRs — they are only ever
@@ -84,14 +96,16 @@ __device__ __forceinline__ void load_row(RowRec& R, const char* recb, int o) {
 }
 
 // operands of one forward step: the entering variable's fifteen entries and the first residual row
-struct FOps { double eo[15]; double rj[BAND_NB]; double rdr, rrr; };
-__device__ __forceinline__ void fload(FOps& P, const Rec& st, const RowRec& row0, const int fl, char* myb) {
+template <class T>
+struct FOps { T eo[15]; T rj[BAND_NB]; T rdr, rrr; };
+template <class T>
+__device__ __forceinline__ void fload(FOps<T>& P, const Rec& st, const RowRec& row0, const int fl, char* myb) {
 #pragma unroll
   for (int q = 0; q < 15; q++) P.eo[q] = LDSD(st.v[BS_DG0 + q]);
   static_assert(BS_RX == BS_DG0 + 14, "the fifteen operands of an entering variable are consecutive words of the step block");
-  P.rdr = 1.0; P.rrr = 0.0;
+  P.rdr = T(1); P.rrr = T(0);
 #pragma unroll
-  for (int k = 0; k < BAND_NB; k++) P.rj[k] = 0.0;
+  for (int k = 0; k < BAND_NB; k++) P.rj[k] = T(0);
   if ((fl >> 8) & 255) {
 #pragma unroll
     for (int k = 0; k < BAND_NB; k++) P.rj[k] = LDSD(row0.v[BR_J0 + k]);
@@ -106,19 +120,19 @@ __device__ __forceinline__ long long band_il_offset(int e, int stride) { return 
 
 // one forward step of phase PH = step number % 8: enter slot PH, pivot slot PH - 4; fl = flags word (wave-uniform), o = int
 // offset of the step block in the record buffer.  The operands were read (fload) while the previous step computed.
-template <int PH>
-__device__ __forceinline__ void fstep(Win& W, const FOps& OP, const Rec& st, const int fl, const char* recb, const int o, char* myb,
-                                      const double* __restrict__ gvals, const double* __restrict__ grhs, cptr borders, long long pv, long long pr,
-                                      bool has_rhs, double rho, bool ovr, double tol, int& npos, int& nzer, const int vstride = 0, const int rstride = 0) {
+template <int PH, class T>
+__device__ __forceinline__ void fstep(Win<T>& W, const FOps<T>& OP, const Rec& st, const int fl, const char* recb, const int o, char* myb,
+                                      const T* __restrict__ gvals, const T* __restrict__ grhs, cptr borders, long long pv, long long pr,
+                                      bool has_rhs, T rho, bool ovr, T tol, int& npos, int& nzer, const int vstride = 0, const int rstride = 0) {
   constexpr int es = PH, ps = lslot(PH, 0);
   const int nrows = (fl >> 8) & 255;
-  const double (&eo)[15] = OP.eo;
-  const double (&rj)[BAND_NB] = OP.rj;
-  const double rdr = OP.rdr, rrr = OP.rrr;
+  const T (&eo)[15] = OP.eo;
+  const T (&rj)[BAND_NB] = OP.rj;
+  const T rdr = OP.rdr, rrr = OP.rrr;
   // ---- enter ----
   {
-    const double dg = (eo[0] + eo[1]) + eo[2];
-    double rv = eo[BS_RHO - BS_DG0];
+    const T dg = (eo[0] + eo[1]) + eo[2];
+    T rv = eo[BS_RHO - BS_DG0];
     if (!(fl & (1 << 16))) rv = ovr ? rho : rv;
     W.S[sidx(es, es)] = dg + rv;
 #pragma unroll
@@ -128,7 +142,7 @@ __device__ __forceinline__ void fstep(Win& W, const FOps& OP, const Rec& st, con
   }
   // ---- residual rows completed by the entering variable: products -J_a J_b / d_r, counted in the inertia ----
   for (int i = 0; i < nrows; i++) {
-    double J[BAND_NB], dr, rr;
+    T J[BAND_NB], dr, rr;
     if (i == 0) {
 #pragma unroll
       for (int k = 0; k < BAND_NB; k++) J[k] = rj[k];
@@ -143,12 +157,12 @@ __device__ __forceinline__ void fstep(Win& W, const FOps& OP, const Rec& st, con
     }
     npos += dr > tol;
     nzer += fabs(dr) <= tol;
-    const double r = rrcp(dr);
-    const double w = rdiv(-1.0, dr, r);
-    const double tr = rr * w;
+    const T r = rrcp(dr);
+    const T w = rdiv(T(-1), dr, r);
+    const T tr = rr * w;
 #pragma unroll
     for (int ka = 0; ka < BAND_NB; ka++) {
-      const double ta = J[ka] * w;
+      const T ta = J[ka] * w;
 #pragma unroll
       for (int kb = 0; kb <= ka; kb++) W.S[sidx(lslot(PH, ka), lslot(PH, kb))] = fma(ta, J[kb], W.S[sidx(lslot(PH, ka), lslot(PH, kb))]);
       W.c[lslot(PH, ka)] = fma(tr, J[ka], W.c[lslot(PH, ka)]);
@@ -159,39 +173,39 @@ __device__ __forceinline__ void fstep(Win& W, const FOps& OP, const Rec& st, con
     cptr bt = borders + BAND_BW * __builtin_amdgcn_readfirstlane(st.v[BS_BORDER]);
     // (vstride / rstride != 0: the array is interleaved over the workgroup's problems in blocks of eight doubles, see band_il_offset)
     W.S55 += gvals[pv + band_il_offset(bt[BB_DSRC], vstride)];
-    W.c5 += has_rhs ? grhs[pr + band_il_offset(bt[BB_RHS], rstride)] : 0.0;
-    const double d = W.S55;
+    W.c5 += has_rhs ? grhs[pr + band_il_offset(bt[BB_RHS], rstride)] : T(0);
+    const T d = W.S55;
     npos += d > tol;
     nzer += fabs(d) <= tol;
-    const double r = rrcp(d);
-    double l[BAND_NB], w[BAND_NB];
+    const T r = rrcp(d);
+    T l[BAND_NB], w[BAND_NB];
 #pragma unroll
     for (int k = 0; k < BAND_NB; k++) { w[k] = W.X[lslot(PH, k)]; l[k] = rdiv(w[k], d, r); }
-    const double z = rdiv(W.c5, d, r);
+    const T z = rdiv(W.c5, d, r);
 #pragma unroll
     for (int ka = 0; ka < BAND_NB; ka++) {
 #pragma unroll
       for (int kb = 0; kb <= ka; kb++) W.S[sidx(lslot(PH, ka), lslot(PH, kb))] = fma(w[ka], -l[kb], W.S[sidx(lslot(PH, ka), lslot(PH, kb))]);
       W.c[lslot(PH, ka)] = fma(w[ka], -z, W.c[lslot(PH, ka)]);
     }
-    double* lo = reinterpret_cast<double*>(myb + st.v[BS_LB]);
+    T* lo = reinterpret_cast<T*>(myb + st.v[BS_LB]);
 #pragma unroll
     for (int k = 0; k < BAND_NB; k++) lo[k] = l[k];
     lo[BAND_NB] = z;
 #pragma unroll
-    for (int k = 0; k < BAND_NB; k++) W.X[lslot(PH, k)] = 0.0;
-    W.S55 = 0.0; W.c5 = 0.0;
+    for (int k = 0; k < BAND_NB; k++) W.X[lslot(PH, k)] = T(0);
+    W.S55 = T(0); W.c5 = T(0);
   }
   // ---- band pivot ----
   if (fl & BF_PIVOT_X) {
-    const double d = W.S[sidx(ps, ps)];
+    const T d = W.S[sidx(ps, ps)];
     npos += d > tol;
     nzer += fabs(d) <= tol;
-    const double r = rrcp(d);
-    double l[BAND_NB], w[BAND_NB];
+    const T r = rrcp(d);
+    T l[BAND_NB], w[BAND_NB];
 #pragma unroll
     for (int k = 1; k < BAND_NB; k++) { w[k] = W.S[sidx(lslot(PH, k), ps)]; l[k] = rdiv(w[k], d, r); }
-    const double w5 = W.X[ps], l5 = rdiv(w5, d, r), z = rdiv(W.c[ps], d, r);
+    const T w5 = W.X[ps], l5 = rdiv(w5, d, r), z = rdiv(W.c[ps], d, r);
 #pragma unroll
     for (int ka = 1; ka < BAND_NB; ka++) {
 #pragma unroll
@@ -201,7 +215,7 @@ __device__ __forceinline__ void fstep(Win& W, const FOps& OP, const Rec& st, con
     }
     W.S55 = fma(w5, -l5, W.S55);
     W.c5 = fma(w5, -z, W.c5);
-    double* lo = reinterpret_cast<double*>(myb + st.v[BS_LX]);
+    T* lo = reinterpret_cast<T*>(myb + st.v[BS_LX]);
 #pragma unroll
     for (int k = 1; k < BAND_NB; k++) lo[k - 1] = l[k];
     lo[4] = l5;
@@ -210,20 +224,22 @@ __device__ __forceinline__ void fstep(Win& W, const FOps& OP, const Rec& st, con
 }
 
 // one backward step of phase PH: x of the band pivot, then of the border pivot, then the residual components
-struct BOps { double lx[BAND_LREC], lb[BAND_LREC], rj[BAND_NB]; double rdr, rrr; };
-__device__ __forceinline__ void bload(BOps& P, const Rec& st, const RowRec& row0, const int fl, char* myb) {
+template <class T>
+struct BOps { T lx[BAND_LREC], lb[BAND_LREC], rj[BAND_NB]; T rdr, rrr; };
+template <class T>
+__device__ __forceinline__ void bload(BOps<T>& P, const Rec& st, const RowRec& row0, const int fl, char* myb) {
 #pragma unroll
-  for (int q = 0; q < BAND_LREC; q++) { P.lx[q] = 0.0; P.lb[q] = 0.0; }
+  for (int q = 0; q < BAND_LREC; q++) { P.lx[q] = T(0); P.lb[q] = T(0); }
 #pragma unroll
-  for (int k = 0; k < BAND_NB; k++) P.rj[k] = 0.0;
-  P.rdr = 1.0; P.rrr = 0.0;
+  for (int k = 0; k < BAND_NB; k++) P.rj[k] = T(0);
+  P.rdr = T(1); P.rrr = T(0);
   if (fl & BF_PIVOT_X) {
-    const double* lo = reinterpret_cast<const double*>(myb + st.v[BS_LX]);
+    const T* lo = reinterpret_cast<const T*>(myb + st.v[BS_LX]);
 #pragma unroll
     for (int q = 0; q < BAND_LREC; q++) P.lx[q] = lo[q];
   }
   if (fl & BF_PIVOT_B) {
-    const double* lo = reinterpret_cast<const double*>(myb + st.v[BS_LB]);
+    const T* lo = reinterpret_cast<const T*>(myb + st.v[BS_LB]);
 #pragma unroll
     for (int q = 0; q < BAND_LREC; q++) P.lb[q] = lo[q];
   }
@@ -234,17 +250,17 @@ __device__ __forceinline__ void bload(BOps& P, const Rec& st, const RowRec& row0
     P.rrr = LDSD(row0.v[BR_RR]);
   }
 }
-template <int PH>
-__device__ __forceinline__ void bstep(double (&xs)[NS + 1], const BOps& OP, const Rec& st, const RowRec& row0, const int fl, const char* recb,
-                                      const int o, char* myb, cptr borders, double* __restrict__ gd, long long pd, bool okme) {
+template <int PH, class T>
+__device__ __forceinline__ void bstep(T (&xs)[NS + 1], const BOps<T>& OP, const Rec& st, const RowRec& row0, const int fl, const char* recb,
+                                      const int o, char* myb, cptr borders, T* __restrict__ gd, long long pd, bool okme) {
   constexpr int ps = lslot(PH, 0);
   const int nrows = (fl >> 8) & 255;
-  const double (&lx)[BAND_LREC] = OP.lx;
-  const double (&lb)[BAND_LREC] = OP.lb;
-  const double (&rj)[BAND_NB] = OP.rj;
-  const double rdr = OP.rdr, rrr = OP.rrr;
+  const T (&lx)[BAND_LREC] = OP.lx;
+  const T (&lb)[BAND_LREC] = OP.lb;
+  const T (&rj)[BAND_NB] = OP.rj;
+  const T rdr = OP.rdr, rrr = OP.rrr;
   if (fl & BF_PIVOT_X) {
-    double x = lx[5];
+    T x = lx[5];
 #pragma unroll
     for (int k = 1; k < BAND_NB; k++) x = fma(-lx[k - 1], xs[lslot(PH, k)], x);
     x = fma(-lx[4], xs[NS], x);
@@ -252,14 +268,14 @@ __device__ __forceinline__ void bstep(double (&xs)[NS + 1], const BOps& OP, cons
     LDSW(st.v[BS_DX]) = -x;
   }
   if (fl & BF_PIVOT_B) {
-    double x = lb[BAND_NB];
+    T x = lb[BAND_NB];
 #pragma unroll
     for (int k = 0; k < BAND_NB; k++) x = fma(-lb[k], xs[lslot(PH, k)], x);
     xs[NS] = x;
     if (okme) gd[pd + borders[BAND_BW * __builtin_amdgcn_readfirstlane(st.v[BS_BORDER]) + BB_DOUT]] = -x;
   }
   for (int i = 0; i < nrows; i++) {
-    double J[BAND_NB], dr, rr;
+    T J[BAND_NB], dr, rr;
     int dro;
     if (i == 0) {
 #pragma unroll
@@ -272,26 +288,30 @@ __device__ __forceinline__ void bstep(double (&xs)[NS + 1], const BOps& OP, cons
       for (int k = 0; k < BAND_NB; k++) J[k] = LDSD(rb.v[BR_J0 + k]);
       dr = LDSD(rb.v[BR_DI]); rr = LDSD(rb.v[BR_RR]); dro = rb.v[BR_DR];
     }
-    double acc = -rr;
+    T acc = -rr;
 #pragma unroll
     for (int k = 0; k < BAND_NB; k++) acc = fma(J[k], xs[lslot(PH, k)], acc);
     LDSW(dro) = rdiv(acc, dr, rrcp(dr));
   }
-  if (fl & BF_ENTER_B) xs[NS] = 0.0;
+  if (fl & BF_ENTER_B) xs[NS] = T(0);
 }
 
 }  // namespace
 
 // LDS of a workgroup: [part][NL] lane blocks | [part] record buffers | control block: per problem [rho | flags], one word "all done"
-template <int NL>
+// T = float: the element arrays of LaunchArgs (vals, rhs, d, L, rho_old, rho) hold float arrays (launch_band_f32); params are
+// Float32 values widened to double, narrowed back here exactly.
+template <class T, int NL>
 __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(const BandDev P, const LaunchArgs Ain) {
   constexpr int NI = NL / 8;
+  constexpr int ES = (int)sizeof(T), LS = ES == 8 ? 3 : 2;   // bytes per element, their log2
+  static_assert(ES == 8 || ES == 4, "double or float");
   extern __shared__ double lds[];
   const int mode = Ain.mode, batch = Ain.batch;
-  double* const gvals = as_global(Ain.vals);
-  const double* const grhs = as_global(Ain.rhs);
-  double* const gd = as_global(Ain.d);
-  double* const gL = as_global(Ain.L);
+  T* const gvals = as_global(reinterpret_cast<T*>(Ain.vals));
+  const T* const grhs = as_global(reinterpret_cast<const T*>(Ain.rhs));
+  T* const gd = as_global(reinterpret_cast<T*>(Ain.d));
+  T* const gL = as_global(reinterpret_cast<T*>(Ain.L));
   const int lane = threadIdx.x & 63;
   const int part = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lq = lane >> 3, le = lane & 7;
@@ -301,9 +321,10 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   // so the solve factorises the same values again — the rho slots hold what the ladder left — and sweeps the new right-hand side
   // in the same launch: the arithmetic of the first attempt of newton_system!, no ladder, no outputs but d.
   const bool has_rhs = mode != MODE_FACTOR && grhs != nullptr;
-  char* wblk = reinterpret_cast<char*>(lds + (size_t)part * NL * LANE_D);
-  char* recb = reinterpret_cast<char*>(lds + (size_t)P.nparts * NL * LANE_D) + (size_t)part * BAND_REC_MAX * 4;
-  double* ctrl = reinterpret_cast<double*>(reinterpret_cast<char*>(lds + (size_t)P.nparts * NL * LANE_D) + (size_t)P.nparts * BAND_REC_MAX * 4);
+  T* const ldsT = reinterpret_cast<T*>(lds);
+  char* wblk = reinterpret_cast<char*>(ldsT + (size_t)part * NL * LANE_D);
+  char* recb = reinterpret_cast<char*>(ldsT + (size_t)P.nparts * NL * LANE_D) + (size_t)part * BAND_REC_MAX * 4;
+  double* ctrl = reinterpret_cast<double*>(reinterpret_cast<char*>(ldsT + (size_t)P.nparts * NL * LANE_D) + (size_t)P.nparts * BAND_REC_MAX * 4);
   const int* fops_g = as_global(P.fops[part]);
   const int* bops_g = as_global(P.bops[part]);
   cptr epochs = as_const(P.epochs[part]);
@@ -324,8 +345,8 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   const int vstride = vil ? G8 : 0, rstride = ril ? G8 : 0;
   const long long ilg = prob0 / BAND_IL_GROUP;        // group of the workgroup's problems
   const int ilp = (prob0 % BAND_IL_GROUP) * 8;        // ... and the offset of its first problem inside a block row
-  const double* vbase = gvals + (vil ? ilg * band_il_blocks(nnz) * G8 + ilp : (long long)prob0 * nnz);
-  const double* rbase = !has_rhs ? gvals : grhs + (ril ? ilg * band_il_blocks(N) * G8 + ilp : (long long)prob0 * N);
+  const T* vbase = gvals + (vil ? ilg * band_il_blocks(nnz) * G8 + ilp : (long long)prob0 * nnz);
+  const T* rbase = !has_rhs ? gvals : grhs + (ril ? ilg * band_il_blocks(N) * G8 + ilp : (long long)prob0 * N);
   // The factor records are private to the launch (written by the forward sweep, read by the backward sweep of the SAME workgroup), so
   // their layout is the kernel's choice: INTERLEAVED over the NL problems of the workgroup in blocks of eight doubles — element e of
   // problem p of the workgroup lives at ((e >> 3) * NL + p) * 8 + (e & 7) of the workgroup's region — so that the eight 64-byte runs one
@@ -335,9 +356,9 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   // 7.40 -> 7.75 ms (the address arithmetic costs the latency-bound case more than the layout gives) — so only the 32-problem
   // instantiation interleaves.
   constexpr bool LINT = NL >= 32;
-  double* lbase_g = gL + (long long)prob0 * lsize + (LINT ? 0 : P.loff[part]);
+  T* lbase_g = gL + (long long)prob0 * lsize + (LINT ? 0 : P.loff[part]);
   const int loff8 = LINT ? (int)P.loff[part] : 0;   // a multiple of 8
-  double* dbase = gd ? gd + (long long)prob0 * N : nullptr;
+  T* dbase = gd ? gd + (long long)prob0 * N : nullptr;
   unsigned movp[NI], ldsb[NI];   // problem of the lane inside the workgroup (clamped to the batch), LDS byte offset of its element
   bool movok[NI];
 #pragma unroll
@@ -346,27 +367,27 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
     movok[i] = prob0 + pl < batch;
     if (!movok[i]) pl = batch - 1 - prob0;
     movp[i] = (unsigned)pl;
-    ldsb[i] = ((unsigned)(i * 8 + lq) * (unsigned)LANE_D + (unsigned)le) << 3;
+    ldsb[i] = ((unsigned)(i * 8 + lq) * (unsigned)LANE_D + (unsigned)le) << LS;
   }
   // compute lanes
   const bool clane = lane < NL;
   const int cprob = prob0 + (clane ? lane : 0);
   const bool valid = clane && cprob < batch;
   const int cpl = valid ? cprob - prob0 : batch - 1 - prob0;   // problem whose data this lane's block holds
-  char* myb = wblk + (size_t)(clane ? lane : 0) * LANE_D * 8;
+  char* myb = wblk + (size_t)(clane ? lane : 0) * LANE_D * ES;
   const long long pv = vil ? ilg * band_il_blocks(nnz) * G8 + ilp + cpl * 8 : (long long)(prob0 + cpl) * nnz;
   const long long pr = ril ? ilg * band_il_blocks(N) * G8 + ilp + cpl * 8 : (long long)(prob0 + cpl) * N;
-  for (int t = lane; t < NL; t += 64) *reinterpret_cast<double*>(wblk + ((size_t)t * LANE_D + BAND_ZERO_OFF) * 8) = 0.0;   // every block's zero cell
+  for (int t = lane; t < NL; t += 64) *reinterpret_cast<T*>(wblk + ((size_t)t * LANE_D + BAND_ZERO_OFF) * ES) = T(0);   // every block's zero cell
 
-  const double tol = Ain.params[0], kdec = Ain.params[2], kinc = Ain.params[3], klarge = Ain.params[4], rho0 = Ain.params[5], rhomax = Ain.params[6],
-               rhomin = Ain.params[7];
-  double rho = 0.0, wrote = 0.0;
-  double rho_old = (mode == MODE_NEWTON && valid) ? as_global(Ain.rho_old)[cprob] : 0.0;
+  const T tol = (T)Ain.params[0], kdec = (T)Ain.params[2], kinc = (T)Ain.params[3], klarge = (T)Ain.params[4], rho0 = (T)Ain.params[5],
+          rhomax = (T)Ain.params[6], rhomin = (T)Ain.params[7];
+  T rho = T(0), wrote = T(0);
+  T rho_old = (mode == MODE_NEWTON && valid) ? as_global(reinterpret_cast<T*>(Ain.rho_old))[cprob] : T(0);
   int nfact = 0;
   bool done = !valid, success = false, ovr = false;
 
   static_assert(NI <= 4, "at most four problem groups per mover lane");
-  double stg[NPC][NI];   // operand pieces in flight
+  T stg[NPC][NI];        // operand pieces in flight
   int4 rstg0;            // step blocks in flight (one 16-byte word per lane: 256 ints)
   int pcs[NPC];          // piece descriptors of the epoch being loaded
   static_assert(BAND_REC_MAX <= 256, "record buffer: one dwordx4 per lane");
@@ -376,22 +397,22 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   // piece's array are selected with scalar instructions, the lane's offset is problem * stride + element.  (Three guarded loads
   // made the compiler form all three 64-bit addresses of every piece up front — 96 NI VGPRs; selecting among per-array offset
   // arrays made it index them in scratch memory; lambdas instead of macros put every captured variable into scratch.)
-#define BAND_ISSUE1(K, I) if constexpr (I < NI) stg[K][I] = *reinterpret_cast<const double*>(pb + ((movp[I] * strd + tl) << 3));
-#define BAND_COMMIT1(K, I) if constexpr (I < NI) *reinterpret_cast<double*>(wblk + ldsb[I] + (BAND_IN_OFF + 8 * K) * 8) = stg[K][I];
+#define BAND_ISSUE1(K, I) if constexpr (I < NI) stg[K][I] = *reinterpret_cast<const T*>(pb + ((movp[I] * strd + tl) << LS));
+#define BAND_COMMIT1(K, I) if constexpr (I < NI) *reinterpret_cast<T*>(wblk + ldsb[I] + (BAND_IN_OFF + 8 * K) * ES) = stg[K][I];
 #define BAND_ISSUE(K)                                                                                                         \
   if (pcs[K] >= 0) {   /* (wave-uniform) */                                                                                   \
     const int pc = pcs[K];                                                                                                    \
     const int arr = pc >> 28;                                                                                                 \
     const int el_ = (pc & ((1 << 28) - 1)) + (arr == 2 ? loff8 : 0);                                                          \
-    /* lane offset (doubles) = problem * strd + tl, tl = t + (t >> 3) * gap with t = m + element of the lane: the caller's arrays    \
+    /* lane offset (elements) = problem * strd + tl, tl = t + (t >> 3) * gap with t = m + element of the lane: the caller's arrays    \
        are problem-major (m = 0, t < 8: gap = 0), the factor is interleaved in blocks of eight (see lbase_g) */                \
     const bool il_ = arr == 0 ? vil : arr == 1 ? ril : LINT;   /* (wave-uniform) */                                           \
-    const int ilw_ = arr == 2 ? NL * 8 : BAND_IL_GROUP * 8;    /* doubles per block row: the factor's own layout / the ABI's */  \
+    const int ilw_ = arr == 2 ? NL * 8 : BAND_IL_GROUP * 8;    /* elements per block row: the factor's own layout / the ABI's */ \
     const int m_ = il_ ? (el_ & 7) : 0;                                                                                       \
     const unsigned gap_ = il_ ? (unsigned)(ilw_ - 8) : 0u;                                                                    \
     const char* pb = (arr == 0 ? reinterpret_cast<const char*>(vbase) : arr == 1 ? reinterpret_cast<const char*>(rbase)       \
                                                                                  : reinterpret_cast<const char*>(lbase_g)) +   \
-                     ((il_ ? (long long)(el_ >> 3) * ilw_ : (long long)el_) << 3);                                            \
+                     ((il_ ? (long long)(el_ >> 3) * ilw_ : (long long)el_) << LS);                                           \
     const unsigned strd = il_ ? 8u : arr == 0 ? (unsigned)nnz : arr == 1 ? (unsigned)N : (unsigned)lsize;                     \
     const unsigned t_ = (unsigned)m_ + (unsigned)le;                                                                          \
     const unsigned tl = t_ + (t_ >> 3) * gap_;                                                                                \
@@ -417,18 +438,18 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   }
   static_assert(NPC == 15, "fifteen operand pieces");
 
-  Win W;
+  Win<T> W;
   int npos = 0, nzer = 0;
-  double lj[6], zj[4];   // junction factor (first wavefront)
-  for (int q = 0; q < 6; q++) lj[q] = 0.0;
-  for (int q = 0; q < 4; q++) zj[q] = 0.0;
+  T lj[6], zj[4];   // junction factor (first wavefront)
+  for (int q = 0; q < 6; q++) lj[q] = T(0);
+  for (int q = 0; q < 4; q++) zj[q] = T(0);
   while (true) {
     // ================= forward: assembly, elimination, forward substitution =================
 #pragma unroll
-    for (int q = 0; q < NS * (NS + 1) / 2; q++) W.S[q] = 0.0;
+    for (int q = 0; q < NS * (NS + 1) / 2; q++) W.S[q] = T(0);
 #pragma unroll
-    for (int q = 0; q < NS; q++) { W.X[q] = 0.0; W.c[q] = 0.0; }
-    W.S55 = 0.0; W.c5 = 0.0;
+    for (int q = 0; q < NS; q++) { W.X[q] = T(0); W.c[q] = T(0); }
+    W.S55 = T(0); W.c5 = T(0);
     npos = 0; nzer = 0;
     BAND_ISSUE_ALL(epochs, BE_FP, fops_g, 0)
     for (int e = 0; e < nepochs; e++) {
@@ -455,7 +476,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
         const int onext = o + BAND_SW + BAND_RW * ((fl >> 8) & 255);                                                        \
         if (PHV + 1 < nst) { load_rec(stN, recb, onext); load_row(rwN, recb, onext + BAND_SW); }                            \
         if (clane) {                                                                                                        \
-          FOps op_;                                                                                                         \
+          FOps<T> op_;                                                                                                      \
           fload(op_, stC, rwC, fl, myb);                                                                                    \
           fstep<PHV>(W, op_, stC, fl, recb, o, myb, gvals, grhs, borders, pv, pr, has_rhs, rho, ovr, tol, npos, nzer, vstride, rstride); \
         }                                                                                                                   \
@@ -468,18 +489,18 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
       if (mode != MODE_FACTOR) {                                                                                            \
         const int lc_ = (LC);                                                                                               \
         const int lb_ = (LB) + loff8;                                                                                       \
-        char* lout = reinterpret_cast<char*>(lbase_g) + ((LINT ? (long long)(lb_ >> 3) * (NL * 8) : (long long)lb_) << 3);  \
+        char* lout = reinterpret_cast<char*>(lbase_g) + ((LINT ? (long long)(lb_ >> 3) * (NL * 8) : (long long)lb_) << LS); \
         const unsigned t_ = (LINT ? (unsigned)(lb_ & 7) : 0u) + (unsigned)le;                                               \
         const unsigned tl = t_ + (LINT ? (t_ >> 3) * (unsigned)(NL * 8 - 8) : 0u);                                          \
         const unsigned lstr_ = LINT ? 8u : (unsigned)lsize;                                                                 \
-        constexpr int lcp_ = LINT ? NL * 64 : 64;                                                                           \
-        double lx_[BAND_LOUT_MAX / 8][NI];                                                                                  \
+        constexpr int lcp_ = LINT ? NL * 8 * ES : 8 * ES;                                                                   \
+        T lx_[BAND_LOUT_MAX / 8][NI];                                                                                       \
         _Pragma("unroll") for (int cpc = 0; cpc < BAND_LOUT_MAX / 8; cpc++)                                                 \
-          _Pragma("unroll") for (int i = 0; i < NI; i++) lx_[cpc][i] = *reinterpret_cast<const double*>(wblk + ldsb[i] + (BAND_LOUT_OFF + 8 * cpc) * 8); \
+          _Pragma("unroll") for (int i = 0; i < NI; i++) lx_[cpc][i] = *reinterpret_cast<const T*>(wblk + ldsb[i] + (BAND_LOUT_OFF + 8 * cpc) * ES); \
         _Pragma("unroll") for (int cpc = 0; cpc < BAND_LOUT_MAX / 8; cpc++)                                                 \
           _Pragma("unroll") for (int i = 0; i < NI; i++)                                                                    \
             if (movok[i] && cpc * 8 + le < lc_)                                                                             \
-              *reinterpret_cast<double*>(lout + (((movp[i] * lstr_ + tl) << 3) + lcp_ * cpc)) = lx_[cpc][i];                 \
+              *reinterpret_cast<T*>(lout + (((movp[i] * lstr_ + tl) << LS) + lcp_ * cpc)) = lx_[cpc][i];                     \
       }
       BAND_FSTEP(0)
       if (more_) { BAND_ISSUE(0) BAND_ISSUE(1) BAND_ISSUE(2) BAND_ISSUE(3) }
@@ -500,9 +521,9 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
         for (int a = 0; a < NS; a++)
 #pragma unroll
           for (int b = 0; b <= a; b++)
-            if (b < 4) W.S[sidx(a, b)] = 0.0;
+            if (b < 4) W.S[sidx(a, b)] = T(0);
 #pragma unroll
-        for (int a = 0; a < 4; a++) { W.X[a] = 0.0; W.c[a] = 0.0; }
+        for (int a = 0; a < 4; a++) { W.X[a] = T(0); W.c[a] = T(0); }
       }
       BAND_LFLUSH(E[BE_LBASE2], E[BE_LCNT2])
     }
@@ -511,19 +532,19 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
     if (P.nparts == 2) {
       // windows to LDS (slot order): the junction reads both with run-time slot numbers
       if (clane) {
-        double* ex = reinterpret_cast<double*>(myb + EXCH_OFF * 8);
+        T* ex = reinterpret_cast<T*>(myb + EXCH_OFF * ES);
 #pragma unroll
         for (int q = 0; q < NS * (NS + 1) / 2; q++) ex[q] = W.S[q];
 #pragma unroll
         for (int q = 0; q < NS; q++) ex[36 + q] = W.c[q];
-        ex[44] = (double)npos; ex[45] = (double)nzer;
+        ex[44] = (T)npos; ex[45] = (T)nzer;
       }
       __syncthreads();
       if (part == 0 && clane) {
-        const double* exL = reinterpret_cast<const double*>(myb + EXCH_OFF * 8);
-        const double* exR = reinterpret_cast<const double*>(myb + (size_t)NL * LANE_D * 8 + EXCH_OFF * 8);
+        const T* exL = reinterpret_cast<const T*>(myb + EXCH_OFF * ES);
+        const T* exR = reinterpret_cast<const T*>(myb + (size_t)NL * LANE_D * ES + EXCH_OFF * ES);
         const int tL = P.m0 % NS, tR = (P.n - 1 - P.m0) % NS;
-        double SJ[10], cJ[4];
+        T SJ[10], cJ[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
           const int aL = (tL + i) % NS, aR = (tR - i + NS) % NS;
@@ -539,12 +560,12 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
         tpos += (int)exR[44]; tzer += (int)exR[45];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-          const double d = SJ[sidx(i, i)];
+          const T d = SJ[sidx(i, i)];
           tpos += d > tol;
           tzer += fabs(d) <= tol;
-          const double r = rrcp(d);
+          const T r = rrcp(d);
           zj[i] = rdiv(cJ[i], d, r);
-          double w[4];
+          T w[4];
 #pragma unroll
           for (int a = i + 1; a < 4; a++) { w[a] = SJ[sidx(a, i)]; lj[sidx(a - 1, i)] = rdiv(w[a], d, r); }
 #pragma unroll
@@ -573,10 +594,10 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
         nfact++;
         if (ok) { done = true; success = true; }
         else if (nfact == 1) {
-          rho = rho_old == 0.0 ? rho0 : fmax(rhomin, kdec * rho_old);
+          rho = rho_old == T(0) ? rho0 : fmax(rhomin, kdec * rho_old);
           ovr = true; wrote = rho;
         } else if (rho <= rhomax) {
-          rho = rho_old == 0.0 ? klarge * rho : kinc * rho;
+          rho = rho_old == T(0) ? klarge * rho : kinc * rho;
           if (rho <= rhomax) wrote = rho; else done = true;
         } else done = true;
       }
@@ -587,7 +608,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
     if (P.nparts == 2) {
       __syncthreads();
       if (part == 1) {
-        if (clane) { rho = ctrl[lane]; const int f = (int)ctrl[NL + lane]; ovr = f & 1; success = f & 2; }
+        if (clane) { rho = (T)ctrl[lane]; const int f = (int)ctrl[NL + lane]; ovr = f & 1; success = f & 2; }
         alldone = ctrl[2 * NL] != 0.0;
       }
       __syncthreads();   // the control block is rewritten by the next rung
@@ -600,18 +621,18 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   }
   // ================= backward: d = -K^-1 rhs where the factorisation succeeded =================
   {
-    double xs[NS + 1];
+    T xs[NS + 1];
 #pragma unroll
-    for (int q = 0; q < NS + 1; q++) xs[q] = 0.0;
+    for (int q = 0; q < NS + 1; q++) xs[q] = T(0);
     if (P.nparts == 2) {
       if (part == 0 && clane) {
-        double xj[4];
+        T xj[4];
         xj[3] = zj[3];
         xj[2] = fma(-lj[sidx(2, 2)], xj[3], zj[2]);
         xj[1] = fma(-lj[sidx(2, 1)], xj[3], fma(-lj[sidx(1, 1)], xj[2], zj[1]));
         xj[0] = fma(-lj[sidx(2, 0)], xj[3], fma(-lj[sidx(1, 0)], xj[2], fma(-lj[sidx(0, 0)], xj[1], zj[0])));
-        double* ex = reinterpret_cast<double*>(myb + EXCH_OFF * 8);
-        double* exR = reinterpret_cast<double*>(myb + (size_t)NL * LANE_D * 8 + EXCH_OFF * 8);
+        T* ex = reinterpret_cast<T*>(myb + EXCH_OFF * ES);
+        T* exR = reinterpret_cast<T*>(myb + (size_t)NL * LANE_D * ES + EXCH_OFF * ES);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
           ex[i] = xj[i]; exR[i] = xj[i];
@@ -620,13 +641,13 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
       }
       __syncthreads();
       if (clane) {
-        const double* ex = reinterpret_cast<const double*>(myb + EXCH_OFF * 8);
+        const T* ex = reinterpret_cast<const T*>(myb + EXCH_OFF * ES);
         const int t0 = part == 0 ? P.m0 % NS : (P.n - 1 - P.m0) % NS;
 #pragma unroll
         for (int s = 0; s < NS; s++) {
           // junction variable i sits in slot (t0 + i) % 8 (first part) / (t0 - i) % 8 (second part)
           const int i = part == 0 ? (s - t0 + NS) % NS : (t0 - s + NS) % NS;
-          xs[s] = i < 4 ? ex[i] : 0.0;
+          xs[s] = i < 4 ? ex[i] : T(0);
         }
       }
     }
@@ -656,7 +677,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
         const int onext = o + BAND_SW + BAND_RW * ((fl >> 8) & 255);                                                        \
         if (PHV > 0) { load_rec(stN, recb, onext); load_row(rwN, recb, onext + BAND_SW); }                                  \
         if (clane) {                                                                                                        \
-          BOps op_;                                                                                                         \
+          BOps<T> op_;                                                                                                      \
           bload(op_, stC, rwC, fl, myb);                                                                                    \
           bstep<PHV>(xs, op_, stC, rwC, fl, recb, o, myb, borders, gd, pd, okme);                                           \
         }                                                                                                                   \
@@ -673,24 +694,24 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
       BAND_BSTEP(3) BAND_BSTEP(2) BAND_BSTEP(1) BAND_BSTEP(0)
       // solution components of the epoch
       const int xlo = E[BE_DXLO], xc = E[BE_DXCNT], rlo = E[BE_DRLO], rc = E[BE_DRCNT];
-      char* dxo = reinterpret_cast<char*>(dbase) + ((long long)xlo << 3);
-      char* dro = reinterpret_cast<char*>(dbase) + ((long long)rlo << 3);
+      char* dxo = reinterpret_cast<char*>(dbase) + ((long long)xlo << LS);
+      char* dro = reinterpret_cast<char*>(dbase) + ((long long)rlo << LS);
       {
-        double dx_[NI], dr_[BAND_DR_MAX / 8][NI];
+        T dx_[NI], dr_[BAND_DR_MAX / 8][NI];
 #pragma unroll
-        for (int i = 0; i < NI; i++) dx_[i] = *reinterpret_cast<const double*>(wblk + ldsb[i] + BAND_DX_OFF * 8);
+        for (int i = 0; i < NI; i++) dx_[i] = *reinterpret_cast<const T*>(wblk + ldsb[i] + BAND_DX_OFF * ES);
 #pragma unroll
         for (int cpc = 0; cpc < BAND_DR_MAX / 8; cpc++)
 #pragma unroll
-          for (int i = 0; i < NI; i++) dr_[cpc][i] = *reinterpret_cast<const double*>(wblk + ldsb[i] + (BAND_DR_OFF + 8 * cpc) * 8);
+          for (int i = 0; i < NI; i++) dr_[cpc][i] = *reinterpret_cast<const T*>(wblk + ldsb[i] + (BAND_DR_OFF + 8 * cpc) * ES);
 #pragma unroll
         for (int i = 0; i < NI; i++)
-          if (movst[i] && le < xc) *reinterpret_cast<double*>(dxo + ((movp[i] * (unsigned)N + (unsigned)le) << 3)) = dx_[i];
+          if (movst[i] && le < xc) *reinterpret_cast<T*>(dxo + ((movp[i] * (unsigned)N + (unsigned)le) << LS)) = dx_[i];
 #pragma unroll
         for (int cpc = 0; cpc < BAND_DR_MAX / 8; cpc++)
 #pragma unroll
           for (int i = 0; i < NI; i++)
-            if (movst[i] && cpc * 8 + le < rc) *reinterpret_cast<double*>(dro + (((movp[i] * (unsigned)N + (unsigned)le) << 3) + 64 * cpc)) = dr_[cpc][i];
+            if (movst[i] && cpc * 8 + le < rc) *reinterpret_cast<T*>(dro + (((movp[i] * (unsigned)N + (unsigned)le) << LS) + 8 * ES * cpc)) = dr_[cpc][i];
       }
     }
   }
@@ -698,8 +719,8 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   if (part == 0 && mode == MODE_NEWTON) {
     if (nfact > 1 && rho <= rhomax) rho_old = rho;
     if (valid) {
-      as_global(Ain.rho)[cprob] = rho;
-      as_global(Ain.rho_old)[cprob] = rho_old;
+      as_global(reinterpret_cast<T*>(Ain.rho))[cprob] = rho;
+      as_global(reinterpret_cast<T*>(Ain.rho_old))[cprob] = rho_old;
       as_global(Ain.nfact)[cprob] = nfact;
       as_global(Ain.success)[cprob] = success ? 1 : 0;
     }
@@ -708,12 +729,14 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
       const int nf = __builtin_amdgcn_readlane(nfact, q);
       const int vq = __builtin_amdgcn_readlane((int)valid, q);
       if (nf > 1 && vq) {
-        const double wq = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(wrote), q), __builtin_amdgcn_readlane(__double2loint(wrote), q));
+        T wq;
+        if constexpr (ES == 8) wq = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(wrote), q), __builtin_amdgcn_readlane(__double2loint(wrote), q));
+        else wq = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wrote), q));
         if (vil) {
-          double* vg = gvals + ilg * band_il_blocks(nnz) * G8 + ilp + q * 8;
+          T* vg = gvals + ilg * band_il_blocks(nnz) * G8 + ilp + q * 8;
           for (int i = lane; i < P.nvar; i += 64) vg[band_il_offset(nnz - P.nvar + i, vstride)] = wq;
         } else {
-          double* vt = gvals + (long long)(prob0 + q) * nnz + (nnz - P.nvar);
+          T* vt = gvals + (long long)(prob0 + q) * nnz + (nnz - P.nvar);
           for (int i = lane; i < P.nvar; i += 64) vt[i] = wq;
         }
       }
@@ -721,10 +744,13 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   }
 }
 
-size_t band_lds_bytes(int nparts, int nl) { return ((size_t)nparts * nl * LANE_D + 2 * nl + 8) * sizeof(double) + (size_t)nparts * BAND_REC_MAX * 4; }
+size_t band_lds_bytes(int nparts, int nl, int esz) {
+  return (size_t)nparts * nl * LANE_D * esz + (2 * (size_t)nl + 8) * sizeof(double) + (size_t)nparts * BAND_REC_MAX * 4;
+}
 
-hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream) {
-  const size_t ldsb = band_lds_bytes(P.nparts, nl);
+template <class T>
+static hipError_t launch_band_t(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream) {
+  const size_t ldsb = band_lds_bytes(P.nparts, nl, (int)sizeof(T));
   const int grid = (a.batch + nl - 1) / nl;
   auto go = [&](auto kern) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)ldsb));
@@ -732,10 +758,13 @@ hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * P.nparts), ldsb, stream, P, a);
     return hipGetLastError();
   };
-  if (nl == 32) return go(band_newton_kernel<32>);
-  if (nl == 16) return go(band_newton_kernel<16>);
-  if (nl == 8) return go(band_newton_kernel<8>);
+  if (nl == 32) return go(band_newton_kernel<T, 32>);
+  if (nl == 16) return go(band_newton_kernel<T, 16>);
+  if (nl == 8) return go(band_newton_kernel<T, 8>);
   return hipErrorInvalidConfiguration;
 }
+
+hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream) { return launch_band_t<double>(P, nl, a, stream); }
+hipError_t launch_band_f32(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream) { return launch_band_t<float>(P, nl, a, stream); }
 
 }  // namespace cnl

@@ -12,6 +12,7 @@
 #include <condition_variable>
 #include <functional>
 #include <mutex>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -42,6 +43,8 @@ struct cnl_plan {
   bool split_mode = false;    // bidirectional-chain plan for a batch between one and two wavefronts per SIMD (capi.cpp, run_split)
   cnl::BandPlan band;         // (round 5) band program of a throughput plan (csrc/band.h); band.ok == false: the pattern is no band
   std::vector<int32_t> band_info, band_pinfo[2];
+  cnl::BandPlan band4;        // the same program for 4-byte elements (Float32 handles; cnl_plan_get "band4_*")
+  std::vector<int32_t> band4_info, band4_pinfo[2];
 };
 
 struct cnl_handle {
@@ -127,6 +130,13 @@ struct cnl_handle {
   int64_t jf_lo = 0, jf_n = 0, jc_lo = 0, jc_n = 0;
   int layout = 0;              // band handles: bit 0 = vals (cnl_options.batch_layout), bit 1 = rhs interleaved over groups of 32 problems (band.h)
   double* d_Lband = nullptr;   // [batch][bd.lsize] factor records of the band kernels
+  // Float32 handle (cnl_create_f32): the band kernels on float data, bd = the 4-byte program (plan->band4); nothing else of the
+  // handle's device state exists, and every Float64 entry point refuses it (CNL_ERR_STATE)
+  bool f32 = false;
+  float* f_Lband = nullptr;    // [batch + 32][bd.lsize] float factor records
+  const float* f_last_vals = nullptr;   // vals of the last factorisation (the band solve factorises them again)
+  // staging of the host-pointer calls: vals, rhs, d, and [rho | rho_old | nfact | success] as one block (nfact / success: int32)
+  float *f_vals = nullptr, *f_rhs = nullptr, *f_d = nullptr, *f_res = nullptr;
 };
 
 namespace {
@@ -136,6 +146,26 @@ thread_local std::string g_err;
 int fail(int code, const std::string& m) {
   g_err = m;
   return code;
+}
+
+// element type of a handle against that of the entry point: mixing them is a call-sequence error, refused before anything runs
+int need_f64(const cnl_handle* h, const char* fn) {
+  if (h && h->f32) return fail(CNL_ERR_STATE, std::string(fn) + ": this is a Float32 handle (cnl_create_f32); it takes the _f32 entry points only");
+  return CNL_OK;
+}
+int need_f32(const cnl_handle* h, const char* fn) {
+  if (h && !h->f32) return fail(CNL_ERR_STATE, std::string(fn) + ": this is a Float64 handle; the _f32 entry points need one made by cnl_create_f32");
+  return CNL_OK;
+}
+// the element arrays of cnl::LaunchArgs are double*: a Float32 launch stores its float arrays there (launch_band_f32 reads them as float)
+double* as_args(const float* p) { return reinterpret_cast<double*>(const_cast<float*>(p)); }
+#define CNL_NEED_F64(h) do { if (int rc_ = need_f64((h), __func__)) return rc_; } while (0)
+#define CNL_NEED_F32(h) do { if (int rc_ = need_f32((h), __func__)) return rc_; } while (0)
+
+// band program -> the summaries cnl_plan_get returns as "band_info" / "band_part<q>" (and "band4_...")
+void band_summary(const cnl::BandPlan& Bp, std::vector<int32_t>& info, std::vector<int32_t> (&pinfo)[2]) {
+  info = {Bp.ok ? 1 : 0, Bp.nparts, Bp.m0, Bp.n, Bp.N, Bp.nnz, (int32_t)Bp.lsize, 0};
+  for (int q = 0; q < 2; q++) pinfo[q] = {Bp.part[q].nsteps, Bp.part[q].nepochs, Bp.part[q].npiv, Bp.part[q].nevents, (int32_t)Bp.part[q].loff};
 }
 
 #define HIPCHK(expr)                                                                                   \
@@ -1071,12 +1101,11 @@ static int plan_create_impl(cnl_plan** plan, int64_t N, int64_t nnz, const int64
   if (!latency && o.band_kernel && p->C.active && !p->D.active) {
     cnl::build_band_plan(p->band, N, nnz, rows1, cols1, nvar, nequ, ncon, o.band_kernel == 2 ? 1 : 2);
     if (verbose) fprintf(stderr, "[cnl] band program: %s%s\n", p->band.ok ? "ok" : "no: ", p->band.ok ? "" : p->band.why.c_str());
+    // the program for 4-byte elements (Float32 handles): the same blocks, every LDS offset scaled
+    if (p->band.ok) cnl::build_band_plan(p->band4, N, nnz, rows1, cols1, nvar, nequ, ncon, o.band_kernel == 2 ? 1 : 2, 4);
   }
-  {
-    const cnl::BandPlan& Bp = p->band;
-    p->band_info = {Bp.ok ? 1 : 0, Bp.nparts, Bp.m0, Bp.n, Bp.N, Bp.nnz, (int32_t)Bp.lsize, 0};
-    for (int q = 0; q < 2; q++) p->band_pinfo[q] = {Bp.part[q].nsteps, Bp.part[q].nepochs, Bp.part[q].npiv, Bp.part[q].nevents, (int32_t)Bp.part[q].loff};
-  }
+  band_summary(p->band, p->band_info, p->band_pinfo);
+  band_summary(p->band4, p->band4_info, p->band4_pinfo);
   // Irregular sparsity: when the fill makes fronts larger than the register-front kernel takes and the condensed system is of
   // moderate order, one dense LDL^T of the whole condensed matrix beats the general multifrontal kernel by far
   // (csrc/dense.h; chosen at handle creation for small batches; CNL_NO_GDENSE=1 disables)
@@ -1160,6 +1189,18 @@ int cnl_plan_get(const cnl_plan* plan, const char* name, int32_t* out, int64_t* 
     const cnl::BandPart& Q = plan->band.part[q];
     const std::string k = s.substr(5, s.size() - 6);
     if (k == "part") { src = plan->band_pinfo[q].data(); n = (int64_t)plan->band_pinfo[q].size(); }
+    else if (k == "fops") { src = Q.fops.data(); n = (int64_t)Q.fops.size(); }
+    else if (k == "bops") { src = Q.bops.data(); n = (int64_t)Q.bops.size(); }
+    else if (k == "epochs") { src = Q.epochs.data(); n = (int64_t)Q.epochs.size(); }
+    else if (k == "borders") { src = Q.borders.data(); n = (int64_t)Q.borders.size(); }
+    else return fail(CNL_ERR_ARG, "unknown plan array: " + s);
+  }
+  else if (s == "band4_info") { src = plan->band4_info.data(); n = (int64_t)plan->band4_info.size(); }   // ... for 4-byte elements
+  else if (s.rfind("band4_", 0) == 0 && s.size() >= 7 && (s.back() == '0' || s.back() == '1')) {
+    const int q = s.back() - '0';
+    const cnl::BandPart& Q = plan->band4.part[q];
+    const std::string k = s.substr(6, s.size() - 7);
+    if (k == "part") { src = plan->band4_pinfo[q].data(); n = (int64_t)plan->band4_pinfo[q].size(); }
     else if (k == "fops") { src = Q.fops.data(); n = (int64_t)Q.fops.size(); }
     else if (k == "bops") { src = Q.bops.data(); n = (int64_t)Q.bops.size(); }
     else if (k == "epochs") { src = Q.epochs.data(); n = (int64_t)Q.epochs.size(); }
@@ -1538,6 +1579,7 @@ int cnl_prepare_newton_system_dev(cnl_handle* h, int64_t nnzhF, int64_t nnzhc, i
                                   const double* d_hc, const double* d_Jx, const double* d_Jcx, const double* d_delta, double* d_vals,
                                   void* stream) {
   if (!h || !d_vals || !d_Jx) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F64(h);
   const cnl::DevJt& J = h->djt;
   if (nnzhF < 0 || nnzhc < 0 || nnzjF < 0 || nnzjc < 0 || nnzhF + nnzhc + nnzjF + nnzjc + J.nequ + J.ncon + J.nvar != J.nnz)
     return fail(CNL_ERR_DIM, "segment sizes do not add up to nnz (7-segment layout of src/CaNNOLeS.jl:256-315)");
@@ -1570,6 +1612,7 @@ static int cgls_impl(cnl_handle* h, const cnl::JacSrc& S, const double* d_r, dou
 int cnl_cgls_multipliers_dev(cnl_handle* h, const double* d_vals, const double* d_r, double* d_lambda, double* d_Jxtr, double atol,
                              double rtol, int64_t itmax, int ones_if_zero, int32_t* d_iters, void* stream) {
   if (!h || !d_vals || !d_r) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F64(h);
   if (h->layout & 1) return fail(CNL_ERR_STATE, "cnl_cgls_multipliers_dev reads problem-major vals: on a handle with batch_layout = CNL_LAYOUT_INTERLEAVED use cnl_cgls_multipliers_jac_dev");
   return cgls_impl(h, cnl::JacSrc{d_vals, h->djt.nnz, d_vals, h->djt.nnz, 0, 0}, d_r, d_lambda, d_Jxtr, atol, rtol, itmax, ones_if_zero, d_iters, stream);
 }
@@ -1590,6 +1633,7 @@ int cnl_cgls_multipliers_jac_dev(cnl_handle* h, int64_t nnzjF, int64_t nnzjc, co
                                  double* d_lambda, double* d_Jxtr, double atol, double rtol, int64_t itmax, int ones_if_zero, int32_t* d_iters,
                                  void* stream) {
   if (!h || !d_r) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F64(h);
   cnl::JacSrc S{};
   if (int rc = jac_source(h, nnzjF, nnzjc, d_Jx, d_Jcx, &S)) return rc;
   return cgls_impl(h, S, d_r, d_lambda, d_Jxtr, atol, rtol, itmax, ones_if_zero, d_iters, stream);
@@ -1608,6 +1652,7 @@ static int residual_vectors_impl(cnl_handle* h, const cnl::JacSrc& S, const doub
 int cnl_residual_vectors_dev(cnl_handle* h, const double* d_vals, const double* d_r, const double* d_lambda, const double* d_Fx,
                              const double* d_cx, double* d_rhs, double* d_norms, void* stream) {
   if (!h || !d_vals) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F64(h);
   if (h->layout & 1) return fail(CNL_ERR_STATE, "cnl_residual_vectors_dev reads problem-major vals: on a handle with batch_layout = CNL_LAYOUT_INTERLEAVED use cnl_residual_vectors_jac_dev");
   return residual_vectors_impl(h, cnl::JacSrc{d_vals, h->djt.nnz, d_vals, h->djt.nnz, 0, 0}, d_r, d_lambda, d_Fx, d_cx, d_rhs, d_norms, stream);
 }
@@ -1615,6 +1660,7 @@ int cnl_residual_vectors_dev(cnl_handle* h, const double* d_vals, const double* 
 int cnl_residual_vectors_jac_dev(cnl_handle* h, int64_t nnzjF, int64_t nnzjc, const double* d_Jx, const double* d_Jcx, const double* d_r,
                                  const double* d_lambda, const double* d_Fx, const double* d_cx, double* d_rhs, double* d_norms, void* stream) {
   if (!h) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F64(h);
   cnl::JacSrc S{};
   if (int rc = jac_source(h, nnzjF, nnzjc, d_Jx, d_Jcx, &S)) return rc;
   return residual_vectors_impl(h, S, d_r, d_lambda, d_Fx, d_cx, d_rhs, d_norms, stream);
@@ -1623,6 +1669,7 @@ int cnl_residual_vectors_jac_dev(cnl_handle* h, int64_t nnzjF, int64_t nnzjc, co
 int cnl_trial_point_dev(cnl_handle* h, const double* d_x, const double* d_r, const double* d_lambda, const double* d_d,
                         double max_dlambda, double* d_xt, double* d_rt, double* d_lambdat, double* d_dlambda, void* stream) {
   if (!h || !d_x || !d_r || !d_d || !d_xt || !d_rt) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F64(h);
   if (h->djt.ncon > 0 && (!d_lambda || !d_lambdat || !d_dlambda)) return fail(CNL_ERR_ARG, "lambda vectors are required when ncon > 0");
   HIPCHK(hipSetDevice(h->device));
   hipError_t e = cnl::launch_trial_point(h->djt, d_x, d_r, d_lambda, d_d, max_dlambda, d_xt, d_rt, d_lambdat, d_dlambda, (int)h->batch,
@@ -1655,8 +1702,14 @@ static int convert_layout(cnl_handle* h, int which, const double* src, double* d
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("interleave: ") + hipGetErrorString(e));
   return CNL_OK;
 }
-int cnl_interleave_dev(cnl_handle* h, int which, const double* d_src, double* d_dst, void* stream) { return convert_layout(h, which, d_src, d_dst, 1, stream); }
-int cnl_deinterleave_dev(cnl_handle* h, int which, const double* d_src, double* d_dst, void* stream) { return convert_layout(h, which, d_src, d_dst, 0, stream); }
+int cnl_interleave_dev(cnl_handle* h, int which, const double* d_src, double* d_dst, void* stream) {
+  CNL_NEED_F64(h);
+  return convert_layout(h, which, d_src, d_dst, 1, stream);
+}
+int cnl_deinterleave_dev(cnl_handle* h, int which, const double* d_src, double* d_dst, void* stream) {
+  CNL_NEED_F64(h);
+  return convert_layout(h, which, d_src, d_dst, 0, stream);
+}
 
 int cnl_set_timing(cnl_handle* h, int enable) {
   if (!h) return fail(CNL_ERR_ARG, "null handle");
@@ -1679,6 +1732,10 @@ int cnl_launch_counts(int64_t counts[3]) {
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   if (!h || !cfg) return fail(CNL_ERR_ARG, "null argument");
   std::memset(cfg, 0, 8 * sizeof(int64_t));
+  if (h->f32) {   // Float32 handle: the band kernels only
+    cfg[5] = 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->layout << 25) | ((int64_t)1 << 27);
+    return CNL_OK;
+  }
   cfg[0] = h->cfg.tpp; cfg[1] = h->cfg.ppb; cfg[2] = (int64_t)h->cfg.lds_bytes; cfg[3] = h->cfg.lds_work;
   cfg[4] = (h->batch + h->cfg.ppb - 1) / h->cfg.ppb;
   cfg[5] = (h->dense || h->gdense) ? 3 : (h->use_v2 ? (h->staged ? 4 : 2) : 1);
@@ -1694,6 +1751,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
 // ---- device-pointer entry points -------------------------------------------------
 int cnl_factorize_dev(cnl_handle* h, const double* d_vals, double eig_tol, int32_t* d_success, void* stream) {
   if (!h || !d_vals || !d_success) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F64(h);
   HIPCHK(hipSetDevice(h->device));
   cnl::LaunchArgs a{};
   a.mode = cnl::MODE_FACTOR;
@@ -1706,6 +1764,7 @@ int cnl_factorize_dev(cnl_handle* h, const double* d_vals, double eig_tol, int32
 
 int cnl_solve_dev(cnl_handle* h, const double* d_rhs, double* d_d, void* stream) {
   if (!h || !d_rhs || !d_d) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F64(h);
   if (!h->factorized) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
   HIPCHK(hipSetDevice(h->device));
   cnl::LaunchArgs a{};
@@ -1717,6 +1776,7 @@ int cnl_newton_system_dev(cnl_handle* h, double* d_vals, const double* d_rhs, do
                           int32_t* d_nfact, int32_t* d_success, const double params[9], void* stream) {
   if (!h || !d_vals || !d_rhs || !d_d || !d_rho_old || !d_rho || !d_nfact || !d_success || !params)
     return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F64(h);
   HIPCHK(hipSetDevice(h->device));
   cnl::LaunchArgs a{};
   a.mode = cnl::MODE_NEWTON;
@@ -1730,6 +1790,7 @@ int cnl_newton_system_dev(cnl_handle* h, double* d_vals, const double* d_rhs, do
 // ---- host-pointer entry points (what the Julia glue ccalls) ------------------------
 int cnl_factorize(cnl_handle* h, const double* vals, double eig_tol, int32_t* success, int64_t* npos, int64_t* nzero) {
   if (!h || !vals || !success) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F64(h);
   if (h->layout) return fail(CNL_ERR_STATE, "host-pointer calls take the reference's problem-major arrays: this handle was created with batch_layout = CNL_LAYOUT_INTERLEAVED (device-pointer entry points only)");
   HIPCHK(hipSetDevice(h->device));
   int rc = ensure_staging(h);
@@ -1768,6 +1829,7 @@ int cnl_factorize(cnl_handle* h, const double* vals, double eig_tol, int32_t* su
 
 int cnl_solve(cnl_handle* h, const double* rhs, double* d) {
   if (!h || !rhs || !d) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F64(h);
   if (h->layout) return fail(CNL_ERR_STATE, "host-pointer calls take the reference's problem-major arrays: this handle was created with batch_layout = CNL_LAYOUT_INTERLEAVED (device-pointer entry points only)");
   if (!h->factorized) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
   HIPCHK(hipSetDevice(h->device));
@@ -2004,6 +2066,7 @@ static int host_ladder_run(cnl_handle* h, const double params[9], const double* 
 int cnl_newton_system(cnl_handle* h, double* vals, const double* rhs, double* d, const double* rho_old, const double params[9],
                       double* rho, double* rho_old_out, int32_t* nfact, int32_t* success) {
   if (!h || !vals || !rhs || !d || !params || !rho || !rho_old_out || !nfact || !success) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F64(h);
   if (h->layout) return fail(CNL_ERR_STATE, "host-pointer calls take the reference's problem-major arrays: this handle was created with batch_layout = CNL_LAYOUT_INTERLEAVED (device-pointer entry points only)");
   HIPCHK(hipSetDevice(h->device));
   int rc = ensure_staging(h);
@@ -2218,6 +2281,295 @@ int cnl_newton_system(cnl_handle* h, double* vals, const double* rhs, double* d,
   return CNL_OK;
 }
 
+
+// ---- Float32 handles: LDLFactorization{Float32} / ParamCaNNOLeS(Float32) on the band kernels (include/cannoles_hip.h) ----------
+void cnl_default_params_f32(float p[9]) {
+  // src/CaNNOLeS.jl:48-62 with T = Float32, each value what Julia computes on Float32 operands, rounded once
+  const float eps = FLT_EPSILON;   // eps(Float32) = 2^-23
+  p[0] = eps;
+  p[1] = std::sqrt(eps);
+  p[2] = 1.0f / 3.0f;
+  p[3] = 8.0f;
+  p[4] = std::min(100.0f, (float)(sizeof(float) * 16));   // sizeof(T) * 16 = 64
+  p[5] = (float)std::pow((double)eps, (double)(1.0f / 3.0f));   // eps^(T(1)/3), the Float32 exponent
+  p[6] = (float)std::pow((double)eps, -2.0);
+  p[7] = std::sqrt(eps);
+  p[8] = (float)std::pow((double)eps, 0.25);
+}
+
+static int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, int64_t batch, int device) {
+  cnl_handle* h = new cnl_handle();
+  h->plan = plan; h->device = device; h->batch = batch; h->f32 = true;
+  auto bail = [&](int code) { cnl_destroy(h); return code; };
+  if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
+  int rc = CNL_OK;
+  const cnl::BandPlan& Bp = plan->band4;
+  cnl::BandDev& bd = h->bd;
+  for (int q = 0; q < Bp.nparts; q++) {
+    if ((rc = upload(h, Bp.part[q].fops, &bd.fops[q]))) return bail(rc);
+    if ((rc = upload(h, Bp.part[q].bops, &bd.bops[q]))) return bail(rc);
+    if ((rc = upload(h, Bp.part[q].epochs, &bd.epochs[q]))) return bail(rc);
+    if ((rc = upload(h, Bp.part[q].borders, &bd.borders[q]))) return bail(rc);
+    bd.nsteps[q] = Bp.part[q].nsteps; bd.nepochs[q] = Bp.part[q].nepochs; bd.loff[q] = Bp.part[q].loff;
+  }
+  bd.nparts = Bp.nparts; bd.m0 = Bp.m0; bd.n = Bp.n; bd.N = Bp.N; bd.nnz = Bp.nnz; bd.nvar = (int32_t)plan->nvar; bd.lsize = Bp.lsize;
+  // problems per workgroup: the Float64 handles' rule
+  h->band_nl = plan->opt.band_problems_per_group > 0 ? plan->opt.band_problems_per_group : (batch > 8192 ? 32 : 16);
+  if (h->band_nl != 8 && h->band_nl != 16 && h->band_nl != 32) return bail(fail(CNL_ERR_ARG, "band_problems_per_group must be 8, 16 or 32"));
+  const uint64_t span = sizeof(float) * (uint64_t)h->band_nl * (uint64_t)std::max<int64_t>({plan->nnz, plan->N, bd.lsize});
+  if (span >= (1ull << 32)) return bail(fail(CNL_ERR_ARG, "cnl_create_f32: the arrays of a workgroup's problems span 4 GB or more (32-bit offsets of the band kernels)"));
+  if (cnl::band_lds_bytes(bd.nparts, h->band_nl, (int)sizeof(float)) > std::min<size_t>(cnl::max_lds_bytes(), 160 * 1024))
+    return bail(fail(CNL_ERR_ARG, "cnl_create_f32: the band kernels' LDS does not fit a workgroup"));
+  // (+ 32 problems: the records of a workgroup's problems are interleaved in one region, the last workgroup's is a whole one)
+  const size_t lfloats = ((size_t)batch + 32) * (size_t)bd.lsize + 64;
+  if ((rc = dalloc(h, &h->f_Lband, lfloats))) return bail(rc);
+  if (hipMemset(h->f_Lband, 0, lfloats * sizeof(float)) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipMemset failed"));
+  h->band = true;
+  if (plan->opt.batch_layout != CNL_LAYOUT_PROBLEM_MAJOR) {
+    if (plan->opt.batch_layout != CNL_LAYOUT_INTERLEAVED) return bail(fail(CNL_ERR_ARG, "cnl_options.batch_layout: unknown layout"));
+    h->layout = 1 | (plan->opt.band_rhs_interleaved ? 2 : 0);
+  }
+  // dimensions cnl_layout_len reads
+  h->djt.nvar = (int32_t)plan->nvar; h->djt.nequ = (int32_t)plan->nequ; h->djt.ncon = (int32_t)plan->ncon;
+  h->djt.N = (int32_t)plan->N; h->djt.nnz = (int32_t)plan->nnz;
+  if (hipStreamCreate(&h->stream) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipStreamCreate failed"));
+  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipEventCreate failed"));
+  *hout = h;
+  return CNL_OK;
+}
+
+int cnl_create_f32(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ,
+                   int64_t ncon, int64_t batch, int device) {
+  return cnl_create_f32_ex(hout, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, nullptr);
+}
+
+int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ,
+                      int64_t ncon, int64_t batch, int device, const cnl_options* opt) {
+  if (!hout) return fail(CNL_ERR_ARG, "null handle pointer");
+  *hout = nullptr;
+  cnl::Tuning o;
+  if (int rc = resolve_options(opt, o)) return rc;
+  if (batch < 1 || batch > (1 << 24)) return fail(CNL_ERR_ARG, "batch out of range");
+  if (!o.band_kernel) return fail(CNL_ERR_ARG, "cnl_create_f32: cnl_options.band_kernel = 0, and Float32 handles run on the band kernels only");
+  int ndev = 0;
+  const hipError_t ce = hipGetDeviceCount(&ndev);
+  if (ce != hipSuccess || ndev == 0)
+    return fail(CNL_ERR_HIP, std::string("no HIP device available (this backend has no CPU fallback): hipGetDeviceCount -> ") +
+                                 hipGetErrorString(ce) + ", " + std::to_string(ndev) + " device(s)");
+  if (device < 0 || device >= ndev) return fail(CNL_ERR_ARG, "device index out of range");
+  // the throughput analysis whatever the batch: there is nothing but the band program to run
+  cnl_plan* plan = nullptr;
+  if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, o)) return rc;
+  if (!plan->band4.ok) {   // (the analysis builds it next to the Float64 program; not for a pattern the Float64 handles serve otherwise)
+    cnl::build_band_plan(plan->band4, N, nnz, rows1, cols1, nvar, nequ, ncon, o.band_kernel == 2 ? 1 : 2, (int)sizeof(float));
+    band_summary(plan->band4, plan->band4_info, plan->band4_pinfo);
+  }
+  if (!plan->band4.ok) {
+    const std::string why = plan->band4.why;
+    cnl_plan_destroy(plan);
+    return fail(CNL_ERR_ARG, "cnl_create_f32: the pattern is not served by the band kernels (build_band_plan: " + why +
+                                 "); Float32 stays on the CPU backend for it");
+  }
+  return create_f32_from_plan(hout, plan, batch, device);
+}
+
+static int launch_f32(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
+  if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
+  a.batch = (int)h->batch;
+  a.L = as_args(h->f_Lband);
+  a.layout = h->layout;
+  if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
+  const hipError_t e = cnl::launch_band_f32(h->bd, h->band_nl, a, stream);
+  g_launches[0]++;
+  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("band kernel launch (Float32): ") + hipGetErrorString(e));
+  if (h->timing) {
+    HIPCHK(hipEventRecord(h->ev1, stream));
+    HIPCHK(hipEventSynchronize(h->ev1));
+    HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+  }
+  return CNL_OK;
+}
+
+static int ensure_staging_f32(cnl_handle* h) {
+  if (h->f_vals) return CNL_OK;
+  const cnl_plan& P = *h->plan;
+  const size_t B = (size_t)h->batch;
+  int rc;
+  if ((rc = dalloc(h, &h->f_vals, B * P.nnz))) return rc;
+  if ((rc = dalloc(h, &h->f_rhs, B * P.N))) return rc;
+  if ((rc = dalloc(h, &h->f_d, B * P.N))) return rc;
+  static_assert(sizeof(float) == sizeof(int32_t), "[rho | rho_old | nfact | success]: four arrays of 4-byte words");
+  if ((rc = dalloc(h, &h->f_res, 4 * B))) return rc;
+  if ((rc = dalloc(h, &h->d_npos, B * 2))) return rc;
+  h->d_nzero = h->d_npos + B;
+  return CNL_OK;
+}
+
+int cnl_factorize_f32_dev(cnl_handle* h, const float* d_vals, float eig_tol, int32_t* d_success, void* stream) {
+  if (!h || !d_vals || !d_success) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F32(h);
+  HIPCHK(hipSetDevice(h->device));
+  cnl::LaunchArgs a{};
+  a.mode = cnl::MODE_FACTOR;
+  a.vals = as_args(d_vals);
+  a.success = d_success;
+  a.params[0] = eig_tol;
+  const int rc = launch_f32(h, a, (hipStream_t)stream);
+  if (rc == CNL_OK) { h->factorized = true; h->f_last_vals = d_vals; h->last_ok.clear(); }
+  return rc;
+}
+
+int cnl_solve_f32_dev(cnl_handle* h, const float* d_rhs, float* d_d, void* stream) {
+  if (!h || !d_rhs || !d_d) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F32(h);
+  if (!h->factorized) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
+  HIPCHK(hipSetDevice(h->device));
+  // (the band kernels' solve factorises the values of the last factorisation again, rho slots as the ladder left them: see launch())
+  cnl::LaunchArgs a{};
+  a.mode = cnl::MODE_SOLVE;
+  a.vals = as_args(h->f_last_vals); a.rhs = as_args(d_rhs); a.d = as_args(d_d);
+  return launch_f32(h, a, (hipStream_t)stream);
+}
+
+int cnl_newton_system_f32_dev(cnl_handle* h, float* d_vals, const float* d_rhs, float* d_d, float* d_rho_old, float* d_rho,
+                              int32_t* d_nfact, int32_t* d_success, const float params[9], void* stream) {
+  if (!h || !d_vals || !d_rhs || !d_d || !d_rho_old || !d_rho || !d_nfact || !d_success || !params)
+    return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F32(h);
+  HIPCHK(hipSetDevice(h->device));
+  cnl::LaunchArgs a{};
+  a.mode = cnl::MODE_NEWTON;
+  a.vals = as_args(d_vals); a.rhs = as_args(d_rhs); a.d = as_args(d_d);
+  a.rho_old = as_args(d_rho_old); a.rho = as_args(d_rho); a.nfact = d_nfact; a.success = d_success;
+  for (int k = 0; k < 9; k++) a.params[k] = params[k];   // (exact: the kernel narrows them back)
+  const int rc = launch_f32(h, a, (hipStream_t)stream);
+  if (rc == CNL_OK) { h->factorized = true; h->f_last_vals = d_vals; h->last_ok.clear(); }
+  return rc;
+}
+
+static const char* kHostLayoutF32 = "host-pointer calls take the reference's problem-major arrays: this handle was created with batch_layout = "
+                                    "CNL_LAYOUT_INTERLEAVED (device-pointer entry points only)";
+
+int cnl_factorize_f32(cnl_handle* h, const float* vals, float eig_tol, int32_t* success, int64_t* npos, int64_t* nzero) {
+  if (!h || !vals || !success) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F32(h);
+  if (h->layout) return fail(CNL_ERR_STATE, kHostLayoutF32);
+  HIPCHK(hipSetDevice(h->device));
+  int rc = ensure_staging_f32(h);
+  if (rc) return rc;
+  const cnl_plan& P = *h->plan;
+  const size_t B = (size_t)h->batch;
+  int32_t* d_success = reinterpret_cast<int32_t*>(h->f_res) + 3 * B;
+  HIPCHK(hipMemcpyAsync(h->f_vals, vals, B * P.nnz * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  cnl::LaunchArgs a{};
+  a.mode = cnl::MODE_FACTOR;
+  a.vals = as_args(h->f_vals);
+  a.success = d_success; a.npos = h->d_npos; a.nzero = h->d_nzero;
+  a.params[0] = eig_tol;
+  if ((rc = launch_f32(h, a, h->stream))) return rc;
+  HIPCHK(hipMemcpyAsync(success, d_success, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (npos) HIPCHK(hipMemcpyAsync(npos, h->d_npos, B * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  if (nzero) HIPCHK(hipMemcpyAsync(nzero, h->d_nzero, B * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->f_last_vals = h->f_vals;
+  h->factorized = true;
+  h->last_ok.assign(success, success + B);
+  return CNL_OK;
+}
+
+int cnl_solve_f32(cnl_handle* h, const float* rhs, float* d) {
+  if (!h || !rhs || !d) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F32(h);
+  if (h->layout) return fail(CNL_ERR_STATE, kHostLayoutF32);
+  if (!h->factorized) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
+  const size_t B = (size_t)h->batch;
+  const bool known = h->last_ok.size() == B;
+  if (known && B == 1 && !h->last_ok[0])
+    return fail(CNL_ERR_STATE, "cnl_solve after a factorisation that failed (success = 0): there is no factor to solve with "
+                               "(the reference calls solve_ldl! only after a successful try_to_factorize, src/CaNNOLeS.jl:1049)");
+  HIPCHK(hipSetDevice(h->device));
+  int rc = ensure_staging_f32(h);
+  if (rc) return rc;
+  const cnl_plan& P = *h->plan;
+  HIPCHK(hipMemcpyAsync(h->f_rhs, rhs, B * P.N * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  cnl::LaunchArgs a{};
+  a.mode = cnl::MODE_SOLVE;
+  a.vals = as_args(h->f_last_vals); a.rhs = as_args(h->f_rhs); a.d = as_args(h->f_d);
+  if ((rc = launch_f32(h, a, h->stream))) return rc;
+  size_t b0 = 0;
+  while (b0 < B) {  // rows of the problems that hold a factor (all of them after a device-pointer factorisation); the others stay
+    while (known && b0 < B && !h->last_ok[b0]) b0++;
+    size_t b1 = b0;
+    while (b1 < B && (!known || h->last_ok[b1])) b1++;
+    if (b1 > b0) HIPCHK(hipMemcpyAsync(d + b0 * P.N, h->f_d + b0 * P.N, (b1 - b0) * P.N * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    b0 = b1;
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return CNL_OK;
+}
+
+int cnl_newton_system_f32(cnl_handle* h, float* vals, const float* rhs, float* d, const float* rho_old, const float params[9], float* rho,
+                          float* rho_old_out, int32_t* nfact, int32_t* success) {
+  if (!h || !vals || !rhs || !d || !params || !rho || !rho_old_out || !nfact || !success) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F32(h);
+  if (h->layout) return fail(CNL_ERR_STATE, kHostLayoutF32);
+  HIPCHK(hipSetDevice(h->device));
+  int rc = ensure_staging_f32(h);
+  if (rc) return rc;
+  const cnl_plan& P = *h->plan;
+  const size_t B = (size_t)h->batch;
+  float* d_rho = h->f_res;
+  float* d_rho_old = h->f_res + B;
+  int32_t* d_nfact = reinterpret_cast<int32_t*>(h->f_res + 2 * B);
+  int32_t* d_success = d_nfact + B;
+  HIPCHK(hipMemcpyAsync(h->f_vals, vals, B * P.nnz * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->f_rhs, rhs, B * P.N * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (rho_old) HIPCHK(hipMemcpyAsync(d_rho_old, rho_old, B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  else HIPCHK(hipMemsetAsync(d_rho_old, 0, B * sizeof(float), h->stream));
+  cnl::LaunchArgs a{};
+  a.mode = cnl::MODE_NEWTON;
+  a.vals = as_args(h->f_vals); a.rhs = as_args(h->f_rhs); a.d = as_args(h->f_d);
+  a.rho_old = as_args(d_rho_old); a.rho = as_args(d_rho); a.nfact = d_nfact; a.success = d_success;
+  for (int k = 0; k < 9; k++) a.params[k] = params[k];
+  if ((rc = launch_f32(h, a, h->stream))) return rc;
+  h->f_last_vals = h->f_vals;
+  HIPCHK(hipMemcpyAsync(success, d_success, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  // the reference leaves d untouched when the factorisation fails (src/CaNNOLeS.jl:1049): the rows that succeeded come back
+  size_t b0 = 0;
+  while (b0 < B) {
+    while (b0 < B && !success[b0]) b0++;
+    size_t b1 = b0;
+    while (b1 < B && success[b1]) b1++;
+    if (b1 > b0) HIPCHK(hipMemcpyAsync(d + b0 * P.N, h->f_d + b0 * P.N, (b1 - b0) * P.N * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    b0 = b1;
+  }
+  HIPCHK(hipMemcpyAsync(rho, d_rho, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(rho_old_out, d_rho_old, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(nfact, d_nfact, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  // rho tail of vals (the reference mutates get_vals(LDLT)[end-nvar+1:end], src/CaNNOLeS.jl:1031,1038)
+  if (P.nvar > 0)
+    HIPCHK(hipMemcpy2DAsync(vals + (P.nnz - P.nvar), (size_t)P.nnz * sizeof(float), h->f_vals + (P.nnz - P.nvar), (size_t)P.nnz * sizeof(float),
+                            (size_t)P.nvar * sizeof(float), B, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->factorized = true;
+  h->last_ok.assign(success, success + B);
+  return CNL_OK;
+}
+
+static int convert_layout_f32(cnl_handle* h, int which, const float* src, float* dst, int to_interleaved, void* stream) {
+  if (!h || !src || !dst) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F32(h);
+  if (src == dst) return fail(CNL_ERR_ARG, "the conversion is not in place");
+  int64_t len = 0;
+  if (int rc = layout_rowlen(h, which, &len)) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  hipError_t e = cnl::launch_interleave_f32(src, dst, (int)h->batch, len, to_interleaved, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("interleave: ") + hipGetErrorString(e));
+  return CNL_OK;
+}
+int cnl_interleave_f32_dev(cnl_handle* h, int which, const float* d_src, float* d_dst, void* stream) { return convert_layout_f32(h, which, d_src, d_dst, 1, stream); }
+int cnl_deinterleave_f32_dev(cnl_handle* h, int which, const float* d_src, float* d_dst, void* stream) { return convert_layout_f32(h, which, d_src, d_dst, 0, stream); }
 
 // ---- one caller, several devices: contiguous balanced shards of the batch, one handle + one host thread per
 //      device, no collective — the devices never exchange data --------------------------------------------------------------

@@ -172,7 +172,10 @@ struct BandDev {
 // newton_system! / try_to_factorize of a.batch problems on the band kernels, nl problems per workgroup (8, 16 or 32); a.L = the
 // band factor storage [batch][P.lsize]
 hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream);
-size_t band_lds_bytes(int nparts, int nl);
+// the same on Float32 data: a.vals / rhs / d / L / rho_old / rho hold float arrays (stored through the double* fields), a.params the
+// Float32 parameters widened to double; P is the 4-byte program (build_band_plan with esz = 4), P.lsize counts floats
+hipError_t launch_band_f32(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream);
+size_t band_lds_bytes(int nparts, int nl, int esz = 8);   // esz: bytes per element (8 double, 4 float)
 
 // returns hipSuccess or the launch error
 hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream);
@@ -190,6 +193,7 @@ hipError_t launch_prepare(int nnzhF, int nnzhc, int nnzjF, int nnzjc, int nvar, 
                           const double* Jx, const double* Jcx, const double* delta, double* vals, int batch, int interleaved, hipStream_t stream);
 // problem-major <-> interleaved over groups of 32 problems (band.h: band_il_index); rows of `len` doubles
 hipError_t launch_interleave(const double* src, double* dst, int batch, long long len, int to_interleaved, hipStream_t stream);
+hipError_t launch_interleave_f32(const float* src, float* dst, int batch, long long len, int to_interleaved, hipStream_t stream);
 hipError_t launch_cgls(const DevJt& J, const JacSrc& S, const double* r, double* lambda, double* Jxtr, double* ws, int32_t* iters,
                        double atol, double rtol, int itmax, int ones_if_zero, int batch, hipStream_t stream);
 hipError_t launch_residual_vectors(const DevJt& J, const JacSrc& S, const double* r, const double* lambda, const double* Fx,

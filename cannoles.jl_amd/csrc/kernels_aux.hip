@@ -705,19 +705,21 @@ __device__ __forceinline__ long long il_tile_dst(long long g, long long nb, int 
   kk = bl * 8 + j;
   return ((g * nb + (long long)chunk * (IL_TILE / 8) + bl) * BAND_IL_GROUP + p) * 8 + j;
 }
-__global__ void __launch_bounds__(256) interleave_kernel(const double* __restrict__ src, double* __restrict__ dst, int batch, long long len,
+// (T = float for Float32 handles: the same blocks of eight elements)
+template <class T>
+__global__ void __launch_bounds__(256) interleave_kernel(const T* __restrict__ src, T* __restrict__ dst, int batch, long long len,
                                                          int to_interleaved) {
-  __shared__ double tile[BAND_IL_GROUP * IL_PITCH];
+  __shared__ T tile[BAND_IL_GROUP * IL_PITCH];
   const long long g = blockIdx.y, nb = band_il_blocks(len);
   const int chunk = blockIdx.x, t = threadIdx.x;
   if (to_interleaved) {
-    double x[BAND_IL_GROUP / 2];   // (every load before the first LDS store)
+    T x[BAND_IL_GROUP / 2];   // (every load before the first LDS store)
     const int kk = t & (IL_TILE - 1);
     const long long k = (long long)chunk * IL_TILE + kk;
 #pragma unroll
     for (int it = 0; it < BAND_IL_GROUP / 2; it++) {
       const long long prob = g * BAND_IL_GROUP + 2 * it + (t >> 7);
-      x[it] = (prob < batch && k < len) ? __builtin_nontemporal_load(src + prob * len + k) : 0.0;
+      x[it] = (prob < batch && k < len) ? __builtin_nontemporal_load(src + prob * len + k) : T(0);
     }
 #pragma unroll
     for (int it = 0; it < BAND_IL_GROUP / 2; it++) tile[(2 * it + (t >> 7)) * IL_PITCH + kk] = x[it];
@@ -731,7 +733,7 @@ __global__ void __launch_bounds__(256) interleave_kernel(const double* __restric
     for (int i = 0; i < BAND_IL_GROUP * IL_TILE / 256; i++) {
       int p, kk;
       const long long o = il_tile_dst(g, nb, chunk, i * 256 + t, p, kk);
-      tile[p * IL_PITCH + kk] = ((long long)chunk * (IL_TILE / 8) + kk / 8 < nb) ? __builtin_nontemporal_load(src + o) : 0.0;
+      tile[p * IL_PITCH + kk] = ((long long)chunk * (IL_TILE / 8) + kk / 8 < nb) ? __builtin_nontemporal_load(src + o) : T(0);
     }
     __syncthreads();
     for (int it = 0; it < BAND_IL_GROUP / 2; it++) {
@@ -742,11 +744,18 @@ __global__ void __launch_bounds__(256) interleave_kernel(const double* __restric
   }
 }
 
-hipError_t launch_interleave(const double* src, double* dst, int batch, long long len, int to_interleaved, hipStream_t stream) {
+template <class T>
+static hipError_t launch_interleave_t(const T* src, T* dst, int batch, long long len, int to_interleaved, hipStream_t stream) {
   const long long groups = (batch + BAND_IL_GROUP - 1) / BAND_IL_GROUP, chunks = (band_il_blocks(len) * 8 + IL_TILE - 1) / IL_TILE;
   if (batch <= 0 || len <= 0 || groups > 65535 || chunks > 0x7fffffffLL) return hipErrorInvalidConfiguration;
-  hipLaunchKernelGGL(interleave_kernel, dim3((unsigned)chunks, (unsigned)groups), dim3(256), 0, stream, src, dst, batch, len, to_interleaved);
+  hipLaunchKernelGGL(interleave_kernel<T>, dim3((unsigned)chunks, (unsigned)groups), dim3(256), 0, stream, src, dst, batch, len, to_interleaved);
   return hipGetLastError();
+}
+hipError_t launch_interleave(const double* src, double* dst, int batch, long long len, int to_interleaved, hipStream_t stream) {
+  return launch_interleave_t(src, dst, batch, len, to_interleaved, stream);
+}
+hipError_t launch_interleave_f32(const float* src, float* dst, int batch, long long len, int to_interleaved, hipStream_t stream) {
+  return launch_interleave_t(src, dst, batch, len, to_interleaved, stream);
 }
 
 // prepare_newton_system! writing `vals` interleaved (the values and the "left alone" rules of prepare_kernel above, the tiles of

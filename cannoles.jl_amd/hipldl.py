@@ -42,6 +42,9 @@ ABI_SYMBOLS = [
     "cnl_outer_begin_dev", "cnl_outer_newton_done_dev", "cnl_outer_extrapolated_dev", "cnl_outer_trial_done_dev", "cnl_outer_end_dev",
     "cnl_outer_ls_begin_dev", "cnl_outer_ls_test_dev", "cnl_outer_ls_step_dev", "cnl_outer_ls_take_dev",
     "cnl_layout_len", "cnl_interleave_dev", "cnl_deinterleave_dev", "cnl_residual_vectors_jac_dev", "cnl_cgls_multipliers_jac_dev",
+    "cnl_default_params_f32", "cnl_create_f32", "cnl_create_f32_ex",
+    "cnl_factorize_f32", "cnl_solve_f32", "cnl_newton_system_f32",
+    "cnl_factorize_f32_dev", "cnl_solve_f32_dev", "cnl_newton_system_f32_dev", "cnl_interleave_f32_dev", "cnl_deinterleave_f32_dev",
 ]
 
 
@@ -224,6 +227,19 @@ def lib():
         L.cnl_cgls_multipliers_jac_dev.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, dbl, dbl, i64, C.c_int, vp, vp]
         L.cnl_interleave_dev.argtypes = [vp, C.c_int, vp, vp, vp]
         L.cnl_deinterleave_dev.argtypes = [vp, C.c_int, vp, vp, vp]
+        flt = C.c_float
+        L.cnl_default_params_f32.argtypes = [vp]
+        L.cnl_default_params_f32.restype = None
+        L.cnl_create_f32.argtypes = [C.POINTER(vp), i64, i64, _i64p, _i64p, i64, i64, i64, i64, C.c_int]
+        L.cnl_create_f32_ex.argtypes = [C.POINTER(vp), i64, i64, _i64p, _i64p, i64, i64, i64, i64, C.c_int, vp]
+        L.cnl_factorize_f32.argtypes = [vp, vp, flt, vp, vp, vp]
+        L.cnl_solve_f32.argtypes = [vp, vp, vp]
+        L.cnl_newton_system_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cnl_factorize_f32_dev.argtypes = [vp, vp, flt, vp, vp]
+        L.cnl_solve_f32_dev.argtypes = [vp, vp, vp, vp]
+        L.cnl_newton_system_f32_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cnl_interleave_f32_dev.argtypes = [vp, C.c_int, vp, vp, vp]
+        L.cnl_deinterleave_f32_dev.argtypes = [vp, C.c_int, vp, vp, vp]
         for fn in ("cnl_outer_begin_dev", "cnl_outer_extrapolated_dev", "cnl_outer_trial_done_dev", "cnl_outer_end_dev", "cnl_outer_ls_begin_dev",
                    "cnl_outer_ls_step_dev", "cnl_outer_ls_take_dev"):
             getattr(L, fn).argtypes = [vp, vp]
@@ -240,9 +256,16 @@ def _check(rc):
         raise CnlError(rc, lib().cnl_last_error().decode())
 
 
-def default_params():
-    """ParamCaNNOLeS(Float64) (src/CaNNOLeS.jl:48-62) as
-    [eig_tol, dmin, kdec, kinc, klargeinc, rho0, rhomax, rhomin, gammaA]."""
+def default_params(dtype=np.float64):
+    """ParamCaNNOLeS(T) (src/CaNNOLeS.jl:48-62) as [eig_tol, dmin, kdec, kinc, klargeinc, rho0, rhomax, rhomin, gammaA];
+    T = Float64 (cnl_default_params) or Float32 (cnl_default_params_f32)."""
+    dt = np.dtype(dtype)
+    if dt == np.float32:
+        p = np.zeros(9, np.float32)
+        lib().cnl_default_params_f32(p.ctypes.data)
+        return p
+    if dt != np.float64:
+        raise TypeError(f"ParamCaNNOLeS({dt}): this backend serves Float64 and Float32 only")
     p = np.zeros(9)
     lib().cnl_default_params(p.ctypes.data)
     return p
@@ -316,9 +339,13 @@ class _Factor:
 class HIPLDLStruct:
     """`struct HIPLDLStruct <: LinearSolverStruct` — drop-in for LDLFactStruct
     (src/solver_types.jl:45-65).  `batch > 1` is the batched twin: one shared
-    pattern, problem-major values `vals[b, :]`."""
+    pattern, problem-major values `vals[b, :]`.
 
-    def __init__(self, N, rows, cols, vals, nvar=None, nequ=None, ncon=None, batch=1, device=0, options=None):
+    The element type comes from `vals`, as `LDLFactStruct(N, rows, cols, vals)` takes T from it (`dtype` when vals is None):
+    float64, or float32 — a Float32 handle (cnl_create_f32), which exists for band-structured patterns only (CnlError
+    CNL_ERR_ARG otherwise: the caller stays on the CPU backend)."""
+
+    def __init__(self, N, rows, cols, vals, nvar=None, nequ=None, ncon=None, batch=1, device=0, options=None, dtype=np.float64):
         self.N = int(N)
         self.rows, self.cols = _i64(rows), _i64(cols)
         self.nnz = len(self.rows)
@@ -326,15 +353,20 @@ class HIPLDLStruct:
         if nvar is None:
             raise ValueError("nvar/nequ/ncon are required (the Julia glue passes them from the solver)")
         self.nvar, self.nequ, self.ncon = int(nvar), int(nequ), int(ncon)
+        self.dtype = np.dtype(np.asarray(vals).dtype if vals is not None else dtype)
+        if self.dtype not in (np.float64, np.float32):
+            raise TypeError(f"element type {self.dtype}: this backend serves Float64 and Float32 (band patterns) only; other element types "
+                            "stay on LDLFactStruct")
+        f32 = self.dtype == np.float32
         # `vals` is aliased, not copied: the driver mutates the array returned by get_vals
-        self.vals = vals if vals is not None else np.ones((self.batch, self.nnz) if self.batch > 1 else self.nnz)
+        self.vals = vals if vals is not None else np.ones((self.batch, self.nnz) if self.batch > 1 else self.nnz, self.dtype)
         h = C.c_void_p()
         if options is None:
-            _check(lib().cnl_create(C.byref(h), self.N, self.nnz, self.rows, self.cols, self.nvar, self.nequ, self.ncon,
-                                    self.batch, int(device)))
+            _check((lib().cnl_create_f32 if f32 else lib().cnl_create)(C.byref(h), self.N, self.nnz, self.rows, self.cols, self.nvar, self.nequ,
+                                                                        self.ncon, self.batch, int(device)))
         else:
-            _check(lib().cnl_create_ex(C.byref(h), self.N, self.nnz, self.rows, self.cols, self.nvar, self.nequ, self.ncon,
-                                       self.batch, int(device), _optref(options)))
+            _check((lib().cnl_create_f32_ex if f32 else lib().cnl_create_ex)(C.byref(h), self.N, self.nnz, self.rows, self.cols, self.nvar,
+                                                                              self.nequ, self.ncon, self.batch, int(device), _optref(options)))
         self._h = h
         self.factor = _Factor(self)
         self.info = _plan_info(lib().cnl_get_plan(h))
@@ -344,7 +376,10 @@ class HIPLDLStruct:
                        "kernel": {2: "v2", 3: "dense", 4: "v2-staged"}.get(int(cfg[5]) & 15, "v1"), "wpb": int(cfg[6]), "lds2_bytes": int(cfg[7]),
                        "lean": bool(int(cfg[5]) & 16), "tail": bool(int(cfg[5]) & 32), "band": bool(int(cfg[5]) & 64), "f1_tiles": bool(int(cfg[5]) & 128),
                        "band_nl": (int(cfg[5]) >> 8) & 255, "band_parts": (int(cfg[5]) >> 16) & 255,
-                       "batch_layout": (int(cfg[5]) >> 25) & 1, "rhs_interleaved": bool((int(cfg[5]) >> 26) & 1)}
+                       "batch_layout": (int(cfg[5]) >> 25) & 1, "rhs_interleaved": bool((int(cfg[5]) >> 26) & 1),
+                       "float32": bool((int(cfg[5]) >> 27) & 1)}
+        if self.config["float32"]:
+            self.config["kernel"] = "band"
 
     def plan_array(self, name):
         return _plan_array(lib().cnl_get_plan(self._h), name)
@@ -399,17 +434,46 @@ def _f64c(a, shape=None):
     return a
 
 
+def _is_f32(LDLT):
+    return getattr(LDLT, "dtype", np.float64) == np.float32
+
+
+def _valsc(LDLT, a):
+    """a C-contiguous array of the handle's element type (float64, or float32 on a Float32 handle); mixing types is a TypeError"""
+    if not _is_f32(LDLT):
+        return _f64c(a)
+    a = np.asarray(a)
+    if a.dtype != np.float32 or not a.flags.c_contiguous:
+        raise TypeError(f"expected a C-contiguous float32 array on a Float32 handle, got {a.dtype}")
+    return a
+
+
+def _dev_ptr(LDLT, x):
+    """device address of a `_dev` argument: an int, or a tensor (torch) whose element type must be the handle's"""
+    if hasattr(x, "data_ptr"):
+        want = "float32" if _is_f32(LDLT) else "float64"
+        if str(x.dtype).rsplit(".", 1)[-1] != want:
+            raise TypeError(f"expected a {want} tensor on this handle, got {x.dtype}")
+        return x.data_ptr()
+    return x
+
+
+def _int_ptr(x):
+    return x.data_ptr() if hasattr(x, "data_ptr") else x
+
+
 def try_to_factorize(LDLT, vals, nvar, nequ, ncon, eig_tol, return_inertia=False):
     """success = try_to_factorize(LDLT, vals, nvar, nequ, ncon, eig_tol) (src/solver_types.jl:79-98).
     Batched handles return arrays."""
     assert (nvar, nequ, ncon) == (LDLT.nvar, LDLT.nequ, LDLT.ncon)
-    vals = _f64c(vals)
+    vals = _valsc(LDLT, vals)
     assert vals.size == LDLT.batch * LDLT.nnz
     B = LDLT.batch
     succ = np.zeros(B, np.int32)
     npos = np.zeros(B, np.int64)
     nzer = np.zeros(B, np.int64)
-    _check(lib().cnl_factorize(LDLT._h, vals.ctypes.data, float(eig_tol), succ.ctypes.data, npos.ctypes.data, nzer.ctypes.data))
+    fn = lib().cnl_factorize_f32 if _is_f32(LDLT) else lib().cnl_factorize
+    _check(fn(LDLT._h, vals.ctypes.data, float(eig_tol), succ.ctypes.data, npos.ctypes.data, nzer.ctypes.data))
     if B == 1:
         return (bool(succ[0]), int(npos[0]), int(nzer[0])) if return_inertia else bool(succ[0])
     return (succ.astype(bool), npos, nzer) if return_inertia else succ.astype(bool)
@@ -418,10 +482,10 @@ def try_to_factorize(LDLT, vals, nvar, nequ, ncon, eig_tol, return_inertia=False
 def solve_ldl_(rhs, factor, d):
     """solve_ldl!(rhs, factor, d): d = -(K^-1 rhs), returns true (src/solver_types.jl:69-77)."""
     LDLT = factor._owner
-    rhs = _f64c(rhs)
-    d = _f64c(d)
+    rhs = _valsc(LDLT, rhs)
+    d = _valsc(LDLT, d)
     assert rhs.size == LDLT.batch * LDLT.N and d.size == rhs.size
-    _check(lib().cnl_solve(LDLT._h, rhs.ctypes.data, d.ctypes.data))
+    _check((lib().cnl_solve_f32 if _is_f32(LDLT) else lib().cnl_solve)(LDLT._h, rhs.ctypes.data, d.ctypes.data))
     return True
 
 
@@ -431,17 +495,18 @@ def newton_system_(d, nvar, nequ, ncon, rhs, vals, LDLT, rho_old, params):
     Batched handles take/return arrays for rho_old / success / rho / nfact."""
     assert (nvar, nequ, ncon) == (LDLT.nvar, LDLT.nequ, LDLT.ncon)
     B = LDLT.batch
-    vals = _f64c(vals)
-    rhs = _f64c(rhs)
-    d = _f64c(d)
+    vals = _valsc(LDLT, vals)
+    rhs = _valsc(LDLT, rhs)
+    d = _valsc(LDLT, d)
     assert vals.size == B * LDLT.nnz and rhs.size == B * LDLT.N and d.size == B * LDLT.N
-    ro = np.ascontiguousarray(np.broadcast_to(np.asarray(rho_old, dtype=np.float64), (B,)))
-    params = np.ascontiguousarray(params, dtype=np.float64)
-    rho = np.zeros(B)
-    ro_out = np.zeros(B)
+    T = np.float32 if _is_f32(LDLT) else np.float64
+    ro = np.ascontiguousarray(np.broadcast_to(np.asarray(rho_old, dtype=T), (B,)))
+    params = np.ascontiguousarray(params, dtype=T)
+    rho = np.zeros(B, T)
+    ro_out = np.zeros(B, T)
     nfact = np.zeros(B, np.int32)
     succ = np.zeros(B, np.int32)
-    _check(lib().cnl_newton_system(LDLT._h, vals.ctypes.data, rhs.ctypes.data, d.ctypes.data, ro.ctypes.data,
+    _check((lib().cnl_newton_system_f32 if T == np.float32 else lib().cnl_newton_system)(LDLT._h, vals.ctypes.data, rhs.ctypes.data, d.ctypes.data, ro.ctypes.data,
                                    params.ctypes.data, rho.ctypes.data, ro_out.ctypes.data, nfact.ctypes.data,
                                    succ.ctypes.data))
     if B == 1:
@@ -451,10 +516,25 @@ def newton_system_(d, nvar, nequ, ncon, rhs, vals, LDLT, rho_old, params):
 
 def newton_system_dev(LDLT, vals_ptr, rhs_ptr, d_ptr, rho_old_ptr, rho_ptr, nfact_ptr, success_ptr, params, stream=0):
     """Device-resident twin (cnl_newton_system_dev): all *_ptr are device addresses
-    (e.g. torch.Tensor.data_ptr()); asynchronous on `stream` (a hipStream_t value)."""
-    params = np.ascontiguousarray(params, dtype=np.float64)
-    _check(lib().cnl_newton_system_dev(LDLT._h, vals_ptr, rhs_ptr, d_ptr, rho_old_ptr, rho_ptr, nfact_ptr, success_ptr,
-                                       params.ctypes.data, stream))
+    (e.g. torch.Tensor.data_ptr(), or the tensors themselves: their element type is checked against the handle's);
+    asynchronous on `stream` (a hipStream_t value).  Float32 handles: cnl_newton_system_f32_dev, float32 arrays and params."""
+    f32 = _is_f32(LDLT)
+    params = np.ascontiguousarray(params, dtype=np.float32 if f32 else np.float64)
+    v, r, dd, ro, rh = (_dev_ptr(LDLT, x) for x in (vals_ptr, rhs_ptr, d_ptr, rho_old_ptr, rho_ptr))
+    _check((lib().cnl_newton_system_f32_dev if f32 else lib().cnl_newton_system_dev)(LDLT._h, v, r, dd, ro, rh, _int_ptr(nfact_ptr),
+                                                                                    _int_ptr(success_ptr), params.ctypes.data, stream))
+
+
+def factorize_dev(LDLT, vals_ptr, eig_tol, success_ptr, stream=0):
+    """try_to_factorize on device-resident vals (cnl_factorize_dev / cnl_factorize_f32_dev by the handle's element type)"""
+    fn = lib().cnl_factorize_f32_dev if _is_f32(LDLT) else lib().cnl_factorize_dev
+    _check(fn(LDLT._h, _dev_ptr(LDLT, vals_ptr), float(eig_tol), _int_ptr(success_ptr), stream))
+
+
+def solve_dev(LDLT, rhs_ptr, d_ptr, stream=0):
+    """solve_ldl! on device-resident rhs / d (cnl_solve_dev / cnl_solve_f32_dev by the handle's element type)"""
+    fn = lib().cnl_solve_f32_dev if _is_f32(LDLT) else lib().cnl_solve_dev
+    _check(fn(LDLT._h, _dev_ptr(LDLT, rhs_ptr), _dev_ptr(LDLT, d_ptr), stream))
 
 
 def residual_vectors_dev(LDLT, vals_ptr, r_ptr, lambda_ptr, Fx_ptr, cx_ptr, rhs_ptr, norms_ptr, stream=0):
@@ -479,20 +559,22 @@ def trial_point_dev(LDLT, x_ptr, r_ptr, lambda_ptr, d_ptr, max_dlambda, xt_ptr, 
 
 
 def layout_len(LDLT, which):
-    """doubles of the interleaved array of the handle's batch; which = 0: vals, 1: an N-vector per problem (cnl_layout_len)"""
+    """elements of the interleaved array of the handle's batch; which = 0: vals, 1: an N-vector per problem (cnl_layout_len)"""
     n = C.c_int64(0)
     _check(lib().cnl_layout_len(LDLT._h, int(which), C.byref(n)))
     return int(n.value)
 
 
 def interleave_dev(LDLT, which, src_ptr, dst_ptr, stream=0):
-    """problem-major -> CNL_LAYOUT_INTERLEAVED on the device, out of place (cnl_interleave_dev)"""
-    _check(lib().cnl_interleave_dev(LDLT._h, int(which), src_ptr, dst_ptr, stream))
+    """problem-major -> CNL_LAYOUT_INTERLEAVED on the device, out of place (cnl_interleave_dev / cnl_interleave_f32_dev)"""
+    fn = lib().cnl_interleave_f32_dev if _is_f32(LDLT) else lib().cnl_interleave_dev
+    _check(fn(LDLT._h, int(which), _dev_ptr(LDLT, src_ptr), _dev_ptr(LDLT, dst_ptr), stream))
 
 
 def deinterleave_dev(LDLT, which, src_ptr, dst_ptr, stream=0):
-    """CNL_LAYOUT_INTERLEAVED -> problem-major on the device, out of place (cnl_deinterleave_dev)"""
-    _check(lib().cnl_deinterleave_dev(LDLT._h, int(which), src_ptr, dst_ptr, stream))
+    """CNL_LAYOUT_INTERLEAVED -> problem-major on the device, out of place (cnl_deinterleave_dev / cnl_deinterleave_f32_dev)"""
+    fn = lib().cnl_deinterleave_f32_dev if _is_f32(LDLT) else lib().cnl_deinterleave_dev
+    _check(fn(LDLT._h, int(which), _dev_ptr(LDLT, src_ptr), _dev_ptr(LDLT, dst_ptr), stream))
 
 
 def prepare_newton_system_dev(LDLT, nnzhF, nnzhc, nnzjF, nnzjc, hF_ptr, hc_ptr, Jx_ptr, Jcx_ptr, delta_ptr, vals_ptr, stream=0):

@@ -100,6 +100,79 @@ function newton_system!(f::HIPFactor, vals::Vector{Float64}, rhs::Vector{Float64
   return f.success[] != 0, f.rho[], f.rho_out[], Int(f.nfact[])
 end
 
+# ---- Float32 (LDLFactorization{Float32}) for direct batched callers: band-structured patterns only, on the band kernels
+# (include/cannoles_hip.h, `_f32` entry points).  `HIPFactor` above stays the Float64 factor the extension uses. ---------------
+
+"""
+    HIPFactor32(N, rows, cols, nvar, nequ, ncon; batch = 1, device = 0)
+
+`cnl_create_f32`: a Float32 solver object for `batch` problems sharing the pattern (problem-major arrays `vals[(b-1)*nnz + k]`,
+`rhs[(b-1)*N + i]`).  Throws `CnlError` (code 1) when the pattern is not a band: such a caller stays on `LDLFactStruct`.
+"""
+mutable struct HIPFactor32
+  handle::Ptr{Cvoid}
+  N::Int
+  nnz::Int
+  batch::Int
+end
+
+function destroy!(f::HIPFactor32)
+  if f.handle != C_NULL
+    ccall((:cnl_destroy, libcnl), Cint, (Ptr{Cvoid},), f.handle)
+    f.handle = C_NULL
+  end
+  return nothing
+end
+
+function HIPFactor32(N::Integer, rows::Vector{Int64}, cols::Vector{Int64}, nvar::Integer, nequ::Integer, ncon::Integer;
+                     batch::Integer = 1, device::Integer = 0)
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ccall((:cnl_create_f32, libcnl), Cint,
+    (Ref{Ptr{Cvoid}}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Int64, Int64, Int64, Cint),
+    h, N, length(rows), rows, cols, nvar, nequ, ncon, batch, device))
+  f = HIPFactor32(h[], N, length(rows), batch)
+  finalizer(destroy!, f)
+  return f
+end
+
+"ParamCaNNOLeS(Float32) — /root/reference/src/CaNNOLeS.jl:48-62 — as the 9-tuple `newton_system!` takes"
+function default_params_f32()
+  p = Ref(ntuple(_ -> 0.0f0, 9))
+  ccall((:cnl_default_params_f32, libcnl), Cvoid, (Ref{NTuple{9, Float32}},), p)
+  return p[]
+end
+
+"try_to_factorize of every problem — /root/reference/src/solver_types.jl:79-98; fills `success` (and the inertia counts)"
+function factorize!(f::HIPFactor32, vals::Vector{Float32}, eig_tol::Float32, success::Vector{Int32},
+                    npos::Vector{Int64} = zeros(Int64, f.batch), nzero::Vector{Int64} = zeros(Int64, f.batch))
+  length(vals) == f.batch * f.nnz && length(success) == length(npos) == length(nzero) == f.batch || throw(DimensionMismatch("batched arrays"))
+  check(ccall((:cnl_factorize_f32, libcnl), Cint,
+    (Ptr{Cvoid}, Ptr{Float32}, Float32, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}),
+    f.handle, vals, eig_tol, success, npos, nzero))
+  return success
+end
+
+"solve_ldl! of every problem that holds a factor — /root/reference/src/solver_types.jl:69-77 (the other rows of `d` stay)"
+function solve!(f::HIPFactor32, rhs::Vector{Float32}, d::Vector{Float32})
+  length(rhs) == length(d) == f.batch * f.N || throw(DimensionMismatch("batched arrays"))
+  check(ccall((:cnl_solve_f32, libcnl), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), f.handle, rhs, d))
+  return true
+end
+
+"""
+newton_system! of every problem — /root/reference/src/CaNNOLeS.jl:1008-1052 with T = Float32, fused on the device.  `ρold` is
+read, `ρ`, `ρold_out`, `nfact`, `success` are filled, the rho slots of `vals` are written back as the reference leaves them.
+"""
+function newton_system!(f::HIPFactor32, vals::Vector{Float32}, rhs::Vector{Float32}, d::Vector{Float32}, ρold::Vector{Float32},
+                        params::NTuple{9, Float32}, ρ::Vector{Float32}, ρold_out::Vector{Float32}, nfact::Vector{Int32}, success::Vector{Int32})
+  length(vals) == f.batch * f.nnz && length(rhs) == length(d) == f.batch * f.N || throw(DimensionMismatch("batched arrays"))
+  length(ρold) == length(ρ) == length(ρold_out) == length(nfact) == length(success) == f.batch || throw(DimensionMismatch("per-problem arrays"))
+  check(ccall((:cnl_newton_system_f32, libcnl), Cint,
+    (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ref{NTuple{9, Float32}}, Ptr{Float32}, Ptr{Float32}, Ptr{Int32}, Ptr{Int32}),
+    f.handle, vals, rhs, d, ρold, params, ρ, ρold_out, nfact, success))
+  return success
+end
+
 # ---- optional device-resident helpers (SURVEY rows a4/f1/f2/f4).  They take DEVICE pointers (e.g. `pointer(::ROCArray)` from
 # AMDGPU.jl) and a hipStream_t; batched layouts are problem-major. ---------------------------------------------------------
 

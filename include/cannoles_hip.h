@@ -8,8 +8,11 @@
  *
  * Conventions
  *   - Index arrays are int64, 1-based, exactly as Julia holds `rows`/`cols`
- *     (src/CaNNOLeS.jl:276-315).  Values are double (Float64 only; other
- *     element types must stay on the reference's LDLFactStruct).
+ *     (src/CaNNOLeS.jl:276-315).  Values are double (Float64).  Float32 is
+ *     served on band-structured patterns (the band kernels, csrc/band.h) by
+ *     handles of its own: cnl_create_f32 and the `_f32` entry points below.
+ *     Every other element type, and Float32 on any other pattern, stays on
+ *     the reference's LDLFactStruct.
  *   - The COO pattern is the lower triangle of the KKT matrix in the
  *     reference's 7-segment order [H_F | H_c | J_F | J_c | -I | -dI | rI];
  *     duplicates are summed in COO order (src/solver_types.jl:53-59); the
@@ -344,10 +347,38 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  * + 64 when cnl_newton_system runs on the band kernels (then bits 8-15 = problems per workgroup, bits 16-23 = parts of the chain),
  * + 128 when cnl_residual_vectors_dev runs on column tiles. */
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
+/* ([5] + (1 << 27) on a Float32 handle, which runs the band kernels only: bits 8-26 as above, cfg[0..4], [6], [7] are 0.) */
 /* Launches of the Newton-system kernels since the library was loaded, per kernel family: counts[0] band kernels (csrc/band.hip),
  * [1] register-front kernel (csrc/kernels2.hip, staged launches not included), [2] general kernel (csrc/kernels.hip).  Lets a test
  * pin WHICH kernel served a call sequence (e.g. that solve_ldl! behind a band factorisation launches no second kernel family). */
 int cnl_launch_counts(int64_t counts[3]);
+
+/* ---- Float32 (LDLFactorization{Float32}, ParamCaNNOLeS(Float32)) on the band kernels ------------------------------------
+ * A Float32 handle stores values, rhs, d, rho, rho_old and the factor records as float and computes in float (fmaf, float
+ * compares, the inertia test against eig_tol = eps(Float32)): what the reference computes with T = Float32
+ * (src/solver_types.jl:79-98, src/CaNNOLeS.jl:1008-1052).  It serves the plugin surface only — try_to_factorize, solve_ldl!,
+ * newton_system! — in host-pointer and `_dev` forms, in either cnl_options.batch_layout, always on the band kernels (any batch,
+ * 1 included).  cnl_create_f32 / cnl_create_f32_ex take the arguments of cnl_create / cnl_create_ex and fail with CNL_ERR_ARG
+ * (cnl_last_error names the reason) when the pattern is not a band or cnl_options.band_kernel = 0: the caller stays on the CPU.
+ * The semantics of every call are those of its Float64 twin above.  Mixing element types is CNL_ERR_STATE and does nothing:
+ * a Float64 entry point on a Float32 handle (cnl_factorize..., the row f1 / f2 / f4 / trial-point passes, cnl_interleave_dev...)
+ * and an `_f32` entry point on a Float64 handle.  cnl_layout_len counts elements, so it serves both types.
+ *   cnl_default_params_f32: ParamCaNNOLeS(Float32), src/CaNNOLeS.jl:48-62, in the order of cnl_default_params.       */
+void cnl_default_params_f32(float params[9]);
+int cnl_create_f32(cnl_handle** h, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1,
+                   int64_t nvar, int64_t nequ, int64_t ncon, int64_t batch, int device);
+int cnl_create_f32_ex(cnl_handle** h, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1,
+                      int64_t nvar, int64_t nequ, int64_t ncon, int64_t batch, int device, const cnl_options* opt);
+int cnl_factorize_f32(cnl_handle* h, const float* vals, float eig_tol, int32_t* success, int64_t* npos, int64_t* nzero);
+int cnl_solve_f32(cnl_handle* h, const float* rhs, float* d);
+int cnl_newton_system_f32(cnl_handle* h, float* vals, const float* rhs, float* d, const float* rho_old,
+                          const float params[9], float* rho, float* rho_old_out, int32_t* nfact, int32_t* success);
+int cnl_factorize_f32_dev(cnl_handle* h, const float* d_vals, float eig_tol, int32_t* d_success, void* stream);
+int cnl_solve_f32_dev(cnl_handle* h, const float* d_rhs, float* d_d, void* stream);
+int cnl_newton_system_f32_dev(cnl_handle* h, float* d_vals, const float* d_rhs, float* d_d, float* d_rho_old,
+                              float* d_rho, int32_t* d_nfact, int32_t* d_success, const float params[9], void* stream);
+int cnl_interleave_f32_dev(cnl_handle* h, int which, const float* d_src, float* d_dst, void* stream);
+int cnl_deinterleave_f32_dev(cnl_handle* h, int which, const float* d_src, float* d_dst, void* stream);
 
 #ifdef __cplusplus
 }
