@@ -130,13 +130,14 @@ struct cnl_handle {
   int64_t jf_lo = 0, jf_n = 0, jc_lo = 0, jc_n = 0;
   int layout = 0;              // band handles: bit 0 = vals (cnl_options.batch_layout), bit 1 = rhs interleaved over groups of 32 problems (band.h)
   double* d_Lband = nullptr;   // [batch][bd.lsize] factor records of the band kernels
-  // Float32 handle (cnl_create_f32): the band kernels on float data, bd = the 4-byte program (plan->band4); nothing else of the
-  // handle's device state exists, and every Float64 entry point refuses it (CNL_ERR_STATE)
+  // Float32 handle (cnl_create_f32): the band kernels on float data, bd = the 4-byte program (plan->band4), and the row lists of rows
+  // f1 / f4 (djt, jac_segments); nothing else of the handle's device state exists, and every Float64 entry point refuses it (CNL_ERR_STATE)
   bool f32 = false;
   float* f_Lband = nullptr;    // [batch + 32][bd.lsize] float factor records
   const float* f_last_vals = nullptr;   // vals of the last factorisation (the band solve factorises them again)
   // staging of the host-pointer calls: vals, rhs, d, and [rho | rho_old | nfact | success] as one block (nfact / success: int32)
   float *f_vals = nullptr, *f_rhs = nullptr, *f_d = nullptr, *f_res = nullptr;
+  float* f_cgls_ws = nullptr;  // [batch][2 * nvar] workspace of cnl_cgls_multipliers_f32_dev, allocated on first use
 };
 
 namespace {
@@ -864,6 +865,81 @@ int multi_run(cnl_multi* m, F f) {
 }  // namespace
 
 
+// ---- rows f1 / f2 / f4 and the trial point on device pointers: one implementation per row for both element types (the launchers
+//      of kernels.h are overloaded on float / double); the entry points (extern "C" below) check the handle's element type first ----
+// the CGLS workspace of the handle's element type
+static double*& cgls_ws(cnl_handle* h, const double*) { return h->d_cgls_ws; }
+static float*& cgls_ws(cnl_handle* h, const float*) { return h->f_cgls_ws; }
+
+template <class T>
+static int prepare_impl(cnl_handle* h, int64_t nnzhF, int64_t nnzhc, int64_t nnzjF, int64_t nnzjc, const T* d_hF, const T* d_hc, const T* d_Jx,
+                        const T* d_Jcx, const T* d_delta, T* d_vals, void* stream) {
+  const cnl::DevJt& J = h->djt;
+  if (nnzhF < 0 || nnzhc < 0 || nnzjF < 0 || nnzjc < 0 || nnzhF + nnzhc + nnzjF + nnzjc + J.nequ + J.ncon + J.nvar != J.nnz)
+    return fail(CNL_ERR_DIM, "segment sizes do not add up to nnz (7-segment layout of src/CaNNOLeS.jl:256-315)");
+  if (J.ncon > 0 && (!d_hc || !d_Jcx || !d_delta)) return fail(CNL_ERR_ARG, "hc / Jcx / delta are required when ncon > 0");
+  if (J.ncon == 0 && (nnzhc != 0 || nnzjc != 0)) return fail(CNL_ERR_DIM, "constraint segments must be empty when ncon == 0");
+  HIPCHK(hipSetDevice(h->device));
+  hipError_t e = cnl::launch_prepare((int)nnzhF, (int)nnzhc, (int)nnzjF, (int)nnzjc, J.nvar, J.nequ, J.ncon, d_hF, d_hc, d_Jx, d_Jcx,
+                                     d_delta, d_vals, (int)h->batch, h->layout & 1, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("prepare_newton_system: ") + hipGetErrorString(e));
+  return CNL_OK;
+}
+
+template <class T>
+static int cgls_impl(cnl_handle* h, const cnl::JacSrcT<T>& S, const T* d_r, T* d_lambda, T* d_Jxtr, T atol, T rtol, int64_t itmax,
+                     int ones_if_zero, int32_t* d_iters, void* stream) {
+  if (h->djt.ncon == 0) return CNL_OK;  // nothing to estimate
+  if (!d_lambda) return fail(CNL_ERR_ARG, "null lambda");
+  if (h->djt.ncon > 1024) return fail(CNL_ERR_DIM, "cnl_cgls_multipliers_dev supports at most 1024 constraints");
+  HIPCHK(hipSetDevice(h->device));
+  T*& ws = cgls_ws(h, d_r);
+  if (!ws) {
+    int rc = dalloc(h, &ws, (size_t)h->batch * 2 * (size_t)h->djt.nvar);
+    if (rc) return rc;
+  }
+  if (itmax <= 0) itmax = (int64_t)h->djt.nvar + h->djt.ncon;  // Krylov.jl's default: m + n
+  hipError_t e = cnl::launch_cgls(h->djt, S, d_r, d_lambda, d_Jxtr, ws, d_iters, atol, rtol, (int)itmax, ones_if_zero,
+                                  (int)h->batch, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("cgls: ") + hipGetErrorString(e));
+  return CNL_OK;
+}
+
+// the Jacobian values from the model's arrays (problem-major [batch][nnz(J_F)], [batch][nnz(J_c)]: what cnl_prepare_newton_system_dev takes)
+template <class T>
+static int jac_source(cnl_handle* h, int64_t nnzjF, int64_t nnzjc, const T* d_Jx, const T* d_Jcx, cnl::JacSrcT<T>* S) {
+  if (!h->jac_segments) return fail(CNL_ERR_STATE, "the J_F / J_c entries of this pattern are not one run of slots each (7-segment layout of src/CaNNOLeS.jl:256-315)");
+  if (nnzjF != h->jf_n || nnzjc != h->jc_n) return fail(CNL_ERR_DIM, "nnzjF / nnzjc do not match the pattern's Jacobian entries");
+  if (h->jf_n == 0) return fail(CNL_ERR_STATE, "the pattern has no J_F entries");
+  if (!d_Jx || (h->jc_n > 0 && !d_Jcx)) return fail(CNL_ERR_ARG, "null Jacobian values");
+  // (no J_c entries: the J_c source aliases the J_F one, nothing is read through it but the gather kernel's loads of absent entries)
+  if (h->jc_n > 0) *S = cnl::JacSrcT<T>{d_Jx - h->jf_lo, h->jf_n, d_Jcx - h->jc_lo, h->jc_n, (int)h->jf_lo, (int)h->jc_lo};
+  else *S = cnl::JacSrcT<T>{d_Jx - h->jf_lo, h->jf_n, d_Jx - h->jf_lo, h->jf_n, (int)h->jf_lo, (int)h->jf_lo};
+  return CNL_OK;
+}
+
+template <class T>
+static int residual_vectors_impl(cnl_handle* h, const cnl::JacSrcT<T>& S, const T* d_r, const T* d_lambda, const T* d_Fx,
+                                 const T* d_cx, T* d_rhs, T* d_norms, void* stream) {
+  if (!d_r || !d_Fx || !d_rhs || !d_norms) return fail(CNL_ERR_ARG, "null argument");
+  if (h->djt.ncon > 0 && (!d_lambda || !d_cx)) return fail(CNL_ERR_ARG, "lambda / c are required when ncon > 0");
+  HIPCHK(hipSetDevice(h->device));
+  hipError_t e = cnl::launch_residual_vectors(h->djt, S, d_r, d_lambda, d_Fx, d_cx, d_rhs, d_norms, (int)h->batch, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("residual_vectors: ") + hipGetErrorString(e));
+  return CNL_OK;
+}
+
+template <class T>
+static int trial_point_impl(cnl_handle* h, const T* d_x, const T* d_r, const T* d_lambda, const T* d_d, T max_dlambda, T* d_xt, T* d_rt,
+                            T* d_lambdat, T* d_dlambda, void* stream) {
+  if (h->djt.ncon > 0 && (!d_lambda || !d_lambdat || !d_dlambda)) return fail(CNL_ERR_ARG, "lambda vectors are required when ncon > 0");
+  HIPCHK(hipSetDevice(h->device));
+  hipError_t e = cnl::launch_trial_point(h->djt, d_x, d_r, d_lambda, d_d, max_dlambda, d_xt, d_rt, d_lambdat, d_dlambda, (int)h->batch,
+                                         (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("trial_point: ") + hipGetErrorString(e));
+  return CNL_OK;
+}
+
 extern "C" {
 
 static int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device);
@@ -1249,6 +1325,115 @@ static int create_tuned(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t
 }
 
 // device state for `batch` problems of an analysed pattern; takes ownership of `plan` (freed with the handle, or here on failure)
+// Rows f1 / f4 (both element types): the transposed-Jacobian lists of the pattern (DevJt), the column tiles of row f1 and the J_F / J_c
+// segments of `vals`.  Pattern-sized, shared by all problems of the handle.
+static int build_row_lists(cnl_handle* h, const cnl_plan* plan, const int64_t* rows1, const int64_t* cols1) {
+  const int64_t N = plan->N, nnz = plan->nnz, nvar = plan->nvar, nequ = plan->nequ, ncon = plan->ncon;
+  int rc = CNL_OK;
+  // transposed-Jacobian lists from the pattern: entries with column <= nvar < row, in COO order per column
+  std::vector<int32_t> ptrF(nvar + 1, 0), ptrC(nvar + 1, 0), slotF, idxF, slotC, idxC;
+  for (int64_t e = 0; e < nnz; e++) {
+    const int64_t r0 = rows1[e] - 1, c0 = cols1[e] - 1;
+    if (c0 < nvar && r0 >= nvar) (r0 < nvar + nequ ? ptrF : ptrC)[c0 + 1]++;
+  }
+  for (int64_t j2 = 0; j2 < nvar; j2++) { ptrF[j2 + 1] += ptrF[j2]; ptrC[j2 + 1] += ptrC[j2]; }
+  slotF.resize(ptrF[nvar]); idxF.resize(ptrF[nvar]); slotC.resize(ptrC[nvar]); idxC.resize(ptrC[nvar]);
+  std::vector<int32_t> fillF(ptrF.begin(), ptrF.end() - 1), fillC(ptrC.begin(), ptrC.end() - 1);
+  for (int64_t e = 0; e < nnz; e++) {
+    const int64_t r0 = rows1[e] - 1, c0 = cols1[e] - 1;
+    if (!(c0 < nvar && r0 >= nvar)) continue;
+    if (r0 < nvar + nequ) { const int32_t q = fillF[c0]++; slotF[q] = (int32_t)e; idxF[q] = (int32_t)(r0 - nvar); }
+    else { const int32_t q = fillC[c0]++; slotC[q] = (int32_t)e; idxC[q] = (int32_t)(r0 - nvar - nequ); }
+  }
+  cnl::DevJt& J = h->djt;
+  if ((rc = upload(h, ptrF, &J.ptrF))) return rc;
+  // the J_F / J_c entries as segments of `vals` (the reference's 7-segment layout, src/CaNNOLeS.jl:256-315): rows f1 / f4 can
+  // read them from the model's arrays instead (cnl_residual_vectors_jac_dev) when each kind occupies one run of slots
+  {
+    auto run = [](const std::vector<int32_t>& sl, int64_t& lo) {
+      if (sl.empty()) { lo = 0; return true; }
+      const auto mm = std::minmax_element(sl.begin(), sl.end());
+      lo = *mm.first;
+      return (int64_t)*mm.second - *mm.first + 1 == (int64_t)sl.size();
+    };
+    h->jac_segments = run(slotF, h->jf_lo) && run(slotC, h->jc_lo);
+    h->jf_n = (int64_t)slotF.size(); h->jc_n = (int64_t)slotC.size();
+  }
+  if ((rc = upload(h, slotF, &J.slotF))) return rc;
+  if ((rc = upload(h, idxF, &J.idxF))) return rc;
+  if ((rc = upload(h, ptrC, &J.ptrC))) return rc;
+  if ((rc = upload(h, slotC, &J.slotC))) return rc;
+  if ((rc = upload(h, idxC, &J.idxC))) return rc;
+  {
+    // J_c by rows (CGLS, row f4)
+    std::vector<int32_t> rptr(ncon + 1, 0), rslot(slotC.size()), rcol(slotC.size());
+    for (int64_t j2 = 0; j2 < nvar; j2++) for (int32_t q = ptrC[j2]; q < ptrC[j2 + 1]; q++) rptr[idxC[q] + 1]++;
+    for (int64_t k2 = 0; k2 < ncon; k2++) rptr[k2 + 1] += rptr[k2];
+    std::vector<int32_t> fillr(rptr.begin(), rptr.end() - 1);
+    for (int64_t j2 = 0; j2 < nvar; j2++)
+      for (int32_t q = ptrC[j2]; q < ptrC[j2 + 1]; q++) { const int32_t w = fillr[idxC[q]]++; rslot[w] = slotC[q]; rcol[w] = (int32_t)j2; }
+    if ((rc = upload(h, rptr, &J.rptrC))) return rc;
+    if ((rc = upload(h, rslot, &J.rslotC))) return rc;
+    if ((rc = upload(h, rcol, &J.rcolC))) return rc;
+  }
+  J.nvar = (int32_t)nvar; J.nequ = (int32_t)nequ; J.ncon = (int32_t)ncon; J.N = (int32_t)N; J.nnz = (int32_t)nnz;
+  // (round 5) column tiles of row f1 (kernels.h: DevJt::rv_*): the slot / index ranges of every tile of RVT_COLS columns
+  if (plan->opt.f1_tiles && nvar > 0) {
+    const int32_t nt = (int32_t)((nvar + cnl::RVT_COLS - 1) / cnl::RVT_COLS);
+    std::vector<int32_t> tiles((size_t)nt * cnl::RVT_TW, 0);
+    std::vector<uint32_t> table((size_t)nt * (cnl::RVT_KF + cnl::RVT_KC + 1) * cnl::RVT_COLS, 0u);
+    bool ok = true;
+    int32_t lds_max = 0;
+    for (int32_t t = 0; t < nt && ok; t++) {
+      const int64_t c0 = (int64_t)t * cnl::RVT_COLS, c1 = std::min<int64_t>(nvar, c0 + cnl::RVT_COLS);
+      int32_t fslo = INT32_MAX, fshi = -1, rlo = INT32_MAX, rhi = -1, cslo = INT32_MAX, cshi = -1, llo = INT32_MAX, lhi = -1;
+      for (int32_t q = ptrF[c0]; q < ptrF[c1]; q++) { fslo = std::min(fslo, slotF[q]); fshi = std::max(fshi, slotF[q]); rlo = std::min(rlo, idxF[q]); rhi = std::max(rhi, idxF[q]); }
+      for (int32_t q = ptrC[c0]; q < ptrC[c1]; q++) { cslo = std::min(cslo, slotC[q]); cshi = std::max(cshi, slotC[q]); llo = std::min(llo, idxC[q]); lhi = std::max(lhi, idxC[q]); }
+      int32_t* T = &tiles[(size_t)t * cnl::RVT_TW];
+      T[cnl::RVT_FSLO] = fshi < 0 ? 0 : fslo; T[cnl::RVT_WF] = fshi < 0 ? 0 : fshi - fslo + 1;
+      T[cnl::RVT_RLO] = rhi < 0 ? 0 : rlo;   T[cnl::RVT_WR] = rhi < 0 ? 0 : rhi - rlo + 1;
+      T[cnl::RVT_CSLO] = cshi < 0 ? 0 : cslo; T[cnl::RVT_WC] = cshi < 0 ? 0 : cshi - cslo + 1;
+      T[cnl::RVT_LLO] = lhi < 0 ? 0 : llo;   T[cnl::RVT_WL] = lhi < 0 ? 0 : lhi - llo + 1;
+      if (T[cnl::RVT_WF] > cnl::RVT_MAXF || T[cnl::RVT_WR] > cnl::RVT_MAXR || T[cnl::RVT_WC] > cnl::RVT_MAXC || T[cnl::RVT_WL] > cnl::RVT_MAXL) { ok = false; break; }
+      auto even = [](int32_t w) { return (w + 3) & ~1; };   // a window and the double its 16-byte alignment may put in front
+      lds_max = std::max(lds_max, even(T[cnl::RVT_WF]) + even(T[cnl::RVT_WR]) + even(T[cnl::RVT_WC]) + even(T[cnl::RVT_WL]));
+      uint32_t* tab = &table[(size_t)t * (cnl::RVT_KF + cnl::RVT_KC + 1) * cnl::RVT_COLS];
+      for (int64_t c = c0; c < c1; c++) {
+        const int32_t nF = ptrF[c + 1] - ptrF[c], nC = ptrC[c + 1] - ptrC[c];
+        if (nF > 255 || nC > 255) { ok = false; break; }
+        for (int32_t u = 0; u < std::min(nF, cnl::RVT_KF); u++)
+          tab[(size_t)u * cnl::RVT_COLS + (c - c0)] = (uint32_t)(slotF[ptrF[c] + u] - T[cnl::RVT_FSLO]) | (uint32_t)(idxF[ptrF[c] + u] - T[cnl::RVT_RLO]) << 16;
+        for (int32_t u = 0; u < std::min(nC, cnl::RVT_KC); u++)
+          tab[(size_t)(cnl::RVT_KF + u) * cnl::RVT_COLS + (c - c0)] = (uint32_t)(slotC[ptrC[c] + u] - T[cnl::RVT_CSLO]) | (uint32_t)(idxC[ptrC[c] + u] - T[cnl::RVT_LLO]) << 16;
+        tab[(size_t)(cnl::RVT_KF + cnl::RVT_KC) * cnl::RVT_COLS + (c - c0)] = (uint32_t)nF | (uint32_t)nC << 8;
+      }
+    }
+    if (ok) {
+      // the residual rows a tile has in LDS anyway are the rows whose primal entry F - r it writes: possible when the tiles' row
+      // ranges are ordered and cover 0 .. nequ without gaps (a band); otherwise tiles of rows of their own follow the column tiles
+      bool own = nequ > 0;
+      int32_t prev = 0;
+      for (int32_t t = 0; t < nt && own; t++) {
+        int32_t* T = &tiles[(size_t)t * cnl::RVT_TW];
+        const int32_t lo = T[cnl::RVT_RLO], hi = lo + T[cnl::RVT_WR];
+        const int32_t next_lo = t + 1 < nt ? tiles[(size_t)(t + 1) * cnl::RVT_TW + cnl::RVT_RLO] : (int32_t)nequ;
+        const int32_t own_hi = t + 1 < nt ? std::min(hi, std::max(next_lo, prev)) : (int32_t)nequ;
+        if (prev < lo || own_hi > hi || own_hi < prev) { own = false; break; }
+        T[cnl::RVT_OWNLO] = prev; T[cnl::RVT_OWNHI] = own_hi;
+        prev = own_hi;
+      }
+      if (own && prev != nequ) own = false;
+      if (!own) for (int32_t t = 0; t < nt; t++) tiles[(size_t)t * cnl::RVT_TW + cnl::RVT_OWNLO] = tiles[(size_t)t * cnl::RVT_TW + cnl::RVT_OWNHI] = 0;
+      if ((rc = upload(h, tiles, &J.rv_tiles))) return rc;
+      if ((rc = upload(h, table, &J.rv_table))) return rc;
+      J.rv_ntiles = nt; J.rv_lds_doubles = lds_max;
+      J.rv_primal_tiles = own ? 0 : (int32_t)((nequ + cnl::RVT_PROWS - 1) / cnl::RVT_PROWS);
+    }
+    if (std::getenv("CNL_VERBOSE")) fprintf(stderr, "[cnl] row f1: %s\n", ok ? "column tiles" : "gather kernel (a tile's windows exceed the limits)");
+  }
+  return CNL_OK;
+}
+
 static int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device) {
   const int64_t N = plan->N, nnz = plan->nnz, nvar = plan->nvar, nequ = plan->nequ, ncon = plan->ncon;
   int rc = CNL_OK;
@@ -1425,109 +1610,7 @@ static int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* ro
   if (hipStreamCreate(&h->stream) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipStreamCreate failed"));
   if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess)
     return bail(fail(CNL_ERR_HIP, "hipEventCreate failed"));
-  {
-    // transposed-Jacobian lists from the pattern: entries with column <= nvar < row, in COO order per column
-    std::vector<int32_t> ptrF(nvar + 1, 0), ptrC(nvar + 1, 0), slotF, idxF, slotC, idxC;
-    for (int64_t e = 0; e < nnz; e++) {
-      const int64_t r0 = rows1[e] - 1, c0 = cols1[e] - 1;
-      if (c0 < nvar && r0 >= nvar) (r0 < nvar + nequ ? ptrF : ptrC)[c0 + 1]++;
-    }
-    for (int64_t j2 = 0; j2 < nvar; j2++) { ptrF[j2 + 1] += ptrF[j2]; ptrC[j2 + 1] += ptrC[j2]; }
-    slotF.resize(ptrF[nvar]); idxF.resize(ptrF[nvar]); slotC.resize(ptrC[nvar]); idxC.resize(ptrC[nvar]);
-    std::vector<int32_t> fillF(ptrF.begin(), ptrF.end() - 1), fillC(ptrC.begin(), ptrC.end() - 1);
-    for (int64_t e = 0; e < nnz; e++) {
-      const int64_t r0 = rows1[e] - 1, c0 = cols1[e] - 1;
-      if (!(c0 < nvar && r0 >= nvar)) continue;
-      if (r0 < nvar + nequ) { const int32_t q = fillF[c0]++; slotF[q] = (int32_t)e; idxF[q] = (int32_t)(r0 - nvar); }
-      else { const int32_t q = fillC[c0]++; slotC[q] = (int32_t)e; idxC[q] = (int32_t)(r0 - nvar - nequ); }
-    }
-    cnl::DevJt& J = h->djt;
-    if ((rc = upload(h, ptrF, &J.ptrF))) return bail(rc);
-    // the J_F / J_c entries as segments of `vals` (the reference's 7-segment layout, src/CaNNOLeS.jl:256-315): rows f1 / f4 can
-    // read them from the model's arrays instead (cnl_residual_vectors_jac_dev) when each kind occupies one run of slots
-    {
-      auto run = [](const std::vector<int32_t>& sl, int64_t& lo) {
-        if (sl.empty()) { lo = 0; return true; }
-        const auto mm = std::minmax_element(sl.begin(), sl.end());
-        lo = *mm.first;
-        return (int64_t)*mm.second - *mm.first + 1 == (int64_t)sl.size();
-      };
-      h->jac_segments = run(slotF, h->jf_lo) && run(slotC, h->jc_lo);
-      h->jf_n = (int64_t)slotF.size(); h->jc_n = (int64_t)slotC.size();
-    }
-    if ((rc = upload(h, slotF, &J.slotF))) return bail(rc);
-    if ((rc = upload(h, idxF, &J.idxF))) return bail(rc);
-    if ((rc = upload(h, ptrC, &J.ptrC))) return bail(rc);
-    if ((rc = upload(h, slotC, &J.slotC))) return bail(rc);
-    if ((rc = upload(h, idxC, &J.idxC))) return bail(rc);
-    {
-      // J_c by rows (CGLS, row f4)
-      std::vector<int32_t> rptr(ncon + 1, 0), rslot(slotC.size()), rcol(slotC.size());
-      for (int64_t j2 = 0; j2 < nvar; j2++) for (int32_t q = ptrC[j2]; q < ptrC[j2 + 1]; q++) rptr[idxC[q] + 1]++;
-      for (int64_t k2 = 0; k2 < ncon; k2++) rptr[k2 + 1] += rptr[k2];
-      std::vector<int32_t> fillr(rptr.begin(), rptr.end() - 1);
-      for (int64_t j2 = 0; j2 < nvar; j2++)
-        for (int32_t q = ptrC[j2]; q < ptrC[j2 + 1]; q++) { const int32_t w = fillr[idxC[q]]++; rslot[w] = slotC[q]; rcol[w] = (int32_t)j2; }
-      if ((rc = upload(h, rptr, &J.rptrC))) return bail(rc);
-      if ((rc = upload(h, rslot, &J.rslotC))) return bail(rc);
-      if ((rc = upload(h, rcol, &J.rcolC))) return bail(rc);
-    }
-    J.nvar = (int32_t)nvar; J.nequ = (int32_t)nequ; J.ncon = (int32_t)ncon; J.N = (int32_t)N; J.nnz = (int32_t)nnz;
-    // (round 5) column tiles of row f1 (kernels.h: DevJt::rv_*): the slot / index ranges of every tile of RVT_COLS columns
-    if (plan->opt.f1_tiles && nvar > 0) {
-      const int32_t nt = (int32_t)((nvar + cnl::RVT_COLS - 1) / cnl::RVT_COLS);
-      std::vector<int32_t> tiles((size_t)nt * cnl::RVT_TW, 0);
-      std::vector<uint32_t> table((size_t)nt * (cnl::RVT_KF + cnl::RVT_KC + 1) * cnl::RVT_COLS, 0u);
-      bool ok = true;
-      int32_t lds_max = 0;
-      for (int32_t t = 0; t < nt && ok; t++) {
-        const int64_t c0 = (int64_t)t * cnl::RVT_COLS, c1 = std::min<int64_t>(nvar, c0 + cnl::RVT_COLS);
-        int32_t fslo = INT32_MAX, fshi = -1, rlo = INT32_MAX, rhi = -1, cslo = INT32_MAX, cshi = -1, llo = INT32_MAX, lhi = -1;
-        for (int32_t q = ptrF[c0]; q < ptrF[c1]; q++) { fslo = std::min(fslo, slotF[q]); fshi = std::max(fshi, slotF[q]); rlo = std::min(rlo, idxF[q]); rhi = std::max(rhi, idxF[q]); }
-        for (int32_t q = ptrC[c0]; q < ptrC[c1]; q++) { cslo = std::min(cslo, slotC[q]); cshi = std::max(cshi, slotC[q]); llo = std::min(llo, idxC[q]); lhi = std::max(lhi, idxC[q]); }
-        int32_t* T = &tiles[(size_t)t * cnl::RVT_TW];
-        T[cnl::RVT_FSLO] = fshi < 0 ? 0 : fslo; T[cnl::RVT_WF] = fshi < 0 ? 0 : fshi - fslo + 1;
-        T[cnl::RVT_RLO] = rhi < 0 ? 0 : rlo;   T[cnl::RVT_WR] = rhi < 0 ? 0 : rhi - rlo + 1;
-        T[cnl::RVT_CSLO] = cshi < 0 ? 0 : cslo; T[cnl::RVT_WC] = cshi < 0 ? 0 : cshi - cslo + 1;
-        T[cnl::RVT_LLO] = lhi < 0 ? 0 : llo;   T[cnl::RVT_WL] = lhi < 0 ? 0 : lhi - llo + 1;
-        if (T[cnl::RVT_WF] > cnl::RVT_MAXF || T[cnl::RVT_WR] > cnl::RVT_MAXR || T[cnl::RVT_WC] > cnl::RVT_MAXC || T[cnl::RVT_WL] > cnl::RVT_MAXL) { ok = false; break; }
-        auto even = [](int32_t w) { return (w + 3) & ~1; };   // a window and the double its 16-byte alignment may put in front
-        lds_max = std::max(lds_max, even(T[cnl::RVT_WF]) + even(T[cnl::RVT_WR]) + even(T[cnl::RVT_WC]) + even(T[cnl::RVT_WL]));
-        uint32_t* tab = &table[(size_t)t * (cnl::RVT_KF + cnl::RVT_KC + 1) * cnl::RVT_COLS];
-        for (int64_t c = c0; c < c1; c++) {
-          const int32_t nF = ptrF[c + 1] - ptrF[c], nC = ptrC[c + 1] - ptrC[c];
-          if (nF > 255 || nC > 255) { ok = false; break; }
-          for (int32_t u = 0; u < std::min(nF, cnl::RVT_KF); u++)
-            tab[(size_t)u * cnl::RVT_COLS + (c - c0)] = (uint32_t)(slotF[ptrF[c] + u] - T[cnl::RVT_FSLO]) | (uint32_t)(idxF[ptrF[c] + u] - T[cnl::RVT_RLO]) << 16;
-          for (int32_t u = 0; u < std::min(nC, cnl::RVT_KC); u++)
-            tab[(size_t)(cnl::RVT_KF + u) * cnl::RVT_COLS + (c - c0)] = (uint32_t)(slotC[ptrC[c] + u] - T[cnl::RVT_CSLO]) | (uint32_t)(idxC[ptrC[c] + u] - T[cnl::RVT_LLO]) << 16;
-          tab[(size_t)(cnl::RVT_KF + cnl::RVT_KC) * cnl::RVT_COLS + (c - c0)] = (uint32_t)nF | (uint32_t)nC << 8;
-        }
-      }
-      if (ok) {
-        // the residual rows a tile has in LDS anyway are the rows whose primal entry F - r it writes: possible when the tiles' row
-        // ranges are ordered and cover 0 .. nequ without gaps (a band); otherwise tiles of rows of their own follow the column tiles
-        bool own = nequ > 0;
-        int32_t prev = 0;
-        for (int32_t t = 0; t < nt && own; t++) {
-          int32_t* T = &tiles[(size_t)t * cnl::RVT_TW];
-          const int32_t lo = T[cnl::RVT_RLO], hi = lo + T[cnl::RVT_WR];
-          const int32_t next_lo = t + 1 < nt ? tiles[(size_t)(t + 1) * cnl::RVT_TW + cnl::RVT_RLO] : (int32_t)nequ;
-          const int32_t own_hi = t + 1 < nt ? std::min(hi, std::max(next_lo, prev)) : (int32_t)nequ;
-          if (prev < lo || own_hi > hi || own_hi < prev) { own = false; break; }
-          T[cnl::RVT_OWNLO] = prev; T[cnl::RVT_OWNHI] = own_hi;
-          prev = own_hi;
-        }
-        if (own && prev != nequ) own = false;
-        if (!own) for (int32_t t = 0; t < nt; t++) tiles[(size_t)t * cnl::RVT_TW + cnl::RVT_OWNLO] = tiles[(size_t)t * cnl::RVT_TW + cnl::RVT_OWNHI] = 0;
-        if ((rc = upload(h, tiles, &J.rv_tiles))) return bail(rc);
-        if ((rc = upload(h, table, &J.rv_table))) return bail(rc);
-        J.rv_ntiles = nt; J.rv_lds_doubles = lds_max;
-        J.rv_primal_tiles = own ? 0 : (int32_t)((nequ + cnl::RVT_PROWS - 1) / cnl::RVT_PROWS);
-      }
-      if (std::getenv("CNL_VERBOSE")) fprintf(stderr, "[cnl] row f1: %s\n", ok ? "column tiles" : "gather kernel (a tile's windows exceed the limits)");
-    }
-  }
+  if ((rc = build_row_lists(h, plan, rows1, cols1))) return bail(rc);
   *hout = h;
   return CNL_OK;
 }
@@ -1580,33 +1663,7 @@ int cnl_prepare_newton_system_dev(cnl_handle* h, int64_t nnzhF, int64_t nnzhc, i
                                   void* stream) {
   if (!h || !d_vals || !d_Jx) return fail(CNL_ERR_ARG, "null argument");
   CNL_NEED_F64(h);
-  const cnl::DevJt& J = h->djt;
-  if (nnzhF < 0 || nnzhc < 0 || nnzjF < 0 || nnzjc < 0 || nnzhF + nnzhc + nnzjF + nnzjc + J.nequ + J.ncon + J.nvar != J.nnz)
-    return fail(CNL_ERR_DIM, "segment sizes do not add up to nnz (7-segment layout of src/CaNNOLeS.jl:256-315)");
-  if (J.ncon > 0 && (!d_hc || !d_Jcx || !d_delta)) return fail(CNL_ERR_ARG, "hc / Jcx / delta are required when ncon > 0");
-  if (J.ncon == 0 && (nnzhc != 0 || nnzjc != 0)) return fail(CNL_ERR_DIM, "constraint segments must be empty when ncon == 0");
-  HIPCHK(hipSetDevice(h->device));
-  hipError_t e = cnl::launch_prepare((int)nnzhF, (int)nnzhc, (int)nnzjF, (int)nnzjc, J.nvar, J.nequ, J.ncon, d_hF, d_hc, d_Jx, d_Jcx,
-                                     d_delta, d_vals, (int)h->batch, h->layout & 1, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("prepare_newton_system: ") + hipGetErrorString(e));
-  return CNL_OK;
-}
-
-static int cgls_impl(cnl_handle* h, const cnl::JacSrc& S, const double* d_r, double* d_lambda, double* d_Jxtr, double atol,
-                     double rtol, int64_t itmax, int ones_if_zero, int32_t* d_iters, void* stream) {
-  if (h->djt.ncon == 0) return CNL_OK;  // nothing to estimate
-  if (!d_lambda) return fail(CNL_ERR_ARG, "null lambda");
-  if (h->djt.ncon > 1024) return fail(CNL_ERR_DIM, "cnl_cgls_multipliers_dev supports at most 1024 constraints");
-  HIPCHK(hipSetDevice(h->device));
-  if (!h->d_cgls_ws) {
-    int rc = dalloc(h, &h->d_cgls_ws, (size_t)h->batch * 2 * (size_t)h->djt.nvar);
-    if (rc) return rc;
-  }
-  if (itmax <= 0) itmax = (int64_t)h->djt.nvar + h->djt.ncon;  // Krylov.jl's default: m + n
-  hipError_t e = cnl::launch_cgls(h->djt, S, d_r, d_lambda, d_Jxtr, h->d_cgls_ws, d_iters, atol, rtol, (int)itmax, ones_if_zero,
-                                  (int)h->batch, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("cgls: ") + hipGetErrorString(e));
-  return CNL_OK;
+  return prepare_impl(h, nnzhF, nnzhc, nnzjF, nnzjc, d_hF, d_hc, d_Jx, d_Jcx, d_delta, d_vals, stream);
 }
 
 int cnl_cgls_multipliers_dev(cnl_handle* h, const double* d_vals, const double* d_r, double* d_lambda, double* d_Jxtr, double atol,
@@ -1617,18 +1674,6 @@ int cnl_cgls_multipliers_dev(cnl_handle* h, const double* d_vals, const double* 
   return cgls_impl(h, cnl::JacSrc{d_vals, h->djt.nnz, d_vals, h->djt.nnz, 0, 0}, d_r, d_lambda, d_Jxtr, atol, rtol, itmax, ones_if_zero, d_iters, stream);
 }
 
-// the Jacobian values from the model's arrays (problem-major [batch][nnz(J_F)], [batch][nnz(J_c)]: what cnl_prepare_newton_system_dev takes)
-static int jac_source(cnl_handle* h, int64_t nnzjF, int64_t nnzjc, const double* d_Jx, const double* d_Jcx, cnl::JacSrc* S) {
-  if (!h->jac_segments) return fail(CNL_ERR_STATE, "the J_F / J_c entries of this pattern are not one run of slots each (7-segment layout of src/CaNNOLeS.jl:256-315)");
-  if (nnzjF != h->jf_n || nnzjc != h->jc_n) return fail(CNL_ERR_DIM, "nnzjF / nnzjc do not match the pattern's Jacobian entries");
-  if (h->jf_n == 0) return fail(CNL_ERR_STATE, "the pattern has no J_F entries");
-  if (!d_Jx || (h->jc_n > 0 && !d_Jcx)) return fail(CNL_ERR_ARG, "null Jacobian values");
-  // (no J_c entries: the J_c source aliases the J_F one, nothing is read through it but the gather kernel's loads of absent entries)
-  if (h->jc_n > 0) *S = cnl::JacSrc{d_Jx - h->jf_lo, h->jf_n, d_Jcx - h->jc_lo, h->jc_n, (int)h->jf_lo, (int)h->jc_lo};
-  else *S = cnl::JacSrc{d_Jx - h->jf_lo, h->jf_n, d_Jx - h->jf_lo, h->jf_n, (int)h->jf_lo, (int)h->jf_lo};
-  return CNL_OK;
-}
-
 int cnl_cgls_multipliers_jac_dev(cnl_handle* h, int64_t nnzjF, int64_t nnzjc, const double* d_Jx, const double* d_Jcx, const double* d_r,
                                  double* d_lambda, double* d_Jxtr, double atol, double rtol, int64_t itmax, int ones_if_zero, int32_t* d_iters,
                                  void* stream) {
@@ -1637,16 +1682,6 @@ int cnl_cgls_multipliers_jac_dev(cnl_handle* h, int64_t nnzjF, int64_t nnzjc, co
   cnl::JacSrc S{};
   if (int rc = jac_source(h, nnzjF, nnzjc, d_Jx, d_Jcx, &S)) return rc;
   return cgls_impl(h, S, d_r, d_lambda, d_Jxtr, atol, rtol, itmax, ones_if_zero, d_iters, stream);
-}
-
-static int residual_vectors_impl(cnl_handle* h, const cnl::JacSrc& S, const double* d_r, const double* d_lambda, const double* d_Fx,
-                                 const double* d_cx, double* d_rhs, double* d_norms, void* stream) {
-  if (!d_r || !d_Fx || !d_rhs || !d_norms) return fail(CNL_ERR_ARG, "null argument");
-  if (h->djt.ncon > 0 && (!d_lambda || !d_cx)) return fail(CNL_ERR_ARG, "lambda / c are required when ncon > 0");
-  HIPCHK(hipSetDevice(h->device));
-  hipError_t e = cnl::launch_residual_vectors(h->djt, S, d_r, d_lambda, d_Fx, d_cx, d_rhs, d_norms, (int)h->batch, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("residual_vectors: ") + hipGetErrorString(e));
-  return CNL_OK;
 }
 
 int cnl_residual_vectors_dev(cnl_handle* h, const double* d_vals, const double* d_r, const double* d_lambda, const double* d_Fx,
@@ -1670,12 +1705,58 @@ int cnl_trial_point_dev(cnl_handle* h, const double* d_x, const double* d_r, con
                         double max_dlambda, double* d_xt, double* d_rt, double* d_lambdat, double* d_dlambda, void* stream) {
   if (!h || !d_x || !d_r || !d_d || !d_xt || !d_rt) return fail(CNL_ERR_ARG, "null argument");
   CNL_NEED_F64(h);
-  if (h->djt.ncon > 0 && (!d_lambda || !d_lambdat || !d_dlambda)) return fail(CNL_ERR_ARG, "lambda vectors are required when ncon > 0");
-  HIPCHK(hipSetDevice(h->device));
-  hipError_t e = cnl::launch_trial_point(h->djt, d_x, d_r, d_lambda, d_d, max_dlambda, d_xt, d_rt, d_lambdat, d_dlambda, (int)h->batch,
-                                         (hipStream_t)stream);
-  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("trial_point: ") + hipGetErrorString(e));
-  return CNL_OK;
+  return trial_point_impl(h, d_x, d_r, d_lambda, d_d, max_dlambda, d_xt, d_rt, d_lambdat, d_dlambda, stream);
+}
+
+// Float32 twins (include/cannoles_hip.h): the same rows on a Float32 handle's float arrays
+int cnl_prepare_newton_system_f32_dev(cnl_handle* h, int64_t nnzhF, int64_t nnzhc, int64_t nnzjF, int64_t nnzjc, const float* d_hF,
+                                      const float* d_hc, const float* d_Jx, const float* d_Jcx, const float* d_delta, float* d_vals,
+                                      void* stream) {
+  if (!h || !d_vals || !d_Jx) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F32(h);
+  return prepare_impl(h, nnzhF, nnzhc, nnzjF, nnzjc, d_hF, d_hc, d_Jx, d_Jcx, d_delta, d_vals, stream);
+}
+
+int cnl_residual_vectors_f32_dev(cnl_handle* h, const float* d_vals, const float* d_r, const float* d_lambda, const float* d_Fx,
+                                 const float* d_cx, float* d_rhs, float* d_norms, void* stream) {
+  if (!h || !d_vals) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F32(h);
+  if (h->layout & 1) return fail(CNL_ERR_STATE, "cnl_residual_vectors_f32_dev reads problem-major vals: on a handle with batch_layout = CNL_LAYOUT_INTERLEAVED use cnl_residual_vectors_jac_f32_dev");
+  return residual_vectors_impl(h, cnl::JacSrcF{d_vals, h->djt.nnz, d_vals, h->djt.nnz, 0, 0}, d_r, d_lambda, d_Fx, d_cx, d_rhs, d_norms, stream);
+}
+
+int cnl_residual_vectors_jac_f32_dev(cnl_handle* h, int64_t nnzjF, int64_t nnzjc, const float* d_Jx, const float* d_Jcx, const float* d_r,
+                                     const float* d_lambda, const float* d_Fx, const float* d_cx, float* d_rhs, float* d_norms, void* stream) {
+  if (!h) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F32(h);
+  cnl::JacSrcF S{};
+  if (int rc = jac_source(h, nnzjF, nnzjc, d_Jx, d_Jcx, &S)) return rc;
+  return residual_vectors_impl(h, S, d_r, d_lambda, d_Fx, d_cx, d_rhs, d_norms, stream);
+}
+
+int cnl_cgls_multipliers_f32_dev(cnl_handle* h, const float* d_vals, const float* d_r, float* d_lambda, float* d_Jxtr, float atol,
+                                 float rtol, int64_t itmax, int ones_if_zero, int32_t* d_iters, void* stream) {
+  if (!h || !d_vals || !d_r) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F32(h);
+  if (h->layout & 1) return fail(CNL_ERR_STATE, "cnl_cgls_multipliers_f32_dev reads problem-major vals: on a handle with batch_layout = CNL_LAYOUT_INTERLEAVED use cnl_cgls_multipliers_jac_f32_dev");
+  return cgls_impl(h, cnl::JacSrcF{d_vals, h->djt.nnz, d_vals, h->djt.nnz, 0, 0}, d_r, d_lambda, d_Jxtr, atol, rtol, itmax, ones_if_zero, d_iters, stream);
+}
+
+int cnl_cgls_multipliers_jac_f32_dev(cnl_handle* h, int64_t nnzjF, int64_t nnzjc, const float* d_Jx, const float* d_Jcx, const float* d_r,
+                                     float* d_lambda, float* d_Jxtr, float atol, float rtol, int64_t itmax, int ones_if_zero, int32_t* d_iters,
+                                     void* stream) {
+  if (!h || !d_r) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F32(h);
+  cnl::JacSrcF S{};
+  if (int rc = jac_source(h, nnzjF, nnzjc, d_Jx, d_Jcx, &S)) return rc;
+  return cgls_impl(h, S, d_r, d_lambda, d_Jxtr, atol, rtol, itmax, ones_if_zero, d_iters, stream);
+}
+
+int cnl_trial_point_f32_dev(cnl_handle* h, const float* d_x, const float* d_r, const float* d_lambda, const float* d_d,
+                            float max_dlambda, float* d_xt, float* d_rt, float* d_lambdat, float* d_dlambda, void* stream) {
+  if (!h || !d_x || !d_r || !d_d || !d_xt || !d_rt) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F32(h);
+  return trial_point_impl(h, d_x, d_r, d_lambda, d_d, max_dlambda, d_xt, d_rt, d_lambdat, d_dlambda, stream);
 }
 
 // ---- cnl_options.batch_layout = CNL_LAYOUT_INTERLEAVED: lengths and conversions (csrc/band.h: band_il_index) ----
@@ -1734,6 +1815,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   std::memset(cfg, 0, 8 * sizeof(int64_t));
   if (h->f32) {   // Float32 handle: the band kernels only
     cfg[5] = 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->layout << 25) | ((int64_t)1 << 27);
+    if (h->djt.rv_ntiles > 0) cfg[5] |= 128;
     return CNL_OK;
   }
   cfg[0] = h->cfg.tpp; cfg[1] = h->cfg.ppb; cfg[2] = (int64_t)h->cfg.lds_bytes; cfg[3] = h->cfg.lds_work;
@@ -2297,7 +2379,7 @@ void cnl_default_params_f32(float p[9]) {
   p[8] = (float)std::pow((double)eps, 0.25);
 }
 
-static int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, int64_t batch, int device) {
+static int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device) {
   cnl_handle* h = new cnl_handle();
   h->plan = plan; h->device = device; h->batch = batch; h->f32 = true;
   auto bail = [&](int code) { cnl_destroy(h); return code; };
@@ -2329,9 +2411,8 @@ static int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, int64_t batch
     if (plan->opt.batch_layout != CNL_LAYOUT_INTERLEAVED) return bail(fail(CNL_ERR_ARG, "cnl_options.batch_layout: unknown layout"));
     h->layout = 1 | (plan->opt.band_rhs_interleaved ? 2 : 0);
   }
-  // dimensions cnl_layout_len reads
-  h->djt.nvar = (int32_t)plan->nvar; h->djt.nequ = (int32_t)plan->nequ; h->djt.ncon = (int32_t)plan->ncon;
-  h->djt.N = (int32_t)plan->N; h->djt.nnz = (int32_t)plan->nnz;
+  // rows f1 / f2 / f4 and the trial point: the Float64 handles' row lists (they hold the dimensions cnl_layout_len reads)
+  if ((rc = build_row_lists(h, plan, rows1, cols1))) return bail(rc);
   if (hipStreamCreate(&h->stream) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipStreamCreate failed"));
   if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipEventCreate failed"));
   *hout = h;
@@ -2370,7 +2451,7 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
     return fail(CNL_ERR_ARG, "cnl_create_f32: the pattern is not served by the band kernels (build_band_plan: " + why +
                                  "); Float32 stays on the CPU backend for it");
   }
-  return create_f32_from_plan(hout, plan, batch, device);
+  return create_f32_from_plan(hout, plan, rows1, cols1, batch, device);
 }
 
 static int launch_f32(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {

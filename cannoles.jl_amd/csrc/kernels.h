@@ -81,11 +81,15 @@ struct DevJt {
 // where rows f1 / f4 read the Jacobian values: value of slot k (a position in `vals`) of problem b = vF[b * sF + k] for the J_F
 // entries, vC[b * sC + k] for the J_c entries.  From `vals` itself: {vals, nnz, vals, nnz}; from the model's arrays Jx / Jcx (what
 // prepare_newton_system! copies into those segments, src/CaNNOLeS.jl:968-974): {Jx - first J_F slot, nnz(J_F), Jcx - first J_c slot, nnz(J_c)}
-struct JacSrc {
-  const double* vF; long long sF;
-  const double* vC; long long sC;
+// (JacSrcF: the same for the float arrays of a Float32 handle)
+template <class T>
+struct JacSrcT {
+  const T* vF; long long sF;
+  const T* vC; long long sC;
   int safeF, safeC;   // a slot of each kind that exists in every problem (the gather kernel's loads of absent entries; vC is never null)
 };
+typedef JacSrcT<double> JacSrc;
+typedef JacSrcT<float> JacSrcF;
 constexpr int RVT_COLS = 256;   // columns per tile: one per thread of a 256-thread workgroup (two per thread: 190 registers)
 constexpr int RVT_KF = 6, RVT_KC = 2;   // entries of a column held in the table (the rest of a longer column: index lists)
 constexpr int RVT_MAXF = 2046, RVT_MAXR = 510, RVT_MAXC = 510, RVT_MAXL = 510;   // window limits (doubles): 4 + 1 + 1 + 1 chunks of 16 bytes per thread
@@ -200,6 +204,16 @@ hipError_t launch_residual_vectors(const DevJt& J, const JacSrc& S, const double
                                    const double* cx, double* rhs, double* norms, int batch, hipStream_t stream);
 hipError_t launch_trial_point(const DevJt& J, const double* x, const double* r, const double* lambda, const double* d,
                               double max_dlambda, double* xt, double* rt, double* lambdat, double* dlambda, int batch,
+                              hipStream_t stream);
+// float twins of the four launchers above (Float32 handles): the same kernels instantiated for float, the same grid rules
+hipError_t launch_prepare(int nnzhF, int nnzhc, int nnzjF, int nnzjc, int nvar, int nequ, int ncon, const float* hF, const float* hc,
+                          const float* Jx, const float* Jcx, const float* delta, float* vals, int batch, int interleaved, hipStream_t stream);
+hipError_t launch_cgls(const DevJt& J, const JacSrcF& S, const float* r, float* lambda, float* Jxtr, float* ws, int32_t* iters,
+                       float atol, float rtol, int itmax, int ones_if_zero, int batch, hipStream_t stream);
+hipError_t launch_residual_vectors(const DevJt& J, const JacSrcF& S, const float* r, const float* lambda, const float* Fx,
+                                   const float* cx, float* rhs, float* norms, int batch, hipStream_t stream);
+hipError_t launch_trial_point(const DevJt& J, const float* x, const float* r, const float* lambda, const float* d,
+                              float max_dlambda, float* xt, float* rt, float* lambdat, float* dlambda, int batch,
                               hipStream_t stream);
 hipError_t launch_fill_rho(double* vals, long long nnz, int nvar, const double* rho, const int* active, int batch, hipStream_t stream);
 hipError_t launch_lds_fill(int pattern, hipStream_t stream);   // debugging aid, see kernels_aux.hip

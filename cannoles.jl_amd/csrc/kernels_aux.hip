@@ -299,10 +299,17 @@ __global__ void __launch_bounds__(256) expand_kernel(const DevCond Cin, double* 
 // :953-967).  Both transposed products are accumulated per column in COO order, which is the order of the
 // reference's COO mul! (y[col[k]] += val[k] * x[row[k]] for k = 1, 2, ...), and subtracted afterwards as the
 // reference does: the results are bit-identical to that recipe.
-__device__ __forceinline__ void atomic_max_nonneg(double* addr, double v) {
-  // the bit patterns of non-negative doubles (and of NaN, which must win like in norm(., Inf)) are ordered as integers
-  atomicMax(reinterpret_cast<unsigned long long*>(addr), (unsigned long long)__double_as_longlong(v));
-}
+// T = float (Float32 handles): the same sums in float, the norms through 32-bit patterns (ordered like the non-negative floats, NaN
+// above infinity, as the 64-bit ones are for doubles)
+template <class T> struct NormBits;
+template <> struct NormBits<double> {
+  typedef unsigned long long U;
+  static __device__ __forceinline__ U of(double v) { return (unsigned long long)__double_as_longlong(v); }
+};
+template <> struct NormBits<float> {
+  typedef unsigned int U;
+  static __device__ __forceinline__ U of(float v) { return __float_as_uint(v); }
+};
 
 // One thread serves entry i of RPT problems: the index lists are read once and the launch has RPT times fewer
 // wavefronts (with one problem per thread the kernel is bound by the wavefront launch rate).
@@ -312,29 +319,31 @@ constexpr int RPT = 4;
 // the kernel spent its time on (2.4 ms at 8192 systems of cfg3's size, 0.34 of the HBM rate; a workgroup walking several groups of
 // problems, or the slots staged through LDS, changed nothing).  The sum itself stays sequential in COO order.
 constexpr int RV_KF = 6, RV_KC = 2;
-__global__ void __launch_bounds__(256) residual_vectors_kernel(const DevJt Jin, const JacSrc S,
-                                                               const double* __restrict__ r, const double* __restrict__ lambda,
-                                                               const double* __restrict__ Fx, const double* __restrict__ cx,
-                                                               double* __restrict__ rhs, double* __restrict__ norms, int batch) {
+template <class T>
+__global__ void __launch_bounds__(256) residual_vectors_kernel(const DevJt Jin, const JacSrcT<T> S,
+                                                               const T* __restrict__ r, const T* __restrict__ lambda,
+                                                               const T* __restrict__ Fx, const T* __restrict__ cx,
+                                                               T* __restrict__ rhs, T* __restrict__ norms, int batch) {
 #pragma clang fp contract(off)  // separately rounded multiply and add, as the reference's scalar loops
+  typedef typename NormBits<T>::U U;
   DevJt J = Jin;
   J.ptrF = as_global(Jin.ptrF); J.slotF = as_global(Jin.slotF); J.idxF = as_global(Jin.idxF);
   J.ptrC = as_global(Jin.ptrC); J.slotC = as_global(Jin.slotC); J.idxC = as_global(Jin.idxC);
-  const double* __restrict__ vF = S.vF; const double* __restrict__ vC = S.vC;
+  const T* __restrict__ vF = S.vF; const T* __restrict__ vC = S.vC;
   const int i = blockIdx.x * 256 + threadIdx.x;
   const int b0 = blockIdx.y * RPT;
   long long bq[RPT];
 #pragma unroll
   for (int q = 0; q < RPT; q++) bq[q] = b0 + q < batch ? b0 + q : batch - 1;
-  double out[RPT];
+  T out[RPT];
 #pragma unroll
-  for (int q = 0; q < RPT; q++) out[q] = 0.0;
+  for (int q = 0; q < RPT; q++) out[q] = T(0);
   const bool is_dual = i < J.nvar;
   if (i < J.N) {
     if (is_dual) {
-      double s1[RPT], s2[RPT];
+      T s1[RPT], s2[RPT];
 #pragma unroll
-      for (int q = 0; q < RPT; q++) s1[q] = s2[q] = 0.0;
+      for (int q = 0; q < RPT; q++) s1[q] = s2[q] = T(0);
       const int kf0 = J.ptrF[i], kf1 = J.ptrF[i + 1], kc0 = J.ptrC[i], kc1 = J.ptrC[i + 1];
       {
         // the first RV_KF entries: indices, then all operands, in flight together (entries past the end read a slot that exists —
@@ -342,7 +351,7 @@ __global__ void __launch_bounds__(256) residual_vectors_kernel(const DevJt Jin, 
         int sl[RV_KF], ix[RV_KF];
 #pragma unroll
         for (int u = 0; u < RV_KF; u++) { const bool on = kf0 + u < kf1; sl[u] = on ? J.slotF[kf0 + u] : S.safeF; ix[u] = on ? J.idxF[kf0 + u] : 0; }
-        double jv[RV_KF][RPT], xv[RV_KF][RPT];
+        T jv[RV_KF][RPT], xv[RV_KF][RPT];
 #pragma unroll
         for (int u = 0; u < RV_KF; u++)
 #pragma unroll
@@ -351,34 +360,34 @@ __global__ void __launch_bounds__(256) residual_vectors_kernel(const DevJt Jin, 
         for (int u = 0; u < RV_KF; u++)
           if (kf0 + u < kf1) {
 #pragma unroll
-            for (int q = 0; q < RPT; q++) { const double t_ = jv[u][q] * xv[u][q]; s1[q] = s1[q] + t_; }
+            for (int q = 0; q < RPT; q++) { const T t_ = jv[u][q] * xv[u][q]; s1[q] = s1[q] + t_; }
           }
       }
       for (int k = kf0 + RV_KF; k < kf1; k++) {
         const int sl = J.slotF[k], ix = J.idxF[k];
 #pragma unroll
-        for (int q = 0; q < RPT; q++) { const double t_ = vF[bq[q] * S.sF + sl] * r[bq[q] * J.nequ + ix]; s1[q] = s1[q] + t_; }
+        for (int q = 0; q < RPT; q++) { const T t_ = vF[bq[q] * S.sF + sl] * r[bq[q] * J.nequ + ix]; s1[q] = s1[q] + t_; }
       }
       {
         int sl[RV_KC], ix[RV_KC];
 #pragma unroll
         for (int u = 0; u < RV_KC; u++) { const bool on = kc0 + u < kc1; sl[u] = on ? J.slotC[kc0 + u] : S.safeC; ix[u] = on ? J.idxC[kc0 + u] : 0; }
-        double jv[RV_KC][RPT], xv[RV_KC][RPT];
+        T jv[RV_KC][RPT], xv[RV_KC][RPT];
 #pragma unroll
         for (int u = 0; u < RV_KC; u++)
 #pragma unroll
-          for (int q = 0; q < RPT; q++) { jv[u][q] = vC[bq[q] * S.sC + sl[u]]; xv[u][q] = kc0 + u < kc1 ? lambda[bq[q] * J.ncon + ix[u]] : 0.0; }
+          for (int q = 0; q < RPT; q++) { jv[u][q] = vC[bq[q] * S.sC + sl[u]]; xv[u][q] = kc0 + u < kc1 ? lambda[bq[q] * J.ncon + ix[u]] : T(0); }
 #pragma unroll
         for (int u = 0; u < RV_KC; u++)
           if (kc0 + u < kc1) {
 #pragma unroll
-            for (int q = 0; q < RPT; q++) { const double t_ = jv[u][q] * xv[u][q]; s2[q] = s2[q] + t_; }
+            for (int q = 0; q < RPT; q++) { const T t_ = jv[u][q] * xv[u][q]; s2[q] = s2[q] + t_; }
           }
       }
       for (int k = kc0 + RV_KC; k < kc1; k++) {
         const int sl = J.slotC[k], ix = J.idxC[k];
 #pragma unroll
-        for (int q = 0; q < RPT; q++) { const double t_ = vC[bq[q] * S.sC + sl] * lambda[bq[q] * J.ncon + ix]; s2[q] = s2[q] + t_; }
+        for (int q = 0; q < RPT; q++) { const T t_ = vC[bq[q] * S.sC + sl] * lambda[bq[q] * J.ncon + ix]; s2[q] = s2[q] + t_; }
       }
 #pragma unroll
       for (int q = 0; q < RPT; q++) out[q] = s1[q] - s2[q];
@@ -395,19 +404,19 @@ __global__ void __launch_bounds__(256) residual_vectors_kernel(const DevJt Jin, 
   }
   // infinity norms: a workgroup holds entries of one kind except the (at most two) that straddle a boundary.
   // NaN must propagate as in norm(., Inf): fmax drops it, so the integer images are compared (they are ordered like
-  // the non-negative doubles, NaN above infinity).
+  // the non-negative values, NaN above infinity).
 #pragma unroll
   for (int q = 0; q < RPT; q++) {
-    const double ad = (i < J.N && is_dual) ? fabs(out[q]) : 0.0, ap = (i < J.N && !is_dual) ? fabs(out[q]) : 0.0;
-    unsigned long long ud = (unsigned long long)__double_as_longlong(ad), up = (unsigned long long)__double_as_longlong(ap);
+    const T ad = (i < J.N && is_dual) ? fabs(out[q]) : T(0), ap = (i < J.N && !is_dual) ? fabs(out[q]) : T(0);
+    U ud = NormBits<T>::of(ad), up = NormBits<T>::of(ap);
     for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long od = __shfl_xor(ud, o, 64), op = __shfl_xor(up, o, 64);
+      const U od = __shfl_xor(ud, o, 64), op = __shfl_xor(up, o, 64);
       ud = od > ud ? od : ud;
       up = op > up ? op : up;
     }
     if ((threadIdx.x & 63) == 0 && b0 + q < batch) {
-      if (ud) atomicMax(reinterpret_cast<unsigned long long*>(norms + 2 * bq[q]), ud);
-      if (up) atomicMax(reinterpret_cast<unsigned long long*>(norms + 2 * bq[q] + 1), up);
+      if (ud) atomicMax(reinterpret_cast<U*>(norms + 2 * bq[q]), ud);
+      if (up) atomicMax(reinterpret_cast<U*>(norms + 2 * bq[q] + 1), up);
     }
   }
 }
@@ -426,13 +435,26 @@ __global__ void __launch_bounds__(256) residual_vectors_kernel(const DevJt Jin, 
 //
 // A window of w doubles at g (8-byte aligned) is loaded in 16-byte chunks from the 16-byte boundary at or below g: the chunk may
 // start one double before the window and end one double behind it — inside the 16-byte granule of a valid address, never across
-// a page — and element k of the window lands in lds[par + k], par = the parity of g.
+// a page — and element k of the window lands in lds[par + k], par = the parity of g.  For float (Float32 handles) a chunk is four
+// elements: par = the position of g mod 4, and a chunk may start up to three floats before the window.  Windows, LDS offsets and
+// the RVT_* limits count elements.
 typedef double rvt_d2 __attribute__((ext_vector_type(2)));   // (HIP's double2 class keeps arrays of it out of registers)
-template <int NCH, bool NT = false>
-__device__ __forceinline__ void rvt_issue(const double* __restrict__ g, int w, int t, rvt_d2 (&v)[NCH]) {
-  const int par = (int)((reinterpret_cast<uintptr_t>(g) >> 3) & 1);
-  const rvt_d2* g2 = reinterpret_cast<const rvt_d2*>(g - par);
-  const int nch = (w + par + 1) >> 1;
+typedef float rvt_f4 __attribute__((ext_vector_type(4)));
+template <class T> struct RvtChunk;
+template <> struct RvtChunk<double> { typedef rvt_d2 V; static constexpr int E = 2, LE = 1, SH = 3; };   // E = 1 << LE elements
+template <> struct RvtChunk<float> { typedef rvt_f4 V; static constexpr int E = 4, LE = 2, SH = 2; };
+// chunks per thread of a window of at most `maxw` elements (it may start E - 1 elements into its first chunk)
+template <class T>
+constexpr int rvt_nch(int maxw) { return (maxw + 2 * (RvtChunk<T>::E - 1) + 256 * RvtChunk<T>::E - 1) / (256 * RvtChunk<T>::E); }
+template <class T>
+__device__ __forceinline__ int rvt_par(const T* g) { return (int)((reinterpret_cast<uintptr_t>(g) >> RvtChunk<T>::SH) & (RvtChunk<T>::E - 1)); }
+template <int NCH, bool NT = false, class T>
+__device__ __forceinline__ void rvt_issue(const T* __restrict__ g, int w, int t, typename RvtChunk<T>::V (&v)[NCH]) {
+  typedef typename RvtChunk<T>::V V;
+  constexpr int E = RvtChunk<T>::E;
+  const int par = rvt_par(g);
+  const V* g2 = reinterpret_cast<const V*>(g - par);
+  const int nch = (w + par + E - 1) >> RvtChunk<T>::LE;
 #pragma unroll
   for (int u = 0; u < NCH; u++)
     if (u * 256 < nch) {                      // wavefront-uniform
@@ -440,10 +462,12 @@ __device__ __forceinline__ void rvt_issue(const double* __restrict__ g, int w, i
       if (i < nch) v[u] = NT ? __builtin_nontemporal_load(g2 + i) : g2[i];
     }
 }
-template <int NCH>
-__device__ __forceinline__ void rvt_commit(double* lds, int w, int par, int t, const rvt_d2 (&v)[NCH]) {
-  const int nch = (w + par + 1) >> 1;
-  rvt_d2* l2 = reinterpret_cast<rvt_d2*>(lds);
+template <int NCH, class T>
+__device__ __forceinline__ void rvt_commit(T* lds, int w, int par, int t, const typename RvtChunk<T>::V (&v)[NCH]) {
+  typedef typename RvtChunk<T>::V V;
+  constexpr int E = RvtChunk<T>::E;
+  const int nch = (w + par + E - 1) >> RvtChunk<T>::LE;
+  V* l2 = reinterpret_cast<V*>(lds);
 #pragma unroll
   for (int u = 0; u < NCH; u++)
     if (u * 256 < nch) {
@@ -451,19 +475,24 @@ __device__ __forceinline__ void rvt_commit(double* lds, int w, int par, int t, c
       if (i < nch) l2[i] = v[u];
     }
 }
-__device__ __forceinline__ int rvt_par(const double* g) { return (int)((reinterpret_cast<uintptr_t>(g) >> 3) & 1); }
-__device__ __forceinline__ int rvt_even(int w) { return (w + 3) & ~1; }
+// LDS elements of a window: room for the elements its first chunk holds in front of it, a whole number of chunks (double:
+// (w + 3) & ~1, float: (w + 7) & ~3 — never more bytes than the double window, so the Float64 LDS size serves float tiles)
+template <class T>
+__device__ __forceinline__ int rvt_even(int w) { return (w + 2 * RvtChunk<T>::E - 1) & ~(RvtChunk<T>::E - 1); }
 constexpr int RVT_NFX = (RVT_MAXR + 255) / 256;   // primal rows of a tile per thread
 
-__global__ void __launch_bounds__(256) residual_vectors_tiled_kernel(const DevJt Jin, const JacSrc S,
-                                                                     const double* __restrict__ r, const double* __restrict__ lambda,
-                                                                     const double* __restrict__ Fx, const double* __restrict__ cx,
-                                                                     double* __restrict__ rhs, double* __restrict__ norms, int batch, int pb) {
+template <class T>
+__global__ void __launch_bounds__(256) residual_vectors_tiled_kernel(const DevJt Jin, const JacSrcT<T> S,
+                                                                     const T* __restrict__ r, const T* __restrict__ lambda,
+                                                                     const T* __restrict__ Fx, const T* __restrict__ cx,
+                                                                     T* __restrict__ rhs, T* __restrict__ norms, int batch, int pb) {
 #pragma clang fp contract(off)
+  typedef typename NormBits<T>::U U;
+  typedef typename RvtChunk<T>::V V;
   constexpr bool NT = true;   // streamed once: non-temporal loads and stores (1.29 -> 1.27 ms)
   extern __shared__ rvt_d2 rvt_lds2[];
-  double* lds = reinterpret_cast<double*>(rvt_lds2);
-  __shared__ unsigned long long red[2];
+  T* lds = reinterpret_cast<T*>(rvt_lds2);
+  __shared__ U red[2];
   DevJt J = Jin;
   J.ptrF = as_global(Jin.ptrF); J.slotF = as_global(Jin.slotF); J.idxF = as_global(Jin.idxF);
   J.ptrC = as_global(Jin.ptrC); J.slotC = as_global(Jin.slotC); J.idxC = as_global(Jin.idxC);
@@ -471,31 +500,31 @@ __global__ void __launch_bounds__(256) residual_vectors_tiled_kernel(const DevJt
   const int t = threadIdx.x;
   const int tile = blockIdx.x;
   const int b_begin = blockIdx.y * pb, b_end = min(batch, b_begin + pb);
-  if (t < 2) red[t] = 0ull;
+  if (t < 2) red[t] = U(0);
   if (tile >= J.rv_ntiles) {
     // rows of the primal part that no column tile owns (the column tiles' row ranges are not an ordered cover of 0 .. nequ)
     const int i0 = (tile - J.rv_ntiles) * RVT_PROWS;
     for (int b = b_begin; b < b_end; b++) {
-      unsigned long long up = 0ull;
+      U up = U(0);
 #pragma unroll
       for (int k = 0; k < RVT_PROWS / 256; k++) {
         const int i = i0 + k * 256 + t;
         if (i < J.nequ) {
-          const double o = Fx[(long long)b * J.nequ + i] - r[(long long)b * J.nequ + i];
+          const T o = Fx[(long long)b * J.nequ + i] - r[(long long)b * J.nequ + i];
           rhs[(long long)b * J.N + J.nvar + i] = o;
-          const unsigned long long a = (unsigned long long)__double_as_longlong(fabs(o));
+          const U a = NormBits<T>::of(fabs(o));
           up = a > up ? a : up;
         }
       }
-      for (int o = 32; o > 0; o >>= 1) { const unsigned long long x = __shfl_xor(up, o, 64); up = x > up ? x : up; }
-      if ((t & 63) == 0 && up) atomicMax(reinterpret_cast<unsigned long long*>(norms + 2 * (long long)b + 1), up);
+      for (int o = 32; o > 0; o >>= 1) { const U x = __shfl_xor(up, o, 64); up = x > up ? x : up; }
+      if ((t & 63) == 0 && up) atomicMax(reinterpret_cast<U*>(norms + 2 * (long long)b + 1), up);
     }
     return;
   }
-  const int32_t* T = J.rv_tiles + tile * RVT_TW;
-  const int fslo = T[RVT_FSLO], wF = T[RVT_WF], rlo = T[RVT_RLO], wR = T[RVT_WR], cslo = T[RVT_CSLO], wC = T[RVT_WC], llo = T[RVT_LLO],
-            wL = T[RVT_WL], own_lo = T[RVT_OWNLO], own_hi = T[RVT_OWNHI];
-  const int oF = 0, oR = rvt_even(wF), oC = oR + rvt_even(wR), oL = oC + rvt_even(wC);
+  const int32_t* Tt = J.rv_tiles + tile * RVT_TW;
+  const int fslo = Tt[RVT_FSLO], wF = Tt[RVT_WF], rlo = Tt[RVT_RLO], wR = Tt[RVT_WR], cslo = Tt[RVT_CSLO], wC = Tt[RVT_WC], llo = Tt[RVT_LLO],
+            wL = Tt[RVT_WL], own_lo = Tt[RVT_OWNLO], own_hi = Tt[RVT_OWNHI];
+  const int oF = 0, oR = rvt_even<T>(wF), oC = oR + rvt_even<T>(wR), oL = oC + rvt_even<T>(wC);
   // the column(s) of this thread: window offsets of their first entries, counts
   constexpr int CPT = RVT_COLS / 256;
   uint32_t tab[CPT][RVT_KF + RVT_KC + 1];
@@ -504,17 +533,18 @@ __global__ void __launch_bounds__(256) residual_vectors_tiled_kernel(const DevJt
 #pragma unroll
     for (int w = 0; w < RVT_KF + RVT_KC + 1; w++)
       tab[j][w] = J.rv_table[((size_t)tile * (RVT_KF + RVT_KC + 1) + w) * RVT_COLS + j * 256 + t];
-  rvt_d2 pF[(RVT_MAXF + 2 + 511) / 512], pR[(RVT_MAXR + 2 + 511) / 512], pC[(RVT_MAXC + 2 + 511) / 512], pL[(RVT_MAXL + 2 + 511) / 512];
-  double pX[RVT_NFX];
+  constexpr int NF = rvt_nch<T>(RVT_MAXF), NR = rvt_nch<T>(RVT_MAXR), NC = rvt_nch<T>(RVT_MAXC), NL = rvt_nch<T>(RVT_MAXL);
+  V pF[NF], pR[NR], pC[NC], pL[NL];
+  T pX[RVT_NFX];
   // (a macro: a lambda that captures the register arrays by reference puts them in scratch memory)
 #define RVT_ISSUE(B_)                                                                              \
   {                                                                                                \
     const long long b_ = (B_);                                                                     \
-    rvt_issue<4, NT>(S.vF + b_ * S.sF + fslo, wF, t, pF);                                             \
-    rvt_issue<1, NT>(r + b_ * J.nequ + rlo, wR, t, pR);                                                  \
+    rvt_issue<NF, NT>(S.vF + b_ * S.sF + fslo, wF, t, pF);                                         \
+    rvt_issue<NR, NT>(r + b_ * J.nequ + rlo, wR, t, pR);                                           \
     if (wC) {                                                                                      \
-      rvt_issue<1, NT>(S.vC + b_ * S.sC + cslo, wC, t, pC);                                           \
-      rvt_issue<1, NT>(lambda + b_ * J.ncon + llo, wL, t, pL);                                           \
+      rvt_issue<NC, NT>(S.vC + b_ * S.sC + cslo, wC, t, pC);                                       \
+      rvt_issue<NL, NT>(lambda + b_ * J.ncon + llo, wL, t, pL);                                    \
     }                                                                                              \
     _Pragma("unroll") for (int k = 0; k < RVT_NFX; k++) {                                          \
       const int i = own_lo + k * 256 + t;                                                          \
@@ -528,45 +558,45 @@ __global__ void __launch_bounds__(256) residual_vectors_tiled_kernel(const DevJt
     rvt_commit(lds + oF, wF, parF, t, pF);
     rvt_commit(lds + oR, wR, parR, t, pR);
     if (wC) { rvt_commit(lds + oC, wC, parC, t, pC); rvt_commit(lds + oL, wL, parL, t, pL); }
-    double fx[RVT_NFX];
+    T fx[RVT_NFX];
 #pragma unroll
     for (int k = 0; k < RVT_NFX; k++) fx[k] = pX[k];
     __syncthreads();
     if (b + 1 < b_end) RVT_ISSUE(b + 1)
-    unsigned long long ud = 0ull, up = 0ull;
-    const double* lF = lds + oF + parF; const double* lR = lds + oR + parR; const double* lC = lds + oC + parC; const double* lL = lds + oL + parL;
+    U ud = U(0), up = U(0);
+    const T* lF = lds + oF + parF; const T* lR = lds + oR + parR; const T* lC = lds + oC + parC; const T* lL = lds + oL + parL;
 #pragma unroll
     for (int j = 0; j < CPT; j++) {
       const int col = tile * RVT_COLS + j * 256 + t;
       const int nF = (int)(tab[j][RVT_KF + RVT_KC] & 255u), nC = (int)((tab[j][RVT_KF + RVT_KC] >> 8) & 255u);
-      double jv[RVT_KF], xv[RVT_KF], cv[RVT_KC], lv[RVT_KC];
+      T jv[RVT_KF], xv[RVT_KF], cv[RVT_KC], lv[RVT_KC];
 #pragma unroll
       for (int u = 0; u < RVT_KF; u++) { jv[u] = lF[tab[j][u] & 0xffffu]; xv[u] = lR[tab[j][u] >> 16]; }
       if (wC) {
 #pragma unroll
         for (int u = 0; u < RVT_KC; u++) { cv[u] = lC[tab[j][RVT_KF + u] & 0xffffu]; lv[u] = lL[tab[j][RVT_KF + u] >> 16]; }
       }
-      double s1 = 0.0, s2 = 0.0;
+      T s1 = T(0), s2 = T(0);
 #pragma unroll
       for (int u = 0; u < RVT_KF; u++)
-        if (u < nF) { const double t_ = jv[u] * xv[u]; s1 = s1 + t_; }
+        if (u < nF) { const T t_ = jv[u] * xv[u]; s1 = s1 + t_; }
       if (nF > RVT_KF) {
         const int q0 = J.ptrF[col];
-        for (int k = RVT_KF; k < nF; k++) { const double t_ = S.vF[(long long)b * S.sF + J.slotF[q0 + k]] * r[(long long)b * J.nequ + J.idxF[q0 + k]]; s1 = s1 + t_; }
+        for (int k = RVT_KF; k < nF; k++) { const T t_ = S.vF[(long long)b * S.sF + J.slotF[q0 + k]] * r[(long long)b * J.nequ + J.idxF[q0 + k]]; s1 = s1 + t_; }
       }
       if (wC) {
 #pragma unroll
         for (int u = 0; u < RVT_KC; u++)
-          if (u < nC) { const double t_ = cv[u] * lv[u]; s2 = s2 + t_; }
+          if (u < nC) { const T t_ = cv[u] * lv[u]; s2 = s2 + t_; }
         if (nC > RVT_KC) {
           const int q0 = J.ptrC[col];
-          for (int k = RVT_KC; k < nC; k++) { const double t_ = S.vC[(long long)b * S.sC + J.slotC[q0 + k]] * lambda[(long long)b * J.ncon + J.idxC[q0 + k]]; s2 = s2 + t_; }
+          for (int k = RVT_KC; k < nC; k++) { const T t_ = S.vC[(long long)b * S.sC + J.slotC[q0 + k]] * lambda[(long long)b * J.ncon + J.idxC[q0 + k]]; s2 = s2 + t_; }
         }
       }
       if (col < J.nvar) {
-        const double o = s1 - s2;
+        const T o = s1 - s2;
         if (NT) __builtin_nontemporal_store(o, rhs + (long long)b * J.N + col); else rhs[(long long)b * J.N + col] = o;
-        const unsigned long long a = (unsigned long long)__double_as_longlong(fabs(o));
+        const U a = NormBits<T>::of(fabs(o));
         ud = a > ud ? a : ud;
       }
     }
@@ -574,21 +604,21 @@ __global__ void __launch_bounds__(256) residual_vectors_tiled_kernel(const DevJt
     for (int k = 0; k < RVT_NFX; k++) {
       const int i = own_lo + k * 256 + t;
       if (i < own_hi) {
-        const double o = fx[k] - lR[i - rlo];
+        const T o = fx[k] - lR[i - rlo];
         if (NT) __builtin_nontemporal_store(o, rhs + (long long)b * J.N + J.nvar + i); else rhs[(long long)b * J.N + J.nvar + i] = o;
-        const unsigned long long a = (unsigned long long)__double_as_longlong(fabs(o));
+        const U a = NormBits<T>::of(fabs(o));
         up = a > up ? a : up;
       }
     }
     if (tile == 0)
       for (int k = t; k < J.ncon; k += 256) {
-        const double o = cx[(long long)b * J.ncon + k];
+        const T o = cx[(long long)b * J.ncon + k];
         rhs[(long long)b * J.N + J.nvar + J.nequ + k] = o;
-        const unsigned long long a = (unsigned long long)__double_as_longlong(fabs(o));
+        const U a = NormBits<T>::of(fabs(o));
         up = a > up ? a : up;
       }
     for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long xd = __shfl_xor(ud, o, 64), xp = __shfl_xor(up, o, 64);
+      const U xd = __shfl_xor(ud, o, 64), xp = __shfl_xor(up, o, 64);
       ud = xd > ud ? xd : ud;
       up = xp > up ? xp : up;
     }
@@ -598,12 +628,13 @@ __global__ void __launch_bounds__(256) residual_vectors_tiled_kernel(const DevJt
     }
     __syncthreads();
     if (t < 2) {
-      const unsigned long long v = red[t];
-      if (v) atomicMax(reinterpret_cast<unsigned long long*>(norms + 2 * (long long)b + t), v);
-      red[t] = 0ull;
+      const U v = red[t];
+      if (v) atomicMax(reinterpret_cast<U*>(norms + 2 * (long long)b + t), v);
+      red[t] = U(0);
     }
   }
 }
+#undef RVT_ISSUE
 
 // Trial point of the extrapolation step, /root/reference/src/CaNNOLeS.jl:661-668 with dlambda = -d[n+m+1:N] (:654):
 //   xt = x + dx, rt = r + dr, dlambda capped at ||dlambda||_2 <= max_dlambda (1e4), lambdat = lambda + dlambda.
@@ -611,24 +642,27 @@ __global__ void __launch_bounds__(256) residual_vectors_tiled_kernel(const DevJt
 // non-temporal); the workgroups c = 0 also form dlambda (one workgroup per problem: the norm is summed in a fixed order).
 // (Round 5: one workgroup per problem walking all three vectors ran at 0.63 of the HBM rate.)
 constexpr int TP_UNROLL = 4;
-__global__ void __launch_bounds__(256) trial_point_kernel(const DevJt J, const double* __restrict__ x, const double* __restrict__ r,
-                                                          const double* __restrict__ lambda, const double* __restrict__ d,
-                                                          double max_dlambda, double* __restrict__ xt, double* __restrict__ rt,
-                                                          double* __restrict__ lambdat, double* __restrict__ dlambda, int batch) {
+// T = float: the adds in float; the squares of dlambda are summed in double and the norm is rounded to float once (the reference's
+// norm, BLAS snrm2, scales and does not overflow; squares of |dlambda| >= 1.8e19 would), the cap then applied in float.
+template <class T>
+__global__ void __launch_bounds__(256) trial_point_kernel(const DevJt J, const T* __restrict__ x, const T* __restrict__ r,
+                                                          const T* __restrict__ lambda, const T* __restrict__ d,
+                                                          T max_dlambda, T* __restrict__ xt, T* __restrict__ rt,
+                                                          T* __restrict__ lambdat, T* __restrict__ dlambda, int batch) {
   const int t = threadIdx.x;
   __shared__ double part[4];
   // one grid dimension (a second one ends at 65 535 problems): workgroup = (problem, chunk)
   const int nch_ = (J.nvar + J.nequ + 256 * TP_UNROLL - 1) / (256 * TP_UNROLL) > 0 ? (J.nvar + J.nequ + 256 * TP_UNROLL - 1) / (256 * TP_UNROLL) : 1;
   const long long b = blockIdx.x / nch_;
   const int chunk = blockIdx.x % nch_;
-  const double* db = d + b * J.N;
+  const T* db = d + b * J.N;
   {
     const int nxr = J.nvar + J.nequ;   // d[0 .. nvar + nequ) = [dx | dr] lines up with [x | r]
-    double a[TP_UNROLL], c[TP_UNROLL];
+    T a[TP_UNROLL], c[TP_UNROLL];
 #pragma unroll
     for (int j = 0; j < TP_UNROLL; j++) {
       const int k = chunk * (256 * TP_UNROLL) + j * 256 + t;
-      a[j] = 0.0; c[j] = 0.0;
+      a[j] = T(0); c[j] = T(0);
       if (k < nxr) {
         a[j] = __builtin_nontemporal_load(k < J.nvar ? x + b * J.nvar + k : r + b * J.nequ + (k - J.nvar));
         c[j] = __builtin_nontemporal_load(db + k);
@@ -646,9 +680,9 @@ __global__ void __launch_bounds__(256) trial_point_kernel(const DevJt J, const d
   for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
   if ((t & 63) == 0) part[t >> 6] = ss;
   __syncthreads();
-  const double nrm = sqrt(part[0] + part[1] + part[2] + part[3]);
+  const T nrm = (T)sqrt(part[0] + part[1] + part[2] + part[3]);
   for (int k = t; k < J.ncon; k += 256) {
-    double dl = -db[J.nvar + J.nequ + k];
+    T dl = -db[J.nvar + J.nequ + k];
     if (nrm > max_dlambda) dl = dl * max_dlambda / nrm;  // same operation order as dλ .= dλ .* Mdλ ./ norm(dλ)
     dlambda[b * J.ncon + k] = dl;
     lambdat[b * J.ncon + k] = lambda[b * J.ncon + k] + dl;
@@ -661,36 +695,38 @@ __global__ void __launch_bounds__(256) trial_point_kernel(const DevJt J, const d
 //   H_c <- -hc (:971-972), J_F <- Jx (:968-969), J_c <- Jcx (:973-974), -delta I <- -delta[b] (:975-976), rho I <- 0 (:978-979);
 //   the -I segment is never written (:306).
 constexpr int PREP_UNROLL = 4;
+// (U = PREP_UNROLL slots per thread for double, 2 * PREP_UNROLL for float: the same bytes per workgroup)
+template <class T, int U>
 __global__ void __launch_bounds__(256) prepare_kernel(int nnzhF, int nnzhc, int nnzjF, int nnzjc, int nvar, int nequ, int ncon,
-                                                      const double* __restrict__ hF, const double* __restrict__ hc,
-                                                      const double* __restrict__ Jx, const double* __restrict__ Jcx,
-                                                      const double* __restrict__ delta, double* __restrict__ vals, int batch) {
+                                                      const T* __restrict__ hF, const T* __restrict__ hc,
+                                                      const T* __restrict__ Jx, const T* __restrict__ Jcx,
+                                                      const T* __restrict__ delta, T* __restrict__ vals, int batch) {
   // four slots per thread, 256 apart (coalesced 8-byte accesses), every load issued before the first store; the data are touched
   // once: non-temporal.  (One slot per thread: 0.62 of the HBM rate on 1.68 MB per system, bound by the number of workgroups.)
   const int o1 = nnzhF, o2 = o1 + nnzhc, o3 = o2 + nnzjF, o4 = o3 + nnzjc, o5 = o4 + nequ, o6 = o5 + ncon, nnz = o6 + nvar;
   // one grid dimension (a second one ends at 65 535 problems): workgroup = (problem, chunk of 1 024 slots)
-  const int nch_ = (nnz + 256 * PREP_UNROLL - 1) / (256 * PREP_UNROLL);
+  const int nch_ = (nnz + 256 * U - 1) / (256 * U);
   const long long b = blockIdx.x / nch_;
   const int chunk = blockIdx.x % nch_;
-  double* v = vals + b * nnz;
-  double x[PREP_UNROLL];
-  bool st[PREP_UNROLL];
+  T* v = vals + b * nnz;
+  T x[U];
+  bool st[U];
   // one predicated load per slot — source, validity and sign are SELECTED (round 6: loads inside the branches of an if-chain were
   // waited for one by one)
 #pragma unroll
-  for (int j = 0; j < PREP_UNROLL; j++) {
-    const int k = chunk * (256 * PREP_UNROLL) + j * 256 + threadIdx.x;
+  for (int j = 0; j < U; j++) {
+    const int k = chunk * (256 * U) + j * 256 + threadIdx.x;
     const int seg = k < o1 ? 0 : k < o2 ? 1 : k < o3 ? 2 : k < o4 ? 3 : k < o5 ? 4 : k < o6 ? 5 : 6;
-    const double* sp = seg == 0 ? hF + b * nnzhF + k : seg == 1 ? hc + b * nnzhc + (k - o1) : seg == 2 ? Jx + b * nnzjF + (k - o2)
+    const T* sp = seg == 0 ? hF + b * nnzhF + k : seg == 1 ? hc + b * nnzhc + (k - o1) : seg == 2 ? Jx + b * nnzjF + (k - o2)
                      : seg == 3 ? Jcx + b * nnzjc + (k - o3) : delta + b;
     const bool rd = k < nnz && (seg == 0 ? hF != nullptr : seg == 1 || seg == 3 ? ncon > 0 : seg == 2 || seg == 5);
-    const double y = rd ? __builtin_nontemporal_load(sp) : 0.0;
+    const T y = rd ? __builtin_nontemporal_load(sp) : T(0);
     x[j] = (seg == 1 || seg == 5) ? -y : y;
     st[j] = rd || (seg == 6 && k < nnz);   // (rho I <- 0; -I and the segments without a source are left alone)
   }
 #pragma unroll
-  for (int j = 0; j < PREP_UNROLL; j++) {
-    const int k = chunk * (256 * PREP_UNROLL) + j * 256 + threadIdx.x;
+  for (int j = 0; j < U; j++) {
+    const int k = chunk * (256 * U) + j * 256 + threadIdx.x;
     if (st[j]) __builtin_nontemporal_store(x[j], v + k);
   }
 }
@@ -699,11 +735,13 @@ __global__ void __launch_bounds__(256) prepare_kernel(int nnzhF, int nnzhc, int 
 // A workgroup moves a tile of 32 problems x 128 elements through LDS: on the problem-major side a problem's 128 elements are 1 KB
 // contiguous, on the interleaved side the tile is 16 blocks x (32 problems x 8 doubles) = 32 KB contiguous.
 constexpr int IL_TILE = 128, IL_PITCH = IL_TILE + 8;   // (pitch: the 4 x 8 lanes of a half-wavefront hit 32 different bank pairs)
+constexpr int IL_TILE_F32 = 256;   // prepare_il_kernel<float>: 256 floats keep the problem-major runs at 1 KB
+template <int TILE = IL_TILE>
 __device__ __forceinline__ long long il_tile_dst(long long g, long long nb, int chunk, int idx, int& p, int& kk) {
   const int bl = idx >> 8, j = idx & 7;
   p = (idx >> 3) & 31;
   kk = bl * 8 + j;
-  return ((g * nb + (long long)chunk * (IL_TILE / 8) + bl) * BAND_IL_GROUP + p) * 8 + j;
+  return ((g * nb + (long long)chunk * (TILE / 8) + bl) * BAND_IL_GROUP + p) * 8 + j;
 }
 // (T = float for Float32 handles: the same blocks of eight elements)
 template <class T>
@@ -759,40 +797,45 @@ hipError_t launch_interleave_f32(const float* src, float* dst, int batch, long l
 }
 
 // prepare_newton_system! writing `vals` interleaved (the values and the "left alone" rules of prepare_kernel above, the tiles of
-// interleave_kernel): the model's arrays are read 1 KB per problem, `vals` is written 32 KB contiguous per workgroup
+// interleave_kernel): the model's arrays are read 1 KB per problem, `vals` is written 32 KB contiguous per workgroup.
+// TILE elements of a problem per workgroup, 256 / TILE problems per load round: 128 doubles, 256 floats (Float32 handles: the
+// problem-major runs stay 1 KB; IL_TILE_F32 below)
+template <class T, int TILE>
 __global__ void __launch_bounds__(256) prepare_il_kernel(int nnzhF, int nnzhc, int nnzjF, int nnzjc, int nvar, int nequ, int ncon,
-                                                         const double* __restrict__ hF, const double* __restrict__ hc,
-                                                         const double* __restrict__ Jx, const double* __restrict__ Jcx,
-                                                         const double* __restrict__ delta, double* __restrict__ vals, int batch) {
-  __shared__ double tile[BAND_IL_GROUP * IL_PITCH];
+                                                         const T* __restrict__ hF, const T* __restrict__ hc,
+                                                         const T* __restrict__ Jx, const T* __restrict__ Jcx,
+                                                         const T* __restrict__ delta, T* __restrict__ vals, int batch) {
+  constexpr int PITCH = TILE + 8, PPR = 256 / TILE, SH = TILE == 128 ? 7 : 8;   // problems per load round, log2(TILE)
+  static_assert(TILE == 128 || TILE == 256, "a load round covers whole problems");
+  __shared__ T tile[BAND_IL_GROUP * PITCH];
   const int o1 = nnzhF, o2 = o1 + nnzhc, o3 = o2 + nnzjF, o4 = o3 + nnzjc, o5 = o4 + nequ, o6 = o5 + ncon, nnz = o6 + nvar;
   const long long g = blockIdx.y, nb = band_il_blocks(nnz);
   const int chunk = blockIdx.x, t = threadIdx.x;
   // every load is issued before the first LDS store (one predicated load per element: source pointer, validity and sign are selected,
   // not branched on — loads inside the branches of prepare_kernel's chain were waited for one by one: 0.51 of the HBM rate against 0.65)
-  double x[BAND_IL_GROUP / 2];
-  const int kk0 = t & (IL_TILE - 1), k0 = chunk * IL_TILE + kk0;
+  T x[BAND_IL_GROUP / PPR];
+  const int kk0 = t & (TILE - 1), k0 = chunk * TILE + kk0;
   const int seg = k0 < o1 ? 0 : k0 < o2 ? 1 : k0 < o3 ? 2 : k0 < o4 ? 3 : k0 < o5 ? 4 : k0 < o6 ? 5 : 6;
-  const double* sbase = seg == 0 ? hF : seg == 1 ? hc : seg == 2 ? Jx : seg == 3 ? Jcx : delta;
+  const T* sbase = seg == 0 ? hF : seg == 1 ? hc : seg == 2 ? Jx : seg == 3 ? Jcx : delta;
   const long long sstr = seg == 0 ? nnzhF : seg == 1 ? nnzhc : seg == 2 ? nnzjF : seg == 3 ? nnzjc : 1;
   const int soff = seg == 0 ? k0 : seg == 1 ? k0 - o1 : seg == 2 ? k0 - o2 : seg == 3 ? k0 - o3 : 0;
   const bool rd = k0 < nnz && (seg == 0 ? hF != nullptr : seg == 1 || seg == 3 ? ncon > 0 : seg == 2 || seg == 5);
   const bool neg = seg == 1 || seg == 5;
 #pragma unroll
-  for (int it = 0; it < BAND_IL_GROUP / 2; it++) {
-    const long long b = g * BAND_IL_GROUP + 2 * it + (t >> 7);
-    x[it] = (rd && b < batch) ? __builtin_nontemporal_load(sbase + b * sstr + soff) : 0.0;
+  for (int it = 0; it < BAND_IL_GROUP / PPR; it++) {
+    const long long b = g * BAND_IL_GROUP + PPR * it + (t >> SH);
+    x[it] = (rd && b < batch) ? __builtin_nontemporal_load(sbase + b * sstr + soff) : T(0);
   }
 #pragma unroll
-  for (int it = 0; it < BAND_IL_GROUP / 2; it++) tile[(2 * it + (t >> 7)) * IL_PITCH + kk0] = neg ? -x[it] : x[it];
+  for (int it = 0; it < BAND_IL_GROUP / PPR; it++) tile[(PPR * it + (t >> SH)) * PITCH + kk0] = neg ? -x[it] : x[it];
   __syncthreads();
-  for (int i = 0; i < BAND_IL_GROUP * IL_TILE / 256; i++) {
+  for (int i = 0; i < BAND_IL_GROUP * TILE / 256; i++) {
     int p, kk;
-    const long long o = il_tile_dst(g, nb, chunk, i * 256 + t, p, kk);
-    const int k = chunk * IL_TILE + kk;
+    const long long o = il_tile_dst<TILE>(g, nb, chunk, i * 256 + t, p, kk);
+    const int k = chunk * TILE + kk;
     // the slots prepare_newton_system! leaves alone: H_F without a Hessian, the constraint segments without constraints, -I; and the pads
     const bool wr = k < o1 ? hF != nullptr : k < o2 ? ncon > 0 : k < o3 ? true : k < o4 ? ncon > 0 : k < o5 ? false : k < nnz;
-    if (wr && g * BAND_IL_GROUP + p < batch) __builtin_nontemporal_store(tile[p * IL_PITCH + kk], vals + o);
+    if (wr && g * BAND_IL_GROUP + p < batch) __builtin_nontemporal_store(tile[p * PITCH + kk], vals + o);
   }
 }
 
@@ -804,45 +847,49 @@ __global__ void __launch_bounds__(256) prepare_il_kernel(int nnzhF, int nnzhc, i
 // with A = Jc' (nvar x ncon) and b = Jx' r).  One workgroup per problem; the ncon-vectors live in LDS, the two
 // nvar-vectors (residual, q) in a global workspace; reductions in a fixed order (deterministic).
 constexpr int CGLS_PMAX = 1024;
-__device__ __forceinline__ double block_sum(double v, double* red) {
+template <class T>
+__device__ __forceinline__ T block_sum(T v, T* red) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return red[0] + red[1] + red[2] + red[3];
 }
-__global__ void __launch_bounds__(256) cgls_kernel(const DevJt Jin, const JacSrc S, const double* __restrict__ r,
-                                                   double* __restrict__ lambda, double* __restrict__ Jxtr, double* __restrict__ ws,
-                                                   int* __restrict__ iters, double atol, double rtol, int itmax, int ones_if_zero) {
+// T = float (Float32 handles): Krylov.jl's recurrence with T = Float32 — every dot product, axpy and reduction in float, in the
+// same fixed order; the workspace is float
+template <class T>
+__global__ void __launch_bounds__(256) cgls_kernel(const DevJt Jin, const JacSrcT<T> S, const T* __restrict__ r,
+                                                   T* __restrict__ lambda, T* __restrict__ Jxtr, T* __restrict__ ws,
+                                                   int* __restrict__ iters, T atol, T rtol, int itmax, int ones_if_zero) {
   DevJt J = Jin;
   J.ptrF = as_global(Jin.ptrF); J.slotF = as_global(Jin.slotF); J.idxF = as_global(Jin.idxF);
   J.ptrC = as_global(Jin.ptrC); J.slotC = as_global(Jin.slotC); J.idxC = as_global(Jin.idxC);
   J.rptrC = as_global(Jin.rptrC); J.rslotC = as_global(Jin.rslotC); J.rcolC = as_global(Jin.rcolC);
-  __shared__ double x[CGLS_PMAX], sv[CGLS_PMAX], pv[CGLS_PMAX];
-  __shared__ double red[4];
+  __shared__ T x[CGLS_PMAX], sv[CGLS_PMAX], pv[CGLS_PMAX];
+  __shared__ T red[4];
   const long long b = blockIdx.x;
   const int t = threadIdx.x, n = J.nvar, p = J.ncon;
-  const double* __restrict__ vF = S.vF + b * S.sF;
-  const double* __restrict__ vC = S.vC + b * S.sC;
-  const double* rb = r + b * J.nequ;
-  double* res = ws + b * 2 * n;  // residual of the least-squares problem
-  double* q = res + n;
+  const T* __restrict__ vF = S.vF + b * S.sF;
+  const T* __restrict__ vC = S.vC + b * S.sC;
+  const T* rb = r + b * J.nequ;
+  T* res = ws + b * 2 * n;  // residual of the least-squares problem
+  T* q = res + n;
   // b = Jx' r  (mul!(Jxtr, Jx', r), per-column COO-order sums as in residual_vectors_kernel)
   {
 #pragma clang fp contract(off)  // separately rounded multiply and add, as the reference's scalar loop
     for (int j = t; j < n; j += 256) {
-      double s1 = 0.0;
-      for (int k = J.ptrF[j]; k < J.ptrF[j + 1]; k++) { const double t_ = vF[J.slotF[k]] * rb[J.idxF[k]]; s1 = s1 + t_; }
+      T s1 = T(0);
+      for (int k = J.ptrF[j]; k < J.ptrF[j + 1]; k++) { const T t_ = vF[J.slotF[k]] * rb[J.idxF[k]]; s1 = s1 + t_; }
       res[j] = s1;
       if (Jxtr) Jxtr[b * n + j] = s1;
     }
   }
-  for (int k = t; k < p; k += 256) x[k] = 0.0;
+  for (int k = t; k < p; k += 256) x[k] = T(0);
   __syncthreads();
   // s = A' res = Jc res: one wavefront per constraint row
   auto at_res = [&]() {
     for (int k = t >> 6; k < p; k += 4) {
-      double acc = 0.0;
+      T acc = T(0);
       for (int e = J.rptrC[k] + (t & 63); e < J.rptrC[k + 1]; e += 64) acc += vC[J.rslotC[e]] * res[J.rcolC[e]];
       for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
       if ((t & 63) == 0) sv[k] = acc;
@@ -852,108 +899,151 @@ __global__ void __launch_bounds__(256) cgls_kernel(const DevJt Jin, const JacSrc
   at_res();
   for (int k = t; k < p; k += 256) pv[k] = sv[k];
   __syncthreads();
-  double part = 0.0;
+  T part = T(0);
   for (int k = t; k < p; k += 256) part += sv[k] * sv[k];
-  double gamma = block_sum(part, red);
-  const double eps = atol + rtol * sqrt(gamma);
+  T gamma = block_sum(part, red);
+  const T eps = atol + rtol * sqrt(gamma);
   int it = 0;
   while (it < itmax && sqrt(gamma) > eps) {
     // q = A p = Jc' p: thread per variable
-    part = 0.0;
+    part = T(0);
     for (int j = t; j < n; j += 256) {
-      double s2 = 0.0;
+      T s2 = T(0);
       for (int k = J.ptrC[j]; k < J.ptrC[j + 1]; k++) s2 += vC[J.slotC[k]] * pv[J.idxC[k]];
       q[j] = s2;
       part += s2 * s2;
     }
-    const double delta = block_sum(part, red);
-    if (delta == 0.0) break;
-    const double alpha = gamma / delta;
+    const T delta = block_sum(part, red);
+    if (delta == T(0)) break;
+    const T alpha = gamma / delta;
     for (int k = t; k < p; k += 256) x[k] += alpha * pv[k];
     for (int j = t; j < n; j += 256) res[j] -= alpha * q[j];
     __syncthreads();
     at_res();
-    part = 0.0;
+    part = T(0);
     for (int k = t; k < p; k += 256) part += sv[k] * sv[k];
-    const double gnext = block_sum(part, red);
-    const double beta = gnext / gamma;
+    const T gnext = block_sum(part, red);
+    const T beta = gnext / gamma;
     for (int k = t; k < p; k += 256) pv[k] = sv[k] + beta * pv[k];
     __syncthreads();
     gamma = gnext;
     it++;
   }
   // if norm(lambda) == 0: lambda .= 1   (src/CaNNOLeS.jl:515-517)
-  part = 0.0;
+  part = T(0);
   for (int k = t; k < p; k += 256) part += x[k] * x[k];
-  const double xn = block_sum(part, red);
-  for (int k = t; k < p; k += 256) lambda[b * p + k] = (ones_if_zero && xn == 0.0) ? 1.0 : x[k];
+  const T xn = block_sum(part, red);
+  for (int k = t; k < p; k += 256) lambda[b * p + k] = (ones_if_zero && xn == T(0)) ? T(1) : x[k];
   if (t == 0 && iters) iters[b] = it;
 }
 
+template <class T>
+static hipError_t launch_cgls_t(const DevJt& J, const JacSrcT<T>& S, const T* r, T* lambda, T* Jxtr, T* ws, int32_t* iters,
+                                T atol, T rtol, int itmax, int ones_if_zero, int batch, hipStream_t stream) {
+  if (J.ncon > CGLS_PMAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cgls_kernel<T>, dim3(batch), dim3(256), 0, stream, J, S, r, lambda, Jxtr, ws, iters, atol, rtol, itmax, ones_if_zero);
+  return hipGetLastError();
+}
 hipError_t launch_cgls(const DevJt& J, const JacSrc& S, const double* r, double* lambda, double* Jxtr, double* ws, int32_t* iters,
                        double atol, double rtol, int itmax, int ones_if_zero, int batch, hipStream_t stream) {
-  if (J.ncon > CGLS_PMAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(cgls_kernel, dim3(batch), dim3(256), 0, stream, J, S, r, lambda, Jxtr, ws, iters, atol, rtol, itmax, ones_if_zero);
-  return hipGetLastError();
+  return launch_cgls_t(J, S, r, lambda, Jxtr, ws, iters, atol, rtol, itmax, ones_if_zero, batch, stream);
+}
+hipError_t launch_cgls(const DevJt& J, const JacSrcF& S, const float* r, float* lambda, float* Jxtr, float* ws, int32_t* iters,
+                       float atol, float rtol, int itmax, int ones_if_zero, int batch, hipStream_t stream) {
+  return launch_cgls_t(J, S, r, lambda, Jxtr, ws, iters, atol, rtol, itmax, ones_if_zero, batch, stream);
 }
 
 // one linear grid dimension (problem, chunk): the product must fit a 31-bit grid (a larger one would truncate silently)
 static inline bool linear_grid_ok(long long nch, long long batch) { return nch > 0 && batch > 0 && nch * batch <= 0x7fffffffLL; }
 
-hipError_t launch_prepare(int nnzhF, int nnzhc, int nnzjF, int nnzjc, int nvar, int nequ, int ncon, const double* hF, const double* hc,
-                          const double* Jx, const double* Jcx, const double* delta, double* vals, int batch, int interleaved, hipStream_t stream) {
+// the interleaved prepare's tile: 128 doubles or 256 floats, 1 KB runs on the problem-major side either way
+template <class T> constexpr int prep_il_tile() { return sizeof(T) == 8 ? IL_TILE : IL_TILE_F32; }
+template <class T>
+static hipError_t launch_prepare_t(int nnzhF, int nnzhc, int nnzjF, int nnzjc, int nvar, int nequ, int ncon, const T* hF, const T* hc,
+                                   const T* Jx, const T* Jcx, const T* delta, T* vals, int batch, int interleaved, hipStream_t stream) {
   const int nnz = nnzhF + nnzhc + nnzjF + nnzjc + nequ + ncon + nvar;
   if (interleaved) {
-    const long long groups = (batch + BAND_IL_GROUP - 1) / BAND_IL_GROUP, chunks = (nnz + IL_TILE - 1) / IL_TILE;
+    constexpr int TILE = prep_il_tile<T>();
+    const long long groups = (batch + BAND_IL_GROUP - 1) / BAND_IL_GROUP, chunks = (nnz + TILE - 1) / TILE;
     if (batch <= 0 || nnz <= 0 || groups > 65535) return hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL(prepare_il_kernel, dim3((unsigned)chunks, (unsigned)groups), dim3(256), 0, stream, nnzhF, nnzhc, nnzjF, nnzjc, nvar, nequ,
+    hipLaunchKernelGGL((prepare_il_kernel<T, TILE>), dim3((unsigned)chunks, (unsigned)groups), dim3(256), 0, stream, nnzhF, nnzhc, nnzjF, nnzjc, nvar, nequ,
                        ncon, hF, hc, Jx, Jcx, delta, vals, batch);
     return hipGetLastError();
   }
-  const long long nch = (nnz + 256 * PREP_UNROLL - 1) / (256 * PREP_UNROLL);   // (0 when nnz == 0: the kernel divides by it)
+  constexpr int U = sizeof(T) == 8 ? PREP_UNROLL : 2 * PREP_UNROLL;
+  const long long nch = (nnz + 256 * U - 1) / (256 * U);   // (0 when nnz == 0: the kernel divides by it)
   if (!linear_grid_ok(nch, batch)) return hipErrorInvalidConfiguration;
-  hipLaunchKernelGGL(prepare_kernel, dim3((unsigned)(nch * batch)), dim3(256), 0, stream, nnzhF, nnzhc, nnzjF, nnzjc, nvar, nequ, ncon,
+  hipLaunchKernelGGL((prepare_kernel<T, U>), dim3((unsigned)(nch * batch)), dim3(256), 0, stream, nnzhF, nnzhc, nnzjF, nnzjc, nvar, nequ, ncon,
                      hF, hc, Jx, Jcx, delta, vals, batch);
   return hipGetLastError();
 }
+hipError_t launch_prepare(int nnzhF, int nnzhc, int nnzjF, int nnzjc, int nvar, int nequ, int ncon, const double* hF, const double* hc,
+                          const double* Jx, const double* Jcx, const double* delta, double* vals, int batch, int interleaved, hipStream_t stream) {
+  return launch_prepare_t(nnzhF, nnzhc, nnzjF, nnzjc, nvar, nequ, ncon, hF, hc, Jx, Jcx, delta, vals, batch, interleaved, stream);
+}
+hipError_t launch_prepare(int nnzhF, int nnzhc, int nnzjF, int nnzjc, int nvar, int nequ, int ncon, const float* hF, const float* hc,
+                          const float* Jx, const float* Jcx, const float* delta, float* vals, int batch, int interleaved, hipStream_t stream) {
+  return launch_prepare_t(nnzhF, nnzhc, nnzjF, nnzjc, nvar, nequ, ncon, hF, hc, Jx, Jcx, delta, vals, batch, interleaved, stream);
+}
 
-hipError_t launch_residual_vectors(const DevJt& J, const JacSrc& S, const double* r, const double* lambda, const double* Fx,
-                                   const double* cx, double* rhs, double* norms, int batch, hipStream_t stream) {
-  hipError_t e = hipMemsetAsync(norms, 0, sizeof(double) * 2 * (size_t)batch, stream);
+template <class T>
+static hipError_t launch_residual_vectors_t(const DevJt& J, const JacSrcT<T>& S, const T* r, const T* lambda, const T* Fx,
+                                            const T* cx, T* rhs, T* norms, int batch, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(norms, 0, sizeof(T) * 2 * (size_t)batch, stream);
   if (e != hipSuccess) return e;
   // problems per workgroup of the tiled kernel: the table of a tile is read once per workgroup, and a workgroup streams one problem
   // ahead (measured at 8192 systems of cfg3's pattern: 1 -> 1.40 ms, 2 -> 1.30, 4 -> 1.27, 16 -> 1.32)
-  const int pb = J.rv_ntiles > 0 ? (batch >= 512 ? 4 : batch >= 64 ? 2 : 1) : RPT;
+  // (float: 8 — a tile's table is read for twice the problems, the windows of a problem being half the bytes)
+  const int pb = J.rv_ntiles > 0 ? (batch >= 512 ? (sizeof(T) == 4 ? 8 : 4) : batch >= 64 ? 2 : 1) : RPT;
   // the second grid dimension holds at most 65535 groups of problems: larger batches go in slices of that many groups, every
   // per-problem pointer advanced to the slice's first problem (row strides: the Jacobian sources', nequ, ncon, N, 2)
   const long long slice = 65535LL * pb;
   for (long long b0 = 0; b0 < batch; b0 += slice) {
     const int nb = (int)std::min<long long>(slice, batch - b0);
-    const JacSrc v_{S.vF + b0 * S.sF, S.sF, S.vC + b0 * S.sC, S.sC, S.safeF, S.safeC};
-    const double* r_ = r + b0 * J.nequ;
-    const double* l_ = lambda ? lambda + b0 * J.ncon : nullptr;
-    const double* f_ = Fx + b0 * J.nequ;
-    const double* c_ = cx ? cx + b0 * J.ncon : nullptr;
-    double* o_ = rhs + b0 * J.N;
-    double* n_ = norms + 2 * b0;
+    const JacSrcT<T> v_{S.vF + b0 * S.sF, S.sF, S.vC + b0 * S.sC, S.sC, S.safeF, S.safeC};
+    const T* r_ = r + b0 * J.nequ;
+    const T* l_ = lambda ? lambda + b0 * J.ncon : nullptr;
+    const T* f_ = Fx + b0 * J.nequ;
+    const T* c_ = cx ? cx + b0 * J.ncon : nullptr;
+    T* o_ = rhs + b0 * J.N;
+    T* n_ = norms + 2 * b0;
+    // (a float tile's windows take at most the bytes of the double tile's: rvt_even)
     if (J.rv_ntiles > 0)
-      hipLaunchKernelGGL(residual_vectors_tiled_kernel, dim3(J.rv_ntiles + J.rv_primal_tiles, (nb + pb - 1) / pb), dim3(256),
+      hipLaunchKernelGGL(residual_vectors_tiled_kernel<T>, dim3(J.rv_ntiles + J.rv_primal_tiles, (nb + pb - 1) / pb), dim3(256),
                          (size_t)J.rv_lds_doubles * sizeof(double), stream, J, v_, r_, l_, f_, c_, o_, n_, nb, pb);
     else
-      hipLaunchKernelGGL(residual_vectors_kernel, dim3((J.N + 255) / 256, (nb + RPT - 1) / RPT), dim3(256), 0, stream, J, v_, r_, l_, f_, c_, o_, n_, nb);
+      hipLaunchKernelGGL(residual_vectors_kernel<T>, dim3((J.N + 255) / 256, (nb + RPT - 1) / RPT), dim3(256), 0, stream, J, v_, r_, l_, f_, c_, o_, n_, nb);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   return hipSuccess;
 }
+hipError_t launch_residual_vectors(const DevJt& J, const JacSrc& S, const double* r, const double* lambda, const double* Fx,
+                                   const double* cx, double* rhs, double* norms, int batch, hipStream_t stream) {
+  return launch_residual_vectors_t(J, S, r, lambda, Fx, cx, rhs, norms, batch, stream);
+}
+hipError_t launch_residual_vectors(const DevJt& J, const JacSrcF& S, const float* r, const float* lambda, const float* Fx,
+                                   const float* cx, float* rhs, float* norms, int batch, hipStream_t stream) {
+  return launch_residual_vectors_t(J, S, r, lambda, Fx, cx, rhs, norms, batch, stream);
+}
 
+template <class T>
+static hipError_t launch_trial_point_t(const DevJt& J, const T* x, const T* r, const T* lambda, const T* d, T max_dlambda, T* xt, T* rt,
+                                       T* lambdat, T* dlambda, int batch, hipStream_t stream) {
+  const int nch = std::max(1, (J.nvar + J.nequ + 256 * TP_UNROLL - 1) / (256 * TP_UNROLL));
+  if (!linear_grid_ok(nch, batch)) return hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL(trial_point_kernel<T>, dim3((unsigned)((long long)nch * batch)), dim3(256), 0, stream, J, x, r, lambda, d, max_dlambda, xt, rt, lambdat, dlambda,
+                     batch);
+  return hipGetLastError();
+}
 hipError_t launch_trial_point(const DevJt& J, const double* x, const double* r, const double* lambda, const double* d,
                               double max_dlambda, double* xt, double* rt, double* lambdat, double* dlambda, int batch,
                               hipStream_t stream) {
-  const int nch = std::max(1, (J.nvar + J.nequ + 256 * TP_UNROLL - 1) / (256 * TP_UNROLL));
-  if (!linear_grid_ok(nch, batch)) return hipErrorInvalidConfiguration;
-  hipLaunchKernelGGL(trial_point_kernel, dim3((unsigned)((long long)nch * batch)), dim3(256), 0, stream, J, x, r, lambda, d, max_dlambda, xt, rt, lambdat, dlambda,
-                     batch);
-  return hipGetLastError();
+  return launch_trial_point_t(J, x, r, lambda, d, max_dlambda, xt, rt, lambdat, dlambda, batch, stream);
+}
+hipError_t launch_trial_point(const DevJt& J, const float* x, const float* r, const float* lambda, const float* d,
+                              float max_dlambda, float* xt, float* rt, float* lambdat, float* dlambda, int batch,
+                              hipStream_t stream) {
+  return launch_trial_point_t(J, x, r, lambda, d, max_dlambda, xt, rt, lambdat, dlambda, batch, stream);
 }
 
 hipError_t launch_condense(const DevCond& C, const double* vals, const double* rhs, double* cbuf, int slot_begin, int slot_end,

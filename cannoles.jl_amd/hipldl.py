@@ -45,6 +45,8 @@ ABI_SYMBOLS = [
     "cnl_default_params_f32", "cnl_create_f32", "cnl_create_f32_ex",
     "cnl_factorize_f32", "cnl_solve_f32", "cnl_newton_system_f32",
     "cnl_factorize_f32_dev", "cnl_solve_f32_dev", "cnl_newton_system_f32_dev", "cnl_interleave_f32_dev", "cnl_deinterleave_f32_dev",
+    "cnl_prepare_newton_system_f32_dev", "cnl_residual_vectors_f32_dev", "cnl_residual_vectors_jac_f32_dev",
+    "cnl_cgls_multipliers_f32_dev", "cnl_cgls_multipliers_jac_f32_dev", "cnl_trial_point_f32_dev",
 ]
 
 
@@ -240,6 +242,12 @@ def lib():
         L.cnl_newton_system_f32_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cnl_interleave_f32_dev.argtypes = [vp, C.c_int, vp, vp, vp]
         L.cnl_deinterleave_f32_dev.argtypes = [vp, C.c_int, vp, vp, vp]
+        L.cnl_prepare_newton_system_f32_dev.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]
+        L.cnl_residual_vectors_f32_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cnl_residual_vectors_jac_f32_dev.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cnl_cgls_multipliers_f32_dev.argtypes = [vp, vp, vp, vp, vp, flt, flt, i64, C.c_int, vp, vp]
+        L.cnl_cgls_multipliers_jac_f32_dev.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, flt, flt, i64, C.c_int, vp, vp]
+        L.cnl_trial_point_f32_dev.argtypes = [vp, vp, vp, vp, vp, flt, vp, vp, vp, vp, vp]
         for fn in ("cnl_outer_begin_dev", "cnl_outer_extrapolated_dev", "cnl_outer_trial_done_dev", "cnl_outer_end_dev", "cnl_outer_ls_begin_dev",
                    "cnl_outer_ls_step_dev", "cnl_outer_ls_take_dev"):
             getattr(L, fn).argtypes = [vp, vp]
@@ -539,23 +547,28 @@ def solve_dev(LDLT, rhs_ptr, d_ptr, stream=0):
 
 def residual_vectors_dev(LDLT, vals_ptr, r_ptr, lambda_ptr, Fx_ptr, cx_ptr, rhs_ptr, norms_ptr, stream=0):
     """rhs = [dual; primal] with dual = Jx' r - Jc' lambda, primal = [F - r; c], and their infinity norms
-    (src/CaNNOLeS.jl:507-508,519-524,528-529,631-632), batched and device-resident (cnl_residual_vectors_dev).
-    All *_ptr are device addresses; norms_ptr receives [batch][2] doubles."""
-    _check(lib().cnl_residual_vectors_dev(LDLT._h, vals_ptr, r_ptr, lambda_ptr, Fx_ptr, cx_ptr, rhs_ptr, norms_ptr, stream))
+    (src/CaNNOLeS.jl:507-508,519-524,528-529,631-632), batched and device-resident (cnl_residual_vectors_dev, or
+    cnl_residual_vectors_f32_dev on a Float32 handle).  All *_ptr are device addresses (or tensors of the handle's element type);
+    norms_ptr receives [batch][2] values."""
+    fn = lib().cnl_residual_vectors_f32_dev if _is_f32(LDLT) else lib().cnl_residual_vectors_dev
+    _check(fn(LDLT._h, *(_dev_ptr(LDLT, x) for x in (vals_ptr, r_ptr, lambda_ptr, Fx_ptr, cx_ptr, rhs_ptr, norms_ptr)), stream))
 
 
 def residual_vectors_jac_dev(LDLT, nnzjF, nnzjc, Jx_ptr, Jcx_ptr, r_ptr, lambda_ptr, Fx_ptr, cx_ptr, rhs_ptr, norms_ptr, stream=0):
     """residual_vectors_dev with the Jacobian values read from the model's arrays Jx [batch][nnzjF], Jcx [batch][nnzjc] instead of
-    from the J segments of vals (cnl_residual_vectors_jac_dev): no prepare pass in front, any batch_layout"""
-    _check(lib().cnl_residual_vectors_jac_dev(LDLT._h, int(nnzjF), int(nnzjc), Jx_ptr, Jcx_ptr, r_ptr, lambda_ptr, Fx_ptr, cx_ptr, rhs_ptr,
-                                              norms_ptr, stream))
+    from the J segments of vals (cnl_residual_vectors_jac_dev / cnl_residual_vectors_jac_f32_dev): no prepare pass in front, any
+    batch_layout"""
+    fn = lib().cnl_residual_vectors_jac_f32_dev if _is_f32(LDLT) else lib().cnl_residual_vectors_jac_dev
+    _check(fn(LDLT._h, int(nnzjF), int(nnzjc), *(_dev_ptr(LDLT, x) for x in (Jx_ptr, Jcx_ptr, r_ptr, lambda_ptr, Fx_ptr, cx_ptr, rhs_ptr,
+                                                                               norms_ptr)), stream))
 
 
 def trial_point_dev(LDLT, x_ptr, r_ptr, lambda_ptr, d_ptr, max_dlambda, xt_ptr, rt_ptr, lambdat_ptr, dlambda_ptr, stream=0):
     """xt = x + dx, rt = r + dr, dlambda = -d[n+m+1:N] capped at max_dlambda in the 2-norm, lambdat = lambda + dlambda
-    (src/CaNNOLeS.jl:654,661-668), batched and device-resident (cnl_trial_point_dev)."""
-    _check(lib().cnl_trial_point_dev(LDLT._h, x_ptr, r_ptr, lambda_ptr, d_ptr, float(max_dlambda), xt_ptr, rt_ptr, lambdat_ptr,
-                                     dlambda_ptr, stream))
+    (src/CaNNOLeS.jl:654,661-668), batched and device-resident (cnl_trial_point_dev / cnl_trial_point_f32_dev)."""
+    fn = lib().cnl_trial_point_f32_dev if _is_f32(LDLT) else lib().cnl_trial_point_dev
+    x, r, lam, d, xt, rt, lt, dl = (_dev_ptr(LDLT, a) for a in (x_ptr, r_ptr, lambda_ptr, d_ptr, xt_ptr, rt_ptr, lambdat_ptr, dlambda_ptr))
+    _check(fn(LDLT._h, x, r, lam, d, float(max_dlambda), xt, rt, lt, dl, stream))
 
 
 def layout_len(LDLT, which):
@@ -578,31 +591,40 @@ def deinterleave_dev(LDLT, which, src_ptr, dst_ptr, stream=0):
 
 
 def prepare_newton_system_dev(LDLT, nnzhF, nnzhc, nnzjF, nnzjc, hF_ptr, hc_ptr, Jx_ptr, Jcx_ptr, delta_ptr, vals_ptr, stream=0):
-    """prepare_newton_system! (src/CaNNOLeS.jl:947-981) for a batch on the device (cnl_prepare_newton_system_dev):
-    hF / -hc / Jx / Jcx / -delta / 0 into the segments of vals; hF_ptr = 0 leaves H_F alone (Gauss-Newton variants)."""
-    _check(lib().cnl_prepare_newton_system_dev(LDLT._h, int(nnzhF), int(nnzhc), int(nnzjF), int(nnzjc), hF_ptr, hc_ptr, Jx_ptr,
-                                               Jcx_ptr, delta_ptr, vals_ptr, stream))
+    """prepare_newton_system! (src/CaNNOLeS.jl:947-981) for a batch on the device (cnl_prepare_newton_system_dev /
+    cnl_prepare_newton_system_f32_dev): hF / -hc / Jx / Jcx / -delta / 0 into the segments of vals; hF_ptr = 0 leaves H_F alone
+    (Gauss-Newton variants)."""
+    fn = lib().cnl_prepare_newton_system_f32_dev if _is_f32(LDLT) else lib().cnl_prepare_newton_system_dev
+    _check(fn(LDLT._h, int(nnzhF), int(nnzhc), int(nnzjF), int(nnzjc), *(_dev_ptr(LDLT, x) for x in (hF_ptr, hc_ptr, Jx_ptr, Jcx_ptr, delta_ptr,
+                                                                                                    vals_ptr)), stream))
+
+
+def _cgls_tols(LDLT, atol, rtol):
+    """Krylov.jl's defaults sqrt(eps(T)) for the handle's element type T"""
+    eps = float(np.finfo(np.float32 if _is_f32(LDLT) else np.float64).eps)
+    return (np.sqrt(eps) if atol is None else atol), (np.sqrt(eps) if rtol is None else rtol)
 
 
 def cgls_multipliers_dev(LDLT, vals_ptr, r_ptr, lambda_ptr, Jxtr_ptr=0, atol=None, rtol=None, itmax=0, ones_if_zero=True, iters_ptr=0,
                          stream=0):
     """Least-squares multipliers min ||Jc' lambda - Jx' r|| by CGLS (src/CaNNOLeS.jl:507-518), batched and device-resident
-    (cnl_cgls_multipliers_dev).  Default tolerances: sqrt(eps), as Krylov.jl's."""
-    eps = float(np.finfo(np.float64).eps)
-    atol = np.sqrt(eps) if atol is None else atol
-    rtol = np.sqrt(eps) if rtol is None else rtol
-    _check(lib().cnl_cgls_multipliers_dev(LDLT._h, vals_ptr, r_ptr, lambda_ptr, Jxtr_ptr, float(atol), float(rtol), int(itmax),
-                                          1 if ones_if_zero else 0, iters_ptr, stream))
+    (cnl_cgls_multipliers_dev / cnl_cgls_multipliers_f32_dev).  Default tolerances: sqrt(eps) of the handle's element type, as
+    Krylov.jl's."""
+    atol, rtol = _cgls_tols(LDLT, atol, rtol)
+    fn = lib().cnl_cgls_multipliers_f32_dev if _is_f32(LDLT) else lib().cnl_cgls_multipliers_dev
+    v, r, lam, jx = (_dev_ptr(LDLT, x) for x in (vals_ptr, r_ptr, lambda_ptr, Jxtr_ptr))
+    _check(fn(LDLT._h, v, r, lam, jx, float(atol), float(rtol), int(itmax), 1 if ones_if_zero else 0, _int_ptr(iters_ptr), stream))
 
 
 def cgls_multipliers_jac_dev(LDLT, nnzjF, nnzjc, Jx_ptr, Jcx_ptr, r_ptr, lambda_ptr, Jxtr_ptr=0, atol=None, rtol=None, itmax=0,
                              ones_if_zero=True, iters_ptr=0, stream=0):
-    """cgls_multipliers_dev with the Jacobian values read from the model's arrays (cnl_cgls_multipliers_jac_dev)"""
-    eps = float(np.finfo(np.float64).eps)
-    atol = np.sqrt(eps) if atol is None else atol
-    rtol = np.sqrt(eps) if rtol is None else rtol
-    _check(lib().cnl_cgls_multipliers_jac_dev(LDLT._h, int(nnzjF), int(nnzjc), Jx_ptr, Jcx_ptr, r_ptr, lambda_ptr, Jxtr_ptr, float(atol),
-                                              float(rtol), int(itmax), 1 if ones_if_zero else 0, iters_ptr, stream))
+    """cgls_multipliers_dev with the Jacobian values read from the model's arrays (cnl_cgls_multipliers_jac_dev /
+    cnl_cgls_multipliers_jac_f32_dev)"""
+    atol, rtol = _cgls_tols(LDLT, atol, rtol)
+    fn = lib().cnl_cgls_multipliers_jac_f32_dev if _is_f32(LDLT) else lib().cnl_cgls_multipliers_jac_dev
+    jx, jc, r, lam, jt = (_dev_ptr(LDLT, x) for x in (Jx_ptr, Jcx_ptr, r_ptr, lambda_ptr, Jxtr_ptr))
+    _check(fn(LDLT._h, int(nnzjF), int(nnzjc), jx, jc, r, lam, jt, float(atol), float(rtol), int(itmax), 1 if ones_if_zero else 0,
+              _int_ptr(iters_ptr), stream))
 
 
 class MultiHIPLDLStruct:

@@ -214,6 +214,39 @@ cgls_multipliers_jac_dev!(f::HIPFactor, nnzjF, nnzjc, Jx, Jcx, r, λ; Jxtr = C_N
     (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Int64, Cint, Ptr{Int32}, Ptr{Cvoid}),
     f.handle, nnzjF, nnzjc, Jx, Jcx, r, λ, Jxtr, atol, rtol, itmax, ones_if_zero ? 1 : 0, iters, stream))
 
+# Float32 methods (HIPFactor32, `_f32_dev` entry points): the same rows with Float32 device arrays and scalars
+residual_vectors_dev!(f::HIPFactor32, vals, r, λ, Fx, cx, rhs, norms; stream = C_NULL) =
+  check(ccall((:cnl_residual_vectors_f32_dev, libcnl), Cint,
+    (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
+    f.handle, vals, r, λ, Fx, cx, rhs, norms, stream))
+
+trial_point_dev!(f::HIPFactor32, x, r, λ, d, Mdλ, xt, rt, λt, dλ; stream = C_NULL) =
+  check(ccall((:cnl_trial_point_f32_dev, libcnl), Cint,
+    (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Float32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
+    f.handle, x, r, λ, d, Mdλ, xt, rt, λt, dλ, stream))
+
+prepare_newton_system_dev!(f::HIPFactor32, nnzhF, nnzhc, nnzjF, nnzjc, hF, hc, Jx, Jcx, δ, vals; stream = C_NULL) =
+  check(ccall((:cnl_prepare_newton_system_f32_dev, libcnl), Cint,
+    (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
+    f.handle, nnzhF, nnzhc, nnzjF, nnzjc, hF, hc, Jx, Jcx, δ, vals, stream))
+
+cgls_multipliers_dev!(f::HIPFactor32, vals, r, λ; Jxtr = C_NULL, atol = √eps(Float32), rtol = √eps(Float32), itmax = 0,
+                      ones_if_zero = true, iters = C_NULL, stream = C_NULL) =
+  check(ccall((:cnl_cgls_multipliers_f32_dev, libcnl), Cint,
+    (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Float32, Float32, Int64, Cint, Ptr{Int32}, Ptr{Cvoid}),
+    f.handle, vals, r, λ, Jxtr, atol, rtol, itmax, ones_if_zero ? 1 : 0, iters, stream))
+
+residual_vectors_jac_dev!(f::HIPFactor32, nnzjF, nnzjc, Jx, Jcx, r, λ, Fx, cx, rhs, norms; stream = C_NULL) =
+  check(ccall((:cnl_residual_vectors_jac_f32_dev, libcnl), Cint,
+    (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
+    f.handle, nnzjF, nnzjc, Jx, Jcx, r, λ, Fx, cx, rhs, norms, stream))
+
+cgls_multipliers_jac_dev!(f::HIPFactor32, nnzjF, nnzjc, Jx, Jcx, r, λ; Jxtr = C_NULL, atol = √eps(Float32), rtol = √eps(Float32), itmax = 0,
+                          ones_if_zero = true, iters = C_NULL, stream = C_NULL) =
+  check(ccall((:cnl_cgls_multipliers_jac_f32_dev, libcnl), Cint,
+    (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Float32, Float32, Int64, Cint, Ptr{Int32}, Ptr{Cvoid}),
+    f.handle, nnzjF, nnzjc, Jx, Jcx, r, λ, Jxtr, atol, rtol, itmax, ones_if_zero ? 1 : 0, iters, stream))
+
 # ---- `vals` interleaved over groups of 32 problems (cnl_options.batch_layout = CNL_LAYOUT_INTERLEAVED, include/cannoles_hip.h): batched
 # handles created through `cnl_create_ex` with that option take / write this layout at the device-pointer entry points --------------
 

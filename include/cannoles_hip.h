@@ -347,7 +347,7 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  * + 64 when cnl_newton_system runs on the band kernels (then bits 8-15 = problems per workgroup, bits 16-23 = parts of the chain),
  * + 128 when cnl_residual_vectors_dev runs on column tiles. */
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
-/* ([5] + (1 << 27) on a Float32 handle, which runs the band kernels only: bits 8-26 as above, cfg[0..4], [6], [7] are 0.) */
+/* ([5] + (1 << 27) on a Float32 handle, which runs the band kernels only: bits 7-26 as above, cfg[0..4], [6], [7] are 0.) */
 /* Launches of the Newton-system kernels since the library was loaded, per kernel family: counts[0] band kernels (csrc/band.hip),
  * [1] register-front kernel (csrc/kernels2.hip, staged launches not included), [2] general kernel (csrc/kernels.hip).  Lets a test
  * pin WHICH kernel served a call sequence (e.g. that solve_ldl! behind a band factorisation launches no second kernel family). */
@@ -356,9 +356,10 @@ int cnl_launch_counts(int64_t counts[3]);
 /* ---- Float32 (LDLFactorization{Float32}, ParamCaNNOLeS(Float32)) on the band kernels ------------------------------------
  * A Float32 handle stores values, rhs, d, rho, rho_old and the factor records as float and computes in float (fmaf, float
  * compares, the inertia test against eig_tol = eps(Float32)): what the reference computes with T = Float32
- * (src/solver_types.jl:79-98, src/CaNNOLeS.jl:1008-1052).  It serves the plugin surface only — try_to_factorize, solve_ldl!,
+ * (src/solver_types.jl:79-98, src/CaNNOLeS.jl:1008-1052).  It serves the plugin surface — try_to_factorize, solve_ldl!,
  * newton_system! — in host-pointer and `_dev` forms, in either cnl_options.batch_layout, always on the band kernels (any batch,
- * 1 included).  cnl_create_f32 / cnl_create_f32_ex take the arguments of cnl_create / cnl_create_ex and fail with CNL_ERR_ARG
+ * 1 included), and the device-resident passes around it (rows f1 / f2 / f4 and the trial point, `_f32_dev` below).
+ * cnl_create_f32 / cnl_create_f32_ex take the arguments of cnl_create / cnl_create_ex and fail with CNL_ERR_ARG
  * (cnl_last_error names the reason) when the pattern is not a band or cnl_options.band_kernel = 0: the caller stays on the CPU.
  * The semantics of every call are those of its Float64 twin above.  Mixing element types is CNL_ERR_STATE and does nothing:
  * a Float64 entry point on a Float32 handle (cnl_factorize..., the row f1 / f2 / f4 / trial-point passes, cnl_interleave_dev...)
@@ -379,6 +380,31 @@ int cnl_newton_system_f32_dev(cnl_handle* h, float* d_vals, const float* d_rhs, 
                               float* d_rho, int32_t* d_nfact, int32_t* d_success, const float params[9], void* stream);
 int cnl_interleave_f32_dev(cnl_handle* h, int which, const float* d_src, float* d_dst, void* stream);
 int cnl_deinterleave_f32_dev(cnl_handle* h, int which, const float* d_src, float* d_dst, void* stream);
+
+/* Rows f1 / f2 / f4 and the trial point on a Float32 handle: the arguments of the Float64 twins with double replaced by float
+ * (norms: float [batch][2]; atol, rtol, max_dlambda: float), the same layout rules (prepare writes `vals` interleaved on a
+ * CNL_LAYOUT_INTERLEAVED handle; the `vals`-reading f1 / f4 calls refuse such a handle: use the `_jac` twins), all arithmetic in
+ * float as the reference's with T = Float32 — f1 and Jx'r with per-column COO-order sums, multiply and add rounded separately;
+ * CGLS (Krylov.jl with T = Float32; defaults sqrt(eps(Float32))).  One deviation: the trial point sums the squares of dlambda in
+ * double and rounds ||dlambda||_2 to float once (squares of |dlambda| >= 1.8e19 overflow float; BLAS snrm2 scales and does not).
+ *   cnl_prepare_newton_system_f32_dev  src/CaNNOLeS.jl:947-981
+ *   cnl_residual_vectors_f32_dev, cnl_residual_vectors_jac_f32_dev  :507-508, :519-524, :528-529, :722-726, :730-731, :631-632
+ *   cnl_cgls_multipliers_f32_dev, cnl_cgls_multipliers_jac_f32_dev  :507-518, :880-882
+ *   cnl_trial_point_f32_dev            :654, :661-668                                                                         */
+int cnl_prepare_newton_system_f32_dev(cnl_handle* h, int64_t nnzhF, int64_t nnzhc, int64_t nnzjF, int64_t nnzjc, const float* d_hF,
+                                      const float* d_hc, const float* d_Jx, const float* d_Jcx, const float* d_delta, float* d_vals,
+                                      void* stream);
+int cnl_residual_vectors_f32_dev(cnl_handle* h, const float* d_vals, const float* d_r, const float* d_lambda, const float* d_Fx,
+                                 const float* d_cx, float* d_rhs, float* d_norms, void* stream);
+int cnl_residual_vectors_jac_f32_dev(cnl_handle* h, int64_t nnzjF, int64_t nnzjc, const float* d_Jx, const float* d_Jcx, const float* d_r,
+                                     const float* d_lambda, const float* d_Fx, const float* d_cx, float* d_rhs, float* d_norms, void* stream);
+int cnl_cgls_multipliers_f32_dev(cnl_handle* h, const float* d_vals, const float* d_r, float* d_lambda, float* d_Jxtr, float atol,
+                                 float rtol, int64_t itmax, int ones_if_zero, int32_t* d_iters, void* stream);
+int cnl_cgls_multipliers_jac_f32_dev(cnl_handle* h, int64_t nnzjF, int64_t nnzjc, const float* d_Jx, const float* d_Jcx, const float* d_r,
+                                     float* d_lambda, float* d_Jxtr, float atol, float rtol, int64_t itmax, int ones_if_zero,
+                                     int32_t* d_iters, void* stream);
+int cnl_trial_point_f32_dev(cnl_handle* h, const float* d_x, const float* d_r, const float* d_lambda, const float* d_d,
+                            float max_dlambda, float* d_xt, float* d_rt, float* d_lambdat, float* d_dlambda, void* stream);
 
 #ifdef __cplusplus
 }
