@@ -33,8 +33,10 @@ constexpr int BAND_NPIECE = 15;     // 64-byte operand pieces per epoch and lane
 constexpr int BAND_REC_MAX = 256;    // ints of step + row blocks per epoch (LDS record buffer of a wavefront)
 constexpr int BAND_LREC = 6;        // factor doubles per pivot: band multipliers, border multiplier, z  (see band.hip)
 
-// LDS block of one lane, in elements (doubles; floats on Float32 handles): [operand pieces | out ring | zero cell].  The out ring holds the factor records of HALF an
-// epoch in the forward sweep (flushed behind steps 3 and 7) and the solution components of an epoch in the backward sweep.
+// LDS block of one lane, in elements (doubles; floats on Float32 handles): [operand pieces | out ring | zero cell].  The out ring holds the solution
+// components of an epoch in the backward sweep and the factor records of HALF an epoch in the forward sweep (BS_LB / BS_LX relative
+// to BE_LBASE / BE_LBASE2; flushed behind steps 3 and 7).  The 32-problem kernels turn those offsets back into record indices and
+// store the records to global memory directly, so their forward sweep leaves the ring unused.
 // 153 doubles = 1224 bytes per lane: 128 lanes (two workgroups of 32 problems) fit the 160 KB of a CU.
 constexpr int BAND_IN_OFF = 0;
 constexpr int BAND_LOUT_OFF = BAND_NPIECE * 8;                       // forward: factor records of half an epoch
@@ -66,7 +68,7 @@ enum {
   BS_OD,               // BS_OD + 2 (k - 1) + dup: entries coupling the entering variable with the one entered k steps earlier
   BS_BC0 = BS_OD + 2 * BAND_HW, BS_BC1,   // entries coupling it with the live border (multiplier) row
   BS_RX,               // its right-hand-side entry
-  BS_LB,               // LDS offset of the factor record of this step's border pivot (forward: out ring; backward: operand piece)
+  BS_LB,               // LDS offset of the factor record of this step's border pivot (forward: out ring, see above; backward: operand piece)
   BS_LX,               // ... of this step's band pivot
   BS_DX,               // backward: offset in the dx-out ring of the band pivot's solution component
   BS_BORDER,           // index into the border table of the border that enters / is pivoted in this step

@@ -6,10 +6,12 @@
 // has two roles that alternate:
 //  * mover — all 64 lanes: lane (lq, le) = (lane / 8, lane % 8) moves element le of the 64-byte pieces of problems lq, lq + 8, ...
 //    between HBM and the problems' LDS blocks: the operand pieces of the NEXT epoch are loaded into registers while the current
-//    epoch computes (the registers are the look-ahead buffer), written to LDS at the next epoch's start, and the factor records /
-//    solution components an epoch produced go out the same way.  Every vector-memory instruction moves eight 64-byte runs.
+//    epoch computes (the registers are the look-ahead buffer), written to LDS at the next epoch's start, and the solution
+//    components an epoch produced (with 8 or 16 problems per workgroup its factor records too) go out the same way.  Every
+//    vector-memory instruction moves eight 64-byte runs.
 //  * compute — lanes 0 .. NL-1, lane = problem: the window (5 band slots x 5, one border row, the right-hand side: 27 doubles) lives
-//    in registers, every operand is one ds_read_b64 at an offset the generator fixed, every update a plain v_fma_f64.  No
+//    in registers, every operand is one ds_read_b64 at an offset the generator fixed, every update a plain v_fma_f64; with 32
+//    problems per workgroup every factor record goes to global memory from the lane that computed it (frec_index).  No
 //    cross-lane operation, no LDS atomics, no index decode: the step blocks are wave-uniform and come through the scalar cache.
 // Summation order (documented deviation, within the fp64 bar of DESIGN section 5): entering position = plain entries in COO
 // order (src/solver_types.jl:53-59: duplicates summed in COO order), then the condensed rows' products in row order, then the
@@ -118,12 +120,31 @@ __device__ __forceinline__ void fload(FOps<T>& P, const Rec& st, const RowRec& r
 // interleaved over the NL problems of a workgroup in blocks of eight doubles (stride = NL * 8) block e / 8 is NL * 8 doubles further
 __device__ __forceinline__ long long band_il_offset(int e, int stride) { return stride ? (long long)(e >> 3) * stride + (e & 7) : (long long)e; }
 
+// Factor records of the 32-problem instantiations go from the compute lanes straight to global memory (direct_records).  Their
+// layout is private to the launch (written by the forward sweep, read by the backward sweep of the SAME workgroup): ELEMENT-major,
+// problem-minor over the NL problems of the workgroup — element e of problem p at (loff + e) * NL + p of the workgroup's region —
+// so that one store of the compute lanes writes NL contiguous elements (256 bytes, two whole lines, for 32 doubles) and a
+// backward piece of eight elements reads eight such rows (2 KB).  The program's forward BS_LB / BS_LX hold the record's LDS byte offset in the half-epoch out ring the
+// generator still lays out (band.cpp: BAND_LOUT_OFF + event * BAND_LREC - BE_LBASE / BE_LBASE2 of the step's half); recb0 = that
+// half's BE_LBASE* - BAND_LOUT_OFF turns it back into the record's first element (tests/test_band_records_cpu.py).
+// The 8- and 16-problem instantiations keep the records in the LDS out ring at those offsets and the mover flushes them behind
+// steps 3 and 7, problem-major: at 8 192 problems and below the chain of one wavefront per SIMD bounds the time, and the compute
+// lanes' stores and their address arithmetic cost Float32 with 16 problems per workgroup 4 % (tools/time_band_f32.py) while the
+// 32-problem instantiations gain 4 ... 5 %.
+__host__ __device__ constexpr bool direct_records(int nl) { return nl >= 32; }
+template <class T>
+__device__ __forceinline__ int frec_index(int lds_off, int recb0) {
+  return (lds_off >> (sizeof(T) == 8 ? 3 : 2)) + recb0;
+}
+
 // one forward step of phase PH = step number % 8: enter slot PH, pivot slot PH - 4; fl = flags word (wave-uniform), o = int
-// offset of the step block in the record buffer.  The operands were read (fload) while the previous step computed.
-template <int PH, class T>
+// offset of the step block in the record buffer.  The operands were read (fload) while the previous step computed.  The step's
+// factor records go to recp (the lane's first record element, RNL = problems per workgroup) when recst, or to the out ring.
+template <int PH, int RNL, class T>
 __device__ __forceinline__ void fstep(Win<T>& W, const FOps<T>& OP, const Rec& st, const int fl, const char* recb, const int o, char* myb,
                                       const T* __restrict__ gvals, const T* __restrict__ grhs, cptr borders, long long pv, long long pr,
-                                      bool has_rhs, T rho, bool ovr, T tol, int& npos, int& nzer, const int vstride = 0, const int rstride = 0) {
+                                      bool has_rhs, T rho, bool ovr, T tol, int& npos, int& nzer, const int vstride, const int rstride,
+                                      T* recp, const int recb0, const bool recst) {
   constexpr int es = PH, ps = lslot(PH, 0);
   const int nrows = (fl >> 8) & 255;
   const T (&eo)[15] = OP.eo;
@@ -188,10 +209,19 @@ __device__ __forceinline__ void fstep(Win<T>& W, const FOps<T>& OP, const Rec& s
       for (int kb = 0; kb <= ka; kb++) W.S[sidx(lslot(PH, ka), lslot(PH, kb))] = fma(w[ka], -l[kb], W.S[sidx(lslot(PH, ka), lslot(PH, kb))]);
       W.c[lslot(PH, ka)] = fma(w[ka], -z, W.c[lslot(PH, ka)]);
     }
-    T* lo = reinterpret_cast<T*>(myb + st.v[BS_LB]);
+    if constexpr (direct_records(RNL)) {
+      if (recst) {
+        T* lo = recp + frec_index<T>(st.v[BS_LB], recb0) * RNL;
 #pragma unroll
-    for (int k = 0; k < BAND_NB; k++) lo[k] = l[k];
-    lo[BAND_NB] = z;
+        for (int k = 0; k < BAND_NB; k++) lo[k * RNL] = l[k];
+        lo[BAND_NB * RNL] = z;
+      }
+    } else {
+      T* lo = reinterpret_cast<T*>(myb + st.v[BS_LB]);
+#pragma unroll
+      for (int k = 0; k < BAND_NB; k++) lo[k] = l[k];
+      lo[BAND_NB] = z;
+    }
 #pragma unroll
     for (int k = 0; k < BAND_NB; k++) W.X[lslot(PH, k)] = T(0);
     W.S55 = T(0); W.c5 = T(0);
@@ -215,11 +245,21 @@ __device__ __forceinline__ void fstep(Win<T>& W, const FOps<T>& OP, const Rec& s
     }
     W.S55 = fma(w5, -l5, W.S55);
     W.c5 = fma(w5, -z, W.c5);
-    T* lo = reinterpret_cast<T*>(myb + st.v[BS_LX]);
+    if constexpr (direct_records(RNL)) {
+      if (recst) {
+        T* lo = recp + frec_index<T>(st.v[BS_LX], recb0) * RNL;
 #pragma unroll
-    for (int k = 1; k < BAND_NB; k++) lo[k - 1] = l[k];
-    lo[4] = l5;
-    lo[5] = z;
+        for (int k = 1; k < BAND_NB; k++) lo[(k - 1) * RNL] = l[k];
+        lo[4 * RNL] = l5;
+        lo[5 * RNL] = z;
+      }
+    } else {
+      T* lo = reinterpret_cast<T*>(myb + st.v[BS_LX]);
+#pragma unroll
+      for (int k = 1; k < BAND_NB; k++) lo[k - 1] = l[k];
+      lo[4] = l5;
+      lo[5] = z;
+    }
   }
 }
 
@@ -333,8 +373,8 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   const int nnz = P.nnz, N = P.N;
   const long long lsize = P.lsize;
   // mover: wave-uniform base pointers + 32-bit per-lane byte offsets (NL problems span < 4 GB)
-  // cnl_options.batch_layout = 1: `vals` is given INTERLEAVED over groups of 32 problems in blocks of eight doubles, the layout of the
-  // factor records below — element e of problem p of group g at
+  // cnl_options.batch_layout = 1: `vals` is given INTERLEAVED over groups of 32 problems in blocks of eight doubles — element e of
+  // problem p of group g at
   // ((g * band_il_blocks(nnz) + e / 8) * 32 + p) * 8 + e % 8 — so that the eight 64-byte runs of a mover load are 512 contiguous bytes
   // and every 128-byte line that is fetched is used whole (16 384 problems: 12.5 -> 11.0 ms with vals and rhs interleaved, bit-equal).
   // Bit 1 of the layout word: the same for `rhs`.  d is problem-major always.
@@ -347,17 +387,15 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   const int ilp = (prob0 % BAND_IL_GROUP) * 8;        // ... and the offset of its first problem inside a block row
   const T* vbase = gvals + (vil ? ilg * band_il_blocks(nnz) * G8 + ilp : (long long)prob0 * nnz);
   const T* rbase = !has_rhs ? gvals : grhs + (ril ? ilg * band_il_blocks(N) * G8 + ilp : (long long)prob0 * N);
-  // The factor records are private to the launch (written by the forward sweep, read by the backward sweep of the SAME workgroup), so
-  // their layout is the kernel's choice: INTERLEAVED over the NL problems of the workgroup in blocks of eight doubles — element e of
-  // problem p of the workgroup lives at ((e >> 3) * NL + p) * 8 + (e & 7) of the workgroup's region — so that the eight 64-byte runs one
-  // store / load instruction touches are 512 contiguous bytes (tools/seg_bench.hip: this memory system gives scattered 64-byte
-  // segments 3.4 ... 4.5 TB/s, runs of 256 bytes and more 6.0).
-  // Measured on one box (tools/ab_lib.py): 16 384 problems, 32 per workgroup: 12.41 -> 12.22 ms; 8 192 problems, 16 per workgroup:
-  // 7.40 -> 7.75 ms (the address arithmetic costs the latency-bound case more than the layout gives) — so only the 32-problem
-  // instantiation interleaves.
-  constexpr bool LINT = NL >= 32;
-  T* lbase_g = gL + (long long)prob0 * lsize + (LINT ? 0 : P.loff[part]);
-  const int loff8 = LINT ? (int)P.loff[part] : 0;   // a multiple of 8
+  // The factor records are private to the launch.  32 problems per workgroup: element-major over the workgroup's region, stored by
+  // the compute lanes as they are computed (see frec_index; they used to go through the out ring and out with the mover, interleaved
+  // in blocks of eight doubles: a record run that does not start on a block boundary wrote its first and last lines in two epochs, and
+  // the backward pieces fetched them twice — 16 384 problems: 11.19 -> 10.70 ms).  8 or 16 problems: problem-major,
+  // through the out ring.  The mover reads them back in the backward sweep.
+  constexpr bool DREC = direct_records(NL);
+  T* lbase_g = gL + (long long)prob0 * lsize + (DREC ? 0 : P.loff[part]);
+  const int loff8 = DREC ? (int)P.loff[part] : 0;   // a multiple of 8
+  T* const recp = lbase_g + (long long)loff8 * NL + (lane < NL ? lane : 0);   // compute lane's first record element (DREC)
   T* dbase = gd ? gd + (long long)prob0 * N : nullptr;
   unsigned movp[NI], ldsb[NI];   // problem of the lane inside the workgroup (clamped to the batch), LDS byte offset of its element
   bool movok[NI];
@@ -385,6 +423,8 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   T rho_old = (mode == MODE_NEWTON && valid) ? as_global(reinterpret_cast<T*>(Ain.rho_old))[cprob] : T(0);
   int nfact = 0;
   bool done = !valid, success = false, ovr = false;
+  // (try_to_factorize keeps no records: a later solve_ldl! factorises again, see MODE_SOLVE above)
+  const bool recst = valid && mode != MODE_FACTOR;   // (DREC)
 
   static_assert(NI <= 4, "at most four problem groups per mover lane");
   T stg[NPC][NI];        // operand pieces in flight
@@ -404,18 +444,21 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
     const int pc = pcs[K];                                                                                                    \
     const int arr = pc >> 28;                                                                                                 \
     const int el_ = (pc & ((1 << 28) - 1)) + (arr == 2 ? loff8 : 0);                                                          \
-    /* lane offset (elements) = problem * strd + tl, tl = t + (t >> 3) * gap with t = m + element of the lane: the caller's arrays    \
-       are problem-major (m = 0, t < 8: gap = 0), the factor is interleaved in blocks of eight (see lbase_g) */                \
-    const bool il_ = arr == 0 ? vil : arr == 1 ? ril : LINT;   /* (wave-uniform) */                                           \
+    /* lane offset (elements) = problem * strd + tl, tl = t * tm + (t >> 3) * gap with t = m + element of the lane: the caller's    \
+       arrays are problem-major (m = 0, t < 8: gap = 0) or interleaved in blocks of eight, the factor is element-major (see        \
+       lbase_g: a row of NL elements per record element, tm = NL) or problem-major (DREC false) */                           \
+    const bool il_ = arr == 0 ? vil : arr == 1 ? ril : DREC;   /* (wave-uniform) */                                           \
     const int ilw_ = arr == 2 ? NL * 8 : BAND_IL_GROUP * 8;    /* elements per block row: the factor's own layout / the ABI's */ \
     const int m_ = il_ ? (el_ & 7) : 0;                                                                                       \
-    const unsigned gap_ = il_ ? (unsigned)(ilw_ - 8) : 0u;                                                                    \
+    const unsigned gap_ = il_ && !(DREC && arr == 2) ? (unsigned)(ilw_ - 8) : 0u;                                              \
+    const unsigned tm_ = arr == 2 && DREC ? (unsigned)NL : 1u;                                                                \
     const char* pb = (arr == 0 ? reinterpret_cast<const char*>(vbase) : arr == 1 ? reinterpret_cast<const char*>(rbase)       \
                                                                                  : reinterpret_cast<const char*>(lbase_g)) +   \
                      ((il_ ? (long long)(el_ >> 3) * ilw_ : (long long)el_) << LS);                                           \
-    const unsigned strd = il_ ? 8u : arr == 0 ? (unsigned)nnz : arr == 1 ? (unsigned)N : (unsigned)lsize;                     \
+    const unsigned strd = DREC ? (arr == 2 ? 1u : il_ ? 8u : arr == 0 ? (unsigned)nnz : (unsigned)N)                         \
+                               : (il_ ? 8u : arr == 0 ? (unsigned)nnz : arr == 1 ? (unsigned)N : (unsigned)lsize);             \
     const unsigned t_ = (unsigned)m_ + (unsigned)le;                                                                          \
-    const unsigned tl = t_ + (t_ >> 3) * gap_;                                                                                \
+    const unsigned tl = t_ * tm_ + (t_ >> 3) * gap_;                                                                          \
     BAND_ISSUE1(K, 0) BAND_ISSUE1(K, 1) BAND_ISSUE1(K, 2) BAND_ISSUE1(K, 3)                                                   \
   }
 #define BAND_COMMIT(K) { BAND_COMMIT1(K, 0) BAND_COMMIT1(K, 1) BAND_COMMIT1(K, 2) BAND_COMMIT1(K, 3) }
@@ -462,6 +505,8 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
       // The steps of the epoch: step t works on the slots of phase t (every epoch but the last has BAND_EPOCH steps), so the eight
       // instantiations follow each other in straight-line code and the window keeps its registers from step to step.
       const int nst = E[BE_NSTEP];
+      // first record element of each half of the epoch, less the out ring's offset that the program's BS_LB / BS_LX carry
+      const int recb1 = E[BE_LBASE] - BAND_LOUT_OFF, recb2 = E[BE_LBASE2] - BAND_LOUT_OFF;
       int o = 0;
       // the blocks of step t + 1 (step block + first row block) are read from the record buffer while step t computes; the step
       // reads all its operands at its top (one LDS round trip).  (A third stage — operands a step ahead — was measured: no gain,
@@ -478,29 +523,26 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
         if (clane) {                                                                                                        \
           FOps<T> op_;                                                                                                      \
           fload(op_, stC, rwC, fl, myb);                                                                                    \
-          fstep<PHV>(W, op_, stC, fl, recb, o, myb, gvals, grhs, borders, pv, pr, has_rhs, rho, ovr, tol, npos, nzer, vstride, rstride); \
+          fstep<PHV, NL>(W, op_, stC, fl, recb, o, myb, gvals, grhs, borders, pv, pr, has_rhs, rho, ovr, tol, npos, nzer, vstride, rstride, \
+                         recp, PHV < BAND_EPOCH / 2 ? recb1 : recb2, recst);                                              \
         }                                                                                                                   \
         o = onext; stC = stN; rwC = rwN;                                                                                    \
       }
-      // factor records: the out ring holds those of half an epoch; whole 64-byte pieces are read from it (all reads first), lanes
-      // past the records do not store
-      // (try_to_factorize keeps no records: a later solve_ldl! factorises again, see MODE_SOLVE above)
+      // !DREC: the out ring holds the factor records of half an epoch; whole pieces are read from it (all reads first), lanes past
+      // the records do not store
 #define BAND_LFLUSH(LB, LC)                                                                                                 \
-      if (mode != MODE_FACTOR) {                                                                                            \
-        const int lc_ = (LC);                                                                                               \
-        const int lb_ = (LB) + loff8;                                                                                       \
-        char* lout = reinterpret_cast<char*>(lbase_g) + ((LINT ? (long long)(lb_ >> 3) * (NL * 8) : (long long)lb_) << LS); \
-        const unsigned t_ = (LINT ? (unsigned)(lb_ & 7) : 0u) + (unsigned)le;                                               \
-        const unsigned tl = t_ + (LINT ? (t_ >> 3) * (unsigned)(NL * 8 - 8) : 0u);                                          \
-        const unsigned lstr_ = LINT ? 8u : (unsigned)lsize;                                                                 \
-        constexpr int lcp_ = LINT ? NL * 8 * ES : 8 * ES;                                                                   \
-        T lx_[BAND_LOUT_MAX / 8][NI];                                                                                       \
-        _Pragma("unroll") for (int cpc = 0; cpc < BAND_LOUT_MAX / 8; cpc++)                                                 \
-          _Pragma("unroll") for (int i = 0; i < NI; i++) lx_[cpc][i] = *reinterpret_cast<const T*>(wblk + ldsb[i] + (BAND_LOUT_OFF + 8 * cpc) * ES); \
-        _Pragma("unroll") for (int cpc = 0; cpc < BAND_LOUT_MAX / 8; cpc++)                                                 \
-          _Pragma("unroll") for (int i = 0; i < NI; i++)                                                                    \
-            if (movok[i] && cpc * 8 + le < lc_)                                                                             \
-              *reinterpret_cast<T*>(lout + (((movp[i] * lstr_ + tl) << LS) + lcp_ * cpc)) = lx_[cpc][i];                     \
+      if constexpr (!DREC) {                                                                                                \
+        if (mode != MODE_FACTOR) {                                                                                          \
+          const int lc_ = (LC);                                                                                             \
+          char* lout = reinterpret_cast<char*>(lbase_g) + ((long long)(LB) << LS);                                          \
+          T lx_[BAND_LOUT_MAX / 8][NI];                                                                                     \
+          _Pragma("unroll") for (int cpc = 0; cpc < BAND_LOUT_MAX / 8; cpc++)                                               \
+            _Pragma("unroll") for (int i = 0; i < NI; i++) lx_[cpc][i] = *reinterpret_cast<const T*>(wblk + ldsb[i] + (BAND_LOUT_OFF + 8 * cpc) * ES); \
+          _Pragma("unroll") for (int cpc = 0; cpc < BAND_LOUT_MAX / 8; cpc++)                                               \
+            _Pragma("unroll") for (int i = 0; i < NI; i++)                                                                  \
+              if (movok[i] && cpc * 8 + le < lc_)                                                                           \
+                *reinterpret_cast<T*>(lout + (((movp[i] * (unsigned)lsize + (unsigned)le) << LS) + 8 * ES * cpc)) = lx_[cpc][i]; \
+        }                                                                                                                   \
       }
       BAND_FSTEP(0)
       if (more_) { BAND_ISSUE(0) BAND_ISSUE(1) BAND_ISSUE(2) BAND_ISSUE(3) }
