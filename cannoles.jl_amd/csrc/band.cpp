@@ -35,7 +35,7 @@ struct StepOp {
 inline int32_t rhs_src(int64_t i) { return (int32_t)(-(i + 2)); }
 
 // packs the sources of one epoch into 64-byte pieces (eight consecutive elements of one array); returns false when more than
-// BAND_NPIECE are needed.  (Round 5 also had a layout with four 128-byte pieces per epoch: measured equal, removed in round 6.)
+// npiece (the program's piece count) are needed.  (Round 5 also had a layout with four 128-byte pieces per epoch: measured equal, removed in round 6.)
 struct Packer {
   int32_t len[3];
   struct Piece { int32_t arr, base, slot; };
@@ -55,8 +55,9 @@ struct Packer {
         while (i < v.size() && v[i] < b + 8) i++;
       }
     }
-    return (int)pieces.size() <= BAND_NPIECE;
+    return (int)pieces.size() <= npiece;
   }
+  int32_t npiece = BAND_NPIECE;
   int32_t esz = 8;   // bytes per element
   // LDS byte offset of element e of array a
   int32_t off(int a, int32_t e) const {
@@ -69,9 +70,15 @@ struct Packer {
 }  // namespace
 
 void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ,
-                     int64_t ncon, int nparts_wanted, int esz) {
+                     int64_t ncon, int nparts_wanted, int esz, int npiece) {
   B = BandPlan();
   if (esz != 8 && esz != 4) { B.ok = false; B.why = "element size must be 8 or 4 bytes"; return; }
+  if (npiece != BAND_NPIECE && npiece != BAND_NPIECE_WIDE) { B.ok = false; B.why = "piece count must be 15 or 20"; return; }
+  B.npiece = npiece;
+  // lane block and epoch block of a program of npiece pieces (band.h)
+  const int32_t LOUT_OFF = band_lout_off(npiece), DX_OFF = band_dx_off(npiece), DR_OFF = band_dr_off(npiece), ZERO_OFF = band_zero_off(npiece);
+  const int32_t EW = band_ew(npiece);
+  auto EF = [npiece](int f) { return band_ef(f, npiece); };
   auto no = [&](const std::string& w) { B.ok = false; B.why = w; };
   const int64_t n = nvar, m = nequ, p = ncon;
   if (N != n + m + p) return no("N != nvar + nequ + ncon");
@@ -283,9 +290,9 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
     std::vector<std::vector<int32_t>> fblocks(nsteps), bblocks(nsteps);
     Packer pk;
     pk.len[0] = (int32_t)nnz; pk.len[1] = (int32_t)N; pk.len[2] = (int32_t)(lpart + 16);
-    pk.esz = esz;
+    pk.esz = esz; pk.npiece = npiece;
     if (lpart + 16 >= (1 << 27)) return no("factor too long");
-    const int32_t ZB = BAND_ZERO_OFF * esz;
+    const int32_t ZB = ZERO_OFF * esz;
     // An epoch is a run of BAND_EPOCH steps whose operands must fit the pieces and whose outputs the rings.
     std::string why_not;
     auto try_epoch = [&](const int32_t u0, const int32_t u1, int32_t* E) -> bool {
@@ -301,7 +308,7 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
       int32_t oplen = 0;
       for (int32_t u = u0; u < u1; u++) oplen += BAND_SW + BAND_RW * (int32_t)S[u].rows.size();
       if (oplen > BAND_REC_MAX) return no("the blocks of an epoch do not fit the record buffer");
-      E[BE_OPLEN] = oplen;
+      E[EF(BE_OPLEN)] = oplen;
       const int32_t lbase = ev_hi >= 0 ? ev_lo * BAND_LREC : 0, lcnt = ev_hi >= 0 ? (ev_hi - ev_lo + 1) * BAND_LREC : 0;
       // the out ring takes the factor records of half an epoch (steps 0 .. 3, then 4 .. 7)
       const int32_t uh = std::min(u1, u0 + BAND_EPOCH / 2);
@@ -318,9 +325,9 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
       if (x_cnt && x_hi - x_lo + 1 != x_cnt) return no("pivots of an epoch are not consecutive variables");
       if (r_cnt && r_hi - r_lo + 1 != r_cnt) return no("rows of an epoch are not consecutive");
       if (x_cnt > BAND_DX_MAX || r_cnt > BAND_DR_MAX) return no("more outputs in an epoch than the rings hold");
-      E[BE_LBASE] = lbase1; E[BE_LCNT] = lcnt1; E[BE_LBASE2] = lbase2; E[BE_LCNT2] = lcnt2;
-      E[BE_DXLO] = x_cnt ? x_lo : 0; E[BE_DXCNT] = x_cnt;
-      E[BE_DRLO] = r_cnt ? (int32_t)(n + r_lo) : 0; E[BE_DRCNT] = r_cnt;
+      E[EF(BE_LBASE)] = lbase1; E[EF(BE_LCNT)] = lcnt1; E[EF(BE_LBASE2)] = lbase2; E[EF(BE_LCNT2)] = lcnt2;
+      E[EF(BE_DXLO)] = x_cnt ? x_lo : 0; E[EF(BE_DXCNT)] = x_cnt;
+      E[EF(BE_DRLO)] = r_cnt ? (int32_t)(n + r_lo) : 0; E[EF(BE_DRCNT)] = r_cnt;
       // forward operands
       for (int dir = 0; dir < 2; dir++) {
         std::vector<int32_t> need[3];
@@ -345,10 +352,11 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
         if (!pk.pack(need)) {
           std::string w = "an epoch needs more operand pieces than a lane holds (part " + std::to_string(part) + ", steps " + std::to_string(u0) + ".." + std::to_string(u1) + (dir ? ", backward" : ", forward") + ":";
           for (auto& pc : pk.pieces) w += " " + std::to_string(pc.arr) + ":" + std::to_string(pc.base);
+          B.pieces_short = true;
           return no(w + ")");
         }
-        int32_t* PP = E + (dir == 0 ? BE_FP : BE_BP);
-        for (int k = 0; k < BAND_NPIECE; k++) PP[k] = -1;
+        int32_t* PP = E + EF(dir == 0 ? BE_FP : BE_BP);
+        for (int k = 0; k < npiece; k++) PP[k] = -1;
         for (const Packer::Piece& pc : pk.pieces) PP[pc.slot] = pc.base | (pc.arr << 28);
         auto off = [&](int32_t s) -> int32_t {
           if (s == -1) return ZB;
@@ -368,8 +376,8 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
           blk[BS_RX] = dir == 0 ? off(st.rx) : ZB;
           if (dir == 0) {
             const int32_t lbh = u < uh ? lbase1 : lbase2;
-            blk[BS_LB] = st.lev_b >= 0 ? (BAND_LOUT_OFF + st.lev_b * BAND_LREC - lbh) * esz : ZB;
-            blk[BS_LX] = st.lev_x >= 0 ? (BAND_LOUT_OFF + st.lev_x * BAND_LREC - lbh) * esz : ZB;
+            blk[BS_LB] = st.lev_b >= 0 ? (LOUT_OFF + st.lev_b * BAND_LREC - lbh) * esz : ZB;
+            blk[BS_LX] = st.lev_x >= 0 ? (LOUT_OFF + st.lev_x * BAND_LREC - lbh) * esz : ZB;
             blk[BS_DX] = ZB;
           } else {
             blk[BS_LB] = st.lev_b >= 0 ? pk.off(2, st.lev_b * BAND_LREC) : ZB;
@@ -380,14 +388,14 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
               if (ev >= 0)
                 for (int i = 0; i < BAND_LREC; i++)
                   if (pk.off(2, ev * BAND_LREC + i) != pk.off(2, ev * BAND_LREC) + esz * i) return no("internal: factor record not contiguous in LDS");
-            blk[BS_DX] = (st.flags & BF_PIVOT_X) ? (BAND_DX_OFF + st.xpiv - x_lo) * esz : ZB;
+            blk[BS_DX] = (st.flags & BF_PIVOT_X) ? (DX_OFF + st.xpiv - x_lo) * esz : ZB;
           }
           for (size_t i = 0; i < st.rows.size(); i++) {
             const RowOp& ro = st.rows[i];
             int32_t* rb = blk.data() + BAND_SW + BAND_RW * i;
             rb[BR_DI] = off(ro.di); rb[BR_RR] = off(ro.rr);
             for (int s = 0; s < BAND_NB; s++) rb[BR_J0 + s] = off(ro.j[s]);
-            rb[BR_DR] = (BAND_DR_OFF + ro.r - r_lo) * esz;
+            rb[BR_DR] = (DR_OFF + ro.r - r_lo) * esz;
             if (rb[BR_DI] < 0 || rb[BR_RR] < 0) return no("internal: operand without a piece");
             for (int s = 0; s < BAND_NB; s++) if (rb[BR_J0 + s] < 0) return no("internal: operand without a piece");
           }
@@ -397,21 +405,21 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
       return true;
     };
     for (int32_t u0 = 0; u0 < nsteps;) {
-      std::vector<int32_t> E(BAND_EW, 0);
+      std::vector<int32_t> E(EW, 0);
       // every epoch but the last has exactly BAND_EPOCH steps: the kernels' step code is specialised by step number modulo
       // BAND_EPOCH (= the number of window slots), so an epoch starts at slot 0
       const int32_t cnt = std::min<int32_t>(BAND_EPOCH, nsteps - u0);
       if (!try_epoch(u0, u0 + cnt, E.data())) return no(why_not);
-      E[BE_NSTEP] = cnt;
+      E[EF(BE_NSTEP)] = cnt;
       Q.epochs.insert(Q.epochs.end(), E.begin(), E.end());
       u0 += cnt;
     }
-    Q.nepochs = (int32_t)(Q.epochs.size() / BAND_EW);
+    Q.nepochs = (int32_t)(Q.epochs.size() / EW);
     {
       int32_t fo = 0;
-      for (int32_t e = 0; e < Q.nepochs; e++) { Q.epochs[(size_t)e * BAND_EW + BE_FOFF] = fo; fo += Q.epochs[(size_t)e * BAND_EW + BE_OPLEN]; }
+      for (int32_t e = 0; e < Q.nepochs; e++) { Q.epochs[(size_t)e * EW + EF(BE_FOFF)] = fo; fo += Q.epochs[(size_t)e * EW + EF(BE_OPLEN)]; }
       int32_t bo = 0;
-      for (int32_t e = Q.nepochs - 1; e >= 0; e--) { Q.epochs[(size_t)e * BAND_EW + BE_BOFF] = bo; bo += Q.epochs[(size_t)e * BAND_EW + BE_OPLEN]; }
+      for (int32_t e = Q.nepochs - 1; e >= 0; e--) { Q.epochs[(size_t)e * EW + EF(BE_BOFF)] = bo; bo += Q.epochs[(size_t)e * EW + EF(BE_OPLEN)]; }
     }
     for (int32_t u = 0; u < nsteps; u++) Q.fops.insert(Q.fops.end(), fblocks[u].begin(), fblocks[u].end());
     // backward order: steps reversed, the rows of a step reversed

@@ -30,6 +30,11 @@ constexpr int BAND_EPOCH = 8;       // steps per epoch (one round of operand pie
                                     // slot t % 8 (five consecutive slots are live at a time), so step u of an epoch always works on the same slots
 constexpr int BAND_NS = BAND_EPOCH;
 constexpr int BAND_NPIECE = 15;     // 64-byte operand pieces per epoch and lane (BASELINE config 3 needs 15 in the forward sweep)
+constexpr int BAND_NPIECE_WIDE = 20;   // ... of the WIDE form of the program: the pattern a constrained model produces — H_c filled with the
+                                    // model's whole Hessian structure (src/CaNNOLeS.jl:256, :288-291), every Hessian position twice — needs
+                                    // 18; two spare pieces for constraint runs and -delta / rhs reads at another alignment.  The piece count
+                                    // is a property of the built program (BandPlan::npiece); everything below that depends on it is a function
+                                    // of it, and the constants without an argument describe the 15-piece program.
 constexpr int BAND_REC_MAX = 256;    // ints of step + row blocks per epoch (LDS record buffer of a wavefront)
 constexpr int BAND_LREC = 6;        // factor doubles per pivot: band multipliers, border multiplier, z  (see band.hip)
 
@@ -48,6 +53,14 @@ constexpr int BAND_DR_MAX = 24;
 constexpr int BAND_ZERO_OFF = BAND_LOUT_OFF + BAND_LOUT_MAX;         // holds 0.0: every absent operand reads it
 constexpr int BAND_LANE_DOUBLES = BAND_ZERO_OFF + 1;                 // 153: odd, so that 32 lanes reading one offset hit 32 bank pairs
 static_assert(BAND_DR_OFF + BAND_DR_MAX <= BAND_ZERO_OFF && BAND_LANE_DOUBLES % 2 == 1, "lane block layout");
+// the same for a program of npc pieces (20: out ring at 160, zero cell at 192, 193 elements per lane — odd again)
+constexpr int band_lout_off(int npc) { return npc * 8; }
+constexpr int band_dx_off(int npc) { return band_lout_off(npc); }
+constexpr int band_dr_off(int npc) { return band_dx_off(npc) + BAND_DX_MAX; }
+constexpr int band_zero_off(int npc) { return band_lout_off(npc) + BAND_LOUT_MAX; }
+constexpr int band_lane_elems(int npc) { return band_zero_off(npc) + 1; }
+static_assert(band_lout_off(BAND_NPIECE) == BAND_LOUT_OFF && band_dr_off(BAND_NPIECE) == BAND_DR_OFF && band_zero_off(BAND_NPIECE) == BAND_ZERO_OFF &&
+              band_lane_elems(BAND_NPIECE) == BAND_LANE_DOUBLES && band_lane_elems(BAND_NPIECE_WIDE) % 2 == 1, "lane block layout");
 
 // cnl_options.batch_layout = 1 (include/cannoles_hip.h): `vals` interleaved over groups of BAND_IL_GROUP problems in blocks of eight
 // doubles — element e of problem p at ((p / 32 * band_il_blocks(nnz) + e / 8) * 32 + p % 32) * 8 + e % 8.  One spare block per problem:
@@ -92,6 +105,10 @@ enum {
   BE_OPLEN,
   BAND_EW = 44
 };
+// epoch block of a program of npc pieces: the two piece lists hold npc words each, the fields behind them move up
+constexpr int band_ef(int f, int npc) { return f < BE_BP ? f : f < BE_LBASE ? f + (npc - BAND_NPIECE) : f + 2 * (npc - BAND_NPIECE); }
+constexpr int band_ew(int npc) { return (band_ef(BE_OPLEN, npc) + 1 + 3) & ~3; }
+static_assert(band_ew(BAND_NPIECE) == BAND_EW && band_ew(BAND_NPIECE_WIDE) == 52, "epoch block layout");
 // border table: BAND_BW ints per border
 enum { BB_DSRC = 0, BB_RHS, BB_DOUT, BB_SPARE, BAND_BW = 4 };
 
@@ -106,6 +123,8 @@ struct BandPart {
 struct BandPlan {
   bool ok = false;
   std::string why;            // why not, when !ok
+  bool pieces_short = false;  // !ok because an epoch needs more than npiece operand pieces (and for no other reason found before that)
+  int32_t npiece = BAND_NPIECE;   // operand pieces per epoch the program was built for: lane block and epoch block follow it
   int32_t nparts = 0;
   int32_t m0 = 0;             // part 0 pivots variables [0, m0), part 1 pivots [m0 + BAND_HW, n) downwards (nparts == 2)
   int32_t n = 0, N = 0, nnz = 0;
@@ -114,8 +133,10 @@ struct BandPlan {
 };
 
 // rows1/cols1: the reference's 1-based COO pattern (src/CaNNOLeS.jl:256-315).  Fills B (B.ok, B.why); nparts_wanted: 1 or 2;
-// esz: bytes per element of the kernel that runs the program (8: double, 4: float), the scale of its LDS byte offsets.
+// esz: bytes per element of the kernel that runs the program (8: double, 4: float), the scale of its LDS byte offsets;
+// npiece: BAND_NPIECE or BAND_NPIECE_WIDE.  The packing of the operands does not depend on npiece: a pattern that fits 15 pieces gives
+// the same steps, pieces and arithmetic in both forms, only the out ring, the zero cell and the epoch fields sit further back.
 void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ,
-                     int64_t ncon, int nparts_wanted, int esz = 8);
+                     int64_t ncon, int nparts_wanted, int esz = 8, int npiece = BAND_NPIECE);
 
 }  // namespace cnl

@@ -17,7 +17,7 @@
 // order (src/solver_types.jl:53-59: duplicates summed in COO order), then the condensed rows' products in row order, then the
 // pivots' updates as they happen.
 // Element type T (LDLFactorization{T}): double, or float for Float32 handles (cnl_create_f32).  The program is the same — steps,
-// epochs, pieces of EIGHT elements, the lane block of BAND_LANE_DOUBLES elements — with its LDS byte offsets written for
+// epochs, pieces of EIGHT elements, the lane block of band_lane_elems(NPC) elements — with its LDS byte offsets written for
 // sizeof(T) (build_band_plan's element size), so a float operand is one ds_read_b32 at an offset the generator fixed.  All
 // arithmetic is in T (fmaf, float compares, v_rcp_f32); only the control block of the two wavefronts stays double (a float
 // widens to double exactly).
@@ -38,8 +38,6 @@ __device__ __forceinline__ T* as_global(T* p) {
 typedef const __attribute__((address_space(4))) int* cptr;   // program blocks: wave-uniform, read through the scalar cache
 __device__ __forceinline__ cptr as_const(const int* p) { return (cptr)(const __attribute__((address_space(1))) int*)p; }
 
-constexpr int NPC = BAND_NPIECE;
-constexpr int LANE_D = BAND_LANE_DOUBLES;
 constexpr int EXCH_OFF = BAND_IN_OFF;   // junction exchange (46 doubles) in a lane block: over the operand pieces, idle between the sweeps
 static_assert(48 <= BAND_NPIECE * 8, "exchange area inside the operand pieces");
 
@@ -339,11 +337,19 @@ __device__ __forceinline__ void bstep(T (&xs)[NS + 1], const BOps<T>& OP, const 
 }  // namespace
 
 // LDS of a workgroup: [part][NL] lane blocks | [part] record buffers | control block: per problem [rho | flags], one word "all done"
+// NPC = operand pieces per epoch of the program the instance runs (BandPlan::npiece): 15, or 20 for the wide form (band.h) — the lane
+// block (LANE_D elements, out ring and zero cell behind the pieces), the epoch block (EW words, EF(field)), the staging registers and
+// the mover's issue / commit sequences follow it; steps, arithmetic and record format do not, so a pattern both forms can run gives
+// bit-equal outputs.
 // T = float: the element arrays of LaunchArgs (vals, rhs, d, L, rho_old, rho) hold float arrays (launch_band_f32); params are
 // Float32 values widened to double, narrowed back here exactly.
-template <class T, int NL>
-__global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(const BandDev P, const LaunchArgs Ain) {
+#define EF(F) band_ef(F, NPC)
+template <class T, int NL, int NPC>
+__global__ void __launch_bounds__(128, (NL <= 8 && NPC == BAND_NPIECE ? 2 : 1)) band_newton_kernel(const BandDev P, const LaunchArgs Ain) {
   constexpr int NI = NL / 8;
+  constexpr int LANE_D = band_lane_elems(NPC), LOUT_OFF = band_lout_off(NPC), DX_OFF = band_dx_off(NPC), DR_OFF = band_dr_off(NPC),
+                ZERO_OFF = band_zero_off(NPC), EW = band_ew(NPC);
+  static_assert(NPC == BAND_NPIECE || NPC == BAND_NPIECE_WIDE, "fifteen or twenty operand pieces");
   constexpr int ES = (int)sizeof(T), LS = ES == 8 ? 3 : 2;   // bytes per element, their log2
   static_assert(ES == 8 || ES == 4, "double or float");
   extern __shared__ double lds[];
@@ -415,7 +421,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   char* myb = wblk + (size_t)(clane ? lane : 0) * LANE_D * ES;
   const long long pv = vil ? ilg * band_il_blocks(nnz) * G8 + ilp + cpl * 8 : (long long)(prob0 + cpl) * nnz;
   const long long pr = ril ? ilg * band_il_blocks(N) * G8 + ilp + cpl * 8 : (long long)(prob0 + cpl) * N;
-  for (int t = lane; t < NL; t += 64) *reinterpret_cast<T*>(wblk + ((size_t)t * LANE_D + BAND_ZERO_OFF) * ES) = T(0);   // every block's zero cell
+  for (int t = lane; t < NL; t += 64) *reinterpret_cast<T*>(wblk + ((size_t)t * LANE_D + ZERO_OFF) * ES) = T(0);   // every block's zero cell
 
   const T tol = (T)Ain.params[0], kdec = (T)Ain.params[2], kinc = (T)Ain.params[3], klarge = (T)Ain.params[4], rho0 = (T)Ain.params[5],
           rhomax = (T)Ain.params[6], rhomin = (T)Ain.params[7];
@@ -431,7 +437,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   int4 rstg0;            // step blocks in flight (one 16-byte word per lane: 256 ints)
   int pcs[NPC];          // piece descriptors of the epoch being loaded
   static_assert(BAND_REC_MAX <= 256, "record buffer: one dwordx4 per lane");
-  // The mover is written for back-to-back issue: the fifteen piece descriptors of an epoch come with one scalar load, unused
+  // The mover is written for back-to-back issue: the NPC piece descriptors of an epoch come with one scalar load, unused
   // pieces are skipped with a wave-uniform branch (a load that hits in cache costs the CU's memory pipeline what any other costs),
   // every staged piece is written to LDS whether used or not.  One load per piece and problem group: base pointer and stride of the
   // piece's array are selected with scalar instructions, the lane's offset is problem * stride + element.  (Three guarded loads
@@ -471,15 +477,30 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
     BAND_ISSUE_DESC(EP, OFS)                                                                                                  \
     BAND_ISSUE(0) BAND_ISSUE(1) BAND_ISSUE(2) BAND_ISSUE(3) BAND_ISSUE(4) BAND_ISSUE(5) BAND_ISSUE(6) BAND_ISSUE(7)           \
     BAND_ISSUE(8) BAND_ISSUE(9) BAND_ISSUE(10) BAND_ISSUE(11) BAND_ISSUE(12) BAND_ISSUE(13) BAND_ISSUE(14)                    \
+    if constexpr (NPC > 15) { BAND_ISSUE(15) BAND_ISSUE(16) BAND_ISSUE(17) BAND_ISSUE(18) BAND_ISSUE(19) }                    \
     BAND_ISSUE_REC(OPS, OPOFF)                                                                                                \
   }
 #define BAND_COMMIT_ALL()                                                                                                     \
   {                                                                                                                           \
     BAND_COMMIT(0) BAND_COMMIT(1) BAND_COMMIT(2) BAND_COMMIT(3) BAND_COMMIT(4) BAND_COMMIT(5) BAND_COMMIT(6) BAND_COMMIT(7)   \
     BAND_COMMIT(8) BAND_COMMIT(9) BAND_COMMIT(10) BAND_COMMIT(11) BAND_COMMIT(12) BAND_COMMIT(13) BAND_COMMIT(14)             \
+    if constexpr (NPC > 15) { BAND_COMMIT(15) BAND_COMMIT(16) BAND_COMMIT(17) BAND_COMMIT(18) BAND_COMMIT(19) }               \
     reinterpret_cast<int4*>(recb)[lane] = rstg0;                                                                              \
   }
-  static_assert(NPC == 15, "fifteen operand pieces");
+  // the next epoch's loads go out in four groups behind the first four steps of the current one: 4 + 4 + 4 + 3 pieces, 5 + 5 + 5 + 5 in
+  // the wide form; the last group takes the step blocks along
+#define BAND_ISSUE_G0()                                                                                                       \
+  if constexpr (NPC > 15) { BAND_ISSUE(0) BAND_ISSUE(1) BAND_ISSUE(2) BAND_ISSUE(3) BAND_ISSUE(4) }                           \
+  else { BAND_ISSUE(0) BAND_ISSUE(1) BAND_ISSUE(2) BAND_ISSUE(3) }
+#define BAND_ISSUE_G1()                                                                                                       \
+  if constexpr (NPC > 15) { BAND_ISSUE(5) BAND_ISSUE(6) BAND_ISSUE(7) BAND_ISSUE(8) BAND_ISSUE(9) }                           \
+  else { BAND_ISSUE(4) BAND_ISSUE(5) BAND_ISSUE(6) BAND_ISSUE(7) }
+#define BAND_ISSUE_G2()                                                                                                       \
+  if constexpr (NPC > 15) { BAND_ISSUE(10) BAND_ISSUE(11) BAND_ISSUE(12) BAND_ISSUE(13) BAND_ISSUE(14) }                      \
+  else { BAND_ISSUE(8) BAND_ISSUE(9) BAND_ISSUE(10) BAND_ISSUE(11) }
+#define BAND_ISSUE_G3()                                                                                                       \
+  if constexpr (NPC > 15) { BAND_ISSUE(15) BAND_ISSUE(16) BAND_ISSUE(17) BAND_ISSUE(18) BAND_ISSUE(19) }                      \
+  else { BAND_ISSUE(12) BAND_ISSUE(13) BAND_ISSUE(14) }
 
   Win<T> W;
   int npos = 0, nzer = 0;
@@ -494,19 +515,19 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
     for (int q = 0; q < NS; q++) { W.X[q] = T(0); W.c[q] = T(0); }
     W.S55 = T(0); W.c5 = T(0);
     npos = 0; nzer = 0;
-    BAND_ISSUE_ALL(epochs, BE_FP, fops_g, 0)
+    BAND_ISSUE_ALL(epochs, EF(BE_FP), fops_g, 0)
     for (int e = 0; e < nepochs; e++) {
-      cptr E = epochs + e * BAND_EW;
+      cptr E = epochs + e * EW;
       BAND_COMMIT_ALL()
       // the next epoch's loads are issued in four groups behind the first four steps (a burst of 34 loads stalled the wavefront on
       // the CU's memory pipeline for ~2 500 cycles per epoch, in-kernel stamps), still four steps ahead of their use
       const bool more_ = e + 1 < nepochs;
-      if (more_) BAND_ISSUE_DESC(epochs + (e + 1) * BAND_EW, BE_FP)
+      if (more_) BAND_ISSUE_DESC(epochs + (e + 1) * EW, EF(BE_FP))
       // The steps of the epoch: step t works on the slots of phase t (every epoch but the last has BAND_EPOCH steps), so the eight
       // instantiations follow each other in straight-line code and the window keeps its registers from step to step.
-      const int nst = E[BE_NSTEP];
+      const int nst = E[EF(BE_NSTEP)];
       // first record element of each half of the epoch, less the out ring's offset that the program's BS_LB / BS_LX carry
-      const int recb1 = E[BE_LBASE] - BAND_LOUT_OFF, recb2 = E[BE_LBASE2] - BAND_LOUT_OFF;
+      const int recb1 = E[EF(BE_LBASE)] - LOUT_OFF, recb2 = E[EF(BE_LBASE2)] - LOUT_OFF;
       int o = 0;
       // the blocks of step t + 1 (step block + first row block) are read from the record buffer while step t computes; the step
       // reads all its operands at its top (one LDS round trip).  (A third stage — operands a step ahead — was measured: no gain,
@@ -537,7 +558,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
           char* lout = reinterpret_cast<char*>(lbase_g) + ((long long)(LB) << LS);                                          \
           T lx_[BAND_LOUT_MAX / 8][NI];                                                                                     \
           _Pragma("unroll") for (int cpc = 0; cpc < BAND_LOUT_MAX / 8; cpc++)                                               \
-            _Pragma("unroll") for (int i = 0; i < NI; i++) lx_[cpc][i] = *reinterpret_cast<const T*>(wblk + ldsb[i] + (BAND_LOUT_OFF + 8 * cpc) * ES); \
+            _Pragma("unroll") for (int i = 0; i < NI; i++) lx_[cpc][i] = *reinterpret_cast<const T*>(wblk + ldsb[i] + (LOUT_OFF + 8 * cpc) * ES); \
           _Pragma("unroll") for (int cpc = 0; cpc < BAND_LOUT_MAX / 8; cpc++)                                               \
             _Pragma("unroll") for (int i = 0; i < NI; i++)                                                                  \
               if (movok[i] && cpc * 8 + le < lc_)                                                                           \
@@ -545,14 +566,14 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
         }                                                                                                                   \
       }
       BAND_FSTEP(0)
-      if (more_) { BAND_ISSUE(0) BAND_ISSUE(1) BAND_ISSUE(2) BAND_ISSUE(3) }
+      if (more_) { BAND_ISSUE_G0() }
       BAND_FSTEP(1)
-      if (more_) { BAND_ISSUE(4) BAND_ISSUE(5) BAND_ISSUE(6) BAND_ISSUE(7) }
+      if (more_) { BAND_ISSUE_G1() }
       BAND_FSTEP(2)
-      if (more_) { BAND_ISSUE(8) BAND_ISSUE(9) BAND_ISSUE(10) BAND_ISSUE(11) }
+      if (more_) { BAND_ISSUE_G2() }
       BAND_FSTEP(3)
-      if (more_) { BAND_ISSUE(12) BAND_ISSUE(13) BAND_ISSUE(14) BAND_ISSUE_REC(fops_g, epochs[(e + 1) * BAND_EW + BE_FOFF]) }
-      BAND_LFLUSH(E[BE_LBASE], E[BE_LCNT])
+      if (more_) { BAND_ISSUE_G3() BAND_ISSUE_REC(fops_g, epochs[(e + 1) * EW + EF(BE_FOFF)]) }
+      BAND_LFLUSH(E[EF(BE_LBASE)], E[EF(BE_LCNT)])
       BAND_FSTEP(4) BAND_FSTEP(5) BAND_FSTEP(6) BAND_FSTEP(7)
       static_assert(BAND_EPOCH == 8, "eight step instantiations per epoch");
       if (nst == BAND_EPOCH) {
@@ -567,7 +588,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
 #pragma unroll
         for (int a = 0; a < 4; a++) { W.X[a] = T(0); W.c[a] = T(0); }
       }
-      BAND_LFLUSH(E[BE_LBASE2], E[BE_LCNT2])
+      BAND_LFLUSH(E[EF(BE_LBASE2)], E[EF(BE_LCNT2)])
     }
     // ================= junction + inertia rule + rho ladder (src/solver_types.jl:90-97, src/CaNNOLeS.jl:1023-1047) ==========
     int tpos = npos, tzer = nzer;
@@ -701,13 +722,13 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
     for (int i = 0; i < NI; i++) movst[i] = movok[i] && ctrl[NL + i * 8 + lq] != 0.0;
     const bool okme = valid && ctrl[NL + lane % NL] != 0.0 && clane;
     const long long pd = (long long)(prob0 + cpl) * N;
-    BAND_ISSUE_ALL(epochs + (nepochs - 1) * BAND_EW, BE_BP, bops_g, 0)
+    BAND_ISSUE_ALL(epochs + (nepochs - 1) * EW, EF(BE_BP), bops_g, 0)
     for (int e = nepochs - 1; e >= 0; e--) {
-      cptr E = epochs + e * BAND_EW;
+      cptr E = epochs + e * EW;
       BAND_COMMIT_ALL()
       const bool more_ = e > 0;
-      if (more_) BAND_ISSUE_DESC(epochs + (e - 1) * BAND_EW, BE_BP)
-      const int nst = E[BE_NSTEP];
+      if (more_) BAND_ISSUE_DESC(epochs + (e - 1) * EW, EF(BE_BP))
+      const int nst = E[EF(BE_NSTEP)];
       int o = 0;
       Rec stC, stN;
       RowRec rwC, rwN;
@@ -726,26 +747,26 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
         o = onext; stC = stN; rwC = rwN;                                                                                    \
       }
       BAND_BSTEP(7)
-      if (more_) { BAND_ISSUE(0) BAND_ISSUE(1) BAND_ISSUE(2) BAND_ISSUE(3) }
+      if (more_) { BAND_ISSUE_G0() }
       BAND_BSTEP(6)
-      if (more_) { BAND_ISSUE(4) BAND_ISSUE(5) BAND_ISSUE(6) BAND_ISSUE(7) }
+      if (more_) { BAND_ISSUE_G1() }
       BAND_BSTEP(5)
-      if (more_) { BAND_ISSUE(8) BAND_ISSUE(9) BAND_ISSUE(10) BAND_ISSUE(11) }
+      if (more_) { BAND_ISSUE_G2() }
       BAND_BSTEP(4)
-      if (more_) { BAND_ISSUE(12) BAND_ISSUE(13) BAND_ISSUE(14) BAND_ISSUE_REC(bops_g, epochs[(e - 1) * BAND_EW + BE_BOFF]) }
+      if (more_) { BAND_ISSUE_G3() BAND_ISSUE_REC(bops_g, epochs[(e - 1) * EW + EF(BE_BOFF)]) }
       BAND_BSTEP(3) BAND_BSTEP(2) BAND_BSTEP(1) BAND_BSTEP(0)
       // solution components of the epoch
-      const int xlo = E[BE_DXLO], xc = E[BE_DXCNT], rlo = E[BE_DRLO], rc = E[BE_DRCNT];
+      const int xlo = E[EF(BE_DXLO)], xc = E[EF(BE_DXCNT)], rlo = E[EF(BE_DRLO)], rc = E[EF(BE_DRCNT)];
       char* dxo = reinterpret_cast<char*>(dbase) + ((long long)xlo << LS);
       char* dro = reinterpret_cast<char*>(dbase) + ((long long)rlo << LS);
       {
         T dx_[NI], dr_[BAND_DR_MAX / 8][NI];
 #pragma unroll
-        for (int i = 0; i < NI; i++) dx_[i] = *reinterpret_cast<const T*>(wblk + ldsb[i] + BAND_DX_OFF * ES);
+        for (int i = 0; i < NI; i++) dx_[i] = *reinterpret_cast<const T*>(wblk + ldsb[i] + DX_OFF * ES);
 #pragma unroll
         for (int cpc = 0; cpc < BAND_DR_MAX / 8; cpc++)
 #pragma unroll
-          for (int i = 0; i < NI; i++) dr_[cpc][i] = *reinterpret_cast<const T*>(wblk + ldsb[i] + (BAND_DR_OFF + 8 * cpc) * ES);
+          for (int i = 0; i < NI; i++) dr_[cpc][i] = *reinterpret_cast<const T*>(wblk + ldsb[i] + (DR_OFF + 8 * cpc) * ES);
 #pragma unroll
         for (int i = 0; i < NI; i++)
           if (movst[i] && le < xc) *reinterpret_cast<T*>(dxo + ((movp[i] * (unsigned)N + (unsigned)le) << LS)) = dx_[i];
@@ -786,13 +807,24 @@ __global__ void __launch_bounds__(128, (NL <= 8 ? 2 : 1)) band_newton_kernel(con
   }
 }
 
-size_t band_lds_bytes(int nparts, int nl, int esz) {
-  return (size_t)nparts * nl * LANE_D * esz + (2 * (size_t)nl + 8) * sizeof(double) + (size_t)nparts * BAND_REC_MAX * 4;
+#undef EF
+
+// The wide instances.  LDS: a Float64 lane block is 193 * 8 = 1 544 bytes, so two parts of 32 problems take 98.8 KB (one workgroup
+// per CU), of 16 problems 49.4 KB (three); a Float32 block is 772 bytes.  Registers: stg grows by 5 * NI elements, and
+// the Float64 instance of 32 problems, which spills 43 VGPRs at 15 pieces, would spill 148 (508 bytes of scratch, reloads inside the
+// epoch loop) — it does not exist: band_wide_has(8, 32) is false and a wide Float64 handle runs 16 problems per workgroup at every
+// batch.  The 8-problem wide instances are bounded for one workgroup per SIMD pair instead of two, which keeps them out of scratch.
+bool band_wide_has(int esz, int nl) { return nl == 8 || nl == 16 || (nl == 32 && esz == 4); }
+
+size_t band_lds_bytes(int nparts, int nl, int esz, int npiece) {
+  return (size_t)nparts * nl * band_lane_elems(npiece) * esz + (2 * (size_t)nl + 8) * sizeof(double) + (size_t)nparts * BAND_REC_MAX * 4;
 }
 
 template <class T>
-static hipError_t launch_band_t(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream) {
-  const size_t ldsb = band_lds_bytes(P.nparts, nl, (int)sizeof(T));
+static hipError_t launch_band_t(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece) {
+  if (npiece != BAND_NPIECE && npiece != BAND_NPIECE_WIDE) return hipErrorInvalidConfiguration;
+  const bool wide = npiece == BAND_NPIECE_WIDE;
+  const size_t ldsb = band_lds_bytes(P.nparts, nl, (int)sizeof(T), npiece);
   const int grid = (a.batch + nl - 1) / nl;
   auto go = [&](auto kern) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)ldsb));
@@ -800,13 +832,19 @@ static hipError_t launch_band_t(const BandDev& P, int nl, const LaunchArgs& a, h
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * P.nparts), ldsb, stream, P, a);
     return hipGetLastError();
   };
-  if (nl == 32) return go(band_newton_kernel<T, 32>);
-  if (nl == 16) return go(band_newton_kernel<T, 16>);
-  if (nl == 8) return go(band_newton_kernel<T, 8>);
+  if (wide) {
+    if constexpr (sizeof(T) == 4) { if (nl == 32) return go(band_newton_kernel<T, 32, BAND_NPIECE_WIDE>); }
+    if (nl == 16) return go(band_newton_kernel<T, 16, BAND_NPIECE_WIDE>);
+    if (nl == 8) return go(band_newton_kernel<T, 8, BAND_NPIECE_WIDE>);
+    return hipErrorInvalidConfiguration;
+  }
+  if (nl == 32) return go(band_newton_kernel<T, 32, BAND_NPIECE>);
+  if (nl == 16) return go(band_newton_kernel<T, 16, BAND_NPIECE>);
+  if (nl == 8) return go(band_newton_kernel<T, 8, BAND_NPIECE>);
   return hipErrorInvalidConfiguration;
 }
 
-hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream) { return launch_band_t<double>(P, nl, a, stream); }
-hipError_t launch_band_f32(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream) { return launch_band_t<float>(P, nl, a, stream); }
+hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece) { return launch_band_t<double>(P, nl, a, stream, npiece); }
+hipError_t launch_band_f32(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece) { return launch_band_t<float>(P, nl, a, stream, npiece); }
 
 }  // namespace cnl

@@ -45,6 +45,11 @@ struct cnl_plan {
   std::vector<int32_t> band_info, band_pinfo[2];
   cnl::BandPlan band4;        // the same program for 4-byte elements (Float32 handles; cnl_plan_get "band4_*")
   std::vector<int32_t> band4_info, band4_pinfo[2];
+  // the WIDE form of the program (band.h: BAND_NPIECE_WIDE operand pieces per epoch), for 8- and 4-byte elements: built where the pattern
+  // needs more than 15 pieces — a constrained model's H_c as wide as H_F — or where tuning band_pieces = 20 asks for it
+  // (cnl_plan_get "bandw_*" / "bandw4_*"; the names above keep describing the 15-piece program)
+  cnl::BandPlan bandw, bandw4;
+  std::vector<int32_t> bandw_info, bandw_pinfo[2], bandw4_info, bandw4_pinfo[2];
 };
 
 struct cnl_handle {
@@ -126,6 +131,7 @@ struct cnl_handle {
   bool band = false;
   cnl::BandDev bd{};
   int band_nl = 16;            // problems per workgroup
+  int band_npiece = 15;        // operand pieces per epoch of the program in bd: 15, or 20 = the wide kernel instances
   bool jac_segments = false;   // the J_F and the J_c entries are one run of slots each: [jf_lo, jf_lo + jf_n), [jc_lo, jc_lo + jc_n)
   int64_t jf_lo = 0, jf_n = 0, jc_lo = 0, jc_n = 0;
   int layout = 0;              // band handles: bit 0 = vals (cnl_options.batch_layout), bit 1 = rhs interleaved over groups of 32 problems (band.h)
@@ -165,8 +171,43 @@ double* as_args(const float* p) { return reinterpret_cast<double*>(const_cast<fl
 
 // band program -> the summaries cnl_plan_get returns as "band_info" / "band_part<q>" (and "band4_...")
 void band_summary(const cnl::BandPlan& Bp, std::vector<int32_t>& info, std::vector<int32_t> (&pinfo)[2]) {
-  info = {Bp.ok ? 1 : 0, Bp.nparts, Bp.m0, Bp.n, Bp.N, Bp.nnz, (int32_t)Bp.lsize, 0};
+  // (the last word: the piece count of a wide program; 0 = the fifteen of "band_*" / "band4_*", as it always was)
+  info = {Bp.ok ? 1 : 0, Bp.nparts, Bp.m0, Bp.n, Bp.N, Bp.nnz, (int32_t)Bp.lsize, Bp.ok && Bp.npiece != cnl::BAND_NPIECE ? Bp.npiece : 0};
   for (int q = 0; q < 2; q++) pinfo[q] = {Bp.part[q].nsteps, Bp.part[q].nepochs, Bp.part[q].npiv, Bp.part[q].nevents, (int32_t)Bp.part[q].loff};
+}
+
+// The band programs of a pattern for one element size: the 15-piece program whenever the pattern fits it, word for word what it always
+// was; the wide one only where it does not fit (tuning band_pieces = 0), never (15), or also where 15 fit (20: the wide kernel
+// instances then run the handle — same steps, same arithmetic, bit-equal outputs).
+void build_band_programs(cnl::BandPlan& B15, cnl::BandPlan& Bw, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar,
+                         int64_t nequ, int64_t ncon, const cnl::Tuning& o, int esz) {
+  const int nparts = o.band_kernel == 2 ? 1 : 2;
+  cnl::build_band_plan(B15, N, nnz, rows1, cols1, nvar, nequ, ncon, nparts, esz, cnl::BAND_NPIECE);
+  Bw = cnl::BandPlan();
+  Bw.why = B15.ok ? "fifteen operand pieces per epoch suffice" : B15.why;
+  if (o.band_pieces != 15 && (B15.ok ? o.band_pieces == 20 : B15.pieces_short))
+    cnl::build_band_plan(Bw, N, nnz, rows1, cols1, nvar, nequ, ncon, nparts, esz, cnl::BAND_NPIECE_WIDE);
+}
+// the program a handle runs: the wide one where the plan has it (the pattern needs it, or tuning band_pieces = 20)
+const cnl::BandPlan& band_program(const cnl_plan* plan, bool f32) {
+  const cnl::BandPlan& w = f32 ? plan->bandw4 : plan->bandw;
+  return w.ok ? w : (f32 ? plan->band4 : plan->band);
+}
+
+// Float64 handles have the register-front kernel beside the band kernels.  On the pattern that needs the wide program it measured
+// FASTER than the wide kernel (model_band_structure(10000, 50), same machine, alternated: 8 192 problems 8.31 against 8.67 ms, 16 384
+// problems 15.78 against 17.42 ms; `vals` interleaved 8.68 / 17.2 ms — DESIGN section 4, tools/time_band_wide.py), so a Float64 handle
+// runs the wide program only where tuning band_pieces = 20 asks for it; the 15-piece program is chosen as it always was.
+// (Float32 handles have no other kernel: they always take the wide program where the pattern needs it.)
+bool band_wide_serves_f64(const cnl_plan* plan) {
+  return band_program(plan, false).npiece == cnl::BAND_NPIECE || plan->opt.band_pieces == cnl::BAND_NPIECE_WIDE;
+}
+
+void band_summaries(cnl_plan* p) {
+  band_summary(p->band, p->band_info, p->band_pinfo);
+  band_summary(p->band4, p->band4_info, p->band4_pinfo);
+  band_summary(p->bandw, p->bandw_info, p->bandw_pinfo);
+  band_summary(p->bandw4, p->bandw4_info, p->bandw4_pinfo);
 }
 
 #define HIPCHK(expr)                                                                                   \
@@ -402,10 +443,12 @@ int launch(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
     cnl::LaunchArgs b = a;
     b.L = h->d_Lband;
     b.layout = h->layout;
-    e = cnl::launch_band(h->bd, h->band_nl, b, stream);
+    e = cnl::launch_band(h->bd, h->band_nl, b, stream, h->band_npiece);
     g_launches[0]++;
-  } else if (h->layout) {
-    return fail(CNL_ERR_STATE, "this call is not served by the band kernels: a handle with batch_layout = CNL_LAYOUT_INTERLEAVED has no other");
+  } else if (h->band) {
+    // (a band handle owns the band factor records alone: the buffers of the other kernels do not exist for it)
+    return fail(CNL_ERR_STATE, "this call is not served by the band kernels, and a band handle has no other"
+                               " (no factor panels, no condensed buffer; interleaved `vals` are the band kernels' layout)");
   } else if (h->use_v2 && (a.mode != cnl::MODE_SOLVE || h->v2_solve)) {
     a.scratch = h->d_gs;
     e = cnl::launch_newton2(h->dp2, h->wpb2, h->lds2, a, stream);
@@ -998,6 +1041,8 @@ static int resolve_options(const cnl_options* in, cnl::Tuning& out) {
   tun[sizeof(in->tuning)] = 0;
   const std::string err = cnl::tuning_parse(out, tun);
   if (!err.empty()) return fail(CNL_ERR_ARG, err);
+  if (out.band_pieces != 0 && out.band_pieces != cnl::BAND_NPIECE && out.band_pieces != cnl::BAND_NPIECE_WIDE)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: band_pieces must be 0 (automatic), 15 or 20");
   return CNL_OK;
 }
 
@@ -1175,13 +1220,14 @@ static int plan_create_impl(cnl_plan** plan, int64_t N, int64_t nnz, const int64
   lap("records");
   // (round 5) large batches of band-structured problems: the sliding-window elimination with one lane per (problem, part)
   if (!latency && o.band_kernel && p->C.active && !p->D.active) {
-    cnl::build_band_plan(p->band, N, nnz, rows1, cols1, nvar, nequ, ncon, o.band_kernel == 2 ? 1 : 2);
+    build_band_programs(p->band, p->bandw, N, nnz, rows1, cols1, nvar, nequ, ncon, o, 8);
     if (verbose) fprintf(stderr, "[cnl] band program: %s%s\n", p->band.ok ? "ok" : "no: ", p->band.ok ? "" : p->band.why.c_str());
-    // the program for 4-byte elements (Float32 handles): the same blocks, every LDS offset scaled
-    if (p->band.ok) cnl::build_band_plan(p->band4, N, nnz, rows1, cols1, nvar, nequ, ncon, o.band_kernel == 2 ? 1 : 2, 4);
+    if (verbose && !p->band.ok && p->band.pieces_short)
+      fprintf(stderr, "[cnl] wide band program (%d pieces): %s%s\n", cnl::BAND_NPIECE_WIDE, p->bandw.ok ? "ok" : "no: ", p->bandw.ok ? "" : p->bandw.why.c_str());
+    // the programs for 4-byte elements (Float32 handles): the same blocks, every LDS offset scaled
+    if (p->band.ok || p->bandw.ok) build_band_programs(p->band4, p->bandw4, N, nnz, rows1, cols1, nvar, nequ, ncon, o, 4);
   }
-  band_summary(p->band, p->band_info, p->band_pinfo);
-  band_summary(p->band4, p->band4_info, p->band4_pinfo);
+  band_summaries(p);
   // Irregular sparsity: when the fill makes fronts larger than the register-front kernel takes and the condensed system is of
   // moderate order, one dense LDL^T of the whole condensed matrix beats the general multifrontal kernel by far
   // (csrc/dense.h; chosen at handle creation for small batches; CNL_NO_GDENSE=1 disables)
@@ -1259,28 +1305,28 @@ int cnl_plan_get(const cnl_plan* plan, const char* name, int32_t* out, int64_t* 
   else if (s == "stage_ptr") { src = P.stage_ptr.data(); n = (int64_t)P.stage_ptr.size(); }
   else if (s == "rec") { src = P.rec.data(); n = P.v2_ok ? (int64_t)P.rec.size() : 0; }     // record streams of the
   else if (s == "brec") { src = P.brec.data(); n = P.v2_ok ? (int64_t)P.brec.size() : 0; }  // register-front kernel
-  else if (s == "band_info") { src = plan->band_info.data(); n = (int64_t)plan->band_info.size(); }   // band program (csrc/band.h)
-  else if (s.rfind("band_", 0) == 0 && s.size() >= 6 && (s.back() == '0' || s.back() == '1')) {
-    const int q = s.back() - '0';
-    const cnl::BandPart& Q = plan->band.part[q];
-    const std::string k = s.substr(5, s.size() - 6);
-    if (k == "part") { src = plan->band_pinfo[q].data(); n = (int64_t)plan->band_pinfo[q].size(); }
-    else if (k == "fops") { src = Q.fops.data(); n = (int64_t)Q.fops.size(); }
-    else if (k == "bops") { src = Q.bops.data(); n = (int64_t)Q.bops.size(); }
-    else if (k == "epochs") { src = Q.epochs.data(); n = (int64_t)Q.epochs.size(); }
-    else if (k == "borders") { src = Q.borders.data(); n = (int64_t)Q.borders.size(); }
-    else return fail(CNL_ERR_ARG, "unknown plan array: " + s);
-  }
-  else if (s == "band4_info") { src = plan->band4_info.data(); n = (int64_t)plan->band4_info.size(); }   // ... for 4-byte elements
-  else if (s.rfind("band4_", 0) == 0 && s.size() >= 7 && (s.back() == '0' || s.back() == '1')) {
-    const int q = s.back() - '0';
-    const cnl::BandPart& Q = plan->band4.part[q];
-    const std::string k = s.substr(6, s.size() - 7);
-    if (k == "part") { src = plan->band4_pinfo[q].data(); n = (int64_t)plan->band4_pinfo[q].size(); }
-    else if (k == "fops") { src = Q.fops.data(); n = (int64_t)Q.fops.size(); }
-    else if (k == "bops") { src = Q.bops.data(); n = (int64_t)Q.bops.size(); }
-    else if (k == "epochs") { src = Q.epochs.data(); n = (int64_t)Q.epochs.size(); }
-    else if (k == "borders") { src = Q.borders.data(); n = (int64_t)Q.borders.size(); }
+  else if (s.rfind("band", 0) == 0) {
+    // band programs (csrc/band.h): "band_*" the 15-piece program, "band4_*" the same for 4-byte elements, "bandw_*" / "bandw4_*" the
+    // wide program (its piece count: info[7]); "<prefix>info", and per part q "<prefix>part<q>", "fops<q>", "bops<q>", "epochs<q>", "borders<q>"
+    struct Fam { const char* prefix; const cnl::BandPlan* B; const std::vector<int32_t>* info; const std::vector<int32_t>* pinfo; };
+    const Fam fams[4] = {{"bandw4_", &plan->bandw4, &plan->bandw4_info, plan->bandw4_pinfo}, {"bandw_", &plan->bandw, &plan->bandw_info, plan->bandw_pinfo},
+                         {"band4_", &plan->band4, &plan->band4_info, plan->band4_pinfo}, {"band_", &plan->band, &plan->band_info, plan->band_pinfo}};
+    const Fam* f = nullptr;
+    for (const Fam& c : fams) if (!f && s.rfind(c.prefix, 0) == 0) f = &c;
+    if (!f) return fail(CNL_ERR_ARG, "unknown plan array: " + s);
+    const std::string rest = s.substr(std::strlen(f->prefix));
+    if (rest == "info") { src = f->info->data(); n = (int64_t)f->info->size(); }
+    else if (!rest.empty() && (rest.back() == '0' || rest.back() == '1')) {
+      const int q = rest.back() - '0';
+      const cnl::BandPart& Q = f->B->part[q];
+      const std::string k = rest.substr(0, rest.size() - 1);
+      if (k == "part") { src = f->pinfo[q].data(); n = (int64_t)f->pinfo[q].size(); }
+      else if (k == "fops") { src = Q.fops.data(); n = (int64_t)Q.fops.size(); }
+      else if (k == "bops") { src = Q.bops.data(); n = (int64_t)Q.bops.size(); }
+      else if (k == "epochs") { src = Q.epochs.data(); n = (int64_t)Q.epochs.size(); }
+      else if (k == "borders") { src = Q.borders.data(); n = (int64_t)Q.borders.size(); }
+      else return fail(CNL_ERR_ARG, "unknown plan array: " + s);
+    }
     else return fail(CNL_ERR_ARG, "unknown plan array: " + s);
   }
   else return fail(CNL_ERR_ARG, "unknown plan array: " + s);
@@ -1500,9 +1546,11 @@ static int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* ro
   }
   if ((rc = choose_config(h))) return bail(rc);
   if ((rc = setup_v2(h))) return bail(rc);
-  if (plan->band.ok && plan->opt.band_kernel && h->use_v2 && !h->staged && h->v2_solve && h->lean && plan->P.back_rows && !plan->latency && !plan->split_mode) {
-    // band kernels for newton_system (csrc/band.h); the register-front kernel keeps try_to_factorize / solve_ldl!
-    const cnl::BandPlan& Bp = plan->band;
+  if (band_program(plan, false).ok && band_wide_serves_f64(plan) && plan->opt.band_kernel && h->use_v2 && !h->staged && h->v2_solve && h->lean && plan->P.back_rows && !plan->latency && !plan->split_mode) {
+    // band kernels for newton_system, try_to_factorize and solve_ldl! (csrc/band.h); the wide program where the plan has one
+    const cnl::BandPlan& Bp = band_program(plan, false);
+    h->band_npiece = Bp.npiece;
+    const bool wide = Bp.npiece != cnl::BAND_NPIECE;
     cnl::BandDev& bd = h->bd;
     for (int q = 0; q < Bp.nparts; q++) {
       if ((rc = upload(h, Bp.part[q].fops, &bd.fops[q]))) return bail(rc);
@@ -1514,11 +1562,15 @@ static int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* ro
     bd.nparts = Bp.nparts; bd.m0 = Bp.m0; bd.n = Bp.n; bd.N = Bp.N; bd.nnz = Bp.nnz; bd.nvar = (int32_t)nvar; bd.lsize = Bp.lsize;
     // 16 problems per workgroup (two workgroups = four wavefronts per CU: one per SIMD) up to the 8192 problems that fills; above,
     // 32 per workgroup (the LDS of a CU holds two such workgroups: 16384 problems resident) — tools/time_band.py
-    h->band_nl = plan->opt.band_problems_per_group > 0 ? plan->opt.band_problems_per_group : (batch > 8192 ? 32 : 16);
+    // (wide program, Float64: 16 at every batch — three workgroups per CU hold 48 problems where one of 32 would hold 32, and the
+    // 32-problem instance would spill; band.hip, band_wide_has)
+    h->band_nl = plan->opt.band_problems_per_group > 0 ? plan->opt.band_problems_per_group : (batch > 8192 && !wide ? 32 : 16);
     if (h->band_nl != 8 && h->band_nl != 16 && h->band_nl != 32) return bail(fail(CNL_ERR_ARG, "band_problems_per_group must be 8, 16 or 32"));
+    if (wide && !cnl::band_wide_has(8, h->band_nl))
+      return bail(fail(CNL_ERR_ARG, "band_problems_per_group = 32: the wide band program (20 operand pieces) has Float64 kernels for 8 and 16 problems per workgroup only"));
     // 32-bit byte offsets inside a workgroup's problems
     const uint64_t span = 8ull * (uint64_t)h->band_nl * (uint64_t)std::max<int64_t>({(int64_t)nnz, N, bd.lsize});
-    if (span < (1ull << 32) && cnl::band_lds_bytes(bd.nparts, h->band_nl) <= std::min<size_t>(cnl::max_lds_bytes(), 160 * 1024)) {
+    if (span < (1ull << 32) && cnl::band_lds_bytes(bd.nparts, h->band_nl, 8, h->band_npiece) <= std::min<size_t>(cnl::max_lds_bytes(), 160 * 1024)) {
       // (+ 32 problems: the band kernels interleave the records of a workgroup's problems, the last workgroup's region is a whole one)
       if ((rc = dalloc(h, &h->d_Lband, ((size_t)batch + 32) * (size_t)bd.lsize + 64))) return bail(rc);
       if (hipMemset(h->d_Lband, 0, (((size_t)batch + 32) * (size_t)bd.lsize + 64) * sizeof(double)) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipMemset failed"));
@@ -1814,7 +1866,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   if (!h || !cfg) return fail(CNL_ERR_ARG, "null argument");
   std::memset(cfg, 0, 8 * sizeof(int64_t));
   if (h->f32) {   // Float32 handle: the band kernels only
-    cfg[5] = 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->layout << 25) | ((int64_t)1 << 27);
+    cfg[5] = 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->layout << 25) | ((int64_t)1 << 27) | ((int64_t)h->band_npiece << 28);
     if (h->djt.rv_ntiles > 0) cfg[5] |= 128;
     return CNL_OK;
   }
@@ -1823,7 +1875,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   cfg[5] = (h->dense || h->gdense) ? 3 : (h->use_v2 ? (h->staged ? 4 : 2) : 1);
   if (h->lean && !h->dense && !h->gdense) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->tail) cfg[5] |= 32;                             // the remainder of the batch runs on a handle of its own (split_tail)
-  if (h->band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->layout << 25);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts
+  if (h->band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts, layout, operand pieces per epoch
   if (h->djt.rv_ntiles > 0) cfg[5] |= 128;               // row f1 runs on column tiles (kernels.h: DevJt::rv_*)
   cfg[6] = h->wpb2;
   cfg[7] = (int64_t)h->lds2;
@@ -2385,7 +2437,8 @@ static int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t
   auto bail = [&](int code) { cnl_destroy(h); return code; };
   if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
   int rc = CNL_OK;
-  const cnl::BandPlan& Bp = plan->band4;
+  const cnl::BandPlan& Bp = band_program(plan, true);   // the wide program where the plan has one
+  h->band_npiece = Bp.npiece;
   cnl::BandDev& bd = h->bd;
   for (int q = 0; q < Bp.nparts; q++) {
     if ((rc = upload(h, Bp.part[q].fops, &bd.fops[q]))) return bail(rc);
@@ -2400,7 +2453,7 @@ static int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t
   if (h->band_nl != 8 && h->band_nl != 16 && h->band_nl != 32) return bail(fail(CNL_ERR_ARG, "band_problems_per_group must be 8, 16 or 32"));
   const uint64_t span = sizeof(float) * (uint64_t)h->band_nl * (uint64_t)std::max<int64_t>({plan->nnz, plan->N, bd.lsize});
   if (span >= (1ull << 32)) return bail(fail(CNL_ERR_ARG, "cnl_create_f32: the arrays of a workgroup's problems span 4 GB or more (32-bit offsets of the band kernels)"));
-  if (cnl::band_lds_bytes(bd.nparts, h->band_nl, (int)sizeof(float)) > std::min<size_t>(cnl::max_lds_bytes(), 160 * 1024))
+  if (cnl::band_lds_bytes(bd.nparts, h->band_nl, (int)sizeof(float), h->band_npiece) > std::min<size_t>(cnl::max_lds_bytes(), 160 * 1024))
     return bail(fail(CNL_ERR_ARG, "cnl_create_f32: the band kernels' LDS does not fit a workgroup"));
   // (+ 32 problems: the records of a workgroup's problems are interleaved in one region, the last workgroup's is a whole one)
   const size_t lfloats = ((size_t)batch + 32) * (size_t)bd.lsize + 64;
@@ -2441,12 +2494,12 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
   // the throughput analysis whatever the batch: there is nothing but the band program to run
   cnl_plan* plan = nullptr;
   if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, o)) return rc;
-  if (!plan->band4.ok) {   // (the analysis builds it next to the Float64 program; not for a pattern the Float64 handles serve otherwise)
-    cnl::build_band_plan(plan->band4, N, nnz, rows1, cols1, nvar, nequ, ncon, o.band_kernel == 2 ? 1 : 2, (int)sizeof(float));
-    band_summary(plan->band4, plan->band4_info, plan->band4_pinfo);
+  if (!band_program(plan, true).ok) {   // (the analysis builds it next to the Float64 program; not for a pattern the Float64 handles serve otherwise)
+    build_band_programs(plan->band4, plan->bandw4, N, nnz, rows1, cols1, nvar, nequ, ncon, o, (int)sizeof(float));
+    band_summaries(plan);
   }
-  if (!plan->band4.ok) {
-    const std::string why = plan->band4.why;
+  if (!band_program(plan, true).ok) {
+    const std::string why = plan->bandw4.why.empty() ? plan->band4.why : plan->bandw4.why;
     cnl_plan_destroy(plan);
     return fail(CNL_ERR_ARG, "cnl_create_f32: the pattern is not served by the band kernels (build_band_plan: " + why +
                                  "); Float32 stays on the CPU backend for it");
@@ -2460,7 +2513,7 @@ static int launch_f32(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
   a.L = as_args(h->f_Lband);
   a.layout = h->layout;
   if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
-  const hipError_t e = cnl::launch_band_f32(h->bd, h->band_nl, a, stream);
+  const hipError_t e = cnl::launch_band_f32(h->bd, h->band_nl, a, stream, h->band_npiece);
   g_launches[0]++;
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("band kernel launch (Float32): ") + hipGetErrorString(e));
   if (h->timing) {

@@ -175,11 +175,13 @@ struct BandDev {
 };
 // newton_system! / try_to_factorize of a.batch problems on the band kernels, nl problems per workgroup (8, 16 or 32); a.L = the
 // band factor storage [batch][P.lsize]
-hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream);
+// npiece: operand pieces per epoch of the program P was uploaded from (BandPlan::npiece): 15, or 20 = the wide kernel instances
+hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece = 15);
 // the same on Float32 data: a.vals / rhs / d / L / rho_old / rho hold float arrays (stored through the double* fields), a.params the
 // Float32 parameters widened to double; P is the 4-byte program (build_band_plan with esz = 4), P.lsize counts floats
-hipError_t launch_band_f32(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream);
-size_t band_lds_bytes(int nparts, int nl, int esz = 8);   // esz: bytes per element (8 double, 4 float)
+hipError_t launch_band_f32(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece = 15);
+bool band_wide_has(int esz, int nl);   // is there a wide (20-piece) instance for this element size and problems per workgroup?
+size_t band_lds_bytes(int nparts, int nl, int esz = 8, int npiece = 15);   // esz: bytes per element (8 double, 4 float); npiece: of the program
 
 // returns hipSuccess or the launch error
 hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream);

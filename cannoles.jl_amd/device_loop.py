@@ -157,7 +157,7 @@ PROFILE = False   # tools/time_device_loop.py --profile: wall time per section o
 
 
 def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=None, rtol=None, Fatol=None, Frtol=None, delta_dec=0.1,
-                       device_index=0, layout="auto"):
+                       device_index=0, layout="auto", tuning=None):
     """All B problems of `fam` in lockstep on the device.  Returns a dict of numpy arrays: solution [B, n], multipliers,
     status (list of strings), iter, nfact, nlinsolve, nbk, objective, and `steps` (global steps = batched Newton rounds).
 
@@ -182,17 +182,21 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     P = max(p, 1)
     rows, cols, (nnzhF, nnzhc, nnzjF, nnzjc) = kkt_pattern_of(fam)
     nnz = len(rows)
+    # tuning: further hipldl.Options fields for the handle — e.g. {"band_pieces": 20}: a constrained family's pattern (H_c as wide as H_F)
+    # on the wide band kernels, which a Float64 handle takes on request only
+    tuning = dict(tuning or {})
     # `vals` interleaved over groups of 32 problems where the band kernels serve the batch (cnl_options.batch_layout, round 6): row f2
     # writes that layout, newton_system reads it; rows f1 / f4 read the Jacobian values from the model's arrays, whatever the layout
     L = None
     if layout in ("auto", "interleaved"):
         try:
-            L = hipldl.HIPLDLStruct(N, rows, cols, None, n, m, p, batch=B, device=device_index, options=hipldl.Options(batch_layout=hipldl.LAYOUT_INTERLEAVED))
+            L = hipldl.HIPLDLStruct(N, rows, cols, None, n, m, p, batch=B, device=device_index,
+                                    options=hipldl.Options(batch_layout=hipldl.LAYOUT_INTERLEAVED, **tuning))
         except hipldl.CnlError:
             if layout == "interleaved":
                 raise
     if L is None:
-        L = hipldl.HIPLDLStruct(N, rows, cols, None, n, m, p, batch=B, device=device_index)
+        L = hipldl.HIPLDLStruct(N, rows, cols, None, n, m, p, batch=B, device=device_index, options=hipldl.Options(**tuning) if tuning else None)
     lib = hipldl.lib()
     f64 = dict(dtype=t.float64, device=dev)
     Z = lambda *sh: t.zeros(sh, **f64)
@@ -387,7 +391,7 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     names = {UNKNOWN: "unknown", FIRST: "first_order", SMALL: "small_residual", EXC: "exception", TIRED: "max_eval", STALL: "stalled"}
     out = {"solution": x.cpu().numpy(), "multipliers": lam[:, :p].cpu().numpy(), "status": [names[int(v)] for v in status.cpu().numpy()],
            "iter": it.cpu().numpy(), "nfact": nfact.cpu().numpy(), "nlinsolve": nlin.cpu().numpy(), "nbk": nbk.cpu().numpy(),
-           "objective": fx.cpu().numpy(), "steps": steps, "kernel": L.config["kernel"], "vals_layout": "interleaved" if L.config.get("batch_layout") else "problem-major",
+           "objective": fx.cpu().numpy(), "steps": steps, "kernel": "band" if L.config.get("band") else L.config["kernel"], "vals_layout": "interleaved" if L.config.get("batch_layout") else "problem-major",
            "loop_seconds": loop_seconds}   # the global steps alone (the symbolic analysis of the pattern and the start-up evaluations are not in it)
     if prof is not None:
         out["profile_ms_per_step"] = {k: 1e3 * v / max(steps, 1) for k, v in prof.items()}

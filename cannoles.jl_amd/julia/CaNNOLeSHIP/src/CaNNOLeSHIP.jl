@@ -100,7 +100,9 @@ function newton_system!(f::HIPFactor, vals::Vector{Float64}, rhs::Vector{Float64
   return f.success[] != 0, f.rho[], f.rho_out[], Int(f.nfact[])
 end
 
-# ---- Float32 (LDLFactorization{Float32}) for direct batched callers: band-structured patterns only, on the band kernels
+# ---- Float32 (LDLFactorization{Float32}) for direct batched callers: band-structured patterns only, on the band kernels —
+# unconstrained models and constrained ones alike: the pattern CaNNOLeS builds with constraints (H_c filled with hess_structure(nls),
+# every Hessian position twice) is served by the wide form of the band program
 # (include/cannoles_hip.h, `_f32` entry points).  `HIPFactor` above stays the Float64 factor the extension uses. ---------------
 
 """

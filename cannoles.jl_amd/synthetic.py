@@ -161,6 +161,35 @@ def band_values(s, seed, delta=0.1, stress=None):
     return vals, rhs
 
 
+def model_band_structure(n, p, name="band-model", hw=2):
+    """band_structure as a constrained MODEL hands it over: the reference fills the H_c segment with hess_structure(nls), the
+    model's whole Hessian structure (src/CaNNOLeS.jl:256, :288-291), so H_c is a band as wide as H_F and every Hessian
+    position appears twice.  Entry for entry the pattern of device_loop.kkt_pattern_of; p = 0: band_structure itself."""
+    s = band_structure(n, p, name=name, hw=hw)
+    if p == 0:
+        return s
+    return Structure(s.nvar, s.nequ, s.ncon, s.hF, s.hF, s.jF, s.jc, name=name, meta=dict(s.meta, hw=hw))
+
+
+def model_band_values(s, seed, delta=0.1, stress=None):
+    """Values for one problem of model_band_structure: what band_values gives for the band_structure twin (same seed, same
+    numbers, the H_c diagonal as band_values makes it) with small entries on the off-diagonal H_c positions (none under
+    "ladder", whose H_c is zero)."""
+    if s.ncon == 0:
+        return band_values(s, seed, delta=delta, stress=stress)
+    twin = band_structure(s.nvar, s.ncon, hw=s.meta["hw"])
+    v0, rhs = band_values(twin, seed, delta=delta, stress=stress)
+    o0, o1 = twin.offsets(), s.offsets()
+    vals = np.zeros(s.nnzNS)
+    vals[o1[0]:o1[1]] = v0[o0[0]:o0[1]]
+    r, c = np.asarray(s.hc[0]), np.asarray(s.hc[1])
+    rng = np.random.default_rng([seed, 1])   # a stream of its own: band_values' draws stay what they are
+    hcv = np.where(r == c, v0[o0[1]:o0[2]][c - 1], 0.0 if stress == "ladder" else rng.uniform(-0.01, 0.01, len(r)))
+    vals[o1[1]:o1[2]] = hcv
+    vals[o1[2]:] = v0[o0[2]:]
+    return vals, rhs
+
+
 def dense_structure(n, m, name="dense"):
     """cfg2: unconstrained, J_F dense m x n in column-major COO, H_F diagonal."""
     jr = np.tile(np.arange(1, m + 1), n)

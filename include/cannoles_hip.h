@@ -96,7 +96,13 @@ typedef struct cnl_options {
                                   operands streamed through LDS) — newton_system, try_to_factorize (the forward sweep alone) and
                                   solve_ldl! (which factorises the values of the last factorisation again and sweeps the new
                                   right-hand side in the same launch); 2: the same with the chain in one part; 0: the register-front
-                                  kernel                                                                                        */
+                                  kernel.  The band program moves its operands in 15 pieces of eight elements per epoch; the pattern
+                                  of a CONSTRAINED model, whose H_c segment has the model's whole Hessian structure (every Hessian
+                                  position twice), needs up to 18 and gets the WIDE form of the program and of the kernels (20
+                                  pieces).  Float32 handles take it automatically; Float64 handles keep the register-front kernel
+                                  for such a pattern, which measured faster, unless tuning "band_pieces=20" asks for the wide form
+                                  ("band_pieces=15": never build it; 20 on a pattern 15 pieces serve: the wide kernels, bit-equal
+                                  outputs).  cnl_get_config reports the piece count                                              */
   int32_t dense_backend;       /* 1: dense residual blocks (BASELINE config 2) go to the dense backend (fp64 MFMA)              */
   int32_t staged;              /* 1: latency plans run stage by stage (tasks of the elimination tree on different wavefronts)   */
   int32_t dataflow;            /* 1: smallest batches run all tasks in one launch per phase, waiting on device counters         */
@@ -344,7 +350,9 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  * kernel (kernels2.hip) serves newton_system/factorize (4: with staged execution of the first attempt), 3 dense backend, else 1;
  * + 16 when newton_system / factorize run the LEAN instantiation (fast-class fronts with row-form products only), [6]=its wavefronts per workgroup,
  * [7]=its LDS bytes per workgroup; [5] + 32 when the remainder of the batch runs on a handle of its own (cnl_options.split_tail),
- * + 64 when cnl_newton_system runs on the band kernels (then bits 8-15 = problems per workgroup, bits 16-23 = parts of the chain),
+ * + 64 when cnl_newton_system runs on the band kernels (then bits 8-15 = problems per workgroup, bits 16-23 = parts of the chain,
+ *   bits 25-26 = cnl_options.batch_layout / rhs interleaved, bits 28-33 = operand pieces per epoch of the band program: 15, or 20
+ *   for the wide form),
  * + 128 when cnl_residual_vectors_dev runs on column tiles. */
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
 /* ([5] + (1 << 27) on a Float32 handle, which runs the band kernels only: bits 7-26 as above, cfg[0..4], [6], [7] are 0.) */
@@ -361,6 +369,8 @@ int cnl_launch_counts(int64_t counts[3]);
  * 1 included), and the device-resident passes around it (rows f1 / f2 / f4 and the trial point, `_f32_dev` below).
  * cnl_create_f32 / cnl_create_f32_ex take the arguments of cnl_create / cnl_create_ex and fail with CNL_ERR_ARG
  * (cnl_last_error names the reason) when the pattern is not a band or cnl_options.band_kernel = 0: the caller stays on the CPU.
+ * Accepted: the band patterns of cnl_options.band_kernel, the pattern of a constrained model included (H_c with the model's whole
+ * Hessian structure: the wide form of the band program, csrc/band.h) — half-widths up to 2, one live multiplier at a time.
  * The semantics of every call are those of its Float64 twin above.  Mixing element types is CNL_ERR_STATE and does nothing:
  * a Float64 entry point on a Float32 handle (cnl_factorize..., the row f1 / f2 / f4 / trial-point passes, cnl_interleave_dev...)
  * and an `_f32` entry point on a Float64 handle.  cnl_layout_len counts elements, so it serves both types.

@@ -1,0 +1,224 @@
+"""The wide form of the band program (csrc/band.h: BAND_NPIECE_WIDE operand pieces per epoch) without a GPU.
+
+A constrained model hands over a KKT pattern whose H_c segment has the model's whole Hessian structure
+(the reference's src/CaNNOLeS.jl:256, :288-291): for a band model every Hessian position appears twice, and an epoch of the band
+program needs up to 18 operand pieces where 15 is what the program always had.  The generator writes a second, wide form for such
+patterns (cnl_plan_get "bandw_*"); tests/support/band_sim_wide.py executes it — the piece count taken from the program — and the
+result is compared with the oracle exactly as tests/test_band_cpu.py compares the 15-piece program."""
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+import cannoles_jl_amd  # noqa: F401
+from cannoles_jl_amd import device_loop, hipldl, synthetic as syn
+from oracle import oracle as O
+from tests.support.band_sim import BandSim
+from tests.support.band_sim_wide import BandSimWide
+from tests.test_float32_cpu import _offset_mask
+
+MODEL_SHAPES = [(300, 4, 2), (1000, 10, 2), (10000, 50, 2), (360, 6, 1), (1000, 8, 2), (1000, 100, 2), (1000, 250, 2), (997, 1, 2)]
+# half-width 1 has one off-diagonal position per variable: even with every Hessian position twice its epochs fit fifteen pieces, so the
+# 15-piece program serves (360, 6, 1) as it always did, and the wide form is built for it on request only (band_pieces = 20)
+NEEDS_WIDE = [sh for sh in MODEL_SHAPES if sh[2] == 2]
+PARTS = ("part", "fops", "bops", "epochs", "borders")
+
+
+def _plan(s, **opt):
+    rows, cols = s.kkt_pattern()
+    return hipldl.Plan(s.N, rows, cols, s.nvar, s.nequ, s.ncon, options=hipldl.Options(plan_kind=hipldl.PLAN_THROUGHPUT, **opt)), rows, cols
+
+
+def _model_structure(n, p, hw):
+    # (997, 1): band_structure wants p to divide n, and one constraint over all variables does
+    return syn.model_band_structure(n, p, hw=hw)
+
+
+def _check(s, vals, rhs, params, rho_old=0.0, **opt):
+    """tests/test_band_cpu.py's _check, on the wide program"""
+    pl, rows, cols = _plan(s, **opt)
+    sim = BandSimWide(pl)
+    assert sim.ok, "the pattern is a band that needs the wide form: the generator must write it"
+    B = vals.shape[0]
+    v = vals.copy()
+    d, ok, rho, ro, nf = sim.newton_system(v, rhs, s.nvar, rho_old, params)
+    orc = O.Oracle(s.N, rows, cols, O.canonical_perm(s.nvar, s.nequ, s.ncon))
+    v0 = vals.copy()
+    d0, ok0, rho0, ro0, nf0 = O.newton_system_batch(orc, B, s.nvar, s.nequ, s.ncon, rhs, v0, np.full(B, float(rho_old)), params)
+    assert np.array_equal(ok, ok0) and np.array_equal(nf, nf0) and np.array_equal(rho, rho0) and np.array_equal(ro, ro0)
+    assert np.array_equal(v[:, -s.nvar:], v0[:, -s.nvar:])   # rho slots left as the reference leaves them
+    for b in range(B):
+        if ok0[b]:
+            assert np.abs(d[b] - d0[b]).max() <= 1e-11 * np.abs(d0[b]).max()
+    return sim, (ok0, nf0, rho0)
+
+
+@pytest.mark.parametrize("n,p,hw", MODEL_SHAPES)
+def test_model_band_structure_is_the_pattern_a_model_hands_over(n, p, hw):
+    """model_band_structure: band_structure with hc = hF — entry for entry what device_loop.kkt_pattern_of (and outer_loop.solve)
+    build from a model on band_structure; band_structure itself keeps its diagonal H_c"""
+    s = _model_structure(n, p, hw)
+    base = syn.band_structure(n, p, hw=hw)
+    rows, cols = s.kkt_pattern()
+    r0, c0, seg = device_loop.kkt_pattern_of(SimpleNamespace(s=base))
+    assert rows.dtype == r0.dtype and np.array_equal(rows, r0) and np.array_equal(cols, c0)
+    assert seg == (s.nnzhF, s.nnzhc, s.nnzjF, s.nnzjc) and s.nnzhc == s.nnzhF
+    assert base.nnzhc == n and len(rows) == len(base.kkt_pattern()[0]) + s.nnzhF - n
+
+
+def test_model_band_values_extend_band_values():
+    """the value generator keeps band_values' numbers (same seed) and adds small off-diagonal H_c entries; ladder: H_c = 0"""
+    s, base = syn.model_band_structure(300, 4), syn.band_structure(300, 4)
+    for stress in (None, "ladder", "illcond"):
+        v, r = syn.model_band_values(s, 4001, stress=stress)
+        v0, r0 = syn.band_values(base, 4001, stress=stress)
+        o, o0 = s.offsets(), base.offsets()
+        assert np.array_equal(r, r0) and np.array_equal(v[o[0]:o[1]], v0[o0[0]:o0[1]]) and np.array_equal(v[o[2]:], v0[o0[2]:])
+        hr, hc = np.asarray(s.hc[0]), np.asarray(s.hc[1])
+        hcv = v[o[1]:o[2]]
+        assert np.array_equal(hcv[hr == hc], v0[o0[1]:o0[2]])
+        off = hcv[hr != hc]
+        assert (np.abs(off) <= 0.01).all() and (off.any() if stress != "ladder" else not off.any())
+
+
+@pytest.mark.parametrize("n,p,hw", NEEDS_WIDE)
+def test_model_shaped_patterns_get_the_wide_program(built, n, p, hw):
+    """the 15-piece names keep saying "no band" (tests/support/band_sim.py hard-codes fifteen), the wide program exists, holds at most
+    twenty pieces and at least one epoch uses more than fifteen; band_pieces = 15 is the behaviour before the wide form"""
+    s = _model_structure(n, p, hw)
+    pl, _, _ = _plan(s)
+    assert pl.array("band_info")[0] == 0 and pl.array("band4_info")[0] == 0
+    iw, iw4 = pl.array("bandw_info"), pl.array("bandw4_info")
+    assert iw[0] == 1 and np.array_equal(iw, iw4)
+    assert 15 < iw[7] <= 20
+    sim = BandSimWide(pl)
+    assert 15 < sim.pieces_used() <= sim.NPIECE == iw[7]
+    assert not BandSim(pl).ok
+    p15, _, _ = _plan(s, band_pieces=15)
+    assert p15.array("band_info")[0] == 0 and p15.array("bandw_info")[0] == 0 and p15.array("bandw4_info")[0] == 0
+
+
+def test_model_shaped_half_width_one_keeps_the_fifteen_piece_program(built):
+    """the 15-piece program whenever the pattern fits it; the wide form of the same pattern on request"""
+    s = _model_structure(360, 6, 1)
+    pl, _, _ = _plan(s)
+    assert pl.array("band_info")[0] == 1 and pl.array("bandw_info")[0] == 0
+    assert BandSimWide(pl, prefix="band").pieces_used() <= 15
+    pw, _, _ = _plan(s, band_pieces=20)
+    assert pw.array("band_info")[0] == 1 and pw.array("bandw_info")[0] == 1 and pw.array("bandw_info")[7] == 20
+    for q in range(2):
+        assert np.array_equal(pl.array(f"band_fops{q}"), pw.array(f"band_fops{q}"))
+
+
+def test_half_width_three_is_refused_in_both_forms(built):
+    for s in (syn.band_structure(200, 4, hw=3), syn.model_band_structure(200, 4, hw=3)):
+        for opt in ({}, {"band_pieces": 20}):
+            pl, _, _ = _plan(s, **opt)
+            assert pl.array("band_info")[0] == 0 and pl.array("bandw_info")[0] == 0
+
+
+def test_band_pieces_takes_0_15_20_only(built):
+    s = syn.band_structure(200, 4)
+    rows, cols = s.kkt_pattern()
+    for bad in ("band_pieces=18", "band_pieces=-1", "band_pieces=21"):
+        with pytest.raises(hipldl.CnlError) as e:
+            hipldl.Plan(s.N, rows, cols, s.nvar, s.nequ, s.ncon, batch=4, options=hipldl.Options(tuning=bad))
+        assert e.value.code == 1
+
+
+@pytest.mark.parametrize("n,p,hw,kernel", [(300, 4, 2, 1), (300, 4, 2, 2), (360, 6, 1, 1), (360, 6, 1, 2), (1000, 10, 2, 1), (1000, 10, 2, 2)])
+def test_wide_program_reproduces_the_oracle(built, params, n, p, hw, kernel):
+    """the wide program, interpreted on the CPU, against the oracle: two parts and one, half-widths 1 and 2"""
+    s = syn.model_band_structure(n, p, hw=hw)
+    vals, rhs = syn.batch_values(s, 3, cfg=4, gen=syn.model_band_values)
+    sim, (ok0, nf0, _) = _check(s, vals, rhs, params, band_kernel=kernel, **({"band_pieces": 20} if hw == 1 else {}))
+    assert sim.nparts == (1 if kernel == 2 else 2)
+    assert ok0.all() and (nf0 == 1).all()
+
+
+def test_wide_program_ladder_and_hopeless(built, params):
+    """the ladder problems climb to rho = 605.5 with six factorisations, as on the synthetic pattern; a problem no rho rescues gives up
+    with rho > rho_max and leaves rho_old alone (src/CaNNOLeS.jl:1036-1047)"""
+    s = syn.model_band_structure(300, 4)
+    gen = [syn.model_band_values(s, 5000 + b, stress="ladder") for b in range(3)]
+    vals, rhs = np.stack([g[0] for g in gen]), np.stack([g[1] for g in gen])
+    vals[2, s.offsets()[0]] = -1e300   # hopeless
+    for rho_old in (0.0, 0.3):
+        _, (ok0, nf0, rho0) = _check(s, vals, rhs, params, rho_old=rho_old)
+        assert ok0[:2].all() and not ok0[2]
+        if rho_old == 0.0:
+            assert (nf0[:2] == 6).all() and np.allclose(rho0[:2], 605.5454452393343, rtol=1e-12)
+
+
+def test_wide_program_full_size(built, params):
+    """the model-shaped twin of BASELINE config 3 (n = nequ = 1e4, ncon = 50): two parts of 5 002 steps"""
+    s = syn.model_band_structure(10000, 50)
+    vals, rhs = syn.batch_values(s, 2, cfg=3, gen=syn.model_band_values)
+    sim, _ = _check(s, vals, rhs, params)
+    assert sim.nparts == 2 and sim.parts[0]["nsteps"] == sim.parts[1]["nsteps"] == 5002
+    assert sim.lsize * 8 < 0.5e6
+
+
+def test_wide_form_of_a_fifteen_piece_pattern_is_bit_equal(built, params):
+    """band_pieces = 20 on a pattern fifteen pieces serve: same steps, same pieces, same arithmetic — every output of the wide
+    interpreter on the wide program equals BandSim's on the 15-piece program bit for bit (the property the GPU test of the wide
+    kernel instances rests on)"""
+    s = syn.band_structure(1000, 10)
+    pl, _, _ = _plan(s, band_pieces=20)
+    assert pl.array("band_info")[0] == 1 and pl.array("bandw_info")[0] == 1 and pl.array("bandw_info")[7] == 20
+    narrow, wide = BandSim(pl), BandSimWide(pl)
+    assert wide.pieces_used() <= 15
+    gen = [syn.band_values(s, 4000 + b) for b in range(2)] + [syn.band_values(s, 5000 + b, stress="ladder") for b in range(2)]
+    vals, rhs = np.stack([g[0] for g in gen]), np.stack([g[1] for g in gen])
+    v1, v2 = vals.copy(), vals.copy()
+    out1 = narrow.newton_system(v1, rhs, s.nvar, 0.0, params)
+    out2 = wide.newton_system(v2, rhs, s.nvar, 0.0, params)
+    assert (out1[4] == [1, 1, 6, 6]).all()
+    for a, b in zip(out1, out2):
+        assert np.array_equal(a, b)
+    assert np.array_equal(v1, v2)
+    # ... and the 15-piece program through the wide interpreter: the interpreters agree on common ground
+    out3 = BandSimWide(pl, prefix="band").newton_system(vals.copy(), rhs, s.nvar, 0.0, params)
+    for a, b in zip(out1, out3):
+        assert np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("shape,opt", [((1000, 10, 2), {}), ((360, 6, 1), {"band_pieces": 20}), ((10000, 50, 2), {}), ((1000, 10, 2), {"band_kernel": 2})])
+def test_wide_four_byte_program_is_the_eight_byte_one_with_halved_offsets(built, shape, opt):
+    """the rule of tests/test_float32_cpu.py for the wide program"""
+    n, p, hw = shape
+    pl, _, _ = _plan(syn.model_band_structure(n, p, hw=hw), **opt)
+    info8, info4 = pl.array("bandw_info"), pl.array("bandw4_info")
+    assert info8[0] == 1 and np.array_equal(info8, info4)
+    nparts = int(info8[1])
+    assert nparts == (1 if opt.get("band_kernel") == 2 else 2)
+    checked = 0
+    for q in range(nparts):
+        part8, part4 = pl.array(f"bandw_part{q}"), pl.array(f"bandw4_part{q}")
+        assert np.array_equal(part8, part4)
+        for k in ("epochs", "borders"):
+            assert np.array_equal(pl.array(f"bandw_{k}{q}"), pl.array(f"bandw4_{k}{q}"))
+        for k in ("fops", "bops"):
+            a8, a4 = pl.array(f"bandw_{k}{q}"), pl.array(f"bandw4_{k}{q}")
+            assert a8.shape == a4.shape
+            mask, used = _offset_mask(a8, int(part8[0]))
+            assert np.array_equal(a8[~mask], a4[~mask])
+            off8, off4 = a8[mask], a4[mask]
+            assert (off8 % 8 == 0).all() and (off8 >= 0).all() and off8.max() <= 192 * 8
+            assert np.array_equal(off8 // 2, off4)
+            checked += int(mask.sum())
+    assert checked > 0
+
+
+@pytest.mark.parametrize("n,p,hw", [(10000, 50, 2), (1000, 10, 2), (200, 0, 2), (360, 6, 1)])
+def test_fifteen_piece_programs_are_unchanged_by_default(built, n, p, hw):
+    """default options on a pattern fifteen pieces serve: the program of band_pieces = 15, word for word, and no wide program"""
+    s = syn.band_structure(n, p, hw=hw)
+    a, _, _ = _plan(s)
+    b, _, _ = _plan(s, band_pieces=15)
+    assert a.array("band_info")[0] == 1 and a.array("bandw_info")[0] == 0 and a.array("bandw4_info")[0] == 0
+    for fam in ("band", "band4"):
+        assert np.array_equal(a.array(f"{fam}_info"), b.array(f"{fam}_info"))
+        for q in range(int(a.array("band_info")[1])):
+            for k in PARTS:
+                assert np.array_equal(a.array(f"{fam}_{k}{q}"), b.array(f"{fam}_{k}{q}"))
