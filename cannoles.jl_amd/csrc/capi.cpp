@@ -1,8 +1,9 @@
 // capi.cpp — the C ABI declared in include/cannoles_hip.h.
 //
 // Host-side driver: owns the symbolic plan, uploads it once, chooses the kernel
-// configuration for the front sizes at hand, stages host buffers for the
-// host-pointer entry points and launches the fused kernel (kernels.hip).
+// backend for the handle (band kernels, register-front / general multifrontal
+// kernels, dense), stages host buffers for the host-pointer entry points and
+// launches the kernels.  Band handles of both element types run through run_band.
 // There is no CPU execution path: every numeric entry point needs the device.
 #include <hip/hip_runtime_api.h>
 
@@ -41,16 +42,18 @@ struct cnl_plan {
   cnl::Tuning opt{};          // the switches the plan was built with (options.h; the handle reads its execution switches from here)
   std::atomic<int> refs{1};   // handles of a cnl_multi share one analysis (read-only after creation)
   bool split_mode = false;    // bidirectional-chain plan for a batch between one and two wavefronts per SIMD (capi.cpp, run_split)
-  cnl::BandPlan band;         // (round 5) band program of a throughput plan (csrc/band.h); band.ok == false: the pattern is no band
-  std::vector<int32_t> band_info, band_pinfo[2];
-  cnl::BandPlan band4;        // the same program for 4-byte elements (Float32 handles; cnl_plan_get "band4_*")
-  std::vector<int32_t> band4_info, band4_pinfo[2];
-  // the WIDE form of the program (band.h: BAND_NPIECE_WIDE operand pieces per epoch), for 8- and 4-byte elements: built where the pattern
-  // needs more than 15 pieces — a constrained model's H_c as wide as H_F — or where tuning band_pieces = 20 asks for it
-  // (cnl_plan_get "bandw_*" / "bandw4_*"; the names above keep describing the 15-piece program)
-  cnl::BandPlan bandw, bandw4;
-  std::vector<int32_t> bandw_info, bandw_pinfo[2], bandw4_info, bandw4_pinfo[2];
+  // (round 5) band programs of a throughput plan (csrc/band.h), [f32][wide]: for 8-byte (Float64 handles) and 4-byte elements
+  // (Float32 handles), each in the 15-piece form and in the WIDE form (band.h: BAND_NPIECE_WIDE operand pieces per epoch), which is
+  // built where the pattern needs more than 15 pieces — a constrained model's H_c as wide as H_F — or where tuning band_pieces = 20
+  // asks for it.  B.ok == false: the pattern is no band (of that form).  info / pinfo: the summaries cnl_plan_get returns.
+  struct BandSlot {
+    cnl::BandPlan B;
+    std::vector<int32_t> info, pinfo[2];
+  };
+  BandSlot band_prog[2][2];
 };
+// the names cnl_plan_get answers for band_prog[f32][wide]: "band_*" / "band4_*" keep describing the 15-piece program
+static const char* const kBandPrefix[2][2] = {{"band_", "bandw_"}, {"band4_", "bandw4_"}};
 
 struct cnl_handle {
   cnl_plan* plan = nullptr;
@@ -126,7 +129,7 @@ struct cnl_handle {
   cnl::DenseState* dense = nullptr;
   cnl::DenseState* gdense = nullptr;  // dense treatment of an arbitrary condensed system (irregular sparsity, small batch)
   cnl::GeneralOps gops{};
-  double* d_cgls_ws = nullptr;  // [batch][2 * nvar] workspace of cnl_cgls_multipliers_dev, allocated on first use
+  void* cgls_ws = nullptr;    // [batch][2 * nvar] elements: workspace of cnl_cgls_multipliers_dev / _f32_dev, allocated on first use
   // (round 5) band kernels (csrc/band.h): newton_system of a throughput handle whose pattern is a band
   bool band = false;
   cnl::BandDev bd{};
@@ -135,15 +138,13 @@ struct cnl_handle {
   bool jac_segments = false;   // the J_F and the J_c entries are one run of slots each: [jf_lo, jf_lo + jf_n), [jc_lo, jc_lo + jc_n)
   int64_t jf_lo = 0, jf_n = 0, jc_lo = 0, jc_n = 0;
   int layout = 0;              // band handles: bit 0 = vals (cnl_options.batch_layout), bit 1 = rhs interleaved over groups of 32 problems (band.h)
-  double* d_Lband = nullptr;   // [batch][bd.lsize] factor records of the band kernels
-  // Float32 handle (cnl_create_f32): the band kernels on float data, bd = the 4-byte program (plan->band4), and the row lists of rows
-  // f1 / f4 (djt, jac_segments); nothing else of the handle's device state exists, and every Float64 entry point refuses it (CNL_ERR_STATE)
+  void* d_Lband = nullptr;     // [batch + 32][bd.lsize] factor records of the band kernels, in the handle's element type
+  // Float32 handle (cnl_create_f32): the band kernels on float data, bd = the 4-byte program, and the row lists of rows f1 / f4 (djt,
+  // jac_segments); nothing else of the handle's device state exists, and every Float64 entry point refuses it (CNL_ERR_STATE).
+  // last_vals holds its float array of the last factorisation (as_args; the band solve factorises those values again).
   bool f32 = false;
-  float* f_Lband = nullptr;    // [batch + 32][bd.lsize] float factor records
-  const float* f_last_vals = nullptr;   // vals of the last factorisation (the band solve factorises them again)
-  // staging of the host-pointer calls: vals, rhs, d, and [rho | rho_old | nfact | success] as one block (nfact / success: int32)
+  // staging of the Float32 host-pointer calls: vals, rhs, d, and [rho | rho_old | nfact | success] as one block (nfact / success: int32)
   float *f_vals = nullptr, *f_rhs = nullptr, *f_d = nullptr, *f_res = nullptr;
-  float* f_cgls_ws = nullptr;  // [batch][2 * nvar] workspace of cnl_cgls_multipliers_f32_dev, allocated on first use
 };
 
 namespace {
@@ -169,18 +170,27 @@ double* as_args(const float* p) { return reinterpret_cast<double*>(const_cast<fl
 #define CNL_NEED_F64(h) do { if (int rc_ = need_f64((h), __func__)) return rc_; } while (0)
 #define CNL_NEED_F32(h) do { if (int rc_ = need_f32((h), __func__)) return rc_; } while (0)
 
-// band program -> the summaries cnl_plan_get returns as "band_info" / "band_part<q>" (and "band4_...")
-void band_summary(const cnl::BandPlan& Bp, std::vector<int32_t>& info, std::vector<int32_t> (&pinfo)[2]) {
-  // (the last word: the piece count of a wide program; 0 = the fifteen of "band_*" / "band4_*", as it always was)
-  info = {Bp.ok ? 1 : 0, Bp.nparts, Bp.m0, Bp.n, Bp.N, Bp.nnz, (int32_t)Bp.lsize, Bp.ok && Bp.npiece != cnl::BAND_NPIECE ? Bp.npiece : 0};
-  for (int q = 0; q < 2; q++) pinfo[q] = {Bp.part[q].nsteps, Bp.part[q].nepochs, Bp.part[q].npiv, Bp.part[q].nevents, (int32_t)Bp.part[q].loff};
+const char* const kHostLayout = "host-pointer calls take the reference's problem-major arrays: this handle was created with batch_layout = "
+                                "CNL_LAYOUT_INTERLEAVED (device-pointer entry points only)";
+
+// band programs -> the summaries cnl_plan_get returns as "<prefix>info" / "<prefix>part<q>"
+void band_summaries(cnl_plan* p) {
+  for (auto& row : p->band_prog)
+    for (cnl_plan::BandSlot& s : row) {
+      const cnl::BandPlan& Bp = s.B;
+      // (the last word: the piece count of a wide program; 0 = the fifteen of "band_*" / "band4_*", as it always was)
+      s.info = {Bp.ok ? 1 : 0, Bp.nparts, Bp.m0, Bp.n, Bp.N, Bp.nnz, (int32_t)Bp.lsize, Bp.ok && Bp.npiece != cnl::BAND_NPIECE ? Bp.npiece : 0};
+      for (int q = 0; q < 2; q++) s.pinfo[q] = {Bp.part[q].nsteps, Bp.part[q].nepochs, Bp.part[q].npiv, Bp.part[q].nevents, (int32_t)Bp.part[q].loff};
+    }
 }
 
 // The band programs of a pattern for one element size: the 15-piece program whenever the pattern fits it, word for word what it always
 // was; the wide one only where it does not fit (tuning band_pieces = 0), never (15), or also where 15 fit (20: the wide kernel
 // instances then run the handle — same steps, same arithmetic, bit-equal outputs).
-void build_band_programs(cnl::BandPlan& B15, cnl::BandPlan& Bw, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar,
-                         int64_t nequ, int64_t ncon, const cnl::Tuning& o, int esz) {
+void build_band_programs(cnl_plan* p, const int64_t* rows1, const int64_t* cols1, int esz) {
+  const cnl::Tuning& o = p->opt;
+  const int64_t N = p->N, nnz = p->nnz, nvar = p->nvar, nequ = p->nequ, ncon = p->ncon;
+  cnl::BandPlan &B15 = p->band_prog[esz == 4][0].B, &Bw = p->band_prog[esz == 4][1].B;
   const int nparts = o.band_kernel == 2 ? 1 : 2;
   cnl::build_band_plan(B15, N, nnz, rows1, cols1, nvar, nequ, ncon, nparts, esz, cnl::BAND_NPIECE);
   Bw = cnl::BandPlan();
@@ -190,8 +200,7 @@ void build_band_programs(cnl::BandPlan& B15, cnl::BandPlan& Bw, int64_t N, int64
 }
 // the program a handle runs: the wide one where the plan has it (the pattern needs it, or tuning band_pieces = 20)
 const cnl::BandPlan& band_program(const cnl_plan* plan, bool f32) {
-  const cnl::BandPlan& w = f32 ? plan->bandw4 : plan->bandw;
-  return w.ok ? w : (f32 ? plan->band4 : plan->band);
+  return plan->band_prog[f32][plan->band_prog[f32][1].B.ok].B;
 }
 
 // Float64 handles have the register-front kernel beside the band kernels.  On the pattern that needs the wide program it measured
@@ -201,13 +210,6 @@ const cnl::BandPlan& band_program(const cnl_plan* plan, bool f32) {
 // (Float32 handles have no other kernel: they always take the wide program where the pattern needs it.)
 bool band_wide_serves_f64(const cnl_plan* plan) {
   return band_program(plan, false).npiece == cnl::BAND_NPIECE || plan->opt.band_pieces == cnl::BAND_NPIECE_WIDE;
-}
-
-void band_summaries(cnl_plan* p) {
-  band_summary(p->band, p->band_info, p->band_pinfo);
-  band_summary(p->band4, p->band4_info, p->band4_pinfo);
-  band_summary(p->bandw, p->bandw_info, p->bandw_pinfo);
-  band_summary(p->bandw4, p->bandw4_info, p->bandw4_pinfo);
 }
 
 #define HIPCHK(expr)                                                                                   \
@@ -424,6 +426,82 @@ const int* dbg_ldsfill() {
 // launches per kernel family since the library was loaded (cnl_launch_counts): [band kernels, register-front kernel, general kernel]
 std::atomic<long long> g_launches[3];
 
+// the time between the handle's two events (cnl_set_timing), once the second one has been recorded
+int read_timing(cnl_handle* h) {
+  HIPCHK(hipEventSynchronize(h->ev1));
+  HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+  return CNL_OK;
+}
+
+// the handle's pinned host block (results of host-pointer calls), at least `bytes` long
+int ensure_pinned(cnl_handle* h, size_t bytes) {
+  if (h->pin && h->pin_bytes >= bytes) return CNL_OK;
+  if (h->pin) (void)hipHostFree(h->pin);
+  h->pin = nullptr;
+  HIPCHK(hipHostMalloc(&h->pin, bytes, hipHostMallocDefault));
+  h->pin_bytes = bytes;
+  return CNL_OK;
+}
+
+// rows [b][N] of the problems with ok(b) from the device to the host, one copy per maximal run of them (one in the common case): the
+// reference leaves d untouched where the factorisation failed (src/CaNNOLeS.jl:1049)
+template <class T, class Ok>
+hipError_t copy_rows_where(Ok ok, T* dst, const T* d_src, size_t B, size_t N, hipStream_t stream) {
+  size_t b0 = 0;
+  while (b0 < B) {
+    while (b0 < B && !ok(b0)) b0++;
+    size_t b1 = b0;
+    while (b1 < B && ok(b1)) b1++;
+    if (b1 > b0)
+      if (hipError_t e = hipMemcpyAsync(dst + b0 * N, d_src + b0 * N, (b1 - b0) * N * sizeof(T), hipMemcpyDeviceToHost, stream)) return e;
+    b0 = b1;
+  }
+  return hipSuccess;
+}
+
+// the per-problem result arrays of a call, from problem b0 on
+cnl::LaunchArgs shifted(cnl::LaunchArgs a, int64_t b0) {
+  if (a.rho_old) a.rho_old += b0;
+  if (a.rho) a.rho += b0;
+  if (a.nfact) a.nfact += b0;
+  if (a.success) a.success += b0;
+  if (a.npos) a.npos += b0;
+  if (a.nzero) a.nzero += b0;
+  return a;
+}
+
+// A call of the plugin surface on a band handle, either element type (Float32: the element arrays are float arrays behind the
+// double* of LaunchArgs, see as_args): exactly one launch of the band kernels.  try_to_factorize is the forward sweep alone;
+// solve_ldl! factorises the values of the last factorisation again (rho slots as the ladder left them) and sweeps the new
+// right-hand side in the same launch — the band kernels' six-element records hold z = c / d of the one right-hand side they were
+// computed with, so there is no stored factor a second right-hand side could use.
+int run_band(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, double* d_d, hipStream_t stream) {
+  // (a band handle owns the band factor records alone: the buffers of the other kernels do not exist for it)
+  if (a.skip_done || a.only_if_status || (a.mode == cnl::MODE_NEWTON && !d_rhs))
+    return fail(CNL_ERR_STATE, "this call is not served by the band kernels, and a band handle has no other"
+                               " (no factor panels, no condensed buffer; interleaved `vals` are the band kernels' layout)");
+  if (a.mode == cnl::MODE_SOLVE && !h->last_vals) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
+  if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
+  a.vals = a.mode == cnl::MODE_SOLVE ? const_cast<double*>(h->last_vals) : d_vals;
+  a.rhs = d_rhs; a.d = d_d;
+  a.batch = (int)h->batch;
+  a.L = static_cast<double*>(h->d_Lband);
+  a.layout = h->layout;
+  if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
+  const hipError_t e = h->f32 ? cnl::launch_band_f32(h->bd, h->band_nl, a, stream, h->band_npiece)
+                              : cnl::launch_band(h->bd, h->band_nl, a, stream, h->band_npiece);
+  g_launches[0]++;
+  if (e != hipSuccess)
+    return fail(CNL_ERR_HIP, std::string("band kernel launch (") + (h->f32 ? "Float32, " : "") + std::to_string(h->band_nl) +
+                                 " problems per workgroup): " + hipGetErrorString(e));
+  if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
+  if (h->timing) {
+    HIPCHK(hipEventRecord(h->ev1, stream));
+    return read_timing(h);
+  }
+  return CNL_OK;
+}
+
 int launch(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
   if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
   a.batch = (int)h->batch;
@@ -433,23 +511,7 @@ int launch(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
   a.scratch = h->d_scratch;
   hipError_t e;
   if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));  // events bracket the multifrontal kernel only
-  if (h->band && !a.skip_done && !a.only_if_status && (a.mode != cnl::MODE_NEWTON || a.rhs)) {
-    // band handles: all three calls of the plugin surface run on the band kernels (round 6).  try_to_factorize is the forward
-    // sweep alone; solve_ldl! factorises the values of the last factorisation again (a.vals = the handle's last_vals, rho slots as
-    // the ladder left them) and sweeps the new right-hand side in the same launch — the band kernels' six-double records hold
-    // z = c / d of the one right-hand side they were computed with, so there is no stored factor a second right-hand side could use,
-    // and the register-front refactorisation rounds 5 put in front of such a solve (a second, slower kernel whose flags nobody read)
-    // is gone
-    cnl::LaunchArgs b = a;
-    b.L = h->d_Lband;
-    b.layout = h->layout;
-    e = cnl::launch_band(h->bd, h->band_nl, b, stream, h->band_npiece);
-    g_launches[0]++;
-  } else if (h->band) {
-    // (a band handle owns the band factor records alone: the buffers of the other kernels do not exist for it)
-    return fail(CNL_ERR_STATE, "this call is not served by the band kernels, and a band handle has no other"
-                               " (no factor panels, no condensed buffer; interleaved `vals` are the band kernels' layout)");
-  } else if (h->use_v2 && (a.mode != cnl::MODE_SOLVE || h->v2_solve)) {
+  if (h->use_v2 && (a.mode != cnl::MODE_SOLVE || h->v2_solve)) {
     a.scratch = h->d_gs;
     e = cnl::launch_newton2(h->dp2, h->wpb2, h->lds2, a, stream);
     g_launches[1]++;
@@ -490,18 +552,21 @@ int launch_staged(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
 struct SubBatch {
   cnl_handle* h;
   int64_t batch;
-  double *L, *gs, *scratch, *cbuf, *d2, *Lband;
+  double *L, *gs, *scratch, *cbuf, *d2;
+  void* Lband;
   int *xpos, *xzer, *gcnt, *dep, *lad, *stat;
   const double* last_vals;
   bool staged;
   SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged = true) : h(h_) {
     last_vals = h->last_vals; staged = h->staged;
-    if (h->last_vals) h->last_vals += b0 * h->plan->nnz;
+    // (last_vals and the band records are arrays of the handle's element type behind their double* / void*: offsets in bytes)
+    const size_t esz = h->f32 ? sizeof(float) : sizeof(double);
+    if (h->last_vals) h->last_vals = reinterpret_cast<const double*>(reinterpret_cast<const char*>(h->last_vals) + b0 * h->plan->nnz * esz);
     if (!allow_staged) h->staged = false;
     batch = h->batch; L = h->d_L; gs = h->d_gs; scratch = h->d_scratch; cbuf = h->d_cbuf; d2 = h->d_d2;
     xpos = h->d_xpos; xzer = h->d_xzer; gcnt = h->d_gcnt; dep = h->d_dep; lad = h->d_lad; stat = h->d_stat;
     Lband = h->d_Lband;
-    if (h->d_Lband) h->d_Lband += b0 * h->bd.lsize;
+    if (h->d_Lband) h->d_Lband = static_cast<char*>(h->d_Lband) + b0 * h->bd.lsize * esz;
     const cnl::Cond& C = h->plan->C;
     h->batch = nb;
     h->d_L += b0 * h->dp.lsize;
@@ -552,13 +617,7 @@ int run_split(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d
       rc = run(h, b, d_vals, d_rhs, d_d, stream);
     }
     if (rc == CNL_OK) {
-      cnl::LaunchArgs b = a;
-      if (b.rho_old) b.rho_old += nA;
-      if (b.rho) b.rho += nA;
-      if (b.nfact) b.nfact += nA;
-      if (b.success) b.success += nA;
-      if (b.npos) b.npos += nA;
-      if (b.nzero) b.nzero += nA;
+      cnl::LaunchArgs b = shifted(a, nA);
       double* tv = d_vals ? d_vals + nA * nnz : nullptr;
       const double* tr = d_rhs ? d_rhs + nA * N : nullptr;
       double* td = d_d ? d_d + nA * N : nullptr;
@@ -578,8 +637,7 @@ int run_split(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d
     if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
     if (tm) {
       HIPCHK(hipEventRecord(h->ev1, stream));
-      HIPCHK(hipEventSynchronize(h->ev1));
-      HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+      return read_timing(h);
     }
     return CNL_OK;
   }
@@ -591,13 +649,7 @@ int run_split(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d
     for (int part = 0; part < 2 && rc == CNL_OK; part++) {
       const int64_t b0 = part ? nA : 0, nb = part ? nB : nA;
       SubBatch view(h, b0, nb, true);
-      cnl::LaunchArgs b = a;
-      if (b.rho_old) b.rho_old += b0;
-      if (b.rho) b.rho += b0;
-      if (b.nfact) b.nfact += b0;
-      if (b.success) b.success += b0;
-      if (b.npos) b.npos += b0;
-      if (b.nzero) b.nzero += b0;
+      cnl::LaunchArgs b = shifted(a, b0);
       rc = run(h, b, d_vals ? d_vals + b0 * nnz : nullptr, d_rhs ? d_rhs + b0 * N : nullptr, d_d ? d_d + b0 * N : nullptr, stream);
     }
     h->in_split = false;
@@ -606,8 +658,7 @@ int run_split(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d
     if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
     if (tm) {
       HIPCHK(hipEventRecord(h->ev1, stream));
-      HIPCHK(hipEventSynchronize(h->ev1));
-      HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+      return read_timing(h);
     }
     return CNL_OK;
   }
@@ -616,13 +667,7 @@ int run_split(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d
   int rc;
   {
     SubBatch view(h, nA, nB, false);
-    cnl::LaunchArgs b = a;
-    if (b.rho_old) b.rho_old += nA;
-    if (b.rho) b.rho += nA;
-    if (b.nfact) b.nfact += nA;
-    if (b.success) b.success += nA;
-    if (b.npos) b.npos += nA;
-    if (b.nzero) b.nzero += nA;
+    cnl::LaunchArgs b = shifted(a, nA);
     rc = run(h, b, d_vals ? d_vals + nA * nnz : nullptr, d_rhs ? d_rhs + nA * N : nullptr, d_d ? d_d + nA * N : nullptr, h->aux_stream);
   }
   if (rc == CNL_OK) {
@@ -639,8 +684,7 @@ int run_split(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d
   if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
   if (tm) {
     HIPCHK(hipEventRecord(h->ev1, stream));
-    HIPCHK(hipEventSynchronize(h->ev1));
-    HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    return read_timing(h);
   }
   return CNL_OK;
 }
@@ -664,6 +708,7 @@ int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, 
   const cnl::Cond& C = h->plan->C;
   int rc = CNL_OK;
   if (h->split_staged > 0 && !h->in_split && (h->staged || h->tail) && h->split_staged < h->batch) return run_split(h, a, d_vals, d_rhs, d_d, stream);
+  if (h->band) return run_band(h, a, d_vals, d_rhs, d_d, stream);
   if (h->dense || h->gdense)
     if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
   if (h->dense) {
@@ -676,8 +721,7 @@ int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, 
     if (rc) return fail(rc == 5 ? CNL_ERR_STATE : CNL_ERR_HIP, "dense backend: " + err);
     if (h->timing) {
       HIPCHK(hipEventRecord(h->ev1, stream));
-      HIPCHK(hipEventSynchronize(h->ev1));
-      HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+      return read_timing(h);
     }
     return CNL_OK;
   }
@@ -712,8 +756,7 @@ int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, 
     }
     if (h->timing) {
       HIPCHK(hipEventRecord(h->ev1, stream));
-      HIPCHK(hipEventSynchronize(h->ev1));
-      HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+      return read_timing(h);
     }
     return CNL_OK;
   }
@@ -723,7 +766,7 @@ int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, 
   } else {
     const int B = (int)h->batch;
     const int s_mat = (int)(C.ncs + C.nvar), s_all = (int)C.cstride;
-    double* crhs = h->d_cbuf ? h->d_cbuf + s_mat : nullptr;   // (band handles own no condensed buffer)
+    double* crhs = h->d_cbuf + s_mat;
     hipError_t e = hipSuccess;
     const bool direct = h->use_v2 && h->plan->P.rec_direct;  // the register-front kernel condenses on the fly
     const bool count_d = direct && h->dp2.count_d;  // the kernel counts the condensed pivots itself
@@ -817,11 +860,7 @@ int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, 
     }
   }
   if (rc) return rc;
-  if (h->timing) {
-    HIPCHK(hipEventSynchronize(h->ev1));
-    HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-  }
-  return CNL_OK;
+  return h->timing ? read_timing(h) : CNL_OK;
 }
 
 int ensure_staging(cnl_handle* h) {
@@ -910,10 +949,6 @@ int multi_run(cnl_multi* m, F f) {
 
 // ---- rows f1 / f2 / f4 and the trial point on device pointers: one implementation per row for both element types (the launchers
 //      of kernels.h are overloaded on float / double); the entry points (extern "C" below) check the handle's element type first ----
-// the CGLS workspace of the handle's element type
-static double*& cgls_ws(cnl_handle* h, const double*) { return h->d_cgls_ws; }
-static float*& cgls_ws(cnl_handle* h, const float*) { return h->f_cgls_ws; }
-
 template <class T>
 static int prepare_impl(cnl_handle* h, int64_t nnzhF, int64_t nnzhc, int64_t nnzjF, int64_t nnzjc, const T* d_hF, const T* d_hc, const T* d_Jx,
                         const T* d_Jcx, const T* d_delta, T* d_vals, void* stream) {
@@ -936,10 +971,11 @@ static int cgls_impl(cnl_handle* h, const cnl::JacSrcT<T>& S, const T* d_r, T* d
   if (!d_lambda) return fail(CNL_ERR_ARG, "null lambda");
   if (h->djt.ncon > 1024) return fail(CNL_ERR_DIM, "cnl_cgls_multipliers_dev supports at most 1024 constraints");
   HIPCHK(hipSetDevice(h->device));
-  T*& ws = cgls_ws(h, d_r);
+  T* ws = static_cast<T*>(h->cgls_ws);   // (the entry points have checked T against the handle's element type)
   if (!ws) {
     int rc = dalloc(h, &ws, (size_t)h->batch * 2 * (size_t)h->djt.nvar);
     if (rc) return rc;
+    h->cgls_ws = ws;
   }
   if (itmax <= 0) itmax = (int64_t)h->djt.nvar + h->djt.ncon;  // Krylov.jl's default: m + n
   hipError_t e = cnl::launch_cgls(h->djt, S, d_r, d_lambda, d_Jxtr, ws, d_iters, atol, rtol, (int)itmax, ones_if_zero,
@@ -980,6 +1016,102 @@ static int trial_point_impl(cnl_handle* h, const T* d_x, const T* d_r, const T* 
   hipError_t e = cnl::launch_trial_point(h->djt, d_x, d_r, d_lambda, d_d, max_dlambda, d_xt, d_rt, d_lambdat, d_dlambda, (int)h->batch,
                                          (hipStream_t)stream);
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("trial_point: ") + hipGetErrorString(e));
+  return CNL_OK;
+}
+
+// ---- handle creation: what the creators of both element types share ----
+// what every creator checks before it analyses anything
+static int check_batch(int64_t batch) {
+  if (batch < 1 || batch > (1 << 24)) return fail(CNL_ERR_ARG, "batch out of range");
+  return CNL_OK;
+}
+static int check_device(int device) {
+  int ndev = 0;
+  const hipError_t ce = hipGetDeviceCount(&ndev);
+  if (ce != hipSuccess || ndev == 0)
+    return fail(CNL_ERR_HIP, std::string("no HIP device available (this backend has no CPU fallback): hipGetDeviceCount -> ") +
+                                 hipGetErrorString(ce) + ", " + std::to_string(ndev) + " device(s)");
+  if (device < 0 || device >= ndev) return fail(CNL_ERR_ARG, "device index out of range");
+  return CNL_OK;
+}
+
+// The band kernels for a handle of either element type (h->f32): uploads the program, chooses the problems per workgroup and
+// allocates the factor records; h->band says whether they serve the handle.  They do not where the program does not fit them —
+// *unfit then names the reason and the caller decides what that means (a Float64 handle has the register-front kernel, a Float32
+// handle nothing).  An option that asks for an instance that does not exist is an error.
+static int setup_band(cnl_handle* h, const cnl::BandPlan& Bp, const char** unfit) {
+  const cnl_plan* plan = h->plan;
+  const int esz = h->f32 ? (int)sizeof(float) : (int)sizeof(double);
+  const int64_t batch = h->batch;
+  int rc;
+  h->band_npiece = Bp.npiece;
+  const bool wide = Bp.npiece != cnl::BAND_NPIECE;
+  cnl::BandDev& bd = h->bd;
+  for (int q = 0; q < Bp.nparts; q++) {
+    if ((rc = upload(h, Bp.part[q].fops, &bd.fops[q]))) return rc;
+    if ((rc = upload(h, Bp.part[q].bops, &bd.bops[q]))) return rc;
+    if ((rc = upload(h, Bp.part[q].epochs, &bd.epochs[q]))) return rc;
+    if ((rc = upload(h, Bp.part[q].borders, &bd.borders[q]))) return rc;
+    bd.nsteps[q] = Bp.part[q].nsteps; bd.nepochs[q] = Bp.part[q].nepochs; bd.loff[q] = Bp.part[q].loff;
+  }
+  bd.nparts = Bp.nparts; bd.m0 = Bp.m0; bd.n = Bp.n; bd.N = Bp.N; bd.nnz = Bp.nnz; bd.nvar = (int32_t)plan->nvar; bd.lsize = Bp.lsize;
+  // 16 problems per workgroup (two workgroups = four wavefronts per CU: one per SIMD) up to the 8192 problems that fills; above,
+  // 32 per workgroup (the LDS of a CU holds two such workgroups: 16384 problems resident) — tools/time_band.py
+  // (wide program, Float64: 16 at every batch — three workgroups per CU hold 48 problems where one of 32 would hold 32, and the
+  // 32-problem instance would spill; band.hip, band_wide_has)
+  h->band_nl = plan->opt.band_problems_per_group > 0 ? plan->opt.band_problems_per_group
+                                                     : (batch > 8192 && (!wide || cnl::band_wide_has(esz, 32)) ? 32 : 16);
+  if (h->band_nl != 8 && h->band_nl != 16 && h->band_nl != 32) return fail(CNL_ERR_ARG, "band_problems_per_group must be 8, 16 or 32");
+  if (wide && !cnl::band_wide_has(esz, h->band_nl))   // (there is a wide Float32 instance for each of the three)
+    return fail(CNL_ERR_ARG, "band_problems_per_group = 32: the wide band program (20 operand pieces) has Float64 kernels for 8 and 16 problems per workgroup only");
+  // 32-bit byte offsets inside a workgroup's problems
+  const uint64_t span = (uint64_t)esz * (uint64_t)h->band_nl * (uint64_t)std::max<int64_t>({plan->nnz, plan->N, bd.lsize});
+  if (span >= (1ull << 32)) { *unfit = "the arrays of a workgroup's problems span 4 GB or more (32-bit offsets of the band kernels)"; return CNL_OK; }
+  if (cnl::band_lds_bytes(bd.nparts, h->band_nl, esz, h->band_npiece) > std::min<size_t>(cnl::max_lds_bytes(), 160 * 1024)) {
+    *unfit = "the band kernels' LDS does not fit a workgroup";
+    return CNL_OK;
+  }
+  // (+ 32 problems: the band kernels interleave the records of a workgroup's problems, the last workgroup's region is a whole one)
+  const size_t lbytes = (((size_t)batch + 32) * (size_t)bd.lsize + 64) * (size_t)esz;
+  char* L = nullptr;
+  if ((rc = dalloc(h, &L, lbytes))) return rc;
+  if (hipMemset(L, 0, lbytes) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
+  h->d_Lband = L;
+  h->band = true;
+  return CNL_OK;
+}
+
+// cnl_options.batch_layout: the interleaved layout is the band kernels' (groups of 32 problems = one workgroup of the 32-problem
+// instantiation)
+static int setup_layout(cnl_handle* h) {
+  const cnl::Tuning& o = h->plan->opt;
+  if (o.batch_layout == CNL_LAYOUT_PROBLEM_MAJOR) return CNL_OK;
+  if (o.batch_layout != CNL_LAYOUT_INTERLEAVED) return fail(CNL_ERR_ARG, "cnl_options.batch_layout: unknown layout");
+  if (!h->band)
+    return fail(CNL_ERR_ARG, "batch_layout = CNL_LAYOUT_INTERLEAVED needs a handle the band kernels serve "
+                             "(band-structured pattern, throughput plan, cnl_options.band_kernel != 0; csrc/band.h)");
+  h->layout = 1 | (o.band_rhs_interleaved ? 2 : 0);
+  return CNL_OK;
+}
+
+// ---- cnl_options.batch_layout = CNL_LAYOUT_INTERLEAVED: lengths and conversions (csrc/band.h: band_il_index) ----
+static int layout_rowlen(const cnl_handle* h, int which, int64_t* len) {
+  if (which == 0) *len = h->djt.nnz;
+  else if (which == 1) *len = (int64_t)h->djt.nvar + h->djt.nequ + h->djt.ncon;
+  else return fail(CNL_ERR_ARG, "which: 0 = vals, 1 = an N-vector per problem (rhs)");
+  return CNL_OK;
+}
+template <class T>
+static int convert_layout(cnl_handle* h, int which, const T* src, T* dst, int to_interleaved, void* stream) {
+  if (!h || !src || !dst) return fail(CNL_ERR_ARG, "null argument");
+  if (src == dst) return fail(CNL_ERR_ARG, "the conversion is not in place");
+  int64_t len = 0;
+  if (int rc = layout_rowlen(h, which, &len)) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  hipError_t e;
+  if constexpr (sizeof(T) == 4) e = cnl::launch_interleave_f32(src, dst, (int)h->batch, len, to_interleaved, (hipStream_t)stream);
+  else e = cnl::launch_interleave(src, dst, (int)h->batch, len, to_interleaved, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("interleave: ") + hipGetErrorString(e));
   return CNL_OK;
 }
 
@@ -1220,12 +1352,13 @@ static int plan_create_impl(cnl_plan** plan, int64_t N, int64_t nnz, const int64
   lap("records");
   // (round 5) large batches of band-structured problems: the sliding-window elimination with one lane per (problem, part)
   if (!latency && o.band_kernel && p->C.active && !p->D.active) {
-    build_band_programs(p->band, p->bandw, N, nnz, rows1, cols1, nvar, nequ, ncon, o, 8);
-    if (verbose) fprintf(stderr, "[cnl] band program: %s%s\n", p->band.ok ? "ok" : "no: ", p->band.ok ? "" : p->band.why.c_str());
-    if (verbose && !p->band.ok && p->band.pieces_short)
-      fprintf(stderr, "[cnl] wide band program (%d pieces): %s%s\n", cnl::BAND_NPIECE_WIDE, p->bandw.ok ? "ok" : "no: ", p->bandw.ok ? "" : p->bandw.why.c_str());
+    build_band_programs(p, rows1, cols1, 8);
+    const cnl::BandPlan &b15 = p->band_prog[0][0].B, &bw = p->band_prog[0][1].B;
+    if (verbose) fprintf(stderr, "[cnl] band program: %s%s\n", b15.ok ? "ok" : "no: ", b15.ok ? "" : b15.why.c_str());
+    if (verbose && !b15.ok && b15.pieces_short)
+      fprintf(stderr, "[cnl] wide band program (%d pieces): %s%s\n", cnl::BAND_NPIECE_WIDE, bw.ok ? "ok" : "no: ", bw.ok ? "" : bw.why.c_str());
     // the programs for 4-byte elements (Float32 handles): the same blocks, every LDS offset scaled
-    if (p->band.ok || p->bandw.ok) build_band_programs(p->band4, p->bandw4, N, nnz, rows1, cols1, nvar, nequ, ncon, o, 4);
+    if (b15.ok || bw.ok) build_band_programs(p, rows1, cols1, 4);
   }
   band_summaries(p);
   // Irregular sparsity: when the fill makes fronts larger than the register-front kernel takes and the condensed system is of
@@ -1308,17 +1441,18 @@ int cnl_plan_get(const cnl_plan* plan, const char* name, int32_t* out, int64_t* 
   else if (s.rfind("band", 0) == 0) {
     // band programs (csrc/band.h): "band_*" the 15-piece program, "band4_*" the same for 4-byte elements, "bandw_*" / "bandw4_*" the
     // wide program (its piece count: info[7]); "<prefix>info", and per part q "<prefix>part<q>", "fops<q>", "bops<q>", "epochs<q>", "borders<q>"
-    struct Fam { const char* prefix; const cnl::BandPlan* B; const std::vector<int32_t>* info; const std::vector<int32_t>* pinfo; };
-    const Fam fams[4] = {{"bandw4_", &plan->bandw4, &plan->bandw4_info, plan->bandw4_pinfo}, {"bandw_", &plan->bandw, &plan->bandw_info, plan->bandw_pinfo},
-                         {"band4_", &plan->band4, &plan->band4_info, plan->band4_pinfo}, {"band_", &plan->band, &plan->band_info, plan->band_pinfo}};
-    const Fam* f = nullptr;
-    for (const Fam& c : fams) if (!f && s.rfind(c.prefix, 0) == 0) f = &c;
+    // (every prefix ends with the '_' another has a letter or digit at: at most one matches)
+    const cnl_plan::BandSlot* f = nullptr;
+    size_t plen = 0;
+    for (int t = 0; t < 2; t++)
+      for (int w = 0; w < 2; w++)
+        if (s.rfind(kBandPrefix[t][w], 0) == 0) { f = &plan->band_prog[t][w]; plen = std::strlen(kBandPrefix[t][w]); }
     if (!f) return fail(CNL_ERR_ARG, "unknown plan array: " + s);
-    const std::string rest = s.substr(std::strlen(f->prefix));
-    if (rest == "info") { src = f->info->data(); n = (int64_t)f->info->size(); }
+    const std::string rest = s.substr(plen);
+    if (rest == "info") { src = f->info.data(); n = (int64_t)f->info.size(); }
     else if (!rest.empty() && (rest.back() == '0' || rest.back() == '1')) {
       const int q = rest.back() - '0';
-      const cnl::BandPart& Q = f->B->part[q];
+      const cnl::BandPart& Q = f->B.part[q];
       const std::string k = rest.substr(0, rest.size() - 1);
       if (k == "part") { src = f->pinfo[q].data(); n = (int64_t)f->pinfo[q].size(); }
       else if (k == "fops") { src = Q.fops.data(); n = (int64_t)Q.fops.size(); }
@@ -1356,13 +1490,8 @@ int cnl_create_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows
 static int create_tuned(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar,
                         int64_t nequ, int64_t ncon, int64_t batch, int device, const cnl::Tuning& o) {
   *hout = nullptr;
-  if (batch < 1 || batch > (1 << 24)) return fail(CNL_ERR_ARG, "batch out of range");
-  int ndev = 0;
-  const hipError_t ce = hipGetDeviceCount(&ndev);
-  if (ce != hipSuccess || ndev == 0)
-    return fail(CNL_ERR_HIP, std::string("no HIP device available (this backend has no CPU fallback): hipGetDeviceCount -> ") +
-                                 hipGetErrorString(ce) + ", " + std::to_string(ndev) + " device(s)");
-  if (device < 0 || device >= ndev) return fail(CNL_ERR_ARG, "device index out of range");
+  if (int rc = check_batch(batch)) return rc;
+  if (int rc = check_device(device)) return rc;
   cnl_plan* plan = nullptr;
   // small batches cannot fill the chip with one wavefront per four problems: plan for latency (bushy order, tasks)
   int rc = plan_create_tuned(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, o);
@@ -1547,44 +1676,12 @@ static int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* ro
   if ((rc = choose_config(h))) return bail(rc);
   if ((rc = setup_v2(h))) return bail(rc);
   if (band_program(plan, false).ok && band_wide_serves_f64(plan) && plan->opt.band_kernel && h->use_v2 && !h->staged && h->v2_solve && h->lean && plan->P.back_rows && !plan->latency && !plan->split_mode) {
-    // band kernels for newton_system, try_to_factorize and solve_ldl! (csrc/band.h); the wide program where the plan has one
-    const cnl::BandPlan& Bp = band_program(plan, false);
-    h->band_npiece = Bp.npiece;
-    const bool wide = Bp.npiece != cnl::BAND_NPIECE;
-    cnl::BandDev& bd = h->bd;
-    for (int q = 0; q < Bp.nparts; q++) {
-      if ((rc = upload(h, Bp.part[q].fops, &bd.fops[q]))) return bail(rc);
-      if ((rc = upload(h, Bp.part[q].bops, &bd.bops[q]))) return bail(rc);
-      if ((rc = upload(h, Bp.part[q].epochs, &bd.epochs[q]))) return bail(rc);
-      if ((rc = upload(h, Bp.part[q].borders, &bd.borders[q]))) return bail(rc);
-      bd.nsteps[q] = Bp.part[q].nsteps; bd.nepochs[q] = Bp.part[q].nepochs; bd.loff[q] = Bp.part[q].loff;
-    }
-    bd.nparts = Bp.nparts; bd.m0 = Bp.m0; bd.n = Bp.n; bd.N = Bp.N; bd.nnz = Bp.nnz; bd.nvar = (int32_t)nvar; bd.lsize = Bp.lsize;
-    // 16 problems per workgroup (two workgroups = four wavefronts per CU: one per SIMD) up to the 8192 problems that fills; above,
-    // 32 per workgroup (the LDS of a CU holds two such workgroups: 16384 problems resident) — tools/time_band.py
-    // (wide program, Float64: 16 at every batch — three workgroups per CU hold 48 problems where one of 32 would hold 32, and the
-    // 32-problem instance would spill; band.hip, band_wide_has)
-    h->band_nl = plan->opt.band_problems_per_group > 0 ? plan->opt.band_problems_per_group : (batch > 8192 && !wide ? 32 : 16);
-    if (h->band_nl != 8 && h->band_nl != 16 && h->band_nl != 32) return bail(fail(CNL_ERR_ARG, "band_problems_per_group must be 8, 16 or 32"));
-    if (wide && !cnl::band_wide_has(8, h->band_nl))
-      return bail(fail(CNL_ERR_ARG, "band_problems_per_group = 32: the wide band program (20 operand pieces) has Float64 kernels for 8 and 16 problems per workgroup only"));
-    // 32-bit byte offsets inside a workgroup's problems
-    const uint64_t span = 8ull * (uint64_t)h->band_nl * (uint64_t)std::max<int64_t>({(int64_t)nnz, N, bd.lsize});
-    if (span < (1ull << 32) && cnl::band_lds_bytes(bd.nparts, h->band_nl, 8, h->band_npiece) <= std::min<size_t>(cnl::max_lds_bytes(), 160 * 1024)) {
-      // (+ 32 problems: the band kernels interleave the records of a workgroup's problems, the last workgroup's region is a whole one)
-      if ((rc = dalloc(h, &h->d_Lband, ((size_t)batch + 32) * (size_t)bd.lsize + 64))) return bail(rc);
-      if (hipMemset(h->d_Lband, 0, (((size_t)batch + 32) * (size_t)bd.lsize + 64) * sizeof(double)) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipMemset failed"));
-      h->band = true;
-    }
+    // band kernels for newton_system, try_to_factorize and solve_ldl! (csrc/band.h); the wide program where the plan has one.
+    // (A program that does not fit them — setup_band — leaves the handle on the register-front kernel.)
+    const char* unfit = nullptr;
+    if ((rc = setup_band(h, band_program(plan, false), &unfit))) return bail(rc);
   }
-  if (plan->opt.batch_layout != CNL_LAYOUT_PROBLEM_MAJOR) {
-    // the interleaved layout is the band kernels' (groups of 32 problems = one workgroup of the 32-problem instantiation)
-    if (plan->opt.batch_layout != CNL_LAYOUT_INTERLEAVED) return bail(fail(CNL_ERR_ARG, "cnl_options.batch_layout: unknown layout"));
-    if (!h->band)
-      return bail(fail(CNL_ERR_ARG, "batch_layout = CNL_LAYOUT_INTERLEAVED needs a handle the band kernels serve "
-                                    "(band-structured pattern, throughput plan, cnl_options.band_kernel != 0; csrc/band.h)"));
-    h->layout = 1 | (plan->opt.band_rhs_interleaved ? 2 : 0);
-  }
+  if ((rc = setup_layout(h))) return bail(rc);
   // Storage only the register-front / general kernels and the stand-alone condensation passes use.  A band handle runs all three
   // calls of the plugin surface on the band kernels (round 6), so it owns the band factor records alone: 0.48 MB per problem of
   // cfg3's size instead of 0.48 + 1.16 (factor panels) + 0.64 (condensed buffer, reduced solution) — 16 384 problems: 29 GB less,
@@ -1811,28 +1908,11 @@ int cnl_trial_point_f32_dev(cnl_handle* h, const float* d_x, const float* d_r, c
   return trial_point_impl(h, d_x, d_r, d_lambda, d_d, max_dlambda, d_xt, d_rt, d_lambdat, d_dlambda, stream);
 }
 
-// ---- cnl_options.batch_layout = CNL_LAYOUT_INTERLEAVED: lengths and conversions (csrc/band.h: band_il_index) ----
-static int layout_rowlen(const cnl_handle* h, int which, int64_t* len) {
-  if (which == 0) *len = h->djt.nnz;
-  else if (which == 1) *len = (int64_t)h->djt.nvar + h->djt.nequ + h->djt.ncon;
-  else return fail(CNL_ERR_ARG, "which: 0 = vals, 1 = an N-vector per problem (rhs)");
-  return CNL_OK;
-}
 int cnl_layout_len(const cnl_handle* h, int which, int64_t* doubles) {
   if (!h || !doubles) return fail(CNL_ERR_ARG, "null argument");
   int64_t len = 0;
   if (int rc = layout_rowlen(h, which, &len)) return rc;
   *doubles = cnl::band_il_len(h->batch, len);
-  return CNL_OK;
-}
-static int convert_layout(cnl_handle* h, int which, const double* src, double* dst, int to_interleaved, void* stream) {
-  if (!h || !src || !dst) return fail(CNL_ERR_ARG, "null argument");
-  if (src == dst) return fail(CNL_ERR_ARG, "the conversion is not in place");
-  int64_t len = 0;
-  if (int rc = layout_rowlen(h, which, &len)) return rc;
-  HIPCHK(hipSetDevice(h->device));
-  hipError_t e = cnl::launch_interleave(src, dst, (int)h->batch, len, to_interleaved, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("interleave: ") + hipGetErrorString(e));
   return CNL_OK;
 }
 int cnl_interleave_dev(cnl_handle* h, int which, const double* d_src, double* d_dst, void* stream) {
@@ -1925,7 +2005,7 @@ int cnl_newton_system_dev(cnl_handle* h, double* d_vals, const double* d_rhs, do
 int cnl_factorize(cnl_handle* h, const double* vals, double eig_tol, int32_t* success, int64_t* npos, int64_t* nzero) {
   if (!h || !vals || !success) return fail(CNL_ERR_ARG, "null argument");
   CNL_NEED_F64(h);
-  if (h->layout) return fail(CNL_ERR_STATE, "host-pointer calls take the reference's problem-major arrays: this handle was created with batch_layout = CNL_LAYOUT_INTERLEAVED (device-pointer entry points only)");
+  if (h->layout) return fail(CNL_ERR_STATE, kHostLayout);
   HIPCHK(hipSetDevice(h->device));
   int rc = ensure_staging(h);
   if (rc) return rc;
@@ -1942,12 +2022,7 @@ int cnl_factorize(cnl_handle* h, const double* vals, double eig_tol, int32_t* su
     // results through the handle's pinned block: asynchronous copies (a copy into pageable memory blocks, one after the other),
     // the inertia counts with one copy (npos | nzero are one block on the device, ensure_staging), a single synchronisation
     const size_t o_su = 0, o_np = (B * 4 + 7) & ~(size_t)7, total = o_np + B * 16;
-    if (!h->pin || h->pin_bytes < total) {
-      if (h->pin) (void)hipHostFree(h->pin);
-      h->pin = nullptr;
-      HIPCHK(hipHostMalloc(&h->pin, total, hipHostMallocDefault));
-      h->pin_bytes = total;
-    }
+    if (int prc = ensure_pinned(h, total)) return prc;
     char* pb = static_cast<char*>(h->pin);
     HIPCHK(hipMemcpyAsync(pb + o_su, h->d_success, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     if (npos || nzero) HIPCHK(hipMemcpyAsync(pb + o_np, h->d_npos, B * 16, hipMemcpyDeviceToHost, h->stream));
@@ -1964,7 +2039,7 @@ int cnl_factorize(cnl_handle* h, const double* vals, double eig_tol, int32_t* su
 int cnl_solve(cnl_handle* h, const double* rhs, double* d) {
   if (!h || !rhs || !d) return fail(CNL_ERR_ARG, "null argument");
   CNL_NEED_F64(h);
-  if (h->layout) return fail(CNL_ERR_STATE, "host-pointer calls take the reference's problem-major arrays: this handle was created with batch_layout = CNL_LAYOUT_INTERLEAVED (device-pointer entry points only)");
+  if (h->layout) return fail(CNL_ERR_STATE, kHostLayout);
   if (!h->factorized) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
   HIPCHK(hipSetDevice(h->device));
   int rc = ensure_staging(h);
@@ -1979,18 +2054,8 @@ int cnl_solve(cnl_handle* h, const double* rhs, double* d) {
     return fail(CNL_ERR_STATE, "cnl_solve after a factorisation that failed (success = 0): there is no factor to solve with "
                                "(the reference calls solve_ldl! only after a successful try_to_factorize, src/CaNNOLeS.jl:1049)");
   if ((rc = run(h, a, nullptr, h->d_rhs, h->d_d, h->stream))) return rc;
-  if (!known) {
-    HIPCHK(hipMemcpyAsync(d, h->d_d, B * P.N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  } else {
-    size_t b0 = 0;
-    while (b0 < B) {  // rows of the problems that hold a factor; the others stay as the caller passed them
-      while (b0 < B && !h->last_ok[b0]) b0++;
-      size_t b1 = b0;
-      while (b1 < B && h->last_ok[b1]) b1++;
-      if (b1 > b0) HIPCHK(hipMemcpyAsync(d + b0 * P.N, h->d_d + b0 * P.N, (b1 - b0) * P.N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      b0 = b1;
-    }
-  }
+  // rows of the problems that hold a factor (all of them after a device-pointer factorisation); the others stay as the caller passed them
+  HIPCHK(copy_rows_where([&](size_t b) { return !known || h->last_ok[b]; }, d, h->d_d, B, (size_t)P.N, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return CNL_OK;
 }
@@ -2037,15 +2102,7 @@ static int newton_system_pipelined(cnl_handle* h, double* vals, const double* rh
       if (!chk(hipEventSynchronize(h->pipe_ev[c]), "hipEventSynchronize")) continue;
       if (!chk(hipMemcpyAsync(success + b0, h->d_success + b0, nb * sizeof(int32_t), hipMemcpyDeviceToHost, st), "copy success")) continue;
       if (!chk(hipStreamSynchronize(st), "hipStreamSynchronize")) continue;
-      // the reference leaves d untouched when the factorisation fails (src/CaNNOLeS.jl:1049): maximal runs of successes
-      size_t q0 = 0;
-      while (q0 < nb) {
-        while (q0 < nb && !success[b0 + q0]) q0++;
-        size_t q1 = q0;
-        while (q1 < nb && success[b0 + q1]) q1++;
-        if (q1 > q0) chk(hipMemcpyAsync(d + (b0 + q0) * P.N, h->d_d + (b0 + q0) * P.N, (q1 - q0) * P.N * sizeof(double), hipMemcpyDeviceToHost, st), "copy d");
-        q0 = q1;
-      }
+      chk(copy_rows_where([&](size_t q) { return success[b0 + q] != 0; }, d + b0 * P.N, h->d_d + b0 * P.N, nb, (size_t)P.N, st), "copy d");
       chk(hipMemcpyAsync(rho + b0, h->d_rho + b0, nb * sizeof(double), hipMemcpyDeviceToHost, st), "copy rho");
       chk(hipMemcpyAsync(rho_old_out + b0, h->d_rho_old + b0, nb * sizeof(double), hipMemcpyDeviceToHost, st), "copy rho_old");
       chk(hipMemcpyAsync(nfact + b0, h->d_nfact + b0, nb * sizeof(int32_t), hipMemcpyDeviceToHost, st), "copy nfact");
@@ -2117,12 +2174,7 @@ static int newton_system_pipelined(cnl_handle* h, double* vals, const double* rh
     for (size_t b = 0; b < B; b++) { failed[b] = !success[b]; any_failed |= failed[b] != 0; }
     if (any_failed) {
       const size_t need = B * 16;
-      if (!h->pin || h->pin_bytes < need) {
-        if (h->pin) (void)hipHostFree(h->pin);
-        h->pin = nullptr;
-        HIPCHK(hipHostMalloc(&h->pin, need, hipHostMallocDefault));
-        h->pin_bytes = need;
-      }
+      if (int prc = ensure_pinned(h, need)) return prc;
       char* pb2 = static_cast<char*>(h->pin);
       int rc = host_ladder_run(h, params, rho_old, rho, rho_old_out, nfact, success, pb2, reinterpret_cast<int32_t*>(pb2 + B * 12));
       if (rc) return rc;
@@ -2201,7 +2253,7 @@ int cnl_newton_system(cnl_handle* h, double* vals, const double* rhs, double* d,
                       double* rho, double* rho_old_out, int32_t* nfact, int32_t* success) {
   if (!h || !vals || !rhs || !d || !params || !rho || !rho_old_out || !nfact || !success) return fail(CNL_ERR_ARG, "null argument");
   CNL_NEED_F64(h);
-  if (h->layout) return fail(CNL_ERR_STATE, "host-pointer calls take the reference's problem-major arrays: this handle was created with batch_layout = CNL_LAYOUT_INTERLEAVED (device-pointer entry points only)");
+  if (h->layout) return fail(CNL_ERR_STATE, kHostLayout);
   HIPCHK(hipSetDevice(h->device));
   int rc = ensure_staging(h);
   if (rc) return rc;
@@ -2241,12 +2293,7 @@ int cnl_newton_system(cnl_handle* h, double* vals, const double* rhs, double* d,
     }
     if (any_failed) {
       const size_t need = B * 16;
-      if (!h->pin || h->pin_bytes < need) {
-        if (h->pin) (void)hipHostFree(h->pin);
-        h->pin = nullptr;
-        HIPCHK(hipHostMalloc(&h->pin, need, hipHostMallocDefault));
-        h->pin_bytes = need;
-      }
+      if (int prc = ensure_pinned(h, need)) return prc;
       char* pb2 = static_cast<char*>(h->pin);
       if ((rc = host_ladder_run(h, params, rho_old, rho, rho_old_out, nfact, success, pb2, reinterpret_cast<int32_t*>(pb2 + B * 12)))) return rc;
     } else {
@@ -2294,12 +2341,7 @@ int cnl_newton_system(cnl_handle* h, double* vals, const double* rhs, double* d,
   if (small) {
     const size_t o_d = 0, o_tail = o_d + B * P.N * 8, o_rho = o_tail + B * P.nvar * 8, o_ro = o_rho + B * 8, o_nf = o_ro + B * 8,
                  o_su = o_nf + B * 4, o_up = (o_su + B * 4 + 7) & ~(size_t)7, total = o_up + B * 12 + 8;
-    if (!h->pin || h->pin_bytes < total) {
-      if (h->pin) (void)hipHostFree(h->pin);
-      h->pin = nullptr;
-      HIPCHK(hipHostMalloc(&h->pin, total, hipHostMallocDefault));
-      h->pin_bytes = total;
-    }
+    if (int prc = ensure_pinned(h, total)) return prc;
     char* pb = static_cast<char*>(h->pin);
     HIPCHK(hipMemcpyAsync(pb + o_d, h->d_d, B * P.N * 8, hipMemcpyDeviceToHost, h->stream));
     // (with the host-driven ladder the first attempt never writes the rho slots: they come back only behind a ladder, or behind the
@@ -2379,27 +2421,13 @@ int cnl_newton_system(cnl_handle* h, double* vals, const double* rhs, double* d,
       HIPCHK(hipMemcpyAsync(nfact, h->d_nfact, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
       HIPCHK(hipStreamSynchronize(h->stream));
       const size_t need = B * 16;
-      if (!h->pin || h->pin_bytes < need) {
-        if (h->pin) (void)hipHostFree(h->pin);
-        h->pin = nullptr;
-        HIPCHK(hipHostMalloc(&h->pin, need, hipHostMallocDefault));
-        h->pin_bytes = need;
-      }
+      if (int prc = ensure_pinned(h, need)) return prc;
       char* pb2 = static_cast<char*>(h->pin);
       if ((rc = host_ladder_run(h, params, rho_old, rho, rho_old_out, nfact, success, pb2, reinterpret_cast<int32_t*>(pb2 + B * 12)))) return rc;
       laddered = true;
     }
   }
-  {
-    size_t b0 = 0;
-    while (b0 < B) {  // maximal runs of successful problems: one copy in the common case
-      while (b0 < B && !success[b0]) b0++;
-      size_t b1 = b0;
-      while (b1 < B && success[b1]) b1++;
-      if (b1 > b0) HIPCHK(hipMemcpyAsync(d + b0 * P.N, h->d_d + b0 * P.N, (b1 - b0) * P.N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      b0 = b1;
-    }
-  }
+  HIPCHK(copy_rows_where([&](size_t b) { return success[b] != 0; }, d, h->d_d, B, (size_t)P.N, h->stream));
   if (!laddered) {
     HIPCHK(hipMemcpyAsync(rho, h->d_rho, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(rho_old_out, h->d_rho_old, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2437,33 +2465,10 @@ static int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t
   auto bail = [&](int code) { cnl_destroy(h); return code; };
   if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
   int rc = CNL_OK;
-  const cnl::BandPlan& Bp = band_program(plan, true);   // the wide program where the plan has one
-  h->band_npiece = Bp.npiece;
-  cnl::BandDev& bd = h->bd;
-  for (int q = 0; q < Bp.nparts; q++) {
-    if ((rc = upload(h, Bp.part[q].fops, &bd.fops[q]))) return bail(rc);
-    if ((rc = upload(h, Bp.part[q].bops, &bd.bops[q]))) return bail(rc);
-    if ((rc = upload(h, Bp.part[q].epochs, &bd.epochs[q]))) return bail(rc);
-    if ((rc = upload(h, Bp.part[q].borders, &bd.borders[q]))) return bail(rc);
-    bd.nsteps[q] = Bp.part[q].nsteps; bd.nepochs[q] = Bp.part[q].nepochs; bd.loff[q] = Bp.part[q].loff;
-  }
-  bd.nparts = Bp.nparts; bd.m0 = Bp.m0; bd.n = Bp.n; bd.N = Bp.N; bd.nnz = Bp.nnz; bd.nvar = (int32_t)plan->nvar; bd.lsize = Bp.lsize;
-  // problems per workgroup: the Float64 handles' rule
-  h->band_nl = plan->opt.band_problems_per_group > 0 ? plan->opt.band_problems_per_group : (batch > 8192 ? 32 : 16);
-  if (h->band_nl != 8 && h->band_nl != 16 && h->band_nl != 32) return bail(fail(CNL_ERR_ARG, "band_problems_per_group must be 8, 16 or 32"));
-  const uint64_t span = sizeof(float) * (uint64_t)h->band_nl * (uint64_t)std::max<int64_t>({plan->nnz, plan->N, bd.lsize});
-  if (span >= (1ull << 32)) return bail(fail(CNL_ERR_ARG, "cnl_create_f32: the arrays of a workgroup's problems span 4 GB or more (32-bit offsets of the band kernels)"));
-  if (cnl::band_lds_bytes(bd.nparts, h->band_nl, (int)sizeof(float), h->band_npiece) > std::min<size_t>(cnl::max_lds_bytes(), 160 * 1024))
-    return bail(fail(CNL_ERR_ARG, "cnl_create_f32: the band kernels' LDS does not fit a workgroup"));
-  // (+ 32 problems: the records of a workgroup's problems are interleaved in one region, the last workgroup's is a whole one)
-  const size_t lfloats = ((size_t)batch + 32) * (size_t)bd.lsize + 64;
-  if ((rc = dalloc(h, &h->f_Lband, lfloats))) return bail(rc);
-  if (hipMemset(h->f_Lband, 0, lfloats * sizeof(float)) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipMemset failed"));
-  h->band = true;
-  if (plan->opt.batch_layout != CNL_LAYOUT_PROBLEM_MAJOR) {
-    if (plan->opt.batch_layout != CNL_LAYOUT_INTERLEAVED) return bail(fail(CNL_ERR_ARG, "cnl_options.batch_layout: unknown layout"));
-    h->layout = 1 | (plan->opt.band_rhs_interleaved ? 2 : 0);
-  }
+  const char* unfit = nullptr;
+  if ((rc = setup_band(h, band_program(plan, true), &unfit))) return bail(rc);   // the wide program where the plan has one
+  if (!h->band) return bail(fail(CNL_ERR_ARG, std::string("cnl_create_f32: ") + unfit));   // (Float32 handles have no other kernel)
+  if ((rc = setup_layout(h))) return bail(rc);
   // rows f1 / f2 / f4 and the trial point: the Float64 handles' row lists (they hold the dimensions cnl_layout_len reads)
   if ((rc = build_row_lists(h, plan, rows1, cols1))) return bail(rc);
   if (hipStreamCreate(&h->stream) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipStreamCreate failed"));
@@ -2483,45 +2488,23 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
   *hout = nullptr;
   cnl::Tuning o;
   if (int rc = resolve_options(opt, o)) return rc;
-  if (batch < 1 || batch > (1 << 24)) return fail(CNL_ERR_ARG, "batch out of range");
+  if (int rc = check_batch(batch)) return rc;
   if (!o.band_kernel) return fail(CNL_ERR_ARG, "cnl_create_f32: cnl_options.band_kernel = 0, and Float32 handles run on the band kernels only");
-  int ndev = 0;
-  const hipError_t ce = hipGetDeviceCount(&ndev);
-  if (ce != hipSuccess || ndev == 0)
-    return fail(CNL_ERR_HIP, std::string("no HIP device available (this backend has no CPU fallback): hipGetDeviceCount -> ") +
-                                 hipGetErrorString(ce) + ", " + std::to_string(ndev) + " device(s)");
-  if (device < 0 || device >= ndev) return fail(CNL_ERR_ARG, "device index out of range");
+  if (int rc = check_device(device)) return rc;
   // the throughput analysis whatever the batch: there is nothing but the band program to run
   cnl_plan* plan = nullptr;
   if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, o)) return rc;
   if (!band_program(plan, true).ok) {   // (the analysis builds it next to the Float64 program; not for a pattern the Float64 handles serve otherwise)
-    build_band_programs(plan->band4, plan->bandw4, N, nnz, rows1, cols1, nvar, nequ, ncon, o, (int)sizeof(float));
+    build_band_programs(plan, rows1, cols1, (int)sizeof(float));
     band_summaries(plan);
   }
   if (!band_program(plan, true).ok) {
-    const std::string why = plan->bandw4.why.empty() ? plan->band4.why : plan->bandw4.why;
+    const std::string why = plan->band_prog[1][1].B.why.empty() ? plan->band_prog[1][0].B.why : plan->band_prog[1][1].B.why;
     cnl_plan_destroy(plan);
     return fail(CNL_ERR_ARG, "cnl_create_f32: the pattern is not served by the band kernels (build_band_plan: " + why +
                                  "); Float32 stays on the CPU backend for it");
   }
   return create_f32_from_plan(hout, plan, rows1, cols1, batch, device);
-}
-
-static int launch_f32(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
-  if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
-  a.batch = (int)h->batch;
-  a.L = as_args(h->f_Lband);
-  a.layout = h->layout;
-  if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
-  const hipError_t e = cnl::launch_band_f32(h->bd, h->band_nl, a, stream, h->band_npiece);
-  g_launches[0]++;
-  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("band kernel launch (Float32): ") + hipGetErrorString(e));
-  if (h->timing) {
-    HIPCHK(hipEventRecord(h->ev1, stream));
-    HIPCHK(hipEventSynchronize(h->ev1));
-    HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-  }
-  return CNL_OK;
 }
 
 static int ensure_staging_f32(cnl_handle* h) {
@@ -2545,11 +2528,10 @@ int cnl_factorize_f32_dev(cnl_handle* h, const float* d_vals, float eig_tol, int
   HIPCHK(hipSetDevice(h->device));
   cnl::LaunchArgs a{};
   a.mode = cnl::MODE_FACTOR;
-  a.vals = as_args(d_vals);
   a.success = d_success;
   a.params[0] = eig_tol;
-  const int rc = launch_f32(h, a, (hipStream_t)stream);
-  if (rc == CNL_OK) { h->factorized = true; h->f_last_vals = d_vals; h->last_ok.clear(); }
+  const int rc = run(h, a, as_args(d_vals), nullptr, nullptr, (hipStream_t)stream);
+  if (rc == CNL_OK) { h->factorized = true; h->last_vals = as_args(d_vals); h->last_ok.clear(); }
   return rc;
 }
 
@@ -2558,11 +2540,10 @@ int cnl_solve_f32_dev(cnl_handle* h, const float* d_rhs, float* d_d, void* strea
   CNL_NEED_F32(h);
   if (!h->factorized) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
   HIPCHK(hipSetDevice(h->device));
-  // (the band kernels' solve factorises the values of the last factorisation again, rho slots as the ladder left them: see launch())
+  // (the band kernels' solve factorises the values of the last factorisation again, rho slots as the ladder left them: see run_band)
   cnl::LaunchArgs a{};
   a.mode = cnl::MODE_SOLVE;
-  a.vals = as_args(h->f_last_vals); a.rhs = as_args(d_rhs); a.d = as_args(d_d);
-  return launch_f32(h, a, (hipStream_t)stream);
+  return run(h, a, nullptr, as_args(d_rhs), as_args(d_d), (hipStream_t)stream);
 }
 
 int cnl_newton_system_f32_dev(cnl_handle* h, float* d_vals, const float* d_rhs, float* d_d, float* d_rho_old, float* d_rho,
@@ -2573,21 +2554,17 @@ int cnl_newton_system_f32_dev(cnl_handle* h, float* d_vals, const float* d_rhs, 
   HIPCHK(hipSetDevice(h->device));
   cnl::LaunchArgs a{};
   a.mode = cnl::MODE_NEWTON;
-  a.vals = as_args(d_vals); a.rhs = as_args(d_rhs); a.d = as_args(d_d);
   a.rho_old = as_args(d_rho_old); a.rho = as_args(d_rho); a.nfact = d_nfact; a.success = d_success;
   for (int k = 0; k < 9; k++) a.params[k] = params[k];   // (exact: the kernel narrows them back)
-  const int rc = launch_f32(h, a, (hipStream_t)stream);
-  if (rc == CNL_OK) { h->factorized = true; h->f_last_vals = d_vals; h->last_ok.clear(); }
+  const int rc = run(h, a, as_args(d_vals), as_args(d_rhs), as_args(d_d), (hipStream_t)stream);
+  if (rc == CNL_OK) { h->factorized = true; h->last_vals = as_args(d_vals); h->last_ok.clear(); }
   return rc;
 }
-
-static const char* kHostLayoutF32 = "host-pointer calls take the reference's problem-major arrays: this handle was created with batch_layout = "
-                                    "CNL_LAYOUT_INTERLEAVED (device-pointer entry points only)";
 
 int cnl_factorize_f32(cnl_handle* h, const float* vals, float eig_tol, int32_t* success, int64_t* npos, int64_t* nzero) {
   if (!h || !vals || !success) return fail(CNL_ERR_ARG, "null argument");
   CNL_NEED_F32(h);
-  if (h->layout) return fail(CNL_ERR_STATE, kHostLayoutF32);
+  if (h->layout) return fail(CNL_ERR_STATE, kHostLayout);
   HIPCHK(hipSetDevice(h->device));
   int rc = ensure_staging_f32(h);
   if (rc) return rc;
@@ -2597,15 +2574,14 @@ int cnl_factorize_f32(cnl_handle* h, const float* vals, float eig_tol, int32_t* 
   HIPCHK(hipMemcpyAsync(h->f_vals, vals, B * P.nnz * sizeof(float), hipMemcpyHostToDevice, h->stream));
   cnl::LaunchArgs a{};
   a.mode = cnl::MODE_FACTOR;
-  a.vals = as_args(h->f_vals);
   a.success = d_success; a.npos = h->d_npos; a.nzero = h->d_nzero;
   a.params[0] = eig_tol;
-  if ((rc = launch_f32(h, a, h->stream))) return rc;
+  if ((rc = run(h, a, as_args(h->f_vals), nullptr, nullptr, h->stream))) return rc;
   HIPCHK(hipMemcpyAsync(success, d_success, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   if (npos) HIPCHK(hipMemcpyAsync(npos, h->d_npos, B * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
   if (nzero) HIPCHK(hipMemcpyAsync(nzero, h->d_nzero, B * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->f_last_vals = h->f_vals;
+  h->last_vals = as_args(h->f_vals);
   h->factorized = true;
   h->last_ok.assign(success, success + B);
   return CNL_OK;
@@ -2614,7 +2590,7 @@ int cnl_factorize_f32(cnl_handle* h, const float* vals, float eig_tol, int32_t* 
 int cnl_solve_f32(cnl_handle* h, const float* rhs, float* d) {
   if (!h || !rhs || !d) return fail(CNL_ERR_ARG, "null argument");
   CNL_NEED_F32(h);
-  if (h->layout) return fail(CNL_ERR_STATE, kHostLayoutF32);
+  if (h->layout) return fail(CNL_ERR_STATE, kHostLayout);
   if (!h->factorized) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
   const size_t B = (size_t)h->batch;
   const bool known = h->last_ok.size() == B;
@@ -2628,16 +2604,9 @@ int cnl_solve_f32(cnl_handle* h, const float* rhs, float* d) {
   HIPCHK(hipMemcpyAsync(h->f_rhs, rhs, B * P.N * sizeof(float), hipMemcpyHostToDevice, h->stream));
   cnl::LaunchArgs a{};
   a.mode = cnl::MODE_SOLVE;
-  a.vals = as_args(h->f_last_vals); a.rhs = as_args(h->f_rhs); a.d = as_args(h->f_d);
-  if ((rc = launch_f32(h, a, h->stream))) return rc;
-  size_t b0 = 0;
-  while (b0 < B) {  // rows of the problems that hold a factor (all of them after a device-pointer factorisation); the others stay
-    while (known && b0 < B && !h->last_ok[b0]) b0++;
-    size_t b1 = b0;
-    while (b1 < B && (!known || h->last_ok[b1])) b1++;
-    if (b1 > b0) HIPCHK(hipMemcpyAsync(d + b0 * P.N, h->f_d + b0 * P.N, (b1 - b0) * P.N * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    b0 = b1;
-  }
+  if ((rc = run(h, a, nullptr, as_args(h->f_rhs), as_args(h->f_d), h->stream))) return rc;
+  // rows of the problems that hold a factor (all of them after a device-pointer factorisation); the others stay
+  HIPCHK(copy_rows_where([&](size_t b) { return !known || h->last_ok[b]; }, d, h->f_d, B, (size_t)P.N, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return CNL_OK;
 }
@@ -2646,7 +2615,7 @@ int cnl_newton_system_f32(cnl_handle* h, float* vals, const float* rhs, float* d
                           float* rho_old_out, int32_t* nfact, int32_t* success) {
   if (!h || !vals || !rhs || !d || !params || !rho || !rho_old_out || !nfact || !success) return fail(CNL_ERR_ARG, "null argument");
   CNL_NEED_F32(h);
-  if (h->layout) return fail(CNL_ERR_STATE, kHostLayoutF32);
+  if (h->layout) return fail(CNL_ERR_STATE, kHostLayout);
   HIPCHK(hipSetDevice(h->device));
   int rc = ensure_staging_f32(h);
   if (rc) return rc;
@@ -2662,22 +2631,13 @@ int cnl_newton_system_f32(cnl_handle* h, float* vals, const float* rhs, float* d
   else HIPCHK(hipMemsetAsync(d_rho_old, 0, B * sizeof(float), h->stream));
   cnl::LaunchArgs a{};
   a.mode = cnl::MODE_NEWTON;
-  a.vals = as_args(h->f_vals); a.rhs = as_args(h->f_rhs); a.d = as_args(h->f_d);
   a.rho_old = as_args(d_rho_old); a.rho = as_args(d_rho); a.nfact = d_nfact; a.success = d_success;
   for (int k = 0; k < 9; k++) a.params[k] = params[k];
-  if ((rc = launch_f32(h, a, h->stream))) return rc;
-  h->f_last_vals = h->f_vals;
+  if ((rc = run(h, a, as_args(h->f_vals), as_args(h->f_rhs), as_args(h->f_d), h->stream))) return rc;
+  h->last_vals = as_args(h->f_vals);
   HIPCHK(hipMemcpyAsync(success, d_success, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  // the reference leaves d untouched when the factorisation fails (src/CaNNOLeS.jl:1049): the rows that succeeded come back
-  size_t b0 = 0;
-  while (b0 < B) {
-    while (b0 < B && !success[b0]) b0++;
-    size_t b1 = b0;
-    while (b1 < B && success[b1]) b1++;
-    if (b1 > b0) HIPCHK(hipMemcpyAsync(d + b0 * P.N, h->f_d + b0 * P.N, (b1 - b0) * P.N * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    b0 = b1;
-  }
+  HIPCHK(copy_rows_where([&](size_t b) { return success[b] != 0; }, d, h->f_d, B, (size_t)P.N, h->stream));
   HIPCHK(hipMemcpyAsync(rho, d_rho, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(rho_old_out, d_rho_old, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(nfact, d_nfact, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -2691,19 +2651,14 @@ int cnl_newton_system_f32(cnl_handle* h, float* vals, const float* rhs, float* d
   return CNL_OK;
 }
 
-static int convert_layout_f32(cnl_handle* h, int which, const float* src, float* dst, int to_interleaved, void* stream) {
-  if (!h || !src || !dst) return fail(CNL_ERR_ARG, "null argument");
+int cnl_interleave_f32_dev(cnl_handle* h, int which, const float* d_src, float* d_dst, void* stream) {
   CNL_NEED_F32(h);
-  if (src == dst) return fail(CNL_ERR_ARG, "the conversion is not in place");
-  int64_t len = 0;
-  if (int rc = layout_rowlen(h, which, &len)) return rc;
-  HIPCHK(hipSetDevice(h->device));
-  hipError_t e = cnl::launch_interleave_f32(src, dst, (int)h->batch, len, to_interleaved, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("interleave: ") + hipGetErrorString(e));
-  return CNL_OK;
+  return convert_layout(h, which, d_src, d_dst, 1, stream);
 }
-int cnl_interleave_f32_dev(cnl_handle* h, int which, const float* d_src, float* d_dst, void* stream) { return convert_layout_f32(h, which, d_src, d_dst, 1, stream); }
-int cnl_deinterleave_f32_dev(cnl_handle* h, int which, const float* d_src, float* d_dst, void* stream) { return convert_layout_f32(h, which, d_src, d_dst, 0, stream); }
+int cnl_deinterleave_f32_dev(cnl_handle* h, int which, const float* d_src, float* d_dst, void* stream) {
+  CNL_NEED_F32(h);
+  return convert_layout(h, which, d_src, d_dst, 0, stream);
+}
 
 // ---- one caller, several devices: contiguous balanced shards of the batch, one handle + one host thread per
 //      device, no collective — the devices never exchange data --------------------------------------------------------------

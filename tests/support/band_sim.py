@@ -1,6 +1,8 @@
 """CPU interpreter of the band program (csrc/band.h, written by csrc/band.cpp): executes the step / row / epoch blocks exactly as
 the kernels of csrc/band.hip do — operands through per-epoch 64-byte pieces into a lane block, window of 5 band slots + 1 border
-slot, factor records through the out ring, junction of the two parts — vectorised over a batch of problems.  Test
+slot, factor records through the out ring, junction of the two parts — vectorised over a batch of problems.  The piece count is
+a property of the program (csrc/band.h: BandPlan::npiece; `<prefix>_info[7]`, 0 meaning fifteen): the lane-block and epoch-block
+offsets that depend on it are attributes of the interpreter; the module-level ones describe the 15-piece program.  Test
 infrastructure: it pins the GENERATOR against the oracle without a GPU."""
 import numpy as np
 
@@ -24,18 +26,34 @@ BE_LBASE, BE_LCNT, BE_LBASE2, BE_LCNT2, BE_DXLO, BE_DXCNT, BE_DRLO, BE_DRCNT, BE
 
 
 class BandSim:
-    def __init__(self, plan):
-        info = plan.array("band_info")
+    def __init__(self, plan, prefix="band"):
+        """prefix: the program's cnl_plan_get names — "band" (the 15-piece program), "bandw" (the wide one); "band4" / "bandw4" hold
+        byte offsets of 4-byte elements and are not for this interpreter"""
+        info = plan.array(f"{prefix}_info")
         self.ok = bool(info[0])
         if not self.ok:
             return
         self.nparts, self.m0, self.n, self.N, self.nnz, self.lsize = (int(v) for v in info[1:7])
+        # the layout follows the program's piece count (csrc/band.h: band_lout_off .. band_lane_elems, band_ef, band_ew)
+        self.NPIECE = npc = int(info[7]) or NPIECE
+        self.LOUT_OFF = self.DX_OFF = npc * 8
+        self.DR_OFF = self.DX_OFF + DX_MAX
+        self.ZERO_OFF = self.LOUT_OFF + LOUT_MAX
+        self.LANE = self.ZERO_OFF + 1
+        self.BE_FP, self.BE_BP = 0, npc
+        (self.BE_LBASE, self.BE_LCNT, self.BE_LBASE2, self.BE_LCNT2, self.BE_DXLO, self.BE_DXCNT, self.BE_DRLO, self.BE_DRCNT, self.BE_NSTEP,
+         self.BE_FOFF, self.BE_BOFF, self.BE_OPLEN) = (2 * npc + i for i in range(12))
+        self.EW = (self.BE_OPLEN + 1 + 3) & ~3
         self.parts = []
         for q in range(self.nparts):
-            pi = plan.array(f"band_part{q}")
+            pi = plan.array(f"{prefix}_part{q}")
             self.parts.append(dict(nsteps=int(pi[0]), nepochs=int(pi[1]), npiv=int(pi[2]), nevents=int(pi[3]), loff=int(pi[4]),
-                                   fops=plan.array(f"band_fops{q}"), bops=plan.array(f"band_bops{q}"),
-                                   epochs=plan.array(f"band_epochs{q}").reshape(-1, EW), borders=plan.array(f"band_borders{q}").reshape(-1, BW)))
+                                   fops=plan.array(f"{prefix}_fops{q}"), bops=plan.array(f"{prefix}_bops{q}"),
+                                   epochs=plan.array(f"{prefix}_epochs{q}").reshape(-1, self.EW), borders=plan.array(f"{prefix}_borders{q}").reshape(-1, BW)))
+
+    def pieces_used(self):
+        """largest number of operand pieces any epoch of the program uses, forward or backward"""
+        return max(int((P["epochs"][:, o: o + self.NPIECE] >= 0).sum(axis=1).max()) for P in self.parts for o in (self.BE_FP, self.BE_BP))
 
     # ---- one factorisation attempt (+ forward substitution) of every problem -------------------------------------------
     def _load_pieces(self, blk, pieces, arrays):
@@ -55,21 +73,21 @@ class BandSim:
         for q, P in enumerate(self.parts):
             S = np.zeros((NS + 1, NS + 1, B))
             c = np.zeros((NS + 1, B))
-            blk = np.zeros((B, LANE))
+            blk = np.zeros((B, self.LANE))
             ops, o = P["fops"], 0
             Lq = Lst[:, P["loff"]:]
-            starts = np.concatenate([[0], np.cumsum(P["epochs"][:, BE_NSTEP])])
+            starts = np.concatenate([[0], np.cumsum(P["epochs"][:, self.BE_NSTEP])])
             assert starts[-1] == P["nsteps"]
-            ep_of = np.repeat(np.arange(P["nepochs"]), P["epochs"][:, BE_NSTEP])
+            ep_of = np.repeat(np.arange(P["nepochs"]), P["epochs"][:, self.BE_NSTEP])
             for u in range(P["nsteps"]):
                 if u == starts[ep_of[u]]:
                     E = P["epochs"][ep_of[u]]
                     if u:   # factor records of the previous epoch's second half
                         Ep = P["epochs"][ep_of[u] - 1]
-                        Lq[:, Ep[BE_LBASE2]: Ep[BE_LBASE2] + Ep[BE_LCNT2]] = blk[:, LOUT_OFF: LOUT_OFF + Ep[BE_LCNT2]]
-                    blk[:, :ZERO_OFF] = np.nan   # stale operands must not be read
-                    self._load_pieces(blk, E[BE_FP: BE_FP + NPIECE], (vals, rhs))
-                    assert o == E[BE_FOFF] and E[BE_OPLEN] <= 256
+                        Lq[:, Ep[self.BE_LBASE2]: Ep[self.BE_LBASE2] + Ep[self.BE_LCNT2]] = blk[:, self.LOUT_OFF: self.LOUT_OFF + Ep[self.BE_LCNT2]]
+                    blk[:, :self.ZERO_OFF] = np.nan   # stale operands must not be read
+                    self._load_pieces(blk, E[self.BE_FP: self.BE_FP + self.NPIECE], (vals, rhs))
+                    assert o == E[self.BE_FOFF] and E[self.BE_OPLEN] <= 256
                 st = ops[o: o + SW]
                 fl = int(st[BS_FLAGS])
                 nrows = (fl >> 8) & 255
@@ -155,10 +173,10 @@ class BandSim:
                 o += SW + RW * nrows
                 if u - starts[ep_of[u]] == EPOCH // 2 - 1 or (u + 1 == starts[ep_of[u] + 1] and u - starts[ep_of[u]] < EPOCH // 2 - 1):
                     Ec = P["epochs"][ep_of[u]]   # factor records of the epoch's first half
-                    Lq[:, Ec[BE_LBASE]: Ec[BE_LBASE] + Ec[BE_LCNT]] = blk[:, LOUT_OFF: LOUT_OFF + Ec[BE_LCNT]]
-                    blk[:, LOUT_OFF: ZERO_OFF] = np.nan
+                    Lq[:, Ec[self.BE_LBASE]: Ec[self.BE_LBASE] + Ec[self.BE_LCNT]] = blk[:, self.LOUT_OFF: self.LOUT_OFF + Ec[self.BE_LCNT]]
+                    blk[:, self.LOUT_OFF: self.ZERO_OFF] = np.nan
             Ep = P["epochs"][P["nepochs"] - 1]
-            Lq[:, Ep[BE_LBASE2]: Ep[BE_LBASE2] + Ep[BE_LCNT2]] = blk[:, LOUT_OFF: LOUT_OFF + Ep[BE_LCNT2]]
+            Lq[:, Ep[self.BE_LBASE2]: Ep[self.BE_LBASE2] + Ep[self.BE_LCNT2]] = blk[:, self.LOUT_OFF: self.LOUT_OFF + Ep[self.BE_LCNT2]]
             wins.append((S, c))
         junction = None
         if self.nparts == 2:
@@ -205,17 +223,17 @@ class BandSim:
             if xj is not None:
                 for i in range(HW):
                     xs[((m0 + i) if q == 0 else (n - 1 - m0 - i)) % NS] = xj[i]
-            blk = np.zeros((B, LANE))
+            blk = np.zeros((B, self.LANE))
             ops, o = P["bops"], 0
             Lq = Lst[:, P["loff"]:]
-            starts = np.concatenate([[0], np.cumsum(P["epochs"][:, BE_NSTEP])])
-            ep_of = np.repeat(np.arange(P["nepochs"]), P["epochs"][:, BE_NSTEP])
+            starts = np.concatenate([[0], np.cumsum(P["epochs"][:, self.BE_NSTEP])])
+            ep_of = np.repeat(np.arange(P["nepochs"]), P["epochs"][:, self.BE_NSTEP])
             for u in range(P["nsteps"] - 1, -1, -1):
                 if u == starts[ep_of[u] + 1] - 1:
                     E = P["epochs"][ep_of[u]]
-                    blk[:, :ZERO_OFF] = np.nan
-                    self._load_pieces(blk, E[BE_BP: BE_BP + NPIECE], (vals, rhs, Lq))
-                    assert o == E[BE_BOFF]
+                    blk[:, :self.ZERO_OFF] = np.nan
+                    self._load_pieces(blk, E[self.BE_BP: self.BE_BP + self.NPIECE], (vals, rhs, Lq))
+                    assert o == E[self.BE_BOFF]
                 st = ops[o: o + SW]
                 fl = int(st[BS_FLAGS])
                 nrows = (fl >> 8) & 255
@@ -248,8 +266,8 @@ class BandSim:
                 o += SW + RW * nrows
                 if u == starts[ep_of[u]]:
                     E = P["epochs"][ep_of[u]]
-                    d[:, E[BE_DXLO]: E[BE_DXLO] + E[BE_DXCNT]] = blk[:, DX_OFF: DX_OFF + E[BE_DXCNT]]
-                    d[:, E[BE_DRLO]: E[BE_DRLO] + E[BE_DRCNT]] = blk[:, DR_OFF: DR_OFF + E[BE_DRCNT]]
+                    d[:, E[self.BE_DXLO]: E[self.BE_DXLO] + E[self.BE_DXCNT]] = blk[:, self.DX_OFF: self.DX_OFF + E[self.BE_DXCNT]]
+                    d[:, E[self.BE_DRLO]: E[self.BE_DRLO] + E[self.BE_DRCNT]] = blk[:, self.DR_OFF: self.DR_OFF + E[self.BE_DRCNT]]
 
     # ---- newton_system! (src/CaNNOLeS.jl:1008-1052), batched ----------------------------------------------------------
     def newton_system(self, vals, rhs, nvar, rho_old, params):

@@ -3,7 +3,7 @@
 A constrained model hands over a KKT pattern whose H_c segment has the model's whole Hessian structure
 (the reference's src/CaNNOLeS.jl:256, :288-291): for a band model every Hessian position appears twice, and an epoch of the band
 program needs up to 18 operand pieces where 15 is what the program always had.  The generator writes a second, wide form for such
-patterns (cnl_plan_get "bandw_*"); tests/support/band_sim_wide.py executes it — the piece count taken from the program — and the
+patterns (cnl_plan_get "bandw_*"); tests/support/band_sim.py executes it — the piece count taken from the program — and the
 result is compared with the oracle exactly as tests/test_band_cpu.py compares the 15-piece program."""
 from types import SimpleNamespace
 
@@ -14,7 +14,6 @@ import cannoles_jl_amd  # noqa: F401
 from cannoles_jl_amd import device_loop, hipldl, synthetic as syn
 from oracle import oracle as O
 from tests.support.band_sim import BandSim
-from tests.support.band_sim_wide import BandSimWide
 from tests.test_float32_cpu import _offset_mask
 
 MODEL_SHAPES = [(300, 4, 2), (1000, 10, 2), (10000, 50, 2), (360, 6, 1), (1000, 8, 2), (1000, 100, 2), (1000, 250, 2), (997, 1, 2)]
@@ -37,7 +36,7 @@ def _model_structure(n, p, hw):
 def _check(s, vals, rhs, params, rho_old=0.0, **opt):
     """tests/test_band_cpu.py's _check, on the wide program"""
     pl, rows, cols = _plan(s, **opt)
-    sim = BandSimWide(pl)
+    sim = BandSim(pl, prefix="bandw")
     assert sim.ok, "the pattern is a band that needs the wide form: the generator must write it"
     B = vals.shape[0]
     v = vals.copy()
@@ -83,7 +82,7 @@ def test_model_band_values_extend_band_values():
 
 @pytest.mark.parametrize("n,p,hw", NEEDS_WIDE)
 def test_model_shaped_patterns_get_the_wide_program(built, n, p, hw):
-    """the 15-piece names keep saying "no band" (tests/support/band_sim.py hard-codes fifteen), the wide program exists, holds at most
+    """the 15-piece names keep saying "no band" (BandSim's default prefix), the wide program exists, holds at most
     twenty pieces and at least one epoch uses more than fifteen; band_pieces = 15 is the behaviour before the wide form"""
     s = _model_structure(n, p, hw)
     pl, _, _ = _plan(s)
@@ -91,7 +90,7 @@ def test_model_shaped_patterns_get_the_wide_program(built, n, p, hw):
     iw, iw4 = pl.array("bandw_info"), pl.array("bandw4_info")
     assert iw[0] == 1 and np.array_equal(iw, iw4)
     assert 15 < iw[7] <= 20
-    sim = BandSimWide(pl)
+    sim = BandSim(pl, prefix="bandw")
     assert 15 < sim.pieces_used() <= sim.NPIECE == iw[7]
     assert not BandSim(pl).ok
     p15, _, _ = _plan(s, band_pieces=15)
@@ -103,7 +102,7 @@ def test_model_shaped_half_width_one_keeps_the_fifteen_piece_program(built):
     s = _model_structure(360, 6, 1)
     pl, _, _ = _plan(s)
     assert pl.array("band_info")[0] == 1 and pl.array("bandw_info")[0] == 0
-    assert BandSimWide(pl, prefix="band").pieces_used() <= 15
+    assert BandSim(pl).pieces_used() <= 15
     pw, _, _ = _plan(s, band_pieces=20)
     assert pw.array("band_info")[0] == 1 and pw.array("bandw_info")[0] == 1 and pw.array("bandw_info")[7] == 20
     for q in range(2):
@@ -161,12 +160,11 @@ def test_wide_program_full_size(built, params):
 
 def test_wide_form_of_a_fifteen_piece_pattern_is_bit_equal(built, params):
     """band_pieces = 20 on a pattern fifteen pieces serve: same steps, same pieces, same arithmetic — every output of the wide
-    interpreter on the wide program equals BandSim's on the 15-piece program bit for bit (the property the GPU test of the wide
-    kernel instances rests on)"""
+    program equals the 15-piece program's bit for bit (the property the GPU test of the wide kernel instances rests on)"""
     s = syn.band_structure(1000, 10)
     pl, _, _ = _plan(s, band_pieces=20)
     assert pl.array("band_info")[0] == 1 and pl.array("bandw_info")[0] == 1 and pl.array("bandw_info")[7] == 20
-    narrow, wide = BandSim(pl), BandSimWide(pl)
+    narrow, wide = BandSim(pl), BandSim(pl, prefix="bandw")
     assert wide.pieces_used() <= 15
     gen = [syn.band_values(s, 4000 + b) for b in range(2)] + [syn.band_values(s, 5000 + b, stress="ladder") for b in range(2)]
     vals, rhs = np.stack([g[0] for g in gen]), np.stack([g[1] for g in gen])
@@ -177,10 +175,6 @@ def test_wide_form_of_a_fifteen_piece_pattern_is_bit_equal(built, params):
     for a, b in zip(out1, out2):
         assert np.array_equal(a, b)
     assert np.array_equal(v1, v2)
-    # ... and the 15-piece program through the wide interpreter: the interpreters agree on common ground
-    out3 = BandSimWide(pl, prefix="band").newton_system(vals.copy(), rhs, s.nvar, 0.0, params)
-    for a, b in zip(out1, out3):
-        assert np.array_equal(a, b)
 
 
 @pytest.mark.parametrize("shape,opt", [((1000, 10, 2), {}), ((360, 6, 1), {"band_pieces": 20}), ((10000, 50, 2), {}), ((1000, 10, 2), {"band_kernel": 2})])

@@ -79,8 +79,8 @@ def run(B, names, n=10000, p=50, rounds=3):
             out = subprocess.run([sys.executable, "-c", RUN % {"root": ROOT, "B": B, "n": n, "p": p, "reps": reps}], env=env, capture_output=True, text=True)
             line = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT")]
             if not line:
-                print(k, "FAILED", out.stderr[-500:])
-                continue
+                # nothing more is started on a device a child may have faulted
+                raise SystemExit(f"{k} FAILED (exit status {out.returncode}): {out.stderr[-500:]}")
             ms, ok = line[0].split()[1:]
             res[k].append(float(ms))
             print(f"round {r} {k:12s} B={B} {float(ms):.4f} ms/step  {B / float(ms):.1f} k systems/s ok={ok}", flush=True)
