@@ -67,11 +67,105 @@ struct Packer {
   }
 };
 
+// The RESIDENT form (band.h): pieces of `vals` are aligned blocks of eight elements that keep their LDS slot while the next epoch of
+// the sweep still needs them, so a block is loaded once instead of once per epoch that touches it.  Starts from today's packing of the
+// epoch (pk) and decides per piece of `vals`: aligned — the blocks its elements lie in, each in a slot of its own — or packed as today.
+// Everything aligned is tried first; while the epoch needs more slots than the lane block has or more loads than there are staging
+// registers, the piece whose packing leaves the least excess (then the fewest blocks of vals touched, then the lowest base) is packed as today — all of
+// them in the end, which is today's epoch.  rhs and factor pieces are today's; the factor pieces take the last slots, one behind the
+// other (a record may straddle two), and a block resident there gives way.
+struct ResidentPacker {
+  struct Item { int32_t arr, base, slot; bool load, keep; };   // keep: an aligned block of vals, resident for the next epoch
+  std::vector<Item> items;
+  std::vector<int32_t> held;   // per slot: base of the aligned block of vals the previous epoch of the sweep left there, -1 none
+  int32_t nslots = 0, nstage = BAND_NPIECE, esz = 8;
+  void start(int32_t slots) { nslots = slots; held.assign(slots, -1); items.clear(); }
+  bool pack(std::vector<int32_t> (&need)[3], Packer& pk) {
+    items.clear();
+    if (!pk.pack(need)) return false;
+    std::vector<Packer::Piece> G, O;
+    int32_t nf = 0;
+    for (const Packer::Piece& pc : pk.pieces) { (pc.arr == 0 ? G : O).push_back(pc); nf += pc.arr == 2; }
+    if (nf > nslots) return false;
+    for (int32_t s = nslots - nf; s < nslots; s++) held[s] = -1;
+    // piece of today's packing an element of vals belongs to (the last piece may be clamped to the array's end and overlap the one before)
+    std::vector<int32_t> owner(need[0].size());
+    for (size_t i = 0; i < need[0].size(); i++) {
+      owner[i] = -1;
+      for (size_t g = 0; g < G.size() && owner[i] < 0; g++)
+        if (need[0][i] >= G[g].base && need[0][i] < G[g].base + 8) owner[i] = (int32_t)g;
+    }
+    std::vector<char> packed(G.size(), 0);
+    std::vector<int32_t> A;
+    int32_t slots = 0, loads = 0, touch = 0;   // touch: 64-byte blocks of vals the epoch's loads touch
+    auto eval = [&]() {
+      A.clear();
+      for (size_t i = 0; i < need[0].size(); i++)
+        if (!packed[owner[i]]) A.push_back(need[0][i] & ~7);
+      A.erase(std::unique(A.begin(), A.end()), A.end());   // (need is sorted)
+      int32_t np = 0, kept = 0;
+      for (char c : packed) np += c;
+      for (int32_t b : A) kept += std::find(held.begin(), held.end(), b) != held.end();
+      slots = (int32_t)A.size() + np + (int32_t)O.size();
+      loads = slots - kept;
+      touch = (int32_t)A.size() - kept;
+      for (size_t g = 0; g < G.size(); g++) if (packed[g]) touch += G[g].base % 8 ? 2 : 1;
+    };
+    auto excess = [&]() { return std::max(0, slots - nslots) + std::max(0, loads - nstage); };
+    eval();
+    while (excess() > 0) {
+      int best = -1, bex = 0, bld = 0;
+      for (size_t g = 0; g < G.size(); g++) {
+        if (packed[g]) continue;
+        packed[g] = 1; eval(); packed[g] = 0;
+        if (best < 0 || excess() < bex || (excess() == bex && touch < bld)) { best = (int)g; bex = excess(); bld = touch; }
+      }
+      if (best < 0) return false;
+      packed[best] = 1;
+      eval();
+    }
+    // slots: resident blocks stay where they are, the factor pieces take the last ones, everything else the lowest free
+    std::vector<char> used(nslots, 0);
+    for (int32_t s = 0; s < nslots; s++) {
+      if (held[s] >= 0 && std::binary_search(A.begin(), A.end(), held[s])) { items.push_back({0, held[s], s, false, true}); used[s] = 1; }
+      else held[s] = -1;
+    }
+    auto place = [&](int32_t arr, int32_t base, bool keep) {
+      int32_t s = 0;
+      while (s < nslots && used[s]) s++;
+      if (s == nslots) return false;
+      used[s] = 1;
+      items.push_back({arr, base, s, true, keep});
+      return true;
+    };
+    int32_t fs = nslots - nf;
+    for (const Packer::Piece& pc : O)
+      if (pc.arr == 2) { used[fs] = 1; items.push_back({2, pc.base, fs++, true, false}); }
+    for (int32_t b : A)
+      if (std::find(held.begin(), held.end(), b) == held.end() && !place(0, b, true)) return false;
+    for (size_t g = 0; g < G.size(); g++)
+      if (packed[g] && !place(0, G[g].base, false)) return false;
+    for (const Packer::Piece& pc : O)
+      if (pc.arr == 1 && !place(1, pc.base, false)) return false;
+    std::stable_sort(items.begin(), items.end(), [](const Item& x, const Item& y) { return x.arr != y.arr ? x.arr < y.arr : x.base < y.base; });
+    for (int32_t s = 0; s < nslots; s++) held[s] = -1;
+    for (const Item& it : items) if (it.keep) held[it.slot] = it.base;
+    return true;
+  }
+  int32_t off(int a, int32_t e) const {
+    for (const Item& it : items)
+      if (it.arr == a && e >= it.base && e < it.base + 8) return (int32_t)((BAND_IN_OFF + 8 * it.slot + (e - it.base)) * esz);
+    return -1;
+  }
+};
+
 }  // namespace
 
 void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ,
-                     int64_t ncon, int nparts_wanted, int esz, int npiece) {
+                     int64_t ncon, int nparts_wanted, int esz, int npiece, bool resident) {
   B = BandPlan();
+  if (resident && (esz != 8 || npiece != BAND_NPIECE)) { B.ok = false; B.why = "the resident form is the 15-piece program of 8-byte elements"; return; }
+  B.resident = resident;
   if (esz != 8 && esz != 4) { B.ok = false; B.why = "element size must be 8 or 4 bytes"; return; }
   if (npiece != BAND_NPIECE && npiece != BAND_NPIECE_WIDE) { B.ok = false; B.why = "piece count must be 15 or 20"; return; }
   B.npiece = npiece;
@@ -292,10 +386,17 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
     pk.len[0] = (int32_t)nnz; pk.len[1] = (int32_t)N; pk.len[2] = (int32_t)(lpart + 16);
     pk.esz = esz; pk.npiece = npiece;
     if (lpart + 16 >= (1 << 27)) return no("factor too long");
+    // resident form: a descriptor carries the slot above the element index (BAND_RES_SLOT_SHIFT)
+    if (resident && (nnz + 8 >= (1 << BAND_RES_SLOT_SHIFT) || N >= (1 << BAND_RES_SLOT_SHIFT) || lpart + 16 >= (1 << BAND_RES_SLOT_SHIFT)))
+      return no("an array is too long for the resident form's piece descriptors");
+    ResidentPacker rp;
+    rp.esz = esz;
     const int32_t ZB = ZERO_OFF * esz;
     // An epoch is a run of BAND_EPOCH steps whose operands must fit the pieces and whose outputs the rings.
     std::string why_not;
-    auto try_epoch = [&](const int32_t u0, const int32_t u1, int32_t* E) -> bool {
+    // (dirs: bit 0 the forward operands, bit 1 the backward ones — the resident form packs an epoch from what the epoch before it IN
+    //  THE SWEEP left in LDS, so its backward operands are written in a second pass from the last epoch to the first)
+    auto try_epoch = [&](const int32_t u0, const int32_t u1, int32_t* E, const int dirs) -> bool {
       auto no = [&](const std::string& w) { why_not = w; return false; };
       // factor events, pivots and rows of the epoch
       int32_t ev_lo = 1 << 30, ev_hi = -1, x_lo = 1 << 30, x_hi = -1, x_cnt = 0, r_lo = 1 << 30, r_hi = -1, r_cnt = 0;
@@ -330,6 +431,7 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
       E[EF(BE_DRLO)] = r_cnt ? (int32_t)(n + r_lo) : 0; E[EF(BE_DRCNT)] = r_cnt;
       // forward operands
       for (int dir = 0; dir < 2; dir++) {
+        if (!(dirs >> dir & 1)) continue;
         std::vector<int32_t> need[3];
         auto want = [&](int32_t s) {
           if (s == -1) return;
@@ -349,7 +451,7 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
           }
         }
         if (dir == 1) for (int32_t i = 0; i < lcnt; i++) need[2].push_back(lbase + i);
-        if (!pk.pack(need)) {
+        if (resident ? !rp.pack(need, pk) : !pk.pack(need)) {
           std::string w = "an epoch needs more operand pieces than a lane holds (part " + std::to_string(part) + ", steps " + std::to_string(u0) + ".." + std::to_string(u1) + (dir ? ", backward" : ", forward") + ":";
           for (auto& pc : pk.pieces) w += " " + std::to_string(pc.arr) + ":" + std::to_string(pc.base);
           B.pieces_short = true;
@@ -357,10 +459,16 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
         }
         int32_t* PP = E + EF(dir == 0 ? BE_FP : BE_BP);
         for (int k = 0; k < npiece; k++) PP[k] = -1;
-        for (const Packer::Piece& pc : pk.pieces) PP[pc.slot] = pc.base | (pc.arr << 28);
+        if (resident) {
+          int k = 0;
+          for (const ResidentPacker::Item& it : rp.items)
+            if (it.load) PP[k++] = it.base | (it.slot << BAND_RES_SLOT_SHIFT) | (it.arr << 28);
+        } else
+          for (const Packer::Piece& pc : pk.pieces) PP[pc.slot] = pc.base | (pc.arr << 28);
+        auto poff = [&](int a, int32_t e) { return resident ? rp.off(a, e) : pk.off(a, e); };
         auto off = [&](int32_t s) -> int32_t {
           if (s == -1) return ZB;
-          return s >= 0 ? pk.off(0, s) : pk.off(1, -(s + 2));
+          return s >= 0 ? poff(0, s) : poff(1, -(s + 2));
         };
         for (int32_t u = u0; u < u1; u++) {
           const StepOp& st = S[u];
@@ -380,14 +488,14 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
             blk[BS_LX] = st.lev_x >= 0 ? (LOUT_OFF + st.lev_x * BAND_LREC - lbh) * esz : ZB;
             blk[BS_DX] = ZB;
           } else {
-            blk[BS_LB] = st.lev_b >= 0 ? pk.off(2, st.lev_b * BAND_LREC) : ZB;
-            blk[BS_LX] = st.lev_x >= 0 ? pk.off(2, st.lev_x * BAND_LREC) : ZB;
+            blk[BS_LB] = st.lev_b >= 0 ? poff(2, st.lev_b * BAND_LREC) : ZB;
+            blk[BS_LX] = st.lev_x >= 0 ? poff(2, st.lev_x * BAND_LREC) : ZB;
             // a factor record must not straddle two pieces that are not adjacent in LDS: pieces of one array are consecutive and
             // contiguous in the array unless clamped at its end, where they may overlap — check every element
             for (int32_t ev : {st.lev_b, st.lev_x})
               if (ev >= 0)
                 for (int i = 0; i < BAND_LREC; i++)
-                  if (pk.off(2, ev * BAND_LREC + i) != pk.off(2, ev * BAND_LREC) + esz * i) return no("internal: factor record not contiguous in LDS");
+                  if (poff(2, ev * BAND_LREC + i) != poff(2, ev * BAND_LREC) + esz * i) return no("internal: factor record not contiguous in LDS");
             blk[BS_DX] = (st.flags & BF_PIVOT_X) ? (DX_OFF + st.xpiv - x_lo) * esz : ZB;
           }
           for (size_t i = 0; i < st.rows.size(); i++) {
@@ -409,12 +517,20 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
       // every epoch but the last has exactly BAND_EPOCH steps: the kernels' step code is specialised by step number modulo
       // BAND_EPOCH (= the number of window slots), so an epoch starts at slot 0
       const int32_t cnt = std::min<int32_t>(BAND_EPOCH, nsteps - u0);
-      if (!try_epoch(u0, u0 + cnt, E.data())) return no(why_not);
+      if (resident && u0 == 0) rp.start(BAND_RES_FSLOTS);
+      if (!try_epoch(u0, u0 + cnt, E.data(), resident ? 1 : 3)) return no(why_not);
       E[EF(BE_NSTEP)] = cnt;
       Q.epochs.insert(Q.epochs.end(), E.begin(), E.end());
       u0 += cnt;
     }
     Q.nepochs = (int32_t)(Q.epochs.size() / EW);
+    if (resident) {
+      rp.start(BAND_NPIECE);   // the backward sweep needs the out ring: the fifteen piece slots
+      for (int32_t e = Q.nepochs - 1; e >= 0; e--) {
+        const int32_t u0 = e * BAND_EPOCH;
+        if (!try_epoch(u0, std::min(u0 + BAND_EPOCH, nsteps), Q.epochs.data() + (size_t)e * EW, 2)) return no(why_not);
+      }
+    }
     {
       int32_t fo = 0;
       for (int32_t e = 0; e < Q.nepochs; e++) { Q.epochs[(size_t)e * EW + EF(BE_FOFF)] = fo; fo += Q.epochs[(size_t)e * EW + EF(BE_OPLEN)]; }

@@ -62,6 +62,21 @@ constexpr int band_lane_elems(int npc) { return band_zero_off(npc) + 1; }
 static_assert(band_lout_off(BAND_NPIECE) == BAND_LOUT_OFF && band_dr_off(BAND_NPIECE) == BAND_DR_OFF && band_zero_off(BAND_NPIECE) == BAND_ZERO_OFF &&
               band_lane_elems(BAND_NPIECE) == BAND_LANE_DOUBLES && band_lane_elems(BAND_NPIECE_WIDE) % 2 == 1, "lane block layout");
 
+// The RESIDENT form of the 15-piece program of 8-byte elements (build_band_plan(..., resident = true); kernel: band.hip,
+// BAND_NPIECE_RESIDENT).  With `vals` interleaved a 64-byte block of eight elements is what memory delivers, and a piece that
+// starts at the first element needed straddles two of them: the block two consecutive epochs share is fetched twice.  In the resident
+// form a piece of `vals` is an ALIGNED block (base a multiple of 8, the last one may be the spare block of the interleaved layout), and
+// a block the next epoch of the sweep still needs keeps its LDS slot and is not loaded again.  Staged loads and LDS slots are
+// decoupled: descriptor k of an epoch is loaded into staging register set k and names the slot it is committed to,
+//   arr << 28 | slot << BAND_RES_SLOT_SHIFT | element,
+// unused descriptors (-1) commit nothing.  The kernel that runs it stores factor records directly, so the forward sweep has the four
+// slots of the out ring beside the fifteen piece slots (the lane block and the zero cell are unchanged); the backward sweep keeps
+// fifteen.  An epoch that fits neither the slots nor the fifteen staging sets with every piece aligned packs pieces as today until it
+// does (band.cpp, ResidentPacker).  Steps, arithmetic, summation order and records are those of the 15-piece program.
+constexpr int BAND_RES_SLOT_SHIFT = 23;
+constexpr int BAND_RES_FSLOTS = BAND_NPIECE + BAND_LOUT_MAX / 8;     // 19 slots of the forward sweep
+static_assert(BAND_RES_FSLOTS * 8 <= BAND_ZERO_OFF && BAND_RES_FSLOTS <= 32, "resident slots inside the lane block, five bits in a descriptor");
+
 // cnl_options.batch_layout = 1 (include/cannoles_hip.h): `vals` interleaved over groups of BAND_IL_GROUP problems in blocks of eight
 // doubles — element e of problem p at ((p / 32 * band_il_blocks(nnz) + e / 8) * 32 + p % 32) * 8 + e % 8.  One spare block per problem:
 // an operand piece is eight doubles from ANY element, the last one may reach into the block behind the array's last.
@@ -125,6 +140,7 @@ struct BandPlan {
   std::string why;            // why not, when !ok
   bool pieces_short = false;  // !ok because an epoch needs more than npiece operand pieces (and for no other reason found before that)
   int32_t npiece = BAND_NPIECE;   // operand pieces per epoch the program was built for: lane block and epoch block follow it
+  bool resident = false;      // the resident form (see BAND_RES_SLOT_SHIFT)
   int32_t nparts = 0;
   int32_t m0 = 0;             // part 0 pivots variables [0, m0), part 1 pivots [m0 + BAND_HW, n) downwards (nparts == 2)
   int32_t n = 0, N = 0, nnz = 0;
@@ -136,7 +152,8 @@ struct BandPlan {
 // esz: bytes per element of the kernel that runs the program (8: double, 4: float), the scale of its LDS byte offsets;
 // npiece: BAND_NPIECE or BAND_NPIECE_WIDE.  The packing of the operands does not depend on npiece: a pattern that fits 15 pieces gives
 // the same steps, pieces and arithmetic in both forms, only the out ring, the zero cell and the epoch fields sit further back.
+// resident: the resident form (esz = 8, npiece = BAND_NPIECE only).
 void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ,
-                     int64_t ncon, int nparts_wanted, int esz = 8, int npiece = BAND_NPIECE);
+                     int64_t ncon, int nparts_wanted, int esz = 8, int npiece = BAND_NPIECE, bool resident = false);
 
 }  // namespace cnl

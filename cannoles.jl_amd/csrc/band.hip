@@ -343,9 +343,19 @@ __device__ __forceinline__ void bstep(T (&xs)[NS + 1], const BOps<T>& OP, const 
 // bit-equal outputs.
 // T = float: the element arrays of LaunchArgs (vals, rhs, d, L, rho_old, rho) hold float arrays (launch_band_f32); params are
 // Float32 values widened to double, narrowed back here exactly.
+// NPCX = BAND_NPIECE_RESIDENT (RES below): the program is the RESIDENT form of the 15-piece one (band.h) — a piece descriptor names the
+// LDS slot its staged piece is committed to, an unused descriptor commits nothing (its slot may hold a block an earlier epoch
+// loaded), and the forward sweep's slots reach into the out ring, which the kernel that stores factor records directly does not
+// use.  Everything else is the 15-piece kernel.  (A value of the piece-count parameter, not a fourth parameter: the other
+// instances keep their names and, every difference being `if constexpr`, their code.)
+constexpr int BAND_NPIECE_RESIDENT = BAND_NPIECE + 256;
 #define EF(F) band_ef(F, NPC)
-template <class T, int NL, int NPC>
-__global__ void __launch_bounds__(128, (NL <= 8 && NPC == BAND_NPIECE ? 2 : 1)) band_newton_kernel(const BandDev P, const LaunchArgs Ain) {
+template <class T, int NL, int NPCX>
+__global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1)) band_newton_kernel(const BandDev P, const LaunchArgs Ain) {
+  constexpr bool RES = NPCX == BAND_NPIECE_RESIDENT;
+  constexpr int NPC = RES ? BAND_NPIECE : NPCX;
+  static_assert(!RES || (direct_records(NL) && NPC == BAND_NPIECE && sizeof(T) == 8), "the resident form: Float64, 32 problems per workgroup, 15 pieces");
+  constexpr int DBITS = RES ? BAND_RES_SLOT_SHIFT : 28;   // element bits of a piece descriptor
   constexpr int NI = NL / 8;
   constexpr int LANE_D = band_lane_elems(NPC), LOUT_OFF = band_lout_off(NPC), DX_OFF = band_dx_off(NPC), DR_OFF = band_dr_off(NPC),
                 ZERO_OFF = band_zero_off(NPC), EW = band_ew(NPC);
@@ -439,17 +449,19 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPC == BAND_NPIECE ? 2 : 1)) 
   static_assert(BAND_REC_MAX <= 256, "record buffer: one dwordx4 per lane");
   // The mover is written for back-to-back issue: the NPC piece descriptors of an epoch come with one scalar load, unused
   // pieces are skipped with a wave-uniform branch (a load that hits in cache costs the CU's memory pipeline what any other costs),
-  // every staged piece is written to LDS whether used or not.  One load per piece and problem group: base pointer and stride of the
+  // every staged piece is written to LDS whether used or not (resident form: used pieces only, each to the slot its descriptor names).  One load per piece and problem group: base pointer and stride of the
   // piece's array are selected with scalar instructions, the lane's offset is problem * stride + element.  (Three guarded loads
   // made the compiler form all three 64-bit addresses of every piece up front — 96 NI VGPRs; selecting among per-array offset
   // arrays made it index them in scratch memory; lambdas instead of macros put every captured variable into scratch.)
 #define BAND_ISSUE1(K, I) if constexpr (I < NI) stg[K][I] = *reinterpret_cast<const T*>(pb + ((movp[I] * strd + tl) << LS));
 #define BAND_COMMIT1(K, I) if constexpr (I < NI) *reinterpret_cast<T*>(wblk + ldsb[I] + (BAND_IN_OFF + 8 * K) * ES) = stg[K][I];
+  /* resident form: to the descriptor's slot (wave-uniform) */
+#define BAND_COMMITR1(K, I) if constexpr (I < NI) *reinterpret_cast<T*>(wslot_ + ldsb[I]) = stg[K][I];
 #define BAND_ISSUE(K)                                                                                                         \
   if (pcs[K] >= 0) {   /* (wave-uniform) */                                                                                   \
     const int pc = pcs[K];                                                                                                    \
     const int arr = pc >> 28;                                                                                                 \
-    const int el_ = (pc & ((1 << 28) - 1)) + (arr == 2 ? loff8 : 0);                                                          \
+    const int el_ = (pc & ((1 << DBITS) - 1)) + (arr == 2 ? loff8 : 0);                                                          \
     /* lane offset (elements) = problem * strd + tl, tl = t * tm + (t >> 3) * gap with t = m + element of the lane: the caller's    \
        arrays are problem-major (m = 0, t < 8: gap = 0) or interleaved in blocks of eight, the factor is element-major (see        \
        lbase_g: a row of NL elements per record element, tm = NL) or problem-major (DREC false) */                           \
@@ -467,7 +479,14 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPC == BAND_NPIECE ? 2 : 1)) 
     const unsigned tl = t_ * tm_ + (t_ >> 3) * gap_;                                                                          \
     BAND_ISSUE1(K, 0) BAND_ISSUE1(K, 1) BAND_ISSUE1(K, 2) BAND_ISSUE1(K, 3)                                                   \
   }
-#define BAND_COMMIT(K) { BAND_COMMIT1(K, 0) BAND_COMMIT1(K, 1) BAND_COMMIT1(K, 2) BAND_COMMIT1(K, 3) }
+  /* (at commit time pcs[] still holds the descriptors of the epoch being committed: the next epoch's are read behind the commit) */
+#define BAND_COMMIT(K)                                                                                                        \
+  if constexpr (RES) {                                                                                                        \
+    if (pcs[K] >= 0) {                                                                                                        \
+      char* wslot_ = wblk + (BAND_IN_OFF + 8 * ((pcs[K] >> BAND_RES_SLOT_SHIFT) & 31)) * ES;                                  \
+      BAND_COMMITR1(K, 0) BAND_COMMITR1(K, 1) BAND_COMMITR1(K, 2) BAND_COMMITR1(K, 3)                                         \
+    }                                                                                                                         \
+  } else { BAND_COMMIT1(K, 0) BAND_COMMIT1(K, 1) BAND_COMMIT1(K, 2) BAND_COMMIT1(K, 3) }
   // (macros, not lambdas: a closure made the compiler keep every captured variable — the staging registers included — in scratch memory)
 #define BAND_ISSUE_DESC(EP, OFS) { cptr E_ = (EP) + (OFS); _Pragma("unroll") for (int k_ = 0; k_ < NPC; k_++) pcs[k_] = E_[k_]; }
   /* the epoch's step / row blocks (the streams are padded: reading past the epoch's blocks is harmless) */
@@ -844,7 +863,23 @@ static hipError_t launch_band_t(const BandDev& P, int nl, const LaunchArgs& a, h
   return hipErrorInvalidConfiguration;
 }
 
-hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece) { return launch_band_t<double>(P, nl, a, stream, npiece); }
+// the resident instance (named behind the others: instances are emitted in the order they are first named, and the others keep their
+// place in the code object)
+static hipError_t launch_band_resident(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece);
+
+hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece, bool resident) {
+  return resident ? launch_band_resident(P, nl, a, stream, npiece) : launch_band_t<double>(P, nl, a, stream, npiece);
+}
 hipError_t launch_band_f32(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece) { return launch_band_t<float>(P, nl, a, stream, npiece); }
+
+static hipError_t launch_band_resident(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece) {
+  if (nl != 32 || npiece != BAND_NPIECE || !(a.layout & 1)) return hipErrorInvalidConfiguration;
+  const size_t ldsb = band_lds_bytes(P.nparts, nl, (int)sizeof(double), npiece);
+  auto kern = band_newton_kernel<double, 32, BAND_NPIECE_RESIDENT>;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)ldsb));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3((a.batch + nl - 1) / nl), dim3(64 * P.nparts), ldsb, stream, P, a);
+  return hipGetLastError();
+}
 
 }  // namespace cnl

@@ -51,9 +51,13 @@ struct cnl_plan {
     std::vector<int32_t> info, pinfo[2];
   };
   BandSlot band_prog[2][2];
+  // the RESIDENT form of band_prog[0][0] (band.h: aligned blocks of `vals` that stay in LDS while the next epoch needs them), built
+  // beside it unless tuning band_resident = 0; runs the Float64 handles of 32 problems per workgroup with interleaved `vals`
+  BandSlot band_res;
 };
 // the names cnl_plan_get answers for band_prog[f32][wide]: "band_*" / "band4_*" keep describing the 15-piece program
 static const char* const kBandPrefix[2][2] = {{"band_", "bandw_"}, {"band4_", "bandw4_"}};
+static const char* const kBandResPrefix = "bandr_";   // ... and for band_res, a prefix of its own
 
 struct cnl_handle {
   cnl_plan* plan = nullptr;
@@ -135,6 +139,7 @@ struct cnl_handle {
   cnl::BandDev bd{};
   int band_nl = 16;            // problems per workgroup
   int band_npiece = 15;        // operand pieces per epoch of the program in bd: 15, or 20 = the wide kernel instances
+  bool band_resident = false;  // bd holds the plan's resident program (cnl_plan::band_res): the resident kernel instance runs it
   bool jac_segments = false;   // the J_F and the J_c entries are one run of slots each: [jf_lo, jf_lo + jf_n), [jc_lo, jc_lo + jc_n)
   int64_t jf_lo = 0, jf_n = 0, jc_lo = 0, jc_n = 0;
   int layout = 0;              // band handles: bit 0 = vals (cnl_options.batch_layout), bit 1 = rhs interleaved over groups of 32 problems (band.h)
@@ -175,13 +180,14 @@ const char* const kHostLayout = "host-pointer calls take the reference's problem
 
 // band programs -> the summaries cnl_plan_get returns as "<prefix>info" / "<prefix>part<q>"
 void band_summaries(cnl_plan* p) {
-  for (auto& row : p->band_prog)
-    for (cnl_plan::BandSlot& s : row) {
-      const cnl::BandPlan& Bp = s.B;
-      // (the last word: the piece count of a wide program; 0 = the fifteen of "band_*" / "band4_*", as it always was)
-      s.info = {Bp.ok ? 1 : 0, Bp.nparts, Bp.m0, Bp.n, Bp.N, Bp.nnz, (int32_t)Bp.lsize, Bp.ok && Bp.npiece != cnl::BAND_NPIECE ? Bp.npiece : 0};
-      for (int q = 0; q < 2; q++) s.pinfo[q] = {Bp.part[q].nsteps, Bp.part[q].nepochs, Bp.part[q].npiv, Bp.part[q].nevents, (int32_t)Bp.part[q].loff};
-    }
+  cnl_plan::BandSlot* const all[5] = {&p->band_prog[0][0], &p->band_prog[0][1], &p->band_prog[1][0], &p->band_prog[1][1], &p->band_res};
+  for (cnl_plan::BandSlot* sp : all) {
+    cnl_plan::BandSlot& s = *sp;
+    const cnl::BandPlan& Bp = s.B;
+    // (the last word: the piece count of a wide program; 0 = the fifteen of "band_*" / "band4_*", as it always was)
+    s.info = {Bp.ok ? 1 : 0, Bp.nparts, Bp.m0, Bp.n, Bp.N, Bp.nnz, (int32_t)Bp.lsize, Bp.ok && Bp.npiece != cnl::BAND_NPIECE ? Bp.npiece : 0};
+    for (int q = 0; q < 2; q++) s.pinfo[q] = {Bp.part[q].nsteps, Bp.part[q].nepochs, Bp.part[q].npiv, Bp.part[q].nevents, (int32_t)Bp.part[q].loff};
+  }
 }
 
 // The band programs of a pattern for one element size: the 15-piece program whenever the pattern fits it, word for word what it always
@@ -197,6 +203,12 @@ void build_band_programs(cnl_plan* p, const int64_t* rows1, const int64_t* cols1
   Bw.why = B15.ok ? "fifteen operand pieces per epoch suffice" : B15.why;
   if (o.band_pieces != 15 && (B15.ok ? o.band_pieces == 20 : B15.pieces_short))
     cnl::build_band_plan(Bw, N, nnz, rows1, cols1, nvar, nequ, ncon, nparts, esz, cnl::BAND_NPIECE_WIDE);
+  if (esz == 8) {
+    cnl::BandPlan& Br = p->band_res.B;
+    Br = cnl::BandPlan();
+    Br.why = !o.band_resident ? "tuning band_resident = 0" : B15.why;
+    if (B15.ok && o.band_resident) cnl::build_band_plan(Br, N, nnz, rows1, cols1, nvar, nequ, ncon, nparts, esz, cnl::BAND_NPIECE, true);
+  }
 }
 // the program a handle runs: the wide one where the plan has it (the pattern needs it, or tuning band_pieces = 20)
 const cnl::BandPlan& band_program(const cnl_plan* plan, bool f32) {
@@ -489,7 +501,7 @@ int run_band(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_
   a.layout = h->layout;
   if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
   const hipError_t e = h->f32 ? cnl::launch_band_f32(h->bd, h->band_nl, a, stream, h->band_npiece)
-                              : cnl::launch_band(h->bd, h->band_nl, a, stream, h->band_npiece);
+                              : cnl::launch_band(h->bd, h->band_nl, a, stream, h->band_npiece, h->band_resident);
   g_launches[0]++;
   if (e != hipSuccess)
     return fail(CNL_ERR_HIP, std::string("band kernel launch (") + (h->f32 ? "Float32, " : "") + std::to_string(h->band_nl) +
@@ -1039,22 +1051,14 @@ static int check_device(int device) {
 // allocates the factor records; h->band says whether they serve the handle.  They do not where the program does not fit them —
 // *unfit then names the reason and the caller decides what that means (a Float64 handle has the register-front kernel, a Float32
 // handle nothing).  An option that asks for an instance that does not exist is an error.
-static int setup_band(cnl_handle* h, const cnl::BandPlan& Bp, const char** unfit) {
+static int setup_band(cnl_handle* h, const cnl::BandPlan& Bp0, const char** unfit) {
   const cnl_plan* plan = h->plan;
   const int esz = h->f32 ? (int)sizeof(float) : (int)sizeof(double);
   const int64_t batch = h->batch;
   int rc;
-  h->band_npiece = Bp.npiece;
-  const bool wide = Bp.npiece != cnl::BAND_NPIECE;
+  h->band_npiece = Bp0.npiece;
+  const bool wide = Bp0.npiece != cnl::BAND_NPIECE;
   cnl::BandDev& bd = h->bd;
-  for (int q = 0; q < Bp.nparts; q++) {
-    if ((rc = upload(h, Bp.part[q].fops, &bd.fops[q]))) return rc;
-    if ((rc = upload(h, Bp.part[q].bops, &bd.bops[q]))) return rc;
-    if ((rc = upload(h, Bp.part[q].epochs, &bd.epochs[q]))) return rc;
-    if ((rc = upload(h, Bp.part[q].borders, &bd.borders[q]))) return rc;
-    bd.nsteps[q] = Bp.part[q].nsteps; bd.nepochs[q] = Bp.part[q].nepochs; bd.loff[q] = Bp.part[q].loff;
-  }
-  bd.nparts = Bp.nparts; bd.m0 = Bp.m0; bd.n = Bp.n; bd.N = Bp.N; bd.nnz = Bp.nnz; bd.nvar = (int32_t)plan->nvar; bd.lsize = Bp.lsize;
   // 16 problems per workgroup (two workgroups = four wavefronts per CU: one per SIMD) up to the 8192 problems that fills; above,
   // 32 per workgroup (the LDS of a CU holds two such workgroups: 16384 problems resident) — tools/time_band.py
   // (wide program, Float64: 16 at every batch — three workgroups per CU hold 48 problems where one of 32 would hold 32, and the
@@ -1064,6 +1068,19 @@ static int setup_band(cnl_handle* h, const cnl::BandPlan& Bp, const char** unfit
   if (h->band_nl != 8 && h->band_nl != 16 && h->band_nl != 32) return fail(CNL_ERR_ARG, "band_problems_per_group must be 8, 16 or 32");
   if (wide && !cnl::band_wide_has(esz, h->band_nl))   // (there is a wide Float32 instance for each of the three)
     return fail(CNL_ERR_ARG, "band_problems_per_group = 32: the wide band program (20 operand pieces) has Float64 kernels for 8 and 16 problems per workgroup only");
+  // The resident form of the 15-piece program where the plan has it and the handle is the one it was built for: Float64, `vals`
+  // interleaved (an aligned block is then one 64-byte run per problem), 32 problems per workgroup (the instance that stores factor
+  // records directly, so that the out ring's LDS is free in the forward sweep).  Same steps and arithmetic: bit-equal outputs.
+  h->band_resident = !h->f32 && !wide && h->band_nl == 32 && plan->opt.batch_layout == CNL_LAYOUT_INTERLEAVED && plan->band_res.B.ok;
+  const cnl::BandPlan& Bp = h->band_resident ? plan->band_res.B : Bp0;
+  for (int q = 0; q < Bp.nparts; q++) {
+    if ((rc = upload(h, Bp.part[q].fops, &bd.fops[q]))) return rc;
+    if ((rc = upload(h, Bp.part[q].bops, &bd.bops[q]))) return rc;
+    if ((rc = upload(h, Bp.part[q].epochs, &bd.epochs[q]))) return rc;
+    if ((rc = upload(h, Bp.part[q].borders, &bd.borders[q]))) return rc;
+    bd.nsteps[q] = Bp.part[q].nsteps; bd.nepochs[q] = Bp.part[q].nepochs; bd.loff[q] = Bp.part[q].loff;
+  }
+  bd.nparts = Bp.nparts; bd.m0 = Bp.m0; bd.n = Bp.n; bd.N = Bp.N; bd.nnz = Bp.nnz; bd.nvar = (int32_t)plan->nvar; bd.lsize = Bp.lsize;
   // 32-bit byte offsets inside a workgroup's problems
   const uint64_t span = (uint64_t)esz * (uint64_t)h->band_nl * (uint64_t)std::max<int64_t>({plan->nnz, plan->N, bd.lsize});
   if (span >= (1ull << 32)) { *unfit = "the arrays of a workgroup's problems span 4 GB or more (32-bit offsets of the band kernels)"; return CNL_OK; }
@@ -1355,6 +1372,7 @@ static int plan_create_impl(cnl_plan** plan, int64_t N, int64_t nnz, const int64
     build_band_programs(p, rows1, cols1, 8);
     const cnl::BandPlan &b15 = p->band_prog[0][0].B, &bw = p->band_prog[0][1].B;
     if (verbose) fprintf(stderr, "[cnl] band program: %s%s\n", b15.ok ? "ok" : "no: ", b15.ok ? "" : b15.why.c_str());
+    if (verbose && b15.ok) fprintf(stderr, "[cnl] resident band program: %s%s\n", p->band_res.B.ok ? "ok" : "no: ", p->band_res.B.ok ? "" : p->band_res.B.why.c_str());
     if (verbose && !b15.ok && b15.pieces_short)
       fprintf(stderr, "[cnl] wide band program (%d pieces): %s%s\n", cnl::BAND_NPIECE_WIDE, bw.ok ? "ok" : "no: ", bw.ok ? "" : bw.why.c_str());
     // the programs for 4-byte elements (Float32 handles): the same blocks, every LDS offset scaled
@@ -1447,6 +1465,8 @@ int cnl_plan_get(const cnl_plan* plan, const char* name, int32_t* out, int64_t* 
     for (int t = 0; t < 2; t++)
       for (int w = 0; w < 2; w++)
         if (s.rfind(kBandPrefix[t][w], 0) == 0) { f = &plan->band_prog[t][w]; plen = std::strlen(kBandPrefix[t][w]); }
+    // "bandr_*": the resident form of "band_*" (band.h; info[0] = 0 where the plan has none)
+    if (s.rfind(kBandResPrefix, 0) == 0) { f = &plan->band_res; plen = std::strlen(kBandResPrefix); }
     if (!f) return fail(CNL_ERR_ARG, "unknown plan array: " + s);
     const std::string rest = s.substr(plen);
     if (rest == "info") { src = f->info.data(); n = (int64_t)f->info.size(); }
@@ -1955,7 +1975,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   cfg[5] = (h->dense || h->gdense) ? 3 : (h->use_v2 ? (h->staged ? 4 : 2) : 1);
   if (h->lean && !h->dense && !h->gdense) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->tail) cfg[5] |= 32;                             // the remainder of the batch runs on a handle of its own (split_tail)
-  if (h->band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts, layout, operand pieces per epoch
+  if (h->band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->band_resident << 24) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts, layout, operand pieces per epoch
   if (h->djt.rv_ntiles > 0) cfg[5] |= 128;               // row f1 runs on column tiles (kernels.h: DevJt::rv_*)
   cfg[6] = h->wpb2;
   cfg[7] = (int64_t)h->lds2;

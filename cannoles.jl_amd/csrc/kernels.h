@@ -176,7 +176,8 @@ struct BandDev {
 // newton_system! / try_to_factorize of a.batch problems on the band kernels, nl problems per workgroup (8, 16 or 32); a.L = the
 // band factor storage [batch][P.lsize]
 // npiece: operand pieces per epoch of the program P was uploaded from (BandPlan::npiece): 15, or 20 = the wide kernel instances
-hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece = 15);
+// resident: P is the resident form of the 15-piece program (band.h) — nl = 32, `vals` interleaved (a.layout & 1)
+hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece = 15, bool resident = false);
 // the same on Float32 data: a.vals / rhs / d / L / rho_old / rho hold float arrays (stored through the double* fields), a.params the
 // Float32 parameters widened to double; P is the 4-byte program (build_band_plan with esz = 4), P.lsize counts floats
 hipError_t launch_band_f32(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece = 15);

@@ -351,6 +351,8 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  * + 16 when newton_system / factorize run the LEAN instantiation (fast-class fronts with row-form products only), [6]=its wavefronts per workgroup,
  * [7]=its LDS bytes per workgroup; [5] + 32 when the remainder of the batch runs on a handle of its own (cnl_options.split_tail),
  * + 64 when cnl_newton_system runs on the band kernels (then bits 8-15 = problems per workgroup, bits 16-23 = parts of the chain,
+ *   bit 24 = the RESIDENT form of the 15-piece program runs (aligned blocks of `vals` kept in LDS: Float64, batch_layout = 1, 32 problems
+ *   per workgroup; tuning "band_resident=0" keeps the 15-piece program — bit-equal outputs either way),
  *   bits 25-26 = cnl_options.batch_layout / rhs interleaved, bits 28-33 = operand pieces per epoch of the band program: 15, or 20
  *   for the wide form),
  * + 128 when cnl_residual_vectors_dev runs on column tiles. */
