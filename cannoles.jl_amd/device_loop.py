@@ -15,6 +15,11 @@ active problem.  The linear algebra of the path goes through the C ABI on device
 
 Only the model callbacks (residuals, Jacobian / Hessian values) are torch expressions of a closed-form family
 (`BandQuadFamily`); `vals`, `rhs` and `d` never cross PCIe.  There is no CPU fallback.
+
+Element types: `solve!` is generic in T, and so is this loop — a family built with dtype = float32 runs it in Float32 throughout
+(a Float32 band handle, the `_f32_dev` passes, `cnl_outer_state_f32` and the `cnl_outer_*_f32_dev` kernels, ParamCaNNOLeS(Float32) and
+the tolerances of eps(Float32)); nothing of a Float32 run is computed in Float64 except the reductions that csrc/outer_step.hip
+documents.  A pattern without a Float32 band program raises CnlError: there is no fallback to Float64.
 """
 import numpy as np
 
@@ -24,10 +29,16 @@ class BandQuadFamily:
         F_i(x) = sum_{j in band(i)} A_ij x_j + q_i x_i^2 / 2 - y_i,        c_k(x) = sum_{j in block k} C_kj x_j - e_k.
     Jacobian values in the structure's COO order: A + [i == j] q_i x_i and C; sum_i r_i Hess F_i = diag(q r) on the
     lower-band Hessian structure (off-diagonal slots are structural zeros); the constraints are linear (zero Hessian).
-    `host_model(b)` is the numpy twin of problem b with the callbacks outer_loop.solve expects (an NLPModels-like object)."""
+    `host_model(b)` is the numpy twin of problem b with the callbacks outer_loop.solve expects (an NLPModels-like object).
+    dtype = float32: the data is generated as for float64 and then rounded to float32; `h` keeps the rounded values as float64, so
+    host_model(b) is the Float64 twin of exactly the data the device sees, and `d` and every device callback work in torch.float32."""
 
-    def __init__(self, s, B, seed, torch, device, curvature=0.3, start=0.3, noise=0.01):
+    def __init__(self, s, B, seed, torch, device, curvature=0.3, start=0.3, noise=0.01, dtype=np.float64):
         self.s, self.B, self.torch, self.device = s, int(B), torch, device
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.float64, np.float32):
+            raise TypeError(f"BandQuadFamily({self.dtype}): Float64 and Float32 only")
+        self.tdtype = torch.float32 if self.dtype == np.float32 else torch.float64
         n, m, p = s.nvar, s.nequ, s.ncon
         rng = np.random.default_rng(seed)
         jr, jc = np.asarray(s.jF[0]) - 1, np.asarray(s.jF[1]) - 1
@@ -44,8 +55,10 @@ class BandQuadFamily:
         self.h = dict(A=A, q=q, Cv=Cv, x0=xs + start * rng.normal(size=(B, n)))
         self.h["y"] = self._F_np(A, q, xs, np.zeros((B, m))) + noise * rng.normal(size=(B, m))
         self.h["e"] = self._c_np(Cv, xs, np.zeros((B, p)))
+        if self.dtype == np.float32:
+            self.h = {k: v.astype(np.float32).astype(np.float64) for k, v in self.h.items()}
         self.hr, self.hcl = np.asarray(s.hF[0]) - 1, np.asarray(s.hF[1]) - 1
-        t = lambda a, dt=None: torch.as_tensor(a, dtype=dt or torch.float64, device=device)
+        t = lambda a, dt=None: torch.as_tensor(a, dtype=dt or self.tdtype, device=device)
         self.d = {k: t(v) for k, v in self.h.items()}
         self.jr_t, self.jc_t = t(jr, torch.long), t(jc, torch.long)
         self.cc_t = t(cc, torch.long)
@@ -54,6 +67,18 @@ class BandQuadFamily:
         self.jdiag_t = t((jr == jc).astype(np.float64))
         self.hdiag_t = t((self.hr == self.hcl).astype(np.float64))
         self.hr_t = t(self.hr, torch.long)
+
+    def take(self, indices):
+        """the family of the selected problems, in the given order: the structure (index lists, their tensors) is shared, the model data
+        is copied — for running sub-batches"""
+        idx = np.asarray(list(indices), dtype=np.int64)
+        sub = object.__new__(type(self))
+        sub.__dict__.update(self.__dict__)
+        sub.B = len(idx)
+        sub.h = {k: v[idx] for k, v in self.h.items()}
+        idx_t = self.torch.as_tensor(idx, dtype=self.torch.long, device=self.device)
+        sub.d = {k: v[idx_t].contiguous() for k, v in self.d.items()}
+        return sub
 
     @staticmethod
     def _row_lists(rows, nrows, pad):
@@ -80,7 +105,7 @@ class BandQuadFamily:
     # ---- device callbacks, batched: X [B, n] -> ...
     def residual(self, X):
         t = self.torch
-        prod = t.cat([self.d["A"] * X[:, self.jc_t], t.zeros((self.B, 1), dtype=t.float64, device=self.device)], dim=1)
+        prod = t.cat([self.d["A"] * X[:, self.jc_t], t.zeros((self.B, 1), dtype=self.tdtype, device=self.device)], dim=1)
         return prod[:, self.row_ent_t].sum(dim=2) + 0.5 * self.d["q"] * X * X - self.d["y"]
 
     def jac_vals(self, X):
@@ -92,8 +117,8 @@ class BandQuadFamily:
     def cons(self, X):
         t = self.torch
         if self.s.ncon == 0:
-            return t.zeros((self.B, 1), dtype=t.float64, device=self.device)
-        prod = t.cat([self.d["Cv"] * X[:, self.cc_t], t.zeros((self.B, 1), dtype=t.float64, device=self.device)], dim=1)
+            return t.zeros((self.B, 1), dtype=self.tdtype, device=self.device)
+        prod = t.cat([self.d["Cv"] * X[:, self.cc_t], t.zeros((self.B, 1), dtype=self.tdtype, device=self.device)], dim=1)
         return prod[:, self.crow_ent_t].sum(dim=2) - self.d["e"]
 
     def jacc_vals(self, X):
@@ -153,11 +178,34 @@ def kkt_pattern_of(fam):
     return rows, cols, (nnzhF, nnzhc, len(jFr), len(jcr))
 
 
+def _element_type(fam, dtype):
+    """(numpy dtype, is Float32) of a run: the family's by default; a run in another element type than the family's data is refused"""
+    fdt = np.dtype(getattr(fam, "dtype", np.float64))
+    dt = fdt if dtype is None else np.dtype(dtype)
+    if dt not in (np.float64, np.float32):
+        raise TypeError(f"element type {dt}: the lockstep loop runs in Float64 or Float32")
+    if dt != fdt:
+        raise TypeError(f"a {fdt} family cannot run in {dt}: build the family with dtype={dt} (the model data is rounded once, at construction)")
+    return dt, dt == np.float32
+
+
+def _element_ops(t, tdt, dev, f32):
+    """(rdot, rsum, fdiv, fsqrt) for the loop's framework expressions.  Float64: the plain expressions.  Float32: the reductions as
+    csrc/outer_step.hip computes them — exactly widened operands, summed in double, rounded to float once —, and quotient / square root
+    rounded correctly (computed in double and rounded once, which gives the correctly rounded Float32 result; the framework's own
+    Float32 division by a host scalar is a multiplication by its reciprocal)."""
+    if not f32:
+        return (lambda a, b: (a * b).sum(dim=1)), (lambda a: a.sum(dim=1)), (lambda a, b: a / b), t.sqrt
+    wide = lambda a: a.double() if hasattr(a, "double") else t.full((), float(a), dtype=t.float64, device=dev)
+    return (lambda a, b: (a.double() * b.double()).sum(dim=1).to(tdt)), (lambda a: a.double().sum(dim=1).to(tdt)), \
+           (lambda a, b: (wide(a) / wide(b)).to(tdt)), (lambda a: a.double().sqrt().to(tdt))
+
+
 PROFILE = False   # tools/time_device_loop.py --profile: wall time per section of a global step (synchronises at every section)
 
 
 def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=None, rtol=None, Fatol=None, Frtol=None, delta_dec=0.1,
-                       device_index=0, layout="auto", tuning=None):
+                       device_index=0, layout="auto", tuning=None, dtype=None):
     """All B problems of `fam` in lockstep on the device.  Returns a dict of numpy arrays: solution [B, n], multipliers,
     status (list of strings), iter, nfact, nlinsolve, nbk, objective, and `steps` (global steps = batched Newton rounds).
 
@@ -169,12 +217,14 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     from . import hipldl
     t = fam.torch
     dev = fam.device
-    eps = float(np.finfo(float).eps)
+    dt, f32 = _element_type(fam, dtype)
+    tdt = t.float32 if f32 else t.float64
+    eps = float(np.finfo(dt).eps)
     atol = np.sqrt(eps) if atol is None else atol
     rtol = np.sqrt(eps) if rtol is None else rtol
     Fatol = np.sqrt(eps) if Fatol is None else Fatol
     Frtol = eps if Frtol is None else Frtol
-    params = hipldl.default_params() if params is None else np.ascontiguousarray(params, dtype=np.float64)
+    params = hipldl.default_params(dt) if params is None else np.ascontiguousarray(params, dtype=dt)
     dmin, rhomax, gammaA = float(params[1]), float(params[6]), float(params[8])
     s, B = fam.s, fam.B
     n, m, p = s.nvar, s.nequ, s.ncon
@@ -191,14 +241,17 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     if layout in ("auto", "interleaved"):
         try:
             L = hipldl.HIPLDLStruct(N, rows, cols, None, n, m, p, batch=B, device=device_index,
-                                    options=hipldl.Options(batch_layout=hipldl.LAYOUT_INTERLEAVED, **tuning))
+                                    options=hipldl.Options(batch_layout=hipldl.LAYOUT_INTERLEAVED, **tuning), dtype=dt)
         except hipldl.CnlError:
             if layout == "interleaved":
                 raise
     if L is None:
-        L = hipldl.HIPLDLStruct(N, rows, cols, None, n, m, p, batch=B, device=device_index, options=hipldl.Options(**tuning) if tuning else None)
+        L = hipldl.HIPLDLStruct(N, rows, cols, None, n, m, p, batch=B, device=device_index, options=hipldl.Options(**tuning) if tuning else None,
+                                dtype=dt)
     lib = hipldl.lib()
-    f64 = dict(dtype=t.float64, device=dev)
+    f64 = dict(dtype=tdt, device=dev)   # (the run's element type)
+    rdot, rsum, fdiv, fsqrt = _element_ops(t, tdt, dev, f32)
+    huge = float("inf") if f32 else 1e60   # T(1e60), src/CaNNOLeS.jl:638, 647
     Z = lambda *sh: t.zeros(sh, **f64)
     ZI = lambda dt, *sh: t.zeros(sh, dtype=dt, device=dev)
     o_I = nnzhF + nnzhc + nnzjF + nnzjc
@@ -236,14 +289,14 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
 
     W = lambda mask, a, b: t.where(mask if a.dim() == 1 else mask[:, None], a, b)
     smax = 100.0
-    dual_scaling = lambda l_: (t.clamp(l_.abs().sum(dim=1) / p, min=smax) / smax) if p > 0 else t.ones(B, **f64)
+    dual_scaling = lambda l_: fdiv(t.clamp(fdiv(rsum(l_.abs()), p), min=smax), smax) if p > 0 else t.ones(B, **f64)
     ninf = lambda a: a.abs().max(dim=1).values if a.shape[1] else Z(B)
-    cnorm2 = lambda c_: t.sqrt((c_ * c_).sum(dim=1)) if p else Z(B)
+    cnorm2 = lambda c_: fsqrt(rdot(c_, c_)) if p else Z(B)
 
     # ---- state (every array is updated IN PLACE from here on: the kernels hold its address) -------------------------
     x = fam.d["x0"].clone()
     Fx = fam.residual(x).contiguous()
-    fx = (0.5 * (Fx * Fx).sum(dim=1)).contiguous()
+    fx = (0.5 * rdot(Fx, Fx)).contiguous()
     Jv = fam.jac_vals(x).contiguous()
     Jcv = fam.jacc_vals(x)          # the family's constraints are linear: one array serves the current and the trial point
     Jcv = Jcv.contiguous() if p else Z(B, 1)
@@ -254,9 +307,9 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     rhs_cur, nrm0 = Z(B, N), Z(B, 2)
     resid_vectors(Jv, Jcv, r, lam, Fx, cx, rhs_cur, nrm0)
     normdual, normprimal = nrm0[:, 0].clone(), nrm0[:, 1].clone()
-    epsF = (Fatol + Frtol * 2 * t.sqrt(fx)).contiguous()
+    epsF = (Fatol + Frtol * 2 * fsqrt(fx)).contiguous()
     epstol = (atol + rtol * normdual).contiguous()
-    epsc = t.sqrt(epstol).contiguous()
+    epsc = fsqrt(epstol).contiguous()
 
     rv_rhs, rv_nrm = Z(B, N), Z(B, 2)
 
@@ -271,7 +324,7 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
         normprimal.copy_(W(mask, ninf(cx[:, :p]) if p else Z(B), normprimal))
         r.copy_(r2)
 
-    small_residual = (2 * t.sqrt(fx) <= epsF) & (cnorm2(cx) <= epsc)
+    small_residual = (2 * fsqrt(fx) <= epsF) & (cnorm2(cx) <= epsc)
     first_order = t.maximum(normdual / dual_scaling(lam), normprimal) <= epstol
     chk0 = small_residual & ~first_order
     if bool(chk0.any()):
@@ -299,7 +352,7 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     masks = {k: t.zeros(B, dtype=t.bool, device=dev) for k in ("act", "need", "brk", "ext", "lsm", "rej", "chk", "done_in", "tired", "small_res", "bt")}
     flags = ZI(t.int32, 8)
     flags_h = t.zeros(8, dtype=t.int32).pin_memory()
-    S = hipldl.cnl_outer_state()
+    S = hipldl.cnl_outer_state_f32() if f32 else hipldl.cnl_outer_state()
     for k, v in dict(B=B, n=n, m=m, p=p, P=P, N=N, nnzjF=nnzjF, nnzjc=nnzjc, max_inner=max_inner, dmin=dmin, rhomax=rhomax,
                      delta_dec=delta_dec, smax=smax, gammaA=gammaA, eps2=eps ** 2).items():
         setattr(S, k, v)
@@ -314,6 +367,10 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
         setattr(S, k, v.data_ptr())
     Sref = C.byref(S)
     chk_ = hipldl._check
+    sfx = "_f32_dev" if f32 else "_dev"
+    k_begin, k_newton_done, k_extrapolated, k_trial_done, k_end, k_ls_begin, k_ls_test, k_ls_step, k_ls_take = (
+        getattr(lib, "cnl_outer_" + k + sfx) for k in ("begin", "newton_done", "extrapolated", "trial_done", "end", "ls_begin", "ls_test", "ls_step",
+                                                       "ls_take"))
 
     def read_flags():
         flags_h.copy_(flags, non_blocking=True)
@@ -336,7 +393,7 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     # cnl_outer_trial_done_dev, and one per round of backtracking when a line search runs
     while steps < max_steps:
         tk = _time.perf_counter()
-        chk_(lib.cnl_outer_begin_dev(Sref, st))
+        chk_(k_begin(Sref, st))
         any_act, any_need, any_ext, any_ls = read_flags()[:4]
         if not any_act:
             break
@@ -347,28 +404,28 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
             prepare(vals_cur, fam.hess_vals(x, r), Jv, Jcv, delta)
             ro_tmp.copy_(rho_old)
             hipldl.newton_system_dev(L, ptr(vals_cur), ptr(rhs_cur), ptr(d_new), ptr(ro_tmp), ptr(rho_new), ptr(nf_new), ptr(ok_new), params, st)
-        chk_(lib.cnl_outer_newton_done_dev(Sref, 1 if any_need else 0, st))
+        chk_(k_newton_done(Sref, 1 if any_need else 0, st))
         dx = d[:, :n]
         tk = tick("newton", tk)
         # ---- extrapolation step, :654-668
         if any_ext:   # (a superset test: problems that broke above are masked out by `ext`)
             hipldl.trial_point_dev(L, ptr(x), ptr(r), ptr(lam) if p else 0, ptr(d), 1e4, ptr(xt_e), ptr(rt_e), ptr(lamt_e) if p else 0,
                                    ptr(dlam_e) if p else 0, st)
-            chk_(lib.cnl_outer_extrapolated_dev(Sref, st))
+            chk_(k_extrapolated(Sref, st))
         tk = tick("extrapolation", tk)
         # ---- Armijo line search on the merit function, :1054-1112
         if any_ls:
             resid_vectors(Jv, Jcv, Fx, lam_ls, Fx, cx, rv_rhs, rv_nrm)      # dual part: Jx'Fx - Jc'(lam - c/delta), lam_ls by cnl_outer_newton_done_dev
-            chk_(lib.cnl_outer_ls_begin_dev(Sref, st))
+            chk_(k_ls_begin(Sref, st))
             Fl.copy_(fam.residual(xl))
             cl.copy_(fam.cons(xl))
-            chk_(lib.cnl_outer_ls_test_dev(Sref, 1, st))
+            chk_(k_ls_test(Sref, 1, st))
             while read_flags()[6]:
-                chk_(lib.cnl_outer_ls_step_dev(Sref, st))
+                chk_(k_ls_step(Sref, st))
                 Fl.copy_(fam.residual(xl))       # (rows of problems that do not backtrack are recomputed from an unchanged xl: same values)
                 cl.copy_(fam.cons(xl))
-                chk_(lib.cnl_outer_ls_test_dev(Sref, 0, st))
-            chk_(lib.cnl_outer_ls_take_dev(Sref, st))
+                chk_(k_ls_test(Sref, 0, st))
+            chk_(k_ls_take(Sref, st))
         tk = tick("line_search", tk)
         Ft.copy_(fam.residual(xt))
         ct.copy_(fam.cons(xt))
@@ -376,7 +433,7 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
         Jt.copy_(fam.jac_vals(xt))
         resid_vectors(Jt, Jcv, rt, lamt, Ft, ct, rhs_t, nrm_t)
         tk = tick("trial_eval", tk)
-        chk_(lib.cnl_outer_trial_done_dev(Sref, st))
+        chk_(k_trial_done(Sref, st))
         any_rej, any_chk = read_flags()[4:6]
         tk = tick("trial_done", tk)
         if any_rej:   # dual at (x, r, lam) again; primal keeps the trial's value, as in the reference (:742-747)
@@ -384,14 +441,15 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
             rhs_cur[:, :n] = t.where(masks["rej"][:, None], rv_rhs[:, :n], rhs_cur[:, :n])
         if any_chk:
             small_res_check(masks["chk"])
-        chk_(lib.cnl_outer_end_dev(Sref, st))
+        chk_(k_end(Sref, st))
         tk = tick("rej_chk_end", tk)
     t.cuda.synchronize(dev)
     loop_seconds = _time.perf_counter() - t_loop0
     names = {UNKNOWN: "unknown", FIRST: "first_order", SMALL: "small_residual", EXC: "exception", TIRED: "max_eval", STALL: "stalled"}
     out = {"solution": x.cpu().numpy(), "multipliers": lam[:, :p].cpu().numpy(), "status": [names[int(v)] for v in status.cpu().numpy()],
            "iter": it.cpu().numpy(), "nfact": nfact.cpu().numpy(), "nlinsolve": nlin.cpu().numpy(), "nbk": nbk.cpu().numpy(),
-           "objective": fx.cpu().numpy(), "steps": steps, "kernel": "band" if L.config.get("band") else L.config["kernel"], "vals_layout": "interleaved" if L.config.get("batch_layout") else "problem-major",
+           "objective": fx.cpu().numpy(), "dtype": str(dt), "r": r.cpu().numpy(), "normdual": normdual.cpu().numpy(),
+           "normprimal": normprimal.cpu().numpy(), "epstol": epstol.cpu().numpy(), "steps": steps, "kernel": "band" if L.config.get("band") else L.config["kernel"], "vals_layout": "interleaved" if L.config.get("batch_layout") else "problem-major",
            "loop_seconds": loop_seconds}   # the global steps alone (the symbolic analysis of the pattern and the start-up evaluations are not in it)
     if prof is not None:
         out["profile_ms_per_step"] = {k: 1e3 * v / max(steps, 1) for k, v in prof.items()}
@@ -400,7 +458,7 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
 
 
 def solve_batch_device_framework(fam, params=None, max_steps=400, max_inner=10000, atol=None, rtol=None, Fatol=None, Frtol=None, delta_dec=0.1,
-                       device_index=0):
+                       device_index=0, dtype=None):
     """The loop as rounds 2-3 ran it: masks and masked state updates as ~150 framework launches per global step.  Kept as the
     executable restatement solve_batch_device is compared with (tests/test_gpu_parity.py).
     All B problems of `fam` in lockstep on the device.  Returns a dict of numpy arrays: solution [B, n], multipliers,
@@ -408,12 +466,14 @@ def solve_batch_device_framework(fam, params=None, max_steps=400, max_inner=1000
     from . import hipldl
     t = fam.torch
     dev = fam.device
-    eps = float(np.finfo(float).eps)
+    dt, f32 = _element_type(fam, dtype)
+    tdt = t.float32 if f32 else t.float64
+    eps = float(np.finfo(dt).eps)
     atol = np.sqrt(eps) if atol is None else atol
     rtol = np.sqrt(eps) if rtol is None else rtol
     Fatol = np.sqrt(eps) if Fatol is None else Fatol
     Frtol = eps if Frtol is None else Frtol
-    params = hipldl.default_params() if params is None else np.ascontiguousarray(params, dtype=np.float64)
+    params = hipldl.default_params(dt) if params is None else np.ascontiguousarray(params, dtype=dt)
     dmin, rhomax, gammaA = float(params[1]), float(params[6]), float(params[8])
     s, B = fam.s, fam.B
     n, m, p = s.nvar, s.nequ, s.ncon
@@ -421,8 +481,10 @@ def solve_batch_device_framework(fam, params=None, max_steps=400, max_inner=1000
     P = max(p, 1)
     rows, cols, (nnzhF, nnzhc, nnzjF, nnzjc) = kkt_pattern_of(fam)
     nnz = len(rows)
-    L = hipldl.HIPLDLStruct(N, rows, cols, None, n, m, p, batch=B, device=device_index)
-    f64 = dict(dtype=t.float64, device=dev)
+    L = hipldl.HIPLDLStruct(N, rows, cols, None, n, m, p, batch=B, device=device_index, dtype=dt)
+    f64 = dict(dtype=tdt, device=dev)   # (the run's element type)
+    rdot, rsum, fdiv, fsqrt = _element_ops(t, tdt, dev, f32)
+    huge = float("inf") if f32 else 1e60   # T(1e60), src/CaNNOLeS.jl:638, 647
     Z = lambda *sh: t.zeros(sh, **f64)
     o_I = nnzhF + nnzhc + nnzjF + nnzjc
 
@@ -456,13 +518,13 @@ def solve_batch_device_framework(fam, params=None, max_steps=400, max_inner=1000
 
     W = lambda mask, a, b: t.where(mask if a.dim() == 1 else mask[:, None], a, b)
     smax = 100.0
-    dual_scaling = lambda l_: (t.clamp(l_.abs().sum(dim=1) / p, min=smax) / smax) if p > 0 else t.ones(B, **f64)
+    dual_scaling = lambda l_: fdiv(t.clamp(fdiv(rsum(l_.abs()), p), min=smax), smax) if p > 0 else t.ones(B, **f64)
     ninf = lambda a: a.abs().max(dim=1).values if a.shape[1] else Z(B)
 
     # ---- start, src/CaNNOLeS.jl:470-560
     x = fam.d["x0"].clone()
     Fx = fam.residual(x)
-    fx = 0.5 * (Fx * Fx).sum(dim=1)
+    fx = 0.5 * rdot(Fx, Fx)
     Jv, Jcv = fam.jac_vals(x), fam.jacc_vals(x)
     cx = fam.cons(x)
     r = Fx.clone()
@@ -470,10 +532,10 @@ def solve_batch_device_framework(fam, params=None, max_steps=400, max_inner=1000
     prepare(vals_cur, None, Jv, Jcv, delta)
     lam = multipliers(vals_cur, r, True)
     rhs_cur, normdual, normprimal = resid_vectors(vals_cur, r, lam, Fx, cx)
-    epsF = Fatol + Frtol * 2 * t.sqrt(fx)
+    epsF = Fatol + Frtol * 2 * fsqrt(fx)
     epstol = atol + rtol * normdual
-    epsc = t.sqrt(epstol)
-    cnorm2 = lambda c_: t.sqrt((c_ * c_).sum(dim=1)) if p else Z(B)
+    epsc = fsqrt(epstol)
+    cnorm2 = lambda c_: fsqrt(rdot(c_, c_)) if p else Z(B)
 
     def small_res_check(mask, lam, rhs_cur, normdual, normprimal, r):
         """src/CaNNOLeS.jl:873-897 for the problems of `mask`: r = F, least-squares multipliers, dual, primal = [0; c]"""
@@ -485,7 +547,7 @@ def solve_batch_device_framework(fam, params=None, max_steps=400, max_inner=1000
         rhs_n = W(mask, rhs2, rhs_cur)
         return lam_n, rhs_n, W(mask, nd2, normdual), W(mask, ninf(cx[:, :p]) if p else Z(B), normprimal), r2
 
-    small_residual = (2 * t.sqrt(fx) <= epsF) & (cnorm2(cx) <= epsc)
+    small_residual = (2 * fsqrt(fx) <= epsF) & (cnorm2(cx) <= epsc)
     first_order = t.maximum(normdual / dual_scaling(lam), normprimal) <= epstol
     chk = small_residual & ~first_order
     if bool(chk.any()):
@@ -510,7 +572,7 @@ def solve_batch_device_framework(fam, params=None, max_steps=400, max_inner=1000
     nf_new = t.zeros(B, dtype=t.int32, device=dev)
     ok_new = t.zeros(B, dtype=t.int32, device=dev)
     xt_e, rt_e, lamt_e, dlam_e = Z(B, n), Z(B, m), Z(B, P), Z(B, P)
-    phi = lambda F_, c_, l_, et: 0.5 * (F_ * F_).sum(dim=1) - ((l_ * c_).sum(dim=1) if p else 0.0) + (et * (c_ * c_).sum(dim=1) / 2 if p else 0.0)
+    phi = lambda F_, c_, l_, et: 0.5 * rdot(F_, F_) - (rdot(l_, c_) if p else 0.0) + (et * rdot(c_, c_) / 2 if p else 0.0)
     steps = 0
     # host synchronisations per global step: one for the branch flags below, one for (rejected, small-residual) further down,
     # and one per round of backtracking when a line search runs
@@ -540,24 +602,24 @@ def solve_batch_device_framework(fam, params=None, max_steps=400, max_inner=1000
             nfact = nfact + t.where(need, nf_new.to(t.int64), 0)
             nlin = nlin + need.to(t.int64)
             # `broken`: the inner loop is left at once; the end-of-iteration tests below still run for it (:638-652)
-            brk = need & ((rho_new > rhomax) | (ok_new == 0) | ~t.isfinite(d_new).all(dim=1) | (fx >= 1e60))
+            brk = need & ((rho_new > rhomax) | (ok_new == 0) | ~t.isfinite(d_new).all(dim=1) | (fx >= huge))
             act = act & ~brk
         dx = d[:, :n]
         ext, lsm = act & (inner == 0), act & (inner > 0)
         # ---- extrapolation step, :654-668
         if any_ext:   # (a superset test: problems that broke above are masked out by `ext`)
-            epsk = W(ext, t.maximum(t.minimum(1e3 * delta, 99 * epsk / 100), 9 * epsk / 10), epsk)
+            epsk = W(ext, t.maximum(t.minimum(1e3 * delta, fdiv(99 * epsk, 100)), fdiv(9 * epsk, 10)), epsk)
             hipldl.trial_point_dev(L, ptr(x), ptr(r), ptr(lam) if p else 0, ptr(d), 1e4, ptr(xt_e), ptr(rt_e), ptr(lamt_e) if p else 0,
                                    ptr(dlam_e) if p else 0, st)
             xt, rt, lamt = W(ext, xt_e, xt), W(ext, rt_e, rt), W(ext, lamt_e, lamt)
         # ---- Armijo line search on the merit function, :1054-1112
         if any_ls:
-            lam_ls = lam - cx / delta[:, None] if p else lam
+            lam_ls = lam - fdiv(cx, delta[:, None]) if p else lam
             prepare(vals_cur, None, Jv, Jcv, delta)
             g, _, _ = resid_vectors(vals_cur, Fx, lam_ls, Fx, cx)      # dual part: Jx'Fx - Jc'(lam - c/delta)
-            Dphi = (g[:, :n] * dx).sum(dim=1)
+            Dphi = rdot(g[:, :n], dx)
             if p:
-                eta = W(lsm, 1.0 / delta, eta)
+                eta = W(lsm, fdiv(1.0, delta), eta)
             phix = phi(Fx, cx, lam, eta)
             alpha = t.ones(B, **f64)
             xl = x + dx
@@ -583,7 +645,7 @@ def solve_batch_device_framework(fam, params=None, max_steps=400, max_inner=1000
         acc_state = act & ((inner > 0) | good)
         x, r, Fx, cx = W(acc_state, xt, x), W(acc_state, rt, r), W(acc_state, Ft, Fx), W(acc_state, ct, cx)
         Jv, Jcv = W(acc_state, Jt, Jv), W(acc_state, Jct, Jcv)
-        fx = W(acc_state, 0.5 * (Ft * Ft).sum(dim=1), fx)
+        fx = W(acc_state, 0.5 * rdot(Ft, Ft), fx)
         acc_lam = act & good
         lam = W(acc_lam, lamt, lam)
         rhs_cur = W(act, rhs_t, rhs_cur)
@@ -591,14 +653,14 @@ def solve_batch_device_framework(fam, params=None, max_steps=400, max_inner=1000
         delta_next = delta
         if p:
             dr_ = act & (inner > 0) & (ndh <= 0.99 * normdual + epsk / 2) & (nph > 0.99 * normprimal + epsk / 2)
-            delta_next = W(dr_, t.clamp(delta / 10, min=dmin), delta)
+            delta_next = W(dr_, t.clamp(fdiv(delta, 10), min=dmin), delta)
         inner = inner + act.to(t.int64)
         tired = inner > max_inner
         # ---- end of the inner loop -> end of the outer iteration, :765-800 (tests first: one synchronisation for both branches)
         done_in = (act & (good | tired)) | brk
         normdual, normprimal = W(done_in, ndh, normdual), W(done_in, nph, normprimal)
         first_order = t.maximum(normdual / dual_scaling(lam), normprimal) <= epstol
-        small_residual = (2 * t.sqrt(fx) <= epsF) & (cnorm2(cx) <= epsc)
+        small_residual = (2 * fsqrt(fx) <= epsF) & (cnorm2(cx) <= epsc)
         chk = done_in & small_residual & ~first_order
         any_rej, any_chk = t.stack([rej.any(), chk.any()]).tolist()
         if any_rej:   # dual at (x, r, lam) again; primal keeps the trial's value, as in the reference (:742-747)
@@ -617,6 +679,7 @@ def solve_batch_device_framework(fam, params=None, max_steps=400, max_inner=1000
     names = {UNKNOWN: "unknown", FIRST: "first_order", SMALL: "small_residual", EXC: "exception", TIRED: "max_eval", STALL: "stalled"}
     out = {"solution": x.cpu().numpy(), "multipliers": lam[:, :p].cpu().numpy(), "status": [names[int(v)] for v in status.cpu().numpy()],
            "iter": it.cpu().numpy(), "nfact": nfact.cpu().numpy(), "nlinsolve": nlin.cpu().numpy(), "nbk": nbk.cpu().numpy(),
-           "objective": fx.cpu().numpy(), "steps": steps, "kernel": L.config["kernel"]}
+           "objective": fx.cpu().numpy(), "dtype": str(dt), "r": r.cpu().numpy(), "normdual": normdual.cpu().numpy(),
+           "normprimal": normprimal.cpu().numpy(), "epstol": epstol.cpu().numpy(), "steps": steps, "kernel": L.config["kernel"]}
     L.close()
     return out

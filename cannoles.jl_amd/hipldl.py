@@ -47,6 +47,8 @@ ABI_SYMBOLS = [
     "cnl_factorize_f32_dev", "cnl_solve_f32_dev", "cnl_newton_system_f32_dev", "cnl_interleave_f32_dev", "cnl_deinterleave_f32_dev",
     "cnl_prepare_newton_system_f32_dev", "cnl_residual_vectors_f32_dev", "cnl_residual_vectors_jac_f32_dev",
     "cnl_cgls_multipliers_f32_dev", "cnl_cgls_multipliers_jac_f32_dev", "cnl_trial_point_f32_dev",
+    "cnl_outer_begin_f32_dev", "cnl_outer_newton_done_f32_dev", "cnl_outer_extrapolated_f32_dev", "cnl_outer_trial_done_f32_dev",
+    "cnl_outer_end_f32_dev", "cnl_outer_ls_begin_f32_dev", "cnl_outer_ls_test_f32_dev", "cnl_outer_ls_step_f32_dev", "cnl_outer_ls_take_f32_dev",
 ]
 
 
@@ -94,6 +96,23 @@ class cnl_outer_state(C.Structure):
                     "xt", "rt", "Ft", "ct", "Jt", "Jct", "lamt", "rhs_t", "nrm_t",
                     "xt_e", "rt_e", "lamt_e")] +
                 [(k, C.c_double) for k in ("gammaA", "eps2")] +
+                [(k, C.c_void_p) for k in ("ls_g", "xl", "Fl", "cl", "lam_ls", "alpha", "Dphi", "phix", "eta", "nbk", "bt")])
+
+
+class cnl_outer_state_f32(C.Structure):
+    """struct cnl_outer_state_f32 of include/cannoles_hip.h: cnl_outer_state for a Float32 loop (float scalars; the arrays are float32)"""
+    _fields_ = ([(k, C.c_int64) for k in ("B", "n", "m", "p", "P", "N", "nnzjF", "nnzjc", "max_inner")] +
+                [(k, C.c_float) for k in ("dmin", "rhomax", "delta_dec", "smax")] +
+                [(k, C.c_void_p) for k in (
+                    "status", "it", "flags", "nf_new", "ok_new",
+                    "inner", "nfact", "nlin",
+                    "phase0", "act", "need", "brk", "ext", "lsm", "rej", "chk", "done_in", "tired", "small_res",
+                    "normdual", "normprimal", "combined", "combined_hat", "delta", "ndh", "nph", "fx", "epsk", "epstol", "epsF", "epsc", "rho_old",
+                    "d", "d_new", "ro_tmp", "rho_new",
+                    "x", "r", "Fx", "cx", "Jv", "Jcv", "lam", "rhs_cur",
+                    "xt", "rt", "Ft", "ct", "Jt", "Jct", "lamt", "rhs_t", "nrm_t",
+                    "xt_e", "rt_e", "lamt_e")] +
+                [(k, C.c_float) for k in ("gammaA", "eps2")] +
                 [(k, C.c_void_p) for k in ("ls_g", "xl", "Fl", "cl", "lam_ls", "alpha", "Dphi", "phix", "eta", "nbk", "bt")])
 
 
@@ -251,8 +270,10 @@ def lib():
         for fn in ("cnl_outer_begin_dev", "cnl_outer_extrapolated_dev", "cnl_outer_trial_done_dev", "cnl_outer_end_dev", "cnl_outer_ls_begin_dev",
                    "cnl_outer_ls_step_dev", "cnl_outer_ls_take_dev"):
             getattr(L, fn).argtypes = [vp, vp]
-        L.cnl_outer_newton_done_dev.argtypes = [vp, C.c_int, vp]
-        L.cnl_outer_ls_test_dev.argtypes = [vp, C.c_int, vp]
+            getattr(L, fn.replace("_dev", "_f32_dev")).argtypes = [vp, vp]
+        for sfx in ("_dev", "_f32_dev"):
+            getattr(L, "cnl_outer_newton_done" + sfx).argtypes = [vp, C.c_int, vp]
+            getattr(L, "cnl_outer_ls_test" + sfx).argtypes = [vp, C.c_int, vp]
         if L.cnl_version() < 200:
             raise RuntimeError(f"{LIB_PATH}: cnl_version() = {L.cnl_version()}, ABI version 0.2.0 or later required")
         _lib = L

@@ -418,6 +418,48 @@ int cnl_cgls_multipliers_jac_f32_dev(cnl_handle* h, int64_t nnzjF, int64_t nnzjc
 int cnl_trial_point_f32_dev(cnl_handle* h, const float* d_x, const float* d_r, const float* d_lambda, const float* d_d,
                             float max_dlambda, float* d_xt, float* d_rt, float* d_lambdat, float* d_dlambda, void* stream);
 
+/* ---- bookkeeping of the batched outer / inner loop for T = Float32 (row f3; `solve!` is generic in T) --------------------------
+ * The nine entry points of the Float64 section (cnl_outer_begin_dev ... cnl_outer_end_dev) on a Float32 state: `cnl_outer_state_f32`
+ * has the members of `cnl_outer_state` in the same order, float* where that has double* and float for dmin, rhomax, delta_dec, smax,
+ * gammaA, eps2; the integer and mask arrays keep their types.  Same semantics, status codes, flags and argument rules (CNL_ERR_ARG
+ * for a null state, B <= 0 or a missing array, with nothing launched).  The C side cannot tell a Float64 array from a Float32 one:
+ * handing a state of the other element type over is the caller's error.  With a Float32 handle's `_f32_dev` passes around them
+ * (above) they run the whole lockstep loop in Float32 (cannoles.jl_amd/device_loop.py, dtype = float32).
+ * Arithmetic: every decision and update is in float, each operation rounded separately and every literal rounded to float first,
+ * as the reference's T(0.99), T(1e3), T(100.0) (src/CaNNOLeS.jl:532, 623, 659, 664, 736, 750, 760-761, 1106).  Two points differ
+ * from a textual float copy of the Float64 kernels:
+ *   * T(1e60) (:638, 647) is Inf32, so the `broken` test on the objective is fx >= infinity: a finite fx never breaks a Float32
+ *     problem (3e38 does not, inf does);
+ *   * the reductions — |Ft|^2, the three sums of the merit function, g'dx, the count of non-finite entries of d, sum |lambda| and
+ *     sum c^2 — accumulate in double from the exactly widened float operands and are rounded to float once.  The reference's Float32
+ *     dot products have no prescribed order and such a sum is within one rounding of any of them; the decisions do not depend on
+ *     the summation order.                                                                                                        */
+typedef struct cnl_outer_state_f32 {
+  int64_t B, n, m, p, P /* max(p, 1) */, N, nnzjF, nnzjc, max_inner;
+  float dmin, rhomax, delta_dec, smax;
+  int32_t *status, *it, *flags /* [8] */, *nf_new, *ok_new;
+  int64_t *inner, *nfact, *nlin;
+  uint8_t *phase0, *act, *need, *brk, *ext, *lsm, *rej, *chk, *done_in, *tired, *small_res;
+  float *normdual, *normprimal, *combined, *combined_hat, *delta, *ndh, *nph, *fx, *epsk, *epstol, *epsF, *epsc, *rho_old;
+  float *d, *d_new, *ro_tmp, *rho_new;
+  float *x, *r, *Fx, *cx, *Jv, *Jcv, *lam, *rhs_cur;
+  float *xt, *rt, *Ft, *ct, *Jt, *Jct, *lamt, *rhs_t, *nrm_t /* [B][2] */;
+  float *xt_e, *rt_e, *lamt_e;
+  float gammaA, eps2;
+  float *ls_g, *xl, *Fl, *cl, *lam_ls, *alpha, *Dphi, *phix, *eta;
+  int64_t* nbk;
+  uint8_t* bt;
+} cnl_outer_state_f32;
+int cnl_outer_begin_f32_dev(const cnl_outer_state_f32* st, void* stream);
+int cnl_outer_newton_done_f32_dev(const cnl_outer_state_f32* st, int did_newton, void* stream);
+int cnl_outer_extrapolated_f32_dev(const cnl_outer_state_f32* st, void* stream);
+int cnl_outer_trial_done_f32_dev(const cnl_outer_state_f32* st, void* stream);
+int cnl_outer_ls_begin_f32_dev(const cnl_outer_state_f32* st, void* stream);
+int cnl_outer_ls_test_f32_dev(const cnl_outer_state_f32* st, int first, void* stream);
+int cnl_outer_ls_step_f32_dev(const cnl_outer_state_f32* st, void* stream);
+int cnl_outer_ls_take_f32_dev(const cnl_outer_state_f32* st, void* stream);
+int cnl_outer_end_f32_dev(const cnl_outer_state_f32* st, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
