@@ -1,0 +1,738 @@
+// capi_handle.cpp — the device state of a handle, for both element types: creation from a plan (uploads, the choice of the kernel
+// backend and its configuration, band kernels, batch layout, row lists of rows f1 / f4), destruction, and what a caller may read
+// back or switch on a handle (configuration, timing, layout lengths and conversions).
+#include "handle.h"
+
+namespace {
+
+// Float64 handles have the register-front kernel beside the band kernels.  On the pattern that needs the wide program it measured
+// FASTER than the wide kernel (model_band_structure(10000, 50), same machine, alternated: 8 192 problems 8.31 against 8.67 ms, 16 384
+// problems 15.78 against 17.42 ms; `vals` interleaved 8.68 / 17.2 ms — DESIGN section 4, tools/time_band_wide.py), so a Float64 handle
+// runs the wide program only where tuning band_pieces = 20 asks for it; the 15-piece program is chosen as it always was.
+// (Float32 handles have no other kernel: they always take the wide program where the pattern needs it.)
+bool band_wide_serves_f64(const cnl_plan* plan) {
+  return band_program(plan, false).npiece == cnl::BAND_NPIECE || plan->opt.band_pieces == cnl::BAND_NPIECE_WIDE;
+}
+
+int choose_config(cnl_handle* h) {
+  const cnl::Plan& P = h->plan->P;
+  cnl::DevPlan& dp = h->dp;
+  int64_t pb_off = std::max<int64_t>(P.fwd_peak, P.bwd_peak);
+  pb_off = (pb_off + 1) & ~(int64_t)1;
+  int64_t wv_off = pb_off + ((P.panel_max + 1) & ~1);
+  int64_t work = wv_off + 2 * (int64_t)((P.fmax + 1) & ~1);
+  if (work >= ((int64_t)1 << 30)) return fail(CNL_ERR_DIM, "work area too large");
+  dp.pb_off = (int32_t)pb_off;
+  dp.wv_off = (int32_t)wv_off;
+  dp.work_doubles = (int32_t)work;
+  size_t maxlds = cnl::max_lds_bytes();
+  if (maxlds == 0) return fail(CNL_ERR_HIP, "cannot query LDS size (no HIP device?)");
+  maxlds = std::min<size_t>(maxlds, 160 * 1024);
+  cnl::KernelConfig& c = h->cfg;
+  const size_t hdr = 16 * sizeof(double);
+  const size_t per = (size_t)work * sizeof(double);
+  int tpp, ppb, ldsw;
+  if (hdr + per <= maxlds) {
+    ldsw = 1;
+    if (P.fmax <= 96) {
+      tpp = 64;
+      // problems per workgroup: leave room for two workgroups per CU when the work area
+      // allows it, and spread small batches over the 256 CUs
+      size_t fit = (maxlds - hdr) / per;
+      size_t fit2 = maxlds / 2 > hdr ? (maxlds / 2 - hdr) / per : 0;
+      size_t cap = fit2 >= 1 ? fit2 : fit;
+      size_t want = (size_t)std::min<int64_t>(16, std::max<int64_t>(1, h->batch / 256));
+      ppb = 1;
+      for (int cand : {16, 8, 4, 2, 1})
+        if ((size_t)cand <= cap && (size_t)cand <= want) { ppb = cand; break; }
+    } else {
+      tpp = P.fmax <= 400 ? 256 : 1024;
+      ppb = 1;
+    }
+  } else {
+    ldsw = 0;
+    tpp = P.fmax <= 96 ? 64 : (P.fmax <= 400 ? 256 : 1024);
+    ppb = tpp == 64 ? 4 : 1;
+  }
+  const cnl::Tuning& o = h->plan->opt;
+  if (o.v1_tpp > 0) tpp = o.v1_tpp;
+  if (o.v1_ppb > 0) ppb = o.v1_ppb;
+  if (o.v1_lds >= 0) ldsw = o.v1_lds;
+  c.tpp = tpp; c.ppb = ppb; c.lds_work = ldsw;
+  c.lds_bytes = hdr + (ldsw ? (size_t)ppb * per : 0);
+  if (c.lds_bytes > maxlds) return fail(CNL_ERR_DIM, "kernel configuration exceeds LDS");
+  return CNL_OK;
+}
+
+int setup_v2(cnl_handle* h) {
+  const cnl::Plan& P = h->plan->P;
+  h->use_v2 = false;
+  const cnl::Tuning& o = h->plan->opt;
+  if (!P.v2_ok || !o.register_front) return CNL_OK;
+  if (!h->plan->gpos.empty() && (o.general_dense == 2 || (h->plan->prefer_dense && h->batch <= 16))) return CNL_OK;  // the dense route (capi_plan.cpp, plan_create_impl); 2: wherever it is possible
+  cnl::DevPlan2& d = h->dp2;
+  // streams are over-read by the prefetcher: pad with zeros
+  std::vector<int32_t> rec(P.rec), brec(P.brec);
+  rec.resize(rec.size() + 2048, 0);
+  brec.resize(brec.size() + 2048, 0);
+  int rc;
+  if ((rc = upload(h, rec, &d.rec))) return rc;
+  if ((rc = upload(h, brec, &d.brec))) return rc;
+  d.nsuper = P.nsuper; d.N = (int32_t)P.N; d.nnz = (int32_t)P.nnz; d.rho_begin = P.rho_begin; d.nvar = (int32_t)P.nvar;
+  d.N0 = (int32_t)P.N;
+  d.reccap = (P.rec_maxlen + 64 + 3) & ~3;  // + slack: the product loop reads up to 48 words past a list
+  d.breccap = (P.brec_maxlen + 3) & ~3;
+  d.recwords = std::max(d.reccap, 2 * d.breccap);
+  d.u2_peak = P.u2_peak;
+  // (round 5, found by the randomised run with lds_pad = 0: the out-of-line elimination of a class-64 front publishes its pivot row at
+  //  lb[0 .. 65] of the staging area — lanes beyond the pivot park their value at index TE + 1 —, two doubles more than the 64 reserved
+  //  here; without padding between the problems they landed in the next problem's update stack)
+  d.jraw_off = (int32_t)((P.u2_peak + std::max<int64_t>(P.fs2_max, 72) + 1) & ~(int64_t)1);
+  d.bpanel_off = (int32_t)((P.bwd_peak + 2 + 1) & ~(int64_t)1);  // end of the backward sweep's x stack
+  // the raw-value area (128 doubles per problem) is needed only by fast fronts whose products come as lists (plan.h: RF_ROWS)
+  int64_t prob = std::max<int64_t>((int64_t)d.jraw_off + (P.rec_direct && P.listprod_fronts > 0 ? 128 : 0), (int64_t)d.bpanel_off);
+  // per-problem areas 32 banks apart modulo 64 (prob_doubles = 16 mod 32): the 16 lanes of two neighbouring problems
+  // then touch disjoint LDS banks when they read the same row of their images (env CNL_LDS_PAD=0 disables)
+  prob = (prob + 1) & ~(int64_t)1;
+  if (o.lds_pad) while (prob % 32 != 16) prob += 2;
+  d.prob_doubles = (int32_t)prob;
+  d.gs_doubles = P.gs_doubles + 64;
+  d.lsize = h->dp.lsize;  // padded stride, see cnl_create
+  d.vstride = h->dp.vstride; d.rstride = h->dp.rstride; d.dstride = h->dp.dstride;
+  if (P.rec_direct) {  // the assembly lists address the caller's arrays
+    d.nnz = P.nnz_outer; d.rho_begin = P.nnz_outer - (int32_t)P.nvar;
+    d.vstride = P.nnz_outer; d.rstride = P.n_outer;
+    d.N0 = P.n_outer;
+    if (P.d_outer) d.dstride = P.n_outer;
+    d.count_d = P.d_owned == (int64_t)h->plan->C.r_dsrc.size() ? 1 : 0;  // every condensed pivot is staged by some front
+  }
+  // the kernel addresses vals / rhs / L of the 4 problems of a wave with 32-bit byte offsets from the first one
+  if (4 * 8 * (uint64_t)std::max<int64_t>({d.lsize, d.vstride, d.rstride, d.dstride, (int64_t)d.nnz + d.N0}) >= (1ull << 32)) return CNL_OK;
+  const size_t wave_bytes = ((size_t)(d.recwords >> 1) + 4 * (size_t)d.prob_doubles + 16) * sizeof(double);   // + 16: counters, flags, slow_front's scalars (kernels2.hip)
+  size_t maxlds = std::min<size_t>(cnl::max_lds_bytes(), 160 * 1024);
+  if (wave_bytes + 512 > maxlds) return CNL_OK;  // does not fit: stay on v1
+  // waves per workgroup: small workgroups give the dispatcher freedom; 2 keeps the launch grid moderate
+  int wpb = 1;
+  if (o.waves_per_block > 0) wpb = std::max(1, std::min(4, o.waves_per_block));
+  while (wpb > 1 && wpb * wave_bytes + 512 > maxlds) wpb--;
+  h->wpb2 = wpb;
+  h->lds2 = wpb * wave_bytes + 512;
+  if ((rc = dalloc(h, &h->d_gs, (size_t)h->batch * (size_t)d.gs_doubles))) return rc;
+  h->use_v2 = true;
+  h->staged = false;
+  if ((rc = dalloc(h, &h->d_status, 1))) return rc;
+  if (hipMemset(h->d_status, 0, sizeof(int)) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
+  {
+    // wavefronts of this kernel the device holds at once: two per SIMD by the register budget of every instantiation
+    // (profiles/r04_kernel_resources.txt), and what the LDS of a CU holds
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) {
+      const size_t per_wg = (size_t)wpb * wave_bytes + 512;
+      const long long by_lds = (long long)(std::min<size_t>(prop.maxSharedMemoryPerMultiProcessor ? prop.maxSharedMemoryPerMultiProcessor : maxlds, 160 * 1024) / per_wg) * wpb;
+      const long long resident = (long long)prop.multiProcessorCount * std::max<long long>(1, std::min<long long>(8, by_lds));
+      h->resident_waves = (int)std::min<long long>(resident, 1 << 20);
+    }
+  }
+  // Rounds 4 - 5, for the record (profiles/HISTORY.md 4b item 8, 4c): staged handles on plans with out-of-line front classes (order 17 .. 64) gave
+  // history-dependent wrong decisions and memory faults.  Three causes, all found with garbage left in LDS / scratch / registers in
+  // front of every launch (CNL_DBG_SCRATCHFILL, CNL_DBG_LDSFILL) and tools/fuzz_parity.py: the update-matrix slots of the global scratch
+  // were padded for 16-lane rows whatever the class of the front (analysis.cpp); the class-64 elimination publishes its pivot row two
+  // doubles past the LDS staging area (setup above); and — the one that survived both — the compiler placed the register spills of the
+  // call to the out-of-line front path IN FRONT of the EXEC restore of the join block behind the lane-divergent `if (dep_wait)`, so a
+  // task with nothing to wait for stored no spills and reloaded garbage (kernels2.hip: DEP_WAITING; tools/check_spill_exec.py checks the
+  // ISA of every build for the pattern).  No restriction is left: every stageable plan runs staged, with the in-kernel ladder.
+  if (!P.tasks.empty() && P.rec_direct && P.d_outer && d.count_d && o.staged) {
+    std::vector<int32_t> tk;
+    for (const cnl::Task& t : P.tasks) { tk.push_back(t.rec_off); tk.push_back(t.f1 - t.f0); tk.push_back(t.brec_off); tk.push_back(t.is_root); tk.push_back(t.parent); tk.push_back(t.nchild); }
+    if ((rc = upload(h, tk, &h->d_tasks))) return rc;
+    // dataflow execution: per (task, group of four problems) a count of finished children (forward) and a done flag (backward)
+    h->ntasks = (int)P.tasks.size();
+    // (measured, tools/sweep_dataflow.py: one system 0.132 against 0.165 ms, eight 0.177 against 0.193 ms; cfg4's pattern with
+    //  29 tasks: 32 problems 0.110 against 0.131 ms.  With more wavefronts than about half the machine's slots the waiting ones
+    //  crowd out the working ones — cfg3, 501 tasks: sixteen problems 0.233 against 0.196 ms, 256: 82 k against 367 k systems/s —
+    //  so only the top stages whose tasks x groups of problems number at most 1024 run that way; env CNL_DATAFLOW_WAVES)
+    // a wavefront that waits occupies its slot: never more waiting wavefronts than the device holds at once (the scheme
+    // relies on the lowest unfinished workgroup being resident; kernels2.hip)
+    h->df_waves = o.dataflow_waves > 0 ? o.dataflow_waves : 1024;
+    if (h->resident_waves > 0) h->df_waves = std::min(h->df_waves, h->resident_waves);
+    {
+      const size_t B = (size_t)h->batch, nq = (B + 3) / 4, tq = 2 * (size_t)h->ntasks * nq;
+      const size_t total = 4 * B + (size_t)cnl::LAD_WORDS * nq + tq + 2 + (o.dataflow ? tq : 0);
+      if ((rc = dalloc(h, &h->d_gcnt, total))) return rc;
+      if (hipMemset(h->d_gcnt, 0, total * sizeof(int)) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
+      h->d_lgcnt = h->d_gcnt + 2 * B;
+      h->d_lad = h->d_lgcnt + 2 * B;
+      h->d_ldep = h->d_lad + (size_t)cnl::LAD_WORDS * nq;
+      h->d_stat = h->d_ldep + tq;   // per-call status words (kernels2.hip, spin_until)
+      if (o.dataflow) h->d_dep = h->d_stat + 2;
+      h->zero_ints = (long long)total;
+    }
+    h->stage_ptr = P.stage_ptr;
+    h->staged = true;
+    // The in-kernel rho ladder needs all tasks of a group of four problems resident at once.  With more groups than the device
+    // holds the fused launch is repeated over ranges of groups; beyond four such launches the sequential launch keeps the job
+    // (plans of very many tasks on batches that large do not occur: the planner gives large batches few, large tasks).
+    h->lad_mode = 0;
+    // Plans of a few LARGE tasks (the bidirectional chain of mid-size batches) keep the sequential launch when one fused launch
+    // cannot hold the batch: a rung there is the same chain of fronts either way, and two fused launches of two wavefronts per SIMD
+    // lose to one sequential launch of one (cfg5 at 4096 problems: 3.9 against 2.9 ms).
+    if (o.device_ladder && h->resident_waves >= h->ntasks) {
+      const long long slots = h->resident_waves / h->ntasks, nq = (h->batch + 3) / 4;
+      const long long launches = (nq + slots - 1) / slots;
+      if (launches == 1 || (launches <= 4 && h->ntasks >= 16)) h->lad_mode = o.device_ladder_fused ? 2 : 1;
+    }
+  }
+  h->v2_solve = P.rec_direct && P.d_outer && P.ncls[1] == 0 && P.ncls[2] == 0 && !o.v1_solve;
+  h->lean = o.lean_kernel && P.rec_direct && P.d_outer && d.count_d && P.ncls[1] == 0 && P.ncls[2] == 0 && P.listprod_fronts == 0;
+  return CNL_OK;
+}
+
+// ---- handle creation: what the creators of both element types share ----
+// what every creator checks before it analyses anything
+int check_batch(int64_t batch) {
+  if (batch < 1 || batch > (1 << 24)) return fail(CNL_ERR_ARG, "batch out of range");
+  return CNL_OK;
+}
+int check_device(int device) {
+  int ndev = 0;
+  const hipError_t ce = hipGetDeviceCount(&ndev);
+  if (ce != hipSuccess || ndev == 0)
+    return fail(CNL_ERR_HIP, std::string("no HIP device available (this backend has no CPU fallback): hipGetDeviceCount -> ") +
+                                 hipGetErrorString(ce) + ", " + std::to_string(ndev) + " device(s)");
+  if (device < 0 || device >= ndev) return fail(CNL_ERR_ARG, "device index out of range");
+  return CNL_OK;
+}
+
+// The band kernels for a handle of either element type (h->f32): uploads the program, chooses the problems per workgroup and
+// allocates the factor records; h->band says whether they serve the handle.  They do not where the program does not fit them —
+// *unfit then names the reason and the caller decides what that means (a Float64 handle has the register-front kernel, a Float32
+// handle nothing).  An option that asks for an instance that does not exist is an error.
+int setup_band(cnl_handle* h, const cnl::BandPlan& Bp0, const char** unfit) {
+  const cnl_plan* plan = h->plan;
+  const int esz = h->f32 ? (int)sizeof(float) : (int)sizeof(double);
+  const int64_t batch = h->batch;
+  int rc;
+  h->band_npiece = Bp0.npiece;
+  const bool wide = Bp0.npiece != cnl::BAND_NPIECE;
+  cnl::BandDev& bd = h->bd;
+  // 16 problems per workgroup (two workgroups = four wavefronts per CU: one per SIMD) up to the 8192 problems that fills; above,
+  // 32 per workgroup (the LDS of a CU holds two such workgroups: 16384 problems resident) — tools/time_band.py
+  // (wide program, Float64: 16 at every batch — three workgroups per CU hold 48 problems where one of 32 would hold 32, and the
+  // 32-problem instance would spill; band.hip, band_wide_has)
+  h->band_nl = plan->opt.band_problems_per_group > 0 ? plan->opt.band_problems_per_group
+                                                     : (batch > 8192 && (!wide || cnl::band_wide_has(esz, 32)) ? 32 : 16);
+  if (h->band_nl != 8 && h->band_nl != 16 && h->band_nl != 32) return fail(CNL_ERR_ARG, "band_problems_per_group must be 8, 16 or 32");
+  if (wide && !cnl::band_wide_has(esz, h->band_nl))   // (there is a wide Float32 instance for each of the three)
+    return fail(CNL_ERR_ARG, "band_problems_per_group = 32: the wide band program (20 operand pieces) has Float64 kernels for 8 and 16 problems per workgroup only");
+  // The resident form of the 15-piece program where the plan has it and the handle is the one it was built for: Float64, `vals`
+  // interleaved (an aligned block is then one 64-byte run per problem), 32 problems per workgroup (the instance that stores factor
+  // records directly, so that the out ring's LDS is free in the forward sweep).  Same steps and arithmetic: bit-equal outputs.
+  h->band_resident = !h->f32 && !wide && h->band_nl == 32 && plan->opt.batch_layout == CNL_LAYOUT_INTERLEAVED && plan->band_res.B.ok;
+  const cnl::BandPlan& Bp = h->band_resident ? plan->band_res.B : Bp0;
+  for (int q = 0; q < Bp.nparts; q++) {
+    if ((rc = upload(h, Bp.part[q].fops, &bd.fops[q]))) return rc;
+    if ((rc = upload(h, Bp.part[q].bops, &bd.bops[q]))) return rc;
+    if ((rc = upload(h, Bp.part[q].epochs, &bd.epochs[q]))) return rc;
+    if ((rc = upload(h, Bp.part[q].borders, &bd.borders[q]))) return rc;
+    bd.nsteps[q] = Bp.part[q].nsteps; bd.nepochs[q] = Bp.part[q].nepochs; bd.loff[q] = Bp.part[q].loff;
+  }
+  bd.nparts = Bp.nparts; bd.m0 = Bp.m0; bd.n = Bp.n; bd.N = Bp.N; bd.nnz = Bp.nnz; bd.nvar = (int32_t)plan->nvar; bd.lsize = Bp.lsize;
+  // 32-bit byte offsets inside a workgroup's problems
+  const uint64_t span = (uint64_t)esz * (uint64_t)h->band_nl * (uint64_t)std::max<int64_t>({plan->nnz, plan->N, bd.lsize});
+  if (span >= (1ull << 32)) { *unfit = "the arrays of a workgroup's problems span 4 GB or more (32-bit offsets of the band kernels)"; return CNL_OK; }
+  if (cnl::band_lds_bytes(bd.nparts, h->band_nl, esz, h->band_npiece) > std::min<size_t>(cnl::max_lds_bytes(), 160 * 1024)) {
+    *unfit = "the band kernels' LDS does not fit a workgroup";
+    return CNL_OK;
+  }
+  // (+ 32 problems: the band kernels interleave the records of a workgroup's problems, the last workgroup's region is a whole one)
+  const size_t lbytes = (((size_t)batch + 32) * (size_t)bd.lsize + 64) * (size_t)esz;
+  char* L = nullptr;
+  if ((rc = dalloc(h, &L, lbytes))) return rc;
+  if (hipMemset(L, 0, lbytes) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
+  h->d_Lband = L;
+  h->band = true;
+  return CNL_OK;
+}
+
+// cnl_options.batch_layout: the interleaved layout is the band kernels' (groups of 32 problems = one workgroup of the 32-problem
+// instantiation)
+int setup_layout(cnl_handle* h) {
+  const cnl::Tuning& o = h->plan->opt;
+  if (o.batch_layout == CNL_LAYOUT_PROBLEM_MAJOR) return CNL_OK;
+  if (o.batch_layout != CNL_LAYOUT_INTERLEAVED) return fail(CNL_ERR_ARG, "cnl_options.batch_layout: unknown layout");
+  if (!h->band)
+    return fail(CNL_ERR_ARG, "batch_layout = CNL_LAYOUT_INTERLEAVED needs a handle the band kernels serve "
+                             "(band-structured pattern, throughput plan, cnl_options.band_kernel != 0; csrc/band.h)");
+  h->layout = 1 | (o.band_rhs_interleaved ? 2 : 0);
+  return CNL_OK;
+}
+
+// ---- cnl_options.batch_layout = CNL_LAYOUT_INTERLEAVED: lengths and conversions (csrc/band.h: band_il_index) ----
+int layout_rowlen(const cnl_handle* h, int which, int64_t* len) {
+  if (which == 0) *len = h->djt.nnz;
+  else if (which == 1) *len = (int64_t)h->djt.nvar + h->djt.nequ + h->djt.ncon;
+  else return fail(CNL_ERR_ARG, "which: 0 = vals, 1 = an N-vector per problem (rhs)");
+  return CNL_OK;
+}
+template <class T>
+int convert_layout(cnl_handle* h, int which, const T* src, T* dst, int to_interleaved, void* stream) {
+  if (!h || !src || !dst) return fail(CNL_ERR_ARG, "null argument");
+  if (src == dst) return fail(CNL_ERR_ARG, "the conversion is not in place");
+  int64_t len = 0;
+  if (int rc = layout_rowlen(h, which, &len)) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  hipError_t e;
+  if constexpr (sizeof(T) == 4) e = cnl::launch_interleave_f32(src, dst, (int)h->batch, len, to_interleaved, (hipStream_t)stream);
+  else e = cnl::launch_interleave(src, dst, (int)h->batch, len, to_interleaved, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("interleave: ") + hipGetErrorString(e));
+  return CNL_OK;
+}
+
+// Rows f1 / f4 (both element types): the transposed-Jacobian lists of the pattern (DevJt), the column tiles of row f1 and the J_F / J_c
+// segments of `vals`.  Pattern-sized, shared by all problems of the handle.
+int build_row_lists(cnl_handle* h, const cnl_plan* plan, const int64_t* rows1, const int64_t* cols1) {
+  const int64_t N = plan->N, nnz = plan->nnz, nvar = plan->nvar, nequ = plan->nequ, ncon = plan->ncon;
+  int rc = CNL_OK;
+  // transposed-Jacobian lists from the pattern: entries with column <= nvar < row, in COO order per column
+  std::vector<int32_t> ptrF(nvar + 1, 0), ptrC(nvar + 1, 0), slotF, idxF, slotC, idxC;
+  for (int64_t e = 0; e < nnz; e++) {
+    const int64_t r0 = rows1[e] - 1, c0 = cols1[e] - 1;
+    if (c0 < nvar && r0 >= nvar) (r0 < nvar + nequ ? ptrF : ptrC)[c0 + 1]++;
+  }
+  for (int64_t j2 = 0; j2 < nvar; j2++) { ptrF[j2 + 1] += ptrF[j2]; ptrC[j2 + 1] += ptrC[j2]; }
+  slotF.resize(ptrF[nvar]); idxF.resize(ptrF[nvar]); slotC.resize(ptrC[nvar]); idxC.resize(ptrC[nvar]);
+  std::vector<int32_t> fillF(ptrF.begin(), ptrF.end() - 1), fillC(ptrC.begin(), ptrC.end() - 1);
+  for (int64_t e = 0; e < nnz; e++) {
+    const int64_t r0 = rows1[e] - 1, c0 = cols1[e] - 1;
+    if (!(c0 < nvar && r0 >= nvar)) continue;
+    if (r0 < nvar + nequ) { const int32_t q = fillF[c0]++; slotF[q] = (int32_t)e; idxF[q] = (int32_t)(r0 - nvar); }
+    else { const int32_t q = fillC[c0]++; slotC[q] = (int32_t)e; idxC[q] = (int32_t)(r0 - nvar - nequ); }
+  }
+  cnl::DevJt& J = h->djt;
+  if ((rc = upload(h, ptrF, &J.ptrF))) return rc;
+  // the J_F / J_c entries as segments of `vals` (the reference's 7-segment layout, src/CaNNOLeS.jl:256-315): rows f1 / f4 can
+  // read them from the model's arrays instead (cnl_residual_vectors_jac_dev) when each kind occupies one run of slots
+  {
+    auto run = [](const std::vector<int32_t>& sl, int64_t& lo) {
+      if (sl.empty()) { lo = 0; return true; }
+      const auto mm = std::minmax_element(sl.begin(), sl.end());
+      lo = *mm.first;
+      return (int64_t)*mm.second - *mm.first + 1 == (int64_t)sl.size();
+    };
+    h->jac_segments = run(slotF, h->jf_lo) && run(slotC, h->jc_lo);
+    h->jf_n = (int64_t)slotF.size(); h->jc_n = (int64_t)slotC.size();
+  }
+  if ((rc = upload(h, slotF, &J.slotF))) return rc;
+  if ((rc = upload(h, idxF, &J.idxF))) return rc;
+  if ((rc = upload(h, ptrC, &J.ptrC))) return rc;
+  if ((rc = upload(h, slotC, &J.slotC))) return rc;
+  if ((rc = upload(h, idxC, &J.idxC))) return rc;
+  {
+    // J_c by rows (CGLS, row f4)
+    std::vector<int32_t> rptr(ncon + 1, 0), rslot(slotC.size()), rcol(slotC.size());
+    for (int64_t j2 = 0; j2 < nvar; j2++) for (int32_t q = ptrC[j2]; q < ptrC[j2 + 1]; q++) rptr[idxC[q] + 1]++;
+    for (int64_t k2 = 0; k2 < ncon; k2++) rptr[k2 + 1] += rptr[k2];
+    std::vector<int32_t> fillr(rptr.begin(), rptr.end() - 1);
+    for (int64_t j2 = 0; j2 < nvar; j2++)
+      for (int32_t q = ptrC[j2]; q < ptrC[j2 + 1]; q++) { const int32_t w = fillr[idxC[q]]++; rslot[w] = slotC[q]; rcol[w] = (int32_t)j2; }
+    if ((rc = upload(h, rptr, &J.rptrC))) return rc;
+    if ((rc = upload(h, rslot, &J.rslotC))) return rc;
+    if ((rc = upload(h, rcol, &J.rcolC))) return rc;
+  }
+  J.nvar = (int32_t)nvar; J.nequ = (int32_t)nequ; J.ncon = (int32_t)ncon; J.N = (int32_t)N; J.nnz = (int32_t)nnz;
+  // (round 5) column tiles of row f1 (kernels.h: DevJt::rv_*): the slot / index ranges of every tile of RVT_COLS columns
+  if (plan->opt.f1_tiles && nvar > 0) {
+    const int32_t nt = (int32_t)((nvar + cnl::RVT_COLS - 1) / cnl::RVT_COLS);
+    std::vector<int32_t> tiles((size_t)nt * cnl::RVT_TW, 0);
+    std::vector<uint32_t> table((size_t)nt * (cnl::RVT_KF + cnl::RVT_KC + 1) * cnl::RVT_COLS, 0u);
+    bool ok = true;
+    int32_t lds_max = 0;
+    for (int32_t t = 0; t < nt && ok; t++) {
+      const int64_t c0 = (int64_t)t * cnl::RVT_COLS, c1 = std::min<int64_t>(nvar, c0 + cnl::RVT_COLS);
+      int32_t fslo = INT32_MAX, fshi = -1, rlo = INT32_MAX, rhi = -1, cslo = INT32_MAX, cshi = -1, llo = INT32_MAX, lhi = -1;
+      for (int32_t q = ptrF[c0]; q < ptrF[c1]; q++) { fslo = std::min(fslo, slotF[q]); fshi = std::max(fshi, slotF[q]); rlo = std::min(rlo, idxF[q]); rhi = std::max(rhi, idxF[q]); }
+      for (int32_t q = ptrC[c0]; q < ptrC[c1]; q++) { cslo = std::min(cslo, slotC[q]); cshi = std::max(cshi, slotC[q]); llo = std::min(llo, idxC[q]); lhi = std::max(lhi, idxC[q]); }
+      int32_t* T = &tiles[(size_t)t * cnl::RVT_TW];
+      T[cnl::RVT_FSLO] = fshi < 0 ? 0 : fslo; T[cnl::RVT_WF] = fshi < 0 ? 0 : fshi - fslo + 1;
+      T[cnl::RVT_RLO] = rhi < 0 ? 0 : rlo;   T[cnl::RVT_WR] = rhi < 0 ? 0 : rhi - rlo + 1;
+      T[cnl::RVT_CSLO] = cshi < 0 ? 0 : cslo; T[cnl::RVT_WC] = cshi < 0 ? 0 : cshi - cslo + 1;
+      T[cnl::RVT_LLO] = lhi < 0 ? 0 : llo;   T[cnl::RVT_WL] = lhi < 0 ? 0 : lhi - llo + 1;
+      if (T[cnl::RVT_WF] > cnl::RVT_MAXF || T[cnl::RVT_WR] > cnl::RVT_MAXR || T[cnl::RVT_WC] > cnl::RVT_MAXC || T[cnl::RVT_WL] > cnl::RVT_MAXL) { ok = false; break; }
+      auto even = [](int32_t w) { return (w + 3) & ~1; };   // a window and the double its 16-byte alignment may put in front
+      lds_max = std::max(lds_max, even(T[cnl::RVT_WF]) + even(T[cnl::RVT_WR]) + even(T[cnl::RVT_WC]) + even(T[cnl::RVT_WL]));
+      uint32_t* tab = &table[(size_t)t * (cnl::RVT_KF + cnl::RVT_KC + 1) * cnl::RVT_COLS];
+      for (int64_t c = c0; c < c1; c++) {
+        const int32_t nF = ptrF[c + 1] - ptrF[c], nC = ptrC[c + 1] - ptrC[c];
+        if (nF > 255 || nC > 255) { ok = false; break; }
+        for (int32_t u = 0; u < std::min(nF, cnl::RVT_KF); u++)
+          tab[(size_t)u * cnl::RVT_COLS + (c - c0)] = (uint32_t)(slotF[ptrF[c] + u] - T[cnl::RVT_FSLO]) | (uint32_t)(idxF[ptrF[c] + u] - T[cnl::RVT_RLO]) << 16;
+        for (int32_t u = 0; u < std::min(nC, cnl::RVT_KC); u++)
+          tab[(size_t)(cnl::RVT_KF + u) * cnl::RVT_COLS + (c - c0)] = (uint32_t)(slotC[ptrC[c] + u] - T[cnl::RVT_CSLO]) | (uint32_t)(idxC[ptrC[c] + u] - T[cnl::RVT_LLO]) << 16;
+        tab[(size_t)(cnl::RVT_KF + cnl::RVT_KC) * cnl::RVT_COLS + (c - c0)] = (uint32_t)nF | (uint32_t)nC << 8;
+      }
+    }
+    if (ok) {
+      // the residual rows a tile has in LDS anyway are the rows whose primal entry F - r it writes: possible when the tiles' row
+      // ranges are ordered and cover 0 .. nequ without gaps (a band); otherwise tiles of rows of their own follow the column tiles
+      bool own = nequ > 0;
+      int32_t prev = 0;
+      for (int32_t t = 0; t < nt && own; t++) {
+        int32_t* T = &tiles[(size_t)t * cnl::RVT_TW];
+        const int32_t lo = T[cnl::RVT_RLO], hi = lo + T[cnl::RVT_WR];
+        const int32_t next_lo = t + 1 < nt ? tiles[(size_t)(t + 1) * cnl::RVT_TW + cnl::RVT_RLO] : (int32_t)nequ;
+        const int32_t own_hi = t + 1 < nt ? std::min(hi, std::max(next_lo, prev)) : (int32_t)nequ;
+        if (prev < lo || own_hi > hi || own_hi < prev) { own = false; break; }
+        T[cnl::RVT_OWNLO] = prev; T[cnl::RVT_OWNHI] = own_hi;
+        prev = own_hi;
+      }
+      if (own && prev != nequ) own = false;
+      if (!own) for (int32_t t = 0; t < nt; t++) tiles[(size_t)t * cnl::RVT_TW + cnl::RVT_OWNLO] = tiles[(size_t)t * cnl::RVT_TW + cnl::RVT_OWNHI] = 0;
+      if ((rc = upload(h, tiles, &J.rv_tiles))) return rc;
+      if ((rc = upload(h, table, &J.rv_table))) return rc;
+      J.rv_ntiles = nt; J.rv_lds_doubles = lds_max;
+      J.rv_primal_tiles = own ? 0 : (int32_t)((nequ + cnl::RVT_PROWS - 1) / cnl::RVT_PROWS);
+    }
+    if (std::getenv("CNL_VERBOSE")) fprintf(stderr, "[cnl] row f1: %s\n", ok ? "column tiles" : "gather kernel (a tile's windows exceed the limits)");
+  }
+  return CNL_OK;
+}
+
+int create_tuned(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar,
+                 int64_t nequ, int64_t ncon, int64_t batch, int device, const cnl::Tuning& o) {
+  *hout = nullptr;
+  if (int rc = check_batch(batch)) return rc;
+  if (int rc = check_device(device)) return rc;
+  cnl_plan* plan = nullptr;
+  // small batches cannot fill the chip with one wavefront per four problems: plan for latency (bushy order, tasks)
+  int rc = plan_create_tuned(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, o);
+  if (rc) return rc;
+  return create_from_plan(hout, plan, rows1, cols1, batch, device);
+}
+
+}  // namespace
+
+// device state for `batch` problems of an analysed pattern; takes ownership of `plan` (freed with the handle, or here on failure)
+int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device) {
+  const int64_t N = plan->N, nnz = plan->nnz, nvar = plan->nvar, nequ = plan->nequ, ncon = plan->ncon;
+  int rc = CNL_OK;
+  cnl_handle* h = new cnl_handle();
+  h->plan = plan; h->device = device; h->batch = batch;
+  auto bail = [&](int code) { cnl_destroy(h); return code; };
+  if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
+  const cnl::Plan& P = plan->P;
+  cnl::DevPlan& dp = h->dp;
+  if ((rc = upload(h, P.fronts, &dp.fronts))) return bail(rc);
+  if ((rc = upload(h, P.seg_ptr, &dp.seg_ptr))) return bail(rc);
+  if ((rc = upload(h, P.asm_pos, &dp.asm_pos))) return bail(rc);
+  if ((rc = upload(h, P.asm_src, &dp.asm_src))) return bail(rc);
+  if ((rc = upload(h, P.child_idx, &dp.child_idx))) return bail(rc);
+  if ((rc = upload(h, P.rel_idx, &dp.rel_idx))) return bail(rc);
+  if ((rc = upload(h, P.perm, &dp.perm))) return bail(rc);
+  dp.nsuper = P.nsuper; dp.N = (int32_t)P.N; dp.nnz = (int32_t)P.nnz; dp.rho_begin = P.rho_begin;
+  dp.nvar = (int32_t)P.nvar; dp.nequ = (int32_t)P.nequ; dp.ncon = (int32_t)P.ncon;
+  dp.fmax = (P.fmax + 1) & ~1;
+  // factor storage stride per problem: + 16 zero doubles that are never written.  The solve sweeps read a panel row as 16
+  // lanes, so the last rows of a problem's factor are over-read by up to 15 entries, which are multiplied by zeros; without
+  // the pad they would be the first entries of the NEXT problem's factor, and a NaN / Inf there (a neighbour whose
+  // factorisation broke down) would turn 0 * x into NaN in this problem's solution
+  dp.lsize = P.lsize + 16;
+  const cnl::Cond& C = plan->C;
+  dp.vstride = C.active ? C.cstride : (int64_t)nnz;
+  dp.rstride = C.active ? C.cstride : N;
+  dp.dstride = C.active ? C.N2 : N;
+  if (C.active) {
+    cnl::DevCond& dc = h->dc;
+    std::vector<int32_t> cidx(N, -1);
+    for (size_t q = 0; q < C.r_orig.size(); q++) cidx[C.r_orig[q]] = (int32_t)q;
+    if ((rc = upload(h, C.c_ptr, &dc.c_ptr))) return bail(rc);
+    if ((rc = upload(h, C.c_a, &dc.c_a))) return bail(rc);
+    if ((rc = upload(h, C.c_b, &dc.c_b))) return bail(rc);
+    if ((rc = upload(h, C.c_d, &dc.c_d))) return bail(rc);
+    if ((rc = upload(h, C.c_order, &dc.c_order))) return bail(rc);
+    if ((rc = upload(h, C.ch_slot, &dc.ch_slot))) return bail(rc);
+    if ((rc = upload(h, C.ch_rng, &dc.ch_rng))) return bail(rc);
+    if ((rc = upload(h, C.ch_tile, &dc.ch_tile))) return bail(rc);
+    if ((rc = upload(h, C.rng_start, &dc.rng_start))) return bail(rc);
+    if ((rc = upload(h, C.rng_len, &dc.rng_len))) return bail(rc);
+    if ((rc = upload(h, C.c_la, &dc.c_la))) return bail(rc);
+    if ((rc = upload(h, C.c_lb, &dc.c_lb))) return bail(rc);
+    if ((rc = upload(h, C.c_ld, &dc.c_ld))) return bail(rc);
+    if ((rc = upload(h, C.ch_tptr, &dc.ch_tptr))) return bail(rc);
+    if ((rc = upload(h, C.tile_src, &dc.tile_src))) return bail(rc);
+    if ((rc = upload(h, C.c_pack, &dc.c_pack))) return bail(rc);
+    dc.tile_max = C.tile_max; dc.chunk_ncon_max = C.chunk_ncon_max; dc.chunk_nslot_max = C.chunk_nslot_max; dc.tiled_ok = C.tiled_ok ? 1 : 0;
+    if ((rc = upload(h, C.r_dsrc, &dc.r_dsrc))) return bail(rc);
+    if ((rc = upload(h, C.r_ptr, &dc.r_ptr))) return bail(rc);
+    if ((rc = upload(h, C.r_jsrc, &dc.r_jsrc))) return bail(rc);
+    if ((rc = upload(h, C.r_jx, &dc.r_jx))) return bail(rc);
+    if ((rc = upload(h, C.red_of, &dc.red_of))) return bail(rc);
+    if ((rc = upload(h, cidx, &dc.cidx_of))) return bail(rc);
+    if ((rc = upload(h, C.orig_of, &dc.orig_of))) return bail(rc);
+    if ((rc = upload(h, C.r_orig, &dc.r_orig))) return bail(rc);
+    dc.N = (int32_t)N; dc.nnz = (int32_t)nnz; dc.nvar = (int32_t)nvar; dc.N2 = (int32_t)C.N2; dc.ncs = (int32_t)C.ncs;
+    dc.ncond = (int32_t)C.r_orig.size(); dc.cstride = C.cstride;
+    // (d_cbuf / d_d2 — the condensed buffer and the reduced solution of the stand-alone condensation passes — are allocated below,
+    //  once it is known whether the band kernels serve the handle: they never touch them)
+    if ((rc = dalloc(h, &h->d_xpos, (size_t)batch))) return bail(rc);
+    if ((rc = dalloc(h, &h->d_xzer, (size_t)batch))) return bail(rc);
+  }
+  if ((rc = choose_config(h))) return bail(rc);
+  if ((rc = setup_v2(h))) return bail(rc);
+  if (band_program(plan, false).ok && band_wide_serves_f64(plan) && plan->opt.band_kernel && h->use_v2 && !h->staged && h->v2_solve && h->lean && plan->P.back_rows && !plan->latency && !plan->split_mode) {
+    // band kernels for newton_system, try_to_factorize and solve_ldl! (csrc/band.h); the wide program where the plan has one.
+    // (A program that does not fit them — setup_band — leaves the handle on the register-front kernel.)
+    const char* unfit = nullptr;
+    if ((rc = setup_band(h, band_program(plan, false), &unfit))) return bail(rc);
+  }
+  if ((rc = setup_layout(h))) return bail(rc);
+  // Storage only the register-front / general kernels and the stand-alone condensation passes use.  A band handle runs all three
+  // calls of the plugin surface on the band kernels (round 6), so it owns the band factor records alone: 0.48 MB per problem of
+  // cfg3's size instead of 0.48 + 1.16 (factor panels) + 0.64 (condensed buffer, reduced solution) — 16 384 problems: 29 GB less,
+  // and twice the batch fits the 288 GB of a device beside the caller's arrays.
+  if (plan->C.active && !h->band) {
+    if ((rc = dalloc(h, &h->d_cbuf, (size_t)batch * (size_t)plan->C.cstride))) return bail(rc);
+    if ((rc = dalloc(h, &h->d_d2, (size_t)batch * (size_t)plan->C.N2))) return bail(rc);
+  }
+  if (plan->split_mode && h->staged) {
+    // x groups of four problems on the chain (two wavefronts each), the rest on the single stream: 2 x + y = 2048 slots
+    const int64_t nquads = (batch + 3) / 4, x = std::max<int64_t>(0, 2048 - nquads);
+    h->split_staged = std::min<int64_t>(batch, 4 * x);
+    if (h->plan->opt.split_batch == 1 && batch <= 6400) {
+      // two halves on the chain (multiples of four problems), sequentially — measured against chain + single stream concurrently
+      // (cfg3's size, same box, k systems/s): 4608: 768 / 707, 5120: 836 / 790, 6144: 931 / 898, 6656: 912 / ~935, 7168: 956 / 959,
+      // 7424: 904 / ~965 — halves up to 6400 problems (see run_split)
+      h->split_halves = true;
+      h->split_staged = (((batch + 1) / 2) + 3) & ~(int64_t)3;
+    }
+    if (h->split_staged == 0) h->staged = false;  // the whole batch on the single stream
+    // a remainder of at most a quarter of the machine-filling batch: its own handle with its own (many-part) plan — run_split
+    const int64_t smb = ((plan->opt.staged_max_batch > 0 ? plan->opt.staged_max_batch : 4096)) & ~(int64_t)3;
+    if (h->staged && plan->opt.split_batch == 1 && plan->opt.split_tail != 0 && batch > smb && batch - smb <= smb / 4) {
+      cnl_handle* t = nullptr;
+      if (create_tuned(&t, N, nnz, rows1, cols1, nvar, nequ, ncon, batch - smb, device, plan->opt) == CNL_OK) {
+        if (t->staged && t->use_v2 && !t->dense && !t->gdense && !t->tail && t->split_staged == 0) {
+          h->tail = t; h->split_halves = false; h->split_staged = smb;
+        } else {
+          cnl_destroy(t);
+        }
+      }
+      if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
+    }
+  }
+  if (!plan->latency && !plan->split_mode && h->use_v2 && !h->staged && h->resident_waves > 0 && plan->opt.plan_kind == CNL_PLAN_AUTO &&
+      plan->opt.split_tail != 0 && plan->opt.force_order[0] == 0 && !plan->D.active && plan->gpos.empty()) {
+    // The single stream gives a group of four problems ONE wavefront for all fronts, and the device holds `resident_waves` of
+    // them: a batch of k full machine loads + r problems runs k + 1 rounds, the last one for the r problems alone (cfg3's size:
+    // 8448 problems 13.0 ms against 7.9 ms for 8192).  The remainder as a batch of its own has a better plan (many parts, the
+    // bidirectional chain, ...): it gets a handle of its own, enqueued behind the full loads (run_split).
+    // (band kernels: 512 workgroups of 32 problems are resident at once)
+    const int64_t cap = h->band ? 16384 : 4 * (int64_t)h->resident_waves, r = batch % cap;
+    if (batch > cap && r > 0 && r <= cap - cap / 16 && !h->layout) {   // (an interleaved batch is one array of whole groups)
+      cnl_handle* t = nullptr;
+      if (create_tuned(&t, N, nnz, rows1, cols1, nvar, nequ, ncon, r, device, plan->opt) == CNL_OK) {
+        if (t->staged && t->use_v2 && !t->dense && !t->gdense) { h->tail = t; h->split_staged = batch - r; }
+        else cnl_destroy(t);
+      }
+      if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
+    }
+  }
+  if (h->plan->D.active) {
+    std::string derr;
+    int drc = cnl::dense_create(&h->dense, h->plan->D, batch, derr, h->plan->opt.dense_graph != 0, h->plan->opt.dense_syrk_wgs, h->plan->opt.dense_panel_blocks);
+    if (drc) return bail(fail(CNL_ERR_HIP, "dense backend: " + derr));
+  } else if (!h->plan->gpos.empty() && !h->use_v2 &&
+             // S0, S and G in 64 x 64 tiles per problem: small batches always, larger ones while the tiles stay below 8 GB
+             // (round 2 stopped at 16 problems; batches of small irregular systems then fell to the general kernel)
+             (batch <= 16 || (double)batch * 3.0 * 32768.0 * std::pow(std::ceil((double)h->plan->C.N2 / 64.0), 2) <= 8e9)) {
+    std::string derr;
+    const cnl::Cond& C2 = h->plan->C;
+    h->gops.ns = (int32_t)C2.N2; h->gops.nv = (int32_t)nvar; h->gops.nslots = (int32_t)C2.ncs; h->gops.cstride = C2.cstride;
+    if ((rc = upload(h, h->plan->gpos, &h->gops.d_pos))) return bail(rc);
+    int drc = cnl::dense_create_general(&h->gdense, (int32_t)C2.N2, (int32_t)nvar, (int32_t)C2.ncs, h->gops.d_pos, batch, derr, h->plan->opt.dense_graph != 0, h->plan->opt.dense_panel_blocks);
+    if (drc) return bail(fail(CNL_ERR_HIP, "dense backend: " + derr));
+  }
+  {
+    // factor storage, zero-filled and padded: the row prefetch of the backward pass reads (never uses) a little past a panel
+    const size_t ldoubles = (h->band ? 0 : (size_t)batch * (size_t)dp.lsize) + 4096;   // (band handles: see above)
+    if ((rc = dalloc(h, &h->d_L, ldoubles))) return bail(rc);
+    if (hipMemset(h->d_L, 0, ldoubles * sizeof(double)) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipMemset failed"));
+  }
+  if (!h->cfg.lds_work)
+    if ((rc = dalloc(h, &h->d_scratch, (size_t)batch * (size_t)dp.work_doubles))) return bail(rc);
+  if (hipStreamCreate(&h->stream) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipStreamCreate failed"));
+  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess)
+    return bail(fail(CNL_ERR_HIP, "hipEventCreate failed"));
+  if ((rc = build_row_lists(h, plan, rows1, cols1))) return bail(rc);
+  *hout = h;
+  return CNL_OK;
+}
+
+namespace {
+
+int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device) {
+  cnl_handle* h = new cnl_handle();
+  h->plan = plan; h->device = device; h->batch = batch; h->f32 = true;
+  auto bail = [&](int code) { cnl_destroy(h); return code; };
+  if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
+  int rc = CNL_OK;
+  const char* unfit = nullptr;
+  if ((rc = setup_band(h, band_program(plan, true), &unfit))) return bail(rc);   // the wide program where the plan has one
+  if (!h->band) return bail(fail(CNL_ERR_ARG, std::string("cnl_create_f32: ") + unfit));   // (Float32 handles have no other kernel)
+  if ((rc = setup_layout(h))) return bail(rc);
+  // rows f1 / f2 / f4 and the trial point: the Float64 handles' row lists (they hold the dimensions cnl_layout_len reads)
+  if ((rc = build_row_lists(h, plan, rows1, cols1))) return bail(rc);
+  if (hipStreamCreate(&h->stream) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipStreamCreate failed"));
+  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipEventCreate failed"));
+  *hout = h;
+  return CNL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cnl_create(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar,
+               int64_t nequ, int64_t ncon, int64_t batch, int device) {
+  return cnl_create_ex(hout, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, nullptr);
+}
+
+int cnl_create_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar,
+                  int64_t nequ, int64_t ncon, int64_t batch, int device, const cnl_options* opt) {
+  if (!hout) return fail(CNL_ERR_ARG, "null handle pointer");
+  *hout = nullptr;
+  cnl::Tuning o;
+  const int rc0 = resolve_options(opt, o);
+  if (rc0) return rc0;
+  return create_tuned(hout, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, o);
+}
+
+int cnl_create_f32(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ,
+                   int64_t ncon, int64_t batch, int device) {
+  return cnl_create_f32_ex(hout, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, nullptr);
+}
+
+int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ,
+                      int64_t ncon, int64_t batch, int device, const cnl_options* opt) {
+  if (!hout) return fail(CNL_ERR_ARG, "null handle pointer");
+  *hout = nullptr;
+  cnl::Tuning o;
+  if (int rc = resolve_options(opt, o)) return rc;
+  if (int rc = check_batch(batch)) return rc;
+  if (!o.band_kernel) return fail(CNL_ERR_ARG, "cnl_create_f32: cnl_options.band_kernel = 0, and Float32 handles run on the band kernels only");
+  if (int rc = check_device(device)) return rc;
+  // the throughput analysis whatever the batch: there is nothing but the band program to run
+  cnl_plan* plan = nullptr;
+  if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, o)) return rc;
+  if (!band_program(plan, true).ok) {   // (the analysis builds it next to the Float64 program; not for a pattern the Float64 handles serve otherwise)
+    build_band_programs(plan, rows1, cols1, (int)sizeof(float));
+    band_summaries(plan);
+  }
+  if (!band_program(plan, true).ok) {
+    const std::string why = plan->band_prog[1][1].B.why.empty() ? plan->band_prog[1][0].B.why : plan->band_prog[1][1].B.why;
+    cnl_plan_destroy(plan);
+    return fail(CNL_ERR_ARG, "cnl_create_f32: the pattern is not served by the band kernels (build_band_plan: " + why +
+                                 "); Float32 stays on the CPU backend for it");
+  }
+  return create_f32_from_plan(hout, plan, rows1, cols1, batch, device);
+}
+
+int cnl_destroy(cnl_handle* h) {
+  if (!h) return CNL_OK;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (void* p : h->dev_allocs) (void)hipFree(p);
+  if (h->pin) (void)hipHostFree(h->pin);
+  cnl::dense_destroy(h->dense);
+  cnl::dense_destroy(h->gdense);
+  if (h->tail) { cnl_destroy(h->tail); h->tail = nullptr; (void)hipSetDevice(h->device); }
+  if (h->aux_stream) { (void)hipStreamSynchronize(h->aux_stream); (void)hipStreamDestroy(h->aux_stream); }
+  if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
+  if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+  for (hipEvent_t e : h->pipe_ev) (void)hipEventDestroy(e);
+  for (hipStream_t st : h->pipe_stream) if (st) (void)hipStreamDestroy(st);
+  if (h->ev0) (void)hipEventDestroy(h->ev0);
+  if (h->ev1) (void)hipEventDestroy(h->ev1);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  cnl_plan_destroy(h->plan);
+  delete h;
+  return CNL_OK;
+}
+
+const cnl_plan* cnl_get_plan(const cnl_handle* h) { return h ? h->plan : nullptr; }
+
+int cnl_dataflow_timeouts(cnl_handle* h, int64_t* count) {
+  if (!h || !count) return fail(CNL_ERR_ARG, "null argument");
+  *count = 0;
+  if (h->d_status) {
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    int v = 0;
+    HIPCHK(hipMemcpy(&v, h->d_status, sizeof(int), hipMemcpyDeviceToHost));
+    *count = v;
+  }
+  if (h->tail) {
+    int64_t tc = 0;
+    const int rc = cnl_dataflow_timeouts(h->tail, &tc);
+    if (rc) return rc;
+    *count += tc;
+  }
+  return CNL_OK;
+}
+
+int cnl_layout_len(const cnl_handle* h, int which, int64_t* doubles) {
+  if (!h || !doubles) return fail(CNL_ERR_ARG, "null argument");
+  int64_t len = 0;
+  if (int rc = layout_rowlen(h, which, &len)) return rc;
+  *doubles = cnl::band_il_len(h->batch, len);
+  return CNL_OK;
+}
+int cnl_interleave_dev(cnl_handle* h, int which, const double* d_src, double* d_dst, void* stream) {
+  CNL_NEED_F64(h);
+  return convert_layout(h, which, d_src, d_dst, 1, stream);
+}
+int cnl_deinterleave_dev(cnl_handle* h, int which, const double* d_src, double* d_dst, void* stream) {
+  CNL_NEED_F64(h);
+  return convert_layout(h, which, d_src, d_dst, 0, stream);
+}
+int cnl_interleave_f32_dev(cnl_handle* h, int which, const float* d_src, float* d_dst, void* stream) {
+  CNL_NEED_F32(h);
+  return convert_layout(h, which, d_src, d_dst, 1, stream);
+}
+int cnl_deinterleave_f32_dev(cnl_handle* h, int which, const float* d_src, float* d_dst, void* stream) {
+  CNL_NEED_F32(h);
+  return convert_layout(h, which, d_src, d_dst, 0, stream);
+}
+
+int cnl_set_timing(cnl_handle* h, int enable) {
+  if (!h) return fail(CNL_ERR_ARG, "null handle");
+  h->timing = enable != 0;
+  return CNL_OK;
+}
+
+int cnl_last_kernel_ms(cnl_handle* h, float* ms) {
+  if (!h || !ms) return fail(CNL_ERR_ARG, "null argument");
+  *ms = h->last_ms;
+  return CNL_OK;
+}
+
+int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
+  if (!h || !cfg) return fail(CNL_ERR_ARG, "null argument");
+  std::memset(cfg, 0, 8 * sizeof(int64_t));
+  if (h->f32) {   // Float32 handle: the band kernels only
+    cfg[5] = 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->layout << 25) | ((int64_t)1 << 27) | ((int64_t)h->band_npiece << 28);
+    if (h->djt.rv_ntiles > 0) cfg[5] |= 128;
+    return CNL_OK;
+  }
+  cfg[0] = h->cfg.tpp; cfg[1] = h->cfg.ppb; cfg[2] = (int64_t)h->cfg.lds_bytes; cfg[3] = h->cfg.lds_work;
+  cfg[4] = (h->batch + h->cfg.ppb - 1) / h->cfg.ppb;
+  cfg[5] = (h->dense || h->gdense) ? 3 : (h->use_v2 ? (h->staged ? 4 : 2) : 1);
+  if (h->lean && !h->dense && !h->gdense) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
+  if (h->tail) cfg[5] |= 32;                             // the remainder of the batch runs on a handle of its own (split_tail)
+  if (h->band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->band_resident << 24) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts, layout, operand pieces per epoch
+  if (h->djt.rv_ntiles > 0) cfg[5] |= 128;               // row f1 runs on column tiles (kernels.h: DevJt::rv_*)
+  cfg[6] = h->wpb2;
+  cfg[7] = (int64_t)h->lds2;
+  return CNL_OK;
+}
+
+}  // extern "C"

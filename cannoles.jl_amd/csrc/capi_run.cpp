@@ -1,0 +1,406 @@
+// capi_run.cpp — the launch logic: run() hands one call on device-resident data to the handle's backend (band kernels, dense routes,
+// register-front / general multifrontal kernels with their condensation passes, staged execution) or, for a split batch, to views
+// of the handle and its remainder handle (SubBatch, run_split).  Everything is enqueued on the caller's stream.
+#include "handle.h"
+
+namespace {
+
+// debugging aid (include/cannoles_hip.h): CNL_DBG_LDSFILL=<byte pattern> — kernels that leave the pattern in LDS, scratch and registers
+// run in front of every launch.  The variable is read ONCE per process (round 6: it was a getenv per launch in the product build).
+const int* dbg_ldsfill() {
+  static const int pat = [] { const char* e = getenv("CNL_DBG_LDSFILL"); return e ? (int)strtol(e, nullptr, 0) : -1; }();
+  static const bool on = getenv("CNL_DBG_LDSFILL") != nullptr;
+  return on ? &pat : nullptr;
+}
+
+// launches per kernel family since the library was loaded (cnl_launch_counts): [band kernels, register-front kernel, general kernel]
+std::atomic<long long> g_launches[3];
+
+// the time between the handle's two events (cnl_set_timing), once the second one has been recorded
+int read_timing(cnl_handle* h) {
+  HIPCHK(hipEventSynchronize(h->ev1));
+  HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+  return CNL_OK;
+}
+// closes the timed region behind the last launch of a call (cnl_set_timing) and reads it
+int end_timed(cnl_handle* h, hipStream_t stream) {
+  if (!h->timing) return CNL_OK;
+  HIPCHK(hipEventRecord(h->ev1, stream));
+  return read_timing(h);
+}
+
+// the per-problem result arrays of a call, from problem b0 on
+cnl::LaunchArgs shifted(cnl::LaunchArgs a, int64_t b0) {
+  if (a.rho_old) a.rho_old += b0;
+  if (a.rho) a.rho += b0;
+  if (a.nfact) a.nfact += b0;
+  if (a.success) a.success += b0;
+  if (a.npos) a.npos += b0;
+  if (a.nzero) a.nzero += b0;
+  return a;
+}
+
+// A call of the plugin surface on a band handle, either element type (Float32: the element arrays are float arrays behind the
+// double* of LaunchArgs, see as_args): exactly one launch of the band kernels.  try_to_factorize is the forward sweep alone;
+// solve_ldl! factorises the values of the last factorisation again (rho slots as the ladder left them) and sweeps the new
+// right-hand side in the same launch — the band kernels' six-element records hold z = c / d of the one right-hand side they were
+// computed with, so there is no stored factor a second right-hand side could use.
+int run_band(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, double* d_d, hipStream_t stream) {
+  // (a band handle owns the band factor records alone: the buffers of the other kernels do not exist for it)
+  if (a.skip_done || a.only_if_status || (a.mode == cnl::MODE_NEWTON && !d_rhs))
+    return fail(CNL_ERR_STATE, "this call is not served by the band kernels, and a band handle has no other"
+                               " (no factor panels, no condensed buffer; interleaved `vals` are the band kernels' layout)");
+  if (a.mode == cnl::MODE_SOLVE && !h->last_vals) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
+  if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
+  a.vals = a.mode == cnl::MODE_SOLVE ? const_cast<double*>(h->last_vals) : d_vals;
+  a.rhs = d_rhs; a.d = d_d;
+  a.batch = (int)h->batch;
+  a.L = static_cast<double*>(h->d_Lband);
+  a.layout = h->layout;
+  if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
+  const hipError_t e = h->f32 ? cnl::launch_band_f32(h->bd, h->band_nl, a, stream, h->band_npiece)
+                              : cnl::launch_band(h->bd, h->band_nl, a, stream, h->band_npiece, h->band_resident);
+  g_launches[0]++;
+  if (e != hipSuccess)
+    return fail(CNL_ERR_HIP, std::string("band kernel launch (") + (h->f32 ? "Float32, " : "") + std::to_string(h->band_nl) +
+                                 " problems per workgroup): " + hipGetErrorString(e));
+  if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
+  return end_timed(h, stream);
+}
+
+int launch(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
+  if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
+  a.batch = (int)h->batch;
+  a.lean = h->lean ? 1 : 0;
+  a.back_rows = (h->lean && h->plan->P.back_rows) ? 1 : 0;
+  a.L = h->d_L;
+  a.scratch = h->d_scratch;
+  hipError_t e;
+  if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));  // events bracket the multifrontal kernel only
+  if (h->use_v2 && (a.mode != cnl::MODE_SOLVE || h->v2_solve)) {
+    a.scratch = h->d_gs;
+    e = cnl::launch_newton2(h->dp2, h->wpb2, h->lds2, a, stream);
+    g_launches[1]++;
+  } else {
+    e = cnl::launch_newton(h->dp, h->cfg, a, stream);
+    g_launches[2]++;
+  }
+  if (e != hipSuccess)
+    return fail(CNL_ERR_HIP, std::string("kernel launch (tpp=") + std::to_string(h->cfg.tpp) + " ppb=" + std::to_string(h->cfg.ppb) +
+                                 " lds=" + std::to_string(h->cfg.lds_work) + "): " + hipGetErrorString(e));
+  if (h->timing) HIPCHK(hipEventRecord(h->ev1, stream));
+  return CNL_OK;
+}
+
+// one staged pass over the tasks of a latency plan (first attempt of newton_system, try_to_factorize, or solve_ldl!)
+int launch_staged(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
+  if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
+  a.batch = (int)h->batch; a.L = h->d_L; a.scratch = h->d_gs;
+  a.tasks = h->d_tasks; a.gcnt = h->d_gcnt; a.skip_done = 0; a.dep = h->d_dep; a.df_waves = h->df_waves;
+  a.lean = h->lean ? 1 : 0;
+  a.back_rows = (h->lean && h->plan->P.back_rows) ? 1 : 0;
+  a.status_total = h->d_status;
+  a.status_call = h->d_stat;   // (nullptr in views of the handle: one launch per stage, nothing waits)
+  a.lad = h->d_lad; a.lgcnt = h->d_lgcnt; a.ldep = h->d_ldep; a.lad_zero_ints = h->d_stat ? h->zero_ints : 0;
+  a.lad_capacity = h->resident_waves;
+  a.lad_mode = (a.mode == cnl::MODE_NEWTON && h->d_lad && !h->first_attempt_only) ? h->lad_mode : 0;
+  h->ladder_ran = a.lad_mode != 0;
+  a.spin_limit = h->plan->opt.dataflow_spin_limit > 0 ? h->plan->opt.dataflow_spin_limit : (1 << 22);
+  if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
+  hipError_t e = cnl::launch_newton2_staged(h->dp2, h->wpb2, h->lds2, a, h->stage_ptr.data(), (int)h->stage_ptr.size() - 1, stream);
+  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("staged launch: ") + hipGetErrorString(e));
+  return CNL_OK;
+}
+
+}  // namespace
+
+// SubBatch (handle.h): the view is set up by moving the handle's own pointers, and undone when it goes out of scope
+SubBatch::SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged) : h(h_) {
+  last_vals = h->last_vals; staged = h->staged;
+  // (last_vals and the band records are arrays of the handle's element type behind their double* / void*: offsets in bytes)
+  const size_t esz = h->f32 ? sizeof(float) : sizeof(double);
+  if (h->last_vals) h->last_vals = reinterpret_cast<const double*>(reinterpret_cast<const char*>(h->last_vals) + b0 * h->plan->nnz * esz);
+  if (!allow_staged) h->staged = false;
+  batch = h->batch; L = h->d_L; gs = h->d_gs; scratch = h->d_scratch; cbuf = h->d_cbuf; d2 = h->d_d2;
+  xpos = h->d_xpos; xzer = h->d_xzer; gcnt = h->d_gcnt; dep = h->d_dep; lad = h->d_lad; stat = h->d_stat;
+  Lband = h->d_Lband;
+  if (h->d_Lband) h->d_Lband = static_cast<char*>(h->d_Lband) + b0 * h->bd.lsize * esz;
+  const cnl::Cond& C = h->plan->C;
+  h->batch = nb;
+  h->d_L += b0 * h->dp.lsize;
+  if (h->d_gs) h->d_gs += b0 * h->dp2.gs_doubles;
+  if (h->d_scratch) h->d_scratch += b0 * (int64_t)h->dp.work_doubles;
+  if (h->d_cbuf) h->d_cbuf += b0 * C.cstride;
+  if (h->d_d2) h->d_d2 += b0 * C.N2;
+  if (h->d_xpos) h->d_xpos += b0;
+  if (h->d_xzer) h->d_xzer += b0;
+  if (h->d_gcnt) h->d_gcnt += 2 * b0;
+  h->d_dep = nullptr; h->d_lad = nullptr; h->d_stat = nullptr;   // views run one launch per stage and keep the sequential ladder
+}
+
+SubBatch::~SubBatch() {
+  h->batch = batch; h->d_L = L; h->d_gs = gs; h->d_scratch = scratch; h->d_cbuf = cbuf; h->d_d2 = d2;
+  h->d_xpos = xpos; h->d_xzer = xzer; h->d_gcnt = gcnt; h->d_dep = dep; h->d_lad = lad; h->d_stat = stat;
+  h->last_vals = last_vals; h->staged = staged; h->d_Lband = Lband;
+}
+
+namespace {
+
+// Batches between one and two wavefronts per SIMD (4096 .. 8192 problems of cfg3's size): the single stream gives a group of
+// four problems ONE wavefront for 1000 fronts, the bidirectional chain TWO for 500 each, and the machine holds 2048 wavefronts.
+// With x groups on the chain and y on the stream, 2 x + y = 2048 fills every slot whatever the batch: the chain part runs staged
+// on the caller's stream, the rest single-stream on a second stream of the handle, forked and joined with events (no host
+// synchronisation).  Both parts use the SAME plan — the chain order has the throughput order's fronts, and the classic launch
+// runs any plan's records from end to end (it already does behind every staged attempt).
+int run_split(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, double* d_d, hipStream_t stream) {
+  if (!h->aux_stream && !h->tail && !h->split_halves) {
+    HIPCHK(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+  }
+  const int64_t nA = h->split_staged, nB = h->batch - nA, nnz = h->plan->nnz, N = h->plan->N;
+  const bool tm = h->timing;
+  if (tm) HIPCHK(hipEventRecord(h->ev0, stream));
+  h->timing = false;
+  h->in_split = true;
+  if (h->tail) {
+    // 4096 problems fill every wavefront slot on the bidirectional chain (4.1 ms at cfg3's size); a remainder of r <= 1024 problems
+    // takes 0.5 .. 1.7 ms on its own many-part plan, where two halves of the whole batch need 2 x 3 ms (4608 problems: 5.95 -> 5.0 ms)
+    cnl_handle* t = h->tail;
+    const bool on_tail = a.mode != cnl::MODE_SOLVE || h->tail_fresh;
+    int rc;
+    {
+      SubBatch view(h, 0, nA, true);
+      cnl::LaunchArgs b = a;
+      rc = run(h, b, d_vals, d_rhs, d_d, stream);
+    }
+    if (rc == CNL_OK) {
+      cnl::LaunchArgs b = shifted(a, nA);
+      double* tv = d_vals ? d_vals + nA * nnz : nullptr;
+      const double* tr = d_rhs ? d_rhs + nA * N : nullptr;
+      double* td = d_d ? d_d + nA * N : nullptr;
+      if (on_tail) {
+        t->first_attempt_only = h->first_attempt_only;
+        rc = run(t, b, tv, tr, td, stream);
+        t->first_attempt_only = false;
+        if (rc == CNL_OK && a.mode != cnl::MODE_SOLVE) { t->last_vals = tv; t->factorized = true; h->tail_fresh = true; }
+      } else {
+        SubBatch view(h, nA, nB, true);
+        rc = run(h, b, tv, tr, td, stream);
+      }
+    }
+    h->in_split = false;
+    h->timing = tm;
+    if (rc) return rc;
+    if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
+    return end_timed(h, stream);
+  }
+  if (h->split_halves) {
+    // Two halves, each on the bidirectional chain (two wavefronts per group of problems), one behind the other on the caller's
+    // stream: a half of 2304 .. 3840 problems runs at 0.81 .. 0.96 M systems/s, where the single-stream part of the concurrent
+    // split needs its >= 6 ms however few problems it holds (4608 problems: 6.5 ms = 707 k systems/s; two halves: ~5.7 ms).
+    int rc = CNL_OK;
+    for (int part = 0; part < 2 && rc == CNL_OK; part++) {
+      const int64_t b0 = part ? nA : 0, nb = part ? nB : nA;
+      SubBatch view(h, b0, nb, true);
+      cnl::LaunchArgs b = shifted(a, b0);
+      rc = run(h, b, d_vals ? d_vals + b0 * nnz : nullptr, d_rhs ? d_rhs + b0 * N : nullptr, d_d ? d_d + b0 * N : nullptr, stream);
+    }
+    h->in_split = false;
+    h->timing = tm;
+    if (rc) return rc;
+    if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
+    return end_timed(h, stream);
+  }
+  HIPCHK(hipEventRecord(h->ev_fork, stream));
+  HIPCHK(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
+  int rc;
+  {
+    SubBatch view(h, nA, nB, false);
+    cnl::LaunchArgs b = shifted(a, nA);
+    rc = run(h, b, d_vals ? d_vals + nA * nnz : nullptr, d_rhs ? d_rhs + nA * N : nullptr, d_d ? d_d + nA * N : nullptr, h->aux_stream);
+  }
+  if (rc == CNL_OK) {
+    SubBatch view(h, 0, nA, true);
+    rc = run(h, a, d_vals, d_rhs, d_d, stream);
+  }
+  h->in_split = false;
+  h->timing = tm;
+  // join also when an enqueue failed: work already on the second stream must not overlap a later call's use of the handle's arrays
+  const hipError_t je = hipEventRecord(h->ev_join, h->aux_stream);
+  const hipError_t we = je == hipSuccess ? hipStreamWaitEvent(stream, h->ev_join, 0) : je;
+  if (rc) { if (we != hipSuccess) (void)hipStreamSynchronize(h->aux_stream); return rc; }
+  HIPCHK(we);
+  if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
+  return end_timed(h, stream);
+}
+
+// Behind a staged try_to_factorize / solve_ldl! that ran in dataflow fashion: the sequential execution of the same call, which
+// exits at once unless a dataflow wait of the attempt gave up (kernels2.hip, spin_until).  newton_system has its classic launch
+// anyway (the rho ladder of the problems that failed the first attempt).
+int launch_redo(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
+  if (!a.status_call || (!h->d_dep && !h->ladder_ran)) return CNL_OK;  // one launch per stage: nothing waits, nothing can time out
+  const bool tm = h->timing;
+  h->timing = false;
+  a.only_if_status = 1;
+  const int rc = launch(h, a, stream);
+  a.only_if_status = 0;
+  h->timing = tm;
+  return rc;
+}
+
+// The stand-alone condensation passes around a launch on the condensed system (csrc/condense.h).
+// condense: which slots of the handle's condensed buffer are formed from `vals` [and `rhs`] — the values are the tiled kernel's mask
+// (1 matrix, 2 rho, 4 right-hand-side slots), the plain kernel takes the same choice as a slot range
+enum CondensePart { MATRIX_ONLY = 3, RHS_ONLY = 4, WHOLE_SYSTEM = 7 };
+int condense(cnl_handle* h, CondensePart part, const double* vals, const double* rhs, hipStream_t stream) {
+  const cnl::Cond& C = h->plan->C;
+  const int B = (int)h->batch, s_mat = (int)(C.ncs + C.nvar), s_all = (int)C.cstride;
+  const hipError_t e = C.tiled_ok ? cnl::launch_condense_tiled(h->dc, vals, rhs, h->d_cbuf, part, C.ch_region[3], B, stream)
+                                  : cnl::launch_condense(h->dc, vals, rhs, h->d_cbuf, part == RHS_ONLY ? s_mat : 0,
+                                                         part == MATRIX_ONLY ? s_mat : s_all, B, stream);
+  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("condense: ") + hipGetErrorString(e));
+  return CNL_OK;
+}
+// inertia of the condensed pivots, for the kernels that do not count them themselves
+int cond_inertia(cnl_handle* h, const double* vals, double eig_tol, hipStream_t stream) {
+  const hipError_t e = cnl::launch_cond_inertia(h->dc, vals, h->d_xpos, h->d_xzer, eig_tol, (int)h->batch, stream);
+  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("condense: ") + hipGetErrorString(e));
+  return CNL_OK;
+}
+// post-pass: the condensed components of d (and, d2 != nullptr, the kept ones out of the reduced solution)
+int expand(cnl_handle* h, const double* vals, const double* rhs, const double* d2, double* d, const int* success, int copy_rho_tail,
+           hipStream_t stream) {
+  const hipError_t e = cnl::launch_expand(h->dc, const_cast<double*>(vals), rhs, d2, h->d_cbuf, d, success, copy_rho_tail, (int)h->batch, stream);
+  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("expand: ") + hipGetErrorString(e));
+  return CNL_OK;
+}
+
+}  // namespace
+
+// One call of the path on device-resident data: [condense ->] multifrontal kernel [-> expand].
+int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, double* d_d, hipStream_t stream) {
+  const cnl::Cond& C = h->plan->C;
+  int rc = CNL_OK;
+  if (h->split_staged > 0 && !h->in_split && (h->staged || h->tail) && h->split_staged < h->batch) return run_split(h, a, d_vals, d_rhs, d_d, stream);
+  if (h->band) return run_band(h, a, d_vals, d_rhs, d_d, stream);
+  if (h->dense || h->gdense)
+    if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
+  if (h->dense) {
+    // dense residual block: J'WJ + tiled dense LDL^T on the fp64 matrix cores (csrc/dense.hip); asynchronous, the rho ladder
+    // is decided on the device
+    std::string err;
+    if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
+    rc = cnl::dense_run(h->dense, h->plan->D, a.mode, d_vals, d_rhs, d_d, a.rho_old, a.rho, a.nfact, a.success, a.npos, a.nzero,
+                        a.params, stream, err);
+    if (rc) return fail(rc == 5 ? CNL_ERR_STATE : CNL_ERR_HIP, "dense backend: " + err);
+    return end_timed(h, stream);
+  }
+  if (h->gdense) {
+    // condensed system as one dense matrix: condense pass -> dense LDL^T / solves (csrc/dense.hip) -> post-pass
+    std::string err;
+    if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
+    if (a.mode == cnl::MODE_SOLVE) {
+      if (!h->last_vals) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
+      if ((rc = condense(h, RHS_ONLY, h->last_vals, d_rhs, stream))) return rc;
+    } else {
+      const bool nw = a.mode == cnl::MODE_NEWTON;
+      if ((rc = condense(h, nw ? WHOLE_SYSTEM : MATRIX_ONLY, d_vals, nw ? d_rhs : nullptr, stream))) return rc;
+      if ((rc = cond_inertia(h, d_vals, a.params[0], stream))) return rc;
+    }
+    rc = cnl::dense_run_general(h->gdense, h->gops, a.mode, h->d_cbuf, h->d_xpos, h->d_xzer, h->d_d2,
+                                d_vals ? d_vals + (C.nnz - C.nvar) : nullptr, C.nnz, a.rho_old, a.rho, a.nfact, a.success, a.npos, a.nzero,
+                                a.params, stream, err);
+    if (rc) return fail(CNL_ERR_HIP, "dense backend: " + err);
+    if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
+    else {
+      const double* vsrc = a.mode == cnl::MODE_SOLVE ? h->last_vals : d_vals;
+      if ((rc = expand(h, vsrc, d_rhs, h->d_d2, d_d, a.mode == cnl::MODE_NEWTON ? a.success : nullptr, 0, stream))) return rc;
+    }
+    return end_timed(h, stream);
+  }
+  if (!C.active) {
+    a.vals = d_vals; a.rhs = d_rhs; a.d = d_d;
+    rc = launch(h, a, stream);
+  } else {
+    double* crhs = h->d_cbuf + (C.ncs + C.nvar);   // the right-hand-side slots of the condensed buffer
+    const bool direct = h->use_v2 && h->plan->P.rec_direct;  // the register-front kernel condenses on the fly
+    const bool count_d = direct && h->dp2.count_d;  // the kernel counts the condensed pivots itself
+    if (direct && a.mode == cnl::MODE_NEWTON) {
+      if (!count_d && (rc = cond_inertia(h, d_vals, a.params[0], stream))) return rc;
+      const bool d_outer = h->plan->P.d_outer;  // the kernel writes the kept components of d itself
+      a.vals = d_vals; a.rhs = d_rhs; a.d = d_outer ? d_d : h->d_d2;
+      a.extra_pos = count_d ? nullptr : h->d_xpos; a.extra_zer = count_d ? nullptr : h->d_xzer;
+      if (h->staged) {
+        // first attempt (rho as given) stage by stage: the tasks of the elimination tree run on different wavefronts; the
+        // problems that fail it (rare) go through the whole ladder in the classic launch behind it
+        if ((rc = launch_staged(h, a, stream))) return rc;
+        if (h->ladder_ran) {
+          // the problems that failed the attempt have climbed the rho ladder inside the fused launch(es) (kernels2.hip, phase 2);
+          // the sequential launch behind them commits rho_old and the rho slots — or, if a wait gave up, redoes the whole call
+          if ((rc = launch_redo(h, a, stream))) return rc;
+        } else if (h->first_attempt_only) {
+          // the host ladder follows; the sequential launch only if a dataflow wait of the attempt gave up (it then redoes the whole
+          // call on the device, ladder included: the host finds the per-call status word set and leaves the results alone)
+          if (h->d_dep && (rc = launch_redo(h, a, stream))) return rc;
+        } else {
+          a.skip_done = 1;
+          const bool tm = h->timing;
+          h->timing = false;
+          rc = launch(h, a, stream);
+          h->timing = tm;
+          if (rc) return rc;
+        }
+        if (h->timing) HIPCHK(hipEventRecord(h->ev1, stream));
+      } else if ((rc = launch(h, a, stream))) return rc;
+      // (the lean instantiation has recovered the residual components in its backward sweep: plan.h, B_ROWS_FLAG)
+      if (!(h->lean && h->plan->P.back_rows) && (rc = expand(h, d_vals, d_rhs, d_outer ? nullptr : h->d_d2, d_d, a.success, 0, stream))) return rc;
+    } else if (direct && a.mode == cnl::MODE_FACTOR) {
+      if (!count_d && (rc = cond_inertia(h, d_vals, a.params[0], stream))) return rc;
+      a.vals = d_vals; a.extra_pos = count_d ? nullptr : h->d_xpos; a.extra_zer = count_d ? nullptr : h->d_xzer;
+      if (h->staged) {  // try_to_factorize stage by stage (the elimination tree's tasks on different wavefronts)
+        if ((rc = launch_staged(h, a, stream))) return rc;
+        if ((rc = launch_redo(h, a, stream))) return rc;
+        if (h->timing) HIPCHK(hipEventRecord(h->ev1, stream));
+      } else if ((rc = launch(h, a, stream))) return rc;
+      h->last_vals = d_vals;
+    } else if (a.mode == cnl::MODE_NEWTON) {
+      if ((rc = condense(h, WHOLE_SYSTEM, d_vals, d_rhs, stream))) return rc;
+      if ((rc = cond_inertia(h, d_vals, a.params[0], stream))) return rc;
+      a.vals = h->d_cbuf; a.rhs = crhs; a.d = h->d_d2; a.extra_pos = h->d_xpos; a.extra_zer = h->d_xzer;
+      if ((rc = launch(h, a, stream))) return rc;
+      if ((rc = expand(h, d_vals, d_rhs, h->d_d2, d_d, a.success, 1, stream))) return rc;
+    } else if (a.mode == cnl::MODE_FACTOR) {
+      if ((rc = condense(h, MATRIX_ONLY, d_vals, nullptr, stream))) return rc;
+      if ((rc = cond_inertia(h, d_vals, a.params[0], stream))) return rc;
+      a.vals = h->d_cbuf; a.extra_pos = h->d_xpos; a.extra_zer = h->d_xzer;
+      if ((rc = launch(h, a, stream))) return rc;
+      h->last_vals = d_vals;
+    } else if (direct && h->v2_solve) {
+      // solve_ldl! on the register-front kernel: forward substitution with the stored factor, backward sweep, post-pass
+      if (!h->last_vals) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
+      a.vals = const_cast<double*>(h->last_vals); a.rhs = d_rhs; a.d = d_d;
+      if (h->staged) {  // solve_ldl! stage by stage: forward substitution of the tasks, then their backward sweeps
+        if ((rc = launch_staged(h, a, stream))) return rc;
+        if ((rc = launch_redo(h, a, stream))) return rc;
+        if (h->timing) HIPCHK(hipEventRecord(h->ev1, stream));
+      } else if ((rc = launch(h, a, stream))) return rc;
+      // (lean plans: the solve-only instantiation has recovered the residual components in its backward sweep)
+      if (!(h->lean && h->plan->P.back_rows) && (rc = expand(h, h->last_vals, d_rhs, nullptr, d_d, nullptr, 0, stream))) return rc;
+    } else {
+      if (!h->last_vals) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
+      if ((rc = condense(h, RHS_ONLY, h->last_vals, d_rhs, stream))) return rc;
+      a.rhs = crhs; a.d = h->d_d2;
+      if ((rc = launch(h, a, stream))) return rc;
+      if ((rc = expand(h, h->last_vals, d_rhs, h->d_d2, d_d, nullptr, 0, stream))) return rc;
+    }
+  }
+  if (rc) return rc;
+  return h->timing ? read_timing(h) : CNL_OK;
+}
+
+extern "C" int cnl_launch_counts(int64_t counts[3]) {
+  if (!counts) return fail(CNL_ERR_ARG, "null argument");
+  for (int k = 0; k < 3; k++) counts[k] = g_launches[k].load();
+  return CNL_OK;
+}

@@ -39,7 +39,7 @@ int dense_run(DenseState* st, const DensePlan& D, int mode, double* vals, const 
               hipStream_t stream, std::string& err);
 
 // ---- the same dense machinery for an ARBITRARY condensed system (csrc/condense.h) of moderate order: plans whose fill makes
-// the fronts larger than the register-front kernel takes (irregular sparsity) and whose batch is small.  The caller (capi.cpp)
+// the fronts larger than the register-front kernel takes (irregular sparsity) and whose batch is small.  The caller (capi_run.cpp)
 // owns the condensed buffer; per problem it hands over the slots of K2, and gets the factor / solution back.
 struct GeneralOps {
   int32_t ns = 0, nv = 0;          // order of the condensed system, number of variables (they carry rho)

@@ -1,0 +1,247 @@
+// handle.h — what the translation units of the C ABI driver (capi_*.cpp) share: the plan, handle and multi-handle structures, the
+// error helpers and the few functions that cross files.  Host side only: no .hip file includes it.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <functional>
+#include <mutex>
+#include <cfloat>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/cannoles_hip.h"
+#include "band.h"
+#include "condense.h"
+#include "dense.h"
+#include "kernels.h"
+#include "options.h"
+#include "plan.h"
+
+struct cnl_plan {
+  cnl::Cond C;   // static condensation of the residual block (outer -> condensed system)
+  cnl::Plan P;   // multifrontal plan of the (condensed) system
+  int64_t N = 0, nnz = 0, nvar = 0, nequ = 0, ncon = 0;  // outer dimensions, as the reference sees them
+  std::vector<int32_t> perm_outer;
+  bool latency = false;  // ordered and cut into tasks for small batches (staged execution, csrc/plan.h)
+  bool prefer_dense = false;  // latency plan with fronts of the 64 class on a small condensed system: small batches go the dense route
+  cnl::DensePlan D;  // dense residual block (BASELINE config 2): served by the dense backend, csrc/dense.h
+  std::vector<int32_t> gpos;  // non-empty: the condensed system may be treated as ONE dense matrix (position of every K2 slot)
+  cnl::Tuning opt{};          // the switches the plan was built with (options.h; the handle reads its execution switches from here)
+  std::atomic<int> refs{1};   // handles of a cnl_multi share one analysis (read-only after creation)
+  bool split_mode = false;    // bidirectional-chain plan for a batch between one and two wavefronts per SIMD (capi_run.cpp, run_split)
+  // (round 5) band programs of a throughput plan (csrc/band.h), [f32][wide]: for 8-byte (Float64 handles) and 4-byte elements
+  // (Float32 handles), each in the 15-piece form and in the WIDE form (band.h: BAND_NPIECE_WIDE operand pieces per epoch), which is
+  // built where the pattern needs more than 15 pieces — a constrained model's H_c as wide as H_F — or where tuning band_pieces = 20
+  // asks for it.  B.ok == false: the pattern is no band (of that form).  info / pinfo: the summaries cnl_plan_get returns.
+  struct BandSlot {
+    cnl::BandPlan B;
+    std::vector<int32_t> info, pinfo[2];
+  };
+  BandSlot band_prog[2][2];
+  // the RESIDENT form of band_prog[0][0] (band.h: aligned blocks of `vals` that stay in LDS while the next epoch needs them), built
+  // beside it unless tuning band_resident = 0; runs the Float64 handles of 32 problems per workgroup with interleaved `vals`
+  BandSlot band_res;
+};
+
+struct cnl_handle {
+  cnl_plan* plan = nullptr;
+  int device = 0;
+  int64_t batch = 1;
+  std::vector<void*> dev_allocs;
+  cnl::DevPlan dp{};
+  cnl::KernelConfig cfg{};
+  // v2 (register-front kernel): used for newton_system / factorize when every front has order <= 64
+  bool use_v2 = false;
+  bool staged = false;    // newton_system: first attempt stage by stage (tasks of the elimination tree on different wavefronts)
+  const int32_t* d_tasks = nullptr;
+  int* d_gcnt = nullptr;
+  void* pin = nullptr;    // pinned host block for the results of small host-pointer calls
+  size_t pin_bytes = 0;
+  int* d_dep = nullptr;   // dataflow counters of the staged execution (nullptr: one launch per stage)
+  int* d_status = nullptr;  // [1] dataflow waits that gave up (sticky; kernels2.hip spin_until)
+  // counters of a staged call, ONE allocation behind d_gcnt, zeroed with one memset per call:
+  // [gcnt 2B | lgcnt 2B | lad LAD_WORDS * nquads | ldep 2 * tasks * nquads | stat 2 | dep 2 * tasks * nquads (dataflow only)]
+  int *d_lgcnt = nullptr, *d_lad = nullptr, *d_ldep = nullptr, *d_stat = nullptr;
+  long long zero_ints = 0;
+  int resident_waves = 0;   // wavefronts of the register-front kernel the device holds at once
+  int lad_mode = 0;         // in-kernel rho ladder of staged newton_system calls (kernels.h): 0 none, 1 behind the staged attempt, 2 fused
+  bool ladder_ran = false;  // the last launch_staged enqueued fused ladder launches (their commit / redo launch must follow)
+  int ntasks = 0;
+  int df_waves = 1024;
+  std::vector<int32_t> stage_ptr;
+  bool v2_solve = false;  // cnl_solve runs on the register-front kernel too (direct records, every front of the fast class)
+  bool first_attempt_only = false;  // newton_system on a staged handle: no sequential launch behind the staged attempt (the host ladder follows)
+  int* d_act = nullptr;   // [batch] problems whose rho slots the host ladder rewrites
+  bool lean = false;      // every front of the fast class with row-form (or no) products: the kernels' LEAN instantiation serves it
+  cnl::DevPlan2 dp2{};
+  int wpb2 = 1;
+  size_t lds2 = 0;
+  double* d_gs = nullptr;
+  // condensation state
+  cnl::DevCond dc{};
+  double* d_cbuf = nullptr;   // [batch][cstride]
+  double* d_d2 = nullptr;     // [batch][N2]
+  int *d_xpos = nullptr, *d_xzer = nullptr;
+  const double* last_vals = nullptr;  // device vals of the last factorisation (needed to condense later right-hand sides)
+  double* d_L = nullptr;
+  double* d_scratch = nullptr;
+  // staging for the host-pointer API, in the handle's element type (capi_calls.cpp: ensure_staging, stage<T>): vals, rhs, d, the
+  // per-problem results as one block [rho | rho_old | nfact | success] (nfact / success: int32), and [npos | nzero]
+  void *d_vals = nullptr, *d_rhs = nullptr, *d_d = nullptr, *d_res = nullptr;
+  int64_t* d_npos = nullptr;
+  hipStream_t stream = nullptr;
+  int64_t split_staged = 0;   // > 0: problems [0, split_staged) run staged, the rest single-stream, concurrently (run_split)
+  bool split_halves = false;  // ... or (round 4): the rest runs staged as well, BEHIND the first part on the same stream (two halves)
+  bool in_split = false;
+  // (round 4) a batch a little above what fills the machine on the bidirectional chain (staged_max_batch < batch <= 5/4 of it):
+  // problems [0, split_staged) run on this handle's chain plan, the REMAINDER on a handle of its own with the many-part latency
+  // plan cnl_create picks for that small batch, one behind the other on the caller's stream (run_split)
+  cnl_handle* tail = nullptr;
+  bool tail_redone = false;   // (per call) a dataflow wait of the remainder handle gave up: its redo launch has been through the whole device
+                              // ladder for those problems — the host ladder must leave them alone
+  bool tail_fresh = false;    // the factors of the remainder live in the tail handle (false: in this handle's storage — chunked host calls)
+  hipStream_t aux_stream = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  static constexpr int kPipeUp = 2;  // host threads that upload chunks of a host-pointer call (each on its own stream)
+  hipStream_t pipe_stream[kPipeUp + 1] = {};  // chunked host-pointer calls: the uploaders' compute streams, one more for the results
+  std::vector<hipEvent_t> pipe_ev;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool timing = false;
+  float last_ms = 0.f;
+  bool factorized = false;
+  // success flags of the last HOST-pointer factorisation (cnl_factorize / cnl_newton_system), for cnl_solve: the reference never
+  // solves after a failed factorisation (src/CaNNOLeS.jl:1049) — a one-problem cnl_solve then is a call-sequence error, and a
+  // batched one leaves the rows of the failed problems untouched.  Unknown (empty) after a device-pointer factorisation.
+  std::vector<char> last_ok;
+  cnl::DevJt djt{};  // transposed-Jacobian lists (row f1: residual / optimality vectors on the device)
+  cnl::DenseState* dense = nullptr;
+  cnl::DenseState* gdense = nullptr;  // dense treatment of an arbitrary condensed system (irregular sparsity, small batch)
+  cnl::GeneralOps gops{};
+  void* cgls_ws = nullptr;    // [batch][2 * nvar] elements: workspace of cnl_cgls_multipliers_dev / _f32_dev, allocated on first use
+  // (round 5) band kernels (csrc/band.h): newton_system of a throughput handle whose pattern is a band
+  bool band = false;
+  cnl::BandDev bd{};
+  int band_nl = 16;            // problems per workgroup
+  int band_npiece = 15;        // operand pieces per epoch of the program in bd: 15, or 20 = the wide kernel instances
+  bool band_resident = false;  // bd holds the plan's resident program (cnl_plan::band_res): the resident kernel instance runs it
+  bool jac_segments = false;   // the J_F and the J_c entries are one run of slots each: [jf_lo, jf_lo + jf_n), [jc_lo, jc_lo + jc_n)
+  int64_t jf_lo = 0, jf_n = 0, jc_lo = 0, jc_n = 0;
+  int layout = 0;              // band handles: bit 0 = vals (cnl_options.batch_layout), bit 1 = rhs interleaved over groups of 32 problems (band.h)
+  void* d_Lband = nullptr;     // [batch + 32][bd.lsize] factor records of the band kernels, in the handle's element type
+  // Float32 handle (cnl_create_f32): the band kernels on float data, bd = the 4-byte program, and the row lists of rows f1 / f4 (djt,
+  // jac_segments); nothing else of the handle's device state exists, and every Float64 entry point refuses it (CNL_ERR_STATE).
+  // last_vals holds its float array of the last factorisation (the band solve factorises those values again).
+  bool f32 = false;
+};
+
+struct cnl_multi {
+  std::vector<cnl_handle*> h;
+  std::vector<int64_t> start, count;
+  std::vector<int> device;
+  int64_t N = 0, nnz = 0, batch = 0;
+  // one persistent host thread per shard (created with the handle, bound to the shard's device once): the host-pointer
+  // calls hand each of them a job and wait; no thread is created or joined per call
+  std::vector<std::thread> workers;
+  std::mutex mu;
+  std::condition_variable cv_job, cv_done;
+  std::function<int(size_t)> job;
+  uint64_t generation = 0;
+  size_t pending = 0;
+  bool stop = false;
+  std::vector<int> rc;
+  std::vector<std::string> msg;
+};
+
+// Everything below is internal to the library: hidden from its dynamic symbol table, which holds the C ABI alone.
+#pragma GCC visibility push(hidden)
+
+extern thread_local std::string g_err;   // the text cnl_last_error returns (defined in capi_plan.cpp)
+
+inline int fail(int code, const std::string& m) {
+  g_err = m;
+  return code;
+}
+
+// element type of a handle against that of the entry point: mixing them is a call-sequence error, refused before anything runs
+inline int need_f64(const cnl_handle* h, const char* fn) {
+  if (h && h->f32) return fail(CNL_ERR_STATE, std::string(fn) + ": this is a Float32 handle (cnl_create_f32); it takes the _f32 entry points only");
+  return CNL_OK;
+}
+inline int need_f32(const cnl_handle* h, const char* fn) {
+  if (h && !h->f32) return fail(CNL_ERR_STATE, std::string(fn) + ": this is a Float64 handle; the _f32 entry points need one made by cnl_create_f32");
+  return CNL_OK;
+}
+#define CNL_NEED_F64(h) do { if (int rc_ = need_f64((h), __func__)) return rc_; } while (0)
+#define CNL_NEED_F32(h) do { if (int rc_ = need_f32((h), __func__)) return rc_; } while (0)
+
+#define HIPCHK(expr)                                                                                   \
+  do {                                                                                                 \
+    hipError_t e_ = (expr);                                                                            \
+    if (e_ != hipSuccess) return fail(CNL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+template <class T>
+int upload(cnl_handle* h, const std::vector<T>& v, const T** out) {
+  void* p = nullptr;
+  size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
+  HIPCHK(hipMalloc(&p, bytes));
+  h->dev_allocs.push_back(p);
+  if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  *out = (const T*)p;
+  return CNL_OK;
+}
+
+template <class T>
+int dalloc(cnl_handle* h, T** out, size_t count) {
+  void* p = nullptr;
+  static const size_t G = getenv("CNL_DBG_GUARD") ? (size_t)atol(getenv("CNL_DBG_GUARD")) : 0;   // debugging aid: NaN-filled guard zones
+  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+  HIPCHK(hipMalloc(&p, bytes + 2 * G));
+  if (G) HIPCHK(hipMemset(p, getenv("CNL_DBG_GUARD_PAT") ? atoi(getenv("CNL_DBG_GUARD_PAT")) : 0xFF, bytes + 2 * G));
+  h->dev_allocs.push_back(p);
+  *out = (T*)(static_cast<char*>(p) + G);
+  if (G && getenv("CNL_DBG_GUARD_LOG")) fprintf(stderr, "[dalloc] #%zu %p + %zu bytes\n", h->dev_allocs.size(), (void*)*out, bytes);
+  return CNL_OK;
+}
+
+// ---- capi_plan.cpp ----
+int resolve_options(const cnl_options* in, cnl::Tuning& out);
+int plan_create_tuned(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ,
+                      int64_t ncon, int64_t batch, const cnl::Tuning& o);
+int plan_create_impl(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ,
+                     int64_t ncon, int latency, int par, double slots, const cnl::Tuning& o);
+void build_band_programs(cnl_plan* p, const int64_t* rows1, const int64_t* cols1, int esz);
+void band_summaries(cnl_plan* p);
+const cnl::BandPlan& band_program(const cnl_plan* plan, bool f32);
+
+// ---- capi_handle.cpp ----
+int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device);
+
+// ---- capi_run.cpp ----
+int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, double* d_d, hipStream_t stream);
+
+// run() on problems [b0, b0 + nb) of the handle: the base pointer of every per-problem device array of the handle is moved to
+// problem b0 and the batch set to nb for the lifetime of the view (b0 a multiple of 4: a wavefront serves four problems).
+// Dataflow counters are per handle, not per view: views run one launch per stage.
+struct SubBatch {
+  cnl_handle* h;
+  int64_t batch;
+  double *L, *gs, *scratch, *cbuf, *d2;
+  void* Lband;
+  int *xpos, *xzer, *gcnt, *dep, *lad, *stat;
+  const double* last_vals;
+  bool staged;
+  SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged = true);
+  ~SubBatch();
+};
+
+#pragma GCC visibility pop

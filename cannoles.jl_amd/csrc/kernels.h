@@ -1,4 +1,4 @@
-// kernels.h — launch interface between the C ABI (capi.cpp) and the HIP kernels.
+// kernels.h — launch interface between the C ABI driver (capi_*.cpp) and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime_api.h>
 

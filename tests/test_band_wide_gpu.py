@@ -330,7 +330,7 @@ def test_lockstep_loop_of_a_constrained_family_runs_on_the_band_kernels(built):
     (tolerances of tests/test_gpu_parity.py::test_f3_device_resident_lockstep_outer_loop), and layout = "problem-major" gives the same
     counters for all.
     B: with default options a CONSTRAINED band pattern between 4 097 and 7 680 problems is served by the split plan (bidirectional chain
-    + single stream, "v2-staged": csrc/capi.cpp, split_mode) — band_structure(300, 4) with its diagonal H_c just as the model-shaped
+    + single stream, "v2-staged": csrc/capi_plan.cpp, split_mode) — band_structure(300, 4) with its diagonal H_c just as the model-shaped
     pattern — and the wide form is offered only where the register-front throughput handle runs, so the first batch a band handle serves is
     7 681; only unconstrained families get one from 4 097 on."""
     import torch

@@ -170,6 +170,18 @@ def test_two_call_sequence(built):
     c1 = hipldl.launch_counts()
     assert c1["band"] - c0["band"] == 3 and c1["register_front"] == c0["register_front"] and c1["general"] == c0["general"]
     L.close()
+    # one problem whose factorisation failed: solve_ldl! is a call-sequence error (CNL_ERR_STATE), refused before anything is uploaded
+    # or launched, and d stays as passed (the Float32 twin of test_gpu_parity.test_solve_after_a_failed_factorisation)
+    L1 = hipldl.HIPLDLStruct(s.N, rows, cols, lv[0].copy(), s.nvar, s.nequ, s.ncon, batch=1)
+    assert L1.config["float32"]
+    assert not hipldl.try_to_factorize(L1, lv[0], s.nvar, s.nequ, s.ncon, p32[0])
+    d7 = np.full(s.N, 7.0, np.float32)
+    c2 = hipldl.launch_counts()
+    with pytest.raises(hipldl.CnlError) as ei:
+        hipldl.solve_ldl_(lr[0], L1.factor, d7)
+    assert ei.value.code == 5 and (d7 == 7.0).all()
+    assert hipldl.launch_counts() == c2
+    L1.close()
 
 
 @pytest.mark.parametrize("layout", [0, 1])

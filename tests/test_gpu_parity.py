@@ -712,7 +712,7 @@ def test_headline_pattern_large_batch_sample_vs_oracle(built, B, kernel, order, 
     csrc/band.hip LINT; bench.py's 16 384 problems differ only in the grid size), with one problem that climbs the rho ladder inside a
     workgroup of convex ones; B = 8192: the band kernels with 16 problems per workgroup; B = 4608 forced onto the throughput plan;
     then a batch between one and two wavefronts per SIMD (B = 4608: the first 4096 problems on the bidirectional chain, the remaining
-    512 behind them on a handle of their own with a many-part plan — csrc/capi.cpp, run_split, cnl_options.split_tail), one the
+    512 behind them on a handle of their own with a many-part plan — csrc/capi_run.cpp, run_split, cnl_options.split_tail), one the
     bidirectional chain serves alone (B = 3584) and one with many large parts (B = 1536): the whole batch through
     cnl_newton_system_dev, a random sample of 32 problems against the oracle; in the split batch one problem of each part also
     climbs the rho ladder.  config["band"] / ["band_nl"] are asserted: which kernel ran is part of what the test pins."""
@@ -1064,7 +1064,7 @@ def test_split_batch_factorize_then_solve(built):
 def test_split_tail_remainder_on_its_own_plan(built, nA, kernel, order):
     """A batch a little above the one that fills the machine on the bidirectional chain (4096 + r problems, r <= 1024): the first
     4096 problems run on the handle's chain plan, the remainder on a handle of its own with the many-part plan of a batch of r, one
-    behind the other (csrc/capi.cpp, run_split; cnl_options.split_tail).  Against the two-halves form (split_tail = 0) on the same
+    behind the other (csrc/capi_run.cpp, run_split; cnl_options.split_tail).  Against the two-halves form (split_tail = 0) on the same
     data: every decision (success, nfact, rho, rho_old, the rho slots) bit for bit, d to the forward tolerance (the remainder's plan
     has another elimination order); a sample of both parts against the oracle — ladder climbers in both parts, a hopeless problem
     in the remainder.  Then the call sequences that must find each part's own factor: try_to_factorize_dev + solve_dev, and the
@@ -1205,7 +1205,7 @@ def test_split_tail_odd_remainders(built, B):
 
 def test_host_pointer_call_pipelined_in_chunks(built):
     """cnl_newton_system with host pointers on a batch above 96 MB runs chunk by chunk (upload of chunk c + 1, compute of chunk c
-    and download of chunk c - 1 overlap; csrc/capi.cpp, newton_system_pipelined).  Every output must equal the device-resident
+    and download of chunk c - 1 overlap; csrc/capi_calls.cpp, newton_system_pipelined).  Every output must equal the device-resident
     call's on the same handle, bit for bit — including a problem that climbs the rho ladder (its rho slots are written back)
     and a hopeless one (its d stays as the caller left it) — and a sample is checked against the oracle."""
     import torch
@@ -1636,7 +1636,7 @@ def test_random_structures_mid_size_batches(built, seed, B):
     info, cfg = run_case(s, vals, rhs)
     # fronts of order 73 .. 95: too large for the register-front kernel.  Round 2 sent such batches to the general kernel
     # ("v1", correct but slow); they now run as 64 x 64 tiles on the dense machinery (MFMA trailing updates) at any batch size
-    # that fits (csrc/capi.cpp; 2.1 M against 0.3 .. 0.5 M systems/s at 640 problems, tools/time_irregular.py)
+    # that fits (csrc/capi_handle.cpp; 2.1 M against 0.3 .. 0.5 M systems/s at 640 problems, tools/time_irregular.py)
     assert info["fmax"] > 64 and cfg["kernel"] == "dense"
     # the general kernel itself stays covered
     if B == 96:
@@ -1686,7 +1686,7 @@ def test_residual_components_in_the_backward_sweep(built, B):
 @pytest.mark.parametrize("B", [1, 4, 120])   # 120: past the single pinned block of the smallest batches (separate copies)
 def test_host_driven_ladder_equals_the_device_ladder(built, B):
     """The small-batch host-pointer newton_system! drives the rho ladder from the host — every rung a staged try_to_factorize
-    (csrc/capi.cpp; src/CaNNOLeS.jl:1023-1047) — instead of handing failed problems to the sequential device launch
+    (csrc/capi_calls.cpp; src/CaNNOLeS.jl:1023-1047) — instead of handing failed problems to the sequential device launch
     (cnl_options.host_ladder = 0): both must return the oracle's (success, nfact, rho, rho_old) bit for bit, the rho slots of
     vals as the reference leaves them, a solution for the problems that succeed and an untouched d for the hopeless one —
     for a batch that mixes a convex problem (no ladder), ladder climbers with rho_old = 0 and rho_old > 0, and a hopeless one."""
@@ -2179,7 +2179,7 @@ def test_band_two_call_sequence_device_pointers(built):
 @pytest.mark.parametrize("B", [16384 + 37, 8192 + 5])
 def test_band_remainder_handle(built, B):
     """band kernels: 512 workgroups of 32 problems are resident at once (16 384 problems); a batch of one such load + r problems gives
-    the remainder a handle of its own (csrc/capi.cpp, run_split), a batch below it runs in one launch.  Decisions and a sample of
+    the remainder a handle of its own (csrc/capi_run.cpp, run_split), a batch below it runs in one launch.  Decisions and a sample of
     solutions against the oracle; a ladder climber sits in the last problem (in the remainder), solve_ldl! behind it finds each
     part's factor."""
     hipldl, syn, O = _mods()

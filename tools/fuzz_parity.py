@@ -48,7 +48,7 @@ for case in range(ncases):
         else:
             cr_ = cc_ = np.zeros(0, np.int64); hc_s = (np.zeros(0, np.int64), np.zeros(0, np.int64))
         s = syn.Structure(n, m, pc, hF_, hc_s, (jr_ + 1, jc_ + 1), (cr_, cc_), name="degenerate")
-    elif fam == 5:   # a batch just above a (small) staged_max_batch: the chain + a remainder handle, or two halves (capi.cpp, run_split)
+    elif fam == 5:   # a batch just above a (small) staged_max_batch: the chain + a remainder handle, or two halves (capi_run.cpp, run_split)
         pc = int(rng.integers(1, 4)); blocks = int(rng.integers(30, 80)); n = pc * blocks
         s = syn.band_structure(n, pc, hw=2)
     elif fam == 4:   # band family at larger batches: staged plans with many groups of problems, the in-kernel ladder over several groups

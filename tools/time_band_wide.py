@@ -10,7 +10,7 @@ device-resident newton_system!, per-call device events around the `_dev` call af
                  alternates fresh processes on this tree's library and on the other one (a build of the parent commit:
                  tools/ab_lib.py build parent <ref>) with default options — the other library runs what it runs on this pattern
                  (before the wide form: the register-front kernel) — and prints both medians per batch size and round.
-Float64 handles take the wide kernel automatically only where this comparison showed it faster (csrc/capi.cpp, band_wide_serves_f64)."""
+Float64 handles take the wide kernel automatically only where this comparison showed it faster (csrc/capi_handle.cpp, band_wide_serves_f64)."""
 import argparse
 import json
 import os
