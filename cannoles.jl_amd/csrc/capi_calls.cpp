@@ -100,6 +100,7 @@ Results<T> newton_results(const Stage<T>& s, size_t b0 = 0) {
 // cnl_solve consults; nullptr after a device-pointer call, whose flags the host has not seen
 void holds_factor(cnl_handle* h, const void* d_vals, const int32_t* ok = nullptr) {
   h->factorized = true;
+  h->factor_batch = h->batch;
   h->last_vals = static_cast<const double*>(d_vals);
   if (ok) h->last_ok.assign(ok, ok + h->batch);
   else h->last_ok.clear();
@@ -131,7 +132,7 @@ int cgls_impl(cnl_handle* h, const cnl::JacSrcT<T>& S, const T* d_r, T* d_lambda
   HIPCHK(hipSetDevice(h->device));
   T* ws = static_cast<T*>(h->cgls_ws);   // (the entry points have checked T against the handle's element type)
   if (!ws) {
-    int rc = dalloc(h, &ws, (size_t)h->batch * 2 * (size_t)h->djt.nvar);
+    int rc = dalloc(h, &ws, (size_t)h->full_batch * 2 * (size_t)h->djt.nvar);   // (the created batch: cnl_set_active_batch may widen the handle again)
     if (rc) return rc;
     h->cgls_ws = ws;
   }
@@ -192,6 +193,9 @@ int factorize_dev_impl(cnl_handle* h, const T* d_vals, T eig_tol, int32_t* d_suc
 template <class T>
 int solve_dev_impl(cnl_handle* h, const T* d_rhs, T* d_d, void* stream) {
   if (!h->factorized) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
+  if (h->factor_batch < h->batch)
+    return fail(CNL_ERR_STATE, "cnl_solve_dev on " + std::to_string(h->batch) + " problems behind a factorisation of " + std::to_string(h->factor_batch) +
+                                   " (cnl_set_active_batch widened the handle in between)");
   HIPCHK(hipSetDevice(h->device));
   return run_typed<T>(h, cnl::MODE_SOLVE, nullptr, 0, Results<T>(), nullptr, d_rhs, d_d, (hipStream_t)stream);
 }
@@ -794,22 +798,26 @@ int cnl_newton_system_f32_dev(cnl_handle* h, float* d_vals, const float* d_rhs, 
 int cnl_factorize(cnl_handle* h, const double* vals, double eig_tol, int32_t* success, int64_t* npos, int64_t* nzero) {
   if (!h || !vals || !success) return fail(CNL_ERR_ARG, "null argument");
   CNL_NEED_F64(h);
+  CNL_NEED_FULL_BATCH(h);
   return factorize_impl(h, vals, eig_tol, success, npos, nzero);
 }
 int cnl_factorize_f32(cnl_handle* h, const float* vals, float eig_tol, int32_t* success, int64_t* npos, int64_t* nzero) {
   if (!h || !vals || !success) return fail(CNL_ERR_ARG, "null argument");
   CNL_NEED_F32(h);
+  CNL_NEED_FULL_BATCH(h);
   return factorize_impl(h, vals, eig_tol, success, npos, nzero);
 }
 
 int cnl_solve(cnl_handle* h, const double* rhs, double* d) {
   if (!h || !rhs || !d) return fail(CNL_ERR_ARG, "null argument");
   CNL_NEED_F64(h);
+  CNL_NEED_FULL_BATCH(h);
   return solve_impl(h, rhs, d);
 }
 int cnl_solve_f32(cnl_handle* h, const float* rhs, float* d) {
   if (!h || !rhs || !d) return fail(CNL_ERR_ARG, "null argument");
   CNL_NEED_F32(h);
+  CNL_NEED_FULL_BATCH(h);
   return solve_impl(h, rhs, d);
 }
 
@@ -817,6 +825,7 @@ int cnl_newton_system(cnl_handle* h, double* vals, const double* rhs, double* d,
                       double* rho, double* rho_old_out, int32_t* nfact, int32_t* success) {
   if (!h || !vals || !rhs || !d || !params || !rho || !rho_old_out || !nfact || !success) return fail(CNL_ERR_ARG, "null argument");
   CNL_NEED_F64(h);
+  CNL_NEED_FULL_BATCH(h);
   if (h->layout) return fail(CNL_ERR_STATE, kHostLayout);
   HIPCHK(hipSetDevice(h->device));
   if (int rc = ensure_staging(h)) return rc;
@@ -844,6 +853,7 @@ int cnl_newton_system_f32(cnl_handle* h, float* vals, const float* rhs, float* d
                           float* rho_old_out, int32_t* nfact, int32_t* success) {
   if (!h || !vals || !rhs || !d || !params || !rho || !rho_old_out || !nfact || !success) return fail(CNL_ERR_ARG, "null argument");
   CNL_NEED_F32(h);
+  CNL_NEED_FULL_BATCH(h);
   if (h->layout) return fail(CNL_ERR_STATE, kHostLayout);
   HIPCHK(hipSetDevice(h->device));
   if (int rc = ensure_staging(h)) return rc;

@@ -282,8 +282,8 @@ int convert_layout(cnl_handle* h, int which, const T* src, T* dst, int to_interl
   if (int rc = layout_rowlen(h, which, &len)) return rc;
   HIPCHK(hipSetDevice(h->device));
   hipError_t e;
-  if constexpr (sizeof(T) == 4) e = cnl::launch_interleave_f32(src, dst, (int)h->batch, len, to_interleaved, (hipStream_t)stream);
-  else e = cnl::launch_interleave(src, dst, (int)h->batch, len, to_interleaved, (hipStream_t)stream);
+  if constexpr (sizeof(T) == 4) e = cnl::launch_interleave_f32(src, dst, (int)h->batch, (int)h->full_batch, len, to_interleaved, (hipStream_t)stream);
+  else e = cnl::launch_interleave(src, dst, (int)h->batch, (int)h->full_batch, len, to_interleaved, (hipStream_t)stream);
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("interleave: ") + hipGetErrorString(e));
   return CNL_OK;
 }
@@ -416,7 +416,7 @@ int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, co
   const int64_t N = plan->N, nnz = plan->nnz, nvar = plan->nvar, nequ = plan->nequ, ncon = plan->ncon;
   int rc = CNL_OK;
   cnl_handle* h = new cnl_handle();
-  h->plan = plan; h->device = device; h->batch = batch;
+  h->plan = plan; h->device = device; h->batch = h->full_batch = batch;
   auto bail = [&](int code) { cnl_destroy(h); return code; };
   if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
   const cnl::Plan& P = plan->P;
@@ -571,7 +571,7 @@ namespace {
 
 int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device) {
   cnl_handle* h = new cnl_handle();
-  h->plan = plan; h->device = device; h->batch = batch; h->f32 = true;
+  h->plan = plan; h->device = device; h->batch = h->full_batch = batch; h->f32 = true;
   auto bail = [&](int code) { cnl_destroy(h); return code; };
   if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
   int rc = CNL_OK;
@@ -683,7 +683,7 @@ int cnl_layout_len(const cnl_handle* h, int which, int64_t* doubles) {
   if (!h || !doubles) return fail(CNL_ERR_ARG, "null argument");
   int64_t len = 0;
   if (int rc = layout_rowlen(h, which, &len)) return rc;
-  *doubles = cnl::band_il_len(h->batch, len);
+  *doubles = cnl::band_il_len(h->full_batch, len);   // (of the created batch, whatever cnl_set_active_batch says)
   return CNL_OK;
 }
 int cnl_interleave_dev(cnl_handle* h, int which, const double* d_src, double* d_dst, void* stream) {
@@ -701,6 +701,33 @@ int cnl_interleave_f32_dev(cnl_handle* h, int which, const float* d_src, float* 
 int cnl_deinterleave_f32_dev(cnl_handle* h, int which, const float* d_src, float* d_dst, void* stream) {
   CNL_NEED_F32(h);
   return convert_layout(h, which, d_src, d_dst, 0, stream);
+}
+
+// The handle works on its first nb problems from here on: every device-pointer entry point launches over nb problems instead of the
+// created batch, on the same arrays (every kernel of the path is per problem and guards its problem index against the batch it is
+// given, and every per-problem array of the handle is addressed from problem 0: a prefix needs no other address).  Served where a
+// call is one classic launch — the band kernels, the register-front or the general kernel with their condensation passes; executions
+// that cut the batch themselves (staged / dataflow counters sized by the batch, split batches, the dense backend's tiles) refuse.
+int cnl_set_active_batch(cnl_handle* h, int64_t nb) {
+  if (!h) return fail(CNL_ERR_ARG, "null handle");
+  if (nb < 1 || nb > h->full_batch)
+    return fail(CNL_ERR_ARG, "cnl_set_active_batch: nb = " + std::to_string(nb) + " is outside [1, " + std::to_string(h->full_batch) + "] (the created batch)");
+  if (nb == h->batch) return CNL_OK;
+  if (!h->band) {
+    if (h->dense || h->gdense) return fail(CNL_ERR_STATE, "cnl_set_active_batch: this handle runs on the dense backend, which is sized by the created batch");
+    if (h->tail || h->split_halves || h->split_staged > 0)
+      return fail(CNL_ERR_STATE, "cnl_set_active_batch: this handle runs its batch split (tail handle, halves or concurrent parts)");
+    if (h->staged || h->d_dep)
+      return fail(CNL_ERR_STATE, "cnl_set_active_batch: this handle runs staged / dataflow (task counters sized by the created batch)");
+  }
+  h->batch = nb;
+  return CNL_OK;
+}
+
+int cnl_get_active_batch(const cnl_handle* h, int64_t* nb) {
+  if (!h || !nb) return fail(CNL_ERR_ARG, "null argument");
+  *nb = h->batch;
+  return CNL_OK;
 }
 
 int cnl_set_timing(cnl_handle* h, int enable) {
@@ -724,7 +751,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
     return CNL_OK;
   }
   cfg[0] = h->cfg.tpp; cfg[1] = h->cfg.ppb; cfg[2] = (int64_t)h->cfg.lds_bytes; cfg[3] = h->cfg.lds_work;
-  cfg[4] = (h->batch + h->cfg.ppb - 1) / h->cfg.ppb;
+  cfg[4] = (h->full_batch + h->cfg.ppb - 1) / h->cfg.ppb;
   cfg[5] = (h->dense || h->gdense) ? 3 : (h->use_v2 ? (h->staged ? 4 : 2) : 1);
   if (h->lean && !h->dense && !h->gdense) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->tail) cfg[5] |= 32;                             // the remainder of the batch runs on a handle of its own (split_tail)

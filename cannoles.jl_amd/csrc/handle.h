@@ -55,7 +55,9 @@ struct cnl_plan {
 struct cnl_handle {
   cnl_plan* plan = nullptr;
   int device = 0;
-  int64_t batch = 1;
+  int64_t batch = 1;        // problems a call works on: the created batch, or fewer behind cnl_set_active_batch (the first `batch` problems)
+  int64_t full_batch = 1;   // the batch the handle was created with: what every allocation, array address and cnl_layout_len are sized by
+  int64_t factor_batch = 0; // problems the last factorisation covered (cnl_solve_dev must not be asked for more)
   std::vector<void*> dev_allocs;
   cnl::DevPlan dp{};
   cnl::KernelConfig cfg{};
@@ -180,6 +182,14 @@ inline int need_f32(const cnl_handle* h, const char* fn) {
   if (h && !h->f32) return fail(CNL_ERR_STATE, std::string(fn) + ": this is a Float64 handle; the _f32 entry points need one made by cnl_create_f32");
   return CNL_OK;
 }
+// host-pointer entry points take the arrays of the created batch: refused while cnl_set_active_batch holds the handle below it
+inline int need_full_batch(const cnl_handle* h, const char* fn) {
+  if (h && h->batch < h->full_batch)
+    return fail(CNL_ERR_STATE, std::string(fn) + ": the handle works on its first " + std::to_string(h->batch) + " of " + std::to_string(h->full_batch) +
+                                   " problems (cnl_set_active_batch); host-pointer calls need the whole batch");
+  return CNL_OK;
+}
+#define CNL_NEED_FULL_BATCH(h) do { if (int rc_ = need_full_batch((h), __func__)) return rc_; } while (0)
 #define CNL_NEED_F64(h) do { if (int rc_ = need_f64((h), __func__)) return rc_; } while (0)
 #define CNL_NEED_F32(h) do { if (int rc_ = need_f32((h), __func__)) return rc_; } while (0)
 

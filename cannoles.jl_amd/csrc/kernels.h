@@ -199,8 +199,8 @@ hipError_t launch_cond_inertia(const DevCond& C, const double* vals, int* extra_
 hipError_t launch_prepare(int nnzhF, int nnzhc, int nnzjF, int nnzjc, int nvar, int nequ, int ncon, const double* hF, const double* hc,
                           const double* Jx, const double* Jcx, const double* delta, double* vals, int batch, int interleaved, hipStream_t stream);
 // problem-major <-> interleaved over groups of 32 problems (band.h: band_il_index); rows of `len` doubles
-hipError_t launch_interleave(const double* src, double* dst, int batch, long long len, int to_interleaved, hipStream_t stream);
-hipError_t launch_interleave_f32(const float* src, float* dst, int batch, long long len, int to_interleaved, hipStream_t stream);
+hipError_t launch_interleave(const double* src, double* dst, int batch, int full_batch, long long len, int to_interleaved, hipStream_t stream);
+hipError_t launch_interleave_f32(const float* src, float* dst, int batch, int full_batch, long long len, int to_interleaved, hipStream_t stream);
 hipError_t launch_cgls(const DevJt& J, const JacSrc& S, const double* r, double* lambda, double* Jxtr, double* ws, int32_t* iters,
                        double atol, double rtol, int itmax, int ones_if_zero, int batch, hipStream_t stream);
 hipError_t launch_residual_vectors(const DevJt& J, const JacSrc& S, const double* r, const double* lambda, const double* Fx,

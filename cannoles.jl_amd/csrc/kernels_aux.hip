@@ -745,8 +745,8 @@ __device__ __forceinline__ long long il_tile_dst(long long g, long long nb, int 
 }
 // (T = float for Float32 handles: the same blocks of eight elements)
 template <class T>
-__global__ void __launch_bounds__(256) interleave_kernel(const T* __restrict__ src, T* __restrict__ dst, int batch, long long len,
-                                                         int to_interleaved) {
+__global__ void __launch_bounds__(256) interleave_kernel(const T* __restrict__ src, T* __restrict__ dst, int batch, int full_batch,
+                                                         long long len, int to_interleaved) {
   __shared__ T tile[BAND_IL_GROUP * IL_PITCH];
   const long long g = blockIdx.y, nb = band_il_blocks(len);
   const int chunk = blockIdx.x, t = threadIdx.x;
@@ -765,7 +765,9 @@ __global__ void __launch_bounds__(256) interleave_kernel(const T* __restrict__ s
     for (int i = 0; i < BAND_IL_GROUP * IL_TILE / 256; i++) {
       int p, kk;
       const long long o = il_tile_dst(g, nb, chunk, i * 256 + t, p, kk);
-      if ((long long)chunk * (IL_TILE / 8) + kk / 8 < nb) __builtin_nontemporal_store(tile[p * IL_PITCH + kk], dst + o);   // (pads and the spare block: zeros)
+      // (pads and the spare block: zeros; the problems [batch, full_batch) of a handle that works on a prefix of its batch keep theirs)
+      const long long prob = g * BAND_IL_GROUP + p;
+      if ((long long)chunk * (IL_TILE / 8) + kk / 8 < nb && (prob < batch || prob >= full_batch)) __builtin_nontemporal_store(tile[p * IL_PITCH + kk], dst + o);
     }
   } else {
     for (int i = 0; i < BAND_IL_GROUP * IL_TILE / 256; i++) {
@@ -783,17 +785,17 @@ __global__ void __launch_bounds__(256) interleave_kernel(const T* __restrict__ s
 }
 
 template <class T>
-static hipError_t launch_interleave_t(const T* src, T* dst, int batch, long long len, int to_interleaved, hipStream_t stream) {
+static hipError_t launch_interleave_t(const T* src, T* dst, int batch, int full_batch, long long len, int to_interleaved, hipStream_t stream) {
   const long long groups = (batch + BAND_IL_GROUP - 1) / BAND_IL_GROUP, chunks = (band_il_blocks(len) * 8 + IL_TILE - 1) / IL_TILE;
   if (batch <= 0 || len <= 0 || groups > 65535 || chunks > 0x7fffffffLL) return hipErrorInvalidConfiguration;
-  hipLaunchKernelGGL(interleave_kernel<T>, dim3((unsigned)chunks, (unsigned)groups), dim3(256), 0, stream, src, dst, batch, len, to_interleaved);
+  hipLaunchKernelGGL(interleave_kernel<T>, dim3((unsigned)chunks, (unsigned)groups), dim3(256), 0, stream, src, dst, batch, full_batch, len, to_interleaved);
   return hipGetLastError();
 }
-hipError_t launch_interleave(const double* src, double* dst, int batch, long long len, int to_interleaved, hipStream_t stream) {
-  return launch_interleave_t(src, dst, batch, len, to_interleaved, stream);
+hipError_t launch_interleave(const double* src, double* dst, int batch, int full_batch, long long len, int to_interleaved, hipStream_t stream) {
+  return launch_interleave_t(src, dst, batch, full_batch, len, to_interleaved, stream);
 }
-hipError_t launch_interleave_f32(const float* src, float* dst, int batch, long long len, int to_interleaved, hipStream_t stream) {
-  return launch_interleave_t(src, dst, batch, len, to_interleaved, stream);
+hipError_t launch_interleave_f32(const float* src, float* dst, int batch, int full_batch, long long len, int to_interleaved, hipStream_t stream) {
+  return launch_interleave_t(src, dst, batch, full_batch, len, to_interleaved, stream);
 }
 
 // prepare_newton_system! writing `vals` interleaved (the values and the "left alone" rules of prepare_kernel above, the tiles of

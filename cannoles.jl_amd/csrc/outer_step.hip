@@ -8,6 +8,8 @@
 //   cnl_outer_newton_done_dev  takes the Newton system's results (:633-652: d, rho_old, counters, `broken`), extrapolation eps (:659)
 //   cnl_outer_trial_done_dev   acceptance test at the trial point and the state update (:733-763), end-of-inner-loop tests (:765-800)
 //   cnl_outer_end_dev          statuses, outer-iteration counters (:800-857)
+//   cnl_outer_compact_dev      (no counterpart in the reference) the active problems to the front of every per-problem array, so that
+//                              the next steps run on them alone
 // The arithmetic of every test is the reference's, in its operation order; minimum / maximum propagate NaN as the framework's
 // (and Julia's) do.  The model callbacks, the line search and the rare small-residual branch stay with the caller.
 //
@@ -23,6 +25,7 @@
 //     independent of the summation order, which the comparison with the framework form of the loop relies on.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 
@@ -310,6 +313,99 @@ __global__ void __launch_bounds__(256) outer_end_kernel(const ST S) {
   S.phase0[b] = 1;
 }
 
+// ---- compaction of the loop's state: the active problems become the first rows (cnl_outer_compact_dev) -----------------------------
+// A problem that has finished (status != 0) is still a row of every [B, ...] array, and every kernel of a global step still runs over
+// it.  With A = the number of active rows below Bc = S.B: the k-th finished row below A (ascending) and the k-th active row at or above
+// A (ascending) change places, in every per-problem array — afterwards rows 0 .. A-1 are exactly the active problems and the caller
+// goes on with B = A.  Both sets have the same size, sources and destinations are disjoint, so the swap is in place and all B rows
+// stay a permutation of what they were (the caller's d_orig row says which problem a row holds).
+// Two launches back to back on the stream: one workgroup counts, scans and writes the pair list; the swap kernel reads the pair count
+// from the device (the host never learns it) and strides over the pairs.
+constexpr int COMPACT_MAX_ARRAYS = 112, COMPACT_MAX_EXTRA = 24, CP_THREADS = 1024, CP_MAX_GRID = 2048;
+struct CompactArrays {
+  int n, nsmall;                       // arrays; the first nsmall have rows of at most 16 bytes (one thread moves a row)
+  unsigned bytes[COMPACT_MAX_ARRAYS];  // row bytes
+  char* base[COMPACT_MAX_ARRAYS];
+};
+
+// counts = {A, Bc after the call}; work = [pair count, -, (finished row, active row) x pairs]
+__global__ void __launch_bounds__(CP_THREADS) compact_pair_kernel(const int32_t* __restrict__ status, int Bc, long long min_finished,
+                                                                  int32_t* __restrict__ counts, int32_t* __restrict__ work) {
+  __shared__ int wsum[CP_THREADS / 64];
+  __shared__ int below_A;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int per = (Bc + CP_THREADS - 1) / CP_THREADS;
+  const int b0 = min((long long)t * per, (long long)Bc), b1 = min((long long)b0 + per, (long long)Bc);
+  int c = 0;
+  for (int b = b0; b < b1; b++) c += status[b] == 0;
+  int v = c;   // inclusive scan over the wavefront, then over the wavefronts' totals
+  for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(v, o, 64); if (lane >= o) v += u; }
+  if (lane == 63) wsum[wave] = v;
+  __syncthreads();
+  int before = v - c, A = 0;   // active rows below b0; active rows in all
+  for (int w = 0; w < CP_THREADS / 64; w++) { if (w < wave) before += wsum[w]; A += wsum[w]; }
+  if ((long long)Bc - A < min_finished) {   // not worth a pass yet: nothing moves
+    if (t == 0) { counts[0] = A; counts[1] = Bc; work[0] = 0; }
+    return;
+  }
+  // (min_finished >= 1: A < Bc, so one thread's range holds row A)
+  if (b0 <= A && A < b1) {
+    int q = before;
+    for (int b = b0; b < A; b++) q += status[b] == 0;
+    below_A = q;
+  }
+  __syncthreads();
+  const int act_below = below_A;   // active rows below A; A - act_below finished rows there = active rows at or above A = pairs
+  if (t == 0) { counts[0] = A; counts[1] = A; work[0] = A - act_below; }
+  int q = before;
+  for (int b = b0; b < b1; b++) {
+    const bool active = status[b] == 0;
+    if (!active && b < A) work[2 + 2 * (b - q)] = b;                  // finished rows before b: b - q, all of them below A
+    if (active && b >= A) work[2 + 2 * (q - act_below) + 1] = b;
+    q += active;
+  }
+}
+
+template <class V>
+__device__ __forceinline__ void swap_vectors(char* a, char* b, unsigned nv, unsigned first, unsigned step) {
+  V* pa = reinterpret_cast<V*>(a);
+  V* pb = reinterpret_cast<V*>(b);
+  for (unsigned i = first; i < nv; i += step) { const V x = pa[i], y = pb[i]; pa[i] = y; pb[i] = x; }
+}
+// Two rows of nb bytes change places, moved by threads first, first + step, ...: the widest vector both addresses allow (rows are
+// element-aligned only: 16-byte vectors where both rows happen to start on 16 bytes, else 8, 4, 2, 1), the rest of a row that is
+// no multiple of that width in ever narrower pieces.
+__device__ __forceinline__ void swap_rows(char* a, char* b, unsigned nb, unsigned first, unsigned step) {
+  const unsigned m = (unsigned)(reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u;
+  const unsigned w = m == 0 ? 16 : (m & 7) == 0 ? 8 : (m & 3) == 0 ? 4 : (m & 1) == 0 ? 2 : 1;
+  const unsigned nv = nb / w;
+  switch (w) {
+    case 16: swap_vectors<uint4>(a, b, nv, first, step); break;
+    case 8: swap_vectors<uint2>(a, b, nv, first, step); break;
+    case 4: swap_vectors<uint32_t>(a, b, nv, first, step); break;
+    case 2: swap_vectors<uint16_t>(a, b, nv, first, step); break;
+    default: swap_vectors<uint8_t>(a, b, nv, first, step); break;
+  }
+  unsigned off = nv * w, rem = nb - off;   // rem < w; off is a multiple of w: each piece below is aligned to its own width
+  if (rem && first == 0) {
+    if (rem & 8) { swap_vectors<uint2>(a + off, b + off, 1, 0, 1); off += 8; }
+    if (rem & 4) { swap_vectors<uint32_t>(a + off, b + off, 1, 0, 1); off += 4; }
+    if (rem & 2) { swap_vectors<uint16_t>(a + off, b + off, 1, 0, 1); off += 2; }
+    if (rem & 1) swap_vectors<uint8_t>(a + off, b + off, 1, 0, 1);
+  }
+}
+
+// one workgroup per pair (grid-stride: the grid is sized for the worst case the host knows, min(Bc / 2, CP_MAX_GRID), and a workgroup
+// without a pair leaves at once): the short rows one thread each, the long rows by the whole workgroup
+__global__ void __launch_bounds__(256) compact_swap_kernel(const CompactArrays L, const int32_t* __restrict__ work) {
+  const int npairs = work[0], t = threadIdx.x;
+  for (int k = blockIdx.x; k < npairs; k += gridDim.x) {
+    const long long ra = work[2 + 2 * k], rb = work[2 + 2 * k + 1];
+    for (int i = t; i < L.nsmall; i += 256) swap_rows(L.base[i] + ra * L.bytes[i], L.base[i] + rb * L.bytes[i], L.bytes[i], 0, 1);
+    for (int i = L.nsmall; i < L.n; i++) swap_rows(L.base[i] + ra * L.bytes[i], L.base[i] + rb * L.bytes[i], L.bytes[i], t, 256);
+  }
+}
+
 // every array of the state the kernels dereference must be there (the header promises CNL_ERR_ARG for a missing array, not an
 // asynchronous fault).  The members are named one by one (walking the struct as an array of pointers would read a scalar
 // member added later as a pointer).  The multiplier / constraint arrays (lam, cx, ct, lamt, lamt_e, cl, lam_ls) have rows of
@@ -390,6 +486,59 @@ template <class ST> int end_impl(const ST* st, void* stream) {
   return done();
 }
 
+// cnl_outer_compact_dev: the per-problem arrays of the state (every element, counter and mask member; `flags` is global), the caller's
+// extra arrays and d_orig, each once (the loop hands one array over as Jcv and Jct: a row that is swapped twice is back where it was),
+// the short rows in front
+template <class ST> int compact_impl(const ST* st, int64_t nextra, void* const* extra, const int64_t* extra_row_bytes, int64_t min_finished,
+                                     int32_t* d_orig, int32_t* d_counts, int32_t* d_work, void* stream) {
+  using T = elem_t<ST>;
+  if (check(st) || st->B > 0x7fffffffLL) return CNL_ERR_ARG;
+  if (nextra < 0 || nextra > COMPACT_MAX_EXTRA || (nextra > 0 && (!extra || !extra_row_bytes))) return CNL_ERR_ARG;
+  if (min_finished < 1 || !d_orig || !d_counts || !d_work) return CNL_ERR_ARG;
+  for (int64_t i = 0; i < nextra; i++)
+    if (!extra[i] || extra_row_bytes[i] <= 0 || extra_row_bytes[i] > 0x7fffffffLL) return CNL_ERR_ARG;
+  struct Entry { char* p; int64_t bytes; };
+  Entry all[COMPACT_MAX_ARRAYS];
+  int n = 0;
+  auto add = [&](const void* p, int64_t bytes) {
+    if (!p || bytes <= 0) return;   // (an optional array that is not there, a row of no entries)
+    for (int i = 0; i < n; i++) if (all[i].p == p) return;
+    all[n++] = Entry{static_cast<char*>(const_cast<void*>(p)), bytes};
+  };
+  const int64_t e = sizeof(T);
+#define CNL_ROW(m, bytes) add(st->m, (bytes));
+  CNL_ROW(status, 4) CNL_ROW(it, 4) CNL_ROW(nf_new, 4) CNL_ROW(ok_new, 4)
+  CNL_ROW(inner, 8) CNL_ROW(nfact, 8) CNL_ROW(nlin, 8) CNL_ROW(nbk, 8)
+  CNL_ROW(phase0, 1) CNL_ROW(act, 1) CNL_ROW(need, 1) CNL_ROW(brk, 1) CNL_ROW(ext, 1) CNL_ROW(lsm, 1) CNL_ROW(rej, 1) CNL_ROW(chk, 1)
+  CNL_ROW(done_in, 1) CNL_ROW(tired, 1) CNL_ROW(small_res, 1) CNL_ROW(bt, 1)
+  CNL_ROW(normdual, e) CNL_ROW(normprimal, e) CNL_ROW(combined, e) CNL_ROW(combined_hat, e) CNL_ROW(delta, e) CNL_ROW(ndh, e) CNL_ROW(nph, e)
+  CNL_ROW(fx, e) CNL_ROW(epsk, e) CNL_ROW(epstol, e) CNL_ROW(epsF, e) CNL_ROW(epsc, e) CNL_ROW(rho_old, e) CNL_ROW(ro_tmp, e) CNL_ROW(rho_new, e)
+  CNL_ROW(alpha, e) CNL_ROW(Dphi, e) CNL_ROW(phix, e) CNL_ROW(eta, e) CNL_ROW(nrm_t, 2 * e)
+  CNL_ROW(d, e * st->N) CNL_ROW(d_new, e * st->N) CNL_ROW(rhs_cur, e * st->N) CNL_ROW(rhs_t, e * st->N) CNL_ROW(ls_g, e * st->N)
+  CNL_ROW(x, e * st->n) CNL_ROW(xt, e * st->n) CNL_ROW(xt_e, e * st->n) CNL_ROW(xl, e * st->n)
+  CNL_ROW(r, e * st->m) CNL_ROW(Fx, e * st->m) CNL_ROW(rt, e * st->m) CNL_ROW(Ft, e * st->m) CNL_ROW(rt_e, e * st->m) CNL_ROW(Fl, e * st->m)
+  CNL_ROW(cx, e * st->P) CNL_ROW(lam, e * st->P) CNL_ROW(ct, e * st->P) CNL_ROW(lamt, e * st->P) CNL_ROW(lamt_e, e * st->P) CNL_ROW(cl, e * st->P)
+  CNL_ROW(lam_ls, e * st->P)
+  CNL_ROW(Jv, e * st->nnzjF) CNL_ROW(Jt, e * st->nnzjF) CNL_ROW(Jcv, e * st->nnzjc) CNL_ROW(Jct, e * st->nnzjc)
+#undef CNL_ROW
+  static_assert(COMPACT_MAX_ARRAYS >= 72 + COMPACT_MAX_EXTRA + 1, "room for every member, the extra arrays and d_orig");
+  for (int64_t i = 0; i < nextra; i++) add(extra[i], extra_row_bytes[i]);
+  add(d_orig, 4);
+  for (int i = 0; i < n; i++) if (all[i].bytes > 0x7fffffffLL) return CNL_ERR_ARG;
+  CompactArrays L{};
+  for (int pass = 0; pass < 2; pass++) {
+    for (int i = 0; i < n; i++)
+      if ((all[i].bytes <= 16) == (pass == 0)) { L.base[L.n] = all[i].p; L.bytes[L.n] = (unsigned)all[i].bytes; L.n++; }
+    if (pass == 0) L.nsmall = L.n;
+  }
+  hipLaunchKernelGGL(compact_pair_kernel, dim3(1), dim3(CP_THREADS), 0, (hipStream_t)stream, st->status, (int)st->B, (long long)min_finished,
+                     d_counts, d_work);
+  if (hipGetLastError() != hipSuccess) return CNL_ERR_HIP;
+  const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>(st->B / 2, 1), CP_MAX_GRID);
+  hipLaunchKernelGGL(compact_swap_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, L, d_work);
+  return done();
+}
+
 }  // namespace
 
 extern "C" {
@@ -404,6 +553,11 @@ int cnl_outer_ls_step_dev(const cnl_outer_state* st, void* stream) { return ls_s
 int cnl_outer_ls_take_dev(const cnl_outer_state* st, void* stream) { return ls_take_impl(st, stream); }
 int cnl_outer_end_dev(const cnl_outer_state* st, void* stream) { return end_impl(st, stream); }
 
+int cnl_outer_compact_dev(const cnl_outer_state* st, int64_t nextra, void* const* d_extra, const int64_t* extra_row_bytes, int64_t min_finished,
+                          int32_t* d_orig, int32_t* d_counts, int32_t* d_work, void* stream) {
+  return compact_impl(st, nextra, d_extra, extra_row_bytes, min_finished, d_orig, d_counts, d_work, stream);
+}
+
 int cnl_outer_begin_f32_dev(const cnl_outer_state_f32* st, void* stream) { return begin_impl(st, stream); }
 int cnl_outer_newton_done_f32_dev(const cnl_outer_state_f32* st, int did_newton, void* stream) { return newton_done_impl(st, did_newton, stream); }
 int cnl_outer_extrapolated_f32_dev(const cnl_outer_state_f32* st, void* stream) { return extrapolated_impl(st, stream); }
@@ -413,5 +567,10 @@ int cnl_outer_ls_test_f32_dev(const cnl_outer_state_f32* st, int first, void* st
 int cnl_outer_ls_step_f32_dev(const cnl_outer_state_f32* st, void* stream) { return ls_step_impl(st, stream); }
 int cnl_outer_ls_take_f32_dev(const cnl_outer_state_f32* st, void* stream) { return ls_take_impl(st, stream); }
 int cnl_outer_end_f32_dev(const cnl_outer_state_f32* st, void* stream) { return end_impl(st, stream); }
+
+int cnl_outer_compact_f32_dev(const cnl_outer_state_f32* st, int64_t nextra, void* const* d_extra, const int64_t* extra_row_bytes,
+                              int64_t min_finished, int32_t* d_orig, int32_t* d_counts, int32_t* d_work, void* stream) {
+  return compact_impl(st, nextra, d_extra, extra_row_bytes, min_finished, d_orig, d_counts, d_work, stream);
+}
 
 }  // extern "C"

@@ -80,6 +80,24 @@ class BandQuadFamily:
         sub.d = {k: v[idx_t].contiguous() for k, v in self.d.items()}
         return sub
 
+    def per_problem_tensors(self):
+        """the device tensors that hold one row per problem (the model's data), by name: what a caller that reorders the problems of a
+        batch has to reorder with them (solve_batch_device(compact=True) hands them to cnl_outer_compact_dev)"""
+        return dict(self.d)
+
+    def head(self, nb):
+        """the family of the first nb problems as VIEWS of this family's data (nothing is copied; `take` copies): the structure is
+        shared, every callback works on [nb, ...] arrays"""
+        nb = int(nb)
+        if not 1 <= nb <= self.B:
+            raise ValueError(f"head({nb}) of a family of {self.B} problems")
+        sub = object.__new__(type(self))
+        sub.__dict__.update(self.__dict__)
+        sub.B = nb
+        sub.h = {k: v[:nb] for k, v in self.h.items()}
+        sub.d = {k: v[:nb] for k, v in self.d.items()}
+        return sub
+
     @staticmethod
     def _row_lists(rows, nrows, pad):
         cnt = np.bincount(rows, minlength=nrows) if len(rows) else np.zeros(nrows, int)
@@ -205,9 +223,19 @@ PROFILE = False   # tools/time_device_loop.py --profile: wall time per section o
 
 
 def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=None, rtol=None, Fatol=None, Frtol=None, delta_dec=0.1,
-                       device_index=0, layout="auto", tuning=None, dtype=None):
+                       device_index=0, layout="auto", tuning=None, dtype=None, compact=False, compact_min_finished=None):
     """All B problems of `fam` in lockstep on the device.  Returns a dict of numpy arrays: solution [B, n], multipliers,
     status (list of strings), iter, nfact, nlinsolve, nbk, objective, and `steps` (global steps = batched Newton rounds).
+
+    compact=True: a global step runs on the ACTIVE problems only.  Behind every step cnl_outer_compact_dev moves the active problems to
+    the front of every per-problem array (the state, a working copy of the family's data, the row -> problem map), once at least
+    `compact_min_finished` problems have finished since the last pass (default max(32, working batch // 8): a policy knob, no result
+    depends on it); the loop goes on with that prefix — the state's B, the handle (cnl_set_active_batch; a handle that cannot, e.g. a
+    staged one, stays at the full batch and works on finished rows as before) and every framework expression on prefix views.  The
+    counts come back with the next step's branch flags: no further host synchronisation.  Every problem takes the decisions it takes
+    without compaction, the outputs are in the original problem order and `fam` is not touched.  The result then also holds
+    `compactions`, `problem_steps` (the sum of the working batch over the global steps; steps * B without compaction) and
+    `handle_shrunk`.
 
     Round 4: the masks and the masked state updates of a global step are FOUR device kernels working in place on the state
     (cnl_outer_begin_dev / _newton_done_dev / _trial_done_dev / _end_dev, csrc/outer_step.hip) instead of ~150 framework launches;
@@ -270,8 +298,23 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
 
     vals_cur = new_vals()   # (ONE vals array: only newton_system reads it; the trial point's products read Jt)
     hc0 = Z(B, max(nnzhc, 1))
+    # compaction (compact=True): nb = the working batch, the first nb rows of every array; hd(a) = those rows of a; wf = the family
+    # whose data rows follow the state's (a working copy: `fam` stays as it is), fw = its first nb problems.  Without compaction nb = B,
+    # hd(a) is all of a and fw is fam.  `vals_cur` needs no reordering: prepare rewrites every problem's values in front of each use
+    # (the -I segment is the same for all).
+    nb = B
+    hd = lambda a: a[:nb]
+    wf = fw = fam
+    L_nb = B             # the handle's active batch
+    hF_full = None
 
     def prepare(vals, hF, Jv_, Jcv_, delta_):
+        nonlocal hF_full
+        if hF is not None and hF.shape[0] < L_nb:   # a handle that could not shrink reads a Hessian row for every problem it was created with
+            if hF_full is None:
+                hF_full = Z(B, hF.shape[1])
+            hF_full[:hF.shape[0]].copy_(hF)
+            hF = hF_full
         hipldl.prepare_newton_system_dev(L, nnzhF, nnzhc, nnzjF, nnzjc, ptr(hF) if hF is not None else 0, ptr(hc0) if p else 0, ptr(Jv_),
                                          ptr(Jcv_) if p else 0, ptr(delta_) if p else 0, ptr(vals), st)
 
@@ -299,7 +342,8 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     fx = (0.5 * rdot(Fx, Fx)).contiguous()
     Jv = fam.jac_vals(x).contiguous()
     Jcv = fam.jacc_vals(x)          # the family's constraints are linear: one array serves the current and the trial point
-    Jcv = Jcv.contiguous() if p else Z(B, 1)
+    # (the family hands out its own array; with compaction the state's rows change places, so the state gets a copy)
+    Jcv = (Jcv.clone() if compact else Jcv.contiguous()) if p else Z(B, 1)
     cx = fam.cons(x).contiguous()
     r = Fx.clone()
     delta = t.ones(B, **f64)
@@ -314,15 +358,18 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     rv_rhs, rv_nrm = Z(B, N), Z(B, 2)
 
     def small_res_check(mask):
-        """src/CaNNOLeS.jl:873-897 for the problems of `mask`: r = F, least-squares multipliers, dual, primal = [0; c] (in place)"""
-        r2 = W(mask, Fx, r)
+        """src/CaNNOLeS.jl:873-897 for the problems of `mask`: r = F, least-squares multipliers, dual, primal = [0; c] (in place; the
+        working rows only — the handle's passes take whole arrays, whose other rows are not used)"""
+        mask = hd(mask)
+        r2 = r.clone()
+        hd(r2).copy_(W(mask, hd(Fx), hd(r)))
         lam2 = multipliers(Jv, Jcv, r2, False)
-        lam.copy_(W(mask, lam2, lam))
+        hd(lam).copy_(W(mask, hd(lam2), hd(lam)))
         resid_vectors(Jv, Jcv, r2, lam, r2, cx, rv_rhs, rv_nrm)   # F - r = 0 for the masked problems
-        rhs_cur.copy_(W(mask, rv_rhs, rhs_cur))
-        normdual.copy_(W(mask, rv_nrm[:, 0], normdual))
-        normprimal.copy_(W(mask, ninf(cx[:, :p]) if p else Z(B), normprimal))
-        r.copy_(r2)
+        hd(rhs_cur).copy_(W(mask, hd(rv_rhs), hd(rhs_cur)))
+        hd(normdual).copy_(W(mask, hd(rv_nrm)[:, 0], hd(normdual)))
+        hd(normprimal).copy_(W(mask, ninf(hd(cx)[:, :p]) if p else Z(nb), hd(normprimal)))
+        hd(r).copy_(hd(r2))
 
     small_residual = (2 * fsqrt(fx) <= epsF) & (cnorm2(cx) <= epsc)
     first_order = t.maximum(normdual / dual_scaling(lam), normprimal) <= epstol
@@ -350,8 +397,10 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     xl, Fl, cl, lam_ls = Z(B, n), Z(B, m), Z(B, P), Z(B, P)
     alpha, Dphi, phix = Z(B), Z(B), Z(B)
     masks = {k: t.zeros(B, dtype=t.bool, device=dev) for k in ("act", "need", "brk", "ext", "lsm", "rej", "chk", "done_in", "tired", "small_res", "bt")}
-    flags = ZI(t.int32, 8)
-    flags_h = t.zeros(8, dtype=t.int32).pin_memory()
+    # the step's flag words and, behind them, the two counts of cnl_outer_compact_dev: one block, one pinned copy per read
+    flags_counts = ZI(t.int32, 10)
+    flags, counts = flags_counts[:8], flags_counts[8:]
+    flags_h = t.zeros(10, dtype=t.int32).pin_memory()
     S = hipldl.cnl_outer_state_f32() if f32 else hipldl.cnl_outer_state()
     for k, v in dict(B=B, n=n, m=m, p=p, P=P, N=N, nnzjF=nnzjF, nnzjc=nnzjc, max_inner=max_inner, dmin=dmin, rhomax=rhomax,
                      delta_dec=delta_dec, smax=smax, gammaA=gammaA, eps2=eps ** 2).items():
@@ -373,7 +422,7 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
                                                        "ls_take"))
 
     def read_flags():
-        flags_h.copy_(flags, non_blocking=True)
+        flags_h.copy_(flags_counts, non_blocking=True)
         t.cuda.current_stream(dev).synchronize()
         return flags_h.tolist()
 
@@ -386,6 +435,18 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
             prof[name] = prof.get(name, 0.0) + (_time.perf_counter() - t0)
         return _time.perf_counter()
 
+    compactions = problem_steps = 0
+    handle_shrunk, can_shrink, pending = False, True, False
+    if compact:
+        if compact_min_finished is not None and int(compact_min_finished) < 1:
+            raise ValueError("compact_min_finished >= 1")
+        wf = fam.head(B)
+        wf.d = {k: v.clone() for k, v in fam.per_problem_tensors().items()}
+        fw = wf
+        extras = [(v.data_ptr(), v.shape[1] * v.element_size()) for v in wf.d.values() if v.shape[1] > 0]
+        assert all(v.is_contiguous() and v.shape[0] == B for v in wf.d.values())
+        orig = t.arange(B, dtype=t.int32, device=dev)
+        pair_work = ZI(t.int32, B + 2)
     t.cuda.synchronize(dev)
     t_loop0 = _time.perf_counter()
     steps = 0
@@ -393,16 +454,32 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     # cnl_outer_trial_done_dev, and one per round of backtracking when a line search runs
     while steps < max_steps:
         tk = _time.perf_counter()
-        chk_(k_begin(Sref, st))
-        any_act, any_need, any_ext, any_ls = read_flags()[:4]
+        chk_(k_begin(Sref, st))   # (behind a compaction still over the rows of the step before: the ones that left are finished)
+        fl = read_flags()
+        any_act, any_need, any_ext, any_ls = fl[:4]
         if not any_act:
             break
+        moved, pending = pending and fl[9] < nb, False
+        if moved:   # the active problems are the first fl[8] = fl[9] rows now
+            nb = int(fl[9])
+            compactions += 1
+            S.B = nb
+            fw = wf.head(nb)
+            if can_shrink:
+                try:
+                    hipldl.set_active_batch(L, nb)
+                    L_nb, handle_shrunk = nb, True
+                except hipldl.CnlError as err:
+                    if err.code != 5:   # CNL_ERR_STATE: this handle cannot work on a prefix (staged, split, dense) — it keeps its batch
+                        raise
+                    can_shrink = False
         steps += 1
+        problem_steps += nb
         tk = tick("begin", tk)
         # ---- Newton step (skipped on the iteration right after a rejected extrapolation), :627-652
         if any_need:
-            prepare(vals_cur, fam.hess_vals(x, r), Jv, Jcv, delta)
-            ro_tmp.copy_(rho_old)
+            prepare(vals_cur, fw.hess_vals(hd(x), hd(r)), Jv, Jcv, delta)
+            hd(ro_tmp).copy_(hd(rho_old))
             hipldl.newton_system_dev(L, ptr(vals_cur), ptr(rhs_cur), ptr(d_new), ptr(ro_tmp), ptr(rho_new), ptr(nf_new), ptr(ok_new), params, st)
         chk_(k_newton_done(Sref, 1 if any_need else 0, st))
         dx = d[:, :n]
@@ -417,20 +494,20 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
         if any_ls:
             resid_vectors(Jv, Jcv, Fx, lam_ls, Fx, cx, rv_rhs, rv_nrm)      # dual part: Jx'Fx - Jc'(lam - c/delta), lam_ls by cnl_outer_newton_done_dev
             chk_(k_ls_begin(Sref, st))
-            Fl.copy_(fam.residual(xl))
-            cl.copy_(fam.cons(xl))
+            hd(Fl).copy_(fw.residual(hd(xl)))
+            hd(cl).copy_(fw.cons(hd(xl)))
             chk_(k_ls_test(Sref, 1, st))
             while read_flags()[6]:
                 chk_(k_ls_step(Sref, st))
-                Fl.copy_(fam.residual(xl))       # (rows of problems that do not backtrack are recomputed from an unchanged xl: same values)
-                cl.copy_(fam.cons(xl))
+                hd(Fl).copy_(fw.residual(hd(xl)))       # (rows of problems that do not backtrack are recomputed from an unchanged xl: same values)
+                hd(cl).copy_(fw.cons(hd(xl)))
                 chk_(k_ls_test(Sref, 0, st))
             chk_(k_ls_take(Sref, st))
         tk = tick("line_search", tk)
-        Ft.copy_(fam.residual(xt))
-        ct.copy_(fam.cons(xt))
+        hd(Ft).copy_(fw.residual(hd(xt)))
+        hd(ct).copy_(fw.cons(hd(xt)))
         # ---- optimality measures at the trial point, :722-732; acceptance and the state update, :733-800
-        Jt.copy_(fam.jac_vals(xt))
+        hd(Jt).copy_(fw.jac_vals(hd(xt)))
         resid_vectors(Jt, Jcv, rt, lamt, Ft, ct, rhs_t, nrm_t)
         tk = tick("trial_eval", tk)
         chk_(k_trial_done(Sref, st))
@@ -438,19 +515,38 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
         tk = tick("trial_done", tk)
         if any_rej:   # dual at (x, r, lam) again; primal keeps the trial's value, as in the reference (:742-747)
             resid_vectors(Jv, Jcv, r, lam, Fx, cx, rv_rhs, rv_nrm)
-            rhs_cur[:, :n] = t.where(masks["rej"][:, None], rv_rhs[:, :n], rhs_cur[:, :n])
+            hd(rhs_cur)[:, :n] = t.where(hd(masks["rej"])[:, None], hd(rv_rhs)[:, :n], hd(rhs_cur)[:, :n])
         if any_chk:
             small_res_check(masks["chk"])
         chk_(k_end(Sref, st))
+        if compact and nb > 1:
+            # the problems that just finished leave the working rows (once enough of them have); the counts come back with the next
+            # step's flags
+            hipldl.outer_compact_dev(S, extras, compact_min_finished if compact_min_finished is not None else max(32, nb // 8), orig, counts,
+                                     pair_work, st)
+            pending = True
         tk = tick("rej_chk_end", tk)
     t.cuda.synchronize(dev)
     loop_seconds = _time.perf_counter() - t_loop0
     names = {UNKNOWN: "unknown", FIRST: "first_order", SMALL: "small_residual", EXC: "exception", TIRED: "max_eval", STALL: "stalled"}
-    out = {"solution": x.cpu().numpy(), "multipliers": lam[:, :p].cpu().numpy(), "status": [names[int(v)] for v in status.cpu().numpy()],
-           "iter": it.cpu().numpy(), "nfact": nfact.cpu().numpy(), "nlinsolve": nlin.cpu().numpy(), "nbk": nbk.cpu().numpy(),
-           "objective": fx.cpu().numpy(), "dtype": str(dt), "r": r.cpu().numpy(), "normdual": normdual.cpu().numpy(),
-           "normprimal": normprimal.cpu().numpy(), "epstol": epstol.cpu().numpy(), "steps": steps, "kernel": "band" if L.config.get("band") else L.config["kernel"], "vals_layout": "interleaved" if L.config.get("batch_layout") else "problem-major",
+    if compact:   # row b of every array holds problem orig[b]: back to the original order
+        where = orig.cpu().numpy().astype(np.int64)
+        assert np.array_equal(np.sort(where), np.arange(B))
+
+        def host(a):
+            a = a.cpu().numpy()
+            out_ = np.empty_like(a)
+            out_[where] = a
+            return out_
+    else:
+        host = lambda a: a.cpu().numpy()
+    out = {"solution": host(x), "multipliers": host(lam[:, :p]), "status": [names[int(v)] for v in host(status)],
+           "iter": host(it), "nfact": host(nfact), "nlinsolve": host(nlin), "nbk": host(nbk),
+           "objective": host(fx), "dtype": str(dt), "r": host(r), "normdual": host(normdual),
+           "normprimal": host(normprimal), "epstol": host(epstol), "steps": steps, "kernel": "band" if L.config.get("band") else L.config["kernel"], "vals_layout": "interleaved" if L.config.get("batch_layout") else "problem-major",
            "loop_seconds": loop_seconds}   # the global steps alone (the symbolic analysis of the pattern and the start-up evaluations are not in it)
+    if compact:
+        out.update(compactions=compactions, problem_steps=problem_steps, handle_shrunk=handle_shrunk)
     if prof is not None:
         out["profile_ms_per_step"] = {k: 1e3 * v / max(steps, 1) for k, v in prof.items()}
     L.close()

@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "cnl_cgls_multipliers_f32_dev", "cnl_cgls_multipliers_jac_f32_dev", "cnl_trial_point_f32_dev",
     "cnl_outer_begin_f32_dev", "cnl_outer_newton_done_f32_dev", "cnl_outer_extrapolated_f32_dev", "cnl_outer_trial_done_f32_dev",
     "cnl_outer_end_f32_dev", "cnl_outer_ls_begin_f32_dev", "cnl_outer_ls_test_f32_dev", "cnl_outer_ls_step_f32_dev", "cnl_outer_ls_take_f32_dev",
+    "cnl_set_active_batch", "cnl_get_active_batch", "cnl_outer_compact_dev", "cnl_outer_compact_f32_dev",
 ]
 
 
@@ -274,6 +275,10 @@ def lib():
         for sfx in ("_dev", "_f32_dev"):
             getattr(L, "cnl_outer_newton_done" + sfx).argtypes = [vp, C.c_int, vp]
             getattr(L, "cnl_outer_ls_test" + sfx).argtypes = [vp, C.c_int, vp]
+        L.cnl_set_active_batch.argtypes = [vp, i64]
+        L.cnl_get_active_batch.argtypes = [vp, C.POINTER(i64)]
+        for fn in ("cnl_outer_compact_dev", "cnl_outer_compact_f32_dev"):
+            getattr(L, fn).argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, vp]
         if L.cnl_version() < 200:
             raise RuntimeError(f"{LIB_PATH}: cnl_version() = {L.cnl_version()}, ABI version 0.2.0 or later required")
         _lib = L
@@ -442,6 +447,29 @@ class HIPLDLStruct:
         ms = C.c_float(0)
         _check(lib().cnl_last_kernel_ms(self._h, C.byref(ms)))
         return float(ms.value)
+
+
+def set_active_batch(LDLT, nb):
+    """cnl_set_active_batch: the handle's device-pointer entry points work on its first nb problems from here on (arrays keep the
+    addressing of the created batch).  Raises CnlError — code 5 (CNL_ERR_STATE) on a handle that cannot (staged, split, dense)."""
+    _check(lib().cnl_set_active_batch(LDLT._h, int(nb)))
+
+
+def get_active_batch(LDLT):
+    n = C.c_int64(0)
+    _check(lib().cnl_get_active_batch(LDLT._h, C.byref(n)))
+    return int(n.value)
+
+
+def outer_compact_dev(state, extras, min_finished, orig_ptr, counts_ptr, work_ptr, stream=0):
+    """cnl_outer_compact_dev / cnl_outer_compact_f32_dev (by the type of `state`, a cnl_outer_state or cnl_outer_state_f32): the
+    active problems become the first rows of every per-problem array of the state, of the `extras` — (device address, row bytes)
+    pairs — and of orig [B] int32; counts [2] int32 receives (active rows, rows the caller goes on with); work: int32 [B + 2]."""
+    fn = lib().cnl_outer_compact_f32_dev if isinstance(state, cnl_outer_state_f32) else lib().cnl_outer_compact_dev
+    k = len(extras)
+    ptrs = (C.c_void_p * max(k, 1))(*[int(p) for p, _ in extras])
+    rows = (C.c_int64 * max(k, 1))(*[int(b) for _, b in extras])
+    _check(fn(C.byref(state), k, ptrs, rows, int(min_finished), _int_ptr(orig_ptr), _int_ptr(counts_ptr), _int_ptr(work_ptr), stream))
 
 
 def launch_counts():

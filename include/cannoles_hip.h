@@ -55,7 +55,7 @@ typedef struct cnl_plan cnl_plan;     /* host-only symbolic analysis            
 typedef struct cnl_handle cnl_handle; /* plan + device state for one batch      */
 
 const char* cnl_last_error(void);
-/* library / ABI version: major*10000 + minor*100 + patch */
+/* library / ABI version: major*10000 + minor*100 + patch (0.3.0: cnl_set_active_batch, cnl_outer_compact_dev) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -306,7 +306,8 @@ int cnl_multi_synchronize(cnl_multi* m, void* const* streams);
  *   cnl_outer_trial_done_dev   :722-800  optimality measures at the trial point (nrm_t = the norms of cnl_residual_vectors_dev),
  *                                        acceptance, x / r / Fx / cx / Jv / Jcv / lam / rhs_cur / fx / delta / inner updates, end-of-
  *                                        inner-loop tests; rej, chk, done_in; flags[4] = any rejected, flags[5] = any small-residual check
- *   cnl_outer_end_dev          :800-857  statuses, outer-iteration counters, phase0                                                */
+ *   cnl_outer_end_dev          :800-857  statuses, outer-iteration counters, phase0
+ *   cnl_outer_compact_dev      (no counterpart: one problem has no batch) the active problems to the front of every array, below       */
 typedef struct cnl_outer_state {
   int64_t B, n, m, p, P /* max(p, 1): row length of lam, cx, ct, lamt */, N, nnzjF, nnzjc, max_inner;
   double dmin, rhomax, delta_dec, smax;
@@ -337,6 +338,41 @@ int cnl_outer_ls_test_dev(const cnl_outer_state* st, int first, void* stream);
 int cnl_outer_ls_step_dev(const cnl_outer_state* st, void* stream);
 int cnl_outer_ls_take_dev(const cnl_outer_state* st, void* stream);
 int cnl_outer_end_dev(const cnl_outer_state* st, void* stream);
+/* cnl_outer_compact_dev: the active problems (status == 0) become the first rows of the state, so that the caller can go on with
+ * st->B = their number (and cnl_set_active_batch on its handle) instead of running every kernel of a step over finished problems.
+ * Like its siblings: no handle, the current device, asynchronous on `stream`, CNL_ERR_ARG with nothing launched for a null state,
+ * B <= 0, a missing array, a null d_orig / d_counts / d_work, min_finished < 1, nextra outside [0, 24] or a null / empty extra array.
+ * With Bc = st->B and A = the number of rows b < Bc with status[b] == 0:
+ *   Bc - A < min_finished: nothing moves, d_counts = {A, Bc};
+ *   otherwise the k-th finished row below A (ascending) and the k-th active row at or above A (ascending) change places, for every k,
+ *   and d_counts = {A, A}: rows 0 .. A-1 then hold exactly the active problems.
+ * The swap applies to every per-problem array of the state that is there (all element, counter and mask members, nrm_t with its two
+ * entries per row; `flags` is global and stays; an array given under two members, as Jcv / Jct may be, moves once), to the nextra
+ * arrays d_extra[i] with rows of extra_row_bytes[i] bytes (the model's per-problem data) and to d_orig, int32 [B]: the original index
+ * of the problem in each row, which the caller sets to 0 .. B-1 at the start.  Rows change places in place; all B rows stay a
+ * permutation of what they were.  d_extra and extra_row_bytes are HOST arrays (of device pointers / sizes), d_counts is int32 [2] and
+ * d_work int32 [B + 2] on the device (the pair list; nothing is allocated per call).  Two launches, no host synchronisation.      */
+int cnl_outer_compact_dev(const cnl_outer_state* st, int64_t nextra, void* const* d_extra, const int64_t* extra_row_bytes, int64_t min_finished,
+                          int32_t* d_orig, int32_t* d_counts, int32_t* d_work, void* stream);
+
+/* ---- a handle on the first problems of its batch -------------------------------------------------------------------------------
+ * cnl_set_active_batch(h, nb): from here on every DEVICE-pointer entry point of the handle treats it as a batch of the problems
+ * 0 .. nb-1 — cnl_factorize*_dev, cnl_solve*_dev, cnl_newton_system*_dev, cnl_prepare_newton_system*_dev, cnl_residual_vectors*_dev,
+ * cnl_cgls_multipliers*_dev (and their `_jac` twins), cnl_trial_point*_dev, cnl_interleave*_dev, cnl_deinterleave*_dev, either element
+ * type.  Only the launch extent changes: every array keeps the addressing of the CREATED batch (problem-major rows, the groups of 32 of
+ * an interleaved `vals`, cnl_layout_len), what is written for a problem < nb is bit-equal to what the full-batch call writes for it, and
+ * nothing that belongs to a problem >= nb is written (its rows, its elements of an interleaved array — also inside a group of 32 that
+ * is active in part).  A caller whose problems finish at different times (the lockstep loop below, cnl_outer_compact_dev) keeps the
+ * active ones in front and stops paying for the others.
+ *   nb outside [1, created batch]: CNL_ERR_ARG.  nb = created batch restores the handle exactly and is accepted by every handle.
+ *   Served: band handles (Float64 and Float32, both layouts, 15- and 20-piece programs, the resident form) and handles whose calls are
+ *   the one classic launch of the register-front or the general kernel, with or without condensation.  CNL_ERR_STATE, the handle
+ *   unchanged and cnl_last_error naming the case: handles that run staged / dataflow, handles that run their batch split (tail handle,
+ *   halves, concurrent parts), the dense backend.  cnl_multi has no counterpart.
+ *   While nb is below the created batch the host-pointer entry points return CNL_ERR_STATE (they take the whole batch's arrays), and
+ *   cnl_solve*_dev needs a last factorisation that covered at least nb problems (CNL_ERR_STATE otherwise).                        */
+int cnl_set_active_batch(cnl_handle* h, int64_t nb);
+int cnl_get_active_batch(const cnl_handle* h, int64_t* nb);
 
 /* Device time, in milliseconds, of the multifrontal kernel (the dominant kernel) of the last call,
  * measured with HIP events on the call's stream.  Enabling timing makes every call synchronise on
@@ -459,6 +495,8 @@ int cnl_outer_ls_test_f32_dev(const cnl_outer_state_f32* st, int first, void* st
 int cnl_outer_ls_step_f32_dev(const cnl_outer_state_f32* st, void* stream);
 int cnl_outer_ls_take_f32_dev(const cnl_outer_state_f32* st, void* stream);
 int cnl_outer_end_f32_dev(const cnl_outer_state_f32* st, void* stream);
+int cnl_outer_compact_f32_dev(const cnl_outer_state_f32* st, int64_t nextra, void* const* d_extra, const int64_t* extra_row_bytes,
+                              int64_t min_finished, int32_t* d_orig, int32_t* d_counts, int32_t* d_work, void* stream);
 
 #ifdef __cplusplus
 }
