@@ -126,7 +126,7 @@ def solve(nls, make_solver, newton_system, params, method="Newton", x=None, lam=
     nfact = nlinsolve = nbk = 0
     epsk = 1e3
     broken = False
-    tired = nls.neval > max_eval
+    tired = over_eval = nls.neval > max_eval
 
     def status():
         if first_order:
@@ -135,7 +135,7 @@ def solve(nls, make_solver, newton_system, params, method="Newton", x=None, lam=
             return "small_residual"
         if broken:
             return "exception"
-        if tired:
+        if over_eval:   # the evaluation count alone; the inner-iteration limit is `stalled` (src/CaNNOLeS.jl:843, 846)
             return "max_eval"
         if max_iter >= 0 and it > max_iter:
             return "max_iter"
@@ -226,7 +226,8 @@ def solve(nls, make_solver, newton_system, params, method="Newton", x=None, lam=
             if p > 0 and inner > 0 and normdualhat <= 0.99 * normdual + epsk / 2 and normprimalhat > 0.99 * normprimal + epsk / 2:
                 delta = max(delta / 10, params[1])
             inner += 1
-            tired = nls.neval > max_eval or inner > max_inner
+            over_eval = nls.neval > max_eval
+            tired = over_eval or inner > max_inner
         normdual, normprimal = normdualhat, normprimalhat
         first_order = max(normdual / dual_scaling(lam), normprimal) <= epstol
         small_residual = 2 * np.sqrt(fx) <= epsF and np.linalg.norm(cx) <= epsc
