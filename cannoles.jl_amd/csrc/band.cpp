@@ -553,4 +553,48 @@ void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, 
   B.ok = true;
 }
 
+// The mover table (band.h, BAND_MK_*): every used descriptor of an epoch of the resident program gets one staging set — a typed set of
+// its kind while there is one, a general set otherwise — in descriptor order, so the table is a function of the program alone.
+void build_band_mover(BandPlan& B, int fvals, int bvals, int bfactor) {
+  B.mover_ok = false;
+  for (int q = 0; q < 2; q++) B.part[q].mover.clear();
+  auto no = [&](const std::string& w) {
+    for (int q = 0; q < 2; q++) B.part[q].mover.clear();
+    B.mover_why = w;
+  };
+  if (!B.ok || !B.resident) return no("no resident program");
+  for (int q = 0; q < B.nparts; q++) {
+    BandPart& Q = B.part[q];
+    Q.mover.assign((size_t)Q.nepochs * BAND_MOV_EW, -1);
+    for (int32_t e = 0; e < Q.nepochs; e++)
+      for (int sweep = 0; sweep < 2; sweep++) {
+        const int32_t* PP = Q.epochs.data() + (size_t)e * BAND_EW + (sweep ? BE_BP : BE_FP);
+        int32_t* M = Q.mover.data() + (size_t)e * BAND_MOV_EW + sweep * BAND_NPIECE;
+        // first set of each kind and the set behind its last: vals, factor, general
+        const int nv = sweep ? bvals : fvals, nf = sweep ? bfactor : 0;
+        int next[3] = {nv + nf, 0, nv};
+        const int end[3] = {BAND_NPIECE, nv, nv + nf};
+        for (int k = 0; k < BAND_NPIECE; k++) {
+          const int32_t pc = PP[k];
+          if (pc < 0) continue;
+          const int arr = pc >> 28, slot = (pc >> BAND_RES_SLOT_SHIFT) & 31;
+          const int64_t el = pc & ((1 << BAND_RES_SLOT_SHIFT) - 1);
+          int kind = arr == 0 && el % 8 == 0 ? BAND_MK_VALS : arr == 2 ? BAND_MK_FACTOR : BAND_MK_GENERAL;
+          if (next[kind] == end[kind]) kind = BAND_MK_GENERAL;
+          if (next[kind] == end[kind])
+            return no("an epoch does not fit the typed staging sets (part " + std::to_string(q) + ", epoch " + std::to_string(e) + (sweep ? ", backward)" : ", forward)"));
+          int32_t w = pc;
+          if (kind != BAND_MK_GENERAL) {
+            const int64_t off = (el + (kind == BAND_MK_FACTOR ? Q.loff : 0)) * BAND_MOV_EL_BYTES;
+            if (off >= (1ll << 31)) return no("a piece offset does not fit 32 bits");
+            w = (int32_t)off | slot;
+          }
+          M[next[kind]++] = w;
+        }
+      }
+  }
+  B.mover_ok = true;
+  B.mover_why.clear();
+}
+
 }  // namespace cnl

@@ -77,6 +77,33 @@ constexpr int BAND_RES_SLOT_SHIFT = 23;
 constexpr int BAND_RES_FSLOTS = BAND_NPIECE + BAND_LOUT_MAX / 8;     // 19 slots of the forward sweep
 static_assert(BAND_RES_FSLOTS * 8 <= BAND_ZERO_OFF && BAND_RES_FSLOTS <= 32, "resident slots inside the lane block, five bits in a descriptor");
 
+// The MOVER TABLE of a resident program (build_band_mover; kernel: band.hip, BAND_NPIECE_MOVER; cnl_plan_get prefix "bandm_").  The
+// resident kernel derives array, layout, base pointer, stride and lane offset of every piece from its descriptor, in every epoch,
+// although none of it depends on anything the device learns: with `vals` interleaved and the factor records element-major over the
+// 32 problems of a workgroup, the address of a piece is a host-known byte offset from the workgroup's base of its array plus a lane
+// offset that is the same in every epoch.  The table says which of the fifteen staging register sets a piece of an epoch travels in,
+// and every set has a KIND fixed at compile time per sweep (band_mover_kind):
+//   BAND_MK_VALS     an aligned block of interleaved `vals`, first element e (a multiple of 8): byte offset e * 32 * 8 from the
+//                    workgroup's first block, lane offset (problem * 8 + le) * 8
+//   BAND_MK_FACTOR   a factor piece, first element e of the part: byte offset (loff + e) * 32 * 8 from the workgroup's records,
+//                    lane offset (problem + le * 32) * 8 (element-major records: the piece's misalignment drops out)
+//   BAND_MK_GENERAL  any piece: the word is the resident descriptor itself, decoded as the resident kernel decodes it
+// Per part and epoch BAND_MOV_EW words, forward sets first, then backward.  A typed word is  byte offset | slot  (the offsets are
+// multiples of 256, the slot has five bits); an unused set holds -1.  A typed set carries only its kind; a piece whose typed sets are
+// taken travels in a general one.  An epoch that does not fit, or a typed offset of 2^31 or more, refuses the table (BandPlan::mover_ok)
+// and the handle stays on the resident instance.
+enum { BAND_MK_GENERAL = 0, BAND_MK_VALS = 1, BAND_MK_FACTOR = 2 };
+constexpr int BAND_MOV_FVALS = 11;                        // forward: sets 0 .. 10 vals, 11 .. 14 general
+constexpr int BAND_MOV_BVALS = 5, BAND_MOV_BFACTOR = 6;    // backward: sets 0 .. 4 vals, 5 .. 10 factor, 11 .. 14 general
+constexpr int band_mover_kind(int sweep, int k) {
+  return sweep == 0 ? (k < BAND_MOV_FVALS ? BAND_MK_VALS : BAND_MK_GENERAL)
+                    : (k < BAND_MOV_BVALS ? BAND_MK_VALS : k < BAND_MOV_BVALS + BAND_MOV_BFACTOR ? BAND_MK_FACTOR : BAND_MK_GENERAL);
+}
+constexpr int BAND_MOV_EW = 2 * BAND_NPIECE;
+constexpr int BAND_MOV_SLOT_MASK = 31;
+constexpr int BAND_MOV_EL_BYTES = 32 * 8;   // typed byte offset per element index: 32 problems of 8-byte elements
+static_assert(BAND_MOV_EL_BYTES > BAND_MOV_SLOT_MASK && BAND_RES_FSLOTS <= BAND_MOV_SLOT_MASK, "the slot fits below a typed offset");
+
 // cnl_options.batch_layout = 1 (include/cannoles_hip.h): `vals` interleaved over groups of BAND_IL_GROUP problems in blocks of eight
 // doubles — element e of problem p at ((p / 32 * band_il_blocks(nnz) + e / 8) * 32 + p % 32) * 8 + e % 8.  One spare block per problem:
 // an operand piece is eight doubles from ANY element, the last one may reach into the block behind the array's last.
@@ -132,6 +159,7 @@ struct BandPart {
   std::vector<int32_t> fops, bops;   // step (+ row) blocks in forward / backward order
   std::vector<int32_t> epochs;       // BAND_EW ints per epoch
   std::vector<int32_t> borders;      // BAND_BW ints per border
+  std::vector<int32_t> mover;        // mover table of a resident program (BAND_MOV_EW ints per epoch; empty where there is none)
   int64_t loff = 0;                  // first factor double of the part inside a problem's factor storage
 };
 
@@ -141,6 +169,8 @@ struct BandPlan {
   bool pieces_short = false;  // !ok because an epoch needs more than npiece operand pieces (and for no other reason found before that)
   int32_t npiece = BAND_NPIECE;   // operand pieces per epoch the program was built for: lane block and epoch block follow it
   bool resident = false;      // the resident form (see BAND_RES_SLOT_SHIFT)
+  bool mover_ok = false;      // the resident form has a mover table (BandPart::mover)
+  std::string mover_why;      // why not, when !mover_ok
   int32_t nparts = 0;
   int32_t m0 = 0;             // part 0 pivots variables [0, m0), part 1 pivots [m0 + BAND_HW, n) downwards (nparts == 2)
   int32_t n = 0, N = 0, nnz = 0;
@@ -155,5 +185,9 @@ struct BandPlan {
 // resident: the resident form (esz = 8, npiece = BAND_NPIECE only).
 void build_band_plan(BandPlan& B, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ,
                      int64_t ncon, int nparts_wanted, int esz = 8, int npiece = BAND_NPIECE, bool resident = false);
+
+// The mover table of a resident program (see BAND_MK_*): fills B.part[q].mover and B.mover_ok / B.mover_why; the program itself is
+// not touched.  fvals / bvals / bfactor: typed sets per sweep (the kernel's are the defaults; others are for tests of the refusal).
+void build_band_mover(BandPlan& B, int fvals = BAND_MOV_FVALS, int bvals = BAND_MOV_BVALS, int bfactor = BAND_MOV_BFACTOR);
 
 }  // namespace cnl

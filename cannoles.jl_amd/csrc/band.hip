@@ -349,10 +349,17 @@ __device__ __forceinline__ void bstep(T (&xs)[NS + 1], const BOps<T>& OP, const 
 // use.  Everything else is the 15-piece kernel.  (A value of the piece-count parameter, not a fourth parameter: the other
 // instances keep their names and, every difference being `if constexpr`, their code.)
 constexpr int BAND_NPIECE_RESIDENT = BAND_NPIECE + 256;
+// NPCX = BAND_NPIECE_MOVER (MOV below): the resident program with the MOVER TABLE in place of its piece descriptors (band.h, BAND_MK_*):
+// staging set K of a sweep has a kind fixed at compile time; a typed set forms its piece's address with one 64-bit scalar add — the
+// table's byte offset on the workgroup's base of the array — and a per-lane offset that is computed once per launch, where the
+// resident instance decodes array, layout, base, stride and lane offset of every piece in every epoch (about 60 instructions in
+// front of four loads, on a kernel that instruction issue bounds: DESIGN section 4).  General sets decode as the resident instance does.
+constexpr int BAND_NPIECE_MOVER = BAND_NPIECE + 512;
 #define EF(F) band_ef(F, NPC)
 template <class T, int NL, int NPCX>
 __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1)) band_newton_kernel(const BandDev P, const LaunchArgs Ain) {
-  constexpr bool RES = NPCX == BAND_NPIECE_RESIDENT;
+  constexpr bool MOV = NPCX == BAND_NPIECE_MOVER;
+  constexpr bool RES = NPCX == BAND_NPIECE_RESIDENT || MOV;
   constexpr int NPC = RES ? BAND_NPIECE : NPCX;
   static_assert(!RES || (direct_records(NL) && NPC == BAND_NPIECE && sizeof(T) == 8), "the resident form: Float64, 32 problems per workgroup, 15 pieces");
   constexpr int DBITS = RES ? BAND_RES_SLOT_SHIFT : 28;   // element bits of a piece descriptor
@@ -397,7 +404,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
   // (the groups of the LAYOUT are 32 problems whatever the workgroup holds: a workgroup of 16 problems works on half a group)
   constexpr int G8 = BAND_IL_GROUP * 8;
   static_assert(BAND_IL_GROUP % NL == 0, "a workgroup's problems lie in one group of the interleaved layout");
-  const bool vil = (Ain.layout & 1) != 0, ril = (Ain.layout & 2) != 0;
+  const bool vil = MOV || (Ain.layout & 1) != 0, ril = (Ain.layout & 2) != 0;
   const int vstride = vil ? G8 : 0, rstride = ril ? G8 : 0;
   const long long ilg = prob0 / BAND_IL_GROUP;        // group of the workgroup's problems
   const int ilp = (prob0 % BAND_IL_GROUP) * 8;        // ... and the offset of its first problem inside a block row
@@ -422,6 +429,16 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
     if (!movok[i]) pl = batch - 1 - prob0;
     movp[i] = (unsigned)pl;
     ldsb[i] = ((unsigned)(i * 8 + lq) * (unsigned)LANE_D + (unsigned)le) << LS;
+  }
+  // mover-table instance: the lane's byte offset inside an aligned block row of `vals` / inside a factor piece (band.h, BAND_MK_*)
+  unsigned movv[NI], movf[NI];
+  if constexpr (MOV) {
+#pragma unroll
+    for (int i = 0; i < NI; i++) {
+      movv[i] = (movp[i] * 8u + (unsigned)le) << LS;
+      movf[i] = (movp[i] + (unsigned)le * (unsigned)NL) << LS;
+    }
+    static_assert(!MOV || (NL == BAND_IL_GROUP && BAND_MOV_EL_BYTES == NL * ES), "a typed offset counts rows of NL elements");
   }
   // compute lanes
   const bool clane = lane < NL;
@@ -457,7 +474,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
 #define BAND_COMMIT1(K, I) if constexpr (I < NI) *reinterpret_cast<T*>(wblk + ldsb[I] + (BAND_IN_OFF + 8 * K) * ES) = stg[K][I];
   /* resident form: to the descriptor's slot (wave-uniform) */
 #define BAND_COMMITR1(K, I) if constexpr (I < NI) *reinterpret_cast<T*>(wslot_ + ldsb[I]) = stg[K][I];
-#define BAND_ISSUE(K)                                                                                                         \
+#define BAND_ISSUE_GEN(K)                                                                                                     \
   if (pcs[K] >= 0) {   /* (wave-uniform) */                                                                                   \
     const int pc = pcs[K];                                                                                                    \
     const int arr = pc >> 28;                                                                                                 \
@@ -479,11 +496,24 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
     const unsigned tl = t_ * tm_ + (t_ >> 3) * gap_;                                                                          \
     BAND_ISSUE1(K, 0) BAND_ISSUE1(K, 1) BAND_ISSUE1(K, 2) BAND_ISSUE1(K, 3)                                                   \
   }
+  /* mover-table instance, typed set: the word is  byte offset | slot  (negative: unused) */
+#define BAND_ISSUET1(K, I, VO) if constexpr (I < NI) stg[K][I] = *reinterpret_cast<const T*>(pb + VO[I]);
+#define BAND_ISSUET(K, BASE, VO)                                                                                              \
+  if (pcs[K] >= 0) {   /* (wave-uniform) */                                                                                   \
+    const char* pb = reinterpret_cast<const char*>(BASE) + (unsigned)(pcs[K] & ~BAND_MOV_SLOT_MASK);                          \
+    BAND_ISSUET1(K, 0, VO) BAND_ISSUET1(K, 1, VO) BAND_ISSUET1(K, 2, VO) BAND_ISSUET1(K, 3, VO)                               \
+  }
+  /* SW: the sweep (0 forward, 1 backward) — the kind of set K is band_mover_kind(SW, K); one code path per set */
+#define BAND_ISSUE(K, SW)                                                                                                     \
+  if constexpr (MOV && band_mover_kind(SW, K) == BAND_MK_VALS) { BAND_ISSUET(K, vbase, movv) }                                \
+  else if constexpr (MOV && band_mover_kind(SW, K) == BAND_MK_FACTOR) { BAND_ISSUET(K, lbase_g, movf) }                       \
+  else { BAND_ISSUE_GEN(K) }
   /* (at commit time pcs[] still holds the descriptors of the epoch being committed: the next epoch's are read behind the commit) */
-#define BAND_COMMIT(K)                                                                                                        \
+#define BAND_COMMIT(K, SW)                                                                                                    \
   if constexpr (RES) {                                                                                                        \
     if (pcs[K] >= 0) {                                                                                                        \
-      char* wslot_ = wblk + (BAND_IN_OFF + 8 * ((pcs[K] >> BAND_RES_SLOT_SHIFT) & 31)) * ES;                                  \
+      const int sl_ = MOV && band_mover_kind(SW, K) != BAND_MK_GENERAL ? pcs[K] & BAND_MOV_SLOT_MASK : (pcs[K] >> BAND_RES_SLOT_SHIFT) & 31; \
+      char* wslot_ = wblk + (BAND_IN_OFF + 8 * sl_) * ES;                                                                     \
       BAND_COMMITR1(K, 0) BAND_COMMITR1(K, 1) BAND_COMMITR1(K, 2) BAND_COMMITR1(K, 3)                                         \
     }                                                                                                                         \
   } else { BAND_COMMIT1(K, 0) BAND_COMMIT1(K, 1) BAND_COMMIT1(K, 2) BAND_COMMIT1(K, 3) }
@@ -491,35 +521,35 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
 #define BAND_ISSUE_DESC(EP, OFS) { cptr E_ = (EP) + (OFS); _Pragma("unroll") for (int k_ = 0; k_ < NPC; k_++) pcs[k_] = E_[k_]; }
   /* the epoch's step / row blocks (the streams are padded: reading past the epoch's blocks is harmless) */
 #define BAND_ISSUE_REC(OPS, OPOFF) { rstg0 = (reinterpret_cast<const int4*>((OPS) + (OPOFF)) + lane)[0]; }
-#define BAND_ISSUE_ALL(EP, OFS, OPS, OPOFF)                                                                                   \
+#define BAND_ISSUE_ALL(EP, OFS, OPS, OPOFF, SW)                                                                                   \
   {                                                                                                                           \
     BAND_ISSUE_DESC(EP, OFS)                                                                                                  \
-    BAND_ISSUE(0) BAND_ISSUE(1) BAND_ISSUE(2) BAND_ISSUE(3) BAND_ISSUE(4) BAND_ISSUE(5) BAND_ISSUE(6) BAND_ISSUE(7)           \
-    BAND_ISSUE(8) BAND_ISSUE(9) BAND_ISSUE(10) BAND_ISSUE(11) BAND_ISSUE(12) BAND_ISSUE(13) BAND_ISSUE(14)                    \
-    if constexpr (NPC > 15) { BAND_ISSUE(15) BAND_ISSUE(16) BAND_ISSUE(17) BAND_ISSUE(18) BAND_ISSUE(19) }                    \
+    BAND_ISSUE(0, SW) BAND_ISSUE(1, SW) BAND_ISSUE(2, SW) BAND_ISSUE(3, SW) BAND_ISSUE(4, SW) BAND_ISSUE(5, SW) BAND_ISSUE(6, SW) BAND_ISSUE(7, SW)           \
+    BAND_ISSUE(8, SW) BAND_ISSUE(9, SW) BAND_ISSUE(10, SW) BAND_ISSUE(11, SW) BAND_ISSUE(12, SW) BAND_ISSUE(13, SW) BAND_ISSUE(14, SW)                    \
+    if constexpr (NPC > 15) { BAND_ISSUE(15, SW) BAND_ISSUE(16, SW) BAND_ISSUE(17, SW) BAND_ISSUE(18, SW) BAND_ISSUE(19, SW) }                    \
     BAND_ISSUE_REC(OPS, OPOFF)                                                                                                \
   }
-#define BAND_COMMIT_ALL()                                                                                                     \
+#define BAND_COMMIT_ALL(SW)                                                                                                     \
   {                                                                                                                           \
-    BAND_COMMIT(0) BAND_COMMIT(1) BAND_COMMIT(2) BAND_COMMIT(3) BAND_COMMIT(4) BAND_COMMIT(5) BAND_COMMIT(6) BAND_COMMIT(7)   \
-    BAND_COMMIT(8) BAND_COMMIT(9) BAND_COMMIT(10) BAND_COMMIT(11) BAND_COMMIT(12) BAND_COMMIT(13) BAND_COMMIT(14)             \
-    if constexpr (NPC > 15) { BAND_COMMIT(15) BAND_COMMIT(16) BAND_COMMIT(17) BAND_COMMIT(18) BAND_COMMIT(19) }               \
+    BAND_COMMIT(0, SW) BAND_COMMIT(1, SW) BAND_COMMIT(2, SW) BAND_COMMIT(3, SW) BAND_COMMIT(4, SW) BAND_COMMIT(5, SW) BAND_COMMIT(6, SW) BAND_COMMIT(7, SW)   \
+    BAND_COMMIT(8, SW) BAND_COMMIT(9, SW) BAND_COMMIT(10, SW) BAND_COMMIT(11, SW) BAND_COMMIT(12, SW) BAND_COMMIT(13, SW) BAND_COMMIT(14, SW)             \
+    if constexpr (NPC > 15) { BAND_COMMIT(15, SW) BAND_COMMIT(16, SW) BAND_COMMIT(17, SW) BAND_COMMIT(18, SW) BAND_COMMIT(19, SW) }               \
     reinterpret_cast<int4*>(recb)[lane] = rstg0;                                                                              \
   }
   // the next epoch's loads go out in four groups behind the first four steps of the current one: 4 + 4 + 4 + 3 pieces, 5 + 5 + 5 + 5 in
   // the wide form; the last group takes the step blocks along
-#define BAND_ISSUE_G0()                                                                                                       \
-  if constexpr (NPC > 15) { BAND_ISSUE(0) BAND_ISSUE(1) BAND_ISSUE(2) BAND_ISSUE(3) BAND_ISSUE(4) }                           \
-  else { BAND_ISSUE(0) BAND_ISSUE(1) BAND_ISSUE(2) BAND_ISSUE(3) }
-#define BAND_ISSUE_G1()                                                                                                       \
-  if constexpr (NPC > 15) { BAND_ISSUE(5) BAND_ISSUE(6) BAND_ISSUE(7) BAND_ISSUE(8) BAND_ISSUE(9) }                           \
-  else { BAND_ISSUE(4) BAND_ISSUE(5) BAND_ISSUE(6) BAND_ISSUE(7) }
-#define BAND_ISSUE_G2()                                                                                                       \
-  if constexpr (NPC > 15) { BAND_ISSUE(10) BAND_ISSUE(11) BAND_ISSUE(12) BAND_ISSUE(13) BAND_ISSUE(14) }                      \
-  else { BAND_ISSUE(8) BAND_ISSUE(9) BAND_ISSUE(10) BAND_ISSUE(11) }
-#define BAND_ISSUE_G3()                                                                                                       \
-  if constexpr (NPC > 15) { BAND_ISSUE(15) BAND_ISSUE(16) BAND_ISSUE(17) BAND_ISSUE(18) BAND_ISSUE(19) }                      \
-  else { BAND_ISSUE(12) BAND_ISSUE(13) BAND_ISSUE(14) }
+#define BAND_ISSUE_G0(SW)                                                                                                       \
+  if constexpr (NPC > 15) { BAND_ISSUE(0, SW) BAND_ISSUE(1, SW) BAND_ISSUE(2, SW) BAND_ISSUE(3, SW) BAND_ISSUE(4, SW) }                           \
+  else { BAND_ISSUE(0, SW) BAND_ISSUE(1, SW) BAND_ISSUE(2, SW) BAND_ISSUE(3, SW) }
+#define BAND_ISSUE_G1(SW)                                                                                                       \
+  if constexpr (NPC > 15) { BAND_ISSUE(5, SW) BAND_ISSUE(6, SW) BAND_ISSUE(7, SW) BAND_ISSUE(8, SW) BAND_ISSUE(9, SW) }                           \
+  else { BAND_ISSUE(4, SW) BAND_ISSUE(5, SW) BAND_ISSUE(6, SW) BAND_ISSUE(7, SW) }
+#define BAND_ISSUE_G2(SW)                                                                                                       \
+  if constexpr (NPC > 15) { BAND_ISSUE(10, SW) BAND_ISSUE(11, SW) BAND_ISSUE(12, SW) BAND_ISSUE(13, SW) BAND_ISSUE(14, SW) }                      \
+  else { BAND_ISSUE(8, SW) BAND_ISSUE(9, SW) BAND_ISSUE(10, SW) BAND_ISSUE(11, SW) }
+#define BAND_ISSUE_G3(SW)                                                                                                       \
+  if constexpr (NPC > 15) { BAND_ISSUE(15, SW) BAND_ISSUE(16, SW) BAND_ISSUE(17, SW) BAND_ISSUE(18, SW) BAND_ISSUE(19, SW) }                      \
+  else { BAND_ISSUE(12, SW) BAND_ISSUE(13, SW) BAND_ISSUE(14, SW) }
 
   Win<T> W;
   int npos = 0, nzer = 0;
@@ -534,10 +564,10 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
     for (int q = 0; q < NS; q++) { W.X[q] = T(0); W.c[q] = T(0); }
     W.S55 = T(0); W.c5 = T(0);
     npos = 0; nzer = 0;
-    BAND_ISSUE_ALL(epochs, EF(BE_FP), fops_g, 0)
+    BAND_ISSUE_ALL(epochs, EF(BE_FP), fops_g, 0, 0)
     for (int e = 0; e < nepochs; e++) {
       cptr E = epochs + e * EW;
-      BAND_COMMIT_ALL()
+      BAND_COMMIT_ALL(0)
       // the next epoch's loads are issued in four groups behind the first four steps (a burst of 34 loads stalled the wavefront on
       // the CU's memory pipeline for ~2 500 cycles per epoch, in-kernel stamps), still four steps ahead of their use
       const bool more_ = e + 1 < nepochs;
@@ -568,6 +598,23 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
         }                                                                                                                   \
         o = onext; stC = stN; rwC = rwN;                                                                                    \
       }
+      // mover-table instance (BAND_FSTEP_X): the two sets of block registers alternate by step parity — the step of phase PH reads set
+      // PH % 2 (SC / RC) and loads the next step's blocks into the other (SN / RN) — instead of being copied behind every step: the
+      // copies were about 270 v_mov per forward epoch, on a kernel that instruction issue bounds
+#define BAND_FSTEP_P(PHV, SC, SN, RC, RN)                                                                                   \
+      if (PHV < nst) {                                                                                                      \
+        const int fl = __builtin_amdgcn_readfirstlane(SC.v[BS_FLAGS]);                                                      \
+        const int onext = o + BAND_SW + BAND_RW * ((fl >> 8) & 255);                                                        \
+        if (PHV + 1 < nst) { load_rec(SN, recb, onext); load_row(RN, recb, onext + BAND_SW); }                              \
+        if (clane) {                                                                                                        \
+          FOps<T> op_;                                                                                                      \
+          fload(op_, SC, RC, fl, myb);                                                                                      \
+          fstep<PHV, NL>(W, op_, SC, fl, recb, o, myb, gvals, grhs, borders, pv, pr, has_rhs, rho, ovr, tol, npos, nzer, vstride, rstride, \
+                         recp, PHV < BAND_EPOCH / 2 ? recb1 : recb2, recst);                                              \
+        }                                                                                                                   \
+        o = onext;                                                                                                          \
+      }
+#define BAND_FSTEP_X(PHV) if constexpr (MOV) { if constexpr (PHV % 2 == 0) { BAND_FSTEP_P(PHV, stC, stN, rwC, rwN) } else { BAND_FSTEP_P(PHV, stN, stC, rwN, rwC) } } else { BAND_FSTEP(PHV) }
       // !DREC: the out ring holds the factor records of half an epoch; whole pieces are read from it (all reads first), lanes past
       // the records do not store
 #define BAND_LFLUSH(LB, LC)                                                                                                 \
@@ -584,16 +631,16 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
                 *reinterpret_cast<T*>(lout + (((movp[i] * (unsigned)lsize + (unsigned)le) << LS) + 8 * ES * cpc)) = lx_[cpc][i]; \
         }                                                                                                                   \
       }
-      BAND_FSTEP(0)
-      if (more_) { BAND_ISSUE_G0() }
-      BAND_FSTEP(1)
-      if (more_) { BAND_ISSUE_G1() }
-      BAND_FSTEP(2)
-      if (more_) { BAND_ISSUE_G2() }
-      BAND_FSTEP(3)
-      if (more_) { BAND_ISSUE_G3() BAND_ISSUE_REC(fops_g, epochs[(e + 1) * EW + EF(BE_FOFF)]) }
+      BAND_FSTEP_X(0)
+      if (more_) { BAND_ISSUE_G0(0) }
+      BAND_FSTEP_X(1)
+      if (more_) { BAND_ISSUE_G1(0) }
+      BAND_FSTEP_X(2)
+      if (more_) { BAND_ISSUE_G2(0) }
+      BAND_FSTEP_X(3)
+      if (more_) { BAND_ISSUE_G3(0) BAND_ISSUE_REC(fops_g, epochs[(e + 1) * EW + EF(BE_FOFF)]) }
       BAND_LFLUSH(E[EF(BE_LBASE)], E[EF(BE_LCNT)])
-      BAND_FSTEP(4) BAND_FSTEP(5) BAND_FSTEP(6) BAND_FSTEP(7)
+      BAND_FSTEP_X(4) BAND_FSTEP_X(5) BAND_FSTEP_X(6) BAND_FSTEP_X(7)
       static_assert(BAND_EPOCH == 8, "eight step instantiations per epoch");
       if (nst == BAND_EPOCH) {
         // behind a full epoch the slots 0 .. 3 are dead (pivoted in phases 4 .. 7): give them a constant, so that only the ten
@@ -741,18 +788,19 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
     for (int i = 0; i < NI; i++) movst[i] = movok[i] && ctrl[NL + i * 8 + lq] != 0.0;
     const bool okme = valid && ctrl[NL + lane % NL] != 0.0 && clane;
     const long long pd = (long long)(prob0 + cpl) * N;
-    BAND_ISSUE_ALL(epochs + (nepochs - 1) * EW, EF(BE_BP), bops_g, 0)
+    BAND_ISSUE_ALL(epochs + (nepochs - 1) * EW, EF(BE_BP), bops_g, 0, 1)
     for (int e = nepochs - 1; e >= 0; e--) {
       cptr E = epochs + e * EW;
-      BAND_COMMIT_ALL()
+      BAND_COMMIT_ALL(1)
       const bool more_ = e > 0;
       if (more_) BAND_ISSUE_DESC(epochs + (e - 1) * EW, EF(BE_BP))
       const int nst = E[EF(BE_NSTEP)];
       int o = 0;
       Rec stC, stN;
       RowRec rwC, rwN;
-      load_rec(stC, recb, 0);
-      load_row(rwC, recb, BAND_SW);
+      // (mover-table instance: the step of phase PH reads its blocks from set PH % 2, and the first step of the epoch is nst - 1)
+      if (!MOV || (nst & 1)) { load_rec(stC, recb, 0); load_row(rwC, recb, BAND_SW); }
+      else { load_rec(stN, recb, 0); load_row(rwN, recb, BAND_SW); }
 #define BAND_BSTEP(PHV)                                                                                                     \
       if (PHV < nst) {                                                                                                      \
         const int fl = __builtin_amdgcn_readfirstlane(stC.v[BS_FLAGS]);                                                     \
@@ -765,15 +813,28 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
         }                                                                                                                   \
         o = onext; stC = stN; rwC = rwN;                                                                                    \
       }
-      BAND_BSTEP(7)
-      if (more_) { BAND_ISSUE_G0() }
-      BAND_BSTEP(6)
-      if (more_) { BAND_ISSUE_G1() }
-      BAND_BSTEP(5)
-      if (more_) { BAND_ISSUE_G2() }
-      BAND_BSTEP(4)
-      if (more_) { BAND_ISSUE_G3() BAND_ISSUE_REC(bops_g, epochs[(e - 1) * EW + EF(BE_BOFF)]) }
-      BAND_BSTEP(3) BAND_BSTEP(2) BAND_BSTEP(1) BAND_BSTEP(0)
+#define BAND_BSTEP_P(PHV, SC, SN, RC, RN)                                                                                   \
+      if (PHV < nst) {                                                                                                      \
+        const int fl = __builtin_amdgcn_readfirstlane(SC.v[BS_FLAGS]);                                                      \
+        const int onext = o + BAND_SW + BAND_RW * ((fl >> 8) & 255);                                                        \
+        if (PHV > 0) { load_rec(SN, recb, onext); load_row(RN, recb, onext + BAND_SW); }                                    \
+        if (clane) {                                                                                                        \
+          BOps<T> op_;                                                                                                      \
+          bload(op_, SC, RC, fl, myb);                                                                                      \
+          bstep<PHV>(xs, op_, SC, RC, fl, recb, o, myb, borders, gd, pd, okme);                                             \
+        }                                                                                                                   \
+        o = onext;                                                                                                          \
+      }
+#define BAND_BSTEP_X(PHV) if constexpr (MOV) { if constexpr (PHV % 2 == 0) { BAND_BSTEP_P(PHV, stC, stN, rwC, rwN) } else { BAND_BSTEP_P(PHV, stN, stC, rwN, rwC) } } else { BAND_BSTEP(PHV) }
+      BAND_BSTEP_X(7)
+      if (more_) { BAND_ISSUE_G0(1) }
+      BAND_BSTEP_X(6)
+      if (more_) { BAND_ISSUE_G1(1) }
+      BAND_BSTEP_X(5)
+      if (more_) { BAND_ISSUE_G2(1) }
+      BAND_BSTEP_X(4)
+      if (more_) { BAND_ISSUE_G3(1) BAND_ISSUE_REC(bops_g, epochs[(e - 1) * EW + EF(BE_BOFF)]) }
+      BAND_BSTEP_X(3) BAND_BSTEP_X(2) BAND_BSTEP_X(1) BAND_BSTEP_X(0)
       // solution components of the epoch
       const int xlo = E[EF(BE_DXLO)], xc = E[EF(BE_DXCNT)], rlo = E[EF(BE_DRLO)], rc = E[EF(BE_DRCNT)];
       char* dxo = reinterpret_cast<char*>(dbase) + ((long long)xlo << LS);
@@ -867,8 +928,11 @@ static hipError_t launch_band_t(const BandDev& P, int nl, const LaunchArgs& a, h
 // place in the code object)
 static hipError_t launch_band_resident(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece);
 
-hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece, bool resident) {
-  return resident ? launch_band_resident(P, nl, a, stream, npiece) : launch_band_t<double>(P, nl, a, stream, npiece);
+static hipError_t launch_band_mover(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece);
+
+hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece, bool resident, bool mover) {
+  if (mover && !resident) return hipErrorInvalidConfiguration;
+  return mover ? launch_band_mover(P, nl, a, stream, npiece) : resident ? launch_band_resident(P, nl, a, stream, npiece) : launch_band_t<double>(P, nl, a, stream, npiece);
 }
 hipError_t launch_band_f32(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece) { return launch_band_t<float>(P, nl, a, stream, npiece); }
 
@@ -876,6 +940,17 @@ static hipError_t launch_band_resident(const BandDev& P, int nl, const LaunchArg
   if (nl != 32 || npiece != BAND_NPIECE || !(a.layout & 1)) return hipErrorInvalidConfiguration;
   const size_t ldsb = band_lds_bytes(P.nparts, nl, (int)sizeof(double), npiece);
   auto kern = band_newton_kernel<double, 32, BAND_NPIECE_RESIDENT>;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)ldsb));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3((a.batch + nl - 1) / nl), dim3(64 * P.nparts), ldsb, stream, P, a);
+  return hipGetLastError();
+}
+
+// the mover-table instance (named last, for the same reason)
+static hipError_t launch_band_mover(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece) {
+  if (nl != 32 || npiece != BAND_NPIECE || !(a.layout & 1)) return hipErrorInvalidConfiguration;
+  const size_t ldsb = band_lds_bytes(P.nparts, nl, (int)sizeof(double), npiece);
+  auto kern = band_newton_kernel<double, 32, BAND_NPIECE_MOVER>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)ldsb));
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((a.batch + nl - 1) / nl), dim3(64 * P.nparts), ldsb, stream, P, a);

@@ -229,10 +229,19 @@ int setup_band(cnl_handle* h, const cnl::BandPlan& Bp0, const char** unfit) {
   // records directly, so that the out ring's LDS is free in the forward sweep).  Same steps and arithmetic: bit-equal outputs.
   h->band_resident = !h->f32 && !wide && h->band_nl == 32 && plan->opt.batch_layout == CNL_LAYOUT_INTERLEAVED && plan->band_res.B.ok;
   const cnl::BandPlan& Bp = h->band_resident ? plan->band_res.B : Bp0;
+  // ... and its mover table where it has one (band.h, BAND_MK_*; tuning band_mover_table = 0: none): the table's words take the place
+  // of the piece descriptors in the uploaded epoch blocks, which is the whole difference for the device
+  h->band_mover = h->band_resident && plan->opt.band_mover_table && Bp.mover_ok;
   for (int q = 0; q < Bp.nparts; q++) {
     if ((rc = upload(h, Bp.part[q].fops, &bd.fops[q]))) return rc;
     if ((rc = upload(h, Bp.part[q].bops, &bd.bops[q]))) return rc;
-    if ((rc = upload(h, Bp.part[q].epochs, &bd.epochs[q]))) return rc;
+    if (h->band_mover) {
+      std::vector<int32_t> ep = Bp.part[q].epochs;
+      static_assert(cnl::BE_BP == cnl::BE_FP + cnl::BAND_NPIECE && cnl::BAND_MOV_EW == 2 * cnl::BAND_NPIECE, "the two piece lists of an epoch block are adjacent");
+      for (int32_t e = 0; e < Bp.part[q].nepochs; e++)
+        std::copy_n(Bp.part[q].mover.begin() + (size_t)e * cnl::BAND_MOV_EW, cnl::BAND_MOV_EW, ep.begin() + (size_t)e * cnl::BAND_EW + cnl::BE_FP);
+      if ((rc = upload(h, ep, &bd.epochs[q]))) return rc;
+    } else if ((rc = upload(h, Bp.part[q].epochs, &bd.epochs[q]))) return rc;
     if ((rc = upload(h, Bp.part[q].borders, &bd.borders[q]))) return rc;
     bd.nsteps[q] = Bp.part[q].nsteps; bd.nepochs[q] = Bp.part[q].nepochs; bd.loff[q] = Bp.part[q].loff;
   }
@@ -755,7 +764,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   cfg[5] = (h->dense || h->gdense) ? 3 : (h->use_v2 ? (h->staged ? 4 : 2) : 1);
   if (h->lean && !h->dense && !h->gdense) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->tail) cfg[5] |= 32;                             // the remainder of the batch runs on a handle of its own (split_tail)
-  if (h->band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->band_resident << 24) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts, layout, operand pieces per epoch
+  if (h->band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->band_resident << 24) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28) | ((int64_t)h->band_mover << 34);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts, layout, operand pieces per epoch, mover table (bit 34: bit 27 marks a Float32 handle)
   if (h->djt.rv_ntiles > 0) cfg[5] |= 128;               // row f1 runs on column tiles (kernels.h: DevJt::rv_*)
   cfg[6] = h->wpb2;
   cfg[7] = (int64_t)h->lds2;

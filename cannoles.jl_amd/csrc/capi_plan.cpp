@@ -8,6 +8,7 @@ thread_local std::string g_err;
 // the names cnl_plan_get answers for band_prog[f32][wide]: "band_*" / "band4_*" keep describing the 15-piece program
 static const char* const kBandPrefix[2][2] = {{"band_", "bandw_"}, {"band4_", "bandw4_"}};
 static const char* const kBandResPrefix = "bandr_";   // ... and for band_res, a prefix of its own
+static const char* const kBandMovPrefix = "bandm_";   // the mover table of band_res: "bandm_info" = {has one, words per epoch, typed sets}, "bandm_table<q>"
 
 // band programs -> the summaries cnl_plan_get returns as "<prefix>info" / "<prefix>part<q>"
 void band_summaries(cnl_plan* p) {
@@ -19,6 +20,7 @@ void band_summaries(cnl_plan* p) {
     s.info = {Bp.ok ? 1 : 0, Bp.nparts, Bp.m0, Bp.n, Bp.N, Bp.nnz, (int32_t)Bp.lsize, Bp.ok && Bp.npiece != cnl::BAND_NPIECE ? Bp.npiece : 0};
     for (int q = 0; q < 2; q++) s.pinfo[q] = {Bp.part[q].nsteps, Bp.part[q].nepochs, Bp.part[q].npiv, Bp.part[q].nevents, (int32_t)Bp.part[q].loff};
   }
+  p->band_mov_info = {p->band_res.B.mover_ok ? 1 : 0, cnl::BAND_MOV_EW, cnl::BAND_MOV_FVALS, cnl::BAND_MOV_BVALS, cnl::BAND_MOV_BFACTOR};
 }
 
 // The band programs of a pattern for one element size: the 15-piece program whenever the pattern fits it, word for word what it always
@@ -39,6 +41,9 @@ void build_band_programs(cnl_plan* p, const int64_t* rows1, const int64_t* cols1
     Br = cnl::BandPlan();
     Br.why = !o.band_resident ? "tuning band_resident = 0" : B15.why;
     if (B15.ok && o.band_resident) cnl::build_band_plan(Br, N, nnz, rows1, cols1, nvar, nequ, ncon, nparts, esz, cnl::BAND_NPIECE, true);
+    // its mover table (band.h, BAND_MK_*): Br itself stays word for word what it was
+    if (Br.ok && o.band_mover_table) cnl::build_band_mover(Br);
+    else Br.mover_why = Br.ok ? "tuning band_mover_table = 0" : Br.why;
   }
 }
 // the program a handle runs: the wide one where the plan has it (the pattern needs it, or tuning band_pieces = 20)
@@ -386,9 +391,17 @@ int cnl_plan_get(const cnl_plan* plan, const char* name, int32_t* out, int64_t* 
         if (s.rfind(kBandPrefix[t][w], 0) == 0) { f = &plan->band_prog[t][w]; plen = std::strlen(kBandPrefix[t][w]); }
     // "bandr_*": the resident form of "band_*" (band.h; info[0] = 0 where the plan has none)
     if (s.rfind(kBandResPrefix, 0) == 0) { f = &plan->band_res; plen = std::strlen(kBandResPrefix); }
+    // "bandm_*": the mover table of "bandr_*" (band.h, BAND_MK_*): "bandm_info", "bandm_table<q>" (empty where the plan has none)
+    const bool mov = s.rfind(kBandMovPrefix, 0) == 0;
+    if (mov) { f = &plan->band_res; plen = std::strlen(kBandMovPrefix); }
     if (!f) return fail(CNL_ERR_ARG, "unknown plan array: " + s);
     const std::string rest = s.substr(plen);
-    if (rest == "info") { src = f->info.data(); n = (int64_t)f->info.size(); }
+    if (mov) {
+      if (rest == "info") { src = plan->band_mov_info.data(); n = (int64_t)plan->band_mov_info.size(); }
+      else if (rest == "table0" || rest == "table1") { const cnl::BandPart& Q = f->B.part[rest.back() - '0']; src = Q.mover.data(); n = (int64_t)Q.mover.size(); }
+      else return fail(CNL_ERR_ARG, "unknown plan array: " + s);
+    }
+    else if (rest == "info") { src = f->info.data(); n = (int64_t)f->info.size(); }
     else if (!rest.empty() && (rest.back() == '0' || rest.back() == '1')) {
       const int q = rest.back() - '0';
       const cnl::BandPart& Q = f->B.part[q];

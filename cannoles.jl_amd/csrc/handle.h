@@ -50,6 +50,7 @@ struct cnl_plan {
   // the RESIDENT form of band_prog[0][0] (band.h: aligned blocks of `vals` that stay in LDS while the next epoch needs them), built
   // beside it unless tuning band_resident = 0; runs the Float64 handles of 32 problems per workgroup with interleaved `vals`
   BandSlot band_res;
+  std::vector<int32_t> band_mov_info;   // "bandm_info": summary of band_res.B's mover table (band.h, BAND_MK_*)
 };
 
 struct cnl_handle {
@@ -134,6 +135,7 @@ struct cnl_handle {
   cnl::BandDev bd{};
   int band_nl = 16;            // problems per workgroup
   int band_npiece = 15;        // operand pieces per epoch of the program in bd: 15, or 20 = the wide kernel instances
+  bool band_mover = false;     // ... with the piece descriptors of its epoch blocks replaced by the mover table: the mover-table instance runs it
   bool band_resident = false;  // bd holds the plan's resident program (cnl_plan::band_res): the resident kernel instance runs it
   bool jac_segments = false;   // the J_F and the J_c entries are one run of slots each: [jf_lo, jf_lo + jf_n), [jc_lo, jc_lo + jc_n)
   int64_t jf_lo = 0, jf_n = 0, jc_lo = 0, jc_n = 0;

@@ -177,7 +177,8 @@ struct BandDev {
 // band factor storage [batch][P.lsize]
 // npiece: operand pieces per epoch of the program P was uploaded from (BandPlan::npiece): 15, or 20 = the wide kernel instances
 // resident: P is the resident form of the 15-piece program (band.h) — nl = 32, `vals` interleaved (a.layout & 1)
-hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece = 15, bool resident = false);
+// mover: ... whose epoch blocks carry the mover table in place of the piece descriptors (band.h, BAND_MK_*)
+hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece = 15, bool resident = false, bool mover = false);
 // the same on Float32 data: a.vals / rhs / d / L / rho_old / rho hold float arrays (stored through the double* fields), a.params the
 // Float32 parameters widened to double; P is the 4-byte program (build_band_plan with esz = 4), P.lsize counts floats
 hipError_t launch_band_f32(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece = 15);

@@ -55,6 +55,7 @@ namespace cnl {
   X(band_problems_per_group, 0) /* band kernels: problems per workgroup (8, 16, 32); 0 = by batch                           */ \
   X(band_pieces, 0)          /* band program: operand pieces per epoch — 0: 15, the wide form (20) where a pattern needs it; 15: never wide; 20: wide wherever a band */ \
   X(band_resident, 1)        /* band program: the resident form (aligned blocks of vals kept in LDS, band.h) runs the handles it serves; 0: never built */ \
+  X(band_mover_table, 1)     /* resident band program: the mover follows the host-built mover table (band.h, BAND_MK_*); 0: the resident instance decodes descriptors */ \
   X(analysis_threads, 0)     /* host threads of the symbolic analysis (candidate orders); 0 = by the hardware, at most 16      */ \
   X(f1_tiles, 1)             /* row f1 streams column tiles through LDS where the pattern allows; 0: gather kernel          */ \
   X(batch_layout, 0)         /* CNL_LAYOUT_*: layout of `vals` at the device-pointer entry points (band handles)            */ \

@@ -390,7 +390,8 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  *   bit 24 = the RESIDENT form of the 15-piece program runs (aligned blocks of `vals` kept in LDS: Float64, batch_layout = 1, 32 problems
  *   per workgroup; tuning "band_resident=0" keeps the 15-piece program — bit-equal outputs either way),
  *   bits 25-26 = cnl_options.batch_layout / rhs interleaved, bits 28-33 = operand pieces per epoch of the band program: 15, or 20
- *   for the wide form),
+ *   for the wide form, bit 34 = the resident program's mover follows the host-built mover table (csrc/band.h; tuning
+ *   "band_mover_table=0" keeps the resident instance that decodes piece descriptors — bit-equal outputs either way)),
  * + 128 when cnl_residual_vectors_dev runs on column tiles. */
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
 /* ([5] + (1 << 27) on a Float32 handle, which runs the band kernels only: bits 7-26 as above, cfg[0..4], [6], [7] are 0.) */
