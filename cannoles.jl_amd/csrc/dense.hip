@@ -1372,6 +1372,7 @@ int run_cached(DenseState* st, const GraphKey& key, hipStream_t stream, std::str
     st->graphs.erase(st->graphs.begin());
   }
   st->graphs.push_back(ge);
+  // (tests/test_dense_gpu.py::test_dense_graph_cache_states reads the states of this cache off the line below: keep its wording)
   if (getenv("CNL_VERBOSE")) fprintf(stderr, "[cnl] dense: call sequence captured as a graph (%zu cached)\n", st->graphs.size());
   DCHK(hipGraphLaunch(ge.exec, stream));
   return 0;
