@@ -14,14 +14,19 @@ bool band_wide_serves_f64(const cnl_plan* plan) {
   return band_program(plan, false).npiece == cnl::BAND_NPIECE || plan->opt.band_pieces == cnl::BAND_NPIECE_WIDE;
 }
 
+// The general kernel's work area and launch configuration, for the handle's element type.  A Float32 handle is asked with its
+// 4-byte elements — twice the problems per workgroup fit, and fronts up to order ~190 keep their work area in LDS — and chooses
+// among the configurations compiled for float (kernels.h: newton_f32_has).
 int choose_config(cnl_handle* h) {
   const cnl::Plan& P = h->plan->P;
+  const size_t esz = h->f32 ? sizeof(float) : sizeof(double);
   cnl::DevPlan& dp = h->dp;
   int64_t pb_off = std::max<int64_t>(P.fwd_peak, P.bwd_peak);
   pb_off = (pb_off + 1) & ~(int64_t)1;
   int64_t wv_off = pb_off + ((P.panel_max + 1) & ~1);
   int64_t work = wv_off + 2 * (int64_t)((P.fmax + 1) & ~1);
-  if (work >= ((int64_t)1 << 30)) return fail(CNL_ERR_DIM, "work area too large");
+  if (work >= ((int64_t)1 << 30))
+    return fail(CNL_ERR_DIM, h->f32 ? "cnl_create_f32: work area too large (largest front of order " + std::to_string(P.fmax) + ")" : std::string("work area too large"));
   dp.pb_off = (int32_t)pb_off;
   dp.wv_off = (int32_t)wv_off;
   dp.work_doubles = (int32_t)work;
@@ -29,8 +34,8 @@ int choose_config(cnl_handle* h) {
   if (maxlds == 0) return fail(CNL_ERR_HIP, "cannot query LDS size (no HIP device?)");
   maxlds = std::min<size_t>(maxlds, 160 * 1024);
   cnl::KernelConfig& c = h->cfg;
-  const size_t hdr = 16 * sizeof(double);
-  const size_t per = (size_t)work * sizeof(double);
+  const size_t hdr = 16 * esz;
+  const size_t per = (size_t)work * esz;
   int tpp, ppb, ldsw;
   if (hdr + per <= maxlds) {
     ldsw = 1;
@@ -44,14 +49,14 @@ int choose_config(cnl_handle* h) {
       size_t want = (size_t)std::min<int64_t>(16, std::max<int64_t>(1, h->batch / 256));
       ppb = 1;
       for (int cand : {16, 8, 4, 2, 1})
-        if ((size_t)cand <= cap && (size_t)cand <= want) { ppb = cand; break; }
+        if ((size_t)cand <= cap && (size_t)cand <= want && (!h->f32 || cnl::newton_f32_has(tpp, cand, true))) { ppb = cand; break; }
     } else {
-      tpp = P.fmax <= 400 ? 256 : 1024;
+      tpp = P.fmax <= 400 || h->f32 ? 256 : 1024;
       ppb = 1;
     }
   } else {
     ldsw = 0;
-    tpp = P.fmax <= 96 ? 64 : (P.fmax <= 400 ? 256 : 1024);
+    tpp = P.fmax <= 96 ? 64 : (P.fmax <= 400 || h->f32 ? 256 : 1024);
     ppb = tpp == 64 ? 4 : 1;
   }
   const cnl::Tuning& o = h->plan->opt;
@@ -60,6 +65,16 @@ int choose_config(cnl_handle* h) {
   if (o.v1_lds >= 0) ldsw = o.v1_lds;
   c.tpp = tpp; c.ppb = ppb; c.lds_work = ldsw;
   c.lds_bytes = hdr + (ldsw ? (size_t)ppb * per : 0);
+  if (h->f32) {
+    const std::string what = "tpp=" + std::to_string(tpp) + " ppb=" + std::to_string(ppb) + " lds=" + std::to_string(ldsw);
+    if (c.lds_bytes > maxlds)
+      return fail(CNL_ERR_DIM, "cnl_create_f32: the work area of the general kernel (largest front of order " + std::to_string(P.fmax) + ", " +
+                                   std::to_string(per) + " bytes per problem) does not fit the LDS of a workgroup with " + what);
+    if (!cnl::newton_f32_has(tpp, ppb, ldsw != 0))
+      return fail(CNL_ERR_ARG, "cnl_create_f32: the general kernel has no Float32 instance for " + what + " (tuning v1_tpp / v1_ppb / v1_lds; largest front of order " +
+                                   std::to_string(P.fmax) + ")");
+    return CNL_OK;
+  }
   if (c.lds_bytes > maxlds) return fail(CNL_ERR_DIM, "kernel configuration exceeds LDS");
   return CNL_OK;
 }
@@ -418,6 +433,34 @@ int create_tuned(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows1
   return create_from_plan(hout, plan, rows1, cols1, batch, device);
 }
 
+// the device copy of the general kernel's plan (kernels.h: DevPlan), either element type: index data, sizes and strides in elements
+int upload_dev_plan(cnl_handle* h) {
+  const cnl_plan* plan = h->plan;
+  const cnl::Plan& P = plan->P;
+  cnl::DevPlan& dp = h->dp;
+  int rc;
+  if ((rc = upload(h, P.fronts, &dp.fronts))) return rc;
+  if ((rc = upload(h, P.seg_ptr, &dp.seg_ptr))) return rc;
+  if ((rc = upload(h, P.asm_pos, &dp.asm_pos))) return rc;
+  if ((rc = upload(h, P.asm_src, &dp.asm_src))) return rc;
+  if ((rc = upload(h, P.child_idx, &dp.child_idx))) return rc;
+  if ((rc = upload(h, P.rel_idx, &dp.rel_idx))) return rc;
+  if ((rc = upload(h, P.perm, &dp.perm))) return rc;
+  dp.nsuper = P.nsuper; dp.N = (int32_t)P.N; dp.nnz = (int32_t)P.nnz; dp.rho_begin = P.rho_begin;
+  dp.nvar = (int32_t)P.nvar; dp.nequ = (int32_t)P.nequ; dp.ncon = (int32_t)P.ncon;
+  dp.fmax = (P.fmax + 1) & ~1;
+  // factor storage stride per problem: + 16 zero doubles that are never written.  The solve sweeps read a panel row as 16
+  // lanes, so the last rows of a problem's factor are over-read by up to 15 entries, which are multiplied by zeros; without
+  // the pad they would be the first entries of the NEXT problem's factor, and a NaN / Inf there (a neighbour whose
+  // factorisation broke down) would turn 0 * x into NaN in this problem's solution
+  dp.lsize = P.lsize + 16;
+  const cnl::Cond& C = plan->C;
+  dp.vstride = C.active ? C.cstride : plan->nnz;
+  dp.rstride = C.active ? C.cstride : plan->N;
+  dp.dstride = C.active ? C.N2 : plan->N;
+  return CNL_OK;
+}
+
 }  // namespace
 
 // device state for `batch` problems of an analysed pattern; takes ownership of `plan` (freed with the handle, or here on failure)
@@ -428,27 +471,9 @@ int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, co
   h->plan = plan; h->device = device; h->batch = h->full_batch = batch;
   auto bail = [&](int code) { cnl_destroy(h); return code; };
   if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
-  const cnl::Plan& P = plan->P;
   cnl::DevPlan& dp = h->dp;
-  if ((rc = upload(h, P.fronts, &dp.fronts))) return bail(rc);
-  if ((rc = upload(h, P.seg_ptr, &dp.seg_ptr))) return bail(rc);
-  if ((rc = upload(h, P.asm_pos, &dp.asm_pos))) return bail(rc);
-  if ((rc = upload(h, P.asm_src, &dp.asm_src))) return bail(rc);
-  if ((rc = upload(h, P.child_idx, &dp.child_idx))) return bail(rc);
-  if ((rc = upload(h, P.rel_idx, &dp.rel_idx))) return bail(rc);
-  if ((rc = upload(h, P.perm, &dp.perm))) return bail(rc);
-  dp.nsuper = P.nsuper; dp.N = (int32_t)P.N; dp.nnz = (int32_t)P.nnz; dp.rho_begin = P.rho_begin;
-  dp.nvar = (int32_t)P.nvar; dp.nequ = (int32_t)P.nequ; dp.ncon = (int32_t)P.ncon;
-  dp.fmax = (P.fmax + 1) & ~1;
-  // factor storage stride per problem: + 16 zero doubles that are never written.  The solve sweeps read a panel row as 16
-  // lanes, so the last rows of a problem's factor are over-read by up to 15 entries, which are multiplied by zeros; without
-  // the pad they would be the first entries of the NEXT problem's factor, and a NaN / Inf there (a neighbour whose
-  // factorisation broke down) would turn 0 * x into NaN in this problem's solution
-  dp.lsize = P.lsize + 16;
+  if ((rc = upload_dev_plan(h))) return bail(rc);
   const cnl::Cond& C = plan->C;
-  dp.vstride = C.active ? C.cstride : (int64_t)nnz;
-  dp.rstride = C.active ? C.cstride : N;
-  dp.dstride = C.active ? C.N2 : N;
   if (C.active) {
     cnl::DevCond& dc = h->dc;
     std::vector<int32_t> cidx(N, -1);
@@ -586,12 +611,49 @@ int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1
   int rc = CNL_OK;
   const char* unfit = nullptr;
   if ((rc = setup_band(h, band_program(plan, true), &unfit))) return bail(rc);   // the wide program where the plan has one
-  if (!h->band) return bail(fail(CNL_ERR_ARG, std::string("cnl_create_f32: ") + unfit));   // (Float32 handles have no other kernel)
+  if (!h->band) {   // the program does not fit the band kernels: refused, or (tuning float32_general) the caller goes on to the general kernel
+    *hout = nullptr;
+    if (plan->opt.float32_general) { cnl_destroy(h); return CNL_OK; }   // (the plan goes with the handle)
+    return bail(fail(CNL_ERR_ARG, std::string("cnl_create_f32: ") + unfit));
+  }
   if ((rc = setup_layout(h))) return bail(rc);
   // rows f1 / f2 / f4 and the trial point: the Float64 handles' row lists (they hold the dimensions cnl_layout_len reads)
   if ((rc = build_row_lists(h, plan, rows1, cols1))) return bail(rc);
   if (hipStreamCreate(&h->stream) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipStreamCreate failed"));
   if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipEventCreate failed"));
+  *hout = h;
+  return CNL_OK;
+}
+
+// A Float32 handle on the general multifrontal kernel (tuning float32_general): `plan` is the throughput analysis without condensation.
+// The handle owns the device plan, float factor panels (with the zero pad per problem of upload_dev_plan), float global scratch where the
+// work area does not fit LDS, and the row lists; nothing of the register-front, dense, staged or condensation state exists for it.
+int create_f32_general_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device) {
+  cnl_handle* h = new cnl_handle();
+  h->plan = plan; h->device = device; h->batch = h->full_batch = batch; h->f32 = true; h->f32_general = true;
+  auto bail = [&](int code) { cnl_destroy(h); return code; };
+  if (plan->C.active) return bail(fail(CNL_ERR_STATE, "cnl_create_f32: the plan of a Float32 general handle must not be condensed"));
+  if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
+  int rc = CNL_OK;
+  if ((rc = upload_dev_plan(h))) return bail(rc);
+  if ((rc = choose_config(h))) return bail(rc);
+  if ((rc = setup_layout(h))) return bail(rc);   // (batch_layout = CNL_LAYOUT_INTERLEAVED is the band kernels': CNL_ERR_ARG)
+  {
+    // factor panels, zero-filled (the pad of every problem stays zero) and padded as a Float64 handle's
+    float* L = nullptr;
+    const size_t lfloats = (size_t)batch * (size_t)h->dp.lsize + 4096;
+    if ((rc = dalloc(h, &L, lfloats))) return bail(rc);
+    if (hipMemset(L, 0, lfloats * sizeof(float)) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipMemset failed"));
+    h->d_L = reinterpret_cast<double*>(L);
+  }
+  if (!h->cfg.lds_work) {
+    float* S = nullptr;
+    if ((rc = dalloc(h, &S, (size_t)batch * (size_t)h->dp.work_doubles))) return bail(rc);
+    h->d_scratch = reinterpret_cast<double*>(S);
+  }
+  if (hipStreamCreate(&h->stream) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipStreamCreate failed"));
+  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipEventCreate failed"));
+  if ((rc = build_row_lists(h, plan, rows1, cols1))) return bail(rc);
   *hout = h;
   return CNL_OK;
 }
@@ -627,22 +689,39 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
   cnl::Tuning o;
   if (int rc = resolve_options(opt, o)) return rc;
   if (int rc = check_batch(batch)) return rc;
-  if (!o.band_kernel) return fail(CNL_ERR_ARG, "cnl_create_f32: cnl_options.band_kernel = 0, and Float32 handles run on the band kernels only");
-  if (int rc = check_device(device)) return rc;
-  // the throughput analysis whatever the batch: there is nothing but the band program to run
+  if (!o.band_kernel && !o.float32_general)
+    return fail(CNL_ERR_ARG, "cnl_create_f32: cnl_options.band_kernel = 0, and Float32 handles run on the band kernels only (tuning float32_general = 1: "
+                             "the general multifrontal kernel)");
+  // The band kernels first (band_kernel != 0).  The throughput analysis whatever the batch: there is nothing but the band program to
+  // run.  The analysis is host work, so a pattern the band kernels refuse is refused with that reason whether or not a device is there.
   cnl_plan* plan = nullptr;
-  if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, o)) return rc;
-  if (!band_program(plan, true).ok) {   // (the analysis builds it next to the Float64 program; not for a pattern the Float64 handles serve otherwise)
-    build_band_programs(plan, rows1, cols1, (int)sizeof(float));
-    band_summaries(plan);
+  if (o.band_kernel) {
+    if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, o)) return rc;
+    if (!band_program(plan, true).ok) {   // (the analysis builds it next to the Float64 program; not for a pattern the Float64 handles serve otherwise)
+      build_band_programs(plan, rows1, cols1, (int)sizeof(float));
+      band_summaries(plan);
+    }
+    if (!band_program(plan, true).ok) {
+      const std::string why = plan->band_prog[1][1].B.why.empty() ? plan->band_prog[1][0].B.why : plan->band_prog[1][1].B.why;
+      cnl_plan_destroy(plan);
+      plan = nullptr;
+      if (!o.float32_general)
+        return fail(CNL_ERR_ARG, "cnl_create_f32: the pattern is not served by the band kernels (build_band_plan: " + why +
+                                     "); Float32 stays on the CPU backend for it (or tuning float32_general = 1: the general multifrontal kernel)");
+    }
   }
-  if (!band_program(plan, true).ok) {
-    const std::string why = plan->band_prog[1][1].B.why.empty() ? plan->band_prog[1][0].B.why : plan->band_prog[1][1].B.why;
-    cnl_plan_destroy(plan);
-    return fail(CNL_ERR_ARG, "cnl_create_f32: the pattern is not served by the band kernels (build_band_plan: " + why +
-                                 "); Float32 stays on the CPU backend for it");
+  if (int rc = check_device(device)) { cnl_plan_destroy(plan); return rc; }
+  if (plan) {
+    if (int rc = create_f32_from_plan(hout, plan, rows1, cols1, batch, device)) return rc;
+    if (*hout) return CNL_OK;   // (else: the program does not fit the band kernels, and float32_general is set)
   }
-  return create_f32_from_plan(hout, plan, rows1, cols1, batch, device);
+  // tuning float32_general: the general multifrontal kernel in float.  Its plan is the throughput analysis with nothing but that
+  // kernel to run, whatever the caller's options say: no condensation (a call is then the one classic launch), no register-front
+  // records, no dense routes, no staged execution, no band program.
+  cnl::Tuning g = o;
+  g.condense = 0; g.register_front = 0; g.dense_backend = 0; g.general_dense = 0; g.staged = 0; g.band_kernel = 0;
+  if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, g)) return rc;
+  return create_f32_general_from_plan(hout, plan, rows1, cols1, batch, device);
 }
 
 int cnl_destroy(cnl_handle* h) {
@@ -754,7 +833,7 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms) {
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   if (!h || !cfg) return fail(CNL_ERR_ARG, "null argument");
   std::memset(cfg, 0, 8 * sizeof(int64_t));
-  if (h->f32) {   // Float32 handle: the band kernels only
+  if (h->f32 && !h->f32_general) {   // Float32 handle on the band kernels
     cfg[5] = 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->layout << 25) | ((int64_t)1 << 27) | ((int64_t)h->band_npiece << 28);
     if (h->djt.rv_ntiles > 0) cfg[5] |= 128;
     return CNL_OK;
@@ -762,6 +841,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   cfg[0] = h->cfg.tpp; cfg[1] = h->cfg.ppb; cfg[2] = (int64_t)h->cfg.lds_bytes; cfg[3] = h->cfg.lds_work;
   cfg[4] = (h->full_batch + h->cfg.ppb - 1) / h->cfg.ppb;
   cfg[5] = (h->dense || h->gdense) ? 3 : (h->use_v2 ? (h->staged ? 4 : 2) : 1);
+  if (h->f32) cfg[5] |= (int64_t)1 << 27;                // a Float32 handle on the general kernel (tuning float32_general): bit 6 clear
   if (h->lean && !h->dense && !h->gdense) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->tail) cfg[5] |= 32;                             // the remainder of the batch runs on a handle of its own (split_tail)
   if (h->band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->band_resident << 24) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28) | ((int64_t)h->band_mover << 34);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts, layout, operand pieces per epoch, mover table (bit 34: bit 27 marks a Float32 handle)

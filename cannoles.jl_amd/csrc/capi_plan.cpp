@@ -265,8 +265,9 @@ int plan_create_tuned(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* ro
 extern "C" {
 
 const char* cnl_last_error(void) { return g_err.c_str(); }
-// 0.2.0 (round 4: in-kernel device ladder, cnl_options grew); 0.3.0: cnl_set_active_batch, cnl_outer_compact_dev
-int32_t cnl_version(void) { return 300; }
+// 0.2.0 (round 4: in-kernel device ladder, cnl_options grew); 0.3.0: cnl_set_active_batch, cnl_outer_compact_dev;
+// 0.3.1: tuning float32_general (Float32 handles on the general multifrontal kernel), no new symbol
+int32_t cnl_version(void) { return 301; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62

@@ -69,6 +69,10 @@ int run_band(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_
 }
 
 int launch(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
+  // a Float32 handle off the band kernels: the float instantiation of the general kernel serves the three calls of the plugin
+  // surface as one classic launch each, and nothing else
+  if (h->f32 && (a.skip_done || a.only_if_status || (a.mode == cnl::MODE_NEWTON && !a.rhs) || !h->f32_general || h->use_v2))
+    return fail(CNL_ERR_STATE, "this call is not served by the Float32 instantiation of the general kernel, and the handle has no other");
   if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
   a.batch = (int)h->batch;
   a.lean = h->lean ? 1 : 0;
@@ -82,7 +86,7 @@ int launch(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
     e = cnl::launch_newton2(h->dp2, h->wpb2, h->lds2, a, stream);
     g_launches[1]++;
   } else {
-    e = cnl::launch_newton(h->dp, h->cfg, a, stream);
+    e = h->f32 ? cnl::launch_newton_f32(h->dp, h->cfg, a, stream) : cnl::launch_newton(h->dp, h->cfg, a, stream);
     g_launches[2]++;
   }
   if (e != hipSuccess)

@@ -145,6 +145,11 @@ struct cnl_handle {
   // jac_segments); nothing else of the handle's device state exists, and every Float64 entry point refuses it (CNL_ERR_STATE).
   // last_vals holds its float array of the last factorisation (the band solve factorises those values again).
   bool f32 = false;
+  // ... off the band kernels (tuning float32_general = 1 where the band kernels do not serve the handle): the general multifrontal
+  // kernel instantiated for float.  The plan is the throughput analysis without condensation (C.active == false), so every call is
+  // the one classic launch; the handle owns dp, cfg, the row lists and FLOAT factor panels / global scratch behind d_L / d_scratch
+  // (element counts as for double: dp.lsize and dp.work_doubles count elements).  It keeps a real factor: the solve is two sweeps.
+  bool f32_general = false;
 };
 
 struct cnl_multi {

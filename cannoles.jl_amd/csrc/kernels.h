@@ -19,11 +19,11 @@ struct DevPlan {
   const int32_t* perm;
   int32_t nsuper, N, nnz, rho_begin, nvar, nequ, ncon;
   int32_t fmax;
-  int32_t pb_off;        // offset (doubles) of the panel buffer inside a problem's work area
-  int32_t wv_off;        // offset of the two pivot-row staging vectors (2*fmax doubles)
-  int32_t work_doubles;  // work area per problem
-  int64_t lsize;         // factor storage per problem (doubles)
-  int64_t vstride, rstride, dstride;  // per-problem strides (doubles) of vals / rhs / d
+  int32_t pb_off;        // offset (elements: doubles, or floats on a Float32 handle) of the panel buffer inside a problem's work area
+  int32_t wv_off;        // offset of the two pivot-row staging vectors (2*fmax elements)
+  int32_t work_doubles;  // work area per problem (elements)
+  int64_t lsize;         // factor storage per problem (elements)
+  int64_t vstride, rstride, dstride;  // per-problem strides (elements) of vals / rhs / d
 };
 
 struct KernelConfig {
@@ -187,6 +187,12 @@ size_t band_lds_bytes(int nparts, int nl, int esz = 8, int npiece = 15);   // es
 
 // returns hipSuccess or the launch error
 hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream);
+// the same kernel on Float32 data (a Float32 handle off the band kernels, tuning float32_general): a.vals / rhs / d / L / scratch /
+// rho_old / rho hold float arrays (stored through the double* fields), a.params the Float32 parameters widened to double; every
+// offset, stride and size of P counts elements, cfg.lds_bytes = 4 * (16 + ppb * work area).  Only the configurations
+// newton_f32_has() names are compiled for float; any other is hipErrorInvalidConfiguration.
+hipError_t launch_newton_f32(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream);
+bool newton_f32_has(int tpp, int ppb, bool lds_work);
 hipError_t launch_newton2(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream);
 // one attempt at the rho given in vals, stage by stage (stage_ptr: host array of nstages + 1 task offsets)
 hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, LaunchArgs a, const int32_t* stage_ptr, int nstages, hipStream_t stream);

@@ -17,6 +17,11 @@
 // the front and the L panel is its packed suffix (one contiguous, coalesced
 // store to HBM).  The update-matrix stack lives in LDS at offsets computed on
 // the host; there is no inter-workgroup communication and no atomic.
+//
+// Every function is a template on the element type T: double for the Float64 handles, float for the Float32 handles that run on
+// this kernel (tuning float32_general).  With T = float values, right-hand side, d, rho, the factor panels, the
+// work area and the reduction scratch are float and every operation is a float operation; the parameters arrive widened in
+// LaunchArgs::params and are narrowed back, the float arrays travel behind the double* fields of LaunchArgs.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -55,8 +60,13 @@ __device__ __forceinline__ void phase_fence() {
   else __syncthreads();
 }
 
-template <int TPP>
-__device__ __forceinline__ double psum(double v, double* red, int tid) {
+__device__ __forceinline__ double abs_of(double v) { return fabs(v); }
+__device__ __forceinline__ float abs_of(float v) { return fabsf(v); }
+__device__ __forceinline__ double max_of(double a, double b) { return fmax(a, b); }
+__device__ __forceinline__ float max_of(float a, float b) { return fmaxf(a, b); }
+
+template <int TPP, class T>
+__device__ __forceinline__ T psum(T v, T* red, int tid) {
   if (TPP <= 64) {
 #pragma unroll
     for (int o = TPP / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, TPP);
@@ -67,43 +77,44 @@ __device__ __forceinline__ double psum(double v, double* red, int tid) {
     __syncthreads();
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
-    double s = 0;
+    T s = 0;
     for (int w = 0; w < TPP / 64; w++) s += red[w];
     return s;
   }
 }
 
+template <class T>
 struct ProblemCtx {
-  const double* vals;  // this problem's COO values
-  const double* rhs;
-  double* L;
-  double* W;           // work area (LDS or global)
-  double* red;         // cross-wave reduction scratch (TPP > 64)
+  const T* vals;  // this problem's COO values
+  const T* rhs;
+  T* L;
+  T* W;           // work area (LDS or global)
+  T* red;         // cross-wave reduction scratch (TPP > 64)
 };
 
 // ---------------------------------------------------------------------------
 // forward pass over one front: assemble, extend-add, eliminate the pivots,
 // store the L panel, leave the update matrix for the parent.
-template <int TPP, bool LDSW, bool WITH_K>
-__device__ __forceinline__ void front_forward(const DevPlan& P, const FrontHdr& H, const ProblemCtx& c, int tid,
-                                              bool rho_override, double rho, double eig_tol, int& npos, int& nzer) {
+template <int TPP, bool LDSW, bool WITH_K, class T>
+__device__ __forceinline__ void front_forward(const DevPlan& P, const FrontHdr& H, const ProblemCtx<T>& c, int tid,
+                                              bool rho_override, T rho, T eig_tol, int& npos, int& nzer) {
   const int nupd = H.nupd, npiv = H.npiv;
   const int f = 1 + nupd + npiv;
   const int tf = tri_i(f);
   const int tu = tri_i(1 + nupd);
-  double* F = c.W + H.foff;
-  double* Lp = c.L + ((long long)H.lptr_lo | ((long long)H.lptr_hi << 31));
+  T* F = c.W + H.foff;
+  T* Lp = c.L + ((long long)H.lptr_lo | ((long long)H.lptr_hi << 31));
 
   if (WITH_K) {
-    for (int t = tid; t < tf; t += TPP) F[t] = 0.0;
+    for (int t = tid; t < tf; t += TPP) F[t] = T(0);
     psync<TPP, LDSW>();
     // assembly rounds (round r holds the r-th duplicate of every slot: COO-order sums)
     for (int r = H.seg_begin; r < H.seg_end; r++) {
       const int e0 = P.seg_ptr[r], e1 = P.seg_ptr[r + 1];
       for (int e = e0 + tid; e < e1; e += TPP) {
         const int src = P.asm_src[e], pos = P.asm_pos[e];
-        double v;
-        if (src >= P.nnz) v = c.rhs ? c.rhs[src - P.nnz] : 0.0;
+        T v;
+        if (src >= P.nnz) v = c.rhs ? c.rhs[src - P.nnz] : T(0);
         else if (rho_override && src >= P.rho_begin) v = rho;
         else v = c.vals[src];
         F[pos] += v;
@@ -114,7 +125,7 @@ __device__ __forceinline__ void front_forward(const DevPlan& P, const FrontHdr& 
     for (int ci = H.child_begin; ci < H.child_end; ci++) {
       const FrontHdr& C = P.fronts[P.child_idx[ci]];
       const int tuc = tri_i(1 + C.nupd);
-      const double* U = c.W + C.ubase;
+      const T* U = c.W + C.ubase;
       const int* rel = P.rel_idx + C.rel_begin;
       if (tid < tuc) {
         int a, b;
@@ -131,14 +142,14 @@ __device__ __forceinline__ void front_forward(const DevPlan& P, const FrontHdr& 
   } else {
     // vector-only forward solve (cnl_solve): F is the front's right-hand side vector
     for (int t = tid; t < f; t += TPP) {
-      double v = 0.0;
+      T v = T(0);
       if (t > nupd) v = c.rhs[P.perm[H.first_piv + (f - 1 - t)]];
       F[t] = v;
     }
     psync<TPP, LDSW>();
     for (int ci = H.child_begin; ci < H.child_end; ci++) {
       const FrontHdr& C = P.fronts[P.child_idx[ci]];
-      const double* U = c.W + C.ubase;
+      const T* U = c.W + C.ubase;
       const int* rel = P.rel_idx + C.rel_begin;
       for (int a = 1 + tid; a <= C.nupd; a += TPP) F[rel[a]] += U[a];
       psync<TPP, LDSW>();
@@ -146,17 +157,17 @@ __device__ __forceinline__ void front_forward(const DevPlan& P, const FrontHdr& 
   }
 
   if (WITH_K) {
-    double* wv0 = c.W + P.wv_off;
+    T* wv0 = c.W + P.wv_off;
     const int idep = f - H.indep;  // pivots with local index >= idep are mutually independent
     for (int i = f - 1; i > nupd; i--) {
       const int ulim = i >= idep ? idep : i;
-      double* rowi = F + tri_i(i);
-      double* wv = wv0 + ((i & 1) ? P.fmax : 0);
-      const double dpiv = rowi[i];
+      T* rowi = F + tri_i(i);
+      T* wv = wv0 + ((i & 1) ? P.fmax : 0);
+      const T dpiv = rowi[i];
       npos += dpiv > eig_tol;
-      nzer += fabs(dpiv) <= eig_tol;
+      nzer += abs_of(dpiv) <= eig_tol;
       for (int j = tid; j < ulim; j += TPP) {
-        const double w = rowi[j];
+        const T w = rowi[j];
         wv[j] = w;
         rowi[j] = w / dpiv;
       }
@@ -178,14 +189,14 @@ __device__ __forceinline__ void front_forward(const DevPlan& P, const FrontHdr& 
   } else {
     // forward substitution with the stored panel: z_i = w_i / d_i, v_j -= l_ij w_i
     const int idep = f - H.indep;
-    double* PB = c.W + P.pb_off;
+    T* PB = c.W + P.pb_off;
     const int plen = tf - tu;
     for (int t = tid; t < plen; t += TPP) PB[t] = Lp[t];
     psync<TPP, LDSW>();
     for (int i = f - 1; i > nupd; i--) {
       const int ulim = i >= idep ? idep : i;
-      const double* rowi = PB + (tri_i(i) - tu);
-      const double w = F[i];
+      const T* rowi = PB + (tri_i(i) - tu);
+      const T w = F[i];
       psync<TPP, LDSW>();
       for (int j = 1 + tid; j < ulim; j += TPP) F[j] -= rowi[j] * w;
       if (tid == 0) Lp[tri_i(i) - tu] = w / rowi[i];
@@ -196,10 +207,10 @@ __device__ __forceinline__ void front_forward(const DevPlan& P, const FrontHdr& 
   // hand the update matrix (or vector) to the parent: move it down the stack
   const int ulen = WITH_K ? tu : 1 + nupd;
   if (H.ubase != H.foff) {
-    double* U = c.W + H.ubase;
+    T* U = c.W + H.ubase;
     for (int t0 = 0; t0 < ulen; t0 += TPP) {
       const int t = t0 + tid;
-      double v = 0.0;
+      T v = T(0);
       if (t < ulen) v = F[t];
       psync<TPP, LDSW>();
       if (t < ulen) U[t] = v;
@@ -211,22 +222,22 @@ __device__ __forceinline__ void front_forward(const DevPlan& P, const FrontHdr& 
 }
 
 // backward pass over one front: x_i = z_i - sum_j l_ij x_j ;  d = -x
-template <int TPP, bool LDSW>
-__device__ __forceinline__ void front_backward(const DevPlan& P, const FrontHdr& H, const ProblemCtx& c, int tid, double* dout) {
+template <int TPP, bool LDSW, class T>
+__device__ __forceinline__ void front_backward(const DevPlan& P, const FrontHdr& H, const ProblemCtx<T>& c, int tid, T* dout) {
   const int nupd = H.nupd, npiv = H.npiv;
   const int f = 1 + nupd + npiv;
   const int tu = tri_i(1 + nupd);
   const int plen = tri_i(f) - tu;
-  double* X = c.W + H.xoff;
-  const double* Lp = c.L + ((long long)H.lptr_lo | ((long long)H.lptr_hi << 31));
-  double* PB = c.W + P.pb_off;
+  T* X = c.W + H.xoff;
+  const T* Lp = c.L + ((long long)H.lptr_lo | ((long long)H.lptr_hi << 31));
+  T* PB = c.W + P.pb_off;
   for (int t = tid; t < plen; t += TPP) PB[t] = Lp[t];
   if (H.parent >= 0) {
-    const double* Xp = c.W + P.fronts[H.parent].xoff;
+    const T* Xp = c.W + P.fronts[H.parent].xoff;
     const int* rel = P.rel_idx + H.rel_begin;
     for (int j0 = 1; j0 <= nupd; j0 += TPP) {
       const int j = j0 + tid;
-      double v = 0.0;
+      T v = T(0);
       if (j <= nupd) v = Xp[rel[j]];
       psync<TPP, LDSW>();
       if (j <= nupd) X[j] = v;
@@ -235,11 +246,11 @@ __device__ __forceinline__ void front_backward(const DevPlan& P, const FrontHdr&
   }
   psync<TPP, LDSW>();
   for (int i = nupd + 1; i < f; i++) {
-    const double* rowi = PB + (tri_i(i) - tu);
-    double part = 0.0;
+    const T* rowi = PB + (tri_i(i) - tu);
+    T part = T(0);
     for (int j = 1 + tid; j < i; j += TPP) part += rowi[j] * X[j];
-    const double acc = psum<TPP>(part, c.red, tid);
-    const double xi = rowi[0] - acc;
+    const T acc = psum<TPP>(part, c.red, tid);
+    const T xi = rowi[0] - acc;
     if (tid == 0) {
       X[i] = xi;
       dout[P.perm[H.first_piv + (f - 1 - i)]] = -xi;
@@ -248,9 +259,9 @@ __device__ __forceinline__ void front_backward(const DevPlan& P, const FrontHdr&
   }
 }
 
-template <int TPP, bool LDSW>
-__device__ __forceinline__ bool factor_attempt(const DevPlan& P, const ProblemCtx& c, int tid, bool rho_override, double rho,
-                                               double eig_tol, int& npos_out, int& nzer_out, int xpos, int xzer) {
+template <int TPP, bool LDSW, class T>
+__device__ __forceinline__ bool factor_attempt(const DevPlan& P, const ProblemCtx<T>& c, int tid, bool rho_override, T rho,
+                                               T eig_tol, int& npos_out, int& nzer_out, int xpos, int xzer) {
   int npos = xpos, nzer = xzer;
   for (int s = 0; s < P.nsuper; s++) front_forward<TPP, LDSW, true>(P, P.fronts[s], c, tid, rho_override, rho, eig_tol, npos, nzer);
   npos_out = npos; nzer_out = nzer;
@@ -262,7 +273,7 @@ __device__ __forceinline__ T* as_global(T* p) {  // struct members are generic p
   return (T*)(__attribute__((address_space(1))) T*)p;
 }
 
-template <int TPP, int PPB, bool LDSW>
+template <int TPP, int PPB, bool LDSW, class T>
 __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, const LaunchArgs Ain) {
   DevPlan P = Pin;
   P.fronts = as_global(Pin.fronts); P.seg_ptr = as_global(Pin.seg_ptr); P.asm_pos = as_global(Pin.asm_pos);
@@ -273,33 +284,40 @@ __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, con
   A.scratch = as_global(Ain.scratch); A.rho_old = as_global(Ain.rho_old); A.rho = as_global(Ain.rho);
   A.nfact = as_global(Ain.nfact); A.success = as_global(Ain.success); A.npos = as_global(Ain.npos); A.nzero = as_global(Ain.nzero);
   A.extra_pos = as_global(Ain.extra_pos); A.extra_zer = as_global(Ain.extra_zer);
-  extern __shared__ double smem[];
+  extern __shared__ double smem_raw[];
+  T* smem = reinterpret_cast<T*>(smem_raw);
+  // the element arrays of this launch, in the kernel's element type (LaunchArgs carries them as double*)
+  T* const a_vals = reinterpret_cast<T*>(A.vals);
+  const T* const a_rhs = reinterpret_cast<const T*>(A.rhs);
+  T* const a_d = reinterpret_cast<T*>(A.d);
+  T* const a_rho_old = reinterpret_cast<T*>(A.rho_old);
+  T* const a_rho = reinterpret_cast<T*>(A.rho);
   const int gl = threadIdx.x / TPP;     // problem slot inside the workgroup
   const int tid = threadIdx.x % TPP;
   const int b = blockIdx.x * PPB + gl;
   if (b >= A.batch) return;             // whole owner group exits together (no block barrier when PPB > 1)
-  ProblemCtx c;
-  c.vals = A.vals ? A.vals + (long long)b * P.vstride : nullptr;
-  c.rhs = A.rhs ? A.rhs + (long long)b * P.rstride : nullptr;
-  c.L = A.L + (long long)b * P.lsize;
-  double* redbase = smem;               // 16 doubles for cross-wave sums (TPP > 64)
+  ProblemCtx<T> c;
+  c.vals = a_vals ? a_vals + (long long)b * P.vstride : nullptr;
+  c.rhs = a_rhs ? a_rhs + (long long)b * P.rstride : nullptr;
+  c.L = reinterpret_cast<T*>(A.L) + (long long)b * P.lsize;
+  T* redbase = smem;                    // 16 elements for cross-wave sums (TPP > 64)
   c.red = redbase;
-  c.W = LDSW ? (smem + 16 + (long long)gl * P.work_doubles) : (A.scratch + (long long)b * P.work_doubles);
-  double* dout = A.d ? A.d + (long long)b * P.dstride : nullptr;
-  const double eig_tol = A.params[0];
+  c.W = LDSW ? (smem + 16 + (long long)gl * P.work_doubles) : (reinterpret_cast<T*>(A.scratch) + (long long)b * P.work_doubles);
+  T* dout = a_d ? a_d + (long long)b * P.dstride : nullptr;
+  const T eig_tol = (T)A.params[0];
   const int xpos = A.extra_pos ? A.extra_pos[b] : 0, xzer = A.extra_zer ? A.extra_zer[b] : 0;
 
   if (A.mode == MODE_SOLVE) {
     int np = 0, nz = 0;
-    for (int s = 0; s < P.nsuper; s++) front_forward<TPP, LDSW, false>(P, P.fronts[s], c, tid, false, 0.0, eig_tol, np, nz);
+    for (int s = 0; s < P.nsuper; s++) front_forward<TPP, LDSW, false>(P, P.fronts[s], c, tid, false, T(0), eig_tol, np, nz);
     phase_fence<TPP>();
     for (int s = P.nsuper - 1; s >= 0; s--) front_backward<TPP, LDSW>(P, P.fronts[s], c, tid, dout);
     return;
   }
   if (A.mode == MODE_FACTOR) {
     int np, nz;
-    ProblemCtx cf = c; cf.rhs = nullptr;
-    const bool ok = factor_attempt<TPP, LDSW>(P, cf, tid, false, 0.0, eig_tol, np, nz, xpos, xzer);
+    ProblemCtx<T> cf = c; cf.rhs = nullptr;
+    const bool ok = factor_attempt<TPP, LDSW>(P, cf, tid, false, T(0), eig_tol, np, nz, xpos, xzer);
     if (tid == 0) {
       A.success[b] = ok ? 1 : 0;
       if (A.npos) A.npos[b] = np;
@@ -308,20 +326,20 @@ __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, con
     return;
   }
   // ---- newton_system!: src/CaNNOLeS.jl:1019-1051 ----
-  const double kdec = A.params[2], kinc = A.params[3], klarge = A.params[4], rho0 = A.params[5],
-               rhomax = A.params[6], rhomin = A.params[7];
-  double rho_old = A.rho_old[b];
-  double rho = 0.0, wrote = 0.0;
+  const T kdec = (T)A.params[2], kinc = (T)A.params[3], klarge = (T)A.params[4], rho0 = (T)A.params[5],
+          rhomax = (T)A.params[6], rhomin = (T)A.params[7];
+  T rho_old = a_rho_old[b];
+  T rho = T(0), wrote = T(0);
   int nfact = 0, np, nz;
-  bool success = factor_attempt<TPP, LDSW>(P, c, tid, false, 0.0, eig_tol, np, nz, xpos, xzer);
+  bool success = factor_attempt<TPP, LDSW>(P, c, tid, false, T(0), eig_tol, np, nz, xpos, xzer);
   nfact++;
   if (!success) {
-    rho = rho_old == 0.0 ? rho0 : fmax(rhomin, kdec * rho_old);
+    rho = rho_old == T(0) ? rho0 : max_of(rhomin, kdec * rho_old);
     wrote = rho;
     success = factor_attempt<TPP, LDSW>(P, c, tid, true, rho, eig_tol, np, nz, xpos, xzer);
     nfact++;
     while (!success && rho <= rhomax) {
-      rho = rho_old == 0.0 ? klarge * rho : kinc * rho;
+      rho = rho_old == T(0) ? klarge * rho : kinc * rho;
       if (rho <= rhomax) {
         wrote = rho;
         success = factor_attempt<TPP, LDSW>(P, c, tid, true, rho, eig_tol, np, nz, xpos, xzer);
@@ -330,15 +348,15 @@ __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, con
     }
     if (rho <= rhomax) rho_old = rho;
     // the reference leaves the last rho tried in the rho slots of vals
-    double* vt = A.vals + (long long)b * P.vstride + P.rho_begin;
+    T* vt = a_vals + (long long)b * P.vstride + P.rho_begin;
     for (int i = tid; i < P.nvar; i += TPP) vt[i] = wrote;
   }
   phase_fence<TPP>();
   if (success)
     for (int s = P.nsuper - 1; s >= 0; s--) front_backward<TPP, LDSW>(P, P.fronts[s], c, tid, dout);
   if (tid == 0) {
-    A.rho[b] = rho;
-    A.rho_old[b] = rho_old;
+    a_rho[b] = rho;
+    a_rho_old[b] = rho_old;
     A.nfact[b] = nfact;
     A.success[b] = success ? 1 : 0;
   }
@@ -351,9 +369,9 @@ size_t max_lds_bytes() {
   return (size_t)v;
 }
 
-template <int TPP, int PPB, bool LDSW>
+template <int TPP, int PPB, bool LDSW, class T>
 static hipError_t launch_t(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream) {
-  auto kfn = newton_kernel<TPP, PPB, LDSW>;
+  auto kfn = newton_kernel<TPP, PPB, LDSW, T>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)cfg.lds_bytes));
   if (e != hipSuccess) return e;
   const int grid = (a.batch + PPB - 1) / PPB;
@@ -363,12 +381,34 @@ static hipError_t launch_t(const DevPlan& P, const KernelConfig& cfg, const Laun
 
 hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream) {
 #define CNL_CASE(T, B, W) \
-  if (cfg.tpp == T && cfg.ppb == B && (cfg.lds_work != 0) == W) return launch_t<T, B, W>(P, cfg, a, stream);
+  if (cfg.tpp == T && cfg.ppb == B && (cfg.lds_work != 0) == W) return launch_t<T, B, W, double>(P, cfg, a, stream);
   CNL_CASE(64, 16, true) CNL_CASE(64, 8, true) CNL_CASE(64, 4, true) CNL_CASE(64, 2, true) CNL_CASE(64, 1, true)
   CNL_CASE(32, 32, true) CNL_CASE(32, 16, true) CNL_CASE(32, 8, true) CNL_CASE(32, 2, true)
   CNL_CASE(16, 64, true) CNL_CASE(16, 32, true) CNL_CASE(16, 16, true) CNL_CASE(16, 4, true)
   CNL_CASE(256, 1, true) CNL_CASE(1024, 1, true)
   CNL_CASE(64, 4, false) CNL_CASE(256, 1, false) CNL_CASE(1024, 1, false)
+#undef CNL_CASE
+  return hipErrorInvalidConfiguration;
+}
+
+// The Float32 instances: the configurations choose_config picks for a Float32 handle (capi_handle.cpp) plus one per thread count and
+// work-area placement, each launched by tests/test_float32_general_gpu.py.  Every other configuration of the list above is
+// Float64-only.
+#define CNL_F32_CASES(X) \
+  X(64, 1, true) X(64, 4, true) X(32, 2, true) X(16, 4, true) X(256, 1, true) \
+  X(64, 4, false) X(256, 1, false)
+
+bool newton_f32_has(int tpp, int ppb, bool lds_work) {
+#define CNL_CASE(T, B, W) if (tpp == T && ppb == B && lds_work == W) return true;
+  CNL_F32_CASES(CNL_CASE)
+#undef CNL_CASE
+  return false;
+}
+
+hipError_t launch_newton_f32(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream) {
+#define CNL_CASE(T, B, W) \
+  if (cfg.tpp == T && cfg.ppb == B && (cfg.lds_work != 0) == W) return launch_t<T, B, W, float>(P, cfg, a, stream);
+  CNL_F32_CASES(CNL_CASE)
 #undef CNL_CASE
   return hipErrorInvalidConfiguration;
 }

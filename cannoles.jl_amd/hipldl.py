@@ -376,8 +376,9 @@ class HIPLDLStruct:
     pattern, problem-major values `vals[b, :]`.
 
     The element type comes from `vals`, as `LDLFactStruct(N, rows, cols, vals)` takes T from it (`dtype` when vals is None):
-    float64, or float32 — a Float32 handle (cnl_create_f32), which exists for band-structured patterns only (CnlError
-    CNL_ERR_ARG otherwise: the caller stays on the CPU backend)."""
+    float64, or float32 — a Float32 handle (cnl_create_f32), which by default exists for band-structured patterns only (CnlError
+    CNL_ERR_ARG otherwise: the caller stays on the CPU backend); Options(float32_general=1) serves every other pattern on the
+    general multifrontal kernel in float (config["kernel"] == "v1")."""
 
     def __init__(self, N, rows, cols, vals, nvar=None, nequ=None, ncon=None, batch=1, device=0, options=None, dtype=np.float64):
         self.N = int(N)
@@ -413,7 +414,7 @@ class HIPLDLStruct:
                        "band_mover_table": bool((int(cfg[5]) >> 34) & 1),
                        "batch_layout": (int(cfg[5]) >> 25) & 1, "rhs_interleaved": bool((int(cfg[5]) >> 26) & 1),
                        "float32": bool((int(cfg[5]) >> 27) & 1), "band_pieces": (int(cfg[5]) >> 28) & 63}
-        if self.config["float32"]:
+        if self.config["float32"] and self.config["band"]:   # (a Float32 handle off the band kernels — tuning float32_general — is "v1")
             self.config["kernel"] = "band"
 
     def plan_array(self, name):

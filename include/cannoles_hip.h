@@ -9,10 +9,12 @@
  * Conventions
  *   - Index arrays are int64, 1-based, exactly as Julia holds `rows`/`cols`
  *     (src/CaNNOLeS.jl:276-315).  Values are double (Float64).  Float32 is
- *     served on band-structured patterns (the band kernels, csrc/band.h) by
- *     handles of its own: cnl_create_f32 and the `_f32` entry points below.
- *     Every other element type, and Float32 on any other pattern, stays on
- *     the reference's LDLFactStruct.
+ *     served by handles of its own, cnl_create_f32 and the `_f32` entry
+ *     points below: on band-structured patterns by the band kernels
+ *     (csrc/band.h), on any other pattern by the general multifrontal kernel
+ *     where the caller asks for it (tuning "float32_general=1"; without it
+ *     such a pattern is refused and stays on the reference's LDLFactStruct,
+ *     as every other element type does).
  *   - The COO pattern is the lower triangle of the KKT matrix in the
  *     reference's 7-segment order [H_F | H_c | J_F | J_c | -I | -dI | rI];
  *     duplicates are summed in COO order (src/solver_types.jl:53-59); the
@@ -55,7 +57,8 @@ typedef struct cnl_plan cnl_plan;     /* host-only symbolic analysis            
 typedef struct cnl_handle cnl_handle; /* plan + device state for one batch      */
 
 const char* cnl_last_error(void);
-/* library / ABI version: major*10000 + minor*100 + patch (0.3.0: cnl_set_active_batch, cnl_outer_compact_dev) */
+/* library / ABI version: major*10000 + minor*100 + patch (0.3.0: cnl_set_active_batch, cnl_outer_compact_dev;
+ * 0.3.1: tuning "float32_general", no new symbol) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -394,7 +397,9 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  *   "band_mover_table=0" keeps the resident instance that decodes piece descriptors — bit-equal outputs either way)),
  * + 128 when cnl_residual_vectors_dev runs on column tiles. */
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
-/* ([5] + (1 << 27) on a Float32 handle, which runs the band kernels only: bits 7-26 as above, cfg[0..4], [6], [7] are 0.) */
+/* ([5] + (1 << 27) on a Float32 handle.  On the band kernels: bits 7-26 as above, cfg[0..4], [6], [7] are 0.  On the general kernel
+ *  (tuning "float32_general=1"): cfg[0..4] describe that kernel's float instance as they do for a Float64 handle — [2] counts 4-byte
+ *  elements — and [5] = 1 + (1 << 27) with bit 6 clear (+ 128 as above); [6], [7] are 0.) */
 /* Launches of the Newton-system kernels since the library was loaded, per kernel family: counts[0] band kernels (csrc/band.hip),
  * [1] register-front kernel (csrc/kernels2.hip, staged launches not included), [2] general kernel (csrc/kernels.hip).  Lets a test
  * pin WHICH kernel served a call sequence (e.g. that solve_ldl! behind a band factorisation launches no second kernel family). */
@@ -410,6 +415,17 @@ int cnl_launch_counts(int64_t counts[3]);
  * (cnl_last_error names the reason) when the pattern is not a band or cnl_options.band_kernel = 0: the caller stays on the CPU.
  * Accepted: the band patterns of cnl_options.band_kernel, the pattern of a constrained model included (H_c with the model's whole
  * Hessian structure: the wide form of the band program, csrc/band.h) — half-widths up to 2, one live multiplier at a time.
+ *   tuning "float32_general=1" (default 0: everything above, unchanged): where the band kernels do not serve the handle — the
+ * pattern is no such band, the program does not fit them, or cnl_options.band_kernel = 0 — it runs on the general multifrontal
+ * kernel (csrc/kernels.hip) instantiated for float, whatever the pattern, as ONE launch per call (cnl_launch_counts: family 2).  Its
+ * plan is the throughput analysis without condensation, register-front records, dense routes or staged execution, whatever the other
+ * options say.  Such a handle keeps a real factor: cnl_solve_f32 / cnl_solve_f32_dev are the two sweeps on the stored panels, no
+ * refactorisation, and — unlike a band handle, whose solve factorises the values of the last factorisation again — the caller's
+ * d_vals need not stay alive (or unchanged) between cnl_factorize_f32_dev and cnl_solve_f32_dev.  cnl_set_active_batch serves it.
+ * batch_layout = CNL_LAYOUT_INTERLEAVED on it is CNL_ERR_ARG (the layout is the band kernels'; the conversions cnl_interleave_f32_dev /
+ * cnl_deinterleave_f32_dev work on any Float32 handle).  Tuning v1_tpp / v1_ppb / v1_lds may name only a configuration compiled
+ * for float (csrc/kernels.hip, CNL_F32_CASES; CNL_ERR_ARG otherwise); a work area that fits neither LDS nor a global-scratch
+ * instance is CNL_ERR_DIM, cnl_last_error naming the order of the largest front.
  * The semantics of every call are those of its Float64 twin above.  Mixing element types is CNL_ERR_STATE and does nothing:
  * a Float64 entry point on a Float32 handle (cnl_factorize..., the row f1 / f2 / f4 / trial-point passes, cnl_interleave_dev...)
  * and an `_f32` entry point on a Float64 handle.  cnl_layout_len counts elements, so it serves both types.
