@@ -267,7 +267,8 @@ extern "C" {
 const char* cnl_last_error(void) { return g_err.c_str(); }
 // 0.2.0 (round 4: in-kernel device ladder, cnl_options grew); 0.3.0: cnl_set_active_batch, cnl_outer_compact_dev;
 // 0.3.1: tuning float32_general (Float32 handles on the general multifrontal kernel), no new symbol
-int32_t cnl_version(void) { return 301; }
+// 0.4.0: cnl_outer_ctl, cnl_outer_*_ex_dev, cnl_outer_hess_mask_dev
+int32_t cnl_version(void) { return 400; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62

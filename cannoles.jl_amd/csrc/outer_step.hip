@@ -10,6 +10,10 @@
 //   cnl_outer_end_dev          statuses, outer-iteration counters (:800-857)
 //   cnl_outer_compact_dev      (no counterpart in the reference) the active problems to the front of every per-problem array, so that
 //                              the next steps run on them alone
+//   cnl_outer_hess_mask_dev    which problems refresh their residual Hessian under :Newton_vanishing (hessian_approx.jl:55-60)
+// begin, trial_done, ls_test and end also come as `_ex` entry points with a control block `cnl_outer_ctl` (the keywords of `solve!` that
+// the plain calls leave at "off": always_accept_extrapolation, max_iter, max_eval with its per-problem evaluation counter).  One kernel
+// template serves both: it takes the block by value, and the plain entry points pass the block with everything off.
 // The arithmetic of every test is the reference's, in its operation order; minimum / maximum propagate NaN as the framework's
 // (and Julia's) do.  The model callbacks, the line search and the rare small-residual branch stay with the caller.
 //
@@ -62,8 +66,18 @@ __device__ double block_sum(double v, double* sh) {
   return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
+// the control block of a plain call: nothing accepted early, no limits, no evaluation counter
+cnl_outer_ctl ctl_off() {
+  cnl_outer_ctl c{};
+  c.struct_size = (int32_t)sizeof(cnl_outer_ctl);
+  c.max_iter = -1;
+  c.max_eval = -1;
+  return c;
+}
+__device__ __forceinline__ bool over_eval(const cnl_outer_ctl& C, long long b) { return C.neval && C.max_eval >= 0 && C.neval[b] > C.max_eval; }
+
 template <class ST>
-__global__ void __launch_bounds__(256) outer_begin_kernel(const ST S) {
+__global__ void __launch_bounds__(256) outer_begin_kernel(const ST S, const cnl_outer_ctl C) {
   using T = elem_t<ST>;
   const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
   if (b >= S.B) return;
@@ -81,7 +95,8 @@ __global__ void __launch_bounds__(256) outer_begin_kernel(const ST S) {
     S.ndh[b] = nd; S.nph[b] = np_;
     S.phase0[b] = 0;
   }
-  const bool need = act && inner != 1;   // the iteration right behind a rejected extrapolation reuses d (:627)
+  // the iteration right behind a rejected extrapolation reuses d (:627); with always_accept_extrapolation it took the point, so d is due
+  const bool need = act && (inner != 1 || C.always_accept_extrapolation);
   S.act[b] = act; S.need[b] = need; S.brk[b] = 0;
   if (act) atomicOr(S.flags + 0, 1);
   if (need) atomicOr(S.flags + 1, 1);
@@ -149,7 +164,7 @@ __global__ void __launch_bounds__(256) outer_extrapolated_kernel(const ST S) {
 }
 
 template <class ST>
-__global__ void __launch_bounds__(256) outer_trial_done_kernel(const ST S) {
+__global__ void __launch_bounds__(256) outer_trial_done_kernel(const ST S, const cnl_outer_ctl C) {
   using T = elem_t<ST>;
   __shared__ double sh[4];
   __shared__ int dec[4];
@@ -168,8 +183,9 @@ __global__ void __launch_bounds__(256) outer_trial_done_kernel(const ST S) {
     S.ndh[b] = ndh; S.nph[b] = nph; S.combined_hat[b] = chat;
     const T epsk = S.epsk[b];
     const bool good = chat <= T(0.99) * S.combined[b] + epsk;                        // :733
-    const bool acc_state = act && (inner0 > 0 || good);
+    const bool acc_state = act && (inner0 > 0 || C.always_accept_extrapolation || good);   // :735
     const bool acc_lam = act && good;
+    if (C.neval && S.ext[b]) C.neval[b] += C.evals_per_point;   // the extrapolation's trial point was evaluated (the line search counts its own)
     if (acc_state) S.fx[b] = T(0.5) * ss;
     const T delta = S.delta[b];
     T delta_next = delta;
@@ -179,7 +195,7 @@ __global__ void __launch_bounds__(256) outer_trial_done_kernel(const ST S) {
     }
     const long long inner = inner0 + (act ? 1 : 0);
     S.inner[b] = inner;
-    const bool tired = inner > S.max_inner;
+    const bool tired = inner > S.max_inner || over_eval(C, b);
     const bool done_in = (act && (good || tired)) || brk;
     if (done_in) { S.normdual[b] = ndh; S.normprimal[b] = nph; }
     S.delta[b] = delta_next;
@@ -254,7 +270,7 @@ __global__ void __launch_bounds__(256) outer_ls_begin_kernel(const ST S) {
 
 // Armijo test at (Fl, cl) = (F(xl), c(xl)); first != 0: the first test (every lsm problem), else a backtracking round's
 template <class ST>
-__global__ void __launch_bounds__(256) outer_ls_test_kernel(const ST S, int first) {
+__global__ void __launch_bounds__(256) outer_ls_test_kernel(const ST S, int first, const cnl_outer_ctl C) {
   using T = elem_t<ST>;
   __shared__ double sh[4];
   const long long b = blockIdx.x;
@@ -262,6 +278,7 @@ __global__ void __launch_bounds__(256) outer_ls_test_kernel(const ST S, int firs
   if (!cand) { if (first && threadIdx.x == 0) S.bt[b] = 0; return; }
   const T phil = merit<ST, T>(S, b, S.Fl, S.cl, S.eta[b], sh);
   if (threadIdx.x == 0) {
+    if (C.neval) C.neval[b] += C.evals_per_point;   // F and c at this candidate's xl
     const T alpha = S.alpha[b];
     bool bt = !(phil <= S.phix[b] + S.gammaA * alpha * S.Dphi[b]);
     if (!first) bt = bt && (alpha >= S.eps2);
@@ -295,7 +312,7 @@ __global__ void __launch_bounds__(256) outer_ls_take_kernel(const ST S) {
 }
 
 template <class ST>
-__global__ void __launch_bounds__(256) outer_end_kernel(const ST S) {
+__global__ void __launch_bounds__(256) outer_end_kernel(const ST S, const cnl_outer_ctl C) {
   using T = elem_t<ST>;
   const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
   if (b >= S.B) return;
@@ -306,11 +323,28 @@ __global__ void __launch_bounds__(256) outer_end_kernel(const ST S) {
   const T sl = (T)sld;
   const T ds = S.p > 0 ? tmax(sl / (T)S.p, S.smax) / S.smax : T(1);
   const bool first_order = tmax(S.normdual[b] / ds, S.normprimal[b]) <= S.epstol[b];
-  S.it[b] += 1;
-  // tired = inner > max_inner: the reference hands that to get_status as `stalled` (src/CaNNOLeS.jl:846) -> 5; 4 (max_eval) is an
-  // evaluation-count limit, which this loop does not have
-  S.status[b] = first_order ? 1 : (S.small_res[b] ? 2 : (S.brk[b] ? 3 : (S.tired[b] ? 5 : 0)));
+  const int32_t it = S.it[b] + 1;
+  S.it[b] = it;
+  // get_status (src/CaNNOLeS.jl:836-847) in the order of outer_loop.solve: 4 (max_eval) is the evaluation count alone, 6 (max_iter) the
+  // outer-iteration count; an inner loop left at its iteration limit is `stalled` (:846) -> 5.  `tired` holds either cause of leaving
+  // the inner loop, and the evaluation count is tested first, so 5 is reached by the iteration limit only
+  const bool max_it = C.max_iter >= 0 && it > C.max_iter;
+  S.status[b] = first_order ? 1 : (S.small_res[b] ? 2 : (S.brk[b] ? 3 : (over_eval(C, b) ? 4 : (max_it ? 6 : (S.tired[b] ? 5 : 0)))));
   S.phase0[b] = 1;
+}
+
+// :Newton_vanishing (hessian_approx.jl:55-60): the residual Hessian of a problem is refreshed only while dot(Fx, Fx) > 1e-8.  One
+// workgroup per problem; the dot product by the file's reduction rule, then compared with the double literal
+template <class ST>
+__global__ void __launch_bounds__(256) outer_hess_mask_kernel(const ST S, const cnl_outer_ctl C) {
+  using T = elem_t<ST>;
+  __shared__ double sh[4];
+  const long long b = blockIdx.x;
+  const T* Fx = S.Fx + b * S.m;
+  double ssd = 0.0;
+  for (long long k = threadIdx.x; k < S.m; k += 256) ssd += (double)Fx[k] * (double)Fx[k];
+  const T ss = (T)block_sum(ssd, sh);
+  if (threadIdx.x == 0) C.hess_upd[b] = (double)ss > 1e-8;
 }
 
 // ---- compaction of the loop's state: the active problems become the first rows (cnl_outer_compact_dev) -----------------------------
@@ -436,12 +470,19 @@ int check_ls(const ST* st) {
   return 0;
 }
 int done() { return hipGetLastError() == hipSuccess ? CNL_OK : CNL_ERR_HIP; }
+// a caller's control block: its size as this library knows it, the evaluation counter, evals_per_point 1 (residual) or 2 (residual and
+// constraints); NULL stands for the plain call
+int check_ctl(const cnl_outer_ctl* ctl) {
+  if (!ctl) return 0;
+  if (ctl->struct_size != (int32_t)sizeof(cnl_outer_ctl) || !ctl->neval || (ctl->evals_per_point != 1 && ctl->evals_per_point != 2)) return CNL_ERR_ARG;
+  return 0;
+}
 
-// the nine entry points, for either state structure
-template <class ST> int begin_impl(const ST* st, void* stream) {
-  if (check(st)) return CNL_ERR_ARG;
+// the entry points, for either state structure; ctl == nullptr: the plain call
+template <class ST> int begin_impl(const ST* st, const cnl_outer_ctl* ctl, void* stream) {
+  if (check(st) || check_ctl(ctl)) return CNL_ERR_ARG;
   if (hipMemsetAsync(st->flags, 0, 8 * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return CNL_ERR_HIP;
-  hipLaunchKernelGGL(outer_begin_kernel<ST>, dim3((unsigned)((st->B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *st);
+  hipLaunchKernelGGL(outer_begin_kernel<ST>, dim3((unsigned)((st->B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *st, ctl ? *ctl : ctl_off());
   return done();
 }
 template <class ST> int newton_done_impl(const ST* st, int did_newton, void* stream) {
@@ -454,9 +495,9 @@ template <class ST> int extrapolated_impl(const ST* st, void* stream) {
   hipLaunchKernelGGL(outer_extrapolated_kernel<ST>, dim3((unsigned)st->B), dim3(256), 0, (hipStream_t)stream, *st);
   return done();
 }
-template <class ST> int trial_done_impl(const ST* st, void* stream) {
-  if (check(st)) return CNL_ERR_ARG;
-  hipLaunchKernelGGL(outer_trial_done_kernel<ST>, dim3((unsigned)st->B), dim3(256), 0, (hipStream_t)stream, *st);
+template <class ST> int trial_done_impl(const ST* st, const cnl_outer_ctl* ctl, void* stream) {
+  if (check(st) || check_ctl(ctl)) return CNL_ERR_ARG;
+  hipLaunchKernelGGL(outer_trial_done_kernel<ST>, dim3((unsigned)st->B), dim3(256), 0, (hipStream_t)stream, *st, ctl ? *ctl : ctl_off());
   return done();
 }
 template <class ST> int ls_begin_impl(const ST* st, void* stream) {
@@ -464,10 +505,10 @@ template <class ST> int ls_begin_impl(const ST* st, void* stream) {
   hipLaunchKernelGGL(outer_ls_begin_kernel<ST>, dim3((unsigned)st->B), dim3(256), 0, (hipStream_t)stream, *st);
   return done();
 }
-template <class ST> int ls_test_impl(const ST* st, int first, void* stream) {
-  if (check_ls(st)) return CNL_ERR_ARG;
+template <class ST> int ls_test_impl(const ST* st, int first, const cnl_outer_ctl* ctl, void* stream) {
+  if (check_ls(st) || check_ctl(ctl)) return CNL_ERR_ARG;
   if (hipMemsetAsync(st->flags + 6, 0, sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return CNL_ERR_HIP;
-  hipLaunchKernelGGL(outer_ls_test_kernel<ST>, dim3((unsigned)st->B), dim3(256), 0, (hipStream_t)stream, *st, first);
+  hipLaunchKernelGGL(outer_ls_test_kernel<ST>, dim3((unsigned)st->B), dim3(256), 0, (hipStream_t)stream, *st, first, ctl ? *ctl : ctl_off());
   return done();
 }
 template <class ST> int ls_step_impl(const ST* st, void* stream) {
@@ -480,9 +521,15 @@ template <class ST> int ls_take_impl(const ST* st, void* stream) {
   hipLaunchKernelGGL(outer_ls_take_kernel<ST>, dim3((unsigned)st->B), dim3(256), 0, (hipStream_t)stream, *st);
   return done();
 }
-template <class ST> int end_impl(const ST* st, void* stream) {
-  if (check(st)) return CNL_ERR_ARG;
-  hipLaunchKernelGGL(outer_end_kernel<ST>, dim3((unsigned)((st->B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *st);
+template <class ST> int end_impl(const ST* st, const cnl_outer_ctl* ctl, void* stream) {
+  if (check(st) || check_ctl(ctl)) return CNL_ERR_ARG;
+  hipLaunchKernelGGL(outer_end_kernel<ST>, dim3((unsigned)((st->B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *st, ctl ? *ctl : ctl_off());
+  return done();
+}
+// (the mask kernel has no plain form: its output array is a member of the control block)
+template <class ST> int hess_mask_impl(const ST* st, const cnl_outer_ctl* ctl, void* stream) {
+  if (check(st) || !ctl || check_ctl(ctl) || !ctl->hess_upd) return CNL_ERR_ARG;
+  hipLaunchKernelGGL(outer_hess_mask_kernel<ST>, dim3((unsigned)st->B), dim3(256), 0, (hipStream_t)stream, *st, *ctl);
   return done();
 }
 
@@ -543,30 +590,40 @@ template <class ST> int compact_impl(const ST* st, int64_t nextra, void* const* 
 
 extern "C" {
 
-int cnl_outer_begin_dev(const cnl_outer_state* st, void* stream) { return begin_impl(st, stream); }
+int cnl_outer_begin_dev(const cnl_outer_state* st, void* stream) { return begin_impl(st, nullptr, stream); }
 int cnl_outer_newton_done_dev(const cnl_outer_state* st, int did_newton, void* stream) { return newton_done_impl(st, did_newton, stream); }
 int cnl_outer_extrapolated_dev(const cnl_outer_state* st, void* stream) { return extrapolated_impl(st, stream); }
-int cnl_outer_trial_done_dev(const cnl_outer_state* st, void* stream) { return trial_done_impl(st, stream); }
+int cnl_outer_trial_done_dev(const cnl_outer_state* st, void* stream) { return trial_done_impl(st, nullptr, stream); }
 int cnl_outer_ls_begin_dev(const cnl_outer_state* st, void* stream) { return ls_begin_impl(st, stream); }
-int cnl_outer_ls_test_dev(const cnl_outer_state* st, int first, void* stream) { return ls_test_impl(st, first, stream); }
+int cnl_outer_ls_test_dev(const cnl_outer_state* st, int first, void* stream) { return ls_test_impl(st, first, nullptr, stream); }
 int cnl_outer_ls_step_dev(const cnl_outer_state* st, void* stream) { return ls_step_impl(st, stream); }
 int cnl_outer_ls_take_dev(const cnl_outer_state* st, void* stream) { return ls_take_impl(st, stream); }
-int cnl_outer_end_dev(const cnl_outer_state* st, void* stream) { return end_impl(st, stream); }
+int cnl_outer_end_dev(const cnl_outer_state* st, void* stream) { return end_impl(st, nullptr, stream); }
+int cnl_outer_begin_ex_dev(const cnl_outer_state* st, const cnl_outer_ctl* ctl, void* stream) { return begin_impl(st, ctl, stream); }
+int cnl_outer_trial_done_ex_dev(const cnl_outer_state* st, const cnl_outer_ctl* ctl, void* stream) { return trial_done_impl(st, ctl, stream); }
+int cnl_outer_ls_test_ex_dev(const cnl_outer_state* st, int first, const cnl_outer_ctl* ctl, void* stream) { return ls_test_impl(st, first, ctl, stream); }
+int cnl_outer_end_ex_dev(const cnl_outer_state* st, const cnl_outer_ctl* ctl, void* stream) { return end_impl(st, ctl, stream); }
+int cnl_outer_hess_mask_dev(const cnl_outer_state* st, const cnl_outer_ctl* ctl, void* stream) { return hess_mask_impl(st, ctl, stream); }
 
 int cnl_outer_compact_dev(const cnl_outer_state* st, int64_t nextra, void* const* d_extra, const int64_t* extra_row_bytes, int64_t min_finished,
                           int32_t* d_orig, int32_t* d_counts, int32_t* d_work, void* stream) {
   return compact_impl(st, nextra, d_extra, extra_row_bytes, min_finished, d_orig, d_counts, d_work, stream);
 }
 
-int cnl_outer_begin_f32_dev(const cnl_outer_state_f32* st, void* stream) { return begin_impl(st, stream); }
+int cnl_outer_begin_f32_dev(const cnl_outer_state_f32* st, void* stream) { return begin_impl(st, nullptr, stream); }
 int cnl_outer_newton_done_f32_dev(const cnl_outer_state_f32* st, int did_newton, void* stream) { return newton_done_impl(st, did_newton, stream); }
 int cnl_outer_extrapolated_f32_dev(const cnl_outer_state_f32* st, void* stream) { return extrapolated_impl(st, stream); }
-int cnl_outer_trial_done_f32_dev(const cnl_outer_state_f32* st, void* stream) { return trial_done_impl(st, stream); }
+int cnl_outer_trial_done_f32_dev(const cnl_outer_state_f32* st, void* stream) { return trial_done_impl(st, nullptr, stream); }
 int cnl_outer_ls_begin_f32_dev(const cnl_outer_state_f32* st, void* stream) { return ls_begin_impl(st, stream); }
-int cnl_outer_ls_test_f32_dev(const cnl_outer_state_f32* st, int first, void* stream) { return ls_test_impl(st, first, stream); }
+int cnl_outer_ls_test_f32_dev(const cnl_outer_state_f32* st, int first, void* stream) { return ls_test_impl(st, first, nullptr, stream); }
 int cnl_outer_ls_step_f32_dev(const cnl_outer_state_f32* st, void* stream) { return ls_step_impl(st, stream); }
 int cnl_outer_ls_take_f32_dev(const cnl_outer_state_f32* st, void* stream) { return ls_take_impl(st, stream); }
-int cnl_outer_end_f32_dev(const cnl_outer_state_f32* st, void* stream) { return end_impl(st, stream); }
+int cnl_outer_end_f32_dev(const cnl_outer_state_f32* st, void* stream) { return end_impl(st, nullptr, stream); }
+int cnl_outer_begin_ex_f32_dev(const cnl_outer_state_f32* st, const cnl_outer_ctl* ctl, void* stream) { return begin_impl(st, ctl, stream); }
+int cnl_outer_trial_done_ex_f32_dev(const cnl_outer_state_f32* st, const cnl_outer_ctl* ctl, void* stream) { return trial_done_impl(st, ctl, stream); }
+int cnl_outer_ls_test_ex_f32_dev(const cnl_outer_state_f32* st, int first, const cnl_outer_ctl* ctl, void* stream) { return ls_test_impl(st, first, ctl, stream); }
+int cnl_outer_end_ex_f32_dev(const cnl_outer_state_f32* st, const cnl_outer_ctl* ctl, void* stream) { return end_impl(st, ctl, stream); }
+int cnl_outer_hess_mask_f32_dev(const cnl_outer_state_f32* st, const cnl_outer_ctl* ctl, void* stream) { return hess_mask_impl(st, ctl, stream); }
 
 int cnl_outer_compact_f32_dev(const cnl_outer_state_f32* st, int64_t nextra, void* const* d_extra, const int64_t* extra_row_bytes,
                               int64_t min_finished, int32_t* d_orig, int32_t* d_counts, int32_t* d_work, void* stream) {

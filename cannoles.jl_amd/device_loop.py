@@ -181,18 +181,21 @@ class BandQuadFamily:
         return M()
 
 
-def kkt_pattern_of(fam):
+def kkt_pattern_of(fam, method="Newton"):
     """rows, cols (1-based int64) and the segment offsets, exactly as outer_loop.solve builds them from a model
-    (/root/reference/src/CaNNOLeS.jl:276-315): with constraints the H_c segment has the model's Hessian structure."""
+    (/root/reference/src/CaNNOLeS.jl:276-315): with constraints the H_c segment has the model's Hessian structure.
+    method = "Newton_noFHess" (Gauss-Newton): get_nnzh is 0 (hessian_approx.jl:12), the H_F segment is empty."""
+    from .outer_loop import check_method
+    check_method(method)
     s = fam.s
     n, m, p = s.nvar, s.nequ, s.ncon
     hr, hc = np.asarray(s.hF[0]), np.asarray(s.hF[1])
-    nnzhF, nnzhc = len(hr), (len(hr) if p > 0 else 0)
+    nnzhF, nnzhc = (0 if method == "Newton_noFHess" else len(hr)), (len(hr) if p > 0 else 0)
     jFr, jFc = np.asarray(s.jF[0]), np.asarray(s.jF[1])
     jcr, jcc = (np.asarray(s.jc[0]), np.asarray(s.jc[1])) if p else (np.zeros(0, np.int64), np.zeros(0, np.int64))
     N = n + m + p
-    rows = np.concatenate([hr, hr[:nnzhc], jFr + n, jcr + n + m, np.arange(n + 1, n + m + 1), np.arange(n + m + 1, N + 1), np.arange(1, n + 1)]).astype(np.int64)
-    cols = np.concatenate([hc, hc[:nnzhc], jFc, jcc, np.arange(n + 1, n + m + 1), np.arange(n + m + 1, N + 1), np.arange(1, n + 1)]).astype(np.int64)
+    rows = np.concatenate([hr[:nnzhF], hr[:nnzhc], jFr + n, jcr + n + m, np.arange(n + 1, n + m + 1), np.arange(n + m + 1, N + 1), np.arange(1, n + 1)]).astype(np.int64)
+    cols = np.concatenate([hc[:nnzhF], hc[:nnzhc], jFc, jcc, np.arange(n + 1, n + m + 1), np.arange(n + m + 1, N + 1), np.arange(1, n + 1)]).astype(np.int64)
     return rows, cols, (nnzhF, nnzhc, len(jFr), len(jcr))
 
 
@@ -223,9 +226,24 @@ PROFILE = False   # tools/time_device_loop.py --profile: wall time per section o
 
 
 def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=None, rtol=None, Fatol=None, Frtol=None, delta_dec=0.1,
-                       device_index=0, layout="auto", tuning=None, dtype=None, compact=False, compact_min_finished=None):
+                       device_index=0, layout="auto", tuning=None, dtype=None, compact=False, compact_min_finished=None, method="Newton",
+                       x=None, lam=None, use_initial_multiplier=False, max_iter=-1, max_eval=100000, max_time=None,
+                       always_accept_extrapolation=False):
     """All B problems of `fam` in lockstep on the device.  Returns a dict of numpy arrays: solution [B, n], multipliers,
-    status (list of strings), iter, nfact, nlinsolve, nbk, objective, and `steps` (global steps = batched Newton rounds).
+    status (list of strings), iter, nfact, nlinsolve, nbk, neval, objective, and `steps` (global steps = batched Newton rounds).
+
+    The keywords of the reference's `solve!` (src/CaNNOLeS.jl:418-437) and of its solver constructor (:228-271):
+      method   "Newton"; "Newton_noFHess" (Gauss-Newton: no H_F segment in the pattern, `fam.hess_vals` is never called and need not
+               exist); "Newton_vanishing" (a problem's H_F values are refreshed only while dot(Fx, Fx) > 1e-8, cnl_outer_hess_mask_dev;
+               the result reports `hess_skipped`, the skipped refreshes per problem).  "LM" and unknown names raise ValueError.
+      x        [B, n] start points (default: the family's x0);  lam [B, p] with use_initial_multiplier = True: the start multipliers
+               instead of the least-squares estimate (:512-518)
+      max_iter, max_eval   per problem, < 0: no limit; statuses `max_iter`, `max_eval`.  `neval` counts what the problem's
+               single-problem run evaluates: residual (and constraints, when p > 0) at the start point, at every extrapolation trial point
+               and at every line-search candidate — not the evaluations this loop makes on rows that did not need them
+      max_time seconds of wall clock for the WHOLE batch (None: no limit), looked at once per global step: the problems still active then
+               end with status `max_time`
+      always_accept_extrapolation   (:627, :735)
 
     compact=True: a global step runs on the ACTIVE problems only.  Behind every step cnl_outer_compact_dev moves the active problems to
     the front of every per-problem array (the state, a working copy of the family's data, the row -> problem map), once at least
@@ -258,8 +276,13 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     n, m, p = s.nvar, s.nequ, s.ncon
     N = n + m + p
     P = max(p, 1)
-    rows, cols, (nnzhF, nnzhc, nnzjF, nnzjc) = kkt_pattern_of(fam)
+    rows, cols, (nnzhF, nnzhc, nnzjF, nnzjc) = kkt_pattern_of(fam, method)   # (refuses "LM" and unknown names)
     nnz = len(rows)
+    vanishing = method == "Newton_vanishing"
+    max_iter, max_eval = int(max_iter), int(max_eval)
+    epp = 2 if p > 0 else 1   # evaluations per point: residual, and constraints when there are any (eval_fun, :559)
+    import time as _time
+    t_start = _time.perf_counter()
     # tuning: further hipldl.Options fields for the handle — e.g. {"band_pieces": 20}: a constrained family's pattern (H_c as wide as H_F)
     # on the wide band kernels, which a Float64 handle takes on request only
     tuning = dict(tuning or {})
@@ -337,7 +360,12 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     cnorm2 = lambda c_: fsqrt(rdot(c_, c_)) if p else Z(B)
 
     # ---- state (every array is updated IN PLACE from here on: the kernels hold its address) -------------------------
-    x = fam.d["x0"].clone()
+    if x is None:
+        x = fam.d["x0"].clone()
+    else:
+        x = t.as_tensor(np.ascontiguousarray(x, dtype=dt), **f64).clone()
+        if tuple(x.shape) != (B, n):
+            raise ValueError(f"x: [{B}, {n}] start points expected, got {tuple(x.shape)}")
     Fx = fam.residual(x).contiguous()
     fx = (0.5 * rdot(Fx, Fx)).contiguous()
     Jv = fam.jac_vals(x).contiguous()
@@ -347,7 +375,14 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     cx = fam.cons(x).contiguous()
     r = Fx.clone()
     delta = t.ones(B, **f64)
-    lam = multipliers(Jv, Jcv, r, True)
+    if use_initial_multiplier:   # :512-518: no least-squares estimate, no ones-if-zero rule
+        lam0 = np.zeros((B, p), dt) if lam is None else np.ascontiguousarray(lam, dtype=dt)
+        if lam0.shape != (B, p):
+            raise ValueError(f"lam: [{B}, {p}] start multipliers expected, got {lam0.shape}")
+        lam = Z(B, P)
+        lam[:, :p] = t.as_tensor(lam0, **f64)
+    else:
+        lam = multipliers(Jv, Jcv, r, True)
     rhs_cur, nrm0 = Z(B, N), Z(B, 2)
     resid_vectors(Jv, Jcv, r, lam, Fx, cx, rhs_cur, nrm0)
     normdual, normprimal = nrm0[:, 0].clone(), nrm0[:, 1].clone()
@@ -377,12 +412,18 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     if bool(chk0.any()):
         small_res_check(chk0)
         first_order = t.maximum(normdual / dual_scaling(lam), normprimal) <= epstol
-    UNKNOWN, FIRST, SMALL, EXC, TIRED, STALL = 0, 1, 2, 3, 4, 5
-    status = t.where(first_order, FIRST, t.where(small_residual, SMALL, UNKNOWN)).to(t.int32).contiguous()
+    UNKNOWN, FIRST, SMALL, EXC, TIRED, STALL, MAX_ITER, MAX_TIME = 0, 1, 2, 3, 4, 5, 6, 7
+    # the evaluation at the start point; `tired` (:559) may hold already with a tiny limit.  (it = 0 never exceeds a max_iter >= 0)
+    neval = t.full((B,), epp, dtype=t.int64, device=dev)
+    start_rest = TIRED if 0 <= max_eval < epp else UNKNOWN
+    status = t.where(first_order, FIRST, t.where(small_residual, SMALL, start_rest)).to(t.int32).contiguous()
     eta = t.full((B,), 1.0 if p else 0.0, **f64)
     epsk = t.full((B,), 1e3, **f64)
     rho_old = Z(B)
     it, inner = ZI(t.int32, B), ZI(t.int64, B)
+    # :Newton_vanishing: the H_F values each problem's system holds (zero until its first refresh), this step's refresh mask, the skips
+    hess_upd = t.zeros(B, dtype=t.bool, device=dev)
+    hF_cur, hess_skipped = (Z(B, nnzhF), ZI(t.int64, B)) if vanishing else (None, None)
     nfact, nlin, nbk = ZI(t.int64, B), ZI(t.int64, B), ZI(t.int64, B)
     phase0 = t.ones(B, dtype=t.bool, device=dev)
     combined, combined_hat = Z(B), Z(B)
@@ -415,18 +456,19 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
         assert v.is_contiguous(), k
         setattr(S, k, v.data_ptr())
     Sref = C.byref(S)
+    ctl = hipldl.outer_ctl(neval.data_ptr(), epp, always_accept_extrapolation, max_iter, max_eval, hess_upd.data_ptr())
+    Cref = C.byref(ctl)
     chk_ = hipldl._check
     sfx = "_f32_dev" if f32 else "_dev"
-    k_begin, k_newton_done, k_extrapolated, k_trial_done, k_end, k_ls_begin, k_ls_test, k_ls_step, k_ls_take = (
-        getattr(lib, "cnl_outer_" + k + sfx) for k in ("begin", "newton_done", "extrapolated", "trial_done", "end", "ls_begin", "ls_test", "ls_step",
-                                                       "ls_take"))
+    k_begin, k_newton_done, k_extrapolated, k_trial_done, k_end, k_ls_begin, k_ls_test, k_ls_step, k_ls_take, k_hess_mask = (
+        getattr(lib, "cnl_outer_" + k + sfx) for k in ("begin_ex", "newton_done", "extrapolated", "trial_done_ex", "end_ex", "ls_begin", "ls_test_ex",
+                                                       "ls_step", "ls_take", "hess_mask"))
 
     def read_flags():
         flags_h.copy_(flags_counts, non_blocking=True)
         t.cuda.current_stream(dev).synchronize()
         return flags_h.tolist()
 
-    import time as _time
     prof = {} if PROFILE else None
 
     def tick(name, t0):
@@ -444,6 +486,9 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
         wf.d = {k: v.clone() for k, v in fam.per_problem_tensors().items()}
         fw = wf
         extras = [(v.data_ptr(), v.shape[1] * v.element_size()) for v in wf.d.values() if v.shape[1] > 0]
+        extras.append((neval.data_ptr(), 8))   # (per-problem arrays of the control block and of :Newton_vanishing move with the state)
+        if vanishing:
+            extras += [(hF_cur.data_ptr(), nnzhF * hF_cur.element_size()), (hess_skipped.data_ptr(), 8)]
         assert all(v.is_contiguous() and v.shape[0] == B for v in wf.d.values())
         orig = t.arange(B, dtype=t.int32, device=dev)
         pair_work = ZI(t.int32, B + 2)
@@ -454,7 +499,7 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     # cnl_outer_trial_done_dev, and one per round of backtracking when a line search runs
     while steps < max_steps:
         tk = _time.perf_counter()
-        chk_(k_begin(Sref, st))   # (behind a compaction still over the rows of the step before: the ones that left are finished)
+        chk_(k_begin(Sref, Cref, st))   # (behind a compaction still over the rows of the step before: the ones that left are finished)
         fl = read_flags()
         any_act, any_need, any_ext, any_ls = fl[:4]
         if not any_act:
@@ -478,7 +523,16 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
         tk = tick("begin", tk)
         # ---- Newton step (skipped on the iteration right after a rejected extrapolation), :627-652
         if any_need:
-            prepare(vals_cur, fw.hess_vals(hd(x), hd(r)), Jv, Jcv, delta)
+            if nnzhF == 0:          # Gauss-Newton: no H_F segment, no Hessian callback
+                prepare(vals_cur, None, Jv, Jcv, delta)
+            elif vanishing:         # the problems due a system refresh their H_F values where dot(Fx, Fx) > 1e-8 and keep them otherwise
+                chk_(k_hess_mask(Sref, Cref, st))
+                due = hd(masks["need"])
+                hd(hF_cur).copy_(t.where((due & hd(hess_upd))[:, None], fw.hess_vals(hd(x), hd(r)), hd(hF_cur)))
+                hd(hess_skipped).add_((due & ~hd(hess_upd)).to(t.int64))
+                prepare(vals_cur, hF_cur, Jv, Jcv, delta)
+            else:
+                prepare(vals_cur, fw.hess_vals(hd(x), hd(r)), Jv, Jcv, delta)
             hd(ro_tmp).copy_(hd(rho_old))
             hipldl.newton_system_dev(L, ptr(vals_cur), ptr(rhs_cur), ptr(d_new), ptr(ro_tmp), ptr(rho_new), ptr(nf_new), ptr(ok_new), params, st)
         chk_(k_newton_done(Sref, 1 if any_need else 0, st))
@@ -496,12 +550,12 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
             chk_(k_ls_begin(Sref, st))
             hd(Fl).copy_(fw.residual(hd(xl)))
             hd(cl).copy_(fw.cons(hd(xl)))
-            chk_(k_ls_test(Sref, 1, st))
+            chk_(k_ls_test(Sref, 1, Cref, st))
             while read_flags()[6]:
                 chk_(k_ls_step(Sref, st))
                 hd(Fl).copy_(fw.residual(hd(xl)))       # (rows of problems that do not backtrack are recomputed from an unchanged xl: same values)
                 hd(cl).copy_(fw.cons(hd(xl)))
-                chk_(k_ls_test(Sref, 0, st))
+                chk_(k_ls_test(Sref, 0, Cref, st))
             chk_(k_ls_take(Sref, st))
         tk = tick("line_search", tk)
         hd(Ft).copy_(fw.residual(hd(xt)))
@@ -510,7 +564,7 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
         hd(Jt).copy_(fw.jac_vals(hd(xt)))
         resid_vectors(Jt, Jcv, rt, lamt, Ft, ct, rhs_t, nrm_t)
         tk = tick("trial_eval", tk)
-        chk_(k_trial_done(Sref, st))
+        chk_(k_trial_done(Sref, Cref, st))
         any_rej, any_chk = read_flags()[4:6]
         tk = tick("trial_done", tk)
         if any_rej:   # dual at (x, r, lam) again; primal keeps the trial's value, as in the reference (:742-747)
@@ -518,7 +572,10 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
             hd(rhs_cur)[:, :n] = t.where(hd(masks["rej"])[:, None], hd(rv_rhs)[:, :n], hd(rhs_cur)[:, :n])
         if any_chk:
             small_res_check(masks["chk"])
-        chk_(k_end(Sref, st))
+        chk_(k_end(Sref, Cref, st))
+        if max_time is not None and _time.perf_counter() - t_start > max_time:
+            status.masked_fill_(status == UNKNOWN, MAX_TIME)   # (the clock is the caller's: code 7 is never written by a kernel)
+            break
         if compact and nb > 1:
             # the problems that just finished leave the working rows (once enough of them have); the counts come back with the next
             # step's flags
@@ -528,7 +585,7 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
         tk = tick("rej_chk_end", tk)
     t.cuda.synchronize(dev)
     loop_seconds = _time.perf_counter() - t_loop0
-    names = {UNKNOWN: "unknown", FIRST: "first_order", SMALL: "small_residual", EXC: "exception", TIRED: "max_eval", STALL: "stalled"}
+    names = hipldl.OUTER_STATUS_NAMES
     if compact:   # row b of every array holds problem orig[b]: back to the original order
         where = orig.cpu().numpy().astype(np.int64)
         assert np.array_equal(np.sort(where), np.arange(B))
@@ -541,10 +598,12 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     else:
         host = lambda a: a.cpu().numpy()
     out = {"solution": host(x), "multipliers": host(lam[:, :p]), "status": [names[int(v)] for v in host(status)],
-           "iter": host(it), "nfact": host(nfact), "nlinsolve": host(nlin), "nbk": host(nbk),
+           "iter": host(it), "nfact": host(nfact), "nlinsolve": host(nlin), "nbk": host(nbk), "neval": host(neval),
            "objective": host(fx), "dtype": str(dt), "r": host(r), "normdual": host(normdual),
            "normprimal": host(normprimal), "epstol": host(epstol), "steps": steps, "kernel": "band" if L.config.get("band") else L.config["kernel"], "vals_layout": "interleaved" if L.config.get("batch_layout") else "problem-major",
            "loop_seconds": loop_seconds}   # the global steps alone (the symbolic analysis of the pattern and the start-up evaluations are not in it)
+    if vanishing:
+        out["hess_skipped"] = host(hess_skipped)
     if compact:
         out.update(compactions=compactions, problem_steps=problem_steps, handle_shrunk=handle_shrunk)
     if prof is not None:

@@ -50,7 +50,14 @@ ABI_SYMBOLS = [
     "cnl_outer_begin_f32_dev", "cnl_outer_newton_done_f32_dev", "cnl_outer_extrapolated_f32_dev", "cnl_outer_trial_done_f32_dev",
     "cnl_outer_end_f32_dev", "cnl_outer_ls_begin_f32_dev", "cnl_outer_ls_test_f32_dev", "cnl_outer_ls_step_f32_dev", "cnl_outer_ls_take_f32_dev",
     "cnl_set_active_batch", "cnl_get_active_batch", "cnl_outer_compact_dev", "cnl_outer_compact_f32_dev",
+    "cnl_outer_begin_ex_dev", "cnl_outer_trial_done_ex_dev", "cnl_outer_ls_test_ex_dev", "cnl_outer_end_ex_dev", "cnl_outer_hess_mask_dev",
+    "cnl_outer_begin_ex_f32_dev", "cnl_outer_trial_done_ex_f32_dev", "cnl_outer_ls_test_ex_f32_dev", "cnl_outer_end_ex_f32_dev",
+    "cnl_outer_hess_mask_f32_dev",
 ]
+
+# status codes of the lockstep loop's `status` array (include/cannoles_hip.h, row f3); 7 is set by the caller, never by a kernel
+OUTER_STATUS_NAMES = {0: "unknown", 1: "first_order", 2: "small_residual", 3: "exception", 4: "max_eval", 5: "stalled", 6: "max_iter",
+                      7: "max_time"}
 
 
 PLAN_AUTO, PLAN_THROUGHPUT, PLAN_LATENCY = 0, 1, 2
@@ -115,6 +122,18 @@ class cnl_outer_state_f32(C.Structure):
                     "xt_e", "rt_e", "lamt_e")] +
                 [(k, C.c_float) for k in ("gammaA", "eps2")] +
                 [(k, C.c_void_p) for k in ("ls_g", "xl", "Fl", "cl", "lam_ls", "alpha", "Dphi", "phix", "eta", "nbk", "bt")])
+
+
+class cnl_outer_ctl(C.Structure):
+    """struct cnl_outer_ctl of include/cannoles_hip.h: the control block of the cnl_outer_*_ex_dev entry points, either element type"""
+    _fields_ = [("struct_size", C.c_int32), ("always_accept_extrapolation", C.c_int32), ("max_iter", C.c_int64), ("max_eval", C.c_int64),
+                ("evals_per_point", C.c_int64), ("neval", C.c_void_p), ("hess_upd", C.c_void_p)]
+
+
+def outer_ctl(neval, evals_per_point, always_accept_extrapolation=False, max_iter=-1, max_eval=-1, hess_upd=None):
+    """a filled cnl_outer_ctl; neval / hess_upd are device addresses (int64 [B], uint8 [B])"""
+    return cnl_outer_ctl(C.sizeof(cnl_outer_ctl), int(bool(always_accept_extrapolation)), int(max_iter), int(max_eval), int(evals_per_point),
+                         neval, hess_upd)
 
 
 def Options(**kw):
@@ -275,6 +294,9 @@ def lib():
         for sfx in ("_dev", "_f32_dev"):
             getattr(L, "cnl_outer_newton_done" + sfx).argtypes = [vp, C.c_int, vp]
             getattr(L, "cnl_outer_ls_test" + sfx).argtypes = [vp, C.c_int, vp]
+            for k in ("begin_ex", "trial_done_ex", "end_ex", "hess_mask"):
+                getattr(L, "cnl_outer_" + k + sfx).argtypes = [vp, vp, vp]
+            getattr(L, "cnl_outer_ls_test_ex" + sfx).argtypes = [vp, C.c_int, vp, vp]
         L.cnl_set_active_batch.argtypes = [vp, i64]
         L.cnl_get_active_batch.argtypes = [vp, C.POINTER(i64)]
         for fn in ("cnl_outer_compact_dev", "cnl_outer_compact_f32_dev"):

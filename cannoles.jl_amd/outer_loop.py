@@ -44,12 +44,28 @@ def cgls(A, b, atol=None, rtol=None, itmax=0):
         it += 1
     return x
 
+METHODS = ("Newton", "Newton_noFHess", "Newton_vanishing")
+
+
+def check_method(method):
+    """the reference's `method` keyword (src/CaNNOLeS.jl:228-271) as this project runs it: :LM is a name the reference accepts but has
+    no prepare_newton_system! for (:922-940 is a comment), so it is refused here, like any unknown name"""
+    if method == "LM":
+        raise ValueError("method LM: the reference has no prepare_newton_system! method for it (src/CaNNOLeS.jl:922-940)")
+    if method not in METHODS:
+        raise ValueError(f"method {method!r}: one of {', '.join(METHODS)}")
+
+
 def solve(nls, make_solver, newton_system, params, method="Newton", x=None, lam=None, max_iter=-1, max_eval=100000,
           max_inner=10000, atol=None, rtol=None, Fatol=None, Frtol=None, always_accept_extrapolation=False,
-          delta_dec=0.1):
+          delta_dec=0.1, use_initial_multiplier=False):
     """src/CaNNOLeS.jl:418-864.  `make_solver(N, rows, cols, vals, nvar, nequ, ncon)` builds the linear-solver
     object (LinearSolverStruct); `newton_system(LDLT, nvar, nequ, ncon, rhs, vals, rho_old, params)` returns
-    (d, solve_success, rho, rho_old, nfact).  Returns a dict with solution, status, iter, nfact, nlinsolve."""
+    (d, solve_success, rho, rho_old, nfact).  Returns a dict with solution, status, iter, nfact, nlinsolve.
+    method = "Newton_vanishing": the H_F values are refreshed only while dot(Fx, Fx) > 1e-8 (hessian_approx.jl:55-60) and start at
+    zero (the reference's `vals` is undef there); `hess_skipped` counts the skipped refreshes.  use_initial_multiplier: `lam` is
+    the start multiplier instead of the least-squares estimate and its ones-if-zero rule (:512-518)."""
+    check_method(method)
     eps = np.finfo(float).eps
     atol = np.sqrt(eps) if atol is None else atol
     rtol = np.sqrt(eps) if rtol is None else rtol
@@ -73,6 +89,9 @@ def solve(nls, make_solver, newton_system, params, method="Newton", x=None, lam=
     o_d = o_I + m
     o_rho = o_d + p
     vals[o_I:o_d] = -1.0
+    if method == "Newton_vanishing":
+        vals[:nnzhF] = 0.0
+    hess_skipped = 0
     LDLT = make_solver(N, rows, cols, vals, n, m, p)
 
     x = nls.x0.copy() if x is None else np.asarray(x, float).copy()
@@ -92,9 +111,10 @@ def solve(nls, make_solver, newton_system, params, method="Newton", x=None, lam=
     def ls_multipliers(rhs_vec):  # krylov_solve!(cgls_workspace, Jcx', Jxtr): min || Jcx' lam - rhs || (src/CaNNOLeS.jl:512-518)
         return cgls(Jcx.T, rhs_vec) if p else np.zeros(0)
 
-    lam = ls_multipliers(Jxtr)
-    if p and np.linalg.norm(lam) == 0:
-        lam[:] = 1.0
+    if not use_initial_multiplier:
+        lam = ls_multipliers(Jxtr)
+        if p and np.linalg.norm(lam) == 0:
+            lam[:] = 1.0
     dual = Jxtr - Jcx.T @ lam
     primal = np.concatenate([Fx - r, cx])
     normdual = np.linalg.norm(dual, np.inf)
@@ -159,7 +179,10 @@ def solve(nls, make_solver, newton_system, params, method="Newton", x=None, lam=
             if inner != 1 or always_accept_extrapolation:
                 # prepare_newton_system!, src/CaNNOLeS.jl:947-981
                 if use_hF:
-                    vals[:nnzhF] = nls.hess_coord_residual(x, r)
+                    if method == "Newton_vanishing" and not Fx @ Fx > 1e-8:
+                        hess_skipped += 1
+                    else:
+                        vals[:nnzhF] = nls.hess_coord_residual(x, r)
                 vals[o_jF:o_jc] = Jx[nls.jF_rows - 1, nls.jF_cols - 1]
                 if p > 0:
                     vals[nnzhF:o_jF] = -nls.hess_coord_cons(x, lam)
@@ -239,4 +262,4 @@ def solve(nls, make_solver, newton_system, params, method="Newton", x=None, lam=
         if st == "unknown" and inner > max_inner >= 0:
             st = "stalled"
     return {"solution": x, "multipliers": lam, "status": st, "iter": it, "nfact": nfact, "nlinsolve": nlinsolve,
-            "nbk": nbk, "objective": fx}
+            "nbk": nbk, "objective": fx, "hess_skipped": hess_skipped}

@@ -58,7 +58,7 @@ typedef struct cnl_handle cnl_handle; /* plan + device state for one batch      
 
 const char* cnl_last_error(void);
 /* library / ABI version: major*10000 + minor*100 + patch (0.3.0: cnl_set_active_batch, cnl_outer_compact_dev;
- * 0.3.1: tuning "float32_general", no new symbol) */
+ * 0.3.1: tuning "float32_general", no new symbol; 0.4.0: cnl_outer_ctl, the cnl_outer_*_ex_dev entry points, cnl_outer_hess_mask_dev) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -296,7 +296,11 @@ int cnl_multi_synchronize(cnl_multi* m, void* const* streams);
  * arrays in HBM and every branch as a per-problem mask (cannoles.jl_amd/device_loop.py).  The four entry points below do the
  * masks and the masked state updates of one global step IN PLACE on that state, one launch each (the reference's tests in the
  * reference's operation order; minimum / maximum propagate NaN).  `cnl_outer_state` is plain device pointers and sizes; every
- * array is problem-major.  Status codes: 0 unknown (active), 1 first_order, 2 small_residual, 3 exception, 4 max_eval (never produced: this loop has no evaluation counter), 5 stalled (inner > max_inner, src/CaNNOLeS.jl:846).  The entry points
+ * array is problem-major.  Status codes: 0 unknown (active), 1 first_order, 2 small_residual, 3 exception,
+ * 4 max_eval (the evaluation count neval > max_eval; produced by cnl_outer_end_ex_dev only: the plain calls have no evaluation counter),
+ * 5 stalled (inner > max_inner, src/CaNNOLeS.jl:846), 6 max_iter (outer iterations > max_iter; cnl_outer_end_ex_dev only), 7 max_time
+ * (never written by a kernel: reserved for the caller, who owns the clock and sets it in `status` for the problems still active).  Where
+ * several causes hold at once the lowest of 1, 2, 3, 4, 6, 5 in that order is reported (get_status, :836-847).  The entry points
  * take no handle: they launch on the calling thread's CURRENT device, which must be the one the arrays live on, and are asynchronous on
  * `stream`; they return CNL_ERR_ARG for a null state / missing array and CNL_ERR_HIP when the launch fails.  Every array is required
  * — the multiplier / constraint arrays lam, cx, ct, lamt, lamt_e (cl, lam_ls for the line search) have rows of P = max(p, 1) entries and
@@ -310,7 +314,9 @@ int cnl_multi_synchronize(cnl_multi* m, void* const* streams);
  *                                        acceptance, x / r / Fx / cx / Jv / Jcv / lam / rhs_cur / fx / delta / inner updates, end-of-
  *                                        inner-loop tests; rej, chk, done_in; flags[4] = any rejected, flags[5] = any small-residual check
  *   cnl_outer_end_dev          :800-857  statuses, outer-iteration counters, phase0
- *   cnl_outer_compact_dev      (no counterpart: one problem has no batch) the active problems to the front of every array, below       */
+ *   cnl_outer_compact_dev      (no counterpart: one problem has no batch) the active problems to the front of every array, below
+ * The keywords of `solve!` beyond max_inner and the tolerances (:418-437) come through a control block, `cnl_outer_ctl` below, and the
+ * `_ex` twins of begin / trial_done / ls_test / end; cnl_outer_hess_mask_dev serves method = :Newton_vanishing.                       */
 typedef struct cnl_outer_state {
   int64_t B, n, m, p, P /* max(p, 1): row length of lam, cx, ct, lamt */, N, nnzjF, nnzjc, max_inner;
   double dmin, rhomax, delta_dec, smax;
@@ -341,6 +347,36 @@ int cnl_outer_ls_test_dev(const cnl_outer_state* st, int first, void* stream);
 int cnl_outer_ls_step_dev(const cnl_outer_state* st, void* stream);
 int cnl_outer_ls_take_dev(const cnl_outer_state* st, void* stream);
 int cnl_outer_end_dev(const cnl_outer_state* st, void* stream);
+/* Control block of the `_ex` entry points: the keywords always_accept_extrapolation, max_iter and max_eval of `solve!` (:418-437).
+ * Integers only, so one structure serves both element types.  neval[b] is the number of model evaluations problem b has made, as its
+ * single-problem run counts them: the caller sets it to evals_per_point for the evaluation at the start point, and the kernels add
+ * evals_per_point for every point they know was evaluated for the problem — the extrapolation's trial point (trial_done_ex, the problems
+ * of `ext`) and each candidate of the line search (ls_test_ex: the problems of `lsm` when first != 0, else those of `bt`).  Evaluations
+ * a batched caller makes for its own convenience on rows that did not need them are not the problem's and are not counted.
+ *   cnl_outer_begin_ex_dev       need = act && (inner != 1 || always_accept_extrapolation)                                   (:627)
+ *   cnl_outer_trial_done_ex_dev  the state is accepted where act && (inner > 0 || always_accept_extrapolation || good)       (:735);
+ *                                neval += evals_per_point where ext; tired = inner > max_inner || (max_eval >= 0 && neval > max_eval)
+ *   cnl_outer_ls_test_ex_dev     neval += evals_per_point for every candidate of the call
+ *   cnl_outer_end_ex_dev         statuses 4 (max_eval >= 0 && neval > max_eval) and 6 (max_iter >= 0 && it > max_iter, `it` already
+ *                                incremented) in the chain 1, 2, 3, 4, 6, 5
+ *   cnl_outer_hess_mask_dev      hess_upd[b] = dot(Fx_b, Fx_b) > 1e-8 (hessian_approx.jl:55-60; the dot product accumulated in double,
+ *                                rounded to the element type once, compared with the double literal); one workgroup per problem
+ * ctl == NULL: exactly the plain call (cnl_outer_hess_mask_dev needs a block).  CNL_ERR_ARG with nothing launched for a struct_size other
+ * than sizeof(cnl_outer_ctl), a null neval, evals_per_point outside {1, 2}, and for cnl_outer_hess_mask_dev a null hess_upd.           */
+typedef struct cnl_outer_ctl {
+  int32_t struct_size;                   /* sizeof(cnl_outer_ctl) */
+  int32_t always_accept_extrapolation;   /* :627, :735 */
+  int64_t max_iter;                      /* < 0: no limit */
+  int64_t max_eval;                      /* < 0: no limit */
+  int64_t evals_per_point;               /* 1, or 2 when p > 0: residual + constraints (eval_fun, :559) */
+  int64_t* neval;                        /* [B] device: evaluations per problem, updated in place */
+  uint8_t* hess_upd;                     /* [B] device, optional: out of cnl_outer_hess_mask*_dev */
+} cnl_outer_ctl;
+int cnl_outer_begin_ex_dev(const cnl_outer_state* st, const cnl_outer_ctl* ctl, void* stream);
+int cnl_outer_trial_done_ex_dev(const cnl_outer_state* st, const cnl_outer_ctl* ctl, void* stream);
+int cnl_outer_ls_test_ex_dev(const cnl_outer_state* st, int first, const cnl_outer_ctl* ctl, void* stream);
+int cnl_outer_end_ex_dev(const cnl_outer_state* st, const cnl_outer_ctl* ctl, void* stream);
+int cnl_outer_hess_mask_dev(const cnl_outer_state* st, const cnl_outer_ctl* ctl, void* stream);
 /* cnl_outer_compact_dev: the active problems (status == 0) become the first rows of the state, so that the caller can go on with
  * st->B = their number (and cnl_set_active_batch on its handle) instead of running every kernel of a step over finished problems.
  * Like its siblings: no handle, the current device, asynchronous on `stream`, CNL_ERR_ARG with nothing launched for a null state,
@@ -512,6 +548,12 @@ int cnl_outer_ls_test_f32_dev(const cnl_outer_state_f32* st, int first, void* st
 int cnl_outer_ls_step_f32_dev(const cnl_outer_state_f32* st, void* stream);
 int cnl_outer_ls_take_f32_dev(const cnl_outer_state_f32* st, void* stream);
 int cnl_outer_end_f32_dev(const cnl_outer_state_f32* st, void* stream);
+/* the `_ex` entry points and the mask kernel on a Float32 state; the control block is the same structure */
+int cnl_outer_begin_ex_f32_dev(const cnl_outer_state_f32* st, const cnl_outer_ctl* ctl, void* stream);
+int cnl_outer_trial_done_ex_f32_dev(const cnl_outer_state_f32* st, const cnl_outer_ctl* ctl, void* stream);
+int cnl_outer_ls_test_ex_f32_dev(const cnl_outer_state_f32* st, int first, const cnl_outer_ctl* ctl, void* stream);
+int cnl_outer_end_ex_f32_dev(const cnl_outer_state_f32* st, const cnl_outer_ctl* ctl, void* stream);
+int cnl_outer_hess_mask_f32_dev(const cnl_outer_state_f32* st, const cnl_outer_ctl* ctl, void* stream);
 int cnl_outer_compact_f32_dev(const cnl_outer_state_f32* st, int64_t nextra, void* const* d_extra, const int64_t* extra_row_bytes,
                               int64_t min_finished, int32_t* d_orig, int32_t* d_counts, int32_t* d_work, void* stream);
 

@@ -6,7 +6,8 @@
   --compact                 run every global step on the active problems only (solve_batch_device(compact=True)); the record then also
                             holds compactions, problem_steps and its share of steps * B, handle_shrunk
   --min-finished K          compact_min_finished (default: the loop's own, max(32, working batch // 8))
-  --no-host-loop            skip the single-problem host loop with the CPU oracle"""
+  --no-host-loop            skip the single-problem host loop with the CPU oracle
+  --method NAME             Newton (default), Newton_noFHess or Newton_vanishing (the latter adds cnl_outer_hess_mask_dev to every step)"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,12 +25,15 @@ def main():
     ap.add_argument("--compact", action="store_true")
     ap.add_argument("--min-finished", type=int, default=None)
     ap.add_argument("--no-host-loop", action="store_true")
+    ap.add_argument("--method", default="Newton")
     args = ap.parse_args()
     dtype = np.dtype(args.dtype)
     shapes = [tuple(int(v) for v in sh.split(",")) for sh in args.shape] if args.shape else \
         [(300, 4, 256), (300, 4, 2048), (300, 4, 8192), (2000, 10, 1024), (1000, 10, 16384)]
     out = []
     kw = dict(compact=True, compact_min_finished=args.min_finished) if args.compact else {}
+    if args.method != "Newton":
+        kw["method"] = args.method
     for (n, p, B) in shapes:
         s = syn.band_structure(n, p)
         fam = DL.BandQuadFamily(s, B, seed=7, torch=torch, device="cuda:0", curvature=1.5, start=1.0, noise=0.5, dtype=dtype)
@@ -44,7 +48,7 @@ def main():
         dt = time.perf_counter() - t0
         rec = {"n": n, "p": p, "B": B, "dtype": got["dtype"], "seconds": dt, "problems_per_s": B / dt, "steps": got["steps"], "ms_per_step": 1e3 * got["loop_seconds"] / got["steps"], "setup_seconds": dt - got["loop_seconds"],
                "newton_systems": int(got["nlinsolve"].sum()), "factorisations": int(got["nfact"].sum()),
-               "first_order": sum(st == "first_order" for st in got["status"]), "kernel": got["kernel"], "vals_layout": got.get("vals_layout")}
+               "first_order": sum(st == "first_order" for st in got["status"]), "kernel": got["kernel"], "vals_layout": got.get("vals_layout"), "method": args.method}
         if args.compact:
             rec.update(compact=True, compact_min_finished=args.min_finished, compactions=got["compactions"], problem_steps=got["problem_steps"],
                        problem_step_share=got["problem_steps"] / (got["steps"] * B), handle_shrunk=got["handle_shrunk"])
