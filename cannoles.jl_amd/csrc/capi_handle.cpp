@@ -461,6 +461,87 @@ int upload_dev_plan(cnl_handle* h) {
   return CNL_OK;
 }
 
+// the device copy of the condensation lists (kernels.h: DevCond) and the per-problem inertia counts of the condensed pivots, either
+// element type: index data only.  (d_cbuf / d_d2 — the condensed buffer and the reduced solution of the stand-alone condensation
+// passes — are allocated by the creators, in their element type.)
+int upload_dev_cond(cnl_handle* h) {
+  const cnl_plan* plan = h->plan;
+  const cnl::Cond& C = plan->C;
+  const int64_t N = plan->N, nnz = plan->nnz, nvar = plan->nvar, batch = h->full_batch;
+  int rc;
+  cnl::DevCond& dc = h->dc;
+  std::vector<int32_t> cidx(N, -1);
+  for (size_t q = 0; q < C.r_orig.size(); q++) cidx[C.r_orig[q]] = (int32_t)q;
+  if ((rc = upload(h, C.c_ptr, &dc.c_ptr))) return rc;
+  if ((rc = upload(h, C.c_a, &dc.c_a))) return rc;
+  if ((rc = upload(h, C.c_b, &dc.c_b))) return rc;
+  if ((rc = upload(h, C.c_d, &dc.c_d))) return rc;
+  if ((rc = upload(h, C.c_order, &dc.c_order))) return rc;
+  if ((rc = upload(h, C.ch_slot, &dc.ch_slot))) return rc;
+  if ((rc = upload(h, C.ch_rng, &dc.ch_rng))) return rc;
+  if ((rc = upload(h, C.ch_tile, &dc.ch_tile))) return rc;
+  if ((rc = upload(h, C.rng_start, &dc.rng_start))) return rc;
+  if ((rc = upload(h, C.rng_len, &dc.rng_len))) return rc;
+  if ((rc = upload(h, C.c_la, &dc.c_la))) return rc;
+  if ((rc = upload(h, C.c_lb, &dc.c_lb))) return rc;
+  if ((rc = upload(h, C.c_ld, &dc.c_ld))) return rc;
+  if ((rc = upload(h, C.ch_tptr, &dc.ch_tptr))) return rc;
+  if ((rc = upload(h, C.tile_src, &dc.tile_src))) return rc;
+  if ((rc = upload(h, C.c_pack, &dc.c_pack))) return rc;
+  dc.tile_max = C.tile_max; dc.chunk_ncon_max = C.chunk_ncon_max; dc.chunk_nslot_max = C.chunk_nslot_max; dc.tiled_ok = C.tiled_ok ? 1 : 0;
+  if ((rc = upload(h, C.r_dsrc, &dc.r_dsrc))) return rc;
+  if ((rc = upload(h, C.r_ptr, &dc.r_ptr))) return rc;
+  if ((rc = upload(h, C.r_jsrc, &dc.r_jsrc))) return rc;
+  if ((rc = upload(h, C.r_jx, &dc.r_jx))) return rc;
+  if ((rc = upload(h, C.red_of, &dc.red_of))) return rc;
+  if ((rc = upload(h, cidx, &dc.cidx_of))) return rc;
+  if ((rc = upload(h, C.orig_of, &dc.orig_of))) return rc;
+  if ((rc = upload(h, C.r_orig, &dc.r_orig))) return rc;
+  dc.N = (int32_t)N; dc.nnz = (int32_t)nnz; dc.nvar = (int32_t)nvar; dc.N2 = (int32_t)C.N2; dc.ncs = (int32_t)C.ncs;
+  dc.ncond = (int32_t)C.r_orig.size(); dc.cstride = C.cstride;
+  if ((rc = dalloc(h, &h->d_xpos, (size_t)batch))) return rc;
+  if ((rc = dalloc(h, &h->d_xzer, (size_t)batch))) return rc;
+  return CNL_OK;
+}
+
+// The resident condense kernel for a Float32 general handle (kernels.h: DevCondEll), where it pays and fits: the tiled kernel stages
+// sum(ch_tile) elements per problem, the resident one nnz + N; a dense Jacobian makes the former many times the latter (every chunk's
+// tile holds the whole Jacobian), and where the tile fits no LDS at all the plain kernel gathers from L2 per slot.
+int setup_cond_resident(cnl_handle* h) {
+  const cnl_plan* plan = h->plan;
+  const cnl::Cond& C = plan->C;
+  const int64_t nsrc = plan->nnz + plan->N, nslot = (int64_t)C.c_ptr.size() - 1;
+  if (plan->opt.float32_condense != 1 || nsrc >= 65535) return CNL_OK;
+  if (cnl::condense_resident_lds_bytes(plan->nnz, plan->N) > std::min<size_t>(cnl::max_lds_bytes(), 160 * 1024)) return CNL_OK;
+  int64_t staged = 0;
+  for (int32_t t : C.ch_tile) staged += t;
+  if (C.tiled_ok && staged <= 4 * nsrc) return CNL_OK;   // the tiled kernel's chunks are what they were made for
+  constexpr int NT = cnl::COND_RES_THREADS;
+  const int64_t nblk = (nslot + NT - 1) / NT;
+  std::vector<int32_t> blk_ptr(nblk + 1, 0);
+  for (int64_t j = 0; j < nblk; j++) {
+    int32_t len = 0;
+    for (int64_t s = j * NT; s < std::min<int64_t>(nslot, (j + 1) * NT); s++) len = std::max(len, C.c_ptr[s + 1] - C.c_ptr[s]);
+    const int64_t next = (int64_t)blk_ptr[j] + (int64_t)len * NT;
+    if (next >= ((int64_t)1 << 30)) return CNL_OK;
+    blk_ptr[j + 1] = (int32_t)next;
+  }
+  std::vector<uint64_t> pack((size_t)blk_ptr[nblk], 0);
+  for (int64_t s = 0; s < nslot; s++) {
+    const int64_t j = s / NT, t = s % NT;
+    for (int32_t c = C.c_ptr[s]; c < C.c_ptr[s + 1]; c++)
+      pack[(size_t)blk_ptr[j] + (size_t)(c - C.c_ptr[s]) * NT + t] =
+          (uint64_t)C.c_a[c] | ((uint64_t)(C.c_b[c] + 1) << 16) | ((uint64_t)(C.c_b[c] < 0 ? 0 : C.c_d[c] + 1) << 32);
+  }
+  int rc;
+  if ((rc = upload(h, pack, &h->dce.pack))) return rc;
+  if ((rc = upload(h, blk_ptr, &h->dce.blk_ptr))) return rc;
+  h->dce.c_ptr = h->dc.c_ptr;
+  h->dce.nslot = (int32_t)nslot; h->dce.nnz = (int32_t)plan->nnz; h->dce.N = (int32_t)plan->N; h->dce.cstride = C.cstride;
+  h->cond_resident = true;
+  return CNL_OK;
+}
+
 }  // namespace
 
 // device state for `batch` problems of an analysed pattern; takes ownership of `plan` (freed with the handle, or here on failure)
@@ -474,42 +555,7 @@ int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, co
   cnl::DevPlan& dp = h->dp;
   if ((rc = upload_dev_plan(h))) return bail(rc);
   const cnl::Cond& C = plan->C;
-  if (C.active) {
-    cnl::DevCond& dc = h->dc;
-    std::vector<int32_t> cidx(N, -1);
-    for (size_t q = 0; q < C.r_orig.size(); q++) cidx[C.r_orig[q]] = (int32_t)q;
-    if ((rc = upload(h, C.c_ptr, &dc.c_ptr))) return bail(rc);
-    if ((rc = upload(h, C.c_a, &dc.c_a))) return bail(rc);
-    if ((rc = upload(h, C.c_b, &dc.c_b))) return bail(rc);
-    if ((rc = upload(h, C.c_d, &dc.c_d))) return bail(rc);
-    if ((rc = upload(h, C.c_order, &dc.c_order))) return bail(rc);
-    if ((rc = upload(h, C.ch_slot, &dc.ch_slot))) return bail(rc);
-    if ((rc = upload(h, C.ch_rng, &dc.ch_rng))) return bail(rc);
-    if ((rc = upload(h, C.ch_tile, &dc.ch_tile))) return bail(rc);
-    if ((rc = upload(h, C.rng_start, &dc.rng_start))) return bail(rc);
-    if ((rc = upload(h, C.rng_len, &dc.rng_len))) return bail(rc);
-    if ((rc = upload(h, C.c_la, &dc.c_la))) return bail(rc);
-    if ((rc = upload(h, C.c_lb, &dc.c_lb))) return bail(rc);
-    if ((rc = upload(h, C.c_ld, &dc.c_ld))) return bail(rc);
-    if ((rc = upload(h, C.ch_tptr, &dc.ch_tptr))) return bail(rc);
-    if ((rc = upload(h, C.tile_src, &dc.tile_src))) return bail(rc);
-    if ((rc = upload(h, C.c_pack, &dc.c_pack))) return bail(rc);
-    dc.tile_max = C.tile_max; dc.chunk_ncon_max = C.chunk_ncon_max; dc.chunk_nslot_max = C.chunk_nslot_max; dc.tiled_ok = C.tiled_ok ? 1 : 0;
-    if ((rc = upload(h, C.r_dsrc, &dc.r_dsrc))) return bail(rc);
-    if ((rc = upload(h, C.r_ptr, &dc.r_ptr))) return bail(rc);
-    if ((rc = upload(h, C.r_jsrc, &dc.r_jsrc))) return bail(rc);
-    if ((rc = upload(h, C.r_jx, &dc.r_jx))) return bail(rc);
-    if ((rc = upload(h, C.red_of, &dc.red_of))) return bail(rc);
-    if ((rc = upload(h, cidx, &dc.cidx_of))) return bail(rc);
-    if ((rc = upload(h, C.orig_of, &dc.orig_of))) return bail(rc);
-    if ((rc = upload(h, C.r_orig, &dc.r_orig))) return bail(rc);
-    dc.N = (int32_t)N; dc.nnz = (int32_t)nnz; dc.nvar = (int32_t)nvar; dc.N2 = (int32_t)C.N2; dc.ncs = (int32_t)C.ncs;
-    dc.ncond = (int32_t)C.r_orig.size(); dc.cstride = C.cstride;
-    // (d_cbuf / d_d2 — the condensed buffer and the reduced solution of the stand-alone condensation passes — are allocated below,
-    //  once it is known whether the band kernels serve the handle: they never touch them)
-    if ((rc = dalloc(h, &h->d_xpos, (size_t)batch))) return bail(rc);
-    if ((rc = dalloc(h, &h->d_xzer, (size_t)batch))) return bail(rc);
-  }
+  if (C.active && (rc = upload_dev_cond(h))) return bail(rc);
   if ((rc = choose_config(h))) return bail(rc);
   if ((rc = setup_v2(h))) return bail(rc);
   if (band_program(plan, false).ok && band_wide_serves_f64(plan) && plan->opt.band_kernel && h->use_v2 && !h->staged && h->v2_solve && h->lean && plan->P.back_rows && !plan->latency && !plan->split_mode) {
@@ -519,6 +565,7 @@ int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, co
     if ((rc = setup_band(h, band_program(plan, false), &unfit))) return bail(rc);
   }
   if ((rc = setup_layout(h))) return bail(rc);
+  // (d_cbuf / d_d2 only once it is known whether the band kernels serve the handle: they never touch them)
   // Storage only the register-front / general kernels and the stand-alone condensation passes use.  A band handle runs all three
   // calls of the plugin surface on the band kernels (round 6), so it owns the band factor records alone: 0.48 MB per problem of
   // cfg3's size instead of 0.48 + 1.16 (factor panels) + 0.64 (condensed buffer, reduced solution) — 16 384 problems: 29 GB less,
@@ -625,19 +672,31 @@ int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1
   return CNL_OK;
 }
 
-// A Float32 handle on the general multifrontal kernel (tuning float32_general): `plan` is the throughput analysis without condensation.
-// The handle owns the device plan, float factor panels (with the zero pad per problem of upload_dev_plan), float global scratch where the
-// work area does not fit LDS, and the row lists; nothing of the register-front, dense, staged or condensation state exists for it.
+// A Float32 handle on the general multifrontal kernel (tuning float32_general): `plan` is the throughput analysis without condensation,
+// or (tuning float32_condense) with it.  The handle owns the device plan, float factor panels (with the zero pad per problem of
+// upload_dev_plan), float global scratch where the work area does not fit LDS, and the row lists; on a condensed plan also the
+// condensation lists, the inertia counts of the condensed pivots, and the condensed buffer and reduced solution as FLOAT arrays.
+// Nothing of the register-front, dense or staged state exists for it.
 int create_f32_general_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device) {
   cnl_handle* h = new cnl_handle();
   h->plan = plan; h->device = device; h->batch = h->full_batch = batch; h->f32 = true; h->f32_general = true;
   auto bail = [&](int code) { cnl_destroy(h); return code; };
-  if (plan->C.active) return bail(fail(CNL_ERR_STATE, "cnl_create_f32: the plan of a Float32 general handle must not be condensed"));
+  if (plan->C.active && !plan->opt.float32_condense)
+    return bail(fail(CNL_ERR_STATE, "cnl_create_f32: the plan of a Float32 general handle is condensed only with tuning float32_condense = 1"));
   if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
   int rc = CNL_OK;
-  if ((rc = upload_dev_plan(h))) return bail(rc);
-  if ((rc = choose_config(h))) return bail(rc);
+  if ((rc = upload_dev_plan(h))) return bail(rc);   // (condensed plan: the strides of vals / rhs / d are those of d_cbuf / d_d2)
+  if ((rc = choose_config(h))) return bail(rc);     // (... and the front sizes those of the condensed system)
   if ((rc = setup_layout(h))) return bail(rc);   // (batch_layout = CNL_LAYOUT_INTERLEAVED is the band kernels': CNL_ERR_ARG)
+  if (plan->C.active) {
+    if ((rc = upload_dev_cond(h))) return bail(rc);
+    float *cbuf = nullptr, *d2 = nullptr;
+    if ((rc = dalloc(h, &cbuf, (size_t)batch * (size_t)plan->C.cstride))) return bail(rc);
+    if ((rc = dalloc(h, &d2, (size_t)batch * (size_t)plan->C.N2))) return bail(rc);
+    h->d_cbuf = reinterpret_cast<double*>(cbuf);
+    h->d_d2 = reinterpret_cast<double*>(d2);
+    if ((rc = setup_cond_resident(h))) return bail(rc);
+  }
   {
     // factor panels, zero-filled (the pad of every problem stays zero) and padded as a Float64 handle's
     float* L = nullptr;
@@ -716,10 +775,11 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
     if (*hout) return CNL_OK;   // (else: the program does not fit the band kernels, and float32_general is set)
   }
   // tuning float32_general: the general multifrontal kernel in float.  Its plan is the throughput analysis with nothing but that
-  // kernel to run, whatever the caller's options say: no condensation (a call is then the one classic launch), no register-front
+  // kernel to run, whatever the caller's options say: no condensation (a call is then the one classic launch) unless tuning
+  // float32_condense asks for it (the call is then that launch between the float condensation passes), no register-front
   // records, no dense routes, no staged execution, no band program.
   cnl::Tuning g = o;
-  g.condense = 0; g.register_front = 0; g.dense_backend = 0; g.general_dense = 0; g.staged = 0; g.band_kernel = 0;
+  g.condense = o.float32_condense ? 1 : 0; g.register_front = 0; g.dense_backend = 0; g.general_dense = 0; g.staged = 0; g.band_kernel = 0;
   if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, g)) return rc;
   return create_f32_general_from_plan(hout, plan, rows1, cols1, batch, device);
 }
@@ -842,6 +902,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   cfg[4] = (h->full_batch + h->cfg.ppb - 1) / h->cfg.ppb;
   cfg[5] = (h->dense || h->gdense) ? 3 : (h->use_v2 ? (h->staged ? 4 : 2) : 1);
   if (h->f32) cfg[5] |= (int64_t)1 << 27;                // a Float32 handle on the general kernel (tuning float32_general): bit 6 clear
+  if (h->cond_resident) cfg[5] |= (int64_t)1 << 35;      // ... whose condensation runs the resident condense kernel (tuning float32_condense = 1)
   if (h->lean && !h->dense && !h->gdense) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->tail) cfg[5] |= 32;                             // the remainder of the batch runs on a handle of its own (split_tail)
   if (h->band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->band_resident << 24) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28) | ((int64_t)h->band_mover << 34);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts, layout, operand pieces per epoch, mover table (bit 34: bit 27 marks a Float32 handle)

@@ -372,6 +372,14 @@ int cnl_plan_get(const cnl_plan* plan, const char* name, int32_t* out, int64_t* 
   else if (s == "r_ptr") { src = C.r_ptr.data(); n = (int64_t)C.r_ptr.size(); }
   else if (s == "r_jsrc") { src = C.r_jsrc.data(); n = (int64_t)C.r_jsrc.size(); }
   else if (s == "r_jx") { src = C.r_jx.data(); n = (int64_t)C.r_jx.size(); }
+  else if (s == "cond_info") {
+    // which condense kernel serves the plan (kernels_aux.hip): {1 the LDS-tiled kernel / 0 the plain slot kernel, largest tile in
+    // elements, largest contribution and slot count of a chunk, chunks}; empty where the plan is not condensed
+    static thread_local int32_t ci[5];
+    const int32_t v[5] = {C.tiled_ok ? 1 : 0, C.tile_max, C.chunk_ncon_max, C.chunk_nslot_max, C.ch_region[3]};
+    std::memcpy(ci, v, sizeof(ci));
+    src = ci; n = C.active ? 5 : 0;
+  }
   else if (s == "fronts") { src = reinterpret_cast<const int32_t*>(P.fronts.data()); n = (int64_t)P.fronts.size() * 16; }
   else if (s == "seg_ptr") { src = P.seg_ptr.data(); n = (int64_t)P.seg_ptr.size(); }
   else if (s == "asm_pos") { src = P.asm_pos.data(); n = (int64_t)P.asm_pos.size(); }

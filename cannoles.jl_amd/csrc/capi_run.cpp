@@ -68,11 +68,17 @@ int run_band(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_
   return end_timed(h, stream);
 }
 
-int launch(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
-  // a Float32 handle off the band kernels: the float instantiation of the general kernel serves the three calls of the plugin
-  // surface as one classic launch each, and nothing else
-  if (h->f32 && (a.skip_done || a.only_if_status || (a.mode == cnl::MODE_NEWTON && !a.rhs) || !h->f32_general || h->use_v2))
+// a Float32 handle off the band kernels: the float instantiation of the general kernel serves the three calls of the plugin
+// surface as one classic launch each (on a condensed plan between the float condensation passes), and nothing else.  rhs: the
+// right-hand side the call was given
+int f32_general_serves(const cnl_handle* h, const cnl::LaunchArgs& a, const double* rhs) {
+  if (h->f32 && (a.skip_done || a.only_if_status || (a.mode == cnl::MODE_NEWTON && !rhs) || !h->f32_general || h->use_v2))
     return fail(CNL_ERR_STATE, "this call is not served by the Float32 instantiation of the general kernel, and the handle has no other");
+  return CNL_OK;
+}
+
+int launch(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
+  if (int rc = f32_general_serves(h, a, a.rhs)) return rc;
   if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
   a.batch = (int)h->batch;
   a.lean = h->lean ? 1 : 0;
@@ -131,11 +137,12 @@ SubBatch::SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged) : 
   if (h->d_Lband) h->d_Lband = static_cast<char*>(h->d_Lband) + b0 * h->bd.lsize * esz;
   const cnl::Cond& C = h->plan->C;
   h->batch = nb;
-  h->d_L += b0 * h->dp.lsize;
+  // (factor panels, scratch, condensed buffer and reduced solution hold the handle's element type behind their double*)
+  h->d_L = elem_offset(h, h->d_L, b0 * h->dp.lsize);
   if (h->d_gs) h->d_gs += b0 * h->dp2.gs_doubles;
-  if (h->d_scratch) h->d_scratch += b0 * (int64_t)h->dp.work_doubles;
-  if (h->d_cbuf) h->d_cbuf += b0 * C.cstride;
-  if (h->d_d2) h->d_d2 += b0 * C.N2;
+  if (h->d_scratch) h->d_scratch = elem_offset(h, h->d_scratch, b0 * (int64_t)h->dp.work_doubles);
+  if (h->d_cbuf) h->d_cbuf = elem_offset(h, h->d_cbuf, b0 * C.cstride);
+  if (h->d_d2) h->d_d2 = elem_offset(h, h->d_d2, b0 * C.N2);
   if (h->d_xpos) h->d_xpos += b0;
   if (h->d_xzer) h->d_xzer += b0;
   if (h->d_gcnt) h->d_gcnt += 2 * b0;
@@ -257,25 +264,39 @@ int launch_redo(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
 // condense: which slots of the handle's condensed buffer are formed from `vals` [and `rhs`] — the values are the tiled kernel's mask
 // (1 matrix, 2 rho, 4 right-hand-side slots), the plain kernel takes the same choice as a slot range
 enum CondensePart { MATRIX_ONLY = 3, RHS_ONLY = 4, WHOLE_SYSTEM = 7 };
-int condense(cnl_handle* h, CondensePart part, const double* vals, const double* rhs, hipStream_t stream) {
+// (a Float32 handle's arrays are float arrays behind the double* of this file: the passes' float instantiations take them)
+template <class T>
+hipError_t condense_t(cnl_handle* h, CondensePart part, const double* vals, const double* rhs, hipStream_t stream) {
   const cnl::Cond& C = h->plan->C;
   const int B = (int)h->batch, s_mat = (int)(C.ncs + C.nvar), s_all = (int)C.cstride;
-  const hipError_t e = C.tiled_ok ? cnl::launch_condense_tiled(h->dc, vals, rhs, h->d_cbuf, part, C.ch_region[3], B, stream)
-                                  : cnl::launch_condense(h->dc, vals, rhs, h->d_cbuf, part == RHS_ONLY ? s_mat : 0,
-                                                         part == MATRIX_ONLY ? s_mat : s_all, B, stream);
+  const T* v = reinterpret_cast<const T*>(vals);
+  const T* r = reinterpret_cast<const T*>(rhs);
+  T* cbuf = reinterpret_cast<T*>(h->d_cbuf);
+  if constexpr (sizeof(T) == 4)
+    if (h->cond_resident)
+      return cnl::launch_condense_resident(h->dce, v, r, cbuf, part == RHS_ONLY ? s_mat : 0, part == MATRIX_ONLY ? s_mat : s_all, B, stream);
+  return C.tiled_ok ? cnl::launch_condense_tiled(h->dc, v, r, cbuf, part, C.ch_region[3], B, stream)
+                    : cnl::launch_condense(h->dc, v, r, cbuf, part == RHS_ONLY ? s_mat : 0, part == MATRIX_ONLY ? s_mat : s_all, B, stream);
+}
+int condense(cnl_handle* h, CondensePart part, const double* vals, const double* rhs, hipStream_t stream) {
+  const hipError_t e = h->f32 ? condense_t<float>(h, part, vals, rhs, stream) : condense_t<double>(h, part, vals, rhs, stream);
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("condense: ") + hipGetErrorString(e));
   return CNL_OK;
 }
-// inertia of the condensed pivots, for the kernels that do not count them themselves
+// inertia of the condensed pivots, for the kernels that do not count them themselves (Float32: against eig_tol narrowed to float)
 int cond_inertia(cnl_handle* h, const double* vals, double eig_tol, hipStream_t stream) {
-  const hipError_t e = cnl::launch_cond_inertia(h->dc, vals, h->d_xpos, h->d_xzer, eig_tol, (int)h->batch, stream);
+  const hipError_t e = h->f32 ? cnl::launch_cond_inertia(h->dc, reinterpret_cast<const float*>(vals), h->d_xpos, h->d_xzer, (float)eig_tol, (int)h->batch, stream)
+                              : cnl::launch_cond_inertia(h->dc, vals, h->d_xpos, h->d_xzer, eig_tol, (int)h->batch, stream);
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("condense: ") + hipGetErrorString(e));
   return CNL_OK;
 }
 // post-pass: the condensed components of d (and, d2 != nullptr, the kept ones out of the reduced solution)
 int expand(cnl_handle* h, const double* vals, const double* rhs, const double* d2, double* d, const int* success, int copy_rho_tail,
            hipStream_t stream) {
-  const hipError_t e = cnl::launch_expand(h->dc, const_cast<double*>(vals), rhs, d2, h->d_cbuf, d, success, copy_rho_tail, (int)h->batch, stream);
+  const hipError_t e = h->f32 ? cnl::launch_expand(h->dc, reinterpret_cast<float*>(const_cast<double*>(vals)), reinterpret_cast<const float*>(rhs),
+                                                   reinterpret_cast<const float*>(d2), reinterpret_cast<const float*>(h->d_cbuf),
+                                                   reinterpret_cast<float*>(d), success, copy_rho_tail, (int)h->batch, stream)
+                              : cnl::launch_expand(h->dc, const_cast<double*>(vals), rhs, d2, h->d_cbuf, d, success, copy_rho_tail, (int)h->batch, stream);
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("expand: ") + hipGetErrorString(e));
   return CNL_OK;
 }
@@ -288,6 +309,8 @@ int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, 
   int rc = CNL_OK;
   if (h->split_staged > 0 && !h->in_split && (h->staged || h->tail) && h->split_staged < h->batch) return run_split(h, a, d_vals, d_rhs, d_d, stream);
   if (h->band) return run_band(h, a, d_vals, d_rhs, d_d, stream);
+  // (a Float32 general handle refuses what its kernel does not serve here, before a condensation pass is enqueued)
+  if (h->f32 && (rc = f32_general_serves(h, a, d_rhs))) return rc;
   if (h->dense || h->gdense)
     if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
   if (h->dense) {
@@ -327,7 +350,7 @@ int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, 
     a.vals = d_vals; a.rhs = d_rhs; a.d = d_d;
     rc = launch(h, a, stream);
   } else {
-    double* crhs = h->d_cbuf + (C.ncs + C.nvar);   // the right-hand-side slots of the condensed buffer
+    double* crhs = elem_offset(h, h->d_cbuf, C.ncs + C.nvar);   // the right-hand-side slots of the condensed buffer
     const bool direct = h->use_v2 && h->plan->P.rec_direct;  // the register-front kernel condenses on the fly
     const bool count_d = direct && h->dp2.count_d;  // the kernel counts the condensed pivots itself
     if (direct && a.mode == cnl::MODE_NEWTON) {

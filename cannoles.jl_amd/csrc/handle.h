@@ -94,6 +94,10 @@ struct cnl_handle {
   double* d_cbuf = nullptr;   // [batch][cstride]
   double* d_d2 = nullptr;     // [batch][N2]
   int *d_xpos = nullptr, *d_xzer = nullptr;
+  // Float32 general handles on a condensed plan: the resident condense kernel serves the handle (kernels.h: DevCondEll) — where the
+  // tiled kernel's chunks degenerate (dense Jacobians) and [vals | rhs] of a problem fits LDS; tuning float32_condense = 2: never
+  bool cond_resident = false;
+  cnl::DevCondEll dce{};
   const double* last_vals = nullptr;  // device vals of the last factorisation (needed to condense later right-hand sides)
   double* d_L = nullptr;
   double* d_scratch = nullptr;
@@ -149,6 +153,8 @@ struct cnl_handle {
   // kernel instantiated for float.  The plan is the throughput analysis without condensation (C.active == false), so every call is
   // the one classic launch; the handle owns dp, cfg, the row lists and FLOAT factor panels / global scratch behind d_L / d_scratch
   // (element counts as for double: dp.lsize and dp.work_doubles count elements).  It keeps a real factor: the solve is two sweeps.
+  // With tuning float32_condense = 1 the plan is that analysis WITH condensation (C.active): the handle also owns dc, d_xpos / d_xzer
+  // and FLOAT arrays behind d_cbuf / d_d2, and a call is condense -> the one classic launch on d_cbuf -> expand, all in float.
   bool f32_general = false;
 };
 
@@ -205,6 +211,12 @@ inline int need_full_batch(const cnl_handle* h, const char* fn) {
     hipError_t e_ = (expr);                                                                            \
     if (e_ != hipSuccess) return fail(CNL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
+
+// p + n elements of the handle's element type: the factor panels, work area, condensed buffer and reduced solution of a Float32
+// handle are float arrays behind their double*
+inline double* elem_offset(const cnl_handle* h, double* p, int64_t n) {
+  return h->f32 ? reinterpret_cast<double*>(reinterpret_cast<float*>(p) + n) : p + n;
+}
 
 template <class T>
 int upload(cnl_handle* h, const std::vector<T>& v, const T** out) {

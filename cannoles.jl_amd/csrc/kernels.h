@@ -64,6 +64,20 @@ struct DevCond {
   int64_t cstride;
 };
 
+// The contribution lists once more, for the resident condense kernel of the Float32 general handles (kernels_aux.hip,
+// condense_resident_kernel): slots in blocks of COND_RES_THREADS, block j holding the k-th contribution of its
+// slots side by side at pack[blk_ptr[j] + k * COND_RES_THREADS + t] (one coalesced load per step of a wavefront), as
+// a | (b + 1) << 16 | (d + 1) << 32 with a, b, d indices into [vals | rhs] (all below 65 535); a slot's entries past its own count
+// (c_ptr) are zero words, read and not used.  A separate structure: DevCond is a kernel argument of the Float64 passes too.
+constexpr int COND_RES_THREADS = 1024;
+struct DevCondEll {
+  const uint64_t* pack;
+  const int32_t* blk_ptr;   // [blocks + 1], in entries
+  const int32_t* c_ptr;     // DevCond::c_ptr
+  int32_t nslot, nnz, N;
+  int64_t cstride;
+};
+
 // Transposed-Jacobian lists of the KKT pattern: for every variable column j the entries of
 // J_F and J_c in COO order, as (slot in vals, index into r resp. lambda).
 struct DevJt {
@@ -225,6 +239,20 @@ hipError_t launch_residual_vectors(const DevJt& J, const JacSrcF& S, const float
 hipError_t launch_trial_point(const DevJt& J, const float* x, const float* r, const float* lambda, const float* d,
                               float max_dlambda, float* xt, float* rt, float* lambdat, float* dlambda, int batch,
                               hipStream_t stream);
+// float twins of the condensation passes (Float32 general handles with tuning float32_condense): the same kernels instantiated for
+// float, every operation a float operation, eig_tol narrowed to float
+hipError_t launch_condense(const DevCond& C, const float* vals, const float* rhs, float* cbuf, int slot_begin, int slot_end,
+                           int batch, hipStream_t stream);
+hipError_t launch_condense_tiled(const DevCond& C, const float* vals, const float* rhs, float* cbuf, int mask, int nchunks,
+                                 int batch, hipStream_t stream);
+// ... and the resident form: one workgroup per problem holds [vals | rhs] in LDS and forms the slots [slot_begin, slot_end)
+hipError_t launch_condense_resident(const DevCondEll& E, const float* vals, const float* rhs, float* cbuf, int slot_begin, int slot_end,
+                                    int batch, hipStream_t stream);
+size_t condense_resident_lds_bytes(int64_t nnz, int64_t N);
+hipError_t launch_cond_inertia(const DevCond& C, const float* vals, int* extra_pos, int* extra_zer, float eig_tol, int batch,
+                               hipStream_t stream);
+hipError_t launch_expand(const DevCond& C, float* vals, const float* rhs, const float* d2, const float* cbuf, float* dout,
+                         const int* success, int copy_rho_tail, int batch, hipStream_t stream);
 hipError_t launch_fill_rho(double* vals, long long nnz, int nvar, const double* rho, const int* active, int batch, hipStream_t stream);
 hipError_t launch_lds_fill(int pattern, hipStream_t stream);   // debugging aid, see kernels_aux.hip
 hipError_t launch_expand(const DevCond& C, double* vals, const double* rhs, const double* d2, const double* cbuf, double* dout,

@@ -37,44 +37,52 @@ __device__ __forceinline__ double fast_div_aux(double w, double d) {
   const double q = w * r;
   return fma(fma(-d, q, w), r, q);
 }
+// T = float (Float32 general handles with tuning float32_condense): the correctly rounded float division, as the
+// multifrontal kernel's float instantiation divides (kernels.hip: w / dpiv)
+__device__ __forceinline__ float fast_div_aux(float w, float d) { return w / d; }
+
+// The four passes below are templates on the element type T: double for the Float64 handles, float for the Float32 general handles
+// that condense.  With T = float every load, product, quotient, sum and compare is a float operation, the contributions of a slot are
+// summed in the same list order, and nothing is accumulated in double.
 
 // One thread forms one slot for CPB problems: the contribution indices are read once and reused for
 // every problem, and the CPB independent gathers per index give the memory system some parallelism.
 constexpr int CPB = 4;
-__global__ void __launch_bounds__(256) condense_kernel(const DevCond Cin, const double* __restrict__ vals,
-                                                       const double* __restrict__ rhs, double* __restrict__ cbuf,
+template <class T>
+__global__ void __launch_bounds__(256) condense_kernel(const DevCond Cin, const T* __restrict__ vals,
+                                                       const T* __restrict__ rhs, T* __restrict__ cbuf,
                                                        int slot_begin, int slot_end, int batch) {
   const DevCond C = globalize(Cin);
   const int t = slot_begin + blockIdx.x * 256 + threadIdx.x;
   const int b0 = blockIdx.y * CPB;
   if (t >= slot_end || b0 >= batch) return;
   const int s = C.c_order[t];  // slots of equal contribution count sit together: no divergence inside a wavefront
-  const double* v[CPB];
-  const double* r[CPB];
+  const T* v[CPB];
+  const T* r[CPB];
 #pragma unroll
   for (int q = 0; q < CPB; q++) {
     const int b = b0 + q < batch ? b0 + q : batch - 1;
     v[q] = vals + (long long)b * C.nnz;
     r[q] = rhs ? rhs + (long long)b * C.N - C.nnz : v[q];  // entries >= nnz address the right-hand side
   }
-  double acc[CPB];
+  T acc[CPB];
 #pragma unroll
-  for (int q = 0; q < CPB; q++) acc[q] = 0.0;
+  for (int q = 0; q < CPB; q++) acc[q] = T(0);
   const int c0 = C.c_ptr[s], c1 = C.c_ptr[s + 1];
   for (int c = c0; c < c1; c++) {
     const int a = C.c_a[c], bb = C.c_b[c];
     if (bb < 0) {
 #pragma unroll
       for (int q = 0; q < CPB; q++) {
-        const double xa = a < C.nnz ? v[q][a] : (rhs ? r[q][a] : 0.0);
+        const T xa = a < C.nnz ? v[q][a] : (rhs ? r[q][a] : T(0));
         acc[q] += xa;
       }
     } else {
       const int dd = C.c_d[c];
 #pragma unroll
       for (int q = 0; q < CPB; q++) {
-        const double xa = v[q][a];
-        const double xb = bb < C.nnz ? v[q][bb] : (rhs ? r[q][bb] : 0.0);
+        const T xa = v[q][a];
+        const T xb = bb < C.nnz ? v[q][bb] : (rhs ? r[q][bb] : T(0));
         acc[q] -= fast_div_aux(xa * xb, v[q][dd]);
       }
     }
@@ -90,31 +98,38 @@ __global__ void __launch_bounds__(256) condense_kernel(const DevCond Cin, const 
 // (contribution indices are read once per slot and reused for every problem).  `mask` selects the slot
 // ranges to produce: 1 matrix, 2 rho, 4 right-hand side.
 constexpr int TPB = CONDENSE_TILED_PROBLEMS;
-__global__ void __launch_bounds__(256) condense_tiled_kernel(const DevCond Cin, const double* __restrict__ vals,
-                                                             const double* __restrict__ rhs, double* __restrict__ cbuf,
+// elements of the value tile in front of the staged contribution lists (8-byte words): a float tile is padded to a whole word
+template <class T>
+__host__ __device__ __forceinline__ int cond_tile_elems(int tile_max) {
+  return sizeof(T) == 8 ? TPB * tile_max : (TPB * tile_max + 1) & ~1;
+}
+template <class T>
+__global__ void __launch_bounds__(256) condense_tiled_kernel(const DevCond Cin, const T* __restrict__ vals,
+                                                             const T* __restrict__ rhs, T* __restrict__ cbuf,
                                                              int mask, int batch) {
-  extern __shared__ double tile[];
+  extern __shared__ double tile_raw[];
+  T* tile = reinterpret_cast<T*>(tile_raw);
   const DevCond C = globalize(Cin);
   const int ch = blockIdx.x;
   const int b0 = blockIdx.y * TPB;
-  const int T = C.ch_tile[ch];
+  const int T_ = C.ch_tile[ch];
   const int tid = threadIdx.x;
   {
     const int* tsrc = C.tile_src + C.ch_tptr[ch];
-    for (int t = tid; t < T; t += 256) {
+    for (int t = tid; t < T_; t += 256) {
       const int gsrc = tsrc[t];
 #pragma unroll
       for (int q = 0; q < TPB; q++) {
         const int b = b0 + q < batch ? b0 + q : batch - 1;
-        double v;
+        T v;
         if (gsrc < C.nnz) v = vals[(long long)b * C.nnz + gsrc];
-        else v = rhs ? rhs[(long long)b * C.N + (gsrc - C.nnz)] : 0.0;
-        tile[q * T + t] = v;
+        else v = rhs ? rhs[(long long)b * C.N + (gsrc - C.nnz)] : T(0);
+        tile[q * T_ + t] = v;
       }
     }
   }
   // stage the contribution lists of the chunk too: the compute phase then touches global memory only to store
-  unsigned long long* cpk = reinterpret_cast<unsigned long long*>(tile + TPB * C.tile_max);
+  unsigned long long* cpk = reinterpret_cast<unsigned long long*>(tile + cond_tile_elems<T>(C.tile_max));
   int* cpl = reinterpret_cast<int*>(cpk + C.chunk_ncon_max);  // local contribution pointer of every slot of the chunk (+1 per range)
   const int* rg = C.ch_slot + 6 * ch;
   int coff = 0, soff = 0;
@@ -132,20 +147,20 @@ __global__ void __launch_bounds__(256) condense_tiled_kernel(const DevCond Cin, 
     const int s0 = rg[2 * r], len = rg[2 * r + 1];
     if (mask & (1 << r)) {
       for (int t = tid; t < len; t += 256) {
-        double acc[TPB];
+        T acc[TPB];
 #pragma unroll
-        for (int q = 0; q < TPB; q++) acc[q] = 0.0;
+        for (int q = 0; q < TPB; q++) acc[q] = T(0);
         const int c0 = cpl[soff + t], c1 = cpl[soff + t + 1];
         for (int c = c0; c < c1; c++) {
           const unsigned long long pk = cpk[c];
           const int la = (int)(pk & 0xffff), lb = (int)((pk >> 16) & 0xffff) - 1;
           if (lb < 0) {
 #pragma unroll
-            for (int q = 0; q < TPB; q++) acc[q] += tile[q * T + la];
+            for (int q = 0; q < TPB; q++) acc[q] += tile[q * T_ + la];
           } else {
             const int ld = (int)((pk >> 32) & 0xffff) - 1;
 #pragma unroll
-            for (int q = 0; q < TPB; q++) acc[q] -= fast_div_aux(tile[q * T + la] * tile[q * T + lb], tile[q * T + ld]);
+            for (int q = 0; q < TPB; q++) acc[q] -= fast_div_aux(tile[q * T_ + la] * tile[q * T_ + lb], tile[q * T_ + ld]);
           }
         }
 #pragma unroll
@@ -157,17 +172,61 @@ __global__ void __launch_bounds__(256) condense_tiled_kernel(const DevCond Cin, 
   }
 }
 
+// Resident condense (Float32 general handles whose tiled chunks degenerate: a dense Jacobian puts every residual row into every chunk's
+// tile, so the tiled kernel re-stages the whole Jacobian for a column or two of slots — 31 times at dense_structure(40, 70) — and the
+// plain kernel gathers it from L2 once per slot).  Here ONE workgroup stages [vals | rhs] of ONE problem in LDS, once, and its 1 024
+// threads form all slots from there, a block of 1 024 slots at a time.  The contribution lists come transposed (DevCondEll): step k of
+// a block is one coalesced 8-byte load per lane, independent of the LDS reads, and the loop body has no branch, so the unrolled loads
+// run ahead of the arithmetic.  Same arithmetic as the kernels above: a slot's contributions one after the other in list order,
+// x(a) added or (x(a) * x(b)) / x(d) subtracted, every operation in T.
+template <class T>
+__global__ void __launch_bounds__(COND_RES_THREADS) condense_resident_kernel(const DevCondEll Ein, const T* __restrict__ vals,
+                                                                             const T* __restrict__ rhs, T* __restrict__ cbuf,
+                                                                             int slot_begin, int slot_end) {
+  extern __shared__ double tile_raw[];
+  T* src = reinterpret_cast<T*>(tile_raw);
+  const uint64_t* __restrict__ pack = as_global(Ein.pack);
+  const int* __restrict__ blk_ptr = as_global(Ein.blk_ptr);
+  const int* __restrict__ c_ptr = as_global(Ein.c_ptr);
+  const int nnz = Ein.nnz, N = Ein.N, nslot = Ein.nslot;
+  const long long b = blockIdx.x;
+  const int t = threadIdx.x;
+  for (int i = t; i < nnz; i += COND_RES_THREADS) src[i] = vals[b * nnz + i];
+  for (int i = t; i < N; i += COND_RES_THREADS) src[nnz + i] = rhs ? rhs[b * N + i] : T(0);
+  __syncthreads();
+  for (int j = slot_begin / COND_RES_THREADS; j * COND_RES_THREADS < slot_end; j++) {
+    const int s = j * COND_RES_THREADS + t;
+    const int n = s < nslot ? c_ptr[s + 1] - c_ptr[s] : 0;
+    const int p0 = blk_ptr[j], len = (blk_ptr[j + 1] - p0) / COND_RES_THREADS;   // workgroup-uniform
+    const uint64_t* __restrict__ p = pack + p0 + t;
+    T acc = T(0);
+#pragma unroll 8
+    for (int k = 0; k < len; k++) {
+      const uint64_t pk = p[(long long)k * COND_RES_THREADS];
+      const int la = (int)(pk & 0xffff), lb = (int)((pk >> 16) & 0xffff) - 1, ld = (int)((pk >> 32) & 0xffff) - 1;
+      const bool plain = lb < 0;
+      const T xa = src[la], xb = src[plain ? 0 : lb], xd = src[plain ? 0 : ld];
+      const T q = fast_div_aux(xa * xb, xd);   // (a plain or unused entry: some quotient of element 0, not used)
+      const T next = plain ? acc + xa : acc - q;
+      acc = k < n ? next : acc;
+    }
+    if (s >= slot_begin && s < slot_end) cbuf[b * Ein.cstride + s] = acc;
+  }
+}
+
 // pos_r = #{d_r > eig_tol}, zer_r = #{|d_r| <= eig_tol} over the condensed pivots (src/solver_types.jl:90-95).
 // One workgroup per problem; the counts are written, not accumulated (no memset before the launch).
-__global__ void __launch_bounds__(256) cond_inertia_kernel(const DevCond Cin, const double* __restrict__ vals, int* extra_pos,
-                                                           int* extra_zer, double eig_tol, int batch) {
+// (T = float: eig_tol arrives narrowed to float, as the multifrontal kernel's float instantiation compares)
+template <class T>
+__global__ void __launch_bounds__(256) cond_inertia_kernel(const DevCond Cin, const T* __restrict__ vals, int* extra_pos,
+                                                           int* extra_zer, T eig_tol, int batch) {
   const DevCond C = globalize(Cin);
   const int b = blockIdx.x;
   __shared__ int sp[4], sz[4];
-  const double* v = vals + (long long)b * C.nnz;
+  const T* v = vals + (long long)b * C.nnz;
   int pos = 0, zer = 0;
   for (int q = threadIdx.x; q < C.ncond; q += 256) {
-    const double d = v[C.r_dsrc[q]];
+    const T d = v[C.r_dsrc[q]];
     pos += d > eig_tol;
     zer += fabs(d) <= eig_tol;
   }
@@ -191,14 +250,15 @@ constexpr int XEMAX = 2048; // Jacobian entries staged per workgroup (longer chu
 constexpr int XPB = 8;      // problems per workgroup: the index lists are read once and reused
 // d2 == nullptr: the multifrontal kernel has already written the kept components into dout (caller's numbering);
 // only the residual components are recovered, reading the x components from dout itself.
-__global__ void __launch_bounds__(256) expand_kernel(const DevCond Cin, double* __restrict__ vals, const double* __restrict__ rhs,
-                                                     const double* d2, const double* __restrict__ cbuf,
-                                                     double* dout, const int* __restrict__ success,
+template <class T>
+__global__ void __launch_bounds__(256) expand_kernel(const DevCond Cin, T* __restrict__ vals, const T* __restrict__ rhs,
+                                                     const T* d2, const T* __restrict__ cbuf,
+                                                     T* dout, const int* __restrict__ success,
                                                      int copy_rho_tail, int nb_copy, int batch) {
   const DevCond C = globalize(Cin);
   const int b0 = blockIdx.y * XPB;
   const int t = threadIdx.x;
-  __shared__ double prod[2 * XEMAX];
+  __shared__ T prod[2 * XEMAX];
   if ((int)blockIdx.x < nb_copy) {
     const int j = blockIdx.x * 256 + t;
     const int oj = j < C.N2 ? C.orig_of[j] : 0;
@@ -233,29 +293,29 @@ __global__ void __launch_bounds__(256) expand_kernel(const DevCond Cin, double* 
     // Problems are pipelined: the operands of problem q + 1 are loaded into registers before the products of problem q are
     // parked and summed (two LDS buffers, one barrier per problem), so the loads of the next problem are in flight while
     // this one is reduced.
-    double jv[XE], xv[XE], rh = 0.0, dv = 1.0;
+    T jv[XE], xv[XE], rh = T(0), dv = T(1);
     bool ok_cur = false;
-    auto load = [&](int q, double (&jv_)[XE], double (&xv_)[XE], double& rh_, double& dv_) -> bool {
+    auto load = [&](int q, T (&jv_)[XE], T (&xv_)[XE], T& rh_, T& dv_) -> bool {
       const long long b = b0 + q;
       if (q >= nq || (success && !success[b])) return false;  // workgroup-uniform
-      const double* v = vals + b * C.nnz;
-      const double* x2 = d2 ? d2 + b * C.N2 : dout + b * C.N;
+      const T* v = vals + b * C.nnz;
+      const T* x2 = d2 ? d2 + b * C.N2 : dout + b * C.N;
 #pragma unroll
       for (int k = 0; k < XE; k++) {
         const bool in = t + 256 * k < e1 - e0;
-        jv_[k] = in ? v[js[k]] : 0.0;
-        xv_[k] = in ? x2[jx[k]] : 0.0;
+        jv_[k] = in ? v[js[k]] : T(0);
+        xv_[k] = in ? x2[jx[k]] : T(0);
       }
-      rh_ = has_row ? rhs[b * C.N + i] : 0.0;
-      dv_ = has_row ? v[dsrc] : 1.0;
+      rh_ = has_row ? rhs[b * C.N + i] : T(0);
+      dv_ = has_row ? v[dsrc] : T(1);
       return true;
     };
     ok_cur = load(0, jv, xv, rh, dv);
     for (int q = 0; q < nq; q++) {
-      double jn[XE], xn[XE], rhn = 0.0, dvn = 1.0;
+      T jn[XE], xn[XE], rhn = T(0), dvn = T(1);
       const bool ok_next = load(q + 1, jn, xn, rhn, dvn);
       if (ok_cur) {
-        double* pb = prod + (q & 1) * XEMAX;
+        T* pb = prod + (q & 1) * XEMAX;
 #pragma unroll
         for (int k = 0; k < XE; k++) {
           const int e = t + 256 * k;
@@ -264,8 +324,8 @@ __global__ void __launch_bounds__(256) expand_kernel(const DevCond Cin, double* 
       }
       __syncthreads();  // (also orders the reads of this buffer two problems ago before the writes above)
       if (ok_cur && has_row) {
-        const double* pb = prod + (q & 1) * XEMAX;
-        double s = rh;
+        const T* pb = prod + (q & 1) * XEMAX;
+        T s = rh;
         for (int k = k0; k < k1; k++) s += pb[k - e0];
         dout[(long long)(b0 + q) * C.N + i] = -fast_div_aux(s, dv);
       }
@@ -278,11 +338,11 @@ __global__ void __launch_bounds__(256) expand_kernel(const DevCond Cin, double* 
   for (int q = 0; q < nq; q++) {
     const long long b = b0 + q;
     if (success && !success[b]) continue;  // workgroup-uniform
-    const double* v = vals + b * C.nnz;
+    const T* v = vals + b * C.nnz;
     // x components: reduced index == caller's index for the variables (they are never condensed)
-    const double* x2 = d2 ? d2 + b * C.N2 : dout + b * C.N;
+    const T* x2 = d2 ? d2 + b * C.N2 : dout + b * C.N;
     if (has_row) {
-      double s = rhs[b * C.N + i];
+      T s = rhs[b * C.N + i];
       for (int k = k0; k < k1; k++) s = fma(v[C.r_jsrc[k]], x2[C.r_jx[k]], s);
       dout[b * C.N + i] = -fast_div_aux(s, v[dsrc]);
     }
@@ -1048,38 +1108,82 @@ hipError_t launch_trial_point(const DevJt& J, const float* x, const float* r, co
   return launch_trial_point_t(J, x, r, lambda, d, max_dlambda, xt, rt, lambdat, dlambda, batch, stream);
 }
 
-hipError_t launch_condense(const DevCond& C, const double* vals, const double* rhs, double* cbuf, int slot_begin, int slot_end,
-                           int batch, hipStream_t stream) {
+template <class T>
+static hipError_t launch_condense_t(const DevCond& C, const T* vals, const T* rhs, T* cbuf, int slot_begin, int slot_end, int batch,
+                                    hipStream_t stream) {
   const int n = slot_end - slot_begin;
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(condense_kernel, dim3((n + 255) / 256, (batch + CPB - 1) / CPB), dim3(256), 0, stream, C, vals, rhs, cbuf, slot_begin, slot_end, batch);
+  hipLaunchKernelGGL(condense_kernel<T>, dim3((n + 255) / 256, (batch + CPB - 1) / CPB), dim3(256), 0, stream, C, vals, rhs, cbuf, slot_begin, slot_end, batch);
   return hipGetLastError();
 }
+hipError_t launch_condense(const DevCond& C, const double* vals, const double* rhs, double* cbuf, int slot_begin, int slot_end,
+                           int batch, hipStream_t stream) {
+  return launch_condense_t(C, vals, rhs, cbuf, slot_begin, slot_end, batch, stream);
+}
+hipError_t launch_condense(const DevCond& C, const float* vals, const float* rhs, float* cbuf, int slot_begin, int slot_end,
+                           int batch, hipStream_t stream) {
+  return launch_condense_t(C, vals, rhs, cbuf, slot_begin, slot_end, batch, stream);
+}
 
-hipError_t launch_condense_tiled(const DevCond& C, const double* vals, const double* rhs, double* cbuf, int mask, int nchunks,
-                                 int batch, hipStream_t stream) {
+// (the host's tiled_ok decision counts 8-byte tile elements: a float tile needs at most those bytes)
+template <class T>
+static hipError_t launch_condense_tiled_t(const DevCond& C, const T* vals, const T* rhs, T* cbuf, int mask, int nchunks, int batch,
+                                          hipStream_t stream) {
   if (nchunks <= 0) return hipSuccess;
-  const size_t lds = (size_t)TPB * (size_t)C.tile_max * sizeof(double) + (size_t)C.chunk_ncon_max * 8 + ((size_t)C.chunk_nslot_max + 8) * 4;
+  const size_t lds = (size_t)cond_tile_elems<T>(C.tile_max) * sizeof(T) + (size_t)C.chunk_ncon_max * 8 + ((size_t)C.chunk_nslot_max + 8) * 4;
   {  // per device and cheap: set on every launch (a process may drive several devices from several threads)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(condense_tiled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)lds));
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(condense_tiled_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)lds));
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(condense_tiled_kernel, dim3(nchunks, (batch + TPB - 1) / TPB), dim3(256), lds, stream, C, vals, rhs, cbuf, mask, batch);
+  hipLaunchKernelGGL(condense_tiled_kernel<T>, dim3(nchunks, (batch + TPB - 1) / TPB), dim3(256), lds, stream, C, vals, rhs, cbuf, mask, batch);
+  return hipGetLastError();
+}
+hipError_t launch_condense_tiled(const DevCond& C, const double* vals, const double* rhs, double* cbuf, int mask, int nchunks,
+                                 int batch, hipStream_t stream) {
+  return launch_condense_tiled_t(C, vals, rhs, cbuf, mask, nchunks, batch, stream);
+}
+hipError_t launch_condense_tiled(const DevCond& C, const float* vals, const float* rhs, float* cbuf, int mask, int nchunks,
+                                 int batch, hipStream_t stream) {
+  return launch_condense_tiled_t(C, vals, rhs, cbuf, mask, nchunks, batch, stream);
+}
+
+size_t condense_resident_lds_bytes(int64_t nnz, int64_t N) { return (((size_t)(nnz + N) * sizeof(float)) + 7) & ~(size_t)7; }
+hipError_t launch_condense_resident(const DevCondEll& E, const float* vals, const float* rhs, float* cbuf, int slot_begin, int slot_end,
+                                    int batch, hipStream_t stream) {
+  if (slot_end <= slot_begin || batch <= 0) return hipSuccess;
+  const size_t lds = condense_resident_lds_bytes(E.nnz, E.N);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(condense_resident_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)lds));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(condense_resident_kernel<float>, dim3(batch), dim3(COND_RES_THREADS), lds, stream, E, vals, rhs, cbuf, slot_begin, slot_end);
   return hipGetLastError();
 }
 
 hipError_t launch_cond_inertia(const DevCond& C, const double* vals, int* extra_pos, int* extra_zer, double eig_tol, int batch,
                                hipStream_t stream) {
-  hipLaunchKernelGGL(cond_inertia_kernel, dim3(batch), dim3(256), 0, stream, C, vals, extra_pos, extra_zer, eig_tol, batch);
+  hipLaunchKernelGGL(cond_inertia_kernel<double>, dim3(batch), dim3(256), 0, stream, C, vals, extra_pos, extra_zer, eig_tol, batch);
+  return hipGetLastError();
+}
+hipError_t launch_cond_inertia(const DevCond& C, const float* vals, int* extra_pos, int* extra_zer, float eig_tol, int batch,
+                               hipStream_t stream) {
+  hipLaunchKernelGGL(cond_inertia_kernel<float>, dim3(batch), dim3(256), 0, stream, C, vals, extra_pos, extra_zer, eig_tol, batch);
   return hipGetLastError();
 }
 
-hipError_t launch_expand(const DevCond& C, double* vals, const double* rhs, const double* d2, const double* cbuf, double* dout,
-                         const int* success, int copy_rho_tail, int batch, hipStream_t stream) {
+template <class T>
+static hipError_t launch_expand_t(const DevCond& C, T* vals, const T* rhs, const T* d2, const T* cbuf, T* dout, const int* success,
+                                  int copy_rho_tail, int batch, hipStream_t stream) {
   const int nb_copy = d2 ? ((int)C.N2 + 255) / 256 : 0, nb_r = ((int)C.ncond + XRB - 1) / XRB;
-  hipLaunchKernelGGL(expand_kernel, dim3(nb_copy + nb_r, (batch + XPB - 1) / XPB), dim3(256), 0, stream, C, vals, rhs, d2, cbuf, dout, success,
+  hipLaunchKernelGGL(expand_kernel<T>, dim3(nb_copy + nb_r, (batch + XPB - 1) / XPB), dim3(256), 0, stream, C, vals, rhs, d2, cbuf, dout, success,
                      copy_rho_tail, nb_copy, batch);
   return hipGetLastError();
+}
+hipError_t launch_expand(const DevCond& C, double* vals, const double* rhs, const double* d2, const double* cbuf, double* dout,
+                         const int* success, int copy_rho_tail, int batch, hipStream_t stream) {
+  return launch_expand_t(C, vals, rhs, d2, cbuf, dout, success, copy_rho_tail, batch, stream);
+}
+hipError_t launch_expand(const DevCond& C, float* vals, const float* rhs, const float* d2, const float* cbuf, float* dout,
+                         const int* success, int copy_rho_tail, int batch, hipStream_t stream) {
+  return launch_expand_t(C, vals, rhs, d2, cbuf, dout, success, copy_rho_tail, batch, stream);
 }
 
 // rho slots of the problems marked active: vals[b][nnz - nvar ..] = rho[b] (the host-driven ladder of the small-batch host call)

@@ -60,7 +60,8 @@ namespace cnl {
   X(f1_tiles, 1)             /* row f1 streams column tiles through LDS where the pattern allows; 0: gather kernel          */ \
   X(batch_layout, 0)         /* CNL_LAYOUT_*: layout of `vals` at the device-pointer entry points (band handles)            */ \
   X(band_rhs_interleaved, 0) /* measurement: the band kernels also take `rhs` interleaved (batch_layout = 1 handles)        */ \
-  X(float32_general, 0)      /* cnl_create_f32: a pattern (or option set) the band kernels do not serve runs on the general kernel in float */
+  X(float32_general, 0)      /* cnl_create_f32: a pattern (or option set) the band kernels do not serve runs on the general kernel in float */ \
+  X(float32_condense, 0)     /* ... on the condensed system (the -I block eliminated by the condensation passes in float); only with float32_general */
 
 struct Tuning {
 #define X(name, dflt) int32_t name = dflt;

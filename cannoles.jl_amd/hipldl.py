@@ -400,7 +400,10 @@ class HIPLDLStruct:
     The element type comes from `vals`, as `LDLFactStruct(N, rows, cols, vals)` takes T from it (`dtype` when vals is None):
     float64, or float32 — a Float32 handle (cnl_create_f32), which by default exists for band-structured patterns only (CnlError
     CNL_ERR_ARG otherwise: the caller stays on the CPU backend); Options(float32_general=1) serves every other pattern on the
-    general multifrontal kernel in float (config["kernel"] == "v1")."""
+    general multifrontal kernel in float (config["kernel"] == "v1"), and Options(float32_general=1, float32_condense=1) runs that
+    kernel on the condensed system — the -I block eliminated by the condensation passes in float — which info["ncond"] > 0 identifies
+    (config["cond_resident"]: the resident condense kernel serves it).  Such a handle reads the Jacobian values of `vals` again in
+    solve_ldl!: the array given to try_to_factorize must stay alive and unmodified until the last solve on that factor."""
 
     def __init__(self, N, rows, cols, vals, nvar=None, nequ=None, ncon=None, batch=1, device=0, options=None, dtype=np.float64):
         self.N = int(N)
@@ -433,7 +436,7 @@ class HIPLDLStruct:
                        "kernel": {2: "v2", 3: "dense", 4: "v2-staged"}.get(int(cfg[5]) & 15, "v1"), "wpb": int(cfg[6]), "lds2_bytes": int(cfg[7]),
                        "lean": bool(int(cfg[5]) & 16), "tail": bool(int(cfg[5]) & 32), "band": bool(int(cfg[5]) & 64), "f1_tiles": bool(int(cfg[5]) & 128),
                        "band_nl": (int(cfg[5]) >> 8) & 255, "band_parts": (int(cfg[5]) >> 16) & 255, "band_resident": bool((int(cfg[5]) >> 24) & 1),
-                       "band_mover_table": bool((int(cfg[5]) >> 34) & 1),
+                       "band_mover_table": bool((int(cfg[5]) >> 34) & 1), "cond_resident": bool((int(cfg[5]) >> 35) & 1),
                        "batch_layout": (int(cfg[5]) >> 25) & 1, "rhs_interleaved": bool((int(cfg[5]) >> 26) & 1),
                        "float32": bool((int(cfg[5]) >> 27) & 1), "band_pieces": (int(cfg[5]) >> 28) & 63}
         if self.config["float32"] and self.config["band"]:   # (a Float32 handle off the band kernels — tuning float32_general — is "v1")

@@ -149,7 +149,8 @@ int cnl_plan_info(const cnl_plan* plan, int64_t info[16]);
  * (0-based; condensed residual nodes first).  Multifrontal plan of the (condensed) system: "inner_perm",
  * "fronts" (16 int32 per front, struct FrontHdr in csrc/plan.h), "seg_ptr", "asm_pos", "asm_src",
  * "child_idx", "rel_idx".  Condensation lists (csrc/condense.h): "c_ptr", "c_a", "c_b", "c_d", "orig_of",
- * "r_orig", "r_dsrc", "r_ptr", "r_jsrc", "r_jx".  Record streams of the register-front kernel (csrc/plan.h; empty when that
+ * "r_orig", "r_dsrc", "r_ptr", "r_jsrc", "r_jx"; "cond_info" = {1 if the LDS-tiled condense kernel serves the plan (0: the plain slot
+ * kernel), largest tile in elements, largest contribution and slot count of a chunk, chunks}, empty without condensation.  Record streams of the register-front kernel (csrc/plan.h; empty when that
  * kernel does not serve the plan): "rec", "brec".  Staged plans: "tasks" (8 int32 per task, struct Task in csrc/plan.h: stage,
  * first front, end front, record offset, backward record offset, 1 if a root, parent task or -1, number of child tasks),
  * "stage_ptr".  With out == NULL only *count is set.
@@ -435,7 +436,8 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
 /* ([5] + (1 << 27) on a Float32 handle.  On the band kernels: bits 7-26 as above, cfg[0..4], [6], [7] are 0.  On the general kernel
  *  (tuning "float32_general=1"): cfg[0..4] describe that kernel's float instance as they do for a Float64 handle — [2] counts 4-byte
- *  elements — and [5] = 1 + (1 << 27) with bit 6 clear (+ 128 as above); [6], [7] are 0.) */
+ *  elements — and [5] = 1 + (1 << 27) with bit 6 clear (+ 128 as above; + (1 << 35) where tuning "float32_condense=1" has the
+ *  resident condense kernel form the condensed system); [6], [7] are 0.) */
 /* Launches of the Newton-system kernels since the library was loaded, per kernel family: counts[0] band kernels (csrc/band.hip),
  * [1] register-front kernel (csrc/kernels2.hip, staged launches not included), [2] general kernel (csrc/kernels.hip).  Lets a test
  * pin WHICH kernel served a call sequence (e.g. that solve_ldl! behind a band factorisation launches no second kernel family). */
@@ -462,6 +464,19 @@ int cnl_launch_counts(int64_t counts[3]);
  * cnl_deinterleave_f32_dev work on any Float32 handle).  Tuning v1_tpp / v1_ppb / v1_lds may name only a configuration compiled
  * for float (csrc/kernels.hip, CNL_F32_CASES; CNL_ERR_ARG otherwise); a work area that fits neither LDS nor a global-scratch
  * instance is CNL_ERR_DIM, cnl_last_error naming the order of the largest front.
+ *   tuning "float32_condense=1" (default 0; takes effect only where "float32_general=1" lets the general kernel serve the handle —
+ * every other handle ignores it, and without "float32_general" a non-band pattern is still CNL_ERR_ARG): that plan WITH static
+ * condensation of the residual block.  The -I block is eliminated by the condensation passes (csrc/kernels_aux.hip) instantiated
+ * for float — every load, product, correctly rounded quotient, sum and compare a float operation, a slot's contributions summed
+ * in list order — and the general kernel factorises the system of order nvar + ncon: a call is condense -> ONE launch of family 2
+ * -> post-pass (the passes are not counted by cnl_launch_counts, as for Float64).  cnl_plan_info / cnl_get_plan: ncond > 0.
+ * cnl_set_active_batch serves it; batch_layout = CNL_LAYOUT_INTERLEAVED stays CNL_ERR_ARG.  ("float32_condense=2": the same with
+ * the list-driven condense kernels only, never the resident one — for measurements and tests; bit-equal results.)
+ *   CONTRACT of cnl_solve_f32 / cnl_solve_f32_dev on such a handle: the `vals` / d_vals given to cnl_factorize_f32 /
+ * cnl_factorize_f32_dev (or cnl_newton_system_f32*) must stay alive and UNMODIFIED until the last solve on that factor — the
+ * condensation of every new right-hand side and the post-pass read the Jacobian values and the -I entries from it (host-pointer
+ * calls: the handle's own staged copy, nothing for the caller to keep).  The uncondensed Float32 general handle does not need
+ * this.  The kept factor still serves any number of right-hand sides without refactorising.
  * The semantics of every call are those of its Float64 twin above.  Mixing element types is CNL_ERR_STATE and does nothing:
  * a Float64 entry point on a Float32 handle (cnl_factorize..., the row f1 / f2 / f4 / trial-point passes, cnl_interleave_dev...)
  * and an `_f32` entry point on a Float64 handle.  cnl_layout_len counts elements, so it serves both types.
