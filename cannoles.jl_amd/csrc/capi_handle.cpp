@@ -79,12 +79,18 @@ int choose_config(cnl_handle* h) {
   return CNL_OK;
 }
 
+// The register-front kernel for a handle of either element type.  A Float32 general handle (tuning float32_register_front) is
+// asked with its 4-byte elements: every size "in doubles" of DevPlan2 then counts floats, the wavefront's LDS block and the global
+// scratch are sized in floats, and the 32-bit byte offsets of the kernel reach twice as many elements.  Its plan has no direct
+// records, tasks or dense route, so the staged state, v2_solve and lean stay off.
 int setup_v2(cnl_handle* h) {
   const cnl::Plan& P = h->plan->P;
   h->use_v2 = false;
   const cnl::Tuning& o = h->plan->opt;
+  const size_t esz = h->f32 ? sizeof(float) : sizeof(double);
   if (!P.v2_ok || !o.register_front) return CNL_OK;
-  if (!h->plan->gpos.empty() && (o.general_dense == 2 || (h->plan->prefer_dense && h->batch <= 16))) return CNL_OK;  // the dense route (capi_plan.cpp, plan_create_impl); 2: wherever it is possible
+  if (h->f32 && (P.rec_direct || !P.tasks.empty())) return CNL_OK;   // (not what cnl_create_f32_ex builds: the float kernel has no such instance)
+  if (!h->f32 && !h->plan->gpos.empty() && (o.general_dense == 2 || (h->plan->prefer_dense && h->batch <= 16))) return CNL_OK;  // the dense route (capi_plan.cpp, plan_create_impl); 2: wherever it is possible
   cnl::DevPlan2& d = h->dp2;
   // streams are over-read by the prefetcher: pad with zeros
   std::vector<int32_t> rec(P.rec), brec(P.brec);
@@ -98,18 +104,19 @@ int setup_v2(cnl_handle* h) {
   d.reccap = (P.rec_maxlen + 64 + 3) & ~3;  // + slack: the product loop reads up to 48 words past a list
   d.breccap = (P.brec_maxlen + 3) & ~3;
   d.recwords = std::max(d.reccap, 2 * d.breccap);
-  d.u2_peak = P.u2_peak;
+  d.u2_peak = h->f32 ? (P.u2_peak + 1) & ~1 : P.u2_peak;   // (float: the image behind the stack is zeroed in 8-byte pairs)
   // (round 5, found by the randomised run with lds_pad = 0: the out-of-line elimination of a class-64 front publishes its pivot row at
   //  lb[0 .. 65] of the staging area — lanes beyond the pivot park their value at index TE + 1 —, two doubles more than the 64 reserved
   //  here; without padding between the problems they landed in the next problem's update stack)
-  d.jraw_off = (int32_t)((P.u2_peak + std::max<int64_t>(P.fs2_max, 72) + 1) & ~(int64_t)1);
+  d.jraw_off = (int32_t)((d.u2_peak + std::max<int64_t>(P.fs2_max, 72) + 1) & ~(int64_t)1);
   d.bpanel_off = (int32_t)((P.bwd_peak + 2 + 1) & ~(int64_t)1);  // end of the backward sweep's x stack
   // the raw-value area (128 doubles per problem) is needed only by fast fronts whose products come as lists (plan.h: RF_ROWS)
   int64_t prob = std::max<int64_t>((int64_t)d.jraw_off + (P.rec_direct && P.listprod_fronts > 0 ? 128 : 0), (int64_t)d.bpanel_off);
   // per-problem areas 32 banks apart modulo 64 (prob_doubles = 16 mod 32): the 16 lanes of two neighbouring problems
   // then touch disjoint LDS banks when they read the same row of their images (env CNL_LDS_PAD=0 disables)
   prob = (prob + 1) & ~(int64_t)1;
-  if (o.lds_pad) while (prob % 32 != 16) prob += 2;
+  const int64_t padm = h->f32 ? 64 : 32;   // (elements: 32 banks of 4 bytes are 16 doubles or 32 floats)
+  if (o.lds_pad) while (prob % padm != padm / 2) prob += 2;
   d.prob_doubles = (int32_t)prob;
   d.gs_doubles = P.gs_doubles + 64;
   d.lsize = h->dp.lsize;  // padded stride, see cnl_create
@@ -122,8 +129,8 @@ int setup_v2(cnl_handle* h) {
     d.count_d = P.d_owned == (int64_t)h->plan->C.r_dsrc.size() ? 1 : 0;  // every condensed pivot is staged by some front
   }
   // the kernel addresses vals / rhs / L of the 4 problems of a wave with 32-bit byte offsets from the first one
-  if (4 * 8 * (uint64_t)std::max<int64_t>({d.lsize, d.vstride, d.rstride, d.dstride, (int64_t)d.nnz + d.N0}) >= (1ull << 32)) return CNL_OK;
-  const size_t wave_bytes = ((size_t)(d.recwords >> 1) + 4 * (size_t)d.prob_doubles + 16) * sizeof(double);   // + 16: counters, flags, slow_front's scalars (kernels2.hip)
+  if (4 * esz * (uint64_t)std::max<int64_t>({d.lsize, d.vstride, d.rstride, d.dstride, (int64_t)d.nnz + d.N0}) >= (1ull << 32)) return CNL_OK;
+  const size_t wave_bytes = (size_t)d.recwords * 4 + (4 * (size_t)d.prob_doubles) * esz + 128;   // + 128: counters, flags, slow_front's scalars (kernels2.hip)
   size_t maxlds = std::min<size_t>(cnl::max_lds_bytes(), 160 * 1024);
   if (wave_bytes + 512 > maxlds) return CNL_OK;  // does not fit: stay on v1
   // waves per workgroup: small workgroups give the dispatcher freedom; 2 keeps the launch grid moderate
@@ -132,7 +139,11 @@ int setup_v2(cnl_handle* h) {
   while (wpb > 1 && wpb * wave_bytes + 512 > maxlds) wpb--;
   h->wpb2 = wpb;
   h->lds2 = wpb * wave_bytes + 512;
-  if ((rc = dalloc(h, &h->d_gs, (size_t)h->batch * (size_t)d.gs_doubles))) return rc;
+  if (h->f32) {   // (floats behind the double*, like the handle's other element arrays)
+    float* gs = nullptr;
+    if ((rc = dalloc(h, &gs, (size_t)h->batch * (size_t)d.gs_doubles))) return rc;
+    h->d_gs = reinterpret_cast<double*>(gs);
+  } else if ((rc = dalloc(h, &h->d_gs, (size_t)h->batch * (size_t)d.gs_doubles))) return rc;
   h->use_v2 = true;
   h->staged = false;
   if ((rc = dalloc(h, &h->d_status, 1))) return rc;
@@ -197,8 +208,8 @@ int setup_v2(cnl_handle* h) {
       if (launches == 1 || (launches <= 4 && h->ntasks >= 16)) h->lad_mode = o.device_ladder_fused ? 2 : 1;
     }
   }
-  h->v2_solve = P.rec_direct && P.d_outer && P.ncls[1] == 0 && P.ncls[2] == 0 && !o.v1_solve;
-  h->lean = o.lean_kernel && P.rec_direct && P.d_outer && d.count_d && P.ncls[1] == 0 && P.ncls[2] == 0 && P.listprod_fronts == 0;
+  h->v2_solve = !h->f32 && P.rec_direct && P.d_outer && P.ncls[1] == 0 && P.ncls[2] == 0 && !o.v1_solve;
+  h->lean = !h->f32 && o.lean_kernel && P.rec_direct && P.d_outer && d.count_d && P.ncls[1] == 0 && P.ncls[2] == 0 && P.listprod_fronts == 0;
   return CNL_OK;
 }
 
@@ -676,7 +687,8 @@ int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1
 // or (tuning float32_condense) with it.  The handle owns the device plan, float factor panels (with the zero pad per problem of
 // upload_dev_plan), float global scratch where the work area does not fit LDS, and the row lists; on a condensed plan also the
 // condensation lists, the inertia counts of the condensed pivots, and the condensed buffer and reduced solution as FLOAT arrays.
-// Nothing of the register-front, dense or staged state exists for it.
+// Nothing of the dense or staged state exists for it; the register-front state (setup_v2, in floats) only with tuning
+// float32_register_front on a plan whose fronts that kernel takes.
 int create_f32_general_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device) {
   cnl_handle* h = new cnl_handle();
   h->plan = plan; h->device = device; h->batch = h->full_batch = batch; h->f32 = true; h->f32_general = true;
@@ -697,6 +709,9 @@ int create_f32_general_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_
     h->d_d2 = reinterpret_cast<double*>(d2);
     if ((rc = setup_cond_resident(h))) return bail(rc);
   }
+  // tuning float32_register_front: the register-front kernel in float runs newton_system / try_to_factorize between the passes
+  // where the plan's fronts allow it and its LDS block fits; where not, the handle is the float32_condense handle and nothing else
+  if (plan->opt.float32_register_front && plan->C.active && (rc = setup_v2(h))) return bail(rc);
   {
     // factor panels, zero-filled (the pad of every problem stays zero) and padded as a Float64 handle's
     float* L = nullptr;
@@ -780,6 +795,13 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
   // records, no dense routes, no staged execution, no band program.
   cnl::Tuning g = o;
   g.condense = o.float32_condense ? 1 : 0; g.register_front = 0; g.dense_backend = 0; g.general_dense = 0; g.staged = 0; g.band_kernel = 0;
+  if (o.float32_register_front) {
+    // ... or, tuning float32_register_front, with the register-front records of the condensed system, never direct: the call is
+    // the float condensation passes around ONE launch of the register-front kernel in float (solve_ldl!: of the general kernel,
+    // which reads the same panels).  Implies float32_condense.
+    if (!g.float32_condense) g.float32_condense = 1;
+    g.condense = 1; g.register_front = 1; g.direct_records = 0;
+  }
   if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, g)) return rc;
   return create_f32_general_from_plan(hout, plan, rows1, cols1, batch, device);
 }

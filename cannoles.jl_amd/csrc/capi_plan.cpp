@@ -268,7 +268,8 @@ const char* cnl_last_error(void) { return g_err.c_str(); }
 // 0.2.0 (round 4: in-kernel device ladder, cnl_options grew); 0.3.0: cnl_set_active_batch, cnl_outer_compact_dev;
 // 0.3.1: tuning float32_general (Float32 handles on the general multifrontal kernel), no new symbol
 // 0.4.0: cnl_outer_ctl, cnl_outer_*_ex_dev, cnl_outer_hess_mask_dev
-int32_t cnl_version(void) { return 400; }
+// 0.4.1: tuning float32_register_front (the register-front kernel in float for Float32 general handles), no new symbol
+int32_t cnl_version(void) { return 401; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62

@@ -69,10 +69,11 @@ int run_band(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_
 }
 
 // a Float32 handle off the band kernels: the float instantiation of the general kernel serves the three calls of the plugin
-// surface as one classic launch each (on a condensed plan between the float condensation passes), and nothing else.  rhs: the
-// right-hand side the call was given
+// surface as one classic launch each (on a condensed plan between the float condensation passes), and nothing else; with tuning
+// float32_register_front the launch of newton_system / try_to_factorize is the register-front kernel's float instantiation
+// (launch(), below).  rhs: the right-hand side the call was given
 int f32_general_serves(const cnl_handle* h, const cnl::LaunchArgs& a, const double* rhs) {
-  if (h->f32 && (a.skip_done || a.only_if_status || (a.mode == cnl::MODE_NEWTON && !rhs) || !h->f32_general || h->use_v2))
+  if (h->f32 && (a.skip_done || a.only_if_status || (a.mode == cnl::MODE_NEWTON && !rhs) || !h->f32_general))
     return fail(CNL_ERR_STATE, "this call is not served by the Float32 instantiation of the general kernel, and the handle has no other");
   return CNL_OK;
 }
@@ -89,7 +90,7 @@ int launch(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
   if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));  // events bracket the multifrontal kernel only
   if (h->use_v2 && (a.mode != cnl::MODE_SOLVE || h->v2_solve)) {
     a.scratch = h->d_gs;
-    e = cnl::launch_newton2(h->dp2, h->wpb2, h->lds2, a, stream);
+    e = h->f32 ? cnl::launch_newton2_f32(h->dp2, h->wpb2, h->lds2, a, stream) : cnl::launch_newton2(h->dp2, h->wpb2, h->lds2, a, stream);
     g_launches[1]++;
   } else {
     e = h->f32 ? cnl::launch_newton_f32(h->dp, h->cfg, a, stream) : cnl::launch_newton(h->dp, h->cfg, a, stream);
@@ -139,7 +140,7 @@ SubBatch::SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged) : 
   h->batch = nb;
   // (factor panels, scratch, condensed buffer and reduced solution hold the handle's element type behind their double*)
   h->d_L = elem_offset(h, h->d_L, b0 * h->dp.lsize);
-  if (h->d_gs) h->d_gs += b0 * h->dp2.gs_doubles;
+  if (h->d_gs) h->d_gs = elem_offset(h, h->d_gs, b0 * h->dp2.gs_doubles);
   if (h->d_scratch) h->d_scratch = elem_offset(h, h->d_scratch, b0 * (int64_t)h->dp.work_doubles);
   if (h->d_cbuf) h->d_cbuf = elem_offset(h, h->d_cbuf, b0 * C.cstride);
   if (h->d_d2) h->d_d2 = elem_offset(h, h->d_d2, b0 * C.N2);

@@ -155,6 +155,9 @@ struct cnl_handle {
   // (element counts as for double: dp.lsize and dp.work_doubles count elements).  It keeps a real factor: the solve is two sweeps.
   // With tuning float32_condense = 1 the plan is that analysis WITH condensation (C.active): the handle also owns dc, d_xpos / d_xzer
   // and FLOAT arrays behind d_cbuf / d_d2, and a call is condense -> the one classic launch on d_cbuf -> expand, all in float.
+  // With tuning float32_register_front = 1 that plan also has register-front records (never direct) and setup_v2 may set use_v2:
+  // dp2, wpb2 / lds2 and a FLOAT global scratch behind d_gs (every "doubles" of dp2 counts floats); newton_system / factorize then
+  // launch the register-front kernel's float instantiation, the solve stays on the general kernel (v2_solve, lean, staged: false).
   bool f32_general = false;
 };
 

@@ -208,6 +208,11 @@ hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const Launch
 hipError_t launch_newton_f32(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream);
 bool newton_f32_has(int tpp, int ppb, bool lds_work);
 hipError_t launch_newton2(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream);
+// the register-front kernel on Float32 data (a Float32 general handle with tuning float32_register_front): a.vals / rhs / d / L /
+// scratch / rho_old / rho hold float arrays (stored through the double* fields), a.params the Float32 parameters widened to double;
+// every size of P that says "doubles" counts floats, lds_bytes is computed with 4-byte elements (the record area stays in 32-bit
+// words).  MODE_NEWTON and MODE_FACTOR on non-direct records only: anything else is hipErrorInvalidConfiguration.
+hipError_t launch_newton2_f32(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream);
 // one attempt at the rho given in vals, stage by stage (stage_ptr: host array of nstages + 1 task offsets)
 hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, LaunchArgs a, const int32_t* stage_ptr, int nstages, hipStream_t stream);
 hipError_t launch_condense(const DevCond& C, const double* vals, const double* rhs, double* cbuf, int slot_begin, int slot_end,

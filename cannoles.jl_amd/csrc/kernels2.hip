@@ -25,6 +25,8 @@
 //    offsets were fixed on the host; the few large ones (and the staging of
 //    fronts of order > 32) use a per-problem global scratch instead.
 //  * L rows are stored to HBM straight from registers at their pivot step.
+//  * one body for both element types: double, and float for Float32 general handles (tuning float32_register_front; the plain
+//    instantiation in both LATE settings only — launch_newton2_f32 below).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -71,12 +73,24 @@ __device__ __forceinline__ T* as_global(T* p) {
   return (T*)(__attribute__((address_space(1))) T*)p;
 }
 
+// The kernel is one body for both element types (T = double, or float on a Float32 handle: DESIGN section 9.3).  Sizes the plan
+// gives "in doubles" count ELEMENTS of T; byte offsets are element offsets << Real<T>::SH; the record area stays in 32-bit words.
+template <class T> struct Real;
+template <> struct Real<double> { typedef double2 T2; static constexpr int SH = 3; };
+template <> struct Real<float> { typedef float2 T2; static constexpr int SH = 2; };
+template <class T>
+__device__ __forceinline__ typename Real<T>::T2 zero2() { typename Real<T>::T2 z; z.x = 0; z.y = 0; return z; }
+
 // broadcast lane (group base + a) of a TE-lane group
 template <int TE>
 __device__ __forceinline__ double bcast(double v, int a, int grp4) {
   int lo = __builtin_amdgcn_ds_bpermute(grp4 + a * 4, __double2loint(v));
   int hi = __builtin_amdgcn_ds_bpermute(grp4 + a * 4, __double2hiint(v));
   return __hiloint2double(hi, lo);
+}
+template <int TE>
+__device__ __forceinline__ float bcast(float v, int a, int grp4) {
+  return __int_as_float(__builtin_amdgcn_ds_bpermute(grp4 + a * 4, __float_as_int(v)));
 }
 
 // w / d through a refined reciprocal: shorter dependent chain than the IEEE expansion (no scaling /
@@ -91,6 +105,9 @@ __device__ __forceinline__ double fast_div(double w, double d) {
   const double res = fma(-d, q, w);
   return fma(res, r, q);
 }
+// Float32: the correctly rounded float division, subnormals kept, as in kernels.hip and the float condensation passes (the
+// oracle's rounding: rho, the inertia decisions and with them nfact compare bit for bit)
+__device__ __forceinline__ float fast_div(float w, float d) { return w / d; }
 
 template <int CTRL>
 __device__ __forceinline__ double dpp_mov(double v) {
@@ -100,10 +117,14 @@ __device__ __forceinline__ double dpp_mov(double v) {
   int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
   return __hiloint2double(hi, lo);
 }
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
 
 // sum over the TE lanes of a group, result in every lane
-template <int TE>
-__device__ __forceinline__ double gsum(double v) {
+template <int TE, class T>
+__device__ __forceinline__ T gsum(T v) {
   v += dpp_mov<0x128>(v);  // row_ror:8
   v += dpp_mov<0x124>(v);  // row_ror:4
   v += dpp_mov<0x122>(v);  // row_ror:2
@@ -113,12 +134,13 @@ __device__ __forceinline__ double gsum(double v) {
   return v;
 }
 
+template <class T>
 struct Ctx2 {
-  const double* vals;   // batch base
-  const double* rhs;
-  double* L;
-  double* gs;           // global scratch base
-  double* dout;
+  const T* vals;   // batch base
+  const T* rhs;
+  T* L;
+  T* gs;           // global scratch base
+  T* dout;
   int batch;
 };
 
@@ -131,7 +153,7 @@ struct Ctx2 {
 // The rows are spelled as individual scalars through the X-macro lists of elim_lists.inc.
 #include "elim_lists.inc"
 
-#define CNL_DECL(k) double r##k;
+#define CNL_DECL(k) T r##k;
 // lanes b > row read past the row: harmless garbage in the unused upper triangle (staging is padded)
 #define CNL_LOAD(k) { const int a_ = top - k > 0 ? top - k : 0; r##k = Fs[tri2(a_) + b]; }  /* rows below 0: unused copies of row 0 */
 // The pivot row w (one entry per lane, the pivot d in lane i) is published once per pivot in LDS, undivided
@@ -139,11 +161,16 @@ struct Ctx2 {
 // its column with  F(a,b) -= w_a * lv  where the w_a come back two rows at a time with one broadcast 16-byte
 // read.  One LDS round trip per pivot sits on the dependent chain (publish -> read), no cross-lane shuffles.
 #define CNL_STEPA(km1, k) r##km1 = fma(-lb[1], lv, r##k);
+// (float: lb + k is 4-byte aligned only, so the pair is two 4-byte reads, which the compiler may pair as a read2)
 #define CNL_STEPP(km1, k, kp1)                                                     \
-  {                                                                                \
+  if constexpr (sizeof(T) == 8) {                                                  \
     const double2 l2_ = *reinterpret_cast<const double2*>(lb + k);                 \
     r##km1 = fma(-l2_.x, lv, r##k);                                                \
     r##k = fma(-l2_.y, lv, r##kp1);                                                \
+  } else {                                                                         \
+    const T lx_ = lb[k], ly_ = lb[k + 1];                                          \
+    r##km1 = fma(-lx_, lv, r##k);                                                  \
+    r##k = fma(-ly_, lv, r##kp1);                                                  \
   }
 #define CNL_CHK(k) if (k >= i) goto rows_done;  /* rows i-k >= 1 only (row 0 is the unused rhs-row diagonal) */
 // Update-matrix rows are stored in ASCENDING row order with all lanes active: the lanes b > a of row a
@@ -156,11 +183,12 @@ struct Ctx2 {
 // 16 row loads are one base address plus immediate offsets; lanes past the diagonal read entries of later rows (never used)
 #define CNL_LOADS(k) r##k = Fss[((15 - k) * (16 - k)) / 2];
 #define CNL_DEFINE_ELIM(NAME, INL, TEV, GFS, ALL, REV, STEPS, LOADM)                                                   \
-  __device__ INL void NAME(int P_prob_doubles, int P_u2_peak, long long P_gs_doubles, long long P_lsize, double* cL_,   \
-                           double* cgs_, int cbatch, int lane, int prob0, int pass,                                   \
-                           int f, int nupd, long long lptr, int uoff, int fsoff, bool uglob, double* pbase0,          \
-                           int* cnt, double eig_tol) {                                                                 \
-    Ctx2 c;                                                                                                            \
+  template <class T>                                                                                                   \
+  __device__ INL void NAME(int P_prob_doubles, int P_u2_peak, long long P_gs_doubles, long long P_lsize, T* cL_,        \
+                           T* cgs_, int cbatch, int lane, int prob0, int pass,                                        \
+                           int f, int nupd, long long lptr, int uoff, int fsoff, bool uglob, T* pbase0,               \
+                           int* cnt, T eig_tol) {                                                                      \
+    Ctx2<T> c;                                                                                                         \
     c.L = as_global(cL_); c.gs = as_global(cgs_); c.batch = cbatch;                                                    \
     constexpr int TE_ = TEV;                                                                                           \
     constexpr int PPW = 64 / TE_;                                                                                      \
@@ -174,27 +202,27 @@ struct Ctx2 {
     /* out-of-line calls, spilled, and every reload from scratch waits for ALL outstanding prefetches (vmcnt) */       \
     asm volatile("" : "+v"(pc32_));                                                                                    \
     const long long pclamp = pc32_;                                                                                    \
-    double* pb = pbase0 + gp * P_prob_doubles;                                                                         \
-    const double* Fs = GFS ? (c.gs + pclamp * P_gs_doubles + fsoff) : (pb + P_u2_peak);                                \
-    double* Lp = c.L + pclamp * P_lsize + lptr;                                                                        \
+    T* pb = pbase0 + gp * P_prob_doubles;                                                                              \
+    const T* Fs = GFS ? (c.gs + pclamp * P_gs_doubles + fsoff) : (pb + P_u2_peak);                                     \
+    T* Lp = c.L + pclamp * P_lsize + lptr;                                                                             \
     const int tu = tri2(1 + nupd);                                                                                     \
     const int top = f - 1;                                                                                             \
-    const double* Fss = Fs + (top - 15) * 16 + b;                                                                      \
-    double* lb = pb + P_u2_peak; /* the LDS staging area is dead once the rows are in registers */                     \
+    const T* Fss = Fs + (top - 15) * 16 + b;                                                                           \
+    T* lb = pb + P_u2_peak; /* the LDS staging area is dead once the rows are in registers */                          \
     (void)Fss;                                                                                                         \
     ALL(CNL_DECL)                                                                                                      \
     ALL(LOADM)                                                                                                         \
     int npos = 0, nzer = 0;                                                                                            \
     (void)grp4;                                                                                                        \
     for (int i = top; i > nupd; i--) {                                                                                 \
-      const double w = r0;                                                                                             \
+      const T w = r0;                                                                                                  \
       {                                                                                                                \
         int li_ = i - b;                                                                                               \
         li_ = li_ >= 0 ? li_ : TE_ + 1; /* lanes b > i park their value in an unused slot */                           \
         lb[li_] = w;                                                                                                   \
       }                                                                                                                \
-      const double dpiv = lb[0];                                                                                       \
-      const double lv = fast_div(w, dpiv);                                                                             \
+      const T dpiv = lb[0];                                                                                            \
+      const T lv = fast_div(w, dpiv);                                                                                  \
       npos += dpiv > eig_tol;                                                                                          \
       nzer += fabs(dpiv) <= eig_tol;                                                                                   \
       if (valid && b <= i) Lp[tri2(i) - tu + b] = (b == i) ? dpiv : lv;                                               \
@@ -205,11 +233,11 @@ struct Ctx2 {
     if (b == 0) { cnt[gp * 2] += npos; cnt[gp * 2 + 1] += nzer; }                                                      \
     if (uglob) {                                                                                                       \
       if (valid) {                                                                                                     \
-        double* Ug = c.gs + pclamp * P_gs_doubles + uoff;                                                              \
+        T* Ug = c.gs + pclamp * P_gs_doubles + uoff;                                                                   \
         REV(CNL_USTG)                                                                                                  \
       }                                                                                                                \
     } else {                                                                                                           \
-      double* Ul = pb + uoff;                                                                                          \
+      T* Ul = pb + uoff;                                                                                               \
       REV(CNL_USTL)                                                                                                    \
     }                                                                                                                  \
   }
@@ -239,45 +267,51 @@ struct Ctx2 {
 // systems/s: its waits are short anyway and the burst of ten stores sits in front of the next gathers — so the kernel is
 // compiled both ways (template parameter LATE) and the launcher chooses by the wavefronts in flight.
 #define CNL_LPEND_LIST(M) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15)
+template <class T>
 struct LPend {
-#define CNL_LP_MEMBER(i) double v##i;
+#define CNL_LP_MEMBER(i) T v##i;
   CNL_LPEND_LIST(CNL_LP_MEMBER)
 #undef CNL_LP_MEMBER
   unsigned pm;     // pivot positions whose rows are pending (0: nothing)
   unsigned lofs;   // per-lane byte offset into the factor of the wave's first problem
-  long long lptr;  // factor offset (doubles) of the front
+  long long lptr;  // factor offset (elements) of the front
 };
 #define CNL_LROW_OUT(i)                                                                                                              \
   if constexpr (LATE) LP.v##i = (bm_ == i) ? dpiv : lv;                                                                              \
-  else if (bm_ <= i) *reinterpret_cast<double*>(L_wb + (lofs + ((unsigned)tri2(i) << 3))) = (bm_ == i) ? dpiv : lv;
-__device__ __forceinline__ void flush_lrows(LPend& LP, char* L_wb0, int bm_) {
+  else if (bm_ <= i) *reinterpret_cast<T*>(L_wb + (lofs + ((unsigned)tri2(i) << Real<T>::SH))) = (bm_ == i) ? dpiv : lv;
+template <class T>
+__device__ __forceinline__ void flush_lrows(LPend<T>& LP, char* L_wb0, int bm_) {
   if (LP.pm == 0) return;
-  char* L_wb = L_wb0 + (LP.lptr << 3);
+  char* L_wb = L_wb0 + (LP.lptr << Real<T>::SH);
   const unsigned lofs = LP.lofs;
 #define CNL_LP_FLUSH(i)                                                                                                   \
   if (LP.pm & (1u << i)) {                                                                                                \
     asm volatile("" : "+v"(bm_));                                                                                         \
-    if (bm_ <= i) *reinterpret_cast<double*>(L_wb + (lofs + ((unsigned)tri2(i) << 3))) = LP.v##i;                         \
+    if (bm_ <= i) *reinterpret_cast<T*>(L_wb + (lofs + ((unsigned)tri2(i) << Real<T>::SH))) = LP.v##i;                    \
   }
   CNL_LPEND_LIST(CNL_LP_FLUSH)
 #undef CNL_LP_FLUSH
   LP.pm = 0;
 }
-#define CNL_DPPF(X, W, NL, A) \
-  asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:" #A " row_mask:0xf bank_mask:0xf" : "+v"(X) : "v"(W), "v"(NL));
+// (float data: the same instruction on 32 bits, v_fmac_f32_dpp; the row broadcast and the wait states are the same)
+#define CNL_DPPF(X, W, NL, A)                                                                                                          \
+  if constexpr (sizeof(T) == 8) asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:" #A " row_mask:0xf bank_mask:0xf" : "+v"(X) : "v"(W), "v"(NL)); \
+  else asm volatile("v_fmac_f32_dpp %0, %1, %2 row_newbcast:" #A " row_mask:0xf bank_mask:0xf" : "+v"(X) : "v"(W), "v"(NL));
 // first DPP read of a row the previous pivot's updates wrote: hipcc pads no hazards inside asm (VALU write -> DPP read: 2 wait states)
-#define CNL_DPPF_NOP(X, W, NL, A) \
-  asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:" #A " row_mask:0xf bank_mask:0xf" : "+v"(X) : "v"(W), "v"(NL));
-#define CNL_DPP_DECL(a) double R##a = Fs[(a * (a + 1)) / 2 + b];
+#define CNL_DPPF_NOP(X, W, NL, A)                                                                                                      \
+  if constexpr (sizeof(T) == 8) asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:" #A " row_mask:0xf bank_mask:0xf" : "+v"(X) : "v"(W), "v"(NL)); \
+  else asm volatile("s_nop 1\n\tv_fmac_f32_dpp %0, %1, %2 row_newbcast:" #A " row_mask:0xf bank_mask:0xf" : "+v"(X) : "v"(W), "v"(NL));
+#define CNL_REAL T
+#define CNL_DPP_DECL(a) T R##a = Fs[(a * (a + 1)) / 2 + b];
 #define CNL_DPP_PRE(i)                                                                                    \
-  const double lv = CNL_DPP_DIV(w_, dpiv);                                                                \
+  const T lv = CNL_DPP_DIV(w_, dpiv);                                                                     \
   npos += dpiv > eig_tol;                                                                                 \
   nzer += fabs(dpiv) <= eig_tol;                                                                          \
   /* the lane number is made opaque per pivot: the sixteen (b <= i) and sixteen (b == i) lane masks would otherwise be hoisted  */ \
   /* out of the fronts loop into 64 SGPRs, spilled to VGPR lanes and fetched back with two v_readlane each (round 2 ISA)       */ \
   asm volatile("" : "+v"(bm_));                                                                           \
   CNL_LROW_OUT(i)                                                                                         \
-  const double nl_ = -lv;
+  const T nl_ = -lv;
 #define CNL_DPP_POST(i)
 #define CNL_DPP_USTG(a) if (a <= nupd) Ug[tri2(a) + b] = R##a;
 #define CNL_DPP_USTL(a) if (a <= nupd) Ul[tri2(a) + b] = R##a;
@@ -288,12 +322,13 @@ __device__ __forceinline__ void flush_lrows(LPend& LP, char* L_wb0, int bm_) {
 // and that instruction (14 cycles) is what the elimination phase is made of.
 constexpr int CNL_BAND_HW = 4;
 #define CNL_DPPU(I, A, RA) if constexpr (BNF == 0 || (A) < BNF || (A) >= (I) - CNL_BAND_HW) { CNL_DPPF(RA, w_, nl_, A) }
-template <bool LATE, int BNF>
-__device__ __forceinline__ void eliminate16_dpp(int P_prob_doubles, int P_u2_peak, long long P_gs_doubles, long long P_lsize, double* cL_,
-                                                double* cgs_, int cbatch, int lane, int prob0, int f, int nupd, long long lptr, int uoff,
-                                                bool uglob, double* pbase0, int* cnt, double eig_tol, LPend& LP) {
-  double* Lg = as_global(cL_);
-  double* gsg = as_global(cgs_);
+template <bool LATE, int BNF, class T>
+__device__ __forceinline__ void eliminate16_dpp(int P_prob_doubles, int P_u2_peak, long long P_gs_doubles, long long P_lsize, T* cL_,
+                                                T* cgs_, int cbatch, int lane, int prob0, int f, int nupd, long long lptr, int uoff,
+                                                bool uglob, T* pbase0, int* cnt, T eig_tol, LPend<T>& LP) {
+  typedef typename Real<T>::T2 T2;
+  T* Lg = as_global(cL_);
+  T* gsg = as_global(cgs_);
   const int gp = lane >> 4;
   const int b = lane & 15;
   const int prob = prob0 + gp;
@@ -301,19 +336,19 @@ __device__ __forceinline__ void eliminate16_dpp(int P_prob_doubles, int P_u2_pea
   int pc32_ = valid ? prob : prob0;
   asm volatile("" : "+v"(pc32_));  // opaque: the per-lane factor base must not be hoisted out of the fronts loop and kept alive (or spilled)
   const long long pclamp = pc32_;
-  double* pb = pbase0 + gp * P_prob_doubles;
-  const double* Fs = pb + P_u2_peak + b;
+  T* pb = pbase0 + gp * P_prob_doubles;
+  const T* Fs = pb + P_u2_peak + b;
   const int prob0u = __builtin_amdgcn_readfirstlane(prob0);
   char* L_wb = reinterpret_cast<char*>(Lg + (long long)prob0u * P_lsize + lptr);
   const int tu = tri2(1 + nupd);
-  const unsigned lofs = ((valid ? (unsigned)gp : 0u) * (unsigned)P_lsize + (unsigned)b - (unsigned)tu) * 8u;
+  const unsigned lofs = ((valid ? (unsigned)gp : 0u) * (unsigned)P_lsize + (unsigned)b - (unsigned)tu) * (unsigned)sizeof(T);
   const int top = f - 1;
-  { const double* Fs_ = Fs; (void)Fs_; }
+  { const T* Fs_ = Fs; (void)Fs_; }
 #undef CNL_DPP_DECL
-#define CNL_DPP_DECL(a) double R##a = Fs[(a * (a + 1)) / 2];
+#define CNL_DPP_DECL(a) T R##a = Fs[(a * (a + 1)) / 2];
   CNL_DPP_ROWS(CNL_DPP_DECL)
   int npos = 0, nzer = 0;
-  const double one_ = 1.0;
+  const T one_ = 1.0;
   // bit I set <=> I is a pivot position (nupd < I <= top), wave-uniform
   int bm_ = valid ? b : 64;  // column of this lane; lanes of problems past the batch never store
   const unsigned pm_ = __builtin_amdgcn_readfirstlane(((2u << top) - 1u) & ~((2u << nupd) - 1u));
@@ -324,21 +359,21 @@ __device__ __forceinline__ void eliminate16_dpp(int P_prob_doubles, int P_u2_pea
   // update matrix: rows 0 .. nupd in ascending order with all lanes active (see CNL_USTG)
   if (uglob) {
     if (valid) {
-      double* Ug = gsg + pclamp * P_gs_doubles + uoff;
+      T* Ug = gsg + pclamp * P_gs_doubles + uoff;
       CNL_DPP_ROWS(CNL_DPP_USTG)
     }
   } else {
-    double* Ul = pb + uoff;
+    T* Ul = pb + uoff;
     CNL_DPP_ROWS(CNL_DPP_USTL)
   }
   // The image is dead: zero it for the NEXT front here (LDS executes a wavefront's operations in order), so that the next front
   // starts with its extend-add instead of five stores and a barrier.  Behind the update-matrix store: its rows are written
   // with all sixteen lanes and may run up to 15 doubles past the top of the stack, into the image.
   {
-    double2* z2 = reinterpret_cast<double2*>(pb + P_u2_peak) + b;
+    T2* z2 = reinterpret_cast<T2*>(pb + P_u2_peak) + b;
 #pragma unroll
-    for (int j = 0; j < 4; j++) z2[16 * j] = make_double2(0.0, 0.0);
-    if (b < FAST_IMG_DOUBLES / 2 - 64) z2[64] = make_double2(0.0, 0.0);
+    for (int j = 0; j < 4; j++) z2[16 * j] = zero2<T>();
+    if (b < FAST_IMG_DOUBLES / 2 - 64) z2[64] = zero2<T>();
   }
 }
 CNL_DEFINE_ELIM(eliminate16g, __attribute__((noinline)), 16, true, CNL_ALL16, CNL_REV16, CNL_STEPS16, CNL_LOAD)
@@ -347,16 +382,16 @@ CNL_DEFINE_ELIM(eliminate32g, __attribute__((noinline)), 32, true, CNL_ALL32, CN
 CNL_DEFINE_ELIM(eliminate64, __attribute__((noinline)), 64, true, CNL_ALL64, CNL_REV64, CNL_STEPS64, CNL_LOAD)
 
 // backward substitution of one front for the problems of a pass
-template <int TE>
-__device__ __attribute__((noinline)) void back_front_call(int P_prob_doubles, long long P_lsize, long long P_dstride, double* cL_, double* cdout_,
+template <int TE, class T>
+__device__ __attribute__((noinline)) void back_front_call(int P_prob_doubles, long long P_lsize, long long P_dstride, T* cL_, T* cdout_,
                                                      int cbatch, int lane, int prob0, int pass, const int* rec, int f, int nupd, int npiv,
-                                                     long long lptr, int xoff, int pxoff, double* pbase0, const int* okflag);
+                                                     long long lptr, int xoff, int pxoff, T* pbase0, const int* okflag);
 
-template <int TE>
-__device__ __forceinline__ void back_front(int P_prob_doubles, long long P_lsize, long long P_dstride, double* cL_, double* cdout_,
+template <int TE, class T>
+__device__ __forceinline__ void back_front(int P_prob_doubles, long long P_lsize, long long P_dstride, T* cL_, T* cdout_,
                                            int cbatch, int lane, int prob0, int pass, const int* rec, int f, int nupd, int npiv,
-                                           long long lptr, int xoff, int pxoff, double* pbase0, const int* okflag) {
-  Ctx2 c;
+                                           long long lptr, int xoff, int pxoff, T* pbase0, const int* okflag) {
+  Ctx2<T> c;
   c.L = as_global(cL_); c.dout = as_global(cdout_); c.batch = cbatch;
   constexpr int PPW = 64 / TE;
   const int gp = pass * PPW + (TE == 64 ? 0 : lane / TE);
@@ -364,20 +399,20 @@ __device__ __forceinline__ void back_front(int P_prob_doubles, long long P_lsize
   const int prob = prob0 + gp;
   const bool valid = prob < c.batch && okflag[gp] != 0;
   const long long pclamp = prob < c.batch ? prob : prob0;
-  double* xs = pbase0 + gp * P_prob_doubles;
-  const double* Lp = c.L + pclamp * P_lsize + lptr;
+  T* xs = pbase0 + gp * P_prob_doubles;
+  const T* Lp = c.L + pclamp * P_lsize + lptr;
   const int tu = tri2(1 + nupd);
-  double xb = 0.0;
+  T xb = 0.0;
   if (pxoff >= 0 && b >= 1 && b <= nupd) xb = xs[pxoff + rec[B_HDR + b]];
   if (pxoff == B_PX_GLOBAL && b >= 1 && b <= nupd) xb = -__hip_atomic_load(c.dout + pclamp * P_dstride + rec[B_HDR + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   wsync();
   // pivots in blocks of KB: the panel rows of a block are loaded together (row i: entries 0..i; lane b takes entry b)
   constexpr int KB = TE - 1 < 8 ? TE - 1 : 8;
   for (int k0 = 0; k0 < npiv; k0 += KB) {
-    double lrow[KB];
+    T lrow[KB];
 #pragma unroll
     for (int k = 0; k < KB; k++) {
-      double v0 = 0.0;
+      T v0 = 0.0;
       if (k0 + k < npiv) {
         const int i = nupd + 1 + k0 + k;
         if (b < i) v0 = Lp[tri2(i) - tu + b];
@@ -388,10 +423,10 @@ __device__ __forceinline__ void back_front(int P_prob_doubles, long long P_lsize
     for (int k = 0; k < KB; k++) {
       if (k0 + k < npiv) {
         const int i = nupd + 1 + k0 + k;
-        const double t = (b >= 1 && b < i) ? lrow[k] * xb : 0.0;
-        const double s = gsum<TE>(t);
-        const double z = bcast<TE>(lrow[k], 0, (lane - b) * 4);
-        const double xi = z - s;
+        const T t = (b >= 1 && b < i) ? lrow[k] * xb : T(0);
+        const T s = gsum<TE>(t);
+        const T z = bcast<TE>(lrow[k], 0, (lane - b) * 4);
+        const T xi = z - s;
         if (b == i) {
           xb = xi;
           if (valid) c.dout[pclamp * P_dstride + rec[B_HDR + 1 + nupd + k0 + k]] = -xi;
@@ -402,11 +437,11 @@ __device__ __forceinline__ void back_front(int P_prob_doubles, long long P_lsize
   if (b >= 1 && b < f) xs[xoff + b] = xb;
 }
 
-template <int TE>
-__device__ __attribute__((noinline)) void back_front_call(int P_prob_doubles, long long P_lsize, long long P_dstride, double* cL_, double* cdout_,
+template <int TE, class T>
+__device__ __attribute__((noinline)) void back_front_call(int P_prob_doubles, long long P_lsize, long long P_dstride, T* cL_, T* cdout_,
                                                      int cbatch, int lane, int prob0, int pass, const int* rec, int f, int nupd, int npiv,
-                                                     long long lptr, int xoff, int pxoff, double* pbase0, const int* okflag) {
-  back_front<TE>(P_prob_doubles, P_lsize, P_dstride, cL_, cdout_, cbatch, lane, prob0, pass, rec, f, nupd, npiv, lptr, xoff, pxoff, pbase0, okflag);
+                                                     long long lptr, int xoff, int pxoff, T* pbase0, const int* okflag) {
+  back_front<TE, T>(P_prob_doubles, P_lsize, P_dstride, cL_, cdout_, cbatch, lane, prob0, pass, rec, f, nupd, npiv, lptr, xoff, pxoff, pbase0, okflag);
 }
 
 // Out-of-line handling of the rare fronts (order > 16, or staged in the global scratch): staging,
@@ -420,30 +455,31 @@ struct SlowArgs {  // the few plan scalars the out-of-line path needs (passed by
 // (round 4: the eight plan scalars come through the wavefront's LDS block — SLOW_ARGS_AT, written once per kernel — so that every
 //  argument of the call travels in registers: with 25 parameters seven dwords went over the stack)
 constexpr int SLOW_ARGS_AT = 16;   // ints behind `cnt`: eight 64-bit slots
+template <class T>
 __device__ __attribute__((noinline)) void slow_front(const int* prec_,
-                                                     const double* vals_, const double* rhs_, double* L_,
-                                                     double* gs_, int batch, int lane, int prob0, const int* rec, int roff,
-                                                     double* pbase0, int* cnt, double eig_tol, double rho, bool ovr, bool count_d) {
+                                                     const T* vals_, const T* rhs_, T* L_,
+                                                     T* gs_, int batch, int lane, int prob0, const int* rec, int roff,
+                                                     T* pbase0, int* cnt, T eig_tol, T rho, bool ovr, bool count_d) {
   SlowArgs P;
   {
     const long long* ps = reinterpret_cast<const long long*>(cnt + SLOW_ARGS_AT);
     P.prob_doubles = (int)rfl((int)ps[0]); P.u2_peak = (int)rfl((int)ps[1]); P.nnz = (int)rfl((int)ps[2]); P.rho_begin = (int)rfl((int)ps[3]);
     P.gs_doubles = ps[4]; P.lsize = ps[5]; P.vstride = ps[6]; P.rstride = ps[7]; P.rec = prec_;
   }
-  const double* vals = as_global(vals_);
-  const double* rhsb = as_global(rhs_);
-  double* Lb = as_global(L_);
-  double* gsb = as_global(gs_);
+  const T* vals = as_global(vals_);
+  const T* rhsb = as_global(rhs_);
+  T* Lb = as_global(L_);
+  T* gsb = as_global(gs_);
   const int* grec = as_global(P.rec) + roff;
   const int g = lane >> 4, l = lane & 15;
   const int prob = prob0 + g;
   const bool valid = prob < batch;
   const long long pclamp = valid ? prob : prob0;
-  const double* myvals = vals + pclamp * P.vstride;
-  const double* myrhs = rhs_ ? rhsb + pclamp * P.rstride : nullptr;
-  double* mygs = gsb + pclamp * P.gs_doubles;
-  double* myU = pbase0 + g * P.prob_doubles;
-  double* myFs = myU + P.u2_peak;
+  const T* myvals = vals + pclamp * P.vstride;
+  const T* myrhs = rhs_ ? rhsb + pclamp * P.rstride : nullptr;
+  T* mygs = gsb + pclamp * P.gs_doubles;
+  T* myU = pbase0 + g * P.prob_doubles;
+  T* myFs = myU + P.u2_peak;
   const int npiv = rfl(rec[R_NPIV]), nupd = rfl(rec[R_NUPD]), nasm = rfl(rec[R_NASM]);
   const int nchild = rfl(rec[R_NCHILD]), uoff = rfl(rec[R_UOFF]), flags = rfl(rec[R_FLAGS]), fsoff = rfl(rec[R_FSOFF]);
   const int cls = flags >> 8, aoff = rfl(rec[R_ASM_OFF]), coff = rfl(rec[R_CHILD_OFF]);
@@ -457,20 +493,20 @@ __device__ __attribute__((noinline)) void slow_front(const int* prec_,
     wsync();
     for (int e = l; e < nasm; e += 16) {
       const int src = grec[aoff + e], pos = grec[aoff + nasm + e];
-      double v = 0.0;
-      if (src >= P.nnz) v = myrhs ? myrhs[src - P.nnz] : 0.0;
+      T v = 0.0;
+      if (src >= P.nnz) v = myrhs ? myrhs[src - P.nnz] : T(0);
       else v = (ovr && src >= P.rho_begin) ? rho : myvals[src];
       __hip_atomic_fetch_add(&myFs[pos], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     }
   } else {
-    double* Fg = mygs + fsoff;
+    T* Fg = mygs + fsoff;
     for (int t = l; t < tf; t += 16) Fg[t] = 0.0;
     gsync();
     for (int e0 = 0; e0 < nasm; e0 += 16) {  // one round of 16 entries at a time: duplicates of a slot sit in different rounds
       const int e = e0 + l;
       const int src = grec[aoff + e], pos = grec[aoff + nasm + e];
-      double v = 0.0;
-      if (src >= P.nnz) v = myrhs ? myrhs[src - P.nnz] : 0.0;
+      T v = 0.0;
+      if (src >= P.nnz) v = myrhs ? myrhs[src - P.nnz] : T(0);
       else v = (ovr && src >= P.rho_begin) ? rho : myvals[src];
       if (valid) Fg[pos] += v;
       gsync();
@@ -484,7 +520,7 @@ __device__ __attribute__((noinline)) void slow_front(const int* prec_,
     const int raw_off = aoff + 2 * nasm;
     int np_ = 0, nz_ = 0;
     for (int t = l; t < nrd_own; t += 16) {
-      const double dv = myvals[grec[raw_off + t]];
+      const T dv = myvals[grec[raw_off + t]];
       np_ += dv > eig_tol;
       nz_ += fabs(dv) <= eig_tol;
     }
@@ -496,13 +532,13 @@ __device__ __attribute__((noinline)) void slow_front(const int* prec_,
     if (gfs) gsync(); else wsync();
     for (int e = l; e < nprod; e += 16) {
       const int pos = grec[prod_off + 2 * e], w = grec[prod_off + 2 * e + 1];
-      double x[3];
+      T x[3];
 #pragma unroll
       for (int q = 0; q < 3; q++) {
         const int src = grec[raw_off + ((w >> (10 * q)) & 1023)];
-        x[q] = src >= P.nnz ? (myrhs ? myrhs[src - P.nnz] : 0.0) : myvals[src];
+        x[q] = src >= P.nnz ? (myrhs ? myrhs[src - P.nnz] : T(0)) : myvals[src];
       }
-      const double v = fast_div(-(x[0] * x[1]), x[2]);
+      const T v = fast_div(-(x[0] * x[1]), x[2]);
       if (!gfs) __hip_atomic_fetch_add(&myFs[pos], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
       else if (valid) __hip_atomic_fetch_add(&mygs[fsoff + pos], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -512,17 +548,17 @@ __device__ __attribute__((noinline)) void slow_front(const int* prec_,
   for (int ci = 0; ci < nchild; ci++) {
     const int cu = rfl(grec[co + C_UOFF]), tuc = rfl(grec[co + C_TUC]), cfl = rfl(grec[co + C_FLAGS]);
     const int* dest = grec + co + C_HDR;
-    const double* Ul = myU + cu;
-    const double* Ug = mygs + cu;
+    const T* Ul = myU + cu;
+    const T* Ug = mygs + cu;
     if (!gfs) {
       for (int t = l; t < tuc; t += 16) {
-        const double u = cfl ? Ug[t] : Ul[t];
+        const T u = cfl ? Ug[t] : Ul[t];
         __hip_atomic_fetch_add(&myFs[dest[t]], u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
       }
     } else {
-      double* Fg = mygs + fsoff;
+      T* Fg = mygs + fsoff;
       for (int t = l; t < tuc; t += 16) {
-        const double u = cfl ? Ug[t] : Ul[t];
+        const T u = cfl ? Ug[t] : Ul[t];
         if (valid) Fg[dest[t]] += u;
       }
       gsync();
@@ -558,11 +594,11 @@ __device__ __attribute__((noinline)) void slow_front(const int* prec_,
 // not loaded.
 #define PREFETCH_ROWS(DST, LPTR, NUPD, NPIV)                                           \
   {                                                                                    \
-    const char* rb_ = L_wb + ((long long)(LPTR) << 3);                                 \
+    const char* rb_ = L_wb + ((long long)(LPTR) << Real<T>::SH);                                 \
     unsigned ro_ = gofs_l;                                                             \
     _Pragma("unroll") for (int k = 0; k < KB; k++) {                                   \
-      if (k < (NPIV)) DST[k] = *reinterpret_cast<const double*>(rb_ + ro_); else DST[k] = 0.0; \
-      ro_ += (unsigned)((NUPD) + 2 + k) << 3;                                          \
+      if (k < (NPIV)) DST[k] = *reinterpret_cast<const T*>(rb_ + ro_); else DST[k] = 0.0; \
+      ro_ += (unsigned)((NUPD) + 2 + k) << Real<T>::SH;                                          \
     }                                                                                  \
   }
 
@@ -572,8 +608,8 @@ __device__ __attribute__((noinline)) void slow_front(const int* prec_,
 // record in one batch; rounds past the end of a list are skipped (the texture addresser is the busiest shared
 // unit of this kernel) and their register is set to zero: a plain "keep the old value" made the compiler merge the
 // guarded values through copies, with a vmcnt(0) wait right behind the first gather.
-#define GATHER_V(SRC) (*reinterpret_cast<const double*>(vals_wb + (((unsigned)(SRC) << 3) + gofs_v)))
-#define GATHER_R(SRC) (*reinterpret_cast<const double*>(rhs_wb + (((unsigned)(SRC) << 3) + gofs_r)))
+#define GATHER_V(SRC) (*reinterpret_cast<const T*>(vals_wb + (((unsigned)(SRC) << Real<T>::SH) + gofs_v)))
+#define GATHER_R(SRC) (*reinterpret_cast<const T*>(rhs_wb + (((unsigned)(SRC) << Real<T>::SH) + gofs_r)))
 #define PREFETCH_VALUES(RECP, AOFF, NASMV, NASM)                                       \
   {                                                                                    \
     const int nv_ = (NASMV);                                                           \
@@ -703,7 +739,7 @@ constexpr int WAVES_PER_SIMD = 2;
 // 162 VGPRs, three wavefronts per SIMD; with the rung loop 213).  FUSED && !STAGED: the sequential launch BEHIND the fused ones
 // (only_if_status): it commits the ladder's rho_old / rho slots, or redoes the call when a wait gave up — the commit is compiled
 // into this instantiation only (in the hot lean kernel the call cost four more spilled SGPRs).
-template <bool STAGED, bool LATE, bool LEAN, bool SOLVE = false, bool FUSED = false>
+template <class T, bool STAGED, bool LATE, bool LEAN, bool SOLVE = false, bool FUSED = false>
 __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const DevPlan2 Pin, const LaunchArgs Ain) {
   DevPlan2 P = Pin;
   P.rec = as_global(Pin.rec); P.brec = as_global(Pin.brec);
@@ -712,6 +748,11 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
   A.scratch = as_global(Ain.scratch); A.rho_old = as_global(Ain.rho_old); A.rho = as_global(Ain.rho);
   A.nfact = as_global(Ain.nfact); A.success = as_global(Ain.success); A.npos = as_global(Ain.npos); A.nzero = as_global(Ain.nzero);
   A.extra_pos = as_global(Ain.extra_pos); A.extra_zer = as_global(Ain.extra_zer);
+  // the element arrays, typed (a Float32 handle's float arrays travel behind the double* fields of LaunchArgs)
+  T* const A_vals = reinterpret_cast<T*>(A.vals); const T* const A_rhs = reinterpret_cast<const T*>(A.rhs); T* const A_d = reinterpret_cast<T*>(A.d);
+  T* const A_L = reinterpret_cast<T*>(A.L); T* const A_scratch = reinterpret_cast<T*>(A.scratch);
+  T* const A_rho_old = reinterpret_cast<T*>(A.rho_old); T* const A_rho = reinterpret_cast<T*>(A.rho);
+  typedef typename Real<T>::T2 T2;
   const int WPB = blockDim.x >> 6;
   extern __shared__ double smem[];
   const int lane = threadIdx.x & 63;
@@ -787,7 +828,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
       // Behind the in-kernel ladder (phase 2 launches): no wait gave up, so its results stand — COMMIT what the ladder must not
       // touch while a sequential redo may still need the caller's inputs: rho_old (in/out) and the rho slots of vals
       // (src/CaNNOLeS.jl:1031,1038,1044-1046).  One wavefront per group of four problems; nothing to do unless a problem climbed.
-      if constexpr (FUSED) if (A.lad && A.mode == MODE_NEWTON && valid_) ladder_commit(as_global(A.lad) + (size_t)widx * LAD_WORDS, g, l, A.rho_old + prob, A.vals + (long long)prob * P.vstride + P.rho_begin, P.nvar);
+      if constexpr (FUSED) if (A.lad && A.mode == MODE_NEWTON && valid_) ladder_commit(as_global(A.lad) + (size_t)widx * LAD_WORDS, g, l, A_rho_old + prob, A_vals + (long long)prob * P.vstride + P.rho_begin, P.nvar);
       return;
     }
     if (A.skip_done && !redo_all && valid_ && as_global(A.success)[prob] == 1) valid_ = false;
@@ -801,14 +842,15 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
   const bool inb = prob < A.batch;
   const long long pclamp = inb ? prob : prob0;
 
-  const int wave_doubles = (P.recwords >> 1) + 4 * P.prob_doubles + 16;
-  double* wbase = smem + wave * wave_doubles;
+  // (elements of T: the record area of recwords 32-bit words, four problems, 128 bytes of counters, flags and slow_front's scalars)
+  const int wave_doubles = (P.recwords >> (Real<T>::SH - 2)) + 4 * P.prob_doubles + (128 >> Real<T>::SH);
+  T* wbase = reinterpret_cast<T*>(smem) + wave * wave_doubles;
   int* recbuf = reinterpret_cast<int*>(wbase);  // forward: one record of up to reccap words; backward: two of breccap
-  double* pbase0 = wbase + (P.recwords >> 1);
+  T* pbase0 = wbase + (P.recwords >> (Real<T>::SH - 2));
   int* cnt = reinterpret_cast<int*>(pbase0 + 4 * P.prob_doubles);
-  double* myU = pbase0 + g * P.prob_doubles;
-  double* myFs = myU + P.u2_peak;
-  double* jraw = myU + P.jraw_off;  // raw values of the current front's products (reciprocal pivots first)
+  T* myU = pbase0 + g * P.prob_doubles;
+  T* myFs = myU + P.u2_peak;
+  T* jraw = myU + P.jraw_off;  // raw values of the current front's products (reciprocal pivots first)
   if constexpr (!LEAN) {   // plan scalars of the out-of-line path (slow_front)
     if (lane == 0) {
       long long* ps = reinterpret_cast<long long*>(cnt + SLOW_ARGS_AT);
@@ -818,31 +860,31 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
     wsync();
   }
 
-  Ctx2 c;
-  c.vals = A.vals; c.rhs = A.rhs; c.L = A.L; c.gs = A.scratch; c.dout = A.d; c.batch = A.batch;
-  const double* myvals = A.vals + pclamp * P.vstride;
-  const bool has_rhs = !(A.mode == MODE_FACTOR || !A.rhs);  // wave-uniform
-  const double* myrhs = has_rhs ? A.rhs + pclamp * P.rstride : nullptr;
-  double* mygs = A.scratch + pclamp * P.gs_doubles;
-  const double eig_tol = A.params[0];
+  Ctx2<T> c;
+  c.vals = A_vals; c.rhs = A_rhs; c.L = A_L; c.gs = A_scratch; c.dout = A_d; c.batch = A.batch;
+  const T* myvals = A_vals + pclamp * P.vstride;
+  const bool has_rhs = !(A.mode == MODE_FACTOR || !A_rhs);  // wave-uniform
+  const T* myrhs = has_rhs ? A_rhs + pclamp * P.rstride : nullptr;
+  T* mygs = A_scratch + pclamp * P.gs_doubles;
+  const T eig_tol = (T)A.params[0];   // (float: narrowed from the widened Float32 parameter, as in newton_kernel<..., float>)
   const int xpos = A.extra_pos ? A.extra_pos[pclamp] : 0, xzer = A.extra_zer ? A.extra_zer[pclamp] : 0;
   // gathers: wave-uniform bases of the first problem of the wave + 32-bit byte offsets (4 problems span < 4 GB)
   const int prob0u = __builtin_amdgcn_readfirstlane(prob0);
-  const char* vals_wb = reinterpret_cast<const char*>(A.vals + (long long)prob0u * P.vstride);
-  const char* rhs_wb = has_rhs ? reinterpret_cast<const char*>(A.rhs + (long long)prob0u * P.rstride) : vals_wb;
+  const char* vals_wb = reinterpret_cast<const char*>(A_vals + (long long)prob0u * P.vstride);
+  const char* rhs_wb = has_rhs ? reinterpret_cast<const char*>(A_rhs + (long long)prob0u * P.rstride) : vals_wb;
   const unsigned gsel = inb ? (unsigned)g : 0u;
-  const unsigned gofs_v = gsel * (unsigned)P.vstride * 8u;
-  const unsigned gofs_r = (gsel * (unsigned)(has_rhs ? P.rstride : P.vstride) - (unsigned)P.nnz) * 8u;  // rhs sources are nnz + index
-  const char* L_wb = reinterpret_cast<const char*>(A.L + (long long)prob0u * P.lsize);
-  const unsigned gofs_l = (gsel * (unsigned)P.lsize + (unsigned)l) * 8u;
+  const unsigned gofs_v = gsel * (unsigned)P.vstride * (unsigned)sizeof(T);
+  const unsigned gofs_r = (gsel * (unsigned)(has_rhs ? P.rstride : P.vstride) - (unsigned)P.nnz) * (unsigned)sizeof(T);  // rhs sources are nnz + index
+  const char* L_wb = reinterpret_cast<const char*>(A_L + (long long)prob0u * P.lsize);
+  const unsigned gofs_l = (gsel * (unsigned)P.lsize + (unsigned)l) * (unsigned)sizeof(T);
 
   // per-problem ladder state, replicated over the 16 lanes of the group
-  double rho = 0.0, wrote = 0.0;
-  double rho_old = (A.mode == MODE_NEWTON) ? A.rho_old[pclamp] : 0.0;
+  T rho = 0.0, wrote = 0.0;
+  T rho_old = (A.mode == MODE_NEWTON) ? A_rho_old[pclamp] : T(0);
   int nfact = 0;
   bool done = !valid, success = false, ovr = false;
-  const double kdec = A.params[2], kinc = A.params[3], klarge = A.params[4], rho0 = A.params[5], rhomax = A.params[6],
-               rhomin = A.params[7];
+  const T kdec = (T)A.params[2], kinc = (T)A.params[3], klarge = (T)A.params[4], rho0 = (T)A.params[5], rhomax = (T)A.params[6],
+          rhomin = (T)A.params[7];
   [[maybe_unused]] int rung = 0;  // fused ladder: factorisations this launch has made of the group
   if constexpr (STAGED) {
     // behind a staged first attempt the problems that failed it enter the ladder at its first rung (src/CaNNOLeS.jl:1030)
@@ -857,11 +899,12 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
   constexpr bool CNL_LEAN = LEAN;
   static_assert(!SOLVE || LEAN, "the solve-only instantiation is a lean one");
   static_assert(!FUSED || !SOLVE, "the fused ladder is an execution of newton_system");
-  if ((SOLVE || (!CNL_LEAN && A.mode == MODE_SOLVE)) && (!STAGED || A.phase == 0)) {
+  // (no float instance runs it: solve_ldl! of a Float32 handle is the general kernel's two sweeps on the same panels)
+  if (sizeof(T) == 8 && (SOLVE || (!CNL_LEAN && A.mode == MODE_SOLVE)) && (!STAGED || A.phase == 0)) {
     const int4* rstream = reinterpret_cast<const int4*>(P.rec);
     int4 R0, R1, R2;
-    double pvr[PVR], prr[2], prh = 0.0;
-    double lr[KB], lrn[KB];
+    T pvr[PVR], prr[2], prh = 0.0;
+    T lr[KB], lrn[KB];
     int roff = t_rec, nxt_off = 0;
     int* recw = recbuf;
     {
@@ -892,7 +935,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
       const int nrd = nrdw & 0xffff, nrawv = nrdw >> 16;
       const long long lptr = (long long)HDRW(hv, R_LPTR_LO) | ((long long)HDRW(hv, R_LPTR_HI) << 31);
       const bool uglob = flags & RF_U_GLOBAL;
-      double* cvec = myFs;  // c_a = entry (a, 0) of the front, a = 0 .. f-1 (a = 0 unused)
+      T* cvec = myFs;  // c_a = entry (a, 0) of the front, a = 0 .. f-1 (a = 0 unused)
       cvec[l] = 0.0;
       const int raw_off = aoff + 2 * nasm;
       const bool rowform = flags & RF_ROWS;
@@ -900,16 +943,16 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
 #pragma unroll
         for (int j = 0; j < PVR; j++)
           if (j * 16 < nrawv) {
-            double v = pvr[j];
+            T v = pvr[j];
             if (j * 16 < nrd) {
-              const double r = fast_div(-1.0, v);
+              const T r = fast_div(T(-1.0), v);
               v = j * 16 + l < nrd ? r : v;
             }
             jraw[j * 16 + l] = v;
           }
         for (int e = PVR * 16 + l; e < nrawv; e += 16) {
-          const double v = myvals[rec[raw_off + e]];
-          jraw[e] = e < nrd ? fast_div(-1.0, v) : v;
+          const T v = myvals[rec[raw_off + e]];
+          jraw[e] = e < nrd ? fast_div(T(-1.0), v) : v;
         }
 #pragma unroll
         for (int q = 0; q < 2; q++)
@@ -931,7 +974,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
         int pw_[ROWS_PW];
 #pragma unroll
         for (int g = 0; g < ROWS_PW; g++) pw_[g] = rw[(2 + ROWS_KM + g) * 16];
-        const double tr = prr[0] * fast_div(-1.0, pvr[ROWS_KM]);
+        const T tr = prr[0] * fast_div(T(-1.0), pvr[ROWS_KM]);
 #pragma unroll
         for (int q = 0; q < ROWS_KM; q++) {
           const int pos = (int)ROW_POS(pw_, ROWS_KM * (ROWS_KM + 1) / 2 + q), prow = tri_row(pos);
@@ -942,7 +985,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
         for (int e = 0; e < nprod; e += 16) {
           const int w = pw[e], pos = w & 255, prow = tri_row(pos);
           if (pos == tri2(prow) && pos < FAST_IMG_TRI) {
-            const double v = jraw[(w >> 8) & 127] * jraw[(w >> 15) & 127] * jraw[(w >> 22) & 127];
+            const T v = jraw[(w >> 8) & 127] * jraw[(w >> 15) & 127] * jraw[(w >> 22) & 127];
             __hip_atomic_fetch_add(&cvec[prow], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
           }
         }
@@ -955,14 +998,14 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
           const int cu = HDRW(cv4, C_UOFF), tuc = HDRW(cv4, C_TUC), cfl = HDRW(cv4, C_FLAGS);
           if (tri2(l) < tuc) {
             const int prow = tri_row(rec[co + C_HDR + tri2(l)]);
-            const double u = cfl ? mygs[cu + l] : myU[cu + l];
+            const T u = cfl ? mygs[cu + l] : myU[cu + l];
             __hip_atomic_fetch_add(&cvec[prow], u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
           }
           co += C_HDR + ((tuc + 3) & ~3);
         }
       }
       wsync();
-      double cv = cvec[l];
+      T cv = cvec[l];
       wsync();
       // next record over the current one, prefetches for the next front
       int nroff = nxt_off;
@@ -1000,11 +1043,11 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
       }
       // substitution over the pivots from the top: lane a holds c_a, row i of the panel is (l_i1 .. l_i,i-1, d_i) in lanes 1..i
       const int tu = tri2(1 + nupd);
-      double* Lcol0 = A.L + pclamp * P.lsize + lptr - tu;  // entry (i, 0) of the panel at tri(i)
+      T* Lcol0 = A_L + pclamp * P.lsize + lptr - tu;  // entry (i, 0) of the panel at tri(i)
       for (int k0 = npiv - 1; k0 >= KB; k0--) {  // fronts with more than KB pivots: their top rows are loaded on demand
         const int i = nupd + 1 + k0;
-        const double lv = A.L[pclamp * P.lsize + lptr + tri2(i) - tu + l];
-        const double ci = bcast<16>(cv, i, (lane - l) * 4);
+        const T lv = A_L[pclamp * P.lsize + lptr + tri2(i) - tu + l];
+        const T ci = bcast<16>(cv, i, (lane - l) * 4);
         if (l == i && valid) Lcol0[tri2(i)] = fast_div(cv, lv);
         if (l >= 1 && l < i) cv = fma(-lv, ci, cv);
       }
@@ -1012,7 +1055,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
       for (int k = KB - 1; k >= 0; k--) {
         if (k < npiv) {
           const int i = nupd + 1 + k;
-          const double ci = bcast<16>(cv, i, (lane - l) * 4);
+          const T ci = bcast<16>(cv, i, (lane - l) * 4);
           if (l == i && valid) Lcol0[tri2(i)] = fast_div(cv, lr[k]);
           if (l >= 1 && l < i) cv = fma(-lr[k], ci, cv);
         }
@@ -1041,7 +1084,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
     const int4* rstream = reinterpret_cast<const int4*>(P.rec);
     const bool needs_fix = __any(ovr) || !has_rhs;  // wave-uniform: some value must be replaced at assembly time
     int4 R0, R1, R2;  // record prefetch registers (named values: an array would be kept in scratch)
-    double pv[PVN], pvr[PVR], prr[2], prh = 0.0;
+    T pv[PVN], pvr[PVR], prr[2], prh = 0.0;
 #pragma unroll
     for (int j = 0; j < PVN; j++) pv[j] = 0.0;
 #pragma unroll
@@ -1050,7 +1093,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
     int roff = t_rec;  // word offset of the current record
     int nxt_off = 0;   // word offset of the next record
     int s = 0;
-    LPend LP;          // L rows of the front just eliminated, stored one front late (flush_lrows)
+    LPend<T> LP;         // L rows of the front just eliminated, stored one front late (flush_lrows)
     LP.pm = 0; LP.lofs = 0; LP.lptr = 0;
     const int lp_bm = valid ? l : 64;
     // Outer loop: (re)start the pipeline at front s, then either hand a rare large front to the out-of-line path
@@ -1074,7 +1117,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
         if (!CNL_LEAN && !fast0) {
           // rare: large or globally staged front, handled out of line
           if constexpr (STAGED) if (DEP_WAITING) { spin_until(dep_wait, dep_target, A.spin_limit, as_global(A.status_total), as_global(A.status_call)); dep_wait = nullptr; }
-          slow_front(P.rec, A.vals, has_rhs ? A.rhs : nullptr, A.L, A.scratch, A.batch, lane, prob0, recw, roff, pbase0, cnt, eig_tol, rho, ovr, P.count_d != 0);
+          slow_front(P.rec, A_vals, has_rhs ? A_rhs : nullptr, A_L, A_scratch, A.batch, lane, prob0, recw, roff, pbase0, cnt, eig_tol, rho, ovr, P.count_d != 0);
           gsync();
           roff = nxt_off;
           s++;
@@ -1106,10 +1149,10 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
       // (1) zero the staging image (packed triangle + padding slots = 152 doubles = 76 pairs: no loop; the fifth round covers 12)
       //     — only at the start of a stretch of fast fronts: inside it the previous front's elimination left the image zeroed
       if (!img_clean) {
-        double2* z2 = reinterpret_cast<double2*>(myFs) + l;
+        T2* z2 = reinterpret_cast<T2*>(myFs) + l;
 #pragma unroll
-        for (int j = 0; j < 4; j++) z2[16 * j] = make_double2(0.0, 0.0);
-        if (l < FAST_IMG_DOUBLES / 2 - 64) z2[64] = make_double2(0.0, 0.0);
+        for (int j = 0; j < 4; j++) z2[16 * j] = zero2<T>();
+        if (l < FAST_IMG_DOUBLES / 2 - 64) z2[64] = zero2<T>();
         wsync();
       }
       img_clean = true;
@@ -1123,11 +1166,11 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
           const int* dest = rec + co + C_HDR;
           if (!cfl) {
             // four rounds in flight; reads past the end of the list / matrix are not used
-            const double* U = myU + cu + l;
+            const T* U = myU + cu + l;
             const int* dl = dest + l;
             for (int t = 0; t < tuc; t += 64) {
               int dp[4];
-              double uv[4];
+              T uv[4];
 #pragma unroll
               for (int q = 0; q < 4; q++) { dp[q] = dl[t + 16 * q]; uv[q] = U[t + 16 * q]; }
 #pragma unroll
@@ -1135,7 +1178,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
                 if (t + 16 * q + l < tuc) __hip_atomic_fetch_add(&myFs[dp[q]], uv[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             }
           } else {
-            const double* Ug = mygs + cu;
+            const T* Ug = mygs + cu;
             for (int t = l; t < tuc; t += 16)
               __hip_atomic_fetch_add(&myFs[dest[t]], Ug[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
           }
@@ -1151,27 +1194,27 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
 #pragma unroll
         for (int j = 0; j < PVR; j++)
           if (j * 16 < nrawv) {
-            double v = pvr[j];
+            T v = pvr[j];
             if (j * 16 < nrd) {
               // the pivots d_r this front owns are counted here (src/solver_types.jl:90-95): per-lane tallies, summed
               // over the 16 lanes once per factorisation
               const bool own = j * 16 + l < nrd_own;
               rpos += own && v > eig_tol;
               rzer += own && fabs(v) <= eig_tol;
-              const double r = fast_div(-1.0, v);
+              const T r = fast_div(T(-1.0), v);
               v = j * 16 + l < nrd ? r : v;
             }
             jraw[j * 16 + l] = v;
           }
         for (int e = PVR * 16 + l; e < nrawv; e += 16) {
-          const double v = myvals[rec[raw_off + e]];
+          const T v = myvals[rec[raw_off + e]];
           rpos += e < nrd_own && v > eig_tol;
           rzer += e < nrd_own && fabs(v) <= eig_tol;
-          jraw[e] = e < nrd ? fast_div(-1.0, v) : v;
+          jraw[e] = e < nrd ? fast_div(T(-1.0), v) : v;
         }
 #pragma unroll
         for (int q = 0; q < 2; q++)
-          if (nrawv + q * 16 < nraw) jraw[nrawv + q * 16 + l] = has_rhs ? prr[q] : 0.0;
+          if (nrawv + q * 16 < nraw) jraw[nrawv + q * 16 + l] = has_rhs ? prr[q] : T(0);
       }
       wsync();
       {
@@ -1190,20 +1233,20 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
           for (int j = 0; j < PVN; j++)
             if (j * 16 < nasmv) {
               const int src = rec[aoff + j * 16 + l];
-              const double v = (ovr && src >= P.rho_begin) ? rho : pv[j];
+              const T v = (ovr && src >= P.rho_begin) ? rho : pv[j];
               __hip_atomic_fetch_add(&myFs[pos[j]], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             }
         }
-        if (nasmv < nasm) __hip_atomic_fetch_add(&myFs[pos[PVN]], has_rhs ? prh : 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        if (nasmv < nasm) __hip_atomic_fetch_add(&myFs[pos[PVN]], has_rhs ? prh : T(0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
       }
       for (int e = PVN * 16 + l; e < nasmv; e += 16) {  // matrix entries beyond the prefetched rounds
         const int src = rec[aoff + e], pos = rec[aoff + nasm + e];
-        const double v = (ovr && src >= P.rho_begin) ? rho : myvals[src];
+        const T v = (ovr && src >= P.rho_begin) ? rho : myvals[src];
         __hip_atomic_fetch_add(&myFs[pos], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
       }
       for (int e = nasmv + 16 + l; e < nasm; e += 16) {  // right-hand-side entries beyond the prefetched round
         const int src = rec[aoff + e], pos = rec[aoff + nasm + e];
-        __hip_atomic_fetch_add(&myFs[pos], myrhs ? myrhs[src - P.nnz] : 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        __hip_atomic_fetch_add(&myFs[pos], myrhs ? myrhs[src - P.nnz] : T(0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
       }
       if (rowform) {
         // row form: lane l = residual row l.  w = -1/d_r once, then (J_p w) J_q to the position byte of pair (p, q); lanes
@@ -1213,15 +1256,15 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
         int pw_[ROWS_PW];
 #pragma unroll
         for (int g = 0; g < ROWS_PW; g++) pw_[g] = rw[(2 + ROWS_KM + g) * 16];
-        const double dv = pvr[ROWS_KM];
+        const T dv = pvr[ROWS_KM];
         const bool own = l < nrd_own;
         rpos += own && dv > eig_tol;
         rzer += own && fabs(dv) <= eig_tol;
-        const double w = fast_div(-1.0, dv);
-        double t_[ROWS_KM];
+        const T w = fast_div(T(-1.0), dv);
+        T t_[ROWS_KM];
 #pragma unroll
         for (int q = 0; q < ROWS_KM; q++) t_[q] = pvr[q] * w;
-        const double tr = (has_rhs ? prr[0] : 0.0) * w;
+        const T tr = (has_rhs ? prr[0] : T(0)) * w;
 #pragma unroll
         for (int p_ = 0; p_ < ROWS_KM; p_++)
 #pragma unroll
@@ -1239,7 +1282,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
         const int* pw = rec + raw_off + nraw + l;
         for (int e = 0; e < nprod; e += 16 * PB) {
           int w[PB];
-          double v[PB];
+          T v[PB];
 #pragma unroll
           for (int q = 0; q < PB; q++) w[q] = pw[e + 16 * q];  // reads past the list stay inside the wave's LDS and are not used
 #pragma unroll
@@ -1335,7 +1378,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
         if (rung > 1) {
           st = __hip_atomic_load(st_w + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           nf = __hip_atomic_load(A.nfact + pclamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          rh = __hip_atomic_load(A.rho + pclamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          rh = __hip_atomic_load(A_rho + pclamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           wr = __hip_atomic_load(wr_w + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else if (!A.lad_first) {
           st = A.success[pclamp] == 1 ? 1 : 0;
@@ -1358,7 +1401,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
         if (valid && l == 0) {
           __hip_atomic_store(st_w + g, st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           __hip_atomic_store(wr_w + g, wr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(A.rho + prob, rh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(A_rho + prob, rh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           __hip_atomic_store(A.nfact + prob, nf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           __hip_atomic_store(gcw + prob * 2, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           __hip_atomic_store(gcw + prob * 2 + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1383,7 +1426,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
       }
       // next rung: every problem of the group is factorised again with its current rho (a problem that is done repeats its
       // last factorisation: same factor)
-      rho = __hip_atomic_load(A.rho + pclamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      rho = __hip_atomic_load(A_rho + pclamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       ovr = valid && rho != 0.0;
       if (t_nchild_l > 0) { dep_wait = as_global(A.ldep) + tix_l * A.nquads + widx; dep_target = (rung + 1) * t_nchild_l; }
       continue;
@@ -1415,7 +1458,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
   if (nfact > 1) {
     if (rho <= rhomax) rho_old = rho;
     if (valid) {
-      double* vt = A.vals + pclamp * P.vstride + P.rho_begin;
+      T* vt = A_vals + pclamp * P.vstride + P.rho_begin;
       for (int i = l; i < P.nvar; i += 16) vt[i] = wrote;
     }
   }
@@ -1440,23 +1483,23 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
     const int4* bstream = reinterpret_cast<const int4*>(P.brec);
     const int* okflag = cnt + 8;
     const bool okme = valid && okflag[g] != 0;
-    const double* myL = A.L + pclamp * P.lsize;
-    double* mydout = A.d + pclamp * P.dstride;
-    double* xs = myU;  // the x stack reuses the per-problem LDS area
+    const T* myL = A_L + pclamp * P.lsize;
+    T* mydout = A_d + pclamp * P.dstride;
+    T* xs = myU;  // the x stack reuses the per-problem LDS area
     int boff = t_brec, nxt = 0;
     int4 Rb;
-    double lr[KB];     // panel rows of the CURRENT front (first KB pivots), prefetched one front ahead
+    T lr[KB];     // panel rows of the CURRENT front (first KB pivots), prefetched one front ahead
     bool primed = false;
     // the scattered store of a front's solution components is issued one front late, right before the NEXT front's prefetch
     // loads: a wait for any load is a vmcnt(0) while a store is in flight (see LPend), and a store issued at the end of front s
     // put its whole round trip on the critical path of front s + 1
     int ipend = -1;
-    double dpend = 0.0;
+    T dpend = 0.0;
     // (lean) operands of the residual rows the CURRENT front owns, prefetched one front ahead; their store is deferred too
     const bool brows = CNL_LEAN && A.back_rows != 0;
-    double bpv[ROWS_KM + 2];
+    T bpv[ROWS_KM + 2];
     int bix = 0, brs = 0, ipend2 = -1;
-    double dpend2 = 0.0;
+    T dpend2 = 0.0;
     int s = 0;
     while (s < nfr) {
       int* recw = recbuf + (s & 1) * P.breccap;
@@ -1486,12 +1529,12 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
         if (cls == 32) {
           for (int pass = 0; pass < 2; pass++) {
             if (prob0 + pass * 2 >= A.batch) break;
-            back_front_call<32>(P.prob_doubles, P.lsize, P.dstride, A.L, A.d, A.batch, lane, prob0, pass, rec, f, nupd, npiv, lptr, xoff, pxoff, pbase0, okflag);
+            back_front_call<32>(P.prob_doubles, P.lsize, P.dstride, A_L, A_d, A.batch, lane, prob0, pass, rec, f, nupd, npiv, lptr, xoff, pxoff, pbase0, okflag);
           }
         } else {
           for (int pass = 0; pass < 4; pass++) {
             if (prob0 + pass >= A.batch) break;
-            back_front_call<64>(P.prob_doubles, P.lsize, P.dstride, A.L, A.d, A.batch, lane, prob0, pass, rec, f, nupd, npiv, lptr, xoff, pxoff, pbase0, okflag);
+            back_front_call<64>(P.prob_doubles, P.lsize, P.dstride, A_L, A_d, A.batch, lane, prob0, pass, rec, f, nupd, npiv, lptr, xoff, pxoff, pbase0, okflag);
           }
         }
         wsync();
@@ -1501,8 +1544,8 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
         continue;
       }
       // next record into the other buffer, then prefetch the record after it and the next front's panel rows
-      double lrn[KB];
-      double bpvn[ROWS_KM + 2];
+      T lrn[KB];
+      T bpvn[ROWS_KM + 2];
       int bixn = 0, brsn = 0;
       int nboff = nxt;
       if (s + 1 < nfr) {
@@ -1536,7 +1579,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
       // predicate: entries beyond the row multiply zeros.  Lane 0 (the right-hand-side column, where the panel
       // keeps z = D^-1 L^-1 b) holds -1: the lane sum is then (L x) - z = -x_pivot, no separate broadcast of z.
       const int tu = tri2(1 + nupd);
-      double xb = l == 0 ? -1.0 : 0.0;
+      T xb = l == 0 ? T(-1.0) : T(0);
       if (pxoff >= 0 && l >= 1 && l <= nupd) xb = xs[pxoff + rec[B_HDR + l]];
       if (pxoff == B_PX_GLOBAL && l >= 1 && l <= nupd)  // the parent was solved by another task: x = -d of the named components
         xb = -__hip_atomic_load(mydout + rec[B_HDR + l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1544,14 +1587,14 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
 #pragma unroll
       for (int k = 0; k < KB; k++) {
         if (k < npiv) {
-          const double sum = gsum<16>(-lr[k] * xb);
+          const T sum = gsum<16>(-lr[k] * xb);
           if (l == nupd + 1 + k) xb = sum;
         }
       }
       for (int k0 = KB; k0 < npiv; k0++) {  // fronts with more than KB pivots: remaining rows loaded on demand
         const int i = nupd + 1 + k0;
-        const double lv = myL[lptr + tri2(i) - tu + l];
-        const double sum = gsum<16>(-lv * xb);
+        const T lv = myL[lptr + tri2(i) - tu + l];
+        const T sum = gsum<16>(-lv * xb);
         if (l == i) xb = sum;
       }
       // d = -x of the pivots: one scattered store per front (rec holds the original index of every pivot)
@@ -1563,12 +1606,12 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
       if constexpr (CNL_LEAN) {
         // residual components of the rows this front owns: d_r = (sum_p J_p x[l_p] - rhs_r) / d_r with x of the front's own
         // vector (every column of an owned row is a row of this front)
-        const double* xf = xs + xoff;
+        const T* xf = xs + xoff;
         const int nm = (bix >> 20) & 7;
-        double sacc = -bpv[ROWS_KM + 1];
+        T sacc = -bpv[ROWS_KM + 1];
 #pragma unroll
         for (int p_ = 0; p_ < ROWS_KM; p_++) {
-          const double cf = p_ < nm ? bpv[1 + p_] : 0.0;
+          const T cf = p_ < nm ? bpv[1 + p_] : T(0);
           sacc = fma(cf, xf[(bix >> (4 * p_)) & 15], sacc);
         }
         if (ipend2 >= 0) mydout[ipend2] = dpend2;
@@ -1590,10 +1633,10 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
     if (FUSED && A.phase == 2) { task_done(dep_signal, lane, true); return; }  // (outputs: written by the deciding wavefront; rho_old and the slots: committed behind)
     if (A.phase == 1) task_done(dep_signal, lane, A.df_live != 0);  // the children of this task may read its solution components now
     // first attempt only: rho = 0, rho_old untouched; problems that failed are handed to the launch that follows
-    if (valid && l == 0 && t_root && A.mode == MODE_NEWTON) { A.rho[prob] = 0.0; A.nfact[prob] = 1; A.success[prob] = success ? 1 : 0; }
+    if (valid && l == 0 && t_root && A.mode == MODE_NEWTON) { A_rho[prob] = 0.0; A.nfact[prob] = 1; A.success[prob] = success ? 1 : 0; }
   } else if (valid && l == 0 && A.mode == MODE_NEWTON) {
-    A.rho[prob] = rho;
-    A.rho_old[prob] = rho_old;
+    A_rho[prob] = rho;
+    A_rho_old[prob] = rho_old;
     A.nfact[prob] = nfact;
     A.success[prob] = success ? 1 : 0;
   }
@@ -1617,9 +1660,24 @@ hipError_t launch_newton2(const DevPlan2& P, int wpb, size_t lds_bytes, const La
   const bool lean_solve = a.lean != 0 && a.back_rows != 0 && a.mode == MODE_SOLVE;
   const bool late = waves >= 1024 && !lean && !lean_solve;
   const bool commit = a.only_if_status != 0 && a.lad != nullptr && a.mode == MODE_NEWTON;   // behind fused ladder launches
-  auto kern = commit ? (lean ? newton2_kernel_t<false, false, true, false, true> : newton2_kernel_t<false, false, false, false, true>)
-            : lean_solve ? newton2_kernel_t<false, false, true, true>
-            : lean ? newton2_kernel_t<false, false, true> : (late ? newton2_kernel_t<false, true, false> : newton2_kernel_t<false, false, false>);
+  auto kern = commit ? (lean ? newton2_kernel_t<double, false, false, true, false, true> : newton2_kernel_t<double, false, false, false, false, true>)
+            : lean_solve ? newton2_kernel_t<double, false, false, true, true>
+            : lean ? newton2_kernel_t<double, false, false, true> : (late ? newton2_kernel_t<double, false, true, false> : newton2_kernel_t<double, false, false, false>);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)lds_bytes));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wpb), lds_bytes, stream, P, a);
+  return hipGetLastError();
+}
+
+// The same kernel on Float32 data (kernels.h): the plain instantiation in both LATE settings, nothing else — no staged, fused, lean
+// or solve-only instance exists for float, and its records are never direct.  `late` by the Float64 rule.
+hipError_t launch_newton2_f32(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream) {
+  if (wpb < 1 || wpb > 4) return hipErrorInvalidConfiguration;
+  if (a.mode == MODE_SOLVE || a.lean || a.only_if_status || a.skip_done) return hipErrorInvalidConfiguration;
+  const int waves = (a.batch + 3) / 4;
+  const int grid = (waves + wpb - 1) / wpb;
+  const bool late = waves >= 1024;
+  auto kern = late ? newton2_kernel_t<float, false, true, false> : newton2_kernel_t<float, false, false, false>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)lds_bytes));
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wpb), lds_bytes, stream, P, a);
@@ -1650,9 +1708,9 @@ hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, L
   const bool late = (long long)a.nquads * ntask0 >= 1920 && P.nsuper >= 128 * ntask0;
   const bool lean = a.lean != 0 && a.mode != MODE_SOLVE;
   const bool lean_solve = a.lean != 0 && a.back_rows != 0 && a.mode == MODE_SOLVE;
-  auto kern = lean_solve ? newton2_kernel_t<true, false, true, true>
-            : lean ? (late ? newton2_kernel_t<true, true, true> : newton2_kernel_t<true, false, true>)
-                   : (late ? newton2_kernel_t<true, true, false> : newton2_kernel_t<true, false, false>);
+  auto kern = lean_solve ? newton2_kernel_t<double, true, false, true, true>
+            : lean ? (late ? newton2_kernel_t<double, true, true, true> : newton2_kernel_t<double, true, false, true>)
+                   : (late ? newton2_kernel_t<double, true, true, false> : newton2_kernel_t<double, true, false, false>);
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)lds_bytes));
   if (e != hipSuccess) return e;
   const bool ladder = a.mode == MODE_NEWTON && a.lad_mode != 0 && a.lad && a.lgcnt && a.ldep && a.status_call;
@@ -1684,7 +1742,7 @@ hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, L
   }
   a.ntasks_all = ntasks_all;
   // the in-kernel ladder: every task of a group of problems on a wavefront of its own, all of a launch resident at once
-  auto kern_f = lean ? newton2_kernel_t<true, false, true, false, true> : newton2_kernel_t<true, false, false, false, true>;
+  auto kern_f = lean ? newton2_kernel_t<double, true, false, true, false, true> : newton2_kernel_t<double, true, false, false, false, true>;
   if (ladder) {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern_f), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)lds_bytes));
     if (e != hipSuccess) return e;

@@ -402,8 +402,12 @@ class HIPLDLStruct:
     CNL_ERR_ARG otherwise: the caller stays on the CPU backend); Options(float32_general=1) serves every other pattern on the
     general multifrontal kernel in float (config["kernel"] == "v1"), and Options(float32_general=1, float32_condense=1) runs that
     kernel on the condensed system — the -I block eliminated by the condensation passes in float — which info["ncond"] > 0 identifies
-    (config["cond_resident"]: the resident condense kernel serves it).  Such a handle reads the Jacobian values of `vals` again in
-    solve_ldl!: the array given to try_to_factorize must stay alive and unmodified until the last solve on that factor."""
+    (config["cond_resident"]: the resident condense kernel serves it).  Options(float32_general=1, float32_register_front=1) implies
+    float32_condense and runs newton_system! / try_to_factorize on the register-front kernel in float between those passes
+    (config["kernel"] == "v2", config["wpb"] / config["lds2_bytes"] its wavefronts per workgroup and LDS bytes; solve_ldl! runs on the
+    general kernel, on the same panels); where a front exceeds order 64 the handle is the float32_condense handle ("v1").  A condensed
+    handle of either kind reads the Jacobian values of `vals` again in solve_ldl!: the array given to try_to_factorize must stay alive
+    and unmodified until the last solve on that factor."""
 
     def __init__(self, N, rows, cols, vals, nvar=None, nequ=None, ncon=None, batch=1, device=0, options=None, dtype=np.float64):
         self.N = int(N)

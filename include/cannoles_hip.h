@@ -58,7 +58,8 @@ typedef struct cnl_handle cnl_handle; /* plan + device state for one batch      
 
 const char* cnl_last_error(void);
 /* library / ABI version: major*10000 + minor*100 + patch (0.3.0: cnl_set_active_batch, cnl_outer_compact_dev;
- * 0.3.1: tuning "float32_general", no new symbol; 0.4.0: cnl_outer_ctl, the cnl_outer_*_ex_dev entry points, cnl_outer_hess_mask_dev) */
+ * 0.3.1: tuning "float32_general", no new symbol; 0.4.0: cnl_outer_ctl, the cnl_outer_*_ex_dev entry points, cnl_outer_hess_mask_dev;
+ * 0.4.1: tuning "float32_register_front", no new symbol) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -437,7 +438,9 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
 /* ([5] + (1 << 27) on a Float32 handle.  On the band kernels: bits 7-26 as above, cfg[0..4], [6], [7] are 0.  On the general kernel
  *  (tuning "float32_general=1"): cfg[0..4] describe that kernel's float instance as they do for a Float64 handle — [2] counts 4-byte
  *  elements — and [5] = 1 + (1 << 27) with bit 6 clear (+ 128 as above; + (1 << 35) where tuning "float32_condense=1" has the
- *  resident condense kernel form the condensed system); [6], [7] are 0.) */
+ *  resident condense kernel form the condensed system); [6], [7] are 0.  With tuning "float32_register_front=1" where the
+ *  register-front kernel's float instance serves the handle: [5] = 2 + (1 << 27) (+ (1 << 35) as above), [6], [7] = its wavefronts
+ *  per workgroup and LDS bytes per workgroup.) */
 /* Launches of the Newton-system kernels since the library was loaded, per kernel family: counts[0] band kernels (csrc/band.hip),
  * [1] register-front kernel (csrc/kernels2.hip, staged launches not included), [2] general kernel (csrc/kernels.hip).  Lets a test
  * pin WHICH kernel served a call sequence (e.g. that solve_ldl! behind a band factorisation launches no second kernel family). */
@@ -477,6 +480,16 @@ int cnl_launch_counts(int64_t counts[3]);
  * condensation of every new right-hand side and the post-pass read the Jacobian values and the -I entries from it (host-pointer
  * calls: the handle's own staged copy, nothing for the caller to keep).  The uncondensed Float32 general handle does not need
  * this.  The kept factor still serves any number of right-hand sides without refactorising.
+ *   tuning "float32_register_front=1" (default 0; takes effect only where "float32_general=1" lets a general handle serve the
+ * pattern — a band handle ignores it, and without "float32_general" a non-band pattern is still CNL_ERR_ARG): implies
+ * "float32_condense", and cnl_newton_system_f32* / cnl_factorize_f32* run ONE launch of the register-front kernel
+ * (csrc/kernels2.hip) instantiated for float between the float condensation passes (cnl_launch_counts: family 1, none of family
+ * 2); cnl_solve_f32* is one launch of the general kernel's float instance (family 2) on the panels the register-front kernel
+ * stored.  The plan is the throughput analysis of the condensed system with register-front records that are never direct, whatever
+ * the other options say.  Every operation is a float operation (correctly rounded quotients, subnormals kept).  Where a front
+ * exceeds order 64, or the kernel's LDS block or 32-bit offsets do not fit, the handle is exactly the "float32_condense=1"
+ * handle.  cnl_set_active_batch serves it; batch_layout = CNL_LAYOUT_INTERLEAVED stays CNL_ERR_ARG.  The CONTRACT above holds
+ * unchanged: `vals` / d_vals of the factorisation stay alive and unmodified until the last solve on that factor.
  * The semantics of every call are those of its Float64 twin above.  Mixing element types is CNL_ERR_STATE and does nothing:
  * a Float64 entry point on a Float32 handle (cnl_factorize..., the row f1 / f2 / f4 / trial-point passes, cnl_interleave_dev...)
  * and an `_f32` entry point on a Float64 handle.  cnl_layout_len counts elements, so it serves both types.
