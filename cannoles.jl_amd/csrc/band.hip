@@ -371,10 +371,10 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
   static_assert(ES == 8 || ES == 4, "double or float");
   extern __shared__ double lds[];
   const int mode = Ain.mode, batch = Ain.batch;
-  T* const gvals = as_global(reinterpret_cast<T*>(Ain.vals));
-  const T* const grhs = as_global(reinterpret_cast<const T*>(Ain.rhs));
-  T* const gd = as_global(reinterpret_cast<T*>(Ain.d));
-  T* const gL = as_global(reinterpret_cast<T*>(Ain.L));
+  T* const gvals = as_global(static_cast<T*>(Ain.vals));
+  const T* const grhs = as_global(static_cast<const T*>(Ain.rhs));
+  T* const gd = as_global(static_cast<T*>(Ain.d));
+  T* const gL = as_global(static_cast<T*>(Ain.L));
   const int lane = threadIdx.x & 63;
   const int part = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lq = lane >> 3, le = lane & 7;
@@ -453,7 +453,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
   const T tol = (T)Ain.params[0], kdec = (T)Ain.params[2], kinc = (T)Ain.params[3], klarge = (T)Ain.params[4], rho0 = (T)Ain.params[5],
           rhomax = (T)Ain.params[6], rhomin = (T)Ain.params[7];
   T rho = T(0), wrote = T(0);
-  T rho_old = (mode == MODE_NEWTON && valid) ? as_global(reinterpret_cast<T*>(Ain.rho_old))[cprob] : T(0);
+  T rho_old = (mode == MODE_NEWTON && valid) ? as_global(static_cast<T*>(Ain.rho_old))[cprob] : T(0);
   int nfact = 0;
   bool done = !valid, success = false, ovr = false;
   // (try_to_factorize keeps no records: a later solve_ldl! factorises again, see MODE_SOLVE above)
@@ -862,8 +862,8 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
   if (part == 0 && mode == MODE_NEWTON) {
     if (nfact > 1 && rho <= rhomax) rho_old = rho;
     if (valid) {
-      as_global(reinterpret_cast<T*>(Ain.rho))[cprob] = rho;
-      as_global(reinterpret_cast<T*>(Ain.rho_old))[cprob] = rho_old;
+      as_global(static_cast<T*>(Ain.rho))[cprob] = rho;
+      as_global(static_cast<T*>(Ain.rho_old))[cprob] = rho_old;
       as_global(Ain.nfact)[cprob] = nfact;
       as_global(Ain.success)[cprob] = success ? 1 : 0;
     }

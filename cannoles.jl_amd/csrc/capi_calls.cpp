@@ -62,31 +62,30 @@ Stage<T> stage(const cnl_handle* h) {   // (of the whole handle: not inside a Su
 int ensure_staging(cnl_handle* h) {
   if (h->d_vals) return CNL_OK;
   const cnl_plan& P = *h->plan;
-  const size_t B = (size_t)h->batch, esz = h->f32 ? sizeof(float) : sizeof(double);
-  char *vals, *rhs, *d, *res;
+  const size_t B = (size_t)h->batch;
+  void* vals;
+  char* res;
   int rc;
-  if ((rc = dalloc(h, &vals, B * P.nnz * esz))) return rc;
-  if ((rc = dalloc(h, &rhs, B * P.N * esz))) return rc;
-  if ((rc = dalloc(h, &d, B * P.N * esz))) return rc;
-  if ((rc = dalloc(h, &res, B * (2 * esz + 2 * sizeof(int32_t)) + 64))) return rc;
+  if ((rc = dalloc_elems(h, &vals, B * P.nnz))) return rc;
+  if ((rc = dalloc_elems(h, &h->d_rhs, B * P.N))) return rc;
+  if ((rc = dalloc_elems(h, &h->d_d, B * P.N))) return rc;
+  if ((rc = dalloc(h, &res, B * (2 * h->esz() + 2 * sizeof(int32_t)) + 64))) return rc;
   if ((rc = dalloc(h, &h->d_npos, B * 2))) return rc;
-  h->d_rhs = rhs; h->d_d = d; h->d_res = res;
+  h->d_res = res;
   h->d_vals = vals;   // (last: the staging exists)
   return CNL_OK;
 }
 
-// One call on typed device pointers: the only place that fills cnl::LaunchArgs from them.  Its element arrays are double*; a Float32
-// launch stores its float arrays there (launch_band_f32 reads them as float).  params: np values (exact in double; a Float32 kernel
-// narrows them back).
-template <class T>
-double* as_args(const T* p) { return reinterpret_cast<double*>(const_cast<T*>(p)); }
+// One call on typed device pointers: the only place that fills cnl::LaunchArgs from them (its element arrays are untyped, in the
+// handle's element type).  d_vals is written by newton_system alone.  params: np values (exact in double; a Float32 kernel narrows
+// them back).
 template <class T>
 int run_typed(cnl_handle* h, int mode, const T* params, int np, const Results<T>& r, const T* d_vals, const T* d_rhs, T* d_d, hipStream_t stream) {
   cnl::LaunchArgs a{};
   a.mode = mode;
-  a.rho_old = as_args(r.rho_old); a.rho = as_args(r.rho); a.nfact = r.nfact; a.success = r.success; a.npos = r.npos; a.nzero = r.nzero;
+  a.rho_old = r.rho_old; a.rho = r.rho; a.nfact = r.nfact; a.success = r.success; a.npos = r.npos; a.nzero = r.nzero;
   for (int k = 0; k < np; k++) a.params[k] = params[k];
-  return run(h, a, as_args(d_vals), as_args(d_rhs), as_args(d_d), stream);
+  return run(h, a, const_cast<T*>(d_vals), d_rhs, d_d, stream);
 }
 // where newton_system on the staged arrays leaves its results, for the problems from b0 on (no inertia counts: try_to_factorize's)
 template <class T>
@@ -101,7 +100,7 @@ Results<T> newton_results(const Stage<T>& s, size_t b0 = 0) {
 void holds_factor(cnl_handle* h, const void* d_vals, const int32_t* ok = nullptr) {
   h->factorized = true;
   h->factor_batch = h->batch;
-  h->last_vals = static_cast<const double*>(d_vals);
+  h->last_vals = d_vals;
   if (ok) h->last_ok.assign(ok, ok + h->batch);
   else h->last_ok.clear();
 }

@@ -19,7 +19,7 @@ bool band_wide_serves_f64(const cnl_plan* plan) {
 // among the configurations compiled for float (kernels.h: newton_f32_has).
 int choose_config(cnl_handle* h) {
   const cnl::Plan& P = h->plan->P;
-  const size_t esz = h->f32 ? sizeof(float) : sizeof(double);
+  const size_t esz = h->esz();
   cnl::DevPlan& dp = h->dp;
   int64_t pb_off = std::max<int64_t>(P.fwd_peak, P.bwd_peak);
   pb_off = (pb_off + 1) & ~(int64_t)1;
@@ -87,7 +87,7 @@ int setup_v2(cnl_handle* h) {
   const cnl::Plan& P = h->plan->P;
   h->use_v2 = false;
   const cnl::Tuning& o = h->plan->opt;
-  const size_t esz = h->f32 ? sizeof(float) : sizeof(double);
+  const size_t esz = h->esz();
   if (!P.v2_ok || !o.register_front) return CNL_OK;
   if (h->f32 && (P.rec_direct || !P.tasks.empty())) return CNL_OK;   // (not what cnl_create_f32_ex builds: the float kernel has no such instance)
   if (!h->f32 && !h->plan->gpos.empty() && (o.general_dense == 2 || (h->plan->prefer_dense && h->batch <= 16))) return CNL_OK;  // the dense route (capi_plan.cpp, plan_create_impl); 2: wherever it is possible
@@ -139,11 +139,7 @@ int setup_v2(cnl_handle* h) {
   while (wpb > 1 && wpb * wave_bytes + 512 > maxlds) wpb--;
   h->wpb2 = wpb;
   h->lds2 = wpb * wave_bytes + 512;
-  if (h->f32) {   // (floats behind the double*, like the handle's other element arrays)
-    float* gs = nullptr;
-    if ((rc = dalloc(h, &gs, (size_t)h->batch * (size_t)d.gs_doubles))) return rc;
-    h->d_gs = reinterpret_cast<double*>(gs);
-  } else if ((rc = dalloc(h, &h->d_gs, (size_t)h->batch * (size_t)d.gs_doubles))) return rc;
+  if ((rc = dalloc_elems(h, &h->d_gs, (size_t)h->batch * (size_t)d.gs_doubles))) return rc;
   h->use_v2 = true;
   h->staged = false;
   if ((rc = dalloc(h, &h->d_status, 1))) return rc;
@@ -235,7 +231,7 @@ int check_device(int device) {
 // handle nothing).  An option that asks for an instance that does not exist is an error.
 int setup_band(cnl_handle* h, const cnl::BandPlan& Bp0, const char** unfit) {
   const cnl_plan* plan = h->plan;
-  const int esz = h->f32 ? (int)sizeof(float) : (int)sizeof(double);
+  const int esz = (int)h->esz();
   const int64_t batch = h->batch;
   int rc;
   h->band_npiece = Bp0.npiece;
@@ -280,11 +276,9 @@ int setup_band(cnl_handle* h, const cnl::BandPlan& Bp0, const char** unfit) {
     return CNL_OK;
   }
   // (+ 32 problems: the band kernels interleave the records of a workgroup's problems, the last workgroup's region is a whole one)
-  const size_t lbytes = (((size_t)batch + 32) * (size_t)bd.lsize + 64) * (size_t)esz;
-  char* L = nullptr;
-  if ((rc = dalloc(h, &L, lbytes))) return rc;
-  if (hipMemset(L, 0, lbytes) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
-  h->d_Lband = L;
+  const size_t lelems = ((size_t)batch + 32) * (size_t)bd.lsize + 64;
+  if ((rc = dalloc_elems(h, &h->d_Lband, lelems))) return rc;
+  if (hipMemset(h->d_Lband, 0, lelems * (size_t)esz) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
   h->band = true;
   return CNL_OK;
 }
@@ -553,17 +547,41 @@ int setup_cond_resident(cnl_handle* h) {
   return CNL_OK;
 }
 
+// ---- the skeleton the creators share: a fresh handle on `plan` (which it owns from here on: cnl_destroy frees both), `device` current
+int new_handle(cnl_handle** hout, cnl_plan* plan, int64_t batch, int device, bool f32, bool f32_general) {
+  cnl_handle* h = new cnl_handle();
+  h->plan = plan; h->device = device; h->batch = h->full_batch = batch; h->f32 = f32; h->f32_general = f32_general;
+  if (hipSetDevice(device) != hipSuccess) { cnl_destroy(h); return fail(CNL_ERR_HIP, "hipSetDevice failed"); }
+  *hout = h;
+  return CNL_OK;
+}
+// Storage of the general and register-front kernels, in the handle's element type: the factor panels, zero-filled (the pad of every
+// problem stays zero) and padded — the row prefetch of the backward pass reads (never uses) a little past a panel —, and the global
+// work area where it is not in LDS.  (A band handle keeps the pad alone: create_from_plan.)
+int alloc_factor_storage(cnl_handle* h) {
+  int rc;
+  const size_t lelems = (h->band ? 0 : (size_t)h->full_batch * (size_t)h->dp.lsize) + 4096;
+  if ((rc = dalloc_elems(h, &h->d_L, lelems))) return rc;
+  if (hipMemset(h->d_L, 0, lelems * h->esz()) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
+  if (!h->cfg.lds_work && (rc = dalloc_elems(h, &h->d_scratch, (size_t)h->full_batch * (size_t)h->dp.work_doubles))) return rc;
+  return CNL_OK;
+}
+// the handle's stream, its two timing events and the row lists (rows f1 / f2 / f4, the trial point, the dimensions cnl_layout_len reads)
+int finish_handle(cnl_handle* h, const int64_t* rows1, const int64_t* cols1) {
+  if (hipStreamCreate(&h->stream) != hipSuccess) return fail(CNL_ERR_HIP, "hipStreamCreate failed");
+  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return fail(CNL_ERR_HIP, "hipEventCreate failed");
+  return build_row_lists(h, h->plan, rows1, cols1);
+}
+
 }  // namespace
 
 // device state for `batch` problems of an analysed pattern; takes ownership of `plan` (freed with the handle, or here on failure)
 int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device) {
   const int64_t N = plan->N, nnz = plan->nnz, nvar = plan->nvar, nequ = plan->nequ, ncon = plan->ncon;
   int rc = CNL_OK;
-  cnl_handle* h = new cnl_handle();
-  h->plan = plan; h->device = device; h->batch = h->full_batch = batch;
+  cnl_handle* h = nullptr;
+  if ((rc = new_handle(&h, plan, batch, device, false, false))) return rc;
   auto bail = [&](int code) { cnl_destroy(h); return code; };
-  if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
-  cnl::DevPlan& dp = h->dp;
   if ((rc = upload_dev_plan(h))) return bail(rc);
   const cnl::Cond& C = plan->C;
   if (C.active && (rc = upload_dev_cond(h))) return bail(rc);
@@ -582,8 +600,8 @@ int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, co
   // cfg3's size instead of 0.48 + 1.16 (factor panels) + 0.64 (condensed buffer, reduced solution) — 16 384 problems: 29 GB less,
   // and twice the batch fits the 288 GB of a device beside the caller's arrays.
   if (plan->C.active && !h->band) {
-    if ((rc = dalloc(h, &h->d_cbuf, (size_t)batch * (size_t)plan->C.cstride))) return bail(rc);
-    if ((rc = dalloc(h, &h->d_d2, (size_t)batch * (size_t)plan->C.N2))) return bail(rc);
+    if ((rc = dalloc_elems(h, &h->d_cbuf, (size_t)batch * (size_t)plan->C.cstride))) return bail(rc);
+    if ((rc = dalloc_elems(h, &h->d_d2, (size_t)batch * (size_t)plan->C.N2))) return bail(rc);
   }
   if (plan->split_mode && h->staged) {
     // x groups of four problems on the chain (two wavefronts each), the rest on the single stream: 2 x + y = 2048 slots
@@ -643,18 +661,8 @@ int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, co
     int drc = cnl::dense_create_general(&h->gdense, (int32_t)C2.N2, (int32_t)nvar, (int32_t)C2.ncs, h->gops.d_pos, batch, derr, h->plan->opt.dense_graph != 0, h->plan->opt.dense_panel_blocks);
     if (drc) return bail(fail(CNL_ERR_HIP, "dense backend: " + derr));
   }
-  {
-    // factor storage, zero-filled and padded: the row prefetch of the backward pass reads (never uses) a little past a panel
-    const size_t ldoubles = (h->band ? 0 : (size_t)batch * (size_t)dp.lsize) + 4096;   // (band handles: see above)
-    if ((rc = dalloc(h, &h->d_L, ldoubles))) return bail(rc);
-    if (hipMemset(h->d_L, 0, ldoubles * sizeof(double)) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipMemset failed"));
-  }
-  if (!h->cfg.lds_work)
-    if ((rc = dalloc(h, &h->d_scratch, (size_t)batch * (size_t)dp.work_doubles))) return bail(rc);
-  if (hipStreamCreate(&h->stream) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipStreamCreate failed"));
-  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess)
-    return bail(fail(CNL_ERR_HIP, "hipEventCreate failed"));
-  if ((rc = build_row_lists(h, plan, rows1, cols1))) return bail(rc);
+  if ((rc = alloc_factor_storage(h))) return bail(rc);   // (band handles: the pad alone, see above)
+  if ((rc = finish_handle(h, rows1, cols1))) return bail(rc);
   *hout = h;
   return CNL_OK;
 }
@@ -662,11 +670,10 @@ int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, co
 namespace {
 
 int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device) {
-  cnl_handle* h = new cnl_handle();
-  h->plan = plan; h->device = device; h->batch = h->full_batch = batch; h->f32 = true;
-  auto bail = [&](int code) { cnl_destroy(h); return code; };
-  if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
   int rc = CNL_OK;
+  cnl_handle* h = nullptr;
+  if ((rc = new_handle(&h, plan, batch, device, true, false))) return rc;
+  auto bail = [&](int code) { cnl_destroy(h); return code; };
   const char* unfit = nullptr;
   if ((rc = setup_band(h, band_program(plan, true), &unfit))) return bail(rc);   // the wide program where the plan has one
   if (!h->band) {   // the program does not fit the band kernels: refused, or (tuning float32_general) the caller goes on to the general kernel
@@ -675,10 +682,7 @@ int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1
     return bail(fail(CNL_ERR_ARG, std::string("cnl_create_f32: ") + unfit));
   }
   if ((rc = setup_layout(h))) return bail(rc);
-  // rows f1 / f2 / f4 and the trial point: the Float64 handles' row lists (they hold the dimensions cnl_layout_len reads)
-  if ((rc = build_row_lists(h, plan, rows1, cols1))) return bail(rc);
-  if (hipStreamCreate(&h->stream) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipStreamCreate failed"));
-  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipEventCreate failed"));
+  if ((rc = finish_handle(h, rows1, cols1))) return bail(rc);
   *hout = h;
   return CNL_OK;
 }
@@ -690,44 +694,26 @@ int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1
 // Nothing of the dense or staged state exists for it; the register-front state (setup_v2, in floats) only with tuning
 // float32_register_front on a plan whose fronts that kernel takes.
 int create_f32_general_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device) {
-  cnl_handle* h = new cnl_handle();
-  h->plan = plan; h->device = device; h->batch = h->full_batch = batch; h->f32 = true; h->f32_general = true;
+  int rc = CNL_OK;
+  cnl_handle* h = nullptr;
+  if ((rc = new_handle(&h, plan, batch, device, true, true))) return rc;
   auto bail = [&](int code) { cnl_destroy(h); return code; };
   if (plan->C.active && !plan->opt.float32_condense)
     return bail(fail(CNL_ERR_STATE, "cnl_create_f32: the plan of a Float32 general handle is condensed only with tuning float32_condense = 1"));
-  if (hipSetDevice(device) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipSetDevice failed"));
-  int rc = CNL_OK;
   if ((rc = upload_dev_plan(h))) return bail(rc);   // (condensed plan: the strides of vals / rhs / d are those of d_cbuf / d_d2)
   if ((rc = choose_config(h))) return bail(rc);     // (... and the front sizes those of the condensed system)
   if ((rc = setup_layout(h))) return bail(rc);   // (batch_layout = CNL_LAYOUT_INTERLEAVED is the band kernels': CNL_ERR_ARG)
   if (plan->C.active) {
     if ((rc = upload_dev_cond(h))) return bail(rc);
-    float *cbuf = nullptr, *d2 = nullptr;
-    if ((rc = dalloc(h, &cbuf, (size_t)batch * (size_t)plan->C.cstride))) return bail(rc);
-    if ((rc = dalloc(h, &d2, (size_t)batch * (size_t)plan->C.N2))) return bail(rc);
-    h->d_cbuf = reinterpret_cast<double*>(cbuf);
-    h->d_d2 = reinterpret_cast<double*>(d2);
+    if ((rc = dalloc_elems(h, &h->d_cbuf, (size_t)batch * (size_t)plan->C.cstride))) return bail(rc);
+    if ((rc = dalloc_elems(h, &h->d_d2, (size_t)batch * (size_t)plan->C.N2))) return bail(rc);
     if ((rc = setup_cond_resident(h))) return bail(rc);
   }
   // tuning float32_register_front: the register-front kernel in float runs newton_system / try_to_factorize between the passes
   // where the plan's fronts allow it and its LDS block fits; where not, the handle is the float32_condense handle and nothing else
   if (plan->opt.float32_register_front && plan->C.active && (rc = setup_v2(h))) return bail(rc);
-  {
-    // factor panels, zero-filled (the pad of every problem stays zero) and padded as a Float64 handle's
-    float* L = nullptr;
-    const size_t lfloats = (size_t)batch * (size_t)h->dp.lsize + 4096;
-    if ((rc = dalloc(h, &L, lfloats))) return bail(rc);
-    if (hipMemset(L, 0, lfloats * sizeof(float)) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipMemset failed"));
-    h->d_L = reinterpret_cast<double*>(L);
-  }
-  if (!h->cfg.lds_work) {
-    float* S = nullptr;
-    if ((rc = dalloc(h, &S, (size_t)batch * (size_t)h->dp.work_doubles))) return bail(rc);
-    h->d_scratch = reinterpret_cast<double*>(S);
-  }
-  if (hipStreamCreate(&h->stream) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipStreamCreate failed"));
-  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipEventCreate failed"));
-  if ((rc = build_row_lists(h, plan, rows1, cols1))) return bail(rc);
+  if ((rc = alloc_factor_storage(h))) return bail(rc);
+  if ((rc = finish_handle(h, rows1, cols1))) return bail(rc);
   *hout = h;
   return CNL_OK;
 }

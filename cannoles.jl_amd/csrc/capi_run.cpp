@@ -30,9 +30,9 @@ int end_timed(cnl_handle* h, hipStream_t stream) {
 }
 
 // the per-problem result arrays of a call, from problem b0 on
-cnl::LaunchArgs shifted(cnl::LaunchArgs a, int64_t b0) {
-  if (a.rho_old) a.rho_old += b0;
-  if (a.rho) a.rho += b0;
+cnl::LaunchArgs shifted(const cnl_handle* h, cnl::LaunchArgs a, int64_t b0) {
+  a.rho_old = elem_offset(h, a.rho_old, b0);
+  a.rho = elem_offset(h, a.rho, b0);
   if (a.nfact) a.nfact += b0;
   if (a.success) a.success += b0;
   if (a.npos) a.npos += b0;
@@ -40,22 +40,22 @@ cnl::LaunchArgs shifted(cnl::LaunchArgs a, int64_t b0) {
   return a;
 }
 
-// A call of the plugin surface on a band handle, either element type (Float32: the element arrays are float arrays behind the
-// double* of LaunchArgs, see as_args): exactly one launch of the band kernels.  try_to_factorize is the forward sweep alone;
+// A call of the plugin surface on a band handle, either element type: exactly one launch of the band kernels.  try_to_factorize is
+// the forward sweep alone;
 // solve_ldl! factorises the values of the last factorisation again (rho slots as the ladder left them) and sweeps the new
 // right-hand side in the same launch — the band kernels' six-element records hold z = c / d of the one right-hand side they were
 // computed with, so there is no stored factor a second right-hand side could use.
-int run_band(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, double* d_d, hipStream_t stream) {
+int run_band(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream) {
   // (a band handle owns the band factor records alone: the buffers of the other kernels do not exist for it)
   if (a.skip_done || a.only_if_status || (a.mode == cnl::MODE_NEWTON && !d_rhs))
     return fail(CNL_ERR_STATE, "this call is not served by the band kernels, and a band handle has no other"
                                " (no factor panels, no condensed buffer; interleaved `vals` are the band kernels' layout)");
   if (a.mode == cnl::MODE_SOLVE && !h->last_vals) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
   if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
-  a.vals = a.mode == cnl::MODE_SOLVE ? const_cast<double*>(h->last_vals) : d_vals;
+  a.vals = a.mode == cnl::MODE_SOLVE ? const_cast<void*>(h->last_vals) : d_vals;
   a.rhs = d_rhs; a.d = d_d;
   a.batch = (int)h->batch;
-  a.L = static_cast<double*>(h->d_Lband);
+  a.L = h->d_Lband;
   a.layout = h->layout;
   if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
   const hipError_t e = h->f32 ? cnl::launch_band_f32(h->bd, h->band_nl, a, stream, h->band_npiece)
@@ -72,7 +72,7 @@ int run_band(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_
 // surface as one classic launch each (on a condensed plan between the float condensation passes), and nothing else; with tuning
 // float32_register_front the launch of newton_system / try_to_factorize is the register-front kernel's float instantiation
 // (launch(), below).  rhs: the right-hand side the call was given
-int f32_general_serves(const cnl_handle* h, const cnl::LaunchArgs& a, const double* rhs) {
+int f32_general_serves(const cnl_handle* h, const cnl::LaunchArgs& a, const void* rhs) {
   if (h->f32 && (a.skip_done || a.only_if_status || (a.mode == cnl::MODE_NEWTON && !rhs) || !h->f32_general))
     return fail(CNL_ERR_STATE, "this call is not served by the Float32 instantiation of the general kernel, and the handle has no other");
   return CNL_OK;
@@ -128,22 +128,19 @@ int launch_staged(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
 // SubBatch (handle.h): the view is set up by moving the handle's own pointers, and undone when it goes out of scope
 SubBatch::SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged) : h(h_) {
   last_vals = h->last_vals; staged = h->staged;
-  // (last_vals and the band records are arrays of the handle's element type behind their double* / void*: offsets in bytes)
-  const size_t esz = h->f32 ? sizeof(float) : sizeof(double);
-  if (h->last_vals) h->last_vals = reinterpret_cast<const double*>(reinterpret_cast<const char*>(h->last_vals) + b0 * h->plan->nnz * esz);
+  h->last_vals = elem_offset(h, h->last_vals, b0 * h->plan->nnz);
   if (!allow_staged) h->staged = false;
   batch = h->batch; L = h->d_L; gs = h->d_gs; scratch = h->d_scratch; cbuf = h->d_cbuf; d2 = h->d_d2;
   xpos = h->d_xpos; xzer = h->d_xzer; gcnt = h->d_gcnt; dep = h->d_dep; lad = h->d_lad; stat = h->d_stat;
   Lband = h->d_Lband;
-  if (h->d_Lband) h->d_Lband = static_cast<char*>(h->d_Lband) + b0 * h->bd.lsize * esz;
+  h->d_Lband = elem_offset(h, h->d_Lband, b0 * h->bd.lsize);
   const cnl::Cond& C = h->plan->C;
   h->batch = nb;
-  // (factor panels, scratch, condensed buffer and reduced solution hold the handle's element type behind their double*)
   h->d_L = elem_offset(h, h->d_L, b0 * h->dp.lsize);
-  if (h->d_gs) h->d_gs = elem_offset(h, h->d_gs, b0 * h->dp2.gs_doubles);
-  if (h->d_scratch) h->d_scratch = elem_offset(h, h->d_scratch, b0 * (int64_t)h->dp.work_doubles);
-  if (h->d_cbuf) h->d_cbuf = elem_offset(h, h->d_cbuf, b0 * C.cstride);
-  if (h->d_d2) h->d_d2 = elem_offset(h, h->d_d2, b0 * C.N2);
+  h->d_gs = elem_offset(h, h->d_gs, b0 * h->dp2.gs_doubles);
+  h->d_scratch = elem_offset(h, h->d_scratch, b0 * (int64_t)h->dp.work_doubles);
+  h->d_cbuf = elem_offset(h, h->d_cbuf, b0 * C.cstride);
+  h->d_d2 = elem_offset(h, h->d_d2, b0 * C.N2);
   if (h->d_xpos) h->d_xpos += b0;
   if (h->d_xzer) h->d_xzer += b0;
   if (h->d_gcnt) h->d_gcnt += 2 * b0;
@@ -164,7 +161,7 @@ namespace {
 // on the caller's stream, the rest single-stream on a second stream of the handle, forked and joined with events (no host
 // synchronisation).  Both parts use the SAME plan — the chain order has the throughput order's fronts, and the classic launch
 // runs any plan's records from end to end (it already does behind every staged attempt).
-int run_split(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, double* d_d, hipStream_t stream) {
+int run_split(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream) {
   if (!h->aux_stream && !h->tail && !h->split_halves) {
     HIPCHK(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
@@ -187,10 +184,10 @@ int run_split(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d
       rc = run(h, b, d_vals, d_rhs, d_d, stream);
     }
     if (rc == CNL_OK) {
-      cnl::LaunchArgs b = shifted(a, nA);
-      double* tv = d_vals ? d_vals + nA * nnz : nullptr;
-      const double* tr = d_rhs ? d_rhs + nA * N : nullptr;
-      double* td = d_d ? d_d + nA * N : nullptr;
+      cnl::LaunchArgs b = shifted(h, a, nA);
+      void* tv = elem_offset(h, d_vals, nA * nnz);
+      const void* tr = elem_offset(h, d_rhs, nA * N);
+      void* td = elem_offset(h, d_d, nA * N);
       if (on_tail) {
         t->first_attempt_only = h->first_attempt_only;
         rc = run(t, b, tv, tr, td, stream);
@@ -215,8 +212,8 @@ int run_split(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d
     for (int part = 0; part < 2 && rc == CNL_OK; part++) {
       const int64_t b0 = part ? nA : 0, nb = part ? nB : nA;
       SubBatch view(h, b0, nb, true);
-      cnl::LaunchArgs b = shifted(a, b0);
-      rc = run(h, b, d_vals ? d_vals + b0 * nnz : nullptr, d_rhs ? d_rhs + b0 * N : nullptr, d_d ? d_d + b0 * N : nullptr, stream);
+      cnl::LaunchArgs b = shifted(h, a, b0);
+      rc = run(h, b, elem_offset(h, d_vals, b0 * nnz), elem_offset(h, d_rhs, b0 * N), elem_offset(h, d_d, b0 * N), stream);
     }
     h->in_split = false;
     h->timing = tm;
@@ -229,8 +226,8 @@ int run_split(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d
   int rc;
   {
     SubBatch view(h, nA, nB, false);
-    cnl::LaunchArgs b = shifted(a, nA);
-    rc = run(h, b, d_vals ? d_vals + nA * nnz : nullptr, d_rhs ? d_rhs + nA * N : nullptr, d_d ? d_d + nA * N : nullptr, h->aux_stream);
+    cnl::LaunchArgs b = shifted(h, a, nA);
+    rc = run(h, b, elem_offset(h, d_vals, nA * nnz), elem_offset(h, d_rhs, nA * N), elem_offset(h, d_d, nA * N), h->aux_stream);
   }
   if (rc == CNL_OK) {
     SubBatch view(h, 0, nA, true);
@@ -265,39 +262,41 @@ int launch_redo(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
 // condense: which slots of the handle's condensed buffer are formed from `vals` [and `rhs`] — the values are the tiled kernel's mask
 // (1 matrix, 2 rho, 4 right-hand-side slots), the plain kernel takes the same choice as a slot range
 enum CondensePart { MATRIX_ONLY = 3, RHS_ONLY = 4, WHOLE_SYSTEM = 7 };
-// (a Float32 handle's arrays are float arrays behind the double* of this file: the passes' float instantiations take them)
+// (T: the handle's element type, picked from h->f32 by the three functions without a T; each types its arguments once on entry)
 template <class T>
-hipError_t condense_t(cnl_handle* h, CondensePart part, const double* vals, const double* rhs, hipStream_t stream) {
+hipError_t condense_t(cnl_handle* h, CondensePart part, const void* vals, const void* rhs, hipStream_t stream) {
   const cnl::Cond& C = h->plan->C;
   const int B = (int)h->batch, s_mat = (int)(C.ncs + C.nvar), s_all = (int)C.cstride;
-  const T* v = reinterpret_cast<const T*>(vals);
-  const T* r = reinterpret_cast<const T*>(rhs);
-  T* cbuf = reinterpret_cast<T*>(h->d_cbuf);
+  const T* v = static_cast<const T*>(vals);
+  const T* r = static_cast<const T*>(rhs);
+  T* cbuf = static_cast<T*>(h->d_cbuf);
   if constexpr (sizeof(T) == 4)
     if (h->cond_resident)
       return cnl::launch_condense_resident(h->dce, v, r, cbuf, part == RHS_ONLY ? s_mat : 0, part == MATRIX_ONLY ? s_mat : s_all, B, stream);
   return C.tiled_ok ? cnl::launch_condense_tiled(h->dc, v, r, cbuf, part, C.ch_region[3], B, stream)
                     : cnl::launch_condense(h->dc, v, r, cbuf, part == RHS_ONLY ? s_mat : 0, part == MATRIX_ONLY ? s_mat : s_all, B, stream);
 }
-int condense(cnl_handle* h, CondensePart part, const double* vals, const double* rhs, hipStream_t stream) {
+int condense(cnl_handle* h, CondensePart part, const void* vals, const void* rhs, hipStream_t stream) {
   const hipError_t e = h->f32 ? condense_t<float>(h, part, vals, rhs, stream) : condense_t<double>(h, part, vals, rhs, stream);
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("condense: ") + hipGetErrorString(e));
   return CNL_OK;
 }
 // inertia of the condensed pivots, for the kernels that do not count them themselves (Float32: against eig_tol narrowed to float)
-int cond_inertia(cnl_handle* h, const double* vals, double eig_tol, hipStream_t stream) {
-  const hipError_t e = h->f32 ? cnl::launch_cond_inertia(h->dc, reinterpret_cast<const float*>(vals), h->d_xpos, h->d_xzer, (float)eig_tol, (int)h->batch, stream)
-                              : cnl::launch_cond_inertia(h->dc, vals, h->d_xpos, h->d_xzer, eig_tol, (int)h->batch, stream);
+int cond_inertia(cnl_handle* h, const void* vals, double eig_tol, hipStream_t stream) {
+  const hipError_t e = h->f32 ? cnl::launch_cond_inertia(h->dc, static_cast<const float*>(vals), h->d_xpos, h->d_xzer, (float)eig_tol, (int)h->batch, stream)
+                              : cnl::launch_cond_inertia(h->dc, static_cast<const double*>(vals), h->d_xpos, h->d_xzer, eig_tol, (int)h->batch, stream);
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("condense: ") + hipGetErrorString(e));
   return CNL_OK;
 }
 // post-pass: the condensed components of d (and, d2 != nullptr, the kept ones out of the reduced solution)
-int expand(cnl_handle* h, const double* vals, const double* rhs, const double* d2, double* d, const int* success, int copy_rho_tail,
-           hipStream_t stream) {
-  const hipError_t e = h->f32 ? cnl::launch_expand(h->dc, reinterpret_cast<float*>(const_cast<double*>(vals)), reinterpret_cast<const float*>(rhs),
-                                                   reinterpret_cast<const float*>(d2), reinterpret_cast<const float*>(h->d_cbuf),
-                                                   reinterpret_cast<float*>(d), success, copy_rho_tail, (int)h->batch, stream)
-                              : cnl::launch_expand(h->dc, const_cast<double*>(vals), rhs, d2, h->d_cbuf, d, success, copy_rho_tail, (int)h->batch, stream);
+template <class T>
+hipError_t expand_t(cnl_handle* h, const void* vals, const void* rhs, const void* d2, void* d, const int* success, int copy_rho_tail, hipStream_t stream) {
+  return cnl::launch_expand(h->dc, static_cast<T*>(const_cast<void*>(vals)), static_cast<const T*>(rhs), static_cast<const T*>(d2),
+                            static_cast<const T*>(h->d_cbuf), static_cast<T*>(d), success, copy_rho_tail, (int)h->batch, stream);
+}
+int expand(cnl_handle* h, const void* vals, const void* rhs, const void* d2, void* d, const int* success, int copy_rho_tail, hipStream_t stream) {
+  const hipError_t e = h->f32 ? expand_t<float>(h, vals, rhs, d2, d, success, copy_rho_tail, stream)
+                              : expand_t<double>(h, vals, rhs, d2, d, success, copy_rho_tail, stream);
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("expand: ") + hipGetErrorString(e));
   return CNL_OK;
 }
@@ -305,7 +304,7 @@ int expand(cnl_handle* h, const double* vals, const double* rhs, const double* d
 }  // namespace
 
 // One call of the path on device-resident data: [condense ->] multifrontal kernel [-> expand].
-int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, double* d_d, hipStream_t stream) {
+int run(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream) {
   const cnl::Cond& C = h->plan->C;
   int rc = CNL_OK;
   if (h->split_staged > 0 && !h->in_split && (h->staged || h->tail) && h->split_staged < h->batch) return run_split(h, a, d_vals, d_rhs, d_d, stream);
@@ -319,8 +318,8 @@ int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, 
     // is decided on the device
     std::string err;
     if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
-    rc = cnl::dense_run(h->dense, h->plan->D, a.mode, d_vals, d_rhs, d_d, a.rho_old, a.rho, a.nfact, a.success, a.npos, a.nzero,
-                        a.params, stream, err);
+    rc = cnl::dense_run(h->dense, h->plan->D, a.mode, f64(h, d_vals), f64(h, d_rhs), f64(h, d_d), f64(h, a.rho_old), f64(h, a.rho), a.nfact,
+                        a.success, a.npos, a.nzero, a.params, stream, err);
     if (rc) return fail(rc == 5 ? CNL_ERR_STATE : CNL_ERR_HIP, "dense backend: " + err);
     return end_timed(h, stream);
   }
@@ -336,13 +335,13 @@ int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, 
       if ((rc = condense(h, nw ? WHOLE_SYSTEM : MATRIX_ONLY, d_vals, nw ? d_rhs : nullptr, stream))) return rc;
       if ((rc = cond_inertia(h, d_vals, a.params[0], stream))) return rc;
     }
-    rc = cnl::dense_run_general(h->gdense, h->gops, a.mode, h->d_cbuf, h->d_xpos, h->d_xzer, h->d_d2,
-                                d_vals ? d_vals + (C.nnz - C.nvar) : nullptr, C.nnz, a.rho_old, a.rho, a.nfact, a.success, a.npos, a.nzero,
-                                a.params, stream, err);
+    rc = cnl::dense_run_general(h->gdense, h->gops, a.mode, f64(h, h->d_cbuf), h->d_xpos, h->d_xzer, f64(h, h->d_d2),
+                                d_vals ? f64(h, d_vals) + (C.nnz - C.nvar) : nullptr, C.nnz, f64(h, a.rho_old), f64(h, a.rho), a.nfact, a.success,
+                                a.npos, a.nzero, a.params, stream, err);
     if (rc) return fail(CNL_ERR_HIP, "dense backend: " + err);
     if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
     else {
-      const double* vsrc = a.mode == cnl::MODE_SOLVE ? h->last_vals : d_vals;
+      const void* vsrc = a.mode == cnl::MODE_SOLVE ? h->last_vals : d_vals;
       if ((rc = expand(h, vsrc, d_rhs, h->d_d2, d_d, a.mode == cnl::MODE_NEWTON ? a.success : nullptr, 0, stream))) return rc;
     }
     return end_timed(h, stream);
@@ -351,7 +350,7 @@ int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, 
     a.vals = d_vals; a.rhs = d_rhs; a.d = d_d;
     rc = launch(h, a, stream);
   } else {
-    double* crhs = elem_offset(h, h->d_cbuf, C.ncs + C.nvar);   // the right-hand-side slots of the condensed buffer
+    void* crhs = elem_offset(h, h->d_cbuf, C.ncs + C.nvar);   // the right-hand-side slots of the condensed buffer
     const bool direct = h->use_v2 && h->plan->P.rec_direct;  // the register-front kernel condenses on the fly
     const bool count_d = direct && h->dp2.count_d;  // the kernel counts the condensed pivots itself
     if (direct && a.mode == cnl::MODE_NEWTON) {
@@ -407,7 +406,7 @@ int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, 
     } else if (direct && h->v2_solve) {
       // solve_ldl! on the register-front kernel: forward substitution with the stored factor, backward sweep, post-pass
       if (!h->last_vals) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
-      a.vals = const_cast<double*>(h->last_vals); a.rhs = d_rhs; a.d = d_d;
+      a.vals = const_cast<void*>(h->last_vals); a.rhs = d_rhs; a.d = d_d;
       if (h->staged) {  // solve_ldl! stage by stage: forward substitution of the tasks, then their backward sweeps
         if ((rc = launch_staged(h, a, stream))) return rc;
         if ((rc = launch_redo(h, a, stream))) return rc;

@@ -88,19 +88,19 @@ struct cnl_handle {
   cnl::DevPlan2 dp2{};
   int wpb2 = 1;
   size_t lds2 = 0;
-  double* d_gs = nullptr;
+  void* d_gs = nullptr;   // global scratch of the register-front kernel, in the handle's element type (as d_cbuf, d_d2, d_L, d_scratch)
   // condensation state
   cnl::DevCond dc{};
-  double* d_cbuf = nullptr;   // [batch][cstride]
-  double* d_d2 = nullptr;     // [batch][N2]
+  void* d_cbuf = nullptr;   // [batch][cstride]
+  void* d_d2 = nullptr;     // [batch][N2]
   int *d_xpos = nullptr, *d_xzer = nullptr;
   // Float32 general handles on a condensed plan: the resident condense kernel serves the handle (kernels.h: DevCondEll) — where the
   // tiled kernel's chunks degenerate (dense Jacobians) and [vals | rhs] of a problem fits LDS; tuning float32_condense = 2: never
   bool cond_resident = false;
   cnl::DevCondEll dce{};
-  const double* last_vals = nullptr;  // device vals of the last factorisation (needed to condense later right-hand sides)
-  double* d_L = nullptr;
-  double* d_scratch = nullptr;
+  const void* last_vals = nullptr;  // device vals of the last factorisation (needed to condense later right-hand sides)
+  void* d_L = nullptr;
+  void* d_scratch = nullptr;
   // staging for the host-pointer API, in the handle's element type (capi_calls.cpp: ensure_staging, stage<T>): vals, rhs, d, the
   // per-problem results as one block [rho | rho_old | nfact | success] (nfact / success: int32), and [npos | nzero]
   void *d_vals = nullptr, *d_rhs = nullptr, *d_d = nullptr, *d_res = nullptr;
@@ -159,6 +159,7 @@ struct cnl_handle {
   // dp2, wpb2 / lds2 and a FLOAT global scratch behind d_gs (every "doubles" of dp2 counts floats); newton_system / factorize then
   // launch the register-front kernel's float instantiation, the solve stays on the general kernel (v2_solve, lean, staged: false).
   bool f32_general = false;
+  size_t esz() const { return f32 ? sizeof(float) : sizeof(double); }   // bytes per element of every element array of the handle
 };
 
 struct cnl_multi {
@@ -215,11 +216,17 @@ inline int need_full_batch(const cnl_handle* h, const char* fn) {
     if (e_ != hipSuccess) return fail(CNL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
-// p + n elements of the handle's element type: the factor panels, work area, condensed buffer and reduced solution of a Float32
-// handle are float arrays behind their double*
-inline double* elem_offset(const cnl_handle* h, double* p, int64_t n) {
-  return h->f32 ? reinterpret_cast<double*>(reinterpret_cast<float*>(p) + n) : p + n;
+// p + n elements of the handle's element type (an absent array stays absent): the one place that does arithmetic on an untyped
+// element array
+inline const void* elem_offset(const cnl_handle* h, const void* p, int64_t n) { return p ? static_cast<const char*>(p) + n * (int64_t)h->esz() : nullptr; }
+inline void* elem_offset(const cnl_handle* h, void* p, int64_t n) { return const_cast<void*>(elem_offset(h, static_cast<const void*>(p), n)); }
+// An element array of a Float64 handle, typed, for the routes only Float64 handles have (the dense backends).  To be called behind the
+// point where a Float32 handle has been refused (run(): f32_general_serves); one that gets here all the same is a bug, and aborts.
+inline double* f64(const cnl_handle* h, void* p) {
+  if (h->f32) { fprintf(stderr, "cannoles_hip: a Float64-only route was reached on a Float32 handle\n"); abort(); }
+  return static_cast<double*>(p);
 }
+inline const double* f64(const cnl_handle* h, const void* p) { return f64(h, const_cast<void*>(p)); }
 
 template <class T>
 int upload(cnl_handle* h, const std::vector<T>& v, const T** out) {
@@ -244,6 +251,13 @@ int dalloc(cnl_handle* h, T** out, size_t count) {
   if (G && getenv("CNL_DBG_GUARD_LOG")) fprintf(stderr, "[dalloc] #%zu %p + %zu bytes\n", h->dev_allocs.size(), (void*)*out, bytes);
   return CNL_OK;
 }
+// count elements of the handle's element type
+inline int dalloc_elems(cnl_handle* h, void** out, size_t count) {
+  char* p = nullptr;
+  const int rc = dalloc(h, &p, count * h->esz());
+  *out = p;
+  return rc;
+}
 
 // ---- capi_plan.cpp ----
 int resolve_options(const cnl_options* in, cnl::Tuning& out);
@@ -259,7 +273,7 @@ const cnl::BandPlan& band_program(const cnl_plan* plan, bool f32);
 int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device);
 
 // ---- capi_run.cpp ----
-int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, double* d_d, hipStream_t stream);
+int run(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream);
 
 // run() on problems [b0, b0 + nb) of the handle: the base pointer of every per-problem device array of the handle is moved to
 // problem b0 and the batch set to nb for the lifetime of the view (b0 a multiple of 4: a wavefront serves four problems).
@@ -267,10 +281,9 @@ int run(cnl_handle* h, cnl::LaunchArgs& a, double* d_vals, const double* d_rhs, 
 struct SubBatch {
   cnl_handle* h;
   int64_t batch;
-  double *L, *gs, *scratch, *cbuf, *d2;
-  void* Lband;
+  void *L, *gs, *scratch, *cbuf, *d2, *Lband;
   int *xpos, *xzer, *gcnt, *dep, *lad, *stat;
-  const double* last_vals;
+  const void* last_vals;
   bool staged;
   SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged = true);
   ~SubBatch();

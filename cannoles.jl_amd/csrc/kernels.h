@@ -33,7 +33,7 @@ struct KernelConfig {
   size_t lds_bytes = 0;  // dynamic LDS per workgroup
 };
 
-// device-resident v2 plan (record streams, see plan.h / kernels2.hip)
+// device-resident v2 plan (record streams, see plan.h / kernels2.hip); elements: doubles, or floats on a Float32 handle
 struct DevPlan2 {
   const int32_t* rec;
   const int32_t* brec;
@@ -43,13 +43,13 @@ struct DevPlan2 {
   int32_t reccap;        // words of the forward record buffer (one per wave)
   int32_t breccap;       // words per backward record buffer (two per wave, same LDS area)
   int32_t recwords;      // words of that area = max(reccap, 2 * breccap)
-  int32_t u2_peak;       // doubles: per-problem LDS update stack; the staging triangle follows it
-  int32_t prob_doubles;  // doubles of LDS per problem
-  int32_t jraw_off;      // doubles: offset of the raw-value area of the on-the-fly condensation inside the per-problem LDS
-  int32_t bpanel_off;    // doubles: offset of the backward sweep's two panel buffers inside the per-problem LDS (behind the x stack)
-  int64_t gs_doubles;    // doubles of global scratch per problem
+  int32_t u2_peak;       // elements: per-problem LDS update stack; the staging triangle follows it
+  int32_t prob_doubles;  // elements of LDS per problem
+  int32_t jraw_off;      // elements: offset of the raw-value area of the on-the-fly condensation inside the per-problem LDS
+  int32_t bpanel_off;    // elements: offset of the backward sweep's two panel buffers inside the per-problem LDS (behind the x stack)
+  int64_t gs_doubles;    // elements of global scratch per problem
   int64_t lsize;
-  int64_t vstride, rstride, dstride;  // per-problem strides (doubles) of vals / rhs / d
+  int64_t vstride, rstride, dstride;  // per-problem strides (elements) of vals / rhs / d
 };
 
 // device-resident condensation lists (condense.h)
@@ -112,22 +112,23 @@ enum { RVT_FSLO = 0, RVT_WF, RVT_RLO, RVT_WR, RVT_CSLO, RVT_WC, RVT_LLO, RVT_WL,
 
 enum { MODE_NEWTON = 0, MODE_FACTOR = 1, MODE_SOLVE = 2 };
 
+// The element arrays (vals, rhs, d, L, scratch, rho_old, rho) are in the launch's element type: the _f32 launchers read them as float.
 struct LaunchArgs {
   int mode;
   int batch;
-  double* vals;          // [batch][nnz]   (NEWTON: rho tail written back; FACTOR: read only)
-  const double* rhs;     // [batch][N]     (NEWTON, SOLVE)
+  void* vals;            // [batch][nnz]   (NEWTON: rho tail written back; FACTOR: read only)
+  const void* rhs;       // [batch][N]     (NEWTON, SOLVE)
   int layout;            // band kernels, 32 problems per workgroup: bit 0 = vals, bit 1 = rhs interleaved over the workgroup's problems (band.h: band_il_index)
-  double* d;             // [batch][N]     (NEWTON, SOLVE)
-  double* L;             // [batch][lsize] factor storage
-  double* scratch;       // [batch][work_doubles] when !lds_work
-  double* rho_old;       // [batch] in/out (NEWTON)
-  double* rho;           // [batch] out    (NEWTON)
+  void* d;               // [batch][N]     (NEWTON, SOLVE)
+  void* L;               // [batch][lsize] factor storage
+  void* scratch;         // [batch][work_doubles] when !lds_work
+  void* rho_old;         // [batch] in/out (NEWTON)
+  void* rho;             // [batch] out    (NEWTON)
   int32_t* nfact;        // [batch] out    (NEWTON)
   int32_t* success;      // [batch] out    (NEWTON: solve_success, FACTOR: success)
   int64_t* npos;         // [batch] optional (FACTOR)
   int64_t* nzero;        // [batch] optional (FACTOR)
-  double params[9];      // ParamCaNNOLeS; params[0] = eig_tol also for FACTOR
+  double params[9];      // ParamCaNNOLeS; params[0] = eig_tol also for FACTOR (a Float32 launch: the Float32 parameters, widened)
   const int* extra_pos;  // [batch] optional: inertia counts of pivots eliminated outside the kernel (condensed r nodes)
   const int* extra_zer;
   // staged execution (latency plans, kernels2.hip STAGED): one launch per phase when `dep` is given (a task waits for its
@@ -193,25 +194,22 @@ struct BandDev {
 // resident: P is the resident form of the 15-piece program (band.h) — nl = 32, `vals` interleaved (a.layout & 1)
 // mover: ... whose epoch blocks carry the mover table in place of the piece descriptors (band.h, BAND_MK_*)
 hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece = 15, bool resident = false, bool mover = false);
-// the same on Float32 data: a.vals / rhs / d / L / rho_old / rho hold float arrays (stored through the double* fields), a.params the
-// Float32 parameters widened to double; P is the 4-byte program (build_band_plan with esz = 4), P.lsize counts floats
+// the same on Float32 data: P is the 4-byte program (build_band_plan with esz = 4), P.lsize counts floats
 hipError_t launch_band_f32(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece = 15);
 bool band_wide_has(int esz, int nl);   // is there a wide (20-piece) instance for this element size and problems per workgroup?
 size_t band_lds_bytes(int nparts, int nl, int esz = 8, int npiece = 15);   // esz: bytes per element (8 double, 4 float); npiece: of the program
 
 // returns hipSuccess or the launch error
 hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream);
-// the same kernel on Float32 data (a Float32 handle off the band kernels, tuning float32_general): a.vals / rhs / d / L / scratch /
-// rho_old / rho hold float arrays (stored through the double* fields), a.params the Float32 parameters widened to double; every
-// offset, stride and size of P counts elements, cfg.lds_bytes = 4 * (16 + ppb * work area).  Only the configurations
-// newton_f32_has() names are compiled for float; any other is hipErrorInvalidConfiguration.
+// the same kernel on Float32 data (a Float32 handle off the band kernels, tuning float32_general): every offset, stride and size of
+// P counts elements, cfg.lds_bytes = 4 * (16 + ppb * work area).  Only the configurations newton_f32_has() names are compiled for
+// float; any other is hipErrorInvalidConfiguration.
 hipError_t launch_newton_f32(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream);
 bool newton_f32_has(int tpp, int ppb, bool lds_work);
 hipError_t launch_newton2(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream);
-// the register-front kernel on Float32 data (a Float32 general handle with tuning float32_register_front): a.vals / rhs / d / L /
-// scratch / rho_old / rho hold float arrays (stored through the double* fields), a.params the Float32 parameters widened to double;
-// every size of P that says "doubles" counts floats, lds_bytes is computed with 4-byte elements (the record area stays in 32-bit
-// words).  MODE_NEWTON and MODE_FACTOR on non-direct records only: anything else is hipErrorInvalidConfiguration.
+// the register-front kernel on Float32 data (a Float32 general handle with tuning float32_register_front): every size of P named
+// "doubles" counts floats, lds_bytes is computed with 4-byte elements (the record area stays in 32-bit words).  MODE_NEWTON and
+// MODE_FACTOR on non-direct records only: anything else is hipErrorInvalidConfiguration.
 hipError_t launch_newton2_f32(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream);
 // one attempt at the rho given in vals, stage by stage (stage_ptr: host array of nstages + 1 task offsets)
 hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, LaunchArgs a, const int32_t* stage_ptr, int nstages, hipStream_t stream);

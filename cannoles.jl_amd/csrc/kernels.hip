@@ -21,7 +21,7 @@
 // Every function is a template on the element type T: double for the Float64 handles, float for the Float32 handles that run on
 // this kernel (tuning float32_general).  With T = float values, right-hand side, d, rho, the factor panels, the
 // work area and the reduction scratch are float and every operation is a float operation; the parameters arrive widened in
-// LaunchArgs::params and are narrowed back, the float arrays travel behind the double* fields of LaunchArgs.
+// LaunchArgs::params and are narrowed back.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -286,12 +286,12 @@ __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, con
   A.extra_pos = as_global(Ain.extra_pos); A.extra_zer = as_global(Ain.extra_zer);
   extern __shared__ double smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
-  // the element arrays of this launch, in the kernel's element type (LaunchArgs carries them as double*)
-  T* const a_vals = reinterpret_cast<T*>(A.vals);
-  const T* const a_rhs = reinterpret_cast<const T*>(A.rhs);
-  T* const a_d = reinterpret_cast<T*>(A.d);
-  T* const a_rho_old = reinterpret_cast<T*>(A.rho_old);
-  T* const a_rho = reinterpret_cast<T*>(A.rho);
+  // the element arrays of this launch, in the kernel's element type (LaunchArgs carries them untyped)
+  T* const a_vals = static_cast<T*>(A.vals);
+  const T* const a_rhs = static_cast<const T*>(A.rhs);
+  T* const a_d = static_cast<T*>(A.d);
+  T* const a_rho_old = static_cast<T*>(A.rho_old);
+  T* const a_rho = static_cast<T*>(A.rho);
   const int gl = threadIdx.x / TPP;     // problem slot inside the workgroup
   const int tid = threadIdx.x % TPP;
   const int b = blockIdx.x * PPB + gl;
@@ -299,10 +299,10 @@ __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, con
   ProblemCtx<T> c;
   c.vals = a_vals ? a_vals + (long long)b * P.vstride : nullptr;
   c.rhs = a_rhs ? a_rhs + (long long)b * P.rstride : nullptr;
-  c.L = reinterpret_cast<T*>(A.L) + (long long)b * P.lsize;
+  c.L = static_cast<T*>(A.L) + (long long)b * P.lsize;
   T* redbase = smem;                    // 16 elements for cross-wave sums (TPP > 64)
   c.red = redbase;
-  c.W = LDSW ? (smem + 16 + (long long)gl * P.work_doubles) : (reinterpret_cast<T*>(A.scratch) + (long long)b * P.work_doubles);
+  c.W = LDSW ? (smem + 16 + (long long)gl * P.work_doubles) : (static_cast<T*>(A.scratch) + (long long)b * P.work_doubles);
   T* dout = a_d ? a_d + (long long)b * P.dstride : nullptr;
   const T eig_tol = (T)A.params[0];
   const int xpos = A.extra_pos ? A.extra_pos[b] : 0, xzer = A.extra_zer ? A.extra_zer[b] : 0;

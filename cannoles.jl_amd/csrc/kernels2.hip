@@ -748,10 +748,10 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
   A.scratch = as_global(Ain.scratch); A.rho_old = as_global(Ain.rho_old); A.rho = as_global(Ain.rho);
   A.nfact = as_global(Ain.nfact); A.success = as_global(Ain.success); A.npos = as_global(Ain.npos); A.nzero = as_global(Ain.nzero);
   A.extra_pos = as_global(Ain.extra_pos); A.extra_zer = as_global(Ain.extra_zer);
-  // the element arrays, typed (a Float32 handle's float arrays travel behind the double* fields of LaunchArgs)
-  T* const A_vals = reinterpret_cast<T*>(A.vals); const T* const A_rhs = reinterpret_cast<const T*>(A.rhs); T* const A_d = reinterpret_cast<T*>(A.d);
-  T* const A_L = reinterpret_cast<T*>(A.L); T* const A_scratch = reinterpret_cast<T*>(A.scratch);
-  T* const A_rho_old = reinterpret_cast<T*>(A.rho_old); T* const A_rho = reinterpret_cast<T*>(A.rho);
+  // the element arrays, typed
+  T* const A_vals = static_cast<T*>(A.vals); const T* const A_rhs = static_cast<const T*>(A.rhs); T* const A_d = static_cast<T*>(A.d);
+  T* const A_L = static_cast<T*>(A.L); T* const A_scratch = static_cast<T*>(A.scratch);
+  T* const A_rho_old = static_cast<T*>(A.rho_old); T* const A_rho = static_cast<T*>(A.rho);
   typedef typename Real<T>::T2 T2;
   const int WPB = blockDim.x >> 6;
   extern __shared__ double smem[];
