@@ -80,12 +80,13 @@ int ensure_staging(cnl_handle* h) {
 // handle's element type).  d_vals is written by newton_system alone.  params: np values (exact in double; a Float32 kernel narrows
 // them back).
 template <class T>
-int run_typed(cnl_handle* h, int mode, const T* params, int np, const Results<T>& r, const T* d_vals, const T* d_rhs, T* d_d, hipStream_t stream) {
+int run_typed(cnl_handle* h, int mode, const T* params, int np, const Results<T>& r, const T* d_vals, const T* d_rhs, T* d_d, hipStream_t stream,
+              RunOpts o = {}) {
   cnl::LaunchArgs a{};
   a.mode = mode;
   a.rho_old = r.rho_old; a.rho = r.rho; a.nfact = r.nfact; a.success = r.success; a.npos = r.npos; a.nzero = r.nzero;
   for (int k = 0; k < np; k++) a.params[k] = params[k];
-  return run(h, a, const_cast<T*>(d_vals), d_rhs, d_d, stream);
+  return run(h, a, const_cast<T*>(d_vals), d_rhs, d_d, stream, o);
 }
 // where newton_system on the staged arrays leaves its results, for the problems from b0 on (no inertia counts: try_to_factorize's)
 template <class T>
@@ -95,8 +96,11 @@ Results<T> newton_results(const Stage<T>& s, size_t b0 = 0) {
   return r;
 }
 
-// this handle now holds a factor of `vals` (device array of its element type).  ok: the success flags of a host-pointer call, which
-// cnl_solve consults; nullptr after a device-pointer call, whose flags the host has not seen
+// Inside a host-pointer newton_system that goes on after a factorisation (its ladders): the factor on the device is that of the
+// staged `vals` from here on, so a solve of the same call reads them.  (run() sets last_vals for try_to_factorize alone.)
+void factor_is_of(cnl_handle* h, const void* d_vals) { h->last_vals = d_vals; }
+// After a completed call, the only writer: this handle now holds a factor of `vals` (device array of its element type).  ok: the
+// success flags of a host-pointer call, which cnl_solve consults; nullptr after a device-pointer call, whose flags the host has not seen
 void holds_factor(cnl_handle* h, const void* d_vals, const int32_t* ok = nullptr) {
   h->factorized = true;
   h->factor_batch = h->batch;
@@ -318,12 +322,16 @@ int solve_staged_rhs(cnl_handle* h, const Stage<double>& s, const double params[
   return run_typed<double>(h, cnl::MODE_SOLVE, params, 9, Results<double>(), nullptr, s.rhs, s.d, h->stream);
 }
 
+bool host_ladder_serves(const cnl_handle* h, bool any_device_ladder);   // (below, with newton_small_pinned)
+
 // The rho ladder of src/CaNNOLeS.jl:1023-1047 driven from the host for the problems whose first (staged) factorisation failed:
 // every rung is a staged try_to_factorize of the batch and a read-back of the success flags; the solve follows (cnl_newton_system).
 // up: pinned staging of 12 bytes per problem; su_pin: pinned, batch ints.  On return rho / rho_old_out / nfact / success hold the
 // reference's results and the device holds the factors and the solution of everything that succeeded.
+// tail_redone: a dataflow wait of the remainder handle gave up in the first attempt — its redo launch has been through the whole
+// device ladder for those problems, and the ladder here must leave them alone.
 int host_ladder_run(cnl_handle* h, const double params[9], const double* rho_old, double* rho, double* rho_old_out, int32_t* nfact,
-                    int32_t* success, char* up, int32_t* su_pin) {
+                    int32_t* success, char* up, int32_t* su_pin, bool tail_redone = false) {
   const cnl_plan& P = *h->plan;
   const Stage<double> s = stage<double>(h);
   const size_t B = (size_t)h->batch;
@@ -336,7 +344,7 @@ int host_ladder_run(cnl_handle* h, const double params[9], const double* rho_old
   std::vector<double> ro_in(B);
   // split handles: only the chain part [0, split_staged) ran the first attempt alone; the single-stream part has been through the
   // whole device ladder already (a problem that exhausted it there must not climb again: nfact would count twice)
-  const size_t first_only = (h->split_staged > 0 && (size_t)h->split_staged < B && !h->split_halves && (!h->tail || h->tail_redone)) ? (size_t)h->split_staged : B;
+  const size_t first_only = (h->split_staged > 0 && (size_t)h->split_staged < B && !h->split_halves && (!h->tail || tail_redone)) ? (size_t)h->split_staged : B;
   bool any_act = false;
   for (size_t b = 0; b < B; b++) {
     ro_in[b] = rho_old ? rho_old[b] : 0.0;
@@ -363,8 +371,9 @@ int host_ladder_run(cnl_handle* h, const double params[9], const double* rho_old
   }
   for (size_t b = 0; b < first_only; b++)
     if (rho[b] != 0.0 && rho[b] <= rhomax) rho_old_out[b] = rho[b];   // (rho != 0: the problem entered the ladder)
-  // solve_ldl! for everything that holds a valid factor now (the problems of the first attempt are solved again: same factor)
-  h->last_vals = s.vals;
+  // solve_ldl! for everything that holds a valid factor now (the problems of the first attempt are solved again: same factor);
+  // the rungs were try_to_factorize calls on s.vals, also where the first attempt was a newton_system the caller gave other arrays
+  factor_is_of(h, s.vals);
   return solve_staged_rhs(h, s, params);
 }
 
@@ -384,6 +393,9 @@ int newton_system_pipelined(cnl_handle* h, double* vals, const double* rhs, doub
     HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     h->pipe_ev.push_back(e);
   }
+  // staged handles: the chunks run the first attempt only; the problems that failed it go through the host-driven ladder on the
+  // whole (now device-resident) batch behind the last chunk (see newton_staged_ladder), whatever device ladder the handle has
+  const bool host_ladder = host_ladder_serves(h, true);
   std::mutex mu;        // posted[], abort_, and the handle view (SubBatch mutates the handle: one enqueue at a time)
   std::condition_variable cv;
   std::vector<char> posted(nchunks, 0);
@@ -435,7 +447,8 @@ int newton_system_pipelined(cnl_handle* h, double* vals, const double* rhs, doub
       std::lock_guard<std::mutex> lk(mu);
       if (r == CNL_OK) {
         SubBatch view(h, (int64_t)b0, (int64_t)nb);
-        r = run_typed(h, cnl::MODE_NEWTON, params, 9, newton_results(s, b0), s.vals + b0 * P.nnz, s.rhs + b0 * P.N, s.d + b0 * P.N, st);
+        r = run_typed(h, cnl::MODE_NEWTON, params, 9, newton_results(s, b0), s.vals + b0 * P.nnz, s.rhs + b0 * P.N, s.d + b0 * P.N, st,
+                      RunOpts{host_ladder, false});
         if (r) m = g_err;
         if (r == CNL_OK && hipEventRecord(h->pipe_ev[c], st) != hipSuccess) { r = CNL_ERR_HIP; m = "hipEventRecord failed"; }
       }
@@ -444,24 +457,19 @@ int newton_system_pipelined(cnl_handle* h, double* vals, const double* rhs, doub
       cv.notify_all();
     }
   };
-  const bool tm = h->timing;
-  h->timing = false;
   h->tail_fresh = false;   // the chunks factorise every problem in THIS handle's storage (views), the remainder's handle is not used
-  // staged handles: the chunks run the first attempt only; the problems that failed it go through the host-driven ladder on the
-  // whole (now device-resident) batch behind the last chunk (see newton_staged_ladder)
-  const bool host_ladder = h->staged && !h->dense && !h->gdense && h->plan->opt.host_ladder != 0 && h->use_v2 && P.P.rec_direct && P.P.d_outer;
-  h->first_attempt_only = host_ladder;
-  std::vector<std::thread> ups;
-  for (int u = 1; u < NU; u++) ups.emplace_back(uploader, u);
-  uploader(0);
-  for (std::thread& th : ups) th.join();
-  h->first_attempt_only = false;
-  h->timing = tm;
+  {
+    TimingOff untimed(h);   // (a chunked call is not timed: cnl_newton_system comes here on an untimed handle only)
+    std::vector<std::thread> ups;
+    for (int u = 1; u < NU; u++) ups.emplace_back(uploader, u);
+    uploader(0);
+    for (std::thread& th : ups) th.join();
+  }
   down.join();
   for (int u = 0; u < NU; u++) (void)hipStreamSynchronize(h->pipe_stream[u]);
   for (int u = 0; u < NU; u++) if (urc[u] != CNL_OK) return fail(urc[u], umsg[u]);
   if (wrc != CNL_OK) return fail(wrc, "download: " + wmsg);
-  h->last_vals = s.vals;
+  factor_is_of(h, s.vals);   // (the chunks ran on views of the handle, which take their last_vals with them)
   if (host_ladder) {
     std::vector<char> failed(B, 0);
     bool any_failed = false;
@@ -532,20 +540,19 @@ int newton_dense_host_ladder(cnl_handle* h, double* vals, const double* rhs, dou
 // cfg3's size (38 ms for nfact = 6, ten times one CPU core of the oracle); it stays the device-pointer calls' fallback.
 // (handles whose in-kernel device ladder is available use that one: no round trip per rung — 0.67 against 0.9 ms for one system of
 //  cfg3's size that climbs to nfact = 6)
-bool host_ladder_serves(const cnl_handle* h) {
+// any_device_ladder: also where the in-kernel ladder is available (the chunked call: its chunks run on views, which have none)
+bool host_ladder_serves(const cnl_handle* h, bool any_device_ladder) {
   const cnl::Plan& P = h->plan->P;
   return h->staged && !h->dense && !h->gdense && h->plan->opt.host_ladder != 0 && h->use_v2 && P.rec_direct && P.d_outer &&
-         (h->lad_mode == 0 || h->split_staged > 0);
+         (any_device_ladder || h->lad_mode == 0 || h->split_staged > 0);
 }
 // The first attempt of the whole staged batch, as both routes below begin: inputs up, one call of run() — on a handle the host
 // ladder serves the staged attempt alone.
 int newton_first_attempt(cnl_handle* h, const Stage<double>& s, const double* vals, const double* rhs, const double* rho_old, const double params[9],
                          bool host_ladder) {
   HIPCHK(upload_inputs(h, s, 0, (size_t)h->batch, vals, rhs, rho_old, h->stream));
-  h->first_attempt_only = host_ladder;
-  const int rc = run_typed(h, cnl::MODE_NEWTON, params, 9, newton_results(s), s.vals, s.rhs, s.d, h->stream);
-  h->first_attempt_only = false;
-  if (rc == CNL_OK) h->last_vals = s.vals;
+  const int rc = run_typed(h, cnl::MODE_NEWTON, params, 9, newton_results(s), s.vals, s.rhs, s.d, h->stream, RunOpts{host_ladder, false});
+  if (rc == CNL_OK) factor_is_of(h, s.vals);   // (newton_system factorised them: what the caller does next on the device starts from here)
   return rc;
 }
 
@@ -584,7 +591,6 @@ int newton_small_pinned(cnl_handle* h, double* vals, const double* rhs, double* 
   if (host_ladder && h->tail && h->tail->d_dep && h->tail->d_stat)
     HIPCHK(hipMemcpyAsync(&tail_status, h->tail->d_stat, 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->tail_redone = tail_status != 0;
   std::memcpy(rho, pb + o_rho, B * 8);
   std::memcpy(rho_old_out, pb + o_ro, B * 8);
   std::memcpy(nfact, pb + o_nf, B * 4);
@@ -592,7 +598,7 @@ int newton_small_pinned(cnl_handle* h, double* vals, const double* rhs, double* 
   bool any_failed = false;
   for (size_t b = 0; b < B; b++) any_failed |= !success[b];
   if (host_ladder && any_failed && *up_status == 0) {
-    if ((rc = host_ladder_run(h, params, rho_old, rho, rho_old_out, nfact, success, pb + o_up, reinterpret_cast<int32_t*>(pb + o_su)))) return rc;
+    if ((rc = host_ladder_run(h, params, rho_old, rho, rho_old_out, nfact, success, pb + o_up, reinterpret_cast<int32_t*>(pb + o_su), tail_status != 0))) return rc;
     HIPCHK(hipMemcpyAsync(pb + o_d, s.d, B * P.N * 8, hipMemcpyDeviceToHost, h->stream));
     if (P.nvar > 0) {
       HIPCHK(hipMemcpy2DAsync(pb + o_tail, (size_t)P.nvar * 8, s.vals + (P.nnz - P.nvar), (size_t)P.nnz * 8, (size_t)P.nvar * 8, B,
@@ -635,7 +641,6 @@ int newton_staged_ladder(cnl_handle* h, double* vals, const double* rhs, double*
   if (h->d_dep && h->d_stat && h->split_staged == 0) HIPCHK(hipMemcpyAsync(&status_word, h->d_stat, 4, hipMemcpyDeviceToHost, h->stream));
   if (h->tail && h->tail->d_dep && h->tail->d_stat) HIPCHK(hipMemcpyAsync(&tail_status, h->tail->d_stat, 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->tail_redone = tail_status != 0;
   bool any_failed = false;
   for (size_t b = 0; b < B; b++) any_failed |= !success[b];
   HIPCHK(download_rho(s, 0, B, rho, rho_old_out, nfact, h->stream));
@@ -643,7 +648,7 @@ int newton_staged_ladder(cnl_handle* h, double* vals, const double* rhs, double*
     HIPCHK(hipStreamSynchronize(h->stream));
     if ((rc = ensure_pinned(h, B * 16))) return rc;
     char* pb = static_cast<char*>(h->pin);
-    if ((rc = host_ladder_run(h, params, rho_old, rho, rho_old_out, nfact, success, pb, reinterpret_cast<int32_t*>(pb + B * 12)))) return rc;
+    if ((rc = host_ladder_run(h, params, rho_old, rho, rho_old_out, nfact, success, pb, reinterpret_cast<int32_t*>(pb + B * 12), tail_status != 0))) return rc;
   }
   HIPCHK(download_solution(h, s, 0, B, vals, d, success, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -842,7 +847,7 @@ int cnl_newton_system(cnl_handle* h, double* vals, const double* rhs, double* d,
   }
   if (h->dense && !h->timing && P.opt.host_ladder != 0)
     return newton_dense_host_ladder(h, vals, rhs, d, rho_old, params, rho, rho_old_out, nfact, success);
-  const bool host_ladder = host_ladder_serves(h);
+  const bool host_ladder = host_ladder_serves(h, false);
   if (B * (size_t)P.N * sizeof(double) <= ((size_t)1 << 20))
     return newton_small_pinned(h, vals, rhs, d, rho_old, params, rho, rho_old_out, nfact, success, host_ladder);
   if (host_ladder) return newton_staged_ladder(h, vals, rhs, d, rho_old, params, rho, rho_old_out, nfact, success);

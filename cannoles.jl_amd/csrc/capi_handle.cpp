@@ -566,8 +566,12 @@ int alloc_factor_storage(cnl_handle* h) {
   if (!h->cfg.lds_work && (rc = dalloc_elems(h, &h->d_scratch, (size_t)h->full_batch * (size_t)h->dp.work_doubles))) return rc;
   return CNL_OK;
 }
-// the handle's stream, its two timing events and the row lists (rows f1 / f2 / f4, the trial point, the dimensions cnl_layout_len reads)
+// the handle's route (call_shape.h: decided here, once, for run() and everything that asks what kind of handle this is), its stream,
+// its two timing events and the row lists (rows f1 / f2 / f4, the trial point, the dimensions cnl_layout_len reads)
 int finish_handle(cnl_handle* h, const int64_t* rows1, const int64_t* cols1) {
+  using cnl::Route;
+  h->route = h->band ? Route::Band : h->dense ? Route::Dense : h->gdense ? Route::GeneralDense : !h->plan->C.active ? Route::Plain
+             : (h->use_v2 && h->plan->P.rec_direct) ? Route::Direct : Route::Condensed;
   if (hipStreamCreate(&h->stream) != hipSuccess) return fail(CNL_ERR_HIP, "hipStreamCreate failed");
   if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return fail(CNL_ERR_HIP, "hipEventCreate failed");
   return build_row_lists(h, h->plan, rows1, cols1);
@@ -869,8 +873,9 @@ int cnl_set_active_batch(cnl_handle* h, int64_t nb) {
   if (nb < 1 || nb > h->full_batch)
     return fail(CNL_ERR_ARG, "cnl_set_active_batch: nb = " + std::to_string(nb) + " is outside [1, " + std::to_string(h->full_batch) + "] (the created batch)");
   if (nb == h->batch) return CNL_OK;
-  if (!h->band) {
-    if (h->dense || h->gdense) return fail(CNL_ERR_STATE, "cnl_set_active_batch: this handle runs on the dense backend, which is sized by the created batch");
+  const bool dense_route = h->route == cnl::Route::Dense || h->route == cnl::Route::GeneralDense;
+  if (dense_route) return fail(CNL_ERR_STATE, "cnl_set_active_batch: this handle runs on the dense backend, which is sized by the created batch");
+  if (h->route != cnl::Route::Band) {
     if (h->tail || h->split_halves || h->split_staged > 0)
       return fail(CNL_ERR_STATE, "cnl_set_active_batch: this handle runs its batch split (tail handle, halves or concurrent parts)");
     if (h->staged || h->d_dep)
@@ -901,19 +906,20 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms) {
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   if (!h || !cfg) return fail(CNL_ERR_ARG, "null argument");
   std::memset(cfg, 0, 8 * sizeof(int64_t));
-  if (h->f32 && !h->f32_general) {   // Float32 handle on the band kernels
+  const bool on_band = h->route == cnl::Route::Band, dense_route = h->route == cnl::Route::Dense || h->route == cnl::Route::GeneralDense;
+  if (h->f32 && on_band) {   // Float32 handle on the band kernels
     cfg[5] = 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->layout << 25) | ((int64_t)1 << 27) | ((int64_t)h->band_npiece << 28);
     if (h->djt.rv_ntiles > 0) cfg[5] |= 128;
     return CNL_OK;
   }
   cfg[0] = h->cfg.tpp; cfg[1] = h->cfg.ppb; cfg[2] = (int64_t)h->cfg.lds_bytes; cfg[3] = h->cfg.lds_work;
   cfg[4] = (h->full_batch + h->cfg.ppb - 1) / h->cfg.ppb;
-  cfg[5] = (h->dense || h->gdense) ? 3 : (h->use_v2 ? (h->staged ? 4 : 2) : 1);
+  cfg[5] = dense_route ? 3 : (h->use_v2 ? (h->staged ? 4 : 2) : 1);
   if (h->f32) cfg[5] |= (int64_t)1 << 27;                // a Float32 handle on the general kernel (tuning float32_general): bit 6 clear
   if (h->cond_resident) cfg[5] |= (int64_t)1 << 35;      // ... whose condensation runs the resident condense kernel (tuning float32_condense = 1)
-  if (h->lean && !h->dense && !h->gdense) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
+  if (h->lean && !dense_route) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->tail) cfg[5] |= 32;                             // the remainder of the batch runs on a handle of its own (split_tail)
-  if (h->band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->band_resident << 24) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28) | ((int64_t)h->band_mover << 34);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts, layout, operand pieces per epoch, mover table (bit 34: bit 27 marks a Float32 handle)
+  if (on_band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->band_resident << 24) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28) | ((int64_t)h->band_mover << 34);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts, layout, operand pieces per epoch, mover table (bit 34: bit 27 marks a Float32 handle)
   if (h->djt.rv_ntiles > 0) cfg[5] |= 128;               // row f1 runs on column tiles (kernels.h: DevJt::rv_*)
   cfg[6] = h->wpb2;
   cfg[7] = (int64_t)h->lds2;

@@ -3,6 +3,8 @@
 // of the handle and its remainder handle (SubBatch, run_split).  Everything is enqueued on the caller's stream.
 #include "handle.h"
 
+static_assert(cnl::CALL_NEWTON == cnl::MODE_NEWTON && cnl::CALL_FACTOR == cnl::MODE_FACTOR && cnl::CALL_SOLVE == cnl::MODE_SOLVE, "call_shape.h: modes");
+
 namespace {
 
 // debugging aid (include/cannoles_hip.h): CNL_DBG_LDSFILL=<byte pattern> — kernels that leave the pattern in LDS, scratch and registers
@@ -29,6 +31,14 @@ int end_timed(cnl_handle* h, hipStream_t stream) {
   return read_timing(h);
 }
 
+// what every launch of a call begins with: the debug fill, and the fields of the arguments that come from the handle alone
+void begin_launch(const cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
+  if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
+  a.batch = (int)h->batch;
+  a.lean = h->lean ? 1 : 0;
+  a.back_rows = (h->lean && h->plan->P.back_rows) ? 1 : 0;
+}
+
 // the per-problem result arrays of a call, from problem b0 on
 cnl::LaunchArgs shifted(const cnl_handle* h, cnl::LaunchArgs a, int64_t b0) {
   a.rho_old = elem_offset(h, a.rho_old, b0);
@@ -50,11 +60,9 @@ int run_band(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs,
   if (a.skip_done || a.only_if_status || (a.mode == cnl::MODE_NEWTON && !d_rhs))
     return fail(CNL_ERR_STATE, "this call is not served by the band kernels, and a band handle has no other"
                                " (no factor panels, no condensed buffer; interleaved `vals` are the band kernels' layout)");
-  if (a.mode == cnl::MODE_SOLVE && !h->last_vals) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
-  if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
+  begin_launch(h, a, stream);
   a.vals = a.mode == cnl::MODE_SOLVE ? const_cast<void*>(h->last_vals) : d_vals;
   a.rhs = d_rhs; a.d = d_d;
-  a.batch = (int)h->batch;
   a.L = h->d_Lband;
   a.layout = h->layout;
   if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
@@ -64,7 +72,6 @@ int run_band(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs,
   if (e != hipSuccess)
     return fail(CNL_ERR_HIP, std::string("band kernel launch (") + (h->f32 ? "Float32, " : "") + std::to_string(h->band_nl) +
                                  " problems per workgroup): " + hipGetErrorString(e));
-  if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
   return end_timed(h, stream);
 }
 
@@ -78,12 +85,9 @@ int f32_general_serves(const cnl_handle* h, const cnl::LaunchArgs& a, const void
   return CNL_OK;
 }
 
+// one classic launch of the register-front or the general kernel (run() sends no band or dense handle here)
 int launch(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
-  if (int rc = f32_general_serves(h, a, a.rhs)) return rc;
-  if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
-  a.batch = (int)h->batch;
-  a.lean = h->lean ? 1 : 0;
-  a.back_rows = (h->lean && h->plan->P.back_rows) ? 1 : 0;
+  begin_launch(h, a, stream);
   a.L = h->d_L;
   a.scratch = h->d_scratch;
   hipError_t e;
@@ -104,18 +108,17 @@ int launch(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
 }
 
 // one staged pass over the tasks of a latency plan (first attempt of newton_system, try_to_factorize, or solve_ldl!)
-int launch_staged(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
-  if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
-  a.batch = (int)h->batch; a.L = h->d_L; a.scratch = h->d_gs;
+// ladder_ran: the pass enqueued fused ladder launches (their commit / redo launch must follow: staged_follow_up)
+int launch_staged(cnl_handle* h, cnl::LaunchArgs& a, bool first_attempt_only, bool& ladder_ran, hipStream_t stream) {
+  begin_launch(h, a, stream);
+  a.L = h->d_L; a.scratch = h->d_gs;
   a.tasks = h->d_tasks; a.gcnt = h->d_gcnt; a.skip_done = 0; a.dep = h->d_dep; a.df_waves = h->df_waves;
-  a.lean = h->lean ? 1 : 0;
-  a.back_rows = (h->lean && h->plan->P.back_rows) ? 1 : 0;
   a.status_total = h->d_status;
   a.status_call = h->d_stat;   // (nullptr in views of the handle: one launch per stage, nothing waits)
   a.lad = h->d_lad; a.lgcnt = h->d_lgcnt; a.ldep = h->d_ldep; a.lad_zero_ints = h->d_stat ? h->zero_ints : 0;
   a.lad_capacity = h->resident_waves;
-  a.lad_mode = (a.mode == cnl::MODE_NEWTON && h->d_lad && !h->first_attempt_only) ? h->lad_mode : 0;
-  h->ladder_ran = a.lad_mode != 0;
+  a.lad_mode = (a.mode == cnl::MODE_NEWTON && h->d_lad && !first_attempt_only) ? h->lad_mode : 0;
+  ladder_ran = a.lad_mode != 0;
   a.spin_limit = h->plan->opt.dataflow_spin_limit > 0 ? h->plan->opt.dataflow_spin_limit : (1 << 22);
   if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
   hipError_t e = cnl::launch_newton2_staged(h->dp2, h->wpb2, h->lds2, a, h->stage_ptr.data(), (int)h->stage_ptr.size() - 1, stream);
@@ -161,17 +164,11 @@ namespace {
 // on the caller's stream, the rest single-stream on a second stream of the handle, forked and joined with events (no host
 // synchronisation).  Both parts use the SAME plan — the chain order has the throughput order's fronts, and the classic launch
 // runs any plan's records from end to end (it already does behind every staged attempt).
-int run_split(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream) {
-  if (!h->aux_stream && !h->tail && !h->split_halves) {
-    HIPCHK(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-  }
+// (the parts are calls of run() with part_of_split set; the events of a timed call bracket all of them)
+int run_split_parts(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream, RunOpts o) {
   const int64_t nA = h->split_staged, nB = h->batch - nA, nnz = h->plan->nnz, N = h->plan->N;
-  const bool tm = h->timing;
-  if (tm) HIPCHK(hipEventRecord(h->ev0, stream));
-  h->timing = false;
-  h->in_split = true;
+  TimingOff untimed(h);
+  o.part_of_split = true;
   if (h->tail) {
     // 4096 problems fill every wavefront slot on the bidirectional chain (4.1 ms at cfg3's size); a remainder of r <= 1024 problems
     // takes 0.5 .. 1.7 ms on its own many-part plan, where two halves of the whole batch need 2 x 3 ms (4608 problems: 5.95 -> 5.0 ms)
@@ -181,7 +178,7 @@ int run_split(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs
     {
       SubBatch view(h, 0, nA, true);
       cnl::LaunchArgs b = a;
-      rc = run(h, b, d_vals, d_rhs, d_d, stream);
+      rc = run(h, b, d_vals, d_rhs, d_d, stream, o);
     }
     if (rc == CNL_OK) {
       cnl::LaunchArgs b = shifted(h, a, nA);
@@ -189,20 +186,14 @@ int run_split(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs
       const void* tr = elem_offset(h, d_rhs, nA * N);
       void* td = elem_offset(h, d_d, nA * N);
       if (on_tail) {
-        t->first_attempt_only = h->first_attempt_only;
-        rc = run(t, b, tv, tr, td, stream);
-        t->first_attempt_only = false;
+        rc = run(t, b, tv, tr, td, stream, RunOpts{o.first_attempt_only, false});   // (a whole call of the tail handle)
         if (rc == CNL_OK && a.mode != cnl::MODE_SOLVE) { t->last_vals = tv; t->factorized = true; h->tail_fresh = true; }
       } else {
         SubBatch view(h, nA, nB, true);
-        rc = run(h, b, tv, tr, td, stream);
+        rc = run(h, b, tv, tr, td, stream, o);
       }
     }
-    h->in_split = false;
-    h->timing = tm;
-    if (rc) return rc;
-    if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
-    return end_timed(h, stream);
+    return rc;
   }
   if (h->split_halves) {
     // Two halves, each on the bidirectional chain (two wavefronts per group of problems), one behind the other on the caller's
@@ -213,13 +204,9 @@ int run_split(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs
       const int64_t b0 = part ? nA : 0, nb = part ? nB : nA;
       SubBatch view(h, b0, nb, true);
       cnl::LaunchArgs b = shifted(h, a, b0);
-      rc = run(h, b, elem_offset(h, d_vals, b0 * nnz), elem_offset(h, d_rhs, b0 * N), elem_offset(h, d_d, b0 * N), stream);
+      rc = run(h, b, elem_offset(h, d_vals, b0 * nnz), elem_offset(h, d_rhs, b0 * N), elem_offset(h, d_d, b0 * N), stream, o);
     }
-    h->in_split = false;
-    h->timing = tm;
-    if (rc) return rc;
-    if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
-    return end_timed(h, stream);
+    return rc;
   }
   HIPCHK(hipEventRecord(h->ev_fork, stream));
   HIPCHK(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
@@ -227,56 +214,71 @@ int run_split(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs
   {
     SubBatch view(h, nA, nB, false);
     cnl::LaunchArgs b = shifted(h, a, nA);
-    rc = run(h, b, elem_offset(h, d_vals, nA * nnz), elem_offset(h, d_rhs, nA * N), elem_offset(h, d_d, nA * N), h->aux_stream);
+    rc = run(h, b, elem_offset(h, d_vals, nA * nnz), elem_offset(h, d_rhs, nA * N), elem_offset(h, d_d, nA * N), h->aux_stream, o);
   }
   if (rc == CNL_OK) {
     SubBatch view(h, 0, nA, true);
-    rc = run(h, a, d_vals, d_rhs, d_d, stream);
+    rc = run(h, a, d_vals, d_rhs, d_d, stream, o);
   }
-  h->in_split = false;
-  h->timing = tm;
   // join also when an enqueue failed: work already on the second stream must not overlap a later call's use of the handle's arrays
   const hipError_t je = hipEventRecord(h->ev_join, h->aux_stream);
   const hipError_t we = je == hipSuccess ? hipStreamWaitEvent(stream, h->ev_join, 0) : je;
   if (rc) { if (we != hipSuccess) (void)hipStreamSynchronize(h->aux_stream); return rc; }
   HIPCHK(we);
-  if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
+  return CNL_OK;
+}
+int run_split(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream, RunOpts o) {
+  if (!h->aux_stream && !h->tail && !h->split_halves) {
+    HIPCHK(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+  }
+  if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
+  if (int rc = run_split_parts(h, a, d_vals, d_rhs, d_d, stream, o)) return rc;
   return end_timed(h, stream);
 }
 
-// Behind a staged try_to_factorize / solve_ldl! that ran in dataflow fashion: the sequential execution of the same call, which
-// exits at once unless a dataflow wait of the attempt gave up (kernels2.hip, spin_until).  newton_system has its classic launch
-// anyway (the rho ladder of the problems that failed the first attempt).
-int launch_redo(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
-  if (!a.status_call || (!h->d_dep && !h->ladder_ran)) return CNL_OK;  // one launch per stage: nothing waits, nothing can time out
-  const bool tm = h->timing;
-  h->timing = false;
+// The classic launch behind launch_staged (the caller's events bracket it too).  newton_system, whose first attempt (rho as given) ran
+// stage by stage: the problems that failed it (rare) go through the whole rho ladder here, the others are skipped (skip_done).
+// Everything else is the REDO: the sequential execution of the same call, which exits at once unless a dataflow wait of the attempt
+// gave up (kernels2.hip, spin_until) — try_to_factorize, solve_ldl!, a newton_system whose failed problems have climbed the ladder
+// inside the fused launches (ladder_ran: the redo also commits rho_old and the rho slots), or one the host ladder follows
+// (first_attempt_only: the redo goes through the device ladder, and the host finds the per-call status word set).
+int staged_follow_up(cnl_handle* h, cnl::LaunchArgs& a, bool ladder_ran, bool first_attempt_only, hipStream_t stream) {
+  TimingOff untimed(h);
+  if (a.mode == cnl::MODE_NEWTON && !ladder_ran && !first_attempt_only) {
+    a.skip_done = 1;
+    return launch(h, a, stream);
+  }
+  if (!a.status_call || (!h->d_dep && !ladder_ran)) return CNL_OK;  // one launch per stage: nothing waits, nothing can time out
   a.only_if_status = 1;
   const int rc = launch(h, a, stream);
   a.only_if_status = 0;
-  h->timing = tm;
   return rc;
 }
 
 // The stand-alone condensation passes around a launch on the condensed system (csrc/condense.h).
-// condense: which slots of the handle's condensed buffer are formed from `vals` [and `rhs`] — the values are the tiled kernel's mask
-// (1 matrix, 2 rho, 4 right-hand-side slots), the plain kernel takes the same choice as a slot range
-enum CondensePart { MATRIX_ONLY = 3, RHS_ONLY = 4, WHOLE_SYSTEM = 7 };
+// condense: which slots of the handle's condensed buffer are formed from `vals` [and `rhs`] (call_shape.h: CondensePart; the plain
+// kernel takes the tiled kernel's mask as a slot range)
 // (T: the handle's element type, picked from h->f32 by the three functions without a T; each types its arguments once on entry)
 template <class T>
-hipError_t condense_t(cnl_handle* h, CondensePart part, const void* vals, const void* rhs, hipStream_t stream) {
+hipError_t condense_t(cnl_handle* h, cnl::CondensePart part, const void* vals, const void* rhs, hipStream_t stream) {
   const cnl::Cond& C = h->plan->C;
   const int B = (int)h->batch, s_mat = (int)(C.ncs + C.nvar), s_all = (int)C.cstride;
   const T* v = static_cast<const T*>(vals);
   const T* r = static_cast<const T*>(rhs);
   T* cbuf = static_cast<T*>(h->d_cbuf);
+  using cnl::MATRIX_ONLY; using cnl::RHS_ONLY;
   if constexpr (sizeof(T) == 4)
     if (h->cond_resident)
       return cnl::launch_condense_resident(h->dce, v, r, cbuf, part == RHS_ONLY ? s_mat : 0, part == MATRIX_ONLY ? s_mat : s_all, B, stream);
   return C.tiled_ok ? cnl::launch_condense_tiled(h->dc, v, r, cbuf, part, C.ch_region[3], B, stream)
                     : cnl::launch_condense(h->dc, v, r, cbuf, part == RHS_ONLY ? s_mat : 0, part == MATRIX_ONLY ? s_mat : s_all, B, stream);
 }
-int condense(cnl_handle* h, CondensePart part, const void* vals, const void* rhs, hipStream_t stream) {
+// (a handle without the condensed buffer — a band handle — has none of these passes)
+int no_cbuf() { return fail(CNL_ERR_STATE, "this handle has no condensed buffer: the condensation passes do not serve it"); }
+int condense(cnl_handle* h, cnl::CondensePart part, const void* vals, const void* rhs, hipStream_t stream) {
+  if (!h->d_cbuf) return no_cbuf();
   const hipError_t e = h->f32 ? condense_t<float>(h, part, vals, rhs, stream) : condense_t<double>(h, part, vals, rhs, stream);
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("condense: ") + hipGetErrorString(e));
   return CNL_OK;
@@ -295,6 +297,7 @@ hipError_t expand_t(cnl_handle* h, const void* vals, const void* rhs, const void
                             static_cast<const T*>(h->d_cbuf), static_cast<T*>(d), success, copy_rho_tail, (int)h->batch, stream);
 }
 int expand(cnl_handle* h, const void* vals, const void* rhs, const void* d2, void* d, const int* success, int copy_rho_tail, hipStream_t stream) {
+  if (!h->d_cbuf) return no_cbuf();
   const hipError_t e = h->f32 ? expand_t<float>(h, vals, rhs, d2, d, success, copy_rho_tail, stream)
                               : expand_t<double>(h, vals, rhs, d2, d, success, copy_rho_tail, stream);
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("expand: ") + hipGetErrorString(e));
@@ -303,127 +306,81 @@ int expand(cnl_handle* h, const void* vals, const void* rhs, const void* d2, voi
 
 }  // namespace
 
-// One call of the path on device-resident data: [condense ->] multifrontal kernel [-> expand].
-int run(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream) {
+namespace {
+
+// dense residual block: J'WJ + tiled dense LDL^T on the fp64 matrix cores (csrc/dense.hip); asynchronous, the rho ladder is decided
+// on the device
+int run_dense(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream) {
+  std::string err;
+  if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
+  if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
+  const int rc = cnl::dense_run(h->dense, h->plan->D, a.mode, f64(h, d_vals), f64(h, d_rhs), f64(h, d_d), f64(h, a.rho_old), f64(h, a.rho), a.nfact,
+                                a.success, a.npos, a.nzero, a.params, stream, err);
+  if (rc) return fail(rc == 5 ? CNL_ERR_STATE : CNL_ERR_HIP, "dense backend: " + err);
+  return end_timed(h, stream);
+}
+
+// The executor of the Plain, Direct, Condensed and GeneralDense routes: [condense -> inertia ->] launch [-> expand], as S says
+// (call_shape.h).  The launch is the multifrontal kernel — one classic launch, or stage by stage with its follow-up — or, on the
+// GeneralDense route, the dense LDL^T / solves of the condensed system as one matrix (csrc/dense.hip).  The events of a timed call
+// bracket the classic launch alone (launch()), the staged pass with its follow-up, or the whole dense route.
+int execute(cnl_handle* h, const cnl::CallShape& S, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream, RunOpts o) {
   const cnl::Cond& C = h->plan->C;
-  int rc = CNL_OK;
-  if (h->split_staged > 0 && !h->in_split && (h->staged || h->tail) && h->split_staged < h->batch) return run_split(h, a, d_vals, d_rhs, d_d, stream);
-  if (h->band) return run_band(h, a, d_vals, d_rhs, d_d, stream);
-  // (a Float32 general handle refuses what its kernel does not serve here, before a condensation pass is enqueued)
-  if (h->f32 && (rc = f32_general_serves(h, a, d_rhs))) return rc;
-  if (h->dense || h->gdense)
+  const bool gdense = S.launch == cnl::Launch::GeneralDense, factors = a.mode != cnl::MODE_SOLVE, solves = a.mode != cnl::MODE_FACTOR;
+  const void* src = S.needs_last_vals ? h->last_vals : d_vals;   // the values the call is about
+  int rc;
+  if (gdense) {
     if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
-  if (h->dense) {
-    // dense residual block: J'WJ + tiled dense LDL^T on the fp64 matrix cores (csrc/dense.hip); asynchronous, the rho ladder
-    // is decided on the device
-    std::string err;
     if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
-    rc = cnl::dense_run(h->dense, h->plan->D, a.mode, f64(h, d_vals), f64(h, d_rhs), f64(h, d_d), f64(h, a.rho_old), f64(h, a.rho), a.nfact,
-                        a.success, a.npos, a.nzero, a.params, stream, err);
-    if (rc) return fail(rc == 5 ? CNL_ERR_STATE : CNL_ERR_HIP, "dense backend: " + err);
-    return end_timed(h, stream);
   }
-  if (h->gdense) {
-    // condensed system as one dense matrix: condense pass -> dense LDL^T / solves (csrc/dense.hip) -> post-pass
+  if (S.condense && (rc = condense(h, S.condense, src, solves ? d_rhs : nullptr, stream))) return rc;
+  if (S.inertia && (rc = cond_inertia(h, d_vals, a.params[0], stream))) return rc;
+  if (gdense) {
     std::string err;
-    if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
-    if (a.mode == cnl::MODE_SOLVE) {
-      if (!h->last_vals) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
-      if ((rc = condense(h, RHS_ONLY, h->last_vals, d_rhs, stream))) return rc;
-    } else {
-      const bool nw = a.mode == cnl::MODE_NEWTON;
-      if ((rc = condense(h, nw ? WHOLE_SYSTEM : MATRIX_ONLY, d_vals, nw ? d_rhs : nullptr, stream))) return rc;
-      if ((rc = cond_inertia(h, d_vals, a.params[0], stream))) return rc;
-    }
     rc = cnl::dense_run_general(h->gdense, h->gops, a.mode, f64(h, h->d_cbuf), h->d_xpos, h->d_xzer, f64(h, h->d_d2),
                                 d_vals ? f64(h, d_vals) + (C.nnz - C.nvar) : nullptr, C.nnz, f64(h, a.rho_old), f64(h, a.rho), a.nfact, a.success,
                                 a.npos, a.nzero, a.params, stream, err);
     if (rc) return fail(CNL_ERR_HIP, "dense backend: " + err);
-    if (a.mode == cnl::MODE_FACTOR) h->last_vals = d_vals;
-    else {
-      const void* vsrc = a.mode == cnl::MODE_SOLVE ? h->last_vals : d_vals;
-      if ((rc = expand(h, vsrc, d_rhs, h->d_d2, d_d, a.mode == cnl::MODE_NEWTON ? a.success : nullptr, 0, stream))) return rc;
-    }
-    return end_timed(h, stream);
-  }
-  if (!C.active) {
-    a.vals = d_vals; a.rhs = d_rhs; a.d = d_d;
-    rc = launch(h, a, stream);
   } else {
-    void* crhs = elem_offset(h, h->d_cbuf, C.ncs + C.nvar);   // the right-hand-side slots of the condensed buffer
-    const bool direct = h->use_v2 && h->plan->P.rec_direct;  // the register-front kernel condenses on the fly
-    const bool count_d = direct && h->dp2.count_d;  // the kernel counts the condensed pivots itself
-    if (direct && a.mode == cnl::MODE_NEWTON) {
-      if (!count_d && (rc = cond_inertia(h, d_vals, a.params[0], stream))) return rc;
-      const bool d_outer = h->plan->P.d_outer;  // the kernel writes the kept components of d itself
-      a.vals = d_vals; a.rhs = d_rhs; a.d = d_outer ? d_d : h->d_d2;
-      a.extra_pos = count_d ? nullptr : h->d_xpos; a.extra_zer = count_d ? nullptr : h->d_xzer;
-      if (h->staged) {
-        // first attempt (rho as given) stage by stage: the tasks of the elimination tree run on different wavefronts; the
-        // problems that fail it (rare) go through the whole ladder in the classic launch behind it
-        if ((rc = launch_staged(h, a, stream))) return rc;
-        if (h->ladder_ran) {
-          // the problems that failed the attempt have climbed the rho ladder inside the fused launch(es) (kernels2.hip, phase 2);
-          // the sequential launch behind them commits rho_old and the rho slots — or, if a wait gave up, redoes the whole call
-          if ((rc = launch_redo(h, a, stream))) return rc;
-        } else if (h->first_attempt_only) {
-          // the host ladder follows; the sequential launch only if a dataflow wait of the attempt gave up (it then redoes the whole
-          // call on the device, ladder included: the host finds the per-call status word set and leaves the results alone)
-          if (h->d_dep && (rc = launch_redo(h, a, stream))) return rc;
-        } else {
-          a.skip_done = 1;
-          const bool tm = h->timing;
-          h->timing = false;
-          rc = launch(h, a, stream);
-          h->timing = tm;
-          if (rc) return rc;
-        }
-        if (h->timing) HIPCHK(hipEventRecord(h->ev1, stream));
-      } else if ((rc = launch(h, a, stream))) return rc;
-      // (the lean instantiation has recovered the residual components in its backward sweep: plan.h, B_ROWS_FLAG)
-      if (!(h->lean && h->plan->P.back_rows) && (rc = expand(h, d_vals, d_rhs, d_outer ? nullptr : h->d_d2, d_d, a.success, 0, stream))) return rc;
-    } else if (direct && a.mode == cnl::MODE_FACTOR) {
-      if (!count_d && (rc = cond_inertia(h, d_vals, a.params[0], stream))) return rc;
-      a.vals = d_vals; a.extra_pos = count_d ? nullptr : h->d_xpos; a.extra_zer = count_d ? nullptr : h->d_xzer;
-      if (h->staged) {  // try_to_factorize stage by stage (the elimination tree's tasks on different wavefronts)
-        if ((rc = launch_staged(h, a, stream))) return rc;
-        if ((rc = launch_redo(h, a, stream))) return rc;
-        if (h->timing) HIPCHK(hipEventRecord(h->ev1, stream));
-      } else if ((rc = launch(h, a, stream))) return rc;
-      h->last_vals = d_vals;
-    } else if (a.mode == cnl::MODE_NEWTON) {
-      if ((rc = condense(h, WHOLE_SYSTEM, d_vals, d_rhs, stream))) return rc;
-      if ((rc = cond_inertia(h, d_vals, a.params[0], stream))) return rc;
-      a.vals = h->d_cbuf; a.rhs = crhs; a.d = h->d_d2; a.extra_pos = h->d_xpos; a.extra_zer = h->d_xzer;
-      if ((rc = launch(h, a, stream))) return rc;
-      if ((rc = expand(h, d_vals, d_rhs, h->d_d2, d_d, a.success, 1, stream))) return rc;
-    } else if (a.mode == cnl::MODE_FACTOR) {
-      if ((rc = condense(h, MATRIX_ONLY, d_vals, nullptr, stream))) return rc;
-      if ((rc = cond_inertia(h, d_vals, a.params[0], stream))) return rc;
-      a.vals = h->d_cbuf; a.extra_pos = h->d_xpos; a.extra_zer = h->d_xzer;
-      if ((rc = launch(h, a, stream))) return rc;
-      h->last_vals = d_vals;
-    } else if (direct && h->v2_solve) {
-      // solve_ldl! on the register-front kernel: forward substitution with the stored factor, backward sweep, post-pass
-      if (!h->last_vals) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
-      a.vals = const_cast<void*>(h->last_vals); a.rhs = d_rhs; a.d = d_d;
-      if (h->staged) {  // solve_ldl! stage by stage: forward substitution of the tasks, then their backward sweeps
-        if ((rc = launch_staged(h, a, stream))) return rc;
-        if ((rc = launch_redo(h, a, stream))) return rc;
-        if (h->timing) HIPCHK(hipEventRecord(h->ev1, stream));
-      } else if ((rc = launch(h, a, stream))) return rc;
-      // (lean plans: the solve-only instantiation has recovered the residual components in its backward sweep)
-      if (!(h->lean && h->plan->P.back_rows) && (rc = expand(h, h->last_vals, d_rhs, nullptr, d_d, nullptr, 0, stream))) return rc;
-    } else {
-      if (!h->last_vals) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
-      if ((rc = condense(h, RHS_ONLY, h->last_vals, d_rhs, stream))) return rc;
-      a.rhs = crhs; a.d = h->d_d2;
-      if ((rc = launch(h, a, stream))) return rc;
-      if ((rc = expand(h, h->last_vals, d_rhs, h->d_d2, d_d, nullptr, 0, stream))) return rc;
-    }
+    // (from the condensed buffer: the matrix slots where the call factorises, the right-hand-side slots where it solves)
+    a.vals = !S.from_cbuf ? const_cast<void*>(src) : factors ? h->d_cbuf : nullptr;
+    a.rhs = !S.from_cbuf ? d_rhs : solves ? elem_offset(h, h->d_cbuf, C.ncs + C.nvar) : nullptr;
+    a.d = S.d_to_d2 ? h->d_d2 : d_d;
+    a.extra_pos = S.extra_counts ? h->d_xpos : nullptr; a.extra_zer = S.extra_counts ? h->d_xzer : nullptr;
+    if (S.launch == cnl::Launch::Staged) {
+      bool ladder_ran = false;
+      if ((rc = launch_staged(h, a, o.first_attempt_only, ladder_ran, stream))) return rc;
+      if ((rc = staged_follow_up(h, a, ladder_ran, o.first_attempt_only, stream))) return rc;
+      if (h->timing) HIPCHK(hipEventRecord(h->ev1, stream));
+    } else if ((rc = launch(h, a, stream))) return rc;
   }
-  if (rc) return rc;
-  return h->timing ? read_timing(h) : CNL_OK;
+  if (S.expand && (rc = expand(h, src, d_rhs, S.expand_d2 ? h->d_d2 : nullptr, d_d, S.expand_success ? a.success : nullptr, S.copy_rho_tail, stream))) return rc;
+  return gdense ? end_timed(h, stream) : h->timing ? read_timing(h) : CNL_OK;
+}
+
+cnl::RouteFacts route_facts(const cnl_handle* h) {
+  const cnl::Plan& P = h->plan->P;
+  return {h->route, h->dp2.count_d != 0, P.d_outer != 0, h->v2_solve, h->lean && P.back_rows, h->staged};
+}
+
+}  // namespace
+
+// One call of the path on device-resident data.  A split batch comes back here part by part; the rule of last_vals — the solve
+// uses the values of the last factorisation — is checked and kept here for every route (call_shape.h: needs / sets).
+int run(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream, RunOpts o) {
+  const cnl::CallShape S = cnl::call_shape(route_facts(h), a.mode);
+  int rc;
+  if (h->split_staged > 0 && !o.part_of_split && (h->staged || h->tail) && h->split_staged < h->batch) rc = run_split(h, a, d_vals, d_rhs, d_d, stream, o);
+  // (a Float32 general handle refuses what its kernel does not serve here, before a condensation pass is enqueued)
+  else if (h->route != cnl::Route::Band && (rc = f32_general_serves(h, a, d_rhs))) return rc;
+  else if (S.needs_last_vals && !h->last_vals) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
+  else switch (h->route) {
+    case cnl::Route::Band: rc = run_band(h, a, d_vals, d_rhs, d_d, stream); break;
+    case cnl::Route::Dense: rc = run_dense(h, a, d_vals, d_rhs, d_d, stream); break;
+    default: rc = execute(h, S, a, d_vals, d_rhs, d_d, stream, o);
+  }
+  if (rc == CNL_OK && S.sets_last_vals) h->last_vals = d_vals;
+  return rc;
 }
 
 extern "C" int cnl_launch_counts(int64_t counts[3]) {

@@ -20,6 +20,7 @@
 
 #include "../../include/cannoles_hip.h"
 #include "band.h"
+#include "call_shape.h"
 #include "condense.h"
 #include "dense.h"
 #include "kernels.h"
@@ -56,6 +57,7 @@ struct cnl_plan {
 struct cnl_handle {
   cnl_plan* plan = nullptr;
   int device = 0;
+  cnl::Route route = cnl::Route::Plain;   // which backend serves the calls (call_shape.h); set once, by finish_handle
   int64_t batch = 1;        // problems a call works on: the created batch, or fewer behind cnl_set_active_batch (the first `batch` problems)
   int64_t full_batch = 1;   // the batch the handle was created with: what every allocation, array address and cnl_layout_len are sized by
   int64_t factor_batch = 0; // problems the last factorisation covered (cnl_solve_dev must not be asked for more)
@@ -77,12 +79,10 @@ struct cnl_handle {
   long long zero_ints = 0;
   int resident_waves = 0;   // wavefronts of the register-front kernel the device holds at once
   int lad_mode = 0;         // in-kernel rho ladder of staged newton_system calls (kernels.h): 0 none, 1 behind the staged attempt, 2 fused
-  bool ladder_ran = false;  // the last launch_staged enqueued fused ladder launches (their commit / redo launch must follow)
   int ntasks = 0;
   int df_waves = 1024;
   std::vector<int32_t> stage_ptr;
   bool v2_solve = false;  // cnl_solve runs on the register-front kernel too (direct records, every front of the fast class)
-  bool first_attempt_only = false;  // newton_system on a staged handle: no sequential launch behind the staged attempt (the host ladder follows)
   int* d_act = nullptr;   // [batch] problems whose rho slots the host ladder rewrites
   bool lean = false;      // every front of the fast class with row-form (or no) products: the kernels' LEAN instantiation serves it
   cnl::DevPlan2 dp2{};
@@ -108,13 +108,10 @@ struct cnl_handle {
   hipStream_t stream = nullptr;
   int64_t split_staged = 0;   // > 0: problems [0, split_staged) run staged, the rest single-stream, concurrently (run_split)
   bool split_halves = false;  // ... or (round 4): the rest runs staged as well, BEHIND the first part on the same stream (two halves)
-  bool in_split = false;
   // (round 4) a batch a little above what fills the machine on the bidirectional chain (staged_max_batch < batch <= 5/4 of it):
   // problems [0, split_staged) run on this handle's chain plan, the REMAINDER on a handle of its own with the many-part latency
   // plan cnl_create picks for that small batch, one behind the other on the caller's stream (run_split)
   cnl_handle* tail = nullptr;
-  bool tail_redone = false;   // (per call) a dataflow wait of the remainder handle gave up: its redo launch has been through the whole device
-                              // ladder for those problems — the host ladder must leave them alone
   bool tail_fresh = false;    // the factors of the remainder live in the tail handle (false: in this handle's storage — chunked host calls)
   hipStream_t aux_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -273,7 +270,19 @@ const cnl::BandPlan& band_program(const cnl_plan* plan, bool f32);
 int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device);
 
 // ---- capi_run.cpp ----
-int run(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream);
+// what holds for ONE call of run() and is no state of the handle
+struct RunOpts {
+  bool first_attempt_only = false;  // newton_system on a staged handle: no sequential launch behind the staged attempt (the host ladder follows)
+  bool part_of_split = false;       // the call is one part of a split batch (run_split): it is not split again
+};
+int run(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream, RunOpts o = {});
+
+// no timing (cnl_set_timing) of the launches enqueued while this lives: they are part of a call that is timed as a whole, or not at all
+struct TimingOff {
+  cnl_handle* h; const bool was;
+  explicit TimingOff(cnl_handle* h_) : h(h_), was(h_->timing) { h->timing = false; }
+  ~TimingOff() { h->timing = was; }
+};
 
 // run() on problems [b0, b0 + nb) of the handle: the base pointer of every per-problem device array of the handle is moved to
 // problem b0 and the batch set to nb for the lifetime of the view (b0 a multiple of 4: a wavefront serves four problems).

@@ -899,23 +899,43 @@ def test_cfg2_dense_full_size_against_oracle(built):
     run_case(s, vals[None, :], rhs[None, :])
 
 
-@pytest.mark.parametrize("kind", ["dense", "sparse"])
+@pytest.mark.parametrize("kind", ["dense", "sparse", "band", "general_dense", "condensed"])
 def test_factorize_newton_solve_sequence(built, kind):
     """cnl_factorize(A), cnl_newton_system(B), cnl_solve(rhs): the solve uses the LAST factorisation, B's (with B's rho),
-    never a mixture of B's factor and A's values."""
+    never a mixture of B's factor and A's values.  On every backend that keeps the values of the last factorisation for the solve
+    in its own way: the dense backend's own factor, the register-front kernel, the band kernels (which factorise them again), the
+    condensed system as one dense matrix, and the general kernel between the stand-alone condensation passes."""
     hipldl, syn, O = _mods()
+    options = None
     if kind == "dense":
         s = syn.dense_structure(96, 200)
         gen = lambda k: syn.dense_values(s, 3000 + k)
-    else:
+    elif kind == "sparse":
         s = syn.band_structure(300, 4)
         gen = lambda k: syn.band_values(s, 3000 + k)
+    elif kind == "band":             # (the pattern of test_band_newton_system_then_solve_ldl)
+        s = syn.band_structure(800, 8)
+        gen = lambda k: syn.band_values(s, 3000 + k)
+        options = _band_opts(hipldl)
+    elif kind == "general_dense":    # (the smaller pattern of test_irregular_sparsity_dense_treatment)
+        s = syn.random_structure(200, 260, 0, 0.04, seed=2)
+        gen = lambda k: syn.random_values(s, 40 + k)
+    else:                            # (the pattern test_random_structures_mid_size_batches sends to the general kernel)
+        s = syn.random_structure(100, 130, 6, 0.03, 1)
+        gen = lambda k: syn.random_values(s, 40 + k)
+        options = hipldl.Options(general_dense=0)
     rows, cols = s.kkt_pattern()
     (vA, rA), (vB, rB) = gen(0), gen(1)
     off = s.offsets()
     vB[off[0]:off[1]] *= 1.5
     p = hipldl.default_params()
-    L = hipldl.HIPLDLStruct(s.N, rows, cols, vA, s.nvar, s.nequ, s.ncon)
+    L = hipldl.HIPLDLStruct(s.N, rows, cols, vA, s.nvar, s.nequ, s.ncon, options=options)
+    if kind == "band":
+        assert L.config["band"]
+    elif kind == "general_dense":    # fronts the register-front kernel does not take: the dense treatment of the condensed system
+        assert L.config["kernel"] == "dense" and L.info["fmax"] > 64 and L.info["ncond"] > 0
+    elif kind == "condensed":        # the general kernel on a condensed plan: no direct records
+        assert L.config["kernel"] == "v1" and L.info["ncond"] > 0
     assert hipldl.try_to_factorize(L, vA, s.nvar, s.nequ, s.ncon, p[0])
     vB2 = vB.copy()
     d, ok, rho, ro, nf = hipldl.newton_system_(np.zeros(s.N), s.nvar, s.nequ, s.ncon, rB, vB2, L, 0.0, p)
