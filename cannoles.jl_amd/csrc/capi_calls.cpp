@@ -4,6 +4,8 @@
 // element type and forwards to a template on it; the routes only Float64 handles can take are Float64 functions.
 #include "handle.h"
 
+#include <climits>
+
 namespace {
 
 const char* const kHostLayout = "host-pointer calls take the reference's problem-major arrays: this handle was created with batch_layout = "
@@ -140,6 +142,7 @@ int cgls_impl(cnl_handle* h, const cnl::JacSrcT<T>& S, const T* d_r, T* d_lambda
     h->cgls_ws = ws;
   }
   if (itmax <= 0) itmax = (int64_t)h->djt.nvar + h->djt.ncon;  // Krylov.jl's default: m + n
+  if (itmax > INT_MAX) itmax = INT_MAX;  // the kernel counts in int: "no limit" (typemax(Int64)) must not wrap to a negative count
   hipError_t e = cnl::launch_cgls(h->djt, S, d_r, d_lambda, d_Jxtr, ws, d_iters, atol, rtol, (int)itmax, ones_if_zero,
                                   (int)h->batch, (hipStream_t)stream);
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("cgls: ") + hipGetErrorString(e));

@@ -252,7 +252,8 @@ int cnl_deinterleave_dev(cnl_handle* h, int which, const double* d_src, double* 
  * reference obtains with `mul!(Jxtr, Jx', r); krylov_solve!(cgls_workspace, Jcx', Jxtr)` at src/CaNNOLeS.jl:507-518 and
  * :880-882: CGLS started at 0, stopped when ||Jc res|| <= atol + rtol ||Jc b|| or after itmax steps (itmax <= 0: nvar + ncon,
  * Krylov.jl's default; its default tolerances are sqrt(eps)).  ones_if_zero != 0 applies `if norm(lambda) == 0: lambda .= 1`
- * (:515-517).  d_Jxtr (optional) receives Jx' r, d_iters (optional) the iteration counts.  ncon <= 1024.                */
+ * (:515-517).  d_Jxtr (optional) receives Jx' r, d_iters (optional) the iteration counts.  ncon <= 1024.
+ * itmax: any int64_t; <= 0 selects the default nvar + ncon, a value above INT_MAX (typemax(Int64) for "no limit") counts as INT_MAX. */
 int cnl_cgls_multipliers_dev(cnl_handle* h, const double* d_vals, const double* d_r, double* d_lambda, double* d_Jxtr, double atol,
                              double rtol, int64_t itmax, int ones_if_zero, int32_t* d_iters, void* stream);
 

@@ -26,9 +26,9 @@ def column_ranks(rows, cols, nvar, nequ, ncon):
     return out
 
 
-def column_sums(ranks, vals, x, nvar):
+def column_sums(ranks, vals, x, nvar, dtype=F):
     """y[:, j] = sum over the entries of column j, in COO order, of vals[:, slot] * x[:, index] (multiply, then add)"""
-    y = np.zeros((vals.shape[0], nvar), F)
+    y = np.zeros((vals.shape[0], nvar), dtype)
     for c, sl, ix in ranks:
         y[:, c] = y[:, c] + vals[:, sl] * x[:, ix]
     return y
@@ -92,23 +92,25 @@ def trial_point(nvar, nequ, ncon, x, r, lam, d, max_dlambda=1e4):
     return xt, rt, lam + dl, dl
 
 
-def cgls_multipliers(rows, cols, vals, nvar, nequ, ncon, r, atol=None, rtol=None, itmax=0, ones_if_zero=True):
-    """row f4 for ONE problem with T = Float32 (oracle.cgls_multipliers' recurrence).  Returns (lambda, Jxtr, iterations, margin):
-    margin is the smallest relative distance | ||s|| - tol | / tol over the stopping tests taken."""
-    vals = np.asarray(vals, F).reshape(1, -1)
+def cgls_multipliers(rows, cols, vals, nvar, nequ, ncon, r, atol=None, rtol=None, itmax=0, ones_if_zero=True, dtype=F, trace=None):
+    """row f4 for ONE problem with element type `dtype` (oracle.cgls_multipliers' recurrence; Float32 unless told otherwise, and with
+    dtype = float64 the oracle's own results bit for bit).  Returns (lambda, Jxtr, iterations, margin): margin is the smallest relative
+    distance | ||s|| - tol | / tol over the stopping tests taken; `trace` (a list) receives ||s|| / tol of every one of them."""
+    T = np.dtype(dtype).type
+    vals = np.asarray(vals, T).reshape(1, -1)
     rF, rC = column_ranks(rows, cols, nvar, nequ, ncon)
-    Jxtr = column_sums(rF, vals, np.asarray(r, F).reshape(1, -1), nvar)[0]
-    A = np.zeros((nvar, ncon), F)   # A = Jc'
+    Jxtr = column_sums(rF, vals, np.asarray(r, T).reshape(1, -1), nvar, T)[0]
+    A = np.zeros((nvar, ncon), T)   # A = Jc'
     for c, sl, ix in rC:
         A[c, ix] = vals[0, sl]
-    eps = np.finfo(F).eps
-    atol = F(np.sqrt(eps) if atol is None else atol)
-    rtol = F(np.sqrt(eps) if rtol is None else rtol)
-    x = np.zeros(ncon, F)
+    eps = np.finfo(T).eps
+    atol = T(np.sqrt(eps) if atol is None else atol)
+    rtol = T(np.sqrt(eps) if rtol is None else rtol)
+    x = np.zeros(ncon, T)
     res = Jxtr.copy()
     s = A.T @ res
     p = s.copy()
-    gamma = F(s @ s)
+    gamma = T(s @ s)
     tol = atol + rtol * np.sqrt(gamma)
     itmax = nvar + ncon if itmax <= 0 else itmax
     it = 0
@@ -116,20 +118,22 @@ def cgls_multipliers(rows, cols, vals, nvar, nequ, ncon, r, atol=None, rtol=None
     while it < itmax:
         ng = np.sqrt(gamma)
         margin = min(margin, abs(float(ng) - float(tol)) / float(tol))
+        if trace is not None:
+            trace.append(float(ng) / float(tol))
         if not ng > tol:
             break
         q = A @ p
-        delta = F(q @ q)
+        delta = T(q @ q)
         if delta == 0:
             break
         alpha = gamma / delta
         x = x + alpha * p
         res = res - alpha * q
         s = A.T @ res
-        gnext = F(s @ s)
+        gnext = T(s @ s)
         p = s + (gnext / gamma) * p
         gamma = gnext
         it += 1
-    if ones_if_zero and F(x @ x) == 0:
-        x = np.ones(ncon, F)
+    if ones_if_zero and T(x @ x) == 0:
+        x = np.ones(ncon, T)
     return x, Jxtr, it, margin
