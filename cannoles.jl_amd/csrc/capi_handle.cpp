@@ -81,15 +81,16 @@ int choose_config(cnl_handle* h) {
 
 // The register-front kernel for a handle of either element type.  A Float32 general handle (tuning float32_register_front) is
 // asked with its 4-byte elements: every size "in doubles" of DevPlan2 then counts floats, the wavefront's LDS block and the global
-// scratch are sized in floats, and the 32-bit byte offsets of the kernel reach twice as many elements.  Its plan has no direct
-// records, tasks or dense route, so the staged state, v2_solve and lean stay off.
+// scratch are sized in floats, and the 32-bit byte offsets of the kernel reach twice as many elements.  Its plan has no tasks and
+// no dense route, so the staged state and lean stay off; direct records only with tuning float32_direct_records, and then
+// v2_solve by the Float64 rule.
 int setup_v2(cnl_handle* h) {
   const cnl::Plan& P = h->plan->P;
   h->use_v2 = false;
   const cnl::Tuning& o = h->plan->opt;
   const size_t esz = h->esz();
   if (!P.v2_ok || !o.register_front) return CNL_OK;
-  if (h->f32 && (P.rec_direct || !P.tasks.empty())) return CNL_OK;   // (not what cnl_create_f32_ex builds: the float kernel has no such instance)
+  if (h->f32 && !P.tasks.empty()) return CNL_OK;   // (not what cnl_create_f32_ex builds: the float kernel has no staged instance)
   if (!h->f32 && !h->plan->gpos.empty() && (o.general_dense == 2 || (h->plan->prefer_dense && h->batch <= 16))) return CNL_OK;  // the dense route (capi_plan.cpp, plan_create_impl); 2: wherever it is possible
   cnl::DevPlan2& d = h->dp2;
   // streams are over-read by the prefetcher: pad with zeros
@@ -204,7 +205,7 @@ int setup_v2(cnl_handle* h) {
       if (launches == 1 || (launches <= 4 && h->ntasks >= 16)) h->lad_mode = o.device_ladder_fused ? 2 : 1;
     }
   }
-  h->v2_solve = !h->f32 && P.rec_direct && P.d_outer && P.ncls[1] == 0 && P.ncls[2] == 0 && !o.v1_solve;
+  h->v2_solve = P.rec_direct && P.d_outer && P.ncls[1] == 0 && P.ncls[2] == 0 && !o.v1_solve;
   h->lean = !h->f32 && o.lean_kernel && P.rec_direct && P.d_outer && d.count_d && P.ncls[1] == 0 && P.ncls[2] == 0 && P.listprod_fronts == 0;
   return CNL_OK;
 }
@@ -786,14 +787,28 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
   cnl::Tuning g = o;
   g.condense = o.float32_condense ? 1 : 0; g.register_front = 0; g.dense_backend = 0; g.general_dense = 0; g.staged = 0; g.band_kernel = 0;
   if (o.float32_register_front) {
-    // ... or, tuning float32_register_front, with the register-front records of the condensed system, never direct: the call is
-    // the float condensation passes around ONE launch of the register-front kernel in float (solve_ldl!: of the general kernel,
-    // which reads the same panels).  Implies float32_condense.
+    // ... or, tuning float32_register_front, with the register-front records of the condensed system: the call is the float
+    // condensation passes around ONE launch of the register-front kernel in float (solve_ldl!: of the general kernel, which
+    // reads the same panels).  Implies float32_condense.
     if (!g.float32_condense) g.float32_condense = 1;
     g.condense = 1; g.register_front = 1; g.direct_records = 0;
+    // ... or, tuning float32_direct_records on top, with DIRECT records: the kernel condenses on the fly from the caller's vals and
+    // the call is that one launch and the post-pass.  No lean or solve-only float instance exists, so the plan is not shaped for
+    // one (no row form forced on every front, no backward rows).
+    if (o.float32_direct_records) { g.direct_records = 1; g.lean_kernel = 0; g.rows_in_backward = 0; }
   }
   if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, g)) return rc;
-  return create_f32_general_from_plan(hout, plan, rows1, cols1, batch, device);
+  const bool direct_plan = plan->P.rec_direct;
+  if (int rc = create_f32_general_from_plan(hout, plan, rows1, cols1, batch, device)) return rc;
+  if (direct_plan && (*hout)->route != cnl::Route::Direct) {
+    // setup_v2 declined the direct records (their LDS block is the larger one): the handle is the one without the key
+    cnl_destroy(*hout);
+    *hout = nullptr;
+    g.direct_records = 0;
+    if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, g)) return rc;
+    return create_f32_general_from_plan(hout, plan, rows1, cols1, batch, device);
+  }
+  return CNL_OK;
 }
 
 int cnl_destroy(cnl_handle* h) {
@@ -917,6 +932,8 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   cfg[5] = dense_route ? 3 : (h->use_v2 ? (h->staged ? 4 : 2) : 1);
   if (h->f32) cfg[5] |= (int64_t)1 << 27;                // a Float32 handle on the general kernel (tuning float32_general): bit 6 clear
   if (h->cond_resident) cfg[5] |= (int64_t)1 << 35;      // ... whose condensation runs the resident condense kernel (tuning float32_condense = 1)
+  if (h->route == cnl::Route::Direct) cfg[5] |= (int64_t)1 << 36;                 // the Direct route (call_shape.h), either element type
+  if (h->route == cnl::Route::Direct && h->v2_solve) cfg[5] |= (int64_t)1 << 37;  // ... on which solve_ldl! runs on the register-front kernel too
   if (h->lean && !dense_route) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->tail) cfg[5] |= 32;                             // the remainder of the batch runs on a handle of its own (split_tail)
   if (on_band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->band_resident << 24) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28) | ((int64_t)h->band_mover << 34);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts, layout, operand pieces per epoch, mover table (bit 34: bit 27 marks a Float32 handle)

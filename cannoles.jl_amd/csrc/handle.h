@@ -155,6 +155,9 @@ struct cnl_handle {
   // With tuning float32_register_front = 1 that plan also has register-front records (never direct) and setup_v2 may set use_v2:
   // dp2, wpb2 / lds2 and a FLOAT global scratch behind d_gs (every "doubles" of dp2 counts floats); newton_system / factorize then
   // launch the register-front kernel's float instantiation, the solve stays on the general kernel (v2_solve, lean, staged: false).
+  // With tuning float32_direct_records = 1 on top those records are direct (where the analysis can write them and setup_v2 takes
+  // them): route Direct, v2_solve by the Float64 rule (lean, staged: still false); d_cbuf / d_d2 and the condensation lists stay,
+  // for the solve on plans with class-32 / class-64 fronts.
   bool f32_general = false;
   size_t esz() const { return f32 ? sizeof(float) : sizeof(double); }   // bytes per element of every element array of the handle
 };

@@ -208,8 +208,9 @@ hipError_t launch_newton_f32(const DevPlan& P, const KernelConfig& cfg, const La
 bool newton_f32_has(int tpp, int ppb, bool lds_work);
 hipError_t launch_newton2(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream);
 // the register-front kernel on Float32 data (a Float32 general handle with tuning float32_register_front): every size of P named
-// "doubles" counts floats, lds_bytes is computed with 4-byte elements (the record area stays in 32-bit words).  MODE_NEWTON and
-// MODE_FACTOR on non-direct records only: anything else is hipErrorInvalidConfiguration.
+// "doubles" counts floats, lds_bytes is computed with 4-byte elements (the record area stays in 32-bit words).  Direct records with
+// tuning float32_direct_records; MODE_SOLVE (direct records, every front of the fast class) runs an instance of its own.  lean,
+// only_if_status and skip_done are hipErrorInvalidConfiguration.
 hipError_t launch_newton2_f32(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream);
 // one attempt at the rho given in vals, stage by stage (stage_ptr: host array of nstages + 1 task offsets)
 hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, LaunchArgs a, const int32_t* stage_ptr, int nstages, hipStream_t stream);

@@ -25,8 +25,9 @@
 //    offsets were fixed on the host; the few large ones (and the staging of
 //    fronts of order > 32) use a per-problem global scratch instead.
 //  * L rows are stored to HBM straight from registers at their pivot step.
-//  * one body for both element types: double, and float for Float32 general handles (tuning float32_register_front; the plain
-//    instantiation in both LATE settings only — launch_newton2_f32 below).
+//  * one body for both element types: double, and float for Float32 general handles (tuning float32_register_front, on direct
+//    records with float32_direct_records; the plain instantiation in both LATE settings and one that holds the solve alone,
+//    nothing else — launch_newton2_f32 below, DESIGN sections 9.3 and 9.4).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -734,6 +735,8 @@ constexpr int WAVES_PER_SIMD = 2;
 // lean instantiation is 10 % faster on the headline (same box: 965 k -> 1 058 k systems/s).
 // SOLVE: the lean instantiation of solve_ldl! (MODE_SOLVE only): forward substitution + backward sweep with the residual components
 // recovered by the backward records — nothing of the factorisation is compiled in, no post-pass behind the launch.
+// SOLVE && !LEAN (float only): solve_ldl! of a Float32 handle on direct records — the substitution with raw-value staging and
+// product lists, the plain backward sweep, the post-pass behind the launch; nothing of the factorisation either.
 // FUSED (round 4): the staged instantiation that runs the in-kernel rho ladder (LaunchArgs.phase == 2) — a separate instantiation,
 // because the loop over the rungs makes the forward sweep's state loop-carried (the plain staged kernel leaves after one sweep:
 // 162 VGPRs, three wavefronts per SIMD; with the rung loop 213).  FUSED && !STAGED: the sequential launch BEHIND the fused ones
@@ -897,10 +900,11 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
   // goes into column 0 of the stored panel, where the backward sweep below expects it.  The host sends a plan here only
   // when every front is of the fast class (order <= 16, LDS staging).
   constexpr bool CNL_LEAN = LEAN;
-  static_assert(!SOLVE || LEAN, "the solve-only instantiation is a lean one");
+  static_assert(!SOLVE || LEAN || sizeof(T) == 4, "the solve-only instantiation is a lean one, or the float one");
   static_assert(!FUSED || !SOLVE, "the fused ladder is an execution of newton_system");
-  // (no float instance runs it: solve_ldl! of a Float32 handle is the general kernel's two sweeps on the same panels)
-  if (sizeof(T) == 8 && (SOLVE || (!CNL_LEAN && A.mode == MODE_SOLVE)) && (!STAGED || A.phase == 0)) {
+  // (float: compiled into an instance of its own, SOLVE without LEAN — the substitution with every cold path of the direct records,
+  //  then the plain backward sweep; in the two plain float instances it cost spilled registers on the hot path: DESIGN section 9.4)
+  if ((SOLVE || (sizeof(T) == 8 && !CNL_LEAN && A.mode == MODE_SOLVE)) && (!STAGED || A.phase == 0)) {
     const int4* rstream = reinterpret_cast<const int4*>(P.rec);
     int4 R0, R1, R2;
     T pvr[PVR], prr[2], prh = 0.0;
@@ -1669,15 +1673,17 @@ hipError_t launch_newton2(const DevPlan2& P, int wpb, size_t lds_bytes, const La
   return hipGetLastError();
 }
 
-// The same kernel on Float32 data (kernels.h): the plain instantiation in both LATE settings, nothing else — no staged, fused, lean
-// or solve-only instance exists for float, and its records are never direct.  `late` by the Float64 rule.
+// The same kernel on Float32 data (kernels.h): the plain instantiation in both LATE settings and, for MODE_SOLVE, the instance that
+// holds nothing but the solve (SOLVE without LEAN) — no staged, fused or lean instance exists for float.  Its records are direct
+// with tuning float32_direct_records, and only then is it sent a MODE_SOLVE (the handle's v2_solve).  `late` by the Float64 rule.
 hipError_t launch_newton2_f32(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream) {
   if (wpb < 1 || wpb > 4) return hipErrorInvalidConfiguration;
-  if (a.mode == MODE_SOLVE || a.lean || a.only_if_status || a.skip_done) return hipErrorInvalidConfiguration;
+  if (a.lean || a.only_if_status || a.skip_done) return hipErrorInvalidConfiguration;
   const int waves = (a.batch + 3) / 4;
   const int grid = (waves + wpb - 1) / wpb;
   const bool late = waves >= 1024;
-  auto kern = late ? newton2_kernel_t<float, false, true, false> : newton2_kernel_t<float, false, false, false>;
+  auto kern = a.mode == MODE_SOLVE ? newton2_kernel_t<float, false, false, false, true>
+            : late ? newton2_kernel_t<float, false, true, false> : newton2_kernel_t<float, false, false, false>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)lds_bytes));
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wpb), lds_bytes, stream, P, a);

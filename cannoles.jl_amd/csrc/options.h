@@ -62,7 +62,8 @@ namespace cnl {
   X(band_rhs_interleaved, 0) /* measurement: the band kernels also take `rhs` interleaved (batch_layout = 1 handles)        */ \
   X(float32_general, 0)      /* cnl_create_f32: a pattern (or option set) the band kernels do not serve runs on the general kernel in float */ \
   X(float32_condense, 0)     /* ... on the condensed system (the -I block eliminated by the condensation passes in float); only with float32_general */ \
-  X(float32_register_front, 0) /* ... with the register-front kernel in float between the condensation passes (implies float32_condense; fronts of order <= 64, else the float32_condense handle); only with float32_general */
+  X(float32_register_front, 0) /* ... with the register-front kernel in float between the condensation passes (implies float32_condense; fronts of order <= 64, else the float32_condense handle); only with float32_general */ \
+  X(float32_direct_records, 0) /* ... on direct records: the float register-front kernel condenses on the fly from the caller's vals, and solve_ldl! stays on it where every front is of the fast class; only with float32_general and float32_register_front */
 
 struct Tuning {
 #define X(name, dflt) int32_t name = dflt;

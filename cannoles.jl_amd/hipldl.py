@@ -405,7 +405,11 @@ class HIPLDLStruct:
     (config["cond_resident"]: the resident condense kernel serves it).  Options(float32_general=1, float32_register_front=1) implies
     float32_condense and runs newton_system! / try_to_factorize on the register-front kernel in float between those passes
     (config["kernel"] == "v2", config["wpb"] / config["lds2_bytes"] its wavefronts per workgroup and LDS bytes; solve_ldl! runs on the
-    general kernel, on the same panels); where a front exceeds order 64 the handle is the float32_condense handle ("v1").  A condensed
+    general kernel, on the same panels); where a front exceeds order 64 the handle is the float32_condense handle ("v1").  Adding
+    float32_direct_records=1 puts that handle on the Direct route of the Float64 default handle (config["direct"]): the float
+    register-front kernel condenses on the fly, a call is that launch and the post-pass, and solve_ldl! stays on the same kernel where
+    every front is of the fast class (config["v2_solve"]); patterns whose direct records the analysis refuses keep the handle without
+    the key.  A condensed or direct
     handle of either kind reads the Jacobian values of `vals` again in solve_ldl!: the array given to try_to_factorize must stay alive
     and unmodified until the last solve on that factor."""
 
@@ -442,7 +446,8 @@ class HIPLDLStruct:
                        "band_nl": (int(cfg[5]) >> 8) & 255, "band_parts": (int(cfg[5]) >> 16) & 255, "band_resident": bool((int(cfg[5]) >> 24) & 1),
                        "band_mover_table": bool((int(cfg[5]) >> 34) & 1), "cond_resident": bool((int(cfg[5]) >> 35) & 1),
                        "batch_layout": (int(cfg[5]) >> 25) & 1, "rhs_interleaved": bool((int(cfg[5]) >> 26) & 1),
-                       "float32": bool((int(cfg[5]) >> 27) & 1), "band_pieces": (int(cfg[5]) >> 28) & 63}
+                       "float32": bool((int(cfg[5]) >> 27) & 1), "band_pieces": (int(cfg[5]) >> 28) & 63,
+                       "direct": bool((int(cfg[5]) >> 36) & 1), "v2_solve": bool((int(cfg[5]) >> 37) & 1)}
         if self.config["float32"] and self.config["band"]:   # (a Float32 handle off the band kernels — tuning float32_general — is "v1")
             self.config["kernel"] = "band"
 

@@ -59,7 +59,8 @@ typedef struct cnl_handle cnl_handle; /* plan + device state for one batch      
 const char* cnl_last_error(void);
 /* library / ABI version: major*10000 + minor*100 + patch (0.3.0: cnl_set_active_batch, cnl_outer_compact_dev;
  * 0.3.1: tuning "float32_general", no new symbol; 0.4.0: cnl_outer_ctl, the cnl_outer_*_ex_dev entry points, cnl_outer_hess_mask_dev;
- * 0.4.1: tuning "float32_register_front", no new symbol) */
+ * 0.4.1: tuning "float32_register_front", no new symbol; 0.4.2: tuning "float32_direct_records", cnl_get_config bits 36 / 37, no new
+ * symbol) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -434,14 +435,17 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  *   bits 25-26 = cnl_options.batch_layout / rhs interleaved, bits 28-33 = operand pieces per epoch of the band program: 15, or 20
  *   for the wide form, bit 34 = the resident program's mover follows the host-built mover table (csrc/band.h; tuning
  *   "band_mover_table=0" keeps the resident instance that decodes piece descriptors — bit-equal outputs either way)),
- * + 128 when cnl_residual_vectors_dev runs on column tiles. */
+ * + 128 when cnl_residual_vectors_dev runs on column tiles,
+ * bit 36 = the handle runs on the Direct route: the register-front kernel condenses on the fly from the caller's vals (no
+ *   stand-alone condensation pass in front of the launch), either element type,
+ * bit 37 = ... and cnl_solve* runs on the register-front kernel too (every front of the fast class). */
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
 /* ([5] + (1 << 27) on a Float32 handle.  On the band kernels: bits 7-26 as above, cfg[0..4], [6], [7] are 0.  On the general kernel
  *  (tuning "float32_general=1"): cfg[0..4] describe that kernel's float instance as they do for a Float64 handle — [2] counts 4-byte
  *  elements — and [5] = 1 + (1 << 27) with bit 6 clear (+ 128 as above; + (1 << 35) where tuning "float32_condense=1" has the
  *  resident condense kernel form the condensed system); [6], [7] are 0.  With tuning "float32_register_front=1" where the
  *  register-front kernel's float instance serves the handle: [5] = 2 + (1 << 27) (+ (1 << 35) as above), [6], [7] = its wavefronts
- *  per workgroup and LDS bytes per workgroup.) */
+ *  per workgroup and LDS bytes per workgroup; + bits 36 / 37 as above with tuning "float32_direct_records=1".) */
 /* Launches of the Newton-system kernels since the library was loaded, per kernel family: counts[0] band kernels (csrc/band.hip),
  * [1] register-front kernel (csrc/kernels2.hip, staged launches not included), [2] general kernel (csrc/kernels.hip).  Lets a test
  * pin WHICH kernel served a call sequence (e.g. that solve_ldl! behind a band factorisation launches no second kernel family). */
@@ -491,6 +495,21 @@ int cnl_launch_counts(int64_t counts[3]);
  * exceeds order 64, or the kernel's LDS block or 32-bit offsets do not fit, the handle is exactly the "float32_condense=1"
  * handle.  cnl_set_active_batch serves it; batch_layout = CNL_LAYOUT_INTERLEAVED stays CNL_ERR_ARG.  The CONTRACT above holds
  * unchanged: `vals` / d_vals of the factorisation stay alive and unmodified until the last solve on that factor.
+ *   tuning "float32_direct_records=1" (default 0; takes effect only with "float32_general=1" AND "float32_register_front=1" — every
+ * other handle ignores it): the same forced plan with DIRECT records, i.e. the Direct route of the Float64 default handle in float
+ * (cnl_get_config bit 36).  The register-front kernel's float instance forms the condensation products itself from the caller's
+ * vals / rhs and writes the kept components of d itself: cnl_newton_system_f32* is ONE launch of family 1 and the post-pass,
+ * cnl_factorize_f32* that launch alone.  Where every front is of the fast class (order <= 16; bit 37) cnl_solve_f32* is one launch
+ * of family 1 and the post-pass as well; with fronts of class 32 / 64 it stays the condensation of the right-hand side, one
+ * launch of family 2 and the post-pass.  The plan is never shaped for a lean or solve-only instance (none exists for float).
+ * Direct and condensed handles sum the condensation products in different orders: decisions agree, d agrees within the Float32
+ * tolerances, not bit for bit.  Where the analysis cannot write direct records (a fast front with more than 128 raw values, a
+ * front with more than 1 023 — patterns with a dense Jacobian block), or the larger LDS block of the direct records does not fit,
+ * the handle is exactly the "float32_register_front=1" handle (bit 36 clear), and where even that does not apply the
+ * "float32_condense=1" handle.  cnl_set_active_batch serves it; batch_layout = CNL_LAYOUT_INTERLEAVED stays CNL_ERR_ARG.
+ *   CONTRACT (the Direct handles' contract, restated): the `vals` / d_vals given to cnl_factorize_f32* (or
+ * cnl_newton_system_f32*) must stay alive and UNMODIFIED until the last cnl_solve_f32* on that factor — the solve reads the
+ * Jacobian values and the residual pivots of the factorisation's vals (host-pointer calls: the handle's own staged copy).
  * The semantics of every call are those of its Float64 twin above.  Mixing element types is CNL_ERR_STATE and does nothing:
  * a Float64 entry point on a Float32 handle (cnl_factorize..., the row f1 / f2 / f4 / trial-point passes, cnl_interleave_dev...)
  * and an `_f32` entry point on a Float64 handle.  cnl_layout_len counts elements, so it serves both types.
