@@ -723,6 +723,27 @@ int create_f32_general_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_
   return CNL_OK;
 }
 
+// A Float32 handle on the dense backend (tuning float32_dense): `plan` is the uncondensed throughput analysis of a pattern that
+// detect_dense accepted (plan->D).  The three calls of the plugin surface run on the float kernels of csrc/dense_f32.hip (Route::Dense
+// at any batch size, as in Float64); the handle is otherwise the Float32 general handle of that plan — device plan, configuration,
+// factor storage and row lists in float —, so that everything that asks what kind of handle this is finds what it finds there.
+int create_f32_dense_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device) {
+  int rc = CNL_OK;
+  cnl_handle* h = nullptr;
+  if ((rc = new_handle(&h, plan, batch, device, true, true))) return rc;
+  auto bail = [&](int code) { cnl_destroy(h); return code; };
+  if ((rc = upload_dev_plan(h))) return bail(rc);
+  if ((rc = choose_config(h))) return bail(rc);
+  if ((rc = setup_layout(h))) return bail(rc);   // (batch_layout = CNL_LAYOUT_INTERLEAVED is the band kernels': CNL_ERR_ARG)
+  std::string derr;
+  if (cnl::dense_create_f32(&h->dense, plan->D, batch, derr, plan->opt.dense_graph != 0, plan->opt.dense_syrk_wgs, plan->opt.dense_panel_blocks))
+    return bail(fail(CNL_ERR_HIP, "dense backend (Float32): " + derr));
+  if ((rc = alloc_factor_storage(h))) return bail(rc);
+  if ((rc = finish_handle(h, rows1, cols1))) return bail(rc);
+  *hout = h;
+  return CNL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -754,6 +775,8 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
   cnl::Tuning o;
   if (int rc = resolve_options(opt, o)) return rc;
   if (int rc = check_batch(batch)) return rc;
+  if (o.float32_dense && !o.float32_general)
+    return fail(CNL_ERR_ARG, "cnl_create_f32: tuning float32_dense = 1 needs float32_general = 1 (the dense backend in float serves Float32 general handles)");
   if (!o.band_kernel && !o.float32_general)
     return fail(CNL_ERR_ARG, "cnl_create_f32: cnl_options.band_kernel = 0, and Float32 handles run on the band kernels only (tuning float32_general = 1: "
                              "the general multifrontal kernel)");
@@ -786,6 +809,19 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
   // records, no dense routes, no staged execution, no band program.
   cnl::Tuning g = o;
   g.condense = o.float32_condense ? 1 : 0; g.register_front = 0; g.dense_backend = 0; g.general_dense = 0; g.staged = 0; g.band_kernel = 0;
+  // (a dense residual block holds nvar * nequ Jacobian entries, nequ diagonal entries and the nvar rho slots at least: a pattern
+  //  with fewer entries is not analysed a second time for the question)
+  if (o.float32_dense && o.dense_backend && nequ > 0 && nnz / nequ >= nvar) {
+    // tuning float32_dense: a dense residual block goes to the dense backend in float, whatever the batch (as a Float64 handle's
+    // does).  The uncondensed analysis runs detect_dense on the validated pattern; a pattern it does not accept — and every pattern
+    // with cnl_options.dense_backend = 0 — goes on to exactly the handle it gets without the key.
+    cnl::Tuning gd = g;
+    gd.condense = 0; gd.float32_condense = 0; gd.float32_register_front = 0; gd.float32_direct_records = 0; gd.dense_backend = 1;
+    if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, gd)) return rc;
+    if (plan->D.active) return create_f32_dense_from_plan(hout, plan, rows1, cols1, batch, device);
+    cnl_plan_destroy(plan);
+    plan = nullptr;
+  }
   if (o.float32_register_front) {
     // ... or, tuning float32_register_front, with the register-front records of the condensed system: the call is the float
     // condensation passes around ONE launch of the register-front kernel in float (solve_ldl!: of the general kernel, which

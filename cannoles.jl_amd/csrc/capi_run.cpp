@@ -314,8 +314,10 @@ int run_dense(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs
   std::string err;
   if (const int* pat = dbg_ldsfill()) (void)cnl::launch_lds_fill(*pat, stream);
   if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
-  const int rc = cnl::dense_run(h->dense, h->plan->D, a.mode, f64(h, d_vals), f64(h, d_rhs), f64(h, d_d), f64(h, a.rho_old), f64(h, a.rho), a.nfact,
-                                a.success, a.npos, a.nzero, a.params, stream, err);
+  // (a Float32 handle — tuning float32_dense — runs the float kernels of csrc/dense_f32.hip: same sequence, float element arrays)
+  const int rc = h->f32 ? cnl::dense_run_f32(h->dense, a.mode, d_vals, d_rhs, d_d, a.rho_old, a.rho, a.nfact, a.success, a.npos, a.nzero, a.params, stream, err)
+                        : cnl::dense_run(h->dense, h->plan->D, a.mode, f64(h, d_vals), f64(h, d_rhs), f64(h, d_d), f64(h, a.rho_old), f64(h, a.rho), a.nfact,
+                                         a.success, a.npos, a.nzero, a.params, stream, err);
   if (rc) return fail(rc == 5 ? CNL_ERR_STATE : CNL_ERR_HIP, "dense backend: " + err);
   return end_timed(h, stream);
 }

@@ -38,6 +38,14 @@ int dense_run(DenseState* st, const DensePlan& D, int mode, double* vals, const 
               double* rho, int32_t* nfact, int32_t* success, int64_t* npos, int64_t* nzero, const double params[9],
               hipStream_t stream, std::string& err);
 
+// ---- the residual-block form in float (csrc/dense_f32.hip: J'WJ and the trailing updates on v_mfma_f32_16x16x4_f32), for Float32
+// handles with tuning float32_dense.  Same plan, same launch sequence, same state type (dense_destroy frees it; the graph cache is the
+// one of dense_impl.h); the element arrays — vals, rhs, d, rho_old, rho — are float arrays, untyped here as everywhere in the
+// driver, params stay the double[9] of the other float kernels.
+int dense_create_f32(DenseState** st, const DensePlan& D, int64_t batch, std::string& err, bool use_graph = true, int syrk_wgs = 0, int panel_blocks = 1);
+int dense_run_f32(DenseState* st, int mode, void* vals, const void* rhs, void* d, void* rho_old, void* rho, int32_t* nfact,
+                  int32_t* success, int64_t* npos, int64_t* nzero, const double params[9], hipStream_t stream, std::string& err);
+
 // ---- the same dense machinery for an ARBITRARY condensed system (csrc/condense.h) of moderate order: plans whose fill makes
 // the fronts larger than the register-front kernel takes (irregular sparsity) and whose batch is small.  The caller (capi_run.cpp)
 // owns the condensed buffer; per problem it hands over the slots of K2, and gets the factor / solution back.

@@ -158,6 +158,8 @@ struct cnl_handle {
   // With tuning float32_direct_records = 1 on top those records are direct (where the analysis can write them and setup_v2 takes
   // them): route Direct, v2_solve by the Float64 rule (lean, staged: still false); d_cbuf / d_d2 and the condensation lists stay,
   // for the solve on plans with class-32 / class-64 fronts.
+  // With tuning float32_dense = 1 a pattern with a dense residual block (plan->D) is the uncondensed handle plus `dense`, a FLOAT
+  // state of the dense backend (csrc/dense_f32.hip): route Dense, every call runs there (run_dense dispatches on f32).
   bool f32_general = false;
   size_t esz() const { return f32 ? sizeof(float) : sizeof(double); }   // bytes per element of every element array of the handle
 };

@@ -409,7 +409,11 @@ class HIPLDLStruct:
     float32_direct_records=1 puts that handle on the Direct route of the Float64 default handle (config["direct"]): the float
     register-front kernel condenses on the fly, a call is that launch and the post-pass, and solve_ldl! stays on the same kernel where
     every front is of the fast class (config["v2_solve"]); patterns whose direct records the analysis refuses keep the handle without
-    the key.  A condensed or direct
+    the key.  Options(float32_general=1, float32_dense=1) puts a pattern whose residual block is DENSE (every residual row holds one
+    entry per variable plus its diagonal: what the Float64 dense backend takes) on the dense backend in float, at any batch size
+    (config["kernel"] == "dense" and config["float32"]: J'WJ and the trailing updates on the f32 matrix cores, the rho ladder decided
+    on the device); every other pattern, and every pattern with dense_backend=0, gets the handle it gets without the key;
+    float32_dense=1 without float32_general is CNL_ERR_ARG.  A condensed or direct
     handle of either kind reads the Jacobian values of `vals` again in solve_ldl!: the array given to try_to_factorize must stay alive
     and unmodified until the last solve on that factor."""
 

@@ -60,7 +60,7 @@ const char* cnl_last_error(void);
 /* library / ABI version: major*10000 + minor*100 + patch (0.3.0: cnl_set_active_batch, cnl_outer_compact_dev;
  * 0.3.1: tuning "float32_general", no new symbol; 0.4.0: cnl_outer_ctl, the cnl_outer_*_ex_dev entry points, cnl_outer_hess_mask_dev;
  * 0.4.1: tuning "float32_register_front", no new symbol; 0.4.2: tuning "float32_direct_records", cnl_get_config bits 36 / 37, no new
- * symbol) */
+ * symbol; 0.4.3: tuning "float32_dense", no new symbol) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -507,6 +507,16 @@ int cnl_launch_counts(int64_t counts[3]);
  * front with more than 1 023 — patterns with a dense Jacobian block), or the larger LDS block of the direct records does not fit,
  * the handle is exactly the "float32_register_front=1" handle (bit 36 clear), and where even that does not apply the
  * "float32_condense=1" handle.  cnl_set_active_batch serves it; batch_layout = CNL_LAYOUT_INTERLEAVED stays CNL_ERR_ARG.
+ *   tuning "float32_dense=1" (default 0; only with "float32_general=1" — "float32_dense=1" without it is CNL_ERR_ARG, and the message
+ * names both keys): a pattern whose residual block is DENSE — every residual row holds one entry per variable plus its diagonal,
+ * what the dense backend of a Float64 handle takes — gets a Float32 handle on that backend in float, at any batch size:
+ * cnl_get_config reports cfg[5] & 7 == 3 with bit 27 set.  J'WJ and the trailing updates run on the f32 matrix instructions, the
+ * rho ladder is decided on the device (rho, rho_old and the rho slots are the Float64 ladder's values on the float inputs, rounded
+ * to float); cnl_newton_system_f32 / cnl_factorize_f32 / cnl_solve_f32 are the device entries behind an upload.  Every other
+ * pattern (band, irregular, half-widths 3 - 4), and every pattern with cnl_options.dense_backend = 0, gets exactly the handle it
+ * gets without the key.  As on every dense handle cnl_set_active_batch is CNL_ERR_STATE; skip_done / only_if_status calls and a
+ * Newton call without rhs are CNL_ERR_STATE as on every Float32 general handle; batch_layout = CNL_LAYOUT_INTERLEAVED stays
+ * CNL_ERR_ARG.  The handle keeps its own factor: the CONTRACT below does not bind it.
  *   CONTRACT (the Direct handles' contract, restated): the `vals` / d_vals given to cnl_factorize_f32* (or
  * cnl_newton_system_f32*) must stay alive and UNMODIFIED until the last cnl_solve_f32* on that factor — the solve reads the
  * Jacobian values and the residual pivots of the factorisation's vals (host-pointer calls: the handle's own staged copy).
