@@ -697,7 +697,8 @@ int create_f32_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1
 // upload_dev_plan), float global scratch where the work area does not fit LDS, and the row lists; on a condensed plan also the
 // condensation lists, the inertia counts of the condensed pivots, and the condensed buffer and reduced solution as FLOAT arrays.
 // Nothing of the dense or staged state exists for it; the register-front state (setup_v2, in floats) only with tuning
-// float32_register_front on a plan whose fronts that kernel takes.
+// float32_register_front on a plan whose fronts that kernel takes; the general form of the dense backend (`gdense`, a FLOAT state)
+// only with tuning float32_general_dense on a plan it takes.
 int create_f32_general_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device) {
   int rc = CNL_OK;
   cnl_handle* h = nullptr;
@@ -714,9 +715,29 @@ int create_f32_general_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_
     if ((rc = dalloc_elems(h, &h->d_d2, (size_t)batch * (size_t)plan->C.N2))) return bail(rc);
     if ((rc = setup_cond_resident(h))) return bail(rc);
   }
+  // tuning float32_general_dense: the condensed system as ONE dense matrix on the float kernels of csrc/dense_f32.hip (Route::GeneralDense,
+  // as a Float64 default handle's), where the analysis kept the slot positions (condensed order 96 .. 4096), a front exceeds order 64
+  // (2: whatever the fronts) and the Float64 handle's batch rule holds for S0, S and G in 64 x 64 tiles of 4-byte elements
+  const cnl::Cond& C = plan->C;
+  const int gd = plan->opt.float32_general_dense;
+  // ("a front exceeds order 64" is P.fmax > 64 here and not !P.v2_ok: analysis.cpp defines v2_ok as fmax <= 64 && register_front &&
+  // with_rhs_row, and the forced analysis of a Float32 general handle sets register_front = 0, so v2_ok is false for EVERY such plan;
+  // fmax > 64 is the clause of v2_ok that speaks about the fronts.  Keep the 64 in step with analysis.cpp.)
+  const bool gd_fits = gd && C.active && !plan->gpos.empty() && (gd == 2 || plan->P.fmax > 64) &&
+                       (batch <= 16 || (double)batch * 3.0 * 16384.0 * std::pow(std::ceil((double)C.N2 / 64.0), 2) <= 8e9);
   // tuning float32_register_front: the register-front kernel in float runs newton_system / try_to_factorize between the passes
   // where the plan's fronts allow it and its LDS block fits; where not, the handle is the float32_condense handle and nothing else
-  if (plan->opt.float32_register_front && plan->C.active && (rc = setup_v2(h))) return bail(rc);
+  // (a plan that kernel takes stays on it with float32_general_dense = 1; 2 asks for the dense route wherever it is possible)
+  if (plan->opt.float32_register_front && plan->C.active && !(gd == 2 && gd_fits) && (rc = setup_v2(h))) return bail(rc);
+  if (gd_fits && !h->use_v2) {
+    std::string derr;
+    h->gops.ns = (int32_t)C.N2; h->gops.nv = (int32_t)plan->nvar; h->gops.nslots = (int32_t)C.ncs; h->gops.cstride = C.cstride;
+    if ((rc = upload(h, plan->gpos, &h->gops.d_pos))) return bail(rc);
+    // (tuning dense_graph as on every dense handle: the call sequence is captured and replayed, key mode 16 + mode as in double)
+    if (cnl::dense_create_general_f32(&h->gdense, (int32_t)C.N2, (int32_t)plan->nvar, (int32_t)C.ncs, h->gops.d_pos, batch, derr,
+                                      plan->opt.dense_graph != 0, plan->opt.dense_panel_blocks))
+      return bail(fail(CNL_ERR_HIP, "dense backend (Float32): " + derr));
+  }
   if ((rc = alloc_factor_storage(h))) return bail(rc);
   if ((rc = finish_handle(h, rows1, cols1))) return bail(rc);
   *hout = h;
@@ -777,6 +798,10 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
   if (int rc = check_batch(batch)) return rc;
   if (o.float32_dense && !o.float32_general)
     return fail(CNL_ERR_ARG, "cnl_create_f32: tuning float32_dense = 1 needs float32_general = 1 (the dense backend in float serves Float32 general handles)");
+  if (o.float32_general_dense && !o.float32_general)
+    return fail(CNL_ERR_ARG, "cnl_create_f32: tuning float32_general_dense needs float32_general = 1 (the general form of the dense backend in float serves Float32 general handles)");
+  if (o.float32_general_dense < 0 || o.float32_general_dense > 2)
+    return fail(CNL_ERR_ARG, "cnl_create_f32: tuning float32_general_dense is 0, 1 (plans with a front above order 64) or 2 (wherever the order and the batch allow)");
   if (!o.band_kernel && !o.float32_general)
     return fail(CNL_ERR_ARG, "cnl_create_f32: cnl_options.band_kernel = 0, and Float32 handles run on the band kernels only (tuning float32_general = 1: "
                              "the general multifrontal kernel)");
@@ -832,6 +857,13 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
     // the call is that one launch and the post-pass.  No lean or solve-only float instance exists, so the plan is not shaped for
     // one (no row form forced on every front, no backward rows).
     if (o.float32_direct_records) { g.direct_records = 1; g.lean_kernel = 0; g.rows_in_backward = 0; }
+  }
+  if (o.float32_general_dense) {
+    // ... or, tuning float32_general_dense, as ONE dense matrix: the analysis keeps the position of every slot of the condensed
+    // system wherever its order is 96 .. 4096 (plan->gpos), and the handle decides by the fronts and the batch
+    // (create_f32_general_from_plan).  Implies float32_condense.
+    if (!g.float32_condense) g.float32_condense = 1;
+    g.condense = 1; g.general_dense = 2;
   }
   if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, g)) return rc;
   const bool direct_plan = plan->P.rec_direct;

@@ -271,7 +271,8 @@ const char* cnl_last_error(void) { return g_err.c_str(); }
 // 0.4.1: tuning float32_register_front (the register-front kernel in float for Float32 general handles), no new symbol
 // 0.4.2: tuning float32_direct_records (Float32 general handles on the Direct route), cnl_get_config bits 36 / 37, no new symbol
 // 0.4.3: tuning float32_dense (Float32 general handles with a dense residual block on the dense backend in float), no new symbol
-int32_t cnl_version(void) { return 403; }
+// 0.4.4: tuning float32_general_dense (Float32 general handles with large fronts on the general form of the dense backend in float), no new symbol
+int32_t cnl_version(void) { return 404; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62

@@ -339,9 +339,12 @@ int execute(cnl_handle* h, const cnl::CallShape& S, cnl::LaunchArgs& a, void* d_
   if (S.inertia && (rc = cond_inertia(h, d_vals, a.params[0], stream))) return rc;
   if (gdense) {
     std::string err;
-    rc = cnl::dense_run_general(h->gdense, h->gops, a.mode, f64(h, h->d_cbuf), h->d_xpos, h->d_xzer, f64(h, h->d_d2),
-                                d_vals ? f64(h, d_vals) + (C.nnz - C.nvar) : nullptr, C.nnz, f64(h, a.rho_old), f64(h, a.rho), a.nfact, a.success,
-                                a.npos, a.nzero, a.params, stream, err);
+    // (a Float32 handle — tuning float32_general_dense — runs the float kernels of csrc/dense_f32.hip: same sequence, float element arrays)
+    rc = h->f32 ? cnl::dense_run_general_f32(h->gdense, h->gops, a.mode, h->d_cbuf, h->d_xpos, h->d_xzer, h->d_d2, elem_offset(h, d_vals, C.nnz - C.nvar),
+                                             C.nnz, a.rho_old, a.rho, a.nfact, a.success, a.npos, a.nzero, a.params, stream, err)
+                : cnl::dense_run_general(h->gdense, h->gops, a.mode, f64(h, h->d_cbuf), h->d_xpos, h->d_xzer, f64(h, h->d_d2),
+                                         d_vals ? f64(h, d_vals) + (C.nnz - C.nvar) : nullptr, C.nnz, f64(h, a.rho_old), f64(h, a.rho), a.nfact,
+                                         a.success, a.npos, a.nzero, a.params, stream, err);
     if (rc) return fail(CNL_ERR_HIP, "dense backend: " + err);
   } else {
     // (from the condensed buffer: the matrix slots where the call factorises, the right-hand-side slots where it solves)

@@ -53,7 +53,7 @@ struct GeneralOps {
   int32_t ns = 0, nv = 0;          // order of the condensed system, number of variables (they carry rho)
   int32_t nslots = 0;              // unique lower-triangular slots of K2 (without the rho entries)
   const int32_t* d_pos = nullptr;  // device: position i + ns * j of every slot
-  int64_t cstride = 0;             // doubles per problem of the condensed buffer [slots | rho (nv) | rhs (ns)]
+  int64_t cstride = 0;             // elements per problem of the condensed buffer [slots | rho (nv) | rhs (ns)]
 };
 // d_pos (device, owned by the caller): position i + ns * j of every slot of the condensed system
 int dense_create_general(DenseState** st, int32_t ns, int32_t nv, int32_t nslots, const int32_t* d_pos, int64_t batch, std::string& err,
@@ -64,5 +64,14 @@ int dense_create_general(DenseState** st, int32_t ns, int32_t nv, int32_t nslots
 int dense_run_general(DenseState* st, const GeneralOps& G, int mode, const double* cbuf, const int* xpos, const int* xzer, double* d2,
                       double* vals_rho0, int64_t vals_stride, double* rho_old, double* rho, int32_t* nfact, int32_t* success,
                       int64_t* npos, int64_t* nzero, const double params[9], hipStream_t stream, std::string& err);
+
+// ---- the general form in float (csrc/dense_f32.hip), for Float32 general handles with tuning float32_general_dense.  Same launch
+// sequence, same graph cache, same GeneralOps (cstride then counts floats); cbuf, d2, vals_rho0, rho_old and rho are float arrays,
+// untyped as in dense_run_f32.
+int dense_create_general_f32(DenseState** st, int32_t ns, int32_t nv, int32_t nslots, const int32_t* d_pos, int64_t batch, std::string& err,
+                             bool use_graph = true, int panel_blocks = 1);
+int dense_run_general_f32(DenseState* st, const GeneralOps& G, int mode, const void* cbuf, const int* xpos, const int* xzer, void* d2,
+                          void* vals_rho0, int64_t vals_stride, void* rho_old, void* rho, int32_t* nfact, int32_t* success, int64_t* npos,
+                          int64_t* nzero, const double params[9], hipStream_t stream, std::string& err);
 
 }  // namespace cnl

@@ -1244,7 +1244,7 @@ int dense_enqueue_general(DenseState* st, const GeneralOps& G, int mode, const d
   int rc;
   if (mode != 2) {
     hipLaunchKernelGGL(dn_set_counts, dim3(blocks(B)), dim3(256), 0, stream, d, B, xpos, xzer);
-    DCHK(hipMemsetAsync(d.S0, 0, (size_t)B * d.T * d.T * TT * sizeof(double), stream));
+    dn::zero_async(d.S0, (size_t)B * d.T * d.T * TT * sizeof(double), stream);   // (a kernel, not a memset node: dense_impl.h)
     hipLaunchKernelGGL(dn_scatter_general, dim3(std::min(1024, blocks(std::max(d.nslots, d.nsp))), B), dim3(256), 0, stream, d, cbuf, (long long)G.cstride);
     hipLaunchKernelGGL(dn_shift, dim3(d.nlt, B), dim3(256), 0, stream, d);
     if ((rc = enqueue_factor(st, eig_tol, stream, err))) return rc;

@@ -12,6 +12,16 @@
 //   dnf_yrhs, dnf_gt_part, dnf_g_part, dnf_resid_part, dnf_xfinal, dnf_jx, dnf_out   d = -K^-1 rhs through S^-1 = G D G' and one
 //                 step of iterative refinement against S0 (all in float)
 //
+// ... and of the kernels only the GENERAL form enqueues (dense_run_general: an arbitrary condensed system as one dense matrix,
+// Float32 handles with tuning float32_general_dense; m == 0 in DnDevF marks it):
+//   dnf_set_counts, dn_zero16, dnf_scatter_general, dnf_shift   in place of gather / J'WJ / assemble: the inertia counts of the
+//                 condensed pivots handed in, S0 zeroed and scattered out of the float condensed buffer, S = S0 + the rho slots
+//                 behind it.  (S0 is zeroed by a kernel, not by hipMemsetAsync: the call sequence is captured as a graph, and a
+//                 replayed memset node was seen to fill S0 with something other than zeros — DESIGN section 9.6.)
+//   dnf_yrhs_general, dnf_out_general                in place of yrhs / jx / out: y is the condensed right-hand side, d2 = -x
+// Everything between them is the residual-block form's: none of the panel, update, ladder, decide and solve kernels reads n, m, p,
+// J or w — they see S0, S, G, rsh, the counters and the tile lists, which the general form fills the same way.
+//
 // What differs from the double form, and what does not:
 //   * Tile order stays 64, the macro tile of J'WJ stays 128, row chunks stay 16, dnf_yrhs stages 2048 rows at a time, the ladder
 //     takes 7 row tiles per pass and dnf_panel 3 row tiles per workgroup: the float kernels have the edges of the double kernels.
@@ -53,7 +63,7 @@ struct DnStateF {  // per problem, device
   int nfact, success, done, pad;
 };
 
-struct DnDevF {  // dense.hip: DnDev, in floats (the general form is not served)
+struct DnDevF {  // dense.hip: DnDev, in floats (m == 0: the general form, one condensed system as a dense matrix)
   int ns, nv, T, nsp;
   int n, m, p, mp, npj, Tn;
   int nnz;
@@ -63,6 +73,8 @@ struct DnDevF {  // dense.hip: DnDev, in floats (the general form is not served)
   const int *jslot, *dslot;
   const int *lI, *lJ;
   const int *ht_ptr, *hu_loc, *hu_ptr, *hslot;
+  const int* gpos;  // general form: position i + ns j of every slot
+  int nslots;
   float *Jw;
   float *Jd, *w, *slab, *S0, *S, *G, *Wn, *dv, *rsh, *y, *x, *jxp;
   float *part1, *part2, *partA, *partB;
@@ -234,6 +246,31 @@ __global__ void __launch_bounds__(256) dnf_assemble(DnDevF D, const float* __res
 #pragma unroll
   for (int q = 0; q < 4; q++) reinterpret_cast<float4*>(D.S0 + off)[t + 256 * q] = reinterpret_cast<const float4*>(tile)[t + 256 * q];
   shift_tile(D, tile, D.S + off, I, J, sh64 - 64 * I, t, 256);
+}
+
+// general condensed system (dense.hip: dn_scatter_general, dn_shift): S0 from the slots of the float condensed buffer (unique
+// positions; dn_zero16 zeroes S0 in front: n4 groups of 16 bytes, a whole number of tiles of either element type — the double form
+// of dense.hip zeroes its S0 through it too, dn::zero_async —), the rho slots behind them become
+// the shifts; then S = S0 + shift, tile by tile
+__global__ void __launch_bounds__(256) dn_zero16(float4* __restrict__ p, long long n4) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) p[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+__global__ void __launch_bounds__(256) dnf_scatter_general(DnDevF D, const float* __restrict__ cbuf, long long cstride) {
+  const int b = blockIdx.y;
+  const float* cb = cbuf + (size_t)b * cstride;
+  float* S0 = D.S0 + (size_t)b * D.T * D.T * TT;
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < D.nslots; e += gridDim.x * 256) {
+    const int pos = D.gpos[e], i = pos % D.ns, j = pos / D.ns;
+    S0[tile_off(D.T, i >> 6, j >> 6) + (i & 63) + 64 * (j & 63)] = cb[e];
+  }
+  float* rsh = D.rsh + (size_t)b * D.nsp;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < D.nsp; i += gridDim.x * 256) rsh[i] = i < D.nv ? cb[D.nslots + i] : 0.0f;
+}
+__global__ void __launch_bounds__(256) dnf_shift(DnDevF D) {
+  const int b = blockIdx.y, lt = blockIdx.x;
+  const int I = D.lI[lt], J = D.lJ[lt];
+  const size_t off = (size_t)b * D.T * D.T * TT + tile_off(D.T, I, J);
+  shift_tile(D, D.S0 + off, D.S + off, I, J, D.rsh + (size_t)b * D.nsp, threadIdx.x, 256);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -809,6 +846,14 @@ __global__ void __launch_bounds__(256) dnf_yrhs(DnDevF D, const float* __restric
     else if (c < D.nsp) y[c] = c < D.ns ? rb[D.n + D.m + (c - D.n)] : 0.0f;
   }
 }
+// general form: y = the condensed right-hand side, behind the matrix and rho slots of the condensed buffer
+__global__ void __launch_bounds__(256) dnf_yrhs_general(DnDevF D, const float* __restrict__ cbuf, long long cstride, int gate) {
+  const int b = blockIdx.y;
+  if (gate && !D.st[b].success) return;
+  const float* crhs = cbuf + (size_t)b * cstride + D.nslots + D.nv;
+  float* y = D.y + (size_t)b * D.nsp;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < D.nsp; i += gridDim.x * 256) y[i] = i < D.ns ? crhs[i] : 0.0f;
+}
 
 // ---- tile GEMVs of the solve.  Every tile of G (upper, J >= I) resp. S (lower) is one workgroup; a tile product is 64
 // partial sums, and the vector a later kernel needs is summed from the partials in a fixed order by the workgroup that
@@ -964,6 +1009,25 @@ __global__ void __launch_bounds__(256) dnf_out(DnDevF D, const float* __restrict
     db[i] = D.w[(size_t)b * D.mp + q] * (rhs[(size_t)b * N + i] - jx);
   } else db[i] = -x[D.n + (i - D.n - D.m)];
 }
+// general form: d2 = -x in the reduced numbering (the expand pass makes d of it); a problem no rho repairs leaves d2 as it was
+__global__ void __launch_bounds__(256) dnf_out_general(DnDevF D, float* __restrict__ d2, int mode, float* rho_old, float* rho, int32_t* nfact,
+                                                       int32_t* success) {
+  const int b = blockIdx.y;
+  const DnStateF s = D.st[b];
+  if (mode == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+    rho[b] = s.rho; rho_old[b] = s.rho_old; nfact[b] = s.nfact; success[b] = s.success;
+  }
+  if (mode == 0 && !s.success) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < D.ns) d2[(size_t)b * D.ns + i] = -D.x[(size_t)b * D.nsp + i];
+}
+// general form: the residual pivots are counted outside (the inertia pass of the condensation, compared in float)
+__global__ void __launch_bounds__(256) dnf_set_counts(DnDevF D, int batch, const int* __restrict__ xpos, const int* __restrict__ xzer) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= batch) return;
+  D.cnt[b * 4 + 0] = 0; D.cnt[b * 4 + 1] = 0;
+  D.cnt[b * 4 + 2] = xpos ? xpos[b] : 0; D.cnt[b * 4 + 3] = xzer ? xzer[b] : 0;
+}
 
 struct DenseStateF32 : DenseState { DnDevF d{}; };
 inline DnDevF& dev32(DenseState* st) { return static_cast<DenseStateF32*>(st)->d; }
@@ -1025,7 +1089,82 @@ int dense_enqueue_f32(DenseState* st, int mode, float* vals, const float* rhs, f
   return 0;
 }
 
+// the launch sequence of dense.hip: dense_enqueue_general, kernel by kernel (its hipMemsetAsync of S0 is a kernel here: no memset node
+// in the captured graph; the double form zeroes through the same kernel, dn::zero_async)
+int dense_enqueue_general_f32(DenseState* st, const GeneralOps& G, int mode, const float* cbuf, const int* xpos, const int* xzer, float* d2,
+                              float* vals_rho0, int64_t vals_stride, float* rho_old, float* rho, int32_t* nfact, int32_t* success,
+                              int64_t* npos, int64_t* nzero, const double params[9], hipStream_t stream, std::string& err) {
+  const DnDevF& d = dev32(st);
+  const int B = (int)st->batch;
+  const float eig_tol = (float)params[0];  // the inertia rule compares in float
+  int rc;
+  if (mode != 2) {
+    hipLaunchKernelGGL(dnf_set_counts, dim3(dn::blocks(B)), dim3(256), 0, stream, d, B, xpos, xzer);
+    dn::zero_async(d.S0, (size_t)B * d.T * d.T * TT * sizeof(float), stream);   // S0 of the batch (setup_common allocates exactly this)
+    hipLaunchKernelGGL(dnf_scatter_general, dim3(std::min(1024, dn::blocks(std::max(d.nslots, d.nsp))), B), dim3(256), 0, stream, d, cbuf, (long long)G.cstride);
+    hipLaunchKernelGGL(dnf_shift, dim3(d.nlt, B), dim3(256), 0, stream, d);
+    if ((rc = enqueue_factor(st, eig_tol, stream, err))) return rc;
+    if (mode == 0) {
+      // the ladder writes the last rho tried into the caller's rho slots: vals_rho0 + b * vals_stride, nv entries
+      DnDevF dl = d;
+      dl.nnz = (int)vals_stride;  // dnf_ladder addresses vals + b * nnz + (nnz - nv)
+      hipLaunchKernelGGL(dnf_ladder, dim3(B), dim3(LNW * 64), 0, stream, dl, vals_rho0 - (vals_stride - d.nv), rho_old, eig_tol, params[2], params[3],
+                         params[4], params[5], params[6], params[7]);
+    } else
+      hipLaunchKernelGGL(dnf_decide, dim3(dn::blocks(B)), dim3(256), 0, stream, d, B, mode, nullptr, success, npos, nzero);
+    DCHK(hipGetLastError());
+    if (mode == 1) return 0;
+  }
+  const int gate = mode == 0 ? 1 : 0;
+  hipLaunchKernelGGL(dnf_yrhs_general, dim3(std::min(256, dn::blocks(d.nsp)), B), dim3(256), 0, stream, d, cbuf, (long long)G.cstride, gate);
+  if ((rc = enqueue_solve_core(st, gate, stream, err))) return rc;
+  hipLaunchKernelGGL(dnf_out_general, dim3(dn::blocks(d.ns), B), dim3(256), 0, stream, d, d2, mode, rho_old, rho, nfact, success);
+  DCHK(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
+
+// (the launch is not checked here: both callers end their sequence with hipGetLastError)
+void dn::zero_async(void* p, size_t bytes, hipStream_t stream) {
+  const long long n4 = (long long)(bytes / 16);
+  hipLaunchKernelGGL(dn_zero16, dim3((unsigned)std::min<long long>(8192, (n4 + 255) / 256)), dim3(256), 0, stream, static_cast<float4*>(p), n4);
+}
+
+int dense_create_general_f32(DenseState** out, int32_t ns, int32_t nv, int32_t nslots, const int32_t* d_pos, int64_t batch, std::string& err,
+                             bool use_graph, int panel_blocks) {
+  DenseStateF32* st = new DenseStateF32();
+  st->batch = batch;
+  st->f32 = true;
+  st->use_graph = use_graph;
+  st->panel2 = panel_blocks != 0; st->panel2_auto = panel_blocks == 1;
+  st->general = true;
+  *out = st;
+  DnDevF& d = st->d;
+  d.n = ns; d.m = 0; d.p = 0; d.nnz = 0; d.mp = 0; d.npj = 0; d.Tn = 0; d.ntl = 0; d.ks = 1;
+  d.npos_ok = nv;
+  d.nslots = nslots; d.gpos = d_pos;
+  return dn::setup_common(st, d, ns, nv, batch, nullptr, 0, err);
+}
+
+int dense_run_general_f32(DenseState* st, const GeneralOps& G, int mode, const void* cbuf, const int* xpos, const int* xzer, void* d2,
+                          void* vals_rho0, int64_t vals_stride, void* rho_old, void* rho, int32_t* nfact, int32_t* success, int64_t* npos,
+                          int64_t* nzero, const double params[9], hipStream_t stream, std::string& err) {
+  if (!st->f32 || !st->general) { err = "dense_run_general_f32 needs a Float32 state of the general form (dense_create_general_f32)"; return 4; }
+  if (mode == 2 && !st->factored) { err = "cnl_solve before cnl_factorize"; return 5; }
+  GraphKey key;
+  key.mode = 16 + mode;
+  const void* ps[10] = {cbuf, xpos, xzer, d2, vals_rho0, rho_old, rho, nfact, success, npos};
+  for (int i = 0; i < 10; i++) key.p[i] = ps[i];
+  for (int i = 0; i < 9; i++) key.params[i] = params[i];
+  key.extra = (long long)vals_stride ^ ((long long)(uintptr_t)nzero << 1);
+  const int rc = dn::run_cached(st, key, stream, err, [&](hipStream_t s2) {
+    return dense_enqueue_general_f32(st, G, mode, static_cast<const float*>(cbuf), xpos, xzer, static_cast<float*>(d2), static_cast<float*>(vals_rho0),
+                                     vals_stride, static_cast<float*>(rho_old), static_cast<float*>(rho), nfact, success, npos, nzero, params, s2, err);
+  });
+  if (!rc && mode != 2) st->factored = true;
+  return rc;
+}
 
 int dense_create_f32(DenseState** out, const DensePlan& P, int64_t batch, std::string& err, bool use_graph, int syrk_wgs, int panel_blocks) {
   DenseStateF32* st = new DenseStateF32();

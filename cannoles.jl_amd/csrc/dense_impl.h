@@ -252,6 +252,11 @@ int run_cached(DenseState* st, const GraphKey& key, hipStream_t stream, std::str
 
 inline int blocks(long long n) { return (int)((n + 255) / 256); }
 
+// zero `bytes` (a multiple of 16, p 16-byte aligned: whole tiles) with a kernel on `stream` (dense_f32.hip).  Both general forms zero
+// S0 with it inside their captured sequence, NOT with hipMemsetAsync: the memset node of a replayed graph was seen to fill with
+// something other than zeros.  The kernel lives in dense_f32.hip so that dense.hip's device code stays as it is.
+void zero_async(void* p, size_t bytes, hipStream_t stream);
+
 }  // namespace dn
 
 }  // namespace cnl

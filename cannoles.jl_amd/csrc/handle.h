@@ -160,6 +160,9 @@ struct cnl_handle {
   // for the solve on plans with class-32 / class-64 fronts.
   // With tuning float32_dense = 1 a pattern with a dense residual block (plan->D) is the uncondensed handle plus `dense`, a FLOAT
   // state of the dense backend (csrc/dense_f32.hip): route Dense, every call runs there (run_dense dispatches on f32).
+  // With tuning float32_general_dense a condensed plan with a front above order 64 (2: any) whose condensed order is 96 .. 4096 is
+  // the float32_condense handle plus `gdense`, a FLOAT state of the general form, and gops: route GeneralDense, a call is the float
+  // condensation passes around the dense LDL^T of the condensed system (execute dispatches on f32).
   bool f32_general = false;
   size_t esz() const { return f32 ? sizeof(float) : sizeof(double); }   // bytes per element of every element array of the handle
 };

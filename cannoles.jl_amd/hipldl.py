@@ -413,7 +413,12 @@ class HIPLDLStruct:
     entry per variable plus its diagonal: what the Float64 dense backend takes) on the dense backend in float, at any batch size
     (config["kernel"] == "dense" and config["float32"]: J'WJ and the trailing updates on the f32 matrix cores, the rho ladder decided
     on the device); every other pattern, and every pattern with dense_backend=0, gets the handle it gets without the key;
-    float32_dense=1 without float32_general is CNL_ERR_ARG.  A condensed or direct
+    float32_dense=1 without float32_general is CNL_ERR_ARG.  Options(float32_general=1, float32_general_dense=1) (implies
+    float32_condense) puts an IRREGULAR pattern whose condensed plan has a front above order 64, condensed order 96 .. 4096, on the
+    general form of that backend: the float condensation passes around one dense LDL' of the whole condensed system
+    (config["kernel"] == "dense", config["float32"] and info["ncond"] > 0), while batch <= 16 or the tiles stay within 8 GB; 2:
+    whatever the fronts; every other pattern gets the handle it gets without the key, and the key without float32_general is
+    CNL_ERR_ARG.  A condensed or direct
     handle of either kind reads the Jacobian values of `vals` again in solve_ldl!: the array given to try_to_factorize must stay alive
     and unmodified until the last solve on that factor."""
 

@@ -60,7 +60,7 @@ const char* cnl_last_error(void);
 /* library / ABI version: major*10000 + minor*100 + patch (0.3.0: cnl_set_active_batch, cnl_outer_compact_dev;
  * 0.3.1: tuning "float32_general", no new symbol; 0.4.0: cnl_outer_ctl, the cnl_outer_*_ex_dev entry points, cnl_outer_hess_mask_dev;
  * 0.4.1: tuning "float32_register_front", no new symbol; 0.4.2: tuning "float32_direct_records", cnl_get_config bits 36 / 37, no new
- * symbol; 0.4.3: tuning "float32_dense", no new symbol) */
+ * symbol; 0.4.3: tuning "float32_dense", no new symbol; 0.4.4: tuning "float32_general_dense", no new symbol) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -517,6 +517,19 @@ int cnl_launch_counts(int64_t counts[3]);
  * gets without the key.  As on every dense handle cnl_set_active_batch is CNL_ERR_STATE; skip_done / only_if_status calls and a
  * Newton call without rhs are CNL_ERR_STATE as on every Float32 general handle; batch_layout = CNL_LAYOUT_INTERLEAVED stays
  * CNL_ERR_ARG.  The handle keeps its own factor: the CONTRACT below does not bind it.
+ *   tuning "float32_general_dense=1" (default 0; only with "float32_general=1" — without it the call is CNL_ERR_ARG, and the message
+ * names both keys; implies "float32_condense"): an IRREGULAR pattern whose fill makes a front of the condensed throughput plan
+ * larger than order 64 — what the register-front kernel refuses — runs as ONE dense matrix on the general form of the dense backend
+ * in float, as a Float64 default handle's does in double: the float condensation passes around a dense LDL' of the whole condensed
+ * system in 64 x 64 tiles on the f32 matrix instructions, the rho ladder decided on the device.  Taken where the pattern has no band
+ * program, "float32_dense" did not take it, the condensed order is 96 .. 4096, and batch <= 16 or 3 x 16 384 x ceil(order / 64)^2 x
+ * batch <= 8e9 bytes (the Float64 handle's rule with 4-byte elements); "=2" takes it whatever the fronts (measurement, tests).  Every
+ * other pattern gets exactly the handle it gets without the key ("float32_condense=1", or the register-front kernel where
+ * "float32_register_front=1" serves the plan).  cnl_get_config reports cfg[5] & 7 == 3 with bit 27 set; a condensed plan
+ * (cnl_plan_info: ncond > 0) tells it from the "float32_dense" handle.  cnl_set_active_batch, skip_done / only_if_status calls and
+ * a Newton call without rhs are CNL_ERR_STATE, batch_layout = CNL_LAYOUT_INTERLEAVED stays CNL_ERR_ARG, the host-pointer entries are
+ * the device entries behind an upload.  The solve condenses each new right-hand side from the factorisation's vals: the CONTRACT
+ * below binds this handle.  Measured standing (README): opt-in.
  *   CONTRACT (the Direct handles' contract, restated): the `vals` / d_vals given to cnl_factorize_f32* (or
  * cnl_newton_system_f32*) must stay alive and UNMODIFIED until the last cnl_solve_f32* on that factor — the solve reads the
  * Jacobian values and the residual pivots of the factorisation's vals (host-pointer calls: the handle's own staged copy).
