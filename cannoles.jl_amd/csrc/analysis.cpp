@@ -10,6 +10,7 @@
 // every x pivot is an entry of a Schur complement of H + rho I + J'J and
 // "factorisation completes" coincides with "inertia is (nvar, nequ+ncon, 0)".
 #include "plan.h"
+#include "refine.h"
 
 #include <algorithm>
 #include <array>
@@ -1539,6 +1540,27 @@ int write_backward_rows(Plan& P, const BackRowsIn& in) {
   P.back_rows = true;
   finalize_tasks(P);
   return 0;
+}
+
+// refine.h: the rows of the full symmetric matrix of a lower-triangular COO pattern, as (slot, column) pairs.  Two counting passes
+// over the slots in ascending order, so the pairs of a row come out in ascending slot order; a diagonal entry appears once, a
+// strict-lower one in its row and — mirrored — in its column's row.
+void build_kkt_rows(KktRows& R, int64_t N, int64_t nnz, const int32_t* rows0, const int32_t* cols0) {
+  R.ptr.assign((size_t)N + 1, 0);
+  for (int64_t e = 0; e < nnz; e++) {
+    R.ptr[rows0[e] + 1]++;
+    if (rows0[e] != cols0[e]) R.ptr[cols0[e] + 1]++;
+  }
+  R.max_row = 0;
+  for (int64_t i = 0; i < N; i++) { R.max_row = std::max(R.max_row, R.ptr[i + 1]); R.ptr[i + 1] += R.ptr[i]; }
+  R.slot.resize((size_t)R.ptr[N]); R.col.resize((size_t)R.ptr[N]);
+  std::vector<int32_t> fill(R.ptr.begin(), R.ptr.end() - 1);
+  for (int64_t e = 0; e < nnz; e++) {
+    const int32_t r = rows0[e], c = cols0[e];
+    int32_t q = fill[r]++;
+    R.slot[q] = (int32_t)e; R.col[q] = c;
+    if (r != c) { q = fill[c]++; R.slot[q] = (int32_t)e; R.col[q] = r; }
+  }
 }
 
 }  // namespace cnl

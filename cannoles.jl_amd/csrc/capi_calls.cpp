@@ -706,6 +706,13 @@ int cnl_residual_vectors_jac_dev(cnl_handle* h, int64_t nnzjF, int64_t nnzjc, co
   return residual_vectors_impl(h, S, d_r, d_lambda, d_Fx, d_cx, d_rhs, d_norms, stream);
 }
 
+int cnl_kkt_residual_dev(cnl_handle* h, const double* d_vals, const double* d_rhs, const double* d_d, double* d_g, double* d_norms, void* stream) {
+  if (!h || !d_vals || !d_rhs || !d_d || !d_g) return fail(CNL_ERR_ARG, "null argument");
+  CNL_NEED_F64(h);
+  if (h->layout & 1) return fail(CNL_ERR_STATE, "cnl_kkt_residual_dev reads problem-major vals: this handle was created with batch_layout = CNL_LAYOUT_INTERLEAVED");
+  return kkt_residual(h, d_vals, d_rhs, d_d, d_g, d_norms, (hipStream_t)stream);
+}
+
 int cnl_trial_point_dev(cnl_handle* h, const double* d_x, const double* d_r, const double* d_lambda, const double* d_d,
                         double max_dlambda, double* d_xt, double* d_rt, double* d_lambdat, double* d_dlambda, void* stream) {
   if (!h || !d_x || !d_r || !d_d || !d_xt || !d_rt) return fail(CNL_ERR_ARG, "null argument");
@@ -836,6 +843,8 @@ int cnl_newton_system(cnl_handle* h, double* vals, const double* rhs, double* d,
   if (h->layout) return fail(CNL_ERR_STATE, kHostLayout);
   HIPCHK(hipSetDevice(h->device));
   if (int rc = ensure_staging(h)) return rc;
+  // (a refined handle — tuning float32_refine — takes the plain route: the routes below are Float64 kernels' business)
+  if (h->inner) return newton_system_impl(h, vals, rhs, d, rho_old, params, rho, rho_old_out, nfact, success);
   const cnl_plan& P = *h->plan;
   const size_t B = (size_t)h->batch;
   if (!h->dense && !h->gdense && !h->timing && B >= 32 && B * (size_t)(P.nnz + P.N) * sizeof(double) >= ((size_t)96 << 20)) {

@@ -765,7 +765,91 @@ int create_f32_dense_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t*
   return CNL_OK;
 }
 
+// A Float32 general handle off the band kernels, from the caller's options: the dense backend in float where tuning float32_dense finds
+// a dense residual block, else the general / register-front / general-dense handle of the plan (what cnl_create_f32_ex does behind
+// the band kernels, and all the inner handle of a float32_refine handle is)
+int create_f32_general(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ, int64_t ncon,
+                       int64_t batch, int device, const cnl::Tuning& o) {
+  cnl_plan* plan = nullptr;
+  cnl::Tuning g;
+  if (int rc = f32_general_plan(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, o, &g)) return rc;
+  if (plan->D.active) return create_f32_dense_from_plan(hout, plan, rows1, cols1, batch, device);
+  const bool direct_plan = plan->P.rec_direct;
+  if (int rc = create_f32_general_from_plan(hout, plan, rows1, cols1, batch, device)) return rc;
+  if (direct_plan && (*hout)->route != cnl::Route::Direct) {
+    // setup_v2 declined the direct records (their LDS block is the larger one): the handle is the one without the key
+    cnl_destroy(*hout);
+    *hout = nullptr;
+    g.direct_records = 0;
+    if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, g)) return rc;
+    return create_f32_general_from_plan(hout, plan, rows1, cols1, batch, device);
+  }
+  return CNL_OK;
+}
+
+// Tuning float32_refine (handle.h: cnl_handle::inner): the inner Float32 general handle from the caller's own options with band_kernel
+// forced to 0, and around it a Float64 handle on the same plan that owns the Float64 row lists, the rows of the full matrix and the
+// float arrays the refined calls convert into.
+int create_refined(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ, int64_t ncon,
+                   int64_t batch, int device, const cnl::Tuning& o) {
+  if (int rc = check_batch(batch)) return rc;
+  if (int rc = check_f32_options(o, "cnl_create_ex")) return rc;
+  if (int rc = check_device(device)) return rc;
+  cnl::Tuning oi = o;
+  oi.band_kernel = 0; oi.float32_refine = 0;
+  cnl_handle* inner = nullptr;
+  if (int rc = create_f32_general(&inner, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, oi)) return rc;
+  cnl_handle* h = nullptr;
+  inner->plan->refs.fetch_add(1);
+  if (int rc = new_handle(&h, inner->plan, batch, device, false, false)) { cnl_destroy(inner); return rc; }
+  h->inner = inner;
+  h->refine_k = o.float32_refine;
+  auto bail = [&](int code) { cnl_destroy(h); return code; };
+  int rc;
+  const size_t B = (size_t)batch;
+  if ((rc = dalloc(h, &h->r_vals, B * (size_t)nnz))) return bail(rc);
+  if ((rc = dalloc(h, &h->r_rhs, B * (size_t)N))) return bail(rc);
+  if ((rc = dalloc(h, &h->r_e, B * (size_t)N))) return bail(rc);
+  if ((rc = dalloc(h, &h->r_rho, B))) return bail(rc);
+  if ((rc = dalloc(h, &h->r_rho_old, B))) return bail(rc);
+  if ((rc = dalloc(h, &h->r_success, B))) return bail(rc);
+  if ((rc = dalloc(h, &h->r_norms, B * (size_t)h->refine_k))) return bail(rc);
+  {
+    const std::vector<double> none(B * (size_t)h->refine_k, -1.0);   // (no problem holds a factor yet)
+    if (hipMemcpy(h->r_norms, none.data(), none.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipMemcpy failed"));
+  }
+  if ((rc = finish_handle(h, rows1, cols1))) return bail(rc);   // (the route it sets is never read: run() dispatches on h->inner first)
+  if ((rc = ensure_kkt_rows(h))) return bail(rc);
+  *hout = h;
+  return CNL_OK;
+}
+
 }  // namespace
+
+// the rows of the full KKT matrix on the device, on first use (as cgls_ws): pattern-sized, shared by all problems of the handle
+int ensure_kkt_rows(cnl_handle* h) {
+  if (h->dkkt.ptr) return CNL_OK;
+  const cnl::KktRows& R = kkt_rows(h->plan);
+  cnl::DevKktRows D{};
+  int rc;
+  HIPCHK(hipSetDevice(h->device));
+  if ((rc = upload(h, R.slot, &D.slot))) return rc;
+  if ((rc = upload(h, R.col, &D.col))) return rc;
+  D.N = (int32_t)h->plan->N; D.nnz = h->plan->nnz;
+  // the instance (tuning refine_rows: 1 lane, 2 wavefront; 0: by the mean row length, refine.h)
+  const int force = h->plan->opt.refine_rows;
+  D.wave_rows = force ? force == 2 : (int64_t)R.slot.size() >= (int64_t)cnl::KKT_WAVE_ROW_THRESHOLD * h->plan->N;
+  // small batches: several workgroups per problem, each a chunk of whole rows — at least a row per thread (lane rows) or four rows
+  // per wavefront (wavefront rows)
+  const int64_t min_rows = D.wave_rows ? 16 : 256, max_chunks = (h->plan->N + min_rows - 1) / min_rows;
+  D.nchunk = (int32_t)std::max<int64_t>(1, std::min<int64_t>(max_chunks, (cnl::KKT_TARGET_WORKGROUPS + h->full_batch - 1) / h->full_batch));
+  D.rows_per_chunk = (int32_t)((h->plan->N + D.nchunk - 1) / D.nchunk);
+  D.nchunk = (int32_t)((h->plan->N + D.rows_per_chunk - 1) / D.rows_per_chunk);   // (no empty chunk)
+  if (D.nchunk > 1 && (rc = dalloc(h, &D.partial, (size_t)h->full_batch * (size_t)D.nchunk))) return rc;
+  if ((rc = upload(h, R.ptr, &D.ptr))) return rc;   // (last: the lists exist)
+  h->dkkt = D;
+  return CNL_OK;
+}
 
 extern "C" {
 
@@ -781,6 +865,7 @@ int cnl_create_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows
   cnl::Tuning o;
   const int rc0 = resolve_options(opt, o);
   if (rc0) return rc0;
+  if (o.float32_refine) return create_refined(hout, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, o);
   return create_tuned(hout, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, o);
 }
 
@@ -796,12 +881,9 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
   cnl::Tuning o;
   if (int rc = resolve_options(opt, o)) return rc;
   if (int rc = check_batch(batch)) return rc;
-  if (o.float32_dense && !o.float32_general)
-    return fail(CNL_ERR_ARG, "cnl_create_f32: tuning float32_dense = 1 needs float32_general = 1 (the dense backend in float serves Float32 general handles)");
-  if (o.float32_general_dense && !o.float32_general)
-    return fail(CNL_ERR_ARG, "cnl_create_f32: tuning float32_general_dense needs float32_general = 1 (the general form of the dense backend in float serves Float32 general handles)");
-  if (o.float32_general_dense < 0 || o.float32_general_dense > 2)
-    return fail(CNL_ERR_ARG, "cnl_create_f32: tuning float32_general_dense is 0, 1 (plans with a front above order 64) or 2 (wherever the order and the batch allow)");
+  if (o.float32_refine)
+    return fail(CNL_ERR_ARG, "cnl_create_f32: tuning float32_refine makes a Float64 handle on a Float32 factor: it is read by cnl_create_ex, not here");
+  if (int rc = check_f32_options(o, "cnl_create_f32")) return rc;
   if (!o.band_kernel && !o.float32_general)
     return fail(CNL_ERR_ARG, "cnl_create_f32: cnl_options.band_kernel = 0, and Float32 handles run on the band kernels only (tuning float32_general = 1: "
                              "the general multifrontal kernel)");
@@ -828,55 +910,8 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
     if (int rc = create_f32_from_plan(hout, plan, rows1, cols1, batch, device)) return rc;
     if (*hout) return CNL_OK;   // (else: the program does not fit the band kernels, and float32_general is set)
   }
-  // tuning float32_general: the general multifrontal kernel in float.  Its plan is the throughput analysis with nothing but that
-  // kernel to run, whatever the caller's options say: no condensation (a call is then the one classic launch) unless tuning
-  // float32_condense asks for it (the call is then that launch between the float condensation passes), no register-front
-  // records, no dense routes, no staged execution, no band program.
-  cnl::Tuning g = o;
-  g.condense = o.float32_condense ? 1 : 0; g.register_front = 0; g.dense_backend = 0; g.general_dense = 0; g.staged = 0; g.band_kernel = 0;
-  // (a dense residual block holds nvar * nequ Jacobian entries, nequ diagonal entries and the nvar rho slots at least: a pattern
-  //  with fewer entries is not analysed a second time for the question)
-  if (o.float32_dense && o.dense_backend && nequ > 0 && nnz / nequ >= nvar) {
-    // tuning float32_dense: a dense residual block goes to the dense backend in float, whatever the batch (as a Float64 handle's
-    // does).  The uncondensed analysis runs detect_dense on the validated pattern; a pattern it does not accept — and every pattern
-    // with cnl_options.dense_backend = 0 — goes on to exactly the handle it gets without the key.
-    cnl::Tuning gd = g;
-    gd.condense = 0; gd.float32_condense = 0; gd.float32_register_front = 0; gd.float32_direct_records = 0; gd.dense_backend = 1;
-    if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, gd)) return rc;
-    if (plan->D.active) return create_f32_dense_from_plan(hout, plan, rows1, cols1, batch, device);
-    cnl_plan_destroy(plan);
-    plan = nullptr;
-  }
-  if (o.float32_register_front) {
-    // ... or, tuning float32_register_front, with the register-front records of the condensed system: the call is the float
-    // condensation passes around ONE launch of the register-front kernel in float (solve_ldl!: of the general kernel, which
-    // reads the same panels).  Implies float32_condense.
-    if (!g.float32_condense) g.float32_condense = 1;
-    g.condense = 1; g.register_front = 1; g.direct_records = 0;
-    // ... or, tuning float32_direct_records on top, with DIRECT records: the kernel condenses on the fly from the caller's vals and
-    // the call is that one launch and the post-pass.  No lean or solve-only float instance exists, so the plan is not shaped for
-    // one (no row form forced on every front, no backward rows).
-    if (o.float32_direct_records) { g.direct_records = 1; g.lean_kernel = 0; g.rows_in_backward = 0; }
-  }
-  if (o.float32_general_dense) {
-    // ... or, tuning float32_general_dense, as ONE dense matrix: the analysis keeps the position of every slot of the condensed
-    // system wherever its order is 96 .. 4096 (plan->gpos), and the handle decides by the fronts and the batch
-    // (create_f32_general_from_plan).  Implies float32_condense.
-    if (!g.float32_condense) g.float32_condense = 1;
-    g.condense = 1; g.general_dense = 2;
-  }
-  if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, g)) return rc;
-  const bool direct_plan = plan->P.rec_direct;
-  if (int rc = create_f32_general_from_plan(hout, plan, rows1, cols1, batch, device)) return rc;
-  if (direct_plan && (*hout)->route != cnl::Route::Direct) {
-    // setup_v2 declined the direct records (their LDS block is the larger one): the handle is the one without the key
-    cnl_destroy(*hout);
-    *hout = nullptr;
-    g.direct_records = 0;
-    if (int rc = plan_create_impl(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, g)) return rc;
-    return create_f32_general_from_plan(hout, plan, rows1, cols1, batch, device);
-  }
-  return CNL_OK;
+  // tuning float32_general: the general multifrontal kernel in float, on the plan f32_general_plan makes of the options (capi_plan.cpp)
+  return create_f32_general(hout, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, o);
 }
 
 int cnl_destroy(cnl_handle* h) {
@@ -888,6 +923,7 @@ int cnl_destroy(cnl_handle* h) {
   cnl::dense_destroy(h->dense);
   cnl::dense_destroy(h->gdense);
   if (h->tail) { cnl_destroy(h->tail); h->tail = nullptr; (void)hipSetDevice(h->device); }
+  if (h->inner) { cnl_destroy(h->inner); h->inner = nullptr; (void)hipSetDevice(h->device); }
   if (h->aux_stream) { (void)hipStreamSynchronize(h->aux_stream); (void)hipStreamDestroy(h->aux_stream); }
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
@@ -919,6 +955,17 @@ int cnl_dataflow_timeouts(cnl_handle* h, int64_t* count) {
     if (rc) return rc;
     *count += tc;
   }
+  return CNL_OK;
+}
+
+int cnl_get_refine_norms(cnl_handle* h, double* norms, int64_t* steps) {
+  if (!h || !norms || !steps) return fail(CNL_ERR_ARG, "null argument");
+  if (!h->inner) return fail(CNL_ERR_STATE, "cnl_get_refine_norms: the handle was created without tuning float32_refine");
+  if (!h->r_norms_valid) return fail(CNL_ERR_STATE, "cnl_get_refine_norms before a cnl_newton_system or cnl_solve call of the handle");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(norms, h->r_norms, (size_t)h->full_batch * (size_t)h->refine_k * sizeof(double), hipMemcpyDeviceToHost));
+  *steps = h->refine_k;
   return CNL_OK;
 }
 
@@ -955,6 +1002,11 @@ int cnl_set_active_batch(cnl_handle* h, int64_t nb) {
   if (!h) return fail(CNL_ERR_ARG, "null handle");
   if (nb < 1 || nb > h->full_batch)
     return fail(CNL_ERR_ARG, "cnl_set_active_batch: nb = " + std::to_string(nb) + " is outside [1, " + std::to_string(h->full_batch) + "] (the created batch)");
+  if (h->inner) {   // a refined handle: its inner handle decides (the dense routes refuse), and both work on the same problems
+    if (int rc = cnl_set_active_batch(h->inner, nb)) return rc;
+    h->batch = nb;
+    return CNL_OK;
+  }
   if (nb == h->batch) return CNL_OK;
   const bool dense_route = h->route == cnl::Route::Dense || h->route == cnl::Route::GeneralDense;
   if (dense_route) return fail(CNL_ERR_STATE, "cnl_set_active_batch: this handle runs on the dense backend, which is sized by the created batch");
@@ -988,6 +1040,15 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms) {
 
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   if (!h || !cfg) return fail(CNL_ERR_ARG, "null argument");
+  if (h->inner) {
+    // a refined handle (tuning float32_refine): the words of its inner handle, as a Float64 handle (bit 27 clear) with bit 38 set and
+    // the refinement steps in bits 39 .. 41; row f1 (bit 7) is the outer handle's own
+    if (int rc = cnl_get_config(h->inner, cfg)) return rc;
+    cfg[5] &= ~(((int64_t)1 << 27) | (int64_t)128);
+    cfg[5] |= ((int64_t)1 << 38) | ((int64_t)h->refine_k << 39);
+    if (h->djt.rv_ntiles > 0) cfg[5] |= 128;
+    return CNL_OK;
+  }
   std::memset(cfg, 0, 8 * sizeof(int64_t));
   const bool on_band = h->route == cnl::Route::Band, dense_route = h->route == cnl::Route::Dense || h->route == cnl::Route::GeneralDense;
   if (h->f32 && on_band) {   // Float32 handle on the band kernels

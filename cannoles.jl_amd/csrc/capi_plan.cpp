@@ -69,6 +69,15 @@ int resolve_options(const cnl_options* in, cnl::Tuning& out) {
   if (!err.empty()) return fail(CNL_ERR_ARG, err);
   if (out.band_pieces != 0 && out.band_pieces != cnl::BAND_NPIECE && out.band_pieces != cnl::BAND_NPIECE_WIDE)
     return fail(CNL_ERR_ARG, "cnl_options.tuning: band_pieces must be 0 (automatic), 15 or 20");
+  if (out.float32_refine < 0 || out.float32_refine > 4)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: float32_refine is the number of refinement steps, 0 (none) .. 4");
+  if (out.float32_refine && !out.float32_general)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: float32_refine needs float32_general = 1 (the refined handle owns a Float32 general handle, which keeps a factor; "
+                             "the band kernels keep none)");
+  if (out.float32_refine && out.batch_layout == CNL_LAYOUT_INTERLEAVED)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: float32_refine takes problem-major arrays: batch_layout = CNL_LAYOUT_INTERLEAVED is the band kernels' layout");
+  if (out.refine_rows < 0 || out.refine_rows > 2)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: refine_rows is 0 (by the pattern), 1 (a row per lane) or 2 (a row per wavefront)");
   return CNL_OK;
 }
 
@@ -220,8 +229,68 @@ int plan_create_impl(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* row
     p->perm_outer = p->P.perm;
   }
   lap("band program + done");
+  p->pat_rows.resize((size_t)nnz); p->pat_cols.resize((size_t)nnz);   // (validated by the analysis: every index is inside [1, N])
+  for (int64_t e = 0; e < nnz; e++) { p->pat_rows[e] = (int32_t)(rows1[e] - 1); p->pat_cols[e] = (int32_t)(cols1[e] - 1); }
   *plan = p;
   return CNL_OK;
+}
+
+const cnl::KktRows& kkt_rows(const cnl_plan* plan) {
+  std::call_once(plan->kkt_once, [&] { cnl::build_kkt_rows(plan->kkt, plan->N, plan->nnz, plan->pat_rows.data(), plan->pat_cols.data()); });
+  return plan->kkt;
+}
+
+int check_f32_options(const cnl::Tuning& o, const char* fn) {
+  const std::string f(fn);
+  if (o.float32_dense && !o.float32_general)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_dense = 1 needs float32_general = 1 (the dense backend in float serves Float32 general handles)");
+  if (o.float32_general_dense && !o.float32_general)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_general_dense needs float32_general = 1 (the general form of the dense backend in float serves Float32 general handles)");
+  if (o.float32_general_dense < 0 || o.float32_general_dense > 2)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_general_dense is 0, 1 (plans with a front above order 64) or 2 (wherever the order and the batch allow)");
+  return CNL_OK;
+}
+
+int f32_general_plan(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ, int64_t ncon,
+                     const cnl::Tuning& o, cnl::Tuning* used) {
+  // The throughput analysis with nothing but the general kernel to run, whatever the caller's options say: no condensation (a call
+  // is then the one classic launch) unless tuning float32_condense asks for it (the call is then that launch between the float
+  // condensation passes), no register-front records, no dense routes, no staged execution, no band program.
+  cnl::Tuning g = o;
+  g.condense = o.float32_condense ? 1 : 0; g.register_front = 0; g.dense_backend = 0; g.general_dense = 0; g.staged = 0; g.band_kernel = 0;
+  // (a dense residual block holds nvar * nequ Jacobian entries, nequ diagonal entries and the nvar rho slots at least: a pattern
+  //  with fewer entries is not analysed a second time for the question)
+  if (o.float32_dense && o.dense_backend && nequ > 0 && nnz / nequ >= nvar) {
+    // tuning float32_dense: a dense residual block goes to the dense backend in float, whatever the batch (as a Float64 handle's
+    // does).  The uncondensed analysis runs detect_dense on the validated pattern; a pattern it does not accept — and every pattern
+    // with cnl_options.dense_backend = 0 — goes on to exactly the handle it gets without the key.
+    cnl::Tuning gd = g;
+    gd.condense = 0; gd.float32_condense = 0; gd.float32_register_front = 0; gd.float32_direct_records = 0; gd.dense_backend = 1;
+    if (int rc = plan_create_impl(plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, gd)) return rc;
+    if ((*plan)->D.active) { if (used) *used = gd; return CNL_OK; }
+    cnl_plan_destroy(*plan);
+    *plan = nullptr;
+  }
+  if (o.float32_register_front) {
+    // ... or, tuning float32_register_front, with the register-front records of the condensed system: the call is the float
+    // condensation passes around ONE launch of the register-front kernel in float (solve_ldl!: of the general kernel, which
+    // reads the same panels).  Implies float32_condense.
+    if (!g.float32_condense) g.float32_condense = 1;
+    g.condense = 1; g.register_front = 1; g.direct_records = 0;
+    // ... or, tuning float32_direct_records on top, with DIRECT records: the kernel condenses on the fly from the caller's vals and
+    // the call is that one launch and the post-pass.  No lean or solve-only float instance exists, so the plan is not shaped for
+    // one (no row form forced on every front, no backward rows).
+    if (o.float32_direct_records) { g.direct_records = 1; g.lean_kernel = 0; g.rows_in_backward = 0; }
+  }
+  if (o.float32_general_dense) {
+    // ... or, tuning float32_general_dense, as ONE dense matrix: the analysis keeps the position of every slot of the condensed
+    // system wherever its order is 96 .. 4096 (plan->gpos), and the handle decides by the fronts and the batch
+    // (create_f32_general_from_plan).  Implies float32_condense.
+    if (!g.float32_condense) g.float32_condense = 1;
+    g.condense = 1; g.general_dense = 2;
+  }
+  if (used) *used = g;
+  return plan_create_impl(plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 0, 0, 0, g);
 }
 
 int plan_create_tuned(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar,
@@ -272,7 +341,9 @@ const char* cnl_last_error(void) { return g_err.c_str(); }
 // 0.4.2: tuning float32_direct_records (Float32 general handles on the Direct route), cnl_get_config bits 36 / 37, no new symbol
 // 0.4.3: tuning float32_dense (Float32 general handles with a dense residual block on the dense backend in float), no new symbol
 // 0.4.4: tuning float32_general_dense (Float32 general handles with large fronts on the general form of the dense backend in float), no new symbol
-int32_t cnl_version(void) { return 404; }
+// 0.5.0: tuning float32_refine (Float64 handles on a Float32 factor, refined with a Float64 residual), cnl_kkt_residual_dev,
+//        cnl_get_refine_norms, cnl_plan_get "kkt_row_*", cnl_get_config bits 38 .. 41
+int32_t cnl_version(void) { return 500; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62
@@ -320,6 +391,11 @@ int cnl_plan_create_ex(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* r
   cnl::Tuning o;
   int rc = resolve_options(opt, o);
   if (rc) return rc;
+  if (o.float32_refine) {   // the plan of the refined handle is its inner Float32 general handle's
+    if ((rc = check_f32_options(o, "cnl_plan_create_ex"))) return rc;
+    if (!plan) return fail(CNL_ERR_ARG, "null argument");
+    return f32_general_plan(plan, N, nnz, rows1, cols1, nvar, nequ, ncon, o);
+  }
   return plan_create_tuned(plan, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, o);
 }
 
@@ -376,6 +452,10 @@ int cnl_plan_get(const cnl_plan* plan, const char* name, int32_t* out, int64_t* 
   else if (s == "r_ptr") { src = C.r_ptr.data(); n = (int64_t)C.r_ptr.size(); }
   else if (s == "r_jsrc") { src = C.r_jsrc.data(); n = (int64_t)C.r_jsrc.size(); }
   else if (s == "r_jx") { src = C.r_jx.data(); n = (int64_t)C.r_jx.size(); }
+  // rows of the full symmetric matrix (refine.h: KktRows), built on first request
+  else if (s == "kkt_row_ptr") { const cnl::KktRows& R = kkt_rows(plan); src = R.ptr.data(); n = (int64_t)R.ptr.size(); }
+  else if (s == "kkt_row_slot") { const cnl::KktRows& R = kkt_rows(plan); src = R.slot.data(); n = (int64_t)R.slot.size(); }
+  else if (s == "kkt_row_col") { const cnl::KktRows& R = kkt_rows(plan); src = R.col.data(); n = (int64_t)R.col.size(); }
   else if (s == "cond_info") {
     // which condense kernel serves the plan (kernels_aux.hip): {1 the LDS-tiled kernel / 0 the plain slot kernel, largest tile in
     // elements, largest contribution and slot count of a chunk, chunks}; empty where the plan is not condensed

@@ -370,9 +370,83 @@ cnl::RouteFacts route_facts(const cnl_handle* h) {
 
 }  // namespace
 
+namespace {
+
+hipError_t residual_step(cnl_handle* h, const double* vals, const double* rhs, const double* d, int j, hipStream_t stream) {
+  return cnl::launch_kkt_residual(h->dkkt, vals, rhs, d, h->r_rhs, h->r_norms + j, h->refine_k, h->r_success, (int)h->batch, stream);
+}
+
+// One call of a refined handle (tuning float32_refine; handle.h: cnl_handle::inner), everything on the caller's stream and nothing
+// read back: the inputs demoted into the handle's float arrays, the call of the inner Float32 handle — the rho ladder, nfact and
+// success are its own —, the results widened, then k times  g = rhs + K d  (Float64 data, written as float into the inner
+// right-hand side)  ->  e = inner solve(g)  ->  d += e  where the problem holds a factor.
+// eig_tol of the inner factorisation is max((float)eig_tol, eps(Float32)): a pivot below Float32 rounding is noise in a Float32
+// factor — the one deliberate deviation in decisions from a Float64 handle.
+int run_refined(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream) {
+  cnl_handle* in = h->inner;
+  const int64_t B = h->batch, N = h->plan->N, nnz = h->plan->nnz;
+  if (a.skip_done || a.only_if_status || (a.mode == cnl::MODE_NEWTON && !d_rhs))
+    return fail(CNL_ERR_STATE, "this call is not served by a refined handle (tuning float32_refine)");
+  if (a.mode == cnl::MODE_SOLVE && !h->last_vals) return fail(CNL_ERR_STATE, "cnl_solve before cnl_factorize");
+  if (in->batch != B) return fail(CNL_ERR_STATE, "refined handle: the inner handle works on another batch");
+  const double* vals = static_cast<const double*>(a.mode == cnl::MODE_SOLVE ? h->last_vals : d_vals);
+  const double* rhs = static_cast<const double*>(d_rhs);
+  double* d = static_cast<double*>(d_d);
+  auto hip = [](hipError_t e, const char* what) { return e == hipSuccess ? CNL_OK : fail(CNL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
+  int rc;
+  if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
+  if (a.mode != cnl::MODE_SOLVE && (rc = hip(cnl::launch_refine_demote(vals, h->r_vals, B * nnz, stream), "refine_demote"))) return rc;
+  if (a.mode != cnl::MODE_FACTOR && (rc = hip(cnl::launch_refine_demote(rhs, h->r_rhs, B * N, stream), "refine_demote"))) return rc;
+  float p32[9] = {};
+  const int np = a.mode == cnl::MODE_NEWTON ? 9 : a.mode == cnl::MODE_FACTOR ? 1 : 0;
+  for (int k = 0; k < np; k++) p32[k] = (float)a.params[k];
+  if (np) p32[0] = std::max(p32[0], FLT_EPSILON);
+  if (a.mode == cnl::MODE_NEWTON) {
+    if ((rc = hip(cnl::launch_refine_demote(static_cast<const double*>(a.rho_old), h->r_rho_old, B, stream), "refine_demote"))) return rc;
+    if ((rc = cnl_newton_system_f32_dev(in, h->r_vals, h->r_rhs, h->r_e, h->r_rho_old, h->r_rho, a.nfact, a.success, p32, stream))) return rc;
+    if ((rc = hip(cnl::launch_refine_widen_rho(h->r_rho, h->r_rho_old, static_cast<double*>(a.rho), static_cast<double*>(a.rho_old), h->r_vals,
+                                               static_cast<double*>(d_vals), nnz, (int)h->plan->nvar, a.nfact, (int)B, stream), "refine_widen_rho"))) return rc;
+  } else if (a.mode == cnl::MODE_FACTOR) {
+    // (the inertia counts of a host-pointer try_to_factorize: straight through run(), as factorize_impl<float> asks for them)
+    cnl::LaunchArgs f{};
+    f.mode = cnl::MODE_FACTOR; f.success = a.success; f.npos = a.npos; f.nzero = a.nzero; f.params[0] = p32[0];
+    HIPCHK(hipSetDevice(in->device));
+    if ((rc = run(in, f, h->r_vals, nullptr, nullptr, stream))) return rc;
+    in->factorized = true; in->factor_batch = in->batch; in->last_vals = h->r_vals; in->last_ok.clear();
+  } else {
+    if ((rc = cnl_solve_f32_dev(in, h->r_rhs, h->r_e, stream))) return rc;
+  }
+  if (a.mode != cnl::MODE_SOLVE) {
+    HIPCHK(hipMemcpyAsync(h->r_success, a.success, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+    h->last_vals = d_vals;
+  }
+  if (a.mode != cnl::MODE_FACTOR) {
+    if ((rc = hip(cnl::launch_refine_update(d, h->r_e, h->r_success, (int)N, (int)B, 1, stream), "refine_update"))) return rc;
+    for (int j = 0; j < h->refine_k; j++) {
+      if ((rc = hip(residual_step(h, vals, rhs, d, j, stream), "kkt_residual"))) return rc;
+      if ((rc = cnl_solve_f32_dev(in, h->r_rhs, h->r_e, stream))) return rc;
+      if ((rc = hip(cnl::launch_refine_update(d, h->r_e, h->r_success, (int)N, (int)B, 0, stream), "refine_update"))) return rc;
+    }
+    h->r_norms_valid = true;
+  }
+  return end_timed(h, stream);
+}
+
+}  // namespace
+
+// cnl_kkt_residual_dev: the residual kernel on its own, on any Float64 handle with problem-major vals
+int kkt_residual(cnl_handle* h, const double* d_vals, const double* d_rhs, const double* d_d, double* d_g, double* d_norms, hipStream_t stream) {
+  if (int rc = ensure_kkt_rows(h)) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  const hipError_t e = cnl::launch_kkt_residual(h->dkkt, d_vals, d_rhs, d_d, d_g, d_norms, 1, nullptr, (int)h->batch, stream);
+  if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("kkt_residual: ") + hipGetErrorString(e));
+  return CNL_OK;
+}
+
 // One call of the path on device-resident data.  A split batch comes back here part by part; the rule of last_vals — the solve
 // uses the values of the last factorisation — is checked and kept here for every route (call_shape.h: needs / sets).
 int run(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream, RunOpts o) {
+  if (h->inner) return run_refined(h, a, d_vals, d_rhs, d_d, stream);   // (no route of call_shape.h: a sequence of calls of the inner handle)
   const cnl::CallShape S = cnl::call_shape(route_facts(h), a.mode);
   int rc;
   if (h->split_staged > 0 && !o.part_of_split && (h->staged || h->tail) && h->split_staged < h->batch) rc = run_split(h, a, d_vals, d_rhs, d_d, stream, o);

@@ -26,6 +26,7 @@
 #include "kernels.h"
 #include "options.h"
 #include "plan.h"
+#include "refine.h"
 
 struct cnl_plan {
   cnl::Cond C;   // static condensation of the residual block (outer -> condensed system)
@@ -52,6 +53,11 @@ struct cnl_plan {
   // beside it unless tuning band_resident = 0; runs the Float64 handles of 32 problems per workgroup with interleaved `vals`
   BandSlot band_res;
   std::vector<int32_t> band_mov_info;   // "bandm_info": summary of band_res.B's mover table (band.h, BAND_MK_*)
+  // the validated COO pattern, 0-based, and — built on first request (kkt_rows(), below) — the rows of the full symmetric matrix
+  // (refine.h): what cnl_kkt_residual_dev and the refinement of a float32_refine handle gather along; cnl_plan_get "kkt_row_*"
+  std::vector<int32_t> pat_rows, pat_cols;
+  mutable std::once_flag kkt_once;
+  mutable cnl::KktRows kkt;
 };
 
 struct cnl_handle {
@@ -164,6 +170,20 @@ struct cnl_handle {
   // the float32_condense handle plus `gdense`, a FLOAT state of the general form, and gops: route GeneralDense, a call is the float
   // condensation passes around the dense LDL^T of the condensed system (execute dispatches on f32).
   bool f32_general = false;
+  // the rows of the full KKT matrix on the device (refine.h), uploaded on first use: cnl_kkt_residual_dev, refined calls
+  cnl::DevKktRows dkkt{};
+  // Tuning float32_refine = k (cnl_create_ex): a Float64 handle (f32 == false) that owns an INNER Float32 general handle — made by the
+  // code behind cnl_create_f32_ex from the caller's options, band_kernel forced to 0 — and shares its plan.  Of the device state above
+  // it has the row lists (djt, dkkt) and the staging of the host-pointer calls alone; run() hands every call to run_refined
+  // (capi_run.cpp): demote -> the inner handle's call -> widen -> k times [residual in Float64 -> inner solve -> update].
+  // last_vals is the caller's FLOAT64 array of the last factorisation: the residual of a later solve_ldl! reads it.
+  cnl_handle* inner = nullptr;
+  int refine_k = 0;
+  float *r_vals = nullptr, *r_rhs = nullptr, *r_e = nullptr;   // [batch][nnz], [batch][N] (right-hand side, then every residual), [batch][N] (d32, then every correction)
+  float *r_rho = nullptr, *r_rho_old = nullptr;                // [batch]
+  int32_t* r_success = nullptr;                                // [batch] flags of the last factorisation: the mask of every refinement kernel
+  double* r_norms = nullptr;                                   // [batch][k] (cnl_get_refine_norms)
+  bool r_norms_valid = false;                                  // a NEWTON or SOLVE call has written r_norms
   size_t esz() const { return f32 ? sizeof(float) : sizeof(double); }   // bytes per element of every element array of the handle
 };
 
@@ -274,7 +294,16 @@ void build_band_programs(cnl_plan* p, const int64_t* rows1, const int64_t* cols1
 void band_summaries(cnl_plan* p);
 const cnl::BandPlan& band_program(const cnl_plan* plan, bool f32);
 
+const cnl::KktRows& kkt_rows(const cnl_plan* plan);   // built on first request
+// the plan of a Float32 general handle off the band kernels (what cnl_create_f32_ex analyses behind tuning float32_general): the
+// uncondensed throughput analysis, or what float32_condense / _register_front / _direct_records / _dense / _general_dense make of it
+int f32_general_plan(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ, int64_t ncon,
+                     const cnl::Tuning& o, cnl::Tuning* used = nullptr);
+// what every creator checks of the float32_* keys (fn: the creator's name, for the message)
+int check_f32_options(const cnl::Tuning& o, const char* fn);
+
 // ---- capi_handle.cpp ----
+int ensure_kkt_rows(cnl_handle* h);   // h->dkkt on the device
 int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device);
 
 // ---- capi_run.cpp ----
@@ -284,6 +313,7 @@ struct RunOpts {
   bool part_of_split = false;       // the call is one part of a split batch (run_split): it is not split again
 };
 int run(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream, RunOpts o = {});
+int kkt_residual(cnl_handle* h, const double* d_vals, const double* d_rhs, const double* d_d, double* d_g, double* d_norms, hipStream_t stream);
 
 // no timing (cnl_set_timing) of the launches enqueued while this lives: they are part of a call that is timed as a whole, or not at all
 struct TimingOff {

@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "cnl_outer_begin_ex_dev", "cnl_outer_trial_done_ex_dev", "cnl_outer_ls_test_ex_dev", "cnl_outer_end_ex_dev", "cnl_outer_hess_mask_dev",
     "cnl_outer_begin_ex_f32_dev", "cnl_outer_trial_done_ex_f32_dev", "cnl_outer_ls_test_ex_f32_dev", "cnl_outer_end_ex_f32_dev",
     "cnl_outer_hess_mask_f32_dev",
+    "cnl_kkt_residual_dev", "cnl_get_refine_norms",
 ]
 
 # status codes of the lockstep loop's `status` array (include/cannoles_hip.h, row f3); 7 is set by the caller, never by a kernel
@@ -246,6 +247,8 @@ def lib():
         L.cnl_newton_system_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cnl_residual_vectors_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cnl_trial_point_dev.argtypes = [vp, vp, vp, vp, vp, dbl, vp, vp, vp, vp, vp]
+        L.cnl_kkt_residual_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.cnl_get_refine_norms.argtypes = [vp, vp, C.POINTER(i64)]
         L.cnl_prepare_newton_system_dev.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]
         L.cnl_cgls_multipliers_dev.argtypes = [vp, vp, vp, vp, vp, dbl, dbl, i64, C.c_int, vp, vp]
         L.cnl_multi_create.argtypes = [C.POINTER(vp), i64, i64, _i64p, _i64p, i64, i64, i64, i64, vp, C.c_int]
@@ -420,7 +423,17 @@ class HIPLDLStruct:
     whatever the fronts; every other pattern gets the handle it gets without the key, and the key without float32_general is
     CNL_ERR_ARG.  A condensed or direct
     handle of either kind reads the Jacobian values of `vals` again in solve_ldl!: the array given to try_to_factorize must stay alive
-    and unmodified until the last solve on that factor."""
+    and unmodified until the last solve on that factor.
+
+    Mixed precision: HIPLDLStruct(..., dtype=float64, options=Options(float32_general=1, ..., float32_refine=k)), k = 1 .. 4, is a
+    FLOAT64 handle (config["float32"] False, config["refine"] == k) on a Float32 factor: it owns the Float32 general handle the other
+    float32_* keys select (band kernels never: they keep no factor), and config["kernel"], config["direct"] and info["ncond"]
+    describe that inner handle.  A call factorises the demoted values in float — the rho ladder, nfact and success are the Float32
+    handle's, with eig_tol raised to eps(Float32) at least — and corrects d k times with a Float64 residual rhs + K d
+    (kkt_residual_dev is that kernel on its own) and a solve on the kept factor; refine_norms(LDLT) returns the residual norms in
+    front of each correction, which do not fall where the system is too ill-conditioned for a Float32 factor.  solve_ldl! reads the
+    `vals` of the last factorisation again: the rule above binds this handle too.  float32_refine without float32_general, k outside
+    0 .. 4, the key on a float32 handle or a MultiHIPLDLStruct, and batch_layout=LAYOUT_INTERLEAVED are CNL_ERR_ARG."""
 
     def __init__(self, N, rows, cols, vals, nvar=None, nequ=None, ncon=None, batch=1, device=0, options=None, dtype=np.float64):
         self.N = int(N)
@@ -456,7 +469,8 @@ class HIPLDLStruct:
                        "band_mover_table": bool((int(cfg[5]) >> 34) & 1), "cond_resident": bool((int(cfg[5]) >> 35) & 1),
                        "batch_layout": (int(cfg[5]) >> 25) & 1, "rhs_interleaved": bool((int(cfg[5]) >> 26) & 1),
                        "float32": bool((int(cfg[5]) >> 27) & 1), "band_pieces": (int(cfg[5]) >> 28) & 63,
-                       "direct": bool((int(cfg[5]) >> 36) & 1), "v2_solve": bool((int(cfg[5]) >> 37) & 1)}
+                       "direct": bool((int(cfg[5]) >> 36) & 1), "v2_solve": bool((int(cfg[5]) >> 37) & 1),
+                       "refine": (int(cfg[5]) >> 39) & 7 if (int(cfg[5]) >> 38) & 1 else 0}
         if self.config["float32"] and self.config["band"]:   # (a Float32 handle off the band kernels — tuning float32_general — is "v1")
             self.config["kernel"] = "band"
 
@@ -646,6 +660,25 @@ def residual_vectors_dev(LDLT, vals_ptr, r_ptr, lambda_ptr, Fx_ptr, cx_ptr, rhs_
     norms_ptr receives [batch][2] values."""
     fn = lib().cnl_residual_vectors_f32_dev if _is_f32(LDLT) else lib().cnl_residual_vectors_dev
     _check(fn(LDLT._h, *(_dev_ptr(LDLT, x) for x in (vals_ptr, r_ptr, lambda_ptr, Fx_ptr, cx_ptr, rhs_ptr, norms_ptr)), stream))
+
+
+def kkt_residual_dev(LDLT, vals_ptr, rhs_ptr, d_ptr, g_ptr, norms_ptr, stream=0):
+    """g = rhs + K(vals) d and norms = max |g| per problem, in Float64 on device-resident arrays (cnl_kkt_residual_dev): the residual
+    of the Newton system, K the full symmetric matrix of the pattern with the rho slots as they stand in vals.  Float64 handles with
+    problem-major vals; norms_ptr may be None.  Deterministic: two calls give the same bits."""
+    v, r, d, g = (_dev_ptr(LDLT, x) for x in (vals_ptr, rhs_ptr, d_ptr, g_ptr))
+    _check(lib().cnl_kkt_residual_dev(LDLT._h, v, r, d, g, None if norms_ptr is None else _dev_ptr(LDLT, norms_ptr), stream))
+
+
+def refine_norms(LDLT):
+    """[batch][k] residual norms max |rhs + K d_j| in front of correction j of the handle's last newton_system! / solve_ldl! call
+    (cnl_get_refine_norms; d_0 is the raw Float32 solution, -1 marks a problem without a factor).  Synchronises the device.
+    CnlError code 5 on a handle made without float32_refine."""
+    k = max(1, int(LDLT.config.get("refine", 0)))
+    out = np.full((LDLT.batch, k), np.nan)
+    steps = C.c_int64(0)
+    _check(lib().cnl_get_refine_norms(LDLT._h, out.ctypes.data, C.byref(steps)))
+    return out[:, :int(steps.value)]
 
 
 def residual_vectors_jac_dev(LDLT, nnzjF, nnzjc, Jx_ptr, Jcx_ptr, r_ptr, lambda_ptr, Fx_ptr, cx_ptr, rhs_ptr, norms_ptr, stream=0):

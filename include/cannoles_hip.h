@@ -60,7 +60,9 @@ const char* cnl_last_error(void);
 /* library / ABI version: major*10000 + minor*100 + patch (0.3.0: cnl_set_active_batch, cnl_outer_compact_dev;
  * 0.3.1: tuning "float32_general", no new symbol; 0.4.0: cnl_outer_ctl, the cnl_outer_*_ex_dev entry points, cnl_outer_hess_mask_dev;
  * 0.4.1: tuning "float32_register_front", no new symbol; 0.4.2: tuning "float32_direct_records", cnl_get_config bits 36 / 37, no new
- * symbol; 0.4.3: tuning "float32_dense", no new symbol; 0.4.4: tuning "float32_general_dense", no new symbol) */
+ * symbol; 0.4.3: tuning "float32_dense", no new symbol; 0.4.4: tuning "float32_general_dense", no new symbol;
+ * 0.5.0: tuning "float32_refine" / "refine_rows", cnl_kkt_residual_dev, cnl_get_refine_norms, cnl_plan_get "kkt_row_*",
+ * cnl_get_config bits 38 .. 41) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -203,6 +205,8 @@ int cnl_newton_system(cnl_handle* h, double* vals, const double* rhs, double* d,
 /* Device-resident twins.  d_vals/d_rhs/d_d are device pointers with the layouts above.
  * d_rho_old is read and updated in place (rho_old_out); d_rho, d_nfact, d_success are outputs. */
 int cnl_factorize_dev(cnl_handle* h, const double* d_vals, double eig_tol, int32_t* d_success, void* stream);
+/* (cnl_solve_dev on a handle made with tuning "float32_refine" — below — reads the d_vals of the last factorisation again, for its
+ *  Float64 residuals: they must stay alive and UNMODIFIED until the last cnl_solve_dev on that factor.) */
 int cnl_solve_dev(cnl_handle* h, const double* d_rhs, double* d_d, void* stream);
 int cnl_newton_system_dev(cnl_handle* h, double* d_vals, const double* d_rhs, double* d_d, double* d_rho_old,
                           double* d_rho, int32_t* d_nfact, int32_t* d_success, const double params[9], void* stream);
@@ -261,6 +265,17 @@ int cnl_cgls_multipliers_dev(cnl_handle* h, const double* d_vals, const double* 
 /* cnl_trial_point_dev: the extrapolation step's trial point, src/CaNNOLeS.jl:654,661-668:
  *     xt = x + d[1:n],  rt = r + d[n+1:n+m],  dlambda = -d[n+m+1:N], scaled by max_dlambda/||dlambda||_2 when that
  *     norm exceeds max_dlambda (the reference uses 1e4),  lambdat = lambda + dlambda.                               */
+/* cnl_kkt_residual_dev: g[b] = rhs[b] + K(vals[b]) d[b] and norms[b] = max_i |g[b][i]| for the problems the handle works on — the
+ *   residual of the Newton system, K the symmetric matrix of the lower-triangular COO pattern (duplicates summed, strict-lower entries
+ *   mirrored, the rho slots read as they stand in vals).  The only way a device-resident caller can check a Newton step without
+ *   leaving the device.  Any Float64 handle with problem-major vals (batch_layout = CNL_LAYOUT_INTERLEAVED: CNL_ERR_STATE).  Sums run
+ *   in double along the rows of the full matrix (cnl_plan_get "kkt_row_ptr" / "kkt_row_slot" / "kkt_row_col": for every row its
+ *   (slot, column) pairs in ascending slot order; built and uploaded on first use), without atomics: two calls give the same bits.
+ *   d_g [batch][N] must not overlap an input; d_norms [batch] may be null.  Tuning "refine_rows" (0 by the pattern, 1 a row per
+ *   lane, 2 a row per wavefront) picks the kernel instance. */
+int cnl_kkt_residual_dev(cnl_handle* h, const double* d_vals, const double* d_rhs, const double* d_d, double* d_g, double* d_norms,
+                         void* stream);
+
 int cnl_trial_point_dev(cnl_handle* h, const double* d_x, const double* d_r, const double* d_lambda, const double* d_d,
                         double max_dlambda, double* d_xt, double* d_rt, double* d_lambdat, double* d_dlambda, void* stream);
 
@@ -414,6 +429,7 @@ int cnl_outer_compact_dev(const cnl_outer_state* st, int64_t nextra, void* const
  *   halves, concurrent parts), the dense backend.  cnl_multi has no counterpart.
  *   While nb is below the created batch the host-pointer entry points return CNL_ERR_STATE (they take the whole batch's arrays), and
  *   cnl_solve*_dev needs a last factorisation that covered at least nb problems (CNL_ERR_STATE otherwise).                        */
+/*   (A refined handle — tuning "float32_refine" — forwards to its inner handle and returns its answer.) */
 int cnl_set_active_batch(cnl_handle* h, int64_t nb);
 int cnl_get_active_batch(const cnl_handle* h, int64_t* nb);
 
@@ -440,6 +456,8 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  *   stand-alone condensation pass in front of the launch), either element type,
  * bit 37 = ... and cnl_solve* runs on the register-front kernel too (every front of the fast class). */
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
+/* (bit 38 = a refined handle — tuning "float32_refine", below —, bits 39-41 = its refinement steps k; every other word and bit
+ *  describes its inner Float32 handle, with bit 27 clear: the handle is a Float64 handle.) */
 /* ([5] + (1 << 27) on a Float32 handle.  On the band kernels: bits 7-26 as above, cfg[0..4], [6], [7] are 0.  On the general kernel
  *  (tuning "float32_general=1"): cfg[0..4] describe that kernel's float instance as they do for a Float64 handle — [2] counts 4-byte
  *  elements — and [5] = 1 + (1 << 27) with bit 6 clear (+ 128 as above; + (1 << 35) where tuning "float32_condense=1" has the
@@ -538,6 +556,31 @@ int cnl_launch_counts(int64_t counts[3]);
  * and an `_f32` entry point on a Float64 handle.  cnl_layout_len counts elements, so it serves both types.
  *   cnl_default_params_f32: ParamCaNNOLeS(Float32), src/CaNNOLeS.jl:48-62, in the order of cnl_default_params.       */
 void cnl_default_params_f32(float params[9]);
+
+/* ---- Float64 handles on a Float32 factor: tuning "float32_refine=k" (k = 1 .. 4; default 0; only with "float32_general=1") ----
+ * Read by cnl_create_ex and cnl_plan_create_ex.  cnl_create_ex then returns a FLOAT64 handle — every Float64 entry point takes it,
+ * every _f32 entry point refuses it (CNL_ERR_STATE) — that owns an inner Float32 general handle, made as cnl_create_f32_ex makes it
+ * from the same options with band_kernel forced to 0: "float32_condense", "float32_register_front", "float32_direct_records",
+ * "float32_dense" and "float32_general_dense" choose the inner route as they do there.  cnl_get_plan returns the inner handle's plan.
+ * A call demotes its inputs to float (a value beyond FLT_MAX becomes inf, and the Float32 factorisation then reports success = 0 for
+ * that problem), runs the inner handle's call — the rho ladder, nfact and success are the Float32 handle's; rho and rho_old come back
+ * widened, and the rho tail of the caller's Float64 vals receives the widened rho where the ladder wrote it —, and then corrects d
+ * k times:  g = rhs + K d  in Float64 (cnl_kkt_residual_dev's kernel, g written as float),  e = the inner solve of g,  d += e.
+ * Everything is enqueued on the caller's stream; nothing is read back.  d is written where success != 0 only.
+ *   The one deliberate deviation in decisions from a Float64 handle: eig_tol of the inner factorisation is
+ * max((float)eig_tol, eps(Float32)) — a pivot below Float32 rounding is noise in a Float32 factor.
+ *   CONTRACT: cnl_solve* refines against the vals of the last factorisation: the d_vals given to cnl_factorize_dev /
+ * cnl_newton_system_dev must stay alive and unmodified until the last cnl_solve_dev on that factor (host-pointer calls: the handle's
+ * own staged copy).
+ *   Refused, CNL_ERR_ARG: the key without "float32_general=1"; k outside 0 .. 4; the key at cnl_create_f32_ex or cnl_multi_create_ex;
+ * batch_layout = CNL_LAYOUT_INTERLEAVED.  The host-pointer entry points are the device entries behind an upload (no pipelined, pinned
+ * or host-ladder route).  Measured standing: README, DESIGN section 9.7 — opt-in.
+ *   cnl_get_refine_norms: norms[b * k + j] = max_i |rhs + K d_j|_i in front of correction j of the handle's last cnl_newton_system* or
+ * cnl_solve* call (d_0: the raw Float32 solution; [created batch][k] doubles), -1 for a problem without a factor; *steps = k.
+ * Synchronises the device, as cnl_dataflow_timeouts does.  A system too ill-conditioned for a Float32 factor shows here as norms
+ * that do not fall.  CNL_ERR_STATE on a handle without the key, and before the first such call. */
+int cnl_get_refine_norms(cnl_handle* h, double* norms, int64_t* steps);
+
 int cnl_create_f32(cnl_handle** h, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1,
                    int64_t nvar, int64_t nequ, int64_t ncon, int64_t batch, int device);
 int cnl_create_f32_ex(cnl_handle** h, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1,
