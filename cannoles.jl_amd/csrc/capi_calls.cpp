@@ -546,7 +546,9 @@ int newton_dense_host_ladder(cnl_handle* h, double* vals, const double* rhs, dou
 // any_device_ladder: also where the in-kernel ladder is available (the chunked call: its chunks run on views, which have none)
 bool host_ladder_serves(const cnl_handle* h, bool any_device_ladder) {
   const cnl::Plan& P = h->plan->P;
-  return h->staged && !h->dense && !h->gdense && h->plan->opt.host_ladder != 0 && h->use_v2 && P.rec_direct && P.d_outer &&
+  // (a staged Float32 handle — tuning float32_staged — is never claimed: its host-pointer calls take the plain route over the float
+  //  staging, and the routes below stage Float64 arrays)
+  return !h->f32 && h->staged && !h->dense && !h->gdense && h->plan->opt.host_ladder != 0 && h->use_v2 && P.rec_direct && P.d_outer &&
          (any_device_ladder || h->lad_mode == 0 || h->split_staged > 0);
 }
 // The first attempt of the whole staged batch, as both routes below begin: inputs up, one call of run() — on a handle the host

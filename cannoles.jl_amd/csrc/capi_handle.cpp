@@ -81,16 +81,18 @@ int choose_config(cnl_handle* h) {
 
 // The register-front kernel for a handle of either element type.  A Float32 general handle (tuning float32_register_front) is
 // asked with its 4-byte elements: every size "in doubles" of DevPlan2 then counts floats, the wavefront's LDS block and the global
-// scratch are sized in floats, and the 32-bit byte offsets of the kernel reach twice as many elements.  Its plan has no tasks and
-// no dense route, so the staged state and lean stay off; direct records only with tuning float32_direct_records, and then
-// v2_solve by the Float64 rule.
+// scratch are sized in floats, and the 32-bit byte offsets of the kernel reach twice as many elements.  Its plan has no dense route
+// and lean stays off; direct records only with tuning float32_direct_records, and then v2_solve by the Float64 rule (DESIGN section
+// 9.4); tasks, and with them the staged state, only with tuning float32_staged.
 int setup_v2(cnl_handle* h) {
   const cnl::Plan& P = h->plan->P;
   h->use_v2 = false;
   const cnl::Tuning& o = h->plan->opt;
   const size_t esz = h->esz();
   if (!P.v2_ok || !o.register_front) return CNL_OK;
-  if (h->f32 && !P.tasks.empty()) return CNL_OK;   // (not what cnl_create_f32_ex builds: the float kernel has no staged instance)
+  // (a float plan with tasks is the latency plan of tuning float32_staged, f32_general_plan: staged below by the Float64 conditions, one
+  //  launch per stage — the float kernel has staged instances, no dataflow, fused or lean one)
+  if (h->f32 && !P.tasks.empty() && !o.float32_staged) return CNL_OK;
   if (!h->f32 && !h->plan->gpos.empty() && (o.general_dense == 2 || (h->plan->prefer_dense && h->batch <= 16))) return CNL_OK;  // the dense route (capi_plan.cpp, plan_create_impl); 2: wherever it is possible
   cnl::DevPlan2& d = h->dp2;
   // streams are over-read by the prefetcher: pad with zeros
@@ -180,14 +182,15 @@ int setup_v2(cnl_handle* h) {
     if (h->resident_waves > 0) h->df_waves = std::min(h->df_waves, h->resident_waves);
     {
       const size_t B = (size_t)h->batch, nq = (B + 3) / 4, tq = 2 * (size_t)h->ntasks * nq;
-      const size_t total = 4 * B + (size_t)cnl::LAD_WORDS * nq + tq + 2 + (o.dataflow ? tq : 0);
+      const bool dataflow = o.dataflow && !h->f32;   // (float: one launch per stage only — no dataflow part, d_dep stays null)
+      const size_t total = 4 * B + (size_t)cnl::LAD_WORDS * nq + tq + 2 + (dataflow ? tq : 0);
       if ((rc = dalloc(h, &h->d_gcnt, total))) return rc;
       if (hipMemset(h->d_gcnt, 0, total * sizeof(int)) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
       h->d_lgcnt = h->d_gcnt + 2 * B;
       h->d_lad = h->d_lgcnt + 2 * B;
       h->d_ldep = h->d_lad + (size_t)cnl::LAD_WORDS * nq;
       h->d_stat = h->d_ldep + tq;   // per-call status words (kernels2.hip, spin_until)
-      if (o.dataflow) h->d_dep = h->d_stat + 2;
+      if (dataflow) h->d_dep = h->d_stat + 2;
       h->zero_ints = (long long)total;
     }
     h->stage_ptr = P.stage_ptr;
@@ -199,7 +202,8 @@ int setup_v2(cnl_handle* h) {
     // Plans of a few LARGE tasks (the bidirectional chain of mid-size batches) keep the sequential launch when one fused launch
     // cannot hold the batch: a rung there is the same chain of fronts either way, and two fused launches of two wavefronts per SIMD
     // lose to one sequential launch of one (cfg5 at 4096 problems: 3.9 against 2.9 ms).
-    if (o.device_ladder && h->resident_waves >= h->ntasks) {
+    // (float: no fused instance — the problems that fail the attempt climb the ladder in the classic launch behind it)
+    if (!h->f32 && o.device_ladder && h->resident_waves >= h->ntasks) {
       const long long slots = h->resident_waves / h->ntasks, nq = (h->batch + 3) / 4;
       const long long launches = (nq + slots - 1) / slots;
       if (launches == 1 || (launches <= 4 && h->ntasks >= 16)) h->lad_mode = o.device_ladder_fused ? 2 : 1;
@@ -723,8 +727,7 @@ int create_f32_general_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_
   // ("a front exceeds order 64" is P.fmax > 64 here and not !P.v2_ok: analysis.cpp defines v2_ok as fmax <= 64 && register_front &&
   // with_rhs_row, and the forced analysis of a Float32 general handle sets register_front = 0, so v2_ok is false for EVERY such plan;
   // fmax > 64 is the clause of v2_ok that speaks about the fronts.  Keep the 64 in step with analysis.cpp.)
-  const bool gd_fits = gd && C.active && !plan->gpos.empty() && (gd == 2 || plan->P.fmax > 64) &&
-                       (batch <= 16 || (double)batch * 3.0 * 16384.0 * std::pow(std::ceil((double)C.N2 / 64.0), 2) <= 8e9);
+  const bool gd_fits = gd && C.active && !plan->gpos.empty() && (gd == 2 || plan->P.fmax > 64) && f32_general_dense_fits(plan, batch);
   // tuning float32_register_front: the register-front kernel in float runs newton_system / try_to_factorize between the passes
   // where the plan's fronts allow it and its LDS block fits; where not, the handle is the float32_condense handle and nothing else
   // (a plan that kernel takes stays on it with float32_general_dense = 1; 2 asks for the dense route wherever it is possible)
@@ -772,10 +775,17 @@ int create_f32_general(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t*
                        int64_t batch, int device, const cnl::Tuning& o) {
   cnl_plan* plan = nullptr;
   cnl::Tuning g;
-  if (int rc = f32_general_plan(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, o, &g)) return rc;
+  if (int rc = f32_general_plan(&plan, N, nnz, rows1, cols1, nvar, nequ, ncon, o, &g, batch)) return rc;
   if (plan->D.active) return create_f32_dense_from_plan(hout, plan, rows1, cols1, batch, device);
-  const bool direct_plan = plan->P.rec_direct;
+  const bool direct_plan = plan->P.rec_direct, staged_plan = g.float32_staged && plan->latency;
   if (int rc = create_f32_general_from_plan(hout, plan, rows1, cols1, batch, device)) return rc;
+  if (staged_plan && !(*hout)->staged) {
+    // tuning float32_staged, and setup_v2 declined the latency plan (its LDS block, its 32-bit offsets): on the single stream the
+    // latency order is only a worse order, so the handle is the one without the key, from its own throughput analysis
+    cnl_destroy(*hout);
+    *hout = nullptr;
+    return create_f32_general(hout, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, f32_unstaged_options(o));
+  }
   if (direct_plan && (*hout)->route != cnl::Route::Direct) {
     // setup_v2 declined the direct records (their LDS block is the larger one): the handle is the one without the key
     cnl_destroy(*hout);
@@ -866,6 +876,8 @@ int cnl_create_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows
   const int rc0 = resolve_options(opt, o);
   if (rc0) return rc0;
   if (o.float32_refine) return create_refined(hout, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, o);
+  if (o.float32_staged)   // (the key's own rules, as every creator answers them; a Float64 handle reads nothing else of it)
+    if (int rc = check_f32_options(o, "cnl_create_ex")) return rc;
   return create_tuned(hout, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, o);
 }
 

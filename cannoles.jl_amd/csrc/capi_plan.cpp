@@ -248,11 +248,63 @@ int check_f32_options(const cnl::Tuning& o, const char* fn) {
     return fail(CNL_ERR_ARG, f + ": tuning float32_general_dense needs float32_general = 1 (the general form of the dense backend in float serves Float32 general handles)");
   if (o.float32_general_dense < 0 || o.float32_general_dense > 2)
     return fail(CNL_ERR_ARG, f + ": tuning float32_general_dense is 0, 1 (plans with a front above order 64) or 2 (wherever the order and the batch allow)");
+  if (o.float32_staged < 0 || o.float32_staged > 1)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_staged is 0 or 1 (latency plans of Float32 general handles run stage by stage)");
+  if (o.float32_staged && !o.float32_general)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_staged = 1 needs float32_general = 1 (staged execution in float serves Float32 general handles)");
+  if (o.float32_staged && o.float32_refine)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_staged = 1 does not go with float32_refine (no refined handle over a staged Float32 factor)");
   return CNL_OK;
 }
 
+cnl::Tuning f32_unstaged_options(const cnl::Tuning& o) {
+  cnl::Tuning u = o;
+  u.float32_staged = 0; u.float32_register_front = 1; u.float32_direct_records = 1;
+  if (!u.float32_condense) u.float32_condense = 1;
+  return u;
+}
+
+bool f32_general_dense_fits(const cnl_plan* plan, int64_t batch) {
+  return batch <= 16 || (double)batch * 3.0 * 16384.0 * std::pow(std::ceil((double)plan->C.N2 / 64.0), 2) <= 8e9;
+}
+
 int f32_general_plan(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ, int64_t ncon,
-                     const cnl::Tuning& o, cnl::Tuning* used) {
+                     const cnl::Tuning& o, cnl::Tuning* used, int64_t batch) {
+  if (o.float32_staged) {
+    // Tuning float32_staged: the latency analysis exactly where plan_create_tuned makes it for a Float64 handle, with the tuning of
+    // the float direct records plus staged execution — no split plan, no tail.  A plan that cannot run staged (the conditions of
+    // plan_create_impl: tasks, direct records, d in the caller's numbering, every condensed pivot counted by a front), a batch
+    // planned for throughput, and every pattern float32_dense / float32_general_dense serve get the plan they get without the key.
+    const cnl::Tuning u = f32_unstaged_options(o);
+    int latency = 0;
+    if (o.plan_kind == CNL_PLAN_LATENCY) latency = 1;
+    else if (o.plan_kind == CNL_PLAN_AUTO) latency = batch >= 1 && batch <= (o.staged_max_batch > 0 ? o.staged_max_batch : 4096);
+    else if (o.plan_kind != CNL_PLAN_THROUGHPUT) return fail(CNL_ERR_ARG, "unknown plan_kind");
+    if (latency && batch < 1) return fail(CNL_ERR_ARG, "a latency plan needs the batch size");
+    if (latency && ((u.float32_dense && u.dense_backend) || u.float32_general_dense)) {
+      if (int rc = f32_general_plan(plan, N, nnz, rows1, cols1, nvar, nequ, ncon, u, used, batch)) return rc;
+      const cnl_plan* p = *plan;
+      const int gd = u.float32_general_dense;
+      if (p->D.active || (gd && p->C.active && !p->gpos.empty() && (gd == 2 || p->P.fmax > 64) && f32_general_dense_fits(p, batch))) return CNL_OK;
+      cnl_plan_destroy(*plan);
+      *plan = nullptr;
+    }
+    if (latency) {
+      cnl::Tuning g = u;
+      g.float32_staged = 1;
+      g.condense = 1; g.register_front = 1; g.direct_records = 1; g.lean_kernel = 0; g.rows_in_backward = 0;
+      g.dense_backend = 0; g.general_dense = 0; g.band_kernel = 0; g.staged = 1;
+      const int nquads = (int)((batch + 3) / 4);
+      if (int rc = plan_create_impl(plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 1, std::max(1, 2048 / nquads), 2048.0 / nquads, g)) return rc;
+      const cnl_plan* p = *plan;
+      const bool stageable = p->latency && !p->P.tasks.empty() && p->P.v2_ok && p->P.rec_direct && p->P.d_outer &&
+                             p->P.d_owned == (int64_t)p->C.r_dsrc.size();
+      if (stageable) { if (used) *used = g; return CNL_OK; }
+      cnl_plan_destroy(*plan);
+      *plan = nullptr;
+    }
+    return f32_general_plan(plan, N, nnz, rows1, cols1, nvar, nequ, ncon, u, used, batch);
+  }
   // The throughput analysis with nothing but the general kernel to run, whatever the caller's options say: no condensation (a call
   // is then the one classic launch) unless tuning float32_condense asks for it (the call is then that launch between the float
   // condensation passes), no register-front records, no dense routes, no staged execution, no band program.
@@ -343,7 +395,8 @@ const char* cnl_last_error(void) { return g_err.c_str(); }
 // 0.4.4: tuning float32_general_dense (Float32 general handles with large fronts on the general form of the dense backend in float), no new symbol
 // 0.5.0: tuning float32_refine (Float64 handles on a Float32 factor, refined with a Float64 residual), cnl_kkt_residual_dev,
 //        cnl_get_refine_norms, cnl_plan_get "kkt_row_*", cnl_get_config bits 38 .. 41
-int32_t cnl_version(void) { return 500; }
+// 0.5.1: tuning float32_staged (latency plans of Float32 general handles run stage by stage on the float register-front kernel), no new symbol
+int32_t cnl_version(void) { return 501; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62
@@ -395,6 +448,11 @@ int cnl_plan_create_ex(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* r
     if ((rc = check_f32_options(o, "cnl_plan_create_ex"))) return rc;
     if (!plan) return fail(CNL_ERR_ARG, "null argument");
     return f32_general_plan(plan, N, nnz, rows1, cols1, nvar, nequ, ncon, o);
+  }
+  if (o.float32_staged) {   // the plan cnl_create_f32_ex makes behind the band kernels for this batch
+    if ((rc = check_f32_options(o, "cnl_plan_create_ex"))) return rc;
+    if (!plan) return fail(CNL_ERR_ARG, "null argument");
+    return f32_general_plan(plan, N, nnz, rows1, cols1, nvar, nequ, ncon, o, nullptr, batch);
   }
   return plan_create_tuned(plan, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, o);
 }

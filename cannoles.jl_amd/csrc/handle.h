@@ -164,6 +164,10 @@ struct cnl_handle {
   // With tuning float32_direct_records = 1 on top those records are direct (where the analysis can write them and setup_v2 takes
   // them): route Direct, v2_solve by the Float64 rule (lean, staged: still false); d_cbuf / d_d2 and the condensation lists stay,
   // for the solve on plans with class-32 / class-64 fronts.
+  // With tuning float32_staged = 1 on top of that, a batch planned for latency has a latency plan on direct records, and where
+  // setup_v2 stages it the handle owns d_tasks, stage_ptr and the counters block (gcnt, lgcnt, lad, ldep, status words — no dataflow
+  // counters): staged = true, lad_mode = 0, d_dep = nullptr, lean = false.  A call is one launch per stage of the staged float
+  // instances and, for newton_system, the classic float launch behind them (skip_done) for the problems that failed the attempt.
   // With tuning float32_dense = 1 a pattern with a dense residual block (plan->D) is the uncondensed handle plus `dense`, a FLOAT
   // state of the dense backend (csrc/dense_f32.hip): route Dense, every call runs there (run_dense dispatches on f32).
   // With tuning float32_general_dense a condensed plan with a front above order 64 (2: any) whose condensed order is 96 .. 4096 is
@@ -296,9 +300,15 @@ const cnl::BandPlan& band_program(const cnl_plan* plan, bool f32);
 
 const cnl::KktRows& kkt_rows(const cnl_plan* plan);   // built on first request
 // the plan of a Float32 general handle off the band kernels (what cnl_create_f32_ex analyses behind tuning float32_general): the
-// uncondensed throughput analysis, or what float32_condense / _register_front / _direct_records / _dense / _general_dense make of it
+// uncondensed throughput analysis, or what float32_condense / _register_front / _direct_records / _dense / _general_dense make of it.
+// batch: read with tuning float32_staged alone — the latency analysis on direct records where a Float64 handle of that batch would
+// be planned for latency and the plan can run staged, else the plan of f32_unstaged_options(o)
 int f32_general_plan(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ, int64_t ncon,
-                     const cnl::Tuning& o, cnl::Tuning* used = nullptr);
+                     const cnl::Tuning& o, cnl::Tuning* used = nullptr, int64_t batch = 0);
+// tuning float32_staged taken out of `o`, the keys it implies written out: the options of the handle "without the key"
+cnl::Tuning f32_unstaged_options(const cnl::Tuning& o);
+// tuning float32_general_dense: do the tiles of `batch` problems of this plan fit the general form of the dense backend in float?
+bool f32_general_dense_fits(const cnl_plan* plan, int64_t batch);
 // what every creator checks of the float32_* keys (fn: the creator's name, for the message)
 int check_f32_options(const cnl::Tuning& o, const char* fn);
 

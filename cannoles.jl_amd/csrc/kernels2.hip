@@ -27,7 +27,8 @@
 //  * L rows are stored to HBM straight from registers at their pivot step.
 //  * one body for both element types: double, and float for Float32 general handles (tuning float32_register_front, on direct
 //    records with float32_direct_records; the plain instantiation in both LATE settings and one that holds the solve alone,
-//    nothing else — launch_newton2_f32 below, DESIGN sections 9.3 and 9.4).
+//    nothing else — launch_newton2_f32 below, DESIGN sections 9.3 and 9.4; with tuning float32_staged the staged twins of those
+//    three, one launch per stage — staged_kernel_f32 at the end of the file).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1674,11 +1675,12 @@ hipError_t launch_newton2(const DevPlan2& P, int wpb, size_t lds_bytes, const La
 }
 
 // The same kernel on Float32 data (kernels.h): the plain instantiation in both LATE settings and, for MODE_SOLVE, the instance that
-// holds nothing but the solve (SOLVE without LEAN) — no staged, fused or lean instance exists for float.  Its records are direct
+// holds nothing but the solve (SOLVE without LEAN) — no fused or lean instance exists for float; the staged ones are picked by
+// launch_newton2_staged (staged_kernel_f32, at the end of this file).  Its records are direct
 // with tuning float32_direct_records, and only then is it sent a MODE_SOLVE (the handle's v2_solve).  `late` by the Float64 rule.
 hipError_t launch_newton2_f32(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream) {
   if (wpb < 1 || wpb > 4) return hipErrorInvalidConfiguration;
-  if (a.lean || a.only_if_status || a.skip_done) return hipErrorInvalidConfiguration;
+  if (a.lean || a.only_if_status) return hipErrorInvalidConfiguration;   // (skip_done: behind a staged float attempt, the plain instances)
   const int waves = (a.batch + 3) / 4;
   const int grid = (waves + wpb - 1) / wpb;
   const bool late = waves >= 1024;
@@ -1701,8 +1703,14 @@ __global__ void __launch_bounds__(256) staged_decide_kernel(const int* __restric
   if (nzero) nzero[b] = tz;
 }
 
-hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, LaunchArgs a, const int32_t* stage_ptr, int nstages, hipStream_t stream) {
+typedef void (*newton2_kernel_fn)(const DevPlan2, const LaunchArgs);
+newton2_kernel_fn staged_kernel_f32(int mode, bool late);   // (below: the float instances are named last)
+
+hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, LaunchArgs a, const int32_t* stage_ptr, int nstages, hipStream_t stream,
+                                 bool f32) {
   if (wpb < 1 || wpb > 4) return hipErrorInvalidConfiguration;
+  // Float32: one launch per stage only — no instance waits on a device counter (dataflow, fused ladder), none is lean
+  if (f32 && (a.dep || a.lad_mode || a.lean)) return hipErrorInvalidConfiguration;
   a.nquads = (a.batch + 3) / 4;
   // the bidirectional chain of mid-size batches (two large tasks per group of problems) fills the SIMDs like the single stream
   // does: L rows one front late there, immediate stores for the bushy trees of small batches (see LPend)
@@ -1714,7 +1722,8 @@ hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, L
   const bool late = (long long)a.nquads * ntask0 >= 1920 && P.nsuper >= 128 * ntask0;
   const bool lean = a.lean != 0 && a.mode != MODE_SOLVE;
   const bool lean_solve = a.lean != 0 && a.back_rows != 0 && a.mode == MODE_SOLVE;
-  auto kern = lean_solve ? newton2_kernel_t<double, true, false, true, true>
+  auto kern = f32 ? staged_kernel_f32(a.mode, late)
+            : lean_solve ? newton2_kernel_t<double, true, false, true, true>
             : lean ? (late ? newton2_kernel_t<double, true, true, true> : newton2_kernel_t<double, true, false, true>)
                    : (late ? newton2_kernel_t<double, true, true, false> : newton2_kernel_t<double, true, false, false>);
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)lds_bytes));
@@ -1782,6 +1791,15 @@ hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, L
   if (a.mode == MODE_FACTOR)
     hipLaunchKernelGGL(staged_decide_kernel, dim3((a.batch + 255) / 256), dim3(256), 0, stream, a.gcnt, P.nvar, a.batch, a.success, a.npos, a.nzero);
   return hipGetLastError();
+}
+
+// The staged instances on Float32 data (tuning float32_staged): the plain staged instantiation in both LATE settings, chosen by the
+// rule above, and — as for the classic float launch — an instance that holds nothing but the solve for MODE_SOLVE (the forward
+// substitution of a task in the forward launches, its backward sweep in the backward ones), so that the substitution's cold paths
+// stay out of the two factorising instances.
+newton2_kernel_fn staged_kernel_f32(int mode, bool late) {
+  return mode == MODE_SOLVE ? newton2_kernel_t<float, true, false, false, true>
+                            : late ? newton2_kernel_t<float, true, true, false> : newton2_kernel_t<float, true, false, false>;
 }
 
 }  // namespace cnl

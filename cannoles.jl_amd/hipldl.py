@@ -141,7 +141,10 @@ def Options(**kw):
     """cnl_options with the library's defaults (cnl_options_init), then the given switches: explicit arguments instead of
     environment variables — e.g. Options(plan_kind=PLAN_THROUGHPUT), Options(dataflow=0), Options(force_order="nd32+early").
     Fields of the public structure are set directly; any other switch of csrc/options.h (lean_kernel, band_form,
-    band_problems_per_group, ...) goes into its `tuning` string as key=value — the library rejects an unknown key."""
+    band_problems_per_group, ...) goes into its `tuning` string as key=value — the library rejects an unknown key.
+    The float32_* keys (float32_general, float32_condense, float32_register_front, float32_direct_records, float32_dense,
+    float32_general_dense, float32_refine, and float32_staged = 1: latency plans of Float32 general handles run stage by stage on the
+    float register-front kernel) are described with HIPLDLStruct."""
     o = cnl_options()
     lib().cnl_options_init(C.byref(o))
     assert o.struct_size == C.sizeof(cnl_options), "cnl_options layout differs from the library's"
@@ -421,7 +424,14 @@ class HIPLDLStruct:
     general form of that backend: the float condensation passes around one dense LDL' of the whole condensed system
     (config["kernel"] == "dense", config["float32"] and info["ncond"] > 0), while batch <= 16 or the tiles stay within 8 GB; 2:
     whatever the fronts; every other pattern gets the handle it gets without the key, and the key without float32_general is
-    CNL_ERR_ARG.  A condensed or direct
+    CNL_ERR_ARG.  Options(float32_general=1, float32_staged=1) (implies float32_register_front, float32_direct_records and
+    float32_condense; band patterns need band_kernel=0 to get past the band kernels) plans a batch for latency where a Float64 handle
+    would be (plan_kind, 1 <= batch <= staged_max_batch) and runs that plan stage by stage on the staged float instances of the
+    register-front kernel, one launch per stage (config["kernel"] == "v2-staged", config["float32"], config["direct"]); the problems
+    that fail the first attempt climb the rho ladder in one classic launch behind the stages; solve_ldl! runs staged too where
+    config["v2_solve"].  Such a handle refuses set_active_batch (CnlError code 5).  Every other batch or pattern gets the handle it
+    gets with float32_register_front=1, float32_direct_records=1 in place of the key; the key without float32_general, with a value
+    other than 0 / 1 or with float32_refine is CNL_ERR_ARG.  A condensed or direct
     handle of either kind reads the Jacobian values of `vals` again in solve_ldl!: the array given to try_to_factorize must stay alive
     and unmodified until the last solve on that factor.
 

@@ -62,7 +62,7 @@ const char* cnl_last_error(void);
  * 0.4.1: tuning "float32_register_front", no new symbol; 0.4.2: tuning "float32_direct_records", cnl_get_config bits 36 / 37, no new
  * symbol; 0.4.3: tuning "float32_dense", no new symbol; 0.4.4: tuning "float32_general_dense", no new symbol;
  * 0.5.0: tuning "float32_refine" / "refine_rows", cnl_kkt_residual_dev, cnl_get_refine_norms, cnl_plan_get "kkt_row_*",
- * cnl_get_config bits 38 .. 41) */
+ * cnl_get_config bits 38 .. 41; 0.5.1: tuning "float32_staged", no new symbol) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -548,6 +548,27 @@ int cnl_launch_counts(int64_t counts[3]);
  * a Newton call without rhs are CNL_ERR_STATE, batch_layout = CNL_LAYOUT_INTERLEAVED stays CNL_ERR_ARG, the host-pointer entries are
  * the device entries behind an upload.  The solve condenses each new right-hand side from the factorisation's vals: the CONTRACT
  * below binds this handle.  Measured standing (README): opt-in.
+ *   tuning "float32_staged=1" (default 0; only with "float32_general=1" — without it the call is CNL_ERR_ARG and the message names
+ * the key; values other than 0 and 1, and the key together with "float32_refine", are CNL_ERR_ARG too, at cnl_plan_create_ex,
+ * cnl_create_ex, cnl_create_f32_ex and cnl_multi_create_ex alike; implies "float32_register_front", "float32_direct_records" and
+ * "float32_condense"): STAGED execution of latency plans in float.  Where a Float64 handle would be planned for latency —
+ * plan_kind = CNL_PLAN_LATENCY, or CNL_PLAN_AUTO with 1 <= batch <= staged_max_batch — the analysis is the latency analysis (bushy
+ * order, elimination tree cut into tasks) with direct records, never shaped for a lean instance, without split or tail plans, and
+ * the handle runs cnl_newton_system_f32* / cnl_factorize_f32* stage by stage on the staged float instances of the register-front
+ * kernel: ONE launch per stage and phase (no dataflow execution, no in-kernel ladder, no host-driven ladder: nothing waits on a
+ * device counter), the inertia rule on the counts the tasks sum.  The problems that fail the first attempt of cnl_newton_system_f32*
+ * (rare) climb the rho ladder from its first rung in ONE classic launch of the float register-front kernel behind the stages, which
+ * walks the latency plan's fronts sequentially (cnl_launch_counts: family 1 counts that launch alone, as on a staged Float64
+ * handle; family 2 nothing).  cnl_get_config reports cfg[5] & 15 == 4 with bits 27 and 36 set.  cnl_solve_f32* runs staged too
+ * where every front is of the fast class (bit 37); with fronts of class 32 / 64 it is the condensation of the right-hand side, one
+ * launch of family 2 and the post-pass, as on the "float32_direct_records" handle.  The host-pointer calls are the device entries
+ * behind an upload.  Staged and unstaged handles sum in different orders: decisions agree, d agrees within the Float32 tolerances.
+ * "float32_dense" and "float32_general_dense" keep the patterns they serve, and a band pattern goes to the band kernels first
+ * (cnl_options.band_kernel = 0 brings it here).  Everywhere else — a batch planned for throughput, a plan without tasks, a latency
+ * order whose direct records the analysis refuses, an LDS block or 32-bit offsets that do not fit — the handle is EXACTLY the
+ * handle the same options give with "float32_register_front=1, float32_direct_records=1" in place of the key.  As every staged
+ * handle it refuses cnl_set_active_batch (CNL_ERR_STATE); batch_layout = CNL_LAYOUT_INTERLEAVED stays CNL_ERR_ARG.  The CONTRACT
+ * below binds it.  Measured standing (README): opt-in.
  *   CONTRACT (the Direct handles' contract, restated): the `vals` / d_vals given to cnl_factorize_f32* (or
  * cnl_newton_system_f32*) must stay alive and UNMODIFIED until the last cnl_solve_f32* on that factor — the solve reads the
  * Jacobian values and the residual pivots of the factorisation's vals (host-pointer calls: the handle's own staged copy).
