@@ -84,13 +84,41 @@ __device__ __forceinline__ constexpr int lslot(int PH, int k) { return (PH - BAN
 // added to the lane's LDS base — and the flags word goes to an SGPR for the wave-uniform branches.
 struct Rec { int v[BAND_SW]; };
 struct RowRec { int v[BAND_RW]; };
+// AL (mover-table instance): the block starts on a 16-byte boundary of LDS — the record buffers lie behind whole lane blocks of 32
+// problems, BAND_REC_MAX, BAND_SW and BAND_RW are multiples of four ints — which the compiler cannot see: told so, it reads a block
+// with one ds_read_b128 per four words (of the words the sweep uses) where it otherwise reads it in 4- and 8-byte pieces
+static_assert(BAND_SW % 4 == 0 && BAND_RW % 4 == 0 && BAND_REC_MAX % 4 == 0, "step and row blocks start on 16-byte boundaries");
+template <bool AL = false>
+__device__ __forceinline__ const int4* rec_ptr(const char* recb, int o) {
+  if constexpr (AL) return static_cast<const int4*>(__builtin_assume_aligned(recb + 4 * o, 16));
+  else return reinterpret_cast<const int4*>(recb + 4 * o);
+}
+typedef unsigned __int128 __attribute__((may_alias)) rec_u128;
+template <bool AL = false>
 __device__ __forceinline__ void load_rec(Rec& R, const char* recb, int o) {
-  const int4* q = reinterpret_cast<const int4*>(recb + 4 * o);
+  const int4* q = rec_ptr<AL>(recb, o);
+  if constexpr (AL) {
+#pragma unroll
+    for (int k = 0; k < BAND_SW / 4; k++) {
+      const rec_u128 t = reinterpret_cast<const rec_u128*>(q)[k];
+      R.v[4 * k] = (int)t; R.v[4 * k + 1] = (int)(t >> 32); R.v[4 * k + 2] = (int)(t >> 64); R.v[4 * k + 3] = (int)(t >> 96);
+    }
+    return;
+  }
 #pragma unroll
   for (int k = 0; k < BAND_SW / 4; k++) { const int4 t = q[k]; R.v[4 * k] = t.x; R.v[4 * k + 1] = t.y; R.v[4 * k + 2] = t.z; R.v[4 * k + 3] = t.w; }
 }
+template <bool AL = false>
 __device__ __forceinline__ void load_row(RowRec& R, const char* recb, int o) {
-  const int4* q = reinterpret_cast<const int4*>(recb + 4 * o);
+  const int4* q = rec_ptr<AL>(recb, o);
+  if constexpr (AL) {
+#pragma unroll
+    for (int k = 0; k < BAND_RW / 4; k++) {
+      const rec_u128 t = reinterpret_cast<const rec_u128*>(q)[k];
+      R.v[4 * k] = (int)t; R.v[4 * k + 1] = (int)(t >> 32); R.v[4 * k + 2] = (int)(t >> 64); R.v[4 * k + 3] = (int)(t >> 96);
+    }
+    return;
+  }
 #pragma unroll
   for (int k = 0; k < BAND_RW / 4; k++) { const int4 t = q[k]; R.v[4 * k] = t.x; R.v[4 * k + 1] = t.y; R.v[4 * k + 2] = t.z; R.v[4 * k + 3] = t.w; }
 }
@@ -430,6 +458,10 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
     movp[i] = (unsigned)pl;
     ldsb[i] = ((unsigned)(i * 8 + lq) * (unsigned)LANE_D + (unsigned)le) << LS;
   }
+  // mover-table instance: problem group i of a lane lies a constant 8 * i lane blocks behind its group 0, so ONE register and the
+  // offset field of the LDS instruction address all four groups (three registers and three additions per committed set less)
+#define BAND_LDSB(I) (MOV ? ldsb[0] + (unsigned)((I) * 8 * LANE_D * ES) : ldsb[I])
+  static_assert(!MOV || (3 * 8 + 8) * LANE_D * ES < 65536, "a workgroup's lane blocks lie inside the offset field of an LDS instruction");
   // mover-table instance: the lane's byte offset inside an aligned block row of `vals` / inside a factor piece (band.h, BAND_MK_*)
   unsigned movv[NI], movf[NI];
   if constexpr (MOV) {
@@ -473,7 +505,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
 #define BAND_ISSUE1(K, I) if constexpr (I < NI) stg[K][I] = *reinterpret_cast<const T*>(pb + ((movp[I] * strd + tl) << LS));
 #define BAND_COMMIT1(K, I) if constexpr (I < NI) *reinterpret_cast<T*>(wblk + ldsb[I] + (BAND_IN_OFF + 8 * K) * ES) = stg[K][I];
   /* resident form: to the descriptor's slot (wave-uniform) */
-#define BAND_COMMITR1(K, I) if constexpr (I < NI) *reinterpret_cast<T*>(wslot_ + ldsb[I]) = stg[K][I];
+#define BAND_COMMITR1(K, I) if constexpr (I < NI) *reinterpret_cast<T*>(wslot_ + BAND_LDSB(I)) = stg[K][I];
 #define BAND_ISSUE_GEN(K)                                                                                                     \
   if (pcs[K] >= 0) {   /* (wave-uniform) */                                                                                   \
     const int pc = pcs[K];                                                                                                    \
@@ -529,8 +561,12 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
     if constexpr (NPC > 15) { BAND_ISSUE(15, SW) BAND_ISSUE(16, SW) BAND_ISSUE(17, SW) BAND_ISSUE(18, SW) BAND_ISSUE(19, SW) }                    \
     BAND_ISSUE_REC(OPS, OPOFF)                                                                                                \
   }
+  /* mover-table instance: ONE wait for everything in flight (vmcnt 0, the other counters open) in front of the commit.  The loads  \
+     are issued under wave-uniform branches, so the compiler cannot count them and waits in front of every ds_write of every set —   \
+     sixty waits, of which the first (all but the newest three operations) already drains the queue.  Behind this one it places none. */ \
 #define BAND_COMMIT_ALL(SW)                                                                                                     \
   {                                                                                                                           \
+    if constexpr (MOV) __builtin_amdgcn_s_waitcnt(BAND_WAIT_VM0);                                                             \
     BAND_COMMIT(0, SW) BAND_COMMIT(1, SW) BAND_COMMIT(2, SW) BAND_COMMIT(3, SW) BAND_COMMIT(4, SW) BAND_COMMIT(5, SW) BAND_COMMIT(6, SW) BAND_COMMIT(7, SW)   \
     BAND_COMMIT(8, SW) BAND_COMMIT(9, SW) BAND_COMMIT(10, SW) BAND_COMMIT(11, SW) BAND_COMMIT(12, SW) BAND_COMMIT(13, SW) BAND_COMMIT(14, SW)             \
     if constexpr (NPC > 15) { BAND_COMMIT(15, SW) BAND_COMMIT(16, SW) BAND_COMMIT(17, SW) BAND_COMMIT(18, SW) BAND_COMMIT(19, SW) }               \
@@ -551,6 +587,28 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
   if constexpr (NPC > 15) { BAND_ISSUE(15, SW) BAND_ISSUE(16, SW) BAND_ISSUE(17, SW) BAND_ISSUE(18, SW) BAND_ISSUE(19, SW) }                      \
   else { BAND_ISSUE(12, SW) BAND_ISSUE(13, SW) BAND_ISSUE(14, SW) }
 
+  // mover-table instance, EPOCH-BLOCK LOOK-AHEAD: no field of an epoch block is fetched where it is needed.  With the last issue
+  // group of an epoch, lanes 0 .. EW-1 load word `lane` of the block TWO epochs ahead into ebk (one VGPR) — a vector load among the
+  // mover's, which the commit's wait retires; behind the commit v_readlane hands out the NEXT epoch's mover words and step-block
+  // offset, and the next epoch's own fields (steps, record bases, solution ranges), which wait in SGPRs for a turn of the loop
+  // (*N below).  So ebk is free again before the load that refills it, and neither sweep holds a scalar load outside the border
+  // pivots: a lone wavefront per SIMD stood through each of their round trips (five per epoch pair, each waited for on the spot),
+  // and while one was pending every LDS wait was a wait for all.  Both ends of a sweep clamp the block index, and every rung of
+  // the ladder primes ebk and the *N anew.
+  const int* const epochs_g = as_global(P.epochs[part]);
+  int ebk = 0, nstN = 0, lb1N = 0, lb2N = 0, xloN = 0, xcN = 0, rloN = 0, rcN = 0, roffN = 0;
+  /* (the lane number is formed anew at each load, by an asm the compiler does not move: kept in a register through the loops it  \
+     would push one more value into scratch) */                                                                                  \
+#define BAND_EBK_LOAD(B)                                                                                                         \
+  {                                                                                                                              \
+    int el_;                                                                                                                     \
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(el_));                                   \
+    ebk = epochs_g[(B) * EW + (el_ < EW ? el_ : EW - 1)];                                                                        \
+  }
+#define BAND_EBK(F) __builtin_amdgcn_readlane(ebk, EF(F))
+#define BAND_EBK_DESC(F0) { _Pragma("unroll") for (int k_ = 0; k_ < NPC; k_++) pcs[k_] = __builtin_amdgcn_readlane(ebk, EF(F0) + k_); }
+  constexpr int BAND_WAIT_VM0 = 0x0F70;   // s_waitcnt vmcnt(0): vmcnt = bits 15:14 and 3:0, expcnt (6:4) and lgkmcnt (11:8) at their maxima
+
   Win<T> W;
   int npos = 0, nzer = 0;
   T lj[6], zj[4];   // junction factor (first wavefront)
@@ -565,31 +623,42 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
     W.S55 = T(0); W.c5 = T(0);
     npos = 0; nzer = 0;
     BAND_ISSUE_ALL(epochs, EF(BE_FP), fops_g, 0, 0)
+    if constexpr (MOV) {
+      nstN = epochs[EF(BE_NSTEP)]; lb1N = epochs[EF(BE_LBASE)]; lb2N = epochs[EF(BE_LBASE2)];
+      BAND_EBK_LOAD(nepochs > 1 ? 1 : 0)
+    }
     for (int e = 0; e < nepochs; e++) {
       cptr E = epochs + e * EW;
       BAND_COMMIT_ALL(0)
       // the next epoch's loads are issued in four groups behind the first four steps (a burst of 34 loads stalled the wavefront on
       // the CU's memory pipeline for ~2 500 cycles per epoch, in-kernel stamps), still four steps ahead of their use
       const bool more_ = e + 1 < nepochs;
-      if (more_) BAND_ISSUE_DESC(epochs + (e + 1) * EW, EF(BE_FP))
+      if constexpr (!MOV) { if (more_) BAND_ISSUE_DESC(epochs + (e + 1) * EW, EF(BE_FP)) }
       // The steps of the epoch: step t works on the slots of phase t (every epoch but the last has BAND_EPOCH steps), so the eight
       // instantiations follow each other in straight-line code and the window keeps its registers from step to step.
-      const int nst = E[EF(BE_NSTEP)];
       // first record element of each half of the epoch, less the out ring's offset that the program's BS_LB / BS_LX carry
-      const int recb1 = E[EF(BE_LBASE)] - LOUT_OFF, recb2 = E[EF(BE_LBASE2)] - LOUT_OFF;
+      int nst, recb1, recb2;
+      if constexpr (MOV) {
+        // (ebk holds the block of epoch e + 1, or of the last epoch again)
+        nst = nstN; recb1 = lb1N - LOUT_OFF; recb2 = lb2N - LOUT_OFF;
+        BAND_EBK_DESC(BE_FP)
+        roffN = BAND_EBK(BE_FOFF); nstN = BAND_EBK(BE_NSTEP); lb1N = BAND_EBK(BE_LBASE); lb2N = BAND_EBK(BE_LBASE2);
+      } else {
+        nst = E[EF(BE_NSTEP)]; recb1 = E[EF(BE_LBASE)] - LOUT_OFF; recb2 = E[EF(BE_LBASE2)] - LOUT_OFF;
+      }
       int o = 0;
       // the blocks of step t + 1 (step block + first row block) are read from the record buffer while step t computes; the step
       // reads all its operands at its top (one LDS round trip).  (A third stage — operands a step ahead — was measured: no gain,
       // 170 more registers.)
       Rec stC, stN;
       RowRec rwC, rwN;
-      load_rec(stC, recb, 0);
-      load_row(rwC, recb, BAND_SW);
+      load_rec<MOV>(stC, recb, 0);
+      load_row<MOV>(rwC, recb, BAND_SW);
 #define BAND_FSTEP(PHV)                                                                                                     \
       if (PHV < nst) {                                                                                                      \
         const int fl = __builtin_amdgcn_readfirstlane(stC.v[BS_FLAGS]);                                                     \
         const int onext = o + BAND_SW + BAND_RW * ((fl >> 8) & 255);                                                        \
-        if (PHV + 1 < nst) { load_rec(stN, recb, onext); load_row(rwN, recb, onext + BAND_SW); }                            \
+        if (PHV + 1 < nst) { load_rec<MOV>(stN, recb, onext); load_row<MOV>(rwN, recb, onext + BAND_SW); }                            \
         if (clane) {                                                                                                        \
           FOps<T> op_;                                                                                                      \
           fload(op_, stC, rwC, fl, myb);                                                                                    \
@@ -605,7 +674,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
       if (PHV < nst) {                                                                                                      \
         const int fl = __builtin_amdgcn_readfirstlane(SC.v[BS_FLAGS]);                                                      \
         const int onext = o + BAND_SW + BAND_RW * ((fl >> 8) & 255);                                                        \
-        if (PHV + 1 < nst) { load_rec(SN, recb, onext); load_row(RN, recb, onext + BAND_SW); }                              \
+        if (PHV + 1 < nst) { load_rec<MOV>(SN, recb, onext); load_row<MOV>(RN, recb, onext + BAND_SW); }                              \
         if (clane) {                                                                                                        \
           FOps<T> op_;                                                                                                      \
           fload(op_, SC, RC, fl, myb);                                                                                      \
@@ -638,7 +707,8 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
       BAND_FSTEP_X(2)
       if (more_) { BAND_ISSUE_G2(0) }
       BAND_FSTEP_X(3)
-      if (more_) { BAND_ISSUE_G3(0) BAND_ISSUE_REC(fops_g, epochs[(e + 1) * EW + EF(BE_FOFF)]) }
+      if constexpr (MOV) { if (more_) { BAND_ISSUE_G3(0) BAND_ISSUE_REC(fops_g, roffN) BAND_EBK_LOAD(e + 2 < nepochs ? e + 2 : nepochs - 1) } }
+      else if (more_) { BAND_ISSUE_G3(0) BAND_ISSUE_REC(fops_g, epochs[(e + 1) * EW + EF(BE_FOFF)]) }
       BAND_LFLUSH(E[EF(BE_LBASE)], E[EF(BE_LCNT)])
       BAND_FSTEP_X(4) BAND_FSTEP_X(5) BAND_FSTEP_X(6) BAND_FSTEP_X(7)
       static_assert(BAND_EPOCH == 8, "eight step instantiations per epoch");
@@ -789,23 +859,37 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
     const bool okme = valid && ctrl[NL + lane % NL] != 0.0 && clane;
     const long long pd = (long long)(prob0 + cpl) * N;
     BAND_ISSUE_ALL(epochs + (nepochs - 1) * EW, EF(BE_BP), bops_g, 0, 1)
+    if constexpr (MOV) {
+      cptr EL = epochs + (nepochs - 1) * EW;
+      nstN = EL[EF(BE_NSTEP)]; xloN = EL[EF(BE_DXLO)]; xcN = EL[EF(BE_DXCNT)]; rloN = EL[EF(BE_DRLO)]; rcN = EL[EF(BE_DRCNT)];
+      BAND_EBK_LOAD(nepochs > 1 ? nepochs - 2 : 0)
+    }
     for (int e = nepochs - 1; e >= 0; e--) {
       cptr E = epochs + e * EW;
       BAND_COMMIT_ALL(1)
       const bool more_ = e > 0;
-      if (more_) BAND_ISSUE_DESC(epochs + (e - 1) * EW, EF(BE_BP))
-      const int nst = E[EF(BE_NSTEP)];
+      int nst, xlo, xc, rlo, rc;
+      if constexpr (MOV) {
+        // (ebk holds the block of epoch e - 1, or of epoch 0 again)
+        nst = nstN; xlo = xloN; xc = xcN; rlo = rloN; rc = rcN;
+        BAND_EBK_DESC(BE_BP)
+        roffN = BAND_EBK(BE_BOFF); nstN = BAND_EBK(BE_NSTEP);
+        xloN = BAND_EBK(BE_DXLO); xcN = BAND_EBK(BE_DXCNT); rloN = BAND_EBK(BE_DRLO); rcN = BAND_EBK(BE_DRCNT);
+      } else {
+        if (more_) BAND_ISSUE_DESC(epochs + (e - 1) * EW, EF(BE_BP))
+        nst = E[EF(BE_NSTEP)];
+      }
       int o = 0;
       Rec stC, stN;
       RowRec rwC, rwN;
       // (mover-table instance: the step of phase PH reads its blocks from set PH % 2, and the first step of the epoch is nst - 1)
-      if (!MOV || (nst & 1)) { load_rec(stC, recb, 0); load_row(rwC, recb, BAND_SW); }
-      else { load_rec(stN, recb, 0); load_row(rwN, recb, BAND_SW); }
+      if (!MOV || (nst & 1)) { load_rec<MOV>(stC, recb, 0); load_row<MOV>(rwC, recb, BAND_SW); }
+      else { load_rec<MOV>(stN, recb, 0); load_row<MOV>(rwN, recb, BAND_SW); }
 #define BAND_BSTEP(PHV)                                                                                                     \
       if (PHV < nst) {                                                                                                      \
         const int fl = __builtin_amdgcn_readfirstlane(stC.v[BS_FLAGS]);                                                     \
         const int onext = o + BAND_SW + BAND_RW * ((fl >> 8) & 255);                                                        \
-        if (PHV > 0) { load_rec(stN, recb, onext); load_row(rwN, recb, onext + BAND_SW); }                                  \
+        if (PHV > 0) { load_rec<MOV>(stN, recb, onext); load_row<MOV>(rwN, recb, onext + BAND_SW); }                                  \
         if (clane) {                                                                                                        \
           BOps<T> op_;                                                                                                      \
           bload(op_, stC, rwC, fl, myb);                                                                                    \
@@ -817,7 +901,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
       if (PHV < nst) {                                                                                                      \
         const int fl = __builtin_amdgcn_readfirstlane(SC.v[BS_FLAGS]);                                                      \
         const int onext = o + BAND_SW + BAND_RW * ((fl >> 8) & 255);                                                        \
-        if (PHV > 0) { load_rec(SN, recb, onext); load_row(RN, recb, onext + BAND_SW); }                                    \
+        if (PHV > 0) { load_rec<MOV>(SN, recb, onext); load_row<MOV>(RN, recb, onext + BAND_SW); }                                    \
         if (clane) {                                                                                                        \
           BOps<T> op_;                                                                                                      \
           bload(op_, SC, RC, fl, myb);                                                                                      \
@@ -833,20 +917,21 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
       BAND_BSTEP_X(5)
       if (more_) { BAND_ISSUE_G2(1) }
       BAND_BSTEP_X(4)
-      if (more_) { BAND_ISSUE_G3(1) BAND_ISSUE_REC(bops_g, epochs[(e - 1) * EW + EF(BE_BOFF)]) }
+      if constexpr (MOV) { if (more_) { BAND_ISSUE_G3(1) BAND_ISSUE_REC(bops_g, roffN) BAND_EBK_LOAD(e > 2 ? e - 2 : 0) } }
+      else if (more_) { BAND_ISSUE_G3(1) BAND_ISSUE_REC(bops_g, epochs[(e - 1) * EW + EF(BE_BOFF)]) }
       BAND_BSTEP_X(3) BAND_BSTEP_X(2) BAND_BSTEP_X(1) BAND_BSTEP_X(0)
       // solution components of the epoch
-      const int xlo = E[EF(BE_DXLO)], xc = E[EF(BE_DXCNT)], rlo = E[EF(BE_DRLO)], rc = E[EF(BE_DRCNT)];
+      if constexpr (!MOV) { xlo = E[EF(BE_DXLO)]; xc = E[EF(BE_DXCNT)]; rlo = E[EF(BE_DRLO)]; rc = E[EF(BE_DRCNT)]; }
       char* dxo = reinterpret_cast<char*>(dbase) + ((long long)xlo << LS);
       char* dro = reinterpret_cast<char*>(dbase) + ((long long)rlo << LS);
       {
         T dx_[NI], dr_[BAND_DR_MAX / 8][NI];
 #pragma unroll
-        for (int i = 0; i < NI; i++) dx_[i] = *reinterpret_cast<const T*>(wblk + ldsb[i] + DX_OFF * ES);
+        for (int i = 0; i < NI; i++) dx_[i] = *reinterpret_cast<const T*>(wblk + BAND_LDSB(i) + DX_OFF * ES);
 #pragma unroll
         for (int cpc = 0; cpc < BAND_DR_MAX / 8; cpc++)
 #pragma unroll
-          for (int i = 0; i < NI; i++) dr_[cpc][i] = *reinterpret_cast<const T*>(wblk + ldsb[i] + (DR_OFF + 8 * cpc) * ES);
+          for (int i = 0; i < NI; i++) dr_[cpc][i] = *reinterpret_cast<const T*>(wblk + BAND_LDSB(i) + (DR_OFF + 8 * cpc) * ES);
 #pragma unroll
         for (int i = 0; i < NI; i++)
           if (movst[i] && le < xc) *reinterpret_cast<T*>(dxo + ((movp[i] * (unsigned)N + (unsigned)le) << LS)) = dx_[i];

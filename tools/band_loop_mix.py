@@ -7,6 +7,9 @@ backward branches (a branch to a label defined earlier in the function: the loop
 prints, per loop, a count per instruction class.  Nothing here knows the band kernels: give any assembly file.
 
   band_loop_mix.py band.s --kernel Li527E --min 1000      # the loops of 1000 instructions and more of the functions matching
+  band_loop_mix.py band.s --kernel Li527E --min 1000 --regular   # ... each without the text of the loops nested in it: in the band
+                                                          # kernels' epoch loops those are the unrolled residual-row loops (rows
+                                                          # i > 0 of a step), which a regular step never enters
   band_loop_mix.py band.s --resources                     # registers, spills and scratch bytes of every kernel (metadata)
   band_loop_mix.py band.s --digest                        # a hash of every function's instructions (cuid lines and comments
                                                           # dropped): equal hashes = identical device code in two builds
@@ -90,10 +93,12 @@ def loops(body):
     return sorted(best.items())
 
 
-def mix(body, a, b):
+def mix(body, a, b, skip=()):
+    """instruction classes of body[a .. b], the index ranges of `skip` left out"""
     c = dict.fromkeys(CLASSES, 0)
-    for _, op, _ in body[a: b + 1]:
-        if op:
+    for i in range(a, b + 1):
+        op = body[i][1]
+        if op and not any(x <= i <= y for x, y in skip):
             c[classify(op)] += 1
     c["total"] = sum(c[k] for k in CLASSES)
     return c
@@ -113,6 +118,7 @@ def main():
     ap.add_argument("--min", type=int, default=0, help="only loops of at least this many instructions")
     ap.add_argument("--resources", action="store_true")
     ap.add_argument("--digest", action="store_true")
+    ap.add_argument("--regular", action="store_true", help="count a loop without the loops nested in it (the path a regular step runs)")
     a = ap.parse_args()
     text = open(a.asm).read()
     if a.resources:
@@ -130,11 +136,16 @@ def main():
         ls = loops(body)
         print(f"{name}: {sum(1 for _, op, _ in body if op)} instructions, {len(ls)} loops")
         for lo, hi in ls:
-            c = mix(body, lo, hi)
-            if c["total"] < a.min:
+            if mix(body, lo, hi)["total"] < a.min:
                 continue
+            inner = [(x, y) for x, y in ls if lo <= x and y <= hi and (x, y) != (lo, hi)] if a.regular else []
+            c = mix(body, lo, hi, inner)
             depth = sum(1 for x, y in ls if x <= lo and hi <= y) - 1
-            print(f"  loop {body[lo][0]} depth {depth}: " + " ".join(f"{k}={c[k]}" for k in ("total",) + CLASSES))
+            print(f"  loop {body[lo][0]} depth {depth}: " + " ".join(f"{k}={c[k]}" for k in ("total",) + CLASSES)
+                  + (f"  [without {len(inner)} nested loops]" if a.regular else ""))
+    if a.regular and not a.digest:
+        print("note: --regular leaves out the nested loops only.  What a regular step of the band kernels also skips and this count still holds:\n"
+              "the peeled iterations and remainders of those row loops, and the border-pivot blocks (the only blocks with a scalar load).")
     return 0
 
 
