@@ -83,7 +83,8 @@ int choose_config(cnl_handle* h) {
 // asked with its 4-byte elements: every size "in doubles" of DevPlan2 then counts floats, the wavefront's LDS block and the global
 // scratch are sized in floats, and the 32-bit byte offsets of the kernel reach twice as many elements.  Its plan has no dense route
 // and lean stays off; direct records only with tuning float32_direct_records, and then v2_solve by the Float64 rule (DESIGN section
-// 9.4); tasks, and with them the staged state, only with tuning float32_staged.
+// 9.4); tasks, and with them the staged state, only with tuning float32_staged; dataflow counters, the
+// in-kernel ladder and lean by the Float64 rules only with tuning float32_latency on top.
 int setup_v2(cnl_handle* h) {
   const cnl::Plan& P = h->plan->P;
   h->use_v2 = false;
@@ -91,7 +92,7 @@ int setup_v2(cnl_handle* h) {
   const size_t esz = h->esz();
   if (!P.v2_ok || !o.register_front) return CNL_OK;
   // (a float plan with tasks is the latency plan of tuning float32_staged, f32_general_plan: staged below by the Float64 conditions, one
-  //  launch per stage — the float kernel has staged instances, no dataflow, fused or lean one)
+  //  launch per stage; with tuning float32_latency on top also dataflow, the fused ladder and lean)
   if (h->f32 && !P.tasks.empty() && !o.float32_staged) return CNL_OK;
   if (!h->f32 && !h->plan->gpos.empty() && (o.general_dense == 2 || (h->plan->prefer_dense && h->batch <= 16))) return CNL_OK;  // the dense route (capi_plan.cpp, plan_create_impl); 2: wherever it is possible
   cnl::DevPlan2& d = h->dp2;
@@ -182,7 +183,8 @@ int setup_v2(cnl_handle* h) {
     if (h->resident_waves > 0) h->df_waves = std::min(h->df_waves, h->resident_waves);
     {
       const size_t B = (size_t)h->batch, nq = (B + 3) / 4, tq = 2 * (size_t)h->ntasks * nq;
-      const bool dataflow = o.dataflow && !h->f32;   // (float: one launch per stage only — no dataflow part, d_dep stays null)
+      // (float: one launch per stage only — no dataflow part, d_dep stays null — unless tuning float32_latency brings the Float64 rules)
+      const bool dataflow = o.dataflow && (!h->f32 || o.float32_latency);
       const size_t total = 4 * B + (size_t)cnl::LAD_WORDS * nq + tq + 2 + (dataflow ? tq : 0);
       if ((rc = dalloc(h, &h->d_gcnt, total))) return rc;
       if (hipMemset(h->d_gcnt, 0, total * sizeof(int)) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
@@ -202,15 +204,18 @@ int setup_v2(cnl_handle* h) {
     // Plans of a few LARGE tasks (the bidirectional chain of mid-size batches) keep the sequential launch when one fused launch
     // cannot hold the batch: a rung there is the same chain of fronts either way, and two fused launches of two wavefronts per SIMD
     // lose to one sequential launch of one (cfg5 at 4096 problems: 3.9 against 2.9 ms).
-    // (float: no fused instance — the problems that fail the attempt climb the ladder in the classic launch behind it)
-    if (!h->f32 && o.device_ladder && h->resident_waves >= h->ntasks) {
+    // (float: the problems that fail the attempt climb the ladder in the classic launch behind it; with tuning float32_latency the
+    //  rule below, on the fused float instances)
+    if ((!h->f32 || o.float32_latency) && o.device_ladder && h->resident_waves >= h->ntasks) {
       const long long slots = h->resident_waves / h->ntasks, nq = (h->batch + 3) / 4;
       const long long launches = (nq + slots - 1) / slots;
       if (launches == 1 || (launches <= 4 && h->ntasks >= 16)) h->lad_mode = o.device_ladder_fused ? 2 : 1;
     }
   }
   h->v2_solve = P.rec_direct && P.d_outer && P.ncls[1] == 0 && P.ncls[2] == 0 && !o.v1_solve;
-  h->lean = !h->f32 && o.lean_kernel && P.rec_direct && P.d_outer && d.count_d && P.ncls[1] == 0 && P.ncls[2] == 0 && P.listprod_fronts == 0;
+  // (float: lean instances only behind tuning float32_latency, whose plan_create_impl shaped the plan for them — the key stays in the
+  //  options of that latency plan alone, every fallback plan has it cleared: f32_unstaged_options)
+  h->lean = (!h->f32 || o.float32_latency) && o.lean_kernel && P.rec_direct && P.d_outer && d.count_d && P.ncls[1] == 0 && P.ncls[2] == 0 && P.listprod_fronts == 0;
   return CNL_OK;
 }
 
@@ -876,7 +881,7 @@ int cnl_create_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows
   const int rc0 = resolve_options(opt, o);
   if (rc0) return rc0;
   if (o.float32_refine) return create_refined(hout, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, o);
-  if (o.float32_staged)   // (the key's own rules, as every creator answers them; a Float64 handle reads nothing else of it)
+  if (o.float32_staged || o.float32_latency)   // (the key's own rules, as every creator answers them; a Float64 handle reads nothing else of it)
     if (int rc = check_f32_options(o, "cnl_create_ex")) return rc;
   return create_tuned(hout, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, o);
 }
@@ -1076,7 +1081,11 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   if (h->route == cnl::Route::Direct) cfg[5] |= (int64_t)1 << 36;                 // the Direct route (call_shape.h), either element type
   if (h->route == cnl::Route::Direct && h->v2_solve) cfg[5] |= (int64_t)1 << 37;  // ... on which solve_ldl! runs on the register-front kernel too
   if (h->lean && !dense_route) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
-  if (h->tail) cfg[5] |= 32;                             // the remainder of the batch runs on a handle of its own (split_tail)
+  if (h->staged && h->use_v2 && !dense_route) {          // staged handles: how the stages run
+    if (h->d_dep) cfg[5] |= (int64_t)1 << 42;            // dataflow counters present (one launch per phase where the rule allows)
+    cfg[5] |= (int64_t)(h->lad_mode & 3) << 43;          // the in-kernel ladder: 0 none (sequential launch behind the attempt), 1, 2 fused
+  }
+  if (h->tail) cfg[5] |= 32;                          // the remainder of the batch runs on a handle of its own (split_tail)
   if (on_band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->band_resident << 24) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28) | ((int64_t)h->band_mover << 34);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts, layout, operand pieces per epoch, mover table (bit 34: bit 27 marks a Float32 handle)
   if (h->djt.rv_ntiles > 0) cfg[5] |= 128;               // row f1 runs on column tiles (kernels.h: DevJt::rv_*)
   cfg[6] = h->wpb2;

@@ -254,12 +254,18 @@ int check_f32_options(const cnl::Tuning& o, const char* fn) {
     return fail(CNL_ERR_ARG, f + ": tuning float32_staged = 1 needs float32_general = 1 (staged execution in float serves Float32 general handles)");
   if (o.float32_staged && o.float32_refine)
     return fail(CNL_ERR_ARG, f + ": tuning float32_staged = 1 does not go with float32_refine (no refined handle over a staged Float32 factor)");
+  if (o.float32_latency < 0 || o.float32_latency > 1)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_latency is 0 or 1 (latency plans of Float32 general handles on the lean, dataflow and fused-ladder float instances)");
+  if (o.float32_latency && !o.float32_general)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_latency = 1 needs float32_general = 1 (the latency path in float serves Float32 general handles)");
+  if (o.float32_latency && o.float32_refine)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_latency = 1 does not go with float32_refine (no refined handle over a staged Float32 factor)");
   return CNL_OK;
 }
 
 cnl::Tuning f32_unstaged_options(const cnl::Tuning& o) {
   cnl::Tuning u = o;
-  u.float32_staged = 0; u.float32_register_front = 1; u.float32_direct_records = 1;
+  u.float32_staged = 0; u.float32_latency = 0; u.float32_register_front = 1; u.float32_direct_records = 1;
   if (!u.float32_condense) u.float32_condense = 1;
   return u;
 }
@@ -270,7 +276,7 @@ bool f32_general_dense_fits(const cnl_plan* plan, int64_t batch) {
 
 int f32_general_plan(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ, int64_t ncon,
                      const cnl::Tuning& o, cnl::Tuning* used, int64_t batch) {
-  if (o.float32_staged) {
+  if (o.float32_staged || o.float32_latency) {
     // Tuning float32_staged: the latency analysis exactly where plan_create_tuned makes it for a Float64 handle, with the tuning of
     // the float direct records plus staged execution — no split plan, no tail.  A plan that cannot run staged (the conditions of
     // plan_create_impl: tasks, direct records, d in the caller's numbering, every condensed pivot counted by a front), a batch
@@ -293,6 +299,10 @@ int f32_general_plan(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* row
       cnl::Tuning g = u;
       g.float32_staged = 1;
       g.condense = 1; g.register_front = 1; g.direct_records = 1; g.lean_kernel = 0; g.rows_in_backward = 0;
+      // Tuning float32_latency on top: the caller's lean_kernel / rows_in_backward go through, so that
+      // plan_create_impl shapes the plan for the lean float instances as it does for a Float64 handle — the row form on every front
+      // where that makes the plan lean, fronts with more than 16 residual rows cut in two, backward rows
+      if (o.float32_latency) { g.float32_latency = 1; g.lean_kernel = o.lean_kernel; g.rows_in_backward = o.rows_in_backward; }
       g.dense_backend = 0; g.general_dense = 0; g.band_kernel = 0; g.staged = 1;
       const int nquads = (int)((batch + 3) / 4);
       if (int rc = plan_create_impl(plan, N, nnz, rows1, cols1, nvar, nequ, ncon, 1, std::max(1, 2048 / nquads), 2048.0 / nquads, g)) return rc;
@@ -396,7 +406,9 @@ const char* cnl_last_error(void) { return g_err.c_str(); }
 // 0.5.0: tuning float32_refine (Float64 handles on a Float32 factor, refined with a Float64 residual), cnl_kkt_residual_dev,
 //        cnl_get_refine_norms, cnl_plan_get "kkt_row_*", cnl_get_config bits 38 .. 41
 // 0.5.1: tuning float32_staged (latency plans of Float32 general handles run stage by stage on the float register-front kernel), no new symbol
-int32_t cnl_version(void) { return 501; }
+// 0.5.2: tuning float32_latency (lean, dataflow and fused-ladder float instances of the register-front kernel behind float32_staged),
+//        cnl_get_config bits 42 .. 44, no new symbol
+int32_t cnl_version(void) { return 502; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62
@@ -449,7 +461,7 @@ int cnl_plan_create_ex(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* r
     if (!plan) return fail(CNL_ERR_ARG, "null argument");
     return f32_general_plan(plan, N, nnz, rows1, cols1, nvar, nequ, ncon, o);
   }
-  if (o.float32_staged) {   // the plan cnl_create_f32_ex makes behind the band kernels for this batch
+  if (o.float32_staged || o.float32_latency) {   // the plan cnl_create_f32_ex makes behind the band kernels for this batch
     if ((rc = check_f32_options(o, "cnl_plan_create_ex"))) return rc;
     if (!plan) return fail(CNL_ERR_ARG, "null argument");
     return f32_general_plan(plan, N, nnz, rows1, cols1, nvar, nequ, ncon, o, nullptr, batch);

@@ -121,7 +121,8 @@ int launch_staged(cnl_handle* h, cnl::LaunchArgs& a, bool first_attempt_only, bo
   ladder_ran = a.lad_mode != 0;
   a.spin_limit = h->plan->opt.dataflow_spin_limit > 0 ? h->plan->opt.dataflow_spin_limit : (1 << 22);
   if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
-  // (a Float32 handle — tuning float32_staged — runs the staged float instances: lad_mode = 0 and a.dep = nullptr, by setup_v2)
+  // (a Float32 handle — tuning float32_staged — runs the staged float instances: lad_mode = 0, a.dep = nullptr and lean = 0 by
+  //  setup_v2, unless tuning float32_latency set them up by the Float64 rules)
   hipError_t e = cnl::launch_newton2_staged(h->dp2, h->wpb2, h->lds2, a, h->stage_ptr.data(), (int)h->stage_ptr.size() - 1, stream, h->f32);
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("staged launch: ") + hipGetErrorString(e));
   return CNL_OK;

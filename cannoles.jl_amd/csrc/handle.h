@@ -168,6 +168,8 @@ struct cnl_handle {
   // setup_v2 stages it the handle owns d_tasks, stage_ptr and the counters block (gcnt, lgcnt, lad, ldep, status words — no dataflow
   // counters): staged = true, lad_mode = 0, d_dep = nullptr, lean = false.  A call is one launch per stage of the staged float
   // instances and, for newton_system, the classic float launch behind them (skip_done) for the problems that failed the attempt.
+  // With tuning float32_latency = 1 on top of that the staged state is a Float64 handle's: d_dep where
+  // cnl_options.dataflow, lad_mode by the ladder rule, lean (and then no post-pass) by the Float64 conditions of setup_v2.
   // With tuning float32_dense = 1 a pattern with a dense residual block (plan->D) is the uncondensed handle plus `dense`, a FLOAT
   // state of the dense backend (csrc/dense_f32.hip): route Dense, every call runs there (run_dense dispatches on f32).
   // With tuning float32_general_dense a condensed plan with a front above order 64 (2: any) whose condensed order is 96 .. 4096 is

@@ -210,12 +210,14 @@ hipError_t launch_newton2(const DevPlan2& P, int wpb, size_t lds_bytes, const La
 // the register-front kernel on Float32 data (a Float32 general handle with tuning float32_register_front): every size of P named
 // "doubles" counts floats, lds_bytes is computed with 4-byte elements (the record area stays in 32-bit words).  Direct records with
 // tuning float32_direct_records; MODE_SOLVE (direct records, every front of the fast class) runs an instance of its own.  skip_done
-// (the launch behind a staged attempt, tuning float32_staged) is served by the plain instances; lean and only_if_status (no wait
-// can give up in a float execution, and there is no fused ladder to commit) are hipErrorInvalidConfiguration.
+// (the launch behind a staged attempt, tuning float32_staged) is served by the plain instances; lean and only_if_status (a handle
+// of tuning float32_latency: lean plans, the commit / redo behind dataflow and fused-ladder launches) pick from the same table as
+// launch_newton2.
 hipError_t launch_newton2_f32(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream);
 // one attempt at the rho given in vals, stage by stage (stage_ptr: host array of nstages + 1 task offsets)
-// f32: on Float32 data (tuning float32_staged; sizes as for launch_newton2_f32) — one launch per stage only: a.dep, a.lad_mode and
-// a.lean must be unset (hipErrorInvalidConfiguration otherwise)
+// f32: on Float32 data (tuning float32_staged; sizes as for launch_newton2_f32) — the float instances by the same lean / lean-solve /
+// late / ladder rules; a handle without tuning float32_latency hands over a.dep = nullptr, a.lad_mode = 0, a.lean = 0: one launch
+// per stage
 hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, LaunchArgs a, const int32_t* stage_ptr, int nstages, hipStream_t stream,
                                  bool f32 = false);
 hipError_t launch_condense(const DevCond& C, const double* vals, const double* rhs, double* cbuf, int slot_begin, int slot_end,

@@ -28,7 +28,8 @@
 //  * one body for both element types: double, and float for Float32 general handles (tuning float32_register_front, on direct
 //    records with float32_direct_records; the plain instantiation in both LATE settings and one that holds the solve alone,
 //    nothing else — launch_newton2_f32 below, DESIGN sections 9.3 and 9.4; with tuning float32_staged the staged twins of those
-//    three, one launch per stage — staged_kernel_f32 at the end of the file).
+//    three, one launch per stage — staged_kernel_f32 at the end of the file; with tuning float32_latency the
+//    lean, fused-ladder and commit twins of the Float64 latency path, behind those — DESIGN section 9.9).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -717,6 +718,9 @@ __device__ __noinline__ void ladder_commit(const int* lq, int g, int l, double* 
   if (l == 0) *rho_old = ro;
   for (int i = l; i < nvar; i += 16) slots[i] = wr;
 }
+// (Float32 handles, tuning float32_latency: the control block holds floats at the same word offsets, half of each field used; defined
+//  with the float instances at the end of the file)
+__device__ __noinline__ void ladder_commit(const int* lq, int g, int l, float* rho_old, float* slots, int nvar);
 __device__ __forceinline__ void task_done(int* counter, int lane, bool release = true) {
   if (!counter) return;
   if (release) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -1371,15 +1375,16 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) newton2_kernel_t(const De
       }
       fin = rfl(fin);
       int* st_w = lad + 4;
-      double* wr_w = reinterpret_cast<double*>(lad + 8);
-      double* ro_w = reinterpret_cast<double*>(lad + 16);
+      // (typed T: a Float32 handle climbs ParamCaNNOLeS(Float32)'s ladder in float, bit for bit — a float uses half of each field)
+      T* wr_w = reinterpret_cast<T*>(lad + 8);
+      T* ro_w = reinterpret_cast<T*>(lad + 16);
       int epoch;
       if (fin == rung * A.ntasks_all - 1) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         // ladder state of problem g (replicated over its 16 lanes): from the control block, or — first rung — as the launch
         // found it (after a staged first attempt: rho = 0, one factorisation, success flag)
         int st = 0, nf = 0;
-        double rh = 0.0, wr = 0.0;
+        T rh = 0.0, wr = 0.0;
         if (rung > 1) {
           st = __hip_atomic_load(st_w + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           nf = __hip_atomic_load(A.nfact + pclamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1674,17 +1679,31 @@ hipError_t launch_newton2(const DevPlan2& P, int wpb, size_t lds_bytes, const La
   return hipGetLastError();
 }
 
+typedef void (*newton2_kernel_fn)(const DevPlan2, const LaunchArgs);
+newton2_kernel_fn staged_kernel_f32(int mode, bool late);   // (below: the float instances are named last)
+newton2_kernel_fn classic_lean_kernel_f32(bool solve);
+newton2_kernel_fn commit_kernel_f32(bool lean);
+newton2_kernel_fn staged_lean_kernel_f32(bool solve, bool late);
+newton2_kernel_fn fused_kernel_f32(bool lean);
+
 // The same kernel on Float32 data (kernels.h): the plain instantiation in both LATE settings and, for MODE_SOLVE, the instance that
-// holds nothing but the solve (SOLVE without LEAN) — no fused or lean instance exists for float; the staged ones are picked by
-// launch_newton2_staged (staged_kernel_f32, at the end of this file).  Its records are direct
+// holds nothing but the solve (SOLVE without LEAN); the staged ones are picked by launch_newton2_staged (staged_kernel_f32, at the
+// end of this file).  Its records are direct
 // with tuning float32_direct_records, and only then is it sent a MODE_SOLVE (the handle's v2_solve).  `late` by the Float64 rule.
+// A handle of tuning float32_latency also sends lean and only_if_status: the table is launch_newton2's, with the float solve
+// instance where a Float64 handle runs the plain one (the lean, lean-solve and commit instances: end of this file).
 hipError_t launch_newton2_f32(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream) {
   if (wpb < 1 || wpb > 4) return hipErrorInvalidConfiguration;
-  if (a.lean || a.only_if_status) return hipErrorInvalidConfiguration;   // (skip_done: behind a staged float attempt, the plain instances)
   const int waves = (a.batch + 3) / 4;
   const int grid = (waves + wpb - 1) / wpb;
-  const bool late = waves >= 1024;
-  auto kern = a.mode == MODE_SOLVE ? newton2_kernel_t<float, false, false, false, true>
+  const bool lean = a.lean != 0 && a.mode != MODE_SOLVE;
+  const bool lean_solve = a.lean != 0 && a.back_rows != 0 && a.mode == MODE_SOLVE;
+  const bool late = waves >= 1024 && !lean && !lean_solve;
+  const bool commit = a.only_if_status != 0 && a.lad != nullptr && a.mode == MODE_NEWTON;   // behind fused ladder launches
+  auto kern = commit ? commit_kernel_f32(lean)
+            : lean_solve ? classic_lean_kernel_f32(true)
+            : a.mode == MODE_SOLVE ? newton2_kernel_t<float, false, false, false, true>
+            : lean ? classic_lean_kernel_f32(false)
             : late ? newton2_kernel_t<float, false, true, false> : newton2_kernel_t<float, false, false, false>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)lds_bytes));
   if (e != hipSuccess) return e;
@@ -1703,14 +1722,11 @@ __global__ void __launch_bounds__(256) staged_decide_kernel(const int* __restric
   if (nzero) nzero[b] = tz;
 }
 
-typedef void (*newton2_kernel_fn)(const DevPlan2, const LaunchArgs);
-newton2_kernel_fn staged_kernel_f32(int mode, bool late);   // (below: the float instances are named last)
-
 hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, LaunchArgs a, const int32_t* stage_ptr, int nstages, hipStream_t stream,
                                  bool f32) {
   if (wpb < 1 || wpb > 4) return hipErrorInvalidConfiguration;
-  // Float32: one launch per stage only — no instance waits on a device counter (dataflow, fused ladder), none is lean
-  if (f32 && (a.dep || a.lad_mode || a.lean)) return hipErrorInvalidConfiguration;
+  // (Float32: what the handle set up — without tuning float32_latency setup_v2 hands over dep = nullptr, lad_mode = 0, lean = 0, and the
+  //  launches are the three staged instances of float32_staged, one per stage)
   a.nquads = (a.batch + 3) / 4;
   // the bidirectional chain of mid-size batches (two large tasks per group of problems) fills the SIMDs like the single stream
   // does: L rows one front late there, immediate stores for the bushy trees of small batches (see LPend)
@@ -1722,7 +1738,7 @@ hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, L
   const bool late = (long long)a.nquads * ntask0 >= 1920 && P.nsuper >= 128 * ntask0;
   const bool lean = a.lean != 0 && a.mode != MODE_SOLVE;
   const bool lean_solve = a.lean != 0 && a.back_rows != 0 && a.mode == MODE_SOLVE;
-  auto kern = f32 ? staged_kernel_f32(a.mode, late)
+  auto kern = f32 ? (lean_solve ? staged_lean_kernel_f32(true, false) : lean ? staged_lean_kernel_f32(false, late) : staged_kernel_f32(a.mode, late))
             : lean_solve ? newton2_kernel_t<double, true, false, true, true>
             : lean ? (late ? newton2_kernel_t<double, true, true, true> : newton2_kernel_t<double, true, false, true>)
                    : (late ? newton2_kernel_t<double, true, true, false> : newton2_kernel_t<double, true, false, false>);
@@ -1757,7 +1773,8 @@ hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, L
   }
   a.ntasks_all = ntasks_all;
   // the in-kernel ladder: every task of a group of problems on a wavefront of its own, all of a launch resident at once
-  auto kern_f = lean ? newton2_kernel_t<double, true, false, true, false, true> : newton2_kernel_t<double, true, false, false, false, true>;
+  auto kern_f = f32 ? fused_kernel_f32(lean)
+              : lean ? newton2_kernel_t<double, true, false, true, false, true> : newton2_kernel_t<double, true, false, false, false, true>;
   if (ladder) {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern_f), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)lds_bytes));
     if (e != hipSuccess) return e;
@@ -1800,6 +1817,32 @@ hipError_t launch_newton2_staged(const DevPlan2& P, int wpb, size_t lds_bytes, L
 newton2_kernel_fn staged_kernel_f32(int mode, bool late) {
   return mode == MODE_SOLVE ? newton2_kernel_t<float, true, false, false, true>
                             : late ? newton2_kernel_t<float, true, true, false> : newton2_kernel_t<float, true, false, false>;
+}
+
+// The float instances of tuning float32_latency, behind every other so that those keep their place in the code
+// object: the twins of the Float64 latency path's instances, picked by the Float64 rules in the two launchers above.
+//  * staged lean in both LATE settings, and the staged lean solve (forward substitution and backward sweep with the backward rows)
+newton2_kernel_fn staged_lean_kernel_f32(bool solve, bool late) {
+  return solve ? newton2_kernel_t<float, true, false, true, true>
+               : late ? newton2_kernel_t<float, true, true, true> : newton2_kernel_t<float, true, false, true>;
+}
+//  * classic lean and classic lean solve: the launch behind a staged lean attempt (skip_done, the redo of a call whose wait gave up)
+newton2_kernel_fn classic_lean_kernel_f32(bool solve) {
+  return solve ? newton2_kernel_t<float, false, false, true, true> : newton2_kernel_t<float, false, false, true>;
+}
+//  * the fused ladder, lean and not
+newton2_kernel_fn fused_kernel_f32(bool lean) {
+  return lean ? newton2_kernel_t<float, true, false, true, false, true> : newton2_kernel_t<float, true, false, false, false, true>;
+}
+//  * the commit / redo launch behind fused launches (only_if_status), lean and not
+newton2_kernel_fn commit_kernel_f32(bool lean) {
+  return lean ? newton2_kernel_t<float, false, false, true, false, true> : newton2_kernel_t<float, false, false, false, false, true>;
+}
+__device__ __noinline__ void ladder_commit(const int* lq, int g, int l, float* rho_old, float* slots, int nvar) {
+  const float wr = reinterpret_cast<const float*>(lq + 8)[g], ro = reinterpret_cast<const float*>(lq + 16)[g];
+  if (wr == 0.0f) return;   // the problem never climbed
+  if (l == 0) *rho_old = ro;
+  for (int i = l; i < nvar; i += 16) slots[i] = wr;
 }
 
 }  // namespace cnl

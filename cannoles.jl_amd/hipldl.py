@@ -144,7 +144,9 @@ def Options(**kw):
     band_problems_per_group, ...) goes into its `tuning` string as key=value — the library rejects an unknown key.
     The float32_* keys (float32_general, float32_condense, float32_register_front, float32_direct_records, float32_dense,
     float32_general_dense, float32_refine, and float32_staged = 1: latency plans of Float32 general handles run stage by stage on the
-    float register-front kernel) are described with HIPLDLStruct."""
+    float register-front kernel; float32_latency = 1: float32_staged plus the lean, dataflow and fused-ladder float instances, switched
+    by lean_kernel, rows_in_backward, dataflow, dataflow_waves, dataflow_spin_limit, device_ladder and device_ladder_fused as on a
+    Float64 handle) are described with HIPLDLStruct."""
     o = cnl_options()
     lib().cnl_options_init(C.byref(o))
     assert o.struct_size == C.sizeof(cnl_options), "cnl_options layout differs from the library's"
@@ -431,7 +433,11 @@ class HIPLDLStruct:
     that fail the first attempt climb the rho ladder in one classic launch behind the stages; solve_ldl! runs staged too where
     config["v2_solve"].  Such a handle refuses set_active_batch (CnlError code 5).  Every other batch or pattern gets the handle it
     gets with float32_register_front=1, float32_direct_records=1 in place of the key; the key without float32_general, with a value
-    other than 0 / 1 or with float32_refine is CNL_ERR_ARG.  A condensed or direct
+    other than 0 / 1 or with float32_refine is CNL_ERR_ARG.  Options(float32_general=1, float32_latency=1) (implies float32_staged)
+    is that handle with the switches a Float64 latency handle honours — lean_kernel, rows_in_backward, dataflow, dataflow_waves,
+    dataflow_spin_limit, device_ladder, device_ladder_fused, Float64 defaults and rules — on the lean, dataflow and fused-ladder
+    float instances: config["lean"], config["dataflow"] and config["lad_mode"] say which run; the same fallbacks and refusals.
+    A condensed or direct
     handle of either kind reads the Jacobian values of `vals` again in solve_ldl!: the array given to try_to_factorize must stay alive
     and unmodified until the last solve on that factor.
 
@@ -480,7 +486,9 @@ class HIPLDLStruct:
                        "batch_layout": (int(cfg[5]) >> 25) & 1, "rhs_interleaved": bool((int(cfg[5]) >> 26) & 1),
                        "float32": bool((int(cfg[5]) >> 27) & 1), "band_pieces": (int(cfg[5]) >> 28) & 63,
                        "direct": bool((int(cfg[5]) >> 36) & 1), "v2_solve": bool((int(cfg[5]) >> 37) & 1),
-                       "refine": (int(cfg[5]) >> 39) & 7 if (int(cfg[5]) >> 38) & 1 else 0}
+                       "refine": (int(cfg[5]) >> 39) & 7 if (int(cfg[5]) >> 38) & 1 else 0,
+                       # staged handles: dataflow counters present; the in-kernel ladder (0 none, 1, 2 fused)
+                       "dataflow": bool((int(cfg[5]) >> 42) & 1), "lad_mode": (int(cfg[5]) >> 43) & 3}
         if self.config["float32"] and self.config["band"]:   # (a Float32 handle off the band kernels — tuning float32_general — is "v1")
             self.config["kernel"] = "band"
 

@@ -62,7 +62,8 @@ const char* cnl_last_error(void);
  * 0.4.1: tuning "float32_register_front", no new symbol; 0.4.2: tuning "float32_direct_records", cnl_get_config bits 36 / 37, no new
  * symbol; 0.4.3: tuning "float32_dense", no new symbol; 0.4.4: tuning "float32_general_dense", no new symbol;
  * 0.5.0: tuning "float32_refine" / "refine_rows", cnl_kkt_residual_dev, cnl_get_refine_norms, cnl_plan_get "kkt_row_*",
- * cnl_get_config bits 38 .. 41; 0.5.1: tuning "float32_staged", no new symbol) */
+ * cnl_get_config bits 38 .. 41; 0.5.1: tuning "float32_staged", no new symbol; 0.5.2: tuning "float32_latency", cnl_get_config
+ * bits 42 .. 44, no new symbol) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -569,6 +570,25 @@ int cnl_launch_counts(int64_t counts[3]);
  * handle the same options give with "float32_register_front=1, float32_direct_records=1" in place of the key.  As every staged
  * handle it refuses cnl_set_active_batch (CNL_ERR_STATE); batch_layout = CNL_LAYOUT_INTERLEAVED stays CNL_ERR_ARG.  The CONTRACT
  * below binds it.  Measured standing (README): opt-in.
+ *   tuning "float32_latency=1" (default 0; only with "float32_general=1" — without it the call is CNL_ERR_ARG and the message names
+ * the key; values other than 0 and 1, and the key together with "float32_refine", are CNL_ERR_ARG too, at cnl_plan_create_ex,
+ * cnl_create_ex, cnl_create_f32_ex and cnl_multi_create_ex alike; implies "float32_staged" and what that implies): the LATENCY PATH
+ * of a Float64 handle in float.  The handle is the "float32_staged" handle, and its latency plan honours the switches a Float64
+ * handle honours, with their Float64 defaults and rules: lean_kernel and rows_in_backward (the analysis gives every front the row
+ * form where that makes the plan lean, cuts fronts with more than 16 residual rows and writes backward rows: the lean float
+ * instances, no post-pass behind a call), cnl_options.dataflow, dataflow_waves and dataflow_spin_limit (one launch per phase in which
+ * tasks wait for each other on device counters; a wait that gives up is counted — cnl_dataflow_timeouts — and the call is redone
+ * sequentially), cnl_options.device_ladder and device_ladder_fused (the problems that fail the first attempt climb the rho ladder of
+ * ParamCaNNOLeS(Float32), in float, inside fused launches; rho_old and the rho slots of vals are committed by the launch behind
+ * them).  cnl_get_config reports which of them run: bit 4 (lean), and for staged handles of either element type bit 42 (dataflow
+ * counters present) and bits 43 .. 44 (the in-kernel ladder: 0 none, 1 behind a staged first attempt, 2 the first attempt inside
+ * the fused launch too).  With every one of them switched off the handle is the "float32_staged" handle, bit for bit; dataflow and
+ * the ladder do not change a bit of any result.  cnl_launch_counts: family 1 counts the one launch behind the attempt (commit, redo
+ * or the sequential ladder), also for cnl_factorize_f32* / cnl_solve_f32* where dataflow counters are present.  The fallbacks, the
+ * refusals (cnl_set_active_batch: CNL_ERR_STATE; CNL_LAYOUT_INTERLEAVED: CNL_ERR_ARG) and the CONTRACT are those of
+ * "float32_staged", and every fallback is EXACTLY the handle without either key.  Measured standing (README):
+ * faster than "float32_staged" for the smallest batches and for batches with ladder climbers, no gain from 256 problems on, slower
+ * than the Float64 default handle for cnl_newton_system_f32* everywhere: opt-in.
  *   CONTRACT (the Direct handles' contract, restated): the `vals` / d_vals given to cnl_factorize_f32* (or
  * cnl_newton_system_f32*) must stay alive and UNMODIFIED until the last cnl_solve_f32* on that factor — the solve reads the
  * Jacobian values and the residual pivots of the factorisation's vals (host-pointer calls: the handle's own staged copy).
