@@ -133,18 +133,23 @@ int cgls_impl(cnl_handle* h, const cnl::JacSrcT<T>& S, const T* d_r, T* d_lambda
               int ones_if_zero, int32_t* d_iters, void* stream) {
   if (h->djt.ncon == 0) return CNL_OK;  // nothing to estimate
   if (!d_lambda) return fail(CNL_ERR_ARG, "null lambda");
-  if (h->djt.ncon > 1024) return fail(CNL_ERR_DIM, "cnl_cgls_multipliers_dev supports at most 1024 constraints");
+  // the instance (tuning cgls_wide): the ncon-vectors in LDS, at most 1024 constraints; or in the workspace, any number
+  const int mode = h->plan->opt.cgls_wide;
+  const bool wide = mode == 2 || (mode == 1 && h->djt.ncon > 1024);
+  if (!wide && h->djt.ncon > 1024)
+    return fail(CNL_ERR_DIM, "cnl_cgls_multipliers_dev supports at most 1024 constraints (tuning cgls_wide = 1: the instance without that limit)");
   HIPCHK(hipSetDevice(h->device));
   T* ws = static_cast<T*>(h->cgls_ws);   // (the entry points have checked T against the handle's element type)
   if (!ws) {
-    int rc = dalloc(h, &ws, (size_t)h->full_batch * 2 * (size_t)h->djt.nvar);   // (the created batch: cnl_set_active_batch may widen the handle again)
+    // (the created batch: cnl_set_active_batch may widen the handle again; which instance runs is fixed per handle)
+    int rc = dalloc(h, &ws, (size_t)h->full_batch * (2 * (size_t)h->djt.nvar + (wide ? 3 * (size_t)h->djt.ncon : 0)));
     if (rc) return rc;
     h->cgls_ws = ws;
   }
   if (itmax <= 0) itmax = (int64_t)h->djt.nvar + h->djt.ncon;  // Krylov.jl's default: m + n
   if (itmax > INT_MAX) itmax = INT_MAX;  // the kernel counts in int: "no limit" (typemax(Int64)) must not wrap to a negative count
   hipError_t e = cnl::launch_cgls(h->djt, S, d_r, d_lambda, d_Jxtr, ws, d_iters, atol, rtol, (int)itmax, ones_if_zero,
-                                  (int)h->batch, (hipStream_t)stream);
+                                  wide, (int)h->batch, (hipStream_t)stream);
   if (e != hipSuccess) return fail(CNL_ERR_HIP, std::string("cgls: ") + hipGetErrorString(e));
   return CNL_OK;
 }

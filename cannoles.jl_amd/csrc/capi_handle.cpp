@@ -1071,6 +1071,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   if (h->f32 && on_band) {   // Float32 handle on the band kernels
     cfg[5] = 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->layout << 25) | ((int64_t)1 << 27) | ((int64_t)h->band_npiece << 28);
     if (h->djt.rv_ntiles > 0) cfg[5] |= 128;
+    cfg[5] |= (int64_t)(h->plan->opt.cgls_wide & 3) << 45;
     return CNL_OK;
   }
   cfg[0] = h->cfg.tpp; cfg[1] = h->cfg.ppb; cfg[2] = (int64_t)h->cfg.lds_bytes; cfg[3] = h->cfg.lds_work;
@@ -1088,6 +1089,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   if (h->tail) cfg[5] |= 32;                          // the remainder of the batch runs on a handle of its own (split_tail)
   if (on_band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->band_resident << 24) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28) | ((int64_t)h->band_mover << 34);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts, layout, operand pieces per epoch, mover table (bit 34: bit 27 marks a Float32 handle)
   if (h->djt.rv_ntiles > 0) cfg[5] |= 128;               // row f1 runs on column tiles (kernels.h: DevJt::rv_*)
+  cfg[5] |= (int64_t)(h->plan->opt.cgls_wide & 3) << 45;    // row f4: tuning cgls_wide (1: the wide instance above 1024 constraints, 2: always)
   cfg[6] = h->wpb2;
   cfg[7] = (int64_t)h->lds2;
   return CNL_OK;

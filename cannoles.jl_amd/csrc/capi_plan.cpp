@@ -78,6 +78,8 @@ int resolve_options(const cnl_options* in, cnl::Tuning& out) {
     return fail(CNL_ERR_ARG, "cnl_options.tuning: float32_refine takes problem-major arrays: batch_layout = CNL_LAYOUT_INTERLEAVED is the band kernels' layout");
   if (out.refine_rows < 0 || out.refine_rows > 2)
     return fail(CNL_ERR_ARG, "cnl_options.tuning: refine_rows is 0 (by the pattern), 1 (a row per lane) or 2 (a row per wavefront)");
+  if (out.cgls_wide < 0 || out.cgls_wide > 2)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: cgls_wide is 0 (the LDS instance, ncon <= 1024), 1 (the wide instance where ncon > 1024) or 2 (the wide instance always)");
   return CNL_OK;
 }
 
@@ -408,7 +410,9 @@ const char* cnl_last_error(void) { return g_err.c_str(); }
 // 0.5.1: tuning float32_staged (latency plans of Float32 general handles run stage by stage on the float register-front kernel), no new symbol
 // 0.5.2: tuning float32_latency (lean, dataflow and fused-ladder float instances of the register-front kernel behind float32_staged),
 //        cnl_get_config bits 42 .. 44, no new symbol
-int32_t cnl_version(void) { return 502; }
+// 0.5.3: tuning cgls_wide (row f4 with its ncon-vectors in the global workspace: more than 1024 constraints), cnl_get_config bits 45 / 46,
+//        no new symbol
+int32_t cnl_version(void) { return 503; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62

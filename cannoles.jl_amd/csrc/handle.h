@@ -136,7 +136,7 @@ struct cnl_handle {
   cnl::DenseState* dense = nullptr;
   cnl::DenseState* gdense = nullptr;  // dense treatment of an arbitrary condensed system (irregular sparsity, small batch)
   cnl::GeneralOps gops{};
-  void* cgls_ws = nullptr;    // [batch][2 * nvar] elements: workspace of cnl_cgls_multipliers_dev / _f32_dev, allocated on first use
+  void* cgls_ws = nullptr;    // [batch][2 * nvar] elements ([batch][2 * nvar + 3 * ncon] where the wide instance runs, tuning cgls_wide): workspace of cnl_cgls_multipliers_dev / _f32_dev, allocated on first use
   // (round 5) band kernels (csrc/band.h): newton_system of a throughput handle whose pattern is a band
   bool band = false;
   cnl::BandDev bd{};

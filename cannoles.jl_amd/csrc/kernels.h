@@ -232,8 +232,9 @@ hipError_t launch_prepare(int nnzhF, int nnzhc, int nnzjF, int nnzjc, int nvar, 
 // problem-major <-> interleaved over groups of 32 problems (band.h: band_il_index); rows of `len` doubles
 hipError_t launch_interleave(const double* src, double* dst, int batch, int full_batch, long long len, int to_interleaved, hipStream_t stream);
 hipError_t launch_interleave_f32(const float* src, float* dst, int batch, int full_batch, long long len, int to_interleaved, hipStream_t stream);
+// wide: the instance whose ncon-vectors live in `ws` ([batch][2 nvar + 3 ncon] then; [batch][2 nvar] and ncon <= 1024 otherwise)
 hipError_t launch_cgls(const DevJt& J, const JacSrc& S, const double* r, double* lambda, double* Jxtr, double* ws, int32_t* iters,
-                       double atol, double rtol, int itmax, int ones_if_zero, int batch, hipStream_t stream);
+                       double atol, double rtol, int itmax, int ones_if_zero, bool wide, int batch, hipStream_t stream);
 hipError_t launch_residual_vectors(const DevJt& J, const JacSrc& S, const double* r, const double* lambda, const double* Fx,
                                    const double* cx, double* rhs, double* norms, int batch, hipStream_t stream);
 hipError_t launch_trial_point(const DevJt& J, const double* x, const double* r, const double* lambda, const double* d,
@@ -243,7 +244,7 @@ hipError_t launch_trial_point(const DevJt& J, const double* x, const double* r, 
 hipError_t launch_prepare(int nnzhF, int nnzhc, int nnzjF, int nnzjc, int nvar, int nequ, int ncon, const float* hF, const float* hc,
                           const float* Jx, const float* Jcx, const float* delta, float* vals, int batch, int interleaved, hipStream_t stream);
 hipError_t launch_cgls(const DevJt& J, const JacSrcF& S, const float* r, float* lambda, float* Jxtr, float* ws, int32_t* iters,
-                       float atol, float rtol, int itmax, int ones_if_zero, int batch, hipStream_t stream);
+                       float atol, float rtol, int itmax, int ones_if_zero, bool wide, int batch, hipStream_t stream);
 hipError_t launch_residual_vectors(const DevJt& J, const JacSrcF& S, const float* r, const float* lambda, const float* Fx,
                                    const float* cx, float* rhs, float* norms, int batch, hipStream_t stream);
 hipError_t launch_trial_point(const DevJt& J, const float* x, const float* r, const float* lambda, const float* d,

@@ -908,6 +908,10 @@ __global__ void __launch_bounds__(256) prepare_il_kernel(int nnzhF, int nnzhc, i
 //   s = A'r, beta = ||s||^2 / gamma, p = s + beta p;   stop when ||s|| <= atol + rtol ||s_0||  or after itmax steps
 // with A = Jc' (nvar x ncon) and b = Jx' r).  One workgroup per problem; the ncon-vectors live in LDS, the two
 // nvar-vectors (residual, q) in a global workspace; reductions in a fixed order (deterministic).
+// WIDE (tuning cgls_wide): the three ncon-vectors live in the global workspace too, behind the two nvar-vectors ([res | q | x | sv | pv],
+// 2 nvar + 3 ncon elements per problem), so ncon is not bounded by the LDS arrays.  Same loops, same partial sums, same order: only the
+// address space of x, sv and pv differs, and they follow the rule res and q follow already — written by one thread, read by others
+// behind a __syncthreads().  The five vectors are one allocation and are not declared __restrict__ against each other.
 constexpr int CGLS_PMAX = 1024;
 template <class T>
 __device__ __forceinline__ T block_sum(T v, T* red) {
@@ -919,7 +923,7 @@ __device__ __forceinline__ T block_sum(T v, T* red) {
 }
 // T = float (Float32 handles): Krylov.jl's recurrence with T = Float32 — every dot product, axpy and reduction in float, in the
 // same fixed order; the workspace is float
-template <class T>
+template <class T, bool WIDE>
 __global__ void __launch_bounds__(256) cgls_kernel(const DevJt Jin, const JacSrcT<T> S, const T* __restrict__ r,
                                                    T* __restrict__ lambda, T* __restrict__ Jxtr, T* __restrict__ ws,
                                                    int* __restrict__ iters, T atol, T rtol, int itmax, int ones_if_zero) {
@@ -927,15 +931,18 @@ __global__ void __launch_bounds__(256) cgls_kernel(const DevJt Jin, const JacSrc
   J.ptrF = as_global(Jin.ptrF); J.slotF = as_global(Jin.slotF); J.idxF = as_global(Jin.idxF);
   J.ptrC = as_global(Jin.ptrC); J.slotC = as_global(Jin.slotC); J.idxC = as_global(Jin.idxC);
   J.rptrC = as_global(Jin.rptrC); J.rslotC = as_global(Jin.rslotC); J.rcolC = as_global(Jin.rcolC);
-  __shared__ T x[CGLS_PMAX], sv[CGLS_PMAX], pv[CGLS_PMAX];
+  __shared__ T lds[WIDE ? 1 : 3 * CGLS_PMAX];
   __shared__ T red[4];
   const long long b = blockIdx.x;
   const int t = threadIdx.x, n = J.nvar, p = J.ncon;
   const T* __restrict__ vF = S.vF + b * S.sF;
   const T* __restrict__ vC = S.vC + b * S.sC;
   const T* rb = r + b * J.nequ;
-  T* res = ws + b * 2 * n;  // residual of the least-squares problem
+  T* res = ws + b * (2 * (long long)n + (WIDE ? 3 * (long long)p : 0));  // residual of the least-squares problem
   T* q = res + n;
+  T* x = WIDE ? q + n : lds;
+  T* sv = WIDE ? x + p : lds + CGLS_PMAX;
+  T* pv = WIDE ? sv + p : lds + 2 * CGLS_PMAX;
   // b = Jx' r  (mul!(Jxtr, Jx', r), per-column COO-order sums as in residual_vectors_kernel)
   {
 #pragma clang fp contract(off)  // separately rounded multiply and add, as the reference's scalar loop
@@ -1001,18 +1008,22 @@ __global__ void __launch_bounds__(256) cgls_kernel(const DevJt Jin, const JacSrc
 
 template <class T>
 static hipError_t launch_cgls_t(const DevJt& J, const JacSrcT<T>& S, const T* r, T* lambda, T* Jxtr, T* ws, int32_t* iters,
-                                T atol, T rtol, int itmax, int ones_if_zero, int batch, hipStream_t stream) {
+                                T atol, T rtol, int itmax, int ones_if_zero, bool wide, int batch, hipStream_t stream) {
+  if (wide) {   // ws: [batch][2 nvar + 3 ncon]
+    hipLaunchKernelGGL((cgls_kernel<T, true>), dim3(batch), dim3(256), 0, stream, J, S, r, lambda, Jxtr, ws, iters, atol, rtol, itmax, ones_if_zero);
+    return hipGetLastError();
+  }
   if (J.ncon > CGLS_PMAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(cgls_kernel<T>, dim3(batch), dim3(256), 0, stream, J, S, r, lambda, Jxtr, ws, iters, atol, rtol, itmax, ones_if_zero);
+  hipLaunchKernelGGL((cgls_kernel<T, false>), dim3(batch), dim3(256), 0, stream, J, S, r, lambda, Jxtr, ws, iters, atol, rtol, itmax, ones_if_zero);
   return hipGetLastError();
 }
 hipError_t launch_cgls(const DevJt& J, const JacSrc& S, const double* r, double* lambda, double* Jxtr, double* ws, int32_t* iters,
-                       double atol, double rtol, int itmax, int ones_if_zero, int batch, hipStream_t stream) {
-  return launch_cgls_t(J, S, r, lambda, Jxtr, ws, iters, atol, rtol, itmax, ones_if_zero, batch, stream);
+                       double atol, double rtol, int itmax, int ones_if_zero, bool wide, int batch, hipStream_t stream) {
+  return launch_cgls_t(J, S, r, lambda, Jxtr, ws, iters, atol, rtol, itmax, ones_if_zero, wide, batch, stream);
 }
 hipError_t launch_cgls(const DevJt& J, const JacSrcF& S, const float* r, float* lambda, float* Jxtr, float* ws, int32_t* iters,
-                       float atol, float rtol, int itmax, int ones_if_zero, int batch, hipStream_t stream) {
-  return launch_cgls_t(J, S, r, lambda, Jxtr, ws, iters, atol, rtol, itmax, ones_if_zero, batch, stream);
+                       float atol, float rtol, int itmax, int ones_if_zero, bool wide, int batch, hipStream_t stream) {
+  return launch_cgls_t(J, S, r, lambda, Jxtr, ws, iters, atol, rtol, itmax, ones_if_zero, wide, batch, stream);
 }
 
 // one linear grid dimension (problem, chunk): the product must fit a 31-bit grid (a larger one would truncate silently)

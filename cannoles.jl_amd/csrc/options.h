@@ -69,7 +69,8 @@ namespace cnl {
   X(float32_staged, 0)       /* cnl_create_f32: a batch a Float64 handle would plan for latency (plan_kind, staged_max_batch) gets a latency plan on direct records and runs it stage by stage on the float register-front kernel, one launch per stage (no dataflow, no in-kernel ladder; the problems that fail the first attempt climb the rho ladder in the classic launch behind it); implies float32_register_front, float32_direct_records and float32_condense; every other pattern or batch gets the handle it gets without the key; only with float32_general, not with float32_refine */ \
   X(float32_latency, 0)      /* cnl_create_f32: float32_staged, and the latency plan honours the switches a Float64 handle honours — lean_kernel, rows_in_backward, dataflow, dataflow_waves, dataflow_spin_limit, device_ladder, device_ladder_fused, by the Float64 defaults and rules: the lean, dataflow and fused-ladder float instances of the register-front kernel; implies float32_staged and what that implies; every plan that cannot run staged gets the handle it gets without the key; only with float32_general, not with float32_refine */ \
   X(float32_refine, 0)       /* cnl_create_ex / cnl_plan_create_ex: k = 1 .. 4: a Float64 handle on an inner Float32 general handle (made as cnl_create_f32_ex makes it from the same options, band_kernel forced to 0), whose solution is refined k times with a Float64 residual (refine.h); only with float32_general */ \
-  X(refine_rows, 0)          /* the KKT residual kernel (refine.h): 0 by the pattern, 1 a row per lane, 2 a row per wavefront */
+  X(refine_rows, 0)          /* the KKT residual kernel (refine.h): 0 by the pattern, 1 a row per lane, 2 a row per wavefront */ \
+  X(cgls_wide, 0)            /* row f4: 0 the ncon-vectors in LDS, more than 1024 constraints are CNL_ERR_DIM; 1 in the global workspace where ncon > 1024; 2 there always */
 
 struct Tuning {
 #define X(name, dflt) int32_t name = dflt;

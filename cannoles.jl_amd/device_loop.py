@@ -14,7 +14,11 @@ active problem.  The linear algebra of the path goes through the C ABI on device
     least-squares multipliers -> cnl_cgls_multipliers_dev          (row f4)
 
 Only the model callbacks (residuals, Jacobian / Hessian values) are torch expressions of a closed-form family
-(`BandQuadFamily`); `vals`, `rhs` and `d` never cross PCIe.  There is no CPU fallback.
+(`BandQuadFamily`; `BandQuadConFamily` with nonlinear constraints); `vals`, `rhs` and `d` never cross PCIe.  There is no CPU fallback.
+
+Constraints.  A family whose `linear_constraints` is False (missing: True) provides `hess_cons_vals(X, LAM)`, the
+coordinates of sum_k lam_k Hess c_k(x) on the Hessian structure: the loop evaluates it in front of every Newton system (H_c) and the
+constraint Jacobian again at every trial point.  Above 1024 constraints the handle gets tuning cgls_wide = 1 (row f4).
 
 Element types: `solve!` is generic in T, and so is this loop — a family built with dtype = float32 runs it in Float32 throughout
 (a Float32 band handle, the `_f32_dev` passes, `cnl_outer_state_f32` and the `cnl_outer_*_f32_dev` kernels, ParamCaNNOLeS(Float32) and
@@ -181,6 +185,88 @@ class BandQuadFamily:
         return M()
 
 
+class BandQuadConFamily(BandQuadFamily):
+    """BandQuadFamily with NONLINEAR constraints: every block constraint gets a quadratic term of its own curvature g_k,
+        c_k(x) = sum_{j in block k} (C_kj x_j + g_k x_j^2 / 2) - e_k,        g ~ U(-con_curvature, con_curvature),
+    drawn behind every draw of the base class (the base data of a seed are those of BandQuadFamily), e such that c(xs) = 0.
+    Jacobian values in COO order: C + g[row] x[col]; sum_k lam_k Hess c_k = diag_j(sum_{k: j in block k} lam_k g_k) on the model's
+    Hessian structure s.hF (what hess_coord!(nls, x, lam; obj_weight = 0) returns; prepare negates it).  `linear_constraints = False`
+    tells the loop to evaluate `hess_cons_vals` in front of every system and the constraint Jacobian at the trial point."""
+    linear_constraints = False
+
+    def __init__(self, s, B, seed, torch, device, curvature=0.3, start=0.3, noise=0.01, dtype=np.float64, con_curvature=0.2):
+        super().__init__(s, B, seed, torch, device, curvature=curvature, start=start, noise=noise, dtype=dtype)
+        n, m, p = s.nvar, s.nequ, s.ncon
+        if p == 0:
+            raise ValueError("BandQuadConFamily: a structure with constraints expected")
+        # the base class's draws again, in its order (its generator is local to its constructor), for xs and the generator's state
+        rng = np.random.default_rng(seed)
+        nj = len(self.jr)
+        rng.uniform(0, 1, (B, nj)), rng.uniform(-0.5, 0.5, (B, nj)), rng.uniform(-curvature, curvature, (B, n))
+        xs = rng.normal(size=(B, n))
+        rng.uniform(-1, 1, (B, len(self.cr)))
+        x0 = xs + start * rng.normal(size=(B, n))
+        rng.normal(size=(B, m))
+        if not np.array_equal(x0.astype(self.dtype).astype(np.float64), self.h["x0"]):
+            raise RuntimeError("BandQuadConFamily: the draws of BandQuadFamily are not the ones restated here")
+        g = rng.uniform(-con_curvature, con_curvature, (B, p))
+        self.ccol_ent = self._row_lists(self.cc, n, len(self.cr))   # per variable: the J_c entries of its column
+        sq = np.concatenate([xs[:, self.cc] ** 2, np.zeros((B, 1))], axis=1)[:, self.crow_ent].sum(axis=2)
+        new = dict(g=g, e=self.h["e"] + 0.5 * g * sq)
+        if self.dtype == np.float32:
+            new = {k: v.astype(np.float32).astype(np.float64) for k, v in new.items()}
+        self.h.update(new)
+        t = lambda a, dt=None: torch.as_tensor(a, dtype=dt or self.tdtype, device=device)
+        self.d.update({k: t(v) for k, v in new.items()})
+        self.cr_t = t(self.cr, torch.long)
+        self.ccol_ent_t = t(self.ccol_ent, torch.long)
+
+    def _c_np(self, Cv, x, e, g=None):
+        """(the base class calls this with its own three arguments while it generates e for the linear part: g = None there)"""
+        c = super()._c_np(Cv, x, e)
+        if g is None:
+            return c
+        sq = np.concatenate([x[:, self.cc] ** 2, np.zeros((len(x), 1))], axis=1)[:, self.crow_ent].sum(axis=2)
+        return c + 0.5 * g * sq
+
+    def cons(self, X):
+        t = self.torch
+        zero = t.zeros((self.B, 1), dtype=self.tdtype, device=self.device)
+        Xc = X[:, self.cc_t]
+        prod = t.cat([self.d["Cv"] * Xc, zero], dim=1)
+        sq = t.cat([Xc * Xc, zero], dim=1)
+        return prod[:, self.crow_ent_t].sum(dim=2) + 0.5 * self.d["g"] * sq[:, self.crow_ent_t].sum(dim=2) - self.d["e"]
+
+    def jacc_vals(self, X):
+        return self.d["Cv"] + self.d["g"][:, self.cr_t] * X[:, self.cc_t]
+
+    def hess_cons_vals(self, X, LAM):
+        t = self.torch
+        lg = t.cat([(LAM[:, :self.s.ncon] * self.d["g"])[:, self.cr_t], t.zeros((self.B, 1), dtype=self.tdtype, device=self.device)], dim=1)
+        return self.hdiag_t * lg[:, self.ccol_ent_t].sum(dim=2)[:, self.hr_t]
+
+    def host_model(self, b):
+        fam, s = self, self.s
+        n, p = s.nvar, s.ncon
+        base = super().host_model(b)
+        Cv, e, g = (fam.h[k][b] for k in ("Cv", "e", "g"))
+
+        class M(type(base)):
+            def cons(self, x):
+                return fam._c_np(Cv[None], x[None], e[None], g[None])[0]
+
+            def jac(self, x):
+                J = np.zeros((p, n))
+                J[fam.cr, fam.cc] = Cv + g[fam.cr] * x[fam.cc]
+                return J
+
+            def hess_coord_cons(self, x, lam):
+                dj = np.bincount(fam.cc, weights=(lam * g)[fam.cr], minlength=n)
+                return (fam.hr == fam.hcl) * dj[fam.hr]
+
+        return M()
+
+
 def kkt_pattern_of(fam, method="Newton"):
     """rows, cols (1-based int64) and the segment offsets, exactly as outer_loop.solve builds them from a model
     (/root/reference/src/CaNNOLeS.jl:276-315): with constraints the H_c segment has the model's Hessian structure.
@@ -230,7 +316,8 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
                        x=None, lam=None, use_initial_multiplier=False, max_iter=-1, max_eval=100000, max_time=None,
                        always_accept_extrapolation=False):
     """All B problems of `fam` in lockstep on the device.  Returns a dict of numpy arrays: solution [B, n], multipliers,
-    status (list of strings), iter, nfact, nlinsolve, nbk, neval, objective, and `steps` (global steps = batched Newton rounds).
+    status (list of strings), iter, nfact, nlinsolve, nbk, neval, objective, and `steps` (global steps = batched Newton rounds);
+    `jct_shared` (one constraint-Jacobian array serves the current and the trial point: linear constraints) and the handle's `cgls_wide`.
 
     The keywords of the reference's `solve!` (src/CaNNOLeS.jl:418-437) and of its solver constructor (:228-271):
       method   "Newton"; "Newton_noFHess" (Gauss-Newton: no H_F segment in the pattern, `fam.hess_vals` is never called and need not
@@ -286,6 +373,11 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     # tuning: further hipldl.Options fields for the handle — e.g. {"band_pieces": 20}: a constrained family's pattern (H_c as wide as H_F)
     # on the wide band kernels, which a Float64 handle takes on request only
     tuning = dict(tuning or {})
+    if p > 1024:   # row f4 keeps its ncon-vectors in LDS up to 1024 constraints; above, the instance with them in the handle's workspace
+        tuning.setdefault("cgls_wide", 1)
+    # a family with nonlinear constraints (fam.linear_constraints False; missing: linear): H_c = sum_k lam_k Hess c_k from
+    # fam.hess_cons_vals in front of every system, and a constraint Jacobian of its own for the trial point
+    nonlinear = p > 0 and not getattr(fam, "linear_constraints", True)
     # `vals` interleaved over groups of 32 problems where the band kernels serve the batch (cnl_options.batch_layout, round 6): row f2
     # writes that layout, newton_system reads it; rows f1 / f4 read the Jacobian values from the model's arrays, whatever the layout
     L = None
@@ -329,16 +421,24 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     hd = lambda a: a[:nb]
     wf = fw = fam
     L_nb = B             # the handle's active batch
-    hF_full = None
+    hF_full = hc_full = None
 
     def prepare(vals, hF, Jv_, Jcv_, delta_):
-        nonlocal hF_full
+        nonlocal hF_full, hc_full
         if hF is not None and hF.shape[0] < L_nb:   # a handle that could not shrink reads a Hessian row for every problem it was created with
             if hF_full is None:
                 hF_full = Z(B, hF.shape[1])
             hF_full[:hF.shape[0]].copy_(hF)
             hF = hF_full
-        hipldl.prepare_newton_system_dev(L, nnzhF, nnzhc, nnzjF, nnzjc, ptr(hF) if hF is not None else 0, ptr(hc0) if p else 0, ptr(Jv_),
+        hc = hc0
+        if nonlinear:   # sum_k lam_k Hess c_k at the current point and multipliers, fresh for every problem (prepare negates it)
+            hc = fw.hess_cons_vals(hd(x), hd(lam)).contiguous()
+            if hc.shape[0] < L_nb:   # (as hF above)
+                if hc_full is None:
+                    hc_full = Z(B, hc.shape[1])
+                hc_full[:hc.shape[0]].copy_(hc)
+                hc = hc_full
+        hipldl.prepare_newton_system_dev(L, nnzhF, nnzhc, nnzjF, nnzjc, ptr(hF) if hF is not None else 0, ptr(hc) if p else 0, ptr(Jv_),
                                          ptr(Jcv_) if p else 0, ptr(delta_) if p else 0, ptr(vals), st)
 
     def resid_vectors(Jv_, Jcv_, r_, lam_, F_, c_, rhs_out, nrm_out):
@@ -369,9 +469,9 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     Fx = fam.residual(x).contiguous()
     fx = (0.5 * rdot(Fx, Fx)).contiguous()
     Jv = fam.jac_vals(x).contiguous()
-    Jcv = fam.jacc_vals(x)          # the family's constraints are linear: one array serves the current and the trial point
-    # (the family hands out its own array; with compaction the state's rows change places, so the state gets a copy)
-    Jcv = (Jcv.clone() if compact else Jcv.contiguous()) if p else Z(B, 1)
+    Jcv = fam.jacc_vals(x)          # linear constraints: one array serves the current and the trial point
+    # (a linear family hands out its own array; with compaction the state's rows change places, so the state gets a copy)
+    Jcv = (Jcv.clone() if compact or nonlinear else Jcv.contiguous()) if p else Z(B, 1)
     cx = fam.cons(x).contiguous()
     r = Fx.clone()
     delta = t.ones(B, **f64)
@@ -431,6 +531,9 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     d = Z(B, N)
     xt, rt, lamt, Ft, ct = x.clone(), r.clone(), lam.clone(), Fx.clone(), cx.clone()
     Jt = Jv.clone()
+    # nonlinear constraints: Jcv belongs to the current point (the line search's dual part, the rejected-extrapolation branch, the
+    # small-residual check, the start-up multipliers), Jct to the trial point; cnl_outer_trial_done_dev copies Jct to Jcv on acceptance
+    Jct = Jcv.clone() if nonlinear else Jcv
     rhs_t, nrm_t = Z(B, N), Z(B, 2)
     d_new, rho_new, ro_tmp = Z(B, N), Z(B), Z(B)
     nf_new, ok_new = ZI(t.int32, B), ZI(t.int32, B)
@@ -449,7 +552,7 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
     arrays = dict(status=status, it=it, flags=flags, nf_new=nf_new, ok_new=ok_new, inner=inner, nfact=nfact, nlin=nlin, phase0=phase0,
                   normdual=normdual, normprimal=normprimal, combined=combined, combined_hat=combined_hat, delta=delta, ndh=ndh, nph=nph, fx=fx,
                   epsk=epsk, epstol=epstol, epsF=epsF, epsc=epsc, rho_old=rho_old, d=d, d_new=d_new, ro_tmp=ro_tmp, rho_new=rho_new,
-                  x=x, r=r, Fx=Fx, cx=cx, Jv=Jv, Jcv=Jcv, lam=lam, rhs_cur=rhs_cur, xt=xt, rt=rt, Ft=Ft, ct=ct, Jt=Jt, Jct=Jcv, lamt=lamt,
+                  x=x, r=r, Fx=Fx, cx=cx, Jv=Jv, Jcv=Jcv, lam=lam, rhs_cur=rhs_cur, xt=xt, rt=rt, Ft=Ft, ct=ct, Jt=Jt, Jct=Jct, lamt=lamt,
                   rhs_t=rhs_t, nrm_t=nrm_t, xt_e=xt_e, rt_e=rt_e, lamt_e=lamt_e, ls_g=rv_rhs, xl=xl, Fl=Fl, cl=cl, lam_ls=lam_ls, alpha=alpha,
                   Dphi=Dphi, phix=phix, eta=eta, nbk=nbk, **masks)
     for k, v in arrays.items():
@@ -562,7 +665,9 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
         hd(ct).copy_(fw.cons(hd(xt)))
         # ---- optimality measures at the trial point, :722-732; acceptance and the state update, :733-800
         hd(Jt).copy_(fw.jac_vals(hd(xt)))
-        resid_vectors(Jt, Jcv, rt, lamt, Ft, ct, rhs_t, nrm_t)
+        if nonlinear:
+            hd(Jct).copy_(fw.jacc_vals(hd(xt)))
+        resid_vectors(Jt, Jct, rt, lamt, Ft, ct, rhs_t, nrm_t)
         tk = tick("trial_eval", tk)
         chk_(k_trial_done(Sref, Cref, st))
         any_rej, any_chk = read_flags()[4:6]
@@ -601,7 +706,9 @@ def solve_batch_device(fam, params=None, max_steps=400, max_inner=10000, atol=No
            "iter": host(it), "nfact": host(nfact), "nlinsolve": host(nlin), "nbk": host(nbk), "neval": host(neval),
            "objective": host(fx), "dtype": str(dt), "r": host(r), "normdual": host(normdual),
            "normprimal": host(normprimal), "epstol": host(epstol), "steps": steps, "kernel": "band" if L.config.get("band") else L.config["kernel"], "vals_layout": "interleaved" if L.config.get("batch_layout") else "problem-major",
-           "loop_seconds": loop_seconds}   # the global steps alone (the symbolic analysis of the pattern and the start-up evaluations are not in it)
+           "loop_seconds": loop_seconds,   # the global steps alone (the symbolic analysis of the pattern and the start-up evaluations are not in it)
+           "jct_shared": S.Jct == S.Jcv,   # one constraint-Jacobian array for the current and the trial point (linear constraints)
+           "cgls_wide": L.config["cgls_wide"]}
     if vanishing:
         out["hess_skipped"] = host(hess_skipped)
     if compact:
@@ -634,6 +741,9 @@ def solve_batch_device_framework(fam, params=None, max_steps=400, max_inner=1000
     n, m, p = s.nvar, s.nequ, s.ncon
     N = n + m + p
     P = max(p, 1)
+    if p > 0 and not getattr(fam, "linear_constraints", True):
+        raise ValueError("solve_batch_device_framework restates the loop for linear constraints (H_c = 0, one constraint Jacobian): "
+                         "a family with nonlinear constraints runs in solve_batch_device")
     rows, cols, (nnzhF, nnzhc, nnzjF, nnzjc) = kkt_pattern_of(fam)
     nnz = len(rows)
     L = hipldl.HIPLDLStruct(N, rows, cols, None, n, m, p, batch=B, device=device_index, dtype=dt)

@@ -488,7 +488,8 @@ class HIPLDLStruct:
                        "direct": bool((int(cfg[5]) >> 36) & 1), "v2_solve": bool((int(cfg[5]) >> 37) & 1),
                        "refine": (int(cfg[5]) >> 39) & 7 if (int(cfg[5]) >> 38) & 1 else 0,
                        # staged handles: dataflow counters present; the in-kernel ladder (0 none, 1, 2 fused)
-                       "dataflow": bool((int(cfg[5]) >> 42) & 1), "lad_mode": (int(cfg[5]) >> 43) & 3}
+                       "dataflow": bool((int(cfg[5]) >> 42) & 1), "lad_mode": (int(cfg[5]) >> 43) & 3,
+                       "cgls_wide": (int(cfg[5]) >> 45) & 3}
         if self.config["float32"] and self.config["band"]:   # (a Float32 handle off the band kernels — tuning float32_general — is "v1")
             self.config["kernel"] = "band"
 
@@ -754,7 +755,8 @@ def cgls_multipliers_dev(LDLT, vals_ptr, r_ptr, lambda_ptr, Jxtr_ptr=0, atol=Non
                          stream=0):
     """Least-squares multipliers min ||Jc' lambda - Jx' r|| by CGLS (src/CaNNOLeS.jl:507-518), batched and device-resident
     (cnl_cgls_multipliers_dev / cnl_cgls_multipliers_f32_dev).  Default tolerances: sqrt(eps) of the handle's element type, as
-    Krylov.jl's."""
+    Krylov.jl's.  More than 1024 constraints: CnlError (CNL_ERR_DIM) unless the handle was created with Options(cgls_wide=1) (the
+    instance with its ncon-vectors in the handle's workspace where ncon > 1024; 2: always; config["cgls_wide"]); bit-equal results."""
     atol, rtol = _cgls_tols(LDLT, atol, rtol)
     fn = lib().cnl_cgls_multipliers_f32_dev if _is_f32(LDLT) else lib().cnl_cgls_multipliers_dev
     v, r, lam, jx = (_dev_ptr(LDLT, x) for x in (vals_ptr, r_ptr, lambda_ptr, Jxtr_ptr))

@@ -63,7 +63,7 @@ const char* cnl_last_error(void);
  * symbol; 0.4.3: tuning "float32_dense", no new symbol; 0.4.4: tuning "float32_general_dense", no new symbol;
  * 0.5.0: tuning "float32_refine" / "refine_rows", cnl_kkt_residual_dev, cnl_get_refine_norms, cnl_plan_get "kkt_row_*",
  * cnl_get_config bits 38 .. 41; 0.5.1: tuning "float32_staged", no new symbol; 0.5.2: tuning "float32_latency", cnl_get_config
- * bits 42 .. 44, no new symbol) */
+ * bits 42 .. 44, no new symbol; 0.5.3: tuning "cgls_wide", cnl_get_config bits 45 / 46, no new symbol) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -258,7 +258,12 @@ int cnl_deinterleave_dev(cnl_handle* h, int which, const double* d_src, double* 
  * reference obtains with `mul!(Jxtr, Jx', r); krylov_solve!(cgls_workspace, Jcx', Jxtr)` at src/CaNNOLeS.jl:507-518 and
  * :880-882: CGLS started at 0, stopped when ||Jc res|| <= atol + rtol ||Jc b|| or after itmax steps (itmax <= 0: nvar + ncon,
  * Krylov.jl's default; its default tolerances are sqrt(eps)).  ones_if_zero != 0 applies `if norm(lambda) == 0: lambda .= 1`
- * (:515-517).  d_Jxtr (optional) receives Jx' r, d_iters (optional) the iteration counts.  ncon <= 1024.
+ * (:515-517).  d_Jxtr (optional) receives Jx' r, d_iters (optional) the iteration counts.
+ * Number of constraints, tuning "cgls_wide" (all four entry points, cnl_cgls_multipliers[_jac][_f32]_dev; cnl_get_config bits 45 / 46 of
+ * cfg[5] report the value): 0 (the default) the kernel keeps its three ncon-vectors in LDS and ncon > 1024 is CNL_ERR_DIM with nothing
+ * launched; 1 a handle with ncon > 1024 runs the wide instance, whose ncon-vectors live in the handle's workspace (any ncon), every other
+ * handle the LDS instance; 2 the wide instance always.  The two instances do the same operations in the same order: bit-equal results.
+ * Any other value is CNL_ERR_ARG at creation.
  * itmax: any int64_t; <= 0 selects the default nvar + ncon, a value above INT_MAX (typemax(Int64) for "no limit") counts as INT_MAX. */
 int cnl_cgls_multipliers_dev(cnl_handle* h, const double* d_vals, const double* d_r, double* d_lambda, double* d_Jxtr, double atol,
                              double rtol, int64_t itmax, int ones_if_zero, int32_t* d_iters, void* stream);
