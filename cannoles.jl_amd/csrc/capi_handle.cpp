@@ -24,7 +24,10 @@ int choose_config(cnl_handle* h) {
   int64_t pb_off = std::max<int64_t>(P.fwd_peak, P.bwd_peak);
   pb_off = (pb_off + 1) & ~(int64_t)1;
   int64_t wv_off = pb_off + ((P.panel_max + 1) & ~1);
-  int64_t work = wv_off + 2 * (int64_t)((P.fmax + 1) & ~1);
+  // (tuning general_blocked: the panel buffer W[16][fmax] takes the place of the two staging vectors, and the work area is sized —
+  //  and placed in LDS or global scratch — with it whether or not the configuration chosen below has a blocked instance)
+  const bool want_blocked = h->plan->opt.general_blocked != 0 && !h->f32;
+  int64_t work = wv_off + (want_blocked ? 16 : 2) * (int64_t)((P.fmax + 1) & ~1);
   if (work >= ((int64_t)1 << 30))
     return fail(CNL_ERR_DIM, h->f32 ? "cnl_create_f32: work area too large (largest front of order " + std::to_string(P.fmax) + ")" : std::string("work area too large"));
   dp.pb_off = (int32_t)pb_off;
@@ -64,6 +67,7 @@ int choose_config(cnl_handle* h) {
   if (o.v1_ppb > 0) ppb = o.v1_ppb;
   if (o.v1_lds >= 0) ldsw = o.v1_lds;
   c.tpp = tpp; c.ppb = ppb; c.lds_work = ldsw;
+  c.blocked = want_blocked && cnl::newton_blocked_has(tpp, ppb);
   c.lds_bytes = hdr + (ldsw ? (size_t)ppb * per : 0);
   if (h->f32) {
     const std::string what = "tpp=" + std::to_string(tpp) + " ppb=" + std::to_string(ppb) + " lds=" + std::to_string(ldsw);
@@ -676,6 +680,10 @@ int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, co
     if (drc) return bail(fail(CNL_ERR_HIP, "dense backend: " + derr));
   }
   if ((rc = alloc_factor_storage(h))) return bail(rc);   // (band handles: the pad alone, see above)
+  if (h->cfg.blocked && !h->use_v2 && !h->band && !h->dense && !h->gdense) {   // (the handles cnl_get_config reports as blocked)
+    if ((rc = dalloc(h, &h->d_blk_ok, (size_t)batch))) return bail(rc);
+    if (hipMemset(h->d_blk_ok, 0, (size_t)batch * sizeof(int32_t)) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipMemset failed"));
+  }
   if ((rc = finish_handle(h, rows1, cols1))) return bail(rc);
   *hout = h;
   return CNL_OK;
@@ -809,6 +817,7 @@ int create_refined(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* row
                    int64_t batch, int device, const cnl::Tuning& o) {
   if (int rc = check_batch(batch)) return rc;
   if (int rc = check_f32_options(o, "cnl_create_ex")) return rc;
+  if (int rc = check_no_general_blocked(o, "cnl_create_ex (the inner Float32 handle of tuning float32_refine)")) return rc;
   if (int rc = check_device(device)) return rc;
   cnl::Tuning oi = o;
   oi.band_kernel = 0; oi.float32_refine = 0;
@@ -901,6 +910,7 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
   if (o.float32_refine)
     return fail(CNL_ERR_ARG, "cnl_create_f32: tuning float32_refine makes a Float64 handle on a Float32 factor: it is read by cnl_create_ex, not here");
   if (int rc = check_f32_options(o, "cnl_create_f32")) return rc;
+  if (int rc = check_no_general_blocked(o, "cnl_create_f32")) return rc;
   if (!o.band_kernel && !o.float32_general)
     return fail(CNL_ERR_ARG, "cnl_create_f32: cnl_options.band_kernel = 0, and Float32 handles run on the band kernels only (tuning float32_general = 1: "
                              "the general multifrontal kernel)");
@@ -1081,6 +1091,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   if (h->cond_resident) cfg[5] |= (int64_t)1 << 35;      // ... whose condensation runs the resident condense kernel (tuning float32_condense = 1)
   if (h->route == cnl::Route::Direct) cfg[5] |= (int64_t)1 << 36;                 // the Direct route (call_shape.h), either element type
   if (h->route == cnl::Route::Direct && h->v2_solve) cfg[5] |= (int64_t)1 << 37;  // ... on which solve_ldl! runs on the register-front kernel too
+  if (h->cfg.blocked && !h->f32 && !h->use_v2 && !dense_route && !on_band) cfg[5] |= (int64_t)1 << 47;   // newton_system / factorize run a blocked instance of the general kernel (tuning general_blocked)
   if (h->lean && !dense_route) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->staged && h->use_v2 && !dense_route) {          // staged handles: how the stages run
     if (h->d_dep) cfg[5] |= (int64_t)1 << 42;            // dataflow counters present (one launch per phase where the rule allows)

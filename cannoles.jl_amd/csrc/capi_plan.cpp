@@ -78,6 +78,8 @@ int resolve_options(const cnl_options* in, cnl::Tuning& out) {
     return fail(CNL_ERR_ARG, "cnl_options.tuning: float32_refine takes problem-major arrays: batch_layout = CNL_LAYOUT_INTERLEAVED is the band kernels' layout");
   if (out.refine_rows < 0 || out.refine_rows > 2)
     return fail(CNL_ERR_ARG, "cnl_options.tuning: refine_rows is 0 (by the pattern), 1 (a row per lane) or 2 (a row per wavefront)");
+  if (out.general_blocked < 0 || out.general_blocked > 1)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: general_blocked is 0 or 1 (the general kernel eliminates large fronts in panels of 16 pivots)");
   if (out.cgls_wide < 0 || out.cgls_wide > 2)
     return fail(CNL_ERR_ARG, "cnl_options.tuning: cgls_wide is 0 (the LDS instance, ncon <= 1024), 1 (the wide instance where ncon > 1024) or 2 (the wide instance always)");
   return CNL_OK;
@@ -265,6 +267,12 @@ int check_f32_options(const cnl::Tuning& o, const char* fn) {
   return CNL_OK;
 }
 
+int check_no_general_blocked(const cnl::Tuning& o, const char* fn) {
+  if (o.general_blocked)
+    return fail(CNL_ERR_ARG, std::string(fn) + ": tuning general_blocked = 1 is served by Float64 handles only (the blocked instances of the general kernel are double)");
+  return CNL_OK;
+}
+
 cnl::Tuning f32_unstaged_options(const cnl::Tuning& o) {
   cnl::Tuning u = o;
   u.float32_staged = 0; u.float32_latency = 0; u.float32_register_front = 1; u.float32_direct_records = 1;
@@ -412,7 +420,8 @@ const char* cnl_last_error(void) { return g_err.c_str(); }
 //        cnl_get_config bits 42 .. 44, no new symbol
 // 0.5.3: tuning cgls_wide (row f4 with its ncon-vectors in the global workspace: more than 1024 constraints), cnl_get_config bits 45 / 46,
 //        no new symbol
-int32_t cnl_version(void) { return 503; }
+// 0.5.4: tuning general_blocked (the general kernel's blocked instances, Float64), cnl_get_config bit 47, no new symbol
+int32_t cnl_version(void) { return 504; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62
@@ -462,6 +471,7 @@ int cnl_plan_create_ex(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* r
   if (rc) return rc;
   if (o.float32_refine) {   // the plan of the refined handle is its inner Float32 general handle's
     if ((rc = check_f32_options(o, "cnl_plan_create_ex"))) return rc;
+    if ((rc = check_no_general_blocked(o, "cnl_plan_create_ex (the inner Float32 handle of tuning float32_refine)"))) return rc;
     if (!plan) return fail(CNL_ERR_ARG, "null argument");
     return f32_general_plan(plan, N, nnz, rows1, cols1, nvar, nequ, ncon, o);
   }

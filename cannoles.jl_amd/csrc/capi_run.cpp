@@ -97,8 +97,11 @@ int launch(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
     e = h->f32 ? cnl::launch_newton2_f32(h->dp2, h->wpb2, h->lds2, a, stream) : cnl::launch_newton2(h->dp2, h->wpb2, h->lds2, a, stream);
     g_launches[1]++;
   } else {
+    if (h->d_blk_ok && a.mode == cnl::MODE_SOLVE) a.success = h->d_blk_ok;   // (a blocked handle: problems without a factor are skipped)
     e = h->f32 ? cnl::launch_newton_f32(h->dp, h->cfg, a, stream) : cnl::launch_newton(h->dp, h->cfg, a, stream);
     g_launches[2]++;
+    if (h->d_blk_ok && a.mode != cnl::MODE_SOLVE && a.success && e == hipSuccess)   // ... which these flags say, from here on
+      e = hipMemcpyAsync(h->d_blk_ok, a.success, (size_t)h->batch * sizeof(int32_t), hipMemcpyDeviceToDevice, stream);
   }
   if (e != hipSuccess)
     return fail(CNL_ERR_HIP, std::string("kernel launch (tpp=") + std::to_string(h->cfg.tpp) + " ppb=" + std::to_string(h->cfg.ppb) +
@@ -136,6 +139,8 @@ SubBatch::SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged) : 
   h->last_vals = elem_offset(h, h->last_vals, b0 * h->plan->nnz);
   if (!allow_staged) h->staged = false;
   batch = h->batch; L = h->d_L; gs = h->d_gs; scratch = h->d_scratch; cbuf = h->d_cbuf; d2 = h->d_d2;
+  blk_ok = h->d_blk_ok;
+  if (h->d_blk_ok) h->d_blk_ok += b0;
   xpos = h->d_xpos; xzer = h->d_xzer; gcnt = h->d_gcnt; dep = h->d_dep; lad = h->d_lad; stat = h->d_stat;
   Lband = h->d_Lband;
   h->d_Lband = elem_offset(h, h->d_Lband, b0 * h->bd.lsize);
@@ -154,6 +159,7 @@ SubBatch::SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged) : 
 
 SubBatch::~SubBatch() {
   h->batch = batch; h->d_L = L; h->d_gs = gs; h->d_scratch = scratch; h->d_cbuf = cbuf; h->d_d2 = d2;
+  h->d_blk_ok = blk_ok;
   h->d_xpos = xpos; h->d_xzer = xzer; h->d_gcnt = gcnt; h->d_dep = dep; h->d_lad = lad; h->d_stat = stat;
   h->last_vals = last_vals; h->staged = staged; h->d_Lband = Lband;
 }
@@ -361,7 +367,7 @@ int execute(cnl_handle* h, const cnl::CallShape& S, cnl::LaunchArgs& a, void* d_
       if (h->timing) HIPCHK(hipEventRecord(h->ev1, stream));
     } else if ((rc = launch(h, a, stream))) return rc;
   }
-  if (S.expand && (rc = expand(h, src, d_rhs, S.expand_d2 ? h->d_d2 : nullptr, d_d, S.expand_success ? a.success : nullptr, S.copy_rho_tail, stream))) return rc;
+  if (S.expand && (rc = expand(h, src, d_rhs, S.expand_d2 ? h->d_d2 : nullptr, d_d, S.expand_success ? a.success : !solves || factors ? nullptr : h->d_blk_ok, S.copy_rho_tail, stream))) return rc;
   return gdense ? end_timed(h, stream) : h->timing ? read_timing(h) : CNL_OK;
 }
 

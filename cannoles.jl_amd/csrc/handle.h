@@ -100,6 +100,10 @@ struct cnl_handle {
   void* d_cbuf = nullptr;   // [batch][cstride]
   void* d_d2 = nullptr;     // [batch][N2]
   int *d_xpos = nullptr, *d_xzer = nullptr;
+  // tuning general_blocked, where the general kernel's blocked instances serve the handle (cnl_get_config bit 47): the success flags of
+  // the last factorisation of every problem, copied behind each Newton / factorise launch; solve_ldl! leaves the rows of d of a
+  // problem without a factor untouched (the blocked instance and the expand pass read them)
+  int32_t* d_blk_ok = nullptr;
   // Float32 general handles on a condensed plan: the resident condense kernel serves the handle (kernels.h: DevCondEll) — where the
   // tiled kernel's chunks degenerate (dense Jacobians) and [vals | rhs] of a problem fits LDS; tuning float32_condense = 2: never
   bool cond_resident = false;
@@ -313,6 +317,8 @@ cnl::Tuning f32_unstaged_options(const cnl::Tuning& o);
 bool f32_general_dense_fits(const cnl_plan* plan, int64_t batch);
 // what every creator checks of the float32_* keys (fn: the creator's name, for the message)
 int check_f32_options(const cnl::Tuning& o, const char* fn);
+// tuning general_blocked on a creator of Float32 state (cnl_create_f32*, the inner handle of float32_refine): CNL_ERR_ARG
+int check_no_general_blocked(const cnl::Tuning& o, const char* fn);
 
 // ---- capi_handle.cpp ----
 int ensure_kkt_rows(cnl_handle* h);   // h->dkkt on the device
@@ -342,6 +348,7 @@ struct SubBatch {
   int64_t batch;
   void *L, *gs, *scratch, *cbuf, *d2, *Lband;
   int *xpos, *xzer, *gcnt, *dep, *lad, *stat;
+  int32_t* blk_ok;
   const void* last_vals;
   bool staged;
   SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged = true);

@@ -93,9 +93,120 @@ struct ProblemCtx {
 };
 
 // ---------------------------------------------------------------------------
+// Blocked elimination (tuning general_blocked): the pivots of a front leave in PANELS of up to PANEL_W, and what
+// a panel owes the rows below it is one product on the fp64 matrix cores instead of PANEL_W sweeps over the packed triangle.
+constexpr int PANEL_W = 16;
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+// F[a][b] -= sum_k L[k][a] W[k][b] for b <= a < lim, k < kp: L[k] is the scaled row of the panel's pivot p0 + k (in place in F),
+// W[k] its unscaled copy (Wp, stride ws).  16 x 16 tiles of the packed triangle, dealt round-robin to the wavefronts of the
+// workgroup; one tile is four v_mfma_f64_16x16x4_f64 on two accumulator chains (dense.hip, update_block).  Operand layout: lane l
+// holds A[row l & 15][k = l >> 4] and B[k = l >> 4][column l & 15]; result register r of lane l is row (l >> 4) + 4 r, column
+// l & 15.  Rows and columns beyond lim and panel slots beyond kp enter as zeros (selected, not multiplied: the slots may hold
+// anything); a diagonal tile computes the whole tile and stores b <= a.  The trip count depends on the wavefront alone.
+template <int TPP>
+__device__ __forceinline__ void panel_trailing_update(double* F, const double* Wp, int ws, int p0, int kp, int lim, int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 15, lg = lane >> 4;
+  const int nt = (lim + PANEL_W - 1) / PANEL_W, ntiles = tri_i(nt);
+  for (int t = wave; t < ntiles; t += TPP / 64) {
+    int ta, tb;
+    tri_decode(t, ta, tb);
+    const int ar = PANEL_W * ta + li, bc = PANEL_W * tb + li;
+    double aop[4], bop[4];
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+      const int k = 4 * s + lg;
+      aop[s] = (k < kp && ar < lim) ? -F[tri_i(p0 + k) + ar] : 0.0;
+      bop[s] = (k < kp && bc < lim) ? Wp[k * ws + bc] : 0.0;
+    }
+    d4 acc, acc2 = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int a = PANEL_W * ta + lg + 4 * r;
+      acc[r] = (a < lim && bc <= a) ? F[tri_i(a) + bc] : 0.0;
+    }
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[0], bop[0], acc, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[1], bop[1], acc2, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[2], bop[2], acc, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[3], bop[3], acc2, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int a = PANEL_W * ta + lg + 4 * r;
+      if (a < lim && bc <= a) F[tri_i(a) + bc] = acc[r] + acc2[r];
+    }
+  }
+}
+
+// The blocked twin of the WITH_K elimination loop of front_forward, for a front with at least PANEL_W pivots: panels from the highest
+// local index down, the last one of a kind as narrow as it comes.  The leading H.indep pivots (local index >= idep) do not touch
+// each other: their panels need no step inside the panel and their trailing triangle ends at idep.  A dependent panel runs its
+// pivots one by one — pivot read after every earlier pivot's update has reached it, counted against eig_tol, row kept unscaled in
+// W, scaled in place, rank-1 update of the rows of the panel still to come (a contiguous piece of the packed triangle) — and then
+// updates everything below it at once.
+template <int TPP, bool LDSW>
+__device__ __forceinline__ void eliminate_blocked(const DevPlan& P, double* F, double* Wp, int f, int nupd, int idep, int tid, double eig_tol,
+                                                  int& npos, int& nzer) {
+  const int ws = P.fmax;
+  int p1 = f;
+  while (p1 > nupd + 1) {
+    const bool indep = p1 > idep;
+    const int floor_ = indep ? idep : nupd + 1;
+    const int p0 = p1 - PANEL_W > floor_ ? p1 - PANEL_W : floor_;
+    const int kp = p1 - p0;
+    const int lim = indep ? idep : p0;
+    if (indep) {
+      for (int k = 0; k < kp; k++) {
+        double* rowi = F + tri_i(p0 + k);
+        double* wk = Wp + k * ws;
+        const double dpiv = rowi[p0 + k];
+        npos += dpiv > eig_tol;
+        nzer += abs_of(dpiv) <= eig_tol;
+        for (int j = tid; j < lim; j += TPP) {
+          const double w = rowi[j];
+          wk[j] = w;
+          rowi[j] = w / dpiv;
+        }
+      }
+      psync<TPP, LDSW>();
+    } else {
+      for (int k = kp - 1; k >= 0; k--) {
+        const int i = p0 + k;
+        double* rowi = F + tri_i(i);
+        double* wk = Wp + k * ws;
+        const double dpiv = rowi[i];
+        npos += dpiv > eig_tol;
+        nzer += abs_of(dpiv) <= eig_tol;
+        for (int j = tid; j < i; j += TPP) {
+          const double w = rowi[j];
+          wk[j] = w;
+          rowi[j] = w / dpiv;
+        }
+        psync<TPP, LDSW>();
+        const int t0 = tri_i(p0), t1 = tri_i(i);   // rows p0 .. i - 1 of the packed triangle
+        if (t0 + tid < t1) {
+          int a, b;
+          tri_decode(t0 + tid, a, b);
+          for (int t = t0 + tid; t < t1; t += TPP) {
+            F[t] -= rowi[a] * wk[b];
+            b += TPP;
+            while (b > a) { b -= a + 1; a++; }
+          }
+        }
+        psync<TPP, LDSW>();
+      }
+    }
+    panel_trailing_update<TPP>(F, Wp, ws, p0, kp, lim, tid);
+    psync<TPP, LDSW>();
+    p1 = p0;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // forward pass over one front: assemble, extend-add, eliminate the pivots,
 // store the L panel, leave the update matrix for the parent.
-template <int TPP, bool LDSW, bool WITH_K, class T>
+// BLK (double, TPP a multiple of 64): fronts with at least PANEL_W pivots are eliminated by eliminate_blocked
+template <int TPP, bool LDSW, bool WITH_K, class T, bool BLK = false>
 __device__ __forceinline__ void front_forward(const DevPlan& P, const FrontHdr& H, const ProblemCtx<T>& c, int tid,
                                               bool rho_override, T rho, T eig_tol, int& npos, int& nzer) {
   const int nupd = H.nupd, npiv = H.npiv;
@@ -159,7 +270,12 @@ __device__ __forceinline__ void front_forward(const DevPlan& P, const FrontHdr& 
   if (WITH_K) {
     T* wv0 = c.W + P.wv_off;
     const int idep = f - H.indep;  // pivots with local index >= idep are mutually independent
-    for (int i = f - 1; i > nupd; i--) {
+    bool blocked = false;
+    if constexpr (BLK) {
+      blocked = npiv >= PANEL_W;
+      if (blocked) eliminate_blocked<TPP, LDSW>(P, F, wv0, f, nupd, idep, tid, eig_tol, npos, nzer);
+    }
+    for (int i = blocked ? nupd : f - 1; i > nupd; i--) {
       const int ulim = i >= idep ? idep : i;
       T* rowi = F + tri_i(i);
       T* wv = wv0 + ((i & 1) ? P.fmax : 0);
@@ -259,11 +375,11 @@ __device__ __forceinline__ void front_backward(const DevPlan& P, const FrontHdr&
   }
 }
 
-template <int TPP, bool LDSW, class T>
+template <int TPP, bool LDSW, class T, bool BLK>
 __device__ __forceinline__ bool factor_attempt(const DevPlan& P, const ProblemCtx<T>& c, int tid, bool rho_override, T rho,
                                                T eig_tol, int& npos_out, int& nzer_out, int xpos, int xzer) {
   int npos = xpos, nzer = xzer;
-  for (int s = 0; s < P.nsuper; s++) front_forward<TPP, LDSW, true>(P, P.fronts[s], c, tid, rho_override, rho, eig_tol, npos, nzer);
+  for (int s = 0; s < P.nsuper; s++) front_forward<TPP, LDSW, true, T, BLK>(P, P.fronts[s], c, tid, rho_override, rho, eig_tol, npos, nzer);
   npos_out = npos; nzer_out = nzer;
   return npos == P.nvar && nzer == 0;  // src/solver_types.jl:96
 }
@@ -273,7 +389,9 @@ __device__ __forceinline__ T* as_global(T* p) {  // struct members are generic p
   return (T*)(__attribute__((address_space(1))) T*)p;
 }
 
-template <int TPP, int PPB, bool LDSW, class T>
+// BLK: the blocked elimination of large fronts (tuning general_blocked; double, PPB = 1, TPP 256 or 1024: launch_newton); MODE_SOLVE
+// of such an instance reads A.success
+template <int TPP, int PPB, bool LDSW, class T, bool BLK = false>
 __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, const LaunchArgs Ain) {
   DevPlan P = Pin;
   P.fronts = as_global(Pin.fronts); P.seg_ptr = as_global(Pin.seg_ptr); P.asm_pos = as_global(Pin.asm_pos);
@@ -308,6 +426,11 @@ __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, con
   const int xpos = A.extra_pos ? A.extra_pos[b] : 0, xzer = A.extra_zer ? A.extra_zer[b] : 0;
 
   if (A.mode == MODE_SOLVE) {
+    // a blocked handle keeps the success flags of its last factorisation (launch(), capi_run.cpp): a problem that holds no factor is
+    // left alone, its rows of d untouched (one problem per workgroup: the whole workgroup leaves)
+    if constexpr (BLK) {
+      if (A.success && !A.success[b]) return;
+    }
     int np = 0, nz = 0;
     for (int s = 0; s < P.nsuper; s++) front_forward<TPP, LDSW, false>(P, P.fronts[s], c, tid, false, T(0), eig_tol, np, nz);
     phase_fence<TPP>();
@@ -317,7 +440,7 @@ __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, con
   if (A.mode == MODE_FACTOR) {
     int np, nz;
     ProblemCtx<T> cf = c; cf.rhs = nullptr;
-    const bool ok = factor_attempt<TPP, LDSW>(P, cf, tid, false, T(0), eig_tol, np, nz, xpos, xzer);
+    const bool ok = factor_attempt<TPP, LDSW, T, BLK>(P, cf, tid, false, T(0), eig_tol, np, nz, xpos, xzer);
     if (tid == 0) {
       A.success[b] = ok ? 1 : 0;
       if (A.npos) A.npos[b] = np;
@@ -331,18 +454,18 @@ __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, con
   T rho_old = a_rho_old[b];
   T rho = T(0), wrote = T(0);
   int nfact = 0, np, nz;
-  bool success = factor_attempt<TPP, LDSW>(P, c, tid, false, T(0), eig_tol, np, nz, xpos, xzer);
+  bool success = factor_attempt<TPP, LDSW, T, BLK>(P, c, tid, false, T(0), eig_tol, np, nz, xpos, xzer);
   nfact++;
   if (!success) {
     rho = rho_old == T(0) ? rho0 : max_of(rhomin, kdec * rho_old);
     wrote = rho;
-    success = factor_attempt<TPP, LDSW>(P, c, tid, true, rho, eig_tol, np, nz, xpos, xzer);
+    success = factor_attempt<TPP, LDSW, T, BLK>(P, c, tid, true, rho, eig_tol, np, nz, xpos, xzer);
     nfact++;
     while (!success && rho <= rhomax) {
       rho = rho_old == T(0) ? klarge * rho : kinc * rho;
       if (rho <= rhomax) {
         wrote = rho;
-        success = factor_attempt<TPP, LDSW>(P, c, tid, true, rho, eig_tol, np, nz, xpos, xzer);
+        success = factor_attempt<TPP, LDSW, T, BLK>(P, c, tid, true, rho, eig_tol, np, nz, xpos, xzer);
         nfact++;
       }
     }
@@ -369,9 +492,9 @@ size_t max_lds_bytes() {
   return (size_t)v;
 }
 
-template <int TPP, int PPB, bool LDSW, class T>
+template <int TPP, int PPB, bool LDSW, class T, bool BLK = false>
 static hipError_t launch_t(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream) {
-  auto kfn = newton_kernel<TPP, PPB, LDSW, T>;
+  auto kfn = newton_kernel<TPP, PPB, LDSW, T, BLK>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)cfg.lds_bytes));
   if (e != hipSuccess) return e;
   const int grid = (a.batch + PPB - 1) / PPB;
@@ -379,7 +502,19 @@ static hipError_t launch_t(const DevPlan& P, const KernelConfig& cfg, const Laun
   return hipGetLastError();
 }
 
+// the configurations with a blocked instance (tuning general_blocked): whole workgroups of several wavefronts on one problem
+bool newton_blocked_has(int tpp, int ppb) { return ppb == 1 && (tpp == 256 || tpp == 1024); }
+
 hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream) {
+  // (solve_ldl! runs the same sweeps on the factor a blocked launch left; given the flags of that factorisation in a.success it runs
+  //  them in the blocked instance, which skips the problems that hold no factor)
+  if (cfg.blocked && (a.mode != MODE_SOLVE || a.success)) {
+#define CNL_CASE(T, W) \
+  if (cfg.tpp == T && cfg.ppb == 1 && (cfg.lds_work != 0) == W) return launch_t<T, 1, W, double, true>(P, cfg, a, stream);
+    CNL_CASE(256, true) CNL_CASE(1024, true) CNL_CASE(256, false) CNL_CASE(1024, false)
+#undef CNL_CASE
+    return hipErrorInvalidConfiguration;
+  }
 #define CNL_CASE(T, B, W) \
   if (cfg.tpp == T && cfg.ppb == B && (cfg.lds_work != 0) == W) return launch_t<T, B, W, double>(P, cfg, a, stream);
   CNL_CASE(64, 16, true) CNL_CASE(64, 8, true) CNL_CASE(64, 4, true) CNL_CASE(64, 2, true) CNL_CASE(64, 1, true)

@@ -146,7 +146,9 @@ def Options(**kw):
     float32_general_dense, float32_refine, and float32_staged = 1: latency plans of Float32 general handles run stage by stage on the
     float register-front kernel; float32_latency = 1: float32_staged plus the lean, dataflow and fused-ladder float instances, switched
     by lean_kernel, rows_in_backward, dataflow, dataflow_waves, dataflow_spin_limit, device_ladder and device_ladder_fused as on a
-    Float64 handle) are described with HIPLDLStruct."""
+    Float64 handle) are described with HIPLDLStruct.  general_blocked = 1 (Float64 handles only): the general kernel eliminates fronts with
+    16 pivots or more in panels of 16 with the trailing updates on the f64 matrix cores; config["general_blocked"] says whether the
+    handle's launches are a blocked instance."""
     o = cnl_options()
     lib().cnl_options_init(C.byref(o))
     assert o.struct_size == C.sizeof(cnl_options), "cnl_options layout differs from the library's"
@@ -489,7 +491,9 @@ class HIPLDLStruct:
                        "refine": (int(cfg[5]) >> 39) & 7 if (int(cfg[5]) >> 38) & 1 else 0,
                        # staged handles: dataflow counters present; the in-kernel ladder (0 none, 1, 2 fused)
                        "dataflow": bool((int(cfg[5]) >> 42) & 1), "lad_mode": (int(cfg[5]) >> 43) & 3,
-                       "cgls_wide": (int(cfg[5]) >> 45) & 3}
+                       "cgls_wide": (int(cfg[5]) >> 45) & 3,
+                       # newton_system / factorize run a blocked instance of the general kernel (Options(general_blocked=1))
+                       "general_blocked": bool((int(cfg[5]) >> 47) & 1)}
         if self.config["float32"] and self.config["band"]:   # (a Float32 handle off the band kernels — tuning float32_general — is "v1")
             self.config["kernel"] = "band"
 

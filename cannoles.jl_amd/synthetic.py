@@ -242,6 +242,42 @@ def random_structure(n, m, p, density, seed, hess=True, name="random"):
     return Structure(n, m, p, hF, hc, jF, jc, name=name)
 
 
+def grid_structure(G, p=0, name="grid"):
+    """Five-point 2-D grid family: G x G variables in row-major order, one residual per grid point that reads the point and its
+    (up to four) neighbours, rows of J_F in row-major order with ascending columns; H_F the lower-triangle pairs of every stencil,
+    each position once, column-major; p constraint rows, row k on the G variables of grid row (k G) // p, H_c diagonal.  An
+    irregular pattern in the sense of the plan: nested dissection leaves separators of order ~G, so the fronts grow with the grid
+    (random_values serves it as is)."""
+    n = G * G
+    r, c = np.divmod(np.arange(n), G)
+    jr, jc = [], []
+    for dr, dc in ((-1, 0), (0, -1), (0, 0), (0, 1), (1, 0)):
+        ok = (r + dr >= 0) & (r + dr < G) & (c + dc >= 0) & (c + dc < G)
+        jr.append(np.arange(n)[ok])
+        jc.append(((r + dr) * G + c + dc)[ok])
+    jr, jc = np.concatenate(jr), np.concatenate(jc)
+    o = np.lexsort((jc, jr))
+    jr, jc = jr[o], jc[o]
+    pairs = set()
+    start = np.searchsorted(jr, np.arange(n + 1))
+    for i in range(n):
+        st = jc[start[i]:start[i + 1]]
+        for a in st:
+            for b in st:
+                if a >= b:
+                    pairs.add((int(b), int(a)))   # (column, row): sorted column-major
+    pairs = np.array(sorted(pairs), np.int64)
+    hF = (pairs[:, 1] + 1, pairs[:, 0] + 1)
+    z = np.zeros(0, np.int64)
+    if p > 0:
+        gr = (np.arange(p) * G) // p
+        jcs = (np.repeat(np.arange(1, p + 1), G), (gr[:, None] * G + np.arange(G)[None, :]).ravel() + 1)
+        hc = (np.arange(1, n + 1), np.arange(1, n + 1))
+    else:
+        jcs, hc = (z, z), (z, z)
+    return Structure(n, n, p, hF, hc, (jr + 1, jc + 1), jcs, name=name, meta={"G": G})
+
+
 def random_values(s, seed, delta=0.1, posdef=True):
     rng = np.random.default_rng(seed)
     off = s.offsets()

@@ -63,7 +63,8 @@ const char* cnl_last_error(void);
  * symbol; 0.4.3: tuning "float32_dense", no new symbol; 0.4.4: tuning "float32_general_dense", no new symbol;
  * 0.5.0: tuning "float32_refine" / "refine_rows", cnl_kkt_residual_dev, cnl_get_refine_norms, cnl_plan_get "kkt_row_*",
  * cnl_get_config bits 38 .. 41; 0.5.1: tuning "float32_staged", no new symbol; 0.5.2: tuning "float32_latency", cnl_get_config
- * bits 42 .. 44, no new symbol; 0.5.3: tuning "cgls_wide", cnl_get_config bits 45 / 46, no new symbol) */
+ * bits 42 .. 44, no new symbol; 0.5.3: tuning "cgls_wide", cnl_get_config bits 45 / 46, no new symbol;
+ * 0.5.4: tuning "general_blocked", cnl_get_config bit 47, no new symbol) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -460,7 +461,20 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  * + 128 when cnl_residual_vectors_dev runs on column tiles,
  * bit 36 = the handle runs on the Direct route: the register-front kernel condenses on the fly from the caller's vals (no
  *   stand-alone condensation pass in front of the launch), either element type,
- * bit 37 = ... and cnl_solve* runs on the register-front kernel too (every front of the fast class). */
+ * bit 37 = ... and cnl_solve* runs on the register-front kernel too (every front of the fast class),
+ * bit 47 = cnl_newton_system* / cnl_factorize* run a BLOCKED instance of the general kernel (tuning "general_blocked=1", below).
+ *
+ * Tuning "general_blocked" (0 default, 1; any other value CNL_ERR_ARG): on a Float64 handle whose newton_system / factorize launches
+ * are the general kernel's (cfg[5] & 15 == 1) with 256 or 1024 threads per problem and one problem per workgroup, a front with 16
+ * pivots or more is eliminated in panels of 16 pivots — the pivots of a panel one by one against the rows of the panel, then ONE
+ * update of everything below the panel on the f64 matrix cores — instead of one sweep over the whole front per pivot.  Same
+ * factor layout and solve sweeps, same inertia rule; such a handle keeps the success flags of its last factorisation, and cnl_solve*
+ * leaves the rows of d of a problem whose factorisation failed untouched (without the key the general kernel overwrites them);
+ * the sums of an update are formed in another order, so d agrees with the key off to rounding, not bit for bit.  The work area grows by 14 rows of the largest front (it may move from LDS
+ * to global scratch: cfg[3]).  A handle whose configuration has no blocked instance (64 threads per problem or fewer, the
+ * register-front kernel, the band kernels, the dense backend) runs as without the key and reports bit 47 clear.  There are no
+ * Float32 instances: cnl_create_f32* with the key, and the key together with "float32_refine", are CNL_ERR_ARG.  cnl_multi shards
+ * inherit it.  Measured: DESIGN section 3.1. */
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
 /* (bit 38 = a refined handle — tuning "float32_refine", below —, bits 39-41 = its refinement steps k; every other word and bit
  *  describes its inner Float32 handle, with bit 27 clear: the handle is a Float64 handle.) */
