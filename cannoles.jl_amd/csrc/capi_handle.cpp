@@ -24,9 +24,10 @@ int choose_config(cnl_handle* h) {
   int64_t pb_off = std::max<int64_t>(P.fwd_peak, P.bwd_peak);
   pb_off = (pb_off + 1) & ~(int64_t)1;
   int64_t wv_off = pb_off + ((P.panel_max + 1) & ~1);
-  // (tuning general_blocked: the panel buffer W[16][fmax] takes the place of the two staging vectors, and the work area is sized —
-  //  and placed in LDS or global scratch — with it whether or not the configuration chosen below has a blocked instance)
-  const bool want_blocked = h->plan->opt.general_blocked != 0 && !h->f32;
+  // (tuning general_blocked, on a Float32 handle float32_blocked: the panel buffer W[16][fmax] takes the place of the two staging
+  //  vectors, and the work area is sized — and placed in LDS or global scratch — with it whether or not the configuration chosen below
+  //  has a blocked instance; elements of the handle's type)
+  const bool want_blocked = h->f32 ? h->plan->opt.float32_blocked != 0 : h->plan->opt.general_blocked != 0;
   int64_t work = wv_off + (want_blocked ? 16 : 2) * (int64_t)((P.fmax + 1) & ~1);
   if (work >= ((int64_t)1 << 30))
     return fail(CNL_ERR_DIM, h->f32 ? "cnl_create_f32: work area too large (largest front of order " + std::to_string(P.fmax) + ")" : std::string("work area too large"));
@@ -67,7 +68,7 @@ int choose_config(cnl_handle* h) {
   if (o.v1_ppb > 0) ppb = o.v1_ppb;
   if (o.v1_lds >= 0) ldsw = o.v1_lds;
   c.tpp = tpp; c.ppb = ppb; c.lds_work = ldsw;
-  c.blocked = want_blocked && cnl::newton_blocked_has(tpp, ppb);
+  c.blocked = want_blocked && cnl::newton_blocked_has(tpp, ppb, h->f32);
   c.lds_bytes = hdr + (ldsw ? (size_t)ppb * per : 0);
   if (h->f32) {
     const std::string what = "tpp=" + std::to_string(tpp) + " ppb=" + std::to_string(ppb) + " lds=" + std::to_string(ldsw);
@@ -80,6 +81,16 @@ int choose_config(cnl_handle* h) {
     return CNL_OK;
   }
   if (c.lds_bytes > maxlds) return fail(CNL_ERR_DIM, "kernel configuration exceeds LDS");
+  return CNL_OK;
+}
+
+// The success flags a blocked handle keeps (handle.h: d_blk_ok), for the handles cnl_get_config reports as blocked (bit 47, in float
+// bit 48): the Newton / factorise launches are the general kernel's, in a configuration with a blocked instance.  No flag set: no
+// problem holds a factor yet.
+int alloc_blocked_flags(cnl_handle* h) {
+  if (!h->cfg.blocked || h->use_v2 || h->band || h->dense || h->gdense) return CNL_OK;
+  if (int rc = dalloc(h, &h->d_blk_ok, (size_t)h->batch)) return rc;
+  if (hipMemset(h->d_blk_ok, 0, (size_t)h->batch * sizeof(int32_t)) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
   return CNL_OK;
 }
 
@@ -680,10 +691,7 @@ int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, co
     if (drc) return bail(fail(CNL_ERR_HIP, "dense backend: " + derr));
   }
   if ((rc = alloc_factor_storage(h))) return bail(rc);   // (band handles: the pad alone, see above)
-  if (h->cfg.blocked && !h->use_v2 && !h->band && !h->dense && !h->gdense) {   // (the handles cnl_get_config reports as blocked)
-    if ((rc = dalloc(h, &h->d_blk_ok, (size_t)batch))) return bail(rc);
-    if (hipMemset(h->d_blk_ok, 0, (size_t)batch * sizeof(int32_t)) != hipSuccess) return bail(fail(CNL_ERR_HIP, "hipMemset failed"));
-  }
+  if ((rc = alloc_blocked_flags(h))) return bail(rc);
   if ((rc = finish_handle(h, rows1, cols1))) return bail(rc);
   *hout = h;
   return CNL_OK;
@@ -755,6 +763,7 @@ int create_f32_general_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_
       return bail(fail(CNL_ERR_HIP, "dense backend (Float32): " + derr));
   }
   if ((rc = alloc_factor_storage(h))) return bail(rc);
+  if ((rc = alloc_blocked_flags(h))) return bail(rc);   // (tuning float32_blocked)
   if ((rc = finish_handle(h, rows1, cols1))) return bail(rc);
   *hout = h;
   return CNL_OK;
@@ -1091,7 +1100,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   if (h->cond_resident) cfg[5] |= (int64_t)1 << 35;      // ... whose condensation runs the resident condense kernel (tuning float32_condense = 1)
   if (h->route == cnl::Route::Direct) cfg[5] |= (int64_t)1 << 36;                 // the Direct route (call_shape.h), either element type
   if (h->route == cnl::Route::Direct && h->v2_solve) cfg[5] |= (int64_t)1 << 37;  // ... on which solve_ldl! runs on the register-front kernel too
-  if (h->cfg.blocked && !h->f32 && !h->use_v2 && !dense_route && !on_band) cfg[5] |= (int64_t)1 << 47;   // newton_system / factorize run a blocked instance of the general kernel (tuning general_blocked)
+  if (h->cfg.blocked && !h->use_v2 && !dense_route && !on_band) cfg[5] |= (int64_t)1 << (h->f32 ? 48 : 47);   // newton_system / factorize run a blocked instance of the general kernel (bit 47: Float64, tuning general_blocked; bit 48: Float32, tuning float32_blocked)
   if (h->lean && !dense_route) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->staged && h->use_v2 && !dense_route) {          // staged handles: how the stages run
     if (h->d_dep) cfg[5] |= (int64_t)1 << 42;            // dataflow counters present (one launch per phase where the rule allows)

@@ -264,12 +264,18 @@ int check_f32_options(const cnl::Tuning& o, const char* fn) {
     return fail(CNL_ERR_ARG, f + ": tuning float32_latency = 1 needs float32_general = 1 (the latency path in float serves Float32 general handles)");
   if (o.float32_latency && o.float32_refine)
     return fail(CNL_ERR_ARG, f + ": tuning float32_latency = 1 does not go with float32_refine (no refined handle over a staged Float32 factor)");
+  if (o.float32_blocked < 0 || o.float32_blocked > 1)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_blocked is 0 or 1 (the general kernel in float eliminates large fronts in panels of 16 pivots)");
+  if (o.float32_blocked && !o.float32_general)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_blocked = 1 needs float32_general = 1 (the blocked float instances of the general kernel serve Float32 general handles)");
+  if (o.float32_blocked && o.float32_refine)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_blocked = 1 does not go with float32_refine (no refined handle over a blocked Float32 factor)");
   return CNL_OK;
 }
 
 int check_no_general_blocked(const cnl::Tuning& o, const char* fn) {
   if (o.general_blocked)
-    return fail(CNL_ERR_ARG, std::string(fn) + ": tuning general_blocked = 1 is served by Float64 handles only (the blocked instances of the general kernel are double)");
+    return fail(CNL_ERR_ARG, std::string(fn) + ": tuning general_blocked = 1 is served by Float64 handles only (a Float32 general handle takes its blocked instances with tuning float32_blocked)");
   return CNL_OK;
 }
 
@@ -421,7 +427,9 @@ const char* cnl_last_error(void) { return g_err.c_str(); }
 // 0.5.3: tuning cgls_wide (row f4 with its ncon-vectors in the global workspace: more than 1024 constraints), cnl_get_config bits 45 / 46,
 //        no new symbol
 // 0.5.4: tuning general_blocked (the general kernel's blocked instances, Float64), cnl_get_config bit 47, no new symbol
-int32_t cnl_version(void) { return 504; }
+// 0.5.5: tuning float32_blocked (the general kernel's blocked instances in float, for Float32 general handles), cnl_get_config bit 48,
+//        no new symbol
+int32_t cnl_version(void) { return 505; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62

@@ -100,7 +100,8 @@ struct cnl_handle {
   void* d_cbuf = nullptr;   // [batch][cstride]
   void* d_d2 = nullptr;     // [batch][N2]
   int *d_xpos = nullptr, *d_xzer = nullptr;
-  // tuning general_blocked, where the general kernel's blocked instances serve the handle (cnl_get_config bit 47): the success flags of
+  // tuning general_blocked (a Float32 handle: float32_blocked), where the general kernel's blocked instances serve the handle
+  // (cnl_get_config bit 47, in float bit 48; capi_handle.cpp: alloc_blocked_flags): the success flags of
   // the last factorisation of every problem, copied behind each Newton / factorise launch; solve_ldl! leaves the rows of d of a
   // problem without a factor untouched (the blocked instance and the expand pass read them)
   int32_t* d_blk_ok = nullptr;

@@ -20,7 +20,7 @@ struct DevPlan {
   int32_t nsuper, N, nnz, rho_begin, nvar, nequ, ncon;
   int32_t fmax;
   int32_t pb_off;        // offset (elements: doubles, or floats on a Float32 handle) of the panel buffer inside a problem's work area
-  int32_t wv_off;        // offset of the two pivot-row staging vectors (2*fmax elements; tuning general_blocked: the panel buffer W, 16*fmax)
+  int32_t wv_off;        // offset of the two pivot-row staging vectors (2*fmax elements; tuning general_blocked / float32_blocked: the panel buffer W, 16*fmax)
   int32_t work_doubles;  // work area per problem (elements)
   int64_t lsize;         // factor storage per problem (elements)
   int64_t vstride, rstride, dstride;  // per-problem strides (elements) of vals / rhs / d
@@ -31,7 +31,7 @@ struct KernelConfig {
   int ppb = 1;           // problems per workgroup
   int lds_work = 1;      // work area in LDS (else global scratch)
   size_t lds_bytes = 0;  // dynamic LDS per workgroup
-  int blocked = 0;       // MODE_NEWTON / MODE_FACTOR run the blocked instance (tuning general_blocked; newton_blocked_has)
+  int blocked = 0;       // MODE_NEWTON / MODE_FACTOR run the blocked instance (tuning general_blocked, float32_blocked on a Float32 handle; newton_blocked_has)
 };
 
 // device-resident v2 plan (record streams, see plan.h / kernels2.hip); elements: doubles, or floats on a Float32 handle
@@ -207,7 +207,7 @@ hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const Launch
 // float; any other is hipErrorInvalidConfiguration.
 hipError_t launch_newton_f32(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream);
 bool newton_f32_has(int tpp, int ppb, bool lds_work);
-bool newton_blocked_has(int tpp, int ppb);   // is there a blocked Float64 instance (cfg.blocked) for this configuration?
+bool newton_blocked_has(int tpp, int ppb, bool f32 = false);   // is there a blocked instance (cfg.blocked) of the element type for this configuration?
 hipError_t launch_newton2(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream);
 // the register-front kernel on Float32 data (a Float32 general handle with tuning float32_register_front): every size of P named
 // "doubles" counts floats, lds_bytes is computed with 4-byte elements (the record area stays in 32-bit words).  Direct records with

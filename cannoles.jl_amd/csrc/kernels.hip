@@ -93,19 +93,40 @@ struct ProblemCtx {
 };
 
 // ---------------------------------------------------------------------------
-// Blocked elimination (tuning general_blocked): the pivots of a front leave in PANELS of up to PANEL_W, and what
-// a panel owes the rows below it is one product on the fp64 matrix cores instead of PANEL_W sweeps over the packed triangle.
+// Blocked elimination (tuning general_blocked, and float32_blocked on a Float32 handle): the pivots of a front
+// leave in PANELS of up to PANEL_W, and what a panel owes the rows below it is one product on the matrix cores instead of PANEL_W
+// sweeps over the packed triangle.
 constexpr int PANEL_W = 16;
 typedef double d4 __attribute__((ext_vector_type(4)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+// The 16 x 16 x 4 matrix-core instruction of an element type.  The operand maps are the same for both — lane l holds
+// A[row l & 15][k = l >> 4] and B[k = l >> 4][column l & 15] — and the result maps are NOT: register r of lane l is column l & 15 of
+// row (l >> 4) + 4 r in double, of row 4 (l >> 4) + r in float (dense_f32.hip, update_block).
+template <class T>
+struct PanelMma;
+template <>
+struct PanelMma<double> {
+  typedef d4 acc_t;
+  static __device__ __forceinline__ int row(int lg, int r) { return lg + 4 * r; }
+  static __device__ __forceinline__ acc_t mma(double a, double b, acc_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+};
+template <>
+struct PanelMma<float> {
+  typedef f4 acc_t;
+  static __device__ __forceinline__ int row(int lg, int r) { return 4 * lg + r; }
+  static __device__ __forceinline__ acc_t mma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+};
 
 // F[a][b] -= sum_k L[k][a] W[k][b] for b <= a < lim, k < kp: L[k] is the scaled row of the panel's pivot p0 + k (in place in F),
 // W[k] its unscaled copy (Wp, stride ws).  16 x 16 tiles of the packed triangle, dealt round-robin to the wavefronts of the
-// workgroup; one tile is four v_mfma_f64_16x16x4_f64 on two accumulator chains (dense.hip, update_block).  Operand layout: lane l
-// holds A[row l & 15][k = l >> 4] and B[k = l >> 4][column l & 15]; result register r of lane l is row (l >> 4) + 4 r, column
-// l & 15.  Rows and columns beyond lim and panel slots beyond kp enter as zeros (selected, not multiplied: the slots may hold
+// workgroup; one tile is four v_mfma_f64_16x16x4_f64 (float: v_mfma_f32_16x16x4_f32) on two accumulator chains (dense.hip,
+// update_block), the accumulator loaded from F and stored back by the result map of the instruction (PanelMma::row).
+// Rows and columns beyond lim and panel slots beyond kp enter as zeros (selected, not multiplied: the slots may hold
 // anything); a diagonal tile computes the whole tile and stores b <= a.  The trip count depends on the wavefront alone.
-template <int TPP>
-__device__ __forceinline__ void panel_trailing_update(double* F, const double* Wp, int ws, int p0, int kp, int lim, int tid) {
+template <int TPP, class T>
+__device__ __forceinline__ void panel_trailing_update(T* F, const T* Wp, int ws, int p0, int kp, int lim, int tid) {
+  typedef PanelMma<T> M;
   const int lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, lg = lane >> 4;
   const int nt = (lim + PANEL_W - 1) / PANEL_W, ntiles = tri_i(nt);
@@ -113,26 +134,26 @@ __device__ __forceinline__ void panel_trailing_update(double* F, const double* W
     int ta, tb;
     tri_decode(t, ta, tb);
     const int ar = PANEL_W * ta + li, bc = PANEL_W * tb + li;
-    double aop[4], bop[4];
+    T aop[4], bop[4];
 #pragma unroll
     for (int s = 0; s < 4; s++) {
       const int k = 4 * s + lg;
-      aop[s] = (k < kp && ar < lim) ? -F[tri_i(p0 + k) + ar] : 0.0;
-      bop[s] = (k < kp && bc < lim) ? Wp[k * ws + bc] : 0.0;
+      aop[s] = (k < kp && ar < lim) ? -F[tri_i(p0 + k) + ar] : T(0);
+      bop[s] = (k < kp && bc < lim) ? Wp[k * ws + bc] : T(0);
     }
-    d4 acc, acc2 = d4{0.0, 0.0, 0.0, 0.0};
+    typename M::acc_t acc, acc2 = typename M::acc_t{T(0), T(0), T(0), T(0)};
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-      const int a = PANEL_W * ta + lg + 4 * r;
-      acc[r] = (a < lim && bc <= a) ? F[tri_i(a) + bc] : 0.0;
+      const int a = PANEL_W * ta + M::row(lg, r);
+      acc[r] = (a < lim && bc <= a) ? F[tri_i(a) + bc] : T(0);
     }
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[0], bop[0], acc, 0, 0, 0);
-    acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[1], bop[1], acc2, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[2], bop[2], acc, 0, 0, 0);
-    acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[3], bop[3], acc2, 0, 0, 0);
+    acc = M::mma(aop[0], bop[0], acc);
+    acc2 = M::mma(aop[1], bop[1], acc2);
+    acc = M::mma(aop[2], bop[2], acc);
+    acc2 = M::mma(aop[3], bop[3], acc2);
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-      const int a = PANEL_W * ta + lg + 4 * r;
+      const int a = PANEL_W * ta + M::row(lg, r);
       if (a < lim && bc <= a) F[tri_i(a) + bc] = acc[r] + acc2[r];
     }
   }
@@ -144,8 +165,8 @@ __device__ __forceinline__ void panel_trailing_update(double* F, const double* W
 // pivots one by one — pivot read after every earlier pivot's update has reached it, counted against eig_tol, row kept unscaled in
 // W, scaled in place, rank-1 update of the rows of the panel still to come (a contiguous piece of the packed triangle) — and then
 // updates everything below it at once.
-template <int TPP, bool LDSW>
-__device__ __forceinline__ void eliminate_blocked(const DevPlan& P, double* F, double* Wp, int f, int nupd, int idep, int tid, double eig_tol,
+template <int TPP, bool LDSW, class T>
+__device__ __forceinline__ void eliminate_blocked(const DevPlan& P, T* F, T* Wp, int f, int nupd, int idep, int tid, T eig_tol,
                                                   int& npos, int& nzer) {
   const int ws = P.fmax;
   int p1 = f;
@@ -157,13 +178,13 @@ __device__ __forceinline__ void eliminate_blocked(const DevPlan& P, double* F, d
     const int lim = indep ? idep : p0;
     if (indep) {
       for (int k = 0; k < kp; k++) {
-        double* rowi = F + tri_i(p0 + k);
-        double* wk = Wp + k * ws;
-        const double dpiv = rowi[p0 + k];
+        T* rowi = F + tri_i(p0 + k);
+        T* wk = Wp + k * ws;
+        const T dpiv = rowi[p0 + k];
         npos += dpiv > eig_tol;
         nzer += abs_of(dpiv) <= eig_tol;
         for (int j = tid; j < lim; j += TPP) {
-          const double w = rowi[j];
+          const T w = rowi[j];
           wk[j] = w;
           rowi[j] = w / dpiv;
         }
@@ -172,13 +193,13 @@ __device__ __forceinline__ void eliminate_blocked(const DevPlan& P, double* F, d
     } else {
       for (int k = kp - 1; k >= 0; k--) {
         const int i = p0 + k;
-        double* rowi = F + tri_i(i);
-        double* wk = Wp + k * ws;
-        const double dpiv = rowi[i];
+        T* rowi = F + tri_i(i);
+        T* wk = Wp + k * ws;
+        const T dpiv = rowi[i];
         npos += dpiv > eig_tol;
         nzer += abs_of(dpiv) <= eig_tol;
         for (int j = tid; j < i; j += TPP) {
-          const double w = rowi[j];
+          const T w = rowi[j];
           wk[j] = w;
           rowi[j] = w / dpiv;
         }
@@ -205,7 +226,7 @@ __device__ __forceinline__ void eliminate_blocked(const DevPlan& P, double* F, d
 // ---------------------------------------------------------------------------
 // forward pass over one front: assemble, extend-add, eliminate the pivots,
 // store the L panel, leave the update matrix for the parent.
-// BLK (double, TPP a multiple of 64): fronts with at least PANEL_W pivots are eliminated by eliminate_blocked
+// BLK (TPP a multiple of 64): fronts with at least PANEL_W pivots are eliminated by eliminate_blocked
 template <int TPP, bool LDSW, bool WITH_K, class T, bool BLK = false>
 __device__ __forceinline__ void front_forward(const DevPlan& P, const FrontHdr& H, const ProblemCtx<T>& c, int tid,
                                               bool rho_override, T rho, T eig_tol, int& npos, int& nzer) {
@@ -389,8 +410,8 @@ __device__ __forceinline__ T* as_global(T* p) {  // struct members are generic p
   return (T*)(__attribute__((address_space(1))) T*)p;
 }
 
-// BLK: the blocked elimination of large fronts (tuning general_blocked; double, PPB = 1, TPP 256 or 1024: launch_newton); MODE_SOLVE
-// of such an instance reads A.success
+// BLK: the blocked elimination of large fronts (PPB = 1; tuning general_blocked: double, TPP 256 or 1024, launch_newton; tuning
+// float32_blocked: float, TPP 256, launch_newton_f32); MODE_SOLVE of such an instance reads A.success
 template <int TPP, int PPB, bool LDSW, class T, bool BLK = false>
 __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, const LaunchArgs Ain) {
   DevPlan P = Pin;
@@ -502,8 +523,9 @@ static hipError_t launch_t(const DevPlan& P, const KernelConfig& cfg, const Laun
   return hipGetLastError();
 }
 
-// the configurations with a blocked instance (tuning general_blocked): whole workgroups of several wavefronts on one problem
-bool newton_blocked_has(int tpp, int ppb) { return ppb == 1 && (tpp == 256 || tpp == 1024); }
+// the configurations with a blocked instance (tuning general_blocked; float32_blocked for f32): whole workgroups of several
+// wavefronts on one problem; in float the 256-thread instances alone (there is no 1024-thread float instance of any kind)
+bool newton_blocked_has(int tpp, int ppb, bool f32) { return ppb == 1 && (tpp == 256 || (tpp == 1024 && !f32)); }
 
 hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream) {
   // (solve_ldl! runs the same sweeps on the factor a blocked launch left; given the flags of that factorisation in a.success it runs
@@ -541,6 +563,13 @@ bool newton_f32_has(int tpp, int ppb, bool lds_work) {
 }
 
 hipError_t launch_newton_f32(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream) {
+  // (tuning float32_blocked: the rule of launch_newton — Newton and factorise launches, and the solve sweeps where the flags of the
+  //  last factorisation come with them)
+  if (cfg.blocked && (a.mode != MODE_SOLVE || a.success)) {
+    if (cfg.tpp == 256 && cfg.ppb == 1)
+      return cfg.lds_work != 0 ? launch_t<256, 1, true, float, true>(P, cfg, a, stream) : launch_t<256, 1, false, float, true>(P, cfg, a, stream);
+    return hipErrorInvalidConfiguration;
+  }
 #define CNL_CASE(T, B, W) \
   if (cfg.tpp == T && cfg.ppb == B && (cfg.lds_work != 0) == W) return launch_t<T, B, W, float>(P, cfg, a, stream);
   CNL_F32_CASES(CNL_CASE)

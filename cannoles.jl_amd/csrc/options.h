@@ -70,7 +70,8 @@ namespace cnl {
   X(float32_latency, 0)      /* cnl_create_f32: float32_staged, and the latency plan honours the switches a Float64 handle honours — lean_kernel, rows_in_backward, dataflow, dataflow_waves, dataflow_spin_limit, device_ladder, device_ladder_fused, by the Float64 defaults and rules: the lean, dataflow and fused-ladder float instances of the register-front kernel; implies float32_staged and what that implies; every plan that cannot run staged gets the handle it gets without the key; only with float32_general, not with float32_refine */ \
   X(float32_refine, 0)       /* cnl_create_ex / cnl_plan_create_ex: k = 1 .. 4: a Float64 handle on an inner Float32 general handle (made as cnl_create_f32_ex makes it from the same options, band_kernel forced to 0), whose solution is refined k times with a Float64 residual (refine.h); only with float32_general */ \
   X(refine_rows, 0)          /* the KKT residual kernel (refine.h): 0 by the pattern, 1 a row per lane, 2 a row per wavefront */ \
-  X(general_blocked, 0)      /* general kernel, Float64: 1 = fronts with 16 pivots or more leave in panels of 16, trailing updates on the f64 matrix cores (configurations with 256 or 1024 threads per problem; the others run as without the key); no Float32 instances: cnl_create_f32* and float32_refine refuse it */ \
+  X(general_blocked, 0)      /* general kernel, Float64: 1 = fronts with 16 pivots or more leave in panels of 16, trailing updates on the f64 matrix cores (configurations with 256 or 1024 threads per problem; the others run as without the key); Float64 handles only: cnl_create_f32* and float32_refine refuse it (the Float32 instances have a key of their own, float32_blocked) */ \
+  X(float32_blocked, 0)      /* cnl_create_f32: general_blocked for a Float32 general handle: where its newton_system / factorize launches are the general kernel in float with 256 threads per problem, fronts with 16 pivots or more leave in panels of 16, trailing updates on the f32 matrix cores; selects no route: every handle gets the route it gets without the key, and 64 threads per problem run unblocked; 0 or 1; only with float32_general, not with float32_refine; a Float64 creator without float32_refine reads nothing of it, as of float32_condense */ \
   X(cgls_wide, 0)            /* row f4: 0 the ncon-vectors in LDS, more than 1024 constraints are CNL_ERR_DIM; 1 in the global workspace where ncon > 1024; 2 there always */
 
 struct Tuning {

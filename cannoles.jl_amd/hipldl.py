@@ -148,7 +148,13 @@ def Options(**kw):
     by lean_kernel, rows_in_backward, dataflow, dataflow_waves, dataflow_spin_limit, device_ladder and device_ladder_fused as on a
     Float64 handle) are described with HIPLDLStruct.  general_blocked = 1 (Float64 handles only): the general kernel eliminates fronts with
     16 pivots or more in panels of 16 with the trailing updates on the f64 matrix cores; config["general_blocked"] says whether the
-    handle's launches are a blocked instance."""
+    handle's launches are a blocked instance.  float32_blocked = 1 (only with float32_general = 1, not with float32_refine; 0 or 1): the
+    same for a Float32 general handle, on the f32 matrix cores — where its newton_system / factorize launches are the general kernel in
+    float with 256 threads per problem (a front above order 96 and no dense route; uncondensed, float32_condense, or
+    float32_register_front fallen back to it); the key selects no route, 64 threads per problem run unblocked, and
+    config["float32_blocked"] says whether the launches are a blocked instance.  Such a handle keeps the success flags of its last
+    factorisation: solve leaves the rows of d of a failed problem untouched.  A Float64 handle without float32_refine reads nothing of
+    the key (as of float32_condense)."""
     o = cnl_options()
     lib().cnl_options_init(C.byref(o))
     assert o.struct_size == C.sizeof(cnl_options), "cnl_options layout differs from the library's"
@@ -493,7 +499,9 @@ class HIPLDLStruct:
                        "dataflow": bool((int(cfg[5]) >> 42) & 1), "lad_mode": (int(cfg[5]) >> 43) & 3,
                        "cgls_wide": (int(cfg[5]) >> 45) & 3,
                        # newton_system / factorize run a blocked instance of the general kernel (Options(general_blocked=1))
-                       "general_blocked": bool((int(cfg[5]) >> 47) & 1)}
+                       "general_blocked": bool((int(cfg[5]) >> 47) & 1),
+                       # ... of the general kernel in float, on a Float32 general handle (Options(float32_blocked=1))
+                       "float32_blocked": bool((int(cfg[5]) >> 48) & 1)}
         if self.config["float32"] and self.config["band"]:   # (a Float32 handle off the band kernels — tuning float32_general — is "v1")
             self.config["kernel"] = "band"
 

@@ -64,7 +64,8 @@ const char* cnl_last_error(void);
  * 0.5.0: tuning "float32_refine" / "refine_rows", cnl_kkt_residual_dev, cnl_get_refine_norms, cnl_plan_get "kkt_row_*",
  * cnl_get_config bits 38 .. 41; 0.5.1: tuning "float32_staged", no new symbol; 0.5.2: tuning "float32_latency", cnl_get_config
  * bits 42 .. 44, no new symbol; 0.5.3: tuning "cgls_wide", cnl_get_config bits 45 / 46, no new symbol;
- * 0.5.4: tuning "general_blocked", cnl_get_config bit 47, no new symbol) */
+ * 0.5.4: tuning "general_blocked", cnl_get_config bit 47, no new symbol; 0.5.5: tuning "float32_blocked", cnl_get_config bit 48,
+ * no new symbol) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -473,8 +474,28 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  * the sums of an update are formed in another order, so d agrees with the key off to rounding, not bit for bit.  The work area grows by 14 rows of the largest front (it may move from LDS
  * to global scratch: cfg[3]).  A handle whose configuration has no blocked instance (64 threads per problem or fewer, the
  * register-front kernel, the band kernels, the dense backend) runs as without the key and reports bit 47 clear.  There are no
- * Float32 instances: cnl_create_f32* with the key, and the key together with "float32_refine", are CNL_ERR_ARG.  cnl_multi shards
- * inherit it.  Measured: DESIGN section 3.1. */
+ * Float32 instances behind THIS key: cnl_create_f32* with the key, and the key together with "float32_refine", are CNL_ERR_ARG
+ * (a Float32 general handle has "float32_blocked", next).  cnl_multi shards inherit it.  Measured: DESIGN section 3.1.
+ *
+ * bit 48 = cnl_newton_system_f32* / cnl_factorize_f32* of a Float32 general handle run a BLOCKED float instance of the general kernel
+ * (tuning "float32_blocked=1"); bit 47 keeps its Float64-only meaning.
+ *
+ * Tuning "float32_blocked" (0 default, 1): "general_blocked" for a Float32 general handle, with the trailing updates on the f32
+ * matrix cores (v_mfma_f32_16x16x4_f32).  Rules, all answered before a device is looked for: only together with
+ * "float32_general=1" (alone: CNL_ERR_ARG); any value other than 0 / 1 is CNL_ERR_ARG; together with "float32_refine" it is
+ * CNL_ERR_ARG at cnl_create_ex and at cnl_plan_create_ex (no refined handle over a blocked Float32 factor), as "float32_staged" is.
+ * A Float64 creator without "float32_refine" reads nothing of the key, neither its value nor its rules — exactly as it reads
+ * nothing of "float32_condense".  The key selects no route: every handle gets the route it gets without it (band kernels,
+ * register-front kernel, staged / latency, "float32_dense", "float32_general_dense"), and it acts only where that route launches
+ * the general kernel in float for newton_system / factorize with one problem per workgroup and 256 threads — the uncondensed
+ * Float32 general handle and the "float32_condense" one (also a "float32_register_front" handle that fell back to it because a
+ * front is above order 64) whose largest front is above order 96, or with "v1_tpp=256".  With 64 threads per problem (largest
+ * front of order <= 96 without "v1_tpp") there is no blocked instance: the handle runs unblocked and reports bit 48 clear.  The work
+ * area grows by 14 rows of the largest front, in 4-byte elements, and is placed in LDS or global scratch with that size (cfg[3]).
+ * As in Float64 the handle keeps the success flags of its last factorisation and cnl_solve_f32* leaves the rows of d of a failed
+ * problem untouched; decisions (success, nfact, rho, rho_old, the rho slots) are those of the handle without the key wherever the
+ * pivots keep the project's Float32 margin from eig_tol, d agrees to Float32 rounding, not bit for bit.  Measured: DESIGN
+ * section 9.10. */
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
 /* (bit 38 = a refined handle — tuning "float32_refine", below —, bits 39-41 = its refinement steps k; every other word and bit
  *  describes its inner Float32 handle, with bit 27 clear: the handle is a Float64 handle.) */
