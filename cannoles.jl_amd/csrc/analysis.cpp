@@ -968,6 +968,82 @@ int build_plan(Plan& P, int64_t N64, int64_t nnz, const int64_t* rows1, const in
     P.bwd_peak = (int32_t)bpeak;
   }
 
+  // ---- subtree execution of the general kernel (tuning general_subtrees; plan.h: GTask) -------------------
+  // The cut is the rule of the staged tasks below: maximal subtrees of at most `cap` fronts at the bottom, every front above on
+  // its own, stage = 1 + latest child stage.  The layout gives every task a region of its own — the static stack above lets a
+  // sibling subtree reuse the space of the one before it, which tasks that run at the same time cannot share.
+  P.gtasks.clear(); P.gstage_ptr.clear(); P.gfronts.clear(); P.gwork = 0; P.gcap = 0;
+  if (opt.general_subtrees && ns >= 1) {
+    const int cap = opt.task_cap > 0 ? opt.task_cap : 8;
+    ivec nsub(ns, 1), fdesc(ns), stage(ns, 0);
+    for (int32_t s = 0; s < ns; s++) {
+      fdesc[s] = s;
+      for (int32_t c : skids[s]) { nsub[s] += nsub[c]; fdesc[s] = std::min(fdesc[s], fdesc[c]); }
+    }
+    std::vector<GTask> ts;
+    for (int32_t s = 0; s < ns; s++) {
+      if (nsub[s] <= cap) {
+        stage[s] = 0;
+        if (sparent[s] < 0 || nsub[sparent[s]] > cap) ts.push_back({0, fdesc[s], s + 1, -1, 0, 0, 0, 0});
+      } else {
+        int32_t st = 0;
+        for (int32_t c : skids[s]) st = std::max(st, stage[c]);
+        stage[s] = st + 1;
+        ts.push_back({stage[s], s, s + 1, -1, 0, 0, 0, 0});
+      }
+    }
+    std::stable_sort(ts.begin(), ts.end(), [](const GTask& x, const GTask& y) { return x.stage < y.stage; });
+    ivec task_of(ns, -1);
+    for (size_t k = 0; k < ts.size(); k++) for (int32_t f = ts[k].f0; f < ts[k].f1; f++) task_of[f] = (int32_t)k;
+    for (GTask& t : ts) t.parent = sparent[t.f1 - 1] >= 0 ? task_of[sparent[t.f1 - 1]] : -1;
+    // regions: [stack of the task's fronts, classic rule from the base | panel buffer | staging rows]
+    const int64_t rows = opt.gsub_rows > 0 ? opt.gsub_rows : 2;
+    std::vector<FrontHdr> gf = P.fronts;
+    int64_t base = 0;
+    bool fits = true;
+    for (GTask& t : ts) {
+      int64_t sp = base, peak = base, bpeak = base, fm = 0, pm = 0;
+      for (int32_t s = t.f0; s < t.f1; s++) {
+        FrontHdr& F = gf[s];
+        const int64_t f = 1 + (int64_t)F.nupd + F.npiv;
+        int64_t b = sp;
+        // (a bottom subtree holds every child of its fronts; the children of a front above the cut are other tasks')
+        if (F.child_end > F.child_begin && task_of[P.child_idx[F.child_begin]] == task_of[s]) b = gf[P.child_idx[F.child_begin]].ubase;
+        F.foff = (int32_t)sp;
+        peak = std::max(peak, sp + tri(f));
+        F.ubase = (int32_t)b;
+        sp = b + tri(1 + F.nupd);
+        fm = std::max(fm, f);
+        pm = std::max(pm, tri(f) - tri(1 + F.nupd));
+      }
+      for (int32_t s = t.f1 - 1; s >= t.f0; s--) {
+        FrontHdr& F = gf[s];
+        const int64_t f = 1 + (int64_t)F.nupd + F.npiv;
+        if (s == t.f1 - 1) F.xoff = (int32_t)base;   // (the task's root: its parent's vector, if any, is in the parent's region)
+        else {
+          const FrontHdr& Pp = gf[F.parent];
+          F.xoff = P.child_idx[Pp.child_begin] == s ? Pp.xoff : Pp.xoff + (1 + Pp.nupd + Pp.npiv);
+        }
+        bpeak = std::max(bpeak, (int64_t)F.xoff + f);
+      }
+      const int64_t pb = (std::max(peak, bpeak) + 1) & ~(int64_t)1;
+      const int64_t wv = pb + ((pm + 1) & ~(int64_t)1);
+      t.base = (int32_t)base; t.pb_off = (int32_t)pb; t.wv_off = (int32_t)wv; t.fmax = (int32_t)((fm + 1) & ~(int64_t)1);
+      base = wv + rows * t.fmax;
+      if (base >= ((int64_t)1 << 30)) { fits = false; break; }   // (32-bit element offsets: the plan keeps no cut, the handle runs as without the key)
+    }
+    if (fits) {
+      P.gtasks = ts; P.gfronts = gf; P.gwork = base; P.gcap = cap;
+      const int32_t nst = ts.back().stage + 1;
+      P.gstage_ptr.assign(nst + 1, 0);
+      for (const GTask& t : ts) P.gstage_ptr[t.stage + 1]++;
+      for (int32_t q = 0; q < nst; q++) P.gstage_ptr[q + 1] += P.gstage_ptr[q];
+      if (verbose)
+        fprintf(stderr, "[cnl] general subtrees: %zu tasks in %d stages (cap %d fronts), first stage %d tasks, %lld elements of work area per problem\n",
+                ts.size(), nst, cap, P.gstage_ptr[1], (long long)base);
+    }
+  }
+
   // ---- v2 streams (register-front kernel) ---------------------------------------------
   P.v2_ok = opt.with_rhs_row && P.fmax <= 64 && opt.register_front;
   // ---- tasks of the staged execution: maximal subtrees of at most task_cap fronts at the bottom (postorder makes a

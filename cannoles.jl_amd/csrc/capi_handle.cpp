@@ -88,9 +88,39 @@ int choose_config(cnl_handle* h) {
 // bit 48): the Newton / factorise launches are the general kernel's, in a configuration with a blocked instance.  No flag set: no
 // problem holds a factor yet.
 int alloc_blocked_flags(cnl_handle* h) {
-  if (!h->cfg.blocked || h->use_v2 || h->band || h->dense || h->gdense) return CNL_OK;
+  if ((!h->cfg.blocked && !h->subtrees) || h->use_v2 || h->band || h->dense || h->gdense) return CNL_OK;   // (a subtree handle keeps them too)
   if (int rc = dalloc(h, &h->d_blk_ok, (size_t)h->batch)) return rc;
   if (hipMemset(h->d_blk_ok, 0, (size_t)h->batch * sizeof(int32_t)) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
+  return CNL_OK;
+}
+
+// Tuning general_subtrees: does the key act on this Float64 handle?  A pure function of plan, batch and options
+// (the configuration is choose_config's, which reads the same three and the device's LDS size):
+//   - the Newton / factorise launch is the general kernel: no register-front, band or dense route took the handle;
+//   - one problem per workgroup of 256 or 1024 threads (the configurations with subtree instances);
+//   - the cut has at least two tasks in its first stage (a chain of single-front stages gains nothing: every stage is one task);
+//   - the task regions of the whole batch fit 8e9 bytes (the bound of the dense batch rule).
+// Where it acts the work area becomes the global array of task regions (gwork elements per problem; LDS cannot be shared between
+// workgroups) and the device plan walks the second front table.  Everywhere else nothing of the handle changes.
+// To be called once the routes are decided and before the factor storage (and with it d_scratch) is allocated.
+int setup_subtrees(cnl_handle* h) {
+  const cnl::Plan& P = h->plan->P;
+  if (!h->plan->opt.general_subtrees || h->f32 || h->use_v2 || h->band || h->dense || h->gdense) return CNL_OK;
+  if (!cnl::newton_subtrees_has(h->cfg.tpp, h->cfg.ppb)) return CNL_OK;
+  if (P.gtasks.empty() || P.gstage_ptr.size() < 2 || P.gstage_ptr[1] < 2) return CNL_OK;
+  if ((double)h->full_batch * (double)P.gwork * 8.0 > 8e9) return CNL_OK;
+  int rc;
+  const cnl::FrontHdr* d_gfronts = nullptr;
+  if ((rc = upload(h, P.gfronts, &d_gfronts))) return rc;
+  std::vector<int32_t> tk(reinterpret_cast<const int32_t*>(P.gtasks.data()), reinterpret_cast<const int32_t*>(P.gtasks.data()) + 8 * P.gtasks.size());
+  if ((rc = upload(h, tk, &h->d_gtasks))) return rc;
+  if ((rc = dalloc(h, &h->d_sub_cnt, 2 * (size_t)h->full_batch * P.gtasks.size()))) return rc;
+  h->gstage_ptr = P.gstage_ptr;
+  h->dp.fronts = d_gfronts;
+  h->dp.work_doubles = (int32_t)P.gwork;
+  h->cfg.lds_work = 0;
+  h->cfg.lds_bytes = 16 * sizeof(double);
+  h->subtrees = true;
   return CNL_OK;
 }
 
@@ -690,6 +720,7 @@ int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, co
     int drc = cnl::dense_create_general(&h->gdense, (int32_t)C2.N2, (int32_t)nvar, (int32_t)C2.ncs, h->gops.d_pos, batch, derr, h->plan->opt.dense_graph != 0, h->plan->opt.dense_panel_blocks);
     if (drc) return bail(fail(CNL_ERR_HIP, "dense backend: " + derr));
   }
+  if ((rc = setup_subtrees(h))) return bail(rc);   // (tuning general_subtrees: where it acts, d_scratch below is the task regions)
   if ((rc = alloc_factor_storage(h))) return bail(rc);   // (band handles: the pad alone, see above)
   if ((rc = alloc_blocked_flags(h))) return bail(rc);
   if ((rc = finish_handle(h, rows1, cols1))) return bail(rc);
@@ -1101,6 +1132,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   if (h->route == cnl::Route::Direct) cfg[5] |= (int64_t)1 << 36;                 // the Direct route (call_shape.h), either element type
   if (h->route == cnl::Route::Direct && h->v2_solve) cfg[5] |= (int64_t)1 << 37;  // ... on which solve_ldl! runs on the register-front kernel too
   if (h->cfg.blocked && !h->use_v2 && !dense_route && !on_band) cfg[5] |= (int64_t)1 << (h->f32 ? 48 : 47);   // newton_system / factorize run a blocked instance of the general kernel (bit 47: Float64, tuning general_blocked; bit 48: Float32, tuning float32_blocked)
+  if (h->subtrees) cfg[5] |= (int64_t)1 << 49;   // the three calls run the general kernel's subtree instances stage by stage (tuning general_subtrees, where it acts)
   if (h->lean && !dense_route) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->staged && h->use_v2 && !dense_route) {          // staged handles: how the stages run
     if (h->d_dep) cfg[5] |= (int64_t)1 << 42;            // dataflow counters present (one launch per phase where the rule allows)

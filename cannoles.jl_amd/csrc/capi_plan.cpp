@@ -80,6 +80,8 @@ int resolve_options(const cnl_options* in, cnl::Tuning& out) {
     return fail(CNL_ERR_ARG, "cnl_options.tuning: refine_rows is 0 (by the pattern), 1 (a row per lane) or 2 (a row per wavefront)");
   if (out.general_blocked < 0 || out.general_blocked > 1)
     return fail(CNL_ERR_ARG, "cnl_options.tuning: general_blocked is 0 or 1 (the general kernel eliminates large fronts in panels of 16 pivots)");
+  if (out.general_subtrees < 0 || out.general_subtrees > 1)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: general_subtrees is 0 or 1 (the general kernel runs the subtrees of the elimination tree on workgroups of their own, stage by stage)");
   if (out.cgls_wide < 0 || out.cgls_wide > 2)
     return fail(CNL_ERR_ARG, "cnl_options.tuning: cgls_wide is 0 (the LDS instance, ncon <= 1024), 1 (the wide instance where ncon > 1024) or 2 (the wide instance always)");
   return CNL_OK;
@@ -101,6 +103,7 @@ int plan_create_impl(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* row
   opt.order_mode = o.order_mode; opt.nd_leaf = o.nd_leaf; opt.relax = o.relax; opt.task_cap = o.task_cap;
   opt.early = o.multipliers_early; opt.register_front = o.register_front; opt.ubig = o.ubig; opt.wait_thr = o.wait_thr;
   opt.verbose = verbose ? 1 : 0; opt.force_order = o.force_order; opt.threads = o.analysis_threads;
+  opt.general_subtrees = o.general_subtrees; opt.gsub_rows = o.general_blocked ? 16 : 2;   // (the staging rows choose_config sizes)
   const auto t_start = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) {   // (verbose log: seconds since the analysis started)
     if (verbose) fprintf(stderr, "[cnl] analysis %-28s %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count());
@@ -276,6 +279,8 @@ int check_f32_options(const cnl::Tuning& o, const char* fn) {
 int check_no_general_blocked(const cnl::Tuning& o, const char* fn) {
   if (o.general_blocked)
     return fail(CNL_ERR_ARG, std::string(fn) + ": tuning general_blocked = 1 is served by Float64 handles only (a Float32 general handle takes its blocked instances with tuning float32_blocked)");
+  if (o.general_subtrees)   // (tuning general_subtrees: the same rule — there is no Float32 subtree instance)
+    return fail(CNL_ERR_ARG, std::string(fn) + ": tuning general_subtrees = 1 is served by Float64 handles only (the general kernel has no Float32 subtree instances)");
   return CNL_OK;
 }
 
@@ -429,7 +434,9 @@ const char* cnl_last_error(void) { return g_err.c_str(); }
 // 0.5.4: tuning general_blocked (the general kernel's blocked instances, Float64), cnl_get_config bit 47, no new symbol
 // 0.5.5: tuning float32_blocked (the general kernel's blocked instances in float, for Float32 general handles), cnl_get_config bit 48,
 //        no new symbol
-int32_t cnl_version(void) { return 505; }
+// 0.5.6: tuning general_subtrees (the general kernel stage by stage, one workgroup per problem and task of the elimination tree, Float64),
+//        cnl_get_config bit 49, cnl_plan_get "gtasks" / "gstage_ptr" / "gfronts" / "ginfo", no new symbol
+int32_t cnl_version(void) { return 506; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62
@@ -564,6 +571,18 @@ int cnl_plan_get(const cnl_plan* plan, const char* name, int32_t* out, int64_t* 
   else if (s == "rel_idx") { src = P.rel_idx.data(); n = (int64_t)P.rel_idx.size(); }
   else if (s == "tasks") { src = reinterpret_cast<const int32_t*>(P.tasks.data()); n = (int64_t)P.tasks.size() * 8; }  // struct Task, csrc/plan.h
   else if (s == "stage_ptr") { src = P.stage_ptr.data(); n = (int64_t)P.stage_ptr.size(); }
+  // subtree execution of the general kernel (tuning general_subtrees; plan.h: GTask): empty without the key
+  else if (s == "gtasks") { src = reinterpret_cast<const int32_t*>(P.gtasks.data()); n = (int64_t)P.gtasks.size() * 8; }
+  else if (s == "gstage_ptr") { src = P.gstage_ptr.data(); n = (int64_t)P.gstage_ptr.size(); }
+  else if (s == "gfronts") { src = reinterpret_cast<const int32_t*>(P.gfronts.data()); n = (int64_t)P.gfronts.size() * 16; }
+  else if (s == "ginfo") {
+    // {gwork: elements of work area per problem with every task region side by side, tasks, stages, tasks of the first stage, cap}
+    static thread_local int32_t gi[5];
+    const int32_t nst = (int32_t)P.gstage_ptr.size() - 1;
+    const int32_t v[5] = {(int32_t)P.gwork, (int32_t)P.gtasks.size(), nst < 0 ? 0 : nst, nst >= 1 ? P.gstage_ptr[1] : 0, P.gcap};
+    std::memcpy(gi, v, sizeof(gi));
+    src = gi; n = P.gtasks.empty() ? 0 : 5;
+  }
   else if (s == "rec") { src = P.rec.data(); n = P.v2_ok ? (int64_t)P.rec.size() : 0; }     // record streams of the
   else if (s == "brec") { src = P.brec.data(); n = P.v2_ok ? (int64_t)P.brec.size() : 0; }  // register-front kernel
   else if (s.rfind("band", 0) == 0) {

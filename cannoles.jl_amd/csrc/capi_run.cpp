@@ -131,6 +131,50 @@ int launch_staged(cnl_handle* h, cnl::LaunchArgs& a, bool first_attempt_only, bo
   return CNL_OK;
 }
 
+// One call of a subtree handle (tuning general_subtrees), S = stages of the cut: a launch per stage walks the tasks
+// of that stage forward (one workgroup per problem and task); where the call factorises, the decide kernel behind the last stage
+// makes the flags of the first attempt; where it solves, a launch per stage in reverse runs the backward sweeps of the problems that
+// hold a factor; newton_system ends with the climbers' launch, which takes the failed problems through the whole ladder.
+// Launches: newton_system 2 S + 2, try_to_factorize S + 1, solve_ldl! 2 S.  The order on the stream is the only dependency.
+// The handle keeps the flags of its last factorisation (d_blk_ok), which solve_ldl! and the expand pass read.
+int launch_subtrees(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
+  begin_launch(h, a, stream);
+  const bool newton = a.mode == cnl::MODE_NEWTON, solve = a.mode == cnl::MODE_SOLVE;
+  const int nst = (int)h->gstage_ptr.size() - 1, ntasks = h->gstage_ptr[nst];
+  a.L = h->d_L; a.scratch = h->d_scratch;
+  a.tasks = h->d_gtasks; a.gcnt = h->d_sub_cnt; a.ntasks_all = ntasks; a.skip_done = 0;
+  int32_t* const callers_flags = a.success;
+  if (solve) a.success = h->d_blk_ok;
+  if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
+  hipError_t e = hipSuccess;
+  auto stage = [&](int s, int phase) {
+    a.phase = phase; a.task0 = h->gstage_ptr[s]; a.ntasks = h->gstage_ptr[s + 1] - h->gstage_ptr[s];
+    g_launches[2]++;
+    return cnl::launch_newton_subtrees(h->dp, h->cfg, a, stream);
+  };
+  for (int s = 0; s < nst && e == hipSuccess; s++) e = stage(s, 0);
+  if (!solve && e == hipSuccess) {
+    g_launches[2]++;   // (cnl_launch_counts: the decide kernel is a launch of the pass, counted with the stages)
+    e = cnl::launch_subtree_decide(a, h->d_sub_cnt, ntasks, (int)h->dp.nvar, stream);
+  }
+  if (a.mode != cnl::MODE_FACTOR)
+    for (int s = nst - 1; s >= 0 && e == hipSuccess; s--) e = stage(s, 1);
+  if (newton && e == hipSuccess) {
+    a.phase = 2; a.task0 = 0; a.ntasks = ntasks; a.skip_done = 1;
+    g_launches[2]++;
+    e = cnl::launch_newton_subtrees(h->dp, h->cfg, a, stream);
+    a.skip_done = 0;
+  }
+  if (!solve && e == hipSuccess)
+    e = hipMemcpyAsync(h->d_blk_ok, a.success, (size_t)h->batch * sizeof(int32_t), hipMemcpyDeviceToDevice, stream);
+  a.success = callers_flags;
+  if (e != hipSuccess)
+    return fail(CNL_ERR_HIP, std::string("subtree launch (tpp=") + std::to_string(h->cfg.tpp) + ", " + std::to_string(ntasks) + " tasks in " +
+                                 std::to_string(nst) + " stages): " + hipGetErrorString(e));
+  if (h->timing) HIPCHK(hipEventRecord(h->ev1, stream));
+  return CNL_OK;
+}
+
 }  // namespace
 
 // SubBatch (handle.h): the view is set up by moving the handle's own pointers, and undone when it goes out of scope
@@ -141,6 +185,8 @@ SubBatch::SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged) : 
   batch = h->batch; L = h->d_L; gs = h->d_gs; scratch = h->d_scratch; cbuf = h->d_cbuf; d2 = h->d_d2;
   blk_ok = h->d_blk_ok;
   if (h->d_blk_ok) h->d_blk_ok += b0;
+  sub_cnt = h->d_sub_cnt;
+  if (h->d_sub_cnt) h->d_sub_cnt += 2 * b0 * (int64_t)h->plan->P.gtasks.size();   // (a view's slots: [tasks][nb][2] from here)
   xpos = h->d_xpos; xzer = h->d_xzer; gcnt = h->d_gcnt; dep = h->d_dep; lad = h->d_lad; stat = h->d_stat;
   Lband = h->d_Lband;
   h->d_Lband = elem_offset(h, h->d_Lband, b0 * h->bd.lsize);
@@ -159,7 +205,7 @@ SubBatch::SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged) : 
 
 SubBatch::~SubBatch() {
   h->batch = batch; h->d_L = L; h->d_gs = gs; h->d_scratch = scratch; h->d_cbuf = cbuf; h->d_d2 = d2;
-  h->d_blk_ok = blk_ok;
+  h->d_blk_ok = blk_ok; h->d_sub_cnt = sub_cnt;
   h->d_xpos = xpos; h->d_xzer = xzer; h->d_gcnt = gcnt; h->d_dep = dep; h->d_lad = lad; h->d_stat = stat;
   h->last_vals = last_vals; h->staged = staged; h->d_Lband = Lband;
 }
@@ -333,7 +379,8 @@ int run_dense(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs
 // The executor of the Plain, Direct, Condensed and GeneralDense routes: [condense -> inertia ->] launch [-> expand], as S says
 // (call_shape.h).  The launch is the multifrontal kernel — one classic launch, or stage by stage with its follow-up — or, on the
 // GeneralDense route, the dense LDL^T / solves of the condensed system as one matrix (csrc/dense.hip).  The events of a timed call
-// bracket the classic launch alone (launch()), the staged pass with its follow-up, or the whole dense route.
+// bracket the classic launch alone (launch()), the staged pass with its follow-up (the register-front kernel's, or the general
+// kernel's subtree pass: launch_subtrees), or the whole dense route.
 int execute(cnl_handle* h, const cnl::CallShape& S, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream, RunOpts o) {
   const cnl::Cond& C = h->plan->C;
   const bool gdense = S.launch == cnl::Launch::GeneralDense, factors = a.mode != cnl::MODE_SOLVE, solves = a.mode != cnl::MODE_FACTOR;
@@ -365,6 +412,8 @@ int execute(cnl_handle* h, const cnl::CallShape& S, cnl::LaunchArgs& a, void* d_
       if ((rc = launch_staged(h, a, o.first_attempt_only, ladder_ran, stream))) return rc;
       if ((rc = staged_follow_up(h, a, ladder_ran, o.first_attempt_only, stream))) return rc;
       if (h->timing) HIPCHK(hipEventRecord(h->ev1, stream));
+    } else if (S.launch == cnl::Launch::Subtrees) {
+      if ((rc = launch_subtrees(h, a, stream))) return rc;
     } else if ((rc = launch(h, a, stream))) return rc;
   }
   if (S.expand && (rc = expand(h, src, d_rhs, S.expand_d2 ? h->d_d2 : nullptr, d_d, S.expand_success ? a.success : !solves || factors ? nullptr : h->d_blk_ok, S.copy_rho_tail, stream))) return rc;
@@ -373,7 +422,7 @@ int execute(cnl_handle* h, const cnl::CallShape& S, cnl::LaunchArgs& a, void* d_
 
 cnl::RouteFacts route_facts(const cnl_handle* h) {
   const cnl::Plan& P = h->plan->P;
-  return {h->route, h->dp2.count_d != 0, P.d_outer != 0, h->v2_solve, h->lean && P.back_rows, h->staged};
+  return {h->route, h->dp2.count_d != 0, P.d_outer != 0, h->v2_solve, h->lean && P.back_rows, h->staged, h->subtrees};
 }
 
 }  // namespace

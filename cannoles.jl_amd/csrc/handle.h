@@ -105,6 +105,15 @@ struct cnl_handle {
   // the last factorisation of every problem, copied behind each Newton / factorise launch; solve_ldl! leaves the rows of d of a
   // problem without a factor untouched (the blocked instance and the expand pass read them)
   int32_t* d_blk_ok = nullptr;
+  // tuning general_subtrees, where it acts (capi_handle.cpp: setup_subtrees; cnl_get_config bit 49): the three calls
+  // run the general kernel's subtree instances stage by stage.  dp.fronts is then the plan's task-region front table and
+  // dp.work_doubles its gwork — the work area is d_scratch, global, whatever the configuration said —, d_gtasks the task records,
+  // gstage_ptr the plan's stage pointers, d_sub_cnt [tasks][batch][2] the tasks' pivot counts of the call under way (views of the
+  // handle use disjoint pieces of it).  Such a handle keeps d_blk_ok whether or not its instances are blocked.
+  bool subtrees = false;
+  const int32_t* d_gtasks = nullptr;
+  int* d_sub_cnt = nullptr;
+  std::vector<int32_t> gstage_ptr;
   // Float32 general handles on a condensed plan: the resident condense kernel serves the handle (kernels.h: DevCondEll) — where the
   // tiled kernel's chunks degenerate (dense Jacobians) and [vals | rhs] of a problem fits LDS; tuning float32_condense = 2: never
   bool cond_resident = false;
@@ -318,7 +327,7 @@ cnl::Tuning f32_unstaged_options(const cnl::Tuning& o);
 bool f32_general_dense_fits(const cnl_plan* plan, int64_t batch);
 // what every creator checks of the float32_* keys (fn: the creator's name, for the message)
 int check_f32_options(const cnl::Tuning& o, const char* fn);
-// tuning general_blocked on a creator of Float32 state (cnl_create_f32*, the inner handle of float32_refine): CNL_ERR_ARG
+// tuning general_blocked or general_subtrees on a creator of Float32 state (cnl_create_f32*, the inner handle of float32_refine): CNL_ERR_ARG
 int check_no_general_blocked(const cnl::Tuning& o, const char* fn);
 
 // ---- capi_handle.cpp ----
@@ -348,7 +357,7 @@ struct SubBatch {
   cnl_handle* h;
   int64_t batch;
   void *L, *gs, *scratch, *cbuf, *d2, *Lband;
-  int *xpos, *xzer, *gcnt, *dep, *lad, *stat;
+  int *xpos, *xzer, *gcnt, *dep, *lad, *stat, *sub_cnt;
   int32_t* blk_ok;
   const void* last_vals;
   bool staged;

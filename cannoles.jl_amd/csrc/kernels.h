@@ -140,7 +140,8 @@ struct LaunchArgs {
   int phase;             // 0: forward (assembly + elimination) of the tasks, 1: backward sweep of the tasks
   int nquads;            // groups of four problems
   int* gcnt;             // [batch][2] pivot counts summed over the tasks
-  int skip_done;         // classic launch behind a staged attempt: problems with success[b] == 1 are left alone
+  int skip_done;         // classic launch behind a staged attempt: problems with success[b] == 1 are left alone (register-front kernel;
+                         //    of the general kernel the subtree instances alone read it: the climbers' launch, launch_newton_subtrees)
   int ntasks_all;        // tasks of the plan (the counters of the backward phase follow those of the forward phase)
   int df_live;           // 1: this launch spans several stages (tasks wait on the counters; signals are released); 0: one stage,
                          //    its dependencies are complete by launch order (no wait, plain counter bump)
@@ -208,6 +209,19 @@ hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const Launch
 hipError_t launch_newton_f32(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream);
 bool newton_f32_has(int tpp, int ppb, bool lds_work);
 bool newton_blocked_has(int tpp, int ppb, bool f32 = false);   // is there a blocked instance (cfg.blocked) of the element type for this configuration?
+// Subtree execution of the general kernel (tuning general_subtrees; kernels.hip: newton_subtrees).  One launch of
+// a SUB instance: P.fronts = the plan's task-region front table (Plan::gfronts), P.work_doubles = Plan::gwork, a.tasks = the device copy
+// of Plan::gtasks (8 words per task), a.scratch the global work area, a.gcnt [tasks][batch][2] the tasks' pivot-count slots;
+// a.phase 0: forward (a.mode MODE_NEWTON / MODE_FACTOR: assembly + elimination at rho as given; MODE_SOLVE: the vector sweep) of the
+// tasks [a.task0, a.task0 + a.ntasks), one workgroup per (task, problem); a.phase 1: their backward sweep, problems with
+// a.success[b] == 0 skipped; a.phase 2: the climbers — one workgroup per problem runs the whole sequential newton_system over the
+// a.ntasks_all tasks, and with a.skip_done = 1 (read by these instances alone among the general kernel's) a problem whose
+// a.success[b] is already 1 leaves at once.  MODE_SOLVE skips problems whose a.success[b] is 0 in both phases.
+hipError_t launch_newton_subtrees(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream);
+bool newton_subtrees_has(int tpp, int ppb);   // is there a subtree instance for this configuration? (Float64 alone)
+// behind the last forward stage of a factorising subtree call: success (and a.npos / a.nzero where given) from the slots of gcnt plus
+// a.extra_pos / a.extra_zer; MODE_NEWTON: rho = 0, nfact = 1 of the problems that succeeded
+hipError_t launch_subtree_decide(const LaunchArgs& a, const int* gcnt, int ntasks, int nvar, hipStream_t stream);
 hipError_t launch_newton2(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream);
 // the register-front kernel on Float32 data (a Float32 general handle with tuning float32_register_front): every size of P named
 // "doubles" counts floats, lds_bytes is computed with 4-byte elements (the record area stays in 32-bit words).  Direct records with

@@ -410,10 +410,177 @@ __device__ __forceinline__ T* as_global(T* p) {  // struct members are generic p
   return (T*)(__attribute__((address_space(1))) T*)p;
 }
 
+// ---------------------------------------------------------------------------
+// Subtree execution (tuning general_subtrees; the SUB instances of newton_kernel: double, PPB = 1, work area in
+// global scratch).  P.fronts is the plan's SECOND front table (plan.h: Plan::gfronts), whose offsets lie in the region of the
+// front's task, and A.tasks the task records (plan.h: GTask, 8 words each).  A launch is one of
+//   A.phase 0  forward of the tasks [A.task0, A.task0 + A.ntasks) of one stage, workgroup = (task, problem): MODE_NEWTON / MODE_FACTOR
+//              assemble and eliminate the task's fronts at rho as given and leave the task's pivot counts in its own slot of
+//              A.gcnt [tasks][batch][2] (no atomic, nothing to zero per call); MODE_SOLVE runs the vector sweep over the same fronts;
+//   A.phase 1  backward sweep of the tasks of one stage, fronts from the task's last down; a problem without a factor
+//              (A.success[b] == 0) is skipped by the whole workgroup;
+//   A.phase 2  the climbers (MODE_NEWTON, A.skip_done = 1), workgroup = problem: a problem whose first attempt succeeded leaves at once,
+//              a failed one runs the complete sequential newton_system — first attempt again, ladder, backward sweep, all outputs —
+//              task by task over the same table (the subtree layout is a valid layout of a sequential walk too).
+// Dependencies between tasks are the order of the launches on the stream: nothing here waits, and no two workgroups of a launch
+// touch the same memory.  Control flow around every barrier is uniform per workgroup (one task of one problem).
+enum { GT_STAGE = 0, GT_F0, GT_F1, GT_PARENT, GT_BASE, GT_PB_OFF, GT_WV_OFF, GT_FMAX, GT_WORDS = 8 };
+
+// the plan as task k sees it: its own panel buffer and staging rows
+__device__ __forceinline__ void sub_enter_task(DevPlan& P, const int32_t* tasks, int k, int& f0, int& f1) {
+  const int32_t* t = tasks + (long long)k * GT_WORDS;
+  f0 = t[GT_F0]; f1 = t[GT_F1];
+  P.pb_off = t[GT_PB_OFF]; P.wv_off = t[GT_WV_OFF]; P.fmax = t[GT_FMAX];
+}
+
+template <int TPP, class T, bool BLK>
+__device__ __forceinline__ bool sub_factor_attempt(DevPlan& P, const int32_t* tasks, int ntasks, const ProblemCtx<T>& c, int tid,
+                                                   bool rho_override, T rho, T eig_tol, int xpos, int xzer) {
+  int npos = xpos, nzer = xzer;
+  for (int k = 0; k < ntasks; k++) {
+    int f0, f1;
+    sub_enter_task(P, tasks, k, f0, f1);
+    for (int s = f0; s < f1; s++) front_forward<TPP, false, true, T, BLK>(P, P.fronts[s], c, tid, rho_override, rho, eig_tol, npos, nzer);
+  }
+  return npos == P.nvar && nzer == 0;
+}
+
+template <int TPP, class T>
+__device__ __forceinline__ void sub_backward_all(DevPlan& P, const int32_t* tasks, int ntasks, const ProblemCtx<T>& c, int tid, T* dout) {
+  for (int k = ntasks - 1; k >= 0; k--) {
+    int f0, f1;
+    sub_enter_task(P, tasks, k, f0, f1);
+    for (int s = f1 - 1; s >= f0; s--) front_backward<TPP, false>(P, P.fronts[s], c, tid, dout);
+  }
+}
+
+template <int TPP, class T, bool BLK>
+__device__ __forceinline__ void newton_subtrees(DevPlan& P, const LaunchArgs& A, T* smem) {
+  T* const a_vals = static_cast<T*>(A.vals);
+  const T* const a_rhs = static_cast<const T*>(A.rhs);
+  T* const a_d = static_cast<T*>(A.d);
+  const int32_t* const tasks = as_global(const_cast<int32_t*>(A.tasks));
+  int* const gcnt = as_global(A.gcnt);
+  const int tid = threadIdx.x;
+  const bool climb = A.phase == 2;
+  const int b = climb ? (int)blockIdx.x : (int)(blockIdx.x % (unsigned)A.batch);
+  const int task = climb ? 0 : A.task0 + (int)(blockIdx.x / (unsigned)A.batch);
+  if (b >= A.batch || task >= A.task0 + A.ntasks) return;
+  ProblemCtx<T> c;
+  c.vals = a_vals ? a_vals + (long long)b * P.vstride : nullptr;
+  c.rhs = a_rhs ? a_rhs + (long long)b * P.rstride : nullptr;
+  c.L = static_cast<T*>(A.L) + (long long)b * P.lsize;
+  c.red = smem;
+  c.W = static_cast<T*>(A.scratch) + (long long)b * P.work_doubles;
+  T* dout = a_d ? a_d + (long long)b * P.dstride : nullptr;
+  const T eig_tol = (T)A.params[0];
+
+  if (!climb) {
+    int f0, f1;
+    sub_enter_task(P, tasks, task, f0, f1);
+    if (A.phase == 1) {
+      if (!A.success[b]) return;
+      for (int s = f1 - 1; s >= f0; s--) front_backward<TPP, false>(P, P.fronts[s], c, tid, dout);
+      return;
+    }
+    if (A.mode == MODE_SOLVE) {
+      if (A.success && !A.success[b]) return;
+      int np = 0, nz = 0;
+      for (int s = f0; s < f1; s++) front_forward<TPP, false, false>(P, P.fronts[s], c, tid, false, T(0), eig_tol, np, nz);
+      return;
+    }
+    if (A.mode == MODE_FACTOR) c.rhs = nullptr;
+    int np = 0, nz = 0;
+    for (int s = f0; s < f1; s++) front_forward<TPP, false, true, T, BLK>(P, P.fronts[s], c, tid, false, T(0), eig_tol, np, nz);
+    if (tid == 0) {
+      int* slot = gcnt + 2 * ((long long)task * A.batch + b);
+      slot[0] = np; slot[1] = nz;
+    }
+    return;
+  }
+  // ---- the climbers: newton_system! of one problem from the start (src/CaNNOLeS.jl:1019-1051), as newton_kernel runs it ----
+  if (A.skip_done && A.success[b]) return;
+  T* const a_rho_old = static_cast<T*>(A.rho_old);
+  T* const a_rho = static_cast<T*>(A.rho);
+  const int nt = A.ntasks_all;
+  const int xpos = A.extra_pos ? A.extra_pos[b] : 0, xzer = A.extra_zer ? A.extra_zer[b] : 0;
+  const T kdec = (T)A.params[2], kinc = (T)A.params[3], klarge = (T)A.params[4], rho0 = (T)A.params[5],
+          rhomax = (T)A.params[6], rhomin = (T)A.params[7];
+  T rho_old = a_rho_old[b];
+  T rho = T(0), wrote = T(0);
+  int nfact = 0;
+  bool success = sub_factor_attempt<TPP, T, BLK>(P, tasks, nt, c, tid, false, T(0), eig_tol, xpos, xzer);
+  nfact++;
+  if (!success) {
+    rho = rho_old == T(0) ? rho0 : max_of(rhomin, kdec * rho_old);
+    wrote = rho;
+    success = sub_factor_attempt<TPP, T, BLK>(P, tasks, nt, c, tid, true, rho, eig_tol, xpos, xzer);
+    nfact++;
+    while (!success && rho <= rhomax) {
+      rho = rho_old == T(0) ? klarge * rho : kinc * rho;
+      if (rho <= rhomax) {
+        wrote = rho;
+        success = sub_factor_attempt<TPP, T, BLK>(P, tasks, nt, c, tid, true, rho, eig_tol, xpos, xzer);
+        nfact++;
+      }
+    }
+    if (rho <= rhomax) rho_old = rho;
+    T* vt = a_vals + (long long)b * P.vstride + P.rho_begin;
+    for (int i = tid; i < P.nvar; i += TPP) vt[i] = wrote;
+  }
+  phase_fence<TPP>();
+  if (success) sub_backward_all<TPP>(P, tasks, nt, c, tid, dout);
+  if (tid == 0) {
+    a_rho[b] = rho;
+    a_rho_old[b] = rho_old;
+    A.nfact[b] = nfact;
+    A.success[b] = success ? 1 : 0;
+  }
+}
+
+// Behind the last forward stage of a subtree call that factorises: one thread per problem sums the tasks' pivot counts with the
+// condensed pivots' (extra_pos / extra_zer), applies the inertia test of src/solver_types.jl:96 and writes what newton_kernel writes
+// for a first attempt — success, npos / nzero where the call asks for them (MODE_FACTOR), and for MODE_NEWTON rho = 0, nfact = 1 of the
+// problems that succeeded, rho_old as it is (the climbers write everything of the others).
+__global__ void __launch_bounds__(256) subtree_decide_kernel(const int* gcnt, int ntasks, int batch, int nvar, int mode, const int* extra_pos,
+                                                            const int* extra_zer, int32_t* success, int64_t* npos, int64_t* nzero, double* rho,
+                                                            int32_t* nfact) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= batch) return;
+  int np = extra_pos ? extra_pos[b] : 0, nz = extra_zer ? extra_zer[b] : 0;
+  for (int k = 0; k < ntasks; k++) {
+    const int* slot = gcnt + 2 * ((long long)k * batch + b);
+    np += slot[0]; nz += slot[1];
+  }
+  const bool ok = np == nvar && nz == 0;
+  success[b] = ok ? 1 : 0;
+  if (npos) npos[b] = np;
+  if (nzero) nzero[b] = nz;
+  if (mode == MODE_NEWTON && ok) { rho[b] = 0.0; nfact[b] = 1; }
+}
+
 // BLK: the blocked elimination of large fronts (PPB = 1; tuning general_blocked: double, TPP 256 or 1024, launch_newton; tuning
 // float32_blocked: float, TPP 256, launch_newton_f32); MODE_SOLVE of such an instance reads A.success
-template <int TPP, int PPB, bool LDSW, class T, bool BLK = false>
+// SUB: the subtree instances (tuning general_subtrees: double, PPB = 1, global work area, TPP 256 or 1024, BLK either way;
+// launch_newton_subtrees) — newton_subtrees above; they alone read A.tasks, A.task0, A.ntasks, A.ntasks_all, A.phase, A.gcnt and
+// A.skip_done here.  Every other instance is the code it was.
+template <int TPP, int PPB, bool LDSW, class T, bool BLK = false, bool SUB = false>
 __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, const LaunchArgs Ain) {
+  if constexpr (SUB) {
+    static_assert(PPB == 1 && !LDSW && TPP >= 256, "subtree instances: one problem per workgroup, work area in global scratch");
+    DevPlan P = Pin;
+    P.fronts = as_global(Pin.fronts); P.seg_ptr = as_global(Pin.seg_ptr); P.asm_pos = as_global(Pin.asm_pos);
+    P.asm_src = as_global(Pin.asm_src); P.child_idx = as_global(Pin.child_idx); P.rel_idx = as_global(Pin.rel_idx);
+    P.perm = as_global(Pin.perm);
+    LaunchArgs A = Ain;
+    A.vals = as_global(Ain.vals); A.rhs = as_global(Ain.rhs); A.d = as_global(Ain.d); A.L = as_global(Ain.L);
+    A.scratch = as_global(Ain.scratch); A.rho_old = as_global(Ain.rho_old); A.rho = as_global(Ain.rho);
+    A.nfact = as_global(Ain.nfact); A.success = as_global(Ain.success);
+    A.extra_pos = as_global(Ain.extra_pos); A.extra_zer = as_global(Ain.extra_zer);
+    extern __shared__ double smem_sub[];
+    newton_subtrees<TPP, T, BLK>(P, A, reinterpret_cast<T*>(smem_sub));
+    return;
+  }
   DevPlan P = Pin;
   P.fronts = as_global(Pin.fronts); P.seg_ptr = as_global(Pin.seg_ptr); P.asm_pos = as_global(Pin.asm_pos);
   P.asm_src = as_global(Pin.asm_src); P.child_idx = as_global(Pin.child_idx); P.rel_idx = as_global(Pin.rel_idx);
@@ -546,6 +713,33 @@ hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const Launch
   CNL_CASE(64, 4, false) CNL_CASE(256, 1, false) CNL_CASE(1024, 1, false)
 #undef CNL_CASE
   return hipErrorInvalidConfiguration;
+}
+
+// the configurations with subtree instances (tuning general_subtrees): Float64, one problem per workgroup of 256 or 1024 threads
+bool newton_subtrees_has(int tpp, int ppb) { return ppb == 1 && (tpp == 256 || tpp == 1024); }
+
+// One launch of a subtree instance (newton_subtrees): a.phase 0 / 1 — the a.ntasks tasks of one stage from a.task0 on, one workgroup
+// per (task, problem); a.phase 2 — the climbers, one workgroup per problem.  P.fronts is the task-region front table, P.work_doubles
+// the elements of all regions of a problem, a.tasks the device task records; the work area is a.scratch whatever cfg.lds_work says.
+hipError_t launch_newton_subtrees(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream) {
+  if (!newton_subtrees_has(cfg.tpp, cfg.ppb) || !a.tasks || !a.scratch || a.batch < 1) return hipErrorInvalidConfiguration;
+  const long long grid = a.phase == 2 ? (long long)a.batch : (long long)a.batch * a.ntasks;
+  if (grid < 1 || grid > 0x7fffffffLL) return hipErrorInvalidConfiguration;
+  const size_t lds = 16 * sizeof(double);   // the cross-wave sums of psum
+#define CNL_CASE(T, B) \
+  if (cfg.tpp == T && (cfg.blocked != 0) == B) { \
+    hipLaunchKernelGGL((newton_kernel<T, 1, false, double, B, true>), dim3((unsigned)grid), dim3(T), lds, stream, P, a); \
+    return hipGetLastError(); \
+  }
+  CNL_CASE(256, false) CNL_CASE(256, true) CNL_CASE(1024, false) CNL_CASE(1024, true)
+#undef CNL_CASE
+  return hipErrorInvalidConfiguration;
+}
+
+hipError_t launch_subtree_decide(const LaunchArgs& a, const int* gcnt, int ntasks, int nvar, hipStream_t stream) {
+  hipLaunchKernelGGL(subtree_decide_kernel, dim3((a.batch + 255) / 256), dim3(256), 0, stream, gcnt, ntasks, a.batch, nvar, a.mode, a.extra_pos,
+                     a.extra_zer, a.success, a.npos, a.nzero, static_cast<double*>(a.rho), a.nfact);
+  return hipGetLastError();
 }
 
 // The Float32 instances: the configurations choose_config picks for a Float32 handle (capi_handle.cpp) plus one per thread count and

@@ -20,7 +20,7 @@ namespace cnl {
   X(order_mode, -1)          /* -1 auto (cost model over all candidates), 0 canonical, 1 nested dissection, 2 minimum degree */ \
   X(nd_leaf, 0)              /* nested-dissection leaf size, 0 = sweep                                                      */ \
   X(relax, -1)               /* relaxed-amalgamation budget (explicit zeros per merged column), -1 = default                */ \
-  X(task_cap, 0)             /* fronts per bottom task of a latency plan, 0 = default                                       */ \
+  X(task_cap, 0)             /* fronts per bottom task of a latency plan (and of the cut of general_subtrees), 0 = default  */ \
   X(multipliers_early, 1)    /* candidates with every multiplier right behind the last variable it touches are considered   */ \
   X(condense, 1)             /* static condensation of the -I block                                                         */ \
   X(direct_records, 1)       /* the register-front kernel condenses on the fly (no separate condense pass)                  */ \
@@ -72,7 +72,8 @@ namespace cnl {
   X(refine_rows, 0)          /* the KKT residual kernel (refine.h): 0 by the pattern, 1 a row per lane, 2 a row per wavefront */ \
   X(general_blocked, 0)      /* general kernel, Float64: 1 = fronts with 16 pivots or more leave in panels of 16, trailing updates on the f64 matrix cores (configurations with 256 or 1024 threads per problem; the others run as without the key); Float64 handles only: cnl_create_f32* and float32_refine refuse it (the Float32 instances have a key of their own, float32_blocked) */ \
   X(float32_blocked, 0)      /* cnl_create_f32: general_blocked for a Float32 general handle: where its newton_system / factorize launches are the general kernel in float with 256 threads per problem, fronts with 16 pivots or more leave in panels of 16, trailing updates on the f32 matrix cores; selects no route: every handle gets the route it gets without the key, and 64 threads per problem run unblocked; 0 or 1; only with float32_general, not with float32_refine; a Float64 creator without float32_refine reads nothing of it, as of float32_condense */ \
-  X(cgls_wide, 0)            /* row f4: 0 the ncon-vectors in LDS, more than 1024 constraints are CNL_ERR_DIM; 1 in the global workspace where ncon > 1024; 2 there always */
+  X(general_subtrees, 0)     /* general kernel, Float64: 1 = the elimination tree is cut into tasks (bottom subtrees of at most task_cap fronts, default 8; every front above on its own) and the three calls of the plugin surface run stage by stage, one workgroup per (problem, task), dependencies by launch order alone; acts where the launch is the general kernel with one problem per workgroup of 256 or 1024 threads, the first stage has two tasks or more and batch x gwork x 8 <= 8e9 bytes — every other handle is the one without the key; selects no route, combines with general_blocked; Float64 handles only: cnl_create_f32* and float32_refine refuse it */ \
+  X(cgls_wide, 0)           /* row f4: 0 the ncon-vectors in LDS, more than 1024 constraints are CNL_ERR_DIM; 1 in the global workspace where ncon > 1024; 2 there always */
 
 struct Tuning {
 #define X(name, dflt) int32_t name = dflt;

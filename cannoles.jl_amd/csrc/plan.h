@@ -47,6 +47,10 @@ struct Options {
   int par = 256;
   double slots = 0;  // the same as a fraction (wavefront slots per group of four problems; 0: use par)
   int task_cap = 0;
+  // tuning general_subtrees: cut the tree for the general kernel too (Plan::gtasks) and lay the work area out in task regions;
+  // gsub_rows = rows of pivot-row staging a region holds (2, or the 16 of the W panel with tuning general_blocked)
+  int general_subtrees = 0;
+  int gsub_rows = 2;
   // the rest mirrors cnl_options (include/cannoles_hip.h): explicit switches instead of environment variables, so that the
   // numerical path of a handle depends on its arguments only
   int early = 1;           // consider the "+early" candidates (a multiplier right behind the last variable it touches)
@@ -66,6 +70,19 @@ struct Options {
 struct Task {
   int32_t stage, f0, f1, rec_off, brec_off, is_root;
   int32_t parent, nchild;  // task of the parent front of this task's root (-1: none); number of tasks whose parent this is
+};
+
+// One task of the general kernel's subtree execution (tuning general_subtrees): fronts [f0, f1) — a complete
+// bottom subtree, or a single front above the cut — walked by one workgroup per problem.  The task owns the REGION of the
+// per-problem work area that starts at `base` (elements): the update stack of its fronts by the classic rule from `base` on (and
+// over the same space the solution vectors of the backward sweep), its panel buffer at pb_off and its pivot-row staging / W panel
+// (rows of stride fmax) at wv_off, both absolute offsets.  Regions of different tasks are disjoint and never reused within a call.
+// 8 x int32, uploaded as it stands (kernels.hip reads the words by these positions).
+struct GTask {
+  int32_t stage, f0, f1;
+  int32_t parent;      // task of the parent front of this task's root, -1: none
+  int32_t base, pb_off, wv_off;
+  int32_t fmax;        // largest front order of the task, rounded up to even: the stride of its staging rows
 };
 
 struct Plan {
@@ -129,6 +146,14 @@ struct Plan {
   std::vector<Task> tasks;          // sorted by stage
   std::vector<int32_t> stage_ptr;   // tasks of stage s: [stage_ptr[s], stage_ptr[s + 1])
   double cpath = 0;                 // model cost of the critical path of the chosen order
+  // subtree execution of the general kernel (tuning general_subtrees; empty without the key): the cut by the rule of `tasks`, in
+  // arrays of its own — `tasks` / `stage_ptr` stay the register-front kernel's — and a second front table for it: gfronts[s] is
+  // fronts[s] with foff, ubase and xoff placed inside the region of the front's task (GTask).  `fronts` is what it is without the key.
+  std::vector<GTask> gtasks;        // sorted by stage
+  std::vector<int32_t> gstage_ptr;  // tasks of stage s: [gstage_ptr[s], gstage_ptr[s + 1])
+  std::vector<FrontHdr> gfronts;
+  int64_t gwork = 0;                // elements of work area per problem: all regions side by side
+  int32_t gcap = 0;                 // the cap the cut was made with
 };
 // offsets of the tasks inside the record streams (call again after the forward records are rewritten)
 void finalize_tasks(Plan& P);

@@ -154,7 +154,13 @@ def Options(**kw):
     float32_register_front fallen back to it); the key selects no route, 64 threads per problem run unblocked, and
     config["float32_blocked"] says whether the launches are a blocked instance.  Such a handle keeps the success flags of its last
     factorisation: solve leaves the rows of d of a failed problem untouched.  A Float64 handle without float32_refine reads nothing of
-    the key (as of float32_condense)."""
+    the key (as of float32_condense).  general_subtrees = 1 (Float64 handles only; 0 or 1; combines with general_blocked): the
+    elimination tree is cut into tasks — bottom subtrees of at most task_cap fronts (default 8), every front above on its own — and
+    newton_system / factorize / solve run the general kernel stage by stage, one workgroup per problem and task, on a global work
+    area of Plan.array("ginfo")[0] elements per problem.  It acts where the launch is the general kernel with one problem per
+    workgroup of 256 or 1024 threads, the first stage has two tasks or more and batch x gwork x 8 <= 8e9 bytes;
+    config["general_subtrees"] says whether it does, and every other handle is the one without the key.  Such a handle keeps the
+    success flags of its last factorisation as a blocked one does."""
     o = cnl_options()
     lib().cnl_options_init(C.byref(o))
     assert o.struct_size == C.sizeof(cnl_options), "cnl_options layout differs from the library's"
@@ -501,7 +507,10 @@ class HIPLDLStruct:
                        # newton_system / factorize run a blocked instance of the general kernel (Options(general_blocked=1))
                        "general_blocked": bool((int(cfg[5]) >> 47) & 1),
                        # ... of the general kernel in float, on a Float32 general handle (Options(float32_blocked=1))
-                       "float32_blocked": bool((int(cfg[5]) >> 48) & 1)}
+                       "float32_blocked": bool((int(cfg[5]) >> 48) & 1),
+                       # the three calls run the general kernel's subtree instances stage by stage (Options(general_subtrees=1), where
+                       # it acts: plan_array("gtasks") / ("gstage_ptr") / ("gfronts") / ("ginfo") describe the cut and its work area)
+                       "general_subtrees": bool((int(cfg[5]) >> 49) & 1)}
         if self.config["float32"] and self.config["band"]:   # (a Float32 handle off the band kernels — tuning float32_general — is "v1")
             self.config["kernel"] = "band"
 

@@ -65,6 +65,7 @@ const char* cnl_last_error(void);
  * cnl_get_config bits 38 .. 41; 0.5.1: tuning "float32_staged", no new symbol; 0.5.2: tuning "float32_latency", cnl_get_config
  * bits 42 .. 44, no new symbol; 0.5.3: tuning "cgls_wide", cnl_get_config bits 45 / 46, no new symbol;
  * 0.5.4: tuning "general_blocked", cnl_get_config bit 47, no new symbol; 0.5.5: tuning "float32_blocked", cnl_get_config bit 48,
+ * no new symbol; 0.5.6: tuning "general_subtrees", cnl_get_config bit 49, cnl_plan_get "gtasks" / "gstage_ptr" / "gfronts" / "ginfo",
  * no new symbol) */
 int32_t cnl_version(void);
 
@@ -495,7 +496,30 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  * As in Float64 the handle keeps the success flags of its last factorisation and cnl_solve_f32* leaves the rows of d of a failed
  * problem untouched; decisions (success, nfact, rho, rho_old, the rho slots) are those of the handle without the key wherever the
  * pivots keep the project's Float32 margin from eig_tol, d agrees to Float32 rounding, not bit for bit.  Measured: DESIGN
- * section 9.10. */
+ * section 9.10.
+ *
+ * bit 49 = cnl_newton_system* / cnl_factorize* / cnl_solve* run the general kernel's SUBTREE instances stage by stage (tuning
+ * "general_subtrees=1").
+ *
+ * Tuning "general_subtrees" (0 default, 1; any other value CNL_ERR_ARG; at cnl_create_f32* and together with "float32_refine" — at
+ * cnl_create_ex and cnl_plan_create_ex — CNL_ERR_ARG, answered before a device is looked for): the elimination tree is cut into
+ * tasks — maximal bottom subtrees of at most "task_cap" fronts (default 8), every front above on its own, a task's stage = 1 + the
+ * latest stage of its children's tasks — and each of the three calls runs the general kernel as one launch per stage with one
+ * workgroup per (problem, task): S forward launches, where the call factorises a decide kernel (inertia test over the tasks' pivot
+ * counts), where it solves S backward launches in reverse, and for newton_system one launch more in which the problems that failed
+ * the first attempt run the whole rho ladder sequentially (the others leave at once).  Launches per call: newton_system 2 S + 2,
+ * factorize S + 1, solve 2 S (cnl_launch_counts counts them in its general-kernel slot).  Dependencies are the order of the launches
+ * on the stream alone.  The key selects no route and changes no ordering, front or factor layout; it acts where the launch is the
+ * general kernel ([5] & 15 == 1, condensed or not) with one problem per workgroup of 256 or 1024 threads, the first stage holds at
+ * least two tasks, and batch x gwork x 8 <= 8e9 bytes, gwork = cnl_plan_get "ginfo"[0] elements: every task owns a region of the
+ * per-problem work area (global memory; cfg[3] = 0), never reused within a call.  Every other handle is the one without the key and
+ * reports bit 49 clear.  It combines with "general_blocked" (subtrees for the walk over the small fronts, panels for the separator
+ * fronts).  As a blocked handle it keeps the success flags of its last factorisation: cnl_solve* leaves the rows of d of a failed
+ * problem untouched.  Decisions and d are those of the handle without the key, bit for bit on every tested case (the per-front
+ * arithmetic is the same code).  cnl_plan_get: "gtasks" (8 words per task: stage, first front, end front, parent task, region
+ * base, panel buffer offset, staging offset, staging stride), "gstage_ptr", "gfronts" (the front table with foff / ubase / xoff inside
+ * the task regions), "ginfo" = {gwork, tasks, stages, tasks of the first stage, cap}; all empty without the key.  cnl_multi shards
+ * inherit it.  Measured: DESIGN section 3.2. */
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
 /* (bit 38 = a refined handle — tuning "float32_refine", below —, bits 39-41 = its refinement steps k; every other word and bit
  *  describes its inner Float32 handle, with bit 27 clear: the handle is a Float64 handle.) */

@@ -1,0 +1,184 @@
+"""The general kernel's subtree execution (tuning general_subtrees): whole-call device time of
+cnl_newton_system_dev, cnl_factorize_dev and cnl_solve_dev, taken with device events on the stream, for the SAME handle options with
+the key off and on.
+
+One process.  Per case both handles are created first and make one guarded call (key on agrees with key off in success, nfact and,
+within 1e-9, d); then they take turns call by call, WARMUP rounds and ROUNDS measured rounds: medians, and each side's spread
+(min .. max).  A case counts as FASTER or SLOWER only when the medians differ by more than the larger of the two spreads; otherwise
+it is level.  The baseline is always the key-off handle of the same process.
+
+Cases (CASES): grid_structure(48) and (70) at batch 1, 16 and 256 with general_blocked 0 and 1; task_cap 4, 8, 16, 32 on
+grid_structure(70) x 1 and x 256; the two chain-like trees; the seven-kind mix (tests/support/dense_general_cases.py) repeated to 256
+problems on grid_structure(48), which pays the climbers' repeated first attempt.  Healthy problems everywhere else.
+
+usage: time_general_subtrees.py [--only K,K,...] [--out FILE]
+       time_general_subtrees.py --trace      grid_structure(70) x 1, key on, general_blocked = 1: three newton_system calls and nothing
+                                             else, for a kernel trace taken from outside (profiles/general_subtrees_trace.txt)"""
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WARMUP, ROUNDS = 2, 8
+BASE = dict(general_dense=0, register_front=0, dense_backend=0)
+# (generator, its arguments, batch, extra options, values: "healthy" or "mix")
+CASES = ([("grid", (G,), B, dict(general_blocked=blk), "healthy") for G in (48, 70) for B in (1, 16, 256) for blk in (0, 1)] +
+         [("grid", (70,), B, dict(general_blocked=1, task_cap=cap), "healthy") for B in (1, 256) for cap in (4, 8, 16, 32)] +
+         [("random", (450, 300, 4, 0.02, 1), 256, dict(general_blocked=1), "healthy"),
+          ("random", (1000, 1500, 10, 0.01, 1), 1, dict(general_blocked=1), "healthy"),
+          ("grid", (48,), 256, dict(general_blocked=1), "mix")])
+
+
+def setup():
+    import torch
+    torch.zeros(1, device="cuda")   # torch's HIP runtime first (tests/conftest.py)
+    sys.path.insert(0, ROOT)
+    import cannoles_jl_amd  # noqa: F401
+    from cannoles_jl_amd import hipldl, synthetic as syn
+    return torch, hipldl, syn
+
+
+def inputs(syn, s, B, kind):
+    import numpy as np
+    if kind == "mix":
+        from tests.support import dense_general_cases as GC
+        v, r, ro = GC.values(s, GC.MIX)
+        rep = (B + GC.MIX - 1) // GC.MIX
+        return (np.ascontiguousarray(np.tile(v, (rep, 1))[:B]), np.ascontiguousarray(np.tile(r, (rep, 1))[:B]), np.ascontiguousarray(np.tile(ro, rep)[:B]))
+    nbase = min(B, 8)
+    base = [syn.random_values(s, 40 + 5 * j) for j in range(nbase)]
+    rep = (B + nbase - 1) // nbase
+    return (np.ascontiguousarray(np.tile(np.stack([v for v, _ in base]), (rep, 1))[:B]),
+            np.ascontiguousarray(np.tile(np.stack([r for _, r in base]), (rep, 1))[:B]), np.zeros(B))
+
+
+def make_runs(torch, hipldl, syn, case, keys=(0, 1)):
+    import numpy as np
+    gen, args, B, extra, kind = case
+    s = syn.grid_structure(*args) if gen == "grid" else syn.random_structure(*args)
+    rows, cols = s.kkt_pattern()
+    vh, rh, roh = inputs(syn, s, B, kind)
+    dev = torch.device("cuda", 0)
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    runs = []
+    for key in keys:
+        opt = dict(BASE, general_subtrees=key, **extra)
+        if gen == "grid":
+            opt["plan_kind"] = hipldl.PLAN_THROUGHPUT
+        L = hipldl.HIPLDLStruct(s.N, rows, cols, None, s.nvar, s.nequ, s.ncon, batch=B, options=hipldl.Options(**opt))
+        runs.append(dict(key=key, L=L, vh=torch.from_numpy(vh).to(dev), vals=torch.from_numpy(vh).to(dev), rhs=torch.from_numpy(rh).to(dev), roh=torch.from_numpy(roh).to(dev),
+                         d=torch.zeros((B, s.N), **f64), ro=torch.zeros(B, **f64), rho=torch.zeros(B, **f64), nf=torch.zeros(B, **i32), su=torch.zeros(B, **i32)))
+    return s, runs
+
+
+def one(torch, hipldl, syn, case):
+    import numpy as np
+    gen, args, B, extra, kind = case
+    p = hipldl.default_params()
+    s, runs = make_runs(torch, hipldl, syn, case)
+
+    def reset(r):      # (the ladder writes the rho slots of vals and rho_old: every call starts from the same inputs)
+        r["vals"].copy_(r["vh"])
+        r["ro"].copy_(r["roh"])
+
+    def newton(r):
+        hipldl.newton_system_dev(r["L"], r["vals"].data_ptr(), r["rhs"].data_ptr(), r["d"].data_ptr(), r["ro"].data_ptr(), r["rho"].data_ptr(),
+                                 r["nf"].data_ptr(), r["su"].data_ptr(), p, 0)
+
+    def factorize(r):
+        hipldl.factorize_dev(r["L"], r["vals"].data_ptr(), float(p[0]), r["su"].data_ptr(), stream=0)
+
+    def solve(r):
+        hipldl.solve_dev(r["L"], r["rhs"].data_ptr(), r["d"].data_ptr(), stream=0)
+
+    for r in runs:
+        reset(r)
+        r["d"].fill_(7.0)
+        newton(r)
+        torch.cuda.synchronize()
+    off, on = runs
+    assert off["L"].config["kernel"] == on["L"].config["kernel"] == "v1" and not off["L"].config["general_subtrees"], (off["L"].config, on["L"].config)
+    assert torch.equal(on["su"], off["su"]) and torch.equal(on["nf"], off["nf"]) and torch.equal(on["rho"], off["rho"])
+    ok = off["su"] == 1
+    if kind == "healthy":
+        assert bool(ok.all()) and int(off["nf"].max().item()) == 1
+    agree = float(((on["d"][ok] - off["d"][ok]).abs().amax(1) / off["d"][ok].abs().amax(1)).max().item())
+    assert agree <= 1e-9, agree
+    bit_equal = bool(torch.equal(on["d"][ok], off["d"][ok]))
+    for r in runs:
+        r["t"] = dict(newton=[], factor=[], solve=[])
+    for it in range(WARMUP + ROUNDS):
+        for r in runs:   # the handles take turns; each call between events of its own (solve on the factor of the call before it)
+            for name, fn in (("newton", newton), ("factor", factorize), ("solve", solve)):
+                if name != "solve":
+                    reset(r)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn(r)
+                e1.record()
+                torch.cuda.synchronize()
+                if it >= WARMUP:
+                    r["t"][name].append(e0.elapsed_time(e1))
+    out = []
+    for r in runs:
+        c = r["L"].config
+        gi = r["L"].plan_array("ginfo").tolist()
+        out.append(dict(pattern=f"{gen}{tuple(args)}", B=B, N=s.N, fmax=r["L"].info["fmax"], key=r["key"], subtrees=c["general_subtrees"], blocked=c["general_blocked"],
+                        tpp=c["tpp"], lds_work=c["lds_work"], extra=extra, values=kind, ginfo=gi, bit_equal=bit_equal, agree=agree,
+                        **{k: [float(np.median(v)), min(v), max(v)] for k, v in r["t"].items()}))
+    for r in runs:
+        r["L"].close()
+    return out
+
+
+def verdict(off, on):
+    spread = max(off[2] - off[1], on[2] - on[1])
+    diff = on[0] - off[0]
+    word = "level" if abs(diff) <= spread else ("FASTER" if diff < 0 else "SLOWER")
+    return f"{off[0] / on[0]:6.2f}x {word}"
+
+
+def trace():
+    torch, hipldl, syn = setup()
+    case = ("grid", (70,), 1, dict(general_blocked=1), "healthy")
+    s, runs = make_runs(torch, hipldl, syn, case, keys=(1,))
+    r = runs[0]
+    assert r["L"].config["general_subtrees"] and r["L"].config["general_blocked"], r["L"].config
+    p = hipldl.default_params()
+    for _ in range(3):
+        hipldl.newton_system_dev(r["L"], r["vals"].data_ptr(), r["rhs"].data_ptr(), r["d"].data_ptr(), r["ro"].data_ptr(), r["rho"].data_ptr(),
+                                 r["nf"].data_ptr(), r["su"].data_ptr(), p, 0)
+        torch.cuda.synchronize()
+    assert int(r["su"].item()) == 1
+    print("stage_ptr", r["L"].plan_array("gstage_ptr").tolist(), "ginfo", r["L"].plan_array("ginfo").tolist())
+    r["L"].close()
+    return 0
+
+
+def main(argv):
+    if "--trace" in argv:
+        return trace()
+    torch, hipldl, syn = setup()
+    only = [int(x) for x in argv[argv.index("--only") + 1].split(",")] if "--only" in argv else list(range(len(CASES)))
+    lines = [f"general_subtrees: whole-call device time in ms, median [min .. max] of {ROUNDS} alternated rounds after {WARMUP} warm-up rounds, one process",
+             "pattern x batch, options, tasks / stages (cap), tpp | call | key off | key on | off/on, beyond the larger spread? | d bit-equal"]
+    fmt = lambda t: f"{t[0]:9.3f} [{t[1]:9.3f} .. {t[2]:9.3f}]"
+    for k in only:
+        t0 = time.time()
+        off, on = one(torch, hipldl, syn, CASES[k])
+        gi = on["ginfo"]
+        head = (f"{off['pattern']} x {off['B']}, {'mix, ' if off['values'] == 'mix' else ''}{' '.join(f'{a}={b}' for a, b in off['extra'].items())}, "
+                f"{gi[1]} / {gi[2]} ({gi[4]}), tpp {on['tpp']}, on the route: {on['subtrees']}")
+        for call in ("newton", "factor", "solve"):
+            lines.append(f"[{k}] {head} | {call:6s} | {fmt(off[call])} | {fmt(on[call])} | {verdict(off[call], on[call])} | {on['bit_equal']}")
+        print("\n".join(lines[-3:]) + f"\n    ({time.time() - t0:.1f} s)", flush=True)
+        print(json.dumps(dict(off=off, on=on)), file=sys.stderr, flush=True)
+    if "--out" in argv:
+        with open(argv[argv.index("--out") + 1], "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
