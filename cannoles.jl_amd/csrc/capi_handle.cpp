@@ -89,8 +89,8 @@ int choose_config(cnl_handle* h) {
 // problem holds a factor yet.
 int alloc_blocked_flags(cnl_handle* h) {
   if ((!h->cfg.blocked && !h->subtrees) || h->use_v2 || h->band || h->dense || h->gdense) return CNL_OK;   // (a subtree handle keeps them too)
-  if (int rc = dalloc(h, &h->d_blk_ok, (size_t)h->batch)) return rc;
-  if (hipMemset(h->d_blk_ok, 0, (size_t)h->batch * sizeof(int32_t)) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
+  if (int rc = dalloc_batch(h, &h->d_blk_ok, 1)) return rc;
+  if (hipMemset(h->d_blk_ok, 0, (size_t)h->full_batch * sizeof(int32_t)) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
   return CNL_OK;
 }
 
@@ -114,7 +114,7 @@ int setup_subtrees(cnl_handle* h) {
   if ((rc = upload(h, P.gfronts, &d_gfronts))) return rc;
   std::vector<int32_t> tk(reinterpret_cast<const int32_t*>(P.gtasks.data()), reinterpret_cast<const int32_t*>(P.gtasks.data()) + 8 * P.gtasks.size());
   if ((rc = upload(h, tk, &h->d_gtasks))) return rc;
-  if ((rc = dalloc(h, &h->d_sub_cnt, 2 * (size_t)h->full_batch * P.gtasks.size()))) return rc;
+  if ((rc = dalloc_batch(h, &h->d_sub_cnt, 2 * P.gtasks.size()))) return rc;   // (a view's slots: [tasks][nb][2] from its base)
   h->gstage_ptr = P.gstage_ptr;
   h->dp.fronts = d_gfronts;
   h->dp.work_doubles = (int32_t)P.gwork;
@@ -188,7 +188,7 @@ int setup_v2(cnl_handle* h) {
   while (wpb > 1 && wpb * wave_bytes + 512 > maxlds) wpb--;
   h->wpb2 = wpb;
   h->lds2 = wpb * wave_bytes + 512;
-  if ((rc = dalloc_elems(h, &h->d_gs, (size_t)h->batch * (size_t)d.gs_doubles))) return rc;
+  if ((rc = dalloc_batch(h, &h->d_gs, (size_t)d.gs_doubles))) return rc;
   h->use_v2 = true;
   h->staged = false;
   if ((rc = dalloc(h, &h->d_status, 1))) return rc;
@@ -227,11 +227,13 @@ int setup_v2(cnl_handle* h) {
     h->df_waves = o.dataflow_waves > 0 ? o.dataflow_waves : 1024;
     if (h->resident_waves > 0) h->df_waves = std::min(h->df_waves, h->resident_waves);
     {
-      const size_t B = (size_t)h->batch, nq = (B + 3) / 4, tq = 2 * (size_t)h->ntasks * nq;
+      const size_t B = (size_t)h->full_batch, nq = (B + 3) / 4, tq = 2 * (size_t)h->ntasks * nq;
       // (float: one launch per stage only — no dataflow part, d_dep stays null — unless tuning float32_latency brings the Float64 rules)
       const bool dataflow = o.dataflow && (!h->f32 || o.float32_latency);
       const size_t total = 4 * B + (size_t)cnl::LAD_WORDS * nq + tq + 2 + (dataflow ? tq : 0);
       if ((rc = dalloc(h, &h->d_gcnt, total))) return rc;
+      // (the head of the block, two ints per problem, is what views address: the other counters are per handle — handle.h, SubBatch)
+      if ((rc = register_batch(h, &h->d_gcnt, 2 * sizeof(int)))) return rc;
       if (hipMemset(h->d_gcnt, 0, total * sizeof(int)) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
       h->d_lgcnt = h->d_gcnt + 2 * B;
       h->d_lad = h->d_lgcnt + 2 * B;
@@ -331,9 +333,9 @@ int setup_band(cnl_handle* h, const cnl::BandPlan& Bp0, const char** unfit) {
     return CNL_OK;
   }
   // (+ 32 problems: the band kernels interleave the records of a workgroup's problems, the last workgroup's region is a whole one)
-  const size_t lelems = ((size_t)batch + 32) * (size_t)bd.lsize + 64;
-  if ((rc = dalloc_elems(h, &h->d_Lband, lelems))) return rc;
-  if (hipMemset(h->d_Lband, 0, lelems * (size_t)esz) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
+  const size_t lpad = 32 * (size_t)bd.lsize + 64;
+  if ((rc = dalloc_batch(h, &h->d_Lband, (size_t)bd.lsize, lpad))) return rc;
+  if (hipMemset(h->d_Lband, 0, ((size_t)h->full_batch * (size_t)bd.lsize + lpad) * (size_t)esz) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
   h->band = true;
   return CNL_OK;
 }
@@ -527,7 +529,7 @@ int upload_dev_plan(cnl_handle* h) {
 int upload_dev_cond(cnl_handle* h) {
   const cnl_plan* plan = h->plan;
   const cnl::Cond& C = plan->C;
-  const int64_t N = plan->N, nnz = plan->nnz, nvar = plan->nvar, batch = h->full_batch;
+  const int64_t N = plan->N, nnz = plan->nnz, nvar = plan->nvar;
   int rc;
   cnl::DevCond& dc = h->dc;
   std::vector<int32_t> cidx(N, -1);
@@ -559,9 +561,8 @@ int upload_dev_cond(cnl_handle* h) {
   if ((rc = upload(h, C.r_orig, &dc.r_orig))) return rc;
   dc.N = (int32_t)N; dc.nnz = (int32_t)nnz; dc.nvar = (int32_t)nvar; dc.N2 = (int32_t)C.N2; dc.ncs = (int32_t)C.ncs;
   dc.ncond = (int32_t)C.r_orig.size(); dc.cstride = C.cstride;
-  if ((rc = dalloc(h, &h->d_xpos, (size_t)batch))) return rc;
-  if ((rc = dalloc(h, &h->d_xzer, (size_t)batch))) return rc;
-  return CNL_OK;
+  if ((rc = dalloc_batch(h, &h->d_xpos, 1))) return rc;
+  return dalloc_batch(h, &h->d_xzer, 1);
 }
 
 // The resident condense kernel for a Float32 general handle (kernels.h: DevCondEll), where it pays and fits: the tiled kernel stages
@@ -616,9 +617,10 @@ int new_handle(cnl_handle** hout, cnl_plan* plan, int64_t batch, int device, boo
 int alloc_factor_storage(cnl_handle* h) {
   int rc;
   const size_t lelems = (h->band ? 0 : (size_t)h->full_batch * (size_t)h->dp.lsize) + 4096;
-  if ((rc = dalloc_elems(h, &h->d_L, lelems))) return rc;
+  // (the pad of a band handle is no array of problems — no kernel of such a handle reads d_L —, so there is nothing for a view to move)
+  if ((rc = h->band ? dalloc_elems(h, &h->d_L, lelems) : dalloc_batch(h, &h->d_L, (size_t)h->dp.lsize, 4096))) return rc;
   if (hipMemset(h->d_L, 0, lelems * h->esz()) != hipSuccess) return fail(CNL_ERR_HIP, "hipMemset failed");
-  if (!h->cfg.lds_work && (rc = dalloc_elems(h, &h->d_scratch, (size_t)h->full_batch * (size_t)h->dp.work_doubles))) return rc;
+  if (!h->cfg.lds_work && (rc = dalloc_batch(h, &h->d_scratch, (size_t)h->dp.work_doubles))) return rc;
   return CNL_OK;
 }
 // the handle's route (call_shape.h: decided here, once, for run() and everything that asks what kind of handle this is), its stream,
@@ -659,8 +661,8 @@ int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, co
   // cfg3's size instead of 0.48 + 1.16 (factor panels) + 0.64 (condensed buffer, reduced solution) — 16 384 problems: 29 GB less,
   // and twice the batch fits the 288 GB of a device beside the caller's arrays.
   if (plan->C.active && !h->band) {
-    if ((rc = dalloc_elems(h, &h->d_cbuf, (size_t)batch * (size_t)plan->C.cstride))) return bail(rc);
-    if ((rc = dalloc_elems(h, &h->d_d2, (size_t)batch * (size_t)plan->C.N2))) return bail(rc);
+    if ((rc = dalloc_batch(h, &h->d_cbuf, (size_t)plan->C.cstride))) return bail(rc);
+    if ((rc = dalloc_batch(h, &h->d_d2, (size_t)plan->C.N2))) return bail(rc);
   }
   if (plan->split_mode && h->staged) {
     // x groups of four problems on the chain (two wavefronts each), the rest on the single stream: 2 x + y = 2048 slots
@@ -767,8 +769,8 @@ int create_f32_general_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_
   if ((rc = setup_layout(h))) return bail(rc);   // (batch_layout = CNL_LAYOUT_INTERLEAVED is the band kernels': CNL_ERR_ARG)
   if (plan->C.active) {
     if ((rc = upload_dev_cond(h))) return bail(rc);
-    if ((rc = dalloc_elems(h, &h->d_cbuf, (size_t)batch * (size_t)plan->C.cstride))) return bail(rc);
-    if ((rc = dalloc_elems(h, &h->d_d2, (size_t)batch * (size_t)plan->C.N2))) return bail(rc);
+    if ((rc = dalloc_batch(h, &h->d_cbuf, (size_t)plan->C.cstride))) return bail(rc);
+    if ((rc = dalloc_batch(h, &h->d_d2, (size_t)plan->C.N2))) return bail(rc);
     if ((rc = setup_cond_resident(h))) return bail(rc);
   }
   // tuning float32_general_dense: the condensed system as ONE dense matrix on the float kernels of csrc/dense_f32.hip (Route::GeneralDense,

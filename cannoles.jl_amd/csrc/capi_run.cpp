@@ -177,40 +177,32 @@ int launch_subtrees(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-// SubBatch (handle.h): the view is set up by moving the handle's own pointers, and undone when it goes out of scope
-SubBatch::SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged) : h(h_) {
-  last_vals = h->last_vals; staged = h->staged;
+// SubBatch (handle.h): the table's view moves the handle's per-problem arrays; the rest of the view is set here, and undone when it
+// goes out of scope
+SubBatch::SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged)
+    : h(h_), arrays(h_->batch_arrays, b0), batch(h_->batch), last_vals(h_->last_vals), staged(h_->staged), dep(h_->d_dep), lad(h_->d_lad), stat(h_->d_stat) {
+  h->batch = nb;
   h->last_vals = elem_offset(h, h->last_vals, b0 * h->plan->nnz);
   if (!allow_staged) h->staged = false;
-  batch = h->batch; L = h->d_L; gs = h->d_gs; scratch = h->d_scratch; cbuf = h->d_cbuf; d2 = h->d_d2;
-  blk_ok = h->d_blk_ok;
-  if (h->d_blk_ok) h->d_blk_ok += b0;
-  sub_cnt = h->d_sub_cnt;
-  if (h->d_sub_cnt) h->d_sub_cnt += 2 * b0 * (int64_t)h->plan->P.gtasks.size();   // (a view's slots: [tasks][nb][2] from here)
-  xpos = h->d_xpos; xzer = h->d_xzer; gcnt = h->d_gcnt; dep = h->d_dep; lad = h->d_lad; stat = h->d_stat;
-  Lband = h->d_Lband;
-  h->d_Lband = elem_offset(h, h->d_Lband, b0 * h->bd.lsize);
-  const cnl::Cond& C = h->plan->C;
-  h->batch = nb;
-  h->d_L = elem_offset(h, h->d_L, b0 * h->dp.lsize);
-  h->d_gs = elem_offset(h, h->d_gs, b0 * h->dp2.gs_doubles);
-  h->d_scratch = elem_offset(h, h->d_scratch, b0 * (int64_t)h->dp.work_doubles);
-  h->d_cbuf = elem_offset(h, h->d_cbuf, b0 * C.cstride);
-  h->d_d2 = elem_offset(h, h->d_d2, b0 * C.N2);
-  if (h->d_xpos) h->d_xpos += b0;
-  if (h->d_xzer) h->d_xzer += b0;
-  if (h->d_gcnt) h->d_gcnt += 2 * b0;
   h->d_dep = nullptr; h->d_lad = nullptr; h->d_stat = nullptr;   // views run one launch per stage and keep the sequential ladder
 }
 
 SubBatch::~SubBatch() {
-  h->batch = batch; h->d_L = L; h->d_gs = gs; h->d_scratch = scratch; h->d_cbuf = cbuf; h->d_d2 = d2;
-  h->d_blk_ok = blk_ok; h->d_sub_cnt = sub_cnt;
-  h->d_xpos = xpos; h->d_xzer = xzer; h->d_gcnt = gcnt; h->d_dep = dep; h->d_lad = lad; h->d_stat = stat;
-  h->last_vals = last_vals; h->staged = staged; h->d_Lband = Lband;
+  h->batch = batch; h->last_vals = last_vals; h->staged = staged;
+  h->d_dep = dep; h->d_lad = lad; h->d_stat = stat;
 }
 
 namespace {
+
+// run() on problems [b0, b0 + nb) of the handle and of the caller's arrays, as one part of a split batch: the view, the result arrays
+// and vals / rhs / d from problem b0 on (the caller's `a` is left as it is)
+int run_part(cnl_handle* h, const cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, int64_t b0, int64_t nb, bool allow_staged,
+             hipStream_t stream, RunOpts o) {
+  const int64_t nnz = h->plan->nnz, N = h->plan->N;
+  SubBatch view(h, b0, nb, allow_staged);
+  cnl::LaunchArgs b = shifted(h, a, b0);
+  return run(h, b, elem_offset(h, d_vals, b0 * nnz), elem_offset(h, d_rhs, b0 * N), elem_offset(h, d_d, b0 * N), stream, o);
+}
 
 // Batches between one and two wavefronts per SIMD (4096 .. 8192 problems of cfg3's size): the single stream gives a group of
 // four problems ONE wavefront for 1000 fronts, the bidirectional chain TWO for 500 each, and the machine holds 2048 wavefronts.
@@ -220,60 +212,30 @@ namespace {
 // runs any plan's records from end to end (it already does behind every staged attempt).
 // (the parts are calls of run() with part_of_split set; the events of a timed call bracket all of them)
 int run_split_parts(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs, void* d_d, hipStream_t stream, RunOpts o) {
-  const int64_t nA = h->split_staged, nB = h->batch - nA, nnz = h->plan->nnz, N = h->plan->N;
+  const int64_t nA = h->split_staged, nB = h->batch - nA;
   TimingOff untimed(h);
   o.part_of_split = true;
-  if (h->tail) {
-    // 4096 problems fill every wavefront slot on the bidirectional chain (4.1 ms at cfg3's size); a remainder of r <= 1024 problems
-    // takes 0.5 .. 1.7 ms on its own many-part plan, where two halves of the whole batch need 2 x 3 ms (4608 problems: 5.95 -> 5.0 ms)
+  if (h->tail || h->split_halves) {
+    // One part behind the other on the caller's stream.  Tail: 4096 problems fill every wavefront slot on the bidirectional chain
+    // (4.1 ms at cfg3's size); a remainder of r <= 1024 problems takes 0.5 .. 1.7 ms on its own many-part plan, where two halves of the
+    // whole batch need 2 x 3 ms (4608 problems: 5.95 -> 5.0 ms).  Two halves, each on the chain (two wavefronts per group of problems):
+    // a half of 2304 .. 3840 problems runs at 0.81 .. 0.96 M systems/s, where the single-stream part of the concurrent split needs
+    // its >= 6 ms however few problems it holds (4608 problems: 6.5 ms = 707 k systems/s; two halves: ~5.7 ms).
     cnl_handle* t = h->tail;
-    const bool on_tail = a.mode != cnl::MODE_SOLVE || h->tail_fresh;
-    int rc;
-    {
-      SubBatch view(h, 0, nA, true);
-      cnl::LaunchArgs b = a;
-      rc = run(h, b, d_vals, d_rhs, d_d, stream, o);
-    }
-    if (rc == CNL_OK) {
-      cnl::LaunchArgs b = shifted(h, a, nA);
-      void* tv = elem_offset(h, d_vals, nA * nnz);
-      const void* tr = elem_offset(h, d_rhs, nA * N);
-      void* td = elem_offset(h, d_d, nA * N);
-      if (on_tail) {
-        rc = run(t, b, tv, tr, td, stream, RunOpts{o.first_attempt_only, false});   // (a whole call of the tail handle)
-        if (rc == CNL_OK && a.mode != cnl::MODE_SOLVE) { t->last_vals = tv; t->factorized = true; h->tail_fresh = true; }
-      } else {
-        SubBatch view(h, nA, nB, true);
-        rc = run(h, b, tv, tr, td, stream, o);
-      }
-    }
-    return rc;
-  }
-  if (h->split_halves) {
-    // Two halves, each on the bidirectional chain (two wavefronts per group of problems), one behind the other on the caller's
-    // stream: a half of 2304 .. 3840 problems runs at 0.81 .. 0.96 M systems/s, where the single-stream part of the concurrent
-    // split needs its >= 6 ms however few problems it holds (4608 problems: 6.5 ms = 707 k systems/s; two halves: ~5.7 ms).
-    int rc = CNL_OK;
-    for (int part = 0; part < 2 && rc == CNL_OK; part++) {
-      const int64_t b0 = part ? nA : 0, nb = part ? nB : nA;
-      SubBatch view(h, b0, nb, true);
-      cnl::LaunchArgs b = shifted(h, a, b0);
-      rc = run(h, b, elem_offset(h, d_vals, b0 * nnz), elem_offset(h, d_rhs, b0 * N), elem_offset(h, d_d, b0 * N), stream, o);
-    }
+    const bool on_tail = t && (a.mode != cnl::MODE_SOLVE || h->tail_fresh);   // (else the remainder's factors are in this handle's storage)
+    if (int rc = run_part(h, a, d_vals, d_rhs, d_d, 0, nA, true, stream, o)) return rc;
+    if (!on_tail) return run_part(h, a, d_vals, d_rhs, d_d, nA, nB, true, stream, o);
+    // a whole call of the tail handle, on the caller's arrays from problem nA on
+    cnl::LaunchArgs b = shifted(h, a, nA);
+    void* tv = elem_offset(h, d_vals, nA * h->plan->nnz);
+    const int rc = run(t, b, tv, elem_offset(h, d_rhs, nA * h->plan->N), elem_offset(h, d_d, nA * h->plan->N), stream, RunOpts{o.first_attempt_only, false});
+    if (rc == CNL_OK && a.mode != cnl::MODE_SOLVE) { t->last_vals = tv; t->factorized = true; h->tail_fresh = true; }
     return rc;
   }
   HIPCHK(hipEventRecord(h->ev_fork, stream));
   HIPCHK(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
-  int rc;
-  {
-    SubBatch view(h, nA, nB, false);
-    cnl::LaunchArgs b = shifted(h, a, nA);
-    rc = run(h, b, elem_offset(h, d_vals, nA * nnz), elem_offset(h, d_rhs, nA * N), elem_offset(h, d_d, nA * N), h->aux_stream, o);
-  }
-  if (rc == CNL_OK) {
-    SubBatch view(h, 0, nA, true);
-    rc = run(h, a, d_vals, d_rhs, d_d, stream, o);
-  }
+  int rc = run_part(h, a, d_vals, d_rhs, d_d, nA, nB, false, h->aux_stream, o);
+  if (rc == CNL_OK) rc = run_part(h, a, d_vals, d_rhs, d_d, 0, nA, true, stream, o);
   // join also when an enqueue failed: work already on the second stream must not overlap a later call's use of the handle's arrays
   const hipError_t je = hipEventRecord(h->ev_join, h->aux_stream);
   const hipError_t we = je == hipSuccess ? hipStreamWaitEvent(stream, h->ev_join, 0) : je;

@@ -1,5 +1,7 @@
 // handle.h — what the translation units of the C ABI driver (capi_*.cpp) share: the plan, handle and multi-handle structures, the
 // error helpers and the few functions that cross files.  Host side only: no .hip file includes it.
+// The per-problem device arrays of a handle are declared ONCE, where they are allocated (dalloc_batch, below): that puts them into
+// the handle's table (batch_arrays.h), and the views of a part of the batch (SubBatch) move whatever the table holds.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -20,6 +22,9 @@
 
 #include "../../include/cannoles_hip.h"
 #include "band.h"
+#pragma GCC visibility push(hidden)   // (internal to the library, as everything behind the structures below)
+#include "batch_arrays.h"
+#pragma GCC visibility pop
 #include "call_shape.h"
 #include "condense.h"
 #include "dense.h"
@@ -68,6 +73,11 @@ struct cnl_handle {
   int64_t full_batch = 1;   // the batch the handle was created with: what every allocation, array address and cnl_layout_len are sized by
   int64_t factor_batch = 0; // problems the last factorisation covered (cnl_solve_dev must not be asked for more)
   std::vector<void*> dev_allocs;
+  // The device arrays a kernel indexes by problem, with their bytes per problem (dalloc_batch / register_batch, below): what a SubBatch
+  // view moves.  In it: d_L, d_gs, d_scratch, d_cbuf, d_d2, d_xpos, d_xzer, d_gcnt, d_blk_ok, d_sub_cnt, d_Lband.  NOT in it, and never
+  // moved: the staging of the host-pointer calls (d_vals, d_rhs, d_d, d_res, d_npos: addressed by b0 explicitly), d_act, cgls_ws, the
+  // r_* arrays of a refined handle and dkkt.partial — the calls that use those are not served through views.
+  cnl::BatchArrays batch_arrays;
   cnl::DevPlan dp{};
   cnl::KernelConfig cfg{};
   // v2 (register-front kernel): used for newton_system / factorize when every front has order <= 64
@@ -304,6 +314,26 @@ inline int dalloc_elems(cnl_handle* h, void** out, size_t count) {
   return rc;
 }
 
+// A per-problem device array (batch_arrays.h): put into the handle's table, where the views of a part of the batch find it
+template <class T>
+int register_batch(cnl_handle* h, T** slot, size_t bytes_per_problem) {
+  if (!h->batch_arrays.add(reinterpret_cast<void**>(slot), (int64_t)bytes_per_problem))
+    return fail(CNL_ERR_STATE, "per-problem array registered twice, with no bytes per problem, or beyond the table's capacity (batch_arrays.h)");
+  return CNL_OK;
+}
+// ... allocated and registered in one: `per_problem` items for each problem of the CREATED batch and `pad` more behind the last one.
+// The one way to give a handle an array that a kernel indexes by problem; what is allocated otherwise is not served through views.
+template <class T>
+int dalloc_batch(cnl_handle* h, T** out, size_t per_problem, size_t pad = 0) {
+  if (int rc = dalloc(h, out, (size_t)h->full_batch * per_problem + pad)) return rc;
+  return register_batch(h, out, per_problem * sizeof(T));
+}
+// ... counted in elements of the handle's element type
+inline int dalloc_batch(cnl_handle* h, void** out, size_t per_problem, size_t pad = 0) {
+  if (int rc = dalloc_elems(h, out, (size_t)h->full_batch * per_problem + pad)) return rc;
+  return register_batch(h, out, per_problem * h->esz());
+}
+
 // ---- capi_plan.cpp ----
 int resolve_options(const cnl_options* in, cnl::Tuning& out);
 int plan_create_tuned(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar, int64_t nequ,
@@ -350,17 +380,17 @@ struct TimingOff {
   ~TimingOff() { h->timing = was; }
 };
 
-// run() on problems [b0, b0 + nb) of the handle: the base pointer of every per-problem device array of the handle is moved to
-// problem b0 and the batch set to nb for the lifetime of the view (b0 a multiple of 4: a wavefront serves four problems).
-// Dataflow counters are per handle, not per view: views run one launch per stage.
+// run() on problems [b0, b0 + nb) of the handle: every array of the handle's table (batch_arrays) is moved to problem b0 and the
+// batch set to nb for the lifetime of the view (b0 a multiple of 4: a wavefront serves four problems); last_vals — the caller's array,
+// nnz elements per problem — moves with them.  Views nest: one opened inside another counts b0 from the outer one's first problem.
+// Dataflow counters are per handle, not per view: views run one launch per stage (d_dep, d_lad, d_stat: null); !allow_staged: classic.
 struct SubBatch {
   cnl_handle* h;
+  cnl::BatchView arrays;
   int64_t batch;
-  void *L, *gs, *scratch, *cbuf, *d2, *Lband;
-  int *xpos, *xzer, *gcnt, *dep, *lad, *stat, *sub_cnt;
-  int32_t* blk_ok;
   const void* last_vals;
   bool staged;
+  int *dep, *lad, *stat;
   SubBatch(cnl_handle* h_, int64_t b0, int64_t nb, bool allow_staged = true);
   ~SubBatch();
 };
