@@ -94,21 +94,23 @@ int alloc_blocked_flags(cnl_handle* h) {
   return CNL_OK;
 }
 
-// Tuning general_subtrees: does the key act on this Float64 handle?  A pure function of plan, batch and options
-// (the configuration is choose_config's, which reads the same three and the device's LDS size):
+// Tuning general_subtrees, on a Float32 general handle float32_subtrees: does the key of the
+// handle's element type act on this handle?  A pure function of plan, batch and options (the configuration is choose_config's, which
+// reads the same three and the device's LDS size):
 //   - the Newton / factorise launch is the general kernel: no register-front, band or dense route took the handle;
-//   - one problem per workgroup of 256 or 1024 threads (the configurations with subtree instances);
+//   - one problem per workgroup of 256 or 1024 threads, in float of 256 (the configurations with subtree instances);
 //   - the cut has at least two tasks in its first stage (a chain of single-front stages gains nothing: every stage is one task);
-//   - the task regions of the whole batch fit 8e9 bytes (the bound of the dense batch rule).
+//   - the task regions of the whole batch, in elements of the handle's type, fit 8e9 bytes (the bound of the dense batch rule).
 // Where it acts the work area becomes the global array of task regions (gwork elements per problem; LDS cannot be shared between
 // workgroups) and the device plan walks the second front table.  Everywhere else nothing of the handle changes.
 // To be called once the routes are decided and before the factor storage (and with it d_scratch) is allocated.
 int setup_subtrees(cnl_handle* h) {
   const cnl::Plan& P = h->plan->P;
-  if (!h->plan->opt.general_subtrees || h->f32 || h->use_v2 || h->band || h->dense || h->gdense) return CNL_OK;
-  if (!cnl::newton_subtrees_has(h->cfg.tpp, h->cfg.ppb)) return CNL_OK;
+  const cnl::Tuning& o = h->plan->opt;
+  if (!(h->f32 ? o.float32_subtrees : o.general_subtrees) || h->use_v2 || h->band || h->dense || h->gdense) return CNL_OK;
+  if (!cnl::newton_subtrees_has(h->cfg.tpp, h->cfg.ppb, h->f32)) return CNL_OK;
   if (P.gtasks.empty() || P.gstage_ptr.size() < 2 || P.gstage_ptr[1] < 2) return CNL_OK;
-  if ((double)h->full_batch * (double)P.gwork * 8.0 > 8e9) return CNL_OK;
+  if ((double)h->full_batch * (double)P.gwork * (double)h->esz() > 8e9) return CNL_OK;
   int rc;
   const cnl::FrontHdr* d_gfronts = nullptr;
   if ((rc = upload(h, P.gfronts, &d_gfronts))) return rc;
@@ -119,7 +121,7 @@ int setup_subtrees(cnl_handle* h) {
   h->dp.fronts = d_gfronts;
   h->dp.work_doubles = (int32_t)P.gwork;
   h->cfg.lds_work = 0;
-  h->cfg.lds_bytes = 16 * sizeof(double);
+  h->cfg.lds_bytes = 16 * h->esz();
   h->subtrees = true;
   return CNL_OK;
 }
@@ -795,8 +797,9 @@ int create_f32_general_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_
                                       plan->opt.dense_graph != 0, plan->opt.dense_panel_blocks))
       return bail(fail(CNL_ERR_HIP, "dense backend (Float32): " + derr));
   }
+  if ((rc = setup_subtrees(h))) return bail(rc);   // (tuning float32_subtrees: where it acts, d_scratch below is the task regions, in floats)
   if ((rc = alloc_factor_storage(h))) return bail(rc);
-  if ((rc = alloc_blocked_flags(h))) return bail(rc);   // (tuning float32_blocked)
+  if ((rc = alloc_blocked_flags(h))) return bail(rc);   // (tuning float32_blocked, float32_subtrees)
   if ((rc = finish_handle(h, rows1, cols1))) return bail(rc);
   *hout = h;
   return CNL_OK;
@@ -1134,7 +1137,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   if (h->route == cnl::Route::Direct) cfg[5] |= (int64_t)1 << 36;                 // the Direct route (call_shape.h), either element type
   if (h->route == cnl::Route::Direct && h->v2_solve) cfg[5] |= (int64_t)1 << 37;  // ... on which solve_ldl! runs on the register-front kernel too
   if (h->cfg.blocked && !h->use_v2 && !dense_route && !on_band) cfg[5] |= (int64_t)1 << (h->f32 ? 48 : 47);   // newton_system / factorize run a blocked instance of the general kernel (bit 47: Float64, tuning general_blocked; bit 48: Float32, tuning float32_blocked)
-  if (h->subtrees) cfg[5] |= (int64_t)1 << 49;   // the three calls run the general kernel's subtree instances stage by stage (tuning general_subtrees, where it acts)
+  if (h->subtrees) cfg[5] |= (int64_t)1 << (h->f32 ? 50 : 49);   // the three calls run the general kernel's subtree instances stage by stage (bit 49: Float64, tuning general_subtrees; bit 50: Float32, tuning float32_subtrees; where the key acts)
   if (h->lean && !dense_route) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->staged && h->use_v2 && !dense_route) {          // staged handles: how the stages run
     if (h->d_dep) cfg[5] |= (int64_t)1 << 42;            // dataflow counters present (one launch per phase where the rule allows)

@@ -273,13 +273,19 @@ int check_f32_options(const cnl::Tuning& o, const char* fn) {
     return fail(CNL_ERR_ARG, f + ": tuning float32_blocked = 1 needs float32_general = 1 (the blocked float instances of the general kernel serve Float32 general handles)");
   if (o.float32_blocked && o.float32_refine)
     return fail(CNL_ERR_ARG, f + ": tuning float32_blocked = 1 does not go with float32_refine (no refined handle over a blocked Float32 factor)");
+  if (o.float32_subtrees < 0 || o.float32_subtrees > 1)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_subtrees is 0 or 1 (the general kernel in float runs the subtrees of the elimination tree on workgroups of their own, stage by stage)");
+  if (o.float32_subtrees && !o.float32_general)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_subtrees = 1 needs float32_general = 1 (the float subtree instances of the general kernel serve Float32 general handles)");
+  if (o.float32_subtrees && o.float32_refine)
+    return fail(CNL_ERR_ARG, f + ": tuning float32_subtrees = 1 does not go with float32_refine (no refined handle over a subtree Float32 factor)");
   return CNL_OK;
 }
 
 int check_no_general_blocked(const cnl::Tuning& o, const char* fn) {
   if (o.general_blocked)
     return fail(CNL_ERR_ARG, std::string(fn) + ": tuning general_blocked = 1 is served by Float64 handles only (a Float32 general handle takes its blocked instances with tuning float32_blocked)");
-  if (o.general_subtrees)   // (tuning general_subtrees: the same rule — there is no Float32 subtree instance)
+  if (o.general_subtrees)   // (tuning general_subtrees: the same rule — the float subtree instances have a key of their own, float32_subtrees; the message is kept word for word)
     return fail(CNL_ERR_ARG, std::string(fn) + ": tuning general_subtrees = 1 is served by Float64 handles only (the general kernel has no Float32 subtree instances)");
   return CNL_OK;
 }
@@ -341,6 +347,11 @@ int f32_general_plan(cnl_plan** plan, int64_t N, int64_t nnz, const int64_t* row
   // condensation passes), no register-front records, no dense routes, no staged execution, no band program.
   cnl::Tuning g = o;
   g.condense = o.float32_condense ? 1 : 0; g.register_front = 0; g.dense_backend = 0; g.general_dense = 0; g.staged = 0; g.band_kernel = 0;
+  // tuning float32_subtrees: the analysis cuts the tree for the general kernel (Options::general_subtrees) and gives every task region
+  // the staging rows choose_config sizes for this handle (Options::gsub_rows: 16 with float32_blocked, else 2).  The creators refuse the
+  // caller's own general_subtrees / general_blocked before they come here, so both keys of g are the analysis's alone; the handle reads
+  // float32_subtrees and float32_blocked (setup_subtrees, choose_config).  Plan::gwork and the offsets count elements: floats here.
+  if (o.float32_subtrees) { g.general_subtrees = 1; g.general_blocked = o.float32_blocked ? 1 : 0; }
   // (a dense residual block holds nvar * nequ Jacobian entries, nequ diagonal entries and the nvar rho slots at least: a pattern
   //  with fewer entries is not analysed a second time for the question)
   if (o.float32_dense && o.dense_backend && nequ > 0 && nnz / nequ >= nvar) {
@@ -436,7 +447,9 @@ const char* cnl_last_error(void) { return g_err.c_str(); }
 //        no new symbol
 // 0.5.6: tuning general_subtrees (the general kernel stage by stage, one workgroup per problem and task of the elimination tree, Float64),
 //        cnl_get_config bit 49, cnl_plan_get "gtasks" / "gstage_ptr" / "gfronts" / "ginfo", no new symbol
-int32_t cnl_version(void) { return 506; }
+// 0.5.7: tuning float32_subtrees (the general kernel stage by stage in float, for Float32 general handles), cnl_get_config bit 50,
+//        no new symbol
+int32_t cnl_version(void) { return 507; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62

@@ -131,8 +131,8 @@ int launch_staged(cnl_handle* h, cnl::LaunchArgs& a, bool first_attempt_only, bo
   return CNL_OK;
 }
 
-// One call of a subtree handle (tuning general_subtrees), S = stages of the cut: a launch per stage walks the tasks
-// of that stage forward (one workgroup per problem and task); where the call factorises, the decide kernel behind the last stage
+// One call of a subtree handle of either element type (tuning general_subtrees, float32_subtrees; DESIGN sections 3.2 and 9.11),
+// S = stages of the cut: a launch per stage walks the tasks of that stage forward (one workgroup per problem and task); where the call factorises, the decide kernel behind the last stage
 // makes the flags of the first attempt; where it solves, a launch per stage in reverse runs the backward sweeps of the problems that
 // hold a factor; newton_system ends with the climbers' launch, which takes the failed problems through the whole ladder.
 // Launches: newton_system 2 S + 2, try_to_factorize S + 1, solve_ldl! 2 S.  The order on the stream is the only dependency.
@@ -150,19 +150,19 @@ int launch_subtrees(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
   auto stage = [&](int s, int phase) {
     a.phase = phase; a.task0 = h->gstage_ptr[s]; a.ntasks = h->gstage_ptr[s + 1] - h->gstage_ptr[s];
     g_launches[2]++;
-    return cnl::launch_newton_subtrees(h->dp, h->cfg, a, stream);
+    return cnl::launch_newton_subtrees(h->dp, h->cfg, a, stream, h->f32);
   };
   for (int s = 0; s < nst && e == hipSuccess; s++) e = stage(s, 0);
   if (!solve && e == hipSuccess) {
     g_launches[2]++;   // (cnl_launch_counts: the decide kernel is a launch of the pass, counted with the stages)
-    e = cnl::launch_subtree_decide(a, h->d_sub_cnt, ntasks, (int)h->dp.nvar, stream);
+    e = cnl::launch_subtree_decide(a, h->d_sub_cnt, ntasks, (int)h->dp.nvar, stream, h->f32);
   }
   if (a.mode != cnl::MODE_FACTOR)
     for (int s = nst - 1; s >= 0 && e == hipSuccess; s--) e = stage(s, 1);
   if (newton && e == hipSuccess) {
     a.phase = 2; a.task0 = 0; a.ntasks = ntasks; a.skip_done = 1;
     g_launches[2]++;
-    e = cnl::launch_newton_subtrees(h->dp, h->cfg, a, stream);
+    e = cnl::launch_newton_subtrees(h->dp, h->cfg, a, stream, h->f32);
     a.skip_done = 0;
   }
   if (!solve && e == hipSuccess)

@@ -115,7 +115,8 @@ struct cnl_handle {
   // the last factorisation of every problem, copied behind each Newton / factorise launch; solve_ldl! leaves the rows of d of a
   // problem without a factor untouched (the blocked instance and the expand pass read them)
   int32_t* d_blk_ok = nullptr;
-  // tuning general_subtrees, where it acts (capi_handle.cpp: setup_subtrees; cnl_get_config bit 49): the three calls
+  // tuning general_subtrees, on a Float32 general handle float32_subtrees, where it acts (capi_handle.cpp: setup_subtrees; cnl_get_config
+  // bit 49, in float bit 50; DESIGN sections 3.2 and 9.11; sizes in elements of the handle's type): the three calls
   // run the general kernel's subtree instances stage by stage.  dp.fronts is then the plan's task-region front table and
   // dp.work_doubles its gwork — the work area is d_scratch, global, whatever the configuration said —, d_gtasks the task records,
   // gstage_ptr the plan's stage pointers, d_sub_cnt [tasks][batch][2] the tasks' pivot counts of the call under way (views of the

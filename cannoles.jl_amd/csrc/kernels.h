@@ -209,7 +209,8 @@ hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const Launch
 hipError_t launch_newton_f32(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream);
 bool newton_f32_has(int tpp, int ppb, bool lds_work);
 bool newton_blocked_has(int tpp, int ppb, bool f32 = false);   // is there a blocked instance (cfg.blocked) of the element type for this configuration?
-// Subtree execution of the general kernel (tuning general_subtrees; kernels.hip: newton_subtrees).  One launch of
+// Subtree execution of the general kernel (tuning general_subtrees, float32_subtrees on a Float32 handle; DESIGN sections 3.2 and 9.11;
+// kernels.hip: newton_subtrees).  f32: the element type of the handle (arrays of a, work area, rho).  One launch of
 // a SUB instance: P.fronts = the plan's task-region front table (Plan::gfronts), P.work_doubles = Plan::gwork, a.tasks = the device copy
 // of Plan::gtasks (8 words per task), a.scratch the global work area, a.gcnt [tasks][batch][2] the tasks' pivot-count slots;
 // a.phase 0: forward (a.mode MODE_NEWTON / MODE_FACTOR: assembly + elimination at rho as given; MODE_SOLVE: the vector sweep) of the
@@ -217,11 +218,11 @@ bool newton_blocked_has(int tpp, int ppb, bool f32 = false);   // is there a blo
 // a.success[b] == 0 skipped; a.phase 2: the climbers — one workgroup per problem runs the whole sequential newton_system over the
 // a.ntasks_all tasks, and with a.skip_done = 1 (read by these instances alone among the general kernel's) a problem whose
 // a.success[b] is already 1 leaves at once.  MODE_SOLVE skips problems whose a.success[b] is 0 in both phases.
-hipError_t launch_newton_subtrees(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream);
-bool newton_subtrees_has(int tpp, int ppb);   // is there a subtree instance for this configuration? (Float64 alone)
+hipError_t launch_newton_subtrees(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream, bool f32);
+bool newton_subtrees_has(int tpp, int ppb, bool f32);   // is there a subtree instance of the element type for this configuration?
 // behind the last forward stage of a factorising subtree call: success (and a.npos / a.nzero where given) from the slots of gcnt plus
 // a.extra_pos / a.extra_zer; MODE_NEWTON: rho = 0, nfact = 1 of the problems that succeeded
-hipError_t launch_subtree_decide(const LaunchArgs& a, const int* gcnt, int ntasks, int nvar, hipStream_t stream);
+hipError_t launch_subtree_decide(const LaunchArgs& a, const int* gcnt, int ntasks, int nvar, hipStream_t stream, bool f32);
 hipError_t launch_newton2(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream);
 // the register-front kernel on Float32 data (a Float32 general handle with tuning float32_register_front): every size of P named
 // "doubles" counts floats, lds_bytes is computed with 4-byte elements (the record area stays in 32-bit words).  Direct records with

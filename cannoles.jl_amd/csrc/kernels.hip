@@ -411,9 +411,9 @@ __device__ __forceinline__ T* as_global(T* p) {  // struct members are generic p
 }
 
 // ---------------------------------------------------------------------------
-// Subtree execution (tuning general_subtrees; the SUB instances of newton_kernel: double, PPB = 1, work area in
-// global scratch).  P.fronts is the plan's SECOND front table (plan.h: Plan::gfronts), whose offsets lie in the region of the
-// front's task, and A.tasks the task records (plan.h: GTask, 8 words each).  A launch is one of
+// Subtree execution (tuning general_subtrees, and float32_subtrees on a Float32 handle; DESIGN sections 3.2 and 9.11; the SUB instances
+// of newton_kernel: double or float, PPB = 1, work area in global scratch).  P.fronts is the plan's SECOND front table (plan.h:
+// Plan::gfronts), whose offsets lie in the region of the front's task, and A.tasks the task records (plan.h: GTask, 8 words each).  A launch is one of
 //   A.phase 0  forward of the tasks [A.task0, A.task0 + A.ntasks) of one stage, workgroup = (task, problem): MODE_NEWTON / MODE_FACTOR
 //              assemble and eliminate the task's fronts at rho as given and leave the task's pivot counts in its own slot of
 //              A.gcnt [tasks][batch][2] (no atomic, nothing to zero per call); MODE_SOLVE runs the vector sweep over the same fronts;
@@ -541,9 +541,10 @@ __device__ __forceinline__ void newton_subtrees(DevPlan& P, const LaunchArgs& A,
 // Behind the last forward stage of a subtree call that factorises: one thread per problem sums the tasks' pivot counts with the
 // condensed pivots' (extra_pos / extra_zer), applies the inertia test of src/solver_types.jl:96 and writes what newton_kernel writes
 // for a first attempt — success, npos / nzero where the call asks for them (MODE_FACTOR), and for MODE_NEWTON rho = 0, nfact = 1 of the
-// problems that succeeded, rho_old as it is (the climbers write everything of the others).
+// problems that succeeded, rho_old as it is (the climbers write everything of the others).  T: the element type of the handle's rho.
+template <class T>
 __global__ void __launch_bounds__(256) subtree_decide_kernel(const int* gcnt, int ntasks, int batch, int nvar, int mode, const int* extra_pos,
-                                                            const int* extra_zer, int32_t* success, int64_t* npos, int64_t* nzero, double* rho,
+                                                            const int* extra_zer, int32_t* success, int64_t* npos, int64_t* nzero, T* rho,
                                                             int32_t* nfact) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= batch) return;
@@ -556,14 +557,14 @@ __global__ void __launch_bounds__(256) subtree_decide_kernel(const int* gcnt, in
   success[b] = ok ? 1 : 0;
   if (npos) npos[b] = np;
   if (nzero) nzero[b] = nz;
-  if (mode == MODE_NEWTON && ok) { rho[b] = 0.0; nfact[b] = 1; }
+  if (mode == MODE_NEWTON && ok) { rho[b] = T(0); nfact[b] = 1; }
 }
 
 // BLK: the blocked elimination of large fronts (PPB = 1; tuning general_blocked: double, TPP 256 or 1024, launch_newton; tuning
 // float32_blocked: float, TPP 256, launch_newton_f32); MODE_SOLVE of such an instance reads A.success
-// SUB: the subtree instances (tuning general_subtrees: double, PPB = 1, global work area, TPP 256 or 1024, BLK either way;
-// launch_newton_subtrees) — newton_subtrees above; they alone read A.tasks, A.task0, A.ntasks, A.ntasks_all, A.phase, A.gcnt and
-// A.skip_done here.  Every other instance is the code it was.
+// SUB: the subtree instances (PPB = 1, global work area, BLK either way; tuning general_subtrees: double, TPP 256 or 1024; tuning
+// float32_subtrees: float, TPP 256; launch_newton_subtrees) — newton_subtrees above; they alone read A.tasks, A.task0, A.ntasks,
+// A.ntasks_all, A.phase, A.gcnt and A.skip_done here.  Every other instance is the code it was.
 template <int TPP, int PPB, bool LDSW, class T, bool BLK = false, bool SUB = false>
 __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, const LaunchArgs Ain) {
   if constexpr (SUB) {
@@ -715,30 +716,41 @@ hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const Launch
   return hipErrorInvalidConfiguration;
 }
 
-// the configurations with subtree instances (tuning general_subtrees): Float64, one problem per workgroup of 256 or 1024 threads
-bool newton_subtrees_has(int tpp, int ppb) { return ppb == 1 && (tpp == 256 || tpp == 1024); }
+// the configurations with subtree instances (tuning general_subtrees; float32_subtrees for f32): one problem per workgroup of 256 or
+// 1024 threads, in float of 256 alone (there is no 1024-thread float instance of any kind)
+bool newton_subtrees_has(int tpp, int ppb, bool f32) { return ppb == 1 && (tpp == 256 || (tpp == 1024 && !f32)); }
 
 // One launch of a subtree instance (newton_subtrees): a.phase 0 / 1 — the a.ntasks tasks of one stage from a.task0 on, one workgroup
 // per (task, problem); a.phase 2 — the climbers, one workgroup per problem.  P.fronts is the task-region front table, P.work_doubles
 // the elements of all regions of a problem, a.tasks the device task records; the work area is a.scratch whatever cfg.lds_work says.
-hipError_t launch_newton_subtrees(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream) {
-  if (!newton_subtrees_has(cfg.tpp, cfg.ppb) || !a.tasks || !a.scratch || a.batch < 1) return hipErrorInvalidConfiguration;
+// f32: the element arrays of a and the work area are float (a Float32 general handle, tuning float32_subtrees).
+hipError_t launch_newton_subtrees(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream, bool f32) {
+  if (!newton_subtrees_has(cfg.tpp, cfg.ppb, f32) || !a.tasks || !a.scratch || a.batch < 1) return hipErrorInvalidConfiguration;
   const long long grid = a.phase == 2 ? (long long)a.batch : (long long)a.batch * a.ntasks;
   if (grid < 1 || grid > 0x7fffffffLL) return hipErrorInvalidConfiguration;
-  const size_t lds = 16 * sizeof(double);   // the cross-wave sums of psum
-#define CNL_CASE(T, B) \
+  const size_t lds = 16 * (f32 ? sizeof(float) : sizeof(double));   // the cross-wave sums of psum
+#define CNL_CASE(T, E, B) \
   if (cfg.tpp == T && (cfg.blocked != 0) == B) { \
-    hipLaunchKernelGGL((newton_kernel<T, 1, false, double, B, true>), dim3((unsigned)grid), dim3(T), lds, stream, P, a); \
+    hipLaunchKernelGGL((newton_kernel<T, 1, false, E, B, true>), dim3((unsigned)grid), dim3(T), lds, stream, P, a); \
     return hipGetLastError(); \
   }
-  CNL_CASE(256, false) CNL_CASE(256, true) CNL_CASE(1024, false) CNL_CASE(1024, true)
+  if (f32) {
+    CNL_CASE(256, float, false) CNL_CASE(256, float, true)
+    return hipErrorInvalidConfiguration;
+  }
+  CNL_CASE(256, double, false) CNL_CASE(256, double, true) CNL_CASE(1024, double, false) CNL_CASE(1024, double, true)
 #undef CNL_CASE
   return hipErrorInvalidConfiguration;
 }
 
-hipError_t launch_subtree_decide(const LaunchArgs& a, const int* gcnt, int ntasks, int nvar, hipStream_t stream) {
-  hipLaunchKernelGGL(subtree_decide_kernel, dim3((a.batch + 255) / 256), dim3(256), 0, stream, gcnt, ntasks, a.batch, nvar, a.mode, a.extra_pos,
-                     a.extra_zer, a.success, a.npos, a.nzero, static_cast<double*>(a.rho), a.nfact);
+hipError_t launch_subtree_decide(const LaunchArgs& a, const int* gcnt, int ntasks, int nvar, hipStream_t stream, bool f32) {
+  const dim3 grid((a.batch + 255) / 256), block(256);
+  if (f32)
+    hipLaunchKernelGGL(subtree_decide_kernel<float>, grid, block, 0, stream, gcnt, ntasks, a.batch, nvar, a.mode, a.extra_pos, a.extra_zer,
+                       a.success, a.npos, a.nzero, static_cast<float*>(a.rho), a.nfact);
+  else
+    hipLaunchKernelGGL(subtree_decide_kernel<double>, grid, block, 0, stream, gcnt, ntasks, a.batch, nvar, a.mode, a.extra_pos, a.extra_zer,
+                       a.success, a.npos, a.nzero, static_cast<double*>(a.rho), a.nfact);
   return hipGetLastError();
 }
 

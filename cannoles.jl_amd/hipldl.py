@@ -160,7 +160,12 @@ def Options(**kw):
     area of Plan.array("ginfo")[0] elements per problem.  It acts where the launch is the general kernel with one problem per
     workgroup of 256 or 1024 threads, the first stage has two tasks or more and batch x gwork x 8 <= 8e9 bytes;
     config["general_subtrees"] says whether it does, and every other handle is the one without the key.  Such a handle keeps the
-    success flags of its last factorisation as a blocked one does."""
+    success flags of its last factorisation as a blocked one does.  float32_subtrees = 1 (only with float32_general = 1, not with
+    float32_refine; 0 or 1; combines with float32_blocked and task_cap): the same for a Float32 general handle — where its launch is
+    the general kernel in float (uncondensed, float32_condense, or float32_register_front fallen back to it) with one problem per
+    workgroup of 256 threads, the first stage has two tasks or more and batch x gwork x 4 <= 8e9 bytes; config["float32_subtrees"] says
+    whether it acts, every other handle is the one without the key, and general_subtrees stays refused at the Float32 creators.  A
+    Float64 handle without float32_refine reads nothing of the key."""
     o = cnl_options()
     lib().cnl_options_init(C.byref(o))
     assert o.struct_size == C.sizeof(cnl_options), "cnl_options layout differs from the library's"
@@ -510,7 +515,9 @@ class HIPLDLStruct:
                        "float32_blocked": bool((int(cfg[5]) >> 48) & 1),
                        # the three calls run the general kernel's subtree instances stage by stage (Options(general_subtrees=1), where
                        # it acts: plan_array("gtasks") / ("gstage_ptr") / ("gfronts") / ("ginfo") describe the cut and its work area)
-                       "general_subtrees": bool((int(cfg[5]) >> 49) & 1)}
+                       "general_subtrees": bool((int(cfg[5]) >> 49) & 1),
+                       # ... in float, on a Float32 general handle (Options(float32_subtrees=1), where it acts)
+                       "float32_subtrees": bool((int(cfg[5]) >> 50) & 1)}
         if self.config["float32"] and self.config["band"]:   # (a Float32 handle off the band kernels — tuning float32_general — is "v1")
             self.config["kernel"] = "band"
 

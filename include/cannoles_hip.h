@@ -66,7 +66,7 @@ const char* cnl_last_error(void);
  * bits 42 .. 44, no new symbol; 0.5.3: tuning "cgls_wide", cnl_get_config bits 45 / 46, no new symbol;
  * 0.5.4: tuning "general_blocked", cnl_get_config bit 47, no new symbol; 0.5.5: tuning "float32_blocked", cnl_get_config bit 48,
  * no new symbol; 0.5.6: tuning "general_subtrees", cnl_get_config bit 49, cnl_plan_get "gtasks" / "gstage_ptr" / "gfronts" / "ginfo",
- * no new symbol) */
+ * no new symbol; 0.5.7: tuning "float32_subtrees", cnl_get_config bit 50, no new symbol) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -519,7 +519,26 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  * arithmetic is the same code).  cnl_plan_get: "gtasks" (8 words per task: stage, first front, end front, parent task, region
  * base, panel buffer offset, staging offset, staging stride), "gstage_ptr", "gfronts" (the front table with foff / ubase / xoff inside
  * the task regions), "ginfo" = {gwork, tasks, stages, tasks of the first stage, cap}; all empty without the key.  cnl_multi shards
- * inherit it.  Measured: DESIGN section 3.2. */
+ * inherit it.  Measured: DESIGN section 3.2.
+ *
+ * bit 50 = cnl_newton_system_f32* / cnl_factorize_f32* / cnl_solve_f32* of a Float32 general handle run the general kernel's SUBTREE
+ * instances in float stage by stage (tuning "float32_subtrees=1"); bit 49 keeps its Float64-only meaning.
+ *
+ * Tuning "float32_subtrees" (0 default, 1): "general_subtrees" for a Float32 general handle.  Rules, all answered before a device is
+ * looked for: only together with "float32_general=1" (alone: CNL_ERR_ARG); any value other than 0 / 1 is CNL_ERR_ARG; together with
+ * "float32_refine" it is CNL_ERR_ARG at cnl_create_ex and at cnl_plan_create_ex (no refined handle over a subtree Float32 factor), as
+ * "float32_blocked" is.  A Float64 creator without "float32_refine" reads nothing of the key, neither its value nor its rules.
+ * "general_subtrees" and "general_blocked" themselves stay refused at the Float32 creators.  With the key the forced analysis of the
+ * handle cuts the tree ("task_cap" as above; the classic tables are those of the key-off plan, bit for bit) and lays the task regions
+ * out with the staging rows of the handle (16 with "float32_blocked=1", else 2); gwork and every offset count 4-byte elements.  The
+ * key selects no route.  It acts where the Newton / factorise launch is the general kernel in float — the uncondensed handle, the
+ * "float32_condense" one, a "float32_register_front" handle that fell back to it — with one problem per workgroup of 256 threads
+ * (there is no 1 024-thread float instance), the first stage holds at least two tasks and batch x gwork x 4 <= 8e9 bytes.  Band,
+ * register-front, staged / latency, "float32_dense" and "float32_general_dense" handles, 64 threads per problem and single-task cuts
+ * are the handles they are without the key and report bit 50 clear.  Launches per call as in Float64 (2 S + 2, S + 1, 2 S), the float
+ * condensation passes around them unchanged; the handle keeps the success flags of its last factorisation whether or not it is
+ * blocked, and cnl_solve_f32* leaves the rows of d of a failed problem untouched.  It combines with "float32_blocked" (the intended
+ * pairing).  Decisions are those of the handle without the key.  Measured: DESIGN section 9.11. */
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
 /* (bit 38 = a refined handle — tuning "float32_refine", below —, bits 39-41 = its refinement steps k; every other word and bit
  *  describes its inner Float32 handle, with bit 27 clear: the handle is a Float64 handle.) */

@@ -11,7 +11,12 @@ Cases (CASES): grid_structure(48) and (70) at batch 1, 16 and 256 with general_b
 grid_structure(70) x 1 and x 256; the two chain-like trees; the seven-kind mix (tests/support/dense_general_cases.py) repeated to 256
 problems on grid_structure(48), which pays the climbers' repeated first attempt.  Healthy problems everywhere else.
 
-usage: time_general_subtrees.py [--only K,K,...] [--out FILE]
+--dtype float32: the same measurement for tuning float32_subtrees on Float32 general handles — the
+float32_condense handle with float32_blocked = 1 on both sides, Float32 data and parameters, CASES_F32: grid_structure(48) and (70) at
+batch 1, 16 and 256, the two chain-like trees, and the Float32 five-kind mix (tests/support/f32_general_dense.py) repeated to 256
+problems on grid_structure(48); d of the two handles is compared within the Float32 forward bar (1e-3).
+
+usage: time_general_subtrees.py [--dtype float32] [--only K,K,...] [--out FILE]
        time_general_subtrees.py --trace      grid_structure(70) x 1, key on, general_blocked = 1: three newton_system calls and nothing
                                              else, for a kernel trace taken from outside (profiles/general_subtrees_trace.txt)"""
 import json
@@ -28,6 +33,12 @@ CASES = ([("grid", (G,), B, dict(general_blocked=blk), "healthy") for G in (48, 
          [("random", (450, 300, 4, 0.02, 1), 256, dict(general_blocked=1), "healthy"),
           ("random", (1000, 1500, 10, 0.01, 1), 1, dict(general_blocked=1), "healthy"),
           ("grid", (48,), 256, dict(general_blocked=1), "mix")])
+BASE_F32 = dict(float32_general=1, float32_condense=1)
+CASES_F32 = ([("grid", (G,), B, dict(float32_blocked=1), "healthy") for G in (48, 70) for B in (1, 16, 256)] +
+             [("random", (450, 300, 4, 0.02, 1), 256, dict(float32_blocked=1), "healthy"),
+              ("random", (1000, 1500, 10, 0.01, 1), 1, dict(float32_blocked=1), "healthy"),
+              ("grid", (48,), 256, dict(float32_blocked=1), "mix")])
+F32 = False      # --dtype float32
 
 
 def setup():
@@ -42,7 +53,10 @@ def setup():
 def inputs(syn, s, B, kind):
     import numpy as np
     if kind == "mix":
-        from tests.support import dense_general_cases as GC
+        if F32:
+            from tests.support import f32_general_dense as GC
+        else:
+            from tests.support import dense_general_cases as GC
         v, r, ro = GC.values(s, GC.MIX)
         rep = (B + GC.MIX - 1) // GC.MIX
         return (np.ascontiguousarray(np.tile(v, (rep, 1))[:B]), np.ascontiguousarray(np.tile(r, (rep, 1))[:B]), np.ascontiguousarray(np.tile(ro, rep)[:B]))
@@ -58,15 +72,15 @@ def make_runs(torch, hipldl, syn, case, keys=(0, 1)):
     gen, args, B, extra, kind = case
     s = syn.grid_structure(*args) if gen == "grid" else syn.random_structure(*args)
     rows, cols = s.kkt_pattern()
-    vh, rh, roh = inputs(syn, s, B, kind)
+    vh, rh, roh = (np.ascontiguousarray(a, np.float32 if F32 else np.float64) for a in inputs(syn, s, B, kind))
     dev = torch.device("cuda", 0)
-    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    f64, i32 = dict(dtype=torch.float32 if F32 else torch.float64, device=dev), dict(dtype=torch.int32, device=dev)   # (the run's element type)
     runs = []
     for key in keys:
-        opt = dict(BASE, general_subtrees=key, **extra)
-        if gen == "grid":
+        opt = dict(BASE_F32, float32_subtrees=key, **extra) if F32 else dict(BASE, general_subtrees=key, **extra)
+        if gen == "grid" and not F32:
             opt["plan_kind"] = hipldl.PLAN_THROUGHPUT
-        L = hipldl.HIPLDLStruct(s.N, rows, cols, None, s.nvar, s.nequ, s.ncon, batch=B, options=hipldl.Options(**opt))
+        L = hipldl.HIPLDLStruct(s.N, rows, cols, None, s.nvar, s.nequ, s.ncon, batch=B, options=hipldl.Options(**opt), **(dict(dtype=np.float32) if F32 else {}))
         runs.append(dict(key=key, L=L, vh=torch.from_numpy(vh).to(dev), vals=torch.from_numpy(vh).to(dev), rhs=torch.from_numpy(rh).to(dev), roh=torch.from_numpy(roh).to(dev),
                          d=torch.zeros((B, s.N), **f64), ro=torch.zeros(B, **f64), rho=torch.zeros(B, **f64), nf=torch.zeros(B, **i32), su=torch.zeros(B, **i32)))
     return s, runs
@@ -75,7 +89,8 @@ def make_runs(torch, hipldl, syn, case, keys=(0, 1)):
 def one(torch, hipldl, syn, case):
     import numpy as np
     gen, args, B, extra, kind = case
-    p = hipldl.default_params()
+    p = hipldl.default_params(np.float32) if F32 else hipldl.default_params()
+    KEY, BLK = ("float32_subtrees", "float32_blocked") if F32 else ("general_subtrees", "general_blocked")
     s, runs = make_runs(torch, hipldl, syn, case)
 
     def reset(r):      # (the ladder writes the rho slots of vals and rho_old: every call starts from the same inputs)
@@ -98,13 +113,14 @@ def one(torch, hipldl, syn, case):
         newton(r)
         torch.cuda.synchronize()
     off, on = runs
-    assert off["L"].config["kernel"] == on["L"].config["kernel"] == "v1" and not off["L"].config["general_subtrees"], (off["L"].config, on["L"].config)
+    assert off["L"].config["kernel"] == on["L"].config["kernel"] == "v1" and not off["L"].config[KEY], (off["L"].config, on["L"].config)
+    assert off["L"].config["float32"] == on["L"].config["float32"] == F32 and off["L"].config[BLK] == on["L"].config[BLK]
     assert torch.equal(on["su"], off["su"]) and torch.equal(on["nf"], off["nf"]) and torch.equal(on["rho"], off["rho"])
     ok = off["su"] == 1
     if kind == "healthy":
         assert bool(ok.all()) and int(off["nf"].max().item()) == 1
     agree = float(((on["d"][ok] - off["d"][ok]).abs().amax(1) / off["d"][ok].abs().amax(1)).max().item())
-    assert agree <= 1e-9, agree
+    assert agree <= (1e-3 if F32 else 1e-9), agree
     bit_equal = bool(torch.equal(on["d"][ok], off["d"][ok]))
     for r in runs:
         r["t"] = dict(newton=[], factor=[], solve=[])
@@ -124,7 +140,7 @@ def one(torch, hipldl, syn, case):
     for r in runs:
         c = r["L"].config
         gi = r["L"].plan_array("ginfo").tolist()
-        out.append(dict(pattern=f"{gen}{tuple(args)}", B=B, N=s.N, fmax=r["L"].info["fmax"], key=r["key"], subtrees=c["general_subtrees"], blocked=c["general_blocked"],
+        out.append(dict(pattern=f"{gen}{tuple(args)}", B=B, N=s.N, fmax=r["L"].info["fmax"], key=r["key"], subtrees=c[KEY], blocked=c[BLK],
                         tpp=c["tpp"], lds_work=c["lds_work"], extra=extra, values=kind, ginfo=gi, bit_equal=bit_equal, agree=agree,
                         **{k: [float(np.median(v)), min(v), max(v)] for k, v in r["t"].items()}))
     for r in runs:
@@ -157,16 +173,20 @@ def trace():
 
 
 def main(argv):
+    global F32
     if "--trace" in argv:
         return trace()
+    if "--dtype" in argv:
+        F32 = {"float32": True, "float64": False}[argv[argv.index("--dtype") + 1]]
+    cases = CASES_F32 if F32 else CASES
     torch, hipldl, syn = setup()
-    only = [int(x) for x in argv[argv.index("--only") + 1].split(",")] if "--only" in argv else list(range(len(CASES)))
-    lines = [f"general_subtrees: whole-call device time in ms, median [min .. max] of {ROUNDS} alternated rounds after {WARMUP} warm-up rounds, one process",
+    only = [int(x) for x in argv[argv.index("--only") + 1].split(",")] if "--only" in argv else list(range(len(cases)))
+    lines = [f"{'float32_subtrees' if F32 else 'general_subtrees'}: whole-call device time in ms, median [min .. max] of {ROUNDS} alternated rounds after {WARMUP} warm-up rounds, one process",
              "pattern x batch, options, tasks / stages (cap), tpp | call | key off | key on | off/on, beyond the larger spread? | d bit-equal"]
     fmt = lambda t: f"{t[0]:9.3f} [{t[1]:9.3f} .. {t[2]:9.3f}]"
     for k in only:
         t0 = time.time()
-        off, on = one(torch, hipldl, syn, CASES[k])
+        off, on = one(torch, hipldl, syn, cases[k])
         gi = on["ginfo"]
         head = (f"{off['pattern']} x {off['B']}, {'mix, ' if off['values'] == 'mix' else ''}{' '.join(f'{a}={b}' for a, b in off['extra'].items())}, "
                 f"{gi[1]} / {gi[2]} ({gi[4]}), tpp {on['tpp']}, on the route: {on['subtrees']}")
