@@ -15,7 +15,7 @@ struct BatchArray {
 
 class BatchArrays {
  public:
-  static constexpr int kMax = 16;   // (a handle has 11)
+  static constexpr int kMax = 16;   // (a handle has 13)
   BatchArrays() = default;
   BatchArrays(const BatchArrays&) = delete;   // (the slots point into ONE owner)
   BatchArrays& operator=(const BatchArrays&) = delete;

@@ -123,6 +123,11 @@ int setup_subtrees(cnl_handle* h) {
   h->cfg.lds_work = 0;
   h->cfg.lds_bytes = 16 * h->esz();
   h->subtrees = true;
+  if (o.subtree_ladder > 0) {   // (tuning subtree_ladder: the ladder state of a call, moved and shortened with every array of the table)
+    if ((rc = dalloc_batch(h, &h->d_lad_done, 1))) return rc;
+    if ((rc = dalloc_batch(h, &h->d_lad_rho, 2))) return rc;
+    h->ladder_rungs = o.subtree_ladder;
+  }
   return CNL_OK;
 }
 
@@ -935,6 +940,7 @@ int cnl_create_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows
   const int rc0 = resolve_options(opt, o);
   if (rc0) return rc0;
   if (o.float32_refine) return create_refined(hout, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, o);
+  if (int rc = check_subtree_ladder(o, false, "cnl_create_ex")) return rc;
   if (o.float32_staged || o.float32_latency)   // (the key's own rules, as every creator answers them; a Float64 handle reads nothing else of it)
     if (int rc = check_f32_options(o, "cnl_create_ex")) return rc;
   return create_tuned(hout, N, nnz, rows1, cols1, nvar, nequ, ncon, batch, device, o);
@@ -956,6 +962,7 @@ int cnl_create_f32_ex(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* 
     return fail(CNL_ERR_ARG, "cnl_create_f32: tuning float32_refine makes a Float64 handle on a Float32 factor: it is read by cnl_create_ex, not here");
   if (int rc = check_f32_options(o, "cnl_create_f32")) return rc;
   if (int rc = check_no_general_blocked(o, "cnl_create_f32")) return rc;
+  if (int rc = check_subtree_ladder(o, true, "cnl_create_f32")) return rc;
   if (!o.band_kernel && !o.float32_general)
     return fail(CNL_ERR_ARG, "cnl_create_f32: cnl_options.band_kernel = 0, and Float32 handles run on the band kernels only (tuning float32_general = 1: "
                              "the general multifrontal kernel)");
@@ -1138,6 +1145,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   if (h->route == cnl::Route::Direct && h->v2_solve) cfg[5] |= (int64_t)1 << 37;  // ... on which solve_ldl! runs on the register-front kernel too
   if (h->cfg.blocked && !h->use_v2 && !dense_route && !on_band) cfg[5] |= (int64_t)1 << (h->f32 ? 48 : 47);   // newton_system / factorize run a blocked instance of the general kernel (bit 47: Float64, tuning general_blocked; bit 48: Float32, tuning float32_blocked)
   if (h->subtrees) cfg[5] |= (int64_t)1 << (h->f32 ? 50 : 49);   // the three calls run the general kernel's subtree instances stage by stage (bit 49: Float64, tuning general_subtrees; bit 50: Float32, tuning float32_subtrees; where the key acts)
+  if (h->subtrees) cfg[5] |= (int64_t)(h->ladder_rungs & 127) << 51;   // ... with this many rungs of the rho ladder enqueued behind the first attempt of newton_system (bits 51 .. 57: tuning subtree_ladder, 0 .. 64, where the subtree key acts)
   if (h->lean && !dense_route) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->staged && h->use_v2 && !dense_route) {          // staged handles: how the stages run
     if (h->d_dep) cfg[5] |= (int64_t)1 << 42;            // dataflow counters present (one launch per phase where the rule allows)

@@ -65,6 +65,7 @@ int cnl_multi_create_ex(cnl_multi** mout, int64_t N, int64_t nnz, const int64_t*
   if (rc) return rc;
   if (o.float32_refine) return fail(CNL_ERR_ARG, "cnl_multi_create_ex: tuning float32_refine is served on single-device handles only (cnl_create_ex)");
   if ((o.float32_staged || o.float32_latency) && (rc = check_f32_options(o, "cnl_multi_create_ex"))) return rc;   // (the key's own rules; its handles are Float64: nothing else of it is read)
+  if ((rc = check_subtree_ladder(o, false, "cnl_multi_create_ex"))) return rc;
   int navail = 0;
   if (hipGetDeviceCount(&navail) != hipSuccess || navail == 0) return fail(CNL_ERR_HIP, "no HIP device available (this backend has no CPU fallback)");
   for (int i = 0; i < ndev; i++) if (devices[i] < 0 || devices[i] >= navail) return fail(CNL_ERR_ARG, "device index out of range");

@@ -82,6 +82,12 @@ int resolve_options(const cnl_options* in, cnl::Tuning& out) {
     return fail(CNL_ERR_ARG, "cnl_options.tuning: general_blocked is 0 or 1 (the general kernel eliminates large fronts in panels of 16 pivots)");
   if (out.general_subtrees < 0 || out.general_subtrees > 1)
     return fail(CNL_ERR_ARG, "cnl_options.tuning: general_subtrees is 0 or 1 (the general kernel runs the subtrees of the elimination tree on workgroups of their own, stage by stage)");
+  if (out.subtree_ladder < 0 || out.subtree_ladder > 64)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_ladder is the number of rungs of the rho ladder a subtree handle enqueues behind the first attempt, 0 (none) .. 64");
+  if (out.subtree_ladder && !out.general_subtrees && !out.float32_subtrees)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_ladder needs general_subtrees = 1 (Float64 handles) or float32_subtrees = 1 (Float32 general handles): the rungs run on the subtree instances of the general kernel");
+  if (out.subtree_ladder && out.float32_refine)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_ladder does not go with float32_refine (no refined handle over a subtree factor)");
   if (out.cgls_wide < 0 || out.cgls_wide > 2)
     return fail(CNL_ERR_ARG, "cnl_options.tuning: cgls_wide is 0 (the LDS instance, ncon <= 1024), 1 (the wide instance where ncon > 1024) or 2 (the wide instance always)");
   return CNL_OK;
@@ -290,6 +296,13 @@ int check_no_general_blocked(const cnl::Tuning& o, const char* fn) {
   return CNL_OK;
 }
 
+int check_subtree_ladder(const cnl::Tuning& o, bool f32, const char* fn) {
+  if (o.subtree_ladder && !(f32 ? o.float32_subtrees : o.general_subtrees))
+    return fail(CNL_ERR_ARG, std::string(fn) + (f32 ? ": tuning subtree_ladder needs float32_subtrees = 1 at a Float32 creator (the rungs run on the float subtree instances)"
+                                                    : ": tuning subtree_ladder needs general_subtrees = 1 at a Float64 creator (the rungs run on the Float64 subtree instances)"));
+  return CNL_OK;
+}
+
 cnl::Tuning f32_unstaged_options(const cnl::Tuning& o) {
   cnl::Tuning u = o;
   u.float32_staged = 0; u.float32_latency = 0; u.float32_register_front = 1; u.float32_direct_records = 1;
@@ -449,7 +462,9 @@ const char* cnl_last_error(void) { return g_err.c_str(); }
 //        cnl_get_config bit 49, cnl_plan_get "gtasks" / "gstage_ptr" / "gfronts" / "ginfo", no new symbol
 // 0.5.7: tuning float32_subtrees (the general kernel stage by stage in float, for Float32 general handles), cnl_get_config bit 50,
 //        no new symbol
-int32_t cnl_version(void) { return 507; }
+// 0.5.8: tuning subtree_ladder (subtree handles of either element type climb R rungs of the rho ladder stage by stage), cnl_get_config
+//        bits 51 .. 57, no new symbol
+int32_t cnl_version(void) { return 508; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62

@@ -137,6 +137,10 @@ int launch_staged(cnl_handle* h, cnl::LaunchArgs& a, bool first_attempt_only, bo
 // hold a factor; newton_system ends with the climbers' launch, which takes the failed problems through the whole ladder.
 // Launches: newton_system 2 S + 2, try_to_factorize S + 1, solve_ldl! 2 S.  The order on the stream is the only dependency.
 // The handle keeps the flags of its last factorisation (d_blk_ok), which solve_ldl! and the expand pass read.
+// Tuning subtree_ladder = R > 0 changes newton_system alone: the first decide also writes the ladder state; R rungs
+// follow, each the S stages at every climbing problem's rho and a rung-decide launch; then the backward stages, the commit of the rho
+// slots and the climbers, who resume the problems still climbing.  (R + 2) S + R + 3 launches, whatever the problems need: the host
+// reads nothing back, and a rung no problem needs is S + 1 launches of workgroups that leave at once.
 int launch_subtrees(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
   begin_launch(h, a, stream);
   const bool newton = a.mode == cnl::MODE_NEWTON, solve = a.mode == cnl::MODE_SOLVE;
@@ -152,17 +156,34 @@ int launch_subtrees(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
     g_launches[2]++;
     return cnl::launch_newton_subtrees(h->dp, h->cfg, a, stream, h->f32);
   };
+  const int rungs = newton ? h->ladder_rungs : 0;
+  const cnl::LadderState lad{h->d_lad_done, h->d_lad_rho, rungs};
   for (int s = 0; s < nst && e == hipSuccess; s++) e = stage(s, 0);
   if (!solve && e == hipSuccess) {
     g_launches[2]++;   // (cnl_launch_counts: the decide kernel is a launch of the pass, counted with the stages)
-    e = cnl::launch_subtree_decide(a, h->d_sub_cnt, ntasks, (int)h->dp.nvar, stream, h->f32);
+    e = rungs ? cnl::launch_subtree_ladder_first(a, lad, h->d_sub_cnt, ntasks, (int)h->dp.nvar, stream, h->f32)
+              : cnl::launch_subtree_decide(a, h->d_sub_cnt, ntasks, (int)h->dp.nvar, stream, h->f32);
+  }
+  for (int k = 1; k <= rungs && e == hipSuccess; k++) {
+    for (int s = 0; s < nst && e == hipSuccess; s++) {
+      a.phase = 0; a.task0 = h->gstage_ptr[s]; a.ntasks = h->gstage_ptr[s + 1] - h->gstage_ptr[s];
+      g_launches[2]++;
+      e = cnl::launch_subtree_ladder(h->dp, h->cfg, a, lad, stream, h->f32);
+    }
+    if (e != hipSuccess) break;
+    g_launches[2]++;
+    e = cnl::launch_subtree_rung_decide(a, lad, k, h->d_sub_cnt, ntasks, (int)h->dp.nvar, stream, h->f32);
   }
   if (a.mode != cnl::MODE_FACTOR)
     for (int s = nst - 1; s >= 0 && e == hipSuccess; s--) e = stage(s, 1);
+  if (rungs && e == hipSuccess) {
+    g_launches[2]++;
+    e = cnl::launch_subtree_ladder_commit(h->dp, a, lad, stream, h->f32);
+  }
   if (newton && e == hipSuccess) {
     a.phase = 2; a.task0 = 0; a.ntasks = ntasks; a.skip_done = 1;
     g_launches[2]++;
-    e = cnl::launch_newton_subtrees(h->dp, h->cfg, a, stream, h->f32);
+    e = rungs ? cnl::launch_subtree_ladder(h->dp, h->cfg, a, lad, stream, h->f32) : cnl::launch_newton_subtrees(h->dp, h->cfg, a, stream, h->f32);
     a.skip_done = 0;
   }
   if (!solve && e == hipSuccess)

@@ -74,7 +74,7 @@ struct cnl_handle {
   int64_t factor_batch = 0; // problems the last factorisation covered (cnl_solve_dev must not be asked for more)
   std::vector<void*> dev_allocs;
   // The device arrays a kernel indexes by problem, with their bytes per problem (dalloc_batch / register_batch, below): what a SubBatch
-  // view moves.  In it: d_L, d_gs, d_scratch, d_cbuf, d_d2, d_xpos, d_xzer, d_gcnt, d_blk_ok, d_sub_cnt, d_Lband.  NOT in it, and never
+  // view moves.  In it: d_L, d_gs, d_scratch, d_cbuf, d_d2, d_xpos, d_xzer, d_gcnt, d_blk_ok, d_sub_cnt, d_Lband, d_lad_done, d_lad_rho.  NOT in it, and never
   // moved: the staging of the host-pointer calls (d_vals, d_rhs, d_d, d_res, d_npos: addressed by b0 explicitly), d_act, cgls_ws, the
   // r_* arrays of a refined handle and dkkt.partial — the calls that use those are not served through views.
   cnl::BatchArrays batch_arrays;
@@ -125,6 +125,12 @@ struct cnl_handle {
   const int32_t* d_gtasks = nullptr;
   int* d_sub_cnt = nullptr;
   std::vector<int32_t> gstage_ptr;
+  // tuning subtree_ladder = R > 0 on such a handle (cnl_get_config bits 51 .. 57): newton_system enqueues R rungs of
+  // the rho ladder behind the first attempt, stage by stage.  The state of the call under way (kernels.h: LadderState), written by the
+  // first decide of every call: d_lad_done [batch], d_lad_rho [batch][2] in the handle's element type.  0: the sequence without the key.
+  int ladder_rungs = 0;
+  int32_t* d_lad_done = nullptr;
+  void* d_lad_rho = nullptr;
   // Float32 general handles on a condensed plan: the resident condense kernel serves the handle (kernels.h: DevCondEll) — where the
   // tiled kernel's chunks degenerate (dense Jacobians) and [vals | rhs] of a problem fits LDS; tuning float32_condense = 2: never
   bool cond_resident = false;
@@ -360,6 +366,8 @@ bool f32_general_dense_fits(const cnl_plan* plan, int64_t batch);
 int check_f32_options(const cnl::Tuning& o, const char* fn);
 // tuning general_blocked or general_subtrees on a creator of Float32 state (cnl_create_f32*, the inner handle of float32_refine): CNL_ERR_ARG
 int check_no_general_blocked(const cnl::Tuning& o, const char* fn);
+// tuning subtree_ladder at a creator whose own subtree key (f32: float32_subtrees, else general_subtrees) is off: CNL_ERR_ARG
+int check_subtree_ladder(const cnl::Tuning& o, bool f32, const char* fn);
 
 // ---- capi_handle.cpp ----
 int ensure_kkt_rows(cnl_handle* h);   // h->dkkt on the device

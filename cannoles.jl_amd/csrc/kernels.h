@@ -223,6 +223,24 @@ bool newton_subtrees_has(int tpp, int ppb, bool f32);   // is there a subtree in
 // behind the last forward stage of a factorising subtree call: success (and a.npos / a.nzero where given) from the slots of gcnt plus
 // a.extra_pos / a.extra_zer; MODE_NEWTON: rho = 0, nfact = 1 of the problems that succeeded
 hipError_t launch_subtree_decide(const LaunchArgs& a, const int* gcnt, int ntasks, int nvar, hipStream_t stream, bool f32);
+// The rho ladder of a subtree handle stage by stage (tuning subtree_ladder = R > 0; kernels.hip: subtree_ladder_kernel).
+// The per-problem state of the call under way: done [batch] — 0 climbing, 1 succeeded on the first attempt, 2 finished inside the rungs —,
+// rho [batch][2] in the handle's element type — {the rho of the problem's next rung, the last rho tried}; rungs = R.
+struct LadderState {
+  int32_t* done;
+  void* rho;
+  int rungs;
+};
+// a.phase 0: forward of the tasks [a.task0, a.task0 + a.ntasks) of one stage at every climbing problem's rho (rho_override), one workgroup
+// per (task, problem), pivot counts into the slots of a.gcnt; a.phase 2: the climbers of the problems still climbing after st.rungs rungs,
+// resumed behind them.  MODE_NEWTON only.  Problems that are done are left alone by both.
+hipError_t launch_subtree_ladder(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, const LadderState& st, hipStream_t stream, bool f32);
+// the first decide of such a call (in the place of launch_subtree_decide): its outputs, st.done and rho_1 of every problem
+hipError_t launch_subtree_ladder_first(const LaunchArgs& a, const LadderState& st, const int* gcnt, int ntasks, int nvar, hipStream_t stream, bool f32);
+// behind the stages of rung k = 1 .. R: inertia rule, nfact = k + 1, success / exhaustion / the next rho of every problem that is not done
+hipError_t launch_subtree_rung_decide(const LaunchArgs& a, const LadderState& st, int k, const int* gcnt, int ntasks, int nvar, hipStream_t stream, bool f32);
+// behind the backward stages: the last rho tried into the rho slots of a.vals of the problems that finished inside the rungs
+hipError_t launch_subtree_ladder_commit(const DevPlan& P, const LaunchArgs& a, const LadderState& st, hipStream_t stream, bool f32);
 hipError_t launch_newton2(const DevPlan2& P, int wpb, size_t lds_bytes, const LaunchArgs& a, hipStream_t stream);
 // the register-front kernel on Float32 data (a Float32 general handle with tuning float32_register_front): every size of P named
 // "doubles" counts floats, lds_bytes is computed with 4-byte elements (the record area stays in 32-bit words).  Direct records with

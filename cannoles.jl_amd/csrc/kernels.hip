@@ -754,6 +754,223 @@ hipError_t launch_subtree_decide(const LaunchArgs& a, const int* gcnt, int ntask
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// The rho ladder of a subtree handle, stage by stage (tuning subtree_ladder = R > 0).  Entries of their own, launched
+// by handles with R > 0 alone: newton_kernel's instances and subtree_decide_kernel are the code they were.  Per-problem state (kernels.h:
+// LadderState): done[b] — 0 climbing, 1 succeeded on the first attempt, 2 finished inside the rungs (success, or the ladder exhausted) —
+// and lrho[b][2] = {the rho of the problem's next rung, the last rho tried}.  The first decide writes done and rho_1 of every problem, so
+// nothing is zeroed per call; every later kernel reads done before anything else.  As everywhere in the subtree execution the order of
+// the launches on the stream is the only dependency: nothing waits, no counter, no atomic.
+//
+// subtree_ladder_kernel, CLIMB = false (A.phase 0): forward of the tasks of one stage at the problem's rho_k (rho_override), workgroup = (task, problem);
+// a workgroup whose problem is done leaves before any barrier.  CLIMB = true (A.phase 2): the climbers, workgroup = problem, for a problem still
+// climbing after R rungs: the reference's while loop (src/CaNNOLeS.jl:1033-1043) entered at rho_{R+1}, which the decide of rung R
+// formed and found <= rhomax, with nfact = R + 1 behind it; the backward sweep on success; all outputs.
+template <int TPP, class T, bool BLK, bool CLIMB>
+__global__ void __launch_bounds__(TPP) subtree_ladder_kernel(const DevPlan Pin, const LaunchArgs Ain, const LadderState Sin) {
+  static_assert(TPP >= 256, "subtree instances: one problem per workgroup of 256 or 1024 threads");
+  DevPlan P = Pin;
+  P.fronts = as_global(Pin.fronts); P.seg_ptr = as_global(Pin.seg_ptr); P.asm_pos = as_global(Pin.asm_pos);
+  P.asm_src = as_global(Pin.asm_src); P.child_idx = as_global(Pin.child_idx); P.rel_idx = as_global(Pin.rel_idx);
+  P.perm = as_global(Pin.perm);
+  LaunchArgs A = Ain;
+  A.vals = as_global(Ain.vals); A.rhs = as_global(Ain.rhs); A.d = as_global(Ain.d); A.L = as_global(Ain.L);
+  A.scratch = as_global(Ain.scratch); A.rho_old = as_global(Ain.rho_old); A.rho = as_global(Ain.rho);
+  A.nfact = as_global(Ain.nfact); A.success = as_global(Ain.success);
+  A.extra_pos = as_global(Ain.extra_pos); A.extra_zer = as_global(Ain.extra_zer);
+  const int32_t* const done = as_global(Sin.done);
+  const T* const lrho = as_global(static_cast<T*>(Sin.rho));
+  extern __shared__ double smem_lad[];
+  T* const a_vals = static_cast<T*>(A.vals);
+  const T* const a_rhs = static_cast<const T*>(A.rhs);
+  T* const a_d = static_cast<T*>(A.d);
+  const int32_t* const tasks = as_global(const_cast<int32_t*>(A.tasks));
+  const int tid = threadIdx.x;
+  constexpr bool climb = CLIMB;   // (instances of their own: the rungs keep the registers of a forward pass)
+  const int b = climb ? (int)blockIdx.x : (int)(blockIdx.x % (unsigned)A.batch);
+  const int task = climb ? 0 : A.task0 + (int)(blockIdx.x / (unsigned)A.batch);
+  if (b >= A.batch || task >= A.task0 + A.ntasks) return;
+  if (done[b]) return;   // uniform per workgroup, before any barrier
+  ProblemCtx<T> c;
+  c.vals = a_vals + (long long)b * P.vstride;
+  c.rhs = a_rhs ? a_rhs + (long long)b * P.rstride : nullptr;
+  c.L = static_cast<T*>(A.L) + (long long)b * P.lsize;
+  c.red = reinterpret_cast<T*>(smem_lad);
+  c.W = static_cast<T*>(A.scratch) + (long long)b * P.work_doubles;
+  const T eig_tol = (T)A.params[0];
+  const T rho_next = lrho[2 * (long long)b];
+  if constexpr (!climb) {
+    int f0, f1;
+    sub_enter_task(P, tasks, task, f0, f1);
+    int np = 0, nz = 0;
+    for (int s = f0; s < f1; s++) front_forward<TPP, false, true, T, BLK>(P, P.fronts[s], c, tid, true, rho_next, eig_tol, np, nz);
+    if (tid == 0) {
+      int* slot = as_global(A.gcnt) + 2 * ((long long)task * A.batch + b);
+      slot[0] = np; slot[1] = nz;
+    }
+  } else {
+    T* dout = a_d ? a_d + (long long)b * P.dstride : nullptr;
+    T* const a_rho_old = static_cast<T*>(A.rho_old);
+    T* const a_rho = static_cast<T*>(A.rho);
+    const int nt = A.ntasks_all;
+    const int xpos = A.extra_pos ? A.extra_pos[b] : 0, xzer = A.extra_zer ? A.extra_zer[b] : 0;
+    const T kinc = (T)A.params[3], klarge = (T)A.params[4], rhomax = (T)A.params[6];
+    T rho_old = a_rho_old[b];
+    T rho = rho_next, wrote = rho_next;
+    int nfact = Sin.rungs + 1;
+    bool success = sub_factor_attempt<TPP, T, BLK>(P, tasks, nt, c, tid, true, rho, eig_tol, xpos, xzer);
+    nfact++;
+    while (!success && rho <= rhomax) {
+      rho = rho_old == T(0) ? klarge * rho : kinc * rho;
+      if (rho <= rhomax) {
+        wrote = rho;
+        success = sub_factor_attempt<TPP, T, BLK>(P, tasks, nt, c, tid, true, rho, eig_tol, xpos, xzer);
+        nfact++;
+      }
+    }
+    if (rho <= rhomax) rho_old = rho;
+    T* vt = a_vals + (long long)b * P.vstride + P.rho_begin;
+    for (int i = tid; i < P.nvar; i += TPP) vt[i] = wrote;
+    phase_fence<TPP>();
+    if (success) sub_backward_all<TPP>(P, tasks, nt, c, tid, dout);
+    if (tid == 0) {
+      a_rho[b] = rho;
+      a_rho_old[b] = rho_old;
+      A.nfact[b] = nfact;
+      A.success[b] = success ? 1 : 0;
+    }
+  }
+}
+
+// The first decide of a newton_system with R > 0, in the place of subtree_decide_kernel: what that kernel writes for MODE_NEWTON, and the
+// ladder state of every problem — done = 1 for a success; for a failure done = 0 and rho_1 = rho_old == 0 ? rho0 : max(rhomin, kdec rho_old)
+// (src/CaNNOLeS.jl:1029), tried whatever its relation to rhomax.
+template <class T>
+__global__ void __launch_bounds__(256) subtree_ladder_first_kernel(const int* gcnt, int ntasks, int batch, int nvar, const int* extra_pos,
+                                                                  const int* extra_zer, int32_t* success, T* rho, const T* rho_old, int32_t* nfact,
+                                                                  int32_t* done, T* lrho, T kdec, T rho0, T rhomin) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= batch) return;
+  int np = extra_pos ? extra_pos[b] : 0, nz = extra_zer ? extra_zer[b] : 0;
+  for (int k = 0; k < ntasks; k++) {
+    const int* slot = gcnt + 2 * ((long long)k * batch + b);
+    np += slot[0]; nz += slot[1];
+  }
+  const bool ok = np == nvar && nz == 0;
+  success[b] = ok ? 1 : 0;
+  done[b] = ok ? 1 : 0;
+  if (ok) { rho[b] = T(0); nfact[b] = 1; return; }
+  const T ro = rho_old[b];
+  lrho[2 * (long long)b] = ro == T(0) ? rho0 : max_of(rhomin, kdec * ro);
+}
+
+// Behind the stages of rung k: one thread per problem that is not done sums the slots, applies the inertia test and moves the problem
+// along the ladder as the reference's loop does (src/CaNNOLeS.jl:1031-1047; rho_old[b] is still the call's incoming value, since only
+// a problem that is done has had it written).  nfact = k + 1.  Success: rho = rho_k, rho_old = rho_k only if rho_k <= rhomax, done.
+// Failure: rho_k > rhomax (rung 1 alone can be: the loop never runs) — done with rho = rho_k; else rho_{k+1} = klarge rho_k or kinc rho_k,
+// and rho_{k+1} > rhomax — the ladder is exhausted — done with rho = rho_{k+1}, which is never tried; rho_old unchanged in both.
+// The comparisons are written as the loop's own (rho <= rhomax), so that a NaN leaves the ladder where the sequential kernel leaves it.
+template <class T>
+__global__ void __launch_bounds__(256) subtree_rung_decide_kernel(const int* gcnt, int ntasks, int batch, int nvar, int k, const int* extra_pos,
+                                                                 const int* extra_zer, int32_t* success, T* rho, T* rho_old, int32_t* nfact,
+                                                                 int32_t* done, T* lrho, T kinc, T klarge, T rhomax) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= batch) return;
+  if (done[b]) return;
+  int np = extra_pos ? extra_pos[b] : 0, nz = extra_zer ? extra_zer[b] : 0;
+  for (int t = 0; t < ntasks; t++) {
+    const int* slot = gcnt + 2 * ((long long)t * batch + b);
+    np += slot[0]; nz += slot[1];
+  }
+  const bool ok = np == nvar && nz == 0;
+  const T r = lrho[2 * (long long)b];
+  nfact[b] = k + 1;
+  lrho[2 * (long long)b + 1] = r;
+  if (ok) {
+    success[b] = 1;
+    rho[b] = r;
+    if (r <= rhomax) rho_old[b] = r;
+    done[b] = 2;
+    return;
+  }
+  if (!(r <= rhomax)) { rho[b] = r; done[b] = 2; return; }
+  const T nx = rho_old[b] == T(0) ? klarge * r : kinc * r;
+  if (!(nx <= rhomax)) { rho[b] = nx; done[b] = 2; return; }
+  lrho[2 * (long long)b] = nx;
+}
+
+// The commit behind the backward stages: one workgroup per problem; a problem that failed the first attempt and finished inside the
+// rungs (done == 2) gets the last rho tried in the nvar rho slots of its vals, as the reference leaves it; every other workgroup leaves.
+template <class T>
+__global__ void __launch_bounds__(256) subtree_ladder_commit_kernel(T* vals, long long vstride, int rho_begin, int nvar, int batch,
+                                                                   const int32_t* done, const T* lrho) {
+  const int b = blockIdx.x;
+  if (b >= batch || done[b] != 2) return;
+  const T wrote = lrho[2 * (long long)b + 1];
+  T* vt = vals + (long long)b * vstride + rho_begin;
+  for (int i = threadIdx.x; i < nvar; i += 256) vt[i] = wrote;
+}
+
+hipError_t launch_subtree_ladder(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, const LadderState& st, hipStream_t stream, bool f32) {
+  if (!newton_subtrees_has(cfg.tpp, cfg.ppb, f32) || !a.tasks || !a.scratch || !a.vals || !st.done || !st.rho || a.batch < 1 || a.mode != MODE_NEWTON ||
+      (a.phase != 0 && a.phase != 2))
+    return hipErrorInvalidConfiguration;
+  const long long grid = a.phase == 2 ? (long long)a.batch : (long long)a.batch * a.ntasks;
+  if (grid < 1 || grid > 0x7fffffffLL) return hipErrorInvalidConfiguration;
+  const size_t lds = 16 * (f32 ? sizeof(float) : sizeof(double));   // the cross-wave sums of psum
+#define CNL_CASE(T, E, B) \
+  if (cfg.tpp == T && (cfg.blocked != 0) == B) { \
+    if (a.phase == 2) hipLaunchKernelGGL((subtree_ladder_kernel<T, E, B, true>), dim3((unsigned)grid), dim3(T), lds, stream, P, a, st); \
+    else hipLaunchKernelGGL((subtree_ladder_kernel<T, E, B, false>), dim3((unsigned)grid), dim3(T), lds, stream, P, a, st); \
+    return hipGetLastError(); \
+  }
+  if (f32) {
+    CNL_CASE(256, float, false) CNL_CASE(256, float, true)
+    return hipErrorInvalidConfiguration;
+  }
+  CNL_CASE(256, double, false) CNL_CASE(256, double, true) CNL_CASE(1024, double, false) CNL_CASE(1024, double, true)
+#undef CNL_CASE
+  return hipErrorInvalidConfiguration;
+}
+
+hipError_t launch_subtree_ladder_first(const LaunchArgs& a, const LadderState& st, const int* gcnt, int ntasks, int nvar, hipStream_t stream, bool f32) {
+  const dim3 grid((a.batch + 255) / 256), block(256);
+  if (f32)
+    hipLaunchKernelGGL(subtree_ladder_first_kernel<float>, grid, block, 0, stream, gcnt, ntasks, a.batch, nvar, a.extra_pos, a.extra_zer, a.success,
+                       static_cast<float*>(a.rho), static_cast<const float*>(a.rho_old), a.nfact, st.done, static_cast<float*>(st.rho),
+                       (float)a.params[2], (float)a.params[5], (float)a.params[7]);
+  else
+    hipLaunchKernelGGL(subtree_ladder_first_kernel<double>, grid, block, 0, stream, gcnt, ntasks, a.batch, nvar, a.extra_pos, a.extra_zer, a.success,
+                       static_cast<double*>(a.rho), static_cast<const double*>(a.rho_old), a.nfact, st.done, static_cast<double*>(st.rho),
+                       a.params[2], a.params[5], a.params[7]);
+  return hipGetLastError();
+}
+
+hipError_t launch_subtree_rung_decide(const LaunchArgs& a, const LadderState& st, int k, const int* gcnt, int ntasks, int nvar, hipStream_t stream, bool f32) {
+  const dim3 grid((a.batch + 255) / 256), block(256);
+  if (f32)
+    hipLaunchKernelGGL(subtree_rung_decide_kernel<float>, grid, block, 0, stream, gcnt, ntasks, a.batch, nvar, k, a.extra_pos, a.extra_zer, a.success,
+                       static_cast<float*>(a.rho), static_cast<float*>(a.rho_old), a.nfact, st.done, static_cast<float*>(st.rho),
+                       (float)a.params[3], (float)a.params[4], (float)a.params[6]);
+  else
+    hipLaunchKernelGGL(subtree_rung_decide_kernel<double>, grid, block, 0, stream, gcnt, ntasks, a.batch, nvar, k, a.extra_pos, a.extra_zer, a.success,
+                       static_cast<double*>(a.rho), static_cast<double*>(a.rho_old), a.nfact, st.done, static_cast<double*>(st.rho),
+                       a.params[3], a.params[4], a.params[6]);
+  return hipGetLastError();
+}
+
+hipError_t launch_subtree_ladder_commit(const DevPlan& P, const LaunchArgs& a, const LadderState& st, hipStream_t stream, bool f32) {
+  if (!a.vals || a.batch < 1) return hipErrorInvalidConfiguration;
+  const dim3 grid(a.batch), block(256);
+  if (f32)
+    hipLaunchKernelGGL(subtree_ladder_commit_kernel<float>, grid, block, 0, stream, static_cast<float*>(a.vals), (long long)P.vstride, (int)P.rho_begin,
+                       (int)P.nvar, a.batch, st.done, static_cast<const float*>(st.rho));
+  else
+    hipLaunchKernelGGL(subtree_ladder_commit_kernel<double>, grid, block, 0, stream, static_cast<double*>(a.vals), (long long)P.vstride, (int)P.rho_begin,
+                       (int)P.nvar, a.batch, st.done, static_cast<const double*>(st.rho));
+  return hipGetLastError();
+}
+
 // The Float32 instances: the configurations choose_config picks for a Float32 handle (capi_handle.cpp) plus one per thread count and
 // work-area placement, each launched by tests/test_float32_general_gpu.py.  Every other configuration of the list above is
 // Float64-only.

@@ -74,7 +74,8 @@ namespace cnl {
   X(float32_blocked, 0)      /* cnl_create_f32: general_blocked for a Float32 general handle: where its newton_system / factorize launches are the general kernel in float with 256 threads per problem, fronts with 16 pivots or more leave in panels of 16, trailing updates on the f32 matrix cores; selects no route: every handle gets the route it gets without the key, and 64 threads per problem run unblocked; 0 or 1; only with float32_general, not with float32_refine; a Float64 creator without float32_refine reads nothing of it, as of float32_condense */ \
   X(general_subtrees, 0)     /* general kernel, Float64: 1 = the elimination tree is cut into tasks (bottom subtrees of at most task_cap fronts, default 8; every front above on its own) and the three calls of the plugin surface run stage by stage, one workgroup per (problem, task), dependencies by launch order alone; acts where the launch is the general kernel with one problem per workgroup of 256 or 1024 threads, the first stage has two tasks or more and batch x gwork x 8 <= 8e9 bytes — every other handle is the one without the key; selects no route, combines with general_blocked; Float64 handles only: cnl_create_f32* and float32_refine refuse it */ \
   X(float32_subtrees, 0)     /* cnl_create_f32: general_subtrees for a Float32 general handle: the forced analysis cuts the tree (task_cap as there) and, where the newton_system / factorize launch is the general kernel in float with one problem per workgroup of 256 threads, the first stage has two tasks or more and batch x gwork x 4 <= 8e9 bytes, the three calls run stage by stage on the float subtree instances; selects no route: every other handle is the one without the key; combines with float32_blocked; 0 or 1; only with float32_general, not with float32_refine; a Float64 creator without float32_refine reads nothing of it, as of float32_condense */ \
-  X(cgls_wide, 0)           /* row f4: 0 the ncon-vectors in LDS, more than 1024 constraints are CNL_ERR_DIM; 1 in the global workspace where ncon > 1024; 2 there always */
+  X(subtree_ladder, 0)       /* subtree handles of either element type: R = 0 .. 64 rungs of the rho ladder are enqueued behind the first attempt of newton_system, each stage by stage like it, one rung-decide launch behind each; problems still climbing after R rungs resume in the climbers' launch; (R + 2) S + R + 3 launches; valid only with general_subtrees = 1 (Float64 creators) or float32_subtrees = 1 (Float32 creators), never with float32_refine; selects no route and changes no plan: it acts where the subtree key acts */ \
+  X(cgls_wide, 0)          /* row f4: 0 the ncon-vectors in LDS, more than 1024 constraints are CNL_ERR_DIM; 1 in the global workspace where ncon > 1024; 2 there always */
 
 struct Tuning {
 #define X(name, dflt) int32_t name = dflt;

@@ -165,7 +165,12 @@ def Options(**kw):
     the general kernel in float (uncondensed, float32_condense, or float32_register_front fallen back to it) with one problem per
     workgroup of 256 threads, the first stage has two tasks or more and batch x gwork x 4 <= 8e9 bytes; config["float32_subtrees"] says
     whether it acts, every other handle is the one without the key, and general_subtrees stays refused at the Float32 creators.  A
-    Float64 handle without float32_refine reads nothing of the key."""
+    Float64 handle without float32_refine reads nothing of the key.  subtree_ladder = R (0 .. 64, default 0; only with general_subtrees = 1
+    at a Float64 creator or float32_subtrees = 1 at a Float32 creator, never with float32_refine; else ValueError / CNL_ERR_ARG): where
+    the subtree key acts, newton_system enqueues R rungs of the rho ladder behind the first attempt, each stage by stage with a decide
+    launch behind it — (R + 2) S + R + 3 launches for S stages —, and the climbers' launch resumes only the problems still climbing after
+    R rungs.  Every output is that of R = 0, bit for bit.  It selects no route and changes no plan; config["subtree_ladder"] is R where
+    the rungs are enqueued and 0 everywhere else."""
     o = cnl_options()
     lib().cnl_options_init(C.byref(o))
     assert o.struct_size == C.sizeof(cnl_options), "cnl_options layout differs from the library's"
@@ -517,7 +522,10 @@ class HIPLDLStruct:
                        # it acts: plan_array("gtasks") / ("gstage_ptr") / ("gfronts") / ("ginfo") describe the cut and its work area)
                        "general_subtrees": bool((int(cfg[5]) >> 49) & 1),
                        # ... in float, on a Float32 general handle (Options(float32_subtrees=1), where it acts)
-                       "float32_subtrees": bool((int(cfg[5]) >> 50) & 1)}
+                       "float32_subtrees": bool((int(cfg[5]) >> 50) & 1),
+                       # ... with this many rungs of the rho ladder enqueued behind the first attempt of newton_system
+                       # (Options(subtree_ladder=R), where the subtree key acts; 0 everywhere else)
+                       "subtree_ladder": (int(cfg[5]) >> 51) & 127}
         if self.config["float32"] and self.config["band"]:   # (a Float32 handle off the band kernels — tuning float32_general — is "v1")
             self.config["kernel"] = "band"
 

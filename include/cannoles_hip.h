@@ -66,7 +66,8 @@ const char* cnl_last_error(void);
  * bits 42 .. 44, no new symbol; 0.5.3: tuning "cgls_wide", cnl_get_config bits 45 / 46, no new symbol;
  * 0.5.4: tuning "general_blocked", cnl_get_config bit 47, no new symbol; 0.5.5: tuning "float32_blocked", cnl_get_config bit 48,
  * no new symbol; 0.5.6: tuning "general_subtrees", cnl_get_config bit 49, cnl_plan_get "gtasks" / "gstage_ptr" / "gfronts" / "ginfo",
- * no new symbol; 0.5.7: tuning "float32_subtrees", cnl_get_config bit 50, no new symbol) */
+ * no new symbol; 0.5.7: tuning "float32_subtrees", cnl_get_config bit 50, no new symbol; 0.5.8: tuning "subtree_ladder", cnl_get_config
+ * bits 51 .. 57, no new symbol) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -538,7 +539,33 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  * are the handles they are without the key and report bit 50 clear.  Launches per call as in Float64 (2 S + 2, S + 1, 2 S), the float
  * condensation passes around them unchanged; the handle keeps the success flags of its last factorisation whether or not it is
  * blocked, and cnl_solve_f32* leaves the rows of d of a failed problem untouched.  It combines with "float32_blocked" (the intended
- * pairing).  Decisions are those of the handle without the key.  Measured: DESIGN section 9.11. */
+ * pairing).  Decisions are those of the handle without the key.  Measured: DESIGN section 9.11.
+ *
+ * bits 51 .. 57 = R, the rungs of the rho ladder a subtree handle (bit 49 or bit 50 set) enqueues behind the first attempt of
+ * cnl_newton_system* (tuning "subtree_ladder=R"); 0 on every other handle, whatever the key said.
+ *
+ * Tuning "subtree_ladder" (0 default, 0 .. 64): a subtree handle of either element type climbs the rho ladder stage by stage.  Rules,
+ * all answered before a device is looked for, at the creators and at cnl_plan_create_ex: a value outside 0 .. 64 is CNL_ERR_ARG; so is
+ * the key without a subtree key, at a Float64 creator (cnl_create_ex, cnl_multi_create_ex) without "general_subtrees=1", at a
+ * Float32 creator (cnl_create_f32*) without "float32_subtrees=1", and together with "float32_refine".  The key selects no route and
+ * changes no plan: it acts exactly where the subtree key of the handle acts, and a handle on which that key does not act is the one
+ * without either key, allocation for allocation.  With R > 0 cnl_newton_system* enqueues, behind the S forward launches and the decide
+ * of the first attempt, R RUNGS: the S forward launches again — a workgroup (task, problem) leaves at once if its problem is done,
+ * else assembles and eliminates its task at the problem's rho_k — and one rung-decide launch, one thread per problem, which applies
+ * the inertia rule, sets nfact = k + 1 and either finishes the problem (success: rho = rho_k, rho_old = rho_k only if rho_k <= rhomax;
+ * or the ladder is exhausted: rho = the first value above rhomax, which is never tried, rho_old unchanged) or forms rho_{k+1} by the
+ * reference's recurrence, in the handle's element type.  rho_1 is tried whatever its relation to rhomax, as the reference does.  Then
+ * the S backward launches of every problem that holds a factor, one commit launch (the last rho tried into the rho slots of vals of
+ * the problems that finished inside the rungs) and the climbers' launch, which skips every problem that is done and RESUMES a problem
+ * still climbing after R rungs at rho_{R+1} with nfact = R + 1 — it does not repeat the attempts already made.  (R + 2) S + R + 3
+ * launches, all counted in the general-kernel slot of cnl_launch_counts and bracketed by the events of a timed call; the order on
+ * the stream is the only dependency (no spin wait, no device counter, no atomic, no host synchronisation in a _dev call).  The host
+ * never reads how many rungs a batch needs: rungs beyond every problem's ladder are empty launches, so R = 64 is harmless on any
+ * parameters.  cnl_factorize* and cnl_solve* are untouched (S + 1, 2 S).  Every output — success, nfact, rho, rho_old, the rho slots
+ * of vals, d of the successes; rows of d of the failures untouched — is that of the same handle with R = 0, bit for bit in both element
+ * types.  The ladder state (a done flag and two rho values per problem) is written by the first decide of every call; sub-batch views
+ * and cnl_set_active_batch move and shorten it with every per-problem array.  cnl_multi shards inherit the key.  Measured: DESIGN
+ * section 3.3. */
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
 /* (bit 38 = a refined handle — tuning "float32_refine", below —, bits 39-41 = its refinement steps k; every other word and bit
  *  describes its inner Float32 handle, with bit 27 clear: the handle is a Float64 handle.) */

@@ -16,7 +16,16 @@ float32_condense handle with float32_blocked = 1 on both sides, Float32 data and
 batch 1, 16 and 256, the two chain-like trees, and the Float32 five-kind mix (tests/support/f32_general_dense.py) repeated to 256
 problems on grid_structure(48); d of the two handles is compared within the Float32 forward bar (1e-3).
 
+--ladder R,R,...: the staged rho ladder (tuning subtree_ladder).  newton_system alone, LADDER_CASES, and per case
+the sides "subtree key off" (the classic kernel), "key on, R = 0" (the sequence without the ladder key) and "key on, subtree_ladder = R"
+for every R given, general_blocked / float32_blocked = 1 on all sides, all in one process and taking turns call by call.  Every side
+must agree with the key-off side in success, nfact and rho, and every R > 0 bit for bit with R = 0 in every output.  The cases: the
+mix x 256 on grid_structure(48); grid_structure(70) x 1 with the one problem of kind 2 (nfact 6, in float 5) and of kind 3 (nfact 4);
+grid_structure(70) x 16 with one kind-2 climber among healthy problems; the healthy grid_structure(70) x 1 and x 256 and
+grid_structure(48) x 256, where a rung is S + 1 empty launches.
+
 usage: time_general_subtrees.py [--dtype float32] [--only K,K,...] [--out FILE]
+       time_general_subtrees.py --ladder 3,5,19 [--dtype float32] [--only K,K,...] [--out FILE]
        time_general_subtrees.py --trace      grid_structure(70) x 1, key on, general_blocked = 1: three newton_system calls and nothing
                                              else, for a kernel trace taken from outside (profiles/general_subtrees_trace.txt)"""
 import json
@@ -38,6 +47,10 @@ CASES_F32 = ([("grid", (G,), B, dict(float32_blocked=1), "healthy") for G in (48
              [("random", (450, 300, 4, 0.02, 1), 256, dict(float32_blocked=1), "healthy"),
               ("random", (1000, 1500, 10, 0.01, 1), 1, dict(float32_blocked=1), "healthy"),
               ("grid", (48,), 256, dict(float32_blocked=1), "mix")])
+# --ladder: (generator, its arguments, batch, values) — "mix", "healthy", "kind2" / "kind3" (every problem of that kind of the mix),
+# "one-climber" (problem 0 of kind 2, the others healthy)
+LADDER_CASES = [("grid", (48,), 256, "mix"), ("grid", (70,), 1, "kind2"), ("grid", (70,), 1, "kind3"), ("grid", (70,), 16, "one-climber"),
+                ("grid", (70,), 1, "healthy"), ("grid", (70,), 256, "healthy"), ("grid", (48,), 256, "healthy")]
 F32 = False      # --dtype float32
 
 
@@ -60,6 +73,12 @@ def inputs(syn, s, B, kind):
         v, r, ro = GC.values(s, GC.MIX)
         rep = (B + GC.MIX - 1) // GC.MIX
         return (np.ascontiguousarray(np.tile(v, (rep, 1))[:B]), np.ascontiguousarray(np.tile(r, (rep, 1))[:B]), np.ascontiguousarray(np.tile(ro, rep)[:B]))
+    if kind in ("kind2", "kind3", "one-climber"):      # the mix's rule for an indefinite Hessian block (kind 3: from rho_old = 2)
+        from tests.support import dense_general_cases as GC
+        v, r, ro = inputs(syn, s, B, "healthy")
+        for b in range(B if kind != "one-climber" else 1):
+            ro[b] = GC.apply_kind(s, v[b], 3 if kind == "kind3" else 2)
+        return v, r, ro
     nbase = min(B, 8)
     base = [syn.random_values(s, 40 + 5 * j) for j in range(nbase)]
     rep = (B + nbase - 1) // nbase
@@ -68,6 +87,7 @@ def inputs(syn, s, B, kind):
 
 
 def make_runs(torch, hipldl, syn, case, keys=(0, 1)):
+    """keys: the sides — 0 / 1 the subtree key, or (1, R) the subtree key with subtree_ladder = R"""
     import numpy as np
     gen, args, B, extra, kind = case
     s = syn.grid_structure(*args) if gen == "grid" else syn.random_structure(*args)
@@ -77,11 +97,14 @@ def make_runs(torch, hipldl, syn, case, keys=(0, 1)):
     f64, i32 = dict(dtype=torch.float32 if F32 else torch.float64, device=dev), dict(dtype=torch.int32, device=dev)   # (the run's element type)
     runs = []
     for key in keys:
+        key, rungs = key if isinstance(key, tuple) else (key, None)
         opt = dict(BASE_F32, float32_subtrees=key, **extra) if F32 else dict(BASE, general_subtrees=key, **extra)
+        if rungs is not None:
+            opt["subtree_ladder"] = rungs
         if gen == "grid" and not F32:
             opt["plan_kind"] = hipldl.PLAN_THROUGHPUT
         L = hipldl.HIPLDLStruct(s.N, rows, cols, None, s.nvar, s.nequ, s.ncon, batch=B, options=hipldl.Options(**opt), **(dict(dtype=np.float32) if F32 else {}))
-        runs.append(dict(key=key, L=L, vh=torch.from_numpy(vh).to(dev), vals=torch.from_numpy(vh).to(dev), rhs=torch.from_numpy(rh).to(dev), roh=torch.from_numpy(roh).to(dev),
+        runs.append(dict(key=key, rungs=rungs, L=L, vh=torch.from_numpy(vh).to(dev), vals=torch.from_numpy(vh).to(dev), rhs=torch.from_numpy(rh).to(dev), roh=torch.from_numpy(roh).to(dev),
                          d=torch.zeros((B, s.N), **f64), ro=torch.zeros(B, **f64), rho=torch.zeros(B, **f64), nf=torch.zeros(B, **i32), su=torch.zeros(B, **i32)))
     return s, runs
 
@@ -148,6 +171,87 @@ def one(torch, hipldl, syn, case):
     return out
 
 
+def ladder_one(torch, hipldl, syn, case, Rs):
+    """one case of --ladder: sides key off, (key on, R = 0), (key on, R) for R in Rs; newton_system only"""
+    import numpy as np
+    gen, args, B, kind = case
+    p = hipldl.default_params(np.float32) if F32 else hipldl.default_params()
+    KEY, BLK = ("float32_subtrees", "float32_blocked") if F32 else ("general_subtrees", "general_blocked")
+    extra = {BLK: 1}
+    s, runs = make_runs(torch, hipldl, syn, (gen, args, B, extra, kind), keys=[0, (1, 0)] + [(1, R) for R in Rs])
+
+    def newton(r):
+        r["vals"].copy_(r["vh"])
+        r["ro"].copy_(r["roh"])
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        hipldl.newton_system_dev(r["L"], r["vals"].data_ptr(), r["rhs"].data_ptr(), r["d"].data_ptr(), r["ro"].data_ptr(), r["rho"].data_ptr(),
+                                 r["nf"].data_ptr(), r["su"].data_ptr(), p, 0)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    for r in runs:
+        r["d"].fill_(7.0)
+        before = hipldl.launch_counts()["general"]
+        newton(r)
+        r["launches"] = hipldl.launch_counts()["general"] - before
+    off, r0 = runs[0], runs[1]
+    assert not off["L"].config[KEY] and off["L"].config["subtree_ladder"] == 0, off["L"].config
+    for r in runs[1:]:
+        c = r["L"].config
+        assert c[KEY] and c["subtree_ladder"] == r["rungs"] and c[BLK] == off["L"].config[BLK] and c["kernel"] == "v1", c
+        for k in ("su", "nf", "rho", "ro"):
+            assert torch.equal(r[k], off[k]), (r["rungs"], k)
+        for k in ("su", "nf", "rho", "ro", "d", "vals"):      # bit for bit the sequence without the ladder key (NaN inputs compare as bits)
+            a, b = r[k], r0[k]
+            assert torch.equal(a.view(torch.int32 if a.element_size() == 4 else torch.int64), b.view(torch.int32 if b.element_size() == 4 else torch.int64)), (r["rungs"], k)
+    if kind == "healthy":
+        assert bool((off["su"] == 1).all()) and int(off["nf"].max().item()) == 1
+    nf = off["nf"].cpu().numpy()
+    for r in runs:
+        r["t"] = []
+    for it in range(WARMUP + ROUNDS):
+        for r in runs:
+            t = newton(r)
+            if it >= WARMUP:
+                r["t"].append(t)
+    gi = r0["L"].plan_array("ginfo").tolist()
+    out = dict(pattern=f"{gen}{tuple(args)}", B=B, N=s.N, values=kind, ginfo=gi, tpp=r0["L"].config["tpp"], nfact=sorted(set(int(x) for x in nf)),
+               sides=[dict(key=r["key"], rungs=r["rungs"], launches=r["launches"], t=[float(np.median(r["t"])), min(r["t"]), max(r["t"])]) for r in runs])
+    for r in runs:
+        r["L"].close()
+    return out
+
+
+def ladder(argv):
+    torch, hipldl, syn = setup()
+    Rs = [int(x) for x in argv[argv.index("--ladder") + 1].split(",")]
+    only = [int(x) for x in argv[argv.index("--only") + 1].split(",")] if "--only" in argv else list(range(len(LADDER_CASES)))
+    key = "float32_subtrees" if F32 else "general_subtrees"
+    lines = [f"subtree_ladder with {key} ({'float32_blocked' if F32 else 'general_blocked'} = 1 on all sides): whole-call device time of newton_system_dev in ms, "
+             f"median [min .. max] of {ROUNDS} alternated rounds after {WARMUP} warm-up rounds, one process; every side agrees with the key-off side in success, nfact, rho, rho_old "
+             f"and every R > 0 with R = 0 bit for bit in every output",
+             "pattern x batch, values (nfact present), tasks / stages, tpp | side | launches | time | against key off | against R = 0 (beyond the larger spread?)"]
+    fmt = lambda t: f"{t[0]:9.3f} [{t[1]:9.3f} .. {t[2]:9.3f}]"
+    for k in only:
+        t0 = time.time()
+        o = ladder_one(torch, hipldl, syn, LADDER_CASES[k], Rs)
+        head = f"{o['pattern']} x {o['B']}, {o['values']} (nfact {o['nfact']}), {o['ginfo'][1]} / {o['ginfo'][2]}, tpp {o['tpp']}"
+        off, r0 = o["sides"][0]["t"], o["sides"][1]["t"]
+        n0 = len(lines)
+        for sd in o["sides"]:
+            name = "key off" if not sd["key"] else f"key on, R = {sd['rungs']}"
+            lines.append(f"[{k}] {head} | {name:16s} | {sd['launches']:4d} | {fmt(sd['t'])} | {verdict(off, sd['t']) if sd['key'] else '':>16s} | "
+                         f"{verdict(r0, sd['t']) if sd['key'] and sd['rungs'] else ''}")
+        print("\n".join(lines[n0:]) + f"\n    ({time.time() - t0:.1f} s)", flush=True)
+        print(json.dumps(o), file=sys.stderr, flush=True)
+        if "--out" in argv:      # (written case by case: what was measured is kept if a later case is not reached)
+            with open(argv[argv.index("--out") + 1], "w") as f:
+                f.write("\n".join(lines) + "\n")
+    return 0
+
+
 def verdict(off, on):
     spread = max(off[2] - off[1], on[2] - on[1])
     diff = on[0] - off[0]
@@ -178,6 +282,8 @@ def main(argv):
         return trace()
     if "--dtype" in argv:
         F32 = {"float32": True, "float64": False}[argv[argv.index("--dtype") + 1]]
+    if "--ladder" in argv:
+        return ladder(argv)
     cases = CASES_F32 if F32 else CASES
     torch, hipldl, syn = setup()
     only = [int(x) for x in argv[argv.index("--only") + 1].split(",")] if "--only" in argv else list(range(len(cases)))
