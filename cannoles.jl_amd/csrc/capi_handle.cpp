@@ -128,6 +128,28 @@ int setup_subtrees(cnl_handle* h) {
     if ((rc = dalloc_batch(h, &h->d_lad_rho, 2))) return rc;
     h->ladder_rungs = o.subtree_ladder;
   }
+  // tuning subtree_wide / subtree_lds_panels: the per-stage table of the factorising forward launches
+  const int nst = (int)P.gstage_ptr.size() - 1;
+  h->gstage_fmax.assign(nst, 0);
+  h->gstage_lpan.assign(nst, 0);
+  std::vector<char> has_panel(nst, 0);   // a front with at least PANEL_W (16) pivots: the only fronts eliminate_blocked takes
+  for (const cnl::GTask& t : P.gtasks) {
+    h->gstage_fmax[t.stage] = std::max(h->gstage_fmax[t.stage], t.fmax);
+    for (int32_t f = t.f0; f < t.f1; f++) if (P.gfronts[f].npiv >= 16) has_panel[t.stage] = 1;
+  }
+  if (o.subtree_wide > 0 && h->cfg.tpp == 256) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) return fail(CNL_ERR_HIP, "hipGetDeviceProperties failed");
+    h->sub_wide = o.subtree_wide;
+    h->sub_cus = prop.multiProcessorCount;
+  }
+  if (o.subtree_lds_panels > 0 && h->cfg.blocked) {
+    const size_t cap = std::min<size_t>(cnl::max_lds_bytes(), (size_t)160 * 1024);
+    for (int s = 0; s < nst; s++) {
+      const size_t need = (size_t)(16 + 32 * (int64_t)h->gstage_fmax[s]) * h->esz();
+      if (h->gstage_fmax[s] <= o.subtree_lds_panels && has_panel[s] && need <= cap) h->gstage_lpan[s] = (int32_t)need;
+    }
+  }
   return CNL_OK;
 }
 
@@ -925,6 +947,12 @@ int ensure_kkt_rows(cnl_handle* h) {
   return CNL_OK;
 }
 
+cnl::SubtreeStageShape subtree_stage_shape(const cnl_handle* h, int s, int64_t batch) {
+  const int64_t tasks = h->gstage_ptr[s + 1] - h->gstage_ptr[s];
+  const bool wide = h->sub_wide > 0 && h->gstage_fmax[s] >= h->sub_wide && tasks * batch <= 2 * (int64_t)h->sub_cus;
+  return {wide ? 1024 : h->cfg.tpp, h->gstage_lpan[s] ? h->gstage_lpan[s] : (int32_t)(16 * h->esz())};
+}
+
 extern "C" {
 
 int cnl_create(cnl_handle** hout, int64_t N, int64_t nnz, const int64_t* rows1, const int64_t* cols1, int64_t nvar,
@@ -1146,6 +1174,13 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   if (h->cfg.blocked && !h->use_v2 && !dense_route && !on_band) cfg[5] |= (int64_t)1 << (h->f32 ? 48 : 47);   // newton_system / factorize run a blocked instance of the general kernel (bit 47: Float64, tuning general_blocked; bit 48: Float32, tuning float32_blocked)
   if (h->subtrees) cfg[5] |= (int64_t)1 << (h->f32 ? 50 : 49);   // the three calls run the general kernel's subtree instances stage by stage (bit 49: Float64, tuning general_subtrees; bit 50: Float32, tuning float32_subtrees; where the key acts)
   if (h->subtrees) cfg[5] |= (int64_t)(h->ladder_rungs & 127) << 51;   // ... with this many rungs of the rho ladder enqueued behind the first attempt of newton_system (bits 51 .. 57: tuning subtree_ladder, 0 .. 64, where the subtree key acts)
+  if (h->subtrees) {   // tuning subtree_wide / subtree_lds_panels: bit 58 — at least one stage factorises with 1024 threads at the created batch; bit 59 — at least one stage runs the LPAN instance
+    for (int st = 0; st + 1 < (int)h->gstage_ptr.size(); st++) {
+      const cnl::SubtreeStageShape sh = subtree_stage_shape(h, st, h->full_batch);
+      if (sh.tpp != h->cfg.tpp) cfg[5] |= (int64_t)1 << 58;
+      if (h->gstage_lpan[st]) cfg[5] |= (int64_t)1 << 59;
+    }
+  }
   if (h->lean && !dense_route) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->staged && h->use_v2 && !dense_route) {          // staged handles: how the stages run
     if (h->d_dep) cfg[5] |= (int64_t)1 << 42;            // dataflow counters present (one launch per phase where the rule allows)
@@ -1157,6 +1192,19 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
   cfg[5] |= (int64_t)(h->plan->opt.cgls_wide & 3) << 45;    // row f4: tuning cgls_wide (1: the wide instance above 1024 constraints, 2: always)
   cfg[6] = h->wpb2;
   cfg[7] = (int64_t)h->lds2;
+  return CNL_OK;
+}
+
+int cnl_subtree_stage_shape(const cnl_handle* h, int32_t* tpp, int32_t* lds_bytes, int64_t* nstages) {
+  if (!h || !nstages) return fail(CNL_ERR_ARG, "null argument");
+  if (!h->subtrees) return fail(CNL_ERR_ARG, "cnl_subtree_stage_shape: not a subtree handle (cnl_get_config bits 49 / 50)");
+  const int nst = (int)h->gstage_ptr.size() - 1;
+  *nstages = nst;
+  for (int s = 0; s < nst; s++) {
+    const cnl::SubtreeStageShape sh = subtree_stage_shape(h, s, h->batch);
+    if (tpp) tpp[s] = sh.tpp;
+    if (lds_bytes) lds_bytes[s] = sh.lds_bytes;
+  }
   return CNL_OK;
 }
 

@@ -88,6 +88,16 @@ int resolve_options(const cnl_options* in, cnl::Tuning& out) {
     return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_ladder needs general_subtrees = 1 (Float64 handles) or float32_subtrees = 1 (Float32 general handles): the rungs run on the subtree instances of the general kernel");
   if (out.subtree_ladder && out.float32_refine)
     return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_ladder does not go with float32_refine (no refined handle over a subtree factor)");
+  if (out.subtree_wide < 0 || out.subtree_wide > 4096)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_wide is the task fmax from which a stage of a subtree handle factorises with 1024 threads per workgroup, 1 .. 4096, or 0 (off)");
+  if (out.subtree_lds_panels != 0 && (out.subtree_lds_panels < 16 || out.subtree_lds_panels > 4096))
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_lds_panels is the task fmax up to which a stage of a blocked subtree handle eliminates its dependent pivot panels in LDS, 16 .. 4096, or 0 (off)");
+  if ((out.subtree_wide || out.subtree_lds_panels) && !out.general_subtrees && !out.float32_subtrees)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_wide and subtree_lds_panels need general_subtrees = 1 (Float64 handles) or float32_subtrees = 1 (Float32 general handles): they shape the stage launches of the subtree instances");
+  if ((out.subtree_wide || out.subtree_lds_panels) && out.float32_refine)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_wide and subtree_lds_panels do not go with float32_refine (no refined handle over a subtree factor)");
+  if (out.subtree_lds_panels && !out.general_blocked && !out.float32_blocked)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_lds_panels needs general_blocked = 1 (Float64 handles) or float32_blocked = 1 (Float32 general handles): the pivot panels are those of the blocked instances");
   if (out.cgls_wide < 0 || out.cgls_wide > 2)
     return fail(CNL_ERR_ARG, "cnl_options.tuning: cgls_wide is 0 (the LDS instance, ncon <= 1024), 1 (the wide instance where ncon > 1024) or 2 (the wide instance always)");
   return CNL_OK;
@@ -300,6 +310,13 @@ int check_subtree_ladder(const cnl::Tuning& o, bool f32, const char* fn) {
   if (o.subtree_ladder && !(f32 ? o.float32_subtrees : o.general_subtrees))
     return fail(CNL_ERR_ARG, std::string(fn) + (f32 ? ": tuning subtree_ladder needs float32_subtrees = 1 at a Float32 creator (the rungs run on the float subtree instances)"
                                                     : ": tuning subtree_ladder needs general_subtrees = 1 at a Float64 creator (the rungs run on the Float64 subtree instances)"));
+  // tuning subtree_wide, subtree_lds_panels: the same rule, and the panels need the creator's own blocked key
+  if ((o.subtree_wide || o.subtree_lds_panels) && !(f32 ? o.float32_subtrees : o.general_subtrees))
+    return fail(CNL_ERR_ARG, std::string(fn) + (f32 ? ": tuning subtree_wide / subtree_lds_panels need float32_subtrees = 1 at a Float32 creator (they shape the stage launches of the float subtree instances)"
+                                                    : ": tuning subtree_wide / subtree_lds_panels need general_subtrees = 1 at a Float64 creator (they shape the stage launches of the Float64 subtree instances)"));
+  if (o.subtree_lds_panels && !(f32 ? o.float32_blocked : o.general_blocked))
+    return fail(CNL_ERR_ARG, std::string(fn) + (f32 ? ": tuning subtree_lds_panels needs float32_blocked = 1 at a Float32 creator (the pivot panels are those of the float blocked instances)"
+                                                    : ": tuning subtree_lds_panels needs general_blocked = 1 at a Float64 creator (the pivot panels are those of the Float64 blocked instances)"));
   return CNL_OK;
 }
 
@@ -464,7 +481,9 @@ const char* cnl_last_error(void) { return g_err.c_str(); }
 //        no new symbol
 // 0.5.8: tuning subtree_ladder (subtree handles of either element type climb R rungs of the rho ladder stage by stage), cnl_get_config
 //        bits 51 .. 57, no new symbol
-int32_t cnl_version(void) { return 508; }
+// 0.5.9: tuning subtree_wide (1024-thread factorising stages on 256-thread subtree handles, the float instances among them) and
+//        subtree_lds_panels (dependent pivot panels of blocked subtree handles in LDS), cnl_get_config bits 58 / 59, cnl_subtree_stage_shape
+int32_t cnl_version(void) { return 509; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62

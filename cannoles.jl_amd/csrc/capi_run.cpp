@@ -151,10 +151,14 @@ int launch_subtrees(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
   if (solve) a.success = h->d_blk_ok;
   if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
   hipError_t e = hipSuccess;
+  // (tuning subtree_wide / subtree_lds_panels, DESIGN section 3.4: a factorising forward launch takes its stage's shape at this launch's
+  //  batch; the vector sweeps of solve_ldl! and the backward stages keep the handle's)
   auto stage = [&](int s, int phase) {
     a.phase = phase; a.task0 = h->gstage_ptr[s]; a.ntasks = h->gstage_ptr[s + 1] - h->gstage_ptr[s];
     g_launches[2]++;
-    return cnl::launch_newton_subtrees(h->dp, h->cfg, a, stream, h->f32);
+    if (phase != 0 || solve) return cnl::launch_newton_subtrees(h->dp, h->cfg, a, stream, h->f32);
+    const cnl::SubtreeStageShape sh = subtree_stage_shape(h, s, a.batch);
+    return cnl::launch_newton_subtrees(h->dp, h->cfg, a, stream, h->f32, &sh);
   };
   const int rungs = newton ? h->ladder_rungs : 0;
   const cnl::LadderState lad{h->d_lad_done, h->d_lad_rho, rungs};
@@ -168,7 +172,8 @@ int launch_subtrees(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
     for (int s = 0; s < nst && e == hipSuccess; s++) {
       a.phase = 0; a.task0 = h->gstage_ptr[s]; a.ntasks = h->gstage_ptr[s + 1] - h->gstage_ptr[s];
       g_launches[2]++;
-      e = cnl::launch_subtree_ladder(h->dp, h->cfg, a, lad, stream, h->f32);
+      const cnl::SubtreeStageShape sh = subtree_stage_shape(h, s, a.batch);
+      e = cnl::launch_subtree_ladder(h->dp, h->cfg, a, lad, stream, h->f32, &sh);
     }
     if (e != hipSuccess) break;
     g_launches[2]++;

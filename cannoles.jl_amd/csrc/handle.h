@@ -131,6 +131,14 @@ struct cnl_handle {
   int ladder_rungs = 0;
   int32_t* d_lad_done = nullptr;
   void* d_lad_rho = nullptr;
+  // tuning subtree_wide / subtree_lds_panels on such a handle (cnl_get_config bits 58 / 59): the per-stage table of the
+  // factorising forward launches, built once by setup_subtrees and read by subtree_stage_shape() — which the launch loop and
+  // cnl_subtree_stage_shape both call.  gstage_fmax[s] = F_s, the largest GTask::fmax of stage s; sub_wide = W where the key acts (the
+  // handle has 256 threads per workgroup), else 0; sub_cus the device's CU count; gstage_lpan[s] = the dynamic LDS bytes of stage s's LPAN
+  // launch, 0 where the stage runs without LDS panels (every stage of a handle without the key, or one that is not blocked).
+  int32_t sub_wide = 0;
+  int32_t sub_cus = 0;
+  std::vector<int32_t> gstage_fmax, gstage_lpan;
   // Float32 general handles on a condensed plan: the resident condense kernel serves the handle (kernels.h: DevCondEll) — where the
   // tiled kernel's chunks degenerate (dense Jacobians) and [vals | rhs] of a problem fits LDS; tuning float32_condense = 2: never
   bool cond_resident = false;
@@ -367,11 +375,15 @@ int check_f32_options(const cnl::Tuning& o, const char* fn);
 // tuning general_blocked or general_subtrees on a creator of Float32 state (cnl_create_f32*, the inner handle of float32_refine): CNL_ERR_ARG
 int check_no_general_blocked(const cnl::Tuning& o, const char* fn);
 // tuning subtree_ladder at a creator whose own subtree key (f32: float32_subtrees, else general_subtrees) is off: CNL_ERR_ARG
+// (and tuning subtree_wide / subtree_lds_panels at such a creator, or subtree_lds_panels without the creator's own blocked key)
 int check_subtree_ladder(const cnl::Tuning& o, bool f32, const char* fn);
 
 // ---- capi_handle.cpp ----
 int ensure_kkt_rows(cnl_handle* h);   // h->dkkt on the device
 int create_from_plan(cnl_handle** hout, cnl_plan* plan, const int64_t* rows1, const int64_t* cols1, int64_t batch, int device);
+// a subtree handle: the shape of the factorising forward launch of stage s at a launch of `batch` problems —
+// 1024 threads where tuning subtree_wide acts, F_s >= W and tasks_s x batch <= 2 x CUs; the LPAN bytes where the stage has them
+cnl::SubtreeStageShape subtree_stage_shape(const cnl_handle* h, int s, int64_t batch);
 
 // ---- capi_run.cpp ----
 // what holds for ONE call of run() and is no state of the handle

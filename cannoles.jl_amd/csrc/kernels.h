@@ -218,7 +218,16 @@ bool newton_blocked_has(int tpp, int ppb, bool f32 = false);   // is there a blo
 // a.success[b] == 0 skipped; a.phase 2: the climbers — one workgroup per problem runs the whole sequential newton_system over the
 // a.ntasks_all tasks, and with a.skip_done = 1 (read by these instances alone among the general kernel's) a problem whose
 // a.success[b] is already 1 leaves at once.  MODE_SOLVE skips problems whose a.success[b] is 0 in both phases.
-hipError_t launch_newton_subtrees(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream, bool f32);
+// The shape of one factorising forward launch of a stage (a.phase 0, MODE_NEWTON / MODE_FACTOR, and the rungs of the ladder; DESIGN
+// section 3.4): threads per workgroup — the handle's, or 1024 on a 256-thread handle (tuning subtree_wide) — and dynamic LDS bytes — the
+// 16 elements of psum, or (16 + 32 F_s) elements where the stage eliminates its dependent pivot panels in LDS (tuning subtree_lds_panels,
+// the LPAN instances of a blocked handle).  nullptr everywhere below: the handle's shape.
+struct SubtreeStageShape {
+  int32_t tpp;
+  int32_t lds_bytes;
+};
+hipError_t launch_newton_subtrees(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream, bool f32,
+                                  const SubtreeStageShape* shape = nullptr);
 bool newton_subtrees_has(int tpp, int ppb, bool f32);   // is there a subtree instance of the element type for this configuration?
 // behind the last forward stage of a factorising subtree call: success (and a.npos / a.nzero where given) from the slots of gcnt plus
 // a.extra_pos / a.extra_zer; MODE_NEWTON: rho = 0, nfact = 1 of the problems that succeeded
@@ -234,7 +243,8 @@ struct LadderState {
 // a.phase 0: forward of the tasks [a.task0, a.task0 + a.ntasks) of one stage at every climbing problem's rho (rho_override), one workgroup
 // per (task, problem), pivot counts into the slots of a.gcnt; a.phase 2: the climbers of the problems still climbing after st.rungs rungs,
 // resumed behind them.  MODE_NEWTON only.  Problems that are done are left alone by both.
-hipError_t launch_subtree_ladder(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, const LadderState& st, hipStream_t stream, bool f32);
+hipError_t launch_subtree_ladder(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, const LadderState& st, hipStream_t stream, bool f32,
+                                 const SubtreeStageShape* shape = nullptr);
 // the first decide of such a call (in the place of launch_subtree_decide): its outputs, st.done and rho_1 of every problem
 hipError_t launch_subtree_ladder_first(const LaunchArgs& a, const LadderState& st, const int* gcnt, int ntasks, int nvar, hipStream_t stream, bool f32);
 // behind the stages of rung k = 1 .. R: inertia rule, nfact = k + 1, success / exhaustion / the next rho of every problem that is not done

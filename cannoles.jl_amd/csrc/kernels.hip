@@ -124,8 +124,10 @@ struct PanelMma<float> {
 // update_block), the accumulator loaded from F and stored back by the result map of the instruction (PanelMma::row).
 // Rows and columns beyond lim and panel slots beyond kp enter as zeros (selected, not multiplied: the slots may hold
 // anything); a diagonal tile computes the whole tile and stores b <= a.  The trip count depends on the wavefront alone.
-template <int TPP, class T>
-__device__ __forceinline__ void panel_trailing_update(T* F, const T* Wp, int ws, int p0, int kp, int lim, int tid) {
+// LPAN (tuning subtree_lds_panels): the scaled rows are read from Lr, the copy of the piece F[tri_i(p0) ..) that eliminate_blocked keeps in
+// LDS (Lr[0] is F[tri_i(p0)]), and Wp is in LDS too; the accumulator tiles are F's as ever.
+template <int TPP, class T, bool LPAN = false>
+__device__ __forceinline__ void panel_trailing_update(T* F, const T* Wp, int ws, int p0, int kp, int lim, int tid, const T* Lr = nullptr) {
   typedef PanelMma<T> M;
   const int lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, lg = lane >> 4;
@@ -138,7 +140,8 @@ __device__ __forceinline__ void panel_trailing_update(T* F, const T* Wp, int ws,
 #pragma unroll
     for (int s = 0; s < 4; s++) {
       const int k = 4 * s + lg;
-      aop[s] = (k < kp && ar < lim) ? -F[tri_i(p0 + k) + ar] : T(0);
+      if constexpr (LPAN) aop[s] = (k < kp && ar < lim) ? -Lr[tri_i(p0 + k) - tri_i(p0) + ar] : T(0);
+      else aop[s] = (k < kp && ar < lim) ? -F[tri_i(p0 + k) + ar] : T(0);
       bop[s] = (k < kp && bc < lim) ? Wp[k * ws + bc] : T(0);
     }
     typename M::acc_t acc, acc2 = typename M::acc_t{T(0), T(0), T(0), T(0)};
@@ -165,9 +168,14 @@ __device__ __forceinline__ void panel_trailing_update(T* F, const T* Wp, int ws,
 // pivots one by one — pivot read after every earlier pivot's update has reached it, counted against eig_tol, row kept unscaled in
 // W, scaled in place, rank-1 update of the rows of the panel still to come (a contiguous piece of the packed triangle) — and then
 // updates everything below it at once.
-template <int TPP, bool LDSW, class T>
+// LPAN (tuning subtree_lds_panels; the work area is global): a dependent panel [p0, p1) runs its pivot loop on a copy
+// of its rows in LDS — the contiguous piece F[tri_i(p0) .. tri_i(p1)), at most PANEL_W rows of at most P.fmax elements, at lds; the
+// unscaled rows at lds + PANEL_W * P.fmax, PANEL_W rows of stride P.fmax — with the statements of the loop below in their order, hands
+// both areas to the trailing update and writes the piece back (the trailing update writes rows below p0 only).  The launch sized the
+// areas for the stage's largest P.fmax.  Independent panels run as ever, on F and Wp.
+template <int TPP, bool LDSW, class T, bool LPAN = false>
 __device__ __forceinline__ void eliminate_blocked(const DevPlan& P, T* F, T* Wp, int f, int nupd, int idep, int tid, T eig_tol,
-                                                  int& npos, int& nzer) {
+                                                  int& npos, int& nzer, T* lds = nullptr) {
   const int ws = P.fmax;
   int p1 = f;
   while (p1 > nupd + 1) {
@@ -190,6 +198,42 @@ __device__ __forceinline__ void eliminate_blocked(const DevPlan& P, T* F, T* Wp,
         }
       }
       psync<TPP, LDSW>();
+    } else if constexpr (LPAN) {
+      T* const Ls = lds;
+      T* const Wl = lds + PANEL_W * ws;
+      const int t0 = tri_i(p0), tlen = tri_i(p1) - t0;
+      for (int t = tid; t < tlen; t += TPP) Ls[t] = F[t0 + t];
+      psync<TPP, LDSW>();
+      for (int k = kp - 1; k >= 0; k--) {
+        const int i = p0 + k;
+        T* rowi = Ls + (tri_i(i) - t0);
+        T* wk = Wl + k * ws;
+        const T dpiv = rowi[i];
+        npos += dpiv > eig_tol;
+        nzer += abs_of(dpiv) <= eig_tol;
+        for (int j = tid; j < i; j += TPP) {
+          const T w = rowi[j];
+          wk[j] = w;
+          rowi[j] = w / dpiv;
+        }
+        psync<TPP, LDSW>();
+        const int t1 = tri_i(i);   // rows p0 .. i - 1 of the packed triangle
+        if (t0 + tid < t1) {
+          int a, b;
+          tri_decode(t0 + tid, a, b);
+          for (int t = t0 + tid; t < t1; t += TPP) {
+            Ls[t - t0] -= rowi[a] * wk[b];
+            b += TPP;
+            while (b > a) { b -= a + 1; a++; }
+          }
+        }
+        psync<TPP, LDSW>();
+      }
+      for (int t = tid; t < tlen; t += TPP) F[t0 + t] = Ls[t];
+      panel_trailing_update<TPP, T, true>(F, Wl, ws, p0, kp, lim, tid, Ls);
+      psync<TPP, LDSW>();
+      p1 = p0;
+      continue;
     } else {
       for (int k = kp - 1; k >= 0; k--) {
         const int i = p0 + k;
@@ -227,7 +271,8 @@ __device__ __forceinline__ void eliminate_blocked(const DevPlan& P, T* F, T* Wp,
 // forward pass over one front: assemble, extend-add, eliminate the pivots,
 // store the L panel, leave the update matrix for the parent.
 // BLK (TPP a multiple of 64): fronts with at least PANEL_W pivots are eliminated by eliminate_blocked
-template <int TPP, bool LDSW, bool WITH_K, class T, bool BLK = false>
+// LPAN (only with BLK, work area global): ... whose dependent panels run in the LDS areas behind the 16 elements of c.red
+template <int TPP, bool LDSW, bool WITH_K, class T, bool BLK = false, bool LPAN = false>
 __device__ __forceinline__ void front_forward(const DevPlan& P, const FrontHdr& H, const ProblemCtx<T>& c, int tid,
                                               bool rho_override, T rho, T eig_tol, int& npos, int& nzer) {
   const int nupd = H.nupd, npiv = H.npiv;
@@ -294,7 +339,11 @@ __device__ __forceinline__ void front_forward(const DevPlan& P, const FrontHdr& 
     bool blocked = false;
     if constexpr (BLK) {
       blocked = npiv >= PANEL_W;
-      if (blocked) eliminate_blocked<TPP, LDSW>(P, F, wv0, f, nupd, idep, tid, eig_tol, npos, nzer);
+      if constexpr (LPAN) {
+        if (blocked) eliminate_blocked<TPP, LDSW, T, true>(P, F, wv0, f, nupd, idep, tid, eig_tol, npos, nzer, c.red + 16);
+      } else {
+        if (blocked) eliminate_blocked<TPP, LDSW>(P, F, wv0, f, nupd, idep, tid, eig_tol, npos, nzer);
+      }
     }
     for (int i = blocked ? nupd : f - 1; i > nupd; i--) {
       const int ulim = i >= idep ? idep : i;
@@ -454,7 +503,7 @@ __device__ __forceinline__ void sub_backward_all(DevPlan& P, const int32_t* task
   }
 }
 
-template <int TPP, class T, bool BLK>
+template <int TPP, class T, bool BLK, bool LPAN = false>
 __device__ __forceinline__ void newton_subtrees(DevPlan& P, const LaunchArgs& A, T* smem) {
   T* const a_vals = static_cast<T*>(A.vals);
   const T* const a_rhs = static_cast<const T*>(A.rhs);
@@ -491,7 +540,7 @@ __device__ __forceinline__ void newton_subtrees(DevPlan& P, const LaunchArgs& A,
     }
     if (A.mode == MODE_FACTOR) c.rhs = nullptr;
     int np = 0, nz = 0;
-    for (int s = f0; s < f1; s++) front_forward<TPP, false, true, T, BLK>(P, P.fronts[s], c, tid, false, T(0), eig_tol, np, nz);
+    for (int s = f0; s < f1; s++) front_forward<TPP, false, true, T, BLK, LPAN>(P, P.fronts[s], c, tid, false, T(0), eig_tol, np, nz);
     if (tid == 0) {
       int* slot = gcnt + 2 * ((long long)task * A.batch + b);
       slot[0] = np; slot[1] = nz;
@@ -565,8 +614,12 @@ __global__ void __launch_bounds__(256) subtree_decide_kernel(const int* gcnt, in
 // SUB: the subtree instances (PPB = 1, global work area, BLK either way; tuning general_subtrees: double, TPP 256 or 1024; tuning
 // float32_subtrees: float, TPP 256; launch_newton_subtrees) — newton_subtrees above; they alone read A.tasks, A.task0, A.ntasks,
 // A.ntasks_all, A.phase, A.gcnt and A.skip_done here.  Every other instance is the code it was.
-template <int TPP, int PPB, bool LDSW, class T, bool BLK = false, bool SUB = false>
+// LPAN: the subtree instances whose factorising forward launch (A.phase 0, MODE_NEWTON / MODE_FACTOR) eliminates dependent pivot panels in
+// LDS (tuning subtree_lds_panels; only with BLK and SUB, double or float, TPP 256 or 1024; launch_newton_subtrees, which sizes the dynamic
+// LDS per stage); launched for such launches alone.  The default argument keeps every other instance the code it was.
+template <int TPP, int PPB, bool LDSW, class T, bool BLK = false, bool SUB = false, bool LPAN = false>
 __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, const LaunchArgs Ain) {
+  static_assert(!LPAN || (BLK && SUB), "LDS pivot panels: blocked subtree instances only");
   if constexpr (SUB) {
     static_assert(PPB == 1 && !LDSW && TPP >= 256, "subtree instances: one problem per workgroup, work area in global scratch");
     DevPlan P = Pin;
@@ -579,7 +632,7 @@ __global__ void __launch_bounds__(TPP* PPB) newton_kernel(const DevPlan Pin, con
     A.nfact = as_global(Ain.nfact); A.success = as_global(Ain.success);
     A.extra_pos = as_global(Ain.extra_pos); A.extra_zer = as_global(Ain.extra_zer);
     extern __shared__ double smem_sub[];
-    newton_subtrees<TPP, T, BLK>(P, A, reinterpret_cast<T*>(smem_sub));
+    newton_subtrees<TPP, T, BLK, LPAN>(P, A, reinterpret_cast<T*>(smem_sub));
     return;
   }
   DevPlan P = Pin;
@@ -692,7 +745,8 @@ static hipError_t launch_t(const DevPlan& P, const KernelConfig& cfg, const Laun
 }
 
 // the configurations with a blocked instance (tuning general_blocked; float32_blocked for f32): whole workgroups of several
-// wavefronts on one problem; in float the 256-thread instances alone (there is no 1024-thread float instance of any kind)
+// wavefronts on one problem; in float the 256-thread instances alone (the only 1024-thread float instances are subtree instances that
+// tuning subtree_wide selects per stage, for factorising forward launches: no handle is configured with them)
 bool newton_blocked_has(int tpp, int ppb, bool f32) { return ppb == 1 && (tpp == 256 || (tpp == 1024 && !f32)); }
 
 hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream) {
@@ -717,29 +771,59 @@ hipError_t launch_newton(const DevPlan& P, const KernelConfig& cfg, const Launch
 }
 
 // the configurations with subtree instances (tuning general_subtrees; float32_subtrees for f32): one problem per workgroup of 256 or
-// 1024 threads, in float of 256 alone (there is no 1024-thread float instance of any kind)
+// 1024 threads, in float of 256 alone (1024-thread float subtree and ladder instances exist, but per stage only: tuning subtree_wide
+// launches them for the factorising forward launch of a stage of a 256-thread handle, launch_newton_subtrees' `tpp` argument)
 bool newton_subtrees_has(int tpp, int ppb, bool f32) { return ppb == 1 && (tpp == 256 || (tpp == 1024 && !f32)); }
 
 // One launch of a subtree instance (newton_subtrees): a.phase 0 / 1 — the a.ntasks tasks of one stage from a.task0 on, one workgroup
 // per (task, problem); a.phase 2 — the climbers, one workgroup per problem.  P.fronts is the task-region front table, P.work_doubles
 // the elements of all regions of a problem, a.tasks the device task records; the work area is a.scratch whatever cfg.lds_work says.
 // f32: the element arrays of a and the work area are float (a Float32 general handle, tuning float32_subtrees).
-hipError_t launch_newton_subtrees(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream, bool f32) {
+// shape (kernels.h: SubtreeStageShape), for a factorising forward launch alone (a.phase 0, not MODE_SOLVE): tpp 1024 on a
+// 256-thread handle runs the stage on the 1024-thread instance (tuning subtree_wide: in float the only way to one), and lds_bytes above the
+// 16 elements of psum runs the LPAN instance of a blocked handle with that much dynamic LDS (tuning subtree_lds_panels).
+static bool subtree_shape_ok(const KernelConfig& cfg, const LaunchArgs& a, const SubtreeStageShape& shape, size_t red_bytes) {
+  const bool plain = shape.tpp == cfg.tpp && shape.lds_bytes == (int)red_bytes;
+  if (plain) return true;
+  if (a.phase != 0 || a.mode == MODE_SOLVE) return false;
+  if (shape.tpp != cfg.tpp && !(cfg.tpp == 256 && shape.tpp == 1024)) return false;
+  if (shape.lds_bytes != (int)red_bytes && (!cfg.blocked || shape.lds_bytes < (int)red_bytes)) return false;
+  return true;
+}
+
+template <class K, class... Args>
+static hipError_t launch_subtree_instance(K kfn, long long grid, int tpp, size_t lds, hipStream_t stream, const Args&... args) {
+  if (lds > 64 * 1024) {   // (LPAN areas of a large stage: the limit has to be raised, as launch_t does)
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)lds));
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(tpp), lds, stream, args...);
+  return hipGetLastError();
+}
+
+hipError_t launch_newton_subtrees(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream, bool f32,
+                                  const SubtreeStageShape* shape) {
   if (!newton_subtrees_has(cfg.tpp, cfg.ppb, f32) || !a.tasks || !a.scratch || a.batch < 1) return hipErrorInvalidConfiguration;
   const long long grid = a.phase == 2 ? (long long)a.batch : (long long)a.batch * a.ntasks;
   if (grid < 1 || grid > 0x7fffffffLL) return hipErrorInvalidConfiguration;
-  const size_t lds = 16 * (f32 ? sizeof(float) : sizeof(double));   // the cross-wave sums of psum
+  const size_t red = 16 * (f32 ? sizeof(float) : sizeof(double));   // the cross-wave sums of psum
+  const SubtreeStageShape sh = shape ? *shape : SubtreeStageShape{cfg.tpp, (int32_t)red};
+  if (!subtree_shape_ok(cfg, a, sh, red)) return hipErrorInvalidConfiguration;
+  const size_t lds = (size_t)sh.lds_bytes;
+  const bool lpan = lds > red;
 #define CNL_CASE(T, E, B) \
-  if (cfg.tpp == T && (cfg.blocked != 0) == B) { \
-    hipLaunchKernelGGL((newton_kernel<T, 1, false, E, B, true>), dim3((unsigned)grid), dim3(T), lds, stream, P, a); \
-    return hipGetLastError(); \
-  }
+  if (sh.tpp == T && (cfg.blocked != 0) == B && !lpan) return launch_subtree_instance(newton_kernel<T, 1, false, E, B, true>, grid, T, lds, stream, P, a);
+#define CNL_LPAN(T, E) \
+  if (sh.tpp == T && lpan) return launch_subtree_instance(newton_kernel<T, 1, false, E, true, true, true>, grid, T, lds, stream, P, a);
   if (f32) {
-    CNL_CASE(256, float, false) CNL_CASE(256, float, true)
+    CNL_CASE(256, float, false) CNL_CASE(256, float, true) CNL_CASE(1024, float, false) CNL_CASE(1024, float, true)
+    CNL_LPAN(256, float) CNL_LPAN(1024, float)
     return hipErrorInvalidConfiguration;
   }
   CNL_CASE(256, double, false) CNL_CASE(256, double, true) CNL_CASE(1024, double, false) CNL_CASE(1024, double, true)
+  CNL_LPAN(256, double) CNL_LPAN(1024, double)
 #undef CNL_CASE
+#undef CNL_LPAN
   return hipErrorInvalidConfiguration;
 }
 
@@ -766,9 +850,11 @@ hipError_t launch_subtree_decide(const LaunchArgs& a, const int* gcnt, int ntask
 // a workgroup whose problem is done leaves before any barrier.  CLIMB = true (A.phase 2): the climbers, workgroup = problem, for a problem still
 // climbing after R rungs: the reference's while loop (src/CaNNOLeS.jl:1033-1043) entered at rho_{R+1}, which the decide of rung R
 // formed and found <= rhomax, with nfact = R + 1 behind it; the backward sweep on success; all outputs.
-template <int TPP, class T, bool BLK, bool CLIMB>
+// LPAN (only with BLK, never with CLIMB): the rung instances with dependent pivot panels in LDS, as newton_kernel's.
+template <int TPP, class T, bool BLK, bool CLIMB, bool LPAN = false>
 __global__ void __launch_bounds__(TPP) subtree_ladder_kernel(const DevPlan Pin, const LaunchArgs Ain, const LadderState Sin) {
   static_assert(TPP >= 256, "subtree instances: one problem per workgroup of 256 or 1024 threads");
+  static_assert(!LPAN || (BLK && !CLIMB), "LDS pivot panels: the blocked rung instances only");
   DevPlan P = Pin;
   P.fronts = as_global(Pin.fronts); P.seg_ptr = as_global(Pin.seg_ptr); P.asm_pos = as_global(Pin.asm_pos);
   P.asm_src = as_global(Pin.asm_src); P.child_idx = as_global(Pin.child_idx); P.rel_idx = as_global(Pin.rel_idx);
@@ -803,7 +889,7 @@ __global__ void __launch_bounds__(TPP) subtree_ladder_kernel(const DevPlan Pin, 
     int f0, f1;
     sub_enter_task(P, tasks, task, f0, f1);
     int np = 0, nz = 0;
-    for (int s = f0; s < f1; s++) front_forward<TPP, false, true, T, BLK>(P, P.fronts[s], c, tid, true, rho_next, eig_tol, np, nz);
+    for (int s = f0; s < f1; s++) front_forward<TPP, false, true, T, BLK, LPAN>(P, P.fronts[s], c, tid, true, rho_next, eig_tol, np, nz);
     if (tid == 0) {
       int* slot = as_global(A.gcnt) + 2 * ((long long)task * A.batch + b);
       slot[0] = np; slot[1] = nz;
@@ -911,25 +997,41 @@ __global__ void __launch_bounds__(256) subtree_ladder_commit_kernel(T* vals, lon
   for (int i = threadIdx.x; i < nvar; i += 256) vt[i] = wrote;
 }
 
-hipError_t launch_subtree_ladder(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, const LadderState& st, hipStream_t stream, bool f32) {
+// shape: as launch_newton_subtrees' — the rungs (a.phase 0) are factorising forward launches, the climbers (a.phase 2) keep the handle's shape
+hipError_t launch_subtree_ladder(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, const LadderState& st, hipStream_t stream, bool f32,
+                                 const SubtreeStageShape* shape) {
   if (!newton_subtrees_has(cfg.tpp, cfg.ppb, f32) || !a.tasks || !a.scratch || !a.vals || !st.done || !st.rho || a.batch < 1 || a.mode != MODE_NEWTON ||
       (a.phase != 0 && a.phase != 2))
     return hipErrorInvalidConfiguration;
   const long long grid = a.phase == 2 ? (long long)a.batch : (long long)a.batch * a.ntasks;
   if (grid < 1 || grid > 0x7fffffffLL) return hipErrorInvalidConfiguration;
-  const size_t lds = 16 * (f32 ? sizeof(float) : sizeof(double));   // the cross-wave sums of psum
+  const size_t red = 16 * (f32 ? sizeof(float) : sizeof(double));   // the cross-wave sums of psum
+  const SubtreeStageShape sh = shape ? *shape : SubtreeStageShape{cfg.tpp, (int32_t)red};
+  if (!subtree_shape_ok(cfg, a, sh, red)) return hipErrorInvalidConfiguration;
+  const size_t lds = (size_t)sh.lds_bytes;
+  const bool lpan = lds > red;
 #define CNL_CASE(T, E, B) \
-  if (cfg.tpp == T && (cfg.blocked != 0) == B) { \
-    if (a.phase == 2) hipLaunchKernelGGL((subtree_ladder_kernel<T, E, B, true>), dim3((unsigned)grid), dim3(T), lds, stream, P, a, st); \
-    else hipLaunchKernelGGL((subtree_ladder_kernel<T, E, B, false>), dim3((unsigned)grid), dim3(T), lds, stream, P, a, st); \
-    return hipGetLastError(); \
+  if (sh.tpp == T && (cfg.blocked != 0) == B && !lpan) { \
+    if (a.phase == 2) return launch_subtree_instance(subtree_ladder_kernel<T, E, B, true>, grid, T, lds, stream, P, a, st); \
+    return launch_subtree_instance(subtree_ladder_kernel<T, E, B, false>, grid, T, lds, stream, P, a, st); \
   }
+#define CNL_LPAN(T, E) \
+  if (sh.tpp == T && lpan) return launch_subtree_instance(subtree_ladder_kernel<T, E, true, false, true>, grid, T, lds, stream, P, a, st);
   if (f32) {
     CNL_CASE(256, float, false) CNL_CASE(256, float, true)
+    if (a.phase == 0) {   // (no 1024-thread float climbers: a stage alone is ever wide)
+      if (sh.tpp == 1024 && !lpan) {
+        if (cfg.blocked) return launch_subtree_instance(subtree_ladder_kernel<1024, float, true, false>, grid, 1024, lds, stream, P, a, st);
+        return launch_subtree_instance(subtree_ladder_kernel<1024, float, false, false>, grid, 1024, lds, stream, P, a, st);
+      }
+      CNL_LPAN(256, float) CNL_LPAN(1024, float)
+    }
     return hipErrorInvalidConfiguration;
   }
   CNL_CASE(256, double, false) CNL_CASE(256, double, true) CNL_CASE(1024, double, false) CNL_CASE(1024, double, true)
+  CNL_LPAN(256, double) CNL_LPAN(1024, double)
 #undef CNL_CASE
+#undef CNL_LPAN
   return hipErrorInvalidConfiguration;
 }
 

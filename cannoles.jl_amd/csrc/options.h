@@ -75,6 +75,8 @@ namespace cnl {
   X(general_subtrees, 0)     /* general kernel, Float64: 1 = the elimination tree is cut into tasks (bottom subtrees of at most task_cap fronts, default 8; every front above on its own) and the three calls of the plugin surface run stage by stage, one workgroup per (problem, task), dependencies by launch order alone; acts where the launch is the general kernel with one problem per workgroup of 256 or 1024 threads, the first stage has two tasks or more and batch x gwork x 8 <= 8e9 bytes — every other handle is the one without the key; selects no route, combines with general_blocked; Float64 handles only: cnl_create_f32* and float32_refine refuse it */ \
   X(float32_subtrees, 0)     /* cnl_create_f32: general_subtrees for a Float32 general handle: the forced analysis cuts the tree (task_cap as there) and, where the newton_system / factorize launch is the general kernel in float with one problem per workgroup of 256 threads, the first stage has two tasks or more and batch x gwork x 4 <= 8e9 bytes, the three calls run stage by stage on the float subtree instances; selects no route: every other handle is the one without the key; combines with float32_blocked; 0 or 1; only with float32_general, not with float32_refine; a Float64 creator without float32_refine reads nothing of it, as of float32_condense */ \
   X(subtree_ladder, 0)       /* subtree handles of either element type: R = 0 .. 64 rungs of the rho ladder are enqueued behind the first attempt of newton_system, each stage by stage like it, one rung-decide launch behind each; problems still climbing after R rungs resume in the climbers' launch; (R + 2) S + R + 3 launches; valid only with general_subtrees = 1 (Float64 creators) or float32_subtrees = 1 (Float32 creators), never with float32_refine; selects no route and changes no plan: it acts where the subtree key acts */ \
+  X(subtree_wide, 0)         /* subtree handles of either element type with 256 threads per workgroup: W = 1 .. 4096: the factorising forward launch of a stage (newton_system, factorize, the rungs of subtree_ladder) runs with 1024 threads per workgroup where the stage's largest task fmax F_s >= W and tasks_s x batch <= 2 x the device's CU count; every other launch keeps 256 (backward stages, solve_ldl!, climbers, decide and commit kernels); in float the only way to a 1024-thread instance; the factor and every output are bit-equal to W = 0; 0: off; valid only with general_subtrees = 1 (Float64 creators) or float32_subtrees = 1 (Float32 creators), never with float32_refine; selects no route and changes no plan */ \
+  X(subtree_lds_panels, 0)   /* blocked subtree handles of either element type: M = 16 .. 4096: the factorising forward launch of a stage with F_s <= M, a front of at least 16 pivots and (16 + 32 F_s) elements within the device's LDS per workgroup (at most 160 KB) runs the LPAN instance, which eliminates the dependent pivot panels of its fronts in LDS (the panel's rows and their unscaled copies) with the statements of the global-memory loop in their order: bit-equal factor; 0: off; valid only with the creator's subtree key and its blocked key (general_blocked, float32_blocked), never with float32_refine; combines with subtree_wide; selects no route and changes no plan */ \
   X(cgls_wide, 0)          /* row f4: 0 the ncon-vectors in LDS, more than 1024 constraints are CNL_ERR_DIM; 1 in the global workspace where ncon > 1024; 2 there always */
 
 struct Tuning {

@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "cnl_outer_begin_ex_f32_dev", "cnl_outer_trial_done_ex_f32_dev", "cnl_outer_ls_test_ex_f32_dev", "cnl_outer_end_ex_f32_dev",
     "cnl_outer_hess_mask_f32_dev",
     "cnl_kkt_residual_dev", "cnl_get_refine_norms",
+    "cnl_subtree_stage_shape",
 ]
 
 # status codes of the lockstep loop's `status` array (include/cannoles_hip.h, row f3); 7 is set by the caller, never by a kernel
@@ -170,7 +171,16 @@ def Options(**kw):
     the subtree key acts, newton_system enqueues R rungs of the rho ladder behind the first attempt, each stage by stage with a decide
     launch behind it — (R + 2) S + R + 3 launches for S stages —, and the climbers' launch resumes only the problems still climbing after
     R rungs.  Every output is that of R = 0, bit for bit.  It selects no route and changes no plan; config["subtree_ladder"] is R where
-    the rungs are enqueued and 0 everywhere else."""
+    the rungs are enqueued and 0 everywhere else.  subtree_wide = W (0 .. 4096, default 0 = off) and subtree_lds_panels = M (0 = off, or
+    16 .. 4096) shape the factorising forward launch of each stage of a subtree handle (newton_system, factorize, the rungs of
+    subtree_ladder); both need the creator's own subtree key and refuse float32_refine, M also needs the creator's blocked key
+    (general_blocked / float32_blocked); else ValueError / CNL_ERR_ARG.  With F_s the largest staging stride (word 7 of
+    plan_array("gtasks")) of stage s: on a handle with 256 threads per workgroup a stage with F_s >= W and tasks_s x batch <= 2 x the
+    device's CU count factorises with 1024 threads (in float the only way to a 1024-thread instance); on a blocked handle a stage with
+    F_s <= M, a front of 16 pivots or more and (16 + 32 F_s) elements within the LDS of a workgroup eliminates its dependent pivot panels
+    in LDS.  Backward stages, solve_ldl!, climbers and decide kernels are untouched; every output is that of the keys off, bit for
+    bit; no plan, route or launch count changes.  config["subtree_wide"] / config["subtree_lds_panels"] say whether any stage is
+    affected, subtree_stage_shape(LDLT) gives the table the launch loop reads."""
     o = cnl_options()
     lib().cnl_options_init(C.byref(o))
     assert o.struct_size == C.sizeof(cnl_options), "cnl_options layout differs from the library's"
@@ -331,6 +341,7 @@ def lib():
             getattr(L, "cnl_outer_ls_test_ex" + sfx).argtypes = [vp, C.c_int, vp, vp]
         L.cnl_set_active_batch.argtypes = [vp, i64]
         L.cnl_get_active_batch.argtypes = [vp, C.POINTER(i64)]
+        L.cnl_subtree_stage_shape.argtypes = [vp, vp, vp, C.POINTER(i64)]
         for fn in ("cnl_outer_compact_dev", "cnl_outer_compact_f32_dev"):
             getattr(L, fn).argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, vp]
         if L.cnl_version() < 200:
@@ -525,7 +536,11 @@ class HIPLDLStruct:
                        "float32_subtrees": bool((int(cfg[5]) >> 50) & 1),
                        # ... with this many rungs of the rho ladder enqueued behind the first attempt of newton_system
                        # (Options(subtree_ladder=R), where the subtree key acts; 0 everywhere else)
-                       "subtree_ladder": (int(cfg[5]) >> 51) & 127}
+                       "subtree_ladder": (int(cfg[5]) >> 51) & 127,
+                       # at least one stage factorises with 1024 threads per workgroup at the created batch (Options(subtree_wide=W))
+                       "subtree_wide": bool((int(cfg[5]) >> 58) & 1),
+                       # at least one stage eliminates its dependent pivot panels in LDS (Options(subtree_lds_panels=M))
+                       "subtree_lds_panels": bool((int(cfg[5]) >> 59) & 1)}
         if self.config["float32"] and self.config["band"]:   # (a Float32 handle off the band kernels — tuning float32_general — is "v1")
             self.config["kernel"] = "band"
 
@@ -567,6 +582,17 @@ def set_active_batch(LDLT, nb):
     """cnl_set_active_batch: the handle's device-pointer entry points work on its first nb problems from here on (arrays keep the
     addressing of the created batch).  Raises CnlError — code 5 (CNL_ERR_STATE) on a handle that cannot (staged, split, dense)."""
     _check(lib().cnl_set_active_batch(LDLT._h, int(nb)))
+
+
+def subtree_stage_shape(LDLT):
+    """cnl_subtree_stage_shape: (tpp, lds_bytes), two int32 arrays with one entry per stage of a subtree handle — threads per workgroup
+    and dynamic LDS bytes of the stage's factorising forward launch at the handle's current active batch (Options(subtree_wide=W,
+    subtree_lds_panels=M)).  Raises CnlError (CNL_ERR_ARG) on a handle that is no subtree handle."""
+    n = C.c_int64(0)
+    _check(lib().cnl_subtree_stage_shape(LDLT._h, None, None, C.byref(n)))
+    tpp, lds = np.zeros(int(n.value), np.int32), np.zeros(int(n.value), np.int32)
+    _check(lib().cnl_subtree_stage_shape(LDLT._h, tpp.ctypes.data, lds.ctypes.data, C.byref(n)))
+    return tpp, lds
 
 
 def get_active_batch(LDLT):

@@ -67,7 +67,8 @@ const char* cnl_last_error(void);
  * 0.5.4: tuning "general_blocked", cnl_get_config bit 47, no new symbol; 0.5.5: tuning "float32_blocked", cnl_get_config bit 48,
  * no new symbol; 0.5.6: tuning "general_subtrees", cnl_get_config bit 49, cnl_plan_get "gtasks" / "gstage_ptr" / "gfronts" / "ginfo",
  * no new symbol; 0.5.7: tuning "float32_subtrees", cnl_get_config bit 50, no new symbol; 0.5.8: tuning "subtree_ladder", cnl_get_config
- * bits 51 .. 57, no new symbol) */
+ * bits 51 .. 57, no new symbol; 0.5.9: tuning "subtree_wide" and "subtree_lds_panels", cnl_get_config bits 58 / 59,
+ * cnl_subtree_stage_shape) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -565,8 +566,35 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  * of vals, d of the successes; rows of d of the failures untouched — is that of the same handle with R = 0, bit for bit in both element
  * types.  The ladder state (a done flag and two rho values per problem) is written by the first decide of every call; sub-batch views
  * and cnl_set_active_batch move and shorten it with every per-problem array.  cnl_multi shards inherit the key.  Measured: DESIGN
- * section 3.3. */
+ * section 3.3.
+ *
+ * bit 58 = at least one stage of a subtree handle runs its factorising forward launch with 1 024 threads per workgroup at the created
+ * batch (tuning "subtree_wide"); bit 59 = at least one stage runs it on the LPAN instance, dependent pivot panels in LDS (tuning
+ * "subtree_lds_panels").  Both clear on every handle on which the key does not act.
+ *
+ * Tuning "subtree_wide" (W, 0 default = off, 1 .. 4096) and "subtree_lds_panels" (M, 0 default = off, 16 .. 4096) shape the
+ * FACTORISING FORWARD launch of each stage of a subtree handle of either element type: phase 0 of cnl_newton_system* and
+ * cnl_factorize*, and the rung launches of "subtree_ladder".  Rules, all answered before a device is looked for, at the creators
+ * and at cnl_plan_create_ex: a value out of range is CNL_ERR_ARG; so is either key without the creator's own subtree key
+ * ("general_subtrees=1" at cnl_create_ex / cnl_multi_create_ex, "float32_subtrees=1" at cnl_create_f32*), either key together with
+ * "float32_refine", and "subtree_lds_panels" without the creator's own blocked key ("general_blocked=1", "float32_blocked=1").
+ * Neither changes a plan, a layout, a route or the number of launches.  With F_s = the largest "gtasks" staging stride (word 7) of
+ * the tasks of stage s:
+ *   "subtree_wide=W" acts on a subtree handle with 256 threads per workgroup (cfg[0] == 256): stage s factorises with 1 024 threads
+ *   where F_s >= W and tasks_s x batch <= 2 x the device's CU count, batch being the launch's own (the active prefix, a sub-batch
+ *   view).  The backward stages, every launch of cnl_solve*, the climbers and the decide / commit kernels keep 256.  In float these
+ *   are the only 1 024-thread instances of the general kernel: "v1_tpp=1024" at a Float32 creator stays CNL_ERR_ARG.
+ *   "subtree_lds_panels=M" acts on a subtree handle that is blocked (bit 47 / 48): stage s runs the LPAN instance where F_s <= M, the
+ *   stage has a front of at least 16 pivots and (16 + 32 F_s) elements fit the device's LDS per workgroup (at most 160 KB); the launch
+ *   requests that much dynamic LDS.  A dependent pivot panel's rows are copied to LDS, eliminated there by the statements of the
+ *   global-memory loop in their order, handed to the matrix-core trailing update from there and written back.
+ * Both combine.  The operations on every element of a front and their order are unchanged, so every output is that of the handle
+ * without the keys, bit for bit.  cnl_subtree_stage_shape (below) returns the table the launch loop reads.  Measured: DESIGN section 3.4. */
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
+/* The factorising forward launch of every stage of a subtree handle (bit 49 or 50 of cnl_get_config [5]) at the handle's current
+ * active batch: tpp[s] = threads per workgroup, lds_bytes[s] = dynamic LDS bytes (16 elements without LDS panels), *nstages = S.
+ * tpp and lds_bytes hold S entries each, or are null: the count alone.  A handle that is no subtree handle: CNL_ERR_ARG. */
+int cnl_subtree_stage_shape(const cnl_handle* h, int32_t* tpp, int32_t* lds_bytes, int64_t* nstages);
 /* (bit 38 = a refined handle — tuning "float32_refine", below —, bits 39-41 = its refinement steps k; every other word and bit
  *  describes its inner Float32 handle, with bit 27 clear: the handle is a Float64 handle.) */
 /* ([5] + (1 << 27) on a Float32 handle.  On the band kernels: bits 7-26 as above, cfg[0..4], [6], [7] are 0.  On the general kernel

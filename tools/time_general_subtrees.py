@@ -24,7 +24,16 @@ mix x 256 on grid_structure(48); grid_structure(70) x 1 with the one problem of 
 grid_structure(70) x 16 with one kind-2 climber among healthy problems; the healthy grid_structure(70) x 1 and x 256 and
 grid_structure(48) x 256, where a rung is S + 1 empty launches.
 
+--wide: the per-stage launch shapes (tuning subtree_wide = W and subtree_lds_panels = M).  newton_system_dev and
+factorize_dev, WIDE_CASES in both element types (one table, Float64 first), the subtree key and the blocked key on on every side.  Sides, all
+in one process and taking turns call by call: both keys off; W = 1, 96, 128, 160; M = 4096 alone; every W with M = 4096 (the row of the
+W with the lowest newton_system median is marked "best W + M").  Every side must agree with the keys-off side bit for bit in success,
+nfact, rho, rho_old, d and vals.  The last case is grid_structure(70) x 1 with subtree_ladder = 5 on every side and the one problem of
+kind 2 climbing.  Each row also gives the table of cnl_subtree_stage_shape as threads per stage and LPAN stages.
+
 usage: time_general_subtrees.py [--dtype float32] [--only K,K,...] [--out FILE]
+       time_general_subtrees.py --wide [--only K,K,...] [--out FILE]
+       time_general_subtrees.py --trace-wide W,M   grid_structure(70) x 1, general_blocked = 1, the keys as given: three newton_system calls
        time_general_subtrees.py --ladder 3,5,19 [--dtype float32] [--only K,K,...] [--out FILE]
        time_general_subtrees.py --trace      grid_structure(70) x 1, key on, general_blocked = 1: three newton_system calls and nothing
                                              else, for a kernel trace taken from outside (profiles/general_subtrees_trace.txt)"""
@@ -51,6 +60,10 @@ CASES_F32 = ([("grid", (G,), B, dict(float32_blocked=1), "healthy") for G in (48
 # "one-climber" (problem 0 of kind 2, the others healthy)
 LADDER_CASES = [("grid", (48,), 256, "mix"), ("grid", (70,), 1, "kind2"), ("grid", (70,), 1, "kind3"), ("grid", (70,), 16, "one-climber"),
                 ("grid", (70,), 1, "healthy"), ("grid", (70,), 256, "healthy"), ("grid", (48,), 256, "healthy")]
+# --wide: (generator, its arguments, batch, values, subtree_ladder)
+WIDE_CASES = ([("grid", (70,), B, "healthy", 0) for B in (1, 16, 256)] + [("grid", (48,), B, "healthy", 0) for B in (1, 256)] +
+              [("random", (1000, 1500, 10, 0.01, 1), 1, "healthy", 0), ("grid", (70,), 1, "kind2", 5)])
+WIDE_W, WIDE_M = (1, 96, 128, 160), 4096
 F32 = False      # --dtype float32
 
 
@@ -87,7 +100,8 @@ def inputs(syn, s, B, kind):
 
 
 def make_runs(torch, hipldl, syn, case, keys=(0, 1)):
-    """keys: the sides — 0 / 1 the subtree key, or (1, R) the subtree key with subtree_ladder = R"""
+    """keys: the sides — 0 / 1 the subtree key, (1, R) the subtree key with subtree_ladder = R, or a dict of further options beside the
+    subtree key (--wide)"""
     import numpy as np
     gen, args, B, extra, kind = case
     s = syn.grid_structure(*args) if gen == "grid" else syn.random_structure(*args)
@@ -97,14 +111,15 @@ def make_runs(torch, hipldl, syn, case, keys=(0, 1)):
     f64, i32 = dict(dtype=torch.float32 if F32 else torch.float64, device=dev), dict(dtype=torch.int32, device=dev)   # (the run's element type)
     runs = []
     for key in keys:
-        key, rungs = key if isinstance(key, tuple) else (key, None)
-        opt = dict(BASE_F32, float32_subtrees=key, **extra) if F32 else dict(BASE, general_subtrees=key, **extra)
+        more = key if isinstance(key, dict) else {}
+        key, rungs = key if isinstance(key, tuple) else (1 if isinstance(key, dict) else key, None)
+        opt = dict(BASE_F32, float32_subtrees=key, **extra, **more) if F32 else dict(BASE, general_subtrees=key, **extra, **more)
         if rungs is not None:
             opt["subtree_ladder"] = rungs
         if gen == "grid" and not F32:
             opt["plan_kind"] = hipldl.PLAN_THROUGHPUT
         L = hipldl.HIPLDLStruct(s.N, rows, cols, None, s.nvar, s.nequ, s.ncon, batch=B, options=hipldl.Options(**opt), **(dict(dtype=np.float32) if F32 else {}))
-        runs.append(dict(key=key, rungs=rungs, L=L, vh=torch.from_numpy(vh).to(dev), vals=torch.from_numpy(vh).to(dev), rhs=torch.from_numpy(rh).to(dev), roh=torch.from_numpy(roh).to(dev),
+        runs.append(dict(key=key, rungs=rungs, more=more, L=L, vh=torch.from_numpy(vh).to(dev), vals=torch.from_numpy(vh).to(dev), rhs=torch.from_numpy(rh).to(dev), roh=torch.from_numpy(roh).to(dev),
                          d=torch.zeros((B, s.N), **f64), ro=torch.zeros(B, **f64), rho=torch.zeros(B, **f64), nf=torch.zeros(B, **i32), su=torch.zeros(B, **i32)))
     return s, runs
 
@@ -252,6 +267,106 @@ def ladder(argv):
     return 0
 
 
+def wide_one(torch, hipldl, syn, case):
+    """one case of --wide in the element type F32 says: the sides of the module docstring, newton_system and factorize"""
+    import numpy as np
+    gen, args, B, kind, R = case
+    p = hipldl.default_params(np.float32) if F32 else hipldl.default_params()
+    KEY, BLK = ("float32_subtrees", "float32_blocked") if F32 else ("general_subtrees", "general_blocked")
+    extra = {BLK: 1}
+    if R:
+        extra["subtree_ladder"] = R
+    sides = [{}] + [dict(subtree_wide=W) for W in WIDE_W] + [dict(subtree_lds_panels=WIDE_M)] + [dict(subtree_wide=W, subtree_lds_panels=WIDE_M) for W in WIDE_W]
+    s, runs = make_runs(torch, hipldl, syn, (gen, args, B, extra, kind), keys=sides)
+
+    def timed(r, call):
+        r["vals"].copy_(r["vh"])
+        r["ro"].copy_(r["roh"])
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        if call == "newton":
+            hipldl.newton_system_dev(r["L"], r["vals"].data_ptr(), r["rhs"].data_ptr(), r["d"].data_ptr(), r["ro"].data_ptr(), r["rho"].data_ptr(),
+                                     r["nf"].data_ptr(), r["su"].data_ptr(), p, 0)
+        else:
+            hipldl.factorize_dev(r["L"], r["vals"].data_ptr(), float(p[0]), r["su"].data_ptr(), stream=0)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    off = runs[0]
+    for r in runs:
+        r["d"].fill_(7.0)
+        before = hipldl.launch_counts()["general"]
+        timed(r, "newton")
+        r["launches"] = hipldl.launch_counts()["general"] - before
+        c = r["L"].config
+        assert c[KEY] and c[BLK] and c["kernel"] == "v1" and c["subtree_ladder"] == R and r["launches"] == off["launches"], (c, r["launches"])
+        tpp, lds = hipldl.subtree_stage_shape(r["L"])
+        r["tpp"], r["lpan"] = tpp.tolist(), (lds > 16 * (4 if F32 else 8)).astype(int).tolist()
+        assert c["subtree_wide"] == (max(r["tpp"]) > c["tpp"]) and c["subtree_lds_panels"] == bool(max(r["lpan"]))
+        for k in ("su", "nf", "rho", "ro", "d", "vals"):      # bit for bit the keys-off side (NaN compares as bits)
+            a, b = r[k], off[k]
+            assert torch.equal(a.view(torch.int32 if a.element_size() == 4 else torch.int64), b.view(torch.int32 if b.element_size() == 4 else torch.int64)), (r["more"], k)
+    assert off["tpp"] == [off["L"].config["tpp"]] * len(off["tpp"]) and not max(off["lpan"])
+    if kind == "healthy":
+        assert bool((off["su"] == 1).all()) and int(off["nf"].max().item()) == 1
+    for r in runs:
+        r["t"] = dict(newton=[], factor=[])
+    for it in range(WARMUP + ROUNDS):
+        for r in runs:
+            for call in ("newton", "factor"):
+                t = timed(r, call)
+                if it >= WARMUP:
+                    r["t"][call].append(t)
+    gi = off["L"].plan_array("ginfo").tolist()
+    F = [int(max(t[7] for t in off["L"].plan_array("gtasks").reshape(-1, 8) if t[0] == st)) for st in range(gi[2])]
+    out = dict(pattern=f"{gen}{tuple(args)}", B=B, N=s.N, values=kind, rungs=R, ginfo=gi, tpp=off["L"].config["tpp"], nfact=sorted(set(int(x) for x in off["nf"].cpu().numpy())),
+               F=F, stage_tasks=np.diff(off["L"].plan_array("gstage_ptr")).tolist(), launches=off["launches"],
+               sides=[dict(keys=r["more"], tpp=r["tpp"], lpan=r["lpan"], **{k: [float(np.median(v)), min(v), max(v)] for k, v in r["t"].items()}) for r in runs])
+    for r in runs:
+        r["L"].close()
+    return out
+
+
+def wide(argv):
+    global F32
+    torch, hipldl, syn = setup()
+    only = [int(x) for x in argv[argv.index("--only") + 1].split(",")] if "--only" in argv else list(range(len(WIDE_CASES)))
+    lines = [f"subtree_wide = W / subtree_lds_panels = M on subtree handles, blocked key on on every side: whole-call device time in ms, median [min .. max] of {ROUNDS} "
+             f"alternated rounds after {WARMUP} warm-up rounds, one process; every side agrees with the keys-off side bit for bit in success, nfact, rho, rho_old, d and vals",
+             "against keys off: off / side, FASTER or SLOWER only beyond the larger of the two spreads; ** ** marks what is slower",
+             "[case] pattern x batch, element type, values, F_s per stage, tasks per stage | side: stages at 1024 threads, LPAN stages | newton_system | against keys off | factorize | against keys off"]
+    fmt = lambda t: f"{t[0]:9.3f} [{t[1]:9.3f} .. {t[2]:9.3f}]"
+
+    def mark(v):
+        return f"**{v.strip()}**" if v.endswith("SLOWER") else v.strip()
+    for k in only:
+        for f32 in (False, True):
+            F32 = f32
+            t0 = time.time()
+            o = wide_one(torch, hipldl, syn, WIDE_CASES[k])
+            head = (f"[{k}] {o['pattern']} x {o['B']}, {'Float32' if f32 else 'Float64'}, {o['values']}{', subtree_ladder = %d (nfact %s)' % (o['rungs'], o['nfact']) if o['rungs'] else ''}, "
+                    f"F_s {o['F']}, tasks {o['stage_tasks']}, {o['launches']} launches per newton_system")
+            lines.append(head)
+            off = o["sides"][0]
+            ws = [sd for sd in o["sides"] if set(sd["keys"]) == {"subtree_wide"}]
+            best = min(ws, key=lambda sd: sd["newton"][0])["keys"]["subtree_wide"]
+            n0 = len(lines) - 1
+            for sd in o["sides"]:
+                name = ", ".join(f"{'W' if a == 'subtree_wide' else 'M'} = {b}" for a, b in sd["keys"].items()) or "keys off"
+                if sd["keys"] == dict(subtree_wide=best, subtree_lds_panels=WIDE_M):
+                    name += " (best W + M)"
+                shape = f"{sum(1 for t in sd['tpp'] if t == 1024)} wide {''.join('w' if t == 1024 else '.' for t in sd['tpp'])}, {sum(sd['lpan'])} LPAN {''.join('l' if x else '.' for x in sd['lpan'])}"
+                cmp_ = ["", ""] if not sd["keys"] else [mark(verdict(off[c], sd[c])) for c in ("newton", "factor")]
+                lines.append(f"    {name:34s} | {shape} | {fmt(sd['newton'])} | {cmp_[0]:>18s} | {fmt(sd['factor'])} | {cmp_[1]:>18s}")
+            print("\n".join(lines[n0:]) + f"\n    ({time.time() - t0:.1f} s)", flush=True)
+            print(json.dumps(o), file=sys.stderr, flush=True)
+            if "--out" in argv:      # (written case by case: what was measured is kept if a later case is not reached)
+                with open(argv[argv.index("--out") + 1], "w") as f:
+                    f.write("\n".join(lines) + "\n")
+    return 0
+
+
 def verdict(off, on):
     spread = max(off[2] - off[1], on[2] - on[1])
     diff = on[0] - off[0]
@@ -276,10 +391,33 @@ def trace():
     return 0
 
 
+def trace_wide(argv):
+    W, M = (int(x) for x in argv[argv.index("--trace-wide") + 1].split(","))
+    torch, hipldl, syn = setup()
+    case = ("grid", (70,), 1, dict(general_blocked=1), "healthy")
+    s, runs = make_runs(torch, hipldl, syn, case, keys=[{k: v for k, v in (("subtree_wide", W), ("subtree_lds_panels", M)) if v}])
+    r = runs[0]
+    assert r["L"].config["general_subtrees"] and r["L"].config["general_blocked"], r["L"].config
+    p = hipldl.default_params()
+    for _ in range(3):
+        hipldl.newton_system_dev(r["L"], r["vals"].data_ptr(), r["rhs"].data_ptr(), r["d"].data_ptr(), r["ro"].data_ptr(), r["rho"].data_ptr(),
+                                 r["nf"].data_ptr(), r["su"].data_ptr(), p, 0)
+        torch.cuda.synchronize()
+    assert int(r["su"].item()) == 1
+    tpp, lds = hipldl.subtree_stage_shape(r["L"])
+    print("W", W, "M", M, "stage_ptr", r["L"].plan_array("gstage_ptr").tolist(), "tpp", tpp.tolist(), "lds_bytes", lds.tolist())
+    r["L"].close()
+    return 0
+
+
 def main(argv):
     global F32
     if "--trace" in argv:
         return trace()
+    if "--trace-wide" in argv:
+        return trace_wide(argv)
+    if "--wide" in argv:
+        return wide(argv)
     if "--dtype" in argv:
         F32 = {"float32": True, "float64": False}[argv[argv.index("--dtype") + 1]]
     if "--ladder" in argv:
