@@ -150,6 +150,18 @@ int setup_subtrees(cnl_handle* h) {
       if (h->gstage_fmax[s] <= o.subtree_lds_panels && has_panel[s] && need <= cap) h->gstage_lpan[s] = (int32_t)need;
     }
   }
+  // tuning subtree_solve_panels: the dynamic LDS of a panelled solve sweep of a stage — the front's vector, the panel's
+  // triangle and its 16 values (kernels.h: subtree_solve_lds_elems)
+  h->gstage_solve_lds.assign(nst, 0);
+  if (o.subtree_solve_panels > 0) {
+    const size_t cap = std::min<size_t>(cnl::max_lds_bytes(), (size_t)160 * 1024);
+    bool any = false;
+    for (int s = 0; s < nst; s++) {
+      const size_t need = (size_t)cnl::subtree_solve_lds_elems(h->gstage_fmax[s]) * h->esz();
+      if (need <= cap) { h->gstage_solve_lds[s] = (int32_t)need; any = true; }
+    }
+    if (any) h->solve_panels = o.subtree_solve_panels;   // (no stage fits: every launch is the unpanelled one, and the handle reports 0)
+  }
   return CNL_OK;
 }
 
@@ -1180,6 +1192,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
       if (sh.tpp != h->cfg.tpp) cfg[5] |= (int64_t)1 << 58;
       if (h->gstage_lpan[st]) cfg[5] |= (int64_t)1 << 59;
     }
+    cfg[5] |= (int64_t)(h->solve_panels & 3) << 60;   // tuning subtree_solve_panels: the mask of the solve sweeps that run in panels of 16 pivots (bit 60: backward stages, bit 61: forward stages of solve_ldl!)
   }
   if (h->lean && !dense_route) cfg[5] |= 16;  // newton_system / factorize run the kernels' LEAN instantiation
   if (h->staged && h->use_v2 && !dense_route) {          // staged handles: how the stages run

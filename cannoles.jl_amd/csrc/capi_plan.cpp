@@ -98,6 +98,12 @@ int resolve_options(const cnl_options* in, cnl::Tuning& out) {
     return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_wide and subtree_lds_panels do not go with float32_refine (no refined handle over a subtree factor)");
   if (out.subtree_lds_panels && !out.general_blocked && !out.float32_blocked)
     return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_lds_panels needs general_blocked = 1 (Float64 handles) or float32_blocked = 1 (Float32 general handles): the pivot panels are those of the blocked instances");
+  if (out.subtree_solve_panels < 0 || out.subtree_solve_panels > 3)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_solve_panels is a bit mask, 0 .. 3: bit 0 the backward stage launches of a subtree handle in panels of 16 pivots, bit 1 the forward stage launches of solve_ldl!");
+  if (out.subtree_solve_panels && !out.general_subtrees && !out.float32_subtrees)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_solve_panels needs general_subtrees = 1 (Float64 handles) or float32_subtrees = 1 (Float32 general handles): it shapes the solve sweeps of the subtree instances");
+  if (out.subtree_solve_panels && out.float32_refine)
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: subtree_solve_panels does not go with float32_refine (no refined handle over a subtree factor)");
   if (out.cgls_wide < 0 || out.cgls_wide > 2)
     return fail(CNL_ERR_ARG, "cnl_options.tuning: cgls_wide is 0 (the LDS instance, ncon <= 1024), 1 (the wide instance where ncon > 1024) or 2 (the wide instance always)");
   return CNL_OK;
@@ -317,6 +323,10 @@ int check_subtree_ladder(const cnl::Tuning& o, bool f32, const char* fn) {
   if (o.subtree_lds_panels && !(f32 ? o.float32_blocked : o.general_blocked))
     return fail(CNL_ERR_ARG, std::string(fn) + (f32 ? ": tuning subtree_lds_panels needs float32_blocked = 1 at a Float32 creator (the pivot panels are those of the float blocked instances)"
                                                     : ": tuning subtree_lds_panels needs general_blocked = 1 at a Float64 creator (the pivot panels are those of the Float64 blocked instances)"));
+  // tuning subtree_solve_panels: the creator's own subtree key again
+  if (o.subtree_solve_panels && !(f32 ? o.float32_subtrees : o.general_subtrees))
+    return fail(CNL_ERR_ARG, std::string(fn) + (f32 ? ": tuning subtree_solve_panels needs float32_subtrees = 1 at a Float32 creator (it shapes the solve sweeps of the float subtree instances)"
+                                                    : ": tuning subtree_solve_panels needs general_subtrees = 1 at a Float64 creator (it shapes the solve sweeps of the Float64 subtree instances)"));
   return CNL_OK;
 }
 
@@ -483,7 +493,9 @@ const char* cnl_last_error(void) { return g_err.c_str(); }
 //        bits 51 .. 57, no new symbol
 // 0.5.9: tuning subtree_wide (1024-thread factorising stages on 256-thread subtree handles, the float instances among them) and
 //        subtree_lds_panels (dependent pivot panels of blocked subtree handles in LDS), cnl_get_config bits 58 / 59, cnl_subtree_stage_shape
-int32_t cnl_version(void) { return 509; }
+// 0.5.10: tuning subtree_solve_panels (the solve sweeps of subtree handles in panels of 16 pivots, entries of their own), cnl_get_config
+//        bits 60 / 61, no new symbol
+int32_t cnl_version(void) { return 510; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62

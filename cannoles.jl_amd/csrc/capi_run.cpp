@@ -156,6 +156,11 @@ int launch_subtrees(cnl_handle* h, cnl::LaunchArgs& a, hipStream_t stream) {
   auto stage = [&](int s, int phase) {
     a.phase = phase; a.task0 = h->gstage_ptr[s]; a.ntasks = h->gstage_ptr[s + 1] - h->gstage_ptr[s];
     g_launches[2]++;
+    // (tuning subtree_solve_panels, DESIGN section 3.5: a backward stage — bit 0 — and a forward stage of solve_ldl! — bit 1 — run the
+    //  panelled entries where the stage's vector and panel areas fit a workgroup's LDS)
+    const int panel_bit = phase == 1 ? 1 : (solve ? 2 : 0);
+    if ((h->solve_panels & panel_bit) && h->gstage_solve_lds[s])
+      return cnl::launch_subtree_solve(h->dp, h->cfg, a, stream, h->f32, h->gstage_fmax[s], (size_t)h->gstage_solve_lds[s]);
     if (phase != 0 || solve) return cnl::launch_newton_subtrees(h->dp, h->cfg, a, stream, h->f32);
     const cnl::SubtreeStageShape sh = subtree_stage_shape(h, s, a.batch);
     return cnl::launch_newton_subtrees(h->dp, h->cfg, a, stream, h->f32, &sh);

@@ -139,6 +139,12 @@ struct cnl_handle {
   int32_t sub_wide = 0;
   int32_t sub_cus = 0;
   std::vector<int32_t> gstage_fmax, gstage_lpan;
+  // tuning subtree_solve_panels = P on such a handle (cnl_get_config bits 60 / 61): solve_panels = P (bit 0: the backward
+  // stage launches, bit 1: the forward stage launches of solve_ldl! run subtree_solve_kernel), 0 on every other handle and where no stage fits; gstage_solve_lds[s] =
+  // the dynamic LDS bytes of such a launch of stage s, (round4(F_s) + 288) elements, 0 where that exceeds the device's LDS per workgroup
+  // (the stage then keeps the unpanelled launch).
+  int32_t solve_panels = 0;
+  std::vector<int32_t> gstage_solve_lds;
   // Float32 general handles on a condensed plan: the resident condense kernel serves the handle (kernels.h: DevCondEll) — where the
   // tiled kernel's chunks degenerate (dense Jacobians) and [vals | rhs] of a problem fits LDS; tuning float32_condense = 2: never
   bool cond_resident = false;

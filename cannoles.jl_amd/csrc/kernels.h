@@ -228,6 +228,17 @@ struct SubtreeStageShape {
 };
 hipError_t launch_newton_subtrees(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream, bool f32,
                                   const SubtreeStageShape* shape = nullptr);
+// The solve sweeps of a subtree handle in panels of PANEL_W = 16 pivots (tuning subtree_solve_panels; kernels.hip:
+// subtree_solve_kernel — entries of their own, double at 256 or 1024 threads, float at 256).  One launch of a stage, grid and arguments as
+// launch_newton_subtrees': a.phase 1 — the backward sweep; a.phase 0 with MODE_SOLVE — the forward substitution.  Dynamic LDS of a launch
+// of a stage whose largest task fmax is F_s, in elements: [the front's vector, round4(F_s) | the panel's triangle, 16 rows of stride 17 |
+// the panel's 16 values] — every carve offset a multiple of 4 elements, 16 bytes in float.
+constexpr int SOLVE_PANEL_TRI = 16 * 17;
+inline int64_t subtree_solve_vec_elems(int64_t fmax_s) { return (fmax_s + 3) & ~(int64_t)3; }
+inline int64_t subtree_solve_lds_elems(int64_t fmax_s) { return subtree_solve_vec_elems(fmax_s) + SOLVE_PANEL_TRI + 16; }
+// fmax_s: F_s of the stage; lds_bytes = subtree_solve_lds_elems(fmax_s) x the element size
+hipError_t launch_subtree_solve(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream, bool f32, int fmax_s,
+                                size_t lds_bytes);
 bool newton_subtrees_has(int tpp, int ppb, bool f32);   // is there a subtree instance of the element type for this configuration?
 // behind the last forward stage of a factorising subtree call: success (and a.npos / a.nzero where given) from the slots of gcnt plus
 // a.extra_pos / a.extra_zer; MODE_NEWTON: rho = 0, nfact = 1 of the problems that succeeded

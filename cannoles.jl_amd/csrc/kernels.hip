@@ -839,6 +839,229 @@ hipError_t launch_subtree_decide(const LaunchArgs& a, const int* gcnt, int ntask
 }
 
 // ---------------------------------------------------------------------------
+// The solve sweeps of a subtree handle in panels of PANEL_W pivots (tuning subtree_solve_panels).  Entries of their own,
+// launched for the backward stages (A.phase 1) and the forward stages of solve_ldl! (A.phase 0, MODE_SOLVE) of handles with the key alone:
+// front_forward, front_backward and every instance built from them are the code they were.  Grid, sub_enter_task and the early exit of a
+// problem without a factor are newton_subtrees'.  The front's vector (X, resp. F) lives in dynamic LDS, the stored panel Lp is read in
+// place (no copy to PB: the backward sweep only reads it, the forward one writes column 0 of a row and never reads it), and what other
+// tasks read in later launches goes to the task region as ever: X of the front (backward), the 1 + nupd update entries at ubase (forward).
+// LDS (kernels.h: subtree_solve_lds_elems): [vec: round4(F_s) | tri: PANEL_W rows of stride PANEL_W + 1 | pv: PANEL_W].
+constexpr int SP_LD = PANEL_W + 1;
+static_assert(PANEL_W * SP_LD == SOLVE_PANEL_TRI, "kernels.h sizes the triangle area");
+
+__device__ __forceinline__ double fnma_of(double a, double b, double c) { return __builtin_fma(-a, b, c); }
+__device__ __forceinline__ float fnma_of(float a, float b, float c) { return __builtin_fmaf(-a, b, c); }
+// the value lane k of the wavefront holds, k uniform (a constant once the panel loops are unrolled): v_readlane, no LDS round trip
+__device__ __forceinline__ float lane_value(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
+__device__ __forceinline__ double lane_value(double v, int k) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), k), __builtin_amdgcn_readlane(__double2loint(v), k));
+}
+
+// Backward sweep of one front, x_i = z_i - sum_{1 <= j < i} l_ij x_j, panels [p0, p1) of pivot rows ascending, the last one short.
+// Outer part: s_r = sum_{1 <= j < p0} l_rj x_j of the panel's rows at once, row r on the TPP / PANEL_W lanes tid / G, lanes striding over j
+// (contiguous runs of Lp), reduced by shuffles inside the lane group; t_r = z_r - s_r into pv; the panel's triangle into tri meanwhile.
+// Inner part: the first wavefront, lane r holding t_r: x_k is broadcast in steps k = 0 .. 14 and the lanes r > k subtract l_rk x_k.
+// Two workgroup barriers per panel.  The order of summation is a function of (TPP, front) alone.
+template <int TPP, class T>
+__device__ __forceinline__ void front_backward_panels(const DevPlan& P, const FrontHdr& H, const ProblemCtx<T>& c, int tid, T* dout, T* Xs,
+                                                      T* tri, T* pv) {
+  constexpr int G = TPP / PANEL_W;   // lanes of a row: 16 or 64, never across a wavefront
+  const int nupd = H.nupd, npiv = H.npiv;
+  const int f = 1 + nupd + npiv;
+  const int tu = tri_i(1 + nupd);
+  T* X = c.W + H.xoff;
+  const T* Lp = c.L + ((long long)H.lptr_lo | ((long long)H.lptr_hi << 31));
+  if (H.parent >= 0) {
+    // (the first child's X lies on its parent's: everything is read before anything is written)
+    const T* Xp = c.W + P.fronts[H.parent].xoff;
+    const int* rel = P.rel_idx + H.rel_begin;
+    for (int j = 1 + tid; j <= nupd; j += TPP) Xs[j] = Xp[rel[j]];
+    __syncthreads();
+    for (int j = 1 + tid; j <= nupd; j += TPP) X[j] = Xs[j];
+  }
+  const int r = tid / G, l = tid % G;
+  const int sr = (tid >> 4) & (PANEL_W - 1), sk = tid & (PANEL_W - 1);   // the triangle's element of this thread (tid < 256)
+  for (int p0 = nupd + 1; p0 < f; p0 += PANEL_W) {
+    const int kp = f - p0 < PANEL_W ? f - p0 : PANEL_W;
+    const T* rowr = Lp + (tri_i(p0 + (r < kp ? r : 0)) - tu);
+    T part = T(0);
+    if (r < kp) {
+#pragma unroll 4
+      for (int j = 1 + l; j < p0; j += G) part += rowr[j] * Xs[j];
+    }
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) part += __shfl_xor(part, o, G);
+    if (r < kp && l == 0) pv[r] = rowr[0] - part;
+    if (tid < PANEL_W * PANEL_W && sr < kp && sk < sr) tri[sr * SP_LD + sk] = Lp[tri_i(p0 + sr) - tu + p0 + sk];
+    __syncthreads();
+    if (tid < 64) {
+      T t = tid < kp ? pv[tid] : T(0);
+#pragma unroll
+      for (int k = 0; k < PANEL_W - 1; k++) {
+        const T xk = lane_value(t, k);
+        if (tid > k && tid < kp) t -= tri[tid * SP_LD + k] * xk;
+      }
+      if (tid < kp) {
+        const int i = p0 + tid;
+        Xs[i] = t;
+        X[i] = t;
+        dout[P.perm[H.first_piv + (f - 1 - i)]] = -t;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// Forward substitution of one front with the stored panel, panels [p0, p1) of pivot rows descending, the last one short.  Per pivot i
+// descending the unpanelled loop (front_forward, WITH_K = false) does w = F[i]; F[j] -= l_ij w for 1 <= j < ulim; z_i = w / d_i.  Here the
+// first wavefront runs the panel's pivots on F[p0 .. p1) (lane r holding F[p0 + r]), leaves the w_i in pv and stores the z_i; then every
+// thread applies the panel's pivots, in the same order, to the elements j < p0 it owns.  Every element receives the operations of the
+// unpanelled loop in their order, ulim honoured term by term, each one fused multiply-add as there: bit-equal.
+template <int TPP, class T>
+__device__ __forceinline__ void front_forward_solve_panels(const DevPlan& P, const FrontHdr& H, const ProblemCtx<T>& c, int tid, T* Fs, T* tri,
+                                                           T* pv) {
+  const int nupd = H.nupd, npiv = H.npiv;
+  const int f = 1 + nupd + npiv;
+  const int tu = tri_i(1 + nupd);
+  T* Lp = c.L + ((long long)H.lptr_lo | ((long long)H.lptr_hi << 31));
+  const int idep = f - H.indep;
+  const int sk = (tid >> 4) & (PANEL_W - 1), sr = tid & (PANEL_W - 1);   // the triangle's element of this thread (tid < 256)
+  // the triangle of panel [p0, p0 + kp), diagonal included: tri[k][r] = l_{p0 + k, p0 + r}, r <= k
+  auto stage_tri = [&](int p0, int kp) {
+    if (tid < PANEL_W * PANEL_W && sk < kp && sr <= sk) tri[sk * SP_LD + sr] = Lp[tri_i(p0 + sk) - tu + p0 + sr];
+  };
+  for (int t = tid; t < f; t += TPP) {
+    T v = T(0);
+    if (t > nupd) v = c.rhs[P.perm[H.first_piv + (f - 1 - t)]];
+    Fs[t] = v;
+  }
+  {
+    const int p0 = f - PANEL_W > nupd + 1 ? f - PANEL_W : nupd + 1;
+    stage_tri(p0, f - p0);
+  }
+  __syncthreads();
+  for (int ci = H.child_begin; ci < H.child_end; ci++) {
+    const FrontHdr& C = P.fronts[P.child_idx[ci]];
+    const T* U = c.W + C.ubase;
+    const int* rel = P.rel_idx + C.rel_begin;
+    for (int a = 1 + tid; a <= C.nupd; a += TPP) Fs[rel[a]] += U[a];
+    __syncthreads();
+  }
+  for (int p1 = f; p1 > nupd + 1;) {
+    const int p0 = p1 - PANEL_W > nupd + 1 ? p1 - PANEL_W : nupd + 1;
+    const int kp = p1 - p0;
+    if (tid < 64) {
+      T v = tid < kp ? Fs[p0 + tid] : T(0);
+#pragma unroll
+      for (int k = PANEL_W - 1; k >= 0; k--) {
+        if (k < kp) {   // (uniform)
+          const int i = p0 + k;
+          const int ulim = i >= idep ? idep : i;
+          const T w = lane_value(v, k);
+          if (tid < k && p0 + tid < ulim) v = fnma_of(tri[k * SP_LD + tid], w, v);
+        }
+      }
+      // (lane k is not touched after step k: what it holds is w_k; the 16 quotients at once, off the chain)
+      if (tid < kp) {
+        pv[tid] = v;
+        Lp[tri_i(p0 + tid) - tu] = v / tri[tid * SP_LD + tid];
+      }
+    }
+    __syncthreads();
+    p1 = p0;
+    // the next panel's triangle is fetched while the outer part runs (stored behind it: the first wavefront is done with tri)
+    const int q0 = p1 - PANEL_W > nupd + 1 ? p1 - PANEL_W : nupd + 1;
+    const bool more = p1 > nupd + 1 && tid < PANEL_W * PANEL_W && sk < p1 - q0 && sr <= sk;
+    T tnext = T(0);
+    if (more) tnext = Lp[tri_i(q0 + sk) - tu + q0 + sr];
+    for (int j = 1 + tid; j < p0; j += TPP) {
+      // the panel's 16 rows at column j: independent loads, all in flight before the chain of multiply-adds starts
+      T lv[PANEL_W];
+#pragma unroll
+      for (int k = 0; k < PANEL_W; k++) {
+        const int i = p0 + k;
+        lv[k] = (k < kp && (i < idep || j < idep)) ? Lp[tri_i(i) - tu + j] : T(0);
+      }
+      T v = Fs[j];
+#pragma unroll
+      for (int k = PANEL_W - 1; k >= 0; k--) {
+        const int i = p0 + k;
+        if (k < kp && (i < idep || j < idep)) v = fnma_of(lv[k], pv[k], v);   // (j < ulim, with j < p0 <= i)
+      }
+      Fs[j] = v;
+    }
+    if (more) tri[sk * SP_LD + sr] = tnext;
+    __syncthreads();
+  }
+  // the update vector for the parent, in the task region where the unpanelled sweep leaves it
+  T* U = c.W + H.ubase;
+  for (int t = tid; t <= nupd; t += TPP) U[t] = Fs[t];
+  __syncthreads();
+}
+
+template <int TPP, class T, bool BACKWARD>
+__global__ void __launch_bounds__(TPP) subtree_solve_kernel(const DevPlan Pin, const LaunchArgs Ain, const int vec_elems) {
+  static_assert(TPP >= 256 && TPP % 64 == 0, "subtree instances: one problem per workgroup of 256 or 1024 threads");
+  DevPlan P = Pin;
+  P.fronts = as_global(Pin.fronts); P.child_idx = as_global(Pin.child_idx); P.rel_idx = as_global(Pin.rel_idx);
+  P.perm = as_global(Pin.perm);
+  LaunchArgs A = Ain;
+  A.rhs = as_global(Ain.rhs); A.d = as_global(Ain.d); A.L = as_global(Ain.L);
+  A.scratch = as_global(Ain.scratch); A.success = as_global(Ain.success);
+  const int32_t* const tasks = as_global(const_cast<int32_t*>(A.tasks));
+  extern __shared__ __attribute__((aligned(16))) double smem_solve[];
+  T* const vec = reinterpret_cast<T*>(smem_solve);
+  T* const tri = vec + vec_elems;
+  T* const pv = tri + SOLVE_PANEL_TRI;
+  const int tid = threadIdx.x;
+  const int b = (int)(blockIdx.x % (unsigned)A.batch);
+  const int task = A.task0 + (int)(blockIdx.x / (unsigned)A.batch);
+  if (task >= A.task0 + A.ntasks) return;
+  if (A.success && !A.success[b]) return;   // a problem without a factor: the whole workgroup leaves, before any barrier
+  ProblemCtx<T> c;
+  c.vals = nullptr;
+  c.rhs = A.rhs ? static_cast<const T*>(A.rhs) + (long long)b * P.rstride : nullptr;
+  c.L = static_cast<T*>(A.L) + (long long)b * P.lsize;
+  c.red = nullptr;
+  c.W = static_cast<T*>(A.scratch) + (long long)b * P.work_doubles;
+  int f0, f1;
+  sub_enter_task(P, tasks, task, f0, f1);
+  if constexpr (BACKWARD) {
+    T* const dout = static_cast<T*>(A.d) + (long long)b * P.dstride;
+    for (int s = f1 - 1; s >= f0; s--) front_backward_panels<TPP>(P, P.fronts[s], c, tid, dout, vec, tri, pv);
+  } else {
+    for (int s = f0; s < f1; s++) front_forward_solve_panels<TPP>(P, P.fronts[s], c, tid, vec, tri, pv);
+  }
+}
+
+// One launch of a stage's panelled sweep: a.phase 1 — backward; a.phase 0 with MODE_SOLVE — the forward substitution of solve_ldl!.
+// fmax_s = F_s of the stage (every front of the stage has at most that many rows), lds_bytes = subtree_solve_lds_elems(F_s) elements.
+hipError_t launch_subtree_solve(const DevPlan& P, const KernelConfig& cfg, const LaunchArgs& a, hipStream_t stream, bool f32, int fmax_s,
+                                size_t lds_bytes) {
+  if (!newton_subtrees_has(cfg.tpp, cfg.ppb, f32) || !a.tasks || !a.scratch || !a.L || a.batch < 1) return hipErrorInvalidConfiguration;
+  if ((a.phase == 0 && !a.rhs) || (a.phase == 1 && !a.d)) return hipErrorInvalidConfiguration;
+  const bool backward = a.phase == 1;
+  if (!backward && !(a.phase == 0 && a.mode == MODE_SOLVE)) return hipErrorInvalidConfiguration;
+  if (backward && !a.success) return hipErrorInvalidConfiguration;
+  const long long grid = (long long)a.batch * a.ntasks;
+  if (grid < 1 || grid > 0x7fffffffLL || fmax_s < 1) return hipErrorInvalidConfiguration;
+  const int vec_elems = (int)subtree_solve_vec_elems(fmax_s);
+  if (lds_bytes != (size_t)subtree_solve_lds_elems(fmax_s) * (f32 ? sizeof(float) : sizeof(double))) return hipErrorInvalidConfiguration;
+#define CNL_CASE(T, E) \
+  if (cfg.tpp == T) { \
+    if (backward) return launch_subtree_instance(subtree_solve_kernel<T, E, true>, grid, T, lds_bytes, stream, P, a, vec_elems); \
+    return launch_subtree_instance(subtree_solve_kernel<T, E, false>, grid, T, lds_bytes, stream, P, a, vec_elems); \
+  }
+  if (f32) {
+    CNL_CASE(256, float)
+    return hipErrorInvalidConfiguration;
+  }
+  CNL_CASE(256, double) CNL_CASE(1024, double)
+#undef CNL_CASE
+  return hipErrorInvalidConfiguration;
+}
+
+// ---------------------------------------------------------------------------
 // The rho ladder of a subtree handle, stage by stage (tuning subtree_ladder = R > 0).  Entries of their own, launched
 // by handles with R > 0 alone: newton_kernel's instances and subtree_decide_kernel are the code they were.  Per-problem state (kernels.h:
 // LadderState): done[b] — 0 climbing, 1 succeeded on the first attempt, 2 finished inside the rungs (success, or the ladder exhausted) —

@@ -77,6 +77,7 @@ namespace cnl {
   X(subtree_ladder, 0)       /* subtree handles of either element type: R = 0 .. 64 rungs of the rho ladder are enqueued behind the first attempt of newton_system, each stage by stage like it, one rung-decide launch behind each; problems still climbing after R rungs resume in the climbers' launch; (R + 2) S + R + 3 launches; valid only with general_subtrees = 1 (Float64 creators) or float32_subtrees = 1 (Float32 creators), never with float32_refine; selects no route and changes no plan: it acts where the subtree key acts */ \
   X(subtree_wide, 0)         /* subtree handles of either element type with 256 threads per workgroup: W = 1 .. 4096: the factorising forward launch of a stage (newton_system, factorize, the rungs of subtree_ladder) runs with 1024 threads per workgroup where the stage's largest task fmax F_s >= W and tasks_s x batch <= 2 x the device's CU count; every other launch keeps 256 (backward stages, solve_ldl!, climbers, decide and commit kernels); in float the only way to a 1024-thread instance; the factor and every output are bit-equal to W = 0; 0: off; valid only with general_subtrees = 1 (Float64 creators) or float32_subtrees = 1 (Float32 creators), never with float32_refine; selects no route and changes no plan */ \
   X(subtree_lds_panels, 0)   /* blocked subtree handles of either element type: M = 16 .. 4096: the factorising forward launch of a stage with F_s <= M, a front of at least 16 pivots and (16 + 32 F_s) elements within the device's LDS per workgroup (at most 160 KB) runs the LPAN instance, which eliminates the dependent pivot panels of its fronts in LDS (the panel's rows and their unscaled copies) with the statements of the global-memory loop in their order: bit-equal factor; 0: off; valid only with the creator's subtree key and its blocked key (general_blocked, float32_blocked), never with float32_refine; combines with subtree_wide; selects no route and changes no plan */ \
+  X(subtree_solve_panels, 0) /* subtree handles of either element type, blocked or not, 256 threads per workgroup or a 1024-thread Float64 handle: a bit mask P = 0 .. 3 over the solve sweeps, which run in panels of 16 pivots on entries of their own (subtree_solve_kernel), the front's vector in dynamic LDS, the stored panel read in place — bit 0: the backward stage launches of newton_system and solve_ldl! (outer part of a panel: 16 dot products on lane groups, reduced by shuffles; its triangle on one wavefront; d agrees with P = 0 to rounding and is a fixed function of the front); bit 1: the forward stage launches of solve_ldl! (every operation of the unpanelled loop on every element in its order: bit-equal to P = 0); a stage whose (round4(F_s) + 288) elements exceed the device's LDS per workgroup (at most 160 KB) keeps today's launch; factorising launches, rungs, decide / commit kernels and climbers are untouched; 0: off; valid only with general_subtrees = 1 (Float64 creators) or float32_subtrees = 1 (Float32 creators), never with float32_refine; selects no route, changes no plan, allocation or launch count */ \
   X(cgls_wide, 0)          /* row f4: 0 the ncon-vectors in LDS, more than 1024 constraints are CNL_ERR_DIM; 1 in the global workspace where ncon > 1024; 2 there always */
 
 struct Tuning {

@@ -180,7 +180,14 @@ def Options(**kw):
     F_s <= M, a front of 16 pivots or more and (16 + 32 F_s) elements within the LDS of a workgroup eliminates its dependent pivot panels
     in LDS.  Backward stages, solve_ldl!, climbers and decide kernels are untouched; every output is that of the keys off, bit for
     bit; no plan, route or launch count changes.  config["subtree_wide"] / config["subtree_lds_panels"] say whether any stage is
-    affected, subtree_stage_shape(LDLT) gives the table the launch loop reads."""
+    affected, subtree_stage_shape(LDLT) gives the table the launch loop reads.  subtree_solve_panels = P (a bit mask, 0 .. 3, default
+    0 = off; needs the creator's own subtree key and refuses float32_refine, else ValueError / CNL_ERR_ARG) runs the solve sweeps of a
+    subtree handle — blocked or not, 256 threads per workgroup or a 1024-thread Float64 handle — in panels of 16 pivots on kernel entries
+    of their own, the front's vector in LDS and the stored panel read in place: bit 0 the backward stage launches of newton_system and
+    solve (d agrees with P = 0 to rounding and is a fixed function of the front), bit 1 the forward stage launches of solve (every
+    output bit-equal to P = 0).  A stage whose (round4(F_s) + 288) elements exceed the LDS of a workgroup keeps the unpanelled launch;
+    factorising launches, rungs, decide / commit kernels and climbers are untouched; no plan, route, allocation or launch count
+    changes.  config["subtree_solve_panels"] is the mask where it acts and 0 everywhere else."""
     o = cnl_options()
     lib().cnl_options_init(C.byref(o))
     assert o.struct_size == C.sizeof(cnl_options), "cnl_options layout differs from the library's"
@@ -540,7 +547,9 @@ class HIPLDLStruct:
                        # at least one stage factorises with 1024 threads per workgroup at the created batch (Options(subtree_wide=W))
                        "subtree_wide": bool((int(cfg[5]) >> 58) & 1),
                        # at least one stage eliminates its dependent pivot panels in LDS (Options(subtree_lds_panels=M))
-                       "subtree_lds_panels": bool((int(cfg[5]) >> 59) & 1)}
+                       "subtree_lds_panels": bool((int(cfg[5]) >> 59) & 1),
+                       # the solve sweeps that run in panels of 16 pivots (Options(subtree_solve_panels=P)): bit 0 backward stages, bit 1 forward stages of solve
+                       "subtree_solve_panels": (int(cfg[5]) >> 60) & 3}
         if self.config["float32"] and self.config["band"]:   # (a Float32 handle off the band kernels — tuning float32_general — is "v1")
             self.config["kernel"] = "band"
 

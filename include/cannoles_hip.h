@@ -68,7 +68,7 @@ const char* cnl_last_error(void);
  * no new symbol; 0.5.6: tuning "general_subtrees", cnl_get_config bit 49, cnl_plan_get "gtasks" / "gstage_ptr" / "gfronts" / "ginfo",
  * no new symbol; 0.5.7: tuning "float32_subtrees", cnl_get_config bit 50, no new symbol; 0.5.8: tuning "subtree_ladder", cnl_get_config
  * bits 51 .. 57, no new symbol; 0.5.9: tuning "subtree_wide" and "subtree_lds_panels", cnl_get_config bits 58 / 59,
- * cnl_subtree_stage_shape) */
+ * cnl_subtree_stage_shape; 0.5.10 (510): tuning "subtree_solve_panels", cnl_get_config bits 60 / 61, no new symbol) */
 int32_t cnl_version(void);
 
 /* ParamCaNNOLeS(Float64) defaults, src/CaNNOLeS.jl:48-62, in the order
@@ -589,7 +589,25 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  *   requests that much dynamic LDS.  A dependent pivot panel's rows are copied to LDS, eliminated there by the statements of the
  *   global-memory loop in their order, handed to the matrix-core trailing update from there and written back.
  * Both combine.  The operations on every element of a front and their order are unchanged, so every output is that of the handle
- * without the keys, bit for bit.  cnl_subtree_stage_shape (below) returns the table the launch loop reads.  Measured: DESIGN section 3.4. */
+ * without the keys, bit for bit.  cnl_subtree_stage_shape (below) returns the table the launch loop reads.  Measured: DESIGN section 3.4.
+ *
+ * bits 60 / 61 = the mask of tuning "subtree_solve_panels" on a subtree handle; both clear on every handle that is no subtree handle.
+ *
+ * Tuning "subtree_solve_panels" (P, a bit mask 0 .. 3, default 0 = off) runs the SOLVE SWEEPS of a subtree handle of either element
+ * type — blocked or not, 256 threads per workgroup or a 1 024-thread Float64 handle — in panels of 16 pivots, on kernel entries of
+ * their own with the front's vector in dynamic LDS and the stored panel read in place:
+ *   bit 0: the backward stage launches of cnl_newton_system* and cnl_solve* (with "subtree_ladder" those behind the rungs).  Per
+ *   panel the part of the 16 rows outside the panel is 16 dot products on lane groups, reduced by cross-lane shuffles, and the
+ *   panel's triangle is solved by one wavefront: two workgroup barriers per panel.  The order of summation differs from the
+ *   unpanelled sweep's: d agrees with P = 0 to rounding, and is a fixed function of the front (no atomic, nothing that depends on
+ *   the batch, the grid, the active prefix or on what LDS held);
+ *   bit 1: the forward stage launches of cnl_solve*.  Every element receives the operations of the unpanelled loop in their order:
+ *   every output is that of P = 0, bit for bit.
+ * A stage whose (round4(F_s) + 288) elements exceed the device's LDS per workgroup (at most 160 KB) keeps the unpanelled launch.
+ * The factorising forward launches, the rungs, the decide / commit kernels and the climbers are untouched: a problem that climbs keeps
+ * the unpanelled sweep.  No plan, route, layout, allocation or launch count changes.  Rules, answered before a device is looked for:
+ * a value outside 0 .. 3, the key without the creator's own subtree key, or together with "float32_refine", is CNL_ERR_ARG.
+ * Measured: DESIGN section 3.5. */
 int cnl_get_config(const cnl_handle* h, int64_t cfg[8]);
 /* The factorising forward launch of every stage of a subtree handle (bit 49 or 50 of cnl_get_config [5]) at the handle's current
  * active batch: tpp[s] = threads per workgroup, lds_bytes[s] = dynamic LDS bytes (16 elements without LDS panels), *nstages = S.

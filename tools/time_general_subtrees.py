@@ -31,9 +31,18 @@ W with the lowest newton_system median is marked "best W + M").  Every side must
 nfact, rho, rho_old, d and vals.  The last case is grid_structure(70) x 1 with subtree_ladder = 5 on every side and the one problem of
 kind 2 climbing.  Each row also gives the table of cnl_subtree_stage_shape as threads per stage and LPAN stages.
 
+--solve-panels: the solve sweeps in panels of 16 pivots (tuning subtree_solve_panels = P).  newton_system_dev and
+solve_dev (on the factor the newton_system call before it left), WIDE_CASES in both element types, the subtree key and the blocked key on on
+every side.  Sides, all in one process and taking turns call by call: P = 0, 1, 2, 3; then P = 0 and 3 again with subtree_wide = 1 and
+subtree_lds_panels = 4096.  Every side is checked against the P = 0 side of the same launch shapes: success, nfact, rho, rho_old and vals bit
+for bit, d of both calls bit for bit for P = 2 and within the forward bar (1e-9; float: FWD_TOL of tests/support/f32_general.py) for
+P = 1 and 3, the launch counts equal.
+
 usage: time_general_subtrees.py [--dtype float32] [--only K,K,...] [--out FILE]
        time_general_subtrees.py --wide [--only K,K,...] [--out FILE]
-       time_general_subtrees.py --trace-wide W,M   grid_structure(70) x 1, general_blocked = 1, the keys as given: three newton_system calls
+       time_general_subtrees.py --solve-panels [--only K,K,...] [--out FILE]
+       time_general_subtrees.py --trace-wide W,M[,P] [--with-solve]   grid_structure(70) x 1, general_blocked = 1, the keys as given
+                                             (P: subtree_solve_panels): three newton_system calls, with --with-solve three solve calls behind them
        time_general_subtrees.py --ladder 3,5,19 [--dtype float32] [--only K,K,...] [--out FILE]
        time_general_subtrees.py --trace      grid_structure(70) x 1, key on, general_blocked = 1: three newton_system calls and nothing
                                              else, for a kernel trace taken from outside (profiles/general_subtrees_trace.txt)"""
@@ -367,6 +376,125 @@ def wide(argv):
     return 0
 
 
+SOLVE_SIDES = [dict(subtree_solve_panels=P) if P else {} for P in (0, 1, 2, 3)] + [dict(subtree_wide=1, subtree_lds_panels=WIDE_M),
+                                                                                   dict(subtree_wide=1, subtree_lds_panels=WIDE_M, subtree_solve_panels=3)]
+
+
+def solve_one(torch, hipldl, syn, case):
+    """one case of --solve-panels in the element type F32 says: newton_system and solve (on the factor newton_system left), the sides
+    SOLVE_SIDES; every side with P > 0 is checked against the P = 0 side of the same launch shapes"""
+    import numpy as np
+    gen, args, B, kind, R = case
+    p = hipldl.default_params(np.float32) if F32 else hipldl.default_params()
+    KEY, BLK = ("float32_subtrees", "float32_blocked") if F32 else ("general_subtrees", "general_blocked")
+    if F32:
+        from tests.support.f32_general import FWD_TOL
+    else:
+        FWD_TOL = 1e-9
+    extra = {BLK: 1}
+    if R:
+        extra["subtree_ladder"] = R
+    s, runs = make_runs(torch, hipldl, syn, (gen, args, B, extra, kind), keys=SOLVE_SIDES)
+    bits = lambda a: a.view(torch.int32 if a.element_size() == 4 else torch.int64)
+
+    def timed(r, call):
+        if call == "newton":
+            r["vals"].copy_(r["vh"])
+            r["ro"].copy_(r["roh"])
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        if call == "newton":
+            hipldl.newton_system_dev(r["L"], r["vals"].data_ptr(), r["rhs"].data_ptr(), r["d"].data_ptr(), r["ro"].data_ptr(), r["rho"].data_ptr(),
+                                     r["nf"].data_ptr(), r["su"].data_ptr(), p, 0)
+        else:
+            hipldl.solve_dev(r["L"], r["rhs"].data_ptr(), r["d2"].data_ptr(), stream=0)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    for r in runs:
+        r["d"].fill_(7.0)
+        r["d2"] = torch.full_like(r["d"], 7.0)
+        r["P"] = r["more"].get("subtree_solve_panels", 0)
+        n0 = hipldl.launch_counts()["general"]
+        timed(r, "newton")
+        n1 = hipldl.launch_counts()["general"]
+        timed(r, "solve")
+        r["launches"] = (n1 - n0, hipldl.launch_counts()["general"] - n1)
+        c = r["L"].config
+        assert c[KEY] and c[BLK] and c["kernel"] == "v1" and c["subtree_ladder"] == R and c["subtree_solve_panels"] == r["P"], c
+        base = next(q for q in runs if q["P"] == 0 and q["more"].get("subtree_wide", 0) == r["more"].get("subtree_wide", 0))
+        assert r["launches"] == base["launches"], (r["more"], r["launches"])
+        ok = base["su"] == 1
+        r["agree"] = 0.0
+        for k in ("su", "nf", "rho", "ro", "vals"):      # the decisions and the rho slots: bit for bit
+            assert torch.equal(bits(r[k]), bits(base[k])), (r["more"], k)
+        for k in ("d", "d2"):
+            if r["P"] in (0, 2):                          # the forward substitution in panels: d bit for bit
+                assert torch.equal(bits(r[k]), bits(base[k])), (r["more"], k)
+                continue
+            assert bool((r[k][~ok] == 7.0).all())
+            if bool(ok.any()):
+                r["agree"] = max(r["agree"], float(((r[k][ok] - base[k][ok]).abs().amax(1) / base[k][ok].abs().amax(1)).max().item()))
+        assert r["agree"] <= FWD_TOL, (r["more"], r["agree"])
+    if kind == "healthy":
+        assert bool((runs[0]["su"] == 1).all()) and int(runs[0]["nf"].max().item()) == 1
+    for r in runs:
+        r["t"] = dict(newton=[], solve=[])
+    for it in range(WARMUP + ROUNDS):
+        for r in runs:
+            for call in ("newton", "solve"):
+                t = timed(r, call)
+                if it >= WARMUP:
+                    r["t"][call].append(t)
+    off = runs[0]
+    gi = off["L"].plan_array("ginfo").tolist()
+    F = [int(max(t[7] for t in off["L"].plan_array("gtasks").reshape(-1, 8) if t[0] == st)) for st in range(gi[2])]
+    out = dict(pattern=f"{gen}{tuple(args)}", B=B, N=s.N, values=kind, rungs=R, ginfo=gi, tpp=off["L"].config["tpp"], nfact=sorted(set(int(x) for x in off["nf"].cpu().numpy())),
+               F=F, stage_tasks=np.diff(off["L"].plan_array("gstage_ptr")).tolist(), launches=off["launches"],
+               sides=[dict(keys=r["more"], agree=r["agree"], **{k: [float(np.median(v)), min(v), max(v)] for k, v in r["t"].items()}) for r in runs])
+    for r in runs:
+        r["L"].close()
+    return out
+
+
+def solve_panels(argv):
+    global F32
+    torch, hipldl, syn = setup()
+    only = [int(x) for x in argv[argv.index("--only") + 1].split(",")] if "--only" in argv else list(range(len(WIDE_CASES)))
+    lines = [f"subtree_solve_panels = P on subtree handles, blocked key on on every side: whole-call device time in ms, median [min .. max] of {ROUNDS} alternated rounds after "
+             f"{WARMUP} warm-up rounds, one process; every side agrees with the P = 0 side of the same launch shapes bit for bit in success, nfact, rho, rho_old and vals, P = 2 also in d of "
+             f"both calls, P = 1 and 3 in d within the forward bar (the largest relative difference is printed)",
+             "against P = 0 of the same launch shapes: off / side, FASTER or SLOWER only beyond the larger of the two spreads; ** ** marks what is slower",
+             "[case] pattern x batch, element type, values, F_s per stage, tasks per stage | side | newton_system | against P = 0 | solve | against P = 0 | d against P = 0"]
+    fmt = lambda t: f"{t[0]:9.3f} [{t[1]:9.3f} .. {t[2]:9.3f}]"
+
+    def mark(v):
+        return f"**{v.strip()}**" if v.endswith("SLOWER") else v.strip()
+    for k in only:
+        for f32 in (False, True):
+            F32 = f32
+            t0 = time.time()
+            o = solve_one(torch, hipldl, syn, WIDE_CASES[k])
+            head = (f"[{k}] {o['pattern']} x {o['B']}, {'Float32' if f32 else 'Float64'}, {o['values']}{', subtree_ladder = %d (nfact %s)' % (o['rungs'], o['nfact']) if o['rungs'] else ''}, "
+                    f"F_s {o['F']}, tasks {o['stage_tasks']}, {o['launches'][0]} launches per newton_system, {o['launches'][1]} per solve")
+            lines.append(head)
+            n0 = len(lines) - 1
+            for sd in o["sides"]:
+                P = sd["keys"].get("subtree_solve_panels", 0)
+                wide_side = "subtree_wide" in sd["keys"]
+                name = f"P = {P}" + (", W = 1, M = 4096" if wide_side else "")
+                base = next(q for q in o["sides"] if "subtree_solve_panels" not in q["keys"] and ("subtree_wide" in q["keys"]) == wide_side)
+                cmp_ = ["", ""] if not P else [mark(verdict(base[c], sd[c])) for c in ("newton", "solve")]
+                lines.append(f"    {name:26s} | {fmt(sd['newton'])} | {cmp_[0]:>18s} | {fmt(sd['solve'])} | {cmp_[1]:>18s} | {sd['agree']:.2e}")
+            print("\n".join(lines[n0:]) + f"\n    ({time.time() - t0:.1f} s)", flush=True)
+            print(json.dumps(o), file=sys.stderr, flush=True)
+            if "--out" in argv:      # (written case by case: what was measured is kept if a later case is not reached)
+                with open(argv[argv.index("--out") + 1], "w") as f:
+                    f.write("\n".join(lines) + "\n")
+    return 0
+
+
 def verdict(off, on):
     spread = max(off[2] - off[1], on[2] - on[1])
     diff = on[0] - off[0]
@@ -392,10 +520,10 @@ def trace():
 
 
 def trace_wide(argv):
-    W, M = (int(x) for x in argv[argv.index("--trace-wide") + 1].split(","))
+    W, M, P = (tuple(int(x) for x in argv[argv.index("--trace-wide") + 1].split(",")) + (0,))[:3]
     torch, hipldl, syn = setup()
     case = ("grid", (70,), 1, dict(general_blocked=1), "healthy")
-    s, runs = make_runs(torch, hipldl, syn, case, keys=[{k: v for k, v in (("subtree_wide", W), ("subtree_lds_panels", M)) if v}])
+    s, runs = make_runs(torch, hipldl, syn, case, keys=[{k: v for k, v in (("subtree_wide", W), ("subtree_lds_panels", M), ("subtree_solve_panels", P)) if v}])
     r = runs[0]
     assert r["L"].config["general_subtrees"] and r["L"].config["general_blocked"], r["L"].config
     p = hipldl.default_params()
@@ -404,8 +532,12 @@ def trace_wide(argv):
                                  r["nf"].data_ptr(), r["su"].data_ptr(), p, 0)
         torch.cuda.synchronize()
     assert int(r["su"].item()) == 1
+    if "--with-solve" in argv:      # (three solve_ldl! calls on that factor behind them: 2 S stage launches each)
+        for _ in range(3):
+            hipldl.solve_dev(r["L"], r["rhs"].data_ptr(), r["d"].data_ptr(), stream=0)
+            torch.cuda.synchronize()
     tpp, lds = hipldl.subtree_stage_shape(r["L"])
-    print("W", W, "M", M, "stage_ptr", r["L"].plan_array("gstage_ptr").tolist(), "tpp", tpp.tolist(), "lds_bytes", lds.tolist())
+    print("W", W, "M", M, "P", r["L"].config["subtree_solve_panels"], "stage_ptr", r["L"].plan_array("gstage_ptr").tolist(), "tpp", tpp.tolist(), "lds_bytes", lds.tolist())
     r["L"].close()
     return 0
 
@@ -418,6 +550,8 @@ def main(argv):
         return trace_wide(argv)
     if "--wide" in argv:
         return wide(argv)
+    if "--solve-panels" in argv:
+        return solve_panels(argv)
     if "--dtype" in argv:
         F32 = {"float32": True, "float64": False}[argv[argv.index("--dtype") + 1]]
     if "--ladder" in argv:
