@@ -163,10 +163,32 @@ __device__ __forceinline__ int frec_index(int lds_off, int recb0) {
   return (lds_off >> (sizeof(T) == 8 ? 3 : 2)) + recb0;
 }
 
+// CACHE POLICY of the mover-table instance (tuning band_cache_policy): a compile-time mask POL over the streams the
+// kernel touches ONCE per sweep, so that they leave the XCD's L2 to the lines it touches twice, an epoch apart (the two 64-byte halves
+// of a line of the problem-major rhs and d, the program blocks every workgroup reads).  Builtins only; POL = 0 is the plain code.
+constexpr int BAND_POL_VALS_NT = 1;     // typed BAND_MK_VALS loads are non-temporal
+constexpr int BAND_POL_FACTOR_NT = 2;   // typed BAND_MK_FACTOR loads (backward sweep) are non-temporal
+constexpr int BAND_POL_REC_NT = 4;      // record stores of the compute lanes are non-temporal
+constexpr int BAND_POL_REC_WT = 8;      // ... or written through and dropped from L2 (a relaxed agent-scope atomic store: sc1); not with 4
+constexpr int BAND_POL_D_NT = 16;       // d stores (backward mover, border and junction components) are non-temporal
+template <int POL, class T>
+__device__ __forceinline__ void rec_store(T* p, T v) {
+  static_assert((POL & BAND_POL_REC_NT) == 0 || (POL & BAND_POL_REC_WT) == 0, "a record store is non-temporal or written through, not both");
+  if constexpr ((POL & BAND_POL_REC_NT) != 0) __builtin_nontemporal_store(v, p);
+  else if constexpr ((POL & BAND_POL_REC_WT) != 0) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else *p = v;
+}
+template <int POL, class T>
+__device__ __forceinline__ void d_store(T* p, T v) {
+  if constexpr ((POL & BAND_POL_D_NT) != 0) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+
 // one forward step of phase PH = step number % 8: enter slot PH, pivot slot PH - 4; fl = flags word (wave-uniform), o = int
 // offset of the step block in the record buffer.  The operands were read (fload) while the previous step computed.  The step's
 // factor records go to recp (the lane's first record element, RNL = problems per workgroup) when recst, or to the out ring.
-template <int PH, int RNL, class T>
+// POL: the cache policy of the record stores (rec_store).
+template <int PH, int RNL, int POL, class T>
 __device__ __forceinline__ void fstep(Win<T>& W, const FOps<T>& OP, const Rec& st, const int fl, const char* recb, const int o, char* myb,
                                       const T* __restrict__ gvals, const T* __restrict__ grhs, cptr borders, long long pv, long long pr,
                                       bool has_rhs, T rho, bool ovr, T tol, int& npos, int& nzer, const int vstride, const int rstride,
@@ -239,8 +261,8 @@ __device__ __forceinline__ void fstep(Win<T>& W, const FOps<T>& OP, const Rec& s
       if (recst) {
         T* lo = recp + frec_index<T>(st.v[BS_LB], recb0) * RNL;
 #pragma unroll
-        for (int k = 0; k < BAND_NB; k++) lo[k * RNL] = l[k];
-        lo[BAND_NB * RNL] = z;
+        for (int k = 0; k < BAND_NB; k++) rec_store<POL>(lo + k * RNL, l[k]);
+        rec_store<POL>(lo + BAND_NB * RNL, z);
       }
     } else {
       T* lo = reinterpret_cast<T*>(myb + st.v[BS_LB]);
@@ -275,9 +297,9 @@ __device__ __forceinline__ void fstep(Win<T>& W, const FOps<T>& OP, const Rec& s
       if (recst) {
         T* lo = recp + frec_index<T>(st.v[BS_LX], recb0) * RNL;
 #pragma unroll
-        for (int k = 1; k < BAND_NB; k++) lo[(k - 1) * RNL] = l[k];
-        lo[4 * RNL] = l5;
-        lo[5 * RNL] = z;
+        for (int k = 1; k < BAND_NB; k++) rec_store<POL>(lo + (k - 1) * RNL, l[k]);
+        rec_store<POL>(lo + 4 * RNL, l5);
+        rec_store<POL>(lo + 5 * RNL, z);
       }
     } else {
       T* lo = reinterpret_cast<T*>(myb + st.v[BS_LX]);
@@ -316,7 +338,7 @@ __device__ __forceinline__ void bload(BOps<T>& P, const Rec& st, const RowRec& r
     P.rrr = LDSD(row0.v[BR_RR]);
   }
 }
-template <int PH, class T>
+template <int PH, int POL, class T>
 __device__ __forceinline__ void bstep(T (&xs)[NS + 1], const BOps<T>& OP, const Rec& st, const RowRec& row0, const int fl, const char* recb,
                                       const int o, char* myb, cptr borders, T* __restrict__ gd, long long pd, bool okme) {
   constexpr int ps = lslot(PH, 0);
@@ -338,7 +360,7 @@ __device__ __forceinline__ void bstep(T (&xs)[NS + 1], const BOps<T>& OP, const 
 #pragma unroll
     for (int k = 0; k < BAND_NB; k++) x = fma(-lb[k], xs[lslot(PH, k)], x);
     xs[NS] = x;
-    if (okme) gd[pd + borders[BAND_BW * __builtin_amdgcn_readfirstlane(st.v[BS_BORDER]) + BB_DOUT]] = -x;
+    if (okme) d_store<POL>(gd + (pd + borders[BAND_BW * __builtin_amdgcn_readfirstlane(st.v[BS_BORDER]) + BB_DOUT]), -x);
   }
   for (int i = 0; i < nrows; i++) {
     T J[BAND_NB], dr, rr;
@@ -383,10 +405,16 @@ constexpr int BAND_NPIECE_RESIDENT = BAND_NPIECE + 256;
 // resident instance decodes array, layout, base, stride and lane offset of every piece in every epoch (about 60 instructions in
 // front of four loads, on a kernel that instruction issue bounds: DESIGN section 4).  General sets decode as the resident instance does.
 constexpr int BAND_NPIECE_MOVER = BAND_NPIECE + 512;
+// NPCX = band_npcx_mover(POL): the mover-table instance under cache policy POL (BAND_POL_*, above fstep).  The mask rides on the
+// piece-count parameter for the reason the two forms do: POL = 0 is BAND_NPIECE_MOVER itself, and every instance keeps its name.
+constexpr int BAND_POL_SHIFT = 10;
+constexpr int band_npcx_mover(int pol) { return BAND_NPIECE_MOVER + (pol << BAND_POL_SHIFT); }
 #define EF(F) band_ef(F, NPC)
 template <class T, int NL, int NPCX>
 __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1)) band_newton_kernel(const BandDev P, const LaunchArgs Ain) {
-  constexpr bool MOV = NPCX == BAND_NPIECE_MOVER;
+  constexpr int POL = NPCX >> BAND_POL_SHIFT;
+  constexpr bool MOV = (NPCX & ((1 << BAND_POL_SHIFT) - 1)) == BAND_NPIECE_MOVER;
+  static_assert(POL == 0 || MOV, "a cache policy: the mover-table instance only");
   constexpr bool RES = NPCX == BAND_NPIECE_RESIDENT || MOV;
   constexpr int NPC = RES ? BAND_NPIECE : NPCX;
   static_assert(!RES || (direct_records(NL) && NPC == BAND_NPIECE && sizeof(T) == 8), "the resident form: Float64, 32 problems per workgroup, 15 pieces");
@@ -529,16 +557,22 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
     BAND_ISSUE1(K, 0) BAND_ISSUE1(K, 1) BAND_ISSUE1(K, 2) BAND_ISSUE1(K, 3)                                                   \
   }
   /* mover-table instance, typed set: the word is  byte offset | slot  (negative: unused) */
-#define BAND_ISSUET1(K, I, VO) if constexpr (I < NI) stg[K][I] = *reinterpret_cast<const T*>(pb + VO[I]);
-#define BAND_ISSUET(K, BASE, VO)                                                                                              \
+  // NT: the set's stream is read once per sweep and its loads are non-temporal under the instance's cache policy (a typed piece is
+  // whole lines; general sets — rhs halves of a line, packed pieces — stay plain under every policy)
+#define BAND_ISSUET1(K, I, VO, NT)                                                                                            \
+  if constexpr (I < NI) {                                                                                                     \
+    if constexpr ((POL & (NT)) != 0) stg[K][I] = __builtin_nontemporal_load(reinterpret_cast<const T*>(pb + VO[I]));          \
+    else stg[K][I] = *reinterpret_cast<const T*>(pb + VO[I]);                                                                 \
+  }
+#define BAND_ISSUET(K, BASE, VO, NT)                                                                                          \
   if (pcs[K] >= 0) {   /* (wave-uniform) */                                                                                   \
     const char* pb = reinterpret_cast<const char*>(BASE) + (unsigned)(pcs[K] & ~BAND_MOV_SLOT_MASK);                          \
-    BAND_ISSUET1(K, 0, VO) BAND_ISSUET1(K, 1, VO) BAND_ISSUET1(K, 2, VO) BAND_ISSUET1(K, 3, VO)                               \
+    BAND_ISSUET1(K, 0, VO, NT) BAND_ISSUET1(K, 1, VO, NT) BAND_ISSUET1(K, 2, VO, NT) BAND_ISSUET1(K, 3, VO, NT)               \
   }
   /* SW: the sweep (0 forward, 1 backward) — the kind of set K is band_mover_kind(SW, K); one code path per set */
 #define BAND_ISSUE(K, SW)                                                                                                     \
-  if constexpr (MOV && band_mover_kind(SW, K) == BAND_MK_VALS) { BAND_ISSUET(K, vbase, movv) }                                \
-  else if constexpr (MOV && band_mover_kind(SW, K) == BAND_MK_FACTOR) { BAND_ISSUET(K, lbase_g, movf) }                       \
+  if constexpr (MOV && band_mover_kind(SW, K) == BAND_MK_VALS) { BAND_ISSUET(K, vbase, movv, BAND_POL_VALS_NT) }              \
+  else if constexpr (MOV && band_mover_kind(SW, K) == BAND_MK_FACTOR) { BAND_ISSUET(K, lbase_g, movf, BAND_POL_FACTOR_NT) }   \
   else { BAND_ISSUE_GEN(K) }
   /* (at commit time pcs[] still holds the descriptors of the epoch being committed: the next epoch's are read behind the commit) */
 #define BAND_COMMIT(K, SW)                                                                                                    \
@@ -662,7 +696,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
         if (clane) {                                                                                                        \
           FOps<T> op_;                                                                                                      \
           fload(op_, stC, rwC, fl, myb);                                                                                    \
-          fstep<PHV, NL>(W, op_, stC, fl, recb, o, myb, gvals, grhs, borders, pv, pr, has_rhs, rho, ovr, tol, npos, nzer, vstride, rstride, \
+          fstep<PHV, NL, POL>(W, op_, stC, fl, recb, o, myb, gvals, grhs, borders, pv, pr, has_rhs, rho, ovr, tol, npos, nzer, vstride, rstride, \
                          recp, PHV < BAND_EPOCH / 2 ? recb1 : recb2, recst);                                              \
         }                                                                                                                   \
         o = onext; stC = stN; rwC = rwN;                                                                                    \
@@ -678,7 +712,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
         if (clane) {                                                                                                        \
           FOps<T> op_;                                                                                                      \
           fload(op_, SC, RC, fl, myb);                                                                                      \
-          fstep<PHV, NL>(W, op_, SC, fl, recb, o, myb, gvals, grhs, borders, pv, pr, has_rhs, rho, ovr, tol, npos, nzer, vstride, rstride, \
+          fstep<PHV, NL, POL>(W, op_, SC, fl, recb, o, myb, gvals, grhs, borders, pv, pr, has_rhs, rho, ovr, tol, npos, nzer, vstride, rstride, \
                          recp, PHV < BAND_EPOCH / 2 ? recb1 : recb2, recst);                                              \
         }                                                                                                                   \
         o = onext;                                                                                                          \
@@ -835,7 +869,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
 #pragma unroll
         for (int i = 0; i < 4; i++) {
           ex[i] = xj[i]; exR[i] = xj[i];
-          if (valid && success) gd[(long long)cprob * N + P.m0 + i] = -xj[i];
+          if (valid && success) d_store<POL>(gd + ((long long)cprob * N + P.m0 + i), -xj[i]);
         }
       }
       __syncthreads();
@@ -893,7 +927,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
         if (clane) {                                                                                                        \
           BOps<T> op_;                                                                                                      \
           bload(op_, stC, rwC, fl, myb);                                                                                    \
-          bstep<PHV>(xs, op_, stC, rwC, fl, recb, o, myb, borders, gd, pd, okme);                                           \
+          bstep<PHV, POL>(xs, op_, stC, rwC, fl, recb, o, myb, borders, gd, pd, okme);                                           \
         }                                                                                                                   \
         o = onext; stC = stN; rwC = rwN;                                                                                    \
       }
@@ -905,7 +939,7 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
         if (clane) {                                                                                                        \
           BOps<T> op_;                                                                                                      \
           bload(op_, SC, RC, fl, myb);                                                                                      \
-          bstep<PHV>(xs, op_, SC, RC, fl, recb, o, myb, borders, gd, pd, okme);                                             \
+          bstep<PHV, POL>(xs, op_, SC, RC, fl, recb, o, myb, borders, gd, pd, okme);                                             \
         }                                                                                                                   \
         o = onext;                                                                                                          \
       }
@@ -934,12 +968,12 @@ __global__ void __launch_bounds__(128, (NL <= 8 && NPCX == BAND_NPIECE ? 2 : 1))
           for (int i = 0; i < NI; i++) dr_[cpc][i] = *reinterpret_cast<const T*>(wblk + BAND_LDSB(i) + (DR_OFF + 8 * cpc) * ES);
 #pragma unroll
         for (int i = 0; i < NI; i++)
-          if (movst[i] && le < xc) *reinterpret_cast<T*>(dxo + ((movp[i] * (unsigned)N + (unsigned)le) << LS)) = dx_[i];
+          if (movst[i] && le < xc) d_store<POL>(reinterpret_cast<T*>(dxo + ((movp[i] * (unsigned)N + (unsigned)le) << LS)), dx_[i]);
 #pragma unroll
         for (int cpc = 0; cpc < BAND_DR_MAX / 8; cpc++)
 #pragma unroll
           for (int i = 0; i < NI; i++)
-            if (movst[i] && cpc * 8 + le < rc) *reinterpret_cast<T*>(dro + (((movp[i] * (unsigned)N + (unsigned)le) << LS) + 8 * ES * cpc)) = dr_[cpc][i];
+            if (movst[i] && cpc * 8 + le < rc) d_store<POL>(reinterpret_cast<T*>(dro + (((movp[i] * (unsigned)N + (unsigned)le) << LS) + 8 * ES * cpc)), dr_[cpc][i]);
       }
     }
   }
@@ -1013,11 +1047,11 @@ static hipError_t launch_band_t(const BandDev& P, int nl, const LaunchArgs& a, h
 // place in the code object)
 static hipError_t launch_band_resident(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece);
 
-static hipError_t launch_band_mover(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece);
+static hipError_t launch_band_mover(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece, int policy);
 
-hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece, bool resident, bool mover) {
-  if (mover && !resident) return hipErrorInvalidConfiguration;
-  return mover ? launch_band_mover(P, nl, a, stream, npiece) : resident ? launch_band_resident(P, nl, a, stream, npiece) : launch_band_t<double>(P, nl, a, stream, npiece);
+hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece, bool resident, bool mover, int policy) {
+  if ((mover && !resident) || (policy && !mover)) return hipErrorInvalidConfiguration;
+  return mover ? launch_band_mover(P, nl, a, stream, npiece, policy) : resident ? launch_band_resident(P, nl, a, stream, npiece) : launch_band_t<double>(P, nl, a, stream, npiece);
 }
 hipError_t launch_band_f32(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece) { return launch_band_t<float>(P, nl, a, stream, npiece); }
 
@@ -1032,10 +1066,26 @@ static hipError_t launch_band_resident(const BandDev& P, int nl, const LaunchArg
 }
 
 // the mover-table instance (named last, for the same reason)
-static hipError_t launch_band_mover(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece) {
+// ... and its instances under a cache policy (tuning band_cache_policy, BAND_POL_*), behind it.  BAND_POLICY_MASKS is the list of the
+// masks that are built; band_policy_built answers for plan creation.  Measured (tools/time_band_policy.py: masks
+// 1, 3, 7, 11, 23, 27 against 0 in one process): 7 — both typed load streams and the record stores non-temporal — is the fastest and
+// the library's default; d stores stay plain (non-temporal they cost 6 %: the halves of a line of d meet in L2).  To measure another
+// mask, name it here.
+#define BAND_POLICY_MASKS(X) X(7)
+bool band_policy_built(int policy) {
+#define X(M) if (policy == (M)) return true;
+  BAND_POLICY_MASKS(X)
+#undef X
+  return policy == 0;
+}
+static hipError_t launch_band_mover(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece, int policy) {
   if (nl != 32 || npiece != BAND_NPIECE || !(a.layout & 1)) return hipErrorInvalidConfiguration;
   const size_t ldsb = band_lds_bytes(P.nparts, nl, (int)sizeof(double), npiece);
   auto kern = band_newton_kernel<double, 32, BAND_NPIECE_MOVER>;
+#define X(M) if (policy == (M)) kern = band_newton_kernel<double, 32, band_npcx_mover(M)>;
+  BAND_POLICY_MASKS(X)
+#undef X
+  if (!band_policy_built(policy)) return hipErrorInvalidConfiguration;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr_cap((int)ldsb));
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((a.batch + nl - 1) / nl), dim3(64 * P.nparts), ldsb, stream, P, a);

@@ -352,6 +352,8 @@ int setup_band(cnl_handle* h, const cnl::BandPlan& Bp0, const char** unfit) {
   // ... and its mover table where it has one (band.h, BAND_MK_*; tuning band_mover_table = 0: none): the table's words take the place
   // of the piece descriptors in the uploaded epoch blocks, which is the whole difference for the device
   h->band_mover = h->band_resident && plan->opt.band_mover_table && Bp.mover_ok;
+  // ... under the cache policy of tuning band_cache_policy (band.hip, BAND_POL_*): that instance has them, every other ignores the key
+  h->band_policy = h->band_mover ? plan->opt.band_cache_policy : 0;
   for (int q = 0; q < Bp.nparts; q++) {
     if ((rc = upload(h, Bp.part[q].fops, &bd.fops[q]))) return rc;
     if ((rc = upload(h, Bp.part[q].bops, &bd.bops[q]))) return rc;
@@ -1200,7 +1202,7 @@ int cnl_get_config(const cnl_handle* h, int64_t cfg[8]) {
     cfg[5] |= (int64_t)(h->lad_mode & 3) << 43;          // the in-kernel ladder: 0 none (sequential launch behind the attempt), 1, 2 fused
   }
   if (h->tail) cfg[5] |= 32;                          // the remainder of the batch runs on a handle of its own (split_tail)
-  if (on_band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->band_resident << 24) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28) | ((int64_t)h->band_mover << 34);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts, layout, operand pieces per epoch, mover table (bit 34: bit 27 marks a Float32 handle)
+  if (on_band) cfg[5] |= 64 | ((int64_t)h->band_nl << 8) | ((int64_t)h->bd.nparts << 16) | ((int64_t)h->band_resident << 24) | ((int64_t)h->layout << 25) | ((int64_t)h->band_npiece << 28) | ((int64_t)h->band_mover << 34) | ((int64_t)(h->band_policy & 31) << 18);   // newton_system runs on the band kernels (csrc/band.h): problems per workgroup, parts (bits 16 / 17: one or two), layout, operand pieces per epoch, mover table (bit 34: bit 27 marks a Float32 handle), cache policy of the mover-table instance (bits 18 .. 22: tuning band_cache_policy, 0 on every other instance)
   if (h->djt.rv_ntiles > 0) cfg[5] |= 128;               // row f1 runs on column tiles (kernels.h: DevJt::rv_*)
   cfg[5] |= (int64_t)(h->plan->opt.cgls_wide & 3) << 45;    // row f4: tuning cgls_wide (1: the wide instance above 1024 constraints, 2: always)
   cfg[6] = h->wpb2;

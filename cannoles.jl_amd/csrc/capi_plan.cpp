@@ -69,6 +69,11 @@ int resolve_options(const cnl_options* in, cnl::Tuning& out) {
   if (!err.empty()) return fail(CNL_ERR_ARG, err);
   if (out.band_pieces != 0 && out.band_pieces != cnl::BAND_NPIECE && out.band_pieces != cnl::BAND_NPIECE_WIDE)
     return fail(CNL_ERR_ARG, "cnl_options.tuning: band_pieces must be 0 (automatic), 15 or 20");
+  if (out.band_cache_policy < 0 || out.band_cache_policy > 31 || ((out.band_cache_policy & 4) && (out.band_cache_policy & 8)))
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: band_cache_policy is a bit mask, 0 .. 31 (1 vals loads, 2 factor loads, 4 record stores non-temporal, 8 record stores written through, "
+                             "16 d stores non-temporal); bits 4 and 8 exclude each other");
+  if (!cnl::band_policy_built(out.band_cache_policy))
+    return fail(CNL_ERR_ARG, "cnl_options.tuning: band_cache_policy = " + std::to_string(out.band_cache_policy) + ": the band kernel has no instance under this mask");
   if (out.float32_refine < 0 || out.float32_refine > 4)
     return fail(CNL_ERR_ARG, "cnl_options.tuning: float32_refine is the number of refinement steps, 0 (none) .. 4");
   if (out.float32_refine && !out.float32_general)
@@ -495,7 +500,9 @@ const char* cnl_last_error(void) { return g_err.c_str(); }
 //        subtree_lds_panels (dependent pivot panels of blocked subtree handles in LDS), cnl_get_config bits 58 / 59, cnl_subtree_stage_shape
 // 0.5.10: tuning subtree_solve_panels (the solve sweeps of subtree handles in panels of 16 pivots, entries of their own), cnl_get_config
 //        bits 60 / 61, no new symbol
-int32_t cnl_version(void) { return 510; }
+// 0.5.11: tuning band_cache_policy (cache policy of the band kernel's mover-table instance), cnl_get_config bits 18 .. 22 (bits 16 / 17
+//        keep the parts of the chain), no new symbol
+int32_t cnl_version(void) { return 511; }
 
 void cnl_default_params(double p[9]) {
   const double eps = 2.220446049250313e-16;  // eps(Float64); src/CaNNOLeS.jl:48-62

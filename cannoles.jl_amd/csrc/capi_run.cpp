@@ -67,7 +67,7 @@ int run_band(cnl_handle* h, cnl::LaunchArgs& a, void* d_vals, const void* d_rhs,
   a.layout = h->layout;
   if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
   const hipError_t e = h->f32 ? cnl::launch_band_f32(h->bd, h->band_nl, a, stream, h->band_npiece)
-                              : cnl::launch_band(h->bd, h->band_nl, a, stream, h->band_npiece, h->band_resident, h->band_mover);
+                              : cnl::launch_band(h->bd, h->band_nl, a, stream, h->band_npiece, h->band_resident, h->band_mover, h->band_policy);
   g_launches[0]++;
   if (e != hipSuccess)
     return fail(CNL_ERR_HIP, std::string("band kernel launch (") + (h->f32 ? "Float32, " : "") + std::to_string(h->band_nl) +

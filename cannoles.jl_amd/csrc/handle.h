@@ -188,6 +188,7 @@ struct cnl_handle {
   int band_nl = 16;            // problems per workgroup
   int band_npiece = 15;        // operand pieces per epoch of the program in bd: 15, or 20 = the wide kernel instances
   bool band_mover = false;     // ... with the piece descriptors of its epoch blocks replaced by the mover table: the mover-table instance runs it
+  int band_policy = 0;         // ... under this cache policy mask (tuning band_cache_policy; 0 wherever another instance runs the handle)
   bool band_resident = false;  // bd holds the plan's resident program (cnl_plan::band_res): the resident kernel instance runs it
   bool jac_segments = false;   // the J_F and the J_c entries are one run of slots each: [jf_lo, jf_lo + jf_n), [jc_lo, jc_lo + jc_n)
   int64_t jf_lo = 0, jf_n = 0, jc_lo = 0, jc_n = 0;

@@ -195,7 +195,10 @@ struct BandDev {
 // npiece: operand pieces per epoch of the program P was uploaded from (BandPlan::npiece): 15, or 20 = the wide kernel instances
 // resident: P is the resident form of the 15-piece program (band.h) — nl = 32, `vals` interleaved (a.layout & 1)
 // mover: ... whose epoch blocks carry the mover table in place of the piece descriptors (band.h, BAND_MK_*)
-hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece = 15, bool resident = false, bool mover = false);
+// policy: the cache policy mask of the mover-table instance (tuning band_cache_policy; band.hip, BAND_POL_*): 0, or a mask
+// band_policy_built() names, and then with mover only
+hipError_t launch_band(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece = 15, bool resident = false, bool mover = false, int policy = 0);
+bool band_policy_built(int policy);   // is there a mover-table instance for this cache policy mask? (0: always)
 // the same on Float32 data: P is the 4-byte program (build_band_plan with esz = 4), P.lsize counts floats
 hipError_t launch_band_f32(const BandDev& P, int nl, const LaunchArgs& a, hipStream_t stream, int npiece = 15);
 bool band_wide_has(int esz, int nl);   // is there a wide (20-piece) instance for this element size and problems per workgroup?

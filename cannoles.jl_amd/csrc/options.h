@@ -60,6 +60,7 @@ namespace cnl {
   X(f1_tiles, 1)             /* row f1 streams column tiles through LDS where the pattern allows; 0: gather kernel          */ \
   X(batch_layout, 0)         /* CNL_LAYOUT_*: layout of `vals` at the device-pointer entry points (band handles)            */ \
   X(band_rhs_interleaved, 0) /* measurement: the band kernels also take `rhs` interleaved (batch_layout = 1 handles)        */ \
+  X(band_cache_policy, 7)    /* mover-table instance of the band kernel: cache policy mask over its once-touched streams (band.hip, BAND_POL_*) — 1 typed vals loads non-temporal, 2 typed factor loads non-temporal, 4 record stores non-temporal, 8 record stores written through (not with 4), 16 d stores non-temporal; only the masks that are built (band_policy_built: 0 and 7); every other instance ignores it; 7 measured 5.1 % faster than 0 at 16 384 problems */ \
   X(float32_general, 0)      /* cnl_create_f32: a pattern (or option set) the band kernels do not serve runs on the general kernel in float */ \
   X(float32_condense, 0)     /* ... on the condensed system (the -I block eliminated by the condensation passes in float); only with float32_general */ \
   X(float32_register_front, 0) /* ... with the register-front kernel in float between the condensation passes (implies float32_condense; fronts of order <= 64, else the float32_condense handle); only with float32_general */ \

@@ -187,7 +187,10 @@ def Options(**kw):
     solve (d agrees with P = 0 to rounding and is a fixed function of the front), bit 1 the forward stage launches of solve (every
     output bit-equal to P = 0).  A stage whose (round4(F_s) + 288) elements exceed the LDS of a workgroup keeps the unpanelled launch;
     factorising launches, rungs, decide / commit kernels and climbers are untouched; no plan, route, allocation or launch count
-    changes.  config["subtree_solve_panels"] is the mask where it acts and 0 everywhere else."""
+    changes.  config["subtree_solve_panels"] is the mask where it acts and 0 everywhere else.  band_cache_policy = M (0 or 7, default 7;
+    any other mask ValueError / CNL_ERR_ARG at plan creation): the cache policy of the band kernel's mover-table instance — 1 typed vals
+    loads, 2 typed factor loads, 4 record stores non-temporal; every output bit-equal to 0; config["band_cache_policy"] is the mask
+    where that instance runs and 0 everywhere else."""
     o = cnl_options()
     lib().cnl_options_init(C.byref(o))
     assert o.struct_size == C.sizeof(cnl_options), "cnl_options layout differs from the library's"
@@ -523,7 +526,7 @@ class HIPLDLStruct:
         self.config = {"tpp": int(cfg[0]), "ppb": int(cfg[1]), "lds_bytes": int(cfg[2]), "lds_work": int(cfg[3]), "grid": int(cfg[4]),
                        "kernel": {2: "v2", 3: "dense", 4: "v2-staged"}.get(int(cfg[5]) & 15, "v1"), "wpb": int(cfg[6]), "lds2_bytes": int(cfg[7]),
                        "lean": bool(int(cfg[5]) & 16), "tail": bool(int(cfg[5]) & 32), "band": bool(int(cfg[5]) & 64), "f1_tiles": bool(int(cfg[5]) & 128),
-                       "band_nl": (int(cfg[5]) >> 8) & 255, "band_parts": (int(cfg[5]) >> 16) & 255, "band_resident": bool((int(cfg[5]) >> 24) & 1),
+                       "band_nl": (int(cfg[5]) >> 8) & 255, "band_parts": (int(cfg[5]) >> 16) & 3, "band_cache_policy": (int(cfg[5]) >> 18) & 31,"band_resident": bool((int(cfg[5]) >> 24) & 1),
                        "band_mover_table": bool((int(cfg[5]) >> 34) & 1), "cond_resident": bool((int(cfg[5]) >> 35) & 1),
                        "batch_layout": (int(cfg[5]) >> 25) & 1, "rhs_interleaved": bool((int(cfg[5]) >> 26) & 1),
                        "float32": bool((int(cfg[5]) >> 27) & 1), "band_pieces": (int(cfg[5]) >> 28) & 63,

@@ -456,7 +456,8 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  * kernel (kernels2.hip) serves newton_system/factorize (4: with staged execution of the first attempt), 3 dense backend, else 1;
  * + 16 when newton_system / factorize run the LEAN instantiation (fast-class fronts with row-form products only), [6]=its wavefronts per workgroup,
  * [7]=its LDS bytes per workgroup; [5] + 32 when the remainder of the batch runs on a handle of its own (cnl_options.split_tail),
- * + 64 when cnl_newton_system runs on the band kernels (then bits 8-15 = problems per workgroup, bits 16-23 = parts of the chain,
+ * + 64 when cnl_newton_system runs on the band kernels (then bits 8-15 = problems per workgroup, bits 16-17 = parts of the chain (one or two),
+ *   bits 18-22 = the cache policy mask of the mover-table instance (tuning "band_cache_policy", below; 0 on every other instance),
  *   bit 24 = the RESIDENT form of the 15-piece program runs (aligned blocks of `vals` kept in LDS: Float64, batch_layout = 1, 32 problems
  *   per workgroup; tuning "band_resident=0" keeps the 15-piece program — bit-equal outputs either way),
  *   bits 25-26 = cnl_options.batch_layout / rhs interleaved, bits 28-33 = operand pieces per epoch of the band program: 15, or 20
@@ -467,6 +468,13 @@ int cnl_last_kernel_ms(cnl_handle* h, float* ms);
  *   stand-alone condensation pass in front of the launch), either element type,
  * bit 37 = ... and cnl_solve* runs on the register-front kernel too (every front of the fast class),
  * bit 47 = cnl_newton_system* / cnl_factorize* run a BLOCKED instance of the general kernel (tuning "general_blocked=1", below).
+ *
+ * Tuning "band_cache_policy" (7 default; 0 or 7, any other value CNL_ERR_ARG at plan creation): the cache policy of the band kernel's
+ * mover-table instance (bit 34), a bit mask over the streams it touches once per sweep — 1 typed `vals` loads non-temporal, 2 typed
+ * factor loads non-temporal, 4 factor-record stores non-temporal, 8 the same stores written through (never with 4), 16 `d` stores
+ * non-temporal.  Only the masks the library has an instance for are accepted: 0 (every access plain) and 7.  Every output is bit for
+ * bit that of 0; 7 measured 5 % faster at 16 384 problems (tools/time_band_policy.py).  A handle that runs another
+ * instance ignores the key and reports 0 in bits 18-22.
  *
  * Tuning "general_blocked" (0 default, 1; any other value CNL_ERR_ARG): on a Float64 handle whose newton_system / factorize launches
  * are the general kernel's (cfg[5] & 15 == 1) with 256 or 1024 threads per problem and one problem per workgroup, a front with 16
